@@ -16,6 +16,12 @@ ranks), inputs resident in HBM.  `roofline` describes the dominant kernel: algor
 launch / that kernel's average launch duration (HIP events on the launch stream) against 8 TB/s.
 `cpu_baseline` = the reference CPU path on the host cores (oracle/_ref binary when present, else the
 oracle port) on a bounded sample of the same workload.
+
+`--dump-outputs DIR` writes what the last timed step computed on rank 0 as DIR/<name>.npy (float32 for bytes,
+float64 for counts and bit positions): the histogram the model was built from, the table file, the payload's bit
+count, the payload, the chunk index (bit offset and context apart) and the decoded bytes.  An array of more than
+DUMP_SAMPLE[name] elements is dumped at that many fixed, seeded positions (first and last element included), so the
+files stay under 64 MB; with the same arguments the inputs and the positions are the same from run to run.
 """
 import argparse
 import ctypes
@@ -25,6 +31,7 @@ import subprocess
 import sys
 import tempfile
 import time
+import zlib
 
 import numpy as np
 import torch
@@ -140,6 +147,41 @@ def Codec(mhc, n, device, order=1):
     return sharded.HipBackend(mhc, n, device, order=order, chunk_symbols=CHUNK or 1024,
                               use_fine=not os.environ.get("MH_BENCH_NO_FINE"),
                               two_pass_encode=bool(os.environ.get("MH_BENCH_TWO_PASS_ENCODE")))
+
+
+# elements kept per dumped array; in MB at most: payload, decoded 16 each (float32), the chunk index 8 + 8 (index_bits and
+# index_context, float64, the same positions), counts 8 (float64), table 4 (float32)
+DUMP_SAMPLE = {"payload": 4 << 20, "decoded": 4 << 20, "index_bits": 1 << 20, "counts": 1 << 20, "table": 1 << 20}
+
+
+def dump_sample(name, t):
+    """All of `t` (a 1-D device tensor or numpy array) when it has at most DUMP_SAMPLE[name] elements, else its elements at
+    that many sorted positions drawn from a generator seeded by the name (first and last element always among them)."""
+    m, k = int(t.numel() if torch.is_tensor(t) else t.size), DUMP_SAMPLE[name]
+    if m <= k:
+        return t.cpu().numpy() if torch.is_tensor(t) else t
+    pos = np.sort(np.random.default_rng(zlib.crc32(name.encode())).integers(0, m, k, dtype=np.int64))
+    pos[0], pos[-1] = 0, m - 1
+    return t[torch.from_numpy(pos).to(t.device)].cpu().numpy() if torch.is_tensor(t) else t[pos]
+
+
+def dump_outputs(out_dir, mhc, codec, model, counts, order):
+    """What one step hands its caller (see the module docstring), as DIR/<name>.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    nbits = int(codec.nbits[0].item())
+    mask, shift = (mhc.INDEX_BIT_MASK, 56) if order == 1 else (mhc.INDEX2_BIT_MASK, 48)
+    index = dump_sample("index_bits", codec.index[:codec.nidx]).view(np.uint64)     # (index_context: the same positions)
+    arrays = {
+        "counts": dump_sample("counts", counts).astype(np.float64),
+        "table": dump_sample("table", np.frombuffer(model.table_bytes(), dtype=np.uint8)).astype(np.float32),
+        "nbits": np.array([nbits], dtype=np.float64),
+        "payload": dump_sample("payload", codec.payload[:(nbits + 7) // 8]).astype(np.float32),
+        "index_bits": (index & np.uint64(mask)).astype(np.float64),
+        "index_context": (index >> np.uint64(shift)).astype(np.float64),
+        "decoded": dump_sample("decoded", codec.decoded[:codec.n_now]).astype(np.float32),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def cpu_baseline(mhc, table_bytes, sample, gpu_payload_prefix_check):
@@ -303,7 +345,11 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo (collectives staged through host memory) is only for rehearsing the N>1 path on one GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0) to DIR/<name>.npy, at most 64 MB in all")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus))                   # parent of N ranks: never touches a GPU
@@ -414,6 +460,8 @@ def main():
     for marks in recorded:
         for i, k in enumerate(stage_ms):
             stage_ms[k] += marks[i].elapsed_time(marks[i + 1])
+    if args.dump_outputs and rank == 0:           # before the checks below reuse the decode and histogram buffers
+        dump_outputs(args.dump_outputs, mhc, codec, model, codec.merged if multi else codec.counts, args.order)
     def all_reduce(t, op=dist.ReduceOp.SUM):       # (after the timed region: timing and verdicts of the ranks)
         if t.is_cuda and dist.get_backend() != "nccl":
             c = t.cpu()

@@ -8,6 +8,9 @@ known-answer inputs) and the reference's outputs on them:
     X.ch / X.eh  Huffman stream / table     (markovhuffman X -o X.ch -h -d X.eh)
 plus golden.json with sizes and sha256 of everything.  Both decodes are run and compared with the
 input before anything is written (the round trip of test/main.py:17-50,77).
+
+differential.json: the reference on the seeded random inputs of tests/test_oracle_golden.py's differential
+test (input, stream and table pinned by size and sha256; the tables in full as differential/diff_s<seed>_o<order>.e).
 """
 import hashlib
 import json
@@ -16,6 +19,8 @@ import shutil
 import subprocess
 import sys
 import tempfile
+
+import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
@@ -39,6 +44,21 @@ def kat_inputs():
     out["one_Z"] = b"Z"
     out["nine_Z"] = b"Z" * 9
     return out
+
+
+def differential_input(seed):
+    """Seeded random inputs (same formulas as tests/test_oracle_golden.py); regenerable anywhere without the reference."""
+    rng = np.random.default_rng(seed)
+    n = int(rng.integers(1000, 200000))
+    kind = seed % 3
+    if kind == 0:
+        data = rng.integers(0, 256, n, dtype=np.uint8)
+    elif kind == 1:
+        data = np.minimum(rng.geometric(0.08, n) - 1, 255).astype(np.uint8)
+    else:
+        w = 1.0 / np.arange(1, 257) ** 1.1
+        data = rng.choice(256, size=n, p=w / w.sum()).astype(np.uint8)
+    return data.tobytes()
 
 
 def sha(b):
@@ -103,6 +123,35 @@ def main():
     with open(os.path.join(HERE, "golden.json"), "w") as f:
         json.dump(meta, f, indent=1, sort_keys=True)
     print("wrote", len(meta), "golden entries")
+    differential()
+
+
+def differential():
+    out_dir = os.path.join(HERE, "differential")
+    shutil.rmtree(out_dir, ignore_errors=True)
+    os.makedirs(out_dir)
+    meta = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        for seed in (1, 2, 3):
+            data = differential_input(seed)
+            src = os.path.join(tmp, "in.bin")
+            with open(src, "wb") as f:
+                f.write(data)
+            for order in (0, 1):
+                c, e, d = (os.path.join(tmp, "out" + x) for x in (".c", ".e", ".d"))
+                run([src] + (["-h"] if order == 0 else []) + ["-o", c, "-d", e])
+                run([c, "-o", d] + (["-xh"] if order == 0 else ["-x"]) + ["-e", e])
+                assert open(d, "rb").read() == data, (seed, order)
+                stream, table = open(c, "rb").read(), open(e, "rb").read()
+                name = "diff_s%d_o%d" % (seed, order)
+                meta[name] = {"seed": seed, "order": order, "size": len(data), "sha256": sha(data),
+                              "c": {"size": len(stream), "sha256": sha(stream)},
+                              "e": {"size": len(table), "sha256": sha(table)}}
+                with open(os.path.join(out_dir, name + ".e"), "wb") as f:
+                    f.write(table)
+    with open(os.path.join(HERE, "differential.json"), "w") as f:
+        json.dump(meta, f, indent=1, sort_keys=True)
+    print("wrote", len(meta), "differential entries")
 
 
 if __name__ == "__main__":

@@ -49,3 +49,44 @@ def test_lorem_block_is_seeded_ascii_text():
     g = bench.generate("text", 3000, 1, (8 << 20) - 1000, torch.device("cpu")).numpy().tobytes()
     base = bench.lorem_block(8 << 20, 1)
     assert g == base[-1000:] + base[:2000]
+
+
+def test_dump_sample_is_whole_or_a_fixed_seeded_sample():
+    small = np.arange(1000, dtype=np.uint8)
+    assert np.array_equal(bench.dump_sample("payload", small), small)
+    k = bench.DUMP_SAMPLE["counts"]
+    big = torch.arange(3 * k, dtype=torch.int64)
+    a, b = bench.dump_sample("counts", big), bench.dump_sample("counts", big.numpy())
+    assert a.size == k and np.array_equal(a, b)                              # the same positions for tensor and array
+    assert a[0] == 0 and a[-1] == 3 * k - 1 and np.all(np.diff(a) >= 0)
+    assert np.array_equal(a, bench.dump_sample("counts", big))               # and from run to run
+
+
+def test_dump_outputs_writes_float_arrays_under_64_mb(tmp_path):
+    """dump_outputs on CPU tensors shaped like the flagship step's (16 GiB, chunk 1024): every file float32/float64, the index
+    split exactly, 64 MB in all at most."""
+    class Mhc:
+        INDEX_BIT_MASK, INDEX2_BIT_MASK = 0x00FFFFFFFFFFFFFF, 0x0000FFFFFFFFFFFF
+
+    class Model:
+        def table_bytes(self):
+            return bytes(range(256)) * 40
+
+    class Codec:
+        nidx = 3 << 20
+        n_now = 5 << 20
+        nbits = torch.tensor([(4 << 20) * 8 + 5, 0])
+        index = torch.arange(nidx, dtype=torch.int64) * 8192 | (torch.arange(nidx, dtype=torch.int64) % 256) << 56
+        payload = torch.full((nbits[0] // 8 + 64,), 7, dtype=torch.uint8)
+        decoded = torch.arange(n_now, dtype=torch.int64).to(torch.uint8)
+
+    counts = torch.arange(65536, dtype=torch.int64)
+    bench.dump_outputs(str(tmp_path), Mhc, Codec, Model(), counts, 1)
+    files = {p.stem: np.load(p) for p in tmp_path.glob("*.npy")}
+    assert set(files) == {"counts", "table", "nbits", "payload", "index_bits", "index_context", "decoded"}
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert sum(p.stat().st_size for p in tmp_path.glob("*.npy")) <= 64 << 20
+    assert np.array_equal(files["counts"], counts.numpy()) and files["nbits"][0] == (4 << 20) * 8 + 5
+    assert files["payload"].size == bench.DUMP_SAMPLE["payload"] and np.all(files["payload"] == 7)
+    pos = files["index_bits"] / 8192
+    assert np.array_equal(pos, np.rint(pos)) and np.array_equal(files["index_context"], pos % 256)

@@ -3,17 +3,18 @@
 (1) golden vectors made with the compiled reference (tests/golden/make_golden.py): stream and table
     bytes for Markov (.cm/.e) and plain Huffman (.ch/.eh) on the reference's own test/input files and
     on formula-defined known-answer inputs, incl. the edge cases SURVEY.md §8(c) lists;
-(2) when oracle/_ref/markovhuffman exists (build container, or shipped to the GPU box), a live
-    differential test on seeded random inputs.
+(2) a differential test on seeded random inputs against the reference binary's outputs on them,
+    recorded by the same script (tests/golden/differential.json).
 These are CPU tests (-m "not gpu").
 """
+import hashlib
+import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import check_against_golden, golden, golden_names
+from conftest import GOLDEN_DIR, check_against_golden, golden, golden_names
 
 
 @pytest.mark.parametrize("name", golden_names())
@@ -101,16 +102,8 @@ def test_lut_shape(oracle):
     assert saw_internal  # kat4 has codes up to 15 bits
 
 
-def _ref_bin(oracle):
-    return oracle.REF_BIN if os.path.exists(oracle.REF_BIN) else None
-
-
-@pytest.mark.parametrize("seed", [1, 2, 3])
-@pytest.mark.parametrize("order", [0, 1])
-def test_live_differential_vs_reference_binary(oracle, tmp_path, seed, order):
-    ref = _ref_bin(oracle)
-    if ref is None:
-        pytest.skip("oracle/_ref/markovhuffman not built (needs /root/reference)")
+def differential_input(seed):
+    """Seeded random inputs (same formulas as tests/golden/make_golden.py)."""
     rng = np.random.default_rng(seed)
     n = int(rng.integers(1000, 200000))
     kind = seed % 3
@@ -121,19 +114,29 @@ def test_live_differential_vs_reference_binary(oracle, tmp_path, seed, order):
     else:
         w = 1.0 / np.arange(1, 257) ** 1.1
         data = rng.choice(256, size=n, p=w / w.sum()).astype(np.uint8)
-    data = data.tobytes()
-    src = tmp_path / "in.bin"
-    src.write_bytes(data)
-    args = [ref, str(src), "-o", str(tmp_path / "out.c"), "-d", str(tmp_path / "out.e")]
-    if order == 0:
-        args.insert(2, "-h")
-    subprocess.run(args, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    return data.tobytes()
+
+
+@pytest.mark.parametrize("seed", [1, 2, 3])
+@pytest.mark.parametrize("order", [0, 1])
+def test_live_differential_vs_reference_binary(oracle, seed, order):
+    """The reference binary's outputs on seeded random inputs, recorded by tests/golden/make_golden.py
+    (differential.json: stream and table by size and sha256, the table in full under differential/)."""
+    name = "diff_s%d_o%d" % (seed, order)
+    with open(os.path.join(GOLDEN_DIR, "differential.json")) as f:
+        ref = json.load(f)[name]
+    data = differential_input(seed)
+    assert len(data) == ref["size"] and hashlib.sha256(data).hexdigest() == ref["sha256"], "seeded input drifted"
+    with open(os.path.join(GOLDEN_DIR, "differential", name + ".e"), "rb") as f:
+        ref_table = f.read()
+    assert len(ref_table) == ref["e"]["size"] and hashlib.sha256(ref_table).hexdigest() == ref["e"]["sha256"]
     m = oracle.Model.from_data(data, order)
-    assert m.compress(data)[0] == (tmp_path / "out.c").read_bytes()
-    assert m.table_bytes() == (tmp_path / "out.e").read_bytes()
-    # and the oracle decodes the reference's stream with the reference's table
-    loaded = oracle.Model.from_table((tmp_path / "out.e").read_bytes())
-    assert loaded.decompress((tmp_path / "out.c").read_bytes()) == data
+    blob = m.compress(data)[0]
+    assert len(blob) == ref["c"]["size"] and hashlib.sha256(blob).hexdigest() == ref["c"]["sha256"]
+    assert m.table_bytes() == ref_table
+    # and the oracle decodes the reference's stream (= blob, by its hash) with the reference's table
+    loaded = oracle.Model.from_table(ref_table)
+    assert loaded.decompress(blob) == data
 
 
 def test_order2_generalisation_self_consistency_parity_unpinned(oracle):
