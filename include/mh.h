@@ -464,6 +464,84 @@ int mh_dev_decode_variant(const void *d_ws, void *stream);
  * MH_ERR_TIMEOUT, MH_ERR_CAPACITY). */
 int mh_dev_status(const void *d_ws, void *stream);
 
+/* ------------------------------------------------ batches of independent streams */
+/*
+ * BATCHES OF INDEPENDENT STREAMS — many small messages (log lines, records, packets) under ONE shared model, in a fixed
+ * number of launches instead of several launches and host waits per message: the reference's own remedy for the table
+ * overhead of small files (README.md:152-157; its CLI: `markovhuffman msg -e shared.e -o msg.cm`).  Order 0 and order 1
+ * models; an order-2 model is refused with MH_ERR_ARG.
+ *   - Stream i is bytes [in_off[i], in_off[i+1]) of one buffer; in_off has n_streams + 1 entries, in_off[0] == 0,
+ *     non-decreasing, in_off[n] == total.  Empty streams may appear anywhere, n_streams == 0 is valid.  The device calls
+ *     take n_streams and total as host values (grids are sized without a synchronisation) and check the offsets on the
+ *     device: MH_ERR_ARG through mh_dev_status(d_ws).  The host calls check them before touching a device.
+ *   - Every stream starts in context prev0 (MH_PREV0 for the reference, src/coding.cpp:67,118).  Its payload bits, nbits and
+ *     chunk index are what mh_encode produces for that message alone, so mh_stream_header + payload is the `.cm` file the
+ *     reference writes for it with the shared table — including the reference's NDEBUG behaviour for a pair without a code
+ *     (the symbol is skipped, the context still advances).
+ *   - Payloads are packed byte-aligned, back to back: out_off[n + 1] = exclusive scan of ceil(nbits_i / 8).
+ *   - Chunk index (optional, chunk_symbols under the chunk-index rules): stream i's entries start at
+ *     mh_batch_index_base(in_off[i], i, chunk) = in_off[i] / chunk + i, capacity mh_batch_index_capacity(total, n, chunk)
+ *     = total / chunk + n + 1 entries.  The slices never overlap: ceil(m / c) <= floor((a + m) / c) - floor(a / c) + 1.
+ *     Each slice equals mh_encode's index of that message (context in bits 56..63, bit offsets relative to the stream's own
+ *     payload); entries in the gaps between slices are left untouched.  (Exported functions rather than static inlines:
+ *     every name this header declares is a symbol of the library.)
+ */
+uint64_t mh_batch_index_base(uint64_t in_off, uint64_t stream, uint32_t chunk_symbols);
+uint64_t mh_batch_index_capacity(uint64_t total, uint64_t n_streams, uint32_t chunk_symbols);
+
+/* Training histogram of a shared model: the summed counts of all streams, each starting in context prev0 (the order-1
+ * histogram of the concatenation, then one fix-up per stream boundary: counts[last byte of the previous stream][first
+ * byte] moves to counts[prev0][first byte]).  d_ws: at least mh_dev_histogram_batch_workspace(total) bytes (>= 256,
+ * 16-byte aligned; its status word carries MH_ERR_ARG for bad offsets and the order-1 conservation check). */
+size_t mh_dev_histogram_batch_workspace(size_t total);
+int mh_dev_histogram_o1_batch(const uint8_t *d_data, const uint64_t *d_in_off, size_t n_streams, size_t total, uint8_t prev0,
+                              uint64_t *d_counts /* 65536 */, void *d_ws, size_t ws_bytes, void *stream);
+int mh_dev_histogram_o0_batch(const uint8_t *d_data, const uint64_t *d_in_off, size_t n_streams, size_t total,
+                              uint64_t *d_counts /* 256 */, void *d_ws, size_t ws_bytes, void *stream);
+
+/* Worst-case packed payload bytes of a batch: total * max_code_len bits, one partial byte per stream, + slack. */
+size_t mh_encode_batch_bound(const mh_model *m, size_t total, size_t n_streams);
+size_t mh_dev_encode_batch_workspace(size_t n_streams, size_t total);
+/* Writes d_out_off[n + 1], d_nbits[n], the packed payloads (d_payload 16-byte aligned) and, when d_index != NULL, the index
+ * slices.  Payloads that do not fit `cap`: MH_ERR_CAPACITY through mh_dev_status(d_ws), nothing written beyond cap (the
+ * offsets and lengths are still written).  The input may start anywhere (no alignment needed for d_data). */
+int mh_dev_encode_batch(const mh_model *m, const uint8_t *d_data, const uint64_t *d_in_off, size_t n_streams, size_t total,
+                        uint8_t prev0, uint8_t *d_payload, size_t cap, uint64_t *d_out_off, uint64_t *d_nbits,
+                        uint64_t *d_index, uint32_t chunk_symbols, void *d_ws, size_t ws_bytes, void *stream);
+
+/* Index-free batch decode walks each stream with one lane, from its first bit to its last: a stream longer than this is
+ * refused by the device call (its status is MH_ERR_ARG; the others still decode), because one lane would take the whole
+ * batch's time on it — 8 Mbit already take milliseconds at one lane's rate.  mh_decode_batch decodes such streams with
+ * mh_decode by itself, so the host call never refuses a valid batch. */
+#define MH_BATCH_WALK_MAX_BITS (1ull << 23)
+size_t mh_dev_decode_batch_workspace(size_t n_streams);
+/* Decodes stream i (payload bytes [d_pay_off[i], d_pay_off[i+1]), d_nbits[i] bits, pay_total = pay_off[n]) into d_out.
+ * d_payload and d_out 16-byte aligned; reads stay inside the aligned dwords that hold a stream's payload.
+ *   - with d_index (chunk_symbols, the layout above): d_sym_off[n + 1] is INPUT (the d_in_off of the encode), sym_total its
+ *     last entry as a host value (<= out_cap, else MH_ERR_CAPACITY).  One lane per (stream, chunk); every chunk must end
+ *     exactly at the next entry's offset (the last one at nbits_i), else that stream is MH_ERR_CORRUPT.
+ *   - without (streams the reference wrote): d_sym_off[n + 1] is OUTPUT; a count pass decodes every stream without writing
+ *     and checks that it ends exactly at nbits_i (src/coding.cpp:124,158), a scan gives the offsets, an emit pass writes the
+ *     bytes — nothing at or beyond out_cap (the stream that does not fit: MH_ERR_CAPACITY).
+ * d_stream_status[n] (may be NULL): MH_OK or the stream's error (MH_ERR_CORRUPT, MH_ERR_ARG: nbits_i beyond its payload
+ * bytes or over MH_BATCH_WALK_MAX_BITS, MH_ERR_CAPACITY).  mh_dev_status(d_ws): the first error found. */
+int mh_dev_decode_batch(const mh_model *m, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits,
+                        size_t n_streams, uint64_t pay_total, uint8_t prev0, uint8_t *d_out, uint64_t out_cap,
+                        uint64_t *d_sym_off, uint64_t sym_total, const uint64_t *d_index, uint32_t chunk_symbols,
+                        int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream);
+
+/* Host-buffer forms: the whole batch is uploaded and the device call runs once.  Device footprint of mh_encode_batch:
+ * total + min(cap, mh_encode_batch_bound) + 24 bytes per stream + the index + the workspace (about 8 bytes per KiB of
+ * input and per stream); of mh_decode_batch: the payloads + the output (index-free: at most nbits / shortest code per
+ * stream) + 28 bytes per stream + the index.  `cap` / `out_cap` are the caller's buffer sizes; `index` (when not NULL)
+ * has mh_batch_index_capacity entries, and entries between slices keep their values.  mh_decode_batch: sym_off is input
+ * with an index, output without; stream_status (may be NULL) as above; returns the first stream's error, if any. */
+int mh_encode_batch(const mh_model *m, const uint8_t *data, const uint64_t *in_off, size_t n_streams, uint8_t prev0,
+                    uint8_t *out_payload, size_t cap, uint64_t *out_off, uint64_t *nbits, uint64_t *index, uint32_t chunk_symbols);
+int mh_decode_batch(const mh_model *m, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits, size_t n_streams,
+                    uint8_t prev0, uint8_t *out, size_t out_cap, uint64_t *sym_off, const uint64_t *index, uint32_t chunk_symbols,
+                    int32_t *stream_status);
+
 #ifdef __cplusplus
 }
 #endif

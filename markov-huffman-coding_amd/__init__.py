@@ -40,7 +40,11 @@ EXPORTS = [
     "mh_dev_build_index_workspace", "mh_dev_build_index", "mh_dev_status",
     "mh_dev_model2_workspace", "mh_dev_model2_array", "mh_dev_model2_build_slice", "mh_dev_model2_finish",
     "mh_dev_encode_fine", "mh_dev_encode_ctx_fine", "mh_dev_decode_fine", "mh_dev_build_index_fine", "mh_dev_decode_stream_states", "mh_dev_decode_stream_emit", "mh_dev_index_path", "mh_dev_encode_path", "mh_dev_decode_path", "mh_dev_decode_variant",
+    "mh_batch_index_base", "mh_batch_index_capacity", "mh_dev_histogram_batch_workspace", "mh_dev_histogram_o1_batch", "mh_dev_histogram_o0_batch",
+    "mh_encode_batch_bound", "mh_dev_encode_batch_workspace", "mh_dev_encode_batch", "mh_dev_decode_batch_workspace", "mh_dev_decode_batch",
+    "mh_encode_batch", "mh_decode_batch",
 ]
+BATCH_WALK_MAX_BITS = 1 << 23              # include/mh.h MH_BATCH_WALK_MAX_BITS
 
 
 class MhError(RuntimeError):
@@ -135,6 +139,24 @@ def lib():
         l.mh_dev_decode_variant.argtypes = [vp, vp]
         l.mh_dev_encode_path.argtypes = [vp, vp]
         l.mh_dev_decode_path.argtypes = [vp, vp]
+        l.mh_batch_index_base.argtypes = [u64, u64, u32]
+        l.mh_batch_index_base.restype = u64
+        l.mh_batch_index_capacity.argtypes = [u64, u64, u32]
+        l.mh_batch_index_capacity.restype = u64
+        l.mh_dev_histogram_batch_workspace.argtypes = [sz]
+        l.mh_dev_histogram_batch_workspace.restype = sz
+        l.mh_dev_histogram_o1_batch.argtypes = [vp, vp, sz, sz, u8, vp, vp, sz, vp]
+        l.mh_dev_histogram_o0_batch.argtypes = [vp, vp, sz, sz, vp, vp, sz, vp]
+        l.mh_encode_batch_bound.argtypes = [vp, sz, sz]
+        l.mh_encode_batch_bound.restype = sz
+        l.mh_dev_encode_batch_workspace.argtypes = [sz, sz]
+        l.mh_dev_encode_batch_workspace.restype = sz
+        l.mh_dev_encode_batch.argtypes = [vp, vp, vp, sz, sz, u8, vp, sz, vp, vp, vp, u32, vp, sz, vp]
+        l.mh_dev_decode_batch_workspace.argtypes = [sz]
+        l.mh_dev_decode_batch_workspace.restype = sz
+        l.mh_dev_decode_batch.argtypes = [vp, vp, vp, vp, sz, u64, u8, vp, u64, vp, u64, vp, u32, vp, vp, sz, vp]
+        l.mh_encode_batch.argtypes = [vp, vp, vp, sz, u8, vp, sz, vp, vp, vp, u32]
+        l.mh_decode_batch.argtypes = [vp, vp, vp, vp, sz, u8, vp, sz, vp, vp, u32, vp]
         _lib = l
     return _lib
 
@@ -200,6 +222,35 @@ def histogram_o2(data):
     out = np.zeros(1 << 24, dtype=np.uint64)
     _check(lib().mh_histogram_o2(_ptr(a), a.size, out.ctypes.data), "mh_histogram_o2")
     return out
+
+
+def batch_offsets(messages):
+    """(concatenation as uint8, in_off[n + 1] as uint64) of a list of byte strings."""
+    msgs = [bytes(m) for m in messages]
+    off = np.zeros(len(msgs) + 1, dtype=np.uint64)
+    if msgs:
+        off[1:] = np.cumsum([len(m) for m in msgs], dtype=np.uint64)
+    return np.frombuffer(b"".join(msgs), dtype=np.uint8), off
+
+
+def histogram_o1_batch(messages, prev0=PREV0, order=1):
+    """Summed histogram of independent messages, each starting in context prev0 (mh_dev_histogram_o1_batch / _o0_batch):
+    the training counts of a shared model."""
+    data, off = batch_offsets(messages)
+    l = lib()
+    total, n = int(data.size), len(off) - 1
+    d_data = DeviceBuffer(max(total, 1), data if total else None)
+    d_off = DeviceBuffer(off.nbytes, off)
+    nc = 65536 if order else 256
+    d_counts = DeviceBuffer(nc * 8)
+    wsb = l.mh_dev_histogram_batch_workspace(total)
+    d_ws = DeviceBuffer(wsb)
+    if order:
+        _check(l.mh_dev_histogram_o1_batch(d_data.ptr, d_off.ptr, n, total, prev0, d_counts.ptr, d_ws.ptr, wsb, None), "mh_dev_histogram_o1_batch")
+    else:
+        _check(l.mh_dev_histogram_o0_batch(d_data.ptr, d_off.ptr, n, total, d_counts.ptr, d_ws.ptr, wsb, None), "mh_dev_histogram_o0_batch")
+    _check(l.mh_dev_status(d_ws.ptr, None), "mh_dev_histogram_batch")
+    return d_counts.download(np.uint64)
 
 
 class Model:
@@ -359,3 +410,89 @@ class Model:
             raise MhError(MH_ERR_CORRUPT, "decompress")
         _check(lib().mh_stream_parse_header(self._h, int(a[0]), a.size, C.byref(nbits)), "mh_stream_parse_header")
         return self.decode(a[1:], nbits.value, PREV0, index, chunk_symbols, n_symbols)
+
+    # ---- batches of independent streams (mh_encode_batch / mh_decode_batch) -------------------------------------------
+    def encode_batch(self, messages, prev0=PREV0, chunk_symbols=None):
+        """(packed payloads, out_off[n + 1], nbits[n], index or None, in_off[n + 1]) of one mh_encode_batch call."""
+        data, off = batch_offsets(messages)
+        l = lib()
+        n, total = len(off) - 1, int(data.size)
+        cap = l.mh_encode_batch_bound(self._h, total, n)
+        out = np.zeros(max(cap, 1), dtype=np.uint8)
+        out_off = np.zeros(n + 1, dtype=np.uint64)
+        nbits = np.zeros(max(n, 1), dtype=np.uint64)
+        idx = None
+        if chunk_symbols:
+            idx = np.zeros(max(l.mh_batch_index_capacity(total, n, chunk_symbols), 1), dtype=np.uint64)
+        _check(l.mh_encode_batch(self._h, _ptr(data), off.ctypes.data, n, prev0, out.ctypes.data, cap, out_off.ctypes.data,
+                                 nbits.ctypes.data, idx.ctypes.data if idx is not None else None, chunk_symbols or 0), "mh_encode_batch")
+        return out[:int(out_off[n])], out_off, nbits[:n], idx, off
+
+    def compress_batch(self, messages, chunk_symbols=None):
+        """[(header + payload, nbits, index slice or None)] per message: each blob is the `.cm` file of that message alone."""
+        messages = [bytes(m) for m in messages]
+        payload, out_off, nbits, idx, off = self.encode_batch(messages, PREV0, chunk_symbols)
+        l = lib()
+        res = []
+        for i, m in enumerate(messages):
+            nb = int(nbits[i])
+            blob = bytes([l.mh_stream_header(self._h, nb)]) + payload[int(out_off[i]):int(out_off[i + 1])].tobytes()
+            sl = None
+            if chunk_symbols:
+                b = l.mh_batch_index_base(int(off[i]), i, chunk_symbols)
+                sl = idx[b:b + (len(m) + chunk_symbols - 1) // chunk_symbols].copy()
+            res.append((blob, nb, sl))
+        return res
+
+    def decode_batch(self, payload, pay_off, nbits, prev0=PREV0, sym_off=None, index=None, chunk_symbols=0, out_cap=None, check=True):
+        """mh_decode_batch: (output bytes, sym_off[n + 1], per-stream status[n]).  With an index, sym_off is the encode's in_off.
+        check=False returns the per-stream statuses of a batch with failed streams instead of raising."""
+        l = lib()
+        payload = _u8(payload)
+        pay_off = np.ascontiguousarray(pay_off, dtype=np.uint64)
+        nbits = np.ascontiguousarray(nbits, dtype=np.uint64)
+        n = len(pay_off) - 1
+        if index is not None:
+            so = np.ascontiguousarray(sym_off, dtype=np.uint64).copy()
+            cap = int(so[n]) if out_cap is None else out_cap
+            index = np.ascontiguousarray(index, dtype=np.uint64)
+        else:
+            so = np.zeros(n + 1, dtype=np.uint64)
+            minl = max(self.min_code_len, 1)
+            cap = int(sum(int(b) // minl for b in nbits)) if out_cap is None else out_cap
+        out = np.zeros(max(cap, 1), dtype=np.uint8)
+        st = np.zeros(max(n, 1), dtype=np.int32)
+        rc = l.mh_decode_batch(self._h, _ptr(payload), pay_off.ctypes.data, nbits.ctypes.data if n else None, n, prev0, out.ctypes.data, cap,
+                               so.ctypes.data, index.ctypes.data if index is not None and index.size else (out.ctypes.data if index is not None else None),
+                               chunk_symbols, st.ctypes.data)
+        if rc != MH_OK and (check or rc == MH_ERR_ARG or not st[:n].any()):
+            raise MhError(rc, "mh_decode_batch")
+        return out[:int(so[n])].tobytes(), so, st[:n]
+
+    def decompress_batch(self, blobs, indices=None, chunk_symbols=0, lengths=None):
+        """Whole `.cm` files in, original messages out.  With indices (one slice per blob, from compress_batch) the original
+        lengths must be given too: the index does not record where a stream's last chunk ends."""
+        l = lib()
+        payloads, nbits = [], []
+        for b in blobs:
+            a = _u8(b)
+            if a.size < 1:
+                raise MhError(MH_ERR_CORRUPT, "decompress_batch")
+            nb = C.c_uint64(0)
+            _check(l.mh_stream_parse_header(self._h, int(a[0]), a.size, C.byref(nb)), "mh_stream_parse_header")
+            payloads.append(a[1:].tobytes())
+            nbits.append(nb.value)
+        payload, pay_off = batch_offsets(payloads)
+        sym_off, index = None, None
+        if indices is not None:
+            if lengths is None:
+                raise ValueError("decompress_batch with indices needs the original lengths")
+            sym_off = np.zeros(len(blobs) + 1, dtype=np.uint64)
+            sym_off[1:] = np.cumsum(np.asarray(lengths, dtype=np.uint64), dtype=np.uint64)
+            total, n = int(sym_off[-1]), len(blobs)
+            index = np.zeros(max(l.mh_batch_index_capacity(total, n, chunk_symbols), 1), dtype=np.uint64)
+            for i, sl in enumerate(indices):
+                b = l.mh_batch_index_base(int(sym_off[i]), i, chunk_symbols)
+                index[b:b + len(sl)] = sl
+        out, so, _ = self.decode_batch(payload, pay_off, np.array(nbits, dtype=np.uint64), PREV0, sym_off, index, chunk_symbols)
+        return [out[int(so[i]):int(so[i + 1])] for i in range(len(blobs))]

@@ -1,0 +1,264 @@
+// mh_api_batch.cpp — the batch calls of the C ABI (include/mh.h, "BATCHES OF INDEPENDENT STREAMS"): many small order-0/1
+// streams under one shared model in a few launches (kernels: mh_batch.hip), and their host-buffer forms.
+#include "mh_api_internal.hpp"
+#include "mh_batch.h"
+
+using namespace mhapi;
+
+namespace {
+
+bool offsets_ok(const uint64_t *off, size_t n) {
+    if (off[0] != 0) return false;
+    for (size_t i = 0; i < n; ++i)
+        if (off[i + 1] < off[i]) return false;
+    return true;
+}
+
+bool order01(const mh_model *m) { return m && (m->type == 0 || m->type == 1); }
+
+}  // namespace
+
+extern "C" {
+
+uint64_t mh_batch_index_base(uint64_t in_off, uint64_t stream, uint32_t chunk_symbols) {
+    return chunk_symbols ? in_off / chunk_symbols + stream : 0;
+}
+
+uint64_t mh_batch_index_capacity(uint64_t total, uint64_t n_streams, uint32_t chunk_symbols) {
+    return chunk_symbols ? total / chunk_symbols + n_streams + 1 : 0;
+}
+
+size_t mh_dev_histogram_batch_workspace(size_t total) {
+    const size_t h = mh_dev_histogram_workspace(total);
+    return h > 256 ? h : 256;
+}
+
+static int histogram_batch(const uint8_t *d_data, const uint64_t *d_in_off, size_t n_streams, size_t total, uint8_t prev0,
+                           uint64_t *d_counts, void *d_ws, size_t ws_bytes, void *stream, int order) {
+    if ((!d_data && total) || !d_in_off || !d_counts || !d_ws || !aligned16(d_data) || !aligned16(d_ws)) return MH_ERR_ARG;
+    if (ws_bytes < 256) return MH_ERR_CAPACITY;
+    if (!have_device()) return MH_ERR_NO_DEVICE;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    int rc;
+    if (order) {
+        rc = mh_dev_histogram_o1(d_data, total, prev0, d_counts, d_ws, ws_bytes, stream);   // clears the status word, checks the sum
+    } else {
+        HIP_TRY(hipMemsetAsync(d_ws, 0, 64, st));
+        rc = mh_dev_histogram_o0(d_data, total, d_counts, nullptr, 0, stream);
+    }
+    if (rc != MH_OK) return rc;
+    HIP_TRY(mhb::launch_hist_fixup(d_data, d_in_off, n_streams, total, prev0, reinterpret_cast<unsigned long long *>(d_counts), order,
+                                   static_cast<int *>(d_ws), st));
+    return MH_OK;
+}
+
+int mh_dev_histogram_o1_batch(const uint8_t *d_data, const uint64_t *d_in_off, size_t n_streams, size_t total, uint8_t prev0,
+                              uint64_t *d_counts, void *d_ws, size_t ws_bytes, void *stream) {
+    return histogram_batch(d_data, d_in_off, n_streams, total, prev0, d_counts, d_ws, ws_bytes, stream, 1);
+}
+
+int mh_dev_histogram_o0_batch(const uint8_t *d_data, const uint64_t *d_in_off, size_t n_streams, size_t total, uint64_t *d_counts,
+                              void *d_ws, size_t ws_bytes, void *stream) {
+    return histogram_batch(d_data, d_in_off, n_streams, total, MH_PREV0, d_counts, d_ws, ws_bytes, stream, 0);
+}
+
+size_t mh_encode_batch_bound(const mh_model *m, size_t total, size_t n_streams) {
+    size_t maxlen = m ? size_t(m->max_len) : 64;
+    if (maxlen < 1) maxlen = 1;
+    return (total * maxlen + 7) / 8 + n_streams + 16;            // + one partial byte per stream
+}
+
+size_t mh_dev_encode_batch_workspace(size_t n_streams, size_t total) { return mhb::enc_layout(n_streams, total).total; }
+
+int mh_dev_encode_batch(const mh_model *m, const uint8_t *d_data, const uint64_t *d_in_off, size_t n_streams, size_t total, uint8_t prev0,
+                        uint8_t *d_payload, size_t cap, uint64_t *d_out_off, uint64_t *d_nbits, uint64_t *d_index, uint32_t chunk_symbols,
+                        void *d_ws, size_t ws_bytes, void *stream) {
+    if (!order01(m) || (!d_data && total) || !d_in_off || !d_out_off || (!d_nbits && n_streams) || (!d_payload && cap) || !d_ws) return MH_ERR_ARG;
+    if (!aligned16(d_payload) || !aligned16(d_ws)) return MH_ERR_ARG;
+    const int shift = d_index ? chunk_shift_of(chunk_symbols) : 0;
+    if (shift < 0) return MH_ERR_ARG;
+    if (ws_bytes < mh_dev_encode_batch_workspace(n_streams, total)) return MH_ERR_CAPACITY;
+    if (m->max_len > mh::MAX_CODE_BITS) return MH_ERR_CODE_TOO_LONG;
+    if (!m->d_enc16 || !have_device()) return MH_ERR_NO_DEVICE;
+    mhb::EncBatchParams p{};
+    p.data = d_data; p.in_off = d_in_off; p.n = n_streams; p.total = total; p.prev0 = prev0;
+    p.chunk_shift = uint32_t(shift);
+    p.index = reinterpret_cast<unsigned long long *>(d_index);
+    p.out = d_payload; p.cap = cap;
+    p.out_off = reinterpret_cast<unsigned long long *>(d_out_off);
+    p.nbits = reinterpret_cast<unsigned long long *>(d_nbits);
+    p.enc16 = m->d_enc16; p.len_slot = m->d_len_slot; p.len8 = m->d_len8; p.code64 = m->d_code64; p.max_len = m->max_len;
+    HIP_TRY(mhb::launch_encode_batch(p, d_ws, static_cast<hipStream_t>(stream)));
+    return MH_OK;
+}
+
+size_t mh_dev_decode_batch_workspace(size_t n_streams) { return mhb::dec_layout(n_streams).total; }
+
+int mh_dev_decode_batch(const mh_model *m, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits, size_t n_streams,
+                        uint64_t pay_total, uint8_t prev0, uint8_t *d_out, uint64_t out_cap, uint64_t *d_sym_off, uint64_t sym_total,
+                        const uint64_t *d_index, uint32_t chunk_symbols, int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
+    if (!order01(m) || (!d_payload && pay_total) || !d_pay_off || (!d_nbits && n_streams) || !d_sym_off || (!d_out && out_cap) || !d_ws)
+        return MH_ERR_ARG;
+    if (!aligned16(d_payload) || !aligned16(d_out) || !aligned16(d_ws)) return MH_ERR_ARG;
+    const int shift = d_index ? chunk_shift_of(chunk_symbols) : 0;
+    if (shift < 0) return MH_ERR_ARG;
+    if (ws_bytes < mh_dev_decode_batch_workspace(n_streams)) return MH_ERR_CAPACITY;
+    if (d_index && sym_total > out_cap) return MH_ERR_CAPACITY;
+    if (m->max_len > mh::MAX_CODE_BITS) return MH_ERR_CODE_TOO_LONG;
+    if (!m->d_prim || !have_device()) return MH_ERR_NO_DEVICE;
+    const mhb::DecLayout L = mhb::dec_layout(n_streams);
+    mhb::DecBatchParams p{};
+    p.payload = d_payload; p.pay_off = d_pay_off; p.nbits = d_nbits; p.n = n_streams; p.pay_total = pay_total; p.prev0 = prev0;
+    p.out = d_out; p.out_cap = out_cap;
+    p.sym_off = reinterpret_cast<unsigned long long *>(d_sym_off); p.sym_total = sym_total;
+    p.index = d_index; p.chunk_shift = uint32_t(shift);
+    p.walk_max_bits = MH_BATCH_WALK_MAX_BITS;
+    p.stream_status = d_stream_status ? d_stream_status : reinterpret_cast<int *>(static_cast<unsigned char *>(d_ws) + L.off_status);
+    p.prim = m->d_prim; p.sec = m->d_sec; p.sec_base = m->d_sec_base; p.tree = m->d_tree;
+    p.P = uint32_t(m->dec_bits); p.nsec = m->nsec; p.sec_lds = m->dec_lds ? 1u : 0u;
+    p.direct = m->dec_direct ? 1u : 0u; p.H = uint32_t(m->dec_h);
+    HIP_TRY(mhb::launch_decode_batch(p, d_ws, static_cast<hipStream_t>(stream)));
+    return MH_OK;
+}
+
+/* ------------------------------------------------------- host-buffer calls */
+
+int mh_encode_batch(const mh_model *m, const uint8_t *data, const uint64_t *in_off, size_t n_streams, uint8_t prev0,
+                    uint8_t *out_payload, size_t cap, uint64_t *out_off, uint64_t *nbits, uint64_t *index, uint32_t chunk_symbols) {
+    if (!order01(m) || !in_off || !out_off || (!nbits && n_streams) || (!out_payload && cap)) return MH_ERR_ARG;
+    if (index && chunk_shift_of(chunk_symbols) < 0) return MH_ERR_ARG;
+    if (!offsets_ok(in_off, n_streams)) return MH_ERR_ARG;
+    const size_t total = size_t(in_off[n_streams]);
+    if (!data && total) return MH_ERR_ARG;
+    if (!have_device()) return MH_ERR_NO_DEVICE;
+    if (m->max_len > mh::MAX_CODE_BITS) return MH_ERR_CODE_TOO_LONG;
+    const hipStream_t st = nullptr;
+    const size_t bound = mh_encode_batch_bound(m, total, n_streams);
+    const size_t dcap = cap < bound ? cap : bound;
+    const size_t nidx = index ? size_t(mh_batch_index_capacity(total, n_streams, chunk_symbols)) : 0;
+    const size_t wsb = mh_dev_encode_batch_workspace(n_streams, total);
+    DevBuf d_data, d_in, d_out, d_oo, d_nb, d_idx, d_ws;
+    HIP_TRY(d_data.alloc(total));
+    HIP_TRY(d_in.alloc((n_streams + 1) * 8));
+    HIP_TRY(d_out.alloc(dcap));
+    HIP_TRY(d_oo.alloc((n_streams + 1) * 8));
+    HIP_TRY(d_nb.alloc(n_streams * 8));
+    HIP_TRY(d_idx.alloc(nidx * 8));
+    HIP_TRY(d_ws.alloc(wsb));
+    if (total) HIP_TRY(stage_h2d(d_data.p, data, total, st));
+    HIP_TRY(hipMemcpy(d_in.p, in_off, (n_streams + 1) * 8, hipMemcpyHostToDevice));
+    if (nidx) HIP_TRY(hipMemcpy(d_idx.p, index, nidx * 8, hipMemcpyHostToDevice));   // gap entries stay what the caller had
+    int rc = mh_dev_encode_batch(m, d_data.as<uint8_t>(), d_in.as<uint64_t>(), n_streams, total, prev0, d_out.as<uint8_t>(), dcap,
+                                 d_oo.as<uint64_t>(), d_nb.as<uint64_t>(), index ? d_idx.as<uint64_t>() : nullptr, chunk_symbols, d_ws.p, wsb, st);
+    if (rc == MH_OK) rc = mh_dev_status(d_ws.p, st);
+    if (rc != MH_OK) return rc;
+    HIP_TRY(hipMemcpy(out_off, d_oo.p, (n_streams + 1) * 8, hipMemcpyDeviceToHost));
+    if (n_streams) HIP_TRY(hipMemcpy(nbits, d_nb.p, n_streams * 8, hipMemcpyDeviceToHost));
+    if (out_off[n_streams]) HIP_TRY(stage_d2h(out_payload, d_out.p, size_t(out_off[n_streams]), st));
+    if (nidx) HIP_TRY(hipMemcpy(index, d_idx.p, nidx * 8, hipMemcpyDeviceToHost));
+    return MH_OK;
+}
+
+namespace {
+struct GrowOut { std::vector<uint8_t> v; };
+uint8_t *grow_out(void *ctx, size_t n) {
+    GrowOut *g = static_cast<GrowOut *>(ctx);
+    g->v.resize(n ? n : 1);
+    return g->v.data();
+}
+}  // namespace
+
+int mh_decode_batch(const mh_model *m, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits, size_t n_streams, uint8_t prev0,
+                    uint8_t *out, size_t out_cap, uint64_t *sym_off, const uint64_t *index, uint32_t chunk_symbols, int32_t *stream_status) {
+    if (!order01(m) || !pay_off || (!nbits && n_streams) || !sym_off || (!out && out_cap)) return MH_ERR_ARG;
+    if (index && chunk_shift_of(chunk_symbols) < 0) return MH_ERR_ARG;
+    if (!offsets_ok(pay_off, n_streams)) return MH_ERR_ARG;
+    const uint64_t pay_total = pay_off[n_streams];
+    if (!payload && pay_total) return MH_ERR_ARG;
+    for (size_t i = 0; i < n_streams; ++i)
+        if (nbits[i] > (pay_off[i + 1] - pay_off[i]) * 8) return MH_ERR_ARG;
+    uint64_t sym_total = 0;
+    if (index) {
+        if (!offsets_ok(sym_off, n_streams)) return MH_ERR_ARG;
+        sym_total = sym_off[n_streams];
+        if (sym_total > out_cap) return MH_ERR_CAPACITY;
+    }
+    if (!have_device()) return MH_ERR_NO_DEVICE;
+    if (m->max_len > mh::MAX_CODE_BITS) return MH_ERR_CODE_TOO_LONG;
+    const hipStream_t st = nullptr;
+    // index-free: the output is at most nbits / (shortest code) bytes per stream; streams over the walk cap go through mh_decode
+    std::vector<size_t> long_streams;
+    uint64_t dcap = sym_total;
+    if (!index) {
+        const uint64_t minl = uint64_t(m->min_len > 0 ? m->min_len : 1);
+        uint64_t bound = 0;
+        for (size_t i = 0; i < n_streams; ++i) {
+            if (nbits[i] > MH_BATCH_WALK_MAX_BITS) long_streams.push_back(i);
+            else bound += nbits[i] / minl;
+        }
+        dcap = std::min<uint64_t>(out_cap, bound);
+    }
+    const size_t nidx = index ? size_t(mh_batch_index_capacity(sym_total, n_streams, chunk_symbols)) : 0;
+    const size_t wsb = mh_dev_decode_batch_workspace(n_streams);
+    DevBuf d_pl, d_po, d_nb, d_out, d_so, d_idx, d_st, d_ws;
+    HIP_TRY(d_pl.alloc(size_t(pay_total) + 64));
+    HIP_TRY(d_po.alloc((n_streams + 1) * 8));
+    HIP_TRY(d_nb.alloc(n_streams * 8));
+    HIP_TRY(d_out.alloc(size_t(dcap)));
+    HIP_TRY(d_so.alloc((n_streams + 1) * 8));
+    HIP_TRY(d_idx.alloc(nidx * 8));
+    HIP_TRY(d_st.alloc(n_streams * 4));
+    HIP_TRY(d_ws.alloc(wsb));
+    if (pay_total) HIP_TRY(stage_h2d(d_pl.p, payload, size_t(pay_total), st));
+    HIP_TRY(hipMemcpy(d_po.p, pay_off, (n_streams + 1) * 8, hipMemcpyHostToDevice));
+    if (n_streams) HIP_TRY(hipMemcpy(d_nb.p, nbits, n_streams * 8, hipMemcpyHostToDevice));
+    if (index) {
+        HIP_TRY(hipMemcpy(d_so.p, sym_off, (n_streams + 1) * 8, hipMemcpyHostToDevice));
+        if (nidx) HIP_TRY(hipMemcpy(d_idx.p, index, nidx * 8, hipMemcpyHostToDevice));
+    }
+    int rc = mh_dev_decode_batch(m, d_pl.as<uint8_t>(), d_po.as<uint64_t>(), d_nb.as<uint64_t>(), n_streams, pay_total, prev0,
+                                 d_out.as<uint8_t>(), dcap, d_so.as<uint64_t>(), sym_total, index ? d_idx.as<uint64_t>() : nullptr,
+                                 chunk_symbols, d_st.as<int32_t>(), d_ws.p, wsb, st);
+    if (rc != MH_OK) return rc;
+    const int dev_rc = mh_dev_status(d_ws.p, st);
+    std::vector<int32_t> sst(n_streams);
+    if (n_streams) HIP_TRY(hipMemcpy(sst.data(), d_st.p, n_streams * 4, hipMemcpyDeviceToHost));
+    std::vector<uint64_t> dso(n_streams + 1);
+    HIP_TRY(hipMemcpy(dso.data(), d_so.p, (n_streams + 1) * 8, hipMemcpyDeviceToHost));
+    // the streams the device walk refused (over MH_BATCH_WALK_MAX_BITS) decode one by one; their bytes go in between
+    std::vector<GrowOut> extra(long_streams.size());
+    for (size_t k = 0; k < long_streams.size(); ++k) {
+        const size_t i = long_streams[k];
+        size_t nb = 0;
+        const int r = mh_decode_to(m, payload + pay_off[i], nbits[i], prev0, grow_out, &extra[k], &nb, nullptr, 0, 0);
+        extra[k].v.resize(nb);
+        sst[i] = r;
+    }
+    int first = MH_OK;
+    for (size_t i = 0; i < n_streams && first == MH_OK; ++i) first = sst[i];
+    if (first == MH_OK && dev_rc != MH_OK && dev_rc != MH_ERR_ARG) first = dev_rc;
+    if (stream_status) std::copy(sst.begin(), sst.end(), stream_status);
+    if (long_streams.empty()) {
+        std::copy(dso.begin(), dso.end(), sym_off);
+        if (dso[n_streams] && dso[n_streams] <= out_cap) HIP_TRY(stage_d2h(out, d_out.p, size_t(dso[n_streams]), st));   // (a failed stream's bytes are undefined, its neighbours' are not)
+        return first;
+    }
+    std::vector<uint8_t> dev_bytes(static_cast<size_t>(dso[n_streams]));
+    if (!dev_bytes.empty()) HIP_TRY(stage_d2h(dev_bytes.data(), d_out.p, dev_bytes.size(), st));
+    uint64_t pos = 0;
+    size_t k = 0;
+    for (size_t i = 0; i < n_streams; ++i) {
+        const bool is_long = k < long_streams.size() && long_streams[k] == i;
+        const uint8_t *src = is_long ? extra[k].v.data() : dev_bytes.data() + dso[i];
+        const uint64_t len = is_long ? extra[k].v.size() : dso[i + 1] - dso[i];
+        if (is_long) ++k;
+        sym_off[i] = pos;
+        if (pos + len > out_cap) { if (first == MH_OK) first = MH_ERR_CAPACITY; pos += len; continue; }
+        if (len) std::memcpy(out + pos, src, size_t(len));
+        pos += len;
+    }
+    sym_off[n_streams] = pos;
+    return first;
+}
+
+}  // extern "C"

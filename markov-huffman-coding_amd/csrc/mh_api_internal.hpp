@@ -120,6 +120,7 @@ inline int status_from_device(int s) {
         case mhk::MHK_STATUS_OK: return MH_OK;
         case mhk::MHK_STATUS_TIMEOUT: return MH_ERR_TIMEOUT;
         case mhk::MHK_STATUS_CAPACITY: return MH_ERR_CAPACITY;
+        case 4: return MH_ERR_ARG;               // mhb::BATCH_STATUS_ARG: the batch kernels found bad offsets or a stream they refuse
         default: return MH_ERR_CORRUPT;
     }
 }

@@ -1,0 +1,556 @@
+// mh_batch.hip — batches of independent order-0/1 streams under one shared model (include/mh.h, "BATCHES OF INDEPENDENT
+// STREAMS").  Every stream starts in context prev0, as every file of the reference does (src/coding.cpp:67,118).
+//   batch_check_kernel        offsets non-decreasing, [0] == 0, [n] == total (else MH_ERR_ARG through the status word)
+//   batch_hist_fixup_kernel   the order-1 histogram of the concatenation counted each stream's first pair in the context of
+//                             the previous stream's last byte: one thread per boundary moves it to prev0
+//   batch_enc_len_kernel      one wave per (stream, 1 KiB sub-step): the sub-step's payload bits
+//   batch_scan_*              exclusive scans (unit bits -> stream-relative bit offsets; payload bytes -> out_off)
+//   batch_enc_emit_kernel     one wave per (stream, 1 KiB sub-step): codes through the 12-bit LDS image, longer ones through
+//                             the full (len8, code64) tables; the sub-step's index entries
+//   batch_dec_idx_kernel      one lane per (stream, chunk) with an index
+//   batch_dec_walk_kernel     one lane per stream without an index: a count pass, then (after the scan) an emit pass
+// Hand-offs between workgroups go across launch boundaries only (mh_encode.hip records why the look-back scan lost).
+// The single-stream kernels and their headers are used read-only: nothing here changes how a single stream is coded.
+#include "mh_batch.h"
+#include "mh_decode_dev.hpp"
+#include "mh_dev.hpp"
+#include "../../include/mh.h"
+
+namespace mhb {
+
+using mhk::BitCursor;
+using mhk::BitSrc;
+using mhk::DecTables;
+
+namespace {
+
+constexpr uint32_t SUB_SHIFT = 10;                    // log2(B_SUB)
+static_assert((1u << SUB_SHIFT) == B_SUB && B_SUB == 64 * B_VEC, "a sub-step is one wave of 16-byte lanes");
+
+__device__ __forceinline__ void fail(int *status, int code) { atomicCAS(status, 0, code); }
+__device__ __forceinline__ bool stopped(const int *stop) { return *reinterpret_cast<const volatile int *>(stop) != 0; }
+
+// The stream that owns unit / chunk number u: the largest i <= n with (off[i] >> shift) + i <= u (the closed-form bases are
+// strictly increasing).  i == n: u lies behind the last stream.
+template <typename T>
+__device__ __forceinline__ uint64_t find_stream(const T *off, uint64_t n, uint32_t shift, uint64_t u) {
+    uint64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint64_t mid = (lo + hi + 1) >> 1;
+        if ((off[mid] >> shift) + mid <= u) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+// cnt (1..16) bytes at an arbitrary address, zero beyond cnt; only the dwords that hold bytes of the range are read (a stream
+// starts at any byte, so load_raw's 16-byte alignment does not hold here)
+__device__ __forceinline__ void load16(const uint8_t *p, uint32_t cnt, uint32_t (&x)[4]) {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(p);
+    const uint32_t *w = reinterpret_cast<const uint32_t *>(a & ~uintptr_t(3));
+    const uint32_t sh = uint32_t(a & 3u);
+    const uint32_t nw = (sh + cnt + 3u) >> 2;
+    uint32_t d[5];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) d[k] = uint32_t(k) < nw ? w[k] : 0u;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        uint32_t v = uint32_t(((uint64_t(d[q + 1]) << 32) | d[q]) >> (8u * sh));
+        const uint32_t lo = 4u * uint32_t(q);
+        if (cnt <= lo) v = 0;
+        else if (cnt < lo + 4u) v &= 0xFFFFFFFFu >> (8u * (lo + 4u - cnt));
+        x[q] = v;
+    }
+}
+__device__ __forceinline__ uint32_t byte_of(const uint32_t (&x)[4], uint32_t t) { return (x[t >> 2] >> (8u * (t & 3u))) & 255u; }
+
+// ------------------------------------------------------------------------------------------------ checks, histogram fix-up
+
+__global__ void batch_check_kernel(const uint64_t *off, uint64_t n, uint64_t total, int *status, int *stop, int *stream_status) {
+    const uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i > n) return;
+    bool bad = (i == 0 && off[0] != 0) || (i == n && off[n] != total) || (i < n && off[i + 1] < off[i]);
+    if (bad) { fail(status, BATCH_STATUS_ARG); atomicExch(stop, 1); }
+    if (stream_status && i < n) stream_status[i] = MH_OK;
+}
+
+__global__ void batch_hist_fixup_kernel(const uint8_t *data, const uint64_t *off, uint64_t n, uint64_t total, uint32_t prev0,
+                                        unsigned long long *counts, int order, int *status) {
+    const uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i > n) return;
+    const bool bad = (i == 0 && off[0] != 0) || (i == n && off[n] != total) || (i < n && off[i + 1] < off[i]);
+    if (bad) atomicExch(status, BATCH_STATUS_ARG);               // (the conservation check's CORRUPT gives way: the input was wrong)
+    if (order == 0 || i >= n || bad) return;
+    const uint64_t a = off[i], b = off[i + 1];
+    if (a == 0 || b <= a || b > total) return;
+    const uint32_t first = data[a], p = data[a - 1];
+    if (p == prev0) return;
+    atomicAdd(&counts[p * 256u + first], ~0ull);                  // -1
+    atomicAdd(&counts[prev0 * 256u + first], 1ull);
+}
+
+// ------------------------------------------------------------------------------------------------ scans (exclusive, u64)
+
+constexpr int SCAN_T = 256;                        // SCAN_BLOCK / 4 elements per thread
+
+template <int NT>
+__device__ __forceinline__ unsigned long long block_exclusive(unsigned long long v, unsigned long long *s, unsigned long long &tot) {
+    s[threadIdx.x] = v;
+    __syncthreads();
+    for (int d = 1; d < NT; d <<= 1) {
+        const unsigned long long x = int(threadIdx.x) >= d ? s[threadIdx.x - d] : 0ull;
+        __syncthreads();
+        s[threadIdx.x] += x;
+        __syncthreads();
+    }
+    tot = s[NT - 1];
+    const unsigned long long incl = s[threadIdx.x];
+    __syncthreads();
+    return incl - v;
+}
+
+__global__ __launch_bounds__(SCAN_T) void batch_scan_block_kernel(unsigned long long *a, uint64_t len, unsigned long long *sums, const int *stop) {
+    __shared__ unsigned long long s[SCAN_T];
+    if (stopped(stop)) return;
+    const uint64_t base = uint64_t(blockIdx.x) * SCAN_BLOCK + uint64_t(threadIdx.x) * 4u;
+    unsigned long long v[4], t = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { v[k] = base + k < len ? a[base + k] : 0ull; t += v[k]; }
+    unsigned long long tot;
+    unsigned long long run = block_exclusive<SCAN_T>(t, s, tot);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { if (base + k < len) a[base + k] = run; run += v[k]; }
+    if (threadIdx.x == 0) sums[blockIdx.x] = tot;
+}
+
+__global__ __launch_bounds__(1024) void batch_scan_sums_kernel(unsigned long long *sums, uint64_t nb, const int *stop) {
+    __shared__ unsigned long long s[1024];
+    if (stopped(stop)) return;
+    unsigned long long carry = 0;
+    for (uint64_t c = 0; c < nb; c += 1024) {
+        const uint64_t k = c + threadIdx.x;
+        const unsigned long long v = k < nb ? sums[k] : 0ull;
+        unsigned long long tot;
+        const unsigned long long ex = block_exclusive<1024>(v, s, tot);
+        if (k < nb) sums[k] = carry + ex;
+        carry += tot;
+    }
+}
+
+__global__ __launch_bounds__(SCAN_T) void batch_scan_add_kernel(unsigned long long *a, uint64_t len, const unsigned long long *sums, const int *stop) {
+    if (stopped(stop)) return;
+    const unsigned long long add = sums[blockIdx.x];
+    const uint64_t base = uint64_t(blockIdx.x) * SCAN_BLOCK;
+    for (uint32_t k = threadIdx.x; k < SCAN_BLOCK; k += SCAN_T)
+        if (base + k < len) a[base + k] += add;
+}
+
+hipError_t scan_exclusive(unsigned long long *a, uint64_t len, unsigned long long *sums, const int *stop, hipStream_t st) {
+    if (len == 0) return hipSuccess;
+    const uint64_t nb = scan_blocks(len);
+    hipLaunchKernelGGL(batch_scan_block_kernel, dim3(uint32_t(nb)), dim3(SCAN_T), 0, st, a, len, sums, stop);
+    hipLaunchKernelGGL(batch_scan_sums_kernel, dim3(1), dim3(1024), 0, st, sums, nb, stop);
+    hipLaunchKernelGGL(batch_scan_add_kernel, dim3(uint32_t(nb)), dim3(SCAN_T), 0, st, a, len, sums, stop);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------ encode
+
+// the unit's stream and the lane's bytes; false when the unit (wave-uniform) has nothing to code
+struct UnitLane {
+    uint64_t i, a, ni, ub, j0;
+    uint32_t cnt, prev;
+    uint32_t x[4];
+};
+__device__ __forceinline__ bool unit_lane(const EncBatchParams &p, uint64_t u, UnitLane &l) {
+    l.i = find_stream(p.in_off, p.n, SUB_SHIFT, u);
+    if (l.i >= p.n) return false;
+    l.a = p.in_off[l.i];
+    l.ni = p.in_off[l.i + 1] - l.a;
+    l.ub = (l.a >> SUB_SHIFT) + l.i;
+    const uint64_t s0 = (u - l.ub) << SUB_SHIFT;
+    if (s0 >= l.ni) return false;
+    l.j0 = s0 + uint64_t(mhk::lane_id()) * B_VEC;
+    l.cnt = l.j0 < l.ni ? uint32_t(l.ni - l.j0 < B_VEC ? l.ni - l.j0 : B_VEC) : 0u;
+    l.x[0] = l.x[1] = l.x[2] = l.x[3] = 0;
+    l.prev = p.prev0;
+    if (l.cnt) {
+        load16(p.data + l.a + l.j0, l.cnt, l.x);
+        if (l.j0) l.prev = p.data[l.a + l.j0 - 1];
+    }
+    return true;
+}
+
+__global__ __launch_bounds__(B_THREADS) void batch_enc_len_kernel(EncBatchParams p, uint64_t nunits, unsigned long long *ubits, const int *stop) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    if (stopped(stop)) return;
+    for (uint32_t k = threadIdx.x; k < 65536u / 16u; k += B_THREADS)
+        reinterpret_cast<uint4 *>(smem)[k] = reinterpret_cast<const uint4 *>(p.len_slot)[k];
+    __syncthreads();
+    const uint64_t nw = uint64_t(gridDim.x) * (B_THREADS / 64);
+    for (uint64_t u = uint64_t(blockIdx.x) * (B_THREADS / 64) + threadIdx.x / 64; u < nunits; u += nw) {
+        UnitLane l;
+        uint32_t bits = 0;
+        if (unit_lane(p, u, l)) {
+            uint32_t prev = l.prev;
+#pragma unroll
+            for (uint32_t t = 0; t < B_VEC; ++t) {                // (unrolled: the byte index stays a constant, no scratch)
+                const uint32_t sym = byte_of(l.x, t);
+                if (t < l.cnt) bits += smem[mh::enc_slot(sym << 8 | prev)];
+                prev = sym;
+            }
+        }
+        bits = mhk::wave_sum(bits);
+        if (mhk::lane_id() == 0) ubits[u] = bits;
+    }
+}
+
+// stream i: payload bits from the scanned unit bits, payload bytes into out_off (scanned next)
+__global__ void batch_enc_sizes_kernel(EncBatchParams p, const unsigned long long *ubase, const int *stop) {
+    if (stopped(stop)) return;
+    const uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i > p.n) return;
+    if (i == p.n) { p.out_off[i] = 0; return; }
+    const uint64_t u0 = (p.in_off[i] >> SUB_SHIFT) + i, u1 = (p.in_off[i + 1] >> SUB_SHIFT) + i + 1;
+    const unsigned long long bits = ubase[u1] - ubase[u0];
+    p.nbits[i] = bits;
+    p.out_off[i] = (bits + 7) >> 3;
+}
+
+// zeroes the payload bytes (codes are OR-ed into shared edge dwords) or reports that they do not fit
+__global__ void batch_enc_zero_kernel(EncBatchParams p, int *status, int *stop, uint32_t *tail) {
+    if (stopped(stop)) return;
+    const uint64_t bytes = p.out_off[p.n];
+    if (bytes > p.cap) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) { fail(status, mhk::MHK_STATUS_CAPACITY); atomicExch(stop, 1); }
+        return;
+    }
+    const uint64_t nfull = bytes >> 2;
+    uint32_t *o = reinterpret_cast<uint32_t *>(p.out);
+    for (uint64_t k = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; k < nfull; k += uint64_t(gridDim.x) * blockDim.x) o[k] = 0u;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *tail = 0u;
+}
+
+// Bits into 32-bit words, first stream bit in bit 31 of a word stored byte-swapped (MSB first inside a byte,
+// src/bitbuffer.cpp:12).  A word that lies wholly inside the lane's bits is stored; its edge words are shared with the
+// neighbour lane, sub-step or stream and are OR-ed into zeroed memory.  The last dword of the whole output, when it reaches
+// past the payload, is OR-ed into a workspace word instead and its bytes are copied out afterwards: nothing is touched at or
+// beyond out_off[n] <= cap.
+struct BitWriter {
+    uint32_t *out;
+    uint32_t *tail;
+    uint64_t tail_w;
+    uint64_t w;           // word the accumulator's first bit belongs to
+    uint64_t acc;         // nb pending bits, right-aligned
+    uint32_t nb;
+    bool lead;            // the current word holds bits in front of the lane's
+    __device__ __forceinline__ void init(uint32_t *o, uint32_t *t, uint64_t tw, uint64_t bit) {
+        out = o; tail = t; tail_w = tw; w = bit >> 5; nb = uint32_t(bit & 31u); acc = 0; lead = nb != 0;
+    }
+    __device__ __forceinline__ void put_word(uint32_t v, bool shared) {
+        const uint32_t m = __builtin_bswap32(v);
+        if (w == tail_w) atomicOr(tail, m);
+        else if (shared) atomicOr(out + w, m);
+        else out[w] = m;
+    }
+    __device__ __forceinline__ void push(uint64_t v, uint32_t l) {        // l <= 32
+        if (!l) return;
+        acc = (acc << l) | v;
+        nb += l;
+        if (nb >= 32u) {
+            nb -= 32u;
+            put_word(uint32_t(acc >> nb), lead);
+            lead = false;
+            acc &= (uint64_t(1) << nb) - 1u;
+            ++w;
+        }
+    }
+    __device__ __forceinline__ void code(uint64_t c, uint32_t l) {         // l <= 64
+        if (l > 32u) { push(c >> 32, l - 32u); push(c & 0xFFFFFFFFull, 32u); }
+        else push(c, l);
+    }
+    __device__ __forceinline__ void finish() {
+        if (nb) put_word(uint32_t(acc << (32u - nb)), true);
+    }
+};
+
+__device__ __forceinline__ void lookup(const uint16_t *lenc, const EncBatchParams &p, uint32_t prev, uint32_t sym, uint32_t &len, uint64_t &code) {
+    const uint32_t e = lenc[mh::enc_slot(sym << 8 | prev)];
+    if (e == mh::ENC16_ESCAPE) {                                   // longer than the 12-bit image: the full tables (L2)
+        len = p.len8[prev * 256u + sym];
+        code = p.code64[prev * 256u + sym];
+    } else {
+        len = e >> 12;                                              // 0: the pair has no code, skipped (mh_model.hpp:21)
+        code = e & 0xFFFu;
+    }
+}
+
+__global__ __launch_bounds__(B_THREADS) void batch_enc_emit_kernel(EncBatchParams p, uint64_t nunits, const unsigned long long *ubase,
+                                                                   uint32_t *tail, const int *stop) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    if (stopped(stop)) return;
+    const uint16_t *lenc = reinterpret_cast<const uint16_t *>(smem);
+    for (uint32_t k = threadIdx.x; k < 131072u / 16u; k += B_THREADS)
+        reinterpret_cast<uint4 *>(smem)[k] = reinterpret_cast<const uint4 *>(p.enc16)[k];
+    __syncthreads();
+    const uint64_t bytes = p.out_off[p.n];
+    const uint64_t tail_w = (bytes & 3u) ? bytes >> 2 : ~uint64_t(0);
+    const uint64_t nw = uint64_t(gridDim.x) * (B_THREADS / 64);
+    for (uint64_t u = uint64_t(blockIdx.x) * (B_THREADS / 64) + threadIdx.x / 64; u < nunits; u += nw) {
+        UnitLane l;
+        if (!unit_lane(p, u, l)) continue;                         // wave-uniform
+        uint32_t bits = 0, prev = l.prev;
+#pragma unroll
+        for (uint32_t t = 0; t < B_VEC; ++t) {
+            const uint32_t sym = byte_of(l.x, t);
+            uint32_t len = 0; uint64_t code;
+            if (t < l.cnt) lookup(lenc, p, prev, sym, len, code);
+            bits += len;
+            prev = sym;
+        }
+        const uint32_t excl = mhk::wave_inclusive_sum(bits) - bits;
+        const uint64_t sbit = (ubase[u] - ubase[l.ub]) + excl;     // stream-relative
+        if (p.index && l.cnt && (l.j0 & ((uint64_t(1) << p.chunk_shift) - 1u)) == 0)
+            p.index[(l.a >> p.chunk_shift) + l.i + (l.j0 >> p.chunk_shift)] = (uint64_t(l.prev) << 56) | sbit;
+        if (!bits) continue;
+        BitWriter bw;
+        bw.init(reinterpret_cast<uint32_t *>(p.out), tail, tail_w, uint64_t(p.out_off[l.i]) * 8u + sbit);
+        prev = l.prev;
+#pragma unroll
+        for (uint32_t t = 0; t < B_VEC; ++t) {
+            const uint32_t sym = byte_of(l.x, t);
+            uint32_t len = 0; uint64_t code = 0;
+            if (t < l.cnt) lookup(lenc, p, prev, sym, len, code);
+            bw.code(code, len);
+            prev = sym;
+        }
+        bw.finish();
+    }
+}
+
+__global__ void batch_enc_tail_kernel(EncBatchParams p, const uint32_t *tail, const int *stop) {
+    if (stopped(stop)) return;
+    const uint64_t bytes = p.out_off[p.n];
+    if (!(bytes & 3u)) return;
+    const uint8_t *t = reinterpret_cast<const uint8_t *>(tail);
+    for (uint64_t b = bytes & ~uint64_t(3); b < bytes; ++b) p.out[b] = t[b & 3u];
+}
+
+// ------------------------------------------------------------------------------------------------ decode
+
+// a stream's payload as a bit source: reads stay inside the dwords that hold its bytes
+__device__ __forceinline__ BitSrc stream_src(const uint8_t *payload, uint64_t po, uint64_t nbits, uint64_t &bit0) {
+    const uint64_t base = po & ~uint64_t(3);
+    BitSrc s;
+    s.p = payload + base;
+    s.bytes = po + ((nbits + 7) >> 3) - base;
+    s.full_words = s.bytes >> 2;
+    bit0 = (po - base) * 8u;
+    return s;
+}
+
+// output bytes of one lane: whole aligned dwords where the lane owns them, single bytes at its edges
+struct ByteOut {
+    uint8_t *o;
+    uint64_t beg, pos;
+    uint32_t q;
+    __device__ __forceinline__ void init(uint8_t *out, uint64_t at) { o = out; beg = pos = at; q = 0; }
+    __device__ __forceinline__ void put(uint32_t b) {
+        q |= b << (8u * uint32_t(pos & 3u));
+        if ((pos & 3u) == 3u) {
+            const uint64_t d = pos - 3u;
+            if (d >= beg) *reinterpret_cast<uint32_t *>(o + d) = q;
+            else for (uint64_t k = beg; k <= pos; ++k) o[k] = uint8_t(q >> (8u * uint32_t(k & 3u)));
+            q = 0;
+        }
+        ++pos;
+    }
+    __device__ __forceinline__ void flush() {
+        if (pos & 3u) {
+            const uint64_t d = pos & ~uint64_t(3);
+            for (uint64_t k = d > beg ? d : beg; k < pos; ++k) o[k] = uint8_t(q >> (8u * uint32_t(k & 3u)));
+        }
+    }
+};
+
+__device__ __forceinline__ void stream_fail(const DecBatchParams &p, int *status, uint64_t i, int mh_code, int dev_code) {
+    p.stream_status[i] = mh_code;
+    fail(status, dev_code);
+}
+
+// LDS: sec_base u32[256] | prim u16[256 << P] | sec u16[nsec] when the model's tables fit (the chunk decoder's layout)
+__device__ __forceinline__ DecTables load_tables(const DecBatchParams &p, unsigned char *smem, const uint16_t *&lut, const uint32_t *&sub_base) {
+    uint32_t *sb = reinterpret_cast<uint32_t *>(smem);
+    uint16_t *lp = reinterpret_cast<uint16_t *>(smem + 1024);
+    const uint32_t nprim16 = (256u << p.P) / 8u;
+    for (uint32_t i = threadIdx.x; i < nprim16; i += blockDim.x) reinterpret_cast<uint4 *>(lp)[i] = reinterpret_cast<const uint4 *>(p.prim)[i];
+    uint16_t *lsec = lp + (256u << p.P);
+    if (p.sec_lds) {
+        const uint32_t nsec16 = (p.nsec + 7u) / 8u;
+        for (uint32_t i = threadIdx.x; i < nsec16; i += blockDim.x) reinterpret_cast<uint4 *>(lsec)[i] = reinterpret_cast<const uint4 *>(p.sec)[i];
+    }
+    for (uint32_t i = threadIdx.x; i < 256u; i += blockDim.x) sb[i] = p.sec_base[i];
+    __syncthreads();
+    lut = lp;
+    sub_base = sb;
+    return DecTables{p.sec_lds ? lsec : p.sec, p.tree, p.P, p.direct, p.H,
+                     __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t *>(p.sec), 0, int((p.nsec + 8u) * 2u), 0x00020000)};
+}
+
+__global__ void batch_dec_check_kernel(DecBatchParams p, int *status, int *stop) {
+    const uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i > p.n) return;
+    bool bad = (i == 0 && p.pay_off[0] != 0) || (i == p.n && p.pay_off[p.n] != p.pay_total) || (i < p.n && p.pay_off[i + 1] < p.pay_off[i]);
+    if (p.index)
+        bad |= (i == 0 && p.sym_off[0] != 0) || (i == p.n && p.sym_off[p.n] != p.sym_total) || (i < p.n && p.sym_off[i + 1] < p.sym_off[i]);
+    if (bad) { fail(status, BATCH_STATUS_ARG); atomicExch(stop, 1); }
+    if (i == p.n) return;
+    p.stream_status[i] = MH_OK;
+    if (!bad && p.nbits[i] > (p.pay_off[i + 1] - p.pay_off[i]) * 8u) stream_fail(p, status, i, MH_ERR_ARG, BATCH_STATUS_ARG);
+}
+
+__global__ __launch_bounds__(B_THREADS) void batch_dec_idx_kernel(DecBatchParams p, uint64_t nwork, int *status, const int *stop) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    if (stopped(stop)) return;
+    const uint16_t *lut; const uint32_t *sub_base;
+    const DecTables tabs = load_tables(p, smem, lut, sub_base);
+    const uint32_t cs = p.chunk_shift;
+    for (uint64_t w = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; w < nwork; w += uint64_t(gridDim.x) * blockDim.x) {
+        const uint64_t i = find_stream(p.sym_off, p.n, cs, w);
+        if (i >= p.n) continue;
+        const uint64_t a = p.sym_off[i], ni = p.sym_off[i + 1] - a;
+        const uint64_t first = (w - ((a >> cs) + i)) << cs;
+        if (first >= ni || p.stream_status[i] == MH_ERR_ARG) continue;
+        const uint64_t nb = p.nbits[i];
+        const uint64_t e = p.index[w];
+        const uint64_t start = e & MH_INDEX_BIT_MASK;
+        const bool last = first + (uint64_t(1) << cs) >= ni;
+        const uint64_t end = last ? nb : (p.index[w + 1] & MH_INDEX_BIT_MASK);
+        const uint32_t nsym = uint32_t(last ? ni - first : (uint64_t(1) << cs));
+        if (start > end || end > nb) { stream_fail(p, status, i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT); continue; }
+        uint64_t bit0;
+        const BitSrc src = stream_src(p.payload, p.pay_off[i], nb, bit0);
+        BitCursor bc;
+        bc.init(src, bit0 + start);
+        uint32_t prev = uint32_t(e >> 56), used = 0;
+        bool bad = false;
+        ByteOut bo;
+        bo.init(p.out, a + first);
+        for (uint32_t t = 0; t < nsym && !bad; ++t) {
+            prev = mhk::decode_one(lut, sub_base, tabs, src, bc, prev, used, bad);
+            bo.put(prev);
+        }
+        bo.flush();
+        if (bad || used != end - start) stream_fail(p, status, i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT);
+    }
+}
+
+// EMIT = false: count the stream's symbols into sym_off[i] (scanned next); true: write them at out[sym_off[i] ...)
+template <bool EMIT>
+__global__ __launch_bounds__(B_THREADS) void batch_dec_walk_kernel(DecBatchParams p, int *status, const int *stop) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    if (stopped(stop)) return;
+    const uint16_t *lut; const uint32_t *sub_base;
+    const DecTables tabs = load_tables(p, smem, lut, sub_base);
+    for (uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; i <= p.n; i += uint64_t(gridDim.x) * blockDim.x) {
+        if (i == p.n) { if (!EMIT) p.sym_off[i] = 0; continue; }
+        if (!EMIT) p.sym_off[i] = 0;
+        if (p.stream_status[i] != MH_OK) continue;
+        const uint64_t nb = p.nbits[i];
+        if (!EMIT && nb > p.walk_max_bits) { stream_fail(p, status, i, MH_ERR_ARG, BATCH_STATUS_ARG); continue; }
+        uint64_t count = 0;
+        if (EMIT) {
+            const uint64_t a = p.sym_off[i];
+            count = p.sym_off[i + 1] - a;
+            if (a + count > p.out_cap) { stream_fail(p, status, i, MH_ERR_CAPACITY, mhk::MHK_STATUS_CAPACITY); continue; }
+        }
+        uint64_t bit0;
+        const BitSrc src = stream_src(p.payload, p.pay_off[i], nb, bit0);
+        BitCursor bc;
+        bc.init(src, bit0);
+        uint32_t prev = p.prev0, used = 0;
+        bool bad = false;
+        ByteOut bo;
+        bo.init(p.out, EMIT ? p.sym_off[i] : 0);
+        uint64_t k = 0;
+        // every code has at least one bit: at most nb steps (src/coding.cpp:124 — decode while bits remain)
+        while (used < nb && !bad && (!EMIT || k < count)) {
+            prev = mhk::decode_one(lut, sub_base, tabs, src, bc, prev, used, bad);
+            if (EMIT && !bad) bo.put(prev);
+            ++k;
+        }
+        if (EMIT) bo.flush();
+        if (bad || used != nb || (EMIT && k != count)) { stream_fail(p, status, i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT); continue; }
+        if (!EMIT) p.sym_off[i] = k;                               // src/coding.cpp:158: the stream ends exactly at nbits
+    }
+}
+
+inline int grid_for(uint64_t items, uint64_t per_block, int per_cu) {
+    const uint64_t want = (items + per_block - 1) / per_block;
+    const uint64_t cap = uint64_t(mhk::cu_count()) * uint64_t(per_cu);
+    return int(want < 1 ? 1 : (want > cap ? cap : want));
+}
+
+}  // namespace
+
+hipError_t launch_hist_fixup(const uint8_t *d_data, const uint64_t *d_in_off, uint64_t n, uint64_t total, uint32_t prev0,
+                             unsigned long long *d_counts, int order, int *d_status, hipStream_t st) {
+    const uint64_t threads = n + 1;
+    hipLaunchKernelGGL(batch_hist_fixup_kernel, dim3(uint32_t((threads + 255) / 256)), dim3(256), 0, st, d_data, d_in_off, n, total, prev0,
+                       d_counts, order, d_status);
+    return hipGetLastError();
+}
+
+hipError_t launch_encode_batch(const EncBatchParams &p, void *d_ws, hipStream_t st) {
+    hipError_t attr = mhk::allow_lds(reinterpret_cast<const void *>(batch_enc_len_kernel), 65536);    // (per call: per device)
+    if (attr == hipSuccess) attr = mhk::allow_lds(reinterpret_cast<const void *>(batch_enc_emit_kernel), 131072);
+    if (attr != hipSuccess) return attr;
+    unsigned char *ws = static_cast<unsigned char *>(d_ws);
+    const EncLayout L = enc_layout(p.n, p.total);
+    int *status = reinterpret_cast<int *>(ws), *stop = status + 1;
+    auto *ubits = reinterpret_cast<unsigned long long *>(ws + L.off_units);
+    auto *sums = reinterpret_cast<unsigned long long *>(ws + L.off_sums);
+    auto *tail = reinterpret_cast<uint32_t *>(ws + L.off_tail);
+    const uint64_t U = units_of(p.total, p.n);
+    hipError_t e = hipMemsetAsync(ws, 0, 64, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(batch_check_kernel, dim3(uint32_t((p.n + 1 + 255) / 256)), dim3(256), 0, st, p.in_off, p.n, p.total, status, stop,
+                       static_cast<int *>(nullptr));
+    const int waves_per_block = B_THREADS / 64;
+    hipLaunchKernelGGL(batch_enc_len_kernel, dim3(grid_for(U, waves_per_block, 2)), dim3(B_THREADS), 65536, st, p, U, ubits, stop);
+    if ((e = scan_exclusive(ubits, U, sums, stop, st)) != hipSuccess) return e;
+    hipLaunchKernelGGL(batch_enc_sizes_kernel, dim3(uint32_t((p.n + 1 + 255) / 256)), dim3(256), 0, st, p, ubits, stop);
+    if ((e = scan_exclusive(p.out_off, p.n + 1, sums, stop, st)) != hipSuccess) return e;
+    const uint64_t bound_words = (p.total * uint64_t(p.max_len > 0 ? p.max_len : 1) / 8 + p.n + 4) / 4;
+    hipLaunchKernelGGL(batch_enc_zero_kernel, dim3(grid_for(bound_words, 256, 8)), dim3(256), 0, st, p, status, stop, tail);
+    hipLaunchKernelGGL(batch_enc_emit_kernel, dim3(grid_for(U, waves_per_block, 1)), dim3(B_THREADS), 131072, st, p, U, ubits, tail, stop);
+    hipLaunchKernelGGL(batch_enc_tail_kernel, dim3(1), dim3(1), 0, st, p, tail, stop);
+    return hipGetLastError();
+}
+
+hipError_t launch_decode_batch(const DecBatchParams &p, void *d_ws, hipStream_t st) {
+    const int lds_max = 163840;
+    hipError_t attr = mhk::allow_lds(reinterpret_cast<const void *>(batch_dec_idx_kernel), lds_max);
+    if (attr == hipSuccess) attr = mhk::allow_lds(reinterpret_cast<const void *>(batch_dec_walk_kernel<false>), lds_max);
+    if (attr == hipSuccess) attr = mhk::allow_lds(reinterpret_cast<const void *>(batch_dec_walk_kernel<true>), lds_max);
+    if (attr != hipSuccess) return attr;
+    const size_t lds = 1024 + (size_t(256) << p.P) * 2 + (p.sec_lds ? ((size_t(p.nsec) * 2 + 15) & ~size_t(15)) : 0);
+    if (lds > 163840) return hipErrorInvalidValue;
+    unsigned char *ws = static_cast<unsigned char *>(d_ws);
+    const DecLayout L = dec_layout(p.n);
+    int *status = reinterpret_cast<int *>(ws), *stop = status + 1;
+    auto *sums = reinterpret_cast<unsigned long long *>(ws + L.off_sums);
+    hipError_t e = hipMemsetAsync(ws, 0, 64, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(batch_dec_check_kernel, dim3(uint32_t((p.n + 1 + 255) / 256)), dim3(256), 0, st, p, status, stop);
+    if (p.index) {
+        const uint64_t W = p.sym_total / (uint64_t(1) << p.chunk_shift) + p.n + 1;
+        hipLaunchKernelGGL(batch_dec_idx_kernel, dim3(grid_for(W, B_THREADS, 1)), dim3(B_THREADS), lds, st, p, W, status, stop);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL(batch_dec_walk_kernel<false>, dim3(grid_for(p.n + 1, B_THREADS, 1)), dim3(B_THREADS), lds, st, p, status, stop);
+    if ((e = scan_exclusive(p.sym_off, p.n + 1, sums, stop, st)) != hipSuccess) return e;
+    hipLaunchKernelGGL(batch_dec_walk_kernel<true>, dim3(grid_for(p.n + 1, B_THREADS, 1)), dim3(B_THREADS), lds, st, p, status, stop);
+    return hipGetLastError();
+}
+
+}  // namespace mhb
