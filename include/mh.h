@@ -542,6 +542,87 @@ int mh_decode_batch(const mh_model *m, const uint8_t *payload, const uint64_t *p
                     uint8_t prev0, uint8_t *out, size_t out_cap, uint64_t *sym_off, const uint64_t *index, uint32_t chunk_symbols,
                     int32_t *stream_status);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * BATCHES OF STREAMS, ONE MODEL EACH — the reference's default per-file flow (`markovhuffman f -o f.cm -d f.e`: train a
+ * model on the file, write its table next to its payload) for many messages at once.  Order 0 and order 1; order 2 is
+ * refused with MH_ERR_ARG.  Stream i, in_off, prev0, payload packing and the chunk-index slices are exactly as in the
+ * batch section above.  For every stream each output equals what the single-stream calls give for that message alone
+ * (mh_histogram_o1(m, prev0) or mh_histogram_o0, mh_model_from_counts, then mh_model_write_table and mh_encode): its
+ * table file (an empty order-1 stream: the 33-byte all-empty table; an empty order-0 stream: 0 bytes), its payload and
+ * nbits (mh_stream_header + payload is its `.cm` / `.ch`), its index slice.
+ *
+ * An mh_model_set holds one model per stream on the device: per stream a 256-entry context -> slot map, per live
+ * context (order 1: prev0 and the distinct bytes before the stream's last one) one slot of 3 840 bytes with the
+ * encoder's codes, the reference's 8-bit first decode level and a walk tree for longer codes.  A set takes about
+ * 1 KiB per stream plus 3.8 KiB per live context of device memory.  Codes are at most 64 bits: a tree deeper than that
+ * needs Fibonacci-weighted counts, which take more than 2^40 bytes of input; MH_ERR_CODE_TOO_LONG if it is ever met.
+ * A set is immutable after construction and may be shared by threads.
+ * --------------------------------------------------------------------------------------------------------------------- */
+typedef struct mh_model_set mh_model_set;
+
+/* Trains one model per stream on the device: live contexts, per-stream histograms, one tree per (stream, live context)
+ * with the reference's tie-breaking.  Allocates the set (and, for the duration of the call, 3.1 KiB of tree nodes per
+ * live context), and synchronises `stream` twice: once to size the set (its live-context count), once at the end for the
+ * status.  d_data needs no alignment; d_ws: at least
+ * mh_dev_model_set_train_workspace(n_streams) bytes, 16-byte aligned.  Bad offsets: MH_ERR_ARG. */
+size_t mh_dev_model_set_train_workspace(size_t n_streams);
+int mh_dev_model_set_train(const uint8_t *d_data, const uint64_t *d_in_off, size_t n_streams, size_t total, int order, uint8_t prev0,
+                           void *d_ws, size_t ws_bytes, void *stream, mh_model_set **out);
+/* A set from host models (order 0/1, mixed orders allowed): stream i is coded under models[i]. */
+int mh_model_set_from_models(const mh_model *const *models, size_t n_streams, mh_model_set **out);
+/* A set from table files: stream i's table is bytes [tab_off[i], tab_off[i+1]) of `tables` (a 0-byte table is the
+ * empty order-0 model of an empty stream).  A malformed table: MH_ERR_BADTABLE. */
+int mh_model_set_from_tables(const uint8_t *tables, const uint64_t *tab_off, size_t n_streams, mh_model_set **out);
+void mh_model_set_free(mh_model_set *s);
+size_t mh_model_set_size(const mh_model_set *s);          /* streams */
+size_t mh_model_set_slots(const mh_model_set *s);         /* live contexts over all streams */
+/* Stream i's model: its type (0 or 1) and longest code (0: no code).  Reads the device (synchronous). */
+int mh_model_set_stream_info(const mh_model_set *s, size_t i, int *type, int *max_code_len);
+/* Longest and shortest code of any stream of the set (0: no codes at all). */
+int mh_model_set_code_lens(const mh_model_set *s, int *max_code_len, int *min_code_len);
+
+/* Every stream's table file, packed back to back (no alignment between them): d_tab_off[n + 1] (written).  Table sizes are
+ * computed on the device; they never exceed mh_model_set_tables_bound(s) bytes in all.  Tables that do not fit cap:
+ * MH_ERR_CAPACITY through mh_dev_status(d_ws), nothing written at or beyond cap.  d_out and d_ws 16-byte aligned. */
+size_t mh_model_set_tables_bound(const mh_model_set *s);
+size_t mh_dev_model_set_tables_workspace(const mh_model_set *s);
+int mh_dev_model_set_tables(const mh_model_set *s, uint8_t *d_out, size_t cap, uint64_t *d_tab_off, void *d_ws, size_t ws_bytes, void *stream);
+
+/* mh_dev_encode_batch / mh_dev_decode_batch with stream i under the set's model i (n_streams == mh_model_set_size(s), else
+ * MH_ERR_ARG).  Same layouts, checks, per-stream statuses and MH_BATCH_WALK_MAX_BITS cap.  A symbol whose context or pair
+ * has no code in the stream's model is skipped, as mh_encode does. */
+size_t mh_encode_each_bound(const mh_model_set *s, size_t total, size_t n_streams);
+size_t mh_dev_encode_each_workspace(size_t n_streams, size_t total);
+int mh_dev_encode_each(const mh_model_set *s, const uint8_t *d_data, const uint64_t *d_in_off, size_t n_streams, size_t total,
+                       uint8_t prev0, uint8_t *d_payload, size_t cap, uint64_t *d_out_off, uint64_t *d_nbits,
+                       uint64_t *d_index, uint32_t chunk_symbols, void *d_ws, size_t ws_bytes, void *stream);
+size_t mh_dev_decode_each_workspace(size_t n_streams);
+int mh_dev_decode_each(const mh_model_set *s, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits,
+                       size_t n_streams, uint64_t pay_total, uint8_t prev0, uint8_t *d_out, uint64_t out_cap,
+                       uint64_t *d_sym_off, uint64_t sym_total, const uint64_t *d_index, uint32_t chunk_symbols,
+                       int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream);
+
+/* Host-buffer forms.  Offsets are checked before a device is touched.  The streams are coded in groups whose device
+ * footprint stays near MH_EACH_GROUP_BYTES (environment variable of the same name overrides it, in bytes): a set grows
+ * with the streams' live contexts, up to 256 x 3.8 KiB per stream.  A stream longer than MH_EACH_DIRECT_BYTES goes
+ * through the single-stream calls instead, where the per-call cost is already small against its work.
+ *   mh_compress_each: data + in_off -> tables (tab_off[n + 1]), payloads (out_off[n + 1], nbits[n]) and, when index is not
+ *     NULL, the index slices (mh_batch_index_capacity entries; gap entries keep their values).  The outputs never exceed
+ *     the sizes mh_compress_each_bounds gives: tables 33 n + ceil(20 total / 8) + 16 bytes, payloads the sum over streams
+ *     of ceil(len_i x max(1, min(64, len_i - 1)) / 8), + n + 16.  Smaller caps: MH_ERR_CAPACITY.
+ *   mh_decompress_each: tables + payloads + nbits -> messages (sym_off as in mh_decode_batch: input with an index, output
+ *     without) and per-stream statuses (may be NULL).  Streams over MH_BATCH_WALK_MAX_BITS without an index are decoded
+ *     by mh_decode.  Returns the first stream's error, if any. */
+#define MH_EACH_GROUP_BYTES (1ull << 30)
+#define MH_EACH_DIRECT_BYTES (1ull << 24)
+int mh_compress_each_bounds(const uint64_t *in_off, size_t n_streams, size_t *tables_bound, size_t *payload_bound);
+int mh_compress_each(const uint8_t *data, const uint64_t *in_off, size_t n_streams, int order, uint8_t prev0,
+                     uint8_t *tables, size_t tab_cap, uint64_t *tab_off, uint8_t *out_payload, size_t cap, uint64_t *out_off,
+                     uint64_t *nbits, uint64_t *index, uint32_t chunk_symbols);
+int mh_decompress_each(const uint8_t *tables, const uint64_t *tab_off, const uint8_t *payload, const uint64_t *pay_off,
+                       const uint64_t *nbits, size_t n_streams, uint8_t prev0, uint8_t *out, size_t out_cap, uint64_t *sym_off,
+                       const uint64_t *index, uint32_t chunk_symbols, int32_t *stream_status);
+
 #ifdef __cplusplus
 }
 #endif

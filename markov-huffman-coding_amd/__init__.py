@@ -43,6 +43,10 @@ EXPORTS = [
     "mh_batch_index_base", "mh_batch_index_capacity", "mh_dev_histogram_batch_workspace", "mh_dev_histogram_o1_batch", "mh_dev_histogram_o0_batch",
     "mh_encode_batch_bound", "mh_dev_encode_batch_workspace", "mh_dev_encode_batch", "mh_dev_decode_batch_workspace", "mh_dev_decode_batch",
     "mh_encode_batch", "mh_decode_batch",
+    "mh_dev_model_set_train_workspace", "mh_dev_model_set_train", "mh_model_set_from_models", "mh_model_set_from_tables", "mh_model_set_free",
+    "mh_model_set_size", "mh_model_set_slots", "mh_model_set_stream_info", "mh_model_set_code_lens", "mh_model_set_tables_bound",
+    "mh_dev_model_set_tables_workspace", "mh_dev_model_set_tables", "mh_encode_each_bound", "mh_dev_encode_each_workspace", "mh_dev_encode_each",
+    "mh_dev_decode_each_workspace", "mh_dev_decode_each", "mh_compress_each_bounds", "mh_compress_each", "mh_decompress_each",
 ]
 BATCH_WALK_MAX_BITS = 1 << 23              # include/mh.h MH_BATCH_WALK_MAX_BITS
 
@@ -157,6 +161,35 @@ def lib():
         l.mh_dev_decode_batch.argtypes = [vp, vp, vp, vp, sz, u64, u8, vp, u64, vp, u64, vp, u32, vp, vp, sz, vp]
         l.mh_encode_batch.argtypes = [vp, vp, vp, sz, u8, vp, sz, vp, vp, vp, u32]
         l.mh_decode_batch.argtypes = [vp, vp, vp, vp, sz, u8, vp, sz, vp, vp, u32, vp]
+        l.mh_dev_model_set_train_workspace.argtypes = [sz]
+        l.mh_dev_model_set_train_workspace.restype = sz
+        l.mh_dev_model_set_train.argtypes = [vp, vp, sz, sz, i32, u8, vp, sz, vp, C.POINTER(vp)]
+        l.mh_model_set_from_models.argtypes = [C.POINTER(vp), sz, C.POINTER(vp)]
+        l.mh_model_set_from_tables.argtypes = [vp, vp, sz, C.POINTER(vp)]
+        l.mh_model_set_free.argtypes = [vp]
+        l.mh_model_set_free.restype = None
+        l.mh_model_set_size.argtypes = [vp]
+        l.mh_model_set_size.restype = sz
+        l.mh_model_set_slots.argtypes = [vp]
+        l.mh_model_set_slots.restype = sz
+        l.mh_model_set_stream_info.argtypes = [vp, sz, pi, pi]
+        l.mh_model_set_code_lens.argtypes = [vp, pi, pi]
+        l.mh_model_set_tables_bound.argtypes = [vp]
+        l.mh_model_set_tables_bound.restype = sz
+        l.mh_dev_model_set_tables_workspace.argtypes = [vp]
+        l.mh_dev_model_set_tables_workspace.restype = sz
+        l.mh_dev_model_set_tables.argtypes = [vp, vp, sz, vp, vp, sz, vp]
+        l.mh_encode_each_bound.argtypes = [vp, sz, sz]
+        l.mh_encode_each_bound.restype = sz
+        l.mh_dev_encode_each_workspace.argtypes = [sz, sz]
+        l.mh_dev_encode_each_workspace.restype = sz
+        l.mh_dev_encode_each.argtypes = [vp, vp, vp, sz, sz, u8, vp, sz, vp, vp, vp, u32, vp, sz, vp]
+        l.mh_dev_decode_each_workspace.argtypes = [sz]
+        l.mh_dev_decode_each_workspace.restype = sz
+        l.mh_dev_decode_each.argtypes = [vp, vp, vp, vp, sz, u64, u8, vp, u64, vp, u64, vp, u32, vp, vp, sz, vp]
+        l.mh_compress_each_bounds.argtypes = [vp, sz, psz, psz]
+        l.mh_compress_each.argtypes = [vp, vp, sz, i32, u8, vp, sz, vp, vp, sz, vp, vp, vp, u32]
+        l.mh_decompress_each.argtypes = [vp, vp, vp, vp, vp, sz, u8, vp, sz, vp, vp, u32, vp]
         _lib = l
     return _lib
 
@@ -496,3 +529,245 @@ class Model:
                 index[b:b + len(sl)] = sl
         out, so, _ = self.decode_batch(payload, pay_off, np.array(nbits, dtype=np.uint64), PREV0, sym_off, index, chunk_symbols)
         return [out[int(so[i]):int(so[i + 1])] for i in range(len(blobs))]
+
+
+# ---- batches of streams, one model each (include/mh.h, "BATCHES OF STREAMS, ONE MODEL EACH") ----------------------------
+def stream_header(order, nbits):
+    """The `.cm` / `.ch` header byte of a payload of nbits under an order-0/1 model (src/coding.cpp:88)."""
+    return 0x30 | ((~order & 1) << 3) | ((8 - nbits % 8) % 8)
+
+
+def table_order(table):
+    """Order of a table file: 1 for a Markov table (leading 1 bit), 0 for a Huffman tree (and the empty order-0 table)."""
+    return (table[0] >> 7) & 1 if len(table) else 0
+
+
+def parse_stream_header(order, blob):
+    """nbits of a whole `.cm` / `.ch` file written under a model of this order."""
+    a = _u8(blob)
+    if a.size < 1:
+        raise MhError(MH_ERR_CORRUPT, "parse_stream_header")
+    h = int(a[0])
+    if (h & 0xF0) != 0x30:
+        raise MhError(MH_ERR_CORRUPT, "parse_stream_header")
+    if ((h >> 3) & 1) != (~order & 1):
+        raise MhError(MH_ERR_TYPE, "parse_stream_header")
+    pad = h & 7
+    if (a.size - 1) * 8 < pad:
+        raise MhError(MH_ERR_CORRUPT, "parse_stream_header")
+    return (a.size - 1) * 8 - pad
+
+
+def _offsets(lengths):
+    off = np.zeros(len(lengths) + 1, dtype=np.uint64)
+    if len(lengths):
+        off[1:] = np.cumsum(np.asarray(lengths, dtype=np.uint64), dtype=np.uint64)
+    return off
+
+
+class ModelSet:
+    """Owns an mh_model_set*: one model per stream, resident on the current device."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    @classmethod
+    def train(cls, messages, order=1, prev0=PREV0):
+        """One model per message, trained on the device (mh_dev_model_set_train)."""
+        data, off = batch_offsets(messages)
+        l = lib()
+        total, n = int(data.size), len(off) - 1
+        d_data = DeviceBuffer(max(total, 1), data if total else None)
+        d_off = DeviceBuffer(off.nbytes, off)
+        wsb = l.mh_dev_model_set_train_workspace(n)
+        d_ws = DeviceBuffer(wsb)
+        h = C.c_void_p()
+        _check(l.mh_dev_model_set_train(d_data.ptr, d_off.ptr, n, total, order, prev0, d_ws.ptr, wsb, None, C.byref(h)), "mh_dev_model_set_train")
+        return cls(h)
+
+    @classmethod
+    def from_models(cls, models):
+        arr = (C.c_void_p * max(len(models), 1))(*[m.handle for m in models])
+        h = C.c_void_p()
+        _check(lib().mh_model_set_from_models(arr, len(models), C.byref(h)), "mh_model_set_from_models")
+        return cls(h)
+
+    @classmethod
+    def from_tables(cls, tables):
+        tables = [bytes(t) for t in tables]
+        buf = np.frombuffer(b"".join(tables), dtype=np.uint8)
+        off = _offsets([len(t) for t in tables])
+        h = C.c_void_p()
+        _check(lib().mh_model_set_from_tables(_ptr(buf), off.ctypes.data, len(tables), C.byref(h)), "mh_model_set_from_tables")
+        return cls(h)
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.mh_model_set_free(self._h)
+            self._h = None
+
+    @property
+    def handle(self):
+        return self._h
+
+    def __len__(self):
+        return lib().mh_model_set_size(self._h)
+
+    @property
+    def slots(self):
+        return lib().mh_model_set_slots(self._h)
+
+    def stream_info(self, i):
+        """(type, max code length) of stream i's model."""
+        t, m = C.c_int(), C.c_int()
+        _check(lib().mh_model_set_stream_info(self._h, i, C.byref(t), C.byref(m)), "mh_model_set_stream_info")
+        return t.value, m.value
+
+    def code_lens(self):
+        a, b = C.c_int(), C.c_int()
+        _check(lib().mh_model_set_code_lens(self._h, C.byref(a), C.byref(b)), "mh_model_set_code_lens")
+        return a.value, b.value
+
+    def table_bytes(self):
+        """Every stream's table file (mh_dev_model_set_tables)."""
+        l = lib()
+        n = len(self)
+        cap = l.mh_model_set_tables_bound(self._h)
+        wsb = l.mh_dev_model_set_tables_workspace(self._h)
+        d_out, d_off, d_ws = DeviceBuffer(max(cap, 1)), DeviceBuffer((n + 1) * 8), DeviceBuffer(wsb)
+        _check(l.mh_dev_model_set_tables(self._h, d_out.ptr, cap, d_off.ptr, d_ws.ptr, wsb, None), "mh_dev_model_set_tables")
+        _check(l.mh_dev_status(d_ws.ptr, None), "mh_dev_model_set_tables")
+        off = d_off.download(np.uint64)
+        out = d_out.download()
+        return [out[int(off[i]):int(off[i + 1])].tobytes() for i in range(n)]
+
+    def encode(self, messages, prev0=PREV0, chunk_symbols=None, cap=None, guard=0):
+        """mh_dev_encode_each: (packed payloads, out_off[n + 1], nbits[n], index or None, in_off[n + 1], status).  With cap,
+        the payload buffer has that size and `guard` bytes behind it, which must come back untouched."""
+        data, off = batch_offsets(messages)
+        l = lib()
+        n, total = len(off) - 1, int(data.size)
+        if cap is None:
+            cap = l.mh_encode_each_bound(self._h, total, n)
+        init = np.full(cap + guard, 0xA5, dtype=np.uint8) if guard else None
+        d_data = DeviceBuffer(max(total, 1), data if total else None)
+        d_in = DeviceBuffer(off.nbytes, off)
+        d_out = DeviceBuffer(max(cap + guard, 1), init)
+        d_oo, d_nb = DeviceBuffer((n + 1) * 8), DeviceBuffer(max(n, 1) * 8)
+        d_idx = None
+        if chunk_symbols:
+            d_idx = DeviceBuffer(max(l.mh_batch_index_capacity(total, n, chunk_symbols), 1) * 8)
+        wsb = l.mh_dev_encode_each_workspace(n, total)
+        d_ws = DeviceBuffer(wsb)
+        _check(l.mh_dev_encode_each(self._h, d_data.ptr, d_in.ptr, n, total, prev0, d_out.ptr, cap, d_oo.ptr, d_nb.ptr,
+                                    d_idx.ptr if d_idx else None, chunk_symbols or 0, d_ws.ptr, wsb, None), "mh_dev_encode_each")
+        rc = l.mh_dev_status(d_ws.ptr, None)
+        out = d_out.download()
+        if guard:
+            assert (out[cap:cap + guard] == 0xA5).all(), "bytes written at or beyond cap"
+        oo = d_oo.download(np.uint64)
+        idx = d_idx.download(np.uint64) if d_idx else None
+        return out[:int(oo[n]) if rc == MH_OK else 0], oo, d_nb.download(np.uint64)[:n], idx, off, rc
+
+    def decode(self, payload, pay_off, nbits, prev0=PREV0, sym_off=None, index=None, chunk_symbols=0, out_cap=None, guard=0):
+        """mh_dev_decode_each: (output bytes, sym_off[n + 1], per-stream status[n], device status)."""
+        l = lib()
+        payload = _u8(payload)
+        pay_off = np.ascontiguousarray(pay_off, dtype=np.uint64)
+        nbits = np.ascontiguousarray(nbits, dtype=np.uint64)
+        n = len(pay_off) - 1
+        if index is not None:
+            so = np.ascontiguousarray(sym_off, dtype=np.uint64).copy()
+            cap = int(so[n]) if out_cap is None else out_cap
+        else:
+            so = np.zeros(n + 1, dtype=np.uint64)
+            minl = max(self.code_lens()[1], 1)
+            cap = int(sum(int(b) // minl for b in nbits)) if out_cap is None else out_cap
+        d_pl = DeviceBuffer(max(payload.size, 1) + 64, payload if payload.size else None)
+        d_po, d_nb = DeviceBuffer(pay_off.nbytes, pay_off), DeviceBuffer(max(nbits.nbytes, 8), nbits if n else None)
+        d_out = DeviceBuffer(max(cap + guard, 1), np.full(cap + guard, 0xA5, dtype=np.uint8) if guard else None)
+        d_so = DeviceBuffer(so.nbytes, so)
+        d_idx = None
+        if index is not None:
+            index = np.ascontiguousarray(index, dtype=np.uint64)
+            d_idx = DeviceBuffer(max(index.nbytes, 8), index if index.size else None)
+        d_st = DeviceBuffer(max(n, 1) * 4)
+        wsb = l.mh_dev_decode_each_workspace(n)
+        d_ws = DeviceBuffer(wsb)
+        _check(l.mh_dev_decode_each(self._h, d_pl.ptr, d_po.ptr, d_nb.ptr, n, int(pay_off[n]), prev0, d_out.ptr, cap, d_so.ptr,
+                                    int(so[n]), d_idx.ptr if d_idx else None, chunk_symbols, d_st.ptr, d_ws.ptr, wsb, None), "mh_dev_decode_each")
+        rc = l.mh_dev_status(d_ws.ptr, None)
+        out = d_out.download()
+        if guard:
+            assert (out[cap:cap + guard] == 0xA5).all(), "bytes written at or beyond out_cap"
+        so = d_so.download(np.uint64)
+        return out[:min(int(so[n]), cap)].tobytes(), so, d_st.download(np.int32)[:n], rc
+
+
+def compress_each(messages, order=1, chunk_symbols=None, prev0=PREV0):
+    """[(table bytes, header + payload, nbits, index slice or None)] per message: the `.e`/`.eh` table and `.cm`/`.ch` file the
+    reference writes for that message alone (mh_compress_each)."""
+    messages = [bytes(m) for m in messages]
+    data, off = batch_offsets(messages)
+    l = lib()
+    n = len(messages)
+    tb, pb = C.c_size_t(0), C.c_size_t(0)
+    _check(l.mh_compress_each_bounds(off.ctypes.data, n, C.byref(tb), C.byref(pb)), "mh_compress_each_bounds")
+    tables = np.zeros(max(tb.value, 1), dtype=np.uint8)
+    payload = np.zeros(max(pb.value, 1), dtype=np.uint8)
+    tab_off, out_off = np.zeros(n + 1, dtype=np.uint64), np.zeros(n + 1, dtype=np.uint64)
+    nbits = np.zeros(max(n, 1), dtype=np.uint64)
+    idx = None
+    if chunk_symbols:
+        idx = np.zeros(max(l.mh_batch_index_capacity(int(data.size), n, chunk_symbols), 1), dtype=np.uint64)
+    _check(l.mh_compress_each(_ptr(data), off.ctypes.data, n, order, prev0, tables.ctypes.data, tb.value, tab_off.ctypes.data,
+                              payload.ctypes.data, pb.value, out_off.ctypes.data, nbits.ctypes.data,
+                              idx.ctypes.data if idx is not None else None, chunk_symbols or 0), "mh_compress_each")
+    res = []
+    for i, m in enumerate(messages):
+        nb = int(nbits[i])
+        sl = None
+        if chunk_symbols:
+            b = l.mh_batch_index_base(int(off[i]), i, chunk_symbols)
+            sl = idx[b:b + (len(m) + chunk_symbols - 1) // chunk_symbols].copy()
+        res.append((tables[int(tab_off[i]):int(tab_off[i + 1])].tobytes(),
+                    bytes([stream_header(order, nb)]) + payload[int(out_off[i]):int(out_off[i + 1])].tobytes(), nb, sl))
+    return res
+
+
+def decompress_each(tables, blobs, indices=None, chunk_symbols=0, lengths=None, prev0=PREV0, check=True):
+    """Table files and whole `.cm` / `.ch` files in, original messages out (mh_decompress_each).  With indices (one slice per
+    blob, from compress_each) the original lengths must be given too.  check=False returns (messages, per-stream status)
+    instead of raising on a failed stream."""
+    l = lib()
+    tables = [bytes(t) for t in tables]
+    payloads, nbits = [], []
+    for t, b in zip(tables, blobs):
+        nbits.append(parse_stream_header(table_order(t), b))
+        payloads.append(bytes(b)[1:])
+    n = len(tables)
+    tab, tab_off = batch_offsets(tables)
+    payload, pay_off = batch_offsets(payloads)
+    nb = np.array(nbits if n else [0], dtype=np.uint64)
+    idx = None
+    if indices is not None:
+        if lengths is None:
+            raise ValueError("decompress_each with indices needs the original lengths")
+        sym_off = _offsets(lengths)
+        cap = int(sym_off[n])
+        idx = np.zeros(max(l.mh_batch_index_capacity(cap, n, chunk_symbols), 1), dtype=np.uint64)
+        for i, sl in enumerate(indices):
+            b = l.mh_batch_index_base(int(sym_off[i]), i, chunk_symbols)
+            idx[b:b + len(sl)] = sl
+    else:
+        sym_off = np.zeros(n + 1, dtype=np.uint64)
+        cap = int(sum(int(b) for b in nbits))             # every code has at least one bit
+    out = np.zeros(max(cap, 1), dtype=np.uint8)
+    st = np.zeros(max(n, 1), dtype=np.int32)
+    rc = l.mh_decompress_each(_ptr(tab), tab_off.ctypes.data, _ptr(payload), pay_off.ctypes.data, nb.ctypes.data, n, prev0,
+                              out.ctypes.data, cap, sym_off.ctypes.data, idx.ctypes.data if idx is not None else None,
+                              chunk_symbols, st.ctypes.data)
+    if rc != MH_OK and (check or rc == MH_ERR_ARG or not st[:n].any()):
+        raise MhError(rc, "mh_decompress_each")
+    msgs = [out[int(sym_off[i]):int(sym_off[i + 1])].tobytes() for i in range(n)]
+    return msgs if check else (msgs, st[:n])

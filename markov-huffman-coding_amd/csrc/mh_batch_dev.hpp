@@ -1,0 +1,208 @@
+// mh_batch_dev.hpp — device code shared by the kernels of the two batch families: one shared model (mh_batch.hip) and one
+// model per stream (mh_each.hip).  Closed-form unit and chunk numbering, unaligned 16-byte loads, the segmented u64 scans,
+// the bit writer with shared edge words and the tail word, and the byte-exact output of a decoding lane.  Everything is in an
+// unnamed namespace: each kernel file gets its own copy.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "mh_batch.h"
+#include "mh_decode_dev.hpp"
+#include "mh_dev.hpp"
+
+namespace mhb {
+namespace {
+
+using mhk::BitSrc;
+
+constexpr uint32_t SUB_SHIFT = 10;                    // log2(B_SUB)
+static_assert((1u << SUB_SHIFT) == B_SUB && B_SUB == 64 * B_VEC, "a sub-step is one wave of 16-byte lanes");
+
+__device__ __forceinline__ void fail(int *status, int code) { atomicCAS(status, 0, code); }
+__device__ __forceinline__ bool stopped(const int *stop) { return *reinterpret_cast<const volatile int *>(stop) != 0; }
+
+// The stream that owns unit / chunk number u: the largest i <= n with (off[i] >> shift) + i <= u (the closed-form bases are
+// strictly increasing).  i == n: u lies behind the last stream.
+template <typename T>
+__device__ __forceinline__ uint64_t find_stream(const T *off, uint64_t n, uint32_t shift, uint64_t u) {
+    uint64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint64_t mid = (lo + hi + 1) >> 1;
+        if ((off[mid] >> shift) + mid <= u) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+// cnt (1..16) bytes at an arbitrary address, zero beyond cnt; only the dwords that hold bytes of the range are read (a stream
+// starts at any byte, so load_raw's 16-byte alignment does not hold here)
+__device__ __forceinline__ void load16(const uint8_t *p, uint32_t cnt, uint32_t (&x)[4]) {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(p);
+    const uint32_t *w = reinterpret_cast<const uint32_t *>(a & ~uintptr_t(3));
+    const uint32_t sh = uint32_t(a & 3u);
+    const uint32_t nw = (sh + cnt + 3u) >> 2;
+    uint32_t d[5];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) d[k] = uint32_t(k) < nw ? w[k] : 0u;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        uint32_t v = uint32_t(((uint64_t(d[q + 1]) << 32) | d[q]) >> (8u * sh));
+        const uint32_t lo = 4u * uint32_t(q);
+        if (cnt <= lo) v = 0;
+        else if (cnt < lo + 4u) v &= 0xFFFFFFFFu >> (8u * (lo + 4u - cnt));
+        x[q] = v;
+    }
+}
+__device__ __forceinline__ uint32_t byte_of(const uint32_t (&x)[4], uint32_t t) { return (x[t >> 2] >> (8u * (t & 3u))) & 255u; }
+
+// ------------------------------------------------------------------------------------------------ scans (exclusive, u64)
+
+constexpr int SCAN_T = 256;                        // SCAN_BLOCK / 4 elements per thread
+
+template <int NT>
+__device__ __forceinline__ unsigned long long block_exclusive(unsigned long long v, unsigned long long *s, unsigned long long &tot) {
+    s[threadIdx.x] = v;
+    __syncthreads();
+    for (int d = 1; d < NT; d <<= 1) {
+        const unsigned long long x = int(threadIdx.x) >= d ? s[threadIdx.x - d] : 0ull;
+        __syncthreads();
+        s[threadIdx.x] += x;
+        __syncthreads();
+    }
+    tot = s[NT - 1];
+    const unsigned long long incl = s[threadIdx.x];
+    __syncthreads();
+    return incl - v;
+}
+
+__global__ __launch_bounds__(SCAN_T) void batch_scan_block_kernel(unsigned long long *a, uint64_t len, unsigned long long *sums, const int *stop) {
+    __shared__ unsigned long long s[SCAN_T];
+    if (stopped(stop)) return;
+    const uint64_t base = uint64_t(blockIdx.x) * SCAN_BLOCK + uint64_t(threadIdx.x) * 4u;
+    unsigned long long v[4], t = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { v[k] = base + k < len ? a[base + k] : 0ull; t += v[k]; }
+    unsigned long long tot;
+    unsigned long long run = block_exclusive<SCAN_T>(t, s, tot);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { if (base + k < len) a[base + k] = run; run += v[k]; }
+    if (threadIdx.x == 0) sums[blockIdx.x] = tot;
+}
+
+__global__ __launch_bounds__(1024) void batch_scan_sums_kernel(unsigned long long *sums, uint64_t nb, const int *stop) {
+    __shared__ unsigned long long s[1024];
+    if (stopped(stop)) return;
+    unsigned long long carry = 0;
+    for (uint64_t c = 0; c < nb; c += 1024) {
+        const uint64_t k = c + threadIdx.x;
+        const unsigned long long v = k < nb ? sums[k] : 0ull;
+        unsigned long long tot;
+        const unsigned long long ex = block_exclusive<1024>(v, s, tot);
+        if (k < nb) sums[k] = carry + ex;
+        carry += tot;
+    }
+}
+
+__global__ __launch_bounds__(SCAN_T) void batch_scan_add_kernel(unsigned long long *a, uint64_t len, const unsigned long long *sums, const int *stop) {
+    if (stopped(stop)) return;
+    const unsigned long long add = sums[blockIdx.x];
+    const uint64_t base = uint64_t(blockIdx.x) * SCAN_BLOCK;
+    for (uint32_t k = threadIdx.x; k < SCAN_BLOCK; k += SCAN_T)
+        if (base + k < len) a[base + k] += add;
+}
+
+hipError_t scan_exclusive(unsigned long long *a, uint64_t len, unsigned long long *sums, const int *stop, hipStream_t st) {
+    if (len == 0) return hipSuccess;
+    const uint64_t nb = scan_blocks(len);
+    hipLaunchKernelGGL(batch_scan_block_kernel, dim3(uint32_t(nb)), dim3(SCAN_T), 0, st, a, len, sums, stop);
+    hipLaunchKernelGGL(batch_scan_sums_kernel, dim3(1), dim3(1024), 0, st, sums, nb, stop);
+    hipLaunchKernelGGL(batch_scan_add_kernel, dim3(uint32_t(nb)), dim3(SCAN_T), 0, st, a, len, sums, stop);
+    return hipGetLastError();
+}
+
+// Bits into 32-bit words, first stream bit in bit 31 of a word stored byte-swapped (MSB first inside a byte,
+// src/bitbuffer.cpp:12).  A word that lies wholly inside the lane's bits is stored; its edge words are shared with the
+// neighbour lane, sub-step or stream and are OR-ed into zeroed memory.  The last dword of the whole output, when it reaches
+// past the payload, is OR-ed into a workspace word instead and its bytes are copied out afterwards: nothing is touched at or
+// beyond out_off[n] <= cap.
+struct BitWriter {
+    uint32_t *out;
+    uint32_t *tail;
+    uint64_t tail_w;
+    uint64_t w;           // word the accumulator's first bit belongs to
+    uint64_t acc;         // nb pending bits, right-aligned
+    uint32_t nb;
+    bool lead;            // the current word holds bits in front of the lane's
+    __device__ __forceinline__ void init(uint32_t *o, uint32_t *t, uint64_t tw, uint64_t bit) {
+        out = o; tail = t; tail_w = tw; w = bit >> 5; nb = uint32_t(bit & 31u); acc = 0; lead = nb != 0;
+    }
+    __device__ __forceinline__ void put_word(uint32_t v, bool shared) {
+        const uint32_t m = __builtin_bswap32(v);
+        if (w == tail_w) atomicOr(tail, m);
+        else if (shared) atomicOr(out + w, m);
+        else out[w] = m;
+    }
+    __device__ __forceinline__ void push(uint64_t v, uint32_t l) {        // l <= 32
+        if (!l) return;
+        acc = (acc << l) | v;
+        nb += l;
+        if (nb >= 32u) {
+            nb -= 32u;
+            put_word(uint32_t(acc >> nb), lead);
+            lead = false;
+            acc &= (uint64_t(1) << nb) - 1u;
+            ++w;
+        }
+    }
+    __device__ __forceinline__ void code(uint64_t c, uint32_t l) {         // l <= 64
+        if (l > 32u) { push(c >> 32, l - 32u); push(c & 0xFFFFFFFFull, 32u); }
+        else push(c, l);
+    }
+    __device__ __forceinline__ void finish() {
+        if (nb) put_word(uint32_t(acc << (32u - nb)), true);
+    }
+};
+
+// a stream's payload as a bit source: reads stay inside the dwords that hold its bytes
+__device__ __forceinline__ BitSrc stream_src(const uint8_t *payload, uint64_t po, uint64_t nbits, uint64_t &bit0) {
+    const uint64_t base = po & ~uint64_t(3);
+    BitSrc s;
+    s.p = payload + base;
+    s.bytes = po + ((nbits + 7) >> 3) - base;
+    s.full_words = s.bytes >> 2;
+    bit0 = (po - base) * 8u;
+    return s;
+}
+
+// output bytes of one lane: whole aligned dwords where the lane owns them, single bytes at its edges
+struct ByteOut {
+    uint8_t *o;
+    uint64_t beg, pos;
+    uint32_t q;
+    __device__ __forceinline__ void init(uint8_t *out, uint64_t at) { o = out; beg = pos = at; q = 0; }
+    __device__ __forceinline__ void put(uint32_t b) {
+        q |= b << (8u * uint32_t(pos & 3u));
+        if ((pos & 3u) == 3u) {
+            const uint64_t d = pos - 3u;
+            if (d >= beg) *reinterpret_cast<uint32_t *>(o + d) = q;
+            else for (uint64_t k = beg; k <= pos; ++k) o[k] = uint8_t(q >> (8u * uint32_t(k & 3u)));
+            q = 0;
+        }
+        ++pos;
+    }
+    __device__ __forceinline__ void flush() {
+        if (pos & 3u) {
+            const uint64_t d = pos & ~uint64_t(3);
+            for (uint64_t k = d > beg ? d : beg; k < pos; ++k) o[k] = uint8_t(q >> (8u * uint32_t(k & 3u)));
+        }
+    }
+};
+
+inline int grid_for(uint64_t items, uint64_t per_block, int per_cu) {
+    const uint64_t want = (items + per_block - 1) / per_block;
+    const uint64_t cap = uint64_t(mhk::cu_count()) * uint64_t(per_cu);
+    return int(want < 1 ? 1 : (want > cap ? cap : want));
+}
+
+}  // namespace
+}  // namespace mhb
