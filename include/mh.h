@@ -623,6 +623,53 @@ int mh_decompress_each(const uint8_t *tables, const uint64_t *tab_off, const uin
                        const uint64_t *nbits, size_t n_streams, uint8_t prev0, uint8_t *out, size_t out_cap, uint64_t *sym_off,
                        const uint64_t *index, uint32_t chunk_symbols, int32_t *stream_status);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * RANDOM ACCESS: BYTE RANGES OF AN INDEXED STREAM — a few bytes out of a large stream (4 KiB at offset 9 GiB of a `.cm` with
+ * its --index sidecar; records spread over a compressed log) without decoding or uploading the rest.  Order 0 and order 1
+ * models; an order-2 model is refused with MH_ERR_ARG before anything is launched.
+ *   - A range is [begin, end) in symbols, i.e. bytes of the original input: 2 x uint64 per range.  Empty ranges (begin ==
+ *     end, [n, n) included) are MH_OK and write nothing.  Ranges may overlap each other and come in any order.
+ *   - The stream needs its chunk index (mh_encode, mh_dev_encode*, a batch stream's slice).  A stream without one (what the
+ *     reference writes) gets both indices from mh_dev_build_index_fine first.
+ *   - Work unit: a chunk of the index, or MH_FINE_SYMBOLS symbols with the fine index.  One lane decodes one (range, unit)
+ *     item: it starts at the unit's entry, decodes the symbols in front of the range without storing them, then stores the
+ *     rest of its share.  Without a fine index a lane may skip up to chunk_symbols - 1 symbols to store one; with it, at most
+ *     MH_FINE_SYMBOLS - 1.
+ *   - Checks.  An item that ends exactly on a unit boundary must use exactly the bits between its unit's entry and the next
+ *     one (nbits after the stream's last symbol).  An item that ends inside a unit is checked only for null table entries
+ *     and for running past nbits.  A unit whose entry lies past nbits or behind the entry before it is corrupt: every range
+ *     that touches it or ends on its start boundary gets MH_ERR_CORRUPT; the others decode byte-exact.  Huffman decoding
+ *     re-synchronises, so an entry moved to another plausible position is not always detected.
+ * --------------------------------------------------------------------------------------------------------------------- */
+size_t mh_dev_decode_ranges_workspace(size_t n_ranges);
+/* Decodes n_ranges ranges of ONE stream.  d_ranges: 2 x uint64 per range.  Range j's end - begin bytes go to
+ * d_out[d_out_at[j] ...); outputs of different ranges must not overlap; a range whose output would reach past out_cap writes
+ * nothing (MH_ERR_CAPACITY for that range).  Nothing is written outside the outputs of the ranges that are decoded.
+ * d_payload (any alignment) holds the stream's payload bytes [payload_byte_base, payload_byte_base + payload_bytes): a window
+ * of the payload (the whole payload is base 0, bytes ceil(nbits / 8)); index bit offsets stay relative to the stream start.
+ * Reads touch only the aligned dwords that hold window bytes.  A batch stream is d_payload = batch payload + pay_off[i]
+ * with d_index = its slice (mh_batch_index_base).  d_fine (NULL = none): the stream's fine index (mh_dev_encode_fine,
+ * mh_dev_build_index_fine).  d_out: 16-byte aligned.  d_range_status[j]: MH_OK, MH_ERR_ARG (begin > end, end > n_symbols,
+ * a unit outside the payload window), MH_ERR_CAPACITY or MH_ERR_CORRUPT; the workspace's status word (mh_dev_status) keeps
+ * one of them.  No host synchronisation, no allocation. */
+int mh_dev_decode_ranges(const mh_model *m, const uint8_t *d_payload, uint64_t payload_byte_base, uint64_t payload_bytes,
+                         uint64_t nbits, const uint64_t *d_index, uint32_t chunk_symbols, uint64_t n_symbols,
+                         const uint32_t *d_fine, const uint64_t *d_ranges, size_t n_ranges,
+                         uint8_t *d_out, const uint64_t *d_out_at, uint64_t out_cap,
+                         int32_t *d_range_status, void *d_ws, size_t ws_bytes, void *stream);
+/* Host form: payload and index are the whole stream in host memory (for example a mapped .cm and its sidecar).  Outputs are
+ * packed in range order: out_off[j] = sum of the lengths of the ranges before j (n_ranges + 1 entries, written; a range
+ * refused with MH_ERR_ARG has length 0).  Only the payload bytes of the chunks the ranges touch are uploaded: the byte spans
+ * of those chunks are sorted, spans less than 1 MiB apart are merged into one window, windows are cut at the segment size
+ * (MH_SEGMENT_BYTES), and each window is one mh_dev_decode_ranges call; ranges that cross a window edge are split.  Device
+ * footprint: about one segment of payload and one of output, plus the pieces.  range_status (may be NULL) as above;
+ * returns MH_OK or the first failing range's status. */
+int mh_decode_ranges(const mh_model *m, const uint8_t *payload, uint64_t nbits, const uint64_t *index,
+                     uint32_t chunk_symbols, uint64_t n_symbols, const uint64_t *ranges, size_t n_ranges,
+                     uint8_t *out, size_t out_cap, uint64_t *out_off, int32_t *range_status);
+/* Diagnostic: payload bytes the calling thread's last mh_decode_ranges uploaded. */
+uint64_t mh_last_range_upload_bytes(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -47,6 +47,7 @@ EXPORTS = [
     "mh_model_set_size", "mh_model_set_slots", "mh_model_set_stream_info", "mh_model_set_code_lens", "mh_model_set_tables_bound",
     "mh_dev_model_set_tables_workspace", "mh_dev_model_set_tables", "mh_encode_each_bound", "mh_dev_encode_each_workspace", "mh_dev_encode_each",
     "mh_dev_decode_each_workspace", "mh_dev_decode_each", "mh_compress_each_bounds", "mh_compress_each", "mh_decompress_each",
+    "mh_dev_decode_ranges_workspace", "mh_dev_decode_ranges", "mh_decode_ranges", "mh_last_range_upload_bytes",
 ]
 BATCH_WALK_MAX_BITS = 1 << 23              # include/mh.h MH_BATCH_WALK_MAX_BITS
 
@@ -190,6 +191,12 @@ def lib():
         l.mh_compress_each_bounds.argtypes = [vp, sz, psz, psz]
         l.mh_compress_each.argtypes = [vp, vp, sz, i32, u8, vp, sz, vp, vp, sz, vp, vp, vp, u32]
         l.mh_decompress_each.argtypes = [vp, vp, vp, vp, vp, sz, u8, vp, sz, vp, vp, u32, vp]
+        l.mh_dev_decode_ranges_workspace.argtypes = [sz]
+        l.mh_dev_decode_ranges_workspace.restype = sz
+        l.mh_dev_decode_ranges.argtypes = [vp, vp, u64, u64, u64, vp, u32, u64, vp, vp, sz, vp, vp, u64, vp, vp, sz, vp]
+        l.mh_decode_ranges.argtypes = [vp, vp, u64, vp, u32, u64, vp, sz, vp, sz, vp, vp]
+        l.mh_last_range_upload_bytes.argtypes = []
+        l.mh_last_range_upload_bytes.restype = u64
         _lib = l
     return _lib
 
@@ -443,6 +450,29 @@ class Model:
             raise MhError(MH_ERR_CORRUPT, "decompress")
         _check(lib().mh_stream_parse_header(self._h, int(a[0]), a.size, C.byref(nbits)), "mh_stream_parse_header")
         return self.decode(a[1:], nbits.value, PREV0, index, chunk_symbols, n_symbols)
+
+    # ---- random access (mh_decode_ranges) -----------------------------------------------------------------------------
+    def decode_ranges(self, payload, nbits, index, chunk_symbols, n_symbols, ranges):
+        """Bytes [begin, end) of the original input for every (begin, end) in `ranges`, from an indexed stream (payload without
+        the header byte, its chunk index).  Returns (list of byte strings, int32 status per range); a failed range's bytes are
+        empty.  Raises MhError on a call-level error (bad arguments, no device)."""
+        a = _u8(payload)
+        rg = np.ascontiguousarray(np.asarray(ranges, dtype=np.uint64).reshape(-1, 2))
+        n = rg.shape[0]
+        idx = np.ascontiguousarray(index if index is not None else np.zeros(0), dtype=np.uint64)
+        ok = (rg[:, 0] <= rg[:, 1]) & (rg[:, 1] <= np.uint64(n_symbols))
+        cap = int(np.sum(np.where(ok, rg[:, 1] - rg[:, 0], 0), dtype=np.uint64)) if n else 0
+        out = np.zeros(max(cap, 1), dtype=np.uint8)
+        out_off = np.zeros(n + 1, dtype=np.uint64)
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        ip = idx.ctypes.data if idx.size else (out.ctypes.data if n_symbols == 0 else None)
+        rc = lib().mh_decode_ranges(self._h, _ptr(a), nbits, ip, chunk_symbols, n_symbols, rg.ctypes.data if n else None, n,
+                                    out.ctypes.data, cap, out_off.ctypes.data, status.ctypes.data)
+        status = status[:n]
+        if rc != MH_OK and not np.any(status == rc):
+            raise MhError(rc, "mh_decode_ranges")
+        res = [out[int(out_off[j]):int(out_off[j + 1])].tobytes() if status[j] == MH_OK else b"" for j in range(n)]
+        return res, status
 
     # ---- batches of independent streams (mh_encode_batch / mh_decode_batch) -------------------------------------------
     def encode_batch(self, messages, prev0=PREV0, chunk_symbols=None):

@@ -196,25 +196,6 @@ __device__ __forceinline__ void stream_fail(const DecBatchParams &p, int *status
     fail(status, dev_code);
 }
 
-// LDS: sec_base u32[256] | prim u16[256 << P] | sec u16[nsec] when the model's tables fit (the chunk decoder's layout)
-__device__ __forceinline__ DecTables load_tables(const DecBatchParams &p, unsigned char *smem, const uint16_t *&lut, const uint32_t *&sub_base) {
-    uint32_t *sb = reinterpret_cast<uint32_t *>(smem);
-    uint16_t *lp = reinterpret_cast<uint16_t *>(smem + 1024);
-    const uint32_t nprim16 = (256u << p.P) / 8u;
-    for (uint32_t i = threadIdx.x; i < nprim16; i += blockDim.x) reinterpret_cast<uint4 *>(lp)[i] = reinterpret_cast<const uint4 *>(p.prim)[i];
-    uint16_t *lsec = lp + (256u << p.P);
-    if (p.sec_lds) {
-        const uint32_t nsec16 = (p.nsec + 7u) / 8u;
-        for (uint32_t i = threadIdx.x; i < nsec16; i += blockDim.x) reinterpret_cast<uint4 *>(lsec)[i] = reinterpret_cast<const uint4 *>(p.sec)[i];
-    }
-    for (uint32_t i = threadIdx.x; i < 256u; i += blockDim.x) sb[i] = p.sec_base[i];
-    __syncthreads();
-    lut = lp;
-    sub_base = sb;
-    return DecTables{p.sec_lds ? lsec : p.sec, p.tree, p.P, p.direct, p.H,
-                     __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t *>(p.sec), 0, int((p.nsec + 8u) * 2u), 0x00020000)};
-}
-
 __global__ void batch_dec_check_kernel(DecBatchParams p, int *status, int *stop) {
     const uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
     if (i > p.n) return;

@@ -1,7 +1,8 @@
 // mh_batch_dev.hpp — device code shared by the kernels of the two batch families: one shared model (mh_batch.hip) and one
-// model per stream (mh_each.hip).  Closed-form unit and chunk numbering, unaligned 16-byte loads, the segmented u64 scans,
-// the bit writer with shared edge words and the tail word, and the byte-exact output of a decoding lane.  Everything is in an
-// unnamed namespace: each kernel file gets its own copy.
+// model per stream (mh_each.hip), and by the byte-range decoder (mh_range.hip).  Closed-form unit and chunk numbering,
+// unaligned 16-byte loads, the segmented u64 scans, the bit writer with shared edge words and the tail word, the byte-exact
+// output of a decoding lane and the LDS loader of a shared model's decode tables.  Everything is in an unnamed namespace:
+// each kernel file gets its own copy.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -15,6 +16,7 @@ namespace mhb {
 namespace {
 
 using mhk::BitSrc;
+using mhk::DecTables;
 
 constexpr uint32_t SUB_SHIFT = 10;                    // log2(B_SUB)
 static_assert((1u << SUB_SHIFT) == B_SUB && B_SUB == 64 * B_VEC, "a sub-step is one wave of 16-byte lanes");
@@ -197,6 +199,25 @@ struct ByteOut {
         }
     }
 };
+
+// LDS: sec_base u32[256] | prim u16[256 << P] | sec u16[nsec] when the model's tables fit (the chunk decoder's layout)
+__device__ __forceinline__ DecTables load_tables(const DecBatchParams &p, unsigned char *smem, const uint16_t *&lut, const uint32_t *&sub_base) {
+    uint32_t *sb = reinterpret_cast<uint32_t *>(smem);
+    uint16_t *lp = reinterpret_cast<uint16_t *>(smem + 1024);
+    const uint32_t nprim16 = (256u << p.P) / 8u;
+    for (uint32_t i = threadIdx.x; i < nprim16; i += blockDim.x) reinterpret_cast<uint4 *>(lp)[i] = reinterpret_cast<const uint4 *>(p.prim)[i];
+    uint16_t *lsec = lp + (256u << p.P);
+    if (p.sec_lds) {
+        const uint32_t nsec16 = (p.nsec + 7u) / 8u;
+        for (uint32_t i = threadIdx.x; i < nsec16; i += blockDim.x) reinterpret_cast<uint4 *>(lsec)[i] = reinterpret_cast<const uint4 *>(p.sec)[i];
+    }
+    for (uint32_t i = threadIdx.x; i < 256u; i += blockDim.x) sb[i] = p.sec_base[i];
+    __syncthreads();
+    lut = lp;
+    sub_base = sb;
+    return DecTables{p.sec_lds ? lsec : p.sec, p.tree, p.P, p.direct, p.H,
+                     __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t *>(p.sec), 0, int((p.nsec + 8u) * 2u), 0x00020000)};
+}
 
 inline int grid_for(uint64_t items, uint64_t per_block, int per_cu) {
     const uint64_t want = (items + per_block - 1) / per_block;

@@ -102,7 +102,8 @@ struct InputView {
     void* map = nullptr;
     size_t map_len = 0;
     std::vector<unsigned char> own;
-    explicit InputView(FILE* f) {
+    // whole == false: only parts of the file will be read (--range): no read-ahead, no bulk population
+    explicit InputView(FILE* f, bool whole = true) {
         if (!f) return;                                              // empty view (placeholder)
         struct stat st;
         long pos = ftell(f);
@@ -110,8 +111,8 @@ struct InputView {
             void* m = mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fileno(f), 0);
             if (m != MAP_FAILED) {
                 map = m; map_len = (size_t)st.st_size;
-                (void)madvise(m, map_len, MADV_SEQUENTIAL);
-                populate_read();
+                (void)madvise(m, map_len, whole ? MADV_SEQUENTIAL : MADV_RANDOM);
+                if (whole) populate_read();
                 data = (const unsigned char*)m + pos;
                 size = map_len - (size_t)pos;
                 fseek(f, 0, SEEK_END);
@@ -353,7 +354,7 @@ static uint8_t* open_output_cb(void* ctx, size_t n) {
 
 // src/coding.cpp:96-160
 void i_coding_provider::decompress(FILE* input_fd, FILE* output_fd) {
-    InputView in(input_fd);
+    InputView in(input_fd, ranges_.empty());
     if (in.size == 0) mh_or_die(MH_ERR_CORRUPT, "decompress");
     uint64_t nbits = 0;
     mh_or_die(mh_stream_parse_header(model_, in.data[0], in.size, &nbits), "decompress");
@@ -380,6 +381,35 @@ void i_coding_provider::decompress(FILE* input_fd, FILE* output_fd) {
         }
     }
     const bool have_index = !index.empty();
+    if (!ranges_.empty()) {
+        // --range: only the payload bytes of the chunks the ranges touch are read from the mapping and uploaded
+        if (!have_index) {
+            eprintf("Error: --range needs a usable index sidecar (--index %s).\n", index_path_.c_str());
+            exit(1);
+        }
+        size_t total = 0;
+        for (size_t j = 0; j < ranges_.size(); j += 2) {
+            if (ranges_[j + 1] > n_symbols) {
+                eprintf("Error: --range %llu:%llu lies past the end of the stream (%llu bytes).\n", (unsigned long long)ranges_[j],
+                        (unsigned long long)ranges_[j + 1], (unsigned long long)n_symbols);
+                exit(1);
+            }
+            total += (size_t)(ranges_[j + 1] - ranges_[j]);
+        }
+        const size_t n = ranges_.size() / 2;
+        std::vector<uint64_t> out_off(n + 1);
+        std::vector<int32_t> status(n);
+        OutputView out;
+        out.open(output_fd, total);
+        StageTimer timer("decompress_ranges", total);
+        mh_or_die(mh_decode_ranges(model_, in.data + 1, nbits, index.data(), chunk, n_symbols, ranges_.data(), n, out.data, total,
+                                   out_off.data(), status.data()), "decompress (--range)");
+        out.finish();
+        fclose(input_fd);
+        if (output_fd != stdout) fclose(output_fd);
+        else fflush(output_fd);
+        return;
+    }
     // the output size is known once the symbols are counted (without an index: after the device has
     // rebuilt it); the library then asks for the buffer, which is the mapped output file
     size_t n = 0;

@@ -55,6 +55,8 @@ public:
     void decompress(FILE* input_fd, FILE* output_fd);
     // extension: chunk index sidecar (not part of the reference's format; see include/mh.h)
     void set_index_path(const std::string& path, uint32_t chunk_symbols) { index_path_ = path; chunk_ = chunk_symbols; }
+    // extension: decompress extracts only these [begin, end) byte ranges of the original input (needs the index sidecar)
+    void set_ranges(const std::vector<uint64_t>& begin_end) { ranges_ = begin_end; }
     const mh_model* model() const { return model_; }
 
 protected:
@@ -74,6 +76,7 @@ private:
     encoding_descriptor scratch_desc_;
     tree_node scratch_node_;
     std::string index_path_;
+    std::vector<uint64_t> ranges_;
     std::vector<uint64_t> counts_;               // histogram the tables were built from (empty when loaded from a file)
     uint32_t chunk_ = MH_CHUNK_DEFAULT;
 };

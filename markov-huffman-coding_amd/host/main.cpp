@@ -10,6 +10,7 @@
 //                    parallel; without it extraction first rebuilds the index on the device
 //   --chunk N        symbols per index entry (power of two, 256..8192; default 1024)
 //   --device N       HIP device ordinal
+//   --range B:E      extract only bytes [B, E) of the original input (repeatable; needs -x and --index)
 #include <errno.h>
 #include <stdlib.h>
 #include <string.h>
@@ -34,6 +35,7 @@ static void print_help() {
     eprintf("\t--chunk n      symbols per index entry (default 1024)\n");
     eprintf("\t--order2       contexts of two previous bytes (MI355X extension; own file formats)\n");
     eprintf("\t--device n     HIP device ordinal\n");
+    eprintf("\t--range b:e    with -x and --index: extract only bytes [b, e) (repeatable, concatenated in order)\n");
 }
 
 struct options {
@@ -46,7 +48,21 @@ struct options {
     uint32_t chunk = MH_CHUNK_DEFAULT;
     bool order2 = false;
     int device = -1;
+    std::vector<uint64_t> ranges;                                 // begin, end per --range
 };
+
+// "B:E" with decimal B <= E; anything else is an error
+static bool parse_range(const char* v, uint64_t* b, uint64_t* e) {
+    const char* colon = strchr(v, ':');
+    if (!colon || colon == v || !colon[1] || v[0] == '-' || colon[1] == '-') return false;
+    char* end = nullptr;
+    errno = 0;
+    *b = strtoull(v, &end, 10);
+    if (errno || end != colon) return false;
+    *e = strtoull(colon + 1, &end, 10);
+    if (errno || *end) return false;
+    return *b <= *e;
+}
 
 // Flag grammar of src/main.cpp:55-101.
 static options parse(int argc, char* argv[]) {
@@ -69,6 +85,16 @@ static options parse(int argc, char* argv[]) {
             }
             else if (!strcmp(a, "--device")) o.device = atoi(need(a));
             else if (!strcmp(a, "--order2")) o.order2 = true;
+            else if (!strcmp(a, "--range")) {
+                const char* v = need(a);
+                uint64_t b = 0, e = 0;
+                if (!parse_range(v, &b, &e)) {
+                    eprintf("Error: --range expects B:E with B <= E (byte offsets of the original input), got \"%s\".\n", v);
+                    exit(1);
+                }
+                o.ranges.push_back(b);
+                o.ranges.push_back(e);
+            }
             else eprintf("Warning: Unknown option %s.\n", a);
             continue;
         }
@@ -115,6 +141,16 @@ int main(int argc, char* argv[]) {
         return 1;
     }
     options o = parse(argc, argv);
+    if (!o.ranges.empty()) {                                       // checked before anything is opened or a device is used
+        if (!o.extract || o.index_path.empty()) {
+            eprintf("Error: --range needs -x and --index.\n");
+            exit(1);
+        }
+        if (o.order2) {
+            eprintf("Error: --range does not support --order2.\n");
+            exit(1);
+        }
+    }
 
     // validation of src/main.cpp:103-115
     if (!o.input) {
@@ -179,6 +215,7 @@ int main(int argc, char* argv[]) {
         fseek(input_fd, 0, SEEK_SET);                              // src/main.cpp:183
     }
     if (!o.index_path.empty()) coder->set_index_path(o.index_path, o.chunk);
+    if (!o.ranges.empty()) coder->set_ranges(o.ranges);
 
     if (o.debug) {                                                 // src/main.cpp:186-190
         coder->print_table();
