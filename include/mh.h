@@ -670,6 +670,68 @@ int mh_decode_ranges(const mh_model *m, const uint8_t *payload, uint64_t nbits, 
 /* Diagnostic: payload bytes the calling thread's last mh_decode_ranges uploaded. */
 uint64_t mh_last_range_upload_bytes(void);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * RANDOM ACCESS INTO BATCHES — point lookups into packed records: bytes [begin, end) of stream `stream` of a batch (the
+ * batch section or the one-model-each section above), for many lookups in one call and a fixed number of launches.
+ * Order 0 and order 1; a shared order-2 model is refused with MH_ERR_ARG before anything is launched.  No new format: the
+ * batch is pay_off[n + 1], nbits[n], prev0 and, optionally, the closed-form index slices (mh_batch_index_base).
+ *   - A lookup is 3 x uint64: stream, begin, end; begin and end count symbols from the start of that stream.  Lookups may
+ *     repeat, overlap and come in any order.  Empty lookups ([n_i, n_i) included) are MH_OK and write nothing.
+ *   - With an index, sym_off[n + 1] (the encode's in_off) is input and a lookup with end > n_i is MH_ERR_ARG.  One lane
+ *     decodes one (lookup, chunk) item from the chunk's entry, with the checks of the section above: an entry must lie in
+ *     [0, nbits_i] and not behind its predecessor; an item that ends on a chunk boundary or at n_i must use exactly the bits
+ *     up to the next entry (nbits_i after the last chunk); one that ends inside a chunk is checked for null table entries
+ *     and for running past nbits_i.
+ *   - Without an index (the `.cm` files the reference writes), one lane walks the stream from bit 0 in context prev0, skips
+ *     `begin` symbols and stores the rest.  Streams over MH_BATCH_WALK_MAX_BITS are MH_ERR_ARG for their lookups in the
+ *     device calls (the host forms decode them through mh_decode).  A walk that reaches nbits_i before `end` ran past the
+ *     stream's end: MH_ERR_ARG; running past nbits_i inside a code or a null table entry: MH_ERR_CORRUPT.  sym_off is
+ *     optional here; when given, end > n_i is refused up front and a lookup that ends at n_i must end exactly at nbits_i
+ *     (src/coding.cpp:124,158).
+ *   - Per-lookup status: MH_OK, MH_ERR_ARG (stream >= n_streams, begin > end, nbits_i beyond the stream's payload bytes,
+ *     non-monotone offsets of the stream, the cases above), MH_ERR_CAPACITY (output past out_cap: nothing written) or
+ *     MH_ERR_CORRUPT, the first error kept.  A corrupt entry or payload of stream k fails only the lookups that read it.
+ *     The workspace's status word (mh_dev_status) keeps one of the errors.
+ *   - Only the offsets of the streams the lookups name are read: the device calls' cost does not depend on n_streams.
+ *   - Lookup j writes end - begin bytes to d_out[d_out_at[j] ...); outputs of different lookups must not overlap.  Nothing
+ *     is written outside the outputs of the lookups that are decoded; a lookup that fails while decoding (MH_ERR_CORRUPT,
+ *     or an index-free walk that ends before `end`) may have written part of its own output.
+ * --------------------------------------------------------------------------------------------------------------------- */
+size_t mh_dev_decode_batch_ranges_workspace(size_t n_lookups);
+/* Under one shared model.  d_payload, d_out and d_ws 16-byte aligned; d_sym_off may be NULL only without d_index.  No host
+ * synchronisation, no allocation. */
+int mh_dev_decode_batch_ranges(const mh_model *m, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits,
+                               size_t n_streams, uint8_t prev0, const uint64_t *d_sym_off, const uint64_t *d_index,
+                               uint32_t chunk_symbols, const uint64_t *d_lookups, size_t n_lookups,
+                               uint8_t *d_out, const uint64_t *d_out_at, uint64_t out_cap,
+                               int32_t *d_lookup_status, void *d_ws, size_t ws_bytes, void *stream);
+/* The same with stream i under the set's model i (n_streams == mh_model_set_size(s), else MH_ERR_ARG). */
+int mh_dev_decode_each_ranges(const mh_model_set *s, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits,
+                              size_t n_streams, uint8_t prev0, const uint64_t *d_sym_off, const uint64_t *d_index,
+                              uint32_t chunk_symbols, const uint64_t *d_lookups, size_t n_lookups,
+                              uint8_t *d_out, const uint64_t *d_out_at, uint64_t out_cap,
+                              int32_t *d_lookup_status, void *d_ws, size_t ws_bytes, void *stream);
+/* Host forms: payload (payload_bytes) and tables (tables_bytes) are whole host buffers, for example a mapped archive.
+ * Before a device is touched every lookup is checked, with its stream's offsets against those lengths (a bad one is
+ * MH_ERR_ARG for that lookup), and, for mh_decompress_each_ranges, its stream's table file is parsed: a malformed table
+ * fails that stream's lookups with MH_ERR_BADTABLE; an untouched stream's table and payload are never read.  Outputs are
+ * packed in lookup order: out_off[n_lookups + 1] is written, a refused lookup has length 0 (one that does not fit keeps its
+ * length, MH_ERR_CAPACITY).  Only the touched streams are uploaded: their payloads, whole and compacted, and their index
+ * slices re-based to the compacted sym_off; a touched stream of more than MH_EACH_DIRECT_BYTES of payload, or an index-free
+ * one over MH_BATCH_WALK_MAX_BITS, goes through mh_decode_ranges on its slice (indexed) or mh_decode (index-free) instead.
+ * lookup_status (may be NULL) as above; returns MH_OK or the first failing lookup's status. */
+int mh_decode_batch_ranges(const mh_model *m, const uint8_t *payload, uint64_t payload_bytes, const uint64_t *pay_off,
+                           const uint64_t *nbits, size_t n_streams, uint8_t prev0, const uint64_t *sym_off,
+                           const uint64_t *index, uint32_t chunk_symbols, const uint64_t *lookups, size_t n_lookups,
+                           uint8_t *out, size_t out_cap, uint64_t *out_off, int32_t *lookup_status);
+int mh_decompress_each_ranges(const uint8_t *tables, uint64_t tables_bytes, const uint64_t *tab_off,
+                              const uint8_t *payload, uint64_t payload_bytes, const uint64_t *pay_off,
+                              const uint64_t *nbits, size_t n_streams, uint8_t prev0, const uint64_t *sym_off,
+                              const uint64_t *index, uint32_t chunk_symbols, const uint64_t *lookups, size_t n_lookups,
+                              uint8_t *out, size_t out_cap, uint64_t *out_off, int32_t *lookup_status);
+/* Diagnostic: payload bytes the calling thread's last mh_decode_batch_ranges / mh_decompress_each_ranges uploaded. */
+uint64_t mh_last_batch_range_upload_bytes(void);
+
 #ifdef __cplusplus
 }
 #endif

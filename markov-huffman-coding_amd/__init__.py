@@ -48,6 +48,8 @@ EXPORTS = [
     "mh_dev_model_set_tables_workspace", "mh_dev_model_set_tables", "mh_encode_each_bound", "mh_dev_encode_each_workspace", "mh_dev_encode_each",
     "mh_dev_decode_each_workspace", "mh_dev_decode_each", "mh_compress_each_bounds", "mh_compress_each", "mh_decompress_each",
     "mh_dev_decode_ranges_workspace", "mh_dev_decode_ranges", "mh_decode_ranges", "mh_last_range_upload_bytes",
+    "mh_dev_decode_batch_ranges_workspace", "mh_dev_decode_batch_ranges", "mh_dev_decode_each_ranges", "mh_decode_batch_ranges",
+    "mh_decompress_each_ranges", "mh_last_batch_range_upload_bytes",
 ]
 BATCH_WALK_MAX_BITS = 1 << 23              # include/mh.h MH_BATCH_WALK_MAX_BITS
 
@@ -197,6 +199,14 @@ def lib():
         l.mh_decode_ranges.argtypes = [vp, vp, u64, vp, u32, u64, vp, sz, vp, sz, vp, vp]
         l.mh_last_range_upload_bytes.argtypes = []
         l.mh_last_range_upload_bytes.restype = u64
+        l.mh_dev_decode_batch_ranges_workspace.argtypes = [sz]
+        l.mh_dev_decode_batch_ranges_workspace.restype = sz
+        l.mh_dev_decode_batch_ranges.argtypes = [vp, vp, vp, vp, sz, u8, vp, vp, u32, vp, sz, vp, vp, u64, vp, vp, sz, vp]
+        l.mh_dev_decode_each_ranges.argtypes = [vp, vp, vp, vp, sz, u8, vp, vp, u32, vp, sz, vp, vp, u64, vp, vp, sz, vp]
+        l.mh_decode_batch_ranges.argtypes = [vp, vp, u64, vp, vp, sz, u8, vp, vp, u32, vp, sz, vp, sz, vp, vp]
+        l.mh_decompress_each_ranges.argtypes = [vp, u64, vp, vp, u64, vp, vp, sz, u8, vp, vp, u32, vp, sz, vp, sz, vp, vp]
+        l.mh_last_batch_range_upload_bytes.argtypes = []
+        l.mh_last_batch_range_upload_bytes.restype = u64
         _lib = l
     return _lib
 
@@ -291,6 +301,95 @@ def histogram_o1_batch(messages, prev0=PREV0, order=1):
         _check(l.mh_dev_histogram_o0_batch(d_data.ptr, d_off.ptr, n, total, d_counts.ptr, d_ws.ptr, wsb, None), "mh_dev_histogram_o0_batch")
     _check(l.mh_dev_status(d_ws.ptr, None), "mh_dev_histogram_batch")
     return d_counts.download(np.uint64)
+
+
+# ---- lookups into batches (include/mh.h, "RANDOM ACCESS INTO BATCHES") -----------------------------------------------------
+RANGE_GUARD = 64          # bytes of 0xA5 in front of, between and behind the outputs of the device-call wrappers
+RANGE_FILL = 0xA5
+
+
+def _lookups(lookups):
+    return np.ascontiguousarray(np.asarray(lookups, dtype=np.uint64).reshape(-1, 3))
+
+
+def _lookup_lengths(lk, nbits, sym_off):
+    """Output length of every lookup that can be served: end - begin, 0 for a lookup refused by its arguments alone."""
+    n = len(nbits)
+    s, b, e = lk[:, 0], lk[:, 1], lk[:, 2]
+    ok = (s < np.uint64(n)) & (b <= e)
+    si = np.where(ok, s, 0).astype(np.int64)
+    if sym_off is not None:
+        so = np.asarray(sym_off, dtype=np.uint64)
+        bound = so[si + 1] - so[si] if n else np.zeros(len(lk), dtype=np.uint64)
+    else:
+        bound = np.asarray(nbits, dtype=np.uint64)[si] if n else np.zeros(len(lk), dtype=np.uint64)
+    ok &= e <= bound
+    return np.where(ok, e - b, np.uint64(0)).astype(np.uint64)
+
+
+def _dev_batch_ranges(fn, handle, payload, pay_off, nbits, lookups, prev0, sym_off, index, chunk_symbols, out_cap):
+    """One mh_dev_decode_batch_ranges / mh_dev_decode_each_ranges call with RANGE_GUARD bytes of RANGE_FILL around every
+    output.  Returns (list of bytes per lookup, int32 status per lookup, mh_dev_status); asserts that no byte changed outside
+    the outputs of the lookups that were decoded (a lookup that failed while decoding may have written part of its own)."""
+    l = lib()
+    payload = _u8(payload)
+    pay_off = np.ascontiguousarray(pay_off, dtype=np.uint64)
+    nbits = np.ascontiguousarray(nbits, dtype=np.uint64)
+    n = len(pay_off) - 1
+    lk = _lookups(lookups)
+    m = lk.shape[0]
+    ln = np.where(lk[:, 1] <= lk[:, 2], np.minimum(lk[:, 2] - lk[:, 1], np.uint64(1 << 24)), np.uint64(0)).astype(np.uint64)
+    at = np.zeros(max(m, 1), dtype=np.uint64)
+    pos = RANGE_GUARD
+    for j in range(m):
+        at[j] = pos
+        pos += int(ln[j]) + RANGE_GUARD
+    full = pos
+    cap = full if out_cap is None else out_cap
+    size = max(full, cap) + RANGE_GUARD
+    d_pl = DeviceBuffer(max(payload.size, 1) + 64, payload if payload.size else None)
+    d_po, d_nb = DeviceBuffer(pay_off.nbytes, pay_off), DeviceBuffer(max(nbits.nbytes, 8), nbits if n else None)
+    d_so = DeviceBuffer(max(n + 1, 1) * 8, np.ascontiguousarray(sym_off, dtype=np.uint64)) if sym_off is not None else None
+    d_idx = None
+    if index is not None:
+        index = np.ascontiguousarray(index, dtype=np.uint64)
+        d_idx = DeviceBuffer(max(index.nbytes, 8), index if index.size else None)
+    d_lk = DeviceBuffer(max(lk.nbytes, 24), lk if m else None)
+    d_at = DeviceBuffer(at.nbytes, at)
+    d_out = DeviceBuffer(size, np.full(size, RANGE_FILL, dtype=np.uint8))
+    d_st = DeviceBuffer(max(m, 1) * 4, np.full(max(m, 1), 99, dtype=np.int32))
+    wsb = l.mh_dev_decode_batch_ranges_workspace(m)
+    d_ws = DeviceBuffer(wsb)
+    _check(fn(handle, d_pl.ptr, d_po.ptr, d_nb.ptr, n, prev0, d_so.ptr if d_so else None, d_idx.ptr if d_idx else None, chunk_symbols,
+              d_lk.ptr, m, d_out.ptr, d_at.ptr, cap, d_st.ptr, d_ws.ptr, wsb, None), "mh_dev_decode_*_ranges")
+    rc = l.mh_dev_status(d_ws.ptr, None)
+    out = d_out.download()
+    st = d_st.download(np.int32)[:m]
+    may = np.zeros(size, dtype=bool)
+    for j in range(m):
+        if st[j] in (MH_OK, MH_ERR_CORRUPT, MH_ERR_ARG):        # (MH_ERR_ARG: an index-free walk that ended before `end`)
+            may[int(at[j]):int(at[j]) + int(ln[j])] = True
+    assert (out[~may] == RANGE_FILL).all(), "bytes written outside the outputs of the lookups that decoded"
+    res = [out[int(at[j]):int(at[j]) + int(lk[j, 2] - lk[j, 1])].tobytes() if st[j] == MH_OK else b"" for j in range(m)]
+    return res, st, rc
+
+
+def _host_batch_ranges(call, name, lk, nbits, sym_off):
+    """Runs call(out, cap, out_off, status) of a host form; (list of bytes per lookup, int32 status per lookup)."""
+    m = lk.shape[0]
+    cap = int(np.sum(_lookup_lengths(lk, nbits, sym_off), dtype=np.uint64)) if m else 0
+    out = np.zeros(max(cap, 1), dtype=np.uint8)
+    out_off = np.zeros(m + 1, dtype=np.uint64)
+    st = np.zeros(max(m, 1), dtype=np.int32)
+    rc = call(out.ctypes.data, cap, out_off.ctypes.data, st.ctypes.data)
+    st = st[:m]
+    if rc != MH_OK and not np.any(st == rc):
+        raise MhError(rc, name)
+    return [out[int(out_off[j]):int(out_off[j + 1])].tobytes() if st[j] == MH_OK else b"" for j in range(m)], st
+
+
+def last_batch_range_upload_bytes():
+    return lib().mh_last_batch_range_upload_bytes()
 
 
 class Model:
@@ -473,6 +572,54 @@ class Model:
             raise MhError(rc, "mh_decode_ranges")
         res = [out[int(out_off[j]):int(out_off[j + 1])].tobytes() if status[j] == MH_OK else b"" for j in range(n)]
         return res, status
+
+
+    # ---- lookups into batches (mh_decode_batch_ranges / mh_dev_decode_batch_ranges) ------------------------------------
+    def decode_batch_ranges(self, payload, pay_off, nbits, lookups, prev0=PREV0, sym_off=None, index=None, chunk_symbols=0):
+        """Bytes [begin, end) of stream `stream` for every (stream, begin, end) in `lookups`, from a batch (packed payloads,
+        pay_off[n + 1], nbits[n]; with an index, sym_off is the encode's in_off).  Returns (list of byte strings, int32 status
+        per lookup); a failed lookup's bytes are empty.  Raises MhError on a call-level error (mh_decode_batch_ranges)."""
+        payload = _u8(payload)
+        pay_off = np.ascontiguousarray(pay_off, dtype=np.uint64)
+        nbits = np.ascontiguousarray(nbits, dtype=np.uint64)
+        n = len(pay_off) - 1
+        so = np.ascontiguousarray(sym_off, dtype=np.uint64) if sym_off is not None else None
+        idx = np.ascontiguousarray(index, dtype=np.uint64) if index is not None else None
+        lk = _lookups(lookups)
+        m = lk.shape[0]
+        call = lambda out, cap, oo, st: lib().mh_decode_batch_ranges(
+            self._h, _ptr(payload), payload.size, pay_off.ctypes.data, nbits.ctypes.data if n else None, n, prev0,
+            so.ctypes.data if so is not None else None,
+            (idx.ctypes.data if idx.size else pay_off.ctypes.data) if idx is not None else None, chunk_symbols,
+            lk.ctypes.data if m else None, m, out, cap, oo, st)
+        return _host_batch_ranges(call, "mh_decode_batch_ranges", lk, nbits[:n], so)
+
+    def dev_decode_batch_ranges(self, payload, pay_off, nbits, lookups, prev0=PREV0, sym_off=None, index=None, chunk_symbols=0, out_cap=None):
+        """One mh_dev_decode_batch_ranges call with guard bytes around every output: (list of bytes, status per lookup,
+        mh_dev_status)."""
+        return _dev_batch_ranges(lib().mh_dev_decode_batch_ranges, self._h, payload, pay_off, nbits, lookups, prev0, sym_off, index,
+                                 chunk_symbols, out_cap)
+
+    def decompress_batch_ranges(self, blobs, lookups, indices=None, chunk_symbols=0, lengths=None):
+        """Lookups into whole `.cm` files of this model (decompress_batch's inputs): (list of bytes, status per lookup)."""
+        l = lib()
+        payloads, nbits = [], []
+        for b in blobs:
+            a = _u8(b)
+            if a.size < 1:
+                raise MhError(MH_ERR_CORRUPT, "decompress_batch_ranges")
+            nb = C.c_uint64(0)
+            _check(l.mh_stream_parse_header(self._h, int(a[0]), a.size, C.byref(nb)), "mh_stream_parse_header")
+            payloads.append(a[1:].tobytes())
+            nbits.append(nb.value)
+        payload, pay_off = batch_offsets(payloads)
+        sym_off = _offsets(lengths) if lengths is not None else None
+        index = None
+        if indices is not None:
+            if lengths is None:
+                raise ValueError("decompress_batch_ranges with indices needs the original lengths")
+            index = _batch_index(indices, sym_off, chunk_symbols)
+        return self.decode_batch_ranges(payload, pay_off, np.array(nbits, dtype=np.uint64), lookups, PREV0, sym_off, index, chunk_symbols)
 
     # ---- batches of independent streams (mh_encode_batch / mh_decode_batch) -------------------------------------------
     def encode_batch(self, messages, prev0=PREV0, chunk_symbols=None):
@@ -734,6 +881,12 @@ class ModelSet:
         return out[:min(int(so[n]), cap)].tobytes(), so, d_st.download(np.int32)[:n], rc
 
 
+    def decode_ranges(self, payload, pay_off, nbits, lookups, prev0=PREV0, sym_off=None, index=None, chunk_symbols=0, out_cap=None):
+        """One mh_dev_decode_each_ranges call with guard bytes around every output: (list of bytes, status per lookup,
+        mh_dev_status)."""
+        return _dev_batch_ranges(lib().mh_dev_decode_each_ranges, self._h, payload, pay_off, nbits, lookups, prev0, sym_off, index,
+                                 chunk_symbols, out_cap)
+
 def compress_each(messages, order=1, chunk_symbols=None, prev0=PREV0):
     """[(table bytes, header + payload, nbits, index slice or None)] per message: the `.e`/`.eh` table and `.cm`/`.ch` file the
     reference writes for that message alone (mh_compress_each)."""
@@ -801,3 +954,52 @@ def decompress_each(tables, blobs, indices=None, chunk_symbols=0, lengths=None, 
         raise MhError(rc, "mh_decompress_each")
     msgs = [out[int(sym_off[i]):int(sym_off[i + 1])].tobytes() for i in range(n)]
     return msgs if check else (msgs, st[:n])
+
+
+def _batch_index(indices, sym_off, chunk_symbols):
+    """The batch index of per-stream slices (compress_batch / compress_each), at mh_batch_index_base."""
+    l = lib()
+    n = len(indices)
+    idx = np.zeros(max(l.mh_batch_index_capacity(int(sym_off[n]), n, chunk_symbols), 1), dtype=np.uint64)
+    for i, sl in enumerate(indices):
+        b = l.mh_batch_index_base(int(sym_off[i]), i, chunk_symbols)
+        idx[b:b + len(sl)] = sl
+    return idx
+
+
+def decompress_each_ranges(tables, blobs, lookups, indices=None, chunk_symbols=0, lengths=None, prev0=PREV0):
+    """Lookups (stream, begin, end) into messages given as their table files and whole `.cm` / `.ch` files (decompress_each's
+    inputs), through mh_decompress_each_ranges: only the touched streams' tables are parsed and only their payloads uploaded.
+    Returns (list of byte strings, int32 status per lookup)."""
+    tables = [bytes(t) for t in tables]
+    payloads, nbits = [], []
+    for t, b in zip(tables, blobs):
+        nbits.append(parse_stream_header(table_order(t), b))
+        payloads.append(bytes(b)[1:])
+    tab, tab_off = batch_offsets(tables)
+    payload, pay_off = batch_offsets(payloads)
+    return _each_ranges(tab, tab_off, payload, pay_off, np.array(nbits, dtype=np.uint64), lookups, indices, chunk_symbols, lengths, prev0)
+
+
+def _each_ranges(tab, tab_off, payload, pay_off, nbits, lookups, indices=None, chunk_symbols=0, lengths=None, prev0=PREV0, index=None):
+    """mh_decompress_each_ranges on packed inputs (tables + tab_off, payloads + pay_off, nbits); the index either as per-stream
+    slices (indices) or as the batch index itself (index)."""
+    tab, payload = _u8(tab), _u8(payload)
+    tab_off = np.ascontiguousarray(tab_off, dtype=np.uint64)
+    pay_off = np.ascontiguousarray(pay_off, dtype=np.uint64)
+    nbits = np.ascontiguousarray(nbits, dtype=np.uint64)
+    n = len(pay_off) - 1
+    sym_off = _offsets(lengths) if lengths is not None else None
+    if indices is not None:
+        if lengths is None:
+            raise ValueError("decompress_each_ranges with indices needs the original lengths")
+        index = _batch_index(indices, sym_off, chunk_symbols)
+    if index is not None:
+        index = np.ascontiguousarray(index, dtype=np.uint64)
+    lk = _lookups(lookups)
+    m = lk.shape[0]
+    call = lambda out, cap, oo, st: lib().mh_decompress_each_ranges(
+        _ptr(tab), tab.size, tab_off.ctypes.data, _ptr(payload), payload.size, pay_off.ctypes.data, nbits.ctypes.data if n else None, n,
+        prev0, sym_off.ctypes.data if sym_off is not None else None, index.ctypes.data if index is not None else None,
+        chunk_symbols, lk.ctypes.data if m else None, m, out, cap, oo, st)
+    return _host_batch_ranges(call, "mh_decompress_each_ranges", lk, nbits[:n], sym_off)

@@ -8,13 +8,6 @@
 
 using namespace mhapi;
 
-struct mh_model_set {
-    mhe::SetDev d{};
-    void *block = nullptr;
-    int max_len = 0, min_len = 0;
-    ~mh_model_set() { if (block) (void)hipFree(block); }
-};
-
 namespace {
 
 bool offsets_ok(const uint64_t *off, size_t n) {
@@ -166,6 +159,17 @@ struct HostSet {
         return MH_OK;
     }
 };
+
+}  // namespace
+
+// a table file parsed as mh_model_set_from_tables would parse it, without building anything on the device
+int mhapi::check_table(const uint8_t *t, size_t nb) {
+    HostSet h(1);
+    mh::ContextCoder cc;
+    return h.add_table(0, t, nb, cc);
+}
+
+namespace {
 
 uint64_t stream_pay_bound(uint64_t len) {             // a context of k >= 2 leaves has codes of at most min(64, k - 1) bits
     const uint64_t l = len > 1 ? std::min<uint64_t>(64, len - 1) : 1;

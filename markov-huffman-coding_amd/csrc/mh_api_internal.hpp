@@ -17,6 +17,7 @@
 #include <thread>
 #include <vector>
 
+#include "mh_each.h"
 #include "mh_kernels.h"
 #include "mh_model.hpp"
 
@@ -65,6 +66,14 @@ struct mh_model {
     uint32_t *d_tprim2 = nullptr, *d_tsec2 = nullptr;
     uint32_t o2_nslots = 0, o2_p = 0, o2_h = 0, o2_nsec = 0;
     bool o2_enc_ok = false, o2_dec_ok = false;
+};
+
+// one model per stream on the device (include/mh.h, "BATCHES OF STREAMS, ONE MODEL EACH"; built in mh_api_each.cpp)
+struct mh_model_set {
+    mhe::SetDev d{};
+    void *block = nullptr;
+    int max_len = 0, min_len = 0;
+    ~mh_model_set() { if (block) (void)hipFree(block); }
 };
 
 namespace mhapi {
@@ -177,5 +186,7 @@ size_t segment_bytes();
 int upload_model(mh_model *m);
 int ensure_mirror(const mh_model *cm);
 int finish_model(mh_model *m, mh_model **out);
+// mh_api_each.cpp: MH_OK when mh_model_set_from_tables accepts the table file t[nb] (host only), else its error
+int check_table(const uint8_t *t, size_t nb);
 
 }  // namespace mhapi

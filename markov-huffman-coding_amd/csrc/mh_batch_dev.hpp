@@ -1,5 +1,5 @@
 // mh_batch_dev.hpp — device code shared by the kernels of the two batch families: one shared model (mh_batch.hip) and one
-// model per stream (mh_each.hip), and by the byte-range decoder (mh_range.hip).  Closed-form unit and chunk numbering,
+// model per stream (mh_each.hip), and by the byte-range decoders (mh_range.hip, mh_batch_range.hip).  Closed-form unit and chunk numbering,
 // unaligned 16-byte loads, the segmented u64 scans, the bit writer with shared edge words and the tail word, the byte-exact
 // output of a decoding lane and the LDS loader of a shared model's decode tables.  Everything is in an unnamed namespace:
 // each kernel file gets its own copy.

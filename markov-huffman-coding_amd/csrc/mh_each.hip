@@ -1,6 +1,7 @@
 // mh_each.hip — batches of independent order-0/1 streams, each under its own model (include/mh.h, "BATCHES OF STREAMS, ONE
 // MODEL EACH"): the reference's default per-file flow (train, write the table, encode) for N messages in a fixed number of
-// launches.  Layouts: mh_each.h; shared device code: mh_batch_dev.hpp (units, scans, bit writer); the trees are built by
+// launches.  Layouts: mh_each.h; shared device code: mh_batch_dev.hpp (units, scans, bit writer), mh_each_dev.hpp (the
+// per-stream symbol decoder, shared with mh_batch_range.hip); the trees are built by
 // mh_tree.hip's tree_build_kernel over the live (stream, context) pairs, so the reference's tie-breaking has one copy.
 //   each_check_kernel       offsets non-decreasing, [0] == 0, [n] == total
 //   each_live_kernel        one wave per (stream, 1 KiB sub-step): the contexts the sub-step's symbols are coded in, OR-ed
@@ -18,6 +19,7 @@
 // except for one more tree_build_kernel launch per 4 M live contexts (TREE_SLICE).
 #include "mh_each.h"
 #include "mh_batch_dev.hpp"
+#include "mh_each_dev.hpp"
 #include "../../include/mh.h"
 
 namespace mhe {
@@ -416,36 +418,6 @@ __global__ __launch_bounds__(B_THREADS) void each_enc_emit_kernel(EncEachParams 
 __device__ __forceinline__ void stream_fail(const DecEachParams &p, int *status, uint64_t i, int mh_code, int dev_code) {
     p.stream_status[i] = mh_code;
     fail(status, dev_code);
-}
-
-// one symbol of stream i after prev: the 8-bit first level, then the walk tree for longer codes (<= 64 bits)
-__device__ __forceinline__ uint32_t decode_sym(const SetDev &s, const uint32_t *row, uint32_t ctx, const BitSrc &src, BitCursor &bc,
-                                               uint32_t &used, bool &bad) {
-    const uint32_t slot = row[ctx];
-    if (slot == NO_SLOT) { bad = true; return 0; }            // a context the model has no code for
-    bc.refill(src);
-    const uint32_t e = s.prim[size_t(slot) * 256u + uint32_t(bc.window() >> 56)];
-    if (e & mh::DEC16_LEAF) {
-        const uint32_t len = (e >> 8) & 31u;
-        bad |= (len == 0);
-        bc.drop(len); used += len;
-        return e & 255u;
-    }
-    bc.drop(8);
-    const uint32_t *tr = s.tree + size_t(slot) * 256u;
-    uint32_t node = e & 255u, nb = 8;
-    for (int guard = 0; guard < 56; ++guard) {
-        bc.refill(src);
-        const uint32_t bit = uint32_t(bc.window() >> 63);
-        bc.drop(1); ++nb;
-        const uint32_t pair = tr[node];
-        const uint32_t c = bit ? (pair >> 16) : (pair & 0xFFFFu);
-        if (c & mh::TREE_LEAF) { used += nb; return c & 255u; }
-        node = c & 255u;
-    }
-    bad = true;
-    used += nb;
-    return 0;
 }
 
 __global__ void each_dec_check_kernel(DecEachParams p, int *status, int *stop) {
