@@ -732,6 +732,76 @@ int mh_decompress_each_ranges(const uint8_t *tables, uint64_t tables_bytes, cons
 /* Diagnostic: payload bytes the calling thread's last mh_decode_batch_ranges / mh_decompress_each_ranges uploaded. */
 uint64_t mh_last_batch_range_upload_bytes(void);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * BANKS OF SHARED MODELS — the middle ground between one shared model (a table once, statistics that may not fit) and one
+ * model per stream (an exact fit, a table per message): K shared models, K <= MH_BANK_MAX, and each stream coded under the
+ * one that suits it best (the reference's "general-use Huffman tables stored in a shared manner", README.md:152-157).
+ * No new format: every bank entry is an ordinary order-0/1 table file (`.eh` / `.e`), every stream's `.cm` is what
+ * `markovhuffman msg -e bank_k.e -o msg.cm` writes, and the only side information is one entry number per stream.  Order 0
+ * and order 1; order 2 is refused with MH_ERR_ARG before anything is launched.  in_off, prev0, packed payloads and the
+ * closed-form index slices are those of the batch section above.
+ *
+ * A bank is an ordinary mh_model_set whose K "streams" are the shared models (mh_model_set_from_models,
+ * mh_model_set_from_tables with K table files, or mh_dev_bank_train); mh_dev_model_set_tables on a bank writes its K tables.
+ * --------------------------------------------------------------------------------------------------------------------- */
+#define MH_BANK_MAX 64
+#define MH_BANK_NONE 0xFFFFFFFFu
+
+/* Selection: for every stream i and entry k, nbits(i, k) = the sum of the code lengths of the stream's symbols, each in its
+ * context from prev0.  Entry k is eligible for stream i only when every (context, symbol) pair of the stream has a code in it
+ * (the reference's NDEBUG build would silently drop a symbol without one).  d_choice[i] = the eligible entry with the fewest
+ * bits, ties to the lowest k; MH_BANK_NONE when none is eligible (d_nbits[i] = UINT64_MAX then).  An empty stream costs 0
+ * under every entry: entry 0.  d_nbits (may be NULL) = nbits(i, choice[i]), the nbits mh_encode writes for the message under
+ * that entry.  The bank has 1 .. MH_BANK_MAX entries (else MH_ERR_ARG).  No allocation, no host synchronisation; bad
+ * offsets: MH_ERR_ARG through mh_dev_status(d_ws).  d_ws 16-byte aligned, at least mh_dev_bank_select_workspace bytes. */
+size_t mh_dev_bank_select_workspace(size_t n_entries, size_t n_streams, size_t total);
+int mh_dev_bank_select(const mh_model_set *bank, const uint8_t *d_data, const uint64_t *d_in_off, size_t n_streams, size_t total,
+                       uint8_t prev0, uint32_t *d_choice, uint64_t *d_nbits, void *d_ws, size_t ws_bytes, void *stream);
+
+/* The set view: a set of n_streams streams in which stream i's model is bank entry d_choice[i] (type, longest code and
+ * context -> slot row copied; the slots are the bank's, shared: about 1 KiB per stream).  mh_dev_encode_each,
+ * mh_dev_decode_each and mh_dev_decode_each_ranges take it as any set.  Allocates the view and synchronises `stream` once;
+ * a choice >= K (MH_BANK_NONE included): MH_ERR_ARG and no view.  The view keeps the bank's device memory alive: freeing the
+ * bank first is legal.  mh_model_set_size(view) = n_streams, mh_model_set_slots and mh_model_set_code_lens give the bank's
+ * values; mh_dev_model_set_tables(view) is MH_ERR_ARG (write the bank's tables instead). */
+int mh_dev_model_set_pick(const mh_model_set *bank, const uint32_t *d_choice, size_t n_streams, void *stream, mh_model_set **out);
+
+/* Training.  Seed: the shared model of all streams (mh_dev_histogram_o1_batch / _o0_batch + mh_dev_model_from_counts);
+ * streams stable-sorted by their bits per byte under it (compared exactly, nbits_i x len_j against nbits_j x len_i; an empty
+ * stream counts 0 bits per byte), ties by stream index, cut into min(K, n) groups of equal count.  Then up to max_iters
+ * (>= 1) iterations, stopping early when no choice changes: (1) one model per group, trained on the summed counts of its
+ * streams, each stream from prev0 (the streams are sorted by group and gathered, and the batch histogram runs over each
+ * group); (2) selection under the new models.  Result: the bank of the last (1), without the entries whose group held no
+ * symbol (K' <= K entries, at least 1), and the choices of the (2) that followed, numbered in that bank; *iters_run (may be
+ * NULL) = the iterations run.  Neither step can raise sum_i nbits_i: a Huffman code is optimal for its group's counts and a
+ * stream's old entry stays eligible.  Deterministic.  Allocates the bank and synchronises `stream` a number of times that
+ * depends on K and the iterations, not on n.  n_streams == 0 or total == 0: a bank of one empty model, choices 0.
+ * d_data 16-byte aligned or not; d_ws 16-byte aligned, at least mh_dev_bank_train_workspace bytes. */
+size_t mh_dev_bank_train_workspace(size_t n_streams, size_t total, uint32_t k);
+int mh_dev_bank_train(const uint8_t *d_data, const uint64_t *d_in_off, size_t n_streams, size_t total, int order, uint8_t prev0,
+                      uint32_t k, uint32_t max_iters, uint32_t *d_choice, int *iters_run, void *d_ws, size_t ws_bytes, void *stream,
+                      mh_model_set **bank);
+
+/* Host forms.  Offsets and choices are checked before a device is touched.
+ *   mh_bank_train: the device training on a host batch; choice[n] is written to host memory.
+ *   mh_encode_bank_bound: the exact worst case of the packed payloads, sum_i ceil(len_i x maxlen(choice_i) / 8) + n + 16
+ *     (0 for a null argument or a choice >= K).
+ *   mh_encode_bank: stream i under entry choice[i]: out_off[n + 1], nbits[n], payloads, and the index slices when index is not
+ *     NULL (mh_batch_index_capacity entries; gap entries keep their values).  A cap below what the payloads need:
+ *     MH_ERR_CAPACITY.  Device footprint: input + payloads + 1 KiB per stream + the index + mh_dev_encode_each_workspace.
+ *   mh_decode_bank: the inverse, in the style of mh_decode_batch (sym_off input with an index, output without;
+ *     stream_status may be NULL; returns the first stream's error).  Index-free streams over MH_BATCH_WALK_MAX_BITS are
+ *     decoded by mh_decode under their entry, parsed from the bank's table. */
+int mh_bank_train(const uint8_t *data, const uint64_t *in_off, size_t n_streams, int order, uint8_t prev0, uint32_t k,
+                  uint32_t max_iters, uint32_t *choice, int *iters_run, mh_model_set **bank);
+size_t mh_encode_bank_bound(const mh_model_set *bank, const uint32_t *choice, const uint64_t *in_off, size_t n_streams);
+int mh_encode_bank(const mh_model_set *bank, const uint8_t *data, const uint64_t *in_off, size_t n_streams, uint8_t prev0,
+                   const uint32_t *choice, uint8_t *out_payload, size_t cap, uint64_t *out_off, uint64_t *nbits, uint64_t *index,
+                   uint32_t chunk_symbols);
+int mh_decode_bank(const mh_model_set *bank, const uint32_t *choice, const uint8_t *payload, const uint64_t *pay_off,
+                   const uint64_t *nbits, size_t n_streams, uint8_t prev0, uint8_t *out, size_t out_cap, uint64_t *sym_off,
+                   const uint64_t *index, uint32_t chunk_symbols, int32_t *stream_status);
+
 #ifdef __cplusplus
 }
 #endif

@@ -50,7 +50,11 @@ EXPORTS = [
     "mh_dev_decode_ranges_workspace", "mh_dev_decode_ranges", "mh_decode_ranges", "mh_last_range_upload_bytes",
     "mh_dev_decode_batch_ranges_workspace", "mh_dev_decode_batch_ranges", "mh_dev_decode_each_ranges", "mh_decode_batch_ranges",
     "mh_decompress_each_ranges", "mh_last_batch_range_upload_bytes",
+    "mh_dev_bank_select_workspace", "mh_dev_bank_select", "mh_dev_model_set_pick", "mh_dev_bank_train_workspace", "mh_dev_bank_train",
+    "mh_bank_train", "mh_encode_bank_bound", "mh_encode_bank", "mh_decode_bank",
 ]
+BANK_MAX = 64                              # include/mh.h MH_BANK_MAX
+BANK_NONE = 0xFFFFFFFF                     # include/mh.h MH_BANK_NONE
 BATCH_WALK_MAX_BITS = 1 << 23              # include/mh.h MH_BATCH_WALK_MAX_BITS
 
 
@@ -207,6 +211,18 @@ def lib():
         l.mh_decompress_each_ranges.argtypes = [vp, u64, vp, vp, u64, vp, vp, sz, u8, vp, vp, u32, vp, sz, vp, sz, vp, vp]
         l.mh_last_batch_range_upload_bytes.argtypes = []
         l.mh_last_batch_range_upload_bytes.restype = u64
+        l.mh_dev_bank_select_workspace.argtypes = [sz, sz, sz]
+        l.mh_dev_bank_select_workspace.restype = sz
+        l.mh_dev_bank_select.argtypes = [vp, vp, vp, sz, sz, u8, vp, vp, vp, sz, vp]
+        l.mh_dev_model_set_pick.argtypes = [vp, vp, sz, vp, C.POINTER(vp)]
+        l.mh_dev_bank_train_workspace.argtypes = [sz, sz, u32]
+        l.mh_dev_bank_train_workspace.restype = sz
+        l.mh_dev_bank_train.argtypes = [vp, vp, sz, sz, i32, u8, u32, u32, vp, pi, vp, sz, vp, C.POINTER(vp)]
+        l.mh_bank_train.argtypes = [vp, vp, sz, i32, u8, u32, u32, vp, pi, C.POINTER(vp)]
+        l.mh_encode_bank_bound.argtypes = [vp, vp, vp, sz]
+        l.mh_encode_bank_bound.restype = sz
+        l.mh_encode_bank.argtypes = [vp, vp, vp, sz, u8, vp, vp, sz, vp, vp, vp, u32]
+        l.mh_decode_bank.argtypes = [vp, vp, vp, vp, vp, sz, u8, vp, sz, vp, vp, u32, vp]
         _lib = l
     return _lib
 
@@ -886,6 +902,106 @@ class ModelSet:
         mh_dev_status)."""
         return _dev_batch_ranges(lib().mh_dev_decode_each_ranges, self._h, payload, pay_off, nbits, lookups, prev0, sym_off, index,
                                  chunk_symbols, out_cap)
+
+    # ---- banks of shared models (include/mh.h, "BANKS OF SHARED MODELS"): this set is the bank, its streams the entries ----
+    @classmethod
+    def train_bank(cls, messages, k, order=1, max_iters=8, prev0=PREV0, host=False):
+        """K shared models trained on the messages: (bank, choice uint32[n], iterations run).  host=False drives
+        mh_dev_bank_train on device buffers, host=True the host form mh_bank_train."""
+        data, off = batch_offsets(messages)
+        l = lib()
+        total, n = int(data.size), len(off) - 1
+        h, it = C.c_void_p(), C.c_int(0)
+        if host:
+            ch = np.zeros(max(n, 1), dtype=np.uint32)
+            _check(l.mh_bank_train(_ptr(data), off.ctypes.data, n, order, prev0, k, max_iters, ch.ctypes.data, C.byref(it), C.byref(h)),
+                   "mh_bank_train")
+            return cls(h), ch[:n], it.value
+        d_data = DeviceBuffer(max(total, 1), data if total else None)
+        d_off = DeviceBuffer(off.nbytes, off)
+        d_ch = DeviceBuffer(max(n, 1) * 4)
+        wsb = l.mh_dev_bank_train_workspace(n, total, k)
+        d_ws = DeviceBuffer(wsb)
+        _check(l.mh_dev_bank_train(d_data.ptr, d_off.ptr, n, total, order, prev0, k, max_iters, d_ch.ptr, C.byref(it), d_ws.ptr, wsb, None,
+                                   C.byref(h)), "mh_dev_bank_train")
+        return cls(h), d_ch.download(np.uint32)[:n], it.value
+
+    def select(self, messages, prev0=PREV0, in_off=None):
+        """mh_dev_bank_select with this set as the bank: (choice uint32[n], nbits uint64[n]).  messages: a list of byte strings,
+        or the concatenation with in_off (which may be malformed: the device status is then raised)."""
+        l = lib()
+        if in_off is None:
+            data, off = batch_offsets(messages)
+        else:
+            data, off = _u8(messages), np.ascontiguousarray(in_off, dtype=np.uint64)
+        total, n = int(data.size), len(off) - 1
+        d_data = DeviceBuffer(max(total, 1), data if total else None)
+        d_off = DeviceBuffer(off.nbytes, off)
+        d_ch, d_nb = DeviceBuffer(max(n, 1) * 4), DeviceBuffer(max(n, 1) * 8)
+        wsb = l.mh_dev_bank_select_workspace(len(self), n, total)
+        d_ws = DeviceBuffer(wsb)
+        _check(l.mh_dev_bank_select(self._h, d_data.ptr, d_off.ptr, n, total, prev0, d_ch.ptr, d_nb.ptr, d_ws.ptr, wsb, None), "mh_dev_bank_select")
+        _check(l.mh_dev_status(d_ws.ptr, None), "mh_dev_bank_select")
+        return d_ch.download(np.uint32)[:n], d_nb.download(np.uint64)[:n]
+
+    def pick(self, choice):
+        """mh_dev_model_set_pick: the set in which stream i is coded under this bank's entry choice[i]."""
+        ch = np.ascontiguousarray(choice, dtype=np.uint32)
+        d_ch = DeviceBuffer(max(ch.nbytes, 4), ch if ch.size else None)
+        h = C.c_void_p()
+        _check(lib().mh_dev_model_set_pick(self._h, d_ch.ptr, ch.size, None, C.byref(h)), "mh_dev_model_set_pick")
+        return ModelSet(h)
+
+
+def encode_bank_bound(bank, messages, choice):
+    _, off = batch_offsets(messages)
+    ch = np.ascontiguousarray(choice, dtype=np.uint32)
+    return lib().mh_encode_bank_bound(bank.handle, _ptr(ch), off.ctypes.data, len(off) - 1)
+
+
+def encode_bank(bank, messages, choice, chunk_symbols=None, prev0=PREV0):
+    """mh_encode_bank: (packed payloads, out_off[n + 1], nbits[n], index or None, in_off[n + 1]); stream i under bank entry choice[i]."""
+    data, off = batch_offsets(messages)
+    l = lib()
+    n, total = len(off) - 1, int(data.size)
+    ch = np.ascontiguousarray(choice, dtype=np.uint32)
+    cap = l.mh_encode_bank_bound(bank.handle, _ptr(ch), off.ctypes.data, n)
+    out = np.zeros(max(cap, 1), dtype=np.uint8)
+    out_off = np.zeros(n + 1, dtype=np.uint64)
+    nbits = np.zeros(max(n, 1), dtype=np.uint64)
+    idx = None
+    if chunk_symbols:
+        idx = np.zeros(max(l.mh_batch_index_capacity(total, n, chunk_symbols), 1), dtype=np.uint64)
+    _check(l.mh_encode_bank(bank.handle, _ptr(data), off.ctypes.data, n, prev0, _ptr(ch), out.ctypes.data, cap, out_off.ctypes.data,
+                            nbits.ctypes.data, idx.ctypes.data if idx is not None else None, chunk_symbols or 0), "mh_encode_bank")
+    return out[:int(out_off[n])], out_off, nbits[:n], idx, off
+
+
+def decode_bank(bank, choice, payload, pay_off, nbits, sym_off=None, index=None, chunk_symbols=0, out_cap=None, prev0=PREV0, check=True):
+    """mh_decode_bank: (output bytes, sym_off[n + 1], per-stream status[n]).  With an index, sym_off is the encode's in_off."""
+    l = lib()
+    payload = _u8(payload)
+    pay_off = np.ascontiguousarray(pay_off, dtype=np.uint64)
+    nbits = np.ascontiguousarray(nbits, dtype=np.uint64)
+    ch = np.ascontiguousarray(choice, dtype=np.uint32)
+    n = len(pay_off) - 1
+    if index is not None:
+        so = np.ascontiguousarray(sym_off, dtype=np.uint64).copy()
+        cap = int(so[n]) if out_cap is None else out_cap
+        index = np.ascontiguousarray(index, dtype=np.uint64)
+    else:
+        so = np.zeros(n + 1, dtype=np.uint64)
+        minl = max(bank.code_lens()[1], 1)
+        cap = int(sum(int(b) // minl for b in nbits)) if out_cap is None else out_cap
+    out = np.zeros(max(cap, 1), dtype=np.uint8)
+    st = np.zeros(max(n, 1), dtype=np.int32)
+    rc = l.mh_decode_bank(bank.handle, _ptr(ch), _ptr(payload), pay_off.ctypes.data, nbits.ctypes.data if n else None, n, prev0, out.ctypes.data,
+                          cap, so.ctypes.data, (index.ctypes.data if index.size else out.ctypes.data) if index is not None else None, chunk_symbols,
+                          st.ctypes.data)
+    if rc != MH_OK and (check or rc == MH_ERR_ARG or not st[:n].any()):
+        raise MhError(rc, "mh_decode_bank")
+    return out[:int(so[n])].tobytes(), so, st[:n]
+
 
 def compress_each(messages, order=1, chunk_symbols=None, prev0=PREV0):
     """[(table bytes, header + payload, nbits, index slice or None)] per message: the `.e`/`.eh` table and `.cm`/`.ch` file the

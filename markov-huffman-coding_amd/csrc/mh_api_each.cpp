@@ -24,9 +24,11 @@ hipError_t set_alloc(mh_model_set *s, uint64_t n, uint64_t nslots) {
     const size_t sizes[] = {n, 4 * n, 1024 * n, 8 * (n + 1), 4 * nslots, nslots, 2 * nslots, 256 * nslots, 2048 * nslots, 512 * nslots, 1024 * nslots};
     size_t off[11], total = 0;
     for (int k = 0; k < 11; ++k) { off[k] = total; total += al256(sizes[k]); }
-    hipError_t e = hipMalloc(&s->block, total ? total : 256);
-    if (e != hipSuccess) { s->block = nullptr; return e; }
-    unsigned char *b = static_cast<unsigned char *>(s->block);
+    void *p = nullptr;
+    hipError_t e = hipMalloc(&p, total ? total : 256);
+    if (e != hipSuccess) return e;
+    s->block.reset(p, [](void *q) { (void)hipFree(q); });
+    unsigned char *b = static_cast<unsigned char *>(p);
     s->d.n = n; s->d.nslots = nslots;
     s->d.type = b + off[0];
     s->d.maxlen = reinterpret_cast<uint32_t *>(b + off[1]);
@@ -293,7 +295,7 @@ size_t mh_model_set_tables_bound(const mh_model_set *s) {
 size_t mh_dev_model_set_tables_workspace(const mh_model_set *s) { return s ? mhe::tab_layout(s->d.n, s->d.nslots).total : 0; }
 
 int mh_dev_model_set_tables(const mh_model_set *s, uint8_t *d_out, size_t cap, uint64_t *d_tab_off, void *d_ws, size_t ws_bytes, void *stream) {
-    if (!s || (!d_out && cap) || !d_tab_off || !d_ws || !aligned16(d_out) || !aligned16(d_ws)) return MH_ERR_ARG;
+    if (!s || s->view || (!d_out && cap) || !d_tab_off || !d_ws || !aligned16(d_out) || !aligned16(d_ws)) return MH_ERR_ARG;
     if (ws_bytes < mh_dev_model_set_tables_workspace(s)) return MH_ERR_CAPACITY;
     if (!have_device()) return MH_ERR_NO_DEVICE;
     HIP_TRY(mhe::launch_tables(s->d, d_out, cap, reinterpret_cast<unsigned long long *>(d_tab_off), d_ws, static_cast<hipStream_t>(stream)));

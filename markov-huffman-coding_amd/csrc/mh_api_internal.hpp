@@ -12,6 +12,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <thread>
@@ -69,11 +70,14 @@ struct mh_model {
 };
 
 // one model per stream on the device (include/mh.h, "BATCHES OF STREAMS, ONE MODEL EACH"; built in mh_api_each.cpp)
+// A view (mh_dev_model_set_pick) owns only its stream rows (type, maxlen, ctx_slot) and shares the device block of its bank's
+// slots, so that freeing the bank first is legal; its slot_base / slot_stream are null (table writing refuses a view).
 struct mh_model_set {
     mhe::SetDev d{};
-    void *block = nullptr;
+    std::shared_ptr<void> block;     // the device block that holds the slots (a view: its bank's)
+    std::shared_ptr<void> rows;      // a view's own stream rows; empty for a set that owns its slots
     int max_len = 0, min_len = 0;
-    ~mh_model_set() { if (block) (void)hipFree(block); }
+    bool view = false;
 };
 
 namespace mhapi {
