@@ -802,6 +802,73 @@ int mh_decode_bank(const mh_model_set *bank, const uint32_t *choice, const uint8
                    const uint64_t *nbits, size_t n_streams, uint8_t prev0, uint8_t *out, size_t out_cap, uint64_t *sym_off,
                    const uint64_t *index, uint32_t chunk_symbols, int32_t *stream_status);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * SEGMENT STATES OF INDEX-FREE BATCHES — the batch counterpart of mh_dev_build_index: the `.cm` files the reference writes
+ * carry no index, and without one the batch decoders above walk each stream with one lane.  Three device steps for a batch
+ * of index-free streams under one shared model (mh_dev_batch_*) or a model set (mh_dev_each_*; a bank view of
+ * mh_dev_model_set_pick is a set): STATES, then INDEX and/or EMIT.  Order 0 and order 1; an order-2 model is MH_ERR_ARG
+ * before any launch.  Payload layout, prev0, nbits and the index layout are those of the batch sections above.
+ *   - states: every stream's payload is cut into 512-bit segments (segment k of stream i is number
+ *     pay_off[i] * 8 / 512 + i + k, so a workspace of mh_dev_batch_states_workspace(n, pay_total) bytes holds every one).
+ *     Each segment is decoded from a guessed entry state, a fixed number of repair launches decodes again the segments
+ *     whose entry differs from their predecessor's end, and one lane per stream walks what is still inconsistent.  A
+ *     check kernel then proves entry(k) == end(k - 1), entry(0) == (prev0, bit 0) and an end exactly at nbits_i
+ *     (src/coding.cpp:124,158) for every stream.  d_sym_off[n + 1] (written) is the exclusive scan of the decoded
+ *     lengths — what mh_dev_decode_batch writes index-free; the settled states stay in d_ws.
+ *   - index: the chunk-index slices (mh_batch_index_base(sym_off[i], i, chunk)) from the settled states, each equal to
+ *     the slice mh_dev_encode_batch / mh_dev_encode_each writes for that message; gap entries are left untouched.
+ *     index_cap below mh_batch_index_capacity(sym_off[n], n, chunk): MH_ERR_CAPACITY, nothing written.
+ *   - emit: every stream decoded to d_out[sym_off[i] ...) (16-byte aligned), byte for byte what mh_dev_decode_batch /
+ *     mh_dev_decode_each write index-free; a stream that does not fit out_cap is MH_ERR_CAPACITY and writes nothing.
+ *   - index and emit take the same batch arguments as the states call and the same d_ws, untouched in between: a workspace
+ *     that holds the states of another batch, model or stream count gives MH_ERR_ARG through mh_dev_status(d_ws).
+ *   - per-stream status d_stream_status[n] (may be NULL; the first error is kept): MH_ERR_ARG for nbits_i beyond its
+ *     payload bytes, or for a stream whose sequential fallback walk would exceed MH_BATCH_WALK_MAX_BITS (fixed-length
+ *     "lattice" codes, e.g. uniform bytes, never re-synchronise); MH_ERR_CORRUPT for a null table entry on the true path
+ *     or a stream that does not end exactly at nbits_i; MH_ERR_CAPACITY (emit).  A failed stream decodes to 0 symbols in
+ *     sym_off and never disturbs another stream.  mh_dev_status(d_ws): one of the errors.
+ *   - call-wide errors, found on the device, stop the call and give every stream's status that error, nothing else being
+ *     written: bad offsets (states) and a workspace without the states of this batch (index, emit) are MH_ERR_ARG, an
+ *     index_cap below the capacity is MH_ERR_CAPACITY.
+ *   - the fallback walk is refused by its span, not by the kind of code: it runs from a stream's first inconsistent
+ *     segment to past its last one, so a long stream with two far-apart unsettled spots after the repair launches is
+ *     refused (MH_ERR_ARG) like a lattice when that span exceeds MH_BATCH_WALK_MAX_BITS.
+ * No allocation, no host synchronisation, and a number of launches that does not depend on the data.  d_payload and d_ws
+ * 16-byte aligned.
+ * Host forms: the batch is uploaded, states and index run on the device, sym_off[n] is read once; a stream the device
+ * refuses goes through mh_dev_build_index on its own (its group maps handle lattices), so a valid batch is never refused.
+ * sym_off[n + 1] and stream_status[n] (may be NULL) are written; index (index_cap entries, at least
+ * mh_batch_index_capacity(sym_off[n], n, chunk), else MH_ERR_CAPACITY) gets the slices, gap entries keep their values.
+ * mh_index_each parses stream i's table file (bytes [tab_off[i], tab_off[i+1]) of `tables`) with
+ * mh_model_set_from_tables.  Offsets, nbits and the chunk size are checked before a device is touched; returns the first
+ * stream's error, if any.
+ * --------------------------------------------------------------------------------------------------------------------- */
+size_t mh_dev_batch_states_workspace(size_t n_streams, uint64_t pay_total);
+int mh_dev_batch_states(const mh_model *m, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits,
+                        size_t n_streams, uint64_t pay_total, uint8_t prev0, uint64_t *d_sym_off, int32_t *d_stream_status,
+                        void *d_ws, size_t ws_bytes, void *stream);
+int mh_dev_each_states(const mh_model_set *s, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits,
+                       size_t n_streams, uint64_t pay_total, uint8_t prev0, uint64_t *d_sym_off, int32_t *d_stream_status,
+                       void *d_ws, size_t ws_bytes, void *stream);
+int mh_dev_batch_index(const mh_model *m, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits,
+                       size_t n_streams, uint64_t pay_total, uint8_t prev0, uint64_t *d_index, uint64_t index_cap,
+                       uint32_t chunk_symbols, int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream);
+int mh_dev_each_index(const mh_model_set *s, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits,
+                      size_t n_streams, uint64_t pay_total, uint8_t prev0, uint64_t *d_index, uint64_t index_cap,
+                      uint32_t chunk_symbols, int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream);
+int mh_dev_batch_emit(const mh_model *m, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits,
+                      size_t n_streams, uint64_t pay_total, uint8_t prev0, uint8_t *d_out, uint64_t out_cap,
+                      int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream);
+int mh_dev_each_emit(const mh_model_set *s, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits,
+                     size_t n_streams, uint64_t pay_total, uint8_t prev0, uint8_t *d_out, uint64_t out_cap,
+                     int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream);
+int mh_index_batch(const mh_model *m, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits, size_t n_streams,
+                   uint8_t prev0, uint32_t chunk_symbols, uint64_t *sym_off, uint64_t *index, uint64_t index_cap,
+                   int32_t *stream_status);
+int mh_index_each(const uint8_t *tables, const uint64_t *tab_off, const uint8_t *payload, const uint64_t *pay_off,
+                  const uint64_t *nbits, size_t n_streams, uint8_t prev0, uint32_t chunk_symbols, uint64_t *sym_off,
+                  uint64_t *index, uint64_t index_cap, int32_t *stream_status);
+
 #ifdef __cplusplus
 }
 #endif

@@ -52,6 +52,8 @@ EXPORTS = [
     "mh_decompress_each_ranges", "mh_last_batch_range_upload_bytes",
     "mh_dev_bank_select_workspace", "mh_dev_bank_select", "mh_dev_model_set_pick", "mh_dev_bank_train_workspace", "mh_dev_bank_train",
     "mh_bank_train", "mh_encode_bank_bound", "mh_encode_bank", "mh_decode_bank",
+    "mh_dev_batch_states_workspace", "mh_dev_batch_states", "mh_dev_each_states", "mh_dev_batch_index", "mh_dev_each_index",
+    "mh_dev_batch_emit", "mh_dev_each_emit", "mh_index_batch", "mh_index_each",
 ]
 BANK_MAX = 64                              # include/mh.h MH_BANK_MAX
 BANK_NONE = 0xFFFFFFFF                     # include/mh.h MH_BANK_NONE
@@ -223,6 +225,16 @@ def lib():
         l.mh_encode_bank_bound.restype = sz
         l.mh_encode_bank.argtypes = [vp, vp, vp, sz, u8, vp, vp, sz, vp, vp, vp, u32]
         l.mh_decode_bank.argtypes = [vp, vp, vp, vp, vp, sz, u8, vp, sz, vp, vp, u32, vp]
+        l.mh_dev_batch_states_workspace.argtypes = [sz, u64]
+        l.mh_dev_batch_states_workspace.restype = sz
+        for fn in (l.mh_dev_batch_states, l.mh_dev_each_states):
+            fn.argtypes = [vp, vp, vp, vp, sz, u64, u8, vp, vp, vp, sz, vp]
+        for fn in (l.mh_dev_batch_index, l.mh_dev_each_index):
+            fn.argtypes = [vp, vp, vp, vp, sz, u64, u8, vp, u64, u32, vp, vp, sz, vp]
+        for fn in (l.mh_dev_batch_emit, l.mh_dev_each_emit):
+            fn.argtypes = [vp, vp, vp, vp, sz, u64, u8, vp, u64, vp, vp, sz, vp]
+        l.mh_index_batch.argtypes = [vp, vp, vp, vp, sz, u8, u32, vp, vp, u64, vp]
+        l.mh_index_each.argtypes = [vp, vp, vp, vp, vp, sz, u8, u32, vp, vp, u64, vp]
         _lib = l
     return _lib
 
@@ -695,6 +707,15 @@ class Model:
             raise MhError(rc, "mh_decode_batch")
         return out[:int(so[n])].tobytes(), so, st[:n]
 
+    def index_batch(self, payload, pay_off, nbits, chunk_symbols, prev0=PREV0):
+        """States + index of index-free payloads on the device: (sym_off[n + 1], index, per-stream status).  The outputs plug
+        into decode_batch(..., sym_off=..., index=...) and decode_batch_ranges."""
+        return _index_batch(self, payload, pay_off, nbits, chunk_symbols, prev0)
+
+    def decode_batch_segments(self, payload, pay_off, nbits, prev0=PREV0, out_cap=None):
+        """States + emit of index-free payloads on the device: (output bytes, sym_off[n + 1], per-stream status)."""
+        return _decode_batch_segments(self, payload, pay_off, nbits, prev0, out_cap)
+
     def decompress_batch(self, blobs, indices=None, chunk_symbols=0, lengths=None):
         """Whole `.cm` files in, original messages out.  With indices (one slice per blob, from compress_batch) the original
         lengths must be given too: the index does not record where a stream's last chunk ends."""
@@ -897,6 +918,14 @@ class ModelSet:
         return out[:min(int(so[n]), cap)].tobytes(), so, d_st.download(np.int32)[:n], rc
 
 
+    def index_batch(self, payload, pay_off, nbits, chunk_symbols, prev0=PREV0):
+        """States + index under the set (stream i under model i): (sym_off[n + 1], index, per-stream status)."""
+        return _index_batch(self, payload, pay_off, nbits, chunk_symbols, prev0)
+
+    def decode_batch_segments(self, payload, pay_off, nbits, prev0=PREV0, out_cap=None):
+        """States + emit under the set: (output bytes, sym_off[n + 1], per-stream status)."""
+        return _decode_batch_segments(self, payload, pay_off, nbits, prev0, out_cap)
+
     def decode_ranges(self, payload, pay_off, nbits, lookups, prev0=PREV0, sym_off=None, index=None, chunk_symbols=0, out_cap=None):
         """One mh_dev_decode_each_ranges call with guard bytes around every output: (list of bytes, status per lookup,
         mh_dev_status)."""
@@ -1070,6 +1099,126 @@ def decompress_each(tables, blobs, indices=None, chunk_symbols=0, lengths=None, 
         raise MhError(rc, "mh_decompress_each")
     msgs = [out[int(sym_off[i]):int(sym_off[i + 1])].tobytes() for i in range(n)]
     return msgs if check else (msgs, st[:n])
+
+
+
+# ---- segment states of index-free batches (include/mh.h, "SEGMENT STATES OF INDEX-FREE BATCHES") -------------------------
+class SegmentStates:
+    """mh_dev_batch_states / mh_dev_each_states on a batch of index-free payloads (model: a Model or a ModelSet), with the
+    batch and the workspace kept on the device for index() and emit().  Attributes: sym_off[n + 1], status[n] (per stream),
+    rc (mh_dev_status after the states)."""
+
+    def __init__(self, model, payload, pay_off, nbits, prev0=PREV0):
+        l = lib()
+        self.model = model
+        self.is_set = isinstance(model, ModelSet)
+        payload = _u8(payload)
+        self.pay_off = np.ascontiguousarray(pay_off, dtype=np.uint64)
+        nbits = np.ascontiguousarray(nbits, dtype=np.uint64)
+        self.n = n = len(self.pay_off) - 1
+        self.pay_total = int(self.pay_off[n])
+        self.prev0 = prev0
+        self.d_pl = DeviceBuffer(max(payload.size, 1) + 64, payload if payload.size else None)
+        self.d_po = DeviceBuffer(self.pay_off.nbytes, self.pay_off)
+        self.d_nb = DeviceBuffer(max(nbits.nbytes, 8), nbits if n else None)
+        self.d_so = DeviceBuffer((n + 1) * 8)
+        self.d_st = DeviceBuffer(max(n, 1) * 4)
+        self.wsb = l.mh_dev_batch_states_workspace(n, self.pay_total)
+        self.d_ws = DeviceBuffer(self.wsb)
+        fn = l.mh_dev_each_states if self.is_set else l.mh_dev_batch_states
+        _check(fn(model.handle, self.d_pl.ptr, self.d_po.ptr, self.d_nb.ptr, n, self.pay_total, prev0, self.d_so.ptr, self.d_st.ptr,
+                  self.d_ws.ptr, self.wsb, None), fn.__name__)
+        self.rc = l.mh_dev_status(self.d_ws.ptr, None)
+        self.sym_off = self.d_so.download(np.uint64)
+        self.status = self.d_st.download(np.int32)[:n]
+
+    def _args(self):
+        return (self.model.handle, self.d_pl.ptr, self.d_po.ptr, self.d_nb.ptr, self.n, self.pay_total, self.prev0)
+
+    def index(self, chunk_symbols, index_cap=None, init=None, guard=0, ws=None):
+        """(index[index_cap], per-stream status, device status).  init: the index's previous contents (gap entries keep
+        them); ws: another SegmentStates whose workspace is handed over instead of this one's."""
+        l = lib()
+        if index_cap is None:
+            index_cap = l.mh_batch_index_capacity(int(self.sym_off[self.n]), self.n, chunk_symbols)
+        buf = np.full(index_cap + guard, 0xA5A5A5A5A5A5A5A5, dtype=np.uint64) if init is None else np.concatenate(
+            [np.ascontiguousarray(init, dtype=np.uint64), np.full(guard, 0xA5A5A5A5A5A5A5A5, dtype=np.uint64)])
+        d_idx = DeviceBuffer(max(buf.nbytes, 8), buf if buf.size else None)
+        d_st = DeviceBuffer(max(self.n, 1) * 4)
+        w = ws if ws is not None else self
+        fn = l.mh_dev_each_index if self.is_set else l.mh_dev_batch_index
+        _check(fn(*self._args(), d_idx.ptr, index_cap, chunk_symbols, d_st.ptr, w.d_ws.ptr, w.wsb, None), fn.__name__)
+        rc = l.mh_dev_status(w.d_ws.ptr, None)
+        out = d_idx.download(np.uint64)[:buf.size]
+        if guard:
+            assert (out[index_cap:] == 0xA5A5A5A5A5A5A5A5).all(), "index entries written at or beyond index_cap"
+        return out[:index_cap], d_st.download(np.int32)[:self.n], rc
+
+    def emit(self, out_cap=None, guard=0, ws=None):
+        """(output bytes, per-stream status, device status): the decoded streams at out[sym_off[i] ...)."""
+        l = lib()
+        if out_cap is None:
+            out_cap = int(self.sym_off[self.n])
+        d_out = DeviceBuffer(max(out_cap + guard, 1), np.full(out_cap + guard, 0xA5, dtype=np.uint8) if guard else None)
+        d_st = DeviceBuffer(max(self.n, 1) * 4)
+        w = ws if ws is not None else self
+        fn = l.mh_dev_each_emit if self.is_set else l.mh_dev_batch_emit
+        _check(fn(*self._args(), d_out.ptr, out_cap, d_st.ptr, w.d_ws.ptr, w.wsb, None), fn.__name__)
+        rc = l.mh_dev_status(w.d_ws.ptr, None)
+        out = d_out.download()
+        if guard:
+            assert (out[out_cap:out_cap + guard] == 0xA5).all(), "bytes written at or beyond out_cap"
+        return out[:min(int(self.sym_off[self.n]), out_cap)].tobytes(), d_st.download(np.int32)[:self.n], rc
+
+
+def _index_batch(model, payload, pay_off, nbits, chunk_symbols, prev0):
+    st = SegmentStates(model, payload, pay_off, nbits, prev0)
+    idx, status, _ = st.index(chunk_symbols, init=np.zeros(lib().mh_batch_index_capacity(int(st.sym_off[st.n]), st.n, chunk_symbols),
+                                                         dtype=np.uint64))
+    return st.sym_off, idx, status
+
+
+def _decode_batch_segments(model, payload, pay_off, nbits, prev0, out_cap):
+    st = SegmentStates(model, payload, pay_off, nbits, prev0)
+    out, status, _ = st.emit(out_cap)
+    return out, st.sym_off, status
+
+
+def index_batch_host(model, payload, pay_off, nbits, chunk_symbols, prev0=PREV0, check=True):
+    """mh_index_batch: (sym_off[n + 1], index, per-stream status) of index-free payloads under one shared model; streams the
+    device refuses are indexed one by one."""
+    return _index_host(lambda *a: lib().mh_index_batch(model.handle, *a), payload, pay_off, nbits, chunk_symbols, prev0, check)
+
+
+def _index_host(call, payload, pay_off, nbits, chunk_symbols, prev0, check):
+    l = lib()
+    payload = _u8(payload)
+    pay_off = np.ascontiguousarray(pay_off, dtype=np.uint64)
+    nbits = np.ascontiguousarray(nbits, dtype=np.uint64)
+    n = len(pay_off) - 1
+    cap = l.mh_batch_index_capacity(int(sum(int(b) for b in nbits)), n, chunk_symbols)   # every code has at least one bit
+    so = np.zeros(n + 1, dtype=np.uint64)
+    idx = np.zeros(max(cap, 1), dtype=np.uint64)
+    st = np.zeros(max(n, 1), dtype=np.int32)
+    rc = call(_ptr(payload), pay_off.ctypes.data, nbits.ctypes.data if n else None, n, prev0, chunk_symbols, so.ctypes.data,
+              idx.ctypes.data, cap, st.ctypes.data)
+    if rc != MH_OK and (check or rc == MH_ERR_ARG or not st[:n].any()):
+        raise MhError(rc, "index (host form)")
+    return so, idx[:l.mh_batch_index_capacity(int(so[n]), n, chunk_symbols)], st[:n]
+
+
+def index_each(tables, blobs, chunk_symbols, prev0=PREV0, check=True):
+    """Table files and whole `.cm` / `.ch` files (what the reference writes) in: (sym_off[n + 1], index, per-stream status)
+    of the batch (mh_index_each).  sym_off and index plug into decompress_each / ModelSet.decode / decode_ranges."""
+    tables = [bytes(t) for t in tables]
+    payloads, nbits = [], []
+    for t, b in zip(tables, blobs):
+        nbits.append(parse_stream_header(table_order(t), b))
+        payloads.append(bytes(b)[1:])
+    tab, tab_off = batch_offsets(tables)
+    payload, pay_off = batch_offsets(payloads)
+    call = lambda *a: lib().mh_index_each(_ptr(tab), tab_off.ctypes.data, *a)
+    return _index_host(call, payload, pay_off, np.array(nbits, dtype=np.uint64), chunk_symbols, prev0, check)
 
 
 def _batch_index(indices, sym_off, chunk_symbols):
