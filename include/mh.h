@@ -543,6 +543,47 @@ int mh_decode_batch(const mh_model *m, const uint8_t *payload, const uint64_t *p
                     int32_t *stream_status);
 
 /* ---------------------------------------------------------------------------------------------------------------------
+ * BATCHES OF ORDER-2 STREAMS — the batch section above for ONE shared order-2 model (extension, parity unpinned): the
+ * 65 536-context table is written once for the whole corpus, and every message gets the order-2 payload.  The calls of that
+ * section keep refusing an order-2 model; these refuse any other (MH_ERR_ARG).  Everything not said here is word for word
+ * the section above: in_off[n + 1] and its checks (host calls on the host, device calls through mh_dev_status(d_ws)),
+ * packed byte-aligned payloads with out_off[n + 1], nbits[n], index slices at mh_batch_index_base(in_off[i], i, chunk),
+ * MH_BATCH_WALK_MAX_BITS, d_stream_status, the host forms' footprints.
+ *   - Every stream starts in context (prev0, prev0), as mh_encode starts an order-2 stream: stream i's
+ *     mh_stream_header(m, nbits_i) followed by its payload is what mh_encode writes for that message alone — including the
+ *     skip rule for a pair without a code (the symbol is skipped, the context still advances).
+ *   - Index entries are order-2 entries: (two context bytes) << 48 | bit offset relative to the stream's own payload, equal
+ *     to mh_encode's index of that message.
+ *   - mh_encode_batch_bound serves this family too (it works from the model's longest code).
+ * --------------------------------------------------------------------------------------------------------------------- */
+/* Training histogram of a shared order-2 model: the summed 1 << 24 order-2 counts of all streams, stream i's first symbol
+ * counted in context (prev0, prev0), its second in (prev0, its first byte).  d_ws: at least
+ * mh_dev_histogram_o2_batch_workspace(total) bytes, 256-byte aligned; its status word carries MH_ERR_ARG for bad offsets
+ * and the order-2 conservation check (the counts add up to total).  Needs no model. */
+size_t mh_dev_histogram_o2_batch_workspace(size_t total);
+int mh_dev_histogram_o2_batch(const uint8_t *d_data, const uint64_t *d_in_off, size_t n_streams, size_t total, uint8_t prev0,
+                              uint64_t *d_counts /* 1 << 24 */, void *d_ws, size_t ws_bytes, void *stream);
+/* mh_dev_encode_batch for an order-2 model (arguments, outputs and capacity rule alike). */
+size_t mh_dev_encode_batch_o2_workspace(size_t n_streams, size_t total);
+int mh_dev_encode_batch_o2(const mh_model *m, const uint8_t *d_data, const uint64_t *d_in_off, size_t n_streams, size_t total,
+                           uint8_t prev0, uint8_t *d_payload, size_t cap, uint64_t *d_out_off, uint64_t *d_nbits,
+                           uint64_t *d_index, uint32_t chunk_symbols, void *d_ws, size_t ws_bytes, void *stream);
+/* mh_dev_decode_batch for an order-2 model: indexed (every chunk must end exactly at the next entry) or index-free (count
+ * pass, scan, emit pass; a stream must end exactly at nbits_i; streams over MH_BATCH_WALK_MAX_BITS get MH_ERR_ARG). */
+size_t mh_dev_decode_batch_o2_workspace(size_t n_streams);
+int mh_dev_decode_batch_o2(const mh_model *m, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits,
+                           size_t n_streams, uint64_t pay_total, uint8_t prev0, uint8_t *d_out, uint64_t out_cap,
+                           uint64_t *d_sym_off, uint64_t sym_total, const uint64_t *d_index, uint32_t chunk_symbols,
+                           int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream);
+/* Host-buffer forms, as mh_encode_batch / mh_decode_batch: streams over the walk cap are decoded by mh_decode by themselves,
+ * so a valid batch is never refused. */
+int mh_encode_batch_o2(const mh_model *m, const uint8_t *data, const uint64_t *in_off, size_t n_streams, uint8_t prev0,
+                       uint8_t *out_payload, size_t cap, uint64_t *out_off, uint64_t *nbits, uint64_t *index, uint32_t chunk_symbols);
+int mh_decode_batch_o2(const mh_model *m, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits, size_t n_streams,
+                       uint8_t prev0, uint8_t *out, size_t out_cap, uint64_t *sym_off, const uint64_t *index, uint32_t chunk_symbols,
+                       int32_t *stream_status);
+
+/* ---------------------------------------------------------------------------------------------------------------------
  * BATCHES OF STREAMS, ONE MODEL EACH — the reference's default per-file flow (`markovhuffman f -o f.cm -d f.e`: train a
  * model on the file, write its table next to its payload) for many messages at once.  Order 0 and order 1; order 2 is
  * refused with MH_ERR_ARG.  Stream i, in_off, prev0, payload packing and the chunk-index slices are exactly as in the

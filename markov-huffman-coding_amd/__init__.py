@@ -54,6 +54,8 @@ EXPORTS = [
     "mh_bank_train", "mh_encode_bank_bound", "mh_encode_bank", "mh_decode_bank",
     "mh_dev_batch_states_workspace", "mh_dev_batch_states", "mh_dev_each_states", "mh_dev_batch_index", "mh_dev_each_index",
     "mh_dev_batch_emit", "mh_dev_each_emit", "mh_index_batch", "mh_index_each",
+    "mh_dev_histogram_o2_batch_workspace", "mh_dev_histogram_o2_batch", "mh_dev_encode_batch_o2_workspace", "mh_dev_encode_batch_o2",
+    "mh_dev_decode_batch_o2_workspace", "mh_dev_decode_batch_o2", "mh_encode_batch_o2", "mh_decode_batch_o2",
 ]
 BANK_MAX = 64                              # include/mh.h MH_BANK_MAX
 BANK_NONE = 0xFFFFFFFF                     # include/mh.h MH_BANK_NONE
@@ -170,6 +172,17 @@ def lib():
         l.mh_dev_decode_batch.argtypes = [vp, vp, vp, vp, sz, u64, u8, vp, u64, vp, u64, vp, u32, vp, vp, sz, vp]
         l.mh_encode_batch.argtypes = [vp, vp, vp, sz, u8, vp, sz, vp, vp, vp, u32]
         l.mh_decode_batch.argtypes = [vp, vp, vp, vp, sz, u8, vp, sz, vp, vp, u32, vp]
+        l.mh_dev_histogram_o2_batch_workspace.argtypes = [sz]
+        l.mh_dev_histogram_o2_batch_workspace.restype = sz
+        l.mh_dev_histogram_o2_batch.argtypes = [vp, vp, sz, sz, u8, vp, vp, sz, vp]
+        l.mh_dev_encode_batch_o2_workspace.argtypes = [sz, sz]
+        l.mh_dev_encode_batch_o2_workspace.restype = sz
+        l.mh_dev_encode_batch_o2.argtypes = l.mh_dev_encode_batch.argtypes
+        l.mh_dev_decode_batch_o2_workspace.argtypes = [sz]
+        l.mh_dev_decode_batch_o2_workspace.restype = sz
+        l.mh_dev_decode_batch_o2.argtypes = l.mh_dev_decode_batch.argtypes
+        l.mh_encode_batch_o2.argtypes = l.mh_encode_batch.argtypes
+        l.mh_decode_batch_o2.argtypes = l.mh_decode_batch.argtypes
         l.mh_dev_model_set_train_workspace.argtypes = [sz]
         l.mh_dev_model_set_train_workspace.restype = sz
         l.mh_dev_model_set_train.argtypes = [vp, vp, sz, sz, i32, u8, vp, sz, vp, C.POINTER(vp)]
@@ -328,6 +341,22 @@ def histogram_o1_batch(messages, prev0=PREV0, order=1):
     else:
         _check(l.mh_dev_histogram_o0_batch(d_data.ptr, d_off.ptr, n, total, d_counts.ptr, d_ws.ptr, wsb, None), "mh_dev_histogram_o0_batch")
     _check(l.mh_dev_status(d_ws.ptr, None), "mh_dev_histogram_batch")
+    return d_counts.download(np.uint64)
+
+
+def histogram_o2_batch(messages, prev0=PREV0):
+    """Summed order-2 histogram of independent messages, each starting in context (prev0, prev0) (mh_dev_histogram_o2_batch):
+    the training counts of a shared order-2 model, counts[ctx * 256 + sym] (extension, parity unpinned)."""
+    data, off = batch_offsets(messages)
+    l = lib()
+    total, n = int(data.size), len(off) - 1
+    d_data = DeviceBuffer(max(total, 1), data if total else None)
+    d_off = DeviceBuffer(off.nbytes, off)
+    d_counts = DeviceBuffer((1 << 24) * 8)
+    wsb = l.mh_dev_histogram_o2_batch_workspace(total)
+    d_ws = DeviceBuffer(wsb)
+    _check(l.mh_dev_histogram_o2_batch(d_data.ptr, d_off.ptr, n, total, prev0, d_counts.ptr, d_ws.ptr, wsb, None), "mh_dev_histogram_o2_batch")
+    _check(l.mh_dev_status(d_ws.ptr, None), "mh_dev_histogram_o2_batch")
     return d_counts.download(np.uint64)
 
 
@@ -652,6 +681,9 @@ class Model:
     # ---- batches of independent streams (mh_encode_batch / mh_decode_batch) -------------------------------------------
     def encode_batch(self, messages, prev0=PREV0, chunk_symbols=None):
         """(packed payloads, out_off[n + 1], nbits[n], index or None, in_off[n + 1]) of one mh_encode_batch call."""
+        return self._encode_batch(messages, prev0, chunk_symbols, "mh_encode_batch")
+
+    def _encode_batch(self, messages, prev0, chunk_symbols, fn):
         data, off = batch_offsets(messages)
         l = lib()
         n, total = len(off) - 1, int(data.size)
@@ -662,14 +694,17 @@ class Model:
         idx = None
         if chunk_symbols:
             idx = np.zeros(max(l.mh_batch_index_capacity(total, n, chunk_symbols), 1), dtype=np.uint64)
-        _check(l.mh_encode_batch(self._h, _ptr(data), off.ctypes.data, n, prev0, out.ctypes.data, cap, out_off.ctypes.data,
-                                 nbits.ctypes.data, idx.ctypes.data if idx is not None else None, chunk_symbols or 0), "mh_encode_batch")
+        _check(getattr(l, fn)(self._h, _ptr(data), off.ctypes.data, n, prev0, out.ctypes.data, cap, out_off.ctypes.data,
+                              nbits.ctypes.data, idx.ctypes.data if idx is not None else None, chunk_symbols or 0), fn)
         return out[:int(out_off[n])], out_off, nbits[:n], idx, off
 
     def compress_batch(self, messages, chunk_symbols=None):
         """[(header + payload, nbits, index slice or None)] per message: each blob is the `.cm` file of that message alone."""
+        return self._compress_batch(messages, chunk_symbols, self.encode_batch)
+
+    def _compress_batch(self, messages, chunk_symbols, encode):
         messages = [bytes(m) for m in messages]
-        payload, out_off, nbits, idx, off = self.encode_batch(messages, PREV0, chunk_symbols)
+        payload, out_off, nbits, idx, off = encode(messages, PREV0, chunk_symbols)
         l = lib()
         res = []
         for i, m in enumerate(messages):
@@ -685,6 +720,9 @@ class Model:
     def decode_batch(self, payload, pay_off, nbits, prev0=PREV0, sym_off=None, index=None, chunk_symbols=0, out_cap=None, check=True):
         """mh_decode_batch: (output bytes, sym_off[n + 1], per-stream status[n]).  With an index, sym_off is the encode's in_off.
         check=False returns the per-stream statuses of a batch with failed streams instead of raising."""
+        return self._decode_batch(payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols, out_cap, check, "mh_decode_batch")
+
+    def _decode_batch(self, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols, out_cap, check, fn):
         l = lib()
         payload = _u8(payload)
         pay_off = np.ascontiguousarray(pay_off, dtype=np.uint64)
@@ -700,11 +738,11 @@ class Model:
             cap = int(sum(int(b) // minl for b in nbits)) if out_cap is None else out_cap
         out = np.zeros(max(cap, 1), dtype=np.uint8)
         st = np.zeros(max(n, 1), dtype=np.int32)
-        rc = l.mh_decode_batch(self._h, _ptr(payload), pay_off.ctypes.data, nbits.ctypes.data if n else None, n, prev0, out.ctypes.data, cap,
-                               so.ctypes.data, index.ctypes.data if index is not None and index.size else (out.ctypes.data if index is not None else None),
-                               chunk_symbols, st.ctypes.data)
+        rc = getattr(l, fn)(self._h, _ptr(payload), pay_off.ctypes.data, nbits.ctypes.data if n else None, n, prev0, out.ctypes.data, cap,
+                            so.ctypes.data, index.ctypes.data if index is not None and index.size else (out.ctypes.data if index is not None else None),
+                            chunk_symbols, st.ctypes.data)
         if rc != MH_OK and (check or rc == MH_ERR_ARG or not st[:n].any()):
-            raise MhError(rc, "mh_decode_batch")
+            raise MhError(rc, fn)
         return out[:int(so[n])].tobytes(), so, st[:n]
 
     def index_batch(self, payload, pay_off, nbits, chunk_symbols, prev0=PREV0):
@@ -719,6 +757,9 @@ class Model:
     def decompress_batch(self, blobs, indices=None, chunk_symbols=0, lengths=None):
         """Whole `.cm` files in, original messages out.  With indices (one slice per blob, from compress_batch) the original
         lengths must be given too: the index does not record where a stream's last chunk ends."""
+        return self._decompress_batch(blobs, indices, chunk_symbols, lengths, self.decode_batch)
+
+    def _decompress_batch(self, blobs, indices, chunk_symbols, lengths, decode):
         l = lib()
         payloads, nbits = [], []
         for b in blobs:
@@ -741,8 +782,25 @@ class Model:
             for i, sl in enumerate(indices):
                 b = l.mh_batch_index_base(int(sym_off[i]), i, chunk_symbols)
                 index[b:b + len(sl)] = sl
-        out, so, _ = self.decode_batch(payload, pay_off, np.array(nbits, dtype=np.uint64), PREV0, sym_off, index, chunk_symbols)
+        out, so, _ = decode(payload, pay_off, np.array(nbits, dtype=np.uint64), PREV0, sym_off, index, chunk_symbols)
         return [out[int(so[i]):int(so[i + 1])] for i in range(len(blobs))]
+
+    # ---- batches of order-2 streams (mh_encode_batch_o2 / mh_decode_batch_o2; extension, parity unpinned) ---------------
+    def encode_batch_o2(self, messages, prev0=PREV0, chunk_symbols=None):
+        """encode_batch for an order-2 model: one mh_encode_batch_o2 call (index entries carry two context bytes)."""
+        return self._encode_batch(messages, prev0, chunk_symbols, "mh_encode_batch_o2")
+
+    def compress_batch_o2(self, messages, chunk_symbols=None):
+        """compress_batch for an order-2 model: each blob is what compress gives for that message alone."""
+        return self._compress_batch(messages, chunk_symbols, self.encode_batch_o2)
+
+    def decode_batch_o2(self, payload, pay_off, nbits, prev0=PREV0, sym_off=None, index=None, chunk_symbols=0, out_cap=None, check=True):
+        """decode_batch for an order-2 model (mh_decode_batch_o2)."""
+        return self._decode_batch(payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols, out_cap, check, "mh_decode_batch_o2")
+
+    def decompress_batch_o2(self, blobs, indices=None, chunk_symbols=0, lengths=None):
+        """decompress_batch for an order-2 model."""
+        return self._decompress_batch(blobs, indices, chunk_symbols, lengths, self.decode_batch_o2)
 
 
 # ---- batches of streams, one model each (include/mh.h, "BATCHES OF STREAMS, ONE MODEL EACH") ----------------------------

@@ -121,11 +121,16 @@ int mh_dev_decode_batch(const mh_model *m, const uint8_t *d_payload, const uint6
     return MH_OK;
 }
 
+}  // extern "C"
+
 /* ------------------------------------------------------- host-buffer calls */
 
-int mh_encode_batch(const mh_model *m, const uint8_t *data, const uint64_t *in_off, size_t n_streams, uint8_t prev0,
-                    uint8_t *out_payload, size_t cap, uint64_t *out_off, uint64_t *nbits, uint64_t *index, uint32_t chunk_symbols) {
-    if (!order01(m) || !in_off || !out_off || (!nbits && n_streams) || (!out_payload && cap)) return MH_ERR_ARG;
+// The host-buffer bodies, shared with the order-2 batch calls (mh_api_batch_o2.cpp): `dev` is the device call of the family,
+// the caller has checked the model's order.
+int mhapi::encode_batch_host(const mh_model *m, const uint8_t *data, const uint64_t *in_off, size_t n_streams, uint8_t prev0,
+                             uint8_t *out_payload, size_t cap, uint64_t *out_off, uint64_t *nbits, uint64_t *index, uint32_t chunk_symbols,
+                             DevEncodeBatchFn dev) {
+    if (!m || !in_off || !out_off || (!nbits && n_streams) || (!out_payload && cap)) return MH_ERR_ARG;
     if (index && chunk_shift_of(chunk_symbols) < 0) return MH_ERR_ARG;
     if (!offsets_ok(in_off, n_streams)) return MH_ERR_ARG;
     const size_t total = size_t(in_off[n_streams]);
@@ -148,8 +153,8 @@ int mh_encode_batch(const mh_model *m, const uint8_t *data, const uint64_t *in_o
     if (total) HIP_TRY(stage_h2d(d_data.p, data, total, st));
     HIP_TRY(hipMemcpy(d_in.p, in_off, (n_streams + 1) * 8, hipMemcpyHostToDevice));
     if (nidx) HIP_TRY(hipMemcpy(d_idx.p, index, nidx * 8, hipMemcpyHostToDevice));   // gap entries stay what the caller had
-    int rc = mh_dev_encode_batch(m, d_data.as<uint8_t>(), d_in.as<uint64_t>(), n_streams, total, prev0, d_out.as<uint8_t>(), dcap,
-                                 d_oo.as<uint64_t>(), d_nb.as<uint64_t>(), index ? d_idx.as<uint64_t>() : nullptr, chunk_symbols, d_ws.p, wsb, st);
+    int rc = dev(m, d_data.as<uint8_t>(), d_in.as<uint64_t>(), n_streams, total, prev0, d_out.as<uint8_t>(), dcap,
+                 d_oo.as<uint64_t>(), d_nb.as<uint64_t>(), index ? d_idx.as<uint64_t>() : nullptr, chunk_symbols, d_ws.p, wsb, st);
     if (rc == MH_OK) rc = mh_dev_status(d_ws.p, st);
     if (rc != MH_OK) return rc;
     HIP_TRY(hipMemcpy(out_off, d_oo.p, (n_streams + 1) * 8, hipMemcpyDeviceToHost));
@@ -168,9 +173,10 @@ uint8_t *grow_out(void *ctx, size_t n) {
 }
 }  // namespace
 
-int mh_decode_batch(const mh_model *m, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits, size_t n_streams, uint8_t prev0,
-                    uint8_t *out, size_t out_cap, uint64_t *sym_off, const uint64_t *index, uint32_t chunk_symbols, int32_t *stream_status) {
-    if (!order01(m) || !pay_off || (!nbits && n_streams) || !sym_off || (!out && out_cap)) return MH_ERR_ARG;
+int mhapi::decode_batch_host(const mh_model *m, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits, size_t n_streams,
+                             uint8_t prev0, uint8_t *out, size_t out_cap, uint64_t *sym_off, const uint64_t *index, uint32_t chunk_symbols,
+                             int32_t *stream_status, DevDecodeBatchFn dev) {
+    if (!m || !pay_off || (!nbits && n_streams) || !sym_off || (!out && out_cap)) return MH_ERR_ARG;
     if (index && chunk_shift_of(chunk_symbols) < 0) return MH_ERR_ARG;
     if (!offsets_ok(pay_off, n_streams)) return MH_ERR_ARG;
     const uint64_t pay_total = pay_off[n_streams];
@@ -216,9 +222,9 @@ int mh_decode_batch(const mh_model *m, const uint8_t *payload, const uint64_t *p
         HIP_TRY(hipMemcpy(d_so.p, sym_off, (n_streams + 1) * 8, hipMemcpyHostToDevice));
         if (nidx) HIP_TRY(hipMemcpy(d_idx.p, index, nidx * 8, hipMemcpyHostToDevice));
     }
-    int rc = mh_dev_decode_batch(m, d_pl.as<uint8_t>(), d_po.as<uint64_t>(), d_nb.as<uint64_t>(), n_streams, pay_total, prev0,
-                                 d_out.as<uint8_t>(), dcap, d_so.as<uint64_t>(), sym_total, index ? d_idx.as<uint64_t>() : nullptr,
-                                 chunk_symbols, d_st.as<int32_t>(), d_ws.p, wsb, st);
+    int rc = dev(m, d_pl.as<uint8_t>(), d_po.as<uint64_t>(), d_nb.as<uint64_t>(), n_streams, pay_total, prev0,
+                 d_out.as<uint8_t>(), dcap, d_so.as<uint64_t>(), sym_total, index ? d_idx.as<uint64_t>() : nullptr,
+                 chunk_symbols, d_st.as<int32_t>(), d_ws.p, wsb, st);
     if (rc != MH_OK) return rc;
     const int dev_rc = mh_dev_status(d_ws.p, st);
     std::vector<int32_t> sst(n_streams);
@@ -259,6 +265,21 @@ int mh_decode_batch(const mh_model *m, const uint8_t *payload, const uint64_t *p
     }
     sym_off[n_streams] = pos;
     return first;
+}
+
+extern "C" {
+
+int mh_encode_batch(const mh_model *m, const uint8_t *data, const uint64_t *in_off, size_t n_streams, uint8_t prev0,
+                    uint8_t *out_payload, size_t cap, uint64_t *out_off, uint64_t *nbits, uint64_t *index, uint32_t chunk_symbols) {
+    if (!order01(m)) return MH_ERR_ARG;
+    return encode_batch_host(m, data, in_off, n_streams, prev0, out_payload, cap, out_off, nbits, index, chunk_symbols, mh_dev_encode_batch);
+}
+
+int mh_decode_batch(const mh_model *m, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits, size_t n_streams, uint8_t prev0,
+                    uint8_t *out, size_t out_cap, uint64_t *sym_off, const uint64_t *index, uint32_t chunk_symbols, int32_t *stream_status) {
+    if (!order01(m)) return MH_ERR_ARG;
+    return decode_batch_host(m, payload, pay_off, nbits, n_streams, prev0, out, out_cap, sym_off, index, chunk_symbols, stream_status,
+                             mh_dev_decode_batch);
 }
 
 }  // extern "C"

@@ -190,6 +190,17 @@ size_t segment_bytes();
 int upload_model(mh_model *m);
 int ensure_mirror(const mh_model *cm);
 int finish_model(mh_model *m, mh_model **out);
+// mh_api_batch.cpp: the host-buffer forms of a batch family over its device encode / decode call (mh_encode_batch and
+// mh_decode_batch; mh_encode_batch_o2 and mh_decode_batch_o2).  The order check is the caller's.
+using DevEncodeBatchFn = int (*)(const mh_model *, const uint8_t *, const uint64_t *, size_t, size_t, uint8_t, uint8_t *, size_t, uint64_t *,
+                                 uint64_t *, uint64_t *, uint32_t, void *, size_t, void *);
+using DevDecodeBatchFn = int (*)(const mh_model *, const uint8_t *, const uint64_t *, const uint64_t *, size_t, uint64_t, uint8_t, uint8_t *,
+                                 uint64_t, uint64_t *, uint64_t, const uint64_t *, uint32_t, int32_t *, void *, size_t, void *);
+int encode_batch_host(const mh_model *m, const uint8_t *data, const uint64_t *in_off, size_t n_streams, uint8_t prev0, uint8_t *out_payload,
+                      size_t cap, uint64_t *out_off, uint64_t *nbits, uint64_t *index, uint32_t chunk_symbols, DevEncodeBatchFn dev);
+int decode_batch_host(const mh_model *m, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits, size_t n_streams, uint8_t prev0,
+                      uint8_t *out, size_t out_cap, uint64_t *sym_off, const uint64_t *index, uint32_t chunk_symbols, int32_t *stream_status,
+                      DevDecodeBatchFn dev);
 // mh_api_each.cpp: MH_OK when mh_model_set_from_tables accepts the table file t[nb] (host only), else its error
 int check_table(const uint8_t *t, size_t nb);
 
