@@ -418,13 +418,14 @@ int mh_dev_build_index_fine(const mh_model *m, const uint8_t *d_payload, uint64_
  *       until none is left (the fixed point of mh_dev_build_index), a prefix sum of the segments' symbol counts gives every
  *       segment its output offset; *d_n_symbols = the decoded size.  Synchronises `stream` between its passes.
  *       mh_dev_index_path(d_ws) afterwards: 6 = the workspace holds the states, mh_dev_decode_stream_emit may follow;
- *       0 = this model / stream does not take this path (an order-2 model, no tile tables, a code-length lattice, a code
- *       longer than the tile tables resolve, under a megabit, or segments that do not synchronise): build an index
+ *       0 = this model / stream does not take this path (an order-2 model, no tile tables, a code-length lattice, under a
+ *       megabit, or segments that do not synchronise): build an index
  *       (mh_dev_build_index_fine) and decode from it instead.
  *   mh_dev_decode_stream_emit    pass 2: every segment is decoded once more from its true state and its bytes are written
  *       to d_out[offset of its first symbol ...); nothing is written at or beyond out_cap (MH_ERR_CAPACITY via mh_dev_status).
  *       End state and count of every segment must come out as converged and the stream must end exactly at nbits
- *       (src/coding.cpp:124,158): MH_ERR_CORRUPT otherwise.  No allocation; synchronises `stream` once, before its launch (it
+ *       (src/coding.cpp:124,158): MH_ERR_CORRUPT otherwise.  Segments that hold a code longer than the tile tables resolve
+ *       take the path too: the emit pass walks them one lane each, the stream's last segment included.  No allocation; synchronises `stream` once, before its launch (it
  *       reads the workspace's path word: MH_ERR_ARG when the workspace does not hold the states of this stream).
  * Workspace for both: mh_dev_build_index_workspace(nbits), the same buffer, untouched in between.
  */
@@ -667,7 +668,8 @@ int mh_decompress_each(const uint8_t *tables, const uint64_t *tab_off, const uin
 /* ---------------------------------------------------------------------------------------------------------------------
  * RANDOM ACCESS: BYTE RANGES OF AN INDEXED STREAM — a few bytes out of a large stream (4 KiB at offset 9 GiB of a `.cm` with
  * its --index sidecar; records spread over a compressed log) without decoding or uploading the rest.  Order 0 and order 1
- * models; an order-2 model is refused with MH_ERR_ARG before anything is launched.
+ * models; an order-2 model is refused with MH_ERR_ARG before anything is launched, and so is n_symbols > nbits (every code
+ * has at least one bit: no stream of n_symbols fits in fewer bits).
  *   - A range is [begin, end) in symbols, i.e. bytes of the original input: 2 x uint64 per range.  Empty ranges (begin ==
  *     end, [n, n) included) are MH_OK and write nothing.  Ranges may overlap each other and come in any order.
  *   - The stream needs its chunk index (mh_encode, mh_dev_encode*, a batch stream's slice).  A stream without one (what the

@@ -830,7 +830,10 @@ __global__ __launch_bounds__(256) void segment_walk_emit_kernel(IdxParams p, uin
             ++k;
         }
         const uint64_t over = pos - seg_end;
-        if (bad || pos < seg_end || k != want || uint32_t(p.e16[i]) != ((prev << 8) | uint32_t(over > 254 ? 254 : over))) atomicExch(p.status, MHK_STATUS_CORRUPT);
+        // the stream's last segment must end exactly at nbits (src/coding.cpp:158): e16 of a walk segment was written by the
+        // repair pass with the same overshoot, so comparing with it alone lets a final code that runs past nbits through
+        if (bad || pos < seg_end || k != want || uint32_t(p.e16[i]) != ((prev << 8) | uint32_t(over > 254 ? 254 : over)) ||
+            (seg_end == p.nbits && pos != p.nbits)) atomicExch(p.status, MHK_STATUS_CORRUPT);
     }
 }
 

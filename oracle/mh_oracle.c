@@ -515,3 +515,34 @@ int64_t mho_decompress(const mho_model *m, const uint8_t *in, size_t n, uint8_t 
     }
     return nout;
 }
+
+/* ---------------------------------------------------------- strict span */
+
+int mho_decode_span(const mho_model *m, const uint8_t *payload, size_t payload_bytes,
+                    uint64_t bit0, uint64_t end_bit, unsigned ctx, uint64_t max_symbols,
+                    uint8_t *out, size_t cap, uint64_t *n_symbols, uint64_t *stop_bit) {
+    uint64_t pos = bit0, nout = 0;
+    int rc = MHO_OK;
+    unsigned prev = m->type == 2 ? (ctx & 0xFFFFu) : (ctx & 255u);
+    if (end_bit > (uint64_t)payload_bytes * 8 || bit0 > end_bit) { rc = MHO_ERR_ARG; goto done; }
+    while (nout < max_symbols && pos < end_bit) {
+        const table_t *t = ctx_table(m, (int)prev);
+        int node = t->root;
+        if (node < 0) { rc = MHO_ERR_CORRUPT; goto done; }          /* null entry: a context without a table */
+        while (t->is_internal[node]) {                              /* src/coding.cpp:129-149, from the root */
+            if (pos >= end_bit) { rc = MHO_ERR_CORRUPT; goto done; } /* the code runs past end_bit */
+            unsigned bit = (payload[pos >> 3] >> (7 - (pos & 7))) & 1u;
+            pos++;
+            node = bit ? t->right[node] : t->left[node];
+            if (node < 0) { rc = MHO_ERR_CORRUPT; goto done; }
+        }
+        if (nout < cap) out[nout] = t->value[node];
+        nout++;
+        prev = next_ctx(m, prev, t->value[node]);
+    }
+    if (max_symbols != UINT64_MAX && (nout != max_symbols || pos != end_bit)) rc = MHO_ERR_CORRUPT;
+done:
+    if (n_symbols) *n_symbols = nout;
+    if (stop_bit) *stop_bit = pos;
+    return rc;
+}

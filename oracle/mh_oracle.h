@@ -38,6 +38,7 @@ enum {
     MHO_ERR_TYPE = -2,     /* src/coding.cpp:107-110 table/file type mismatch */
     MHO_ERR_CAPACITY = -3,
     MHO_ERR_BADTABLE = -4,
+    MHO_ERR_ARG = -5,      /* mho_decode_span: end_bit beyond the payload */
 };
 
 /* src/main.cpp:29-39 + 176-178: counts[256*prev + c]++, prev starts at prev0 (' '). */
@@ -72,6 +73,18 @@ size_t mho_compress(const mho_model *m, const uint8_t *in, size_t n, uint8_t *ou
 /* src/coding.cpp:96-160.  in = whole compressed file (header + payload).  Returns decoded byte count
  * (writes min(count, cap) bytes) or a negative MHO_ERR_*. */
 int64_t mho_decompress(const mho_model *m, const uint8_t *in, size_t n, uint8_t *out, size_t cap);
+
+/* STRICT span decoder (not a restatement: the reference's assert(bi == length), src/coding.cpp:158, made a status).
+ * payload = MSB-first bits without the header byte.  Decodes from bit `bit0` in context `ctx` (the previous byte; order 2:
+ * (byte before previous) << 8 | previous byte) by walking the tree one bit at a time (the LUT is not used), until
+ * `max_symbols` symbols are out or the cursor reaches `end_bit`.  MHO_ERR_CORRUPT when a context has no table (null
+ * entry), when a code runs past end_bit, or, with max_symbols != UINT64_MAX, when the two limits are not reached together
+ * (fewer symbols at end_bit, or max_symbols symbols before it).  MHO_ERR_ARG when end_bit lies beyond the payload or
+ * bit0 > end_bit.  Writes min(count, cap) bytes; *n_symbols / *stop_bit (optional) receive the symbols decoded and the cursor
+ * where the decode stopped (also on an error). */
+int mho_decode_span(const mho_model *m, const uint8_t *payload, size_t payload_bytes,
+                    uint64_t bit0, uint64_t end_bit, unsigned ctx, uint64_t max_symbols,
+                    uint8_t *out, size_t cap, uint64_t *n_symbols, uint64_t *stop_bit);
 
 /* ---------------------------------------------------------------------------------------------
  * ORDER 2 (context = the previous TWO bytes) — GENERALISATION, PARITY UNPINNED.

@@ -16,6 +16,9 @@ REF_BIN = os.path.join(_HERE, "_ref", "markovhuffman")
 _u8p = C.POINTER(C.c_uint8)
 _u64p = C.POINTER(C.c_uint64)
 
+OK, ERR_CORRUPT, ERR_TYPE, ERR_CAPACITY, ERR_BADTABLE, ERR_ARG = 0, -1, -2, -3, -4, -5
+UNLIMITED = (1 << 64) - 1
+
 
 def build(force=False):
     """Compile libmh_oracle.so (and oracle/_ref when /root/reference is present)."""
@@ -45,6 +48,9 @@ def _load():
     lib.mho_compress.restype = C.c_size_t
     lib.mho_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
     lib.mho_decompress.restype = C.c_int64
+    lib.mho_decode_span.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint, C.c_uint64,
+                                    C.c_void_p, C.c_size_t, _u64p, _u64p]
+    lib.mho_decode_span.restype = C.c_int
     return lib
 
 
@@ -168,3 +174,18 @@ class Model:
         if n < 0:
             raise ValueError("oracle: decompress error %d" % n)
         return out[:n].tobytes()
+
+    def decode_span(self, payload, bit0, end_bit, ctx=0x20, max_symbols=None, cap=None):
+        """Strict decode of payload bits [bit0, end_bit) from context ctx (mho_decode_span: a tree walk, no LUT).
+        max_symbols None: decode until the cursor reaches end_bit exactly.  Returns (status, bytes, n_symbols, stop_bit);
+        the bytes are those decoded up to the stop, also on an error."""
+        a = _as_u8(payload)
+        ms = UNLIMITED if max_symbols is None else int(max_symbols)
+        if cap is None:
+            cap = (int(end_bit) - int(bit0)) if max_symbols is None else ms
+        cap = max(int(cap), 0)
+        out = np.zeros(max(cap, 1), dtype=np.uint8)
+        ns, stop = C.c_uint64(0), C.c_uint64(0)
+        rc = lib().mho_decode_span(self._h, a.ctypes.data if a.size else None, a.size, int(bit0), int(end_bit), int(ctx), ms,
+                                   out.ctypes.data, cap, C.byref(ns), C.byref(stop))
+        return rc, out[:min(ns.value, cap)].tobytes(), ns.value, stop.value

@@ -143,20 +143,36 @@ def test_a_buffer_too_small_is_reported_and_respected(mhc, oracle):
 
 
 def test_a_stream_that_does_not_belong_to_the_table_is_reported(mhc, oracle):
-    """Cut short inside its last code, or decoded with the table of another source: MH_ERR_CORRUPT from one of the passes (or
-    a symbol count that differs) — never a wild access; the guard bytes stay."""
+    """Cut short inside its last code, or decoded with the table of another source: exactly the contract's verdict
+    (tests/damage.py, from the oracle's strict span decoder) — never a wild access; the guard bytes stay."""
+    import damage
     data = zipf_bytes(2 << 20, 9)
     om = oracle.Model.from_data(data.tobytes(), 1)
     blob, nbits = om.compress(data.tobytes())
     m = mhc.Model.from_table(om.table_bytes())
-    st1, path, ns, st2, out = stream_decode(mhc, m, blob[1:], nbits - 3)
-    assert path in (0, PATH_STATES)
-    assert st1 == mhc.MH_ERR_CORRUPT or path == 0 or st2 == mhc.MH_ERR_CORRUPT or ns != data.size
-    other = mhc.Model.from_table(oracle.Model.from_data(text_like(1 << 20, 4).tobytes() + bytes(range(256)), 1).table_bytes())
+    pl = damage.cut(blob[1:], nbits, nbits - 3)
+    want = damage.verdict_free(om, pl, nbits - 3)
+    st1, path, ns, st2, out = stream_decode(mhc, m, pl, nbits - 3)
+    assert path == PATH_STATES
+    assert (st1 or st2) == want[0]
+    if want[0] == 0:
+        assert out[:ns].tobytes() == want[1]
+    other_om = oracle.Model.from_data(text_like(1 << 20, 4).tobytes() + bytes(range(256)), 1)
+    other = mhc.Model.from_table(other_om.table_bytes())
+    want = damage.verdict_free(other_om, blob[1:], nbits)
     st1, path, ns, st2, out = stream_decode(mhc, other, blob[1:], nbits)
-    assert st1 == mhc.MH_ERR_CORRUPT or path == 0 or st2 == mhc.MH_ERR_CORRUPT or ns != data.size
-    if out is not None:
+    if path == PATH_STATES:
+        assert (st1 or st2) == want[0]
+        if want[0] == 0:
+            assert out[:ns].tobytes() == want[1]
         assert np.all(out[max(ns, 0):][-4096:] == 0x5A)
+    else:
+        assert st1 == 0 and path == 0
+    try:
+        got = (0, other.decode(blob[1:], nbits))
+    except mhc.MhError as e:
+        got = (e.status, None)
+    assert got == want
 
 
 def test_streams_the_path_does_not_take_fall_back_to_the_index(mhc, oracle):
