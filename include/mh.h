@@ -364,7 +364,9 @@ int mh_dev_decode_dn(const mh_model *m, const uint8_t *d_payload, const uint64_t
  * index) and is consumed by mh_dev_decode_fine; it lives and dies in device memory.  chunk_symbols <= 4096 for the
  * decoder to use it.  Order-2 models (extension): entry = two context bytes << 16 | bits from the chunk's index entry
  * to the piece (0xFFFF: does not fit), chunk_symbols <= 1024, and only models whose live contexts all have a slot in
- * the decoder's LDS tables (text-like sources: a few hundred contexts) use it; mh_dev_build_index_fine writes none.
+ * the decoder's LDS tables (text-like sources: a few hundred contexts) use it; mh_dev_build_index_fine writes none.  The
+ * order-2 range calls (mh_dev_decode_ranges_o2) consume the order-2 form for any order-2 model, as work units of
+ * MH_FINE_SYMBOLS symbols; a piece whose entry is 0xFFFF is decoded from an earlier piece of its chunk.
  */
 #ifndef MH_T_SUB_SHIFT            /* (an experimental build may halve the piece: csrc/Makefile, MH_T_SUB_SHIFT=5) */
 #define MH_T_SUB_SHIFT 6
@@ -774,6 +776,52 @@ int mh_decompress_each_ranges(const uint8_t *tables, uint64_t tables_bytes, cons
                               uint8_t *out, size_t out_cap, uint64_t *out_off, int32_t *lookup_status);
 /* Diagnostic: payload bytes the calling thread's last mh_decode_batch_ranges / mh_decompress_each_ranges uploaded. */
 uint64_t mh_last_batch_range_upload_bytes(void);
+
+/* ---------------------------------------------------------------------------------------------------------------------
+ * RANDOM ACCESS INTO ORDER-2 STREAMS (extension, parity unpinned) — the two sections above for order-2 models: byte ranges
+ * of one indexed order-2 stream (mh_encode, mh_dev_encode_ctx*, mh_dev_build_index, a slice of mh_encode_batch_o2) and
+ * lookups into a batch of mh_encode_batch_o2.  Every call mirrors its order-0/1 counterpart argument for argument, and the
+ * contract is that of the sections above word for word, apart from these points:
+ *   - Model.  These calls refuse any model whose mh_model_type is not 2 with MH_ERR_ARG before anything is launched; the
+ *     order-0/1 calls keep refusing order 2.
+ *   - Index entries are order-2 entries: (two context bytes) << 48 | bit offset (MH_INDEX2_BIT_MASK masks the offset; the
+ *     host forms' window logic masks with it too).  Index-free batch streams are walked from bit 0 in context
+ *     (prev0, prev0), under the MH_BATCH_WALK_MAX_BITS cap.
+ *   - Fine index (mh_dev_decode_ranges_o2 only, optional): the order-2 form of the FINE INDEX note, written by
+ *     mh_dev_encode_ctx_fine; chunk_symbols <= 1024 with a fine index (else MH_ERR_ARG), d_fine 4-byte aligned.  The work unit
+ *     is then a piece of MH_FINE_SYMBOLS symbols.  A piece whose entry's low half is 0xFFFF is not used: its lane starts at
+ *     the nearest earlier usable piece of the same chunk (or at the chunk's entry) and skips forward, and an item that ends
+ *     at its start is checked as one that ends inside a unit.  A usable fine entry past the next chunk entry or past nbits
+ *     makes every range that reads that piece (starts there, or ends at its start) MH_ERR_CORRUPT.
+ *   - A range of mh_dev_decode_ranges_o2 whose decode reads past the payload window is MH_ERR_ARG.
+ * --------------------------------------------------------------------------------------------------------------------- */
+size_t mh_dev_decode_ranges_o2_workspace(size_t n_ranges);
+/* mh_dev_decode_ranges for an order-2 model (d_fine: the order-2 fine index or NULL).  No host synchronisation, no
+ * allocation. */
+int mh_dev_decode_ranges_o2(const mh_model *m, const uint8_t *d_payload, uint64_t payload_byte_base, uint64_t payload_bytes,
+                            uint64_t nbits, const uint64_t *d_index, uint32_t chunk_symbols, uint64_t n_symbols,
+                            const uint32_t *d_fine, const uint64_t *d_ranges, size_t n_ranges,
+                            uint8_t *d_out, const uint64_t *d_out_at, uint64_t out_cap,
+                            int32_t *d_range_status, void *d_ws, size_t ws_bytes, void *stream);
+/* mh_decode_ranges for an order-2 model: the same window merging and segment cut; mh_last_range_upload_bytes reports its
+ * upload. */
+int mh_decode_ranges_o2(const mh_model *m, const uint8_t *payload, uint64_t nbits, const uint64_t *index,
+                        uint32_t chunk_symbols, uint64_t n_symbols, const uint64_t *ranges, size_t n_ranges,
+                        uint8_t *out, size_t out_cap, uint64_t *out_off, int32_t *range_status);
+size_t mh_dev_decode_batch_o2_ranges_workspace(size_t n_lookups);
+/* mh_dev_decode_batch_ranges for a shared order-2 model. */
+int mh_dev_decode_batch_o2_ranges(const mh_model *m, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits,
+                                  size_t n_streams, uint8_t prev0, const uint64_t *d_sym_off, const uint64_t *d_index,
+                                  uint32_t chunk_symbols, const uint64_t *d_lookups, size_t n_lookups,
+                                  uint8_t *d_out, const uint64_t *d_out_at, uint64_t out_cap,
+                                  int32_t *d_lookup_status, void *d_ws, size_t ws_bytes, void *stream);
+/* mh_decode_batch_ranges for a shared order-2 model: only the touched streams are uploaded; a touched stream over
+ * MH_EACH_DIRECT_BYTES, or an index-free one over MH_BATCH_WALK_MAX_BITS, goes through mh_decode_ranges_o2 on its slice
+ * (indexed) or mh_decode (index-free).  mh_last_batch_range_upload_bytes reports the upload. */
+int mh_decode_batch_o2_ranges(const mh_model *m, const uint8_t *payload, uint64_t payload_bytes, const uint64_t *pay_off,
+                              const uint64_t *nbits, size_t n_streams, uint8_t prev0, const uint64_t *sym_off,
+                              const uint64_t *index, uint32_t chunk_symbols, const uint64_t *lookups, size_t n_lookups,
+                              uint8_t *out, size_t out_cap, uint64_t *out_off, int32_t *lookup_status);
 
 /* ---------------------------------------------------------------------------------------------------------------------
  * BANKS OF SHARED MODELS — the middle ground between one shared model (a table once, statistics that may not fit) and one

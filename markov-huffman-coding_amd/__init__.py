@@ -56,6 +56,8 @@ EXPORTS = [
     "mh_dev_batch_emit", "mh_dev_each_emit", "mh_index_batch", "mh_index_each",
     "mh_dev_histogram_o2_batch_workspace", "mh_dev_histogram_o2_batch", "mh_dev_encode_batch_o2_workspace", "mh_dev_encode_batch_o2",
     "mh_dev_decode_batch_o2_workspace", "mh_dev_decode_batch_o2", "mh_encode_batch_o2", "mh_decode_batch_o2",
+    "mh_dev_decode_ranges_o2_workspace", "mh_dev_decode_ranges_o2", "mh_decode_ranges_o2",
+    "mh_dev_decode_batch_o2_ranges_workspace", "mh_dev_decode_batch_o2_ranges", "mh_decode_batch_o2_ranges",
 ]
 BANK_MAX = 64                              # include/mh.h MH_BANK_MAX
 BANK_NONE = 0xFFFFFFFF                     # include/mh.h MH_BANK_NONE
@@ -226,6 +228,14 @@ def lib():
         l.mh_decompress_each_ranges.argtypes = [vp, u64, vp, vp, u64, vp, vp, sz, u8, vp, vp, u32, vp, sz, vp, sz, vp, vp]
         l.mh_last_batch_range_upload_bytes.argtypes = []
         l.mh_last_batch_range_upload_bytes.restype = u64
+        l.mh_dev_decode_ranges_o2_workspace.argtypes = [sz]
+        l.mh_dev_decode_ranges_o2_workspace.restype = sz
+        l.mh_dev_decode_ranges_o2.argtypes = l.mh_dev_decode_ranges.argtypes
+        l.mh_decode_ranges_o2.argtypes = l.mh_decode_ranges.argtypes
+        l.mh_dev_decode_batch_o2_ranges_workspace.argtypes = [sz]
+        l.mh_dev_decode_batch_o2_ranges_workspace.restype = sz
+        l.mh_dev_decode_batch_o2_ranges.argtypes = l.mh_dev_decode_batch_ranges.argtypes
+        l.mh_decode_batch_o2_ranges.argtypes = l.mh_decode_batch_ranges.argtypes
         l.mh_dev_bank_select_workspace.argtypes = [sz, sz, sz]
         l.mh_dev_bank_select_workspace.restype = sz
         l.mh_dev_bank_select.argtypes = [vp, vp, vp, sz, sz, u8, vp, vp, vp, sz, vp]
@@ -612,6 +622,15 @@ class Model:
         """Bytes [begin, end) of the original input for every (begin, end) in `ranges`, from an indexed stream (payload without
         the header byte, its chunk index).  Returns (list of byte strings, int32 status per range); a failed range's bytes are
         empty.  Raises MhError on a call-level error (bad arguments, no device)."""
+        return self._decode_ranges(payload, nbits, index, chunk_symbols, n_symbols, ranges, "mh_decode_ranges")
+
+    def decode_ranges_o2(self, payload, nbits, index, chunk_symbols, n_symbols, ranges):
+        """decode_ranges for an order-2 model (mh_decode_ranges_o2; index entries carry two context bytes).  Any other model is
+        refused with MhError(MH_ERR_ARG)."""
+        self._require_o2("mh_decode_ranges_o2")
+        return self._decode_ranges(payload, nbits, index, chunk_symbols, n_symbols, ranges, "mh_decode_ranges_o2")
+
+    def _decode_ranges(self, payload, nbits, index, chunk_symbols, n_symbols, ranges, fn):
         a = _u8(payload)
         rg = np.ascontiguousarray(np.asarray(ranges, dtype=np.uint64).reshape(-1, 2))
         n = rg.shape[0]
@@ -622,11 +641,11 @@ class Model:
         out_off = np.zeros(n + 1, dtype=np.uint64)
         status = np.zeros(max(n, 1), dtype=np.int32)
         ip = idx.ctypes.data if idx.size else (out.ctypes.data if n_symbols == 0 else None)
-        rc = lib().mh_decode_ranges(self._h, _ptr(a), nbits, ip, chunk_symbols, n_symbols, rg.ctypes.data if n else None, n,
-                                    out.ctypes.data, cap, out_off.ctypes.data, status.ctypes.data)
+        rc = getattr(lib(), fn)(self._h, _ptr(a), nbits, ip, chunk_symbols, n_symbols, rg.ctypes.data if n else None, n,
+                                out.ctypes.data, cap, out_off.ctypes.data, status.ctypes.data)
         status = status[:n]
         if rc != MH_OK and not np.any(status == rc):
-            raise MhError(rc, "mh_decode_ranges")
+            raise MhError(rc, fn)
         res = [out[int(out_off[j]):int(out_off[j + 1])].tobytes() if status[j] == MH_OK else b"" for j in range(n)]
         return res, status
 
@@ -636,6 +655,9 @@ class Model:
         """Bytes [begin, end) of stream `stream` for every (stream, begin, end) in `lookups`, from a batch (packed payloads,
         pay_off[n + 1], nbits[n]; with an index, sym_off is the encode's in_off).  Returns (list of byte strings, int32 status
         per lookup); a failed lookup's bytes are empty.  Raises MhError on a call-level error (mh_decode_batch_ranges)."""
+        return self._decode_batch_ranges(payload, pay_off, nbits, lookups, prev0, sym_off, index, chunk_symbols, "mh_decode_batch_ranges")
+
+    def _decode_batch_ranges(self, payload, pay_off, nbits, lookups, prev0, sym_off, index, chunk_symbols, fn):
         payload = _u8(payload)
         pay_off = np.ascontiguousarray(pay_off, dtype=np.uint64)
         nbits = np.ascontiguousarray(nbits, dtype=np.uint64)
@@ -644,12 +666,12 @@ class Model:
         idx = np.ascontiguousarray(index, dtype=np.uint64) if index is not None else None
         lk = _lookups(lookups)
         m = lk.shape[0]
-        call = lambda out, cap, oo, st: lib().mh_decode_batch_ranges(
+        call = lambda out, cap, oo, st: getattr(lib(), fn)(
             self._h, _ptr(payload), payload.size, pay_off.ctypes.data, nbits.ctypes.data if n else None, n, prev0,
             so.ctypes.data if so is not None else None,
             (idx.ctypes.data if idx.size else pay_off.ctypes.data) if idx is not None else None, chunk_symbols,
             lk.ctypes.data if m else None, m, out, cap, oo, st)
-        return _host_batch_ranges(call, "mh_decode_batch_ranges", lk, nbits[:n], so)
+        return _host_batch_ranges(call, fn, lk, nbits[:n], so)
 
     def dev_decode_batch_ranges(self, payload, pay_off, nbits, lookups, prev0=PREV0, sym_off=None, index=None, chunk_symbols=0, out_cap=None):
         """One mh_dev_decode_batch_ranges call with guard bytes around every output: (list of bytes, status per lookup,
@@ -659,6 +681,9 @@ class Model:
 
     def decompress_batch_ranges(self, blobs, lookups, indices=None, chunk_symbols=0, lengths=None):
         """Lookups into whole `.cm` files of this model (decompress_batch's inputs): (list of bytes, status per lookup)."""
+        return self._decompress_batch_ranges(blobs, lookups, indices, chunk_symbols, lengths, self.decode_batch_ranges)
+
+    def _decompress_batch_ranges(self, blobs, lookups, indices, chunk_symbols, lengths, decode):
         l = lib()
         payloads, nbits = [], []
         for b in blobs:
@@ -676,7 +701,7 @@ class Model:
             if lengths is None:
                 raise ValueError("decompress_batch_ranges with indices needs the original lengths")
             index = _batch_index(indices, sym_off, chunk_symbols)
-        return self.decode_batch_ranges(payload, pay_off, np.array(nbits, dtype=np.uint64), lookups, PREV0, sym_off, index, chunk_symbols)
+        return decode(payload, pay_off, np.array(nbits, dtype=np.uint64), lookups, PREV0, sym_off, index, chunk_symbols)
 
     # ---- batches of independent streams (mh_encode_batch / mh_decode_batch) -------------------------------------------
     def encode_batch(self, messages, prev0=PREV0, chunk_symbols=None):
@@ -801,6 +826,29 @@ class Model:
     def decompress_batch_o2(self, blobs, indices=None, chunk_symbols=0, lengths=None):
         """decompress_batch for an order-2 model."""
         return self._decompress_batch(blobs, indices, chunk_symbols, lengths, self.decode_batch_o2)
+
+    # ---- random access into order-2 streams (mh_decode_batch_o2_ranges / mh_dev_decode_batch_o2_ranges; extension) -------
+    def _require_o2(self, what):
+        if self.type != 2:
+            raise MhError(MH_ERR_ARG, what)
+
+    def decode_batch_o2_ranges(self, payload, pay_off, nbits, lookups, prev0=PREV0, sym_off=None, index=None, chunk_symbols=0):
+        """decode_batch_ranges for an order-2 model (mh_decode_batch_o2_ranges): lookups into an encode_batch_o2 batch."""
+        self._require_o2("mh_decode_batch_o2_ranges")
+        return self._decode_batch_ranges(payload, pay_off, nbits, lookups, prev0, sym_off, index, chunk_symbols, "mh_decode_batch_o2_ranges")
+
+    def dev_decode_batch_o2_ranges(self, payload, pay_off, nbits, lookups, prev0=PREV0, sym_off=None, index=None, chunk_symbols=0,
+                                   out_cap=None):
+        """One mh_dev_decode_batch_o2_ranges call with guard bytes around every output: (list of bytes, status per lookup,
+        mh_dev_status)."""
+        self._require_o2("mh_dev_decode_batch_o2_ranges")
+        return _dev_batch_ranges(lib().mh_dev_decode_batch_o2_ranges, self._h, payload, pay_off, nbits, lookups, prev0, sym_off, index,
+                                 chunk_symbols, out_cap)
+
+    def decompress_batch_o2_ranges(self, blobs, lookups, indices=None, chunk_symbols=0, lengths=None):
+        """decompress_batch_ranges for an order-2 model: lookups into whole `.cm` files of compress_batch_o2."""
+        self._require_o2("mh_decode_batch_o2_ranges")
+        return self._decompress_batch_ranges(blobs, lookups, indices, chunk_symbols, lengths, self.decode_batch_o2_ranges)
 
 
 # ---- batches of streams, one model each (include/mh.h, "BATCHES OF STREAMS, ONE MODEL EACH") ----------------------------

@@ -1,6 +1,7 @@
 // mh_api_range.cpp — the byte-range calls of the C ABI (include/mh.h, "RANDOM ACCESS: BYTE RANGES OF AN INDEXED STREAM"):
 // ranges of one indexed order-0/1 stream decoded on the device (kernels: mh_range.hip), and the host-buffer form that
-// uploads only the payload bytes of the chunks the ranges touch.
+// uploads only the payload bytes of the chunks the ranges touch; that host form serves mh_decode_ranges_o2 as well
+// (mh_api_range_o2.cpp).
 #include "mh_api_internal.hpp"
 #include "mh_batch.h"
 #include "mh_range.h"
@@ -9,13 +10,14 @@ using namespace mhapi;
 
 namespace {
 
-thread_local uint64_t t_range_upload = 0;   // payload bytes the calling thread's last mh_decode_ranges uploaded
+thread_local uint64_t t_range_upload = 0;   // payload bytes the calling thread's last mh_decode_ranges(_o2) uploaded
 
 // Byte spans of the payload closer than this are uploaded as one window: one transfer and one launch cost more than the
 // bytes in between (a PCIe transfer of 1 MiB takes about as long as the fixed cost of a call).
 constexpr uint64_t RANGE_MERGE_GAP = uint64_t(1) << 20;
 
 bool order01(const mh_model *m) { return m && (m->type == 0 || m->type == 1); }
+bool order2(const mh_model *m) { return m && m->type == 2; }
 
 // a run of whole chunks [c0, c1] of one range, cut so that its payload bytes and its output fit a segment
 struct Piece {
@@ -69,8 +71,19 @@ int mh_dev_decode_ranges(const mh_model *m, const uint8_t *d_payload, uint64_t p
 int mh_decode_ranges(const mh_model *m, const uint8_t *payload, uint64_t nbits, const uint64_t *index, uint32_t chunk_symbols,
                      uint64_t n_symbols, const uint64_t *ranges, size_t n_ranges, uint8_t *out, size_t out_cap, uint64_t *out_off,
                      int32_t *range_status) {
+    return decode_ranges_host(m, false, payload, nbits, index, chunk_symbols, n_symbols, ranges, n_ranges, out, out_cap, out_off,
+                              range_status);
+}
+
+}  // extern "C"
+
+namespace mhapi {
+
+int decode_ranges_host(const mh_model *m, bool o2, const uint8_t *payload, uint64_t nbits, const uint64_t *index, uint32_t chunk_symbols,
+                       uint64_t n_symbols, const uint64_t *ranges, size_t n_ranges, uint8_t *out, size_t out_cap, uint64_t *out_off,
+                       int32_t *range_status) {
     t_range_upload = 0;
-    if (!order01(m) || (!payload && nbits) || (!index && n_symbols) || (!ranges && n_ranges) || !out_off || (!out && out_cap))
+    if (!(o2 ? order2(m) : order01(m)) || (!payload && nbits) || (!index && n_symbols) || (!ranges && n_ranges) || !out_off || (!out && out_cap))
         return MH_ERR_ARG;
     const int shift = chunk_shift_of(chunk_symbols);
     if (shift < 0 || n_symbols > nbits) return MH_ERR_ARG;
@@ -92,7 +105,8 @@ int mh_decode_ranges(const mh_model *m, const uint8_t *payload, uint64_t nbits, 
     // a segment holds at least MH_CHUNK_MAX symbols, and a chunk's payload is a few KiB)
     const uint64_t seg = segment_bytes();
     const uint64_t nchunks = mh_index_entries(n_symbols, chunk_symbols);
-    auto ent = [&](uint64_t c) { return index[c] & MH_INDEX_BIT_MASK; };
+    const uint64_t pos_mask = o2 ? MH_INDEX2_BIT_MASK : MH_INDEX_BIT_MASK;     // (order 2: two context bytes above)
+    auto ent = [&](uint64_t c) { return index[c] & pos_mask; };
     auto cend = [&](uint64_t c) { return c + 1 < nchunks ? ent(c + 1) : nbits; };
     std::vector<Piece> pieces;
     for (size_t j = 0; j < n_ranges; ++j) {
@@ -153,7 +167,7 @@ int mh_decode_ranges(const mh_model *m, const uint8_t *payload, uint64_t nbits, 
 
     const hipStream_t st = nullptr;
     if (!wins.empty()) {
-        const size_t wsb = mh_dev_decode_ranges_workspace(max_n);
+        const size_t wsb = o2 ? mh_dev_decode_ranges_o2_workspace(max_n) : mh_dev_decode_ranges_workspace(max_n);
         DevBuf d_pl, d_idx, d_rng, d_out, d_st, d_ws;
         HIP_TRY(d_pl.alloc(size_t(max_bytes)));
         HIP_TRY(d_idx.alloc(size_t(max_idx) * 8));
@@ -181,7 +195,7 @@ int mh_decode_ranges(const mh_model *m, const uint8_t *payload, uint64_t nbits, 
                 o += q.e - q.b;
             }
             HIP_TRY(hipMemcpyAsync(d_rng.p, h_rng.data(), k * 24, hipMemcpyHostToDevice, st));
-            int rc = mh_dev_decode_ranges(m, d_pl.as<uint8_t>(), w.lo, bytes, nbits, d_index, chunk_symbols, n_symbols, nullptr,
+            int rc = (o2 ? mh_dev_decode_ranges_o2 : mh_dev_decode_ranges)(m, d_pl.as<uint8_t>(), w.lo, bytes, nbits, d_index, chunk_symbols, n_symbols, nullptr,
                                           d_rng.as<uint64_t>(), k, d_out.as<uint8_t>(), d_rng.as<uint64_t>() + 2 * k, w.out,
                                           d_st.as<int32_t>(), d_ws.p, wsb, st);
             if (rc != MH_OK) return rc;
@@ -201,4 +215,4 @@ int mh_decode_ranges(const mh_model *m, const uint8_t *payload, uint64_t nbits, 
     return first;
 }
 
-}  // extern "C"
+}  // namespace mhapi

@@ -37,4 +37,11 @@ struct BatchRangeParams {
 // shared: the model in p.tab (LDS tables); otherwise the set in p.set (L2 tables)
 hipError_t launch_batch_ranges(const BatchRangeParams &p, bool shared, void *d_ws, hipStream_t st);
 
+// the call-level checks every device lookup call shares (mh_api_batch_range.cpp); fills everything of p but the tables.
+// MH_OK, MH_ERR_ARG or MH_ERR_CAPACITY (workspace).
+int prepare_lookups(const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits, size_t n_streams, uint8_t prev0,
+                    const uint64_t *d_sym_off, const uint64_t *d_index, uint32_t chunk_symbols, const uint64_t *d_lookups, size_t n_lookups,
+                    uint8_t *d_out, const uint64_t *d_out_at, uint64_t out_cap, int32_t *d_lookup_status, void *d_ws, size_t ws_bytes,
+                    BatchRangeParams &p);
+
 }  // namespace mhq
