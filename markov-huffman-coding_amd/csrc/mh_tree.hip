@@ -2,7 +2,7 @@
 //
 //   tree_build_kernel   one wave per context: exact emulation of the reference's heap
 //                       (src/min_pq.tpp:4-52) and merge rule (src/huffman.cpp:131-164), the heap held in
-//                       the wave's registers and driven by scalar code (RegHeap); then all lanes derive
+//                       LDS and every sift done lane-parallel, lane = heap level (LdsHeap); then all lanes derive
 //                       depths, codewords (src/huffman.cpp:97-123) and the encode tables, and size the
 //                       decode tables for every primary width.
 //   tree_pack_kernel    one workgroup per context: fills the two decode-table levels and the walk tree
@@ -13,6 +13,8 @@
 // the host and ~5 ms of host work in the middle of the pipeline.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "mh_kernels.h"
 #include "mh_model.hpp"
@@ -27,222 +29,81 @@ using mh::TREE_STRIDE;
 constexpr uint16_t NONE = 0xFFFF;
 
 // ------------------------------------------------------------------------------------------------
-// The reference's binary heap (src/min_pq.tpp:4-52), emulated comparison for comparison, kept in the
-// wave's REGISTERS: heap level L (positions 0 .. 2^L - 1) lives in one VGPR, position = lane (level 7 takes
-// two, level 8 is the single index 255), so an entry is reached with v_readlane / v_writelane at a
-// wave-uniform position and every level of a sift is a handful of scalar instructions — no LDS round trip
-// and no divergent lane (the first version ran the heap in LDS on lane 0: ~0.8 ms for 256 contexts, bound
-// by the LDS latency of ~4000 dependent accesses per context).  Each entry carries its key (the weight;
-// 32 bits when the context's total fits, else 64), and `item` = node id | subtree height << 16, so the
-// merge loop (src/huffman.cpp:143-151) needs nothing back from memory.
-// All values handled here are wave-uniform; sifts are unrolled over the levels by template recursion.
+// The reference's binary heap (src/min_pq.tpp:4-52), reproduced entry for entry with each sift done lane-parallel
+// (lane = heap level) instead of comparison by comparison.  The heap lives in LDS, 1-based (root e[1], children of
+// n at 2n and 2n + 1), one entry = key (32 bits when the context's total fits, else 64) + `item` = node id |
+// subtree height << 16, so the merge loop (src/huffman.cpp:143-151) needs nothing back from memory.
+// Why this gives the reference's array exactly: the comparisons never look at items, and along any root path the
+// keys never decrease, so
+//   * swim (:29-36, "parent STRICTLY greater"): the ancestors that move down are the bottom run of the root path
+//     whose keys are > the new key — one compare per level, a ballot, and every level written at once;
+//   * sink (:38-52): the path the hole takes is the chain of preferred children (right iff it exists and its key is
+//     STRICTLY smaller than the left's), which depends on the heap before the sink only; the children that move up
+//     are the top run of that path whose keys are < the sinking key.  The preferred-child bits of nodes 1..127 are
+//     two ballots (nodes 128.. never have a right child), the path is a chase of those bits in scalar registers
+//     (four instructions a level), and the rest is again one compare per level, a ballot and one write per level.
+// Per heap operation: one LDS round trip for a swim, two for a sink, and no data-dependent branch.
+// entries 1..256; a lane with no level to work on reads and writes back its own spare slot HEAP_SPARE + lane (> 256)
+constexpr uint32_t HEAP_SPARE = 256, HEAP_SLOTS = 320;
+
 template <bool K64>
-struct RegHeap {
-    uint32_t klo[10], khi[10], itm[10];   // slot: levels 0..6 -> 0..6, level 7 -> 7 (positions 0..63) and 8 (64..127), level 8 -> 9
+struct LdsHeap {
+    using Key = typename std::conditional<K64, unsigned long long, uint32_t>::type;
+    struct alignas(K64 ? 16 : 8) Ent {
+        Key key;
+        uint32_t item;
+    };
+    Ent *e;
+    uint32_t lane;
     uint32_t hn = 0;
 
     static __device__ __forceinline__ uint32_t uni(uint32_t v) { return uint32_t(__builtin_amdgcn_readfirstlane(int(v))); }
-    static __device__ __forceinline__ uint32_t rl(uint32_t v, uint32_t lane) { return uint32_t(__builtin_amdgcn_readlane(int(v), int(lane))); }
-    static __device__ __forceinline__ uint32_t wl(uint32_t val, uint32_t lane, uint32_t old) {
-        // (this clang has no __builtin_amdgcn_writelane; both scalar operands are wave-uniform by construction)
-        // the lane select goes through M0: two different SGPR operands would exceed gfx9's constant-bus limit.
-        // (M0 is a reserved register — the compiler sets it itself before every use of its own — and clang
-        // warns about naming it as a clobber; it is named anyway so that no operand is ever placed in it.)
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-        // (readfirstlane: an "s" operand the compiler holds in a VGPR would be passed as that VGPR)
-        asm("s_mov_b32 m0, %2\n\tv_writelane_b32 %0, %1, m0" : "+v"(old) : "s"(uni(val)), "s"(uni(lane)) : "m0");
-#pragma clang diagnostic pop
-        return old;
+    static __device__ __forceinline__ Key uni_key(Key k) {
+        if constexpr (K64) return (Key(uni(uint32_t(k >> 32))) << 32) | uni(uint32_t(k));
+        else return uni(k);
     }
-    // strict a < b on (hi, lo) pairs
-    static __device__ __forceinline__ bool lt(uint32_t alo, uint32_t ahi, uint32_t blo, uint32_t bhi) {
-        if (K64) return ahi < bhi || (ahi == bhi && alo < blo);
-        return alo < blo;
-    }
-    template <int L>
-    __device__ __forceinline__ void get(uint32_t pos, uint32_t &lo, uint32_t &hi, uint32_t &it) const {
-        if constexpr (L < 7) {
-            lo = rl(klo[L], pos); hi = K64 ? rl(khi[L], pos) : 0u; it = rl(itm[L], pos);
-        } else if constexpr (L == 7) {
-            const uint32_t ln = pos & 63u;
-            const bool up = pos >= 64u;
-            lo = up ? rl(klo[8], ln) : rl(klo[7], ln);
-            hi = K64 ? (up ? rl(khi[8], ln) : rl(khi[7], ln)) : 0u;
-            it = up ? rl(itm[8], ln) : rl(itm[7], ln);
-        } else {
-            lo = rl(klo[9], 0); hi = K64 ? rl(khi[9], 0) : 0u; it = rl(itm[9], 0);
-        }
-    }
-    template <int L>
-    __device__ __forceinline__ void put(uint32_t pos, uint32_t lo, uint32_t hi, uint32_t it) {
-        if constexpr (L < 7) {
-            klo[L] = wl(lo, pos, klo[L]); if (K64) khi[L] = wl(hi, pos, khi[L]); itm[L] = wl(it, pos, itm[L]);
-        } else if constexpr (L == 7) {
-            const uint32_t ln = pos & 63u;
-            if (pos >= 64u) { klo[8] = wl(lo, ln, klo[8]); if (K64) khi[8] = wl(hi, ln, khi[8]); itm[8] = wl(it, ln, itm[8]); }
-            else { klo[7] = wl(lo, ln, klo[7]); if (K64) khi[7] = wl(hi, ln, khi[7]); itm[7] = wl(it, ln, itm[7]); }
-        } else {
-            klo[9] = wl(lo, 0, klo[9]); if (K64) khi[9] = wl(hi, 0, khi[9]); itm[9] = wl(it, 0, itm[9]);
-        }
-    }
-    // [r3] A compact variant was measured against this one: four register sets of 64 slots (children always side by side
-    // in one set), sifts as rolled loops, every write one asm statement that branches inside so that no join sees a
-    // register modified on one path only — 4 400 instructions of kernel instead of 16 000, all tests green, and 1.1 ms per
-    // launch instead of 0.74.  The time is the length of the dependent scalar chain (~250 instructions per heap operation
-    // either way, one wave per CU, nothing to hide behind), not the code size; the unrolled form below stays.
-    // Both sifts are written as a read-only phase that follows the whole path with scalar selects, and a
-    // write phase that stores ONE entry per level unconditionally — the moved entry, the sifted key, or
-    // what the slot held anyway.  (Branches with early exits made the compiler copy all thirty heap registers
-    // at every join: ~500 instructions per heap operation, no faster than the first version's LDS heap.)
 
-    // src/min_pq.tpp:4-7 + 29-36: the new entry, appended at (L, pos), moves up while its parent's key is
-    // STRICTLY greater.  Heap order along the root path means the parents that move form one bottom segment.
-    template <int L>
-    __device__ __forceinline__ void swim_flat(uint32_t pos, uint32_t lo, uint32_t hi, uint32_t it) {
-        uint32_t alo[L + 1], ahi[L + 1], ait[L + 1];            // ancestors: a*[l] = entry at level l on the root path (l < L)
-        uint32_t moves = 0;                                      // parents that move down (counted from the bottom)
-        bool going = true;
-        alo[L] = lo; ahi[L] = hi; ait[L] = it;
-#pragma unroll
-        for (int l = L - 1; l >= 0; --l) {
-            get_dyn(l, pos >> (L - l), alo[l], ahi[l], ait[l]);
-            going = going && lt(lo, hi, alo[l], ahi[l]);         // parent > key
-            moves += going ? 1u : 0u;
-        }
-        const uint32_t f = uint32_t(L) - moves;                  // level where the new entry comes to rest
-#pragma unroll
-        for (int l = L; l >= 0; --l) {
-            // level l gets: its parent's entry if the parent moved into it, the new entry at level f, else itself
-            const bool from_parent = uint32_t(l) > f;
-            const bool self = uint32_t(l) < f;
-            const uint32_t plo = l > 0 ? alo[l > 0 ? l - 1 : 0] : lo, phi = l > 0 ? ahi[l > 0 ? l - 1 : 0] : hi,
-                           pit = l > 0 ? ait[l > 0 ? l - 1 : 0] : it;
-            const uint32_t wlo = from_parent ? plo : self ? alo[l] : lo;
-            const uint32_t whi = from_parent ? phi : self ? ahi[l] : hi;
-            const uint32_t wit = from_parent ? pit : self ? ait[l] : it;
-            put_dyn(l, pos >> (L - l), wlo, whi, wit);
-        }
+    // src/min_pq.tpp:4-7 + 29-36: append at n = hn, then the ancestors (lane l = level l, n >> (L - l)) whose keys
+    // are STRICTLY greater move down one level each and the new entry takes the highest of their places
+    __device__ __forceinline__ void push(Key k, uint32_t it) {
+        const uint32_t n = ++hn;
+        const uint32_t L = 31u - uint32_t(__builtin_clz(n));
+        const uint32_t an = lane <= L ? n >> (L - lane) : HEAP_SPARE + lane;
+        const Ent a = e[an];
+        const Ent p = e[an >> 1];                                  // the entry above it (lane 0: e[0], unused)
+        const uint32_t f = L - uint32_t(__popcll(__ballot(lane < L && a.key > k)));   // level where the entry rests
+        // every lane writes, the lanes that keep their entry write it back: with a conditional write the compiler moves
+        // the read of p behind the ballot (a second LDS round trip); selects field by field (of whole structs: scratch)
+        const bool self = lane == f, down = lane > f && lane <= L;
+        e[an] = Ent{self ? k : down ? p.key : a.key, self ? it : down ? p.item : a.item};
     }
-    // [r3] the same with an early exit: most entries come to rest one or two levels above where they were appended, and the
-    // flat form reads and rewrites the whole root path every time.  One comparison chain, no write until the resting level is
-    // known; then only the levels that change are written (switch on the number of moves: every case writes a fixed set).
-    template <int L>
-    __device__ __forceinline__ void swim_short(uint32_t pos, uint32_t lo, uint32_t hi, uint32_t it) {
-        uint32_t alo[L + 1], ahi[L + 1], ait[L + 1];
-        uint32_t moves = 0;
-#pragma unroll
-        for (int l = L - 1; l >= 0; --l) {
-            get_dyn(l, pos >> (L - l), alo[l], ahi[l], ait[l]);
-            if (!lt(lo, hi, alo[l], ahi[l])) break;              // parent <= key: the entry rests at level l + 1
-            ++moves;
-        }
-        // parents at levels L-1 .. L-moves move down one level each; the new entry goes to level L - moves
-#pragma unroll
-        for (int m = 0; m < L; ++m) {
-            if (uint32_t(m) < moves) put_dyn(L - m, pos >> m, alo[L - 1 - m], ahi[L - 1 - m], ait[L - 1 - m]);
-        }
-        put_any_level<L>(L - moves, pos >> moves, lo, hi, it);
-    }
-    template <int L>
-    __device__ __forceinline__ void put_any_level(uint32_t level, uint32_t pos, uint32_t lo, uint32_t hi, uint32_t it) {
-        switch (level) {
-            case 0: put<0>(pos, lo, hi, it); break;
-            case 1: if (L >= 1) put<1>(pos, lo, hi, it); break;
-            case 2: if (L >= 2) put<2>(pos, lo, hi, it); break;
-            case 3: if (L >= 3) put<3>(pos, lo, hi, it); break;
-            case 4: if (L >= 4) put<4>(pos, lo, hi, it); break;
-            case 5: if (L >= 5) put<5>(pos, lo, hi, it); break;
-            case 6: if (L >= 6) put<6>(pos, lo, hi, it); break;
-            case 7: if (L >= 7) put<7>(pos, lo, hi, it); break;
-            default: if (L >= 8) put<8>(pos, lo, hi, it); break;
-        }
-    }
-    // level known at compile time through the unrolled loops above: these forward to get<>/put<>
-    __device__ __forceinline__ void get_dyn(int l, uint32_t pos, uint32_t &lo, uint32_t &hi, uint32_t &it) const {
-        switch (l) {
-            case 0: get<0>(pos, lo, hi, it); break; case 1: get<1>(pos, lo, hi, it); break; case 2: get<2>(pos, lo, hi, it); break;
-            case 3: get<3>(pos, lo, hi, it); break; case 4: get<4>(pos, lo, hi, it); break; case 5: get<5>(pos, lo, hi, it); break;
-            case 6: get<6>(pos, lo, hi, it); break; case 7: get<7>(pos, lo, hi, it); break; default: get<8>(pos, lo, hi, it); break;
-        }
-    }
-    __device__ __forceinline__ void put_dyn(int l, uint32_t pos, uint32_t lo, uint32_t hi, uint32_t it) {
-        switch (l) {
-            case 0: put<0>(pos, lo, hi, it); break; case 1: put<1>(pos, lo, hi, it); break; case 2: put<2>(pos, lo, hi, it); break;
-            case 3: put<3>(pos, lo, hi, it); break; case 4: put<4>(pos, lo, hi, it); break; case 5: put<5>(pos, lo, hi, it); break;
-            case 6: put<6>(pos, lo, hi, it); break; case 7: put<7>(pos, lo, hi, it); break; default: put<8>(pos, lo, hi, it); break;
-        }
-    }
-    __device__ __forceinline__ void push(uint32_t lo, uint32_t hi, uint32_t it) {     // src/min_pq.tpp:4-7
-        const uint32_t i = hn++;
-        const uint32_t level = 31u - uint32_t(__builtin_clz(i + 1u));
-        const uint32_t pos = i + 1u - (1u << level);
-        switch (level) {
-            case 0: swim_short<0>(pos, lo, hi, it); break;
-            case 1: swim_short<1>(pos, lo, hi, it); break;
-            case 2: swim_short<2>(pos, lo, hi, it); break;
-            case 3: swim_short<3>(pos, lo, hi, it); break;
-            case 4: swim_short<4>(pos, lo, hi, it); break;
-            case 5: swim_short<5>(pos, lo, hi, it); break;
-            case 6: swim_short<6>(pos, lo, hi, it); break;
-            case 7: swim_short<7>(pos, lo, hi, it); break;
-            default: swim_short<8>(pos, lo, hi, it); break;
-        }
-    }
-    // src/min_pq.tpp:38-52: the hole at the root takes the smaller child — the right one only when STRICTLY
-    // smaller than the left — while that child is STRICTLY smaller than the sinking key.
-    // LMAX = deepest level that still holds entries: the path is followed, and written back, no further (the heap
-    // shrinks from 256 entries to one during the merge: on average two levels less than the full eight)
-    template <int LMAX>
-    __device__ __forceinline__ void sink_flat(uint32_t lo, uint32_t hi, uint32_t it) {
-        uint32_t pos[LMAX + 1], clo[LMAX + 1], chi[LMAX + 1], cit[LMAX + 1];   // the min-child path: entry (clo, chi, cit)[l] at (l, pos[l])
-        pos[0] = 0; clo[0] = lo; chi[0] = hi; cit[0] = it;       // level 0 is the hole itself
-        uint32_t moves = 0;                                      // children that move up
-        bool going = true;
-#pragma unroll
-        for (int l = 0; l < LMAX; ++l) {
-            const uint32_t li = ((2u << l) - 1u) + 2u * pos[l];  // heap index of the left child
-            uint32_t llo, lhi, lit, rlo, rhi, rit;
-            get_dyn(l + 1, 2u * pos[l], llo, lhi, lit);
-            get_dyn(l + 1, 2u * pos[l] + 1u, rlo, rhi, rit);     // (level 8 holds one entry: both reads return it, the right one is never valid)
-            const bool right = li + 1u < hn && lt(rlo, rhi, llo, lhi);
-            clo[l + 1] = right ? rlo : llo; chi[l + 1] = right ? rhi : lhi; cit[l + 1] = right ? rit : lit;
-            pos[l + 1] = 2u * pos[l] + (right ? 1u : 0u);
-            going = going && li < hn && lt(clo[l + 1], chi[l + 1], lo, hi);
-            moves += going ? 1u : 0u;
-        }
-#pragma unroll
-        for (int l = 0; l <= LMAX; ++l) {
-            // level l gets: its child's entry if that child moved up, the sinking entry at level `moves`, else itself
-            const bool from_child = uint32_t(l) < moves;
-            const bool self = uint32_t(l) > moves;
-            const int c = l < LMAX ? l + 1 : LMAX;
-            const uint32_t wlo = from_child ? clo[c] : self ? clo[l] : lo;
-            const uint32_t whi = from_child ? chi[c] : self ? chi[l] : hi;
-            const uint32_t wit = from_child ? cit[c] : self ? cit[l] : it;
-            put_dyn(l, pos[l], wlo, whi, wit);
-        }
-    }
-    // src/min_pq.tpp:9-15: returns the minimum's item and key; the last entry sinks from the root
-    __device__ __forceinline__ uint32_t pop(uint32_t &mlo, uint32_t &mhi) {
-        uint32_t top;
-        get<0>(0, mlo, mhi, top);
+
+    // src/min_pq.tpp:9-15 + 38-52: returns the minimum's item and key; the last entry sinks from the root
+    __device__ __forceinline__ uint32_t pop(Key &mkey) {
+        const Ent top = e[1];
+        const Ent last = e[hn];
         --hn;
-        const uint32_t level = 31u - uint32_t(__builtin_clz(hn + 1u));
-        const uint32_t pos = hn + 1u - (1u << level);
-        uint32_t lo, hi, it;
-        switch (level) {                                          // the last entry leaves (level, pos) and sinks from the root
-            case 0: get<0>(pos, lo, hi, it); sink_flat<0>(lo, hi, it); break;
-            case 1: get<1>(pos, lo, hi, it); sink_flat<1>(lo, hi, it); break;
-            case 2: get<2>(pos, lo, hi, it); sink_flat<2>(lo, hi, it); break;
-            case 3: get<3>(pos, lo, hi, it); sink_flat<3>(lo, hi, it); break;
-            case 4: get<4>(pos, lo, hi, it); sink_flat<4>(lo, hi, it); break;
-            case 5: get<5>(pos, lo, hi, it); sink_flat<5>(lo, hi, it); break;
-            case 6: get<6>(pos, lo, hi, it); sink_flat<6>(lo, hi, it); break;
-            case 7: get<7>(pos, lo, hi, it); sink_flat<7>(lo, hi, it); break;
-            default: get<8>(pos, lo, hi, it); sink_flat<8>(lo, hi, it); break;
-        }
-        return top;
+        // preferred-child bits of nodes n = lane and n = 64 + lane, for the heap without its last entry
+        const Ent l0 = e[2u * lane], r0 = e[2u * lane + 1u], l1 = e[128u + 2u * lane], r1 = e[129u + 2u * lane];
+        const unsigned long long pa = __ballot(2u * lane + 1u <= hn && r0.key < l0.key);
+        const unsigned long long pb = __ballot(129u + 2u * lane <= hn && r1.key < l1.key);
+        mkey = uni_key(top.key);
+        const uint32_t titem = uni(top.item);
+        if (hn == 0) return titem;
+        // the path of the hole, chased to level 7 whatever the heap's depth: levels past the last occupied one are
+        // never used (their nodes are > hn) and do not change the path above them
+        uint32_t n = 1;
+#pragma unroll
+        for (int l = 0; l < 7; ++l) n = 2u * n + uint32_t(((l < 6 ? pa : pb) >> (n & 63u)) & 1u);
+        // lane l = level l of the path: its entry, and (lanes 0..6) its child's on the path
+        const uint32_t pn = lane < 8u ? n >> (7u - lane) : HEAP_SPARE + lane;
+        const uint32_t cn = lane < 7u ? n >> (6u - lane) : pn;
+        const Ent pe = e[pn];
+        const Ent ce = e[cn];
+        const uint32_t moves = uint32_t(__popcll(__ballot(lane >= 1u && pn <= hn && pe.key < last.key)));
+        const bool up = lane < moves, here = lane == moves;        // (every lane writes: see push)
+        e[pn] = Ent{up ? ce.key : here ? last.key : pe.key, up ? ce.item : here ? last.item : pe.item};
+        return titem;
     }
 };
 
@@ -250,6 +111,7 @@ struct TreeLds {
     uint16_t *left, *right, *parent, *height;
     uint8_t *sym;
     unsigned long long *weight;
+    uint4 *heap;                                                       // HEAP_SLOTS entries of LdsHeap
 };
 
 // src/huffman.cpp:131-164 for one context: nleaf leaves are already laid out (ascending symbol order) in
@@ -258,21 +120,21 @@ struct TreeLds {
 template <bool K64>
 __device__ __forceinline__ void merge_context(const TreeLds &t, uint32_t nleaf, uint32_t lane, uint32_t &nn_out, uint32_t &root_out,
                                               uint32_t &single_out) {
-    RegHeap<K64> h;
-#pragma unroll
-    for (int i = 0; i < 10; ++i) { h.klo[i] = 0; h.khi[i] = 0; h.itm[i] = 0; }
+    using Heap = LdsHeap<K64>;
+    using Key = typename Heap::Key;
+    Heap h{reinterpret_cast<typename Heap::Ent *>(t.heap), lane};
     for (uint32_t i = 0; i < nleaf; ++i) {                            // :134-138 ascending symbol order
         const unsigned long long w = t.weight[i];
-        h.push(RegHeap<K64>::uni(uint32_t(w)), RegHeap<K64>::uni(uint32_t(w >> 32)), i);   // height 0
+        h.push(Key(w), i);                                             // height 0
     }
     uint32_t nn = nleaf;
     while (h.hn > 1) {                                                 // :143-151
-        uint32_t alo, ahi, blo, bhi;
-        uint32_t a = h.pop(alo, ahi), b = h.pop(blo, bhi);
+        Key ka, kb;
+        uint32_t a = h.pop(ka), b = h.pop(kb);
         if ((a >> 16) > (b >> 16)) {                                   // :147-149 the lower subtree goes left
             uint32_t x = a; a = b; b = x;
         }
-        const unsigned long long w = ((unsigned long long)(ahi) << 32 | alo) + ((unsigned long long)(bhi) << 32 | blo);
+        const unsigned long long w = (unsigned long long)(ka) + (unsigned long long)(kb);
         const uint32_t ha = a >> 16, hb = b >> 16, hnew = (ha > hb ? ha : hb) + 1u;
         const uint32_t ia = a & 0xFFFFu, ib = b & 0xFFFFu;
         if (lane == 0) {
@@ -280,11 +142,11 @@ __device__ __forceinline__ void merge_context(const TreeLds &t, uint32_t nleaf, 
             t.weight[nn] = w; t.height[nn] = uint16_t(hnew);
             t.parent[ia] = t.parent[ib] = uint16_t(nn);
         }
-        h.push(uint32_t(w), uint32_t(w >> 32), nn | (hnew << 16));
+        h.push(Key(w), nn | (hnew << 16));
         ++nn;
     }
-    uint32_t rlo, rhi;
-    const uint32_t root = h.pop(rlo, rhi) & 0xFFFFu;                   // :152
+    Key kr;
+    const uint32_t root = h.pop(kr) & 0xFFFFu;                         // :152
     single_out = 0;
     if (nleaf == 1) {                                                  // :154-162 one-symbol context
         if (lane == 0) {
@@ -310,6 +172,7 @@ __global__ __launch_bounds__(64) void tree_build_kernel(const unsigned long long
     __shared__ uint16_t left[TB_NODE_STRIDE], right[TB_NODE_STRIDE], parent[TB_NODE_STRIDE], height[TB_NODE_STRIDE];
     __shared__ uint8_t sym[TB_NODE_STRIDE];
     __shared__ unsigned long long weight[TB_NODE_STRIDE];
+    __shared__ uint4 heap[HEAP_SLOTS];
     __shared__ uint8_t olen[256];
     __shared__ unsigned long long ocode[256];
     __shared__ uint32_t prof[9];
@@ -341,7 +204,7 @@ __global__ __launch_bounds__(64) void tree_build_kernel(const unsigned long long
     }
     __syncthreads();
     {
-        const TreeLds t{left, right, parent, height, sym, weight};
+        const TreeLds t{left, right, parent, height, sym, weight, heap};
         uint32_t nn = 0, root = 0xFFFFFFFFu, single = 0;
         if (nleaf > 0) {
             // 32-bit keys when every weight that can appear (the root's is the context total) fits
