@@ -47,7 +47,8 @@ enum {
     MH_ERR_CORRUPT = -4,       /* stream not decodable (src/coding.cpp:103-106)          */
     MH_ERR_TYPE = -5,          /* stream/table type mismatch (src/coding.cpp:107-110)    */
     MH_ERR_BADTABLE = -6,      /* table file not parseable (src/huffman.cpp:166-172)     */
-    MH_ERR_CODE_TOO_LONG = -7, /* a codeword exceeds 64 bits (not reachable < 2^44 B)    */
+    MH_ERR_CODE_TOO_LONG = -7, /* a codeword exceeds 64 bits (not reachable < 2^44 B;
+                                  never with a length-limited model)                   */
     MH_ERR_CAPACITY = -8,      /* output buffer or workspace too small                   */
     MH_ERR_TIMEOUT = -9,       /* bounded device-side wait expired (should not happen)   */
     MH_ERR_NOMEM = -10,
@@ -105,6 +106,25 @@ int mh_dev_model_from_counts(const uint64_t *d_counts, int order, void *stream, 
  * model has been freed and the work that uses it has finished.  MH_ERR_CAPACITY when it is too small. */
 size_t mh_dev_model_workspace(int order);
 int mh_dev_model_from_counts_ws(const uint64_t *d_counts, int order, void *d_ws, size_t ws_bytes, void *stream, mh_model **out);
+
+/* Length-limited models (extension): no code of the model is longer than `max_len` bits, at the smallest
+ * possible cost in payload bits.  Per context: the reference tree is built as above; when its depth is <= max_len it is
+ * kept unchanged, otherwise the whole context is re-coded with the lengths package-merge gives (leaves ordered by count,
+ * then symbol; on equal weight a leaf precedes a package) and canonical codewords (order: length, then symbol; first
+ * code all zero bits).  The result is an ordinary mh_model: every call takes it, its table file is a valid reference
+ * table (the file stores the tree), and a model whose trees all fit the limit is the model of the unlimited call, byte
+ * for byte.  With max_len <= 12 the encoders never take an escape route and the decoders' second level resolves every code.
+ * max_len: 8..64, or 0 = no limit (exactly the unlimited call).  Order 0 and 1; order 2 and any other max_len:
+ * MH_ERR_ARG, before a device is touched.  Package weights are sums of at most max_len context totals and are held in
+ * 64 bits: a context that has to be re-coded and whose counts add up to 2^56 or more is refused with MH_ERR_ARG (not
+ * handled in wider arithmetic).
+ * The device calls follow their unlimited twins (order 0 takes the host route; _ws: order 1 only, no allocation, one
+ * synchronisation).  The contexts over the limit are re-coded by one more kernel on `stream` (limit_recode_kernel, one wave
+ * each, all state in LDS) that rewrites their part of the images in place: mh_dev_model_workspace(1) does not grow. */
+int mh_model_from_counts_limited(const uint64_t *counts, int order, int max_len, mh_model **out);
+int mh_dev_model_from_counts_limited(const uint64_t *d_counts, int order, int max_len, void *stream, mh_model **out);
+int mh_dev_model_from_counts_limited_ws(const uint64_t *d_counts, int order, int max_len, void *d_ws, size_t ws_bytes, void *stream,
+                                        mh_model **out);
 
 /* Replaces the table-file constructors huffman_table(bitbuffer&) / markov_huffman_table(bitbuffer&)
  * (src/huffman.cpp:22-25,166-172; src/markov_huffman.cpp:15-25) and main()'s type sniffing on the

@@ -30,6 +30,7 @@ EXPORTS = [
     "mh_strerror", "mh_last_hip_error", "mh_last_index_path", "mh_last_encode_retries", "mh_total_encode_retries", "mh_device_count", "mh_set_device",
     "mh_dev_malloc", "mh_dev_free", "mh_dev_upload", "mh_dev_download",
     "mh_model_from_counts", "mh_dev_model_from_counts", "mh_dev_model_workspace", "mh_dev_model_from_counts_ws",
+    "mh_model_from_counts_limited", "mh_dev_model_from_counts_limited", "mh_dev_model_from_counts_limited_ws",
     "mh_model_from_table_bits", "mh_model_write_table",
     "mh_model_type", "mh_model_max_code_len", "mh_model_min_code_len", "mh_model_get_code", "mh_model_get_lut", "mh_model_decode_layout", "mh_model_tile_layout",
     "mh_model_image", "mh_model_free",
@@ -96,6 +97,9 @@ def lib():
         l.mh_dev_model_workspace.argtypes = [i32]
         l.mh_dev_model_workspace.restype = sz
         l.mh_dev_model_from_counts_ws.argtypes = [vp, i32, vp, sz, vp, C.POINTER(vp)]
+        l.mh_model_from_counts_limited.argtypes = [vp, i32, i32, C.POINTER(vp)]
+        l.mh_dev_model_from_counts_limited.argtypes = [vp, i32, i32, vp, C.POINTER(vp)]
+        l.mh_dev_model_from_counts_limited_ws.argtypes = [vp, i32, i32, vp, sz, vp, C.POINTER(vp)]
         l.mh_model_from_table_bits.argtypes = [vp, sz, C.POINTER(vp)]
         l.mh_model_write_table.argtypes = [vp, vp, sz, psz]
         l.mh_model_type.argtypes = [vp]
@@ -130,6 +134,7 @@ def lib():
         l.mh_dev_encode_workspace.restype = sz
         l.mh_dev_encode.argtypes = [vp, vp, sz, u8, vp, sz, vp, vp, u32, vp, sz, vp]
         l.mh_dev_payload_bits.argtypes = [vp, vp, vp, vp]
+        l.mh_model_payload_bits.argtypes = [vp, vp, pu64]
         l.mh_dev_encode_at.argtypes = [vp, vp, sz, u8, vp, vp, sz, vp, vp, u32, vp, sz, vp]
         l.mh_dev_encode_ctx.argtypes = [vp, vp, sz, u32, vp, vp, sz, vp, vp, u32, vp, sz, vp]
         l.mh_dev_encode_hist.argtypes = [vp, vp, sz, u8, vp, vp, sz, vp, vp, u32, vp, sz, vp, sz, vp]
@@ -466,27 +471,39 @@ class Model:
         self._h = handle
 
     @classmethod
-    def from_counts(cls, counts, order):
+    def from_counts(cls, counts, order, max_len=0):
+        """max_len (8..64, order 0 / 1): no code longer than that, at the least cost in bits; 0 = no limit."""
         c = np.ascontiguousarray(counts, dtype=np.uint64)
         if c.size != {0: 256, 1: 65536, 2: 1 << 24}[order]:
             raise ValueError("counts size")
         h = C.c_void_p()
-        _check(lib().mh_model_from_counts(c.ctypes.data, order, C.byref(h)), "mh_model_from_counts")
+        if max_len:
+            _check(lib().mh_model_from_counts_limited(c.ctypes.data, order, max_len, C.byref(h)), "mh_model_from_counts_limited")
+        else:
+            _check(lib().mh_model_from_counts(c.ctypes.data, order, C.byref(h)), "mh_model_from_counts")
         return cls(h)
 
     @classmethod
-    def from_device_counts(cls, d_counts_ptr, order, stream=None):
+    def from_device_counts(cls, d_counts_ptr, order, stream=None, max_len=0):
         h = C.c_void_p()
-        _check(lib().mh_dev_model_from_counts(d_counts_ptr, order, stream, C.byref(h)), "mh_dev_model_from_counts")
+        if max_len:
+            _check(lib().mh_dev_model_from_counts_limited(d_counts_ptr, order, max_len, stream, C.byref(h)),
+                   "mh_dev_model_from_counts_limited")
+        else:
+            _check(lib().mh_dev_model_from_counts(d_counts_ptr, order, stream, C.byref(h)), "mh_dev_model_from_counts")
         return cls(h)
 
     @classmethod
-    def from_device_counts_ws(cls, d_counts_ptr, order, d_ws_ptr, ws_bytes, stream=None):
+    def from_device_counts_ws(cls, d_counts_ptr, order, d_ws_ptr, ws_bytes, stream=None, max_len=0):
         """Model built into a caller workspace (no allocation inside, one stream sync); the caller keeps
         the workspace alive for as long as the model is used."""
         h = C.c_void_p()
-        _check(lib().mh_dev_model_from_counts_ws(d_counts_ptr, order, d_ws_ptr, ws_bytes, stream, C.byref(h)),
-               "mh_dev_model_from_counts_ws")
+        if max_len:
+            _check(lib().mh_dev_model_from_counts_limited_ws(d_counts_ptr, order, max_len, d_ws_ptr, ws_bytes, stream, C.byref(h)),
+                   "mh_dev_model_from_counts_limited_ws")
+        else:
+            _check(lib().mh_dev_model_from_counts_ws(d_counts_ptr, order, d_ws_ptr, ws_bytes, stream, C.byref(h)),
+                   "mh_dev_model_from_counts_ws")
         return cls(h)
 
     @classmethod
@@ -521,6 +538,15 @@ class Model:
     @property
     def min_code_len(self):
         return lib().mh_model_min_code_len(self._h)
+
+    def payload_bits(self, counts):
+        """Exact payload bits of data with this histogram (host counts: 65536 for a Markov model, 256 for a Huffman model)."""
+        c = np.ascontiguousarray(counts, dtype=np.uint64)
+        if c.size != (65536 if self.type else 256):
+            raise ValueError("counts size")
+        n = C.c_uint64(0)
+        _check(lib().mh_model_payload_bits(self._h, c.ctypes.data, C.byref(n)), "mh_model_payload_bits")
+        return n.value
 
     def decode_layout(self):
         """(primary_bits, secondary_entries, in_lds) of the device decode tables."""

@@ -1,6 +1,7 @@
 // mh_api_model.cpp — models behind the C ABI (include/mh.h): built from counts on the host or on the device, loaded from and
 // written to table files, queried; the order-2 extension's builds.
 #include "mh_api_internal.hpp"
+#include "mh_limit.hpp"
 
 namespace mhapi {
 
@@ -118,21 +119,25 @@ static int model2_from_host_counts(const uint64_t *counts, mh_model **out) {
     return mh_dev_model_from_counts(d_counts.as<uint64_t>(), 2, nullptr, out);
 }
 
-int mh_model_from_counts(const uint64_t *counts, int order, mh_model **out) {
-    if (counts && out && order == 2) return model2_from_host_counts(counts, out);
-    if (!counts || !out || (order != 0 && order != 1)) return MH_ERR_ARG;
+int mh_model_from_counts_limited(const uint64_t *counts, int order, int max_len, mh_model **out) {
+    if (!counts || !out || (order != 0 && order != 1) || !mh::limit_valid(max_len)) return MH_ERR_ARG;
     mh_model *m = new (std::nothrow) mh_model;
     if (!m) return MH_ERR_NOMEM;
-    m->host.build_from_counts(counts, order);
+    if (!mh::build_model_limited(m->host, counts, order, max_len)) { delete m; return MH_ERR_ARG; }   // a context total of 2^56 or more
     return finish_model(m, out);
 }
 
-static int model_from_device_counts_via_host(const uint64_t *d_counts, int order, hipStream_t st, mh_model **out) {
+int mh_model_from_counts(const uint64_t *counts, int order, mh_model **out) {
+    if (counts && out && order == 2) return model2_from_host_counts(counts, out);
+    return mh_model_from_counts_limited(counts, order, 0, out);
+}
+
+static int model_from_device_counts_via_host(const uint64_t *d_counts, int order, int max_len, hipStream_t st, mh_model **out) {
     size_t ncount = order ? 65536 : 256;
     std::vector<uint64_t> counts(ncount);
     HIP_TRY(hipMemcpyAsync(counts.data(), d_counts, ncount * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    return mh_model_from_counts(counts.data(), order, out);
+    return mh_model_from_counts_limited(counts.data(), order, max_len, out);
 }
 
 // Fixed-size part of a device-built model: every image + the node arrays, each piece 256-byte aligned.
@@ -159,7 +164,8 @@ constexpr size_t MODEL_WS_TILE_BYTES = size_t(65536) * 2 + 256 + size_t(32768) *
 // d_ws == nullptr: the model allocates (and owns) its device memory.  Otherwise it lives in the caller's
 // workspace: no allocation, and the stream is synchronised exactly once (16 KiB of table sizes come back
 // so that the host can pick the decode-table layout).
-int dev_model_build(const uint64_t *d_counts, void *d_ws, size_t ws_bytes, hipStream_t st, mh_model **out) {
+// max_len > 0: the contexts deeper than max_len bits are re-coded in place (limit_recode_kernel) before the sizes come back.
+int dev_model_build(const uint64_t *d_counts, int max_len, void *d_ws, size_t ws_bytes, hipStream_t st, mh_model **out) {
     mh_model *m = new (std::nothrow) mh_model;
     if (!m) return MH_ERR_NOMEM;
     m->type = 1;
@@ -193,6 +199,7 @@ int dev_model_build(const uint64_t *d_counts, void *d_ws, size_t ws_bytes, hipSt
     mhk::TreeBuildOut tb{m->d_len8, reinterpret_cast<unsigned long long *>(m->d_code64), m->d_enc16, m->d_len_slot,
                          m->d_node_left, m->d_node_right, m->d_node_sym, d_node_height, m->d_meta, 8u};
     HIP_TRY_M(mhk::launch_tree_build(reinterpret_cast<const unsigned long long *>(d_counts), 256, tb, st));
+    if (max_len > 0) HIP_TRY_M(mhk::launch_tree_limit(reinterpret_cast<const unsigned long long *>(d_counts), 256, uint32_t(max_len), tb, st));
     // (a pinned landing place, one per thread, kept for the life of the process — 16 KiB; freeing it from a destructor at exit
     // would call into a runtime that may already be gone: a copy into pageable memory is staged by the runtime)
     struct PinnedMeta { uint32_t *p = nullptr; };
@@ -222,6 +229,7 @@ int dev_model_build(const uint64_t *d_counts, void *d_ws, size_t ws_bytes, hipSt
         for (int P = 0; P < 9; ++P) { tot[P] += mt[4 + P]; worst[P] = std::max(worst[P], size_t(mt[4 + P])); }
         weight[c] = (uint64_t(mt[14]) << 32) | mt[13];
     }
+    if (max_len > 0 && m->max_len > max_len) return fail(MH_ERR_ARG);   // the kernel left a context of 2^56 symbols or more as it was
     if (m->max_len > mh::MAX_CODE_BITS) { *out = m; return MH_OK; }   // compute calls report MH_ERR_CODE_TOO_LONG
     int P = 0;
     for (int q = 8; q >= 4 && !P; --q)
@@ -636,13 +644,18 @@ int model2_write_table(const mh_model *m, std::vector<uint8_t> &out) {
 
 size_t mh_dev_model_workspace(int order) { return order == 1 ? build_layout().fixed + MODEL_WS_SEC_BYTES + MODEL_WS_TILE_BYTES : 0; }
 
-int mh_dev_model_from_counts_ws(const uint64_t *d_counts, int order, void *d_ws, size_t ws_bytes, void *stream, mh_model **out) {
-    if (!d_counts || !out || order != 1 || !d_ws) return MH_ERR_ARG;
+int mh_dev_model_from_counts_limited_ws(const uint64_t *d_counts, int order, int max_len, void *d_ws, size_t ws_bytes, void *stream,
+                                        mh_model **out) {
+    if (!d_counts || !out || order != 1 || !d_ws || !mh::limit_valid(max_len)) return MH_ERR_ARG;
     if (!have_device()) return MH_ERR_NO_DEVICE;
-    const int rc = dev_model_build(d_counts, d_ws, ws_bytes, static_cast<hipStream_t>(stream), out);
+    const int rc = dev_model_build(d_counts, max_len, d_ws, ws_bytes, static_cast<hipStream_t>(stream), out);
     // the rare model the device packer does not lay out: built on the host instead (that model owns its memory)
-    if (rc == BUILD_NEEDS_HOST) return model_from_device_counts_via_host(d_counts, order, static_cast<hipStream_t>(stream), out);
+    if (rc == BUILD_NEEDS_HOST) return model_from_device_counts_via_host(d_counts, order, max_len, static_cast<hipStream_t>(stream), out);
     return rc;
+}
+
+int mh_dev_model_from_counts_ws(const uint64_t *d_counts, int order, void *d_ws, size_t ws_bytes, void *stream, mh_model **out) {
+    return mh_dev_model_from_counts_limited_ws(d_counts, order, 0, d_ws, ws_bytes, stream, out);
 }
 
 size_t mh_dev_model2_workspace(void) { return build2_layout().total; }
@@ -671,15 +684,21 @@ int mh_dev_model2_finish(void *d_ws, size_t ws_bytes, void *stream, mh_model **o
     return build2_finish(static_cast<unsigned char *>(d_ws), false, static_cast<hipStream_t>(stream), out);
 }
 
-int mh_dev_model_from_counts(const uint64_t *d_counts, int order, void *stream, mh_model **out) {
-    if (!d_counts || !out || order < 0 || order > 2) return MH_ERR_ARG;
+int mh_dev_model_from_counts_limited(const uint64_t *d_counts, int order, int max_len, void *stream, mh_model **out) {
+    if (!d_counts || !out || (order != 0 && order != 1) || !mh::limit_valid(max_len)) return MH_ERR_ARG;
     if (!have_device()) return MH_ERR_NO_DEVICE;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (order == 2) return dev_model_build2(d_counts, st, out);
-    if (order == 0) return model_from_device_counts_via_host(d_counts, order, st, out);   // one tree: not worth a kernel
-    int rc = dev_model_build(d_counts, nullptr, 0, st, out);
-    if (rc == BUILD_NEEDS_HOST) return model_from_device_counts_via_host(d_counts, order, st, out);
+    if (order == 0) return model_from_device_counts_via_host(d_counts, order, max_len, st, out);   // one tree: not worth a kernel
+    int rc = dev_model_build(d_counts, max_len, nullptr, 0, st, out);
+    if (rc == BUILD_NEEDS_HOST) return model_from_device_counts_via_host(d_counts, order, max_len, st, out);
     return rc;
+}
+
+int mh_dev_model_from_counts(const uint64_t *d_counts, int order, void *stream, mh_model **out) {
+    if (!d_counts || !out || order < 0 || order > 2) return MH_ERR_ARG;
+    if (order != 2) return mh_dev_model_from_counts_limited(d_counts, order, 0, stream, out);
+    if (!have_device()) return MH_ERR_NO_DEVICE;
+    return dev_model_build2(d_counts, static_cast<hipStream_t>(stream), out);
 }
 
 int mh_model_from_table_bits(const uint8_t *bytes, size_t n, mh_model **out) {

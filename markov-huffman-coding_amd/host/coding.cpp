@@ -244,10 +244,11 @@ void construct_table(FILE* input_fd, int order, uint64_t* counts64) {
 
 i_coding_provider::~i_coding_provider() { mh_model_free(model_); }
 
-void i_coding_provider::build_from_counts(const uint64_t* counts, int order) {
+void i_coding_provider::build_from_counts(const uint64_t* counts, int order, int max_code_len) {
     counts_.assign(counts, counts + (order == 2 ? (size_t(1) << 24) : order ? 65536 : 256));     // kept: compress() sizes its output from them
     mh_model* m = nullptr;
-    mh_or_die(mh_model_from_counts(counts, order, &m), "table build");
+    mh_or_die(max_code_len ? mh_model_from_counts_limited(counts, order, max_code_len, &m) : mh_model_from_counts(counts, order, &m),
+              "table build");
     adopt(m);
 }
 
@@ -510,14 +511,14 @@ static std::vector<uint64_t> widen_counts(const int* counts, size_t n) {
 }
 
 huffman_table::huffman_table(int* counts) { build_from_counts(widen_counts(counts, 256).data(), 0); }
-huffman_table::huffman_table(const uint64_t* counts) { build_from_counts(counts, 0); }
+huffman_table::huffman_table(const uint64_t* counts, int max_code_len) { build_from_counts(counts, 0, max_code_len); }
 huffman_table::huffman_table(bitbuffer& buffer) { build_from_buffer(buffer, 0); }
 bool huffman_table::empty() { return context_empty(0); }
 void huffman_table::print_table() { print_table_for(0); }
 void huffman_table::print_tree() { print_tree_for(0, false, 0, ""); }
 
 markov_huffman_table::markov_huffman_table(int* counts) { build_from_counts(widen_counts(counts, 65536).data(), 1); }
-markov_huffman_table::markov_huffman_table(const uint64_t* counts) { build_from_counts(counts, 1); }
+markov_huffman_table::markov_huffman_table(const uint64_t* counts, int max_code_len) { build_from_counts(counts, 1, max_code_len); }
 markov_huffman_table::markov_huffman_table(bitbuffer& buffer) { build_from_buffer(buffer, 1); }
 
 // order-2 extension (parity unpinned; include/mh.h): 65536 two-byte contexts

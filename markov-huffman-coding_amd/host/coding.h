@@ -62,7 +62,7 @@ public:
 protected:
     i_coding_provider() = default;
     void adopt(mh_model* m) { model_ = m; }
-    void build_from_counts(const uint64_t* counts, int order);
+    void build_from_counts(const uint64_t* counts, int order, int max_code_len = 0);   // max_code_len: see mh_model_from_counts_limited
     void build_from_buffer(bitbuffer& buffer, int expected_type);
     void print_table_for(int prev);
     int print_tree_for(int prev, bool subgraph, int n, const std::string& label);
@@ -84,7 +84,7 @@ private:
 class huffman_table : public i_coding_provider {
 public:
     explicit huffman_table(int* counts);          // src/huffman.h:14 (256 ints)
-    explicit huffman_table(const uint64_t* counts);
+    explicit huffman_table(const uint64_t* counts, int max_code_len = 0);
     explicit huffman_table(bitbuffer& buffer);    // src/huffman.h:15
     bool empty();
     void print_table() override;
@@ -97,7 +97,7 @@ private:
 class markov_huffman_table : public i_coding_provider {
 public:
     explicit markov_huffman_table(int* counts);   // src/markov_huffman.h:12 (65536 ints)
-    explicit markov_huffman_table(const uint64_t* counts);
+    explicit markov_huffman_table(const uint64_t* counts, int max_code_len = 0);
     explicit markov_huffman_table(bitbuffer& buffer);   // src/markov_huffman.h:13
     void print_table() override;
     void print_tree() override;

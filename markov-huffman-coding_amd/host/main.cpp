@@ -34,6 +34,7 @@ static void print_help() {
     eprintf("\t--index file   chunk-index sidecar for parallel extraction (MI355X extension)\n");
     eprintf("\t--chunk n      symbols per index entry (default 1024)\n");
     eprintf("\t--order2       contexts of two previous bytes (MI355X extension; own file formats)\n");
+    eprintf("\t--max-code-len n  no code longer than n bits, 8..64 (MI355X extension; when training a table: not with -e, -x, --order2)\n");
     eprintf("\t--device n     HIP device ordinal\n");
     eprintf("\t--range b:e    with -x and --index: extract only bytes [b, e) (repeatable, concatenated in order)\n");
 }
@@ -47,6 +48,7 @@ struct options {
     std::string index_path;
     uint32_t chunk = MH_CHUNK_DEFAULT;
     bool order2 = false;
+    int max_code_len = 0;                                         // 0: no limit
     int device = -1;
     std::vector<uint64_t> ranges;                                 // begin, end per --range
 };
@@ -85,6 +87,16 @@ static options parse(int argc, char* argv[]) {
             }
             else if (!strcmp(a, "--device")) o.device = atoi(need(a));
             else if (!strcmp(a, "--order2")) o.order2 = true;
+            else if (!strcmp(a, "--max-code-len")) {
+                const char* v = need(a);
+                char* end = nullptr;
+                const long n = strtol(v, &end, 10);
+                if (!*v || *end || n < 8 || n > 64) {
+                    eprintf("Error: --max-code-len must be between 8 and 64.\n");
+                    exit(1);
+                }
+                o.max_code_len = (int)n;
+            }
             else if (!strcmp(a, "--range")) {
                 const char* v = need(a);
                 uint64_t b = 0, e = 0;
@@ -152,6 +164,11 @@ int main(int argc, char* argv[]) {
         }
     }
 
+    if (o.max_code_len && (o.encoding_input || o.extract || o.order2)) {
+        eprintf("Error: --max-code-len limits a table that is being trained; it cannot be combined with -e, -x or --order2.\n");
+        exit(1);
+    }
+
     // validation of src/main.cpp:103-115
     if (!o.input) {
         eprintf("Error: Must provide input file.\n");
@@ -206,11 +223,11 @@ int main(int argc, char* argv[]) {
         } else if (o.simple_huffman) {
             eprintf("Building simple Huffman encoding table from input...\n");
             construct_table(input_fd, 0, counts.data());
-            coder = new huffman_table(counts.data());
+            coder = new huffman_table(counts.data(), o.max_code_len);
         } else {
             eprintf("Building Markov-Huffman encoding table from input...\n");
             construct_table(input_fd, 1, counts.data());
-            coder = new markov_huffman_table(counts.data());
+            coder = new markov_huffman_table(counts.data(), o.max_code_len);
         }
         fseek(input_fd, 0, SEEK_SET);                              // src/main.cpp:183
     }
