@@ -914,6 +914,70 @@ int mh_decode_bank(const mh_model_set *bank, const uint32_t *choice, const uint8
                    const uint64_t *index, uint32_t chunk_symbols, int32_t *stream_status);
 
 /* ---------------------------------------------------------------------------------------------------------------------
+ * SEARCH IN BATCHES — which streams of a batch contain which byte strings, and where, without writing the decoded bytes:
+ * the batch decoders hold every decoded byte in a register for one step, and here that byte feeds a matcher instead of a
+ * store.  No buffer for the original data is needed; the workspace is a few bytes per chunk.  Order 0 and order 1; an
+ * order-2 model is MH_ERR_ARG before any launch.  The batch is described exactly as for mh_dev_decode_batch /
+ * mh_dev_decode_each (payload layout, pay_off, nbits, prev0, sym_off and the index slices of mh_batch_index_base, the same
+ * alignment rules and up-front checks with the same statuses); a bank view of mh_dev_model_set_pick is a set.
+ *   - A pattern set is a host object (no device needed): up to MH_FIND_MAX_POSITIONS bytes of patterns in all, pattern j =
+ *     bytes[pat_off[j] .. pat_off[j+1]), any byte values.  MH_ERR_ARG for n_patterns == 0, an empty pattern, pat_off[0] != 0,
+ *     decreasing offsets, a total over MH_FIND_MAX_POSITIONS, unknown flag bits, null pointers.  Equal patterns may appear
+ *     twice; each reports its own hits.  With MH_FIND_FOLD_ASCII 'A'..'Z' and 'a'..'z' match each other, in the pattern and
+ *     in the data; no other byte is folded.  The matcher is Shift-And over one 64-bit word: pattern j owns len_j bits.
+ *   - A hit is an occurrence of pattern j at bytes [begin, end) of ONE stream's decoded message, end - begin = len_j, counted
+ *     from the start of that stream.  Overlapping occurrences all count (`aa` occurs three times in `aaaa`).  Nothing
+ *     matches across a stream boundary; a stream shorter than a pattern has no hit of it.
+ *   - d_hit_off[n + 1] (written in full, also count-only and when the hits do not fit) is the exclusive scan of the streams'
+ *     hit counts; d_hit_off[n] is the total.
+ *   - Record r is d_hits[3r .. 3r+2] = (stream, begin, end) and d_hit_pattern[r] = j (d_hit_pattern may be NULL); stream i's
+ *     records are [d_hit_off[i], d_hit_off[i+1]).  The records are the lookups of mh_dev_decode_batch_ranges as they are.
+ *     Their order is fixed: ascending (stream, end, pattern number), whatever chunk_symbols is, with or without an index.
+ *     d_hits == NULL: count only.
+ *   - Records with number >= hit_cap are not written, nothing is written at or beyond hit_cap records, and the workspace
+ *     status is MH_ERR_CAPACITY; the records below hit_cap are the true prefix.
+ *   - d_stream_status[n] (may be NULL): for every stream the verdict mh_dev_decode_batch / mh_dev_decode_each gives the same
+ *     arguments (indexed: every chunk gives its symbols and ends exactly at the next entry, the last at nbits_i; index-free:
+ *     the walk ends exactly at nbits_i with no null table entry; MH_ERR_ARG for nbits_i beyond its payload bytes and,
+ *     index-free, over MH_BATCH_WALK_MAX_BITS).  A failed stream has zero hits in d_hit_off and writes no record; the other
+ *     streams are unaffected.  mh_dev_status(d_ws) keeps one of the errors.
+ *   - Without d_index the call is index-free (one lane walks one stream): d_sym_off may be NULL and is neither read nor
+ *     written, sym_total and chunk_symbols are ignored.  Long index-free streams: mh_dev_batch_states + mh_dev_batch_index
+ *     first.
+ * No allocation, no host synchronisation, a number of launches that does not depend on the data or on n_streams.
+ * d_payload and d_ws 16-byte aligned; d_ws at least mh_dev_find_batch_workspace(n, sym_total, chunk_symbols) bytes
+ * (chunk_symbols 0: index-free).
+ * Host form mh_find_batch: arguments checked before a device is touched, the batch uploaded, the device call run once,
+ * results copied back; returns the first stream's error, else MH_ERR_CAPACITY when the hits do not fit.  Index-free batches
+ * with a stream over MH_BATCH_WALK_MAX_BITS are indexed by mh_index_batch first (chunk MH_CHUNK_DEFAULT) and searched with
+ * that index, so a valid batch is never refused.
+ * --------------------------------------------------------------------------------------------------------------------- */
+typedef struct mh_pattern_set mh_pattern_set;
+#define MH_FIND_MAX_POSITIONS 64          /* sum of the patterns' lengths */
+#define MH_FIND_FOLD_ASCII    1u          /* 'A'..'Z' and 'a'..'z' match each other; no other byte is folded */
+int mh_pattern_set_create(const uint8_t *bytes, const uint32_t *pat_off, size_t n_patterns, uint32_t flags,
+                          mh_pattern_set **out);
+size_t mh_pattern_set_size(const mh_pattern_set *ps);
+int mh_pattern_set_max_len(const mh_pattern_set *ps);
+void mh_pattern_set_free(mh_pattern_set *ps);
+size_t mh_dev_find_batch_workspace(size_t n_streams, uint64_t sym_total, uint32_t chunk_symbols);
+int mh_dev_find_batch(const mh_model *m, const mh_pattern_set *ps, const uint8_t *d_payload, const uint64_t *d_pay_off,
+                      const uint64_t *d_nbits, size_t n_streams, uint64_t pay_total, uint8_t prev0,
+                      const uint64_t *d_sym_off, uint64_t sym_total, const uint64_t *d_index, uint32_t chunk_symbols,
+                      uint64_t *d_hit_off, uint64_t *d_hits, uint32_t *d_hit_pattern, uint64_t hit_cap,
+                      int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream);
+/* The same with stream i under the set's model i (n_streams == mh_model_set_size(s), else MH_ERR_ARG). */
+int mh_dev_find_each(const mh_model_set *s, const mh_pattern_set *ps, const uint8_t *d_payload, const uint64_t *d_pay_off,
+                     const uint64_t *d_nbits, size_t n_streams, uint64_t pay_total, uint8_t prev0,
+                     const uint64_t *d_sym_off, uint64_t sym_total, const uint64_t *d_index, uint32_t chunk_symbols,
+                     uint64_t *d_hit_off, uint64_t *d_hits, uint32_t *d_hit_pattern, uint64_t hit_cap,
+                     int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream);
+int mh_find_batch(const mh_model *m, const mh_pattern_set *ps, const uint8_t *payload, const uint64_t *pay_off,
+                  const uint64_t *nbits, size_t n_streams, uint8_t prev0, const uint64_t *sym_off, const uint64_t *index,
+                  uint32_t chunk_symbols, uint64_t *hit_off, uint64_t *hits, uint32_t *hit_pattern, uint64_t hit_cap,
+                  int32_t *stream_status);
+
+/* ---------------------------------------------------------------------------------------------------------------------
  * SEGMENT STATES OF INDEX-FREE BATCHES — the batch counterpart of mh_dev_build_index: the `.cm` files the reference writes
  * carry no index, and without one the batch decoders above walk each stream with one lane.  Three device steps for a batch
  * of index-free streams under one shared model (mh_dev_batch_*) or a model set (mh_dev_each_*; a bank view of

@@ -59,7 +59,11 @@ EXPORTS = [
     "mh_dev_decode_batch_o2_workspace", "mh_dev_decode_batch_o2", "mh_encode_batch_o2", "mh_decode_batch_o2",
     "mh_dev_decode_ranges_o2_workspace", "mh_dev_decode_ranges_o2", "mh_decode_ranges_o2",
     "mh_dev_decode_batch_o2_ranges_workspace", "mh_dev_decode_batch_o2_ranges", "mh_decode_batch_o2_ranges",
+    "mh_pattern_set_create", "mh_pattern_set_size", "mh_pattern_set_max_len", "mh_pattern_set_free",
+    "mh_dev_find_batch_workspace", "mh_dev_find_batch", "mh_dev_find_each", "mh_find_batch",
 ]
+FIND_MAX_POSITIONS = 64                    # include/mh.h MH_FIND_MAX_POSITIONS
+FIND_FOLD_ASCII = 1                        # include/mh.h MH_FIND_FOLD_ASCII
 BANK_MAX = 64                              # include/mh.h MH_BANK_MAX
 BANK_NONE = 0xFFFFFFFF                     # include/mh.h MH_BANK_NONE
 BATCH_WALK_MAX_BITS = 1 << 23              # include/mh.h MH_BATCH_WALK_MAX_BITS
@@ -263,6 +267,17 @@ def lib():
             fn.argtypes = [vp, vp, vp, vp, sz, u64, u8, vp, u64, vp, vp, sz, vp]
         l.mh_index_batch.argtypes = [vp, vp, vp, vp, sz, u8, u32, vp, vp, u64, vp]
         l.mh_index_each.argtypes = [vp, vp, vp, vp, vp, sz, u8, u32, vp, vp, u64, vp]
+        l.mh_pattern_set_create.argtypes = [vp, vp, sz, u32, C.POINTER(vp)]
+        l.mh_pattern_set_size.argtypes = [vp]
+        l.mh_pattern_set_size.restype = sz
+        l.mh_pattern_set_max_len.argtypes = [vp]
+        l.mh_pattern_set_free.argtypes = [vp]
+        l.mh_pattern_set_free.restype = None
+        l.mh_dev_find_batch_workspace.argtypes = [sz, u64, u32]
+        l.mh_dev_find_batch_workspace.restype = sz
+        for fn in (l.mh_dev_find_batch, l.mh_dev_find_each):
+            fn.argtypes = [vp, vp, vp, vp, vp, sz, u64, u8, vp, u64, vp, u32, vp, vp, vp, u64, vp, vp, sz, vp]
+        l.mh_find_batch.argtypes = [vp, vp, vp, vp, vp, sz, u8, vp, vp, u32, vp, vp, vp, u64, vp]
         _lib = l
     return _lib
 
@@ -462,6 +477,92 @@ def _host_batch_ranges(call, name, lk, nbits, sym_off):
 
 def last_batch_range_upload_bytes():
     return lib().mh_last_batch_range_upload_bytes()
+
+
+# ---- search in batches (include/mh.h, "SEARCH IN BATCHES") -------------------------------------------------------------------
+FIND_GUARD = 8            # guard words of FIND_FILL behind the hit records, the pattern numbers and hit_off
+FIND_FILL = 0xA5A5A5A5A5A5A5A5
+
+
+class PatternSet:
+    """Owns an mh_pattern_set*: up to FIND_MAX_POSITIONS bytes of patterns in all (a host object, no device needed)."""
+
+    def __init__(self, patterns, fold=False, flags=None):
+        pats = [bytes(p) for p in patterns]
+        buf = np.frombuffer(b"".join(pats) or b"\0", dtype=np.uint8)
+        off = np.zeros(len(pats) + 1, dtype=np.uint32)
+        if pats:
+            off[1:] = np.cumsum([len(p) for p in pats])
+        h = C.c_void_p()
+        _check(lib().mh_pattern_set_create(buf.ctypes.data, off.ctypes.data, len(pats),
+                                           (FIND_FOLD_ASCII if fold else 0) if flags is None else flags, C.byref(h)), "mh_pattern_set_create")
+        self._h = h
+        self.patterns = pats
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.mh_pattern_set_free(self._h)
+            self._h = None
+
+    @property
+    def handle(self):
+        return self._h
+
+    def __len__(self):
+        return lib().mh_pattern_set_size(self._h)
+
+    @property
+    def max_len(self):
+        return lib().mh_pattern_set_max_len(self._h)
+
+
+def _dev_find(fn, handle, ps, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols, hit_cap, count_only):
+    """One mh_dev_find_batch / mh_dev_find_each call.  hit_cap None: a count-only call first, then one with room for every
+    hit.  Returns (hit_off[n + 1], hits[k, 3], hit_pattern[k], per-stream status[n], mh_dev_status), k = min(total, hit_cap)
+    (0 when count_only); asserts that the FIND_GUARD words behind the records, the pattern numbers and hit_off, and every
+    record at or beyond hit_cap, kept their fill."""
+    l = lib()
+    payload = _u8(payload)
+    pay_off = np.ascontiguousarray(pay_off, dtype=np.uint64)
+    nbits = np.ascontiguousarray(nbits, dtype=np.uint64)
+    n = len(pay_off) - 1
+    d_pl = DeviceBuffer(max(payload.size, 1) + 64, payload if payload.size else None)
+    d_po, d_nb = DeviceBuffer(pay_off.nbytes, pay_off), DeviceBuffer(max(nbits.nbytes, 8), nbits if n else None)
+    d_so, d_idx, sym_total = None, None, 0
+    if index is not None:
+        so = np.ascontiguousarray(sym_off, dtype=np.uint64)
+        sym_total = int(so[n])
+        d_so = DeviceBuffer(so.nbytes, so)
+        index = np.ascontiguousarray(index, dtype=np.uint64)
+        d_idx = DeviceBuffer(max(index.nbytes, 8), index if index.size else None)
+    wsb = l.mh_dev_find_batch_workspace(n, sym_total, chunk_symbols if index is not None else 0)
+    d_ws = DeviceBuffer(wsb)
+    d_st = DeviceBuffer(max(n, 1) * 4, np.full(max(n, 1), 99, dtype=np.int32))
+
+    def call(d_hits, d_pat, cap):
+        d_ho = DeviceBuffer((n + 1 + FIND_GUARD) * 8, np.full(n + 1 + FIND_GUARD, FIND_FILL, dtype=np.uint64))
+        _check(fn(handle, ps.handle, d_pl.ptr, d_po.ptr, d_nb.ptr, n, int(pay_off[n]), prev0, d_so.ptr if d_so else None, sym_total,
+                  d_idx.ptr if d_idx else None, chunk_symbols, d_ho.ptr, d_hits.ptr if d_hits else None, d_pat.ptr if d_pat else None, cap,
+                  d_st.ptr, d_ws.ptr, wsb, None), "mh_dev_find_*")
+        rc = l.mh_dev_status(d_ws.ptr, None)
+        ho = d_ho.download(np.uint64)
+        assert (ho[n + 1:] == FIND_FILL).all(), "words written behind hit_off"
+        return ho[:n + 1], rc
+
+    none = (np.zeros((0, 3), dtype=np.uint64), np.zeros(0, dtype=np.uint32))
+    if count_only or hit_cap is None:
+        ho, rc = call(None, None, 0)
+        if count_only:
+            return (ho,) + none + (d_st.download(np.int32)[:n], rc)
+    cap = int(ho[n]) if hit_cap is None else hit_cap
+    room = cap + FIND_GUARD
+    d_hits = DeviceBuffer(room * 24, np.full(room * 3, FIND_FILL, dtype=np.uint64))
+    d_pat = DeviceBuffer(room * 4, np.full(room, FIND_FILL & 0xFFFFFFFF, dtype=np.uint32))
+    ho, rc = call(d_hits, d_pat, cap)
+    hits, pat = d_hits.download(np.uint64), d_pat.download(np.uint32)
+    k = min(int(ho[n]), cap)
+    assert (hits[3 * k:] == FIND_FILL).all() and (pat[k:] == FIND_FILL & 0xFFFFFFFF).all(), "records written at or beyond the hits / hit_cap"
+    return ho, hits[:3 * k].reshape(-1, 3), pat[:k], d_st.download(np.int32)[:n], rc
 
 
 class Model:
@@ -704,6 +805,45 @@ class Model:
         mh_dev_status)."""
         return _dev_batch_ranges(lib().mh_dev_decode_batch_ranges, self._h, payload, pay_off, nbits, lookups, prev0, sym_off, index,
                                  chunk_symbols, out_cap)
+
+    def find_batch(self, ps, payload, pay_off, nbits, prev0=PREV0, sym_off=None, index=None, chunk_symbols=0, hit_cap=None, check=True):
+        """mh_find_batch (host form): (hit_off[n + 1], hits[k, 3] = (stream, begin, end), hit_pattern[k], per-stream status[n],
+        return code).  hit_cap None: a count-only call first, then one with room for every hit; hit_cap 'count': count only.
+        check=False returns a failed stream's status or MH_ERR_CAPACITY instead of raising."""
+        l = lib()
+        payload = _u8(payload)
+        pay_off = np.ascontiguousarray(pay_off, dtype=np.uint64)
+        nbits = np.ascontiguousarray(nbits, dtype=np.uint64)
+        n = len(pay_off) - 1
+        so = np.ascontiguousarray(sym_off, dtype=np.uint64) if sym_off is not None else None
+        idx = np.ascontiguousarray(index, dtype=np.uint64) if index is not None else None
+        ho = np.zeros(n + 1, dtype=np.uint64)
+        st = np.zeros(max(n, 1), dtype=np.int32)
+
+        def call(hits, pat, cap):
+            rc = l.mh_find_batch(self._h, ps.handle, _ptr(payload), pay_off.ctypes.data, nbits.ctypes.data if n else None, n, prev0,
+                                 so.ctypes.data if so is not None else None,
+                                 (idx.ctypes.data if idx.size else pay_off.ctypes.data) if idx is not None else None, chunk_symbols,
+                                 ho.ctypes.data, hits.ctypes.data if hits is not None else None, pat.ctypes.data if pat is not None else None,
+                                 cap, st.ctypes.data)
+            if rc != MH_OK and (check or not (st[:n].any() or rc == MH_ERR_CAPACITY)):
+                raise MhError(rc, "mh_find_batch")
+            return rc
+
+        if hit_cap is None or hit_cap == "count":
+            rc = call(None, None, 0)
+            if hit_cap == "count":
+                return ho, np.zeros((0, 3), dtype=np.uint64), np.zeros(0, dtype=np.uint32), st[:n], rc
+        cap = int(ho[n]) if hit_cap is None else hit_cap
+        hits, pat = np.zeros(max(cap, 1) * 3, dtype=np.uint64), np.zeros(max(cap, 1), dtype=np.uint32)
+        rc = call(hits, pat, cap)
+        k = min(int(ho[n]), cap)
+        return ho, hits[:3 * k].reshape(-1, 3), pat[:k], st[:n], rc
+
+    def dev_find_batch(self, ps, payload, pay_off, nbits, prev0=PREV0, sym_off=None, index=None, chunk_symbols=0, hit_cap=None, count_only=False):
+        """One mh_dev_find_batch call (two when hit_cap is None: count, then records) with guard words behind its outputs:
+        (hit_off[n + 1], hits[k, 3], hit_pattern[k], per-stream status[n], mh_dev_status)."""
+        return _dev_find(lib().mh_dev_find_batch, self._h, ps, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols, hit_cap, count_only)
 
     def decompress_batch_ranges(self, blobs, lookups, indices=None, chunk_symbols=0, lengths=None):
         """Lookups into whole `.cm` files of this model (decompress_batch's inputs): (list of bytes, status per lookup)."""
@@ -1063,6 +1203,11 @@ class ModelSet:
         mh_dev_status)."""
         return _dev_batch_ranges(lib().mh_dev_decode_each_ranges, self._h, payload, pay_off, nbits, lookups, prev0, sym_off, index,
                                  chunk_symbols, out_cap)
+
+    def find(self, ps, payload, pay_off, nbits, prev0=PREV0, sym_off=None, index=None, chunk_symbols=0, hit_cap=None, count_only=False):
+        """One mh_dev_find_each call (two when hit_cap is None) with guard words behind its outputs, stream i under model i:
+        (hit_off[n + 1], hits[k, 3], hit_pattern[k], per-stream status[n], mh_dev_status)."""
+        return _dev_find(lib().mh_dev_find_each, self._h, ps, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols, hit_cap, count_only)
 
     # ---- banks of shared models (include/mh.h, "BANKS OF SHARED MODELS"): this set is the bank, its streams the entries ----
     @classmethod

@@ -353,6 +353,29 @@ static uint8_t* open_output_cb(void* ctx, size_t n) {
     return o->data;
 }
 
+// The chunk-index sidecar of a stream of nbits bits: false (index empty) when there is none or it is not usable.
+static bool load_index(const std::string& path, uint64_t nbits, std::vector<uint64_t>& index, uint32_t& chunk, uint64_t& n_symbols) {
+    index.clear();
+    if (path.empty()) return false;
+    FILE* f = fopen(path.c_str(), "rb");
+    if (!f) return false;
+    uint64_t head[3];
+    // The sidecar is untrusted input: a chunk size that is not a power of two in [MH_CHUNK_MIN,
+    // MH_CHUNK_MAX] or a symbol count above the payload's bit count (every code has >= 1 bit) cannot
+    // come from this encoder; such a file is ignored and the stream is decoded without an index.
+    if (fread(head, 8, 3, f) == 3 && head[0] == 0x315844494D48ull && valid_chunk(head[1]) && head[2] <= nbits) {
+        chunk = (uint32_t)head[1];
+        n_symbols = head[2];
+        size_t ne = (size_t)mh_index_entries(n_symbols, chunk);
+        index.resize(ne + 1);
+        if (fread(index.data(), 8, ne, f) != ne) index.clear();
+    } else {
+        eprintf("Warning: index sidecar %s is not usable; extracting without it.\n", path.c_str());
+    }
+    fclose(f);
+    return !index.empty();
+}
+
 // src/coding.cpp:96-160
 void i_coding_provider::decompress(FILE* input_fd, FILE* output_fd) {
     InputView in(input_fd, ranges_.empty());
@@ -362,25 +385,7 @@ void i_coding_provider::decompress(FILE* input_fd, FILE* output_fd) {
     std::vector<uint64_t> index;
     uint64_t n_symbols = 0;
     uint32_t chunk = 0;
-    if (!index_path_.empty()) {
-        FILE* f = fopen(index_path_.c_str(), "rb");
-        if (f) {
-            uint64_t head[3];
-            // The sidecar is untrusted input: a chunk size that is not a power of two in [MH_CHUNK_MIN,
-            // MH_CHUNK_MAX] or a symbol count above the payload's bit count (every code has >= 1 bit) cannot
-            // come from this encoder; such a file is ignored and the stream is decoded without an index.
-            if (fread(head, 8, 3, f) == 3 && head[0] == 0x315844494D48ull && valid_chunk(head[1]) && head[2] <= nbits) {
-                chunk = (uint32_t)head[1];
-                n_symbols = head[2];
-                size_t ne = (size_t)mh_index_entries(n_symbols, chunk);
-                index.resize(ne + 1);
-                if (fread(index.data(), 8, ne, f) != ne) index.clear();
-            } else {
-                eprintf("Warning: index sidecar %s is not usable; extracting without it.\n", index_path_.c_str());
-            }
-            fclose(f);
-        }
-    }
+    load_index(index_path_, nbits, index, chunk, n_symbols);
     const bool have_index = !index.empty();
     if (!ranges_.empty()) {
         // --range: only the payload bytes of the chunks the ranges touch are read from the mapping and uploaded
@@ -423,6 +428,48 @@ void i_coding_provider::decompress(FILE* input_fd, FILE* output_fd) {
     fclose(input_fd);
     if (output_fd != stdout) fclose(output_fd);
     else fflush(output_fd);
+}
+
+// --find: the `.cm` file as a batch of one indexed stream, searched on the device without writing its bytes
+// (mh_find_batch); one line `pattern begin` per hit, ascending (end, pattern number).  Returns the number of hits.
+uint64_t i_coding_provider::find(FILE* input_fd, const std::vector<std::string>& patterns, bool fold) {
+    InputView in(input_fd, true);
+    if (in.size == 0) mh_or_die(MH_ERR_CORRUPT, "find");
+    uint64_t nbits = 0;
+    mh_or_die(mh_stream_parse_header(model_, in.data[0], in.size, &nbits), "find");
+    std::vector<uint64_t> index;
+    uint64_t n_symbols = 0;
+    uint32_t chunk = 0;
+    if (!load_index(index_path_, nbits, index, chunk, n_symbols)) {
+        eprintf("Error: --find needs a usable index sidecar (--index %s).\n", index_path_.c_str());
+        exit(1);
+    }
+    index.resize((size_t)mh_batch_index_capacity(n_symbols, 1, chunk));   // (the slice of stream 0 starts at entry 0)
+    std::string bytes;
+    std::vector<uint32_t> pat_off(1, 0);
+    for (const std::string& p : patterns) {
+        bytes += p;
+        pat_off.push_back((uint32_t)bytes.size());
+    }
+    mh_pattern_set* ps = nullptr;
+    mh_or_die(mh_pattern_set_create((const uint8_t*)bytes.data(), pat_off.data(), patterns.size(), fold ? MH_FIND_FOLD_ASCII : 0u, &ps), "--find");
+    const uint64_t pay_off[2] = {0, (uint64_t)in.size - 1}, sym_off[2] = {0, n_symbols};
+    uint64_t hit_off[2] = {0, 0};
+    StageTimer timer("find", in.size);
+    mh_or_die(mh_find_batch(model_, ps, in.data + 1, pay_off, &nbits, 1, MH_PREV0, sym_off, index.data(), chunk, hit_off, nullptr, nullptr, 0,
+                            nullptr), "find");
+    const uint64_t total = hit_off[1];
+    if (total) {
+        std::vector<uint64_t> hits((size_t)total * 3);
+        std::vector<uint32_t> pat((size_t)total);
+        mh_or_die(mh_find_batch(model_, ps, in.data + 1, pay_off, &nbits, 1, MH_PREV0, sym_off, index.data(), chunk, hit_off, hits.data(),
+                                pat.data(), total, nullptr), "find");
+        for (uint64_t r = 0; r < total; ++r) printf("%u %llu\n", pat[r], (unsigned long long)hits[3 * r + 1]);
+        fflush(stdout);
+    }
+    mh_pattern_set_free(ps);
+    fclose(input_fd);
+    return total;
 }
 
 // ------------------------------------------------------------------------ -g dumps (N3)

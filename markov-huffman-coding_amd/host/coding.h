@@ -57,6 +57,9 @@ public:
     void set_index_path(const std::string& path, uint32_t chunk_symbols) { index_path_ = path; chunk_ = chunk_symbols; }
     // extension: decompress extracts only these [begin, end) byte ranges of the original input (needs the index sidecar)
     void set_ranges(const std::vector<uint64_t>& begin_end) { ranges_ = begin_end; }
+    // extension: prints one line `pattern begin` per occurrence of the patterns in the compressed input (needs the index
+    // sidecar), in ascending (end, pattern number) order, and returns their number; nothing is decompressed to a file
+    uint64_t find(FILE* input_fd, const std::vector<std::string>& patterns, bool fold);
     const mh_model* model() const { return model_; }
 
 protected:

@@ -11,6 +11,8 @@
 //   --chunk N        symbols per index entry (power of two, 256..8192; default 1024)
 //   --device N       HIP device ordinal
 //   --range B:E      extract only bytes [B, E) of the original input (repeatable; needs -x and --index)
+//   --find STRING    print `pattern begin` per occurrence of STRING in the original input, searched on the device without
+//                    decompressing (repeatable, 64 bytes in all; --find-fold folds ASCII case; needs -x and --index)
 #include <errno.h>
 #include <stdlib.h>
 #include <string.h>
@@ -37,6 +39,9 @@ static void print_help() {
     eprintf("\t--max-code-len n  no code longer than n bits, 8..64 (MI355X extension; when training a table: not with -e, -x, --order2)\n");
     eprintf("\t--device n     HIP device ordinal\n");
     eprintf("\t--range b:e    with -x and --index: extract only bytes [b, e) (repeatable, concatenated in order)\n");
+    eprintf("\t--find string  with -x and --index: print `pattern begin` for every occurrence of the string in the original input\n");
+    eprintf("\t               without decompressing it (repeatable, 64 bytes in all; --find-fold: ASCII letters match either case);\n");
+    eprintf("\t               exit status 0 with hits, 1 with none\n");
 }
 
 struct options {
@@ -51,6 +56,8 @@ struct options {
     int max_code_len = 0;                                         // 0: no limit
     int device = -1;
     std::vector<uint64_t> ranges;                                 // begin, end per --range
+    std::vector<std::string> finds;                               // one per --find
+    bool find_fold = false;
 };
 
 // "B:E" with decimal B <= E; anything else is an error
@@ -107,6 +114,8 @@ static options parse(int argc, char* argv[]) {
                 o.ranges.push_back(b);
                 o.ranges.push_back(e);
             }
+            else if (!strcmp(a, "--find")) o.finds.push_back(need(a));
+            else if (!strcmp(a, "--find-fold")) o.find_fold = true;
             else eprintf("Warning: Unknown option %s.\n", a);
             continue;
         }
@@ -164,6 +173,37 @@ int main(int argc, char* argv[]) {
         }
     }
 
+    if (o.find_fold && o.finds.empty()) {
+        eprintf("Error: --find-fold needs --find.\n");
+        exit(1);
+    }
+    if (!o.finds.empty()) {                                        // the same rules as --range, checked as early
+        if (!o.extract || o.index_path.empty()) {
+            eprintf("Error: --find needs -x and --index.\n");
+            exit(1);
+        }
+        if (o.order2) {
+            eprintf("Error: --find does not support --order2.\n");
+            exit(1);
+        }
+        if (!o.ranges.empty()) {
+            eprintf("Error: --find cannot be combined with --range.\n");
+            exit(1);
+        }
+        size_t total = 0;
+        for (const std::string& p : o.finds) {
+            if (p.empty()) {
+                eprintf("Error: --find expects a non-empty string.\n");
+                exit(1);
+            }
+            total += p.size();
+        }
+        if (total > MH_FIND_MAX_POSITIONS) {
+            eprintf("Error: the --find strings are %zu bytes in all; at most %d.\n", total, MH_FIND_MAX_POSITIONS);
+            exit(1);
+        }
+    }
+
     if (o.max_code_len && (o.encoding_input || o.extract || o.order2)) {
         eprintf("Error: --max-code-len limits a table that is being trained; it cannot be combined with -e, -x or --order2.\n");
         exit(1);
@@ -194,7 +234,7 @@ int main(int argc, char* argv[]) {
     if (o.encoding_output) check_access(o.encoding_output, false);
 
     FILE* input_fd = open_or_die(o.input, "rb", "input");
-    FILE* output_fd = o.output ? open_or_die(o.output, "w+b", "output") : stdout;   // read-write: the result is written through a mapping
+    FILE* output_fd = o.output && o.finds.empty() ? open_or_die(o.output, "w+b", "output") : stdout;   // read-write: the result is written through a mapping
 
     i_coding_provider* coder = nullptr;
     if (o.encoding_input) {
@@ -250,6 +290,13 @@ int main(int argc, char* argv[]) {
         coder->write_coding_tree(buffer);
     }
 
+    if (!o.finds.empty()) {                                        // prints the hits; no output file
+        eprintf("Searching %s...\n", o.input);
+        const uint64_t hits = coder->find(input_fd, o.finds, o.find_fold);
+        delete coder;
+        eprintf("Done.\n");
+        return hits ? 0 : 1;
+    }
     if (o.extract) {
         eprintf("Extracting %s ===> %s...\n", o.input, o.output);
         coder->decompress(input_fd, output_fd);
