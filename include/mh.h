@@ -978,6 +978,75 @@ int mh_find_batch(const mh_model *m, const mh_pattern_set *ps, const uint8_t *pa
                   int32_t *stream_status);
 
 /* ---------------------------------------------------------------------------------------------------------------------
+ * RE-CODING BATCHES — a batch of compressed records moved to another model without a buffer for the decoded bytes: the
+ * (prev, sym) histogram of a compressed batch (the training counts of the new model) and the batch coded again under a
+ * destination model, both taken from each decoded symbol while it sits in a register.  Order 0 and order 1 on both sides,
+ * independently; an order-2 model on either side is MH_ERR_ARG before any launch.  The source batch is described exactly as
+ * for mh_dev_decode_batch / mh_dev_decode_each (payload layout, pay_off, nbits, prev0, sym_off and the index slices of
+ * mh_batch_index_base, the same alignment rules and up-front checks with the same statuses); a bank view of
+ * mh_dev_model_set_pick is a set.  An index entry's context byte is taken as the symbol in front of its chunk, as every
+ * index writer of this library writes it.
+ *   - d_stream_status[n] (may be NULL): for every stream the verdict mh_dev_decode_batch / mh_dev_decode_each gives the same
+ *     arguments (see SEARCH IN BATCHES).  mh_dev_status(d_ws) keeps one of the errors.
+ *   - Histogram: `order` (0 or 1, else MH_ERR_ARG) is the order of the histogram, not of the source model; d_counts holds
+ *     256 or 65 536 counts and is written in full: the summed counts of every stream that decodes, each starting in context
+ *     prev0 — for an undamaged batch exactly what mh_dev_histogram_o1_batch / _o0_batch give the original messages.  A
+ *     stream whose verdict is not MH_OK contributes nothing: a chunk counts as it decodes and takes its counts back when it
+ *     fails, and a last pass takes back the chunks that passed inside a stream that failed.  The counters are exact 64-bit
+ *     sums.  Index-free (d_index NULL): one lane walks one stream, d_sym_off may be NULL.
+ *   - Re-code: for every stream whose verdict is MH_OK the output equals what mh_dev_encode_batch(dst, ...) produces from
+ *     the decoded messages: d_out_off[n + 1] (byte-aligned packed payloads), d_out_nbits[n], the payload bytes and the index
+ *     slices in d_out_index (may be NULL; mh_batch_index_base layout, the same chunk_symbols; gap entries untouched).  A
+ *     (prev, sym) pair without a code under dst is skipped and the context advances (the reference's NDEBUG rule);
+ *     d_dropped[n] (may be NULL) counts those symbols per stream, the stream's status stays MH_OK.
+ *   - A stream whose verdict is not MH_OK gets nbits 0 and no payload byte (out_off[i + 1] == out_off[i]); its index slice
+ *     is left untouched and its dropped count is 0.  The other streams are unaffected.
+ *   - Nothing is written at or beyond min(cap, out_off[n]) bytes of d_out_payload.  A payload that does not fit: the
+ *     workspace status is MH_ERR_CAPACITY, offsets, lengths, dropped counts and statuses are still written, payload and
+ *     index are not.  d_out_payload == NULL: count only (cap ignored) — offsets, lengths, d_sym_off (index-free), dropped
+ *     counts, statuses and, when d_out_index is given, the index; the caller sizes the payload from d_out_off[n].
+ *   - Index-free source (d_index NULL): one lane walks one stream under MH_BATCH_WALK_MAX_BITS, d_sym_off[n + 1] is an
+ *     output (required), chunk_symbols and d_out_index describe only the destination index, and sym_total is the number of
+ *     symbols d_out_index was sized for (mh_batch_index_capacity(sym_total, n, chunk) entries): a batch that decodes to
+ *     more is MH_ERR_CAPACITY with neither payload nor index written.  A batch the reference wrote comes out re-coded
+ *     and indexed.
+ * No allocation, no host synchronisation, a number of launches that does not depend on the data or on n_streams.
+ * d_payload, d_out_payload and d_ws 16-byte aligned; d_ws at least the _workspace(n, sym_total, chunk_symbols) bytes
+ * (chunk_symbols 0: index-free): per chunk number and per stream, never per payload or message byte.
+ * Host form mh_recode_batch: arguments checked before a device is touched, the batch uploaded, the device call run once,
+ * results copied back; sym_off is input with an index and output without; out_index (may be NULL) has
+ * mh_batch_index_capacity(sym_off[n], n, chunk) entries with an index, and without one the same for the sum of
+ * nbits_i / mh_model_min_code_len(src) symbols.  Index-free batches with a stream over MH_BATCH_WALK_MAX_BITS are indexed by
+ * mh_index_batch first, so a valid batch is never refused.  Returns the first stream's error, else MH_ERR_CAPACITY.
+ * --------------------------------------------------------------------------------------------------------------------- */
+size_t mh_dev_histogram_coded_workspace(size_t n_streams, uint64_t sym_total, uint32_t chunk_symbols);
+int mh_dev_histogram_coded_batch(const mh_model *src, int order, const uint8_t *d_payload, const uint64_t *d_pay_off,
+                                 const uint64_t *d_nbits, size_t n_streams, uint64_t pay_total, uint8_t prev0,
+                                 const uint64_t *d_sym_off, uint64_t sym_total, const uint64_t *d_index, uint32_t chunk_symbols,
+                                 uint64_t *d_counts, int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream);
+/* The same with stream i under the set's model i (n_streams == mh_model_set_size(src), else MH_ERR_ARG). */
+int mh_dev_histogram_coded_each(const mh_model_set *src, int order, const uint8_t *d_payload, const uint64_t *d_pay_off,
+                                const uint64_t *d_nbits, size_t n_streams, uint64_t pay_total, uint8_t prev0,
+                                const uint64_t *d_sym_off, uint64_t sym_total, const uint64_t *d_index, uint32_t chunk_symbols,
+                                uint64_t *d_counts, int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream);
+size_t mh_dev_recode_batch_workspace(size_t n_streams, uint64_t sym_total, uint32_t chunk_symbols);
+int mh_dev_recode_batch(const mh_model *src, const mh_model *dst, const uint8_t *d_payload, const uint64_t *d_pay_off,
+                        const uint64_t *d_nbits, size_t n_streams, uint64_t pay_total, uint8_t prev0, uint64_t *d_sym_off,
+                        uint64_t sym_total, const uint64_t *d_index, uint32_t chunk_symbols, uint8_t *d_out_payload, size_t cap,
+                        uint64_t *d_out_off, uint64_t *d_out_nbits, uint64_t *d_out_index, uint64_t *d_dropped,
+                        int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream);
+/* The same with stream i under the set's model i (n_streams == mh_model_set_size(src), else MH_ERR_ARG). */
+int mh_dev_recode_each(const mh_model_set *src, const mh_model *dst, const uint8_t *d_payload, const uint64_t *d_pay_off,
+                       const uint64_t *d_nbits, size_t n_streams, uint64_t pay_total, uint8_t prev0, uint64_t *d_sym_off,
+                       uint64_t sym_total, const uint64_t *d_index, uint32_t chunk_symbols, uint8_t *d_out_payload, size_t cap,
+                       uint64_t *d_out_off, uint64_t *d_out_nbits, uint64_t *d_out_index, uint64_t *d_dropped,
+                       int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream);
+int mh_recode_batch(const mh_model *src, const mh_model *dst, const uint8_t *payload, const uint64_t *pay_off,
+                    const uint64_t *nbits, size_t n_streams, uint8_t prev0, uint64_t *sym_off, const uint64_t *index,
+                    uint32_t chunk_symbols, uint8_t *out_payload, size_t cap, uint64_t *out_off, uint64_t *out_nbits,
+                    uint64_t *out_index, uint64_t *dropped, int32_t *stream_status);
+
+/* ---------------------------------------------------------------------------------------------------------------------
  * SEGMENT STATES OF INDEX-FREE BATCHES — the batch counterpart of mh_dev_build_index: the `.cm` files the reference writes
  * carry no index, and without one the batch decoders above walk each stream with one lane.  Three device steps for a batch
  * of index-free streams under one shared model (mh_dev_batch_*) or a model set (mh_dev_each_*; a bank view of

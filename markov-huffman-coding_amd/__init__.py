@@ -61,6 +61,8 @@ EXPORTS = [
     "mh_dev_decode_batch_o2_ranges_workspace", "mh_dev_decode_batch_o2_ranges", "mh_decode_batch_o2_ranges",
     "mh_pattern_set_create", "mh_pattern_set_size", "mh_pattern_set_max_len", "mh_pattern_set_free",
     "mh_dev_find_batch_workspace", "mh_dev_find_batch", "mh_dev_find_each", "mh_find_batch",
+    "mh_dev_histogram_coded_workspace", "mh_dev_histogram_coded_batch", "mh_dev_histogram_coded_each",
+    "mh_dev_recode_batch_workspace", "mh_dev_recode_batch", "mh_dev_recode_each", "mh_recode_batch",
 ]
 FIND_MAX_POSITIONS = 64                    # include/mh.h MH_FIND_MAX_POSITIONS
 FIND_FOLD_ASCII = 1                        # include/mh.h MH_FIND_FOLD_ASCII
@@ -278,6 +280,14 @@ def lib():
         for fn in (l.mh_dev_find_batch, l.mh_dev_find_each):
             fn.argtypes = [vp, vp, vp, vp, vp, sz, u64, u8, vp, u64, vp, u32, vp, vp, vp, u64, vp, vp, sz, vp]
         l.mh_find_batch.argtypes = [vp, vp, vp, vp, vp, sz, u8, vp, vp, u32, vp, vp, vp, u64, vp]
+        for fn in (l.mh_dev_histogram_coded_workspace, l.mh_dev_recode_batch_workspace):
+            fn.argtypes = [sz, u64, u32]
+            fn.restype = sz
+        for fn in (l.mh_dev_histogram_coded_batch, l.mh_dev_histogram_coded_each):
+            fn.argtypes = [vp, i32, vp, vp, vp, sz, u64, u8, vp, u64, vp, u32, vp, vp, vp, sz, vp]
+        for fn in (l.mh_dev_recode_batch, l.mh_dev_recode_each):
+            fn.argtypes = [vp, vp, vp, vp, vp, sz, u64, u8, vp, u64, vp, u32, vp, sz, vp, vp, vp, vp, vp, vp, sz, vp]
+        l.mh_recode_batch.argtypes = [vp, vp, vp, vp, vp, sz, u8, vp, vp, u32, vp, sz, vp, vp, vp, vp, vp]
         _lib = l
     return _lib
 
@@ -565,6 +575,106 @@ def _dev_find(fn, handle, ps, payload, pay_off, nbits, prev0, sym_off, index, ch
     return ho, hits[:3 * k].reshape(-1, 3), pat[:k], d_st.download(np.int32)[:n], rc
 
 
+# ---- re-coding batches (include/mh.h, "RE-CODING BATCHES") -------------------------------------------------------------------
+def _dev_source(payload, pay_off, nbits, sym_off, index):
+    payload = _u8(payload)
+    pay_off = np.ascontiguousarray(pay_off, dtype=np.uint64)
+    nbits = np.ascontiguousarray(nbits, dtype=np.uint64)
+    n = len(pay_off) - 1
+    d_pl = DeviceBuffer(max(payload.size, 1) + 64, payload if payload.size else None)
+    d_po, d_nb = DeviceBuffer(pay_off.nbytes, pay_off), DeviceBuffer(max(nbits.nbytes, 8), nbits if n else None)
+    so, d_idx = None, None
+    if index is not None:
+        so = np.ascontiguousarray(sym_off, dtype=np.uint64)
+        index = np.ascontiguousarray(index, dtype=np.uint64)
+        d_idx = DeviceBuffer(max(index.nbytes, 8), index if index.size else None)
+    return n, int(pay_off[n]), d_pl, d_po, d_nb, so, d_idx
+
+
+def _dev_histogram_coded(fn, handle, order, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols):
+    """One mh_dev_histogram_coded_batch / _each call: (counts[256 or 65536], per-stream status[n], mh_dev_status); asserts that
+    the FIND_GUARD words behind the counts kept their fill."""
+    l = lib()
+    n, pay_total, d_pl, d_po, d_nb, so, d_idx = _dev_source(payload, pay_off, nbits, sym_off, index)
+    sym_total = int(so[n]) if so is not None else 0
+    d_so = DeviceBuffer(so.nbytes, so) if so is not None else None
+    nc = 65536 if order else 256
+    d_counts = DeviceBuffer((nc + FIND_GUARD) * 8, np.full(nc + FIND_GUARD, FIND_FILL, dtype=np.uint64))
+    wsb = l.mh_dev_histogram_coded_workspace(n, sym_total, chunk_symbols if index is not None else 0)
+    d_ws = DeviceBuffer(wsb)
+    d_st = DeviceBuffer(max(n, 1) * 4, np.full(max(n, 1), 99, dtype=np.int32))
+    _check(fn(handle, order, d_pl.ptr, d_po.ptr, d_nb.ptr, n, pay_total, prev0, d_so.ptr if d_so else None, sym_total,
+              d_idx.ptr if d_idx else None, chunk_symbols, d_counts.ptr, d_st.ptr, d_ws.ptr, wsb, None), "mh_dev_histogram_coded_*")
+    rc = l.mh_dev_status(d_ws.ptr, None)
+    counts = d_counts.download(np.uint64)
+    assert (counts[nc:] == FIND_FILL).all(), "words written behind the counts"
+    return counts[:nc], d_st.download(np.int32)[:n], rc
+
+
+def _dev_recode(fn, src, dst, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols, cap=None, count_only=False, want_index=True,
+                sym_total=None):
+    """One mh_dev_recode_batch / mh_dev_recode_each call with guards around every output.  cap None: a count-only call first,
+    then one with exactly out_off[n] bytes of room.  Index-free (index None) with a destination index and no sym_total: the
+    count-only call sizes it.  Returns a dict: payload (the min(cap, out_off[n]) bytes), out_off[n + 1], nbits[n], index (the whole
+    array, FIND_FILL where no slice lies, or None), dropped[n], status[n], sym_off[n + 1], rc (mh_dev_status).  Asserts that
+    nothing changed outside out_off[n] payload bytes, the n + 1 offsets, the n lengths and counts and the index slices of the
+    streams that passed."""
+    l = lib()
+    n, pay_total, d_pl, d_po, d_nb, so, d_idx = _dev_source(payload, pay_off, nbits, sym_off, index)
+    indexed = index is not None
+    G, F = FIND_GUARD, FIND_FILL
+    d_st = DeviceBuffer(max(n, 1) * 4, np.full(max(n, 1), 99, dtype=np.int32))
+
+    def call(room, with_payload, with_index, st):
+        d_so = DeviceBuffer((n + 1 + G) * 8, np.concatenate([so if indexed else np.full(n + 1, F, dtype=np.uint64), np.full(G, F, dtype=np.uint64)]))
+        wsb = l.mh_dev_recode_batch_workspace(n, st, chunk_symbols if indexed else 0)
+        d_ws = DeviceBuffer(wsb)
+        d_out = DeviceBuffer(room + RANGE_GUARD + 16, np.full(room + RANGE_GUARD + 16, RANGE_FILL, dtype=np.uint8)) if with_payload else None
+        d_oo = DeviceBuffer((n + 1 + G) * 8, np.full(n + 1 + G, F, dtype=np.uint64))
+        d_onb = DeviceBuffer((n + G) * 8, np.full(n + G, F, dtype=np.uint64))
+        d_dr = DeviceBuffer((n + G) * 8, np.full(n + G, F, dtype=np.uint64))
+        nidx = int(l.mh_batch_index_capacity(st, n, chunk_symbols)) if with_index else 0
+        d_oi = DeviceBuffer((nidx + G) * 8, np.full(nidx + G, F, dtype=np.uint64)) if with_index else None
+        _check(fn(src, dst, d_pl.ptr, d_po.ptr, d_nb.ptr, n, pay_total, prev0, d_so.ptr, st, d_idx.ptr if d_idx else None, chunk_symbols,
+                  d_out.ptr if d_out else None, room, d_oo.ptr, d_onb.ptr, d_oi.ptr if d_oi else None, d_dr.ptr, d_st.ptr, d_ws.ptr, wsb, None),
+               "mh_dev_recode_*")
+        rc = l.mh_dev_status(d_ws.ptr, None)
+        oo, onb, dr, dso = d_oo.download(np.uint64), d_onb.download(np.uint64), d_dr.download(np.uint64), d_so.download(np.uint64)
+        status = d_st.download(np.int32)[:n]
+        assert (oo[n + 1:] == F).all() and (onb[n:] == F).all() and (dr[n:] == F).all() and (dso[n + 1:] == F).all(), "words written behind an output"
+        if indexed:
+            assert np.array_equal(dso[:n + 1], so), "sym_off written with an index"
+        res = dict(out_off=oo[:n + 1], nbits=onb[:n], dropped=dr[:n], status=status, sym_off=dso[:n + 1], rc=rc, payload=None, index=None)
+        if d_out:
+            out = d_out.download(np.uint8)
+            used = min(int(oo[n]), room) if rc != MH_ERR_CAPACITY else 0
+            assert (out[used:] == RANGE_FILL).all(), "bytes written at or beyond min(cap, out_off[n])"
+            res["payload"] = out[:used].copy()
+        if d_oi:
+            oi = d_oi.download(np.uint64)
+            mine = np.zeros(nidx + G, dtype=bool)
+            if rc != MH_ERR_CAPACITY and dso[n] != F:
+                for i in range(n):
+                    if status[i] == MH_OK:
+                        b = int(dso[i]) // chunk_symbols + i
+                        mine[b:b + (int(dso[i + 1] - dso[i]) + chunk_symbols - 1) // chunk_symbols] = True
+            assert (oi[~mine] == F).all(), "index entries written outside the slices of the streams that passed"
+            res["index"] = oi[:nidx]
+        return res
+
+    st = int(so[n]) if indexed else (sym_total or 0)
+    idx_now = want_index and bool(chunk_symbols) and (indexed or sym_total is not None)
+    if count_only:
+        return call(0, False, idx_now, st)
+    if cap is None or (want_index and chunk_symbols and not indexed and sym_total is None):
+        pre = call(0, False, False, st)
+        if cap is None:
+            cap = int(pre["out_off"][n])
+        if not indexed and sym_total is None:
+            st = int(pre["sym_off"][n])
+    return call(cap, True, want_index and bool(chunk_symbols), st)
+
+
 class Model:
     """Owns an mh_model* (tables resident on the current device)."""
 
@@ -844,6 +954,49 @@ class Model:
         """One mh_dev_find_batch call (two when hit_cap is None: count, then records) with guard words behind its outputs:
         (hit_off[n + 1], hits[k, 3], hit_pattern[k], per-stream status[n], mh_dev_status)."""
         return _dev_find(lib().mh_dev_find_batch, self._h, ps, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols, hit_cap, count_only)
+
+    def dev_histogram_coded(self, order, payload, pay_off, nbits, prev0=PREV0, sym_off=None, index=None, chunk_symbols=0):
+        """One mh_dev_histogram_coded_batch call on a batch coded under this model: (counts, per-stream status[n], mh_dev_status)."""
+        return _dev_histogram_coded(lib().mh_dev_histogram_coded_batch, self._h, order, payload, pay_off, nbits, prev0, sym_off, index,
+                                    chunk_symbols)
+
+    def dev_recode_batch(self, dst, payload, pay_off, nbits, prev0=PREV0, sym_off=None, index=None, chunk_symbols=0, **kw):
+        """One mh_dev_recode_batch call (a batch coded under this model, coded again under `dst`) with guards around its outputs:
+        the dict of _dev_recode."""
+        return _dev_recode(lib().mh_dev_recode_batch, self._h, dst.handle, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols, **kw)
+
+    def recode_batch(self, dst, payload, pay_off, nbits, prev0=PREV0, sym_off=None, index=None, chunk_symbols=0, cap=None, want_index=True,
+                     check=True):
+        """mh_recode_batch (host form): dict(payload, out_off[n + 1], nbits[n], index or None, dropped[n], status[n], sym_off[n + 1], rc).
+        cap None: room for the destination's worst case.  check=False returns a failed stream's status or MH_ERR_CAPACITY
+        instead of raising."""
+        l = lib()
+        payload = _u8(payload)
+        pay_off = np.ascontiguousarray(pay_off, dtype=np.uint64)
+        nbits = np.ascontiguousarray(nbits, dtype=np.uint64)
+        n = len(pay_off) - 1
+        idx = np.ascontiguousarray(index, dtype=np.uint64) if index is not None else None
+        if idx is not None:
+            so = np.ascontiguousarray(sym_off, dtype=np.uint64).copy()
+            bound = int(so[n])
+        else:
+            so = np.zeros(n + 1, dtype=np.uint64)
+            bound = int(sum(int(b) // max(self.min_code_len, 1) for b in nbits))
+        if cap is None:
+            cap = l.mh_encode_batch_bound(dst.handle, bound, n)
+        out = np.zeros(max(cap, 1), dtype=np.uint8)
+        oo, onb, dr = np.zeros(n + 1, dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint64)
+        st = np.zeros(max(n, 1), dtype=np.int32)
+        oi = None
+        if want_index and chunk_symbols:
+            oi = np.full(max(int(l.mh_batch_index_capacity(bound, n, chunk_symbols)), 1), FIND_FILL, dtype=np.uint64)
+        rc = l.mh_recode_batch(self._h, dst.handle, _ptr(payload), pay_off.ctypes.data, nbits.ctypes.data if n else None, n, prev0,
+                               so.ctypes.data, (idx.ctypes.data if idx.size else pay_off.ctypes.data) if idx is not None else None,
+                               chunk_symbols, out.ctypes.data, cap, oo.ctypes.data, onb.ctypes.data, oi.ctypes.data if oi is not None else None,
+                               dr.ctypes.data, st.ctypes.data)
+        if rc != MH_OK and (check or not (st[:n].any() or rc == MH_ERR_CAPACITY)):
+            raise MhError(rc, "mh_recode_batch")
+        return dict(payload=out[:min(int(oo[n]), cap)], out_off=oo, nbits=onb[:n], index=oi, dropped=dr[:n], status=st[:n], sym_off=so, rc=rc)
 
     def decompress_batch_ranges(self, blobs, lookups, indices=None, chunk_symbols=0, lengths=None):
         """Lookups into whole `.cm` files of this model (decompress_batch's inputs): (list of bytes, status per lookup)."""
@@ -1208,6 +1361,16 @@ class ModelSet:
         """One mh_dev_find_each call (two when hit_cap is None) with guard words behind its outputs, stream i under model i:
         (hit_off[n + 1], hits[k, 3], hit_pattern[k], per-stream status[n], mh_dev_status)."""
         return _dev_find(lib().mh_dev_find_each, self._h, ps, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols, hit_cap, count_only)
+
+    def histogram_coded(self, order, payload, pay_off, nbits, prev0=PREV0, sym_off=None, index=None, chunk_symbols=0):
+        """One mh_dev_histogram_coded_each call: (counts, per-stream status[n], mh_dev_status)."""
+        return _dev_histogram_coded(lib().mh_dev_histogram_coded_each, self._h, order, payload, pay_off, nbits, prev0, sym_off, index,
+                                    chunk_symbols)
+
+    def recode(self, dst, payload, pay_off, nbits, prev0=PREV0, sym_off=None, index=None, chunk_symbols=0, **kw):
+        """One mh_dev_recode_each call (stream i coded under this set's model i, coded again under the shared model `dst`):
+        the dict of _dev_recode."""
+        return _dev_recode(lib().mh_dev_recode_each, self._h, dst.handle, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols, **kw)
 
     # ---- banks of shared models (include/mh.h, "BANKS OF SHARED MODELS"): this set is the bank, its streams the entries ----
     @classmethod

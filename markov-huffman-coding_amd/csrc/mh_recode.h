@@ -1,0 +1,84 @@
+// mh_recode.h — launch interface between the re-coding calls of the C ABI (mh_api_recode.cpp) and their kernels
+// (mh_recode.hip): the (prev, sym) histogram of a compressed batch and the batch coded again under another model, both taken
+// from the decoded symbols while they sit in a register (include/mh.h, "RE-CODING BATCHES").  The batch layouts (packed
+// payloads, closed-form index slices) are those of mh_batch.h; the per-stream models those of mh_each.h.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include "mh_batch.h"
+#include "mh_each.h"
+
+namespace mhr {
+
+// the source: the batch and, under a shared model, its decode tables (out / out_cap unused); the models under a set
+struct Src {
+    mhb::DecBatchParams b;
+    mhe::SetDev set;
+};
+
+// the destination model's encoder tables (prev * 256 + sym; an order-0 model repeats its row): ctx_mask 0xFF for order 1,
+// 0 for order 0 (row 0 serves every context)
+struct Dst {
+    const uint8_t *len8;
+    const unsigned long long *code64;
+    uint32_t ctx_mask;
+};
+
+inline uint64_t work_items(uint64_t n_streams, uint64_t sym_total, uint32_t chunk_symbols) {
+    return chunk_symbols ? sym_total / chunk_symbols + n_streams + 1 : 0;
+}
+
+// histogram workspace: status block | per-stream status (when the caller passes none)
+struct HistLayout {
+    size_t off_status, total;
+};
+inline HistLayout hist_layout(uint64_t n_streams) {
+    HistLayout l;
+    l.off_status = 64;
+    l.total = (l.off_status + size_t(n_streams) * 4 + 255) & ~size_t(255);
+    return l;
+}
+
+// re-code workspace: status block (status, stop, -, -, tail word) | per-stream status (when the caller passes none) | per
+// chunk number: destination bits (u64, W + 1, scanned in place), dropped symbols (u32) | scan block sums
+struct RecodeLayout {
+    size_t off_status, off_bits, off_drop, off_sums, total;
+};
+constexpr size_t TAIL_AT = 16;
+inline RecodeLayout recode_layout(uint64_t n_streams, uint64_t nwork) {
+    RecodeLayout l;
+    const uint64_t len = (nwork > n_streams ? nwork : n_streams) + 1;
+    l.off_status = 64;
+    l.off_bits = (l.off_status + size_t(n_streams) * 4 + 15) & ~size_t(15);
+    l.off_drop = l.off_bits + size_t(nwork + 1) * 8;
+    l.off_sums = (l.off_drop + size_t(nwork) * 4 + 15) & ~size_t(15);
+    l.total = (l.off_sums + size_t(mhb::scan_blocks(len) + 1) * 8 + 255) & ~size_t(255);
+    return l;
+}
+
+struct HistParams {
+    Src s;
+    uint32_t order;                 // of the histogram: 0 (256 counts) or 1 (65 536)
+    unsigned long long *counts;
+};
+
+struct RecodeParams {
+    Src s;                          // index-free: s.b.sym_off is written, s.b.index null
+    Dst dst;
+    uint8_t *out;                   // packed payloads, 16-byte aligned; nullptr: count only
+    uint64_t cap;
+    unsigned long long *out_off;    // n + 1 (written)
+    unsigned long long *out_nbits;  // n (written)
+    unsigned long long *out_index;  // slices of the destination index, or nullptr
+    unsigned long long *dropped;    // n, or nullptr
+    uint32_t out_chunk_shift;       // chunk of the destination index (indexed source: the source's)
+};
+
+// shared: one source model (s.b's tables, LDS); else stream i under set model i
+hipError_t launch_histogram_coded(const HistParams &p, bool shared, void *d_ws, hipStream_t st);
+hipError_t launch_recode(const RecodeParams &p, bool shared, void *d_ws, hipStream_t st);
+
+}  // namespace mhr

@@ -472,6 +472,63 @@ uint64_t i_coding_provider::find(FILE* input_fd, const std::vector<std::string>&
     return total;
 }
 
+// --recode: the `.cm` file as a batch of one stream, coded again under `dst` on the device without writing its bytes
+// (mh_recode_batch).  The output is the file the reference writes for the original input with `-e` of dst's table.  With a
+// usable index sidecar the source is read through it and the output's own index is written beside the output.
+void i_coding_provider::recode(FILE* input_fd, FILE* output_fd, const i_coding_provider& dst, const std::string& out_index_path) {
+    InputView in(input_fd, true);
+    if (in.size == 0) mh_or_die(MH_ERR_CORRUPT, "recode");
+    uint64_t nbits = 0;
+    mh_or_die(mh_stream_parse_header(model_, in.data[0], in.size, &nbits), "recode");
+    std::vector<uint64_t> index;
+    uint64_t n_symbols = 0;
+    uint32_t chunk = 0;
+    const bool indexed = load_index(index_path_, nbits, index, chunk, n_symbols);
+    if (!index_path_.empty() && !indexed) {
+        eprintf("Error: --recode with --index needs a usable index sidecar (%s).\n", index_path_.c_str());
+        exit(1);
+    }
+    std::vector<uint64_t> out_index;
+    if (indexed) {
+        index.resize((size_t)mh_batch_index_capacity(n_symbols, 1, chunk));      // (the slice of stream 0 starts at entry 0)
+        out_index.assign(index.size(), 0);
+    }
+    const uint64_t pay_off[2] = {0, (uint64_t)in.size - 1};
+    uint64_t sym_off[2] = {0, n_symbols}, out_off[2] = {0, 0}, out_nbits = 0, dropped = 0;
+    StageTimer timer("recode", in.size);
+    // the output file is mapped at the destination's worst case for the stream's symbols (without an index: at most
+    // nbits / shortest source code of them) and cut to the true size afterwards: one upload, one device call
+    const int minl = mh_model_min_code_len(model_);
+    const uint64_t symbols = indexed ? n_symbols : nbits / (uint64_t)(minl > 0 ? minl : 1);
+    const size_t bound = mh_encode_batch_bound(dst.model(), (size_t)symbols, 1);
+    OutputView out;
+    out.open(output_fd, bound + 1);
+    mh_or_die(mh_recode_batch(model_, dst.model(), in.data + 1, pay_off, &nbits, 1, MH_PREV0, sym_off, indexed ? index.data() : nullptr, chunk,
+                              out.data + 1, bound, out_off, &out_nbits, indexed ? out_index.data() : nullptr, &dropped, nullptr), "recode");
+    out.data[0] = mh_stream_header(dst.model(), out_nbits);
+    const size_t nbytes = (size_t)out_off[1] + 1;
+    const bool mapped = out.map != nullptr;
+    if (!mapped) out.size = nbytes;
+    out.finish();
+    if (mapped && (fflush(output_fd) != 0 || ftruncate(fileno(output_fd), (off_t)nbytes) != 0)) {
+        eprintf("Error occurred while writing file.\n");
+        exit(1);
+    }
+    if (dropped) eprintf("Warning: %llu symbols have no code in the new table and were skipped.\n", (unsigned long long)dropped);
+    if (indexed) {
+        FILE* f = fopen(out_index_path.c_str(), "wb");
+        if (!f) { eprintf("Error while opening index output; %s.\n", strerror(errno)); exit(1); }
+        uint64_t head[3] = {0x315844494D48ull /* "HMIDX1" */, chunk, n_symbols};
+        write_buffer(head, 8, 3, f);
+        size_t ne = (size_t)mh_index_entries(n_symbols, chunk);
+        if (ne) write_buffer(out_index.data(), 8, ne, f);
+        fclose(f);
+    }
+    fclose(input_fd);
+    if (output_fd != stdout) fclose(output_fd);
+    else fflush(output_fd);
+}
+
 // ------------------------------------------------------------------------ -g dumps (N3)
 
 void encoding_descriptor::print() {                                          // src/coding.cpp:29-33

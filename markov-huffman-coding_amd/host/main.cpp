@@ -11,6 +11,8 @@
 //   --chunk N        symbols per index entry (power of two, 256..8192; default 1024)
 //   --device N       HIP device ordinal
 //   --range B:E      extract only bytes [B, E) of the original input (repeatable; needs -x and --index)
+//   --recode TABLE   with -x, -e and -o: write the stream coded again under TABLE, the decoded bytes never written; with
+//                    --index the indexed path, and the output's own index goes to <output>.idx
 //   --find STRING    print `pattern begin` per occurrence of STRING in the original input, searched on the device without
 //                    decompressing (repeatable, 64 bytes in all; --find-fold folds ASCII case; needs -x and --index)
 #include <errno.h>
@@ -42,6 +44,8 @@ static void print_help() {
     eprintf("\t--find string  with -x and --index: print `pattern begin` for every occurrence of the string in the original input\n");
     eprintf("\t               without decompressing it (repeatable, 64 bytes in all; --find-fold: ASCII letters match either case);\n");
     eprintf("\t               exit status 0 with hits, 1 with none\n");
+    eprintf("\t--recode table with -x, -e and -o: write the stream coded again under `table` (the bytes are never written);\n");
+    eprintf("\t               with --index the output's index goes to <output>.idx\n");
 }
 
 struct options {
@@ -58,6 +62,7 @@ struct options {
     std::vector<uint64_t> ranges;                                 // begin, end per --range
     std::vector<std::string> finds;                               // one per --find
     bool find_fold = false;
+    const char* recode_table = nullptr;                           // --recode: the table the stream is coded again under
 };
 
 // "B:E" with decimal B <= E; anything else is an error
@@ -116,6 +121,7 @@ static options parse(int argc, char* argv[]) {
             }
             else if (!strcmp(a, "--find")) o.finds.push_back(need(a));
             else if (!strcmp(a, "--find-fold")) o.find_fold = true;
+            else if (!strcmp(a, "--recode")) o.recode_table = need(a);
             else eprintf("Warning: Unknown option %s.\n", a);
             continue;
         }
@@ -200,6 +206,21 @@ int main(int argc, char* argv[]) {
         }
         if (total > MH_FIND_MAX_POSITIONS) {
             eprintf("Error: the --find strings are %zu bytes in all; at most %d.\n", total, MH_FIND_MAX_POSITIONS);
+            exit(1);
+        }
+    }
+
+    if (o.recode_table) {                                          // checked before anything is opened or a device is used
+        if (!o.extract || !o.encoding_input || !o.output) {
+            eprintf("Error: --recode needs -x, -e and -o.\n");
+            exit(1);
+        }
+        if (!o.finds.empty() || !o.ranges.empty()) {
+            eprintf("Error: --recode cannot be combined with --find or --range.\n");
+            exit(1);
+        }
+        if (o.order2) {
+            eprintf("Error: --recode does not support --order2.\n");
             exit(1);
         }
     }
@@ -296,6 +317,30 @@ int main(int argc, char* argv[]) {
         delete coder;
         eprintf("Done.\n");
         return hits ? 0 : 1;
+    }
+    if (o.recode_table) {                                          // the new table: either kind, whatever the old one is
+        FILE* fd = open_or_die(o.recode_table, "rb", "--recode table");
+        bitbuffer buffer(fd, bitbuffer::read);
+        {                                                          // an order-2 table: refused by name, not by the loader's type error
+            std::vector<uint8_t> bytes;
+            FILE* tf = open_or_die(o.recode_table, "rb", "--recode table");
+            uint8_t chunk[65536];
+            for (size_t k; (k = fread(chunk, 1, sizeof chunk, tf)) > 0;) bytes.insert(bytes.end(), chunk, chunk + k);
+            fclose(tf);
+            mh_model* probe = nullptr;
+            if (mh_model_from_table_bits(bytes.data(), bytes.size(), &probe) == MH_OK && mh_model_type(probe) == 2) {
+                eprintf("Error: --recode does not support an order-2 table (%s).\n", o.recode_table);
+                exit(1);
+            }
+            mh_model_free(probe);
+        }
+        i_coding_provider* dst = buffer.peek_bit() == 0 ? (i_coding_provider*)new huffman_table(buffer) : new markov_huffman_table(buffer);
+        eprintf("Re-coding %s ===> %s...\n", o.input, o.output);
+        coder->recode(input_fd, output_fd, *dst, std::string(o.output) + ".idx");
+        delete dst;
+        delete coder;
+        eprintf("Done.\n");
+        return 0;
     }
     if (o.extract) {
         eprintf("Extracting %s ===> %s...\n", o.input, o.output);
