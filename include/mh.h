@@ -917,7 +917,8 @@ int mh_decode_bank(const mh_model_set *bank, const uint32_t *choice, const uint8
  * SEARCH IN BATCHES — which streams of a batch contain which byte strings, and where, without writing the decoded bytes:
  * the batch decoders hold every decoded byte in a register for one step, and here that byte feeds a matcher instead of a
  * store.  No buffer for the original data is needed; the workspace is a few bytes per chunk.  Order 0 and order 1; an
- * order-2 model is MH_ERR_ARG before any launch.  The batch is described exactly as for mh_dev_decode_batch /
+ * order-2 model is MH_ERR_ARG before any launch (its batches are searched by mh_dev_find_batch_o2, section ORDER 2 IN
+ * SEARCH AND RE-CODING).  The batch is described exactly as for mh_dev_decode_batch /
  * mh_dev_decode_each (payload layout, pay_off, nbits, prev0, sym_off and the index slices of mh_batch_index_base, the same
  * alignment rules and up-front checks with the same statuses); a bank view of mh_dev_model_set_pick is a set.
  *   - A pattern set is a host object (no device needed): up to MH_FIND_MAX_POSITIONS bytes of patterns in all, pattern j =
@@ -981,7 +982,8 @@ int mh_find_batch(const mh_model *m, const mh_pattern_set *ps, const uint8_t *pa
  * RE-CODING BATCHES — a batch of compressed records moved to another model without a buffer for the decoded bytes: the
  * (prev, sym) histogram of a compressed batch (the training counts of the new model) and the batch coded again under a
  * destination model, both taken from each decoded symbol while it sits in a register.  Order 0 and order 1 on both sides,
- * independently; an order-2 model on either side is MH_ERR_ARG before any launch.  The source batch is described exactly as
+ * independently; an order-2 model on either side is MH_ERR_ARG before any launch (the _o2 calls of section ORDER 2 IN
+ * SEARCH AND RE-CODING serve every pair with an order-2 side).  The source batch is described exactly as
  * for mh_dev_decode_batch / mh_dev_decode_each (payload layout, pay_off, nbits, prev0, sym_off and the index slices of
  * mh_batch_index_base, the same alignment rules and up-front checks with the same statuses); a bank view of
  * mh_dev_model_set_pick is a set.  An index entry's context byte is taken as the symbol in front of its chunk, as every
@@ -1045,6 +1047,76 @@ int mh_recode_batch(const mh_model *src, const mh_model *dst, const uint8_t *pay
                     const uint64_t *nbits, size_t n_streams, uint8_t prev0, uint64_t *sym_off, const uint64_t *index,
                     uint32_t chunk_symbols, uint8_t *out_payload, size_t cap, uint64_t *out_off, uint64_t *out_nbits,
                     uint64_t *out_index, uint64_t *dropped, int32_t *stream_status);
+
+/* ---------------------------------------------------------------------------------------------------------------------
+ * ORDER 2 IN SEARCH AND RE-CODING (extension, parity unpinned) — the two sections above with an order-2 model: a batch of
+ * order-2 streams is searched, an order-0/1 batch gives the training counts of an order-2 model and is coded again under
+ * it (and back), all without a buffer for the decoded bytes.  The calls of those sections keep refusing an order-2 model.
+ * Everything not said here is word for word SEARCH IN BATCHES and RE-CODING BATCHES: the batch description, alignment
+ * rules and up-front checks with their statuses, d_stream_status, mh_dev_status(d_ws), the capacity rules, count-only
+ * mode, the index-free walk under MH_BATCH_WALK_MAX_BITS, and "no allocation, no host synchronisation, a number of
+ * launches that does not depend on the data or on n_streams".  Order-2 particulars are those of BATCHES OF ORDER-2
+ * STREAMS: a stream starts in context (prev0, prev0), index entries of an order-2 model carry two context bytes in bits
+ * 48..63 (MH_INDEX2_BIT_MASK), a pair without a code is skipped while the context advances.
+ *   - mh_dev_find_batch_o2 / mh_find_batch_o2: arguments and results of mh_dev_find_batch / mh_find_batch with the same
+ *     mh_pattern_set; the model must be order 2, else MH_ERR_ARG before any launch.  The record order (stream, end,
+ *     pattern) does not depend on the chunk size or on the index; verdicts are those mh_dev_decode_batch_o2 gives the same
+ *     arguments.  The workspace is mh_dev_find_batch_workspace's for the same arguments.
+ *   - mh_dev_histogram_coded_batch_o2: `src` is a shared model of any order and `order` is 0, 1 or 2; at least one of the
+ *     two is 2, anything else is MH_ERR_ARG (mh_dev_histogram_coded_batch serves it).  d_counts holds 256, 65 536 or
+ *     1 << 24 counts and is written in full; for an undamaged batch they are exactly what mh_dev_histogram_o0_batch /
+ *     _o1_batch / _o2_batch give the original messages (order 2: each stream's first symbol counted in (prev0, prev0), its
+ *     second in (prev0, first byte)).  A stream whose verdict is not MH_OK contributes nothing.  The workspace keeps
+ *     nothing per chunk; the caller owns the 128 MiB of order-2 counters.
+ *   - mh_dev_recode_batch_o2 / mh_recode_batch_o2: `src` and `dst` are shared models of any order, at least one of
+ *     order 2, else MH_ERR_ARG.  For every MH_OK stream the output is byte for byte what mh_dev_encode_batch_o2(dst)
+ *     (order-2 dst) or mh_dev_encode_batch(dst) (order-0/1 dst) writes for the decoded message: offsets, nbits, payload
+ *     and the index slices in the DESTINATION's entry format.  d_dropped counts the symbols without a code under dst.  A
+ *     failed stream gets nbits 0, no payload byte, an untouched index slice and dropped 0.  Verdicts are those of
+ *     mh_dev_decode_batch (order-0/1 src) or mh_dev_decode_batch_o2 (order-2 src).  The workspace is at most 24 bytes
+ *     per chunk number + 8 per stream + 4 KiB: never per payload or message byte.
+ *   - With an order-0/1 source and an index, the first symbol of chunk k is priced, coded and counted by the lane of chunk
+ *     k - 1, which decodes it behind its own chunk in the context of the symbols it decoded (an order-0/1 entry does not
+ *     carry the symbol two in front).  As in RE-CODING BATCHES, an entry's context byte is taken as the symbol in front of
+ *     its chunk, as every index writer of this library writes it.  An entry whose context byte is wrong but whose chunk
+ *     still decodes to its end bit keeps its stream's verdict MH_OK, as in mh_dev_decode_batch; that one symbol's code and
+ *     count are then those of the neighbour's decode, not of the chunk's own.  Writes stay in bounds either way: the length
+ *     and the emit pass make the same decode.
+ *   - Host forms check their arguments before a device is touched and never refuse a valid batch.  An order-0/1
+ *     index-free source with a stream over MH_BATCH_WALK_MAX_BITS is indexed by mh_index_batch first.  An order-2 source
+ *     has no batch index builder: such a stream is handled alone, as mh_decode_batch_o2 does — mh_decode, then the
+ *     host-side automaton over its bytes (search) or mh_encode under dst (re-code), the result spliced into place in stream
+ *     order.
+ * Not part of this family: model sets (`_each`) — sets are order 0/1, and a set source with an order-2 destination is a
+ * follow-up; an LDS image of the live contexts for the order-2 decoder; the command-line tool, which keeps refusing
+ * --order2 with --find and --recode.
+ * --------------------------------------------------------------------------------------------------------------------- */
+size_t mh_dev_find_batch_o2_workspace(size_t n_streams, uint64_t sym_total, uint32_t chunk_symbols);
+int mh_dev_find_batch_o2(const mh_model *m, const mh_pattern_set *ps, const uint8_t *d_payload, const uint64_t *d_pay_off,
+                         const uint64_t *d_nbits, size_t n_streams, uint64_t pay_total, uint8_t prev0,
+                         const uint64_t *d_sym_off, uint64_t sym_total, const uint64_t *d_index, uint32_t chunk_symbols,
+                         uint64_t *d_hit_off, uint64_t *d_hits, uint32_t *d_hit_pattern, uint64_t hit_cap,
+                         int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream);
+int mh_find_batch_o2(const mh_model *m, const mh_pattern_set *ps, const uint8_t *payload, const uint64_t *pay_off,
+                     const uint64_t *nbits, size_t n_streams, uint8_t prev0, const uint64_t *sym_off, const uint64_t *index,
+                     uint32_t chunk_symbols, uint64_t *hit_off, uint64_t *hits, uint32_t *hit_pattern, uint64_t hit_cap,
+                     int32_t *stream_status);
+size_t mh_dev_histogram_coded_batch_o2_workspace(size_t n_streams, uint64_t sym_total, uint32_t chunk_symbols);
+int mh_dev_histogram_coded_batch_o2(const mh_model *src, int order, const uint8_t *d_payload, const uint64_t *d_pay_off,
+                                    const uint64_t *d_nbits, size_t n_streams, uint64_t pay_total, uint8_t prev0,
+                                    const uint64_t *d_sym_off, uint64_t sym_total, const uint64_t *d_index,
+                                    uint32_t chunk_symbols, uint64_t *d_counts, int32_t *d_stream_status, void *d_ws,
+                                    size_t ws_bytes, void *stream);
+size_t mh_dev_recode_batch_o2_workspace(size_t n_streams, uint64_t sym_total, uint32_t chunk_symbols);
+int mh_dev_recode_batch_o2(const mh_model *src, const mh_model *dst, const uint8_t *d_payload, const uint64_t *d_pay_off,
+                           const uint64_t *d_nbits, size_t n_streams, uint64_t pay_total, uint8_t prev0, uint64_t *d_sym_off,
+                           uint64_t sym_total, const uint64_t *d_index, uint32_t chunk_symbols, uint8_t *d_out_payload,
+                           size_t cap, uint64_t *d_out_off, uint64_t *d_out_nbits, uint64_t *d_out_index, uint64_t *d_dropped,
+                           int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream);
+int mh_recode_batch_o2(const mh_model *src, const mh_model *dst, const uint8_t *payload, const uint64_t *pay_off,
+                       const uint64_t *nbits, size_t n_streams, uint8_t prev0, uint64_t *sym_off, const uint64_t *index,
+                       uint32_t chunk_symbols, uint8_t *out_payload, size_t cap, uint64_t *out_off, uint64_t *out_nbits,
+                       uint64_t *out_index, uint64_t *dropped, int32_t *stream_status);
 
 /* ---------------------------------------------------------------------------------------------------------------------
  * SEGMENT STATES OF INDEX-FREE BATCHES — the batch counterpart of mh_dev_build_index: the `.cm` files the reference writes

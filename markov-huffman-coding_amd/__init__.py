@@ -63,6 +63,8 @@ EXPORTS = [
     "mh_dev_find_batch_workspace", "mh_dev_find_batch", "mh_dev_find_each", "mh_find_batch",
     "mh_dev_histogram_coded_workspace", "mh_dev_histogram_coded_batch", "mh_dev_histogram_coded_each",
     "mh_dev_recode_batch_workspace", "mh_dev_recode_batch", "mh_dev_recode_each", "mh_recode_batch",
+    "mh_dev_find_batch_o2_workspace", "mh_dev_find_batch_o2", "mh_find_batch_o2", "mh_dev_histogram_coded_batch_o2_workspace",
+    "mh_dev_histogram_coded_batch_o2", "mh_dev_recode_batch_o2_workspace", "mh_dev_recode_batch_o2", "mh_recode_batch_o2",
 ]
 FIND_MAX_POSITIONS = 64                    # include/mh.h MH_FIND_MAX_POSITIONS
 FIND_FOLD_ASCII = 1                        # include/mh.h MH_FIND_FOLD_ASCII
@@ -288,6 +290,14 @@ def lib():
         for fn in (l.mh_dev_recode_batch, l.mh_dev_recode_each):
             fn.argtypes = [vp, vp, vp, vp, vp, sz, u64, u8, vp, u64, vp, u32, vp, sz, vp, vp, vp, vp, vp, vp, sz, vp]
         l.mh_recode_batch.argtypes = [vp, vp, vp, vp, vp, sz, u8, vp, vp, u32, vp, sz, vp, vp, vp, vp, vp]
+        for fn in (l.mh_dev_find_batch_o2_workspace, l.mh_dev_histogram_coded_batch_o2_workspace, l.mh_dev_recode_batch_o2_workspace):
+            fn.argtypes = [sz, u64, u32]
+            fn.restype = sz
+        l.mh_dev_find_batch_o2.argtypes = l.mh_dev_find_batch.argtypes
+        l.mh_find_batch_o2.argtypes = l.mh_find_batch.argtypes
+        l.mh_dev_histogram_coded_batch_o2.argtypes = l.mh_dev_histogram_coded_batch.argtypes
+        l.mh_dev_recode_batch_o2.argtypes = l.mh_dev_recode_batch.argtypes
+        l.mh_recode_batch_o2.argtypes = l.mh_recode_batch.argtypes
         _lib = l
     return _lib
 
@@ -526,7 +536,7 @@ class PatternSet:
         return lib().mh_pattern_set_max_len(self._h)
 
 
-def _dev_find(fn, handle, ps, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols, hit_cap, count_only):
+def _dev_find(fn, handle, ps, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols, hit_cap, count_only, ws_fn=None):
     """One mh_dev_find_batch / mh_dev_find_each call.  hit_cap None: a count-only call first, then one with room for every
     hit.  Returns (hit_off[n + 1], hits[k, 3], hit_pattern[k], per-stream status[n], mh_dev_status), k = min(total, hit_cap)
     (0 when count_only); asserts that the FIND_GUARD words behind the records, the pattern numbers and hit_off, and every
@@ -545,7 +555,7 @@ def _dev_find(fn, handle, ps, payload, pay_off, nbits, prev0, sym_off, index, ch
         d_so = DeviceBuffer(so.nbytes, so)
         index = np.ascontiguousarray(index, dtype=np.uint64)
         d_idx = DeviceBuffer(max(index.nbytes, 8), index if index.size else None)
-    wsb = l.mh_dev_find_batch_workspace(n, sym_total, chunk_symbols if index is not None else 0)
+    wsb = (ws_fn or l.mh_dev_find_batch_workspace)(n, sym_total, chunk_symbols if index is not None else 0)
     d_ws = DeviceBuffer(wsb)
     d_st = DeviceBuffer(max(n, 1) * 4, np.full(max(n, 1), 99, dtype=np.int32))
 
@@ -591,16 +601,16 @@ def _dev_source(payload, pay_off, nbits, sym_off, index):
     return n, int(pay_off[n]), d_pl, d_po, d_nb, so, d_idx
 
 
-def _dev_histogram_coded(fn, handle, order, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols):
-    """One mh_dev_histogram_coded_batch / _each call: (counts[256 or 65536], per-stream status[n], mh_dev_status); asserts that
-    the FIND_GUARD words behind the counts kept their fill."""
+def _dev_histogram_coded(fn, handle, order, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols, ws_fn=None):
+    """One mh_dev_histogram_coded_batch / _each / _batch_o2 call: (counts[256, 65536 or 1 << 24], per-stream status[n],
+    mh_dev_status); asserts that the FIND_GUARD words behind the counts kept their fill."""
     l = lib()
     n, pay_total, d_pl, d_po, d_nb, so, d_idx = _dev_source(payload, pay_off, nbits, sym_off, index)
     sym_total = int(so[n]) if so is not None else 0
     d_so = DeviceBuffer(so.nbytes, so) if so is not None else None
-    nc = 65536 if order else 256
+    nc = (1 << 24) if order == 2 else (65536 if order else 256)
     d_counts = DeviceBuffer((nc + FIND_GUARD) * 8, np.full(nc + FIND_GUARD, FIND_FILL, dtype=np.uint64))
-    wsb = l.mh_dev_histogram_coded_workspace(n, sym_total, chunk_symbols if index is not None else 0)
+    wsb = (ws_fn or l.mh_dev_histogram_coded_workspace)(n, sym_total, chunk_symbols if index is not None else 0)
     d_ws = DeviceBuffer(wsb)
     d_st = DeviceBuffer(max(n, 1) * 4, np.full(max(n, 1), 99, dtype=np.int32))
     _check(fn(handle, order, d_pl.ptr, d_po.ptr, d_nb.ptr, n, pay_total, prev0, d_so.ptr if d_so else None, sym_total,
@@ -612,7 +622,7 @@ def _dev_histogram_coded(fn, handle, order, payload, pay_off, nbits, prev0, sym_
 
 
 def _dev_recode(fn, src, dst, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols, cap=None, count_only=False, want_index=True,
-                sym_total=None):
+                sym_total=None, ws_fn=None):
     """One mh_dev_recode_batch / mh_dev_recode_each call with guards around every output.  cap None: a count-only call first,
     then one with exactly out_off[n] bytes of room.  Index-free (index None) with a destination index and no sym_total: the
     count-only call sizes it.  Returns a dict: payload (the min(cap, out_off[n]) bytes), out_off[n + 1], nbits[n], index (the whole
@@ -627,7 +637,7 @@ def _dev_recode(fn, src, dst, payload, pay_off, nbits, prev0, sym_off, index, ch
 
     def call(room, with_payload, with_index, st):
         d_so = DeviceBuffer((n + 1 + G) * 8, np.concatenate([so if indexed else np.full(n + 1, F, dtype=np.uint64), np.full(G, F, dtype=np.uint64)]))
-        wsb = l.mh_dev_recode_batch_workspace(n, st, chunk_symbols if indexed else 0)
+        wsb = (ws_fn or l.mh_dev_recode_batch_workspace)(n, st, chunk_symbols if indexed else 0)
         d_ws = DeviceBuffer(wsb)
         d_out = DeviceBuffer(room + RANGE_GUARD + 16, np.full(room + RANGE_GUARD + 16, RANGE_FILL, dtype=np.uint8)) if with_payload else None
         d_oo = DeviceBuffer((n + 1 + G) * 8, np.full(n + 1 + G, F, dtype=np.uint64))
@@ -673,6 +683,14 @@ def _dev_recode(fn, src, dst, payload, pay_off, nbits, prev0, sym_off, index, ch
         if not indexed and sym_total is None:
             st = int(pre["sym_off"][n])
     return call(cap, True, want_index and bool(chunk_symbols), st)
+
+
+def histogram_coded_batch_o2(src, order, payload, pay_off, nbits, prev0=PREV0, sym_off=None, index=None, chunk_symbols=0):
+    """The training counts of an order-`order` model from a batch coded under `src`, no decoded byte written
+    (mh_dev_histogram_coded_batch_o2; `src` or `order` is 2): counts[256, 65536 or 1 << 24].  Raises when a stream fails."""
+    counts, status, rc = src.dev_histogram_coded_o2(order, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols)
+    _check(rc, "mh_dev_histogram_coded_batch_o2")
+    return counts
 
 
 class Model:
@@ -917,7 +935,12 @@ class Model:
                                  chunk_symbols, out_cap)
 
     def find_batch(self, ps, payload, pay_off, nbits, prev0=PREV0, sym_off=None, index=None, chunk_symbols=0, hit_cap=None, check=True):
-        """mh_find_batch (host form): (hit_off[n + 1], hits[k, 3] = (stream, begin, end), hit_pattern[k], per-stream status[n],
+        """mh_find_batch (host form): the arguments and results of _find_batch."""
+        return self._find_batch(lib().mh_find_batch, "mh_find_batch", ps, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols,
+                                hit_cap, check)
+
+    def _find_batch(self, fn, what, ps, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols, hit_cap, check):
+        """mh_find_batch / mh_find_batch_o2 (host form): (hit_off[n + 1], hits[k, 3] = (stream, begin, end), hit_pattern[k], per-stream status[n],
         return code).  hit_cap None: a count-only call first, then one with room for every hit; hit_cap 'count': count only.
         check=False returns a failed stream's status or MH_ERR_CAPACITY instead of raising."""
         l = lib()
@@ -931,13 +954,13 @@ class Model:
         st = np.zeros(max(n, 1), dtype=np.int32)
 
         def call(hits, pat, cap):
-            rc = l.mh_find_batch(self._h, ps.handle, _ptr(payload), pay_off.ctypes.data, nbits.ctypes.data if n else None, n, prev0,
-                                 so.ctypes.data if so is not None else None,
-                                 (idx.ctypes.data if idx.size else pay_off.ctypes.data) if idx is not None else None, chunk_symbols,
-                                 ho.ctypes.data, hits.ctypes.data if hits is not None else None, pat.ctypes.data if pat is not None else None,
-                                 cap, st.ctypes.data)
+            rc = fn(self._h, ps.handle, _ptr(payload), pay_off.ctypes.data, nbits.ctypes.data if n else None, n, prev0,
+                    so.ctypes.data if so is not None else None,
+                    (idx.ctypes.data if idx.size else pay_off.ctypes.data) if idx is not None else None, chunk_symbols,
+                    ho.ctypes.data, hits.ctypes.data if hits is not None else None, pat.ctypes.data if pat is not None else None,
+                    cap, st.ctypes.data)
             if rc != MH_OK and (check or not (st[:n].any() or rc == MH_ERR_CAPACITY)):
-                raise MhError(rc, "mh_find_batch")
+                raise MhError(rc, what)
             return rc
 
         if hit_cap is None or hit_cap == "count":
@@ -967,7 +990,12 @@ class Model:
 
     def recode_batch(self, dst, payload, pay_off, nbits, prev0=PREV0, sym_off=None, index=None, chunk_symbols=0, cap=None, want_index=True,
                      check=True):
-        """mh_recode_batch (host form): dict(payload, out_off[n + 1], nbits[n], index or None, dropped[n], status[n], sym_off[n + 1], rc).
+        """mh_recode_batch (host form): the arguments and results of _recode_batch."""
+        return self._recode_batch(lib().mh_recode_batch, "mh_recode_batch", dst, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols,
+                                  cap, want_index, check)
+
+    def _recode_batch(self, fn, what, dst, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols, cap, want_index, check):
+        """mh_recode_batch / mh_recode_batch_o2 (host form): dict(payload, out_off[n + 1], nbits[n], index or None, dropped[n], status[n], sym_off[n + 1], rc).
         cap None: room for the destination's worst case.  check=False returns a failed stream's status or MH_ERR_CAPACITY
         instead of raising."""
         l = lib()
@@ -990,12 +1018,12 @@ class Model:
         oi = None
         if want_index and chunk_symbols:
             oi = np.full(max(int(l.mh_batch_index_capacity(bound, n, chunk_symbols)), 1), FIND_FILL, dtype=np.uint64)
-        rc = l.mh_recode_batch(self._h, dst.handle, _ptr(payload), pay_off.ctypes.data, nbits.ctypes.data if n else None, n, prev0,
-                               so.ctypes.data, (idx.ctypes.data if idx.size else pay_off.ctypes.data) if idx is not None else None,
-                               chunk_symbols, out.ctypes.data, cap, oo.ctypes.data, onb.ctypes.data, oi.ctypes.data if oi is not None else None,
-                               dr.ctypes.data, st.ctypes.data)
+        rc = fn(self._h, dst.handle, _ptr(payload), pay_off.ctypes.data, nbits.ctypes.data if n else None, n, prev0,
+                so.ctypes.data, (idx.ctypes.data if idx.size else pay_off.ctypes.data) if idx is not None else None,
+                chunk_symbols, out.ctypes.data, cap, oo.ctypes.data, onb.ctypes.data, oi.ctypes.data if oi is not None else None,
+                dr.ctypes.data, st.ctypes.data)
         if rc != MH_OK and (check or not (st[:n].any() or rc == MH_ERR_CAPACITY)):
-            raise MhError(rc, "mh_recode_batch")
+            raise MhError(rc, what)
         return dict(payload=out[:min(int(oo[n]), cap)], out_off=oo, nbits=onb[:n], index=oi, dropped=dr[:n], status=st[:n], sym_off=so, rc=rc)
 
     def decompress_batch_ranges(self, blobs, lookups, indices=None, chunk_symbols=0, lengths=None):
@@ -1163,6 +1191,35 @@ class Model:
         self._require_o2("mh_dev_decode_batch_o2_ranges")
         return _dev_batch_ranges(lib().mh_dev_decode_batch_o2_ranges, self._h, payload, pay_off, nbits, lookups, prev0, sym_off, index,
                                  chunk_symbols, out_cap)
+
+    # ---- order 2 in search and re-coding (include/mh.h, "ORDER 2 IN SEARCH AND RE-CODING") -----------------------------------
+    def find_batch_o2(self, ps, payload, pay_off, nbits, prev0=PREV0, sym_off=None, index=None, chunk_symbols=0, hit_cap=None, check=True):
+        """mh_find_batch_o2 (host form; this model is order 2): find_batch's arguments and results."""
+        return self._find_batch(lib().mh_find_batch_o2, "mh_find_batch_o2", ps, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols,
+                                hit_cap, check)
+
+    def dev_find_batch_o2(self, ps, payload, pay_off, nbits, prev0=PREV0, sym_off=None, index=None, chunk_symbols=0, hit_cap=None,
+                          count_only=False):
+        """One mh_dev_find_batch_o2 call (two when hit_cap is None) with guard words behind its outputs: dev_find_batch's results."""
+        return _dev_find(lib().mh_dev_find_batch_o2, self._h, ps, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols, hit_cap,
+                         count_only, ws_fn=lib().mh_dev_find_batch_o2_workspace)
+
+    def dev_histogram_coded_o2(self, order, payload, pay_off, nbits, prev0=PREV0, sym_off=None, index=None, chunk_symbols=0):
+        """One mh_dev_histogram_coded_batch_o2 call on a batch coded under this model (any order; the model or `order` is 2):
+        (counts[256, 65536 or 1 << 24], per-stream status[n], mh_dev_status)."""
+        return _dev_histogram_coded(lib().mh_dev_histogram_coded_batch_o2, self._h, order, payload, pay_off, nbits, prev0, sym_off, index,
+                                    chunk_symbols, ws_fn=lib().mh_dev_histogram_coded_batch_o2_workspace)
+
+    def dev_recode_batch_o2(self, dst, payload, pay_off, nbits, prev0=PREV0, sym_off=None, index=None, chunk_symbols=0, **kw):
+        """One mh_dev_recode_batch_o2 call (this model or `dst` is order 2) with guards around its outputs: the dict of _dev_recode."""
+        return _dev_recode(lib().mh_dev_recode_batch_o2, self._h, dst.handle, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols,
+                           ws_fn=lib().mh_dev_recode_batch_o2_workspace, **kw)
+
+    def recode_batch_o2(self, dst, payload, pay_off, nbits, prev0=PREV0, sym_off=None, index=None, chunk_symbols=0, cap=None, want_index=True,
+                        check=True):
+        """mh_recode_batch_o2 (host form; this model or `dst` is order 2): recode_batch's arguments and results."""
+        return self._recode_batch(lib().mh_recode_batch_o2, "mh_recode_batch_o2", dst, payload, pay_off, nbits, prev0, sym_off, index,
+                                  chunk_symbols, cap, want_index, check)
 
     def decompress_batch_o2_ranges(self, blobs, lookups, indices=None, chunk_symbols=0, lengths=None):
         """decompress_batch_ranges for an order-2 model: lookups into whole `.cm` files of compress_batch_o2."""
