@@ -1,0 +1,194 @@
+"""The references of the batch-family fuzz (tests/batch_ref.py) pinned to the CPU oracle and the golden fixtures, and the
+coverage that the fixed case list of tests/test_gpu_batch_fuzz.py must keep.  No GPU, no library call: everything here is the
+oracle, numpy and the committed files."""
+import functools
+import os
+
+import numpy as np
+import pytest
+
+import batch_ref
+import find_ref
+import recode_ref
+from conftest import GOLDEN_DIR, expected_file, golden, golden_names
+from oracle import mh_oracle
+
+TEXTS = ["input_ipsum.txt", "input_wiki_cpp.html", "input_wiki_cpp.txt"]
+
+
+def lines_of(name, limit=400):
+    data = golden()[name]["data"]
+    return ([ln for ln in data.split(b"\n")][:limit] + [b""]) if len(data) < (1 << 19) else [data]
+
+
+# ---------------------------------------------------------------------------------------------------- the packer
+@pytest.mark.parametrize("name", golden_names())
+@pytest.mark.parametrize("order", [0, 1, 2])
+def test_pack_equals_the_oracle_s_compress_of_every_line(name, order):
+    msgs = lines_of(name)
+    o = mh_oracle.Model.from_data(golden()[name]["data"], order)
+    lens, codes = (o.codes_o2() if order == 2 else o.codes())
+    p = batch_ref.pack(msgs, lens, codes, order, 0x20, 256)
+    assert p.pay_off[0] == 0                                     # (a line's first pair may lack a code: the oracle skips it too)
+    for i, m in enumerate(msgs):
+        blob, nbits = o.compress(m)
+        assert int(p.nbits[i]) == nbits, (name, i)
+        assert p.payload[int(p.pay_off[i]):int(p.pay_off[i + 1])].tobytes() == blob[1:], (name, i)
+        if order < 2:
+            assert np.array_equal(p.slices[i], recode_ref.index_slice(lens, m, order, 256)), (name, i)
+
+
+def test_order_2_index_entries_carry_both_bytes_in_front():
+    msgs = [b"abcdefgh" * 40, b"", b"x", b"xy" * 128, b"q" * 257]
+    o = mh_oracle.Model.from_counts(batch_ref.histogram(msgs, 2, 0x61), 2)
+    lens, codes = o.codes_o2()
+    p = batch_ref.pack(msgs, lens, codes, 2, 0x61, 256)
+    assert [s.size for s in p.slices] == [2, 0, 1, 1, 2]
+    assert int(p.slices[0][0]) == 0x6161 << 48 and int(p.slices[2][0]) == 0x6161 << 48
+    rel = int(lens[batch_ref.keys([msgs[0][:256]], 2, 0x61)[0]].sum())
+    assert int(p.slices[0][1]) == (ord("g") << 56) | (ord("h") << 48) | rel
+    assert int(p.slices[4][1]) == (ord("q") << 56) | (ord("q") << 48) | int(p.nbits[4]) - int(lens[(0x7171 << 8) | 0x71])
+    assert np.array_equal(p.slices_of(p.index_array(256), 256), p.all_slices())
+
+
+@pytest.mark.parametrize("x,y", [("input_wiki_cpp.txt", "input_wiki_cpp.html"), ("input_ipsum.txt", "input_wiki_cpp.html"),
+                                 ("input_wiki_cpp.html", "input_ipsum.txt")])
+@pytest.mark.parametrize("order", [0, 1])
+def test_pack_equals_recode_ref_under_a_destination_with_drops(x, y, order):
+    msgs = lines_of(x)
+    dst = mh_oracle.Model.from_data(golden()[y]["data"], order)
+    lens, codes = dst.codes()
+    p = batch_ref.pack(msgs, lens, codes, order, 0x20, 512)
+    want = recode_ref.recode(msgs, dst, 512)
+    payload, off, nbits, dropped = recode_ref.packed(want)
+    assert dropped.sum() > 0 or (order == 0 and y != "input_ipsum.txt")      # (the html has every byte value of the texts)
+    assert np.array_equal(p.payload, payload) and np.array_equal(p.pay_off, off)
+    assert np.array_equal(p.nbits, nbits) and np.array_equal(p.dropped, dropped)
+    assert all(np.array_equal(a, w[3]) for a, w in zip(p.slices, want))
+
+
+@pytest.mark.parametrize("x,y", [("input_a.txt", "input_b.txt"), ("input_ipsum.txt", "union_ipsum_wiki"), ("input_wiki_cpp.txt", "union_ipsum_wiki"),
+                                 ("input_wiki_cpp.txt", "input_wiki_cpp.html"), ("input_ipsum.txt", "input_wiki_cpp.html"),
+                                 ("input_wiki_cpp.html", "input_ipsum.txt")])
+def test_pack_equals_the_files_the_reference_program_wrote(x, y):
+    table = expected_file(y, "e")
+    if table is None:
+        with open(os.path.join(GOLDEN_DIR, "recode", y + ".e"), "rb") as f:
+            table = f.read()
+    with open(os.path.join(GOLDEN_DIR, "recode", "%s__%s.cm" % (x, y)), "rb") as f:
+        want = f.read()
+    lens, codes = mh_oracle.Model.from_table(table).codes()
+    p = batch_ref.pack([golden()[x]["data"]], lens, codes, 1, 0x20)
+    assert p.payload.tobytes() == want[1:] and (8 - int(p.nbits[0]) % 8) % 8 == want[0] & 7
+
+
+@pytest.mark.parametrize("name", golden_names())
+def test_histograms_equal_the_oracle_s(name):
+    data = golden()[name]["data"][:200000]
+    assert np.array_equal(batch_ref.histogram([data], 0), mh_oracle.histogram_o0(data))
+    for prev0 in (0x20, 0x65):
+        assert np.array_equal(batch_ref.histogram([data], 1, prev0), mh_oracle.histogram_o1(data, prev0))
+    assert np.array_equal(batch_ref.histogram([data], 2), mh_oracle.histogram_o2(data))
+    if name in TEXTS:                                                # a batch is the sum of its messages
+        msgs = lines_of(name, 50)
+        for order, fn in ((0, mh_oracle.histogram_o0), (1, mh_oracle.histogram_o1), (2, mh_oracle.histogram_o2)):
+            assert np.array_equal(batch_ref.histogram(msgs, order), sum(fn(m) for m in msgs))
+
+
+@pytest.mark.parametrize("limit", [8, 12])
+def test_limited_codes_equal_the_rule_s_table_read_by_the_oracle(limit):
+    from test_limit_abi import limited_model
+    counts = mh_oracle.histogram_o1(golden()["input_wiki_cpp.html"]["data"])
+    table, recoded = limited_model(counts, 1, limit, mh_oracle.Model.from_counts(counts, 1).table_bytes())
+    assert any(r is not None for r in recoded)
+    lens, codes = mh_oracle.Model.from_table(table).codes()
+    got_l, got_c = batch_ref.limited_codes(counts, 1, limit)
+    assert got_l.max() == limit and np.array_equal(got_l, lens) and np.array_equal(got_c[lens > 0], codes[lens > 0])
+
+
+def test_select_takes_the_cheapest_entry_that_covers_the_stream():
+    msgs = [b"aaaa", b"", b"abab", b"zz", b"ab"]
+    a = batch_ref.oracle_codes(batch_ref.histogram([b"aaaaaaab"], 0), 0)[0]
+    b = batch_ref.oracle_codes(batch_ref.histogram([b"abababab" * 4 + b"aa"], 1, 0x20), 1)[0]
+    choice, nbits = batch_ref.select([(0, a), (1, b), (0, a)], msgs)
+    assert choice.tolist() == [0, 0, 0, batch_ref.BANK_NONE, 0] and nbits.tolist()[:3] == [4, 0, 4] and nbits[3] == 2 ** 64 - 1
+    choice, _ = batch_ref.select([(1, b), (0, a)], msgs)
+    assert choice.tolist() == [0, 0, 0, batch_ref.BANK_NONE, 0]       # ties go to the lowest entry
+
+
+# ---------------------------------------------------------------------------------------------------- coverage
+@functools.lru_cache(maxsize=1)
+def stats():
+    out = []
+    for case in batch_ref.draw_cases():
+        w = case.world()
+        so, do = case.orders
+        c = case.chunk
+        src = batch_ref.pack(w.messages, *case.codes("src"), so, w.prev0, c)
+        dst = batch_ref.pack(w.messages, *case.codes("dst"), do, w.prev0, c)
+        ln = np.diff(src.sym_off.astype(np.int64))
+        hits = find_ref.find_hits(w.messages, w.patterns, fold=w.fold)
+        heads = np.concatenate([np.arange(int(a) + c, int(b), c) for a, b in zip(src.sym_off[:-1], src.sym_off[1:])] + [np.zeros(0, dtype=np.int64)])
+        own = batch_ref.histogram(w.messages, max(so, 1), w.prev0).reshape(-1, 256)
+        out.append(dict(case=case, prev0=w.prev0, total=int(ln.sum()), empty=bool((ln == 0).any()), multiple=bool(((ln > 0) & (ln % c == 0)).any()),
+                        src_max=int(src.used.max()), dst_max=int(dst.used.max()), one_symbol=bool(((own > 0).sum(axis=1) == 1).any()),
+                        straddle=find_ref.straddles(hits, c), at_end=sum(1 for i, _, e, _ in hits if e == ln[i]), hits=len(hits),
+                        drops=int(dst.dropped.sum()), head_max=int(dst.used[heads.astype(np.int64)].max()) if heads.size else 0,
+                        nowhere=len(set(range(len(w.patterns))) - {h[3] for h in hits})))
+    return out
+
+
+def count(pred):
+    return sum(1 for s in stats() if pred(s))
+
+
+def test_the_case_list_is_fixed_and_sized():
+    cases = batch_ref.draw_cases()
+    assert [c.id for c in cases] == [c.id for c in batch_ref.draw_cases.__wrapped__(batch_ref.SEED)]
+    assert len(set(c.id for c in cases)) == len(cases) == 96
+    assert sum(1 for c in cases if 2 not in c.orders) == 64
+    for s in stats():
+        case, w = s["case"], s["case"].world()
+        assert 0 < s["total"] <= (batch_ref.DEEP_BYTES if case.deep else batch_ref.CASE_BYTES), case.id
+        assert len(w.messages) == case.n_streams and len(w.lookups) == 32, case.id
+        assert 1 <= len(w.patterns) <= 15 and sum(len(p) for p in w.patterns) <= 64 and all(w.patterns), case.id
+        assert s["straddle"] >= 1 and s["at_end"] >= 1 and s["nowhere"] >= 1, case.id
+        assert any(b == e for _, b, e in w.lookups) and any(b == 0 and e == len(w.messages[i]) for i, b, e in w.lookups), case.id
+        assert any(b // case.chunk != (e - 1) // case.chunk for _, b, e in w.lookups if e > b), case.id
+        assert case.src_kind != "foreign" and (s["drops"] == 0 or case.dst_kind == "foreign"), case.id
+
+
+def test_coverage_of_the_fixed_case_list():
+    """What the fuzz must keep reaching, computed from the references alone."""
+    for c in batch_ref.CHUNKS:
+        assert count(lambda s: s["case"].chunk == c) >= 4, c
+    for n in batch_ref.STREAM_COUNTS:
+        assert count(lambda s: s["case"].n_streams == n) >= 3, n
+    assert count(lambda s: s["prev0"] != 0x20) >= 10
+    assert count(lambda s: s["empty"]) >= 10
+    assert count(lambda s: s["multiple"]) >= 10
+    deep = lambda s: s["case"].deep
+    assert count(lambda s: deep(s) and max(s["src_max"], s["dst_max"]) > 32) >= 8
+    assert count(lambda s: deep(s) and max(s["src_max"], s["dst_max"]) > 56) >= 3
+    n_deep = count(deep)
+    assert 3 * count(lambda s: deep(s) and s["case"].alphabet > 57) >= n_deep       # the longest code is over 56 bits
+    assert count(lambda s: max(s["src_max"], s["dst_max"]) > 12) >= 10
+    assert count(lambda s: s["one_symbol"]) >= 10
+    assert count(lambda s: s["straddle"] > 0) >= 10 and count(lambda s: s["at_end"] > 0) >= 10
+    assert count(lambda s: s["drops"] > 0) >= 10
+    for so in (0, 1, 2):
+        for do in (0, 1, 2):
+            assert count(lambda s: s["case"].orders == (so, do)) >= 4, (so, do)
+    assert count(lambda s: s["case"].orders == (1, 2) and s["head_max"] > 32) >= 3
+    # the lookups with two seams inside, the [0, 0) of an empty stream, an index-free lookup that ends at the stream's end
+    assert count(lambda s: any((e - 1) // s["case"].chunk - b // s["case"].chunk >= 2 for _, b, e in s["case"].world().lookups if e > b)) >= 10
+    assert count(lambda s: any(e == 0 and not s["case"].world().messages[i] for i, b, e in s["case"].world().lookups)) >= 10
+
+
+def test_the_new_files_leave_no_test_out():
+    here = os.path.dirname(os.path.abspath(__file__))
+    for name in ("batch_ref.py", "test_batch_ref.py", "test_gpu_batch_fuzz.py"):
+        with open(os.path.join(here, name)) as f:
+            text = f.read()
+        for word in ("pytest.sk", "mark.sk", "importorsk", "xfa"):
+            assert word + ("ip" if word.endswith("k") else "il") not in text, (name, word)

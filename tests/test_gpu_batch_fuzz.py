@@ -1,0 +1,240 @@
+"""Seeded differential fuzz of the batch call family on the GPU: every case of tests/batch_ref.py goes through every batch call
+of include/mh.h — encode, histograms, decode (indexed, index-free, segment states), lookups, search, coded histogram, re-code,
+per-stream models and banks — and every result is compared exactly with the references of tests/batch_ref.py: the CPU oracle's
+code tables and plain numpy on the original messages, never another call of the library.  tests/test_batch_ref.py pins those
+references and the edges that the case list reaches.
+
+One test per case; its id names the case.  A case runs every family and then reports all that differed, so one failure does
+not hide the next.  The decoders read the reference's payloads and index, not the encoder's output."""
+import numpy as np
+import pytest
+
+import __graft_entry__ as entry
+import batch_ref
+import find_ref
+from oracle import mh_oracle
+
+pytestmark = pytest.mark.gpu
+
+CASES = batch_ref.draw_cases()
+FEEDBACK = 256                     # hit records fed back as lookups: all of them, or this many evenly spaced ones (first and last included)
+
+
+@pytest.fixture(scope="module")
+def mhc():
+    mod = entry.load_package()
+    mod.lib()
+    assert mod.device_count() >= 1, "GPU tests need a device; the codec has no CPU fallback"
+    return mod
+
+
+def same(a, b):
+    return np.array_equal(np.asarray(a), np.asarray(b))
+
+
+class Rig:
+    """One case on the device: the models, the reference forms of the batch and a list of what differed."""
+
+    def __init__(self, mhc, case):
+        self.mhc, self.case, self.w = mhc, case, case.world()
+        self.so, self.do = case.orders
+        self.c, self.p0, self.msgs = case.chunk, self.w.prev0, self.w.messages
+        self.n = len(self.msgs)
+        self.joined = b"".join(self.msgs)
+        self.bad = []
+        (sc, sl), (dc, dl) = case.counts("src"), case.counts("dst")
+        self.S, self.D = mhc.Model.from_counts(sc, self.so, max_len=sl), mhc.Model.from_counts(dc, self.do, max_len=dl)
+        self.rs = batch_ref.pack(self.msgs, *case.codes("src"), self.so, self.p0, self.c)
+        self.rd = batch_ref.pack(self.msgs, *case.codes("dst"), self.do, self.p0, self.c)
+
+    def check(self, ok, what):
+        if not ok:
+            self.bad.append(what)
+
+    def ok(self, rc, st, what):
+        self.check(rc == self.mhc.MH_OK and not np.asarray(st).any(), what + ": status")
+
+    def family(self, fn):
+        try:
+            fn()
+        except Exception as e:                                    # (a call that raises is a finding of this family; the others still run)
+            self.bad.append("%s: %s: %s" % (fn.__name__, type(e).__name__, e))
+
+    def source(self, ref, indexed):
+        """(payload, pay_off, nbits), keywords of a reader of the reference's batch."""
+        kw = dict(prev0=self.p0, chunk_symbols=self.c)
+        if indexed:
+            kw.update(sym_off=ref.sym_off, index=ref.index_array(self.c))
+        return (ref.payload, ref.pay_off, ref.nbits), kw
+
+    def same_batch(self, got, ref, what):
+        pay, off, nb, idx, so = got
+        self.check(same(off, ref.pay_off) and same(nb, ref.nbits) and same(so, ref.sym_off), what + ": offsets, nbits")
+        self.check(same(pay, ref.payload), what + ": payload")
+        self.check(same(ref.slices_of(idx, self.c), ref.all_slices()), what + ": index slices")
+
+    # ---- encode ----
+    def encode(self):
+        enc = lambda m, o: (m.encode_batch_o2 if o == 2 else m.encode_batch)(self.msgs, prev0=self.p0, chunk_symbols=self.c)
+        self.same_batch(enc(self.S, self.so), self.rs, "encode (source)")
+        self.same_batch(enc(self.D, self.do), self.rd, "encode (destination, %s)" % self.case.dst_kind)
+        if self.case.dst_kind != "foreign" and self.so < 2:       # encode-only under a model that lacks pairs of the batch
+            counts = batch_ref.histogram(self.w.foreign, self.so, self.p0)
+            ref = batch_ref.pack(self.msgs, *batch_ref.oracle_codes(counts, self.so), self.so, self.p0, self.c)
+            self.same_batch(enc(self.mhc.Model.from_counts(counts, self.so), self.so), ref, "encode (foreign)")
+        for order in (0, 1):
+            got = self.mhc.histogram_o1_batch(self.msgs, prev0=self.p0, order=order)
+            self.check(same(got, batch_ref.histogram(self.msgs, order, self.p0)), "histogram_o1_batch order %d" % order)
+        self.check(same(self.mhc.histogram_o2_batch(self.msgs, prev0=self.p0), batch_ref.histogram(self.msgs, 2, self.p0)), "histogram_o2_batch")
+
+    # ---- decode ----
+    def decode(self):
+        S, rs = self.S, self.rs
+        dec = S.decode_batch_o2 if self.so == 2 else S.decode_batch
+        for indexed in (True, False):
+            src, kw = self.source(rs, indexed)
+            if not indexed:
+                kw.pop("chunk_symbols")
+            out, so, st = dec(*src, check=False, **kw)
+            self.check(not st.any() and out == self.joined and same(so, rs.sym_off), "decode indexed=%s" % indexed)
+        if self.so < 2:
+            src = (rs.payload, rs.pay_off, rs.nbits)
+            out, so, st = S.decode_batch_segments(*src, prev0=self.p0)
+            self.check(not st.any() and out == self.joined and same(so, rs.sym_off), "decode_batch_segments")
+            so, idx, st = S.index_batch(*src, self.c, prev0=self.p0)
+            self.check(not st.any() and same(so, rs.sym_off) and same(rs.slices_of(idx, self.c), rs.all_slices()), "index_batch")
+
+    # ---- lookups ----
+    def lookups(self):
+        S, rs, w = self.S, self.rs, self.w
+        dev = S.dev_decode_batch_o2_ranges if self.so == 2 else S.dev_decode_batch_ranges
+        host = S.decode_batch_o2_ranges if self.so == 2 else S.decode_batch_ranges
+        for indexed in (True, False):
+            src, kw = self.source(rs, indexed)
+            got, st, rc = dev(*src, w.lookups, **kw)
+            self.ok(rc, st, "lookups indexed=%s" % indexed)
+            self.check(got == w.lookup_bytes, "lookups indexed=%s" % indexed)
+            if self.case.index % 4 == 0:
+                got, st = host(*src, w.lookups, **kw)
+                self.check(not st.any() and got == w.lookup_bytes, "lookups (host form) indexed=%s" % indexed)
+
+    # ---- search ----
+    def search(self, find=None, ref=None, what="search"):
+        w, cap_error = self.w, self.mhc.MH_ERR_CAPACITY
+        find = find or (self.S.dev_find_batch_o2 if self.so == 2 else self.S.dev_find_batch)
+        ref = ref or self.rs
+        ps = self.mhc.PatternSet(w.patterns, fold=w.fold)
+        hits = find_ref.find_hits(self.msgs, w.patterns, fold=w.fold)
+        w_off, w_rec, w_pat = find_ref.hit_arrays(hits, self.n)
+        for indexed in (True, False):
+            tag = "%s indexed=%s" % (what, indexed)
+            src, kw = self.source(ref, indexed)
+            ho, rec, pat, st, rc = find(ps, *src, **kw)
+            self.ok(rc, st, tag)
+            self.check(same(ho, w_off) and same(rec, w_rec) and same(pat, w_pat), tag + ": records")
+            ho, _, _, st, rc = find(ps, *src, count_only=True, **kw)
+            self.ok(rc, st, tag + " count only")
+            self.check(same(ho, w_off), tag + ": count only")
+            cap = len(hits) - 1
+            ho, rec, pat, st, rc = find(ps, *src, hit_cap=cap, **kw)
+            self.check(rc == cap_error and not st.any() and same(ho, w_off) and same(rec, w_rec[:cap]) and same(pat, w_pat[:cap]), tag + ": hit_cap")
+        return w_rec, w_pat
+
+    def search_and_feed_back(self):
+        w_rec, w_pat = self.search()
+        pick = np.unique(np.linspace(0, len(w_rec) - 1, min(len(w_rec), FEEDBACK)).astype(np.int64))
+        dev = self.S.dev_decode_batch_o2_ranges if self.so == 2 else self.S.dev_decode_batch_ranges
+        src, kw = self.source(self.rs, True)
+        got, st, rc = dev(*src, w_rec[pick], **kw)
+        self.ok(rc, st, "hit records as lookups")
+        fold = find_ref.fold_ascii if self.w.fold else bytes
+        self.check([fold(g) for g in got] == [fold(self.w.patterns[int(j)]) for j in w_pat[pick]], "hit records as lookups")
+
+    # ---- coded histogram ----
+    def coded_histogram(self):
+        for order in (0, 1, 2):
+            fn = self.S.dev_histogram_coded_o2 if 2 in (order, self.so) else self.S.dev_histogram_coded
+            want = batch_ref.histogram(self.msgs, order, self.p0)
+            for indexed in (True, False):
+                src, kw = self.source(self.rs, indexed)
+                counts, st, rc = fn(order, *src, **kw)
+                self.ok(rc, st, "coded histogram order %d indexed=%s" % (order, indexed))
+                self.check(same(counts, want), "coded histogram order %d indexed=%s" % (order, indexed))
+
+    # ---- re-code ----
+    def recode(self, fn=None, ref=None, what="recode"):
+        fn = fn or (self.S.dev_recode_batch_o2 if 2 in self.case.orders else self.S.dev_recode_batch)
+        rd = self.rd
+        for indexed in (True, False):
+            tag = "%s indexed=%s" % (what, indexed)
+            src, kw = self.source(ref or self.rs, indexed)
+            got = fn(self.D, *src, **kw)
+            self.ok(got["rc"], got["status"], tag)
+            self.check(same(got["out_off"], rd.pay_off) and same(got["nbits"], rd.nbits) and same(got["sym_off"], rd.sym_off), tag + ": offsets, nbits")
+            self.check(same(got["payload"], rd.payload), tag + ": payload")
+            self.check(same(got["dropped"], rd.dropped), tag + ": dropped")
+            self.check(same(rd.slices_of(got["index"], self.c), rd.all_slices()), tag + ": index slices")
+            count = fn(self.D, *src, count_only=True, **kw)
+            self.ok(count["rc"], count["status"], tag + " count only")
+            self.check(same(count["out_off"], got["out_off"]) and same(count["nbits"], got["nbits"]) and same(count["dropped"], got["dropped"]),
+                       tag + ": count only")
+
+    # ---- per-stream models ----
+    def each(self):
+        mhc, c, p0 = self.mhc, self.c, self.p0
+        re, tables = batch_ref.pack_each(self.msgs, self.so, p0, c)
+        got = mhc.compress_each(self.msgs, order=self.so, chunk_symbols=c, prev0=p0)
+        self.check([g[0] for g in got] == tables, "compress_each: tables")
+        self.check([g[2] for g in got] == re.nbits.tolist(), "compress_each: nbits")
+        self.check(b"".join(g[1][1:] for g in got) == re.payload.tobytes(), "compress_each: payloads")
+        self.check(same(np.concatenate([g[3] for g in got]), re.all_slices()), "compress_each: index slices")
+        if p0 == batch_ref.PREV0:                                 # the oracle's own stream of every message alone
+            blobs = [mh_oracle.Model.from_data(m, self.so).compress(m)[0] for m in self.msgs]
+            self.check([g[1] for g in got] == blobs, "compress_each: the oracle's files")
+        ms = mhc.ModelSet.from_tables(tables)
+        for indexed in (True, False):
+            src, kw = self.source(re, indexed)
+            if not indexed:
+                kw.pop("chunk_symbols")
+            out, so, st, rc = ms.decode(*src, **kw)
+            self.ok(rc, st, "each decode indexed=%s" % indexed)
+            self.check(out == self.joined and same(so, re.sym_off), "each decode indexed=%s" % indexed)
+            src, kw = self.source(re, indexed)
+            res, st, rc = ms.decode_ranges(*src, self.w.lookups, **kw)
+            self.ok(rc, st, "each lookups indexed=%s" % indexed)
+            self.check(res == self.w.lookup_bytes, "each lookups indexed=%s" % indexed)
+            for order in (0, 1):
+                counts, st, rc = ms.histogram_coded(order, *src, **kw)
+                self.ok(rc, st, "each coded histogram")
+                self.check(same(counts, batch_ref.histogram(self.msgs, order, p0)), "each coded histogram order %d indexed=%s" % (order, indexed))
+        self.search(ms.find, re, "each search")
+        self.recode(ms.recode, re, "each recode")
+
+    # ---- banks ----
+    def bank(self):
+        mhc, p0, msgs = self.mhc, self.p0, self.msgs
+        drawn = [(1, msgs[:(self.n + 1) // 2]), (0, self.w.foreign), (self.so, msgs[::3]), (self.so, msgs)]
+        counts = [(o, batch_ref.histogram(m, o, p0)) for o, m in drawn]
+        codes = [(o, batch_ref.oracle_codes(h, o)) for o, h in counts]
+        bank = mhc.ModelSet.from_models([mhc.Model.from_counts(h, o) for o, h in counts])
+        choice, nbits = bank.select(msgs, prev0=p0)
+        want_c, want_n = batch_ref.select([(o, lc[0]) for o, lc in codes], msgs, p0)
+        self.check(same(choice, want_c) and same(nbits, want_n), "bank select")
+        ref = batch_ref.merge([batch_ref.pack([m], *codes[k][1], codes[k][0], p0, self.c) for m, k in zip(msgs, want_c)])
+        self.same_batch(mhc.encode_bank(bank, msgs, want_c, chunk_symbols=self.c, prev0=p0), ref, "encode_bank")
+        out, so, st = mhc.decode_bank(bank, want_c, ref.payload, ref.pay_off, ref.nbits, prev0=p0, check=False)
+        self.check(not st.any() and out == self.joined and same(so, ref.sym_off), "decode_bank index-free")
+        out, so, st = mhc.decode_bank(bank, want_c, ref.payload, ref.pay_off, ref.nbits, sym_off=ref.sym_off, index=ref.index_array(self.c),
+                                      chunk_symbols=self.c, prev0=p0, check=False)
+        self.check(not st.any() and out == self.joined, "decode_bank indexed")
+
+
+@pytest.mark.parametrize("case", CASES, ids=[c.id for c in CASES])
+def test_every_batch_call_equals_the_references(mhc, case):
+    rig = Rig(mhc, case)
+    families = [rig.encode, rig.decode, rig.lookups, rig.search_and_feed_back, rig.coded_histogram, rig.recode]
+    if 2 not in case.orders and case.n_streams <= 65:
+        families += [rig.each, rig.bank]
+    for fn in families:
+        rig.family(fn)
+    assert not rig.bad, "%s: %d differences:\n  %s" % (case.id, len(rig.bad), "\n  ".join(rig.bad))
