@@ -5,19 +5,6 @@
 
 using namespace mhapi;
 
-namespace {
-
-bool offsets_ok(const uint64_t *off, size_t n) {
-    if (off[0] != 0) return false;
-    for (size_t i = 0; i < n; ++i)
-        if (off[i + 1] < off[i]) return false;
-    return true;
-}
-
-bool order01(const mh_model *m) { return m && (m->type == 0 || m->type == 1); }
-
-}  // namespace
-
 extern "C" {
 
 uint64_t mh_batch_index_base(uint64_t in_off, uint64_t stream, uint32_t chunk_symbols) {
@@ -114,9 +101,7 @@ int mh_dev_decode_batch(const mh_model *m, const uint8_t *d_payload, const uint6
     p.index = d_index; p.chunk_shift = uint32_t(shift);
     p.walk_max_bits = MH_BATCH_WALK_MAX_BITS;
     p.stream_status = d_stream_status ? d_stream_status : reinterpret_cast<int *>(static_cast<unsigned char *>(d_ws) + L.off_status);
-    p.prim = m->d_prim; p.sec = m->d_sec; p.sec_base = m->d_sec_base; p.tree = m->d_tree;
-    p.P = uint32_t(m->dec_bits); p.nsec = m->nsec; p.sec_lds = m->dec_lds ? 1u : 0u;
-    p.direct = m->dec_direct ? 1u : 0u; p.H = uint32_t(m->dec_h);
+    fill_dec_tables(m, p);
     HIP_TRY(mhb::launch_decode_batch(p, d_ws, static_cast<hipStream_t>(stream)));
     return MH_OK;
 }

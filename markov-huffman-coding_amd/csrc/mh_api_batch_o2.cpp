@@ -6,12 +6,6 @@
 
 using namespace mhapi;
 
-namespace {
-
-bool order2(const mh_model *m) { return m && m->type == 2; }
-
-}  // namespace
-
 extern "C" {
 
 size_t mh_dev_histogram_o2_batch_workspace(size_t total) {
@@ -81,8 +75,7 @@ int mh_dev_decode_batch_o2(const mh_model *m, const uint8_t *d_payload, const ui
     p.index = d_index; p.chunk_shift = uint32_t(shift);
     p.walk_max_bits = MH_BATCH_WALK_MAX_BITS;
     p.stream_status = d_stream_status ? d_stream_status : reinterpret_cast<int *>(static_cast<unsigned char *>(d_ws) + L.off_status);
-    p.prim = m->d_prim; p.sec = m->d_sec; p.sec_base = m->d_sec_base; p.tree = m->d_tree;
-    p.P = uint32_t(m->dec_bits); p.nsec = m->nsec;                 // (general form in L2: sec_lds = direct = 0, as decode2_kernel)
+    fill_dec_tables(m, p);
     HIP_TRY(mhb::launch_decode_batch_o2(p, d_ws, static_cast<hipStream_t>(stream)));
     return MH_OK;
 }

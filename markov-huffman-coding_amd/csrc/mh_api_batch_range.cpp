@@ -15,8 +15,6 @@ namespace {
 
 thread_local uint64_t t_batch_range_upload = 0;   // payload bytes the calling thread's last host form uploaded
 
-bool order01(const mh_model *m) { return m && (m->type == 0 || m->type == 1); }
-bool order2(const mh_model *m) { return m && m->type == 2; }
 
 
 // ------------------------------------------------------------------------------------------------ host forms
@@ -313,9 +311,7 @@ int mh_dev_decode_batch_ranges(const mh_model *m, const uint8_t *d_payload, cons
     if (rc != MH_OK) return rc;
     if (m->max_len > mh::MAX_CODE_BITS) return MH_ERR_CODE_TOO_LONG;
     if (!m->d_prim || !have_device()) return MH_ERR_NO_DEVICE;
-    p.tab.prim = m->d_prim; p.tab.sec = m->d_sec; p.tab.sec_base = m->d_sec_base; p.tab.tree = m->d_tree;
-    p.tab.P = uint32_t(m->dec_bits); p.tab.nsec = m->nsec; p.tab.sec_lds = m->dec_lds ? 1u : 0u;
-    p.tab.direct = m->dec_direct ? 1u : 0u; p.tab.H = uint32_t(m->dec_h);
+    fill_dec_tables(m, p.tab);
     HIP_TRY(mhq::launch_batch_ranges(p, true, d_ws, static_cast<hipStream_t>(stream)));
     return MH_OK;
 }

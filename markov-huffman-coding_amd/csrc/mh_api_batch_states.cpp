@@ -8,15 +8,6 @@ using namespace mhapi;
 
 namespace {
 
-bool offsets_ok(const uint64_t *off, size_t n) {
-    if (off[0] != 0) return false;
-    for (size_t i = 0; i < n; ++i)
-        if (off[i + 1] < off[i]) return false;
-    return true;
-}
-
-bool order01(const mh_model *m) { return m && (m->type == 0 || m->type == 1); }
-
 // the arguments every device call takes; the model's part is filled by the callers
 int common(mhs::StParams &p, int kind, const void *model, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits,
            size_t n, uint64_t pay_total, uint8_t prev0, void *d_ws, size_t ws_bytes) {
@@ -40,11 +31,8 @@ int shared_model(mhs::StParams &p, const mh_model *m) {
     if (!order01(m)) return MH_ERR_ARG;
     if (m->max_len > mh::MAX_CODE_BITS) return MH_ERR_CODE_TOO_LONG;
     if (!m->d_prim || !have_device()) return MH_ERR_NO_DEVICE;
-    mhb::DecBatchParams &t = p.tabs;
-    t.prim = m->d_prim; t.sec = m->d_sec; t.sec_base = m->d_sec_base; t.tree = m->d_tree;
-    t.P = uint32_t(m->dec_bits); t.nsec = m->nsec; t.sec_lds = m->dec_lds ? 1u : 0u;
-    t.direct = m->dec_direct ? 1u : 0u; t.H = uint32_t(m->dec_h);
-    p.lds = 1024 + (size_t(256) << t.P) * 2 + (t.sec_lds ? ((size_t(t.nsec) * 2 + 15) & ~size_t(15)) : 0);
+    fill_dec_tables(m, p.tabs);
+    p.lds = mhb::tables_lds(p.tabs);
     if (p.lds > 163840) return MH_ERR_ARG;
     return MH_OK;
 }

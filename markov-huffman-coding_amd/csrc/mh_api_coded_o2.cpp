@@ -1,32 +1,19 @@
-// mh_api_coded_o2.cpp — the calls of include/mh.h, "ORDER 2 IN SEARCH AND RE-CODING": search in batches of order-2 streams
-// (kernels: mh_find_o2.hip), the coded histogram and the re-coding with an order-2 model on at least one side (kernels:
-// mh_recode_o2.hip), and the host-buffer forms.  Extension, parity unpinned.
+// mh_api_coded_o2.cpp — the re-coding calls of include/mh.h, "ORDER 2 IN SEARCH AND RE-CODING": the coded histogram and the
+// re-coding with an order-2 model on at least one side (kernels: mh_recode_o2.hip), and the host-buffer form.  The search
+// calls of that section are in mh_api_find.cpp.  Extension, parity unpinned.
 #include "mh_api_internal.hpp"
 #include "mh_batch.h"
-#include "mh_find_o2.h"
 #include "mh_recode_o2.h"
 
 using namespace mhapi;
 
 namespace {
 
-bool order2(const mh_model *m) { return m && m->type == 2; }
-bool order012(const mh_model *m) { return m && m->type >= 0 && m->type <= 2; }
-
-bool offsets_ok(const uint64_t *off, size_t n) {
-    if (off[0] != 0) return false;
-    for (size_t i = 0; i < n; ++i)
-        if (off[i + 1] < off[i]) return false;
-    return true;
-}
-
 // the source model's decode tables: order 0/1 as mh_dev_decode_batch hands them over, order 2 as mh_dev_decode_batch_o2
 int source_tables(const mh_model *m, mhb::DecBatchParams &b) {
     if (m->max_len > mh::MAX_CODE_BITS) return MH_ERR_CODE_TOO_LONG;
     if (!m->d_prim || !have_device()) return MH_ERR_NO_DEVICE;
-    b.prim = m->d_prim; b.sec = m->d_sec; b.sec_base = m->d_sec_base; b.tree = m->d_tree;
-    b.P = uint32_t(m->dec_bits); b.nsec = m->nsec;
-    if (m->type != 2) { b.sec_lds = m->dec_lds ? 1u : 0u; b.direct = m->dec_direct ? 1u : 0u; b.H = uint32_t(m->dec_h); }
+    fill_dec_tables(m, b);
     return MH_OK;
 }
 
@@ -47,23 +34,10 @@ int source(const mh_model *m, const uint8_t *d_payload, const uint64_t *d_pay_of
     return MH_OK;
 }
 
-// the hits of one decoded message under the host-side automaton, in (end, pattern) order
-struct Hit { uint64_t begin, end; uint32_t pattern; };
-void host_find(const mh_pattern_set *ps, const uint8_t *data, size_t n, std::vector<Hit> &out) {
-    uint64_t D = 0;
-    for (size_t k = 0; k < n; ++k) {
-        D = ((D << 1) | ps->first) & ps->mask[data[k]];
-        for (uint64_t h = D & ps->last; h; h &= h - 1) {
-            const uint32_t b = uint32_t(__builtin_ctzll(h));
-            const uint32_t j = uint32_t(__builtin_popcountll(ps->last & ((1ull << b) - 1ull)));
-            const uint32_t lo = 63u - uint32_t(__builtin_clzll(ps->first & ((2ull << b) - 1ull)));
-            out.push_back(Hit{k + 1 - (b - lo + 1u), k + 1, j});
-        }
-    }
-}
+}  // namespace
 
 // an index-free order-2 stream over the walk cap, decoded alone
-int decode_alone(const mh_model *m, const uint8_t *payload, uint64_t nbits, uint8_t prev0, std::vector<uint8_t> &out) {
+int mhapi::decode_alone(const mh_model *m, const uint8_t *payload, uint64_t nbits, uint8_t prev0, std::vector<uint8_t> &out) {
     const uint64_t minl = uint64_t(m->min_len > 0 ? m->min_len : 1);
     out.assign(size_t(nbits / minl) + 1, 0);
     size_t nb = 0;
@@ -72,150 +46,7 @@ int decode_alone(const mh_model *m, const uint8_t *payload, uint64_t nbits, uint
     return rc;
 }
 
-}  // namespace
-
 extern "C" {
-
-/* ------------------------------------------------------------------------------------------------------- search */
-
-size_t mh_dev_find_batch_o2_workspace(size_t n_streams, uint64_t sym_total, uint32_t chunk_symbols) {
-    return mh_dev_find_batch_workspace(n_streams, sym_total, chunk_symbols);
-}
-
-int mh_dev_find_batch_o2(const mh_model *m, const mh_pattern_set *ps, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits,
-                         size_t n_streams, uint64_t pay_total, uint8_t prev0, const uint64_t *d_sym_off, uint64_t sym_total,
-                         const uint64_t *d_index, uint32_t chunk_symbols, uint64_t *d_hit_off, uint64_t *d_hits, uint32_t *d_hit_pattern,
-                         uint64_t hit_cap, int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
-    if (!order2(m)) return MH_ERR_ARG;
-    if (!ps || (!d_payload && pay_total) || !d_pay_off || (!d_nbits && n_streams) || !d_hit_off || !d_ws) return MH_ERR_ARG;
-    if (!aligned16(d_payload) || !aligned16(d_ws)) return MH_ERR_ARG;
-    int shift = 0;
-    if (d_index && ((shift = chunk_shift_of(chunk_symbols)) < 0 || !d_sym_off)) return MH_ERR_ARG;
-    const uint64_t W = d_index ? mhf::work_items(n_streams, sym_total, chunk_symbols) : 0;
-    const mhf::FindLayout L = mhf::find_layout(n_streams, W);
-    if (ws_bytes < L.total) return MH_ERR_CAPACITY;
-    mhf::FindParams p{};
-    p.b.payload = d_payload; p.b.pay_off = d_pay_off; p.b.nbits = d_nbits; p.b.n = n_streams; p.b.pay_total = pay_total;
-    p.b.prev0 = ctx_of_prev0(m, prev0);
-    p.b.sym_off = d_index ? reinterpret_cast<unsigned long long *>(const_cast<uint64_t *>(d_sym_off)) : nullptr;   // (read only)
-    p.b.sym_total = d_index ? sym_total : 0;
-    p.b.index = d_index; p.b.chunk_shift = uint32_t(shift);
-    p.b.walk_max_bits = MH_BATCH_WALK_MAX_BITS;
-    p.b.stream_status = d_stream_status ? d_stream_status : reinterpret_cast<int *>(static_cast<unsigned char *>(d_ws) + L.off_status);
-    p.first = ps->first; p.last = ps->last; p.max_len = ps->max_len;
-    p.hit_off = reinterpret_cast<unsigned long long *>(d_hit_off);
-    p.hits = reinterpret_cast<unsigned long long *>(d_hits);
-    p.hit_pattern = d_hits ? d_hit_pattern : nullptr;
-    p.hit_cap = d_hits ? hit_cap : 0;
-    const int t = source_tables(m, p.b);
-    if (t != MH_OK) return t;
-    mhf::Automaton a;
-    std::memcpy(a.mask, ps->mask, sizeof a.mask);
-    HIP_TRY(mhf::launch_find_o2(p, a, d_ws, static_cast<hipStream_t>(stream)));
-    return MH_OK;
-}
-
-int mh_find_batch_o2(const mh_model *m, const mh_pattern_set *ps, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits,
-                     size_t n_streams, uint8_t prev0, const uint64_t *sym_off, const uint64_t *index, uint32_t chunk_symbols, uint64_t *hit_off,
-                     uint64_t *hits, uint32_t *hit_pattern, uint64_t hit_cap, int32_t *stream_status) {
-    if (!order2(m) || !ps || !pay_off || (!nbits && n_streams) || !hit_off) return MH_ERR_ARG;
-    if (index && (chunk_shift_of(chunk_symbols) < 0 || !sym_off)) return MH_ERR_ARG;
-    if (!offsets_ok(pay_off, n_streams)) return MH_ERR_ARG;
-    const uint64_t pay_total = pay_off[n_streams];
-    if (!payload && pay_total) return MH_ERR_ARG;
-    for (size_t i = 0; i < n_streams; ++i)
-        if (nbits[i] > (pay_off[i + 1] - pay_off[i]) * 8) return MH_ERR_ARG;
-    if (index && !offsets_ok(sym_off, n_streams)) return MH_ERR_ARG;
-    if (!have_device()) return MH_ERR_NO_DEVICE;
-    if (m->max_len > mh::MAX_CODE_BITS) return MH_ERR_CODE_TOO_LONG;
-    // index-free streams over the walk cap: the device call refuses them; each is decoded alone and searched by the
-    // host-side automaton, its records spliced into place in stream order
-    std::vector<size_t> long_streams;
-    if (!index)
-        for (size_t i = 0; i < n_streams; ++i)
-            if (nbits[i] > MH_BATCH_WALK_MAX_BITS) long_streams.push_back(i);
-    const hipStream_t st = nullptr;
-    const uint64_t sym_total = index ? sym_off[n_streams] : 0;
-    const size_t nidx = index ? size_t(mh_batch_index_capacity(sym_total, n_streams, chunk_symbols)) : 0;
-    const size_t wsb = mh_dev_find_batch_o2_workspace(n_streams, sym_total, index ? chunk_symbols : 0);
-    const uint64_t cap = hits ? hit_cap : 0;
-    DevBuf d_pl, d_po, d_nb, d_so, d_idx, d_ho, d_hits, d_pat, d_st, d_ws;
-    HIP_TRY(d_pl.alloc(size_t(pay_total) + 64));
-    HIP_TRY(d_po.alloc((n_streams + 1) * 8));
-    HIP_TRY(d_nb.alloc(n_streams * 8));
-    HIP_TRY(d_so.alloc((n_streams + 1) * 8));
-    HIP_TRY(d_idx.alloc(nidx * 8));
-    HIP_TRY(d_ho.alloc((n_streams + 1) * 8));
-    HIP_TRY(d_hits.alloc(size_t(cap) * 24));
-    HIP_TRY(d_pat.alloc(size_t(cap) * 4));
-    HIP_TRY(d_st.alloc(n_streams * 4));
-    HIP_TRY(d_ws.alloc(wsb));
-    if (pay_total) HIP_TRY(stage_h2d(d_pl.p, payload, size_t(pay_total), st));
-    HIP_TRY(hipMemcpy(d_po.p, pay_off, (n_streams + 1) * 8, hipMemcpyHostToDevice));
-    if (n_streams) HIP_TRY(hipMemcpy(d_nb.p, nbits, n_streams * 8, hipMemcpyHostToDevice));
-    if (index) {
-        HIP_TRY(hipMemcpy(d_so.p, sym_off, (n_streams + 1) * 8, hipMemcpyHostToDevice));
-        if (nidx) HIP_TRY(hipMemcpy(d_idx.p, index, nidx * 8, hipMemcpyHostToDevice));
-    }
-    int rc = mh_dev_find_batch_o2(m, ps, d_pl.as<uint8_t>(), d_po.as<uint64_t>(), d_nb.as<uint64_t>(), n_streams, pay_total, prev0,
-                                  index ? d_so.as<uint64_t>() : nullptr, sym_total, index ? d_idx.as<uint64_t>() : nullptr, chunk_symbols,
-                                  d_ho.as<uint64_t>(), hits ? d_hits.as<uint64_t>() : nullptr, hit_pattern ? d_pat.as<uint32_t>() : nullptr, cap,
-                                  d_st.as<int32_t>(), d_ws.p, wsb, st);
-    if (rc != MH_OK) return rc;
-    int dev_rc = mh_dev_status(d_ws.p, st);
-    std::vector<int32_t> sst(n_streams);
-    if (n_streams) HIP_TRY(hipMemcpy(sst.data(), d_st.p, n_streams * 4, hipMemcpyDeviceToHost));
-    std::vector<uint64_t> dho(n_streams + 1);
-    HIP_TRY(hipMemcpy(dho.data(), d_ho.p, (n_streams + 1) * 8, hipMemcpyDeviceToHost));
-    const uint64_t dev_rec = std::min<uint64_t>(dho[n_streams], cap);
-    if (long_streams.empty()) {
-        std::copy(dho.begin(), dho.end(), hit_off);
-        if (dev_rec) {
-            HIP_TRY(hipMemcpy(hits, d_hits.p, size_t(dev_rec) * 24, hipMemcpyDeviceToHost));
-            if (hit_pattern) HIP_TRY(hipMemcpy(hit_pattern, d_pat.p, size_t(dev_rec) * 4, hipMemcpyDeviceToHost));
-        }
-    } else {
-        std::vector<uint64_t> dh(static_cast<size_t>(dev_rec) * 3);
-        std::vector<uint32_t> dp(static_cast<size_t>(dev_rec));
-        if (dev_rec) {
-            HIP_TRY(hipMemcpy(dh.data(), d_hits.p, dh.size() * 8, hipMemcpyDeviceToHost));
-            if (hit_pattern) HIP_TRY(hipMemcpy(dp.data(), d_pat.p, dp.size() * 4, hipMemcpyDeviceToHost));
-        }
-        uint64_t r = 0;
-        size_t k = 0;
-        std::vector<uint8_t> bytes;
-        std::vector<Hit> found;
-        for (size_t i = 0; i < n_streams; ++i) {
-            hit_off[i] = r;
-            if (k < long_streams.size() && long_streams[k] == i) {
-                ++k;
-                found.clear();
-                sst[i] = decode_alone(m, payload + pay_off[i], nbits[i], prev0, bytes);
-                if (sst[i] == MH_OK) host_find(ps, bytes.data(), bytes.size(), found);
-                for (const Hit &h : found) {
-                    if (r < cap) {
-                        hits[3 * r] = i; hits[3 * r + 1] = h.begin; hits[3 * r + 2] = h.end;
-                        if (hit_pattern) hit_pattern[r] = h.pattern;
-                    }
-                    ++r;
-                }
-                continue;
-            }
-            for (uint64_t q = dho[i]; q < dho[i + 1]; ++q, ++r) {
-                if (r >= cap) continue;                             // (q <= r: the device kept this record)
-                hits[3 * r] = dh[3 * q]; hits[3 * r + 1] = dh[3 * q + 1]; hits[3 * r + 2] = dh[3 * q + 2];
-                if (hit_pattern) hit_pattern[r] = dp[q];
-            }
-        }
-        hit_off[n_streams] = r;
-        dev_rc = hits && r > cap ? MH_ERR_CAPACITY : MH_OK;
-    }
-    int first = MH_OK;
-    for (size_t i = 0; i < n_streams && first == MH_OK; ++i) first = sst[i];
-    if (first == MH_OK && dev_rc != MH_OK && dev_rc != MH_ERR_ARG) first = dev_rc;      // MH_ERR_CAPACITY: the hits do not fit
-    if (stream_status) std::copy(sst.begin(), sst.end(), stream_status);
-    return first;
-}
 
 /* -------------------------------------------------------------------------------------------- coded histogram */
 
@@ -247,7 +78,7 @@ int mh_dev_histogram_coded_batch_o2(const mh_model *src, int order, const uint8_
 /* ---------------------------------------------------------------------------------------------------- re-code */
 
 size_t mh_dev_recode_batch_o2_workspace(size_t n_streams, uint64_t sym_total, uint32_t chunk_symbols) {
-    const uint64_t W = chunk_shift_of(chunk_symbols) >= 0 ? mhr::work_items(n_streams, sym_total, chunk_symbols) : 0;
+    const uint64_t W = chunk_shift_of(chunk_symbols) >= 0 ? mhb::work_items(n_streams, sym_total, chunk_symbols) : 0;
     return mhr::recode2_layout(n_streams, W).total;
 }
 
@@ -264,7 +95,7 @@ int mh_dev_recode_batch_o2(const mh_model *src, const mh_model *dst, const uint8
     if (!aligned16(d_out_payload)) return MH_ERR_ARG;
     int oshift = int(p.s.b.chunk_shift);
     if (!d_index && d_out_index && (oshift = chunk_shift_of(chunk_symbols)) < 0) return MH_ERR_ARG;
-    const uint64_t W = d_index ? mhr::work_items(n_streams, sym_total, chunk_symbols) : 0;
+    const uint64_t W = d_index ? mhb::work_items(n_streams, sym_total, chunk_symbols) : 0;
     const mhr::Recode2Layout L = mhr::recode2_layout(n_streams, W);
     if (ws_bytes < L.total) return MH_ERR_CAPACITY;
     p.s.b.stream_status = d_stream_status ? d_stream_status : reinterpret_cast<int *>(static_cast<unsigned char *>(d_ws) + L.off_status);

@@ -10,13 +10,6 @@ using namespace mhapi;
 
 namespace {
 
-bool offsets_ok(const uint64_t *off, size_t n) {
-    if (off[0] != 0) return false;
-    for (size_t i = 0; i < n; ++i)
-        if (off[i + 1] < off[i]) return false;
-    return true;
-}
-
 size_t al256(size_t x) { return (x + 255) & ~size_t(255); }
 
 // one device block for the whole set (mh_each.h, SetDev)

@@ -1,6 +1,6 @@
-// mh_api_find.cpp — the search calls of the C ABI (include/mh.h, "SEARCH IN BATCHES"): the pattern set (a host object: the
-// Shift-And automaton of mh_find.h), the device calls under one shared model or a model set (kernels: mh_find.hip) and the
-// host-buffer form.
+// mh_api_find.cpp — the search calls of the C ABI (include/mh.h, "SEARCH IN BATCHES" and the search part of "ORDER 2 IN
+// SEARCH AND RE-CODING"): the pattern set (a host object: the Shift-And automaton of mh_find.h), the device calls under one
+// shared model of order 0/1 or 2 or under a model set (kernels: mh_find.hip) and the host-buffer forms.
 #include "mh_api_internal.hpp"
 #include "mh_batch.h"
 #include "mh_find.h"
@@ -9,28 +9,19 @@ using namespace mhapi;
 
 namespace {
 
-bool order01(const mh_model *m) { return m && (m->type == 0 || m->type == 1); }
-
-bool offsets_ok(const uint64_t *off, size_t n) {
-    if (off[0] != 0) return false;
-    for (size_t i = 0; i < n; ++i)
-        if (off[i + 1] < off[i]) return false;
-    return true;
-}
-
-// the checks both device calls share, in the order of mh_dev_decode_batch, and the batch part of the parameters
+// the checks all device calls share, in the order of mh_dev_decode_batch, and the batch part of the parameters
 int prepare(const mh_pattern_set *ps, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits, size_t n_streams,
-            uint64_t pay_total, uint8_t prev0, const uint64_t *d_sym_off, uint64_t sym_total, const uint64_t *d_index, uint32_t chunk_symbols,
+            uint64_t pay_total, uint32_t ctx0, const uint64_t *d_sym_off, uint64_t sym_total, const uint64_t *d_index, uint32_t chunk_symbols,
             uint64_t *d_hit_off, uint64_t *d_hits, uint32_t *d_hit_pattern, uint64_t hit_cap, int32_t *d_stream_status, void *d_ws,
             size_t ws_bytes, mhf::FindParams &p) {
     if (!ps || (!d_payload && pay_total) || !d_pay_off || (!d_nbits && n_streams) || !d_hit_off || !d_ws) return MH_ERR_ARG;
     if (!aligned16(d_payload) || !aligned16(d_ws)) return MH_ERR_ARG;
     int shift = 0;
     if (d_index && ((shift = chunk_shift_of(chunk_symbols)) < 0 || !d_sym_off)) return MH_ERR_ARG;
-    const uint64_t W = d_index ? mhf::work_items(n_streams, sym_total, chunk_symbols) : 0;
+    const uint64_t W = d_index ? mhb::work_items(n_streams, sym_total, chunk_symbols) : 0;
     const mhf::FindLayout L = mhf::find_layout(n_streams, W);
     if (ws_bytes < L.total) return MH_ERR_CAPACITY;
-    p.b.payload = d_payload; p.b.pay_off = d_pay_off; p.b.nbits = d_nbits; p.b.n = n_streams; p.b.pay_total = pay_total; p.b.prev0 = prev0;
+    p.b.payload = d_payload; p.b.pay_off = d_pay_off; p.b.nbits = d_nbits; p.b.n = n_streams; p.b.pay_total = pay_total; p.b.prev0 = ctx0;
     p.b.sym_off = d_index ? reinterpret_cast<unsigned long long *>(const_cast<uint64_t *>(d_sym_off)) : nullptr;   // (read only)
     p.b.sym_total = d_index ? sym_total : 0;
     p.b.index = d_index; p.b.chunk_shift = uint32_t(shift);
@@ -44,11 +35,124 @@ int prepare(const mh_pattern_set *ps, const uint8_t *d_payload, const uint64_t *
     return MH_OK;
 }
 
-int run(const mhf::FindParams &p, const mh_pattern_set *ps, bool shared, void *d_ws, void *stream) {
+int run(const mhf::FindParams &p, const mh_pattern_set *ps, mhf::Model model, void *d_ws, void *stream) {
     mhf::Automaton a;
     std::memcpy(a.mask, ps->mask, sizeof a.mask);
-    HIP_TRY(mhf::launch_find(p, a, shared, d_ws, static_cast<hipStream_t>(stream)));
+    HIP_TRY(mhf::launch_find(p, a, model, d_ws, static_cast<hipStream_t>(stream)));
     return MH_OK;
+}
+
+// mh_dev_find_batch and mh_dev_find_batch_o2 behind their order checks: one shared model, its tables as the model's batch
+// decoder takes them
+int find_shared(const mh_model *m, mhf::Model model, const mh_pattern_set *ps, const uint8_t *d_payload, const uint64_t *d_pay_off,
+                const uint64_t *d_nbits, size_t n_streams, uint64_t pay_total, uint8_t prev0, const uint64_t *d_sym_off, uint64_t sym_total,
+                const uint64_t *d_index, uint32_t chunk_symbols, uint64_t *d_hit_off, uint64_t *d_hits, uint32_t *d_hit_pattern, uint64_t hit_cap,
+                int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
+    mhf::FindParams p{};
+    const int rc = prepare(ps, d_payload, d_pay_off, d_nbits, n_streams, pay_total, ctx_of_prev0(m, prev0), d_sym_off, sym_total, d_index,
+                           chunk_symbols, d_hit_off, d_hits, d_hit_pattern, hit_cap, d_stream_status, d_ws, ws_bytes, p);
+    if (rc != MH_OK) return rc;
+    if (m->max_len > mh::MAX_CODE_BITS) return MH_ERR_CODE_TOO_LONG;
+    if (!m->d_prim || !have_device()) return MH_ERR_NO_DEVICE;
+    fill_dec_tables(m, p.b);
+    return run(p, ps, model, d_ws, stream);
+}
+
+// the argument checks of the two host forms, in the order of mh_decode_batch
+int host_args(const mh_model *m, const mh_pattern_set *ps, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits, size_t n_streams,
+              const uint64_t *sym_off, const uint64_t *index, uint32_t chunk_symbols, const uint64_t *hit_off) {
+    if (!ps || !pay_off || (!nbits && n_streams) || !hit_off) return MH_ERR_ARG;
+    if (index && (chunk_shift_of(chunk_symbols) < 0 || !sym_off)) return MH_ERR_ARG;
+    if (!offsets_ok(pay_off, n_streams)) return MH_ERR_ARG;
+    if (!payload && pay_off[n_streams]) return MH_ERR_ARG;
+    for (size_t i = 0; i < n_streams; ++i)
+        if (nbits[i] > (pay_off[i + 1] - pay_off[i]) * 8) return MH_ERR_ARG;
+    if (index && !offsets_ok(sym_off, n_streams)) return MH_ERR_ARG;
+    if (!have_device()) return MH_ERR_NO_DEVICE;
+    if (m->max_len > mh::MAX_CODE_BITS) return MH_ERR_CODE_TOO_LONG;
+    return MH_OK;
+}
+
+// One host-form search on the device: search() uploads the batch, runs the device call of the model's order and brings back
+// the verdicts and hit_off; records() then brings the records the device kept to wherever the caller wants them.
+struct HostSearch {
+    DevBuf d_pl, d_po, d_nb, d_so, d_idx, d_ho, d_hits, d_pat, d_st, d_ws;
+    std::vector<int32_t> sst;           // per-stream verdicts
+    std::vector<uint64_t> hit_off;      // n + 1, as the device wrote them
+    uint64_t cap = 0, nrec = 0;         // records asked for, records kept
+    int dev_rc = MH_OK;
+
+    int search(const mh_model *m, const mh_pattern_set *ps, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits, size_t n_streams,
+               uint8_t prev0, const uint64_t *sym_off, const uint64_t *index, uint32_t chunk_symbols, bool want_hits, bool want_pattern,
+               uint64_t hit_cap) {
+        const hipStream_t st = nullptr;
+        const uint64_t pay_total = pay_off[n_streams];
+        const uint64_t sym_total = index ? sym_off[n_streams] : 0;
+        const size_t nidx = index ? size_t(mh_batch_index_capacity(sym_total, n_streams, chunk_symbols)) : 0;
+        const size_t wsb = mh_dev_find_batch_workspace(n_streams, sym_total, index ? chunk_symbols : 0);
+        cap = want_hits ? hit_cap : 0;
+        HIP_TRY(d_pl.alloc(size_t(pay_total) + 64));
+        HIP_TRY(d_po.alloc((n_streams + 1) * 8));
+        HIP_TRY(d_nb.alloc(n_streams * 8));
+        HIP_TRY(d_so.alloc((n_streams + 1) * 8));
+        HIP_TRY(d_idx.alloc(nidx * 8));
+        HIP_TRY(d_ho.alloc((n_streams + 1) * 8));
+        HIP_TRY(d_hits.alloc(size_t(cap) * 24));
+        HIP_TRY(d_pat.alloc(size_t(cap) * 4));
+        HIP_TRY(d_st.alloc(n_streams * 4));
+        HIP_TRY(d_ws.alloc(wsb));
+        if (pay_total) HIP_TRY(stage_h2d(d_pl.p, payload, size_t(pay_total), st));
+        HIP_TRY(hipMemcpy(d_po.p, pay_off, (n_streams + 1) * 8, hipMemcpyHostToDevice));
+        if (n_streams) HIP_TRY(hipMemcpy(d_nb.p, nbits, n_streams * 8, hipMemcpyHostToDevice));
+        if (index) {
+            HIP_TRY(hipMemcpy(d_so.p, sym_off, (n_streams + 1) * 8, hipMemcpyHostToDevice));
+            if (nidx) HIP_TRY(hipMemcpy(d_idx.p, index, nidx * 8, hipMemcpyHostToDevice));
+        }
+        const auto dev = order2(m) ? mh_dev_find_batch_o2 : mh_dev_find_batch;
+        const int rc = dev(m, ps, d_pl.as<uint8_t>(), d_po.as<uint64_t>(), d_nb.as<uint64_t>(), n_streams, pay_total, prev0,
+                           index ? d_so.as<uint64_t>() : nullptr, sym_total, index ? d_idx.as<uint64_t>() : nullptr, chunk_symbols,
+                           d_ho.as<uint64_t>(), want_hits ? d_hits.as<uint64_t>() : nullptr, want_pattern ? d_pat.as<uint32_t>() : nullptr, cap,
+                           d_st.as<int32_t>(), d_ws.p, wsb, st);
+        if (rc != MH_OK) return rc;
+        dev_rc = mh_dev_status(d_ws.p, st);
+        sst.resize(n_streams);
+        hit_off.resize(n_streams + 1);
+        if (n_streams) HIP_TRY(hipMemcpy(sst.data(), d_st.p, n_streams * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(hit_off.data(), d_ho.p, (n_streams + 1) * 8, hipMemcpyDeviceToHost));
+        nrec = std::min<uint64_t>(hit_off[n_streams], cap);
+        return MH_OK;
+    }
+
+    int records(uint64_t *hits, uint32_t *hit_pattern) {
+        if (!nrec) return MH_OK;
+        HIP_TRY(hipMemcpy(hits, d_hits.p, size_t(nrec) * 24, hipMemcpyDeviceToHost));
+        if (hit_pattern) HIP_TRY(hipMemcpy(hit_pattern, d_pat.p, size_t(nrec) * 4, hipMemcpyDeviceToHost));
+        return MH_OK;
+    }
+
+    // the call's result: the first failed stream's error, else the device's (MH_ERR_CAPACITY: the hits do not fit)
+    int finish(int32_t *stream_status) const {
+        int first = MH_OK;
+        for (size_t i = 0; i < sst.size() && first == MH_OK; ++i) first = sst[i];
+        if (first == MH_OK && dev_rc != MH_OK && dev_rc != MH_ERR_ARG) first = dev_rc;
+        if (stream_status) std::copy(sst.begin(), sst.end(), stream_status);
+        return first;
+    }
+};
+
+// the hits of one decoded message under the host-side automaton, in (end, pattern) order
+struct Hit { uint64_t begin, end; uint32_t pattern; };
+void host_find(const mh_pattern_set *ps, const uint8_t *data, size_t n, std::vector<Hit> &out) {
+    uint64_t D = 0;
+    for (size_t k = 0; k < n; ++k) {
+        D = ((D << 1) | ps->first) & ps->mask[data[k]];
+        for (uint64_t h = D & ps->last; h; h &= h - 1) {
+            const uint32_t b = uint32_t(__builtin_ctzll(h));
+            const uint32_t j = uint32_t(__builtin_popcountll(ps->last & ((1ull << b) - 1ull)));
+            const uint32_t lo = 63u - uint32_t(__builtin_clzll(ps->first & ((2ull << b) - 1ull)));
+            out.push_back(Hit{k + 1 - (b - lo + 1u), k + 1, j});
+        }
+    }
 }
 
 }  // namespace
@@ -89,7 +193,7 @@ int mh_pattern_set_max_len(const mh_pattern_set *ps) { return ps ? int(ps->max_l
 void mh_pattern_set_free(mh_pattern_set *ps) { delete ps; }
 
 size_t mh_dev_find_batch_workspace(size_t n_streams, uint64_t sym_total, uint32_t chunk_symbols) {
-    const uint64_t W = chunk_shift_of(chunk_symbols) >= 0 ? mhf::work_items(n_streams, sym_total, chunk_symbols) : 0;
+    const uint64_t W = chunk_shift_of(chunk_symbols) >= 0 ? mhb::work_items(n_streams, sym_total, chunk_symbols) : 0;
     return mhf::find_layout(n_streams, W).total;
 }
 
@@ -98,16 +202,21 @@ int mh_dev_find_batch(const mh_model *m, const mh_pattern_set *ps, const uint8_t
                       uint32_t chunk_symbols, uint64_t *d_hit_off, uint64_t *d_hits, uint32_t *d_hit_pattern, uint64_t hit_cap,
                       int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
     if (!order01(m)) return MH_ERR_ARG;
-    mhf::FindParams p{};
-    const int rc = prepare(ps, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index, chunk_symbols, d_hit_off,
-                           d_hits, d_hit_pattern, hit_cap, d_stream_status, d_ws, ws_bytes, p);
-    if (rc != MH_OK) return rc;
-    if (m->max_len > mh::MAX_CODE_BITS) return MH_ERR_CODE_TOO_LONG;
-    if (!m->d_prim || !have_device()) return MH_ERR_NO_DEVICE;
-    p.b.prim = m->d_prim; p.b.sec = m->d_sec; p.b.sec_base = m->d_sec_base; p.b.tree = m->d_tree;
-    p.b.P = uint32_t(m->dec_bits); p.b.nsec = m->nsec; p.b.sec_lds = m->dec_lds ? 1u : 0u;
-    p.b.direct = m->dec_direct ? 1u : 0u; p.b.H = uint32_t(m->dec_h);
-    return run(p, ps, true, d_ws, stream);
+    return find_shared(m, mhf::Model::Shared, ps, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index,
+                       chunk_symbols, d_hit_off, d_hits, d_hit_pattern, hit_cap, d_stream_status, d_ws, ws_bytes, stream);
+}
+
+size_t mh_dev_find_batch_o2_workspace(size_t n_streams, uint64_t sym_total, uint32_t chunk_symbols) {
+    return mh_dev_find_batch_workspace(n_streams, sym_total, chunk_symbols);
+}
+
+int mh_dev_find_batch_o2(const mh_model *m, const mh_pattern_set *ps, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits,
+                         size_t n_streams, uint64_t pay_total, uint8_t prev0, const uint64_t *d_sym_off, uint64_t sym_total,
+                         const uint64_t *d_index, uint32_t chunk_symbols, uint64_t *d_hit_off, uint64_t *d_hits, uint32_t *d_hit_pattern,
+                         uint64_t hit_cap, int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
+    if (!order2(m)) return MH_ERR_ARG;
+    return find_shared(m, mhf::Model::Shared2, ps, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index,
+                       chunk_symbols, d_hit_off, d_hits, d_hit_pattern, hit_cap, d_stream_status, d_ws, ws_bytes, stream);
 }
 
 int mh_dev_find_each(const mh_model_set *s, const mh_pattern_set *ps, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits,
@@ -121,22 +230,15 @@ int mh_dev_find_each(const mh_model_set *s, const mh_pattern_set *ps, const uint
     if (rc != MH_OK) return rc;
     if (!have_device()) return MH_ERR_NO_DEVICE;
     p.set = s->d;
-    return run(p, ps, false, d_ws, stream);
+    return run(p, ps, mhf::Model::Set, d_ws, stream);
 }
 
 int mh_find_batch(const mh_model *m, const mh_pattern_set *ps, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits,
                   size_t n_streams, uint8_t prev0, const uint64_t *sym_off, const uint64_t *index, uint32_t chunk_symbols, uint64_t *hit_off,
                   uint64_t *hits, uint32_t *hit_pattern, uint64_t hit_cap, int32_t *stream_status) {
-    if (!order01(m) || !ps || !pay_off || (!nbits && n_streams) || !hit_off) return MH_ERR_ARG;
-    if (index && (chunk_shift_of(chunk_symbols) < 0 || !sym_off)) return MH_ERR_ARG;
-    if (!offsets_ok(pay_off, n_streams)) return MH_ERR_ARG;
-    const uint64_t pay_total = pay_off[n_streams];
-    if (!payload && pay_total) return MH_ERR_ARG;
-    for (size_t i = 0; i < n_streams; ++i)
-        if (nbits[i] > (pay_off[i + 1] - pay_off[i]) * 8) return MH_ERR_ARG;
-    if (index && !offsets_ok(sym_off, n_streams)) return MH_ERR_ARG;
-    if (!have_device()) return MH_ERR_NO_DEVICE;
-    if (m->max_len > mh::MAX_CODE_BITS) return MH_ERR_CODE_TOO_LONG;
+    if (!order01(m)) return MH_ERR_ARG;
+    int rc = host_args(m, ps, payload, pay_off, nbits, n_streams, sym_off, index, chunk_symbols, hit_off);
+    if (rc != MH_OK) return rc;
     // index-free with a stream over the walk cap: index the batch first (mh_index_batch never refuses a valid stream), then
     // search it as an indexed batch; a stream the indexing fails keeps that error and has no symbols, so no hits
     std::vector<uint64_t> own_so, own_idx;
@@ -152,56 +254,76 @@ int mh_find_batch(const mh_model *m, const mh_pattern_set *ps, const uint8_t *pa
         own_so.assign(n_streams + 1, 0);
         own_idx.assign(size_t(mh_batch_index_capacity(bound, n_streams, chunk_symbols)), 0);
         idx_st.assign(n_streams, MH_OK);
-        const int rc = mh_index_batch(m, payload, pay_off, nbits, n_streams, prev0, chunk_symbols, own_so.data(), own_idx.data(), own_idx.size(),
-                                      idx_st.data());
+        rc = mh_index_batch(m, payload, pay_off, nbits, n_streams, prev0, chunk_symbols, own_so.data(), own_idx.data(), own_idx.size(),
+                            idx_st.data());
         if (rc == MH_ERR_HIP || rc == MH_ERR_NO_DEVICE || rc == MH_ERR_NOMEM || rc == MH_ERR_CAPACITY) return rc;
         sym_off = own_so.data();
         index = own_idx.data();
     }
-    const hipStream_t st = nullptr;
-    const uint64_t sym_total = index ? sym_off[n_streams] : 0;
-    const size_t nidx = index ? size_t(mh_batch_index_capacity(sym_total, n_streams, chunk_symbols)) : 0;
-    const size_t wsb = mh_dev_find_batch_workspace(n_streams, sym_total, index ? chunk_symbols : 0);
-    const uint64_t cap = hits ? hit_cap : 0;
-    DevBuf d_pl, d_po, d_nb, d_so, d_idx, d_ho, d_hits, d_pat, d_st, d_ws;
-    HIP_TRY(d_pl.alloc(size_t(pay_total) + 64));
-    HIP_TRY(d_po.alloc((n_streams + 1) * 8));
-    HIP_TRY(d_nb.alloc(n_streams * 8));
-    HIP_TRY(d_so.alloc((n_streams + 1) * 8));
-    HIP_TRY(d_idx.alloc(nidx * 8));
-    HIP_TRY(d_ho.alloc((n_streams + 1) * 8));
-    HIP_TRY(d_hits.alloc(size_t(cap) * 24));
-    HIP_TRY(d_pat.alloc(size_t(cap) * 4));
-    HIP_TRY(d_st.alloc(n_streams * 4));
-    HIP_TRY(d_ws.alloc(wsb));
-    if (pay_total) HIP_TRY(stage_h2d(d_pl.p, payload, size_t(pay_total), st));
-    HIP_TRY(hipMemcpy(d_po.p, pay_off, (n_streams + 1) * 8, hipMemcpyHostToDevice));
-    if (n_streams) HIP_TRY(hipMemcpy(d_nb.p, nbits, n_streams * 8, hipMemcpyHostToDevice));
-    if (index) {
-        HIP_TRY(hipMemcpy(d_so.p, sym_off, (n_streams + 1) * 8, hipMemcpyHostToDevice));
-        if (nidx) HIP_TRY(hipMemcpy(d_idx.p, index, nidx * 8, hipMemcpyHostToDevice));
-    }
-    int rc = mh_dev_find_batch(m, ps, d_pl.as<uint8_t>(), d_po.as<uint64_t>(), d_nb.as<uint64_t>(), n_streams, pay_total, prev0,
-                               index ? d_so.as<uint64_t>() : nullptr, sym_total, index ? d_idx.as<uint64_t>() : nullptr, chunk_symbols,
-                               d_ho.as<uint64_t>(), hits ? d_hits.as<uint64_t>() : nullptr, hit_pattern ? d_pat.as<uint32_t>() : nullptr, cap,
-                               d_st.as<int32_t>(), d_ws.p, wsb, st);
+    HostSearch hs;
+    rc = hs.search(m, ps, payload, pay_off, nbits, n_streams, prev0, sym_off, index, chunk_symbols, hits != nullptr, hit_pattern != nullptr, hit_cap);
     if (rc != MH_OK) return rc;
-    const int dev_rc = mh_dev_status(d_ws.p, st);
-    std::vector<int32_t> sst(n_streams);
-    if (n_streams) HIP_TRY(hipMemcpy(sst.data(), d_st.p, n_streams * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(hit_off, d_ho.p, (n_streams + 1) * 8, hipMemcpyDeviceToHost));
-    const uint64_t nrec = std::min<uint64_t>(hit_off[n_streams], cap);
-    if (nrec) {
-        HIP_TRY(hipMemcpy(hits, d_hits.p, size_t(nrec) * 24, hipMemcpyDeviceToHost));
-        if (hit_pattern) HIP_TRY(hipMemcpy(hit_pattern, d_pat.p, size_t(nrec) * 4, hipMemcpyDeviceToHost));
-    }
+    std::copy(hs.hit_off.begin(), hs.hit_off.end(), hit_off);
+    if ((rc = hs.records(hits, hit_pattern)) != MH_OK) return rc;
     for (size_t i = 0; i < idx_st.size(); ++i)
-        if (idx_st[i] != MH_OK) sst[i] = idx_st[i];
-    int first = MH_OK;
-    for (size_t i = 0; i < n_streams && first == MH_OK; ++i) first = sst[i];
-    if (first == MH_OK && dev_rc != MH_OK && dev_rc != MH_ERR_ARG) first = dev_rc;      // MH_ERR_CAPACITY: the hits do not fit
-    if (stream_status) std::copy(sst.begin(), sst.end(), stream_status);
-    return first;
+        if (idx_st[i] != MH_OK) hs.sst[i] = idx_st[i];
+    return hs.finish(stream_status);
+}
+
+int mh_find_batch_o2(const mh_model *m, const mh_pattern_set *ps, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits,
+                     size_t n_streams, uint8_t prev0, const uint64_t *sym_off, const uint64_t *index, uint32_t chunk_symbols, uint64_t *hit_off,
+                     uint64_t *hits, uint32_t *hit_pattern, uint64_t hit_cap, int32_t *stream_status) {
+    if (!order2(m)) return MH_ERR_ARG;
+    int rc = host_args(m, ps, payload, pay_off, nbits, n_streams, sym_off, index, chunk_symbols, hit_off);
+    if (rc != MH_OK) return rc;
+    // index-free streams over the walk cap: the device call refuses them; each is decoded alone and searched by the
+    // host-side automaton, its records spliced into place in stream order
+    std::vector<size_t> long_streams;
+    if (!index)
+        for (size_t i = 0; i < n_streams; ++i)
+            if (nbits[i] > MH_BATCH_WALK_MAX_BITS) long_streams.push_back(i);
+    HostSearch hs;
+    rc = hs.search(m, ps, payload, pay_off, nbits, n_streams, prev0, sym_off, index, chunk_symbols, hits != nullptr, hit_pattern != nullptr, hit_cap);
+    if (rc != MH_OK) return rc;
+    if (long_streams.empty()) {
+        std::copy(hs.hit_off.begin(), hs.hit_off.end(), hit_off);
+        if ((rc = hs.records(hits, hit_pattern)) != MH_OK) return rc;
+        return hs.finish(stream_status);
+    }
+    const uint64_t cap = hs.cap;
+    const std::vector<uint64_t> &dho = hs.hit_off;
+    std::vector<uint64_t> dh(static_cast<size_t>(hs.nrec) * 3);
+    std::vector<uint32_t> dp(static_cast<size_t>(hs.nrec));
+    if ((rc = hs.records(dh.data(), hit_pattern ? dp.data() : nullptr)) != MH_OK) return rc;
+    uint64_t r = 0;
+    size_t k = 0;
+    std::vector<uint8_t> bytes;
+    std::vector<Hit> found;
+    for (size_t i = 0; i < n_streams; ++i) {
+        hit_off[i] = r;
+        if (k < long_streams.size() && long_streams[k] == i) {
+            ++k;
+            found.clear();
+            hs.sst[i] = decode_alone(m, payload + pay_off[i], nbits[i], prev0, bytes);
+            if (hs.sst[i] == MH_OK) host_find(ps, bytes.data(), bytes.size(), found);
+            for (const Hit &h : found) {
+                if (r < cap) {
+                    hits[3 * r] = i; hits[3 * r + 1] = h.begin; hits[3 * r + 2] = h.end;
+                    if (hit_pattern) hit_pattern[r] = h.pattern;
+                }
+                ++r;
+            }
+            continue;
+        }
+        for (uint64_t q = dho[i]; q < dho[i + 1]; ++q, ++r) {
+            if (r >= cap) continue;                             // (q <= r: the device kept this record)
+            hits[3 * r] = dh[3 * q]; hits[3 * r + 1] = dh[3 * q + 1]; hits[3 * r + 2] = dh[3 * q + 2];
+            if (hit_pattern) hit_pattern[r] = dp[q];
+        }
+    }
+    hit_off[n_streams] = r;
+    hs.dev_rc = hits && r > cap ? MH_ERR_CAPACITY : MH_OK;
+    return hs.finish(stream_status);
 }
 
 }  // extern "C"

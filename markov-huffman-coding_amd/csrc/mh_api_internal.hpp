@@ -155,6 +155,29 @@ struct DevBuf {
     template <typename T> T *as() { return static_cast<T *>(p); }
 };
 
+// what the batch calls ask of a model's order
+inline bool order01(const mh_model *m) { return m && (m->type == 0 || m->type == 1); }
+inline bool order2(const mh_model *m) { return m && m->type == 2; }
+inline bool order012(const mh_model *m) { return m && m->type >= 0 && m->type <= 2; }
+
+// n + 1 offsets of a host-buffer batch call: [0] == 0, non-decreasing
+inline bool offsets_ok(const uint64_t *off, size_t n) {
+    if (off[0] != 0) return false;
+    for (size_t i = 0; i < n; ++i)
+        if (off[i + 1] < off[i]) return false;
+    return true;
+}
+
+// The model's decode tables as the batch kernels take them (T: mhb::DecBatchParams or a struct with its table fields).  An
+// order-2 model's tables are read in the general form from L2, as decode2_kernel reads them: sec_lds, direct and H stay
+// what they are in a zero-initialised T.
+template <typename T>
+inline void fill_dec_tables(const mh_model *m, T &t) {
+    t.prim = m->d_prim; t.sec = m->d_sec; t.sec_base = m->d_sec_base; t.tree = m->d_tree;
+    t.P = uint32_t(m->dec_bits); t.nsec = m->nsec;
+    if (m->type != 2) { t.sec_lds = m->dec_lds ? 1u : 0u; t.direct = m->dec_direct ? 1u : 0u; t.H = uint32_t(m->dec_h); }
+}
+
 // the context in front of a stream's first symbol as the kernels want it (order 2: two bytes)
 inline uint32_t ctx_of_prev0(const mh_model *m, uint8_t prev0) { return m && m->type == 2 ? (uint32_t(prev0) << 8 | prev0) : prev0; }
 
@@ -201,6 +224,8 @@ int encode_batch_host(const mh_model *m, const uint8_t *data, const uint64_t *in
 int decode_batch_host(const mh_model *m, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits, size_t n_streams, uint8_t prev0,
                       uint8_t *out, size_t out_cap, uint64_t *sym_off, const uint64_t *index, uint32_t chunk_symbols, int32_t *stream_status,
                       DevDecodeBatchFn dev);
+// mh_api_coded_o2.cpp: an index-free order-2 stream over the walk cap, decoded alone (out: its bytes, empty unless MH_OK)
+int decode_alone(const mh_model *m, const uint8_t *payload, uint64_t nbits, uint8_t prev0, std::vector<uint8_t> &out);
 // mh_api_each.cpp: MH_OK when mh_model_set_from_tables accepts the table file t[nb] (host only), else its error
 int check_table(const uint8_t *t, size_t nb);
 // mh_api_range.cpp / mh_api_batch_range.cpp: the host forms of the range and lookup calls (mh_decode_ranges,

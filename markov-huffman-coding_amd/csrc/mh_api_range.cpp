@@ -16,8 +16,6 @@ thread_local uint64_t t_range_upload = 0;   // payload bytes the calling thread'
 // bytes in between (a PCIe transfer of 1 MiB takes about as long as the fixed cost of a call).
 constexpr uint64_t RANGE_MERGE_GAP = uint64_t(1) << 20;
 
-bool order01(const mh_model *m) { return m && (m->type == 0 || m->type == 1); }
-bool order2(const mh_model *m) { return m && m->type == 2; }
 
 // a run of whole chunks [c0, c1] of one range, cut so that its payload bytes and its output fit a segment
 struct Piece {
@@ -59,9 +57,7 @@ int mh_dev_decode_ranges(const mh_model *m, const uint8_t *d_payload, uint64_t p
     p.ranges = d_ranges; p.n = n_ranges;
     p.out = d_out; p.out_at = d_out_at; p.out_cap = out_cap;
     p.range_status = d_range_status;
-    p.tab.prim = m->d_prim; p.tab.sec = m->d_sec; p.tab.sec_base = m->d_sec_base; p.tab.tree = m->d_tree;
-    p.tab.P = uint32_t(m->dec_bits); p.tab.nsec = m->nsec; p.tab.sec_lds = m->dec_lds ? 1u : 0u;
-    p.tab.direct = m->dec_direct ? 1u : 0u; p.tab.H = uint32_t(m->dec_h);
+    fill_dec_tables(m, p.tab);
     HIP_TRY(mhr::launch_decode_ranges(p, d_ws, static_cast<hipStream_t>(stream)));
     return MH_OK;
 }

@@ -9,18 +9,6 @@
 
 using namespace mhapi;
 
-namespace {
-
-bool order2(const mh_model *m) { return m && m->type == 2; }
-
-// the model's order-2 decode tables, read in the general form from L2 (as mh_dev_decode_batch_o2)
-void tables_o2(const mh_model *m, mhb::DecBatchParams &t) {
-    t.prim = m->d_prim; t.sec = m->d_sec; t.sec_base = m->d_sec_base; t.tree = m->d_tree;
-    t.P = uint32_t(m->dec_bits); t.nsec = m->nsec;
-}
-
-}  // namespace
-
 extern "C" {
 
 size_t mh_dev_decode_ranges_o2_workspace(size_t n_ranges) { return mhr::range_layout(n_ranges).total; }
@@ -50,7 +38,7 @@ int mh_dev_decode_ranges_o2(const mh_model *m, const uint8_t *d_payload, uint64_
     p.ranges = d_ranges; p.n = n_ranges;
     p.out = d_out; p.out_at = d_out_at; p.out_cap = out_cap;
     p.range_status = d_range_status;
-    tables_o2(m, p.tab);
+    fill_dec_tables(m, p.tab);
     HIP_TRY(mhr::launch_decode_ranges_o2(p, d_ws, static_cast<hipStream_t>(stream)));
     return MH_OK;
 }
@@ -76,7 +64,7 @@ int mh_dev_decode_batch_o2_ranges(const mh_model *m, const uint8_t *d_payload, c
     if (m->max_len > mh::MAX_CODE_BITS) return MH_ERR_CODE_TOO_LONG;
     if (!m->d_prim || !have_device()) return MH_ERR_NO_DEVICE;
     p.prev0 = ctx_of_prev0(m, prev0);
-    tables_o2(m, p.tab);
+    fill_dec_tables(m, p.tab);
     HIP_TRY(mhr::launch_batch_ranges_o2(p, d_ws, static_cast<hipStream_t>(stream)));
     return MH_OK;
 }

@@ -9,15 +9,6 @@ using namespace mhapi;
 
 namespace {
 
-bool order01(const mh_model *m) { return m && (m->type == 0 || m->type == 1); }
-
-bool offsets_ok(const uint64_t *off, size_t n) {
-    if (off[0] != 0) return false;
-    for (size_t i = 0; i < n; ++i)
-        if (off[i + 1] < off[i]) return false;
-    return true;
-}
-
 // the source batch, checked in the order of mh_dev_decode_batch; sym_off is written by an index-free re-code
 int source(const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits, size_t n_streams, uint64_t pay_total, uint8_t prev0,
            const uint64_t *d_sym_off, uint64_t sym_total, const uint64_t *d_index, uint32_t chunk_symbols, const void *d_ws, mhr::Src &s) {
@@ -36,9 +27,7 @@ int source(const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *
 int shared_tables(const mh_model *m, mhr::Src &s) {
     if (m->max_len > mh::MAX_CODE_BITS) return MH_ERR_CODE_TOO_LONG;
     if (!m->d_prim || !have_device()) return MH_ERR_NO_DEVICE;
-    s.b.prim = m->d_prim; s.b.sec = m->d_sec; s.b.sec_base = m->d_sec_base; s.b.tree = m->d_tree;
-    s.b.P = uint32_t(m->dec_bits); s.b.nsec = m->nsec; s.b.sec_lds = m->dec_lds ? 1u : 0u;
-    s.b.direct = m->dec_direct ? 1u : 0u; s.b.H = uint32_t(m->dec_h);
+    fill_dec_tables(m, s.b);
     return MH_OK;
 }
 
@@ -80,7 +69,7 @@ int recode(const mh_model *m, const mh_model_set *set, const mh_model *dst, cons
     if (!aligned16(d_out_payload)) return MH_ERR_ARG;
     int oshift = int(p.s.b.chunk_shift);
     if (!d_index && d_out_index && (oshift = chunk_shift_of(chunk_symbols)) < 0) return MH_ERR_ARG;
-    const uint64_t W = d_index ? mhr::work_items(n_streams, sym_total, chunk_symbols) : 0;
+    const uint64_t W = d_index ? mhb::work_items(n_streams, sym_total, chunk_symbols) : 0;
     const mhr::RecodeLayout L = mhr::recode_layout(n_streams, W);
     if (ws_bytes < L.total) return MH_ERR_CAPACITY;
     p.s.b.stream_status = d_stream_status ? d_stream_status : reinterpret_cast<int *>(static_cast<unsigned char *>(d_ws) + L.off_status);
@@ -134,7 +123,7 @@ int mh_dev_histogram_coded_each(const mh_model_set *src, int order, const uint8_
 }
 
 size_t mh_dev_recode_batch_workspace(size_t n_streams, uint64_t sym_total, uint32_t chunk_symbols) {
-    const uint64_t W = chunk_shift_of(chunk_symbols) >= 0 ? mhr::work_items(n_streams, sym_total, chunk_symbols) : 0;
+    const uint64_t W = chunk_shift_of(chunk_symbols) >= 0 ? mhb::work_items(n_streams, sym_total, chunk_symbols) : 0;
     return mhr::recode_layout(n_streams, W).total;
 }
 

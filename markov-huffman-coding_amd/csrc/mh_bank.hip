@@ -31,6 +31,8 @@ using mhb::byte_of;
 using mhb::fail;
 using mhb::find_stream;
 using mhb::grid_for;
+using mhb::grid_threads;
+using mhb::gtid;
 using mhb::load16;
 using mhb::scan_exclusive;
 using mhb::stopped;
@@ -42,8 +44,6 @@ constexpr uint32_t WAVES = B_THREADS / 64;
 // the same way by every kernel, so that no index leaves its array)
 __device__ __forceinline__ uint32_t group_of(const uint32_t *group, uint64_t i, uint32_t K) { const uint32_t g = group[i]; return g < K ? g : K - 1u; }
 
-__device__ __forceinline__ uint64_t gtid() { return uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; }
-inline dim3 grid_threads(uint64_t items, uint32_t per_block) { return dim3(uint32_t((items + per_block - 1) / per_block)); }
 
 __global__ void bank_check_kernel(const uint64_t *off, uint64_t n, uint64_t total, int *status, int *stop) {
     const uint64_t i = gtid();

@@ -24,6 +24,10 @@ constexpr uint32_t SCAN_BLOCK = 1024;           // elements per workgroup of the
 
 inline uint64_t units_of(uint64_t total, uint64_t n_streams) { return total / B_SUB + n_streams + 1; }
 inline uint64_t scan_blocks(uint64_t len) { return (len + SCAN_BLOCK - 1) / SCAN_BLOCK; }
+// chunk numbers of an indexed batch: stream i's chunks from sym_off_i / chunk_symbols + i (0 chunk_symbols: index-free, none)
+inline uint64_t work_items(uint64_t n_streams, uint64_t sym_total, uint32_t chunk_symbols) {
+    return chunk_symbols ? sym_total / chunk_symbols + n_streams + 1 : 0;
+}
 
 // encode workspace: status block | unit bits (u64, scanned in place) | scan block sums | tail word
 struct EncLayout {
@@ -91,6 +95,13 @@ struct DecBatchParams {
     const uint32_t *tree;
     uint32_t P, nsec, sec_lds, direct, H;
 };
+
+// LDS bytes of a shared model's decode tables as mhb::load_tables (mh_batch_dev.hpp) lays them out: the two are a pair, and
+// this is the only copy of the size.  T: any struct with P, nsec and sec_lds (DecBatchParams, the single-stream DecodeParams).
+template <typename T>
+inline size_t tables_lds(const T &t) {
+    return 1024 + (size_t(256) << t.P) * 2 + (t.sec_lds ? ((size_t(t.nsec) * 2 + 15) & ~size_t(15)) : 0);
+}
 
 // histogram fix-up: validates the offsets, then moves each stream's first pair from the concatenation's context to prev0
 hipError_t launch_hist_fixup(const uint8_t *d_data, const uint64_t *d_in_off, uint64_t n, uint64_t total, uint32_t prev0,

@@ -191,21 +191,10 @@ __global__ void batch_enc_tail_kernel(EncBatchParams p, const uint32_t *tail, co
 
 // ------------------------------------------------------------------------------------------------ decode
 
-__device__ __forceinline__ void stream_fail(const DecBatchParams &p, int *status, uint64_t i, int mh_code, int dev_code) {
-    p.stream_status[i] = mh_code;
-    fail(status, dev_code);
-}
-
 __global__ void batch_dec_check_kernel(DecBatchParams p, int *status, int *stop) {
     const uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
     if (i > p.n) return;
-    bool bad = (i == 0 && p.pay_off[0] != 0) || (i == p.n && p.pay_off[p.n] != p.pay_total) || (i < p.n && p.pay_off[i + 1] < p.pay_off[i]);
-    if (p.index)
-        bad |= (i == 0 && p.sym_off[0] != 0) || (i == p.n && p.sym_off[p.n] != p.sym_total) || (i < p.n && p.sym_off[i + 1] < p.sym_off[i]);
-    if (bad) { fail(status, BATCH_STATUS_ARG); atomicExch(stop, 1); }
-    if (i == p.n) return;
-    p.stream_status[i] = MH_OK;
-    if (!bad && p.nbits[i] > (p.pay_off[i + 1] - p.pay_off[i]) * 8u) stream_fail(p, status, i, MH_ERR_ARG, BATCH_STATUS_ARG);
+    check_batch(p, i, status, stop);
 }
 
 __global__ __launch_bounds__(B_THREADS) void batch_dec_idx_kernel(DecBatchParams p, uint64_t nwork, int *status, const int *stop) {
@@ -327,7 +316,7 @@ hipError_t launch_decode_batch(const DecBatchParams &p, void *d_ws, hipStream_t 
     if (attr == hipSuccess) attr = mhk::allow_lds(reinterpret_cast<const void *>(batch_dec_walk_kernel<false>), lds_max);
     if (attr == hipSuccess) attr = mhk::allow_lds(reinterpret_cast<const void *>(batch_dec_walk_kernel<true>), lds_max);
     if (attr != hipSuccess) return attr;
-    const size_t lds = 1024 + (size_t(256) << p.P) * 2 + (p.sec_lds ? ((size_t(p.nsec) * 2 + 15) & ~size_t(15)) : 0);
+    const size_t lds = tables_lds(p);
     if (lds > 163840) return hipErrorInvalidValue;
     unsigned char *ws = static_cast<unsigned char *>(d_ws);
     const DecLayout L = dec_layout(p.n);

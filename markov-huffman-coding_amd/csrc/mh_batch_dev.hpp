@@ -1,8 +1,16 @@
-// mh_batch_dev.hpp — device code shared by the kernels of the two batch families: one shared model (mh_batch.hip) and one
-// model per stream (mh_each.hip), and by the byte-range decoders (mh_range.hip, mh_batch_range.hip).  Closed-form unit and chunk numbering,
-// unaligned 16-byte loads, the segmented u64 scans, the bit writer with shared edge words and the tail word, the byte-exact
-// output of a decoding lane and the LDS loader of a shared model's decode tables.  Everything is in an unnamed namespace:
-// each kernel file gets its own copy.
+// mh_batch_dev.hpp — device code shared by the kernels of the batch call family: the decoders (mh_batch.hip, mh_each.hip,
+// mh_batch_o2.hip), the byte-range decoders (mh_range.hip, mh_batch_range.hip), the state builder (mh_batch_states.hip), the
+// search (mh_find.hip) and the re-coders (mh_recode.hip, mh_recode_o2.hip).  What lives here, once:
+//   gtid, grid_threads, grid_for     thread numbering and grid sizes
+//   fail, stopped, stream_fail       the status word, the stop flag, a stream's verdict
+//   find_stream                      closed-form unit and chunk numbering
+//   offsets_bad, check_batch         the up-front checks of a batch to decode: every call of the family gives the same verdicts
+//   Chunk, chunk_of<O2>              chunk w of an indexed batch in either entry format
+//   load16, byte_of                  unaligned 16-byte loads
+//   scan_exclusive                   the segmented u64 scans
+//   BitWriter, ByteOut, stream_src   bits out with shared edge words and the tail word, bytes out, a payload as a bit source
+//   load_tables                      a shared model's decode tables into LDS (their size: mhb::tables_lds, mh_batch.h)
+// Everything is in an unnamed namespace: each kernel file gets its own copy.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -11,6 +19,7 @@
 #include "mh_batch.h"
 #include "mh_decode_dev.hpp"
 #include "mh_dev.hpp"
+#include "../../include/mh.h"
 
 namespace mhb {
 namespace {
@@ -23,6 +32,35 @@ static_assert((1u << SUB_SHIFT) == B_SUB && B_SUB == 64 * B_VEC, "a sub-step is 
 
 __device__ __forceinline__ void fail(int *status, int code) { atomicCAS(status, 0, code); }
 __device__ __forceinline__ bool stopped(const int *stop) { return *reinterpret_cast<const volatile int *>(stop) != 0; }
+__device__ __forceinline__ uint64_t gtid() { return uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; }
+inline dim3 grid_threads(uint64_t items, uint32_t per_block) { return dim3(uint32_t((items + per_block - 1) / per_block)); }
+
+// stream i's verdict (P: DecBatchParams or DecEachParams)
+template <typename P>
+__device__ __forceinline__ void stream_fail(const P &p, int *status, uint64_t i, int mh_code, int dev_code) {
+    p.stream_status[i] = mh_code;
+    fail(status, dev_code);
+}
+
+// thread i <= n of an offset check: [0] == 0, [n] == total, non-decreasing
+template <typename T>
+__device__ __forceinline__ bool offsets_bad(const T *off, uint64_t n, uint64_t total, uint64_t i) {
+    return (i == 0 && off[0] != 0) || (i == n && off[n] != total) || (i < n && off[i + 1] < off[i]);
+}
+
+// The up-front checks of a batch to decode, thread i <= n: pay_off[0] != 0, pay_off[n] != pay_total or a decreasing pair, the
+// same of sym_off with an index -> BATCH_STATUS_ARG and the call stops (returns true); else stream_status[i] = MH_OK, or
+// MH_ERR_ARG when nbits_i does not fit the stream's payload.  P: DecBatchParams or DecEachParams.
+template <typename P>
+__device__ __forceinline__ bool check_batch(const P &p, uint64_t i, int *status, int *stop) {
+    bool bad = offsets_bad(p.pay_off, p.n, p.pay_total, i);
+    if (p.index) bad |= offsets_bad(p.sym_off, p.n, p.sym_total, i);
+    if (bad) { fail(status, BATCH_STATUS_ARG); atomicExch(stop, 1); }
+    if (i == p.n) return bad;
+    p.stream_status[i] = MH_OK;
+    if (!bad && p.nbits[i] > (p.pay_off[i + 1] - p.pay_off[i]) * 8u) stream_fail(p, status, i, MH_ERR_ARG, BATCH_STATUS_ARG);
+    return bad;
+}
 
 // The stream that owns unit / chunk number u: the largest i <= n with (off[i] >> shift) + i <= u (the closed-form bases are
 // strictly increasing).  i == n: u lies behind the last stream.
@@ -34,6 +72,35 @@ __device__ __forceinline__ uint64_t find_stream(const T *off, uint64_t n, uint32
         if ((off[mid] >> shift) + mid <= u) lo = mid; else hi = mid - 1;
     }
     return lo;
+}
+
+// chunk w of an indexed batch: its stream, symbols, bit span and the raw context field of its entry
+struct Chunk {
+    uint64_t i, ni, first, nb, start, end;
+    uint32_t nsym, ctx;
+    bool last;
+    __device__ __forceinline__ bool entry_ok() const { return start <= end && end <= nb; }
+};
+// O2: entries of an order-2 index (position in IDX2_POS, two context bytes from bit 48), else of an order-0/1 index
+// (MH_INDEX_BIT_MASK, one byte from bit 56).  false when w is a gap.
+template <bool O2>
+__device__ __forceinline__ bool chunk_of(const DecBatchParams &b, uint64_t w, Chunk &c) {
+    constexpr uint64_t pos = O2 ? mhk::IDX2_POS : MH_INDEX_BIT_MASK;
+    const uint32_t cs = b.chunk_shift;
+    c.i = find_stream(b.sym_off, b.n, cs, w);
+    if (c.i >= b.n) return false;
+    const uint64_t a = b.sym_off[c.i];
+    c.ni = b.sym_off[c.i + 1] - a;
+    c.first = (w - ((a >> cs) + c.i)) << cs;
+    if (c.first >= c.ni) return false;
+    c.nb = b.nbits[c.i];
+    const uint64_t e = b.index[w];
+    c.start = e & pos;
+    c.ctx = uint32_t(e >> (O2 ? 48 : 56));
+    c.last = c.first + (uint64_t(1) << cs) >= c.ni;
+    c.end = c.last ? c.nb : (b.index[w + 1] & pos);
+    c.nsym = uint32_t(c.last ? c.ni - c.first : (uint64_t(1) << cs));
+    return true;
 }
 
 // cnt (1..16) bytes at an arbitrary address, zero beyond cnt; only the dwords that hold bytes of the range are read (a stream
@@ -200,7 +267,8 @@ struct ByteOut {
     }
 };
 
-// LDS: sec_base u32[256] | prim u16[256 << P] | sec u16[nsec] when the model's tables fit (the chunk decoder's layout)
+// LDS: sec_base u32[256] | prim u16[256 << P] | sec u16[nsec] when the model's tables fit (the chunk decoder's layout).
+// mhb::tables_lds (mh_batch.h) is the size of exactly this layout: the two are a pair, change them together.
 __device__ __forceinline__ DecTables load_tables(const DecBatchParams &p, unsigned char *smem, const uint16_t *&lut, const uint32_t *&sub_base) {
     uint32_t *sb = reinterpret_cast<uint32_t *>(smem);
     uint16_t *lp = reinterpret_cast<uint16_t *>(smem + 1024);

@@ -54,11 +54,6 @@ constexpr uint32_t HOT_ESCAPE = 0xD000u;          // image entries at or above: 
 
 // ------------------------------------------------------------------------------------------------ checks, histogram fix-up
 
-template <typename T>
-__device__ __forceinline__ bool offsets_bad(const T *off, uint64_t n, uint64_t total, uint64_t i) {
-    return (i == 0 && off[0] != 0) || (i == n && off[n] != total) || (i < n && off[i + 1] < off[i]);
-}
-
 __global__ void batch2_check_kernel(const uint64_t *off, uint64_t n, uint64_t total, int *status, int *stop) {
     const uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
     if (i > n) return;
@@ -254,20 +249,10 @@ __global__ void batch2_enc_tail_kernel(EncBatchO2Params p, const uint32_t *tail,
 
 constexpr int D2_THREADS = 256;                     // no tables in LDS: small workgroups, many waves per CU for the L2 gathers
 
-__device__ __forceinline__ void stream_fail(const DecBatchParams &p, int *status, uint64_t i, int mh_code, int dev_code) {
-    p.stream_status[i] = mh_code;
-    fail(status, dev_code);
-}
-
 __global__ void batch2_dec_check_kernel(DecBatchParams p, int *status, int *stop) {
     const uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
     if (i > p.n) return;
-    bool bad = offsets_bad(p.pay_off, p.n, p.pay_total, i);
-    if (p.index) bad |= offsets_bad(p.sym_off, p.n, p.sym_total, i);
-    if (bad) { fail(status, BATCH_STATUS_ARG); atomicExch(stop, 1); }
-    if (i == p.n) return;
-    p.stream_status[i] = MH_OK;
-    if (!bad && p.nbits[i] > (p.pay_off[i + 1] - p.pay_off[i]) * 8u) stream_fail(p, status, i, MH_ERR_ARG, BATCH_STATUS_ARG);
+    check_batch(p, i, status, stop);
 }
 
 // the model's order-2 tables as decode2_kernel reads them: general form, every level gathered

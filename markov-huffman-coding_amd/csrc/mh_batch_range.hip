@@ -183,8 +183,7 @@ hipError_t launch_batch_ranges(const BatchRangeParams &p, bool shared, void *d_w
         hipError_t attr = mhk::allow_lds(reinterpret_cast<const void *>(batch_range_decode_kernel<SharedTables, true>), lds_max);
         if (attr == hipSuccess) attr = mhk::allow_lds(reinterpret_cast<const void *>(batch_range_decode_kernel<SharedTables, false>), lds_max);
         if (attr != hipSuccess) return attr;
-        const mhb::DecBatchParams &t = p.tab;
-        lds = 1024 + (size_t(256) << t.P) * 2 + (t.sec_lds ? ((size_t(t.nsec) * 2 + 15) & ~size_t(15)) : 0);
+        lds = mhb::tables_lds(p.tab);
         if (lds > size_t(lds_max)) return hipErrorInvalidValue;
     }
     unsigned char *ws = static_cast<unsigned char *>(d_ws);

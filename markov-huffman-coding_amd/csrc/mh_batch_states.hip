@@ -33,6 +33,7 @@ namespace mhs {
 
 using mhb::fail;
 using mhb::find_stream;
+using mhb::gtid;
 using mhb::stopped;
 using mhk::BitCursor;
 using mhk::BitSrc;
@@ -69,7 +70,6 @@ struct SetD {
     }
 };
 
-__device__ __forceinline__ uint64_t gtid() { return uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; }
 __device__ __forceinline__ uint64_t gstride() { return uint64_t(gridDim.x) * blockDim.x; }
 __device__ __forceinline__ uint64_t nseg_of(uint64_t nb) { return nb ? (nb + SEG_BITS - 1) / SEG_BITS : 1; }
 __device__ __forceinline__ uint64_t seg_base(const StParams &p, uint64_t i) { return (p.pay_off[i] >> SEG_SHIFT) + i; }
@@ -126,8 +126,7 @@ __device__ __forceinline__ BitSrc src_of(const StParams &p, const Seg &s, uint64
 __global__ void bseg_check_kernel(StParams p, int *hdr, int *status, unsigned long long *first, unsigned long long *last) {
     const uint64_t i = gtid();
     if (i > p.n) return;
-    const bool bad = (i == 0 && p.pay_off[0] != 0) || (i == p.n && p.pay_off[p.n] != p.pay_total) ||
-                     (i < p.n && p.pay_off[i + 1] < p.pay_off[i]);
+    const bool bad = mhb::offsets_bad(p.pay_off, p.n, p.pay_total, i);
     if (bad) { fail(hdr + HDR_STATUS, mhb::BATCH_STATUS_ARG); atomicExch(hdr + HDR_STOP, 1); }
     if (i == 0) hdr[HDR_CHANGED] = 1;                   // the speculation wrote every record: pass 1 runs
     if (i == p.n) return;

@@ -35,20 +35,22 @@ constexpr uint16_t NONE = 0xFFFF;                // (mh_tree.hip: a node without
 namespace {
 
 using mhb::byte_of;
+using mhb::check_batch;
 using mhb::fail;
 using mhb::find_stream;
 using mhb::grid_for;
+using mhb::grid_threads;
+using mhb::gtid;
 using mhb::load16;
 using mhb::scan_exclusive;
 using mhb::stopped;
+using mhb::stream_fail;
 using mhb::SUB_SHIFT;
 
 constexpr uint32_t WAVES = B_THREADS / 64;
 constexpr uint64_t TREE_SLICE = 1u << 22;          // slots per tree_build_kernel launch: 2^22 x TB_NODE_STRIDE < 2^32
 static_assert((TREE_SLICE - 1) * mhk::TB_NODE_STRIDE + mhk::TB_NODE_STRIDE <= (1ull << 32), "tree_build_kernel's 32-bit node offsets");
 
-__device__ __forceinline__ uint64_t gtid() { return uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; }
-inline dim3 grid_threads(uint64_t items, uint32_t per_block) { return dim3(uint32_t((items + per_block - 1) / per_block)); }
 
 __global__ void each_check_kernel(const uint64_t *off, uint64_t n, uint64_t total, int *status, int *stop) {
     const uint64_t i = gtid();
@@ -415,21 +417,10 @@ __global__ __launch_bounds__(B_THREADS) void each_enc_emit_kernel(EncEachParams 
 
 // ------------------------------------------------------------------------------------------------ decode
 
-__device__ __forceinline__ void stream_fail(const DecEachParams &p, int *status, uint64_t i, int mh_code, int dev_code) {
-    p.stream_status[i] = mh_code;
-    fail(status, dev_code);
-}
-
 __global__ void each_dec_check_kernel(DecEachParams p, int *status, int *stop) {
     const uint64_t i = gtid();
     if (i > p.n) return;
-    bool bad = (i == 0 && p.pay_off[0] != 0) || (i == p.n && p.pay_off[p.n] != p.pay_total) || (i < p.n && p.pay_off[i + 1] < p.pay_off[i]);
-    if (p.index)
-        bad |= (i == 0 && p.sym_off[0] != 0) || (i == p.n && p.sym_off[p.n] != p.sym_total) || (i < p.n && p.sym_off[i + 1] < p.sym_off[i]);
-    if (bad) { fail(status, BATCH_STATUS_ARG); atomicExch(stop, 1); }
-    if (i == p.n) return;
-    p.stream_status[i] = MH_OK;
-    if (!bad && p.nbits[i] > (p.pay_off[i + 1] - p.pay_off[i]) * 8u) stream_fail(p, status, i, MH_ERR_ARG, BATCH_STATUS_ARG);
+    check_batch(p, i, status, stop);
 }
 
 __global__ __launch_bounds__(256) void each_dec_idx_kernel(DecEachParams p, uint64_t nwork, int *status, const int *stop) {

@@ -33,9 +33,6 @@ struct Automaton {
 struct FindLayout {
     size_t off_mask, off_status, off_state, off_own, off_tail, off_cnt, off_sums, total;
 };
-inline uint64_t work_items(uint64_t n_streams, uint64_t sym_total, uint32_t chunk_symbols) {
-    return chunk_symbols ? sym_total / chunk_symbols + n_streams + 1 : 0;
-}
 inline FindLayout find_layout(uint64_t n_streams, uint64_t nwork) {
     FindLayout l;
     const uint64_t len = (nwork > n_streams ? nwork : n_streams) + 1;
@@ -61,7 +58,11 @@ struct FindParams {
     uint64_t hit_cap;
 };
 
-// shared: one model (b's tables, LDS); else stream i under set model i
-hipError_t launch_find(const FindParams &p, const Automaton &a, bool shared, void *d_ws, hipStream_t st);
+// The model the batch was coded under.  Shared: one order-0/1 model (b's tables go to LDS, b.prev0 is a byte, index entries
+// carry one context byte).  Set: stream i under set model i.  Shared2: one order-2 model, described as for
+// launch_decode_batch_o2 (mh_batch_o2.h): b's tables are the order-2 tables (general form, L2), b.prev0 is the 16-bit start
+// context, index entries carry the context in bits 48..63.
+enum class Model { Shared, Set, Shared2 };
+hipError_t launch_find(const FindParams &p, const Automaton &a, Model model, void *d_ws, hipStream_t st);
 
 }  // namespace mhf

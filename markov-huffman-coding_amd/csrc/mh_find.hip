@@ -2,7 +2,7 @@
 // BATCHES").  The batch decoders hold every decoded byte in a register for one step; here that byte feeds a Shift-And
 // automaton (mh_find.h) instead of a store: D = ((D << 1) | first) & mask[c], hits = D & last.  The update hangs off the
 // decoder's dependent chain (context -> table -> next context), it is not part of it.
-//   find_check_kernel        the batch checks of batch_dec_check_kernel; hit_off zeroed; the masks into the workspace
+//   find_check_kernel        the batch checks (mhb::check_batch); hit_off zeroed; the masks into the workspace
 //   find_idx_count_kernel    one lane per (stream, chunk), D from 0: the hits that end in the chunk, the chunk's end state, and
 //                            a tail into the next chunk with no new starts (the hits that begin here and end there)
 //   find_comb_kernel         hits that end in chunk k = own(k) + tail(k - 1); 0 for a failed stream (every chunk is judged by now)
@@ -14,8 +14,9 @@
 //   find_cap_kernel          index-free: hits beyond hit_cap -> MHK_STATUS_CAPACITY
 // A chunk that is not its stream's last has chunk_symbols >= 256 > 63 symbols, so a state started at 0 is the true state at
 // its end, and a hit spans at most two chunks.  Verdicts are the batch decoders': same checks, same statuses.  Every loop is
-// bounded by a symbol count or nbits_i.  Shared model: tables in LDS as load_tables lays them out, the 2 KiB of masks behind
-// them when they leave room (MLDS), else read from the workspace.  Model set: tables in L2, masks in LDS.
+// bounded by a symbol count or nbits_i.  One kernel family serves three models (Dec<K>): a shared order-0/1 model (tables in
+// LDS as load_tables lays them out, the 2 KiB of masks behind them when they leave room (MLDS), else read from the workspace),
+// a model set and a shared order-2 model (tables in L2, masks in LDS at offset 0).
 #include "mh_find.h"
 #include "mh_batch_dev.hpp"
 #include "mh_each_dev.hpp"
@@ -30,37 +31,62 @@ using mhk::DecTables;
 
 namespace {
 
+using mhb::check_batch;
+using mhb::Chunk;
+using mhb::chunk_of;
 using mhb::fail;
 using mhb::find_stream;
 using mhb::grid_for;
+using mhb::grid_threads;
+using mhb::gtid;
 using mhb::scan_exclusive;
 using mhb::stopped;
+using mhb::stream_fail;
 
-constexpr int NT_SHARED = mhb::B_THREADS;          // batch_dec_idx_kernel's shape: one workgroup per CU beside the tables
-constexpr int NT_EACH = 256;                       // each_dec_idx_kernel's
-
-__device__ __forceinline__ uint64_t gtid() { return uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; }
-inline dim3 grid_threads(uint64_t items, uint32_t per_block) { return dim3(uint32_t((items + per_block - 1) / per_block)); }
-
-// the symbol decoder of a lane: the shared model's two-level tables, or stream i's slots
-template <bool SHARED> struct Dec;
-template <> struct Dec<true> {
+// The symbol decoder of a lane, one policy per model.  next() decodes one symbol in the lane's context ctx and rolls ctx on:
+// the kernels feed the symbol to the matcher and never touch the context.  A stream starts in b.prev0 (order 2: both bytes).
+//   NT, PER_CU   the workgroup shape: that of the model's batch decoder
+//   O2           the format of the batch's index entries (mhb::chunk_of)
+template <Model K> struct Dec;
+// the shared model's two-level tables in LDS; one workgroup per CU beside them (batch_dec_idx_kernel's shape)
+template <> struct Dec<Model::Shared> {
+    static constexpr int NT = mhb::B_THREADS, PER_CU = 1;
+    static constexpr bool O2 = false;
     const uint16_t *lut;
     const uint32_t *sub_base;
     DecTables tabs;
     __device__ __forceinline__ Dec(const FindParams &p, unsigned char *smem) : tabs(mhb::load_tables(p.b, smem, lut, sub_base)) {}
     __device__ __forceinline__ void stream(const FindParams &, uint64_t) {}
-    __device__ __forceinline__ uint32_t next(const FindParams &, const BitSrc &src, BitCursor &bc, uint32_t prev, uint32_t &used, bool &bad) const {
-        return mhk::decode_one(lut, sub_base, tabs, src, bc, prev, used, bad);
+    __device__ __forceinline__ uint32_t next(const FindParams &, const BitSrc &src, BitCursor &bc, uint32_t &ctx, uint32_t &used, bool &bad) const {
+        return ctx = mhk::decode_one(lut, sub_base, tabs, src, bc, ctx, used, bad);
     }
 };
-template <> struct Dec<false> {
+// stream i's slots in L2 (each_dec_idx_kernel's shape)
+template <> struct Dec<Model::Set> {
+    static constexpr int NT = 256, PER_CU = 8;
+    static constexpr bool O2 = false;
     const uint32_t *row;
     bool o1;
     __device__ __forceinline__ Dec(const FindParams &, unsigned char *) : row(nullptr), o1(false) {}
     __device__ __forceinline__ void stream(const FindParams &p, uint64_t i) { row = p.set.ctx_slot + i * 256u; o1 = p.set.type[i] != 0; }
-    __device__ __forceinline__ uint32_t next(const FindParams &p, const BitSrc &src, BitCursor &bc, uint32_t prev, uint32_t &used, bool &bad) const {
-        return mhe::decode_sym(p.set, row, o1 ? prev : 0u, src, bc, used, bad);
+    __device__ __forceinline__ uint32_t next(const FindParams &p, const BitSrc &src, BitCursor &bc, uint32_t &ctx, uint32_t &used, bool &bad) const {
+        return ctx = mhe::decode_sym(p.set, row, o1 ? ctx : 0u, src, bc, used, bad);
+    }
+};
+// the shared model's order-2 tables as decode2_kernel reads them: general form, every level gathered from L2
+// (batch2_dec_idx_kernel's shape); ctx holds the last two symbols
+template <> struct Dec<Model::Shared2> {
+    static constexpr int NT = 256, PER_CU = 8;
+    static constexpr bool O2 = true;
+    const uint16_t *prim;
+    const uint32_t *sec_base;
+    DecTables tabs;
+    __device__ __forceinline__ Dec(const FindParams &p, unsigned char *) : prim(p.b.prim), sec_base(p.b.sec_base), tabs{p.b.sec, p.b.tree, p.b.P, 0u, 0u} {}
+    __device__ __forceinline__ void stream(const FindParams &, uint64_t) {}
+    __device__ __forceinline__ uint32_t next(const FindParams &, const BitSrc &src, BitCursor &bc, uint32_t &ctx, uint32_t &used, bool &bad) const {
+        const uint32_t sym = mhk::decode_one(prim, sec_base, tabs, src, bc, ctx, used, bad);
+        ctx = ((ctx << 8) | sym) & 0xFFFFu;
+        return sym;
     }
 };
 
@@ -91,76 +117,41 @@ __device__ __forceinline__ void put_hit(const FindParams &p, uint64_t r, uint64_
     if (p.hit_pattern) p.hit_pattern[r] = j;
 }
 
-__device__ __forceinline__ void stream_fail(const FindParams &p, int *status, uint64_t i, int mh_code, int dev_code) {
-    p.b.stream_status[i] = mh_code;
-    fail(status, dev_code);
-}
-
 __global__ __launch_bounds__(256) void find_check_kernel(FindParams p, Automaton a, uint64_t *ws_mask, int *status, int *stop) {
     const uint64_t i = gtid();
     if (i < 256u) ws_mask[i] = a.mask[i];
     if (i > p.b.n) return;
     p.hit_off[i] = 0;
-    bool bad = (i == 0 && p.b.pay_off[0] != 0) || (i == p.b.n && p.b.pay_off[p.b.n] != p.b.pay_total) || (i < p.b.n && p.b.pay_off[i + 1] < p.b.pay_off[i]);
-    if (p.b.index)
-        bad |= (i == 0 && p.b.sym_off[0] != 0) || (i == p.b.n && p.b.sym_off[p.b.n] != p.b.sym_total) || (i < p.b.n && p.b.sym_off[i + 1] < p.b.sym_off[i]);
-    if (bad) { fail(status, BATCH_STATUS_ARG); atomicExch(stop, 1); }
-    if (i == p.b.n) return;
-    p.b.stream_status[i] = MH_OK;
-    if (!bad && p.b.nbits[i] > (p.b.pay_off[i + 1] - p.b.pay_off[i]) * 8u) stream_fail(p, status, i, MH_ERR_ARG, BATCH_STATUS_ARG);
+    check_batch(p.b, i, status, stop);
 }
 
-// chunk w of the indexed batch: its stream, symbols and bit span; false when w is a gap or its stream was refused
-struct Chunk {
-    uint64_t i, ni, first, nb, start, end;
-    uint32_t nsym, prev;
-    bool last;
-};
-__device__ __forceinline__ bool chunk_of(const FindParams &p, uint64_t w, Chunk &c) {
-    const uint32_t cs = p.b.chunk_shift;
-    c.i = find_stream(p.b.sym_off, p.b.n, cs, w);
-    if (c.i >= p.b.n) return false;
-    const uint64_t a = p.b.sym_off[c.i];
-    c.ni = p.b.sym_off[c.i + 1] - a;
-    c.first = (w - ((a >> cs) + c.i)) << cs;
-    if (c.first >= c.ni) return false;
-    c.nb = p.b.nbits[c.i];
-    const uint64_t e = p.b.index[w];
-    c.start = e & MH_INDEX_BIT_MASK;
-    c.prev = uint32_t(e >> 56);
-    c.last = c.first + (uint64_t(1) << cs) >= c.ni;
-    c.end = c.last ? c.nb : (p.b.index[w + 1] & MH_INDEX_BIT_MASK);
-    c.nsym = uint32_t(c.last ? c.ni - c.first : (uint64_t(1) << cs));
-    return true;
-}
-
-template <bool SHARED, bool MLDS>
-__global__ __launch_bounds__(SHARED ? NT_SHARED : NT_EACH) void find_idx_count_kernel(FindParams p, uint64_t nwork, const uint64_t *ws_mask,
-                                                                                    uint32_t lds_at, unsigned long long *state, uint32_t *own,
-                                                                                    uint32_t *tail, int *status, const int *stop) {
+template <Model K, bool MLDS>
+__global__ __launch_bounds__(Dec<K>::NT) void find_idx_count_kernel(FindParams p, uint64_t nwork, const uint64_t *ws_mask, uint32_t lds_at,
+                                                                    unsigned long long *state, uint32_t *own, uint32_t *tail, int *status,
+                                                                    const int *stop) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     if (stopped(stop)) return;
-    Dec<SHARED> dec(p, smem);
+    Dec<K> dec(p, smem);
     const Masks<MLDS> M(ws_mask, smem, lds_at);
     const uint64_t F = p.first, L = p.last;
     for (uint64_t w = gtid(); w < nwork; w += uint64_t(gridDim.x) * blockDim.x) {
         Chunk c;
-        if (!chunk_of(p, w, c) || p.b.stream_status[c.i] == MH_ERR_ARG) continue;
-        if (c.start > c.end || c.end > c.nb) { stream_fail(p, status, c.i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT); continue; }
+        if (!chunk_of<Dec<K>::O2>(p.b, w, c) || p.b.stream_status[c.i] == MH_ERR_ARG) continue;
+        if (!c.entry_ok()) { stream_fail(p.b, status, c.i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT); continue; }
         uint64_t bit0;
         const BitSrc src = mhb::stream_src(p.b.payload, p.b.pay_off[c.i], c.nb, bit0);
         BitCursor bc;
         bc.init(src, bit0 + c.start);
         dec.stream(p, c.i);
-        uint32_t prev = c.prev, used = 0, cnt = 0;
+        uint32_t ctx = c.ctx, used = 0, cnt = 0;
         bool bad = false;
         uint64_t D = 0;
         for (uint32_t t = 0; t < c.nsym && !bad; ++t) {
-            prev = dec.next(p, src, bc, prev, used, bad);
-            D = ((D << 1) | F) & M(prev);
+            const uint32_t sym = dec.next(p, src, bc, ctx, used, bad);
+            D = ((D << 1) | F) & M(sym);
             cnt += uint32_t(__popcll(D & L));
         }
-        if (bad || used != c.end - c.start) { stream_fail(p, status, c.i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT); continue; }
+        if (bad || used != c.end - c.start) { stream_fail(p.b, status, c.i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT); continue; }
         own[w] = cnt;
         state[w] = D;
         if (c.last || !D) continue;
@@ -170,9 +161,9 @@ __global__ __launch_bounds__(SHARED ? NT_SHARED : NT_EACH) void find_idx_count_k
         const uint32_t lim = uint32_t(rest < p.max_len - 1u ? rest : p.max_len - 1u);
         uint32_t tc = 0;
         for (uint32_t t = 0; t < lim && D; ++t) {
-            prev = dec.next(p, src, bc, prev, used, bad);
+            const uint32_t sym = dec.next(p, src, bc, ctx, used, bad);
             if (bad) break;
-            D = (D << 1) & ~F & M(prev);
+            D = (D << 1) & ~F & M(sym);
             tc += uint32_t(__popcll(D & L));
         }
         tail[w] = tc;
@@ -206,31 +197,31 @@ __global__ __launch_bounds__(256) void find_off_kernel(FindParams p, uint64_t nw
     if (i == p.b.n && p.hits && v > p.hit_cap) fail(status, mhk::MHK_STATUS_CAPACITY);
 }
 
-template <bool SHARED, bool MLDS>
-__global__ __launch_bounds__(SHARED ? NT_SHARED : NT_EACH) void find_idx_emit_kernel(FindParams p, uint64_t nwork, const uint64_t *ws_mask,
-                                                                                   uint32_t lds_at, const unsigned long long *state,
-                                                                                   const unsigned long long *cnt, const int *stop) {
+template <Model K, bool MLDS>
+__global__ __launch_bounds__(Dec<K>::NT) void find_idx_emit_kernel(FindParams p, uint64_t nwork, const uint64_t *ws_mask, uint32_t lds_at,
+                                                                   const unsigned long long *state, const unsigned long long *cnt,
+                                                                   const int *stop) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     if (stopped(stop)) return;
-    Dec<SHARED> dec(p, smem);
+    Dec<K> dec(p, smem);
     const Masks<MLDS> M(ws_mask, smem, lds_at);
     const uint64_t F = p.first, L = p.last;
     for (uint64_t w = gtid(); w < nwork; w += uint64_t(gridDim.x) * blockDim.x) {
         const uint64_t r0 = cnt[w], r1 = cnt[w + 1];
         if (r1 == r0 || r0 >= p.hit_cap) continue;                // (a chunk with hits belongs to a stream that passed)
         Chunk c;
-        if (!chunk_of(p, w, c)) continue;
+        if (!chunk_of<Dec<K>::O2>(p.b, w, c)) continue;
         uint64_t bit0;
         const BitSrc src = mhb::stream_src(p.b.payload, p.b.pay_off[c.i], c.nb, bit0);
         BitCursor bc;
         bc.init(src, bit0 + c.start);
         dec.stream(p, c.i);
-        uint32_t prev = c.prev, used = 0;
+        uint32_t ctx = c.ctx, used = 0;
         bool bad = false;
         uint64_t D = c.first ? state[w - 1] : 0ull, r = r0;
         for (uint32_t t = 0; t < c.nsym && r < r1 && !bad; ++t) {
-            prev = dec.next(p, src, bc, prev, used, bad);
-            D = ((D << 1) | F) & M(prev);
+            const uint32_t sym = dec.next(p, src, bc, ctx, used, bad);
+            D = ((D << 1) | F) & M(sym);
             for (uint64_t h = D & L; h && r < r1; h &= h - 1ull, ++r)
                 if (r < p.hit_cap) put_hit(p, r, c.i, c.first + t + 1u, uint32_t(__builtin_ctzll(h)));
         }
@@ -238,12 +229,12 @@ __global__ __launch_bounds__(SHARED ? NT_SHARED : NT_EACH) void find_idx_emit_ke
 }
 
 // EMIT = false: the stream's verdict and its hit count into hit_off[i] (scanned next); true: its records from hit_off[i]
-template <bool SHARED, bool MLDS, bool EMIT>
-__global__ __launch_bounds__(SHARED ? NT_SHARED : NT_EACH) void find_walk_kernel(FindParams p, const uint64_t *ws_mask, uint32_t lds_at,
-                                                                               int *status, const int *stop) {
+template <Model K, bool MLDS, bool EMIT>
+__global__ __launch_bounds__(Dec<K>::NT) void find_walk_kernel(FindParams p, const uint64_t *ws_mask, uint32_t lds_at, int *status,
+                                                               const int *stop) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     if (stopped(stop)) return;
-    Dec<SHARED> dec(p, smem);
+    Dec<K> dec(p, smem);
     const Masks<MLDS> M(ws_mask, smem, lds_at);
     const uint64_t F = p.first, L = p.last;
     for (uint64_t i = gtid(); i < p.b.n; i += uint64_t(gridDim.x) * blockDim.x) {
@@ -254,7 +245,7 @@ __global__ __launch_bounds__(SHARED ? NT_SHARED : NT_EACH) void find_walk_kernel
             r = p.hit_off[i]; r1 = p.hit_off[i + 1];
             if (r1 == r || r >= p.hit_cap) continue;
         } else if (nb > p.b.walk_max_bits) {
-            stream_fail(p, status, i, MH_ERR_ARG, BATCH_STATUS_ARG);
+            stream_fail(p.b, status, i, MH_ERR_ARG, BATCH_STATUS_ARG);
             continue;
         }
         uint64_t bit0;
@@ -262,13 +253,13 @@ __global__ __launch_bounds__(SHARED ? NT_SHARED : NT_EACH) void find_walk_kernel
         BitCursor bc;
         bc.init(src, bit0);
         dec.stream(p, i);
-        uint32_t prev = p.b.prev0, used = 0;
+        uint32_t ctx = p.b.prev0, used = 0;
         bool bad = false;
         uint64_t D = 0, k = 0, cnt = 0;
         // every code has at least one bit: at most nb steps (src/coding.cpp:124 — decode while bits remain)
         while (used < nb && !bad && (!EMIT || r < r1)) {
-            prev = dec.next(p, src, bc, prev, used, bad);
-            D = ((D << 1) | F) & M(prev);
+            const uint32_t sym = dec.next(p, src, bc, ctx, used, bad);
+            D = ((D << 1) | F) & M(sym);
             ++k;
             if (EMIT) {
                 for (uint64_t h = D & L; h && r < r1; h &= h - 1ull, ++r)
@@ -278,7 +269,7 @@ __global__ __launch_bounds__(SHARED ? NT_SHARED : NT_EACH) void find_walk_kernel
             }
         }
         if (EMIT) continue;
-        if (bad || used != nb) { stream_fail(p, status, i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT); continue; }
+        if (bad || used != nb) { stream_fail(p.b, status, i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT); continue; }
         p.hit_off[i] = cnt;                                       // src/coding.cpp:158: the stream ends exactly at nbits
     }
 }
@@ -288,23 +279,22 @@ __global__ void find_cap_kernel(FindParams p, int *status, const int *stop) {
     if (p.hits && p.hit_off[p.b.n] > p.hit_cap) fail(status, mhk::MHK_STATUS_CAPACITY);
 }
 
-template <bool SHARED, bool MLDS>
+template <Model K, bool MLDS>
 hipError_t launch(const FindParams &p, const Automaton &a, size_t lds_tables, void *d_ws, hipStream_t st) {
-    constexpr int NT = SHARED ? NT_SHARED : NT_EACH;
-    constexpr int PER_CU = SHARED ? 1 : 8;
+    constexpr int NT = Dec<K>::NT, PER_CU = Dec<K>::PER_CU;
     const size_t lds = lds_tables + (MLDS ? 2048 : 0);
     const uint32_t lds_at = uint32_t(lds_tables);
-    if (SHARED) {
+    if (K == Model::Shared) {
         const int lds_max = 163840;
-        hipError_t attr = mhk::allow_lds(reinterpret_cast<const void *>(find_idx_count_kernel<SHARED, MLDS>), lds_max);
-        if (attr == hipSuccess) attr = mhk::allow_lds(reinterpret_cast<const void *>(find_idx_emit_kernel<SHARED, MLDS>), lds_max);
-        if (attr == hipSuccess) attr = mhk::allow_lds(reinterpret_cast<const void *>(find_walk_kernel<SHARED, MLDS, false>), lds_max);
-        if (attr == hipSuccess) attr = mhk::allow_lds(reinterpret_cast<const void *>(find_walk_kernel<SHARED, MLDS, true>), lds_max);
+        hipError_t attr = mhk::allow_lds(reinterpret_cast<const void *>(find_idx_count_kernel<K, MLDS>), lds_max);
+        if (attr == hipSuccess) attr = mhk::allow_lds(reinterpret_cast<const void *>(find_idx_emit_kernel<K, MLDS>), lds_max);
+        if (attr == hipSuccess) attr = mhk::allow_lds(reinterpret_cast<const void *>(find_walk_kernel<K, MLDS, false>), lds_max);
+        if (attr == hipSuccess) attr = mhk::allow_lds(reinterpret_cast<const void *>(find_walk_kernel<K, MLDS, true>), lds_max);
         if (attr != hipSuccess) return attr;
     }
     unsigned char *ws = static_cast<unsigned char *>(d_ws);
     const uint64_t n = p.b.n;
-    const uint64_t W = p.b.index ? p.b.sym_total / (uint64_t(1) << p.b.chunk_shift) + n + 1 : 0;
+    const uint64_t W = p.b.index ? mhb::work_items(n, p.b.sym_total, 1u << p.b.chunk_shift) : 0;
     const FindLayout L = find_layout(n, W);
     int *status = reinterpret_cast<int *>(ws), *stop = status + 1;
     uint64_t *ws_mask = reinterpret_cast<uint64_t *>(ws + L.off_mask);
@@ -318,32 +308,34 @@ hipError_t launch(const FindParams &p, const Automaton &a, size_t lds_tables, vo
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(find_check_kernel, grid_threads((n + 1 > 256 ? n + 1 : 256), 256), dim3(256), 0, st, p, a, ws_mask, status, stop);
     if (p.b.index) {
-        hipLaunchKernelGGL((find_idx_count_kernel<SHARED, MLDS>), dim3(grid_for(W, NT, PER_CU)), dim3(NT), lds, st, p, W, ws_mask, lds_at, state,
+        hipLaunchKernelGGL((find_idx_count_kernel<K, MLDS>), dim3(grid_for(W, NT, PER_CU)), dim3(NT), lds, st, p, W, ws_mask, lds_at, state,
                            own, tail, status, stop);
         hipLaunchKernelGGL(find_comb_kernel, grid_threads(W + 1, 256), dim3(256), 0, st, p, W, own, tail, cnt, stop);
         if ((e = scan_exclusive(cnt, W + 1, sums, stop, st)) != hipSuccess) return e;
         hipLaunchKernelGGL(find_off_kernel, grid_threads(n + 1, 256), dim3(256), 0, st, p, W, cnt, status, stop);
         if (p.hits)
-            hipLaunchKernelGGL((find_idx_emit_kernel<SHARED, MLDS>), dim3(grid_for(W, NT, PER_CU)), dim3(NT), lds, st, p, W, ws_mask, lds_at,
+            hipLaunchKernelGGL((find_idx_emit_kernel<K, MLDS>), dim3(grid_for(W, NT, PER_CU)), dim3(NT), lds, st, p, W, ws_mask, lds_at,
                                state, cnt, stop);
         return hipGetLastError();
     }
-    hipLaunchKernelGGL((find_walk_kernel<SHARED, MLDS, false>), dim3(grid_for(n + 1, NT, PER_CU)), dim3(NT), lds, st, p, ws_mask, lds_at, status, stop);
+    hipLaunchKernelGGL((find_walk_kernel<K, MLDS, false>), dim3(grid_for(n + 1, NT, PER_CU)), dim3(NT), lds, st, p, ws_mask, lds_at, status, stop);
     if ((e = scan_exclusive(p.hit_off, n + 1, sums, stop, st)) != hipSuccess) return e;
     hipLaunchKernelGGL(find_cap_kernel, dim3(1), dim3(1), 0, st, p, status, stop);
     if (p.hits)
-        hipLaunchKernelGGL((find_walk_kernel<SHARED, MLDS, true>), dim3(grid_for(n + 1, NT, PER_CU)), dim3(NT), lds, st, p, ws_mask, lds_at, status, stop);
+        hipLaunchKernelGGL((find_walk_kernel<K, MLDS, true>), dim3(grid_for(n + 1, NT, PER_CU)), dim3(NT), lds, st, p, ws_mask, lds_at, status, stop);
     return hipGetLastError();
 }
 
 }  // namespace
 
-hipError_t launch_find(const FindParams &p, const Automaton &a, bool shared, void *d_ws, hipStream_t st) {
-    if (!shared) return launch<false, true>(p, a, 0, d_ws, st);
+hipError_t launch_find(const FindParams &p, const Automaton &a, Model model, void *d_ws, hipStream_t st) {
+    // tables in L2: the masks alone in LDS, at offset 0
+    if (model == Model::Set) return launch<Model::Set, true>(p, a, 0, d_ws, st);
+    if (model == Model::Shared2) return launch<Model::Shared2, true>(p, a, 0, d_ws, st);
     // the tables as launch_decode_batch places them; the masks behind them when 2 KiB are left of the 160 KiB
-    const size_t lds = 1024 + (size_t(256) << p.b.P) * 2 + (p.b.sec_lds ? ((size_t(p.b.nsec) * 2 + 15) & ~size_t(15)) : 0);
+    const size_t lds = mhb::tables_lds(p.b);
     if (lds > 163840) return hipErrorInvalidValue;
-    return lds + 2048 <= 163840 ? launch<true, true>(p, a, lds, d_ws, st) : launch<true, false>(p, a, lds, d_ws, st);
+    return lds + 2048 <= 163840 ? launch<Model::Shared, true>(p, a, lds, d_ws, st) : launch<Model::Shared, false>(p, a, lds, d_ws, st);
 }
 
 }  // namespace mhf

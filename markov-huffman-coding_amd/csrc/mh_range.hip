@@ -119,8 +119,7 @@ hipError_t launch_decode_ranges(const RangeParams &p, void *d_ws, hipStream_t st
     const int lds_max = 163840;
     hipError_t attr = mhk::allow_lds(reinterpret_cast<const void *>(range_decode_kernel), lds_max);
     if (attr != hipSuccess) return attr;
-    const mhb::DecBatchParams &t = p.tab;
-    const size_t lds = 1024 + (size_t(256) << t.P) * 2 + (t.sec_lds ? ((size_t(t.nsec) * 2 + 15) & ~size_t(15)) : 0);
+    const size_t lds = mhb::tables_lds(p.tab);
     if (lds > size_t(lds_max)) return hipErrorInvalidValue;
     unsigned char *ws = static_cast<unsigned char *>(d_ws);
     const RangeLayout L = range_layout(p.n);

@@ -27,10 +27,6 @@ struct Dst {
     uint32_t ctx_mask;
 };
 
-inline uint64_t work_items(uint64_t n_streams, uint64_t sym_total, uint32_t chunk_symbols) {
-    return chunk_symbols ? sym_total / chunk_symbols + n_streams + 1 : 0;
-}
-
 // histogram workspace: status block | per-stream status (when the caller passes none)
 struct HistLayout {
     size_t off_status, total;
@@ -65,16 +61,21 @@ struct HistParams {
     unsigned long long *counts;
 };
 
-struct RecodeParams {
+// what every re-coding call has, whatever the orders of its models: the source and the outputs.  The kernels that never decode
+// (mh_recode_dev.hpp) take this part alone.
+struct RecodeIO {
     Src s;                          // index-free: s.b.sym_off is written, s.b.index null
-    Dst dst;
     uint8_t *out;                   // packed payloads, 16-byte aligned; nullptr: count only
     uint64_t cap;
     unsigned long long *out_off;    // n + 1 (written)
     unsigned long long *out_nbits;  // n (written)
-    unsigned long long *out_index;  // slices of the destination index, or nullptr
+    unsigned long long *out_index;  // slices of the destination index in dst's entry format, or nullptr
     unsigned long long *dropped;    // n, or nullptr
     uint32_t out_chunk_shift;       // chunk of the destination index (indexed source: the source's)
+};
+
+struct RecodeParams : RecodeIO {
+    Dst dst;
 };
 
 // shared: one source model (s.b's tables, LDS); else stream i under set model i

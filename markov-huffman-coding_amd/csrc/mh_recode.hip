@@ -1,7 +1,8 @@
 // mh_recode.hip — a compressed batch's training histogram and the batch coded again under another model, without writing
 // the decoded bytes (include/mh.h, "RE-CODING BATCHES").  The batch decoders hold every decoded byte in a register for one
 // step; here that byte feeds a counter, or the destination model's code and a BitWriter, instead of a store.
-//   recode_check_kernel      the batch checks of batch_dec_check_kernel; out_off, nbits and dropped zeroed
+//   recode_check_kernel      the batch checks (mhb::check_batch); out_off, nbits and dropped zeroed (this and the other kernels
+//                            that never decode — sizes, cap, zero, tail — are in mh_recode_dev.hpp)
 //   recode_idx_len_kernel    one lane per (stream, chunk): decodes under src, sums dst's code lengths and the symbols without a code
 //   recode_comb_kernel       the chunks of failed streams count 0 bits; the dropped symbols of the others go to dropped[i]
 //   (scan)                   chunk bits -> bit offsets (mh_batch_dev.hpp); then payload bytes -> out_off
@@ -20,6 +21,7 @@
 // The counters: a direct-mapped cache of (pair -> u64) in the LDS the tables leave, 64-bit global atomics behind it.
 #include "mh_recode.h"
 #include "mh_batch_dev.hpp"
+#include "mh_recode_dev.hpp"
 #include "mh_each_dev.hpp"
 #include "../../include/mh.h"
 
@@ -33,18 +35,20 @@ using mhk::DecTables;
 namespace {
 
 using mhb::BitWriter;
+using mhb::Chunk;
+using mhb::chunk_of;
 using mhb::fail;
 using mhb::find_stream;
 using mhb::grid_for;
+using mhb::grid_threads;
+using mhb::gtid;
 using mhb::scan_exclusive;
 using mhb::stopped;
+using mhb::stream_fail;
 
 constexpr int NT_SHARED = mhb::B_THREADS;          // batch_dec_idx_kernel's shape: one workgroup per CU beside the tables
 constexpr int NT_EACH = 256;                       // each_dec_idx_kernel's
 constexpr int LDS_MAX = 163840;
-
-__device__ __forceinline__ uint64_t gtid() { return uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; }
-inline dim3 grid_threads(uint64_t items, uint32_t per_block) { return dim3(uint32_t((items + per_block - 1) / per_block)); }
 
 // the symbol decoder of a lane: the shared model's two-level tables, or stream i's slots
 template <bool SHARED> struct Dec;
@@ -86,50 +90,6 @@ template <bool DLDS> struct Lens {
         if constexpr (DLDS) return l[idx]; else return g[idx];
     }
 };
-
-__device__ __forceinline__ void stream_fail(const Src &s, int *status, uint64_t i, int mh_code, int dev_code) {
-    s.b.stream_status[i] = mh_code;
-    fail(status, dev_code);
-}
-
-// the up-front checks of one stream (thread i <= n); true when the call must stop
-__device__ __forceinline__ bool check_stream(const Src &s, uint64_t i, int *status, int *stop) {
-    const mhb::DecBatchParams &b = s.b;
-    bool bad = (i == 0 && b.pay_off[0] != 0) || (i == b.n && b.pay_off[b.n] != b.pay_total) || (i < b.n && b.pay_off[i + 1] < b.pay_off[i]);
-    if (b.index)
-        bad |= (i == 0 && b.sym_off[0] != 0) || (i == b.n && b.sym_off[b.n] != b.sym_total) || (i < b.n && b.sym_off[i + 1] < b.sym_off[i]);
-    if (bad) { fail(status, BATCH_STATUS_ARG); atomicExch(stop, 1); }
-    if (i == b.n) return bad;
-    b.stream_status[i] = MH_OK;
-    if (!bad && b.nbits[i] > (b.pay_off[i + 1] - b.pay_off[i]) * 8u) stream_fail(s, status, i, MH_ERR_ARG, BATCH_STATUS_ARG);
-    return bad;
-}
-
-// chunk w of the indexed batch: its stream, symbols and bit span; false when w is a gap
-struct Chunk {
-    uint64_t i, ni, first, nb, start, end;
-    uint32_t nsym, prev;
-    bool last;
-    __device__ __forceinline__ bool entry_ok() const { return start <= end && end <= nb; }
-};
-__device__ __forceinline__ bool chunk_of(const Src &s, uint64_t w, Chunk &c) {
-    const mhb::DecBatchParams &b = s.b;
-    const uint32_t cs = b.chunk_shift;
-    c.i = find_stream(b.sym_off, b.n, cs, w);
-    if (c.i >= b.n) return false;
-    const uint64_t a = b.sym_off[c.i];
-    c.ni = b.sym_off[c.i + 1] - a;
-    c.first = (w - ((a >> cs) + c.i)) << cs;
-    if (c.first >= c.ni) return false;
-    c.nb = b.nbits[c.i];
-    const uint64_t e = b.index[w];
-    c.start = e & MH_INDEX_BIT_MASK;
-    c.prev = uint32_t(e >> 56);
-    c.last = c.first + (uint64_t(1) << cs) >= c.ni;
-    c.end = c.last ? c.nb : (b.index[w + 1] & MH_INDEX_BIT_MASK);
-    c.nsym = uint32_t(c.last ? c.ni - c.first : (uint64_t(1) << cs));
-    return true;
-}
 
 // ------------------------------------------------------------------------------------------------ histogram
 
@@ -184,7 +144,7 @@ __device__ __forceinline__ uint32_t walk_chunk(const Src &s, const Dec<SHARED> &
     const BitSrc src = mhb::stream_src(s.b.payload, s.b.pay_off[c.i], c.nb, bit0);
     BitCursor bc;
     bc.init(src, bit0 + c.start);
-    uint32_t prev = c.prev, t = 0;
+    uint32_t prev = c.ctx, t = 0;
     used = 0; bad = false;
     for (; t < count; ++t) {
         const uint32_t sym = dec.next(s, src, bc, prev, used, bad);
@@ -207,17 +167,17 @@ __global__ __launch_bounds__(SHARED ? NT_SHARED : NT_EACH) void histc_idx_kernel
     for (uint64_t base = uint64_t(blockIdx.x) * blockDim.x; base < nwork; base += uint64_t(gridDim.x) * blockDim.x) {
         const uint64_t w = base + threadIdx.x;
         Chunk c;
-        if (w < nwork && chunk_of(p.s, w, c)) {
+        if (w < nwork && chunk_of<false>(p.s.b, w, c)) {
             dec.stream(p.s, c.i);
             const int verdict = p.s.b.stream_status[c.i];
             uint32_t used; bool bad;
             if (!FIX && verdict != MH_ERR_ARG) {
                 if (!c.entry_ok()) {
-                    stream_fail(p.s, status, c.i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT);
+                    stream_fail(p.s.b, status, c.i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT);
                 } else {
                     const uint32_t done = walk_chunk<SHARED>(p.s, dec, c, c.nsym, 1, pc, used, bad);
                     if (bad || used != c.end - c.start) {
-                        stream_fail(p.s, status, c.i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT);
+                        stream_fail(p.s.b, status, c.i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT);
                         walk_chunk<SHARED>(p.s, dec, c, done, -1, pc, used, bad);
                     }
                 }
@@ -267,13 +227,13 @@ __global__ __launch_bounds__(SHARED ? NT_SHARED : NT_EACH) void histc_walk_kerne
         if (i < n && p.s.b.stream_status[i] == MH_OK) {
             const uint64_t nb = p.s.b.nbits[i];
             if (nb > p.s.b.walk_max_bits) {
-                stream_fail(p.s, status, i, MH_ERR_ARG, BATCH_STATUS_ARG);
+                stream_fail(p.s.b, status, i, MH_ERR_ARG, BATCH_STATUS_ARG);
             } else {
                 dec.stream(p.s, i);
                 uint32_t used; bool bad;
                 const uint64_t done = walk_stream<SHARED>(p.s, dec, i, nb, ~uint64_t(0), 1, pc, used, bad);
                 if (bad || used != nb) {                            // src/coding.cpp:158: the stream ends exactly at nbits
-                    stream_fail(p.s, status, i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT);
+                    stream_fail(p.s.b, status, i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT);
                     walk_stream<SHARED>(p.s, dec, i, nb, done, -1, pc, used, bad);
                 }
             }
@@ -282,26 +242,7 @@ __global__ __launch_bounds__(SHARED ? NT_SHARED : NT_EACH) void histc_walk_kerne
     pc.flush();
 }
 
-__global__ __launch_bounds__(256) void histc_check_kernel(HistParams p, int *status, int *stop) {
-    const uint64_t i = gtid();
-    if (i > p.s.b.n) return;
-    check_stream(p.s, i, status, stop);
-}
-
 // ------------------------------------------------------------------------------------------------ re-code
-
-__global__ __launch_bounds__(256) void recode_check_kernel(RecodeParams p, int *status, int *stop) {
-    const uint64_t i = gtid();
-    const uint64_t n = p.s.b.n;
-    if (i > n) return;
-    p.out_off[i] = 0;
-    if (!p.s.b.index) p.s.b.sym_off[i] = 0;
-    if (i < n) {
-        p.out_nbits[i] = 0;
-        if (p.dropped) p.dropped[i] = 0;
-    }
-    check_stream(p.s, i, status, stop);
-}
 
 template <bool SHARED, bool DLDS>
 __global__ __launch_bounds__(SHARED ? NT_SHARED : NT_EACH) void recode_idx_len_kernel(RecodeParams p, uint64_t nwork, uint32_t lds_at,
@@ -313,14 +254,14 @@ __global__ __launch_bounds__(SHARED ? NT_SHARED : NT_EACH) void recode_idx_len_k
     const Lens<DLDS> L(p.dst, smem, lds_at);
     for (uint64_t w = gtid(); w < nwork; w += uint64_t(gridDim.x) * blockDim.x) {
         Chunk c;
-        if (!chunk_of(p.s, w, c) || p.s.b.stream_status[c.i] == MH_ERR_ARG) continue;
-        if (!c.entry_ok()) { stream_fail(p.s, status, c.i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT); continue; }
+        if (!chunk_of<false>(p.s.b, w, c) || p.s.b.stream_status[c.i] == MH_ERR_ARG) continue;
+        if (!c.entry_ok()) { stream_fail(p.s.b, status, c.i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT); continue; }
         uint64_t bit0;
         const BitSrc src = mhb::stream_src(p.s.b.payload, p.s.b.pay_off[c.i], c.nb, bit0);
         BitCursor bc;
         bc.init(src, bit0 + c.start);
         dec.stream(p.s, c.i);
-        uint32_t prev = c.prev, used = 0, bits = 0, drops = 0;
+        uint32_t prev = c.ctx, used = 0, bits = 0, drops = 0;
         bool bad = false;
         for (uint32_t t = 0; t < c.nsym && !bad; ++t) {
             const uint32_t sym = dec.next(p.s, src, bc, prev, used, bad);
@@ -330,7 +271,7 @@ __global__ __launch_bounds__(SHARED ? NT_SHARED : NT_EACH) void recode_idx_len_k
             drops += l == 0u;
             prev = sym;
         }
-        if (bad || used != c.end - c.start) { stream_fail(p.s, status, c.i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT); continue; }
+        if (bad || used != c.end - c.start) { stream_fail(p.s.b, status, c.i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT); continue; }
         cbits[w] = bits;
         cdrop[w] = drops;
     }
@@ -358,46 +299,6 @@ __global__ __launch_bounds__(256) void recode_comb_kernel(RecodeParams p, uint64
     cbits[w] = v;
 }
 
-// stream i: payload bits (indexed: from the scanned chunk bits; index-free: the count pass wrote them), bytes into out_off
-__global__ __launch_bounds__(256) void recode_sizes_kernel(RecodeParams p, const unsigned long long *cbase, int *status, int *stop) {
-    if (stopped(stop)) return;
-    const uint64_t i = gtid();
-    const uint64_t n = p.s.b.n;
-    if (i > n) return;
-    if (i == n) { p.out_off[i] = 0; return; }
-    unsigned long long bits;
-    if (p.s.b.index) {
-        const uint32_t cs = p.s.b.chunk_shift;
-        const uint64_t w0 = (p.s.b.sym_off[i] >> cs) + i, w1 = (p.s.b.sym_off[i + 1] >> cs) + i + 1;
-        bits = cbase[w1] - cbase[w0];
-        p.out_nbits[i] = bits;
-    } else {
-        bits = p.out_nbits[i];
-    }
-    p.out_off[i] = (bits + 7) >> 3;
-}
-
-// index-free: the destination index was sized from sym_total; more symbols than that do not fit it (after the scans: offsets
-// and lengths are complete)
-__global__ void recode_cap_kernel(RecodeParams p, int *status, int *stop) {
-    if (stopped(stop)) return;
-    if (p.s.b.sym_off[p.s.b.n] > p.s.b.sym_total) { fail(status, mhk::MHK_STATUS_CAPACITY); atomicExch(stop, 1); }
-}
-
-// zeroes the payload bytes (codes are OR-ed into shared edge dwords) or reports that they do not fit
-__global__ __launch_bounds__(256) void recode_zero_kernel(RecodeParams p, int *status, int *stop, uint32_t *tail) {
-    if (stopped(stop)) return;
-    const uint64_t bytes = p.out_off[p.s.b.n];
-    if (bytes > p.cap) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) { fail(status, mhk::MHK_STATUS_CAPACITY); atomicExch(stop, 1); }
-        return;
-    }
-    const uint64_t nfull = bytes >> 2;
-    uint32_t *o = reinterpret_cast<uint32_t *>(p.out);
-    for (uint64_t k = gtid(); k < nfull; k += uint64_t(gridDim.x) * blockDim.x) o[k] = 0u;
-    if (blockIdx.x == 0 && threadIdx.x == 0) *tail = 0u;
-}
-
 template <bool SHARED, bool DLDS>
 __global__ __launch_bounds__(SHARED ? NT_SHARED : NT_EACH) void recode_idx_emit_kernel(RecodeParams p, uint64_t nwork, uint32_t lds_at,
                                                                                      const unsigned long long *cbase, uint32_t *tail,
@@ -411,10 +312,10 @@ __global__ __launch_bounds__(SHARED ? NT_SHARED : NT_EACH) void recode_idx_emit_
     const uint32_t cs = p.s.b.chunk_shift;
     for (uint64_t w = gtid(); w < nwork; w += uint64_t(gridDim.x) * blockDim.x) {
         Chunk c;
-        if (!chunk_of(p.s, w, c) || p.s.b.stream_status[c.i] != MH_OK) continue;
+        if (!chunk_of<false>(p.s.b, w, c) || p.s.b.stream_status[c.i] != MH_OK) continue;
         const unsigned long long b0 = cbase[w];
         const uint64_t rel = b0 - cbase[(p.s.b.sym_off[c.i] >> cs) + c.i];          // relative to the stream's own payload
-        if (p.out_index) p.out_index[w] = (uint64_t(c.prev) << 56) | rel;
+        if (p.out_index) p.out_index[w] = (uint64_t(c.ctx) << 56) | rel;
         if (!p.out || cbase[w + 1] == b0) continue;
         uint64_t bit0;
         const BitSrc src = mhb::stream_src(p.s.b.payload, p.s.b.pay_off[c.i], c.nb, bit0);
@@ -423,7 +324,7 @@ __global__ __launch_bounds__(SHARED ? NT_SHARED : NT_EACH) void recode_idx_emit_
         dec.stream(p.s, c.i);
         BitWriter bw;
         bw.init(reinterpret_cast<uint32_t *>(p.out), tail, tail_w, uint64_t(p.out_off[c.i]) * 8u + rel);
-        uint32_t prev = c.prev, used = 0;
+        uint32_t prev = c.ctx, used = 0;
         bool bad = false;
         for (uint32_t t = 0; t < c.nsym && !bad; ++t) {            // (the stream passed: bad stays false)
             const uint32_t sym = dec.next(p.s, src, bc, prev, used, bad);
@@ -458,7 +359,7 @@ __global__ __launch_bounds__(SHARED ? NT_SHARED : NT_EACH) void recode_walk_kern
             count = p.s.b.sym_off[i + 1] - a;
             if (!count) continue;
         } else if (nb > p.s.b.walk_max_bits) {
-            stream_fail(p.s, status, i, MH_ERR_ARG, BATCH_STATUS_ARG);
+            stream_fail(p.s.b, status, i, MH_ERR_ARG, BATCH_STATUS_ARG);
             continue;
         }
         uint64_t bit0;
@@ -486,24 +387,11 @@ __global__ __launch_bounds__(SHARED ? NT_SHARED : NT_EACH) void recode_walk_kern
             ++k;
         }
         if (EMIT) { if (p.out) bw.finish(); continue; }
-        if (bad || used != nb) { stream_fail(p.s, status, i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT); continue; }
+        if (bad || used != nb) { stream_fail(p.s.b, status, i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT); continue; }
         p.s.b.sym_off[i] = k;                                       // src/coding.cpp:158: the stream ends exactly at nbits
         p.out_nbits[i] = bits;
         if (p.dropped) p.dropped[i] = drops;
     }
-}
-
-__global__ void recode_tail_kernel(RecodeParams p, const uint32_t *tail, const int *stop) {
-    if (stopped(stop)) return;
-    const uint64_t bytes = p.out_off[p.s.b.n];
-    if (!(bytes & 3u)) return;
-    const uint8_t *t = reinterpret_cast<const uint8_t *>(tail);
-    for (uint64_t b = bytes & ~uint64_t(3); b < bytes; ++b) p.out[b] = t[b & 3u];
-}
-
-// LDS of a shared source model's tables, as launch_decode_batch places them
-inline size_t tables_lds(const mhb::DecBatchParams &b) {
-    return 1024 + (size_t(256) << b.P) * 2 + (b.sec_lds ? ((size_t(b.nsec) * 2 + 15) & ~size_t(15)) : 0);
 }
 
 template <bool SHARED>
@@ -529,9 +417,9 @@ hipError_t launch_hist(const HistParams &p, size_t lds_tables, void *d_ws, hipSt
     hipError_t e = hipMemsetAsync(ws, 0, 64, st);
     if (e == hipSuccess) e = hipMemsetAsync(p.counts, 0, (p.order ? 65536u : 256u) * sizeof(unsigned long long), st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(histc_check_kernel, grid_threads(n + 1, 256), dim3(256), 0, st, p, status, stop);
+    hipLaunchKernelGGL(histc_check_kernel, grid_threads(n + 1, 256), dim3(256), 0, st, p.s, status, stop);
     if (p.s.b.index) {
-        const uint64_t W = p.s.b.sym_total / (uint64_t(1) << p.s.b.chunk_shift) + n + 1;
+        const uint64_t W = mhb::work_items(n, p.s.b.sym_total, 1u << p.s.b.chunk_shift);
         hipLaunchKernelGGL((histc_idx_kernel<SHARED, false>), dim3(grid_for(W, NT, PER_CU)), dim3(NT), lds, st, p, W, lds_at, log2n, status, stop);
         hipLaunchKernelGGL((histc_idx_kernel<SHARED, true>), dim3(grid_for(W, NT, PER_CU)), dim3(NT), lds, st, p, W, lds_at, log2n, status, stop);
         return hipGetLastError();
@@ -555,7 +443,7 @@ hipError_t launch_rc(const RecodeParams &p, size_t lds_tables, void *d_ws, hipSt
     }
     unsigned char *ws = static_cast<unsigned char *>(d_ws);
     const uint64_t n = p.s.b.n;
-    const uint64_t W = p.s.b.index ? p.s.b.sym_total / (uint64_t(1) << p.s.b.chunk_shift) + n + 1 : 0;
+    const uint64_t W = p.s.b.index ? mhb::work_items(n, p.s.b.sym_total, 1u << p.s.b.chunk_shift) : 0;
     const RecodeLayout L = recode_layout(n, W);
     int *status = reinterpret_cast<int *>(ws), *stop = status + 1;
     uint32_t *tail = reinterpret_cast<uint32_t *>(ws + TAIL_AT);
@@ -576,7 +464,7 @@ hipError_t launch_rc(const RecodeParams &p, size_t lds_tables, void *d_ws, hipSt
                            stop);
         if ((e = scan_exclusive(p.s.b.sym_off, n + 1, sums, stop, st)) != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(recode_sizes_kernel, grid_threads(n + 1, 256), dim3(256), 0, st, p, cbits, status, stop);
+    hipLaunchKernelGGL(recode_sizes_kernel, grid_threads(n + 1, 256), dim3(256), 0, st, p, cbits, stop);
     if ((e = scan_exclusive(p.out_off, n + 1, sums, stop, st)) != hipSuccess) return e;
     if (!p.s.b.index && p.out_index) hipLaunchKernelGGL(recode_cap_kernel, dim3(1), dim3(1), 0, st, p, status, stop);
     if (p.out) hipLaunchKernelGGL(recode_zero_kernel, dim3(grid_for(p.cap / 4 + 1, 256, 8)), dim3(256), 0, st, p, status, stop, tail);
@@ -596,7 +484,7 @@ hipError_t launch_rc(const RecodeParams &p, size_t lds_tables, void *d_ws, hipSt
 
 hipError_t launch_histogram_coded(const HistParams &p, bool shared, void *d_ws, hipStream_t st) {
     if (!shared) return launch_hist<false>(p, 0, d_ws, st);
-    const size_t lds = tables_lds(p.s.b);
+    const size_t lds = mhb::tables_lds(p.s.b);
     if (lds > size_t(LDS_MAX)) return hipErrorInvalidValue;
     return launch_hist<true>(p, lds, d_ws, st);
 }
@@ -604,7 +492,7 @@ hipError_t launch_histogram_coded(const HistParams &p, bool shared, void *d_ws, 
 hipError_t launch_recode(const RecodeParams &p, bool shared, void *d_ws, hipStream_t st) {
     // a model set's tables stay in L2 and eight workgroups share a CU: only an order-0 image (256 B) goes to LDS
     if (!shared) return p.dst.ctx_mask ? launch_rc<false, false>(p, 0, d_ws, st) : launch_rc<false, true>(p, 0, d_ws, st);
-    const size_t lds = tables_lds(p.s.b);
+    const size_t lds = mhb::tables_lds(p.s.b);
     if (lds > size_t(LDS_MAX)) return hipErrorInvalidValue;
     const size_t img = p.dst.ctx_mask ? 65536 : 256;
     return lds + img <= size_t(LDS_MAX) ? launch_rc<true, true>(p, lds, d_ws, st) : launch_rc<true, false>(p, lds, d_ws, st);

@@ -43,17 +43,9 @@ struct Hist2Params {
     unsigned long long *counts;
 };
 
-struct Recode2Params {
-    Src s;                          // index-free: s.b.sym_off is written, s.b.index null
+struct Recode2Params : RecodeIO {
     bool src2;
     Dst2 dst;
-    uint8_t *out;                   // packed payloads, 16-byte aligned; nullptr: count only
-    uint64_t cap;
-    unsigned long long *out_off;    // n + 1 (written)
-    unsigned long long *out_nbits;  // n (written)
-    unsigned long long *out_index;  // slices of the destination index in dst's entry format, or nullptr
-    unsigned long long *dropped;    // n, or nullptr
-    uint32_t out_chunk_shift;       // chunk of the destination index (indexed source: the source's)
 };
 
 hipError_t launch_histogram_coded_o2(const Hist2Params &p, void *d_ws, hipStream_t st);

@@ -24,6 +24,7 @@
 // statuses.  Every loop is bounded by a symbol count or nbits_i.
 #include "mh_recode_o2.h"
 #include "mh_batch_dev.hpp"
+#include "mh_recode_dev.hpp"
 #include "../../include/mh.h"
 
 namespace mhr {
@@ -36,19 +37,21 @@ using mhk::DecTables;
 namespace {
 
 using mhb::BitWriter;
+using mhb::Chunk;
 using mhb::fail;
 using mhb::find_stream;
 using mhb::grid_for;
+using mhb::grid_threads;
+using mhb::gtid;
 using mhb::scan_exclusive;
 using mhb::stopped;
+using mhb::stream_fail;
 
 constexpr int NT_LDS = mhb::B_THREADS;             // order-0/1 source: one workgroup per CU beside the tables
 constexpr int NT_L2 = 256;                         // order-2 source: batch2_dec_idx_kernel's shape
 constexpr int LDS_MAX = 163840;
 template <bool S2> constexpr int nt_of() { return S2 ? NT_L2 : NT_LDS; }
 
-__device__ __forceinline__ uint64_t gtid() { return uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; }
-inline dim3 grid_threads(uint64_t items, uint32_t per_block) { return dim3(uint32_t((items + per_block - 1) / per_block)); }
 __device__ __forceinline__ uint32_t roll(uint32_t c16, uint32_t sym) { return ((c16 << 8) | sym) & 0xFFFFu; }
 
 // the symbol decoder of a lane, in the 16-bit context c16 (an order-0/1 model reads its last byte)
@@ -102,53 +105,15 @@ struct Enc {
     }
 };
 
-__device__ __forceinline__ void stream_fail(const Src &s, int *status, uint64_t i, int mh_code, int dev_code) {
-    s.b.stream_status[i] = mh_code;
-    fail(status, dev_code);
-}
-
-// the up-front checks of one stream (thread i <= n); true when the call must stop
-__device__ __forceinline__ bool check_stream(const Src &s, uint64_t i, int *status, int *stop) {
-    const mhb::DecBatchParams &b = s.b;
-    bool bad = (i == 0 && b.pay_off[0] != 0) || (i == b.n && b.pay_off[b.n] != b.pay_total) || (i < b.n && b.pay_off[i + 1] < b.pay_off[i]);
-    if (b.index)
-        bad |= (i == 0 && b.sym_off[0] != 0) || (i == b.n && b.sym_off[b.n] != b.sym_total) || (i < b.n && b.sym_off[i + 1] < b.sym_off[i]);
-    if (bad) { fail(status, BATCH_STATUS_ARG); atomicExch(stop, 1); }
-    if (i == b.n) return bad;
-    b.stream_status[i] = MH_OK;
-    if (!bad && b.nbits[i] > (b.pay_off[i + 1] - b.pay_off[i]) * 8u) stream_fail(s, status, i, MH_ERR_ARG, BATCH_STATUS_ARG);
-    return bad;
-}
-
 // the context in front of a stream's first symbol: (prev0, prev0)
 template <bool S2> __device__ __forceinline__ uint32_t start16(const Src &s) { return S2 ? s.b.prev0 : ((s.b.prev0 & 0xFFu) * 0x101u); }
 
-// chunk w of the indexed batch: its stream, symbols, bit span and the context its lane starts in; false when w is a gap.
-// Order-0/1 source: c16's high byte is known only in a stream's first chunk (prev0), elsewhere the lane does not own symbol 0.
-struct Chunk {
-    uint64_t i, ni, first, nb, start, end;
-    uint32_t nsym, c16;
-    bool last;
-    __device__ __forceinline__ bool entry_ok() const { return start <= end && end <= nb; }
-};
+// chunk w of the indexed batch with its entry's context widened to the 16 bits the lane starts in; false when w is a gap.
+// Order-0/1 source: the high byte is known only in a stream's first chunk (prev0), elsewhere the lane does not own symbol 0.
 template <bool S2>
 __device__ __forceinline__ bool chunk_of(const Src &s, uint64_t w, Chunk &c) {
-    const mhb::DecBatchParams &b = s.b;
-    const uint32_t cs = b.chunk_shift;
-    const uint64_t pos = S2 ? mhk::IDX2_POS : MH_INDEX_BIT_MASK;
-    c.i = find_stream(b.sym_off, b.n, cs, w);
-    if (c.i >= b.n) return false;
-    const uint64_t a = b.sym_off[c.i];
-    c.ni = b.sym_off[c.i + 1] - a;
-    c.first = (w - ((a >> cs) + c.i)) << cs;
-    if (c.first >= c.ni) return false;
-    c.nb = b.nbits[c.i];
-    const uint64_t e = b.index[w];
-    c.start = e & pos;
-    c.c16 = S2 ? uint32_t(e >> 48) : (uint32_t(e >> 56) | (c.first ? 0u : (b.prev0 & 0xFFu) << 8));
-    c.last = c.first + (uint64_t(1) << cs) >= c.ni;
-    c.end = c.last ? c.nb : (b.index[w + 1] & pos);
-    c.nsym = uint32_t(c.last ? c.ni - c.first : (uint64_t(1) << cs));
+    if (!mhb::chunk_of<S2>(s.b, w, c)) return false;
+    if (!S2) c.ctx |= c.first ? 0u : (s.b.prev0 & 0xFFu) << 8;
     return true;
 }
 // symbol t of chunk c belongs to c's lane (else to the lane of the chunk in front, which knows both context bytes)
@@ -208,7 +173,7 @@ __device__ __forceinline__ uint32_t walk_chunk(const Src &s, const Dec<S2> &dec,
     const BitSrc src = mhb::stream_src(s.b.payload, s.b.pay_off[c.i], c.nb, bit0);
     BitCursor bc;
     bc.init(src, bit0 + c.start);
-    uint32_t c16 = c.c16, t = 0;
+    uint32_t c16 = c.ctx, t = 0;
     used = 0; bad = false;
     for (; t < count; ++t) {
         const uint32_t sym = dec.next(src, bc, c16, used, bad);
@@ -242,11 +207,11 @@ __global__ __launch_bounds__(nt_of<S2>()) void histc2_idx_kernel(Hist2Params p, 
             uint32_t used; bool bad;
             if (!FIX && verdict != MH_ERR_ARG) {
                 if (!c.entry_ok()) {
-                    stream_fail(p.s, status, c.i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT);
+                    stream_fail(p.s.b, status, c.i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT);
                 } else {
                     const uint32_t done = walk_chunk<S2>(p.s, dec, c, c.nsym, true, 1, kc, used, bad);
                     if (bad || used != c.end - c.start) {           // (the extra symbol was not counted)
-                        stream_fail(p.s, status, c.i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT);
+                        stream_fail(p.s.b, status, c.i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT);
                         walk_chunk<S2>(p.s, dec, c, done, false, -1, kc, used, bad);
                     }
                 }
@@ -295,12 +260,12 @@ __global__ __launch_bounds__(nt_of<S2>()) void histc2_walk_kernel(Hist2Params p,
         if (i < n && p.s.b.stream_status[i] == MH_OK) {
             const uint64_t nb = p.s.b.nbits[i];
             if (nb > p.s.b.walk_max_bits) {
-                stream_fail(p.s, status, i, MH_ERR_ARG, BATCH_STATUS_ARG);
+                stream_fail(p.s.b, status, i, MH_ERR_ARG, BATCH_STATUS_ARG);
             } else {
                 uint32_t used; bool bad;
                 const uint64_t done = walk_stream<S2>(p.s, dec, i, nb, ~uint64_t(0), 1, kc, used, bad);
                 if (bad || used != nb) {                            // the stream ends exactly at nbits
-                    stream_fail(p.s, status, i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT);
+                    stream_fail(p.s.b, status, i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT);
                     walk_stream<S2>(p.s, dec, i, nb, done, -1, kc, used, bad);
                 }
             }
@@ -309,26 +274,7 @@ __global__ __launch_bounds__(nt_of<S2>()) void histc2_walk_kernel(Hist2Params p,
     kc.flush();
 }
 
-__global__ __launch_bounds__(256) void histc2_check_kernel(Hist2Params p, int *status, int *stop) {
-    const uint64_t i = gtid();
-    if (i > p.s.b.n) return;
-    check_stream(p.s, i, status, stop);
-}
-
 // ------------------------------------------------------------------------------------------------ re-code
-
-__global__ __launch_bounds__(256) void recode2_check_kernel(Recode2Params p, int *status, int *stop) {
-    const uint64_t i = gtid();
-    const uint64_t n = p.s.b.n;
-    if (i > n) return;
-    p.out_off[i] = 0;
-    if (!p.s.b.index) p.s.b.sym_off[i] = 0;
-    if (i < n) {
-        p.out_nbits[i] = 0;
-        if (p.dropped) p.dropped[i] = 0;
-    }
-    check_stream(p.s, i, status, stop);
-}
 
 template <bool S2>
 __global__ __launch_bounds__(nt_of<S2>()) void recode2_idx_len_kernel(Recode2Params p, uint64_t nwork, unsigned long long *cbits, uint32_t *cdrop,
@@ -340,12 +286,12 @@ __global__ __launch_bounds__(nt_of<S2>()) void recode2_idx_len_kernel(Recode2Par
     for (uint64_t w = gtid(); w < nwork; w += uint64_t(gridDim.x) * blockDim.x) {
         Chunk c;
         if (!chunk_of<S2>(p.s, w, c) || p.s.b.stream_status[c.i] == MH_ERR_ARG) continue;
-        if (!c.entry_ok()) { stream_fail(p.s, status, c.i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT); continue; }
+        if (!c.entry_ok()) { stream_fail(p.s.b, status, c.i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT); continue; }
         uint64_t bit0;
         const BitSrc src = mhb::stream_src(p.s.b.payload, p.s.b.pay_off[c.i], c.nb, bit0);
         BitCursor bc;
         bc.init(src, bit0 + c.start);
-        uint32_t c16 = c.c16, used = 0, bits = 0, drops = 0;
+        uint32_t c16 = c.ctx, used = 0, bits = 0, drops = 0;
         bool bad = false;
         for (uint32_t t = 0; t < c.nsym && !bad; ++t) {
             const uint32_t sym = dec.next(src, bc, c16, used, bad);
@@ -357,7 +303,7 @@ __global__ __launch_bounds__(nt_of<S2>()) void recode2_idx_len_kernel(Recode2Par
             }
             c16 = roll(c16, sym);
         }
-        if (bad || used != c.end - c.start) { stream_fail(p.s, status, c.i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT); continue; }
+        if (bad || used != c.end - c.start) { stream_fail(p.s.b, status, c.i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT); continue; }
         if (!S2 && !c.last) {
             // the next chunk's first symbol, whose two context bytes only this lane knows.  No verdict: when the stream
             // passes, the next chunk's lane decoded the same bits in the same context.
@@ -401,45 +347,6 @@ __global__ __launch_bounds__(256) void recode2_comb_kernel(Recode2Params p, uint
     cbits[w] = v;
 }
 
-// stream i: payload bits (indexed: from the scanned chunk bits; index-free: the count pass wrote them), bytes into out_off
-__global__ __launch_bounds__(256) void recode2_sizes_kernel(Recode2Params p, const unsigned long long *cbase, const int *stop) {
-    if (stopped(stop)) return;
-    const uint64_t i = gtid();
-    const uint64_t n = p.s.b.n;
-    if (i > n) return;
-    if (i == n) { p.out_off[i] = 0; return; }
-    unsigned long long bits;
-    if (p.s.b.index) {
-        const uint32_t cs = p.s.b.chunk_shift;
-        const uint64_t w0 = (p.s.b.sym_off[i] >> cs) + i, w1 = (p.s.b.sym_off[i + 1] >> cs) + i + 1;
-        bits = cbase[w1] - cbase[w0];
-        p.out_nbits[i] = bits;
-    } else {
-        bits = p.out_nbits[i];
-    }
-    p.out_off[i] = (bits + 7) >> 3;
-}
-
-// index-free: the destination index was sized from sym_total; more symbols than that do not fit it
-__global__ void recode2_cap_kernel(Recode2Params p, int *status, int *stop) {
-    if (stopped(stop)) return;
-    if (p.s.b.sym_off[p.s.b.n] > p.s.b.sym_total) { fail(status, mhk::MHK_STATUS_CAPACITY); atomicExch(stop, 1); }
-}
-
-// zeroes the payload bytes (codes are OR-ed into shared edge dwords) or reports that they do not fit
-__global__ __launch_bounds__(256) void recode2_zero_kernel(Recode2Params p, int *status, int *stop, uint32_t *tail) {
-    if (stopped(stop)) return;
-    const uint64_t bytes = p.out_off[p.s.b.n];
-    if (bytes > p.cap) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) { fail(status, mhk::MHK_STATUS_CAPACITY); atomicExch(stop, 1); }
-        return;
-    }
-    const uint64_t nfull = bytes >> 2;
-    uint32_t *o = reinterpret_cast<uint32_t *>(p.out);
-    for (uint64_t k = gtid(); k < nfull; k += uint64_t(gridDim.x) * blockDim.x) o[k] = 0u;
-    if (blockIdx.x == 0 && threadIdx.x == 0) *tail = 0u;
-}
-
 template <bool S2>
 __global__ __launch_bounds__(nt_of<S2>()) void recode2_idx_emit_kernel(Recode2Params p, uint64_t nwork, const unsigned long long *cbase,
                                                                        const uint32_t *chead, const uint32_t *cclose, uint32_t *tail,
@@ -457,7 +364,7 @@ __global__ __launch_bounds__(nt_of<S2>()) void recode2_idx_emit_kernel(Recode2Pa
         const unsigned long long b0 = cbase[w];
         const uint64_t rel = b0 - cbase[(p.s.b.sym_off[c.i] >> cs) + c.i];          // relative to the stream's own payload
         const bool seam = !S2 && c.first != 0u;                                     // symbol 0 is the lane's in front
-        if (p.out_index) p.out_index[w] = E.entry(seam ? cclose[w - 1] : c.c16, rel);
+        if (p.out_index) p.out_index[w] = E.entry(seam ? cclose[w - 1] : c.ctx, rel);
         if (!p.out) continue;
         uint64_t bit0;
         const BitSrc src = mhb::stream_src(p.s.b.payload, p.s.b.pay_off[c.i], c.nb, bit0);
@@ -465,7 +372,7 @@ __global__ __launch_bounds__(nt_of<S2>()) void recode2_idx_emit_kernel(Recode2Pa
         bc.init(src, bit0 + c.start);
         BitWriter bw;
         bw.init(reinterpret_cast<uint32_t *>(p.out), tail, tail_w, uint64_t(p.out_off[c.i]) * 8u + rel + (seam ? chead[w - 1] : 0u));
-        uint32_t c16 = c.c16, used = 0, l;
+        uint32_t c16 = c.ctx, used = 0, l;
         uint64_t code;
         bool bad = false, any = false;
         for (uint32_t t = 0; t < c.nsym && !bad; ++t) {            // (the stream passed: bad stays false)
@@ -506,7 +413,7 @@ __global__ __launch_bounds__(nt_of<S2>()) void recode2_walk_kernel(Recode2Params
             count = p.s.b.sym_off[i + 1] - a;
             if (!count) continue;
         } else if (nb > p.s.b.walk_max_bits) {
-            stream_fail(p.s, status, i, MH_ERR_ARG, BATCH_STATUS_ARG);
+            stream_fail(p.s.b, status, i, MH_ERR_ARG, BATCH_STATUS_ARG);
             continue;
         }
         uint64_t bit0;
@@ -538,31 +445,18 @@ __global__ __launch_bounds__(nt_of<S2>()) void recode2_walk_kernel(Recode2Params
             ++k;
         }
         if (EMIT) { if (p.out && bits) bw.finish(); continue; }
-        if (bad || used != nb) { stream_fail(p.s, status, i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT); continue; }
+        if (bad || used != nb) { stream_fail(p.s.b, status, i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT); continue; }
         p.s.b.sym_off[i] = k;                                       // the stream ends exactly at nbits
         p.out_nbits[i] = bits;
         if (p.dropped) p.dropped[i] = drops;
     }
 }
 
-__global__ void recode2_tail_kernel(Recode2Params p, const uint32_t *tail, const int *stop) {
-    if (stopped(stop)) return;
-    const uint64_t bytes = p.out_off[p.s.b.n];
-    if (!(bytes & 3u)) return;
-    const uint8_t *t = reinterpret_cast<const uint8_t *>(tail);
-    for (uint64_t b = bytes & ~uint64_t(3); b < bytes; ++b) p.out[b] = t[b & 3u];
-}
-
-// LDS of an order-0/1 source model's tables, as launch_decode_batch places them
-inline size_t tables_lds(const mhb::DecBatchParams &b) {
-    return 1024 + (size_t(256) << b.P) * 2 + (b.sec_lds ? ((size_t(b.nsec) * 2 + 15) & ~size_t(15)) : 0);
-}
-
 template <bool S2>
 hipError_t launch_hist(const Hist2Params &p, void *d_ws, hipStream_t st) {
     constexpr int NT = nt_of<S2>();
     constexpr int PER_CU = S2 ? 8 : 1;
-    const size_t lds_tables = S2 ? 0 : tables_lds(p.s.b);
+    const size_t lds_tables = S2 ? 0 : mhb::tables_lds(p.s.b);
     if (lds_tables > size_t(LDS_MAX)) return hipErrorInvalidValue;
     // the counters take what the tables leave, 12 bytes a slot: 256 .. 4096 slots (order-2 source, eight workgroups per
     // CU: 1024), or none
@@ -585,9 +479,9 @@ hipError_t launch_hist(const Hist2Params &p, void *d_ws, hipStream_t st) {
     hipError_t e = hipMemsetAsync(ws, 0, 64, st);
     if (e == hipSuccess) e = hipMemsetAsync(p.counts, 0, ncounts * sizeof(unsigned long long), st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(histc2_check_kernel, grid_threads(n + 1, 256), dim3(256), 0, st, p, status, stop);
+    hipLaunchKernelGGL(histc_check_kernel, grid_threads(n + 1, 256), dim3(256), 0, st, p.s, status, stop);
     if (p.s.b.index) {
-        const uint64_t W = p.s.b.sym_total / (uint64_t(1) << p.s.b.chunk_shift) + n + 1;
+        const uint64_t W = mhb::work_items(n, p.s.b.sym_total, 1u << p.s.b.chunk_shift);
         hipLaunchKernelGGL((histc2_idx_kernel<S2, false>), dim3(grid_for(W, NT, PER_CU)), dim3(NT), lds, st, p, W, lds_at, log2n, status, stop);
         hipLaunchKernelGGL((histc2_idx_kernel<S2, true>), dim3(grid_for(W, NT, PER_CU)), dim3(NT), lds, st, p, W, lds_at, log2n, status, stop);
         return hipGetLastError();
@@ -600,7 +494,7 @@ template <bool S2>
 hipError_t launch_rc(const Recode2Params &p, void *d_ws, hipStream_t st) {
     constexpr int NT = nt_of<S2>();
     constexpr int PER_CU = S2 ? 8 : 1;
-    const size_t lds = S2 ? 0 : tables_lds(p.s.b);
+    const size_t lds = S2 ? 0 : mhb::tables_lds(p.s.b);
     if (lds > size_t(LDS_MAX)) return hipErrorInvalidValue;
     if (!S2) {
         hipError_t attr = mhk::allow_lds(reinterpret_cast<const void *>(recode2_idx_len_kernel<S2>), LDS_MAX);
@@ -611,7 +505,7 @@ hipError_t launch_rc(const Recode2Params &p, void *d_ws, hipStream_t st) {
     }
     unsigned char *ws = static_cast<unsigned char *>(d_ws);
     const uint64_t n = p.s.b.n;
-    const uint64_t W = p.s.b.index ? p.s.b.sym_total / (uint64_t(1) << p.s.b.chunk_shift) + n + 1 : 0;
+    const uint64_t W = p.s.b.index ? mhb::work_items(n, p.s.b.sym_total, 1u << p.s.b.chunk_shift) : 0;
     const Recode2Layout L = recode2_layout(n, W);
     int *status = reinterpret_cast<int *>(ws), *stop = status + 1;
     uint32_t *tail = reinterpret_cast<uint32_t *>(ws + TAIL_AT);
@@ -623,7 +517,7 @@ hipError_t launch_rc(const Recode2Params &p, void *d_ws, hipStream_t st) {
     hipError_t e = hipMemsetAsync(ws, 0, 64, st);
     if (e == hipSuccess && W) e = hipMemsetAsync(ws + L.off_bits, 0, L.off_sums - L.off_bits, st);    // chunk bits, dropped counts, heads
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(recode2_check_kernel, grid_threads(n + 1, 256), dim3(256), 0, st, p, status, stop);
+    hipLaunchKernelGGL(recode_check_kernel, grid_threads(n + 1, 256), dim3(256), 0, st, p, status, stop);
     if (p.s.b.index) {
         hipLaunchKernelGGL((recode2_idx_len_kernel<S2>), dim3(grid_for(W, NT, PER_CU)), dim3(NT), lds, st, p, W, cbits, cdrop, chead, cclose,
                            status, stop);
@@ -633,10 +527,10 @@ hipError_t launch_rc(const Recode2Params &p, void *d_ws, hipStream_t st) {
         hipLaunchKernelGGL((recode2_walk_kernel<S2, false>), dim3(grid_for(n + 1, NT, PER_CU)), dim3(NT), lds, st, p, tail, status, stop);
         if ((e = scan_exclusive(p.s.b.sym_off, n + 1, sums, stop, st)) != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(recode2_sizes_kernel, grid_threads(n + 1, 256), dim3(256), 0, st, p, cbits, stop);
+    hipLaunchKernelGGL(recode_sizes_kernel, grid_threads(n + 1, 256), dim3(256), 0, st, p, cbits, stop);
     if ((e = scan_exclusive(p.out_off, n + 1, sums, stop, st)) != hipSuccess) return e;
-    if (!p.s.b.index && p.out_index) hipLaunchKernelGGL(recode2_cap_kernel, dim3(1), dim3(1), 0, st, p, status, stop);
-    if (p.out) hipLaunchKernelGGL(recode2_zero_kernel, dim3(grid_for(p.cap / 4 + 1, 256, 8)), dim3(256), 0, st, p, status, stop, tail);
+    if (!p.s.b.index && p.out_index) hipLaunchKernelGGL(recode_cap_kernel, dim3(1), dim3(1), 0, st, p, status, stop);
+    if (p.out) hipLaunchKernelGGL(recode_zero_kernel, dim3(grid_for(p.cap / 4 + 1, 256, 8)), dim3(256), 0, st, p, status, stop, tail);
     if (p.s.b.index) {
         if (p.out || p.out_index)
             hipLaunchKernelGGL((recode2_idx_emit_kernel<S2>), dim3(grid_for(W, NT, PER_CU)), dim3(NT), lds, st, p, W, cbits, chead, cclose, tail,
@@ -644,7 +538,7 @@ hipError_t launch_rc(const Recode2Params &p, void *d_ws, hipStream_t st) {
     } else if (p.out || p.out_index) {
         hipLaunchKernelGGL((recode2_walk_kernel<S2, true>), dim3(grid_for(n + 1, NT, PER_CU)), dim3(NT), lds, st, p, tail, status, stop);
     }
-    if (p.out) hipLaunchKernelGGL(recode2_tail_kernel, dim3(1), dim3(1), 0, st, p, tail, stop);
+    if (p.out) hipLaunchKernelGGL(recode_tail_kernel, dim3(1), dim3(1), 0, st, p, tail, stop);
     return hipGetLastError();
 }
 

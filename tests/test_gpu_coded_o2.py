@@ -137,6 +137,60 @@ def test_search_equals_reference(mhc, world, name):
         assert all(bytes(o) == NEEDLE for o in outs)
 
 
+def check_all_ways_o2(mhc, msgs, chunk, patterns, hits, what=""):
+    """test_gpu_find.check_all_ways for order 2: the messages coded by mh_encode_batch_o2 (the host form over
+    mh_dev_encode_batch_o2) under an order-2 model trained on them; mh_dev_find_batch_o2 indexed and index-free,
+    count-only and with records, against the reference's hits."""
+    w = World(mhc, msgs)
+    ps = mhc.PatternSet(patterns)
+    off, wrec, wpat = find_ref.hit_arrays(hits, w.n)
+    for indexed in (True, False):
+        src, kw = w.kw(2, chunk, indexed)
+        tag = (what, chunk, indexed)
+        ho, rec, pat, st, rc = w.model[2].dev_find_batch_o2(ps, *src, count_only=True, **kw)
+        assert rc == mhc.MH_OK and (st == mhc.MH_OK).all() and np.array_equal(ho, off) and rec.size == 0, tag
+        ho, rec, pat, st, rc = w.model[2].dev_find_batch_o2(ps, *src, **kw)
+        assert rc == mhc.MH_OK and (st == mhc.MH_OK).all(), (tag, rc, np.unique(st))
+        assert np.array_equal(ho, off) and np.array_equal(rec, wrec) and np.array_equal(pat, wpat), tag
+
+
+@pytest.mark.parametrize("chunk", CHUNKS)
+def test_seams_64_byte_pattern_at_every_offset_behind_a_boundary(mhc, chunk):
+    """The order-2 counterpart of test_gpu_find's test: the seam rule (a hit spans at most two chunks, the tail takes no
+    new starts) at the smallest shape where it can go wrong, a 64-position automaton against chunks of 256 symbols."""
+    pattern = bytes(range(1, 65))
+    assert len(pattern) == mhc.FIND_MAX_POSITIONS
+    msgs = []
+    for k in range(64):                                        # the pattern ends k bytes behind every chunk boundary
+        m = bytearray(b"\xee" * 5000)
+        for edge in range(chunk, 5000 - 64, chunk):
+            m[edge + k - 64:edge + k] = pattern
+        msgs.append(bytes(m))
+    hits = find_ref.find_hits(msgs, [pattern])
+    per = len(range(chunk, 5000 - 64, chunk))
+    assert len(hits) == 64 * per and find_ref.straddles(hits, chunk) == 63 * per
+    check_all_ways_o2(mhc, msgs, chunk, [pattern], hits, what="seams")
+
+
+@pytest.mark.parametrize("chunk", CHUNKS)
+def test_seams_suffix_patterns_and_runs(mhc, chunk):
+    """The order-2 counterpart of test_gpu_find's test: a pattern, its suffixes and a duplicate end at the same symbol, on
+    both sides of a seam; a run of one byte matches at every position."""
+    rng = np.random.default_rng(5)
+    text = bytes(rng.choice(np.frombuffer(b"abcx", dtype=np.uint8), size=6000))
+    pats = [b"abcab", b"cab", b"b", b"abcab", b"ab"]          # a pattern, its suffixes, a duplicate: equal ends, all pattern numbers
+    msgs = [text, b"a" * 300, text[::-1], b"abcab" * 700]
+    hits = find_ref.find_hits(msgs, pats)
+    ends = {}
+    for i, _, e, j in hits:
+        ends.setdefault((i, e), []).append(j)
+    assert any(len(v) >= 4 for v in ends.values()) and find_ref.straddles(hits, chunk) >= 5
+    check_all_ways_o2(mhc, msgs, chunk, pats, hits, what="suffixes")
+    run = find_ref.find_hits(msgs, [b"aaaa"])
+    assert len([h for h in run if h[0] == 1]) == 297
+    check_all_ways_o2(mhc, msgs, chunk, [b"aaaa"], run, what="aaaa")
+
+
 # ---------------------------------------------------------------------------------------------------- re-code
 
 def check_recode(mhc, w, so, do, dst=None, what=""):
