@@ -426,7 +426,8 @@ int mh_dev_build_index(const mh_model *m, const uint8_t *d_payload, uint64_t nbi
                        uint64_t *d_index, uint64_t index_cap, uint32_t chunk_symbols,
                        uint64_t *d_n_symbols, void *d_ws, size_t ws_bytes, void *stream);
 /* mh_dev_build_index that also fills the fine index (see above) of the stream: d_fine[fine_cap], one entry per 64
- * symbols (nbits / 64 + 2 entries always suffice: a code has at least one bit). */
+ * symbols (nbits / 64 + 2 entries always suffice: a code has at least one bit).  Synchronises `stream` as mh_dev_build_index
+ * does. */
 int mh_dev_build_index_fine(const mh_model *m, const uint8_t *d_payload, uint64_t nbits, uint8_t prev0,
                             uint64_t *d_index, uint64_t index_cap, uint32_t chunk_symbols,
                             uint32_t *d_fine, uint64_t fine_cap,
@@ -457,7 +458,8 @@ int mh_dev_decode_stream_emit(const mh_model *m, const uint8_t *d_payload, uint6
                               uint8_t *d_out, uint64_t out_cap, void *d_ws, size_t ws_bytes, void *stream);
 /* Diagnostic: how the last mh_dev_build_index on this workspace arrived at the index — 1 the segment iteration
  * converged, 2 per-group context maps (fixed-length codes), 3 per-group state maps (mixed lengths), 4 the one-lane
- * walk, 0 nothing ran.  Synchronises `stream`. */
+ * walk, 5 the tile decoder's segment states (the fast path: a model with tile tables, a stream of a megabit or more), 0 nothing
+ * ran.  Synchronises `stream`. */
 int mh_dev_index_path(const void *d_ws, void *stream);
 /* Diagnostic: which encoder the last mh_dev_encode* call on this workspace ran — 1 the region encoder (priced from a
  * histogram of the input, one read), 3 the same with its escape variant launched too (model with codes over 12

@@ -321,13 +321,73 @@ def _ptr(a):
     return a.ctypes.data if a.size else None
 
 
+class _DeviceMemory:
+    """The process-wide allocation mode of DeviceBuffer (device_memory below).  `served` / `missed`: the requests without
+    `init` that the recycle pool did / did not serve."""
+
+    def __init__(self):
+        self.mode, self.byte, self.pool, self.served, self.missed = None, 0, [], 0, 0
+
+    def take(self, nbytes):
+        """Best fit: the smallest pooled block of at least nbytes as (address, block size), or None."""
+        fit = [k for k, (cap, _) in enumerate(self.pool) if cap >= nbytes]
+        if not fit:
+            return None
+        cap, addr = self.pool.pop(min(fit, key=lambda k: self.pool[k][0]))
+        return addr, cap
+
+    def drain(self):
+        while self.pool:
+            _lib.mh_dev_free(C.c_void_p(self.pool.pop()[1]))
+
+
+_memory = _DeviceMemory()
+
+
+class device_memory:
+    """Context manager of DeviceBuffer's allocation mode, for tests of dirty and reused workspaces and outputs (process-wide,
+    not nested; outside it DeviceBuffer is a plain hipMalloc / hipFree):
+      device_memory("fill", byte)   every buffer created without `init` is filled with `byte` before it is handed out;
+      device_memory("recycle")      freed buffers go to a pool that is never cleared, a request takes the smallest pooled block
+                                    of at least its size and keeps the block's contents (`init`, when given, is uploaded over its
+                                    front); leaving the mode frees the pool.
+    `with` yields the mode's state: .served / .missed count the requests without `init` that the pool did / did not serve."""
+
+    def __init__(self, mode, byte=0):
+        if mode not in ("fill", "recycle"):
+            raise ValueError("device_memory mode")
+        self.mode, self.byte = mode, byte
+
+    def __enter__(self):
+        if _memory.mode is not None:
+            raise RuntimeError("device_memory does not nest")
+        lib()
+        _memory.mode, _memory.byte, _memory.served, _memory.missed = self.mode, self.byte, 0, 0
+        return _memory
+
+    def __exit__(self, *exc):
+        _memory.mode = None
+        _memory.drain()
+        return False
+
+
 class DeviceBuffer:
-    """A hipMalloc'ed buffer (for tests that drive the mh_dev_* calls without torch)."""
+    """A hipMalloc'ed buffer (for tests that drive the mh_dev_* calls without torch).  Without `init` its contents are
+    whatever the allocator returned, or what device_memory arranges."""
 
     def __init__(self, nbytes, init=None):
-        self.nbytes = nbytes
+        self.nbytes = self.block = nbytes
         self.ptr = C.c_void_p()
-        _check(lib().mh_dev_malloc(C.byref(self.ptr), nbytes), "mh_dev_malloc")
+        got = _memory.take(nbytes) if _memory.mode == "recycle" else None
+        if _memory.mode == "recycle" and init is None:
+            _memory.served += got is not None
+            _memory.missed += got is None
+        if got is not None:
+            self.ptr.value, self.block = got
+        else:
+            _check(lib().mh_dev_malloc(C.byref(self.ptr), nbytes), "mh_dev_malloc")
+        if init is None and _memory.mode == "fill":
+            init = np.full(nbytes, _memory.byte, dtype=np.uint8)
         if init is not None:
             a = np.ascontiguousarray(init)
             _check(lib().mh_dev_upload(self.ptr, a.ctypes.data, a.nbytes), "mh_dev_upload")
@@ -339,7 +399,10 @@ class DeviceBuffer:
 
     def __del__(self):
         if getattr(self, "ptr", None) and _lib is not None:
-            _lib.mh_dev_free(self.ptr)
+            if _memory.mode == "recycle":
+                _memory.pool.append((self.block, self.ptr.value))
+            else:
+                _lib.mh_dev_free(self.ptr)
             self.ptr = None
 
 
@@ -1352,7 +1415,8 @@ class ModelSet:
         d_oo, d_nb = DeviceBuffer((n + 1) * 8), DeviceBuffer(max(n, 1) * 8)
         d_idx = None
         if chunk_symbols:
-            d_idx = DeviceBuffer(max(l.mh_batch_index_capacity(total, n, chunk_symbols), 1) * 8)
+            nidx = max(l.mh_batch_index_capacity(total, n, chunk_symbols), 1)
+            d_idx = DeviceBuffer(nidx * 8, np.zeros(nidx, dtype=np.uint64))       # (gap entries are left untouched: mh.h)
         wsb = l.mh_dev_encode_each_workspace(n, total)
         d_ws = DeviceBuffer(wsb)
         _check(l.mh_dev_encode_each(self._h, d_data.ptr, d_in.ptr, n, total, prev0, d_out.ptr, cap, d_oo.ptr, d_nb.ptr,

@@ -229,12 +229,25 @@ class Rig:
         self.check(not st.any() and out == self.joined, "decode_bank indexed")
 
 
+    # ---- all of them ----
+    @staticmethod
+    def eligible(case):
+        """Whether a case runs the per-stream-model and bank families (sets are order 0 / 1; a set grows with its streams)."""
+        return 2 not in case.orders and case.n_streams <= 65
+
+    def families(self):
+        """Every family that runs for this case, in order."""
+        fams = [self.encode, self.decode, self.lookups, self.search_and_feed_back, self.coded_histogram, self.recode]
+        return fams + [self.each, self.bank] if self.eligible(self.case) else fams
+
+    def run_all(self):
+        for fn in self.families():
+            self.family(fn)
+        return self.bad
+
+
 @pytest.mark.parametrize("case", CASES, ids=[c.id for c in CASES])
 def test_every_batch_call_equals_the_references(mhc, case):
     rig = Rig(mhc, case)
-    families = [rig.encode, rig.decode, rig.lookups, rig.search_and_feed_back, rig.coded_histogram, rig.recode]
-    if 2 not in case.orders and case.n_streams <= 65:
-        families += [rig.each, rig.bank]
-    for fn in families:
-        rig.family(fn)
+    rig.run_all()
     assert not rig.bad, "%s: %d differences:\n  %s" % (case.id, len(rig.bad), "\n  ".join(rig.bad))
