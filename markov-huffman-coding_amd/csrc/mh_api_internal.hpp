@@ -224,7 +224,7 @@ int encode_batch_host(const mh_model *m, const uint8_t *data, const uint64_t *in
 int decode_batch_host(const mh_model *m, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits, size_t n_streams, uint8_t prev0,
                       uint8_t *out, size_t out_cap, uint64_t *sym_off, const uint64_t *index, uint32_t chunk_symbols, int32_t *stream_status,
                       DevDecodeBatchFn dev);
-// mh_api_coded_o2.cpp: an index-free order-2 stream over the walk cap, decoded alone (out: its bytes, empty unless MH_OK)
+// mh_api_recode.cpp: an index-free order-2 stream over the walk cap, decoded alone (out: its bytes, empty unless MH_OK)
 int decode_alone(const mh_model *m, const uint8_t *payload, uint64_t nbits, uint8_t prev0, std::vector<uint8_t> &out);
 // mh_api_each.cpp: MH_OK when mh_model_set_from_tables accepts the table file t[nb] (host only), else its error
 int check_table(const uint8_t *t, size_t nb);

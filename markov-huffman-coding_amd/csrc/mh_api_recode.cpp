@@ -1,6 +1,7 @@
-// mh_api_recode.cpp — the re-coding calls of the C ABI (include/mh.h, "RE-CODING BATCHES"): the training histogram of a
-// compressed batch and the batch coded again under another model, under one shared source model or a model set (kernels:
-// mh_recode.hip), and the host-buffer form.
+// mh_api_recode.cpp — the re-coding calls of the C ABI (include/mh.h, "RE-CODING BATCHES" and the re-coding part of "ORDER 2
+// IN SEARCH AND RE-CODING"): the training histogram of a compressed batch and the batch coded again under another model,
+// under one shared source model of any order or a model set (kernels: mh_recode.hip), and the host-buffer forms.  The order
+// rules of an entry point are in that entry point; everything behind them is here once.
 #include "mh_api_internal.hpp"
 #include "mh_batch.h"
 #include "mh_recode.h"
@@ -9,14 +10,16 @@ using namespace mhapi;
 
 namespace {
 
-// the source batch, checked in the order of mh_dev_decode_batch; sym_off is written by an index-free re-code
-int source(const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits, size_t n_streams, uint64_t pay_total, uint8_t prev0,
-           const uint64_t *d_sym_off, uint64_t sym_total, const uint64_t *d_index, uint32_t chunk_symbols, const void *d_ws, mhr::Src &s) {
+// the source batch, checked in the order of mh_dev_decode_batch; sym_off is written by an index-free re-code (m: null under a set)
+int source(const mh_model *m, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits, size_t n_streams, uint64_t pay_total,
+           uint8_t prev0, const uint64_t *d_sym_off, uint64_t sym_total, const uint64_t *d_index, uint32_t chunk_symbols, const void *d_ws,
+           mhr::Src &s) {
     if ((!d_payload && pay_total) || !d_pay_off || (!d_nbits && n_streams) || !d_ws) return MH_ERR_ARG;
     if (!aligned16(d_payload) || !aligned16(d_ws)) return MH_ERR_ARG;
     int shift = 0;
     if (d_index && ((shift = chunk_shift_of(chunk_symbols)) < 0 || !d_sym_off)) return MH_ERR_ARG;
-    s.b.payload = d_payload; s.b.pay_off = d_pay_off; s.b.nbits = d_nbits; s.b.n = n_streams; s.b.pay_total = pay_total; s.b.prev0 = prev0;
+    s.b.payload = d_payload; s.b.pay_off = d_pay_off; s.b.nbits = d_nbits; s.b.n = n_streams; s.b.pay_total = pay_total;
+    s.b.prev0 = ctx_of_prev0(m, prev0);
     s.b.sym_off = reinterpret_cast<unsigned long long *>(const_cast<uint64_t *>(d_sym_off));
     s.b.sym_total = sym_total;
     s.b.index = d_index; s.b.chunk_shift = uint32_t(shift);
@@ -24,53 +27,59 @@ int source(const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *
     return MH_OK;
 }
 
-int shared_tables(const mh_model *m, mhr::Src &s) {
+// the source's models: a shared model's decode tables (order 0/1 as mh_dev_decode_batch hands them over, order 2 as
+// mh_dev_decode_batch_o2), or the set
+int source_tables(const mh_model *m, const mh_model_set *set, mhr::Src &s, mhb::Model &model) {
+    if (set) {
+        if (!have_device()) return MH_ERR_NO_DEVICE;
+        s.set = set->d;
+        model = mhb::Model::Set;
+        return MH_OK;
+    }
     if (m->max_len > mh::MAX_CODE_BITS) return MH_ERR_CODE_TOO_LONG;
     if (!m->d_prim || !have_device()) return MH_ERR_NO_DEVICE;
     fill_dec_tables(m, s.b);
+    model = m->type == 2 ? mhb::Model::Shared2 : mhb::Model::Shared;
     return MH_OK;
 }
 
+// behind the order rules of mh_dev_histogram_coded_batch, _each and _batch_o2: m or set is the source
 int histogram_coded(const mh_model *m, const mh_model_set *set, int order, const uint8_t *d_payload, const uint64_t *d_pay_off,
                     const uint64_t *d_nbits, size_t n_streams, uint64_t pay_total, uint8_t prev0, const uint64_t *d_sym_off, uint64_t sym_total,
                     const uint64_t *d_index, uint32_t chunk_symbols, uint64_t *d_counts, int32_t *d_stream_status, void *d_ws, size_t ws_bytes,
                     void *stream) {
-    if (set ? n_streams != set->d.n : !order01(m)) return MH_ERR_ARG;
-    if ((order != 0 && order != 1) || !d_counts) return MH_ERR_ARG;
+    if (!d_counts) return MH_ERR_ARG;
     mhr::HistParams p{};
-    const int rc = source(d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index, chunk_symbols, d_ws, p.s);
+    const int rc = source(m, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index, chunk_symbols, d_ws, p.s);
     if (rc != MH_OK) return rc;
     const mhr::HistLayout L = mhr::hist_layout(n_streams);
     if (ws_bytes < L.total) return MH_ERR_CAPACITY;
     p.s.b.stream_status = d_stream_status ? d_stream_status : reinterpret_cast<int *>(static_cast<unsigned char *>(d_ws) + L.off_status);
     p.order = uint32_t(order);
     p.counts = reinterpret_cast<unsigned long long *>(d_counts);
-    if (set) {
-        if (!have_device()) return MH_ERR_NO_DEVICE;
-        p.s.set = set->d;
-    } else {
-        const int t = shared_tables(m, p.s);
-        if (t != MH_OK) return t;
-    }
-    HIP_TRY(mhr::launch_histogram_coded(p, !set, d_ws, static_cast<hipStream_t>(stream)));
+    mhb::Model model;
+    const int t = source_tables(m, set, p.s, model);
+    if (t != MH_OK) return t;
+    HIP_TRY(mhr::launch_histogram_coded(p, model, d_ws, static_cast<hipStream_t>(stream)));
     return MH_OK;
 }
 
-int recode(const mh_model *m, const mh_model_set *set, const mh_model *dst, const uint8_t *d_payload, const uint64_t *d_pay_off,
+// behind the order rules of mh_dev_recode_batch, _each and _batch_o2: m or set is the source; seam: the workspace of the _o2
+// call, which has room for the seam's arrays
+int recode(const mh_model *m, const mh_model_set *set, const mh_model *dst, bool seam, const uint8_t *d_payload, const uint64_t *d_pay_off,
            const uint64_t *d_nbits, size_t n_streams, uint64_t pay_total, uint8_t prev0, uint64_t *d_sym_off, uint64_t sym_total,
            const uint64_t *d_index, uint32_t chunk_symbols, uint8_t *d_out_payload, size_t cap, uint64_t *d_out_off, uint64_t *d_out_nbits,
            uint64_t *d_out_index, uint64_t *d_dropped, int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
-    if (set ? n_streams != set->d.n : !order01(m)) return MH_ERR_ARG;
-    if (!order01(dst) || !d_out_off || (!d_out_nbits && n_streams)) return MH_ERR_ARG;
+    if (!d_out_off || (!d_out_nbits && n_streams)) return MH_ERR_ARG;
     if (!d_index && !d_sym_off) return MH_ERR_ARG;                    // index-free: the decoded lengths are an output
     mhr::RecodeParams p{};
-    const int rc = source(d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index, chunk_symbols, d_ws, p.s);
+    const int rc = source(m, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index, chunk_symbols, d_ws, p.s);
     if (rc != MH_OK) return rc;
     if (!aligned16(d_out_payload)) return MH_ERR_ARG;
     int oshift = int(p.s.b.chunk_shift);
     if (!d_index && d_out_index && (oshift = chunk_shift_of(chunk_symbols)) < 0) return MH_ERR_ARG;
     const uint64_t W = d_index ? mhb::work_items(n_streams, sym_total, chunk_symbols) : 0;
-    const mhr::RecodeLayout L = mhr::recode_layout(n_streams, W);
+    const mhr::RecodeLayout L = mhr::recode_layout(n_streams, W, seam);
     if (ws_bytes < L.total) return MH_ERR_CAPACITY;
     p.s.b.stream_status = d_stream_status ? d_stream_status : reinterpret_cast<int *>(static_cast<unsigned char *>(d_ws) + L.off_status);
     p.out = d_out_payload; p.cap = d_out_payload ? cap : 0;
@@ -80,35 +89,172 @@ int recode(const mh_model *m, const mh_model_set *set, const mh_model *dst, cons
     p.dropped = reinterpret_cast<unsigned long long *>(d_dropped);
     p.out_chunk_shift = uint32_t(oshift);
     if (dst->max_len > mh::MAX_CODE_BITS) return MH_ERR_CODE_TOO_LONG;
-    if (set) {
-        if (!have_device()) return MH_ERR_NO_DEVICE;
-        p.s.set = set->d;
-    } else {
-        const int t = shared_tables(m, p.s);
-        if (t != MH_OK) return t;
-    }
+    mhb::Model model;
+    const int t = source_tables(m, set, p.s, model);
+    if (t != MH_OK) return t;
     if (!dst->d_len8 || !dst->d_code64) return MH_ERR_NO_DEVICE;
     p.dst.len8 = dst->d_len8;
     p.dst.code64 = reinterpret_cast<const unsigned long long *>(dst->d_code64);
-    p.dst.ctx_mask = dst->type ? 0xFFu : 0u;
-    HIP_TRY(mhr::launch_recode(p, !set, d_ws, static_cast<hipStream_t>(stream)));
+    p.dst.enc64 = dst->type == 2 ? reinterpret_cast<const unsigned long long *>(dst->d_enc64) : nullptr;
+    p.dst.ctx_mask = dst->type == 2 ? 0xFFFFu : (dst->type ? 0xFFu : 0u);
+    HIP_TRY(mhr::launch_recode(p, model, d_ws, static_cast<hipStream_t>(stream)));
     return MH_OK;
 }
 
+size_t recode_workspace(size_t n_streams, uint64_t sym_total, uint32_t chunk_symbols, bool seam) {
+    const uint64_t W = chunk_shift_of(chunk_symbols) >= 0 ? mhb::work_items(n_streams, sym_total, chunk_symbols) : 0;
+    return mhr::recode_layout(n_streams, W, seam).total;
+}
+
+// the argument checks of the two host forms behind their order rules, in the order of mh_decode_batch
+int host_args(const mh_model *src, const mh_model *dst, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits, size_t n_streams,
+              const uint64_t *sym_off, const uint64_t *index, uint32_t chunk_symbols, const uint64_t *out_off, const uint64_t *out_nbits,
+              const uint64_t *out_index) {
+    if (!pay_off || (!nbits && n_streams) || !out_off || (!out_nbits && n_streams) || !sym_off) return MH_ERR_ARG;
+    if ((index || out_index) && chunk_shift_of(chunk_symbols) < 0) return MH_ERR_ARG;
+    if (!offsets_ok(pay_off, n_streams)) return MH_ERR_ARG;
+    if (!payload && pay_off[n_streams]) return MH_ERR_ARG;
+    for (size_t i = 0; i < n_streams; ++i)
+        if (nbits[i] > (pay_off[i + 1] - pay_off[i]) * 8) return MH_ERR_ARG;
+    if (index && !offsets_ok(sym_off, n_streams)) return MH_ERR_ARG;
+    if (!have_device()) return MH_ERR_NO_DEVICE;
+    if (src->max_len > mh::MAX_CODE_BITS || dst->max_len > mh::MAX_CODE_BITS) return MH_ERR_CODE_TOO_LONG;
+    return MH_OK;
+}
+
+// at most this many symbols in the batch: what an index-free call sizes the destination index for
+uint64_t symbol_bound(const mh_model *src, const uint64_t *nbits, size_t n_streams) {
+    const uint64_t minl = uint64_t(src->min_len > 0 ? src->min_len : 1);
+    uint64_t bound = 0;
+    for (size_t i = 0; i < n_streams; ++i) bound += nbits[i] / minl;
+    return bound;
+}
+
+// An index-free batch of an order-0/1 source with a stream over the walk cap: index the batch first (mh_index_batch never
+// refuses a valid stream), then re-code it as an indexed batch; a stream the indexing fails keeps that error (idx_st) and has
+// no symbols, so no payload.
+int index_first(const mh_model *src, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits, size_t n_streams, uint8_t prev0,
+                uint64_t bound, bool keep_chunk, uint32_t &chunk_symbols, uint64_t *sym_off, std::vector<uint64_t> &own_idx,
+                std::vector<int32_t> &idx_st) {
+    if (!keep_chunk) chunk_symbols = MH_CHUNK_DEFAULT;
+    own_idx.assign(size_t(mh_batch_index_capacity(bound, n_streams, chunk_symbols)), 0);
+    idx_st.assign(n_streams, MH_OK);
+    const int rc = mh_index_batch(src, payload, pay_off, nbits, n_streams, prev0, chunk_symbols, sym_off, own_idx.data(), own_idx.size(),
+                                  idx_st.data());
+    return (rc == MH_ERR_HIP || rc == MH_ERR_NO_DEVICE || rc == MH_ERR_NOMEM || rc == MH_ERR_CAPACITY) ? rc : MH_OK;
+}
+
+// One host-form re-code on the device: run() uploads the batch, runs the device call of the family and brings back the
+// verdicts, offsets, lengths and dropped counts; payload() and slices() then bring what the device wrote to wherever the
+// caller wants it.
+struct HostRecode {
+    using DevFn = decltype(&mh_dev_recode_batch);
+    DevBuf d_pl, d_po, d_nb, d_so, d_idx, d_out, d_oo, d_onb, d_oidx, d_drop, d_st, d_ws;
+    std::vector<int32_t> sst;           // per-stream verdicts
+    std::vector<uint64_t> drop;         // per-stream dropped symbols
+    size_t noidx = 0, dcap = 0;         // entries of the destination index, bytes of the payload buffer
+    int dev_rc = MH_OK;
+
+    int run(DevFn dev, bool seam, const mh_model *src, const mh_model *dst, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits,
+            size_t n_streams, uint8_t prev0, uint64_t *sym_off, uint64_t sym_total, const uint64_t *index, uint32_t chunk_symbols,
+            bool want_payload, size_t cap, uint64_t *out_off, uint64_t *out_nbits, const uint64_t *out_index) {
+        const hipStream_t st = nullptr;
+        const uint64_t pay_total = pay_off[n_streams];
+        const size_t nidx = index ? size_t(mh_batch_index_capacity(sym_total, n_streams, chunk_symbols)) : 0;
+        noidx = out_index ? size_t(mh_batch_index_capacity(sym_total, n_streams, chunk_symbols)) : 0;
+        const size_t wsb = recode_workspace(n_streams, sym_total, index ? chunk_symbols : 0, seam);
+        dcap = want_payload ? cap : 0;
+        HIP_TRY(d_pl.alloc(size_t(pay_total) + 64));
+        HIP_TRY(d_po.alloc((n_streams + 1) * 8));
+        HIP_TRY(d_nb.alloc(n_streams * 8));
+        HIP_TRY(d_so.alloc((n_streams + 1) * 8));
+        HIP_TRY(d_idx.alloc(nidx * 8));
+        HIP_TRY(d_out.alloc(dcap));
+        HIP_TRY(d_oo.alloc((n_streams + 1) * 8));
+        HIP_TRY(d_onb.alloc(n_streams * 8));
+        HIP_TRY(d_oidx.alloc(noidx * 8));
+        HIP_TRY(d_drop.alloc(n_streams * 8));
+        HIP_TRY(d_st.alloc(n_streams * 4));
+        HIP_TRY(d_ws.alloc(wsb));
+        if (pay_total) HIP_TRY(stage_h2d(d_pl.p, payload, size_t(pay_total), st));
+        HIP_TRY(hipMemcpy(d_po.p, pay_off, (n_streams + 1) * 8, hipMemcpyHostToDevice));
+        if (n_streams) HIP_TRY(hipMemcpy(d_nb.p, nbits, n_streams * 8, hipMemcpyHostToDevice));
+        if (index) {
+            HIP_TRY(hipMemcpy(d_so.p, sym_off, (n_streams + 1) * 8, hipMemcpyHostToDevice));
+            if (nidx) HIP_TRY(hipMemcpy(d_idx.p, index, nidx * 8, hipMemcpyHostToDevice));
+        }
+        if (noidx) HIP_TRY(hipMemcpy(d_oidx.p, out_index, noidx * 8, hipMemcpyHostToDevice));   // gap entries stay what the caller had
+        const int rc = dev(src, dst, d_pl.as<uint8_t>(), d_po.as<uint64_t>(), d_nb.as<uint64_t>(), n_streams, pay_total, prev0,
+                           d_so.as<uint64_t>(), sym_total, index ? d_idx.as<uint64_t>() : nullptr, chunk_symbols,
+                           want_payload ? d_out.as<uint8_t>() : nullptr, dcap, d_oo.as<uint64_t>(), d_onb.as<uint64_t>(),
+                           out_index ? d_oidx.as<uint64_t>() : nullptr, d_drop.as<uint64_t>(), d_st.as<int32_t>(), d_ws.p, wsb, st);
+        if (rc != MH_OK) return rc;
+        dev_rc = mh_dev_status(d_ws.p, st);
+        sst.resize(n_streams);
+        drop.resize(n_streams);
+        if (n_streams) HIP_TRY(hipMemcpy(sst.data(), d_st.p, n_streams * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(out_off, d_oo.p, (n_streams + 1) * 8, hipMemcpyDeviceToHost));
+        if (n_streams) HIP_TRY(hipMemcpy(out_nbits, d_onb.p, n_streams * 8, hipMemcpyDeviceToHost));
+        if (n_streams) HIP_TRY(hipMemcpy(drop.data(), d_drop.p, n_streams * 8, hipMemcpyDeviceToHost));
+        if (!index) HIP_TRY(hipMemcpy(sym_off, d_so.p, (n_streams + 1) * 8, hipMemcpyDeviceToHost));
+        return MH_OK;
+    }
+
+    // the device's payload (`bytes` of it) and index slices; nothing when the payload did not fit
+    bool fit() const { return dev_rc != MH_ERR_CAPACITY; }
+    int payload(uint8_t *to, uint64_t bytes) {
+        if (to && bytes && bytes <= dcap && fit()) HIP_TRY(stage_d2h(to, d_out.p, size_t(bytes), nullptr));
+        return MH_OK;
+    }
+    int slices(uint64_t *to) {
+        if (noidx && fit()) HIP_TRY(hipMemcpy(to, d_oidx.p, noidx * 8, hipMemcpyDeviceToHost));
+        return MH_OK;
+    }
+
+    // the call's result: the first failed stream's error (idx_st: what indexing the batch first found), else the device's
+    // (MH_ERR_CAPACITY: the payload does not fit)
+    int finish(const std::vector<int32_t> &idx_st, uint64_t *dropped, int32_t *stream_status) {
+        if (dropped) std::copy(drop.begin(), drop.end(), dropped);
+        for (size_t i = 0; i < idx_st.size(); ++i)
+            if (idx_st[i] != MH_OK) sst[i] = idx_st[i];
+        int first = MH_OK;
+        for (size_t i = 0; i < sst.size() && first == MH_OK; ++i) first = sst[i];
+        if (first == MH_OK && dev_rc != MH_OK && dev_rc != MH_ERR_ARG) first = dev_rc;
+        if (stream_status) std::copy(sst.begin(), sst.end(), stream_status);
+        return first;
+    }
+};
+
 }  // namespace
 
+// an index-free order-2 stream over the walk cap, decoded alone
+int mhapi::decode_alone(const mh_model *m, const uint8_t *payload, uint64_t nbits, uint8_t prev0, std::vector<uint8_t> &out) {
+    const uint64_t minl = uint64_t(m->min_len > 0 ? m->min_len : 1);
+    out.assign(size_t(nbits / minl) + 1, 0);
+    size_t nb = 0;
+    const int rc = mh_decode(m, payload, nbits, prev0, out.data(), out.size(), &nb, nullptr, 0, 0);
+    out.resize(rc == MH_OK ? nb : 0);
+    return rc;
+}
+
 extern "C" {
+
+/* -------------------------------------------------------------------------------------------- coded histogram */
 
 size_t mh_dev_histogram_coded_workspace(size_t n_streams, uint64_t sym_total, uint32_t chunk_symbols) {
     (void)sym_total; (void)chunk_symbols;                             // the counting keeps nothing per chunk
     return mhr::hist_layout(n_streams).total;
 }
 
+size_t mh_dev_histogram_coded_batch_o2_workspace(size_t n_streams, uint64_t sym_total, uint32_t chunk_symbols) {
+    return mh_dev_histogram_coded_workspace(n_streams, sym_total, chunk_symbols);
+}
+
 int mh_dev_histogram_coded_batch(const mh_model *src, int order, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits,
                                  size_t n_streams, uint64_t pay_total, uint8_t prev0, const uint64_t *d_sym_off, uint64_t sym_total,
                                  const uint64_t *d_index, uint32_t chunk_symbols, uint64_t *d_counts, int32_t *d_stream_status, void *d_ws,
                                  size_t ws_bytes, void *stream) {
-    if (!src) return MH_ERR_ARG;
+    if (!order01(src) || (order != 0 && order != 1)) return MH_ERR_ARG;
     return histogram_coded(src, nullptr, order, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index,
                            chunk_symbols, d_counts, d_stream_status, d_ws, ws_bytes, stream);
 }
@@ -117,116 +263,175 @@ int mh_dev_histogram_coded_each(const mh_model_set *src, int order, const uint8_
                                 size_t n_streams, uint64_t pay_total, uint8_t prev0, const uint64_t *d_sym_off, uint64_t sym_total,
                                 const uint64_t *d_index, uint32_t chunk_symbols, uint64_t *d_counts, int32_t *d_stream_status, void *d_ws,
                                 size_t ws_bytes, void *stream) {
-    if (!src) return MH_ERR_ARG;
+    if (!src || n_streams != src->d.n || (order != 0 && order != 1)) return MH_ERR_ARG;
     return histogram_coded(nullptr, src, order, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index,
                            chunk_symbols, d_counts, d_stream_status, d_ws, ws_bytes, stream);
 }
 
+int mh_dev_histogram_coded_batch_o2(const mh_model *src, int order, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits,
+                                    size_t n_streams, uint64_t pay_total, uint8_t prev0, const uint64_t *d_sym_off, uint64_t sym_total,
+                                    const uint64_t *d_index, uint32_t chunk_symbols, uint64_t *d_counts, int32_t *d_stream_status, void *d_ws,
+                                    size_t ws_bytes, void *stream) {
+    if (!order012(src) || order < 0 || order > 2 || (src->type != 2 && order != 2)) return MH_ERR_ARG;
+    return histogram_coded(src, nullptr, order, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index,
+                           chunk_symbols, d_counts, d_stream_status, d_ws, ws_bytes, stream);
+}
+
+/* ---------------------------------------------------------------------------------------------------- re-code */
+
 size_t mh_dev_recode_batch_workspace(size_t n_streams, uint64_t sym_total, uint32_t chunk_symbols) {
-    const uint64_t W = chunk_shift_of(chunk_symbols) >= 0 ? mhb::work_items(n_streams, sym_total, chunk_symbols) : 0;
-    return mhr::recode_layout(n_streams, W).total;
+    return recode_workspace(n_streams, sym_total, chunk_symbols, false);
+}
+
+size_t mh_dev_recode_batch_o2_workspace(size_t n_streams, uint64_t sym_total, uint32_t chunk_symbols) {
+    return recode_workspace(n_streams, sym_total, chunk_symbols, true);
 }
 
 int mh_dev_recode_batch(const mh_model *src, const mh_model *dst, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits,
                         size_t n_streams, uint64_t pay_total, uint8_t prev0, uint64_t *d_sym_off, uint64_t sym_total, const uint64_t *d_index,
                         uint32_t chunk_symbols, uint8_t *d_out_payload, size_t cap, uint64_t *d_out_off, uint64_t *d_out_nbits,
                         uint64_t *d_out_index, uint64_t *d_dropped, int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
-    if (!src) return MH_ERR_ARG;
-    return recode(src, nullptr, dst, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index, chunk_symbols,
-                  d_out_payload, cap, d_out_off, d_out_nbits, d_out_index, d_dropped, d_stream_status, d_ws, ws_bytes, stream);
+    if (!order01(src) || !order01(dst)) return MH_ERR_ARG;
+    return recode(src, nullptr, dst, false, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index,
+                  chunk_symbols, d_out_payload, cap, d_out_off, d_out_nbits, d_out_index, d_dropped, d_stream_status, d_ws, ws_bytes, stream);
 }
 
 int mh_dev_recode_each(const mh_model_set *src, const mh_model *dst, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits,
                        size_t n_streams, uint64_t pay_total, uint8_t prev0, uint64_t *d_sym_off, uint64_t sym_total, const uint64_t *d_index,
                        uint32_t chunk_symbols, uint8_t *d_out_payload, size_t cap, uint64_t *d_out_off, uint64_t *d_out_nbits,
                        uint64_t *d_out_index, uint64_t *d_dropped, int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
-    if (!src) return MH_ERR_ARG;
-    return recode(nullptr, src, dst, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index, chunk_symbols,
-                  d_out_payload, cap, d_out_off, d_out_nbits, d_out_index, d_dropped, d_stream_status, d_ws, ws_bytes, stream);
+    if (!src || n_streams != src->d.n || !order01(dst)) return MH_ERR_ARG;
+    return recode(nullptr, src, dst, false, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index,
+                  chunk_symbols, d_out_payload, cap, d_out_off, d_out_nbits, d_out_index, d_dropped, d_stream_status, d_ws, ws_bytes, stream);
+}
+
+int mh_dev_recode_batch_o2(const mh_model *src, const mh_model *dst, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits,
+                           size_t n_streams, uint64_t pay_total, uint8_t prev0, uint64_t *d_sym_off, uint64_t sym_total, const uint64_t *d_index,
+                           uint32_t chunk_symbols, uint8_t *d_out_payload, size_t cap, uint64_t *d_out_off, uint64_t *d_out_nbits,
+                           uint64_t *d_out_index, uint64_t *d_dropped, int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
+    if (!order012(src) || !order012(dst) || (src->type != 2 && dst->type != 2)) return MH_ERR_ARG;
+    return recode(src, nullptr, dst, true, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index,
+                  chunk_symbols, d_out_payload, cap, d_out_off, d_out_nbits, d_out_index, d_dropped, d_stream_status, d_ws, ws_bytes, stream);
 }
 
 int mh_recode_batch(const mh_model *src, const mh_model *dst, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits,
                     size_t n_streams, uint8_t prev0, uint64_t *sym_off, const uint64_t *index, uint32_t chunk_symbols, uint8_t *out_payload,
                     size_t cap, uint64_t *out_off, uint64_t *out_nbits, uint64_t *out_index, uint64_t *dropped, int32_t *stream_status) {
-    if (!order01(src) || !order01(dst) || !pay_off || (!nbits && n_streams) || !out_off || (!out_nbits && n_streams) || !sym_off)
-        return MH_ERR_ARG;
-    if ((index || out_index) && chunk_shift_of(chunk_symbols) < 0) return MH_ERR_ARG;
-    if (!offsets_ok(pay_off, n_streams)) return MH_ERR_ARG;
-    const uint64_t pay_total = pay_off[n_streams];
-    if (!payload && pay_total) return MH_ERR_ARG;
-    for (size_t i = 0; i < n_streams; ++i)
-        if (nbits[i] > (pay_off[i + 1] - pay_off[i]) * 8) return MH_ERR_ARG;
-    if (index && !offsets_ok(sym_off, n_streams)) return MH_ERR_ARG;
-    if (!have_device()) return MH_ERR_NO_DEVICE;
-    if (src->max_len > mh::MAX_CODE_BITS || dst->max_len > mh::MAX_CODE_BITS) return MH_ERR_CODE_TOO_LONG;
-    // index-free with a stream over the walk cap: index the batch first (mh_index_batch never refuses a valid stream), then
-    // re-code it as an indexed batch; a stream the indexing fails keeps that error and has no symbols, so no payload
-    const uint64_t minl = uint64_t(src->min_len > 0 ? src->min_len : 1);
-    uint64_t bound = 0;
-    for (size_t i = 0; i < n_streams; ++i) bound += nbits[i] / minl;
+    if (!order01(src) || !order01(dst)) return MH_ERR_ARG;
+    int rc = host_args(src, dst, payload, pay_off, nbits, n_streams, sym_off, index, chunk_symbols, out_off, out_nbits, out_index);
+    if (rc != MH_OK) return rc;
+    const uint64_t bound = symbol_bound(src, nbits, n_streams);
+    // index-free with a stream over the walk cap: index first
     std::vector<uint64_t> own_idx;
     std::vector<int32_t> idx_st;
     bool over = false;
     if (!index)
         for (size_t i = 0; i < n_streams && !over; ++i) over = nbits[i] > MH_BATCH_WALK_MAX_BITS;
     if (over) {
-        if (!out_index) chunk_symbols = MH_CHUNK_DEFAULT;
-        own_idx.assign(size_t(mh_batch_index_capacity(bound, n_streams, chunk_symbols)), 0);
-        idx_st.assign(n_streams, MH_OK);
-        const int rc = mh_index_batch(src, payload, pay_off, nbits, n_streams, prev0, chunk_symbols, sym_off, own_idx.data(), own_idx.size(),
-                                      idx_st.data());
-        if (rc == MH_ERR_HIP || rc == MH_ERR_NO_DEVICE || rc == MH_ERR_NOMEM || rc == MH_ERR_CAPACITY) return rc;
+        rc = index_first(src, payload, pay_off, nbits, n_streams, prev0, bound, out_index != nullptr, chunk_symbols, sym_off, own_idx, idx_st);
+        if (rc != MH_OK) return rc;
         index = own_idx.data();
     }
-    const hipStream_t st = nullptr;
-    const uint64_t sym_total = index ? sym_off[n_streams] : bound;    // index-free: what the destination index is sized for
-    const size_t nidx = index ? size_t(mh_batch_index_capacity(sym_total, n_streams, chunk_symbols)) : 0;
-    const size_t noidx = out_index ? size_t(mh_batch_index_capacity(sym_total, n_streams, chunk_symbols)) : 0;
-    const size_t wsb = mh_dev_recode_batch_workspace(n_streams, sym_total, index ? chunk_symbols : 0);
-    const size_t dcap = out_payload ? cap : 0;
-    DevBuf d_pl, d_po, d_nb, d_so, d_idx, d_out, d_oo, d_onb, d_oidx, d_drop, d_st, d_ws;
-    HIP_TRY(d_pl.alloc(size_t(pay_total) + 64));
-    HIP_TRY(d_po.alloc((n_streams + 1) * 8));
-    HIP_TRY(d_nb.alloc(n_streams * 8));
-    HIP_TRY(d_so.alloc((n_streams + 1) * 8));
-    HIP_TRY(d_idx.alloc(nidx * 8));
-    HIP_TRY(d_out.alloc(dcap));
-    HIP_TRY(d_oo.alloc((n_streams + 1) * 8));
-    HIP_TRY(d_onb.alloc(n_streams * 8));
-    HIP_TRY(d_oidx.alloc(noidx * 8));
-    HIP_TRY(d_drop.alloc(n_streams * 8));
-    HIP_TRY(d_st.alloc(n_streams * 4));
-    HIP_TRY(d_ws.alloc(wsb));
-    if (pay_total) HIP_TRY(stage_h2d(d_pl.p, payload, size_t(pay_total), st));
-    HIP_TRY(hipMemcpy(d_po.p, pay_off, (n_streams + 1) * 8, hipMemcpyHostToDevice));
-    if (n_streams) HIP_TRY(hipMemcpy(d_nb.p, nbits, n_streams * 8, hipMemcpyHostToDevice));
-    if (index) {
-        HIP_TRY(hipMemcpy(d_so.p, sym_off, (n_streams + 1) * 8, hipMemcpyHostToDevice));
-        if (nidx) HIP_TRY(hipMemcpy(d_idx.p, index, nidx * 8, hipMemcpyHostToDevice));
-    }
-    if (noidx) HIP_TRY(hipMemcpy(d_oidx.p, out_index, noidx * 8, hipMemcpyHostToDevice));   // gap entries stay what the caller had
-    int rc = mh_dev_recode_batch(src, dst, d_pl.as<uint8_t>(), d_po.as<uint64_t>(), d_nb.as<uint64_t>(), n_streams, pay_total, prev0,
-                                 d_so.as<uint64_t>(), sym_total, index ? d_idx.as<uint64_t>() : nullptr, chunk_symbols,
-                                 out_payload ? d_out.as<uint8_t>() : nullptr, dcap, d_oo.as<uint64_t>(), d_onb.as<uint64_t>(),
-                                 out_index ? d_oidx.as<uint64_t>() : nullptr, d_drop.as<uint64_t>(), d_st.as<int32_t>(), d_ws.p, wsb, st);
+    HostRecode hr;
+    rc = hr.run(mh_dev_recode_batch, false, src, dst, payload, pay_off, nbits, n_streams, prev0, sym_off, index ? sym_off[n_streams] : bound, index,
+                chunk_symbols, out_payload != nullptr, cap, out_off, out_nbits, out_index);
     if (rc != MH_OK) return rc;
-    const int dev_rc = mh_dev_status(d_ws.p, st);
-    std::vector<int32_t> sst(n_streams);
-    if (n_streams) HIP_TRY(hipMemcpy(sst.data(), d_st.p, n_streams * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_off, d_oo.p, (n_streams + 1) * 8, hipMemcpyDeviceToHost));
-    if (n_streams) HIP_TRY(hipMemcpy(out_nbits, d_onb.p, n_streams * 8, hipMemcpyDeviceToHost));
-    if (n_streams && dropped) HIP_TRY(hipMemcpy(dropped, d_drop.p, n_streams * 8, hipMemcpyDeviceToHost));
-    if (!index) HIP_TRY(hipMemcpy(sym_off, d_so.p, (n_streams + 1) * 8, hipMemcpyDeviceToHost));
-    if (out_payload && out_off[n_streams] && out_off[n_streams] <= dcap && dev_rc != MH_ERR_CAPACITY)
-        HIP_TRY(stage_d2h(out_payload, d_out.p, size_t(out_off[n_streams]), st));
-    if (noidx && dev_rc != MH_ERR_CAPACITY) HIP_TRY(hipMemcpy(out_index, d_oidx.p, noidx * 8, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < idx_st.size(); ++i)
-        if (idx_st[i] != MH_OK) sst[i] = idx_st[i];
-    int first = MH_OK;
-    for (size_t i = 0; i < n_streams && first == MH_OK; ++i) first = sst[i];
-    if (first == MH_OK && dev_rc != MH_OK && dev_rc != MH_ERR_ARG) first = dev_rc;      // MH_ERR_CAPACITY: the payload does not fit
-    if (stream_status) std::copy(sst.begin(), sst.end(), stream_status);
-    return first;
+    if ((rc = hr.payload(out_payload, out_off[n_streams])) != MH_OK || (rc = hr.slices(out_index)) != MH_OK) return rc;
+    return hr.finish(idx_st, dropped, stream_status);
+}
+
+int mh_recode_batch_o2(const mh_model *src, const mh_model *dst, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits,
+                       size_t n_streams, uint8_t prev0, uint64_t *sym_off, const uint64_t *index, uint32_t chunk_symbols, uint8_t *out_payload,
+                       size_t cap, uint64_t *out_off, uint64_t *out_nbits, uint64_t *out_index, uint64_t *dropped, int32_t *stream_status) {
+    if (!order012(src) || !order012(dst) || (src->type != 2 && dst->type != 2)) return MH_ERR_ARG;
+    int rc = host_args(src, dst, payload, pay_off, nbits, n_streams, sym_off, index, chunk_symbols, out_off, out_nbits, out_index);
+    if (rc != MH_OK) return rc;
+    const uint64_t bound = symbol_bound(src, nbits, n_streams);
+    // index-free with a stream over the walk cap.  Order-0/1 source: index first.  Order-2 source (no batch index builder): the
+    // device call refuses such a stream; it is decoded alone, coded by mh_encode under dst and spliced into place in stream order.
+    std::vector<uint64_t> own_idx;
+    std::vector<int32_t> idx_st;
+    std::vector<size_t> long_streams;
+    if (!index)
+        for (size_t i = 0; i < n_streams; ++i)
+            if (nbits[i] > MH_BATCH_WALK_MAX_BITS) long_streams.push_back(i);
+    if (!long_streams.empty() && src->type != 2) {
+        long_streams.clear();
+        rc = index_first(src, payload, pay_off, nbits, n_streams, prev0, bound, out_index != nullptr, chunk_symbols, sym_off, own_idx, idx_st);
+        if (rc != MH_OK) return rc;
+        index = own_idx.data();
+    }
+    HostRecode hr;
+    rc = hr.run(mh_dev_recode_batch_o2, true, src, dst, payload, pay_off, nbits, n_streams, prev0, sym_off, index ? sym_off[n_streams] : bound,
+                index, chunk_symbols, out_payload != nullptr, cap, out_off, out_nbits, out_index);
+    if (rc != MH_OK) return rc;
+    if (long_streams.empty()) {
+        if ((rc = hr.payload(out_payload, out_off[n_streams])) != MH_OK || (rc = hr.slices(out_index)) != MH_OK) return rc;
+    } else {
+        // the device's part, then every stream moved to its place behind the long streams' payloads, symbols and slices
+        const bool dev_fit = hr.dev_rc != MH_ERR_CAPACITY;
+        std::vector<uint8_t> dev_out(out_payload && dev_fit ? size_t(out_off[n_streams]) : 0);
+        if (!dev_out.empty()) HIP_TRY(stage_d2h(dev_out.data(), hr.d_out.p, dev_out.size(), nullptr));
+        std::vector<uint64_t> dev_idx(dev_fit ? hr.noidx : 0);
+        if (!dev_idx.empty()) HIP_TRY(hipMemcpy(dev_idx.data(), hr.d_oidx.p, hr.noidx * 8, hipMemcpyDeviceToHost));
+        // dst's code lengths, for the dropped symbols of the long streams
+        const uint32_t dmask = dst->type == 2 ? 0xFFFFu : (dst->type ? 0xFFu : 0u);
+        std::vector<uint8_t> len8((size_t(dmask) + 1) << 8);
+        if (!dst->d_len8) return MH_ERR_NO_DEVICE;
+        HIP_TRY(hipMemcpy(len8.data(), dst->d_len8, len8.size(), hipMemcpyDeviceToHost));
+        const std::vector<uint64_t> dso(sym_off, sym_off + n_streams + 1), doo(out_off, out_off + n_streams + 1);
+        std::vector<uint8_t> bytes, coded;
+        std::vector<uint64_t> slice;
+        uint64_t pos = 0, sym = 0;
+        size_t k = 0;
+        bool fits = dev_fit;
+        for (size_t i = 0; i < n_streams; ++i) {
+            const bool is_long = k < long_streams.size() && long_streams[k] == i;
+            uint64_t len = doo[i + 1] - doo[i], cnt = dso[i + 1] - dso[i];
+            const uint8_t *from = dev_out.empty() ? nullptr : dev_out.data() + doo[i];
+            const uint64_t *ifrom = dev_idx.empty() ? nullptr : dev_idx.data() + mh_batch_index_base(dso[i], i, chunk_symbols ? chunk_symbols : 1);
+            if (is_long) {
+                ++k;
+                len = cnt = 0;
+                hr.sst[i] = decode_alone(src, payload + pay_off[i], nbits[i], prev0, bytes);
+                if (hr.sst[i] == MH_OK) {
+                    coded.assign(mh_encode_bound(dst, bytes.size()) + 16, 0);
+                    slice.assign(out_index ? size_t(mh_index_entries(bytes.size(), chunk_symbols)) : 0, 0);
+                    uint64_t nb = 0;
+                    const int er = mh_encode(dst, bytes.data(), bytes.size(), prev0, coded.data(), coded.size(), &nb,
+                                             out_index ? slice.data() : nullptr, out_index ? chunk_symbols : 0);
+                    if (er != MH_OK) return er;
+                    out_nbits[i] = nb;
+                    len = (nb + 7) / 8; cnt = bytes.size();
+                    from = coded.data(); ifrom = slice.data();
+                    uint32_t c16 = uint32_t(prev0) * 0x101u;
+                    uint64_t d = 0;
+                    for (uint8_t b : bytes) {
+                        const uint8_t l = len8[(size_t(c16 & dmask) << 8) | b];
+                        d += l == 0 || l > 64;
+                        c16 = ((c16 << 8) | b) & 0xFFFFu;
+                    }
+                    hr.drop[i] = d;
+                }
+            }
+            out_off[i] = pos;
+            sym_off[i] = sym;
+            if (out_payload && len) {
+                if (pos + len > cap || !from) fits = false;
+                else std::memcpy(out_payload + pos, from, size_t(len));
+            }
+            if (out_index && cnt && ifrom && fits) {
+                const uint64_t ne = mh_index_entries(cnt, chunk_symbols);
+                std::memcpy(out_index + mh_batch_index_base(sym, i, chunk_symbols), ifrom, size_t(ne) * 8);
+            }
+            pos += len;
+            sym += cnt;
+        }
+        out_off[n_streams] = pos;
+        sym_off[n_streams] = sym;
+        hr.dev_rc = (out_payload && !fits) ? MH_ERR_CAPACITY : MH_OK;
+    }
+    return hr.finish(idx_st, dropped, stream_status);
 }
 
 }  // extern "C"

@@ -96,6 +96,13 @@ struct DecBatchParams {
     uint32_t P, nsec, sec_lds, direct, H;
 };
 
+// The model a batch to decode was coded under, for the call families that serve all three (search: mh_find.h, re-coding:
+// mh_recode.h).  Shared: one order-0/1 model (the tables go to LDS, prev0 is a byte, index entries carry one context byte).
+// Set: stream i under set model i (mh_each.h).  Shared2: one order-2 model, described as for launch_decode_batch_o2
+// (mh_batch_o2.h): the tables are the order-2 tables (general form, L2), prev0 is the 16-bit start context, index entries
+// carry the context in bits 48..63.
+enum class Model { Shared, Set, Shared2 };
+
 // LDS bytes of a shared model's decode tables as mhb::load_tables (mh_batch_dev.hpp) lays them out: the two are a pair, and
 // this is the only copy of the size.  T: any struct with P, nsec and sec_lds (DecBatchParams, the single-stream DecodeParams).
 template <typename T>

@@ -58,11 +58,8 @@ struct FindParams {
     uint64_t hit_cap;
 };
 
-// The model the batch was coded under.  Shared: one order-0/1 model (b's tables go to LDS, b.prev0 is a byte, index entries
-// carry one context byte).  Set: stream i under set model i.  Shared2: one order-2 model, described as for
-// launch_decode_batch_o2 (mh_batch_o2.h): b's tables are the order-2 tables (general form, L2), b.prev0 is the 16-bit start
-// context, index entries carry the context in bits 48..63.
-enum class Model { Shared, Set, Shared2 };
+// model: what the batch was coded under (mhb::Model, mh_batch.h); b's tables and b.prev0 as that model's batch decoder takes them
+using mhb::Model;
 hipError_t launch_find(const FindParams &p, const Automaton &a, Model model, void *d_ws, hipStream_t st);
 
 }  // namespace mhf

@@ -1,6 +1,7 @@
 // mh_recode.h — launch interface between the re-coding calls of the C ABI (mh_api_recode.cpp) and their kernels
-// (mh_recode.hip): the (prev, sym) histogram of a compressed batch and the batch coded again under another model, both taken
-// from the decoded symbols while they sit in a register (include/mh.h, "RE-CODING BATCHES").  The batch layouts (packed
+// (mh_recode.hip): the context histogram of a compressed batch and the batch coded again under another model, both taken
+// from the decoded symbols while they sit in a register (include/mh.h, "RE-CODING BATCHES" and the re-coding part of "ORDER 2
+// IN SEARCH AND RE-CODING").  The batch layouts (packed
 // payloads, closed-form index slices) are those of mh_batch.h; the per-stream models those of mh_each.h.
 #pragma once
 
@@ -19,11 +20,13 @@ struct Src {
     mhe::SetDev set;
 };
 
-// the destination model's encoder tables (prev * 256 + sym; an order-0 model repeats its row): ctx_mask 0xFF for order 1,
-// 0 for order 0 (row 0 serves every context)
+// the destination model's encoder tables at (ctx & ctx_mask) << 8 | sym: order 2 keeps both context bytes (0xFFFF) and may
+// have the packed table enc64 (len << 56 | code; len 255: longer than 56 bits, read len8 / code64), order 1 the last byte
+// (0xFF), order 0 none (0: row 0 serves every context)
 struct Dst {
     const uint8_t *len8;
     const unsigned long long *code64;
+    const unsigned long long *enc64;    // order 2 only, may be nullptr
     uint32_t ctx_mask;
 };
 
@@ -39,30 +42,33 @@ inline HistLayout hist_layout(uint64_t n_streams) {
 }
 
 // re-code workspace: status block (status, stop, -, -, tail word) | per-stream status (when the caller passes none) | per
-// chunk number: destination bits (u64, W + 1, scanned in place), dropped symbols (u32) | scan block sums
+// chunk number: destination bits (u64, W + 1, scanned in place), dropped symbols (u32) and, with seam (an order-0/1 batch
+// coded under order-2 contexts, mh_recode.hip), head bits (u32: the next chunk's first symbol under dst) and closing context
+// (u32: the chunk's last two symbols) | scan block sums
 struct RecodeLayout {
-    size_t off_status, off_bits, off_drop, off_sums, total;
+    size_t off_status, off_bits, off_drop, off_head, off_close, off_sums, total;
 };
 constexpr size_t TAIL_AT = 16;
-inline RecodeLayout recode_layout(uint64_t n_streams, uint64_t nwork) {
+inline RecodeLayout recode_layout(uint64_t n_streams, uint64_t nwork, bool seam) {
     RecodeLayout l;
     const uint64_t len = (nwork > n_streams ? nwork : n_streams) + 1;
     l.off_status = 64;
     l.off_bits = (l.off_status + size_t(n_streams) * 4 + 15) & ~size_t(15);
     l.off_drop = l.off_bits + size_t(nwork + 1) * 8;
-    l.off_sums = (l.off_drop + size_t(nwork) * 4 + 15) & ~size_t(15);
+    l.off_head = l.off_drop + size_t(nwork) * 4;
+    l.off_close = l.off_head + (seam ? size_t(nwork) * 4 : 0);
+    l.off_sums = (l.off_close + (seam ? size_t(nwork) * 4 : 0) + 15) & ~size_t(15);
     l.total = (l.off_sums + size_t(mhb::scan_blocks(len) + 1) * 8 + 255) & ~size_t(255);
     return l;
 }
 
 struct HistParams {
     Src s;
-    uint32_t order;                 // of the histogram: 0 (256 counts) or 1 (65 536)
+    uint32_t order;                 // of the histogram: 0 (256 counts), 1 (65 536) or 2 (1 << 24)
     unsigned long long *counts;
 };
 
-// what every re-coding call has, whatever the orders of its models: the source and the outputs.  The kernels that never decode
-// (mh_recode_dev.hpp) take this part alone.
+// the source and the outputs: the kernels that never decode take this part alone
 struct RecodeIO {
     Src s;                          // index-free: s.b.sym_off is written, s.b.index null
     uint8_t *out;                   // packed payloads, 16-byte aligned; nullptr: count only
@@ -78,8 +84,9 @@ struct RecodeParams : RecodeIO {
     Dst dst;
 };
 
-// shared: one source model (s.b's tables, LDS); else stream i under set model i
-hipError_t launch_histogram_coded(const HistParams &p, bool shared, void *d_ws, hipStream_t st);
-hipError_t launch_recode(const RecodeParams &p, bool shared, void *d_ws, hipStream_t st);
+// model: what the batch was coded under (mhb::Model, mh_batch.h); s.b's tables and s.b.prev0 as that model's batch decoder
+// takes them.  Any order of the histogram or of dst under a shared model; a model set with an order-2 side is refused.
+hipError_t launch_histogram_coded(const HistParams &p, mhb::Model model, void *d_ws, hipStream_t st);
+hipError_t launch_recode(const RecodeParams &p, mhb::Model model, void *d_ws, hipStream_t st);
 
 }  // namespace mhr

@@ -1,33 +1,56 @@
 // mh_recode.hip — a compressed batch's training histogram and the batch coded again under another model, without writing
-// the decoded bytes (include/mh.h, "RE-CODING BATCHES").  The batch decoders hold every decoded byte in a register for one
-// step; here that byte feeds a counter, or the destination model's code and a BitWriter, instead of a store.
-//   recode_check_kernel      the batch checks (mhb::check_batch); out_off, nbits and dropped zeroed (this and the other kernels
-//                            that never decode — sizes, cap, zero, tail — are in mh_recode_dev.hpp)
+// the decoded bytes (include/mh.h, "RE-CODING BATCHES" and "ORDER 2 IN SEARCH AND RE-CODING").  The batch decoders hold every
+// decoded byte in a register for one step; here that byte feeds a counter, or the destination model's code and a BitWriter,
+// instead of a store.
+//   histc_check_kernel       the batch checks (mhb::check_batch) of a coded histogram
+//   recode_check_kernel      the batch checks; out_off, nbits and dropped zeroed
 //   recode_idx_len_kernel    one lane per (stream, chunk): decodes under src, sums dst's code lengths and the symbols without a code
 //   recode_comb_kernel       the chunks of failed streams count 0 bits; the dropped symbols of the others go to dropped[i]
 //   (scan)                   chunk bits -> bit offsets (mh_batch_dev.hpp); then payload bytes -> out_off
 //   recode_sizes_kernel      stream i: nbits from the scanned chunk bits, its bytes into out_off
 //   recode_cap_kernel        index-free: more symbols than the destination index was sized for -> MHK_STATUS_CAPACITY
 //   recode_zero_kernel       clears the payload (edge words are OR-ed) or reports that it does not fit
-//   recode_idx_emit_kernel   decodes again and pushes (len8, code64) of dst through BitWriter; the chunk's index entry
+//   recode_idx_emit_kernel   decodes again and pushes dst's codes through BitWriter; the chunk's index entry
 //   recode_walk_kernel       index-free, one lane per stream: count (scans) emit, under the walk cap of batch_dec_walk_kernel
 //   recode_tail_kernel       the bytes of the last, partial dword
 //   histc_idx_kernel         one lane per (stream, chunk): counts the pairs as it decodes; a chunk that fails takes its own
 //                            counts back; <FIX>: the chunks that passed inside a stream that failed take theirs back
 //   histc_walk_kernel        index-free, one lane per stream: counts, and takes the stream's counts back when it fails
-// Verdicts are the batch decoders': same checks, same statuses.  Every loop is bounded by a symbol count or nbits_i.  Shared
-// source model: tables in LDS as load_tables lays them out; behind them dst's len8 image (64 KiB order 1, 256 B order 0)
-// when it fits, else len8 comes from L2; code64 always comes from L2.  Model set: tables in L2, an order-0 len8 image in LDS.
-// The counters: a direct-mapped cache of (pair -> u64) in the LDS the tables leave, 64-bit global atomics behind it.
+// Verdicts are the batch decoders' (mh_dev_decode_batch, _each, _batch_o2 by the source model): same checks, same statuses.
+// Every loop is bounded by a symbol count or nbits_i.  One kernel family serves every order:
+//   Dec<K, W>    the source decoder, one policy per model (mhb::Model).  Shared: the order-0/1 tables in LDS as load_tables
+//                lays them out, one workgroup per CU.  Set: stream i's slots in L2.  Shared2: the model's order-2 tables
+//                read from L2 as batch2_dec_idx_kernel reads them, entries masked with IDX2_POS and their context taken
+//                from e >> 48.  Set and Shared2: workgroups of 256 lanes, eight per CU.
+//   W            some side is order 2: the lane rolls a 16-bit context ((ctx << 8) | sym) & 0xFFFF, of which an order-0/1
+//                model reads the last byte.  Else the context is the last symbol.
+//   Enc<DLDS, W> the destination's (len, code) at (ctx & mask) << 8 | sym.  DLDS: an order-0/1 destination's len8 image (64
+//                KiB order 1, 256 B order 0) in LDS behind the source's tables when it fits (a model set: the order-0
+//                image only); else len8 comes from L2.  Codes come from L2: from code64, or under W from the packed enc64
+//                of an order-2 model ((len8, code64) over 56 bits or without a packed table).
+//   the seam     (SEAM: Shared source under W, so the destination or the histogram is order 2.)  An order-0/1 entry carries
+//                one context byte, so the lane of chunk k does not know the symbol two in front of its first one.  The lane
+//                of chunk k therefore owns symbols first + 1 ... first + nsym: it decodes one symbol into the next chunk,
+//                whose two context bytes it knows; the lane of a stream's first chunk also owns symbol 0 under (prev0,
+//                prev0).  recode_idx_len_kernel keeps that symbol's bits apart ("head") and the chunk's last two symbols
+//                ("close"); recode_comb_kernel adds head(k - 1) to the bits of chunk k, so the scanned value is the bit
+//                offset of chunk k's first code, its destination entry.  The extra symbol never sets a verdict: the next
+//                chunk's own lane judges that chunk, and when the stream passed, that lane decoded the same bits in the
+//                same context.  A chunk that is not its stream's last has >= 256 symbols, so the two symbols in front of a
+//                chunk lie in the previous chunk.  An order-2 source and the index-free walk need none of this.  The
+//                histogram's take-back repeats exactly what was counted, the extra symbol included (it is counted only by
+//                a chunk that passed).
+// The counters: a direct-mapped cache of (key -> u64) in the LDS the tables leave, 64-bit global atomics behind it into the
+// caller's 256, 65 536 or 1 << 24 counts.
 #include "mh_recode.h"
 #include "mh_batch_dev.hpp"
-#include "mh_recode_dev.hpp"
 #include "mh_each_dev.hpp"
 #include "../../include/mh.h"
 
 namespace mhr {
 
 using mhb::BATCH_STATUS_ARG;
+using mhb::Model;
 using mhk::BitCursor;
 using mhk::BitSrc;
 using mhk::DecTables;
@@ -36,7 +59,6 @@ namespace {
 
 using mhb::BitWriter;
 using mhb::Chunk;
-using mhb::chunk_of;
 using mhb::fail;
 using mhb::find_stream;
 using mhb::grid_for;
@@ -46,38 +68,74 @@ using mhb::scan_exclusive;
 using mhb::stopped;
 using mhb::stream_fail;
 
-constexpr int NT_SHARED = mhb::B_THREADS;          // batch_dec_idx_kernel's shape: one workgroup per CU beside the tables
-constexpr int NT_EACH = 256;                       // each_dec_idx_kernel's
 constexpr int LDS_MAX = 163840;
 
-// the symbol decoder of a lane: the shared model's two-level tables, or stream i's slots
-template <bool SHARED> struct Dec;
-template <> struct Dec<true> {
+// The symbol decoder of a lane, one policy per model; next() decodes one symbol in the lane's context ctx.
+//   NT, PER_CU   the workgroup shape: that of the model's batch decoder
+//   O2           the format of the batch's index entries (mhb::chunk_of)
+template <Model K, bool W> struct Dec;
+template <bool W> struct Dec<Model::Shared, W> {
+    static constexpr int NT = mhb::B_THREADS, PER_CU = 1;
+    static constexpr bool O2 = false;
     const uint16_t *lut;
     const uint32_t *sub_base;
     DecTables tabs;
     __device__ __forceinline__ Dec(const Src &s, unsigned char *smem) : tabs(mhb::load_tables(s.b, smem, lut, sub_base)) {}
     __device__ __forceinline__ void stream(const Src &, uint64_t) {}
-    __device__ __forceinline__ uint32_t next(const Src &, const BitSrc &src, BitCursor &bc, uint32_t prev, uint32_t &used, bool &bad) const {
-        return mhk::decode_one(lut, sub_base, tabs, src, bc, prev, used, bad);
+    __device__ __forceinline__ uint32_t next(const Src &, const BitSrc &src, BitCursor &bc, uint32_t ctx, uint32_t &used, bool &bad) const {
+        return mhk::decode_one(lut, sub_base, tabs, src, bc, W ? ctx & 0xFFu : ctx, used, bad);
     }
 };
-template <> struct Dec<false> {
+template <> struct Dec<Model::Set, false> {
+    static constexpr int NT = 256, PER_CU = 8;
+    static constexpr bool O2 = false;
     const uint32_t *row;
     bool o1;
     __device__ __forceinline__ Dec(const Src &, unsigned char *) : row(nullptr), o1(false) {}
     __device__ __forceinline__ void stream(const Src &s, uint64_t i) { row = s.set.ctx_slot + i * 256u; o1 = s.set.type[i] != 0; }
-    __device__ __forceinline__ uint32_t next(const Src &s, const BitSrc &src, BitCursor &bc, uint32_t prev, uint32_t &used, bool &bad) const {
-        return mhe::decode_sym(s.set, row, o1 ? prev : 0u, src, bc, used, bad);
+    __device__ __forceinline__ uint32_t next(const Src &s, const BitSrc &src, BitCursor &bc, uint32_t ctx, uint32_t &used, bool &bad) const {
+        return mhe::decode_sym(s.set, row, o1 ? ctx : 0u, src, bc, used, bad);
     }
 };
+template <> struct Dec<Model::Shared2, true> {
+    static constexpr int NT = 256, PER_CU = 8;
+    static constexpr bool O2 = true;
+    const uint16_t *prim;
+    const uint32_t *sec_base;
+    DecTables tabs;
+    __device__ __forceinline__ Dec(const Src &s, unsigned char *) : prim(s.b.prim), sec_base(s.b.sec_base), tabs{s.b.sec, s.b.tree, s.b.P, 0u, 0u} {}
+    __device__ __forceinline__ void stream(const Src &, uint64_t) {}
+    __device__ __forceinline__ uint32_t next(const Src &, const BitSrc &src, BitCursor &bc, uint32_t ctx, uint32_t &used, bool &bad) const {
+        return mhk::decode_one(prim, sec_base, tabs, src, bc, ctx, used, bad);
+    }
+};
+template <Model K, bool W> constexpr bool SEAM = K == Model::Shared && W;
 
-// dst's code lengths: one ds_read_u8 (DLDS) or a byte from L2; the index serves code64 too
-template <bool DLDS> struct Lens {
+// the lane's context behind sym
+template <bool W> __device__ __forceinline__ uint32_t roll(uint32_t ctx, uint32_t sym) { return W ? ((ctx << 8) | sym) & 0xFFFFu : sym; }
+// the context in front of a stream's first symbol: prev0, under W (prev0, prev0) (an order-2 source: the call made it so)
+template <Model K, bool W> __device__ __forceinline__ uint32_t start_ctx(const Src &s) {
+    return SEAM<K, W> ? (s.b.prev0 & 0xFFu) * 0x101u : s.b.prev0;
+}
+// chunk w of the indexed batch, its entry's context as the lane starts in it; false when w is a gap.  Under SEAM the high
+// byte is known only in a stream's first chunk (prev0), elsewhere the lane does not own symbol 0.
+template <Model K, bool W>
+__device__ __forceinline__ bool chunk_of(const Src &s, uint64_t w, Chunk &c) {
+    if (!mhb::chunk_of<Dec<K, W>::O2>(s.b, w, c)) return false;
+    if (SEAM<K, W>) c.ctx |= c.first ? 0u : (s.b.prev0 & 0xFFu) << 8;
+    return true;
+}
+// symbol t of chunk c belongs to c's lane (else to the lane of the chunk in front, which knows both context bytes)
+template <bool SEAM_> __device__ __forceinline__ bool owns(const Chunk &c, uint32_t t) { return !SEAM_ || t > 0u || c.first == 0u; }
+
+// the destination's codes
+template <bool DLDS, bool W> struct Enc {
     const uint8_t *g;
     const uint8_t *l;
+    const unsigned long long *code64, *enc64;
     uint32_t mask;
-    __device__ __forceinline__ Lens(const Dst &d, unsigned char *smem, uint32_t lds_at) : g(d.len8), l(smem + lds_at), mask(d.ctx_mask) {
+    __device__ __forceinline__ Enc(const Dst &d, unsigned char *smem, uint32_t lds_at)
+        : g(d.len8), l(smem + lds_at), code64(d.code64), enc64(d.enc64), mask(d.ctx_mask) {
         if (DLDS) {
             const uint32_t n16 = (d.ctx_mask ? 65536u : 256u) / 16u;
             uint4 *dl = reinterpret_cast<uint4 *>(smem + lds_at);
@@ -85,39 +143,136 @@ template <bool DLDS> struct Lens {
             __syncthreads();
         }
     }
-    __device__ __forceinline__ uint32_t at(uint32_t prev, uint32_t sym) const { return ((prev & mask) << 8) | sym; }
-    __device__ __forceinline__ uint32_t operator()(uint32_t idx) const {
-        if constexpr (DLDS) return l[idx]; else return g[idx];
+    __device__ __forceinline__ uint32_t at(uint32_t ctx, uint32_t sym) const { return ((ctx & mask) << 8) | sym; }
+    // one ds_read_u8 (DLDS) or a byte from L2; 0: the pair has no code, skipped (mh_model.hpp:21)
+    __device__ __forceinline__ uint32_t len(uint32_t key) const {
+        uint32_t v;
+        if constexpr (DLDS) v = l[key]; else v = g[key];
+        if constexpr (W) return v > 64u ? 0u : v; else return v;
+    }
+    // the pair's code into bw when `on`; returns its length (0: none)
+    __device__ __forceinline__ uint32_t put(BitWriter &bw, uint32_t key, bool on) const {
+        if constexpr (W) {
+            const uint64_t e = enc64 ? enc64[key] : 0xFF00000000000000ull;
+            uint32_t n = uint32_t(e >> 56);
+            uint64_t c = e & 0x00FFFFFFFFFFFFFFull;
+            if (n == 255u) {                                      // longer than 56 bits, or no packed table
+                n = g[key];
+                c = code64[key];
+            }
+            if (n > 64u) n = 0;
+            if (n && on) bw.code(c, n);
+            return n;
+        } else {
+            const uint32_t n = len(key);
+            if (n && on) bw.code(code64[key], n);
+            return n;
+        }
+    }
+    // a destination index entry: the context part in dst's format
+    __device__ __forceinline__ uint64_t entry(uint32_t ctx, uint64_t bit) const {
+        if constexpr (W) return mask == 0xFFFFu ? (uint64_t(ctx) << 48) | bit : (uint64_t(ctx & 0xFFu) << 56) | bit;
+        else return (uint64_t(ctx) << 56) | bit;
     }
 };
 
+// ------------------------------------------------------------------------------------------------ the kernels that never decode
+// (they read the source batch and the outputs, mhr::RecodeIO, and neither model)
+
+__global__ __launch_bounds__(256) void histc_check_kernel(Src s, int *status, int *stop) {
+    const uint64_t i = mhb::gtid();
+    if (i > s.b.n) return;
+    mhb::check_batch(s.b, i, status, stop);
+}
+
+__global__ __launch_bounds__(256) void recode_check_kernel(RecodeIO p, int *status, int *stop) {
+    const uint64_t i = mhb::gtid();
+    const uint64_t n = p.s.b.n;
+    if (i > n) return;
+    p.out_off[i] = 0;
+    if (!p.s.b.index) p.s.b.sym_off[i] = 0;
+    if (i < n) {
+        p.out_nbits[i] = 0;
+        if (p.dropped) p.dropped[i] = 0;
+    }
+    mhb::check_batch(p.s.b, i, status, stop);
+}
+
+// stream i: payload bits (indexed: from the scanned chunk bits; index-free: the count pass wrote them), bytes into out_off
+__global__ __launch_bounds__(256) void recode_sizes_kernel(RecodeIO p, const unsigned long long *cbase, const int *stop) {
+    if (mhb::stopped(stop)) return;
+    const uint64_t i = mhb::gtid();
+    const uint64_t n = p.s.b.n;
+    if (i > n) return;
+    if (i == n) { p.out_off[i] = 0; return; }
+    unsigned long long bits;
+    if (p.s.b.index) {
+        const uint32_t cs = p.s.b.chunk_shift;
+        const uint64_t w0 = (p.s.b.sym_off[i] >> cs) + i, w1 = (p.s.b.sym_off[i + 1] >> cs) + i + 1;
+        bits = cbase[w1] - cbase[w0];
+        p.out_nbits[i] = bits;
+    } else {
+        bits = p.out_nbits[i];
+    }
+    p.out_off[i] = (bits + 7) >> 3;
+}
+
+// index-free: the destination index was sized from sym_total; more symbols than that do not fit it (after the scans: offsets
+// and lengths are complete)
+__global__ void recode_cap_kernel(RecodeIO p, int *status, int *stop) {
+    if (mhb::stopped(stop)) return;
+    if (p.s.b.sym_off[p.s.b.n] > p.s.b.sym_total) { mhb::fail(status, mhk::MHK_STATUS_CAPACITY); atomicExch(stop, 1); }
+}
+
+// zeroes the payload bytes (codes are OR-ed into shared edge dwords) or reports that they do not fit
+__global__ __launch_bounds__(256) void recode_zero_kernel(RecodeIO p, int *status, int *stop, uint32_t *tail) {
+    if (mhb::stopped(stop)) return;
+    const uint64_t bytes = p.out_off[p.s.b.n];
+    if (bytes > p.cap) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) { mhb::fail(status, mhk::MHK_STATUS_CAPACITY); atomicExch(stop, 1); }
+        return;
+    }
+    const uint64_t nfull = bytes >> 2;
+    uint32_t *o = reinterpret_cast<uint32_t *>(p.out);
+    for (uint64_t k = mhb::gtid(); k < nfull; k += uint64_t(gridDim.x) * blockDim.x) o[k] = 0u;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *tail = 0u;
+}
+
+__global__ void recode_tail_kernel(RecodeIO p, const uint32_t *tail, const int *stop) {
+    if (mhb::stopped(stop)) return;
+    const uint64_t bytes = p.out_off[p.s.b.n];
+    if (!(bytes & 3u)) return;
+    const uint8_t *t = reinterpret_cast<const uint8_t *>(tail);
+    for (uint64_t b = bytes & ~uint64_t(3); b < bytes; ++b) p.out[b] = t[b & 3u];
+}
+
 // ------------------------------------------------------------------------------------------------ histogram
 
-// Direct-mapped counters in LDS: slot -> (pair, u64 count); a pair that finds its slot taken goes to the 64-bit global
+// Direct-mapped counters in LDS: slot -> (key, u64 count); a key that finds its slot taken goes to the 64-bit global
 // counter.  Counts go up and down (a failed chunk takes its counts back): the sums wrap modulo 2^64 and are exact.
-// nslot == 0: no LDS left, global atomics only.
-struct PairCache {
+// nslot == 0: no LDS left, global atomics only.  The slot hash goes by the key's width: 16 bits, or 24 under W.
+template <bool W> struct KeyCache {
     static constexpr uint32_t EMPTY = 0xFFFFFFFFu;
     unsigned long long *cnt;
     uint32_t *tag;
-    uint32_t shift, nslot;
-    bool o1;
+    uint32_t shift, nslot, mask;
     unsigned long long *g;
     __device__ __forceinline__ void init(unsigned char *smem, uint32_t lds_at, uint32_t log2n, uint32_t order, unsigned long long *counts) {
         nslot = log2n ? 1u << log2n : 0u;
-        shift = 16u - log2n;
+        shift = (W ? 32u : 16u) - log2n;
         cnt = reinterpret_cast<unsigned long long *>(smem + lds_at);
         tag = reinterpret_cast<uint32_t *>(cnt + nslot);
-        o1 = order != 0;
+        mask = W && order == 2u ? 0xFFFFu : (order ? 0xFFu : 0u);
         g = counts;
         for (uint32_t k = threadIdx.x; k < nslot; k += blockDim.x) { tag[k] = EMPTY; cnt[k] = 0ull; }
         __syncthreads();
     }
-    __device__ __forceinline__ void add(uint32_t prev, uint32_t sym, int delta) {
-        const uint32_t p = o1 ? (prev << 8 | sym) : sym;
+    __device__ __forceinline__ uint32_t hash(uint32_t p) const { return W ? (p * 2654435761u) >> shift : ((p * 40503u) & 0xFFFFu) >> shift; }
+    __device__ __forceinline__ void add(uint32_t ctx, uint32_t sym, int delta) {
+        const uint32_t p = W ? ((ctx & mask) << 8) | sym : (mask ? (ctx << 8) | sym : sym);    // (!W: ctx is one byte)
         const unsigned long long d = static_cast<unsigned long long>(static_cast<long long>(delta));
         if (nslot) {
-            const uint32_t slot = o1 ? ((p * 40503u) & 0xFFFFu) >> shift : p;      // (nslot >= 256: order 0 never collides)
+            const uint32_t slot = mask ? hash(p) : p;                              // (nslot >= 256: order 0 never collides)
             uint32_t t = tag[slot];
             if (t == EMPTY) {
                 const uint32_t old = atomicCAS(&tag[slot], EMPTY, p);
@@ -136,38 +291,48 @@ struct PairCache {
     }
 };
 
-// `count` symbols of chunk c from its entry, each pair counted `delta` times (0: decode only); returns the symbols done
-template <bool SHARED>
-__device__ __forceinline__ uint32_t walk_chunk(const Src &s, const Dec<SHARED> &dec, const Chunk &c, uint32_t count, int delta, PairCache &pc,
-                                               uint32_t &used, bool &bad) {
+// `count` symbols of chunk c from its entry, the lane's own counted `delta` times (0: decode only); ext (SEAM only): when
+// these symbols end exactly at the chunk's end, the first symbol of the next chunk is counted too.  Returns the symbols done;
+// used / bad describe the `count` symbols alone.
+template <Model K, bool W>
+__device__ __forceinline__ uint32_t walk_chunk(const Src &s, const Dec<K, W> &dec, const Chunk &c, uint32_t count, bool ext, int delta,
+                                               KeyCache<W> &kc, uint32_t &used, bool &bad) {
     uint64_t bit0;
     const BitSrc src = mhb::stream_src(s.b.payload, s.b.pay_off[c.i], c.nb, bit0);
     BitCursor bc;
     bc.init(src, bit0 + c.start);
-    uint32_t prev = c.ctx, t = 0;
+    uint32_t ctx = c.ctx, t = 0;
     used = 0; bad = false;
     for (; t < count; ++t) {
-        const uint32_t sym = dec.next(s, src, bc, prev, used, bad);
+        const uint32_t sym = dec.next(s, src, bc, ctx, used, bad);
         if (bad) break;
-        if (delta) pc.add(prev, sym, delta);
-        prev = sym;
+        if (delta && owns<SEAM<K, W>>(c, t)) kc.add(ctx, sym, delta);
+        ctx = roll<W>(ctx, sym);
+    }
+    if constexpr (SEAM<K, W>) {
+        if (ext && !c.last && !bad && used == c.end - c.start) {
+            uint32_t u2 = used;
+            bool b2 = false;
+            const uint32_t sym = dec.next(s, src, bc, ctx, u2, b2);
+            if (!b2 && delta) kc.add(ctx, sym, delta);
+        }
     }
     return t;
 }
 
-template <bool SHARED, bool FIX>
-__global__ __launch_bounds__(SHARED ? NT_SHARED : NT_EACH) void histc_idx_kernel(HistParams p, uint64_t nwork, uint32_t lds_at, uint32_t log2n,
-                                                                               int *status, const int *stop) {
+template <Model K, bool W, bool FIX>
+__global__ __launch_bounds__((Dec<K, W>::NT)) void histc_idx_kernel(HistParams p, uint64_t nwork, uint32_t lds_at, uint32_t log2n, int *status,
+                                                                  const int *stop) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     if (stopped(stop)) return;
     if (FIX && *reinterpret_cast<const volatile int *>(status) == 0) return;      // no stream failed: nothing to take back
-    Dec<SHARED> dec(p.s, smem);
-    PairCache pc;
-    pc.init(smem, lds_at, log2n, p.order, p.counts);
+    Dec<K, W> dec(p.s, smem);
+    KeyCache<W> kc;
+    kc.init(smem, lds_at, log2n, p.order, p.counts);
     for (uint64_t base = uint64_t(blockIdx.x) * blockDim.x; base < nwork; base += uint64_t(gridDim.x) * blockDim.x) {
         const uint64_t w = base + threadIdx.x;
         Chunk c;
-        if (w < nwork && chunk_of<false>(p.s.b, w, c)) {
+        if (w < nwork && chunk_of<K, W>(p.s, w, c)) {
             dec.stream(p.s, c.i);
             const int verdict = p.s.b.stream_status[c.i];
             uint32_t used; bool bad;
@@ -175,52 +340,51 @@ __global__ __launch_bounds__(SHARED ? NT_SHARED : NT_EACH) void histc_idx_kernel
                 if (!c.entry_ok()) {
                     stream_fail(p.s.b, status, c.i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT);
                 } else {
-                    const uint32_t done = walk_chunk<SHARED>(p.s, dec, c, c.nsym, 1, pc, used, bad);
-                    if (bad || used != c.end - c.start) {
+                    const uint32_t done = walk_chunk<K, W>(p.s, dec, c, c.nsym, true, 1, kc, used, bad);
+                    if (bad || used != c.end - c.start) {           // (the extra symbol was not counted)
                         stream_fail(p.s.b, status, c.i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT);
-                        walk_chunk<SHARED>(p.s, dec, c, done, -1, pc, used, bad);
+                        walk_chunk<K, W>(p.s, dec, c, done, false, -1, kc, used, bad);
                     }
                 }
             }
             if (FIX && verdict == MH_ERR_CORRUPT && c.entry_ok()) {               // (a chunk that failed has taken its counts back)
-                walk_chunk<SHARED>(p.s, dec, c, c.nsym, 0, pc, used, bad);
-                if (!bad && used == c.end - c.start) walk_chunk<SHARED>(p.s, dec, c, c.nsym, -1, pc, used, bad);
+                walk_chunk<K, W>(p.s, dec, c, c.nsym, false, 0, kc, used, bad);
+                if (!bad && used == c.end - c.start) walk_chunk<K, W>(p.s, dec, c, c.nsym, true, -1, kc, used, bad);
             }
         }
     }
-    pc.flush();
+    kc.flush();
 }
 
-// at most `limit` symbols of stream i from bit 0, each pair counted `delta` times; returns the symbols done
-template <bool SHARED>
-__device__ __forceinline__ uint64_t walk_stream(const Src &s, const Dec<SHARED> &dec, uint64_t i, uint64_t nb, uint64_t limit, int delta,
-                                                PairCache &pc, uint32_t &used, bool &bad) {
+// at most `limit` symbols of stream i from bit 0, each counted `delta` times; returns the symbols done
+template <Model K, bool W>
+__device__ __forceinline__ uint64_t walk_stream(const Src &s, const Dec<K, W> &dec, uint64_t i, uint64_t nb, uint64_t limit, int delta,
+                                                KeyCache<W> &kc, uint32_t &used, bool &bad) {
     uint64_t bit0;
     const BitSrc src = mhb::stream_src(s.b.payload, s.b.pay_off[i], nb, bit0);
     BitCursor bc;
     bc.init(src, bit0);
-    uint32_t prev = s.b.prev0;
+    uint32_t ctx = start_ctx<K, W>(s);
     uint64_t k = 0;
     used = 0; bad = false;
     // every code has at least one bit: at most nb steps (src/coding.cpp:124 — decode while bits remain)
     while (used < nb && k < limit) {
-        const uint32_t sym = dec.next(s, src, bc, prev, used, bad);
+        const uint32_t sym = dec.next(s, src, bc, ctx, used, bad);
         if (bad) break;
-        pc.add(prev, sym, delta);
-        prev = sym;
+        kc.add(ctx, sym, delta);
+        ctx = roll<W>(ctx, sym);
         ++k;
     }
     return k;
 }
 
-template <bool SHARED>
-__global__ __launch_bounds__(SHARED ? NT_SHARED : NT_EACH) void histc_walk_kernel(HistParams p, uint32_t lds_at, uint32_t log2n, int *status,
-                                                                                const int *stop) {
+template <Model K, bool W>
+__global__ __launch_bounds__((Dec<K, W>::NT)) void histc_walk_kernel(HistParams p, uint32_t lds_at, uint32_t log2n, int *status, const int *stop) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     if (stopped(stop)) return;
-    Dec<SHARED> dec(p.s, smem);
-    PairCache pc;
-    pc.init(smem, lds_at, log2n, p.order, p.counts);
+    Dec<K, W> dec(p.s, smem);
+    KeyCache<W> kc;
+    kc.init(smem, lds_at, log2n, p.order, p.counts);
     const uint64_t n = p.s.b.n;
     for (uint64_t base = uint64_t(blockIdx.x) * blockDim.x; base < n; base += uint64_t(gridDim.x) * blockDim.x) {
         const uint64_t i = base + threadIdx.x;
@@ -231,54 +395,74 @@ __global__ __launch_bounds__(SHARED ? NT_SHARED : NT_EACH) void histc_walk_kerne
             } else {
                 dec.stream(p.s, i);
                 uint32_t used; bool bad;
-                const uint64_t done = walk_stream<SHARED>(p.s, dec, i, nb, ~uint64_t(0), 1, pc, used, bad);
+                const uint64_t done = walk_stream<K, W>(p.s, dec, i, nb, ~uint64_t(0), 1, kc, used, bad);
                 if (bad || used != nb) {                            // src/coding.cpp:158: the stream ends exactly at nbits
                     stream_fail(p.s.b, status, i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT);
-                    walk_stream<SHARED>(p.s, dec, i, nb, done, -1, pc, used, bad);
+                    walk_stream<K, W>(p.s, dec, i, nb, done, -1, kc, used, bad);
                 }
             }
         }
     }
-    pc.flush();
+    kc.flush();
 }
 
 // ------------------------------------------------------------------------------------------------ re-code
 
-template <bool SHARED, bool DLDS>
-__global__ __launch_bounds__(SHARED ? NT_SHARED : NT_EACH) void recode_idx_len_kernel(RecodeParams p, uint64_t nwork, uint32_t lds_at,
-                                                                                    unsigned long long *cbits, uint32_t *cdrop, int *status,
-                                                                                    const int *stop) {
+template <Model K, bool DLDS, bool W>
+__global__ __launch_bounds__((Dec<K, W>::NT)) void recode_idx_len_kernel(RecodeParams p, uint64_t nwork, uint32_t lds_at, unsigned long long *cbits,
+                                                                       uint32_t *cdrop, uint32_t *chead, uint32_t *cclose, int *status,
+                                                                       const int *stop) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     if (stopped(stop)) return;
-    Dec<SHARED> dec(p.s, smem);
-    const Lens<DLDS> L(p.dst, smem, lds_at);
+    Dec<K, W> dec(p.s, smem);
+    const Enc<DLDS, W> E(p.dst, smem, lds_at);
     for (uint64_t w = gtid(); w < nwork; w += uint64_t(gridDim.x) * blockDim.x) {
         Chunk c;
-        if (!chunk_of<false>(p.s.b, w, c) || p.s.b.stream_status[c.i] == MH_ERR_ARG) continue;
+        if (!chunk_of<K, W>(p.s, w, c) || p.s.b.stream_status[c.i] == MH_ERR_ARG) continue;
         if (!c.entry_ok()) { stream_fail(p.s.b, status, c.i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT); continue; }
         uint64_t bit0;
         const BitSrc src = mhb::stream_src(p.s.b.payload, p.s.b.pay_off[c.i], c.nb, bit0);
         BitCursor bc;
         bc.init(src, bit0 + c.start);
         dec.stream(p.s, c.i);
-        uint32_t prev = c.ctx, used = 0, bits = 0, drops = 0;
+        uint32_t ctx = c.ctx, used = 0, bits = 0, drops = 0;
         bool bad = false;
         for (uint32_t t = 0; t < c.nsym && !bad; ++t) {
-            const uint32_t sym = dec.next(p.s, src, bc, prev, used, bad);
+            const uint32_t sym = dec.next(p.s, src, bc, ctx, used, bad);
             if (bad) break;
-            const uint32_t l = L(L.at(prev, sym));
-            bits += l;
-            drops += l == 0u;
-            prev = sym;
+            if (owns<SEAM<K, W>>(c, t)) {
+                const uint32_t l = E.len(E.at(ctx, sym));
+                bits += l;
+                drops += l == 0u;
+            }
+            ctx = roll<W>(ctx, sym);
         }
         if (bad || used != c.end - c.start) { stream_fail(p.s.b, status, c.i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT); continue; }
+        if constexpr (SEAM<K, W>) {
+            if (!c.last) {
+                // the next chunk's first symbol, whose two context bytes only this lane knows.  No verdict: when the stream
+                // passes, the next chunk's lane decoded the same bits in the same context.
+                cclose[w] = ctx;
+                uint32_t u2 = used;
+                bool b2 = false;
+                const uint32_t sym = dec.next(p.s, src, bc, ctx, u2, b2);
+                if (!b2) {
+                    const uint32_t l = E.len(E.at(ctx, sym));
+                    chead[w] = l;
+                    drops += l == 0u;
+                }
+            }
+        }
         cbits[w] = bits;
         cdrop[w] = drops;
     }
 }
 
+// the chunks of failed streams count 0 bits; chunk k of the others: its own bits and, behind a seam, its first symbol's,
+// which the lane in front priced; the dropped symbols go to dropped[i]
+template <bool SEAM_>
 __global__ __launch_bounds__(256) void recode_comb_kernel(RecodeParams p, uint64_t nwork, unsigned long long *cbits, const uint32_t *cdrop,
-                                                          const int *stop) {
+                                                          const uint32_t *chead, const int *stop) {
     if (stopped(stop)) return;
     const uint64_t w = gtid();
     if (w > nwork) return;
@@ -291,6 +475,7 @@ __global__ __launch_bounds__(256) void recode_comb_kernel(RecodeParams p, uint64
             const uint64_t k = w - ((a >> cs) + i);
             if ((k << cs) < ni && p.s.b.stream_status[i] == MH_OK) {
                 v = cbits[w];
+                if constexpr (SEAM_) v += k ? chead[w - 1] : 0u;
                 const uint32_t d = cdrop[w];
                 if (d && p.dropped) atomicAdd(&p.dropped[i], static_cast<unsigned long long>(d));
             }
@@ -299,39 +484,45 @@ __global__ __launch_bounds__(256) void recode_comb_kernel(RecodeParams p, uint64
     cbits[w] = v;
 }
 
-template <bool SHARED, bool DLDS>
-__global__ __launch_bounds__(SHARED ? NT_SHARED : NT_EACH) void recode_idx_emit_kernel(RecodeParams p, uint64_t nwork, uint32_t lds_at,
-                                                                                     const unsigned long long *cbase, uint32_t *tail,
-                                                                                     const int *stop) {
+template <Model K, bool DLDS, bool W>
+__global__ __launch_bounds__((Dec<K, W>::NT)) void recode_idx_emit_kernel(RecodeParams p, uint64_t nwork, uint32_t lds_at,
+                                                                        const unsigned long long *cbase, const uint32_t *chead,
+                                                                        const uint32_t *cclose, uint32_t *tail, const int *stop) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     if (stopped(stop)) return;
-    Dec<SHARED> dec(p.s, smem);
-    const Lens<DLDS> L(p.dst, smem, lds_at);
+    Dec<K, W> dec(p.s, smem);
+    const Enc<DLDS, W> E(p.dst, smem, lds_at);
     const uint64_t bytes = p.out_off[p.s.b.n];
     const uint64_t tail_w = (bytes & 3u) ? bytes >> 2 : ~uint64_t(0);
     const uint32_t cs = p.s.b.chunk_shift;
     for (uint64_t w = gtid(); w < nwork; w += uint64_t(gridDim.x) * blockDim.x) {
         Chunk c;
-        if (!chunk_of<false>(p.s.b, w, c) || p.s.b.stream_status[c.i] != MH_OK) continue;
+        if (!chunk_of<K, W>(p.s, w, c) || p.s.b.stream_status[c.i] != MH_OK) continue;
         const unsigned long long b0 = cbase[w];
         const uint64_t rel = b0 - cbase[(p.s.b.sym_off[c.i] >> cs) + c.i];          // relative to the stream's own payload
-        if (p.out_index) p.out_index[w] = (uint64_t(c.ctx) << 56) | rel;
-        if (!p.out || cbase[w + 1] == b0) continue;
+        const bool seam = SEAM<K, W> && c.first != 0u;                              // symbol 0 is the lane's in front
+        if (p.out_index) p.out_index[w] = E.entry(seam ? cclose[w - 1] : c.ctx, rel);
+        if (!p.out) continue;
+        if constexpr (!SEAM<K, W>) { if (cbase[w + 1] == b0) continue; }            // (SEAM: the lane's codes are not the chunk's)
         uint64_t bit0;
         const BitSrc src = mhb::stream_src(p.s.b.payload, p.s.b.pay_off[c.i], c.nb, bit0);
         BitCursor bc;
         bc.init(src, bit0 + c.start);
         dec.stream(p.s, c.i);
         BitWriter bw;
-        bw.init(reinterpret_cast<uint32_t *>(p.out), tail, tail_w, uint64_t(p.out_off[c.i]) * 8u + rel);
-        uint32_t prev = c.ctx, used = 0;
+        bw.init(reinterpret_cast<uint32_t *>(p.out), tail, tail_w, uint64_t(p.out_off[c.i]) * 8u + rel + (seam ? chead[w - 1] : 0u));
+        uint32_t ctx = c.ctx, used = 0;
         bool bad = false;
         for (uint32_t t = 0; t < c.nsym && !bad; ++t) {            // (the stream passed: bad stays false)
-            const uint32_t sym = dec.next(p.s, src, bc, prev, used, bad);
-            const uint32_t at = L.at(prev, sym);
-            const uint32_t l = L(at);
-            if (l) bw.code(p.dst.code64[at], l);                    // 0: the pair has no code, skipped (mh_model.hpp:21)
-            prev = sym;
+            const uint32_t sym = dec.next(p.s, src, bc, ctx, used, bad);
+            if (owns<SEAM<K, W>>(c, t)) E.put(bw, E.at(ctx, sym), true);
+            ctx = roll<W>(ctx, sym);
+        }
+        if constexpr (SEAM<K, W>) {
+            if (!c.last && !bad) {
+                const uint32_t sym = dec.next(p.s, src, bc, ctx, used, bad);
+                E.put(bw, E.at(ctx, sym), !bad);
+            }
         }
         bw.finish();
     }
@@ -339,13 +530,12 @@ __global__ __launch_bounds__(SHARED ? NT_SHARED : NT_EACH) void recode_idx_emit_
 
 // EMIT = false: the stream's verdict, its symbols into sym_off[i] (scanned next), its dst bits and dropped symbols;
 // true: its codes from out_off[i] and its index entries
-template <bool SHARED, bool DLDS, bool EMIT>
-__global__ __launch_bounds__(SHARED ? NT_SHARED : NT_EACH) void recode_walk_kernel(RecodeParams p, uint32_t lds_at, uint32_t *tail, int *status,
-                                                                                 const int *stop) {
+template <Model K, bool DLDS, bool W, bool EMIT>
+__global__ __launch_bounds__((Dec<K, W>::NT)) void recode_walk_kernel(RecodeParams p, uint32_t lds_at, uint32_t *tail, int *status, const int *stop) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     if (stopped(stop)) return;
-    Dec<SHARED> dec(p.s, smem);
-    const Lens<DLDS> L(p.dst, smem, lds_at);
+    Dec<K, W> dec(p.s, smem);
+    const Enc<DLDS, W> E(p.dst, smem, lds_at);
     const uint64_t n = p.s.b.n;
     const uint64_t bytes = EMIT ? p.out_off[n] : 0;
     const uint64_t tail_w = (bytes & 3u) ? bytes >> 2 : ~uint64_t(0);
@@ -369,21 +559,24 @@ __global__ __launch_bounds__(SHARED ? NT_SHARED : NT_EACH) void recode_walk_kern
         dec.stream(p.s, i);
         BitWriter bw;
         if (EMIT && p.out) bw.init(reinterpret_cast<uint32_t *>(p.out), tail, tail_w, uint64_t(p.out_off[i]) * 8u);
-        uint32_t prev = p.s.b.prev0, used = 0;
+        uint32_t ctx = start_ctx<K, W>(p.s), used = 0;
         bool bad = false;
         uint64_t k = 0, bits = 0, drops = 0;
         // every code has at least one bit: at most nb steps (src/coding.cpp:124 — decode while bits remain)
         while (used < nb && !bad && k < count) {
-            if (EMIT && p.out_index && (k & ((uint64_t(1) << ocs) - 1u)) == 0)
-                p.out_index[(a >> ocs) + i + (k >> ocs)] = (uint64_t(prev) << 56) | bits;
-            const uint32_t sym = dec.next(p.s, src, bc, prev, used, bad);
+            if (EMIT && p.out_index && (k & ((uint64_t(1) << ocs) - 1u)) == 0) p.out_index[(a >> ocs) + i + (k >> ocs)] = E.entry(ctx, bits);
+            const uint32_t sym = dec.next(p.s, src, bc, ctx, used, bad);
             if (bad) break;
-            const uint32_t at = L.at(prev, sym);
-            const uint32_t l = L(at);
-            if (EMIT) { if (l && p.out) bw.code(p.dst.code64[at], l); }
-            else drops += l == 0u;
+            const uint32_t key = E.at(ctx, sym);
+            uint32_t l;
+            if (EMIT) {
+                l = E.put(bw, key, p.out != nullptr);
+            } else {
+                l = E.len(key);
+                drops += l == 0u;
+            }
             bits += l;
-            prev = sym;
+            ctx = roll<W>(ctx, sym);
             ++k;
         }
         if (EMIT) { if (p.out) bw.finish(); continue; }
@@ -394,74 +587,81 @@ __global__ __launch_bounds__(SHARED ? NT_SHARED : NT_EACH) void recode_walk_kern
     }
 }
 
-template <bool SHARED>
-hipError_t launch_hist(const HistParams &p, size_t lds_tables, void *d_ws, hipStream_t st) {
-    constexpr int NT = SHARED ? NT_SHARED : NT_EACH;
-    constexpr int PER_CU = SHARED ? 1 : 8;
-    // the counters take what the tables leave, 12 bytes a slot: 256 .. 4096 slots (a model set: 1024), or none
+// ------------------------------------------------------------------------------------------------ launches
+
+template <Model K, bool W>
+hipError_t launch_hist(const HistParams &p, void *d_ws, hipStream_t st) {
+    constexpr int NT = Dec<K, W>::NT, PER_CU = Dec<K, W>::PER_CU;
+    constexpr bool LDS_TABLES = K == Model::Shared;
+    const size_t lds_tables = LDS_TABLES ? mhb::tables_lds(p.s.b) : 0;
+    if (lds_tables > size_t(LDS_MAX)) return hipErrorInvalidValue;
+    // the counters take what the tables leave, 12 bytes a slot: 256 .. 4096 slots (tables in L2, eight workgroups per CU:
+    // 1024), or none
     uint32_t log2n = 0;
-    const size_t room = SHARED ? size_t(LDS_MAX) - lds_tables : size_t(12288);
+    const size_t room = LDS_TABLES ? size_t(LDS_MAX) - lds_tables : size_t(12288);
     for (uint32_t k = 8; k <= 12; ++k)
         if ((size_t(12) << k) <= room) log2n = k;
     const size_t lds = lds_tables + (log2n ? size_t(12) << log2n : 0);
     const uint32_t lds_at = uint32_t(lds_tables);
-    if (SHARED) {
-        hipError_t attr = mhk::allow_lds(reinterpret_cast<const void *>(histc_idx_kernel<SHARED, false>), LDS_MAX);
-        if (attr == hipSuccess) attr = mhk::allow_lds(reinterpret_cast<const void *>(histc_idx_kernel<SHARED, true>), LDS_MAX);
-        if (attr == hipSuccess) attr = mhk::allow_lds(reinterpret_cast<const void *>(histc_walk_kernel<SHARED>), LDS_MAX);
+    if (LDS_TABLES) {
+        hipError_t attr = mhk::allow_lds(reinterpret_cast<const void *>(histc_idx_kernel<K, W, false>), LDS_MAX);
+        if (attr == hipSuccess) attr = mhk::allow_lds(reinterpret_cast<const void *>(histc_idx_kernel<K, W, true>), LDS_MAX);
+        if (attr == hipSuccess) attr = mhk::allow_lds(reinterpret_cast<const void *>(histc_walk_kernel<K, W>), LDS_MAX);
         if (attr != hipSuccess) return attr;
     }
     unsigned char *ws = static_cast<unsigned char *>(d_ws);
     const uint64_t n = p.s.b.n;
     int *status = reinterpret_cast<int *>(ws), *stop = status + 1;
+    const size_t ncounts = p.order == 2u ? (size_t(1) << 24) : (p.order ? 65536u : 256u);
     hipError_t e = hipMemsetAsync(ws, 0, 64, st);
-    if (e == hipSuccess) e = hipMemsetAsync(p.counts, 0, (p.order ? 65536u : 256u) * sizeof(unsigned long long), st);
+    if (e == hipSuccess) e = hipMemsetAsync(p.counts, 0, ncounts * sizeof(unsigned long long), st);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(histc_check_kernel, grid_threads(n + 1, 256), dim3(256), 0, st, p.s, status, stop);
     if (p.s.b.index) {
-        const uint64_t W = mhb::work_items(n, p.s.b.sym_total, 1u << p.s.b.chunk_shift);
-        hipLaunchKernelGGL((histc_idx_kernel<SHARED, false>), dim3(grid_for(W, NT, PER_CU)), dim3(NT), lds, st, p, W, lds_at, log2n, status, stop);
-        hipLaunchKernelGGL((histc_idx_kernel<SHARED, true>), dim3(grid_for(W, NT, PER_CU)), dim3(NT), lds, st, p, W, lds_at, log2n, status, stop);
+        const uint64_t nw = mhb::work_items(n, p.s.b.sym_total, 1u << p.s.b.chunk_shift);
+        hipLaunchKernelGGL((histc_idx_kernel<K, W, false>), dim3(grid_for(nw, NT, PER_CU)), dim3(NT), lds, st, p, nw, lds_at, log2n, status, stop);
+        hipLaunchKernelGGL((histc_idx_kernel<K, W, true>), dim3(grid_for(nw, NT, PER_CU)), dim3(NT), lds, st, p, nw, lds_at, log2n, status, stop);
         return hipGetLastError();
     }
-    hipLaunchKernelGGL((histc_walk_kernel<SHARED>), dim3(grid_for(n + 1, NT, PER_CU)), dim3(NT), lds, st, p, lds_at, log2n, status, stop);
+    hipLaunchKernelGGL((histc_walk_kernel<K, W>), dim3(grid_for(n + 1, NT, PER_CU)), dim3(NT), lds, st, p, lds_at, log2n, status, stop);
     return hipGetLastError();
 }
 
-template <bool SHARED, bool DLDS>
+template <Model K, bool DLDS, bool W>
 hipError_t launch_rc(const RecodeParams &p, size_t lds_tables, void *d_ws, hipStream_t st) {
-    constexpr int NT = SHARED ? NT_SHARED : NT_EACH;
-    constexpr int PER_CU = SHARED ? 1 : 8;
+    constexpr int NT = Dec<K, W>::NT, PER_CU = Dec<K, W>::PER_CU;
     const size_t lds = lds_tables + (DLDS ? (p.dst.ctx_mask ? 65536 : 256) : 0);
     const uint32_t lds_at = uint32_t(lds_tables);
-    if (SHARED) {
-        hipError_t attr = mhk::allow_lds(reinterpret_cast<const void *>(recode_idx_len_kernel<SHARED, DLDS>), LDS_MAX);
-        if (attr == hipSuccess) attr = mhk::allow_lds(reinterpret_cast<const void *>(recode_idx_emit_kernel<SHARED, DLDS>), LDS_MAX);
-        if (attr == hipSuccess) attr = mhk::allow_lds(reinterpret_cast<const void *>(recode_walk_kernel<SHARED, DLDS, false>), LDS_MAX);
-        if (attr == hipSuccess) attr = mhk::allow_lds(reinterpret_cast<const void *>(recode_walk_kernel<SHARED, DLDS, true>), LDS_MAX);
+    if (K == Model::Shared) {
+        hipError_t attr = mhk::allow_lds(reinterpret_cast<const void *>(recode_idx_len_kernel<K, DLDS, W>), LDS_MAX);
+        if (attr == hipSuccess) attr = mhk::allow_lds(reinterpret_cast<const void *>(recode_idx_emit_kernel<K, DLDS, W>), LDS_MAX);
+        if (attr == hipSuccess) attr = mhk::allow_lds(reinterpret_cast<const void *>(recode_walk_kernel<K, DLDS, W, false>), LDS_MAX);
+        if (attr == hipSuccess) attr = mhk::allow_lds(reinterpret_cast<const void *>(recode_walk_kernel<K, DLDS, W, true>), LDS_MAX);
         if (attr != hipSuccess) return attr;
     }
     unsigned char *ws = static_cast<unsigned char *>(d_ws);
     const uint64_t n = p.s.b.n;
-    const uint64_t W = p.s.b.index ? mhb::work_items(n, p.s.b.sym_total, 1u << p.s.b.chunk_shift) : 0;
-    const RecodeLayout L = recode_layout(n, W);
+    const uint64_t nw = p.s.b.index ? mhb::work_items(n, p.s.b.sym_total, 1u << p.s.b.chunk_shift) : 0;
+    const RecodeLayout L = recode_layout(n, nw, SEAM<K, W>);
     int *status = reinterpret_cast<int *>(ws), *stop = status + 1;
     uint32_t *tail = reinterpret_cast<uint32_t *>(ws + TAIL_AT);
     auto *cbits = reinterpret_cast<unsigned long long *>(ws + L.off_bits);
     auto *cdrop = reinterpret_cast<uint32_t *>(ws + L.off_drop);
+    uint32_t *chead = SEAM<K, W> ? reinterpret_cast<uint32_t *>(ws + L.off_head) : nullptr;
+    uint32_t *cclose = SEAM<K, W> ? reinterpret_cast<uint32_t *>(ws + L.off_close) : nullptr;
     auto *sums = reinterpret_cast<unsigned long long *>(ws + L.off_sums);
     hipError_t e = hipMemsetAsync(ws, 0, 64, st);
-    if (e == hipSuccess && W) e = hipMemsetAsync(ws + L.off_bits, 0, L.off_sums - L.off_bits, st);    // chunk bits and dropped counts
+    if (e == hipSuccess && nw) e = hipMemsetAsync(ws + L.off_bits, 0, L.off_sums - L.off_bits, st);   // chunk bits, dropped counts, heads
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(recode_check_kernel, grid_threads(n + 1, 256), dim3(256), 0, st, p, status, stop);
     if (p.s.b.index) {
-        hipLaunchKernelGGL((recode_idx_len_kernel<SHARED, DLDS>), dim3(grid_for(W, NT, PER_CU)), dim3(NT), lds, st, p, W, lds_at, cbits, cdrop,
-                           status, stop);
-        hipLaunchKernelGGL(recode_comb_kernel, grid_threads(W + 1, 256), dim3(256), 0, st, p, W, cbits, cdrop, stop);
-        if ((e = scan_exclusive(cbits, W + 1, sums, stop, st)) != hipSuccess) return e;
+        hipLaunchKernelGGL((recode_idx_len_kernel<K, DLDS, W>), dim3(grid_for(nw, NT, PER_CU)), dim3(NT), lds, st, p, nw, lds_at, cbits, cdrop,
+                           chead, cclose, status, stop);
+        hipLaunchKernelGGL((recode_comb_kernel<SEAM<K, W>>), grid_threads(nw + 1, 256), dim3(256), 0, st, p, nw, cbits, cdrop, chead, stop);
+        if ((e = scan_exclusive(cbits, nw + 1, sums, stop, st)) != hipSuccess) return e;
     } else {
-        hipLaunchKernelGGL((recode_walk_kernel<SHARED, DLDS, false>), dim3(grid_for(n + 1, NT, PER_CU)), dim3(NT), lds, st, p, lds_at, tail, status,
-                           stop);
+        hipLaunchKernelGGL((recode_walk_kernel<K, DLDS, W, false>), dim3(grid_for(n + 1, NT, PER_CU)), dim3(NT), lds, st, p, lds_at, tail,
+                           status, stop);
         if ((e = scan_exclusive(p.s.b.sym_off, n + 1, sums, stop, st)) != hipSuccess) return e;
     }
     hipLaunchKernelGGL(recode_sizes_kernel, grid_threads(n + 1, 256), dim3(256), 0, st, p, cbits, stop);
@@ -470,11 +670,11 @@ hipError_t launch_rc(const RecodeParams &p, size_t lds_tables, void *d_ws, hipSt
     if (p.out) hipLaunchKernelGGL(recode_zero_kernel, dim3(grid_for(p.cap / 4 + 1, 256, 8)), dim3(256), 0, st, p, status, stop, tail);
     if (p.s.b.index) {
         if (p.out || p.out_index)
-            hipLaunchKernelGGL((recode_idx_emit_kernel<SHARED, DLDS>), dim3(grid_for(W, NT, PER_CU)), dim3(NT), lds, st, p, W, lds_at, cbits, tail,
-                               stop);
+            hipLaunchKernelGGL((recode_idx_emit_kernel<K, DLDS, W>), dim3(grid_for(nw, NT, PER_CU)), dim3(NT), lds, st, p, nw, lds_at, cbits,
+                               chead, cclose, tail, stop);
     } else if (p.out || p.out_index) {
-        hipLaunchKernelGGL((recode_walk_kernel<SHARED, DLDS, true>), dim3(grid_for(n + 1, NT, PER_CU)), dim3(NT), lds, st, p, lds_at, tail, status,
-                           stop);
+        hipLaunchKernelGGL((recode_walk_kernel<K, DLDS, W, true>), dim3(grid_for(n + 1, NT, PER_CU)), dim3(NT), lds, st, p, lds_at, tail,
+                           status, stop);
     }
     if (p.out) hipLaunchKernelGGL(recode_tail_kernel, dim3(1), dim3(1), 0, st, p, tail, stop);
     return hipGetLastError();
@@ -482,20 +682,27 @@ hipError_t launch_rc(const RecodeParams &p, size_t lds_tables, void *d_ws, hipSt
 
 }  // namespace
 
-hipError_t launch_histogram_coded(const HistParams &p, bool shared, void *d_ws, hipStream_t st) {
-    if (!shared) return launch_hist<false>(p, 0, d_ws, st);
-    const size_t lds = mhb::tables_lds(p.s.b);
-    if (lds > size_t(LDS_MAX)) return hipErrorInvalidValue;
-    return launch_hist<true>(p, lds, d_ws, st);
+hipError_t launch_histogram_coded(const HistParams &p, Model model, void *d_ws, hipStream_t st) {
+    if (model == Model::Shared2) return launch_hist<Model::Shared2, true>(p, d_ws, st);
+    if (model == Model::Set) return p.order == 2u ? hipErrorInvalidValue : launch_hist<Model::Set, false>(p, d_ws, st);
+    return p.order == 2u ? launch_hist<Model::Shared, true>(p, d_ws, st) : launch_hist<Model::Shared, false>(p, d_ws, st);
 }
 
-hipError_t launch_recode(const RecodeParams &p, bool shared, void *d_ws, hipStream_t st) {
-    // a model set's tables stay in L2 and eight workgroups share a CU: only an order-0 image (256 B) goes to LDS
-    if (!shared) return p.dst.ctx_mask ? launch_rc<false, false>(p, 0, d_ws, st) : launch_rc<false, true>(p, 0, d_ws, st);
+hipError_t launch_recode(const RecodeParams &p, Model model, void *d_ws, hipStream_t st) {
+    const bool dst2 = p.dst.ctx_mask == 0xFFFFu;
+    // tables in L2 and eight workgroups to a CU: of the destination only an order-0 image (256 B) goes to LDS, and that
+    // under a model set alone
+    if (model == Model::Shared2) return launch_rc<Model::Shared2, false, true>(p, 0, d_ws, st);
+    if (model == Model::Set) {
+        if (dst2) return hipErrorInvalidValue;
+        return p.dst.ctx_mask ? launch_rc<Model::Set, false, false>(p, 0, d_ws, st) : launch_rc<Model::Set, true, false>(p, 0, d_ws, st);
+    }
     const size_t lds = mhb::tables_lds(p.s.b);
     if (lds > size_t(LDS_MAX)) return hipErrorInvalidValue;
+    if (dst2) return launch_rc<Model::Shared, false, true>(p, lds, d_ws, st);
     const size_t img = p.dst.ctx_mask ? 65536 : 256;
-    return lds + img <= size_t(LDS_MAX) ? launch_rc<true, true>(p, lds, d_ws, st) : launch_rc<true, false>(p, lds, d_ws, st);
+    return lds + img <= size_t(LDS_MAX) ? launch_rc<Model::Shared, true, false>(p, lds, d_ws, st)
+                                        : launch_rc<Model::Shared, false, false>(p, lds, d_ws, st);
 }
 
 }  // namespace mhr

@@ -364,3 +364,112 @@ def test_order2_and_wrong_set_size_are_refused_on_the_card(mhc, ragged):
     with pytest.raises(mhc.MhError) as e:
         ms.recode(src.model, src.payload, src.pay_off, src.nbits, **src.kw(True))
     assert e.value.status == mhc.MH_ERR_ARG
+
+
+# ---- every branch of the two launchers -----------------------------------------------------------------------------------------
+# Which kernels a call runs depends on the LDS the shared source model's decode tables take (mhb::tables_lds): the destination's
+# code lengths come from an LDS image behind the tables when it fits into the 160 KiB, else from L2, and the histogram's counter
+# cache takes 12 << log2n bytes of what the tables leave (none when less than 3 KiB are left).  A model set keeps its tables in
+# L2: an order-0 image, lengths of an order-1 destination from L2, 1 << 10 counters.
+
+LDS_MAX = 163840
+BRANCH_LENS = [0, 1, 255, 256, 257, 1300]      # at chunk 256: empty, a short chunk, a chunk that ends on the boundary, one past, several
+
+
+def zipf_counts(s, k=256, scale=1 << 20):
+    return (np.floor(scale / np.arange(1, k + 1) ** s) + 1).astype(np.uint64)
+
+
+def zipf_below(k, n, seed):
+    """n iid Zipf symbols below k."""
+    rng = np.random.default_rng(seed)
+    w = 1.0 / np.arange(1, k + 1) ** 1.1
+    return rng.choice(k, size=n, p=w / w.sum()).astype(np.uint8).tobytes()
+
+
+def deep_context_source(seed_base):
+    """P = 7 with a small second level.  Context 0 has seventeen subtrees at depth 8, each a chain of eight more levels (the
+    weights are dyadic, scaled apart by a thousandth per chain so that no tie lets the tree builder balance them): their
+    second-level tables at P = 8 would take 17 * 256 entries, more than one context may have, while at P = 7 they pair up into nine
+    tables.  Every other context has 128 symbols of 7 bits and no second level."""
+    row = []
+    for j in range(17):
+        row += [(1 << (16 - d)) * (1000 + j) for d in (9, 10, 11, 12, 13, 14, 15, 16, 16)]
+    row += [(1 << (16 - d)) * 1008 for d in (1, 2, 3, 5, 6, 7, 8)]
+    c = np.zeros((256, 256), dtype=np.uint64)
+    c[:, :128] = 1
+    c[0, :] = 0
+    c[0, :len(row)] = row
+    msgs = []
+    for i, n in enumerate(BRANCH_LENS):
+        rng = np.random.default_rng(seed_base + i)
+        m = rng.integers(1, 128, n, dtype=np.uint8)                    # contexts 1..127: any symbol below 128 has a code
+        at = np.arange(3, n - 1, 7)
+        m[at] = 0                                                      # context 0: all 160 symbols, the 16-bit ones among them
+        m[at + 1] = rng.integers(0, len(row), at.size, dtype=np.uint8)
+        msgs.append(m.tobytes())                                       # (behind a symbol >= 128 comes one below 128 again)
+    return c, msgs
+
+
+def branch_source(kind):
+    """(counts of the source model, messages, (P, table bytes in LDS)) for one launcher branch."""
+    c = np.zeros((256, 256), dtype=np.uint64)
+    if kind == "P7_SMALL":
+        c, msgs = deep_context_source(900)
+        return c, msgs, (7, 1024 + (512 << 7) + 2 * 9 * 256)
+    if kind == "P8":                              # forty symbols, codes up to 9 bits: a small second level beside a full first level
+        c[:40, :40] = zipf_counts(1.5, 40)
+        k, want = 40, (8, None)
+    elif kind == "P7_FULL":                       # 96 contexts of 256 Zipf symbols: the tables leave less than 3 KiB
+        c[:96] = zipf_counts(1.1)
+        c[96:, 0] = 1
+        k, want = 96, (7, None)
+    else:
+        raise ValueError(kind)
+    return c, [zipf_below(k, n, 910 + i) for i, n in enumerate(BRANCH_LENS)], want
+
+
+def tables_lds(model):
+    P, nsec, in_lds = model.decode_layout()
+    return P, 1024 + (512 << P) + (((2 * nsec + 15) & ~15) if in_lds else 0)
+
+
+def counter_log2n(room):
+    return max([k for k in range(8, 13) if (12 << k) <= room], default=0)
+
+
+@pytest.fixture(scope="module")
+def branch_dsts(mhc):
+    train = [zipf(200000, 7)]
+    return {do: mhc.Model.from_counts(mhc.histogram_o1_batch(train, order=do), do) for do in (0, 1)}
+
+
+@pytest.mark.parametrize("kind,img1_in_lds,img0_in_lds,log2n", [("P7_SMALL", True, True, 12), ("P8", False, True, 11), ("P7_FULL", False, True, 0)])
+def test_every_launcher_branch_of_a_shared_source(mhc, branch_dsts, kind, img1_in_lds, img0_in_lds, log2n):
+    counts, msgs, (want_p, want_lds) = branch_source(kind)
+    assert [len(m) for m in msgs] == BRANCH_LENS
+    model = mhc.Model.from_counts(counts.reshape(-1), 1)
+    P, lds = tables_lds(model)
+    assert P == want_p and model.decode_layout()[2] and (want_lds is None or lds == want_lds), (kind, model.decode_layout())
+    # the recipe is on its branch
+    assert (lds + 65536 <= LDS_MAX) == img1_in_lds and (lds + 256 <= LDS_MAX) == img0_in_lds and counter_log2n(LDS_MAX - lds) == log2n, (kind, lds)
+    src = Source(mhc, msgs, 256, model=model)
+    for do in (1, 0):
+        check_parity(mhc, src, branch_dsts[do], do, "%s -> order %d" % (kind, do), oracle=False)
+    for order in (0, 1):
+        want = mhc.histogram_o1_batch(msgs, order=order)
+        for indexed in (True, False):
+            got, st, rc = src.histogram(order, indexed)
+            assert rc == mhc.MH_OK and (st == mhc.MH_OK).all() and np.array_equal(got, want), (kind, order, indexed)
+
+
+def test_every_launcher_branch_of_a_model_set(mhc, branch_dsts):
+    msgs = [zipf(n, 930 + i) for i, n in enumerate(BRANCH_LENS)]
+    src = Source(mhc, msgs, 256, each=True)
+    for do in (1, 0):
+        check_parity(mhc, src, branch_dsts[do], do, "set -> order %d" % do, oracle=False)
+    for order in (0, 1):
+        want = mhc.histogram_o1_batch(msgs, order=order)
+        for indexed in (True, False):
+            got, st, rc = src.histogram(order, indexed)
+            assert rc == mhc.MH_OK and (st == mhc.MH_OK).all() and np.array_equal(got, want), (order, indexed)

@@ -61,6 +61,23 @@ def test_workspaces_are_plain_arithmetic_inside_the_cap(mhc):
     assert lib.mh_dev_recode_batch_workspace(65536, 65536 * 4096, 1024) < 8 << 20
 
 
+# (n_streams, sym_total, chunk_symbols) -> what each workspace function returned before the re-coders of all orders became one
+# kernel family: the layouts are part of the ABI (a caller may have sized a pool by them), 300 is not a valid chunk size
+PINNED_ARGS = [(0, 0, 256), (1, 1, 256), (7, 5000, 256), (7, 5000, 0), (7, 5000, 300), (65536, 1 << 28, 1024)]
+PINNED_WORKSPACES = {
+    "mh_dev_recode_batch_workspace": [256, 256, 512, 256, 256, 4197120],
+    "mh_dev_recode_batch_o2_workspace": [256, 256, 768, 256, 256, 6818560],
+    "mh_dev_histogram_coded_workspace": [256, 256, 256, 256, 256, 262400],
+    "mh_dev_histogram_coded_batch_o2_workspace": [256, 256, 256, 256, 256, 262400],
+}
+
+
+def test_workspace_sizes_are_pinned(mhc):
+    for name, want in PINNED_WORKSPACES.items():
+        fn = getattr(mhc.lib(), name)
+        assert [fn(*a) for a in PINNED_ARGS] == want, name
+
+
 def _dev_recode(mhc, **kw):
     w = np.zeros(1 << 14, dtype=np.uint64)
     p = (w.ctypes.data + 255) & ~255
