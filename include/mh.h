@@ -1086,9 +1086,9 @@ int mh_recode_batch(const mh_model *src, const mh_model *dst, const uint8_t *pay
  *     and the emit pass make the same decode.
  *   - Host forms check their arguments before a device is touched and never refuse a valid batch.  An order-0/1
  *     index-free source with a stream over MH_BATCH_WALK_MAX_BITS is indexed by mh_index_batch first.  An order-2 source
- *     has no batch index builder: such a stream is handled alone, as mh_decode_batch_o2 does — mh_decode, then the
- *     host-side automaton over its bytes (search) or mh_encode under dst (re-code), the result spliced into place in stream
- *     order.
+ *     is not yet moved onto its batch index builder (mh_index_batch_o2, a follow-up): such a stream is handled alone, as
+ *     mh_decode_batch_o2 does — mh_decode, then the host-side automaton over its bytes (search) or mh_encode under dst
+ *     (re-code), the result spliced into place in stream order.
  * Not part of this family: model sets (`_each`) — sets are order 0/1, and a set source with an order-2 destination is a
  * follow-up; an LDS image of the live contexts for the order-2 decoder; the command-line tool, which keeps refusing
  * --order2 with --find and --recode.
@@ -1121,11 +1121,56 @@ int mh_recode_batch_o2(const mh_model *src, const mh_model *dst, const uint8_t *
                        uint64_t *out_index, uint64_t *dropped, int32_t *stream_status);
 
 /* ---------------------------------------------------------------------------------------------------------------------
+ * SEGMENT STATES OF INDEX-FREE ORDER-2 BATCHES (extension, parity unpinned) — the _o2 twins of the segment-state calls of
+ * the next section, for a batch coded under one shared order-2 model (what mh_dev_encode_batch_o2 writes, stored without
+ * its sidecar index).  Same arguments, layouts, workspace arithmetic, launch sequence and guarantees as the twins; what
+ * differs:
+ *   - prev0 stands for both context bytes: every stream starts in context (prev0, prev0).
+ *   - an order-0/1 model is MH_ERR_ARG before any launch (and the twins keep refusing an order-2 model).
+ *   - a segment state is (two context bytes) << 48 | stream-relative bit, the order-2 index-entry format
+ *     (MH_INDEX2_BIT_MASK masks the position); the index slices equal, byte for byte, those mh_dev_encode_batch_o2 writes
+ *     (gap entries untouched), emit writes what the index-free mh_dev_decode_batch_o2 writes, and nothing is written at or
+ *     beyond index_cap / out_cap.
+ *   - a workspace that holds the states of an order-0/1 call, or of another batch, is refused by mh_dev_batch_index_o2 /
+ *     mh_dev_batch_emit_o2 with MH_ERR_ARG, and an order-2 workspace by the order-0/1 calls.
+ *   - the speculation differs.  Most of the 65536 contexts have no codes, so a guessed context dies almost at once.  A
+ *     segment's entry guess therefore decodes the whole segment in front of it (512 bits) from context (prev0, prev0) and
+ *     recovers: in a context without codes it goes on, at the same bit, in the model's heaviest context that ends in the
+ *     same byte (or, where there is none, in (prev0, prev0) one bit further); when the bits match no code of a context
+ *     that has some, it skips one bit.  Segment 1 is warmed up from the stream's true start and is exact.  Correctness
+ *     never rests on the guess: the repair launches, the one-lane walk and the proof kernel are the twins'.
+ *   - per-stream statuses and call-wide errors as for the twins; a stream whose fallback walk would exceed
+ *     MH_BATCH_WALK_MAX_BITS is refused alone (MH_ERR_ARG).
+ * mh_index_batch_o2 is the host form: a stream the device refuses is indexed alone by mh_dev_build_index (for an order-2
+ * model a one-lane walk) and its slice moved into the batch layout, so a valid batch is never refused.
+ * mh_find_batch_o2, mh_recode_batch_o2 and mh_decode_batch_o2 keep their own fallbacks for refused streams; moving them
+ * onto this builder is a follow-up.
+ * mh_dev_batch_states_stats (read-only, any order; synchronises the stream) says how the last states call in d_ws settled:
+ * repair_passes_run = the repair launches (of 8) that rewrote a record, streams_walked = the streams the one-lane fallback
+ * walked (refused ones included).  Exact outputs cannot show a silent degradation to the one-lane walk; this can.
+ * MH_ERR_ARG when d_ws holds no states.
+ * --------------------------------------------------------------------------------------------------------------------- */
+size_t mh_dev_batch_states_o2_workspace(size_t n_streams, uint64_t pay_total);
+int mh_dev_batch_states_o2(const mh_model *m, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits,
+                           size_t n_streams, uint64_t pay_total, uint8_t prev0, uint64_t *d_sym_off, int32_t *d_stream_status,
+                           void *d_ws, size_t ws_bytes, void *stream);
+int mh_dev_batch_index_o2(const mh_model *m, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits,
+                          size_t n_streams, uint64_t pay_total, uint8_t prev0, uint64_t *d_index, uint64_t index_cap,
+                          uint32_t chunk_symbols, int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream);
+int mh_dev_batch_emit_o2(const mh_model *m, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits,
+                         size_t n_streams, uint64_t pay_total, uint8_t prev0, uint8_t *d_out, uint64_t out_cap,
+                         int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream);
+int mh_index_batch_o2(const mh_model *m, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits,
+                      size_t n_streams, uint8_t prev0, uint32_t chunk_symbols, uint64_t *sym_off, uint64_t *index,
+                      uint64_t index_cap, int32_t *stream_status);
+int mh_dev_batch_states_stats(const void *d_ws, void *stream, uint32_t *repair_passes_run, uint64_t *streams_walked);
+
+/* ---------------------------------------------------------------------------------------------------------------------
  * SEGMENT STATES OF INDEX-FREE BATCHES — the batch counterpart of mh_dev_build_index: the `.cm` files the reference writes
  * carry no index, and without one the batch decoders above walk each stream with one lane.  Three device steps for a batch
  * of index-free streams under one shared model (mh_dev_batch_*) or a model set (mh_dev_each_*; a bank view of
  * mh_dev_model_set_pick is a set): STATES, then INDEX and/or EMIT.  Order 0 and order 1; an order-2 model is MH_ERR_ARG
- * before any launch.  Payload layout, prev0, nbits and the index layout are those of the batch sections above.
+ * before any launch (its calls are the _o2 twins of the section above).  Payload layout, prev0, nbits and the index layout are those of the batch sections above.
  *   - states: every stream's payload is cut into 512-bit segments (segment k of stream i is number
  *     pay_off[i] * 8 / 512 + i + k, so a workspace of mh_dev_batch_states_workspace(n, pay_total) bytes holds every one).
  *     Each segment is decoded from a guessed entry state, a fixed number of repair launches decodes again the segments

@@ -65,6 +65,8 @@ EXPORTS = [
     "mh_dev_recode_batch_workspace", "mh_dev_recode_batch", "mh_dev_recode_each", "mh_recode_batch",
     "mh_dev_find_batch_o2_workspace", "mh_dev_find_batch_o2", "mh_find_batch_o2", "mh_dev_histogram_coded_batch_o2_workspace",
     "mh_dev_histogram_coded_batch_o2", "mh_dev_recode_batch_o2_workspace", "mh_dev_recode_batch_o2", "mh_recode_batch_o2",
+    "mh_dev_batch_states_o2_workspace", "mh_dev_batch_states_o2", "mh_dev_batch_index_o2", "mh_dev_batch_emit_o2", "mh_index_batch_o2",
+    "mh_dev_batch_states_stats",
 ]
 FIND_MAX_POSITIONS = 64                    # include/mh.h MH_FIND_MAX_POSITIONS
 FIND_FOLD_ASCII = 1                        # include/mh.h MH_FIND_FOLD_ASCII
@@ -298,6 +300,13 @@ def lib():
         l.mh_dev_histogram_coded_batch_o2.argtypes = l.mh_dev_histogram_coded_batch.argtypes
         l.mh_dev_recode_batch_o2.argtypes = l.mh_dev_recode_batch.argtypes
         l.mh_recode_batch_o2.argtypes = l.mh_recode_batch.argtypes
+        l.mh_dev_batch_states_o2_workspace.argtypes = [sz, u64]
+        l.mh_dev_batch_states_o2_workspace.restype = sz
+        l.mh_dev_batch_states_o2.argtypes = l.mh_dev_batch_states.argtypes
+        l.mh_dev_batch_index_o2.argtypes = l.mh_dev_batch_index.argtypes
+        l.mh_dev_batch_emit_o2.argtypes = l.mh_dev_batch_emit.argtypes
+        l.mh_index_batch_o2.argtypes = l.mh_index_batch.argtypes
+        l.mh_dev_batch_states_stats.argtypes = [vp, vp, C.POINTER(u32), pu64]
         _lib = l
     return _lib
 
@@ -1284,6 +1293,16 @@ class Model:
         return self._recode_batch(lib().mh_recode_batch_o2, "mh_recode_batch_o2", dst, payload, pay_off, nbits, prev0, sym_off, index,
                                   chunk_symbols, cap, want_index, check)
 
+    # ---- segment states of index-free order-2 batches (include/mh.h, "SEGMENT STATES OF INDEX-FREE ORDER-2 BATCHES") --------
+    def index_batch_o2(self, payload, pay_off, nbits, chunk_symbols, prev0=PREV0):
+        """index_batch for an order-2 model (mh_dev_batch_states_o2 + mh_dev_batch_index_o2): the outputs plug into
+        decode_batch_o2(..., sym_off=..., index=...), decode_batch_o2_ranges and the indexed find / recode calls."""
+        return _index_batch(self, payload, pay_off, nbits, chunk_symbols, prev0, o2=True)
+
+    def decode_batch_segments_o2(self, payload, pay_off, nbits, prev0=PREV0, out_cap=None):
+        """decode_batch_segments for an order-2 model (mh_dev_batch_states_o2 + mh_dev_batch_emit_o2)."""
+        return _decode_batch_segments(self, payload, pay_off, nbits, prev0, out_cap, o2=True)
+
     def decompress_batch_o2_ranges(self, blobs, lookups, indices=None, chunk_symbols=0, lengths=None):
         """decompress_batch_ranges for an order-2 model: lookups into whole `.cm` files of compress_batch_o2."""
         self._require_o2("mh_decode_batch_o2_ranges")
@@ -1666,13 +1685,17 @@ def decompress_each(tables, blobs, indices=None, chunk_symbols=0, lengths=None, 
 # ---- segment states of index-free batches (include/mh.h, "SEGMENT STATES OF INDEX-FREE BATCHES") -------------------------
 class SegmentStates:
     """mh_dev_batch_states / mh_dev_each_states on a batch of index-free payloads (model: a Model or a ModelSet), with the
-    batch and the workspace kept on the device for index() and emit().  Attributes: sym_off[n + 1], status[n] (per stream),
-    rc (mh_dev_status after the states)."""
+    batch and the workspace kept on the device for index() and emit().  o2=True: the _o2 calls, for a batch coded under a
+    Model of type 2 (the order-0/1 calls refuse one).  Attributes: sym_off[n + 1], status[n] (per stream), rc
+    (mh_dev_status after the states)."""
 
-    def __init__(self, model, payload, pay_off, nbits, prev0=PREV0):
+    def __init__(self, model, payload, pay_off, nbits, prev0=PREV0, o2=False):
         l = lib()
         self.model = model
         self.is_set = isinstance(model, ModelSet)
+        if o2 and self.is_set:
+            raise MhError(MH_ERR_ARG, "mh_dev_batch_states_o2")
+        self.o2 = o2
         payload = _u8(payload)
         self.pay_off = np.ascontiguousarray(pay_off, dtype=np.uint64)
         nbits = np.ascontiguousarray(nbits, dtype=np.uint64)
@@ -1684,9 +1707,9 @@ class SegmentStates:
         self.d_nb = DeviceBuffer(max(nbits.nbytes, 8), nbits if n else None)
         self.d_so = DeviceBuffer((n + 1) * 8)
         self.d_st = DeviceBuffer(max(n, 1) * 4)
-        self.wsb = l.mh_dev_batch_states_workspace(n, self.pay_total)
+        self.wsb = (l.mh_dev_batch_states_o2_workspace if o2 else l.mh_dev_batch_states_workspace)(n, self.pay_total)
         self.d_ws = DeviceBuffer(self.wsb)
-        fn = l.mh_dev_each_states if self.is_set else l.mh_dev_batch_states
+        fn = l.mh_dev_batch_states_o2 if o2 else l.mh_dev_each_states if self.is_set else l.mh_dev_batch_states
         _check(fn(model.handle, self.d_pl.ptr, self.d_po.ptr, self.d_nb.ptr, n, self.pay_total, prev0, self.d_so.ptr, self.d_st.ptr,
                   self.d_ws.ptr, self.wsb, None), fn.__name__)
         self.rc = l.mh_dev_status(self.d_ws.ptr, None)
@@ -1695,6 +1718,13 @@ class SegmentStates:
 
     def _args(self):
         return (self.model.handle, self.d_pl.ptr, self.d_po.ptr, self.d_nb.ptr, self.n, self.pay_total, self.prev0)
+
+    def states_stats(self):
+        """mh_dev_batch_states_stats of this workspace: (repair launches that rewrote a record, streams the one-lane fallback
+        walked)."""
+        passes, walked = C.c_uint32(0), C.c_uint64(0)
+        _check(lib().mh_dev_batch_states_stats(self.d_ws.ptr, None, C.byref(passes), C.byref(walked)), "mh_dev_batch_states_stats")
+        return passes.value, walked.value
 
     def index(self, chunk_symbols, index_cap=None, init=None, guard=0, ws=None):
         """(index[index_cap], per-stream status, device status).  init: the index's previous contents (gap entries keep
@@ -1707,7 +1737,7 @@ class SegmentStates:
         d_idx = DeviceBuffer(max(buf.nbytes, 8), buf if buf.size else None)
         d_st = DeviceBuffer(max(self.n, 1) * 4)
         w = ws if ws is not None else self
-        fn = l.mh_dev_each_index if self.is_set else l.mh_dev_batch_index
+        fn = l.mh_dev_batch_index_o2 if self.o2 else l.mh_dev_each_index if self.is_set else l.mh_dev_batch_index
         _check(fn(*self._args(), d_idx.ptr, index_cap, chunk_symbols, d_st.ptr, w.d_ws.ptr, w.wsb, None), fn.__name__)
         rc = l.mh_dev_status(w.d_ws.ptr, None)
         out = d_idx.download(np.uint64)[:buf.size]
@@ -1723,7 +1753,7 @@ class SegmentStates:
         d_out = DeviceBuffer(max(out_cap + guard, 1), np.full(out_cap + guard, 0xA5, dtype=np.uint8) if guard else None)
         d_st = DeviceBuffer(max(self.n, 1) * 4)
         w = ws if ws is not None else self
-        fn = l.mh_dev_each_emit if self.is_set else l.mh_dev_batch_emit
+        fn = l.mh_dev_batch_emit_o2 if self.o2 else l.mh_dev_each_emit if self.is_set else l.mh_dev_batch_emit
         _check(fn(*self._args(), d_out.ptr, out_cap, d_st.ptr, w.d_ws.ptr, w.wsb, None), fn.__name__)
         rc = l.mh_dev_status(w.d_ws.ptr, None)
         out = d_out.download()
@@ -1732,15 +1762,15 @@ class SegmentStates:
         return out[:min(int(self.sym_off[self.n]), out_cap)].tobytes(), d_st.download(np.int32)[:self.n], rc
 
 
-def _index_batch(model, payload, pay_off, nbits, chunk_symbols, prev0):
-    st = SegmentStates(model, payload, pay_off, nbits, prev0)
+def _index_batch(model, payload, pay_off, nbits, chunk_symbols, prev0, o2=False):
+    st = SegmentStates(model, payload, pay_off, nbits, prev0, o2=o2)
     idx, status, _ = st.index(chunk_symbols, init=np.zeros(lib().mh_batch_index_capacity(int(st.sym_off[st.n]), st.n, chunk_symbols),
                                                          dtype=np.uint64))
     return st.sym_off, idx, status
 
 
-def _decode_batch_segments(model, payload, pay_off, nbits, prev0, out_cap):
-    st = SegmentStates(model, payload, pay_off, nbits, prev0)
+def _decode_batch_segments(model, payload, pay_off, nbits, prev0, out_cap, o2=False):
+    st = SegmentStates(model, payload, pay_off, nbits, prev0, o2=o2)
     out, status, _ = st.emit(out_cap)
     return out, st.sym_off, status
 
@@ -1749,6 +1779,11 @@ def index_batch_host(model, payload, pay_off, nbits, chunk_symbols, prev0=PREV0,
     """mh_index_batch: (sym_off[n + 1], index, per-stream status) of index-free payloads under one shared model; streams the
     device refuses are indexed one by one."""
     return _index_host(lambda *a: lib().mh_index_batch(model.handle, *a), payload, pay_off, nbits, chunk_symbols, prev0, check)
+
+
+def index_batch_host_o2(model, payload, pay_off, nbits, chunk_symbols, prev0=PREV0, check=True):
+    """mh_index_batch_o2: index_batch_host for a batch coded under an order-2 model."""
+    return _index_host(lambda *a: lib().mh_index_batch_o2(model.handle, *a), payload, pay_off, nbits, chunk_symbols, prev0, check)
 
 
 def _index_host(call, payload, pay_off, nbits, chunk_symbols, prev0, check):

@@ -1,6 +1,7 @@
-// mh_api_batch_states.cpp — the segment-state calls of the C ABI (include/mh.h, "SEGMENT STATES OF INDEX-FREE BATCHES"):
-// states, then index or emit, for a batch of index-free streams under one shared model or a model set (kernels:
-// mh_batch_states.hip), and the host forms that build a whole batch's index.
+// mh_api_batch_states.cpp — the segment-state calls of the C ABI (include/mh.h, "SEGMENT STATES OF INDEX-FREE BATCHES" and
+// "SEGMENT STATES OF INDEX-FREE ORDER-2 BATCHES"): states, then index or emit, for a batch of index-free streams under one
+// shared model of order 0/1, a model set or one shared order-2 model (kernels: mh_batch_states.hip), and the host forms
+// that build a whole batch's index.
 #include "mh_api_internal.hpp"
 #include "mh_batch_states.h"
 
@@ -18,10 +19,13 @@ int common(mhs::StParams &p, int kind, const void *model, const uint8_t *d_paylo
     p.payload = d_payload; p.pay_off = d_pay_off; p.nbits = d_nbits; p.n = n; p.pay_total = pay_total;
     p.segs = mhs::segs_of(pay_total, n);
     p.prev0 = prev0;
+    const bool o2 = kind == mhs::KIND_SHARED2;
+    p.state0 = o2 ? (uint64_t(prev0) << 8 | prev0) << 48 : uint64_t(prev0) << 56;
+    p.pos_mask = o2 ? MH_INDEX2_BIT_MASK : MH_INDEX_BIT_MASK;
     p.walk_max_bits = MH_BATCH_WALK_MAX_BITS;
     p.kind = kind;
     const unsigned long long tag[mhs::TAG_WORDS] = {
-        0x6273656700000000ull | unsigned(kind), n, pay_total, prev0, reinterpret_cast<uintptr_t>(d_payload),
+        mhs::TAG_MAGIC | unsigned(kind), n, pay_total, prev0, reinterpret_cast<uintptr_t>(d_payload),
         reinterpret_cast<uintptr_t>(d_pay_off), reinterpret_cast<uintptr_t>(d_nbits), reinterpret_cast<uintptr_t>(model)};
     std::copy(tag, tag + mhs::TAG_WORDS, p.tag);
     return MH_OK;
@@ -34,6 +38,16 @@ int shared_model(mhs::StParams &p, const mh_model *m) {
     fill_dec_tables(m, p.tabs);
     p.lds = mhb::tables_lds(p.tabs);
     if (p.lds > 163840) return MH_ERR_ARG;
+    return MH_OK;
+}
+
+int shared2_model(mhs::StParams &p, const mh_model *m) {
+    if (!order2(m)) return MH_ERR_ARG;
+    if (m->max_len > mh::MAX_CODE_BITS) return MH_ERR_CODE_TOO_LONG;
+    if (!m->d_prim || !m->d_o2rep || !have_device()) return MH_ERR_NO_DEVICE;
+    fill_dec_tables(m, p.tabs);
+    p.rep = m->d_rep();
+    p.live = m->d_live();
     return MH_OK;
 }
 
@@ -143,6 +157,46 @@ int index_host(const uint8_t *payload, const uint64_t *pay_off, const uint64_t *
     }
     return first;
 }
+
+// the three device calls of a shared model, order 0/1 (KIND_SHARED) or order 2 (KIND_SHARED2)
+int model_of_kind(mhs::StParams &p, int kind, const mh_model *m) { return kind == mhs::KIND_SHARED2 ? shared2_model(p, m) : shared_model(p, m); }
+
+int dev_states(int kind, const mh_model *m, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits, size_t n_streams,
+               uint64_t pay_total, uint8_t prev0, uint64_t *d_sym_off, int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
+    mhs::StParams p;
+    if (!d_sym_off) return MH_ERR_ARG;
+    int rc = common(p, kind, m, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_ws, ws_bytes);
+    if (rc == MH_OK) rc = model_of_kind(p, kind, m);
+    if (rc != MH_OK) return rc;
+    p.sym_off = reinterpret_cast<unsigned long long *>(d_sym_off);
+    p.caller_status = d_stream_status;
+    HIP_TRY(mhs::launch_states(p, d_ws, static_cast<hipStream_t>(stream)));
+    return MH_OK;
+}
+
+int dev_index(int kind, const mh_model *m, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits, size_t n_streams,
+              uint64_t pay_total, uint8_t prev0, uint64_t *d_index, uint64_t index_cap, uint32_t chunk_symbols, int32_t *d_stream_status,
+              void *d_ws, size_t ws_bytes, void *stream) {
+    mhs::StParams p;
+    int rc = common(p, kind, m, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_ws, ws_bytes);
+    if (rc == MH_OK) rc = index_args(p, d_index, index_cap, chunk_symbols, d_stream_status);
+    if (rc == MH_OK) rc = model_of_kind(p, kind, m);
+    if (rc != MH_OK) return rc;
+    HIP_TRY(mhs::launch_index(p, d_ws, static_cast<hipStream_t>(stream)));
+    return MH_OK;
+}
+
+int dev_emit(int kind, const mh_model *m, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits, size_t n_streams,
+             uint64_t pay_total, uint8_t prev0, uint8_t *d_out, uint64_t out_cap, int32_t *d_stream_status, void *d_ws, size_t ws_bytes,
+             void *stream) {
+    mhs::StParams p;
+    int rc = common(p, kind, m, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_ws, ws_bytes);
+    if (rc == MH_OK) rc = emit_args(p, d_out, out_cap, d_stream_status);
+    if (rc == MH_OK) rc = model_of_kind(p, kind, m);
+    if (rc != MH_OK) return rc;
+    HIP_TRY(mhs::launch_emit(p, d_ws, static_cast<hipStream_t>(stream)));
+    return MH_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -152,15 +206,7 @@ size_t mh_dev_batch_states_workspace(size_t n_streams, uint64_t pay_total) { ret
 int mh_dev_batch_states(const mh_model *m, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits, size_t n_streams,
                         uint64_t pay_total, uint8_t prev0, uint64_t *d_sym_off, int32_t *d_stream_status, void *d_ws, size_t ws_bytes,
                         void *stream) {
-    mhs::StParams p;
-    if (!d_sym_off) return MH_ERR_ARG;
-    int rc = common(p, mhs::KIND_SHARED, m, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_ws, ws_bytes);
-    if (rc == MH_OK) rc = shared_model(p, m);
-    if (rc != MH_OK) return rc;
-    p.sym_off = reinterpret_cast<unsigned long long *>(d_sym_off);
-    p.caller_status = d_stream_status;
-    HIP_TRY(mhs::launch_states(p, d_ws, static_cast<hipStream_t>(stream)));
-    return MH_OK;
+    return dev_states(mhs::KIND_SHARED, m, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, d_stream_status, d_ws, ws_bytes, stream);
 }
 
 int mh_dev_each_states(const mh_model_set *s, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits, size_t n_streams,
@@ -180,13 +226,8 @@ int mh_dev_each_states(const mh_model_set *s, const uint8_t *d_payload, const ui
 int mh_dev_batch_index(const mh_model *m, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits, size_t n_streams,
                        uint64_t pay_total, uint8_t prev0, uint64_t *d_index, uint64_t index_cap, uint32_t chunk_symbols,
                        int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
-    mhs::StParams p;
-    int rc = common(p, mhs::KIND_SHARED, m, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_ws, ws_bytes);
-    if (rc == MH_OK) rc = index_args(p, d_index, index_cap, chunk_symbols, d_stream_status);
-    if (rc == MH_OK) rc = shared_model(p, m);
-    if (rc != MH_OK) return rc;
-    HIP_TRY(mhs::launch_index(p, d_ws, static_cast<hipStream_t>(stream)));
-    return MH_OK;
+    return dev_index(mhs::KIND_SHARED, m, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_index, index_cap, chunk_symbols, d_stream_status,
+                     d_ws, ws_bytes, stream);
 }
 
 int mh_dev_each_index(const mh_model_set *s, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits, size_t n_streams,
@@ -204,13 +245,7 @@ int mh_dev_each_index(const mh_model_set *s, const uint8_t *d_payload, const uin
 int mh_dev_batch_emit(const mh_model *m, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits, size_t n_streams,
                       uint64_t pay_total, uint8_t prev0, uint8_t *d_out, uint64_t out_cap, int32_t *d_stream_status, void *d_ws,
                       size_t ws_bytes, void *stream) {
-    mhs::StParams p;
-    int rc = common(p, mhs::KIND_SHARED, m, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_ws, ws_bytes);
-    if (rc == MH_OK) rc = emit_args(p, d_out, out_cap, d_stream_status);
-    if (rc == MH_OK) rc = shared_model(p, m);
-    if (rc != MH_OK) return rc;
-    HIP_TRY(mhs::launch_emit(p, d_ws, static_cast<hipStream_t>(stream)));
-    return MH_OK;
+    return dev_emit(mhs::KIND_SHARED, m, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_out, out_cap, d_stream_status, d_ws, ws_bytes, stream);
 }
 
 int mh_dev_each_emit(const mh_model_set *s, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits, size_t n_streams,
@@ -222,6 +257,50 @@ int mh_dev_each_emit(const mh_model_set *s, const uint8_t *d_payload, const uint
     if (rc == MH_OK) rc = set_model(p, s, n_streams);
     if (rc != MH_OK) return rc;
     HIP_TRY(mhs::launch_emit(p, d_ws, static_cast<hipStream_t>(stream)));
+    return MH_OK;
+}
+
+/* ------------------------------------------------------- order 2 */
+
+size_t mh_dev_batch_states_o2_workspace(size_t n_streams, uint64_t pay_total) { return mh_dev_batch_states_workspace(n_streams, pay_total); }
+
+int mh_dev_batch_states_o2(const mh_model *m, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits, size_t n_streams,
+                           uint64_t pay_total, uint8_t prev0, uint64_t *d_sym_off, int32_t *d_stream_status, void *d_ws, size_t ws_bytes,
+                           void *stream) {
+    return dev_states(mhs::KIND_SHARED2, m, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, d_stream_status, d_ws, ws_bytes, stream);
+}
+
+int mh_dev_batch_index_o2(const mh_model *m, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits, size_t n_streams,
+                          uint64_t pay_total, uint8_t prev0, uint64_t *d_index, uint64_t index_cap, uint32_t chunk_symbols,
+                          int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
+    return dev_index(mhs::KIND_SHARED2, m, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_index, index_cap, chunk_symbols, d_stream_status,
+                     d_ws, ws_bytes, stream);
+}
+
+int mh_dev_batch_emit_o2(const mh_model *m, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits, size_t n_streams,
+                         uint64_t pay_total, uint8_t prev0, uint8_t *d_out, uint64_t out_cap, int32_t *d_stream_status, void *d_ws,
+                         size_t ws_bytes, void *stream) {
+    return dev_emit(mhs::KIND_SHARED2, m, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_out, out_cap, d_stream_status, d_ws, ws_bytes, stream);
+}
+
+// what the states call left in the header: the repair launches that rewrote a record, the streams the one-lane walk walked
+int mh_dev_batch_states_stats(const void *d_ws, void *stream, uint32_t *repair_passes_run, uint64_t *streams_walked) {
+    if (!d_ws || !repair_passes_run || !streams_walked) return MH_ERR_ARG;
+    if (!have_device()) return MH_ERR_NO_DEVICE;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    unsigned char hdr[mhs::HDR_BYTES];
+    HIP_TRY(hipMemcpyAsync(hdr, d_ws, sizeof hdr, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    int words[mhs::HDR_BYTES / 4];
+    unsigned long long tag0;
+    std::memcpy(words, hdr, sizeof hdr);
+    std::memcpy(&tag0, hdr + mhs::HDR_TAG, 8);
+    const unsigned long long kind = tag0 & 0xFFFFFFFFull;
+    if ((tag0 & ~0xFFFFFFFFull) != mhs::TAG_MAGIC || kind < mhs::KIND_SHARED || kind > mhs::KIND_SHARED2) return MH_ERR_ARG;   // no states in d_ws
+    uint32_t passes = 0;
+    for (int pass = 1; pass <= mhs::REPAIR_PASSES; ++pass) passes += words[mhs::HDR_CHANGED + pass] != 0;
+    *repair_passes_run = passes;
+    *streams_walked = uint64_t(uint32_t(words[mhs::HDR_WALKED]));
     return MH_OK;
 }
 
@@ -248,6 +327,23 @@ int mh_index_batch(const mh_model *m, const uint8_t *payload, const uint64_t *pa
     auto dev_index = [&](const uint8_t *pl, const uint64_t *po, const uint64_t *nb, uint64_t pt, uint64_t *idx, uint64_t cap, int32_t *st, void *ws,
                          size_t wsb) {
         return mh_dev_batch_index(m, pl, po, nb, n_streams, pt, prev0, idx, cap, chunk_symbols, st, ws, wsb, nullptr);
+    };
+    auto model_of = [&](size_t, mh_model *&out, bool &owned) { out = const_cast<mh_model *>(m); owned = false; return MH_OK; };
+    return index_host(payload, pay_off, nbits, n_streams, prev0, chunk_symbols, sym_off, index, index_cap, stream_status, states, dev_index, model_of);
+}
+
+int mh_index_batch_o2(const mh_model *m, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits, size_t n_streams, uint8_t prev0,
+                      uint32_t chunk_symbols, uint64_t *sym_off, uint64_t *index, uint64_t index_cap, int32_t *stream_status) {
+    if (!order2(m)) return MH_ERR_ARG;
+    int rc = host_args(payload, pay_off, nbits, n_streams, chunk_symbols, sym_off, index);
+    if (rc != MH_OK) return rc;
+    if (!have_device()) return MH_ERR_NO_DEVICE;
+    auto states = [&](const uint8_t *pl, const uint64_t *po, const uint64_t *nb, uint64_t pt, uint64_t *so, int32_t *st, void *ws, size_t wsb) {
+        return mh_dev_batch_states_o2(m, pl, po, nb, n_streams, pt, prev0, so, st, ws, wsb, nullptr);
+    };
+    auto dev_index = [&](const uint8_t *pl, const uint64_t *po, const uint64_t *nb, uint64_t pt, uint64_t *idx, uint64_t cap, int32_t *st, void *ws,
+                         size_t wsb) {
+        return mh_dev_batch_index_o2(m, pl, po, nb, n_streams, pt, prev0, idx, cap, chunk_symbols, st, ws, wsb, nullptr);
     };
     auto model_of = [&](size_t, mh_model *&out, bool &owned) { out = const_cast<mh_model *>(m); owned = false; return MH_OK; };
     return index_host(payload, pay_off, nbits, n_streams, prev0, chunk_symbols, sym_off, index, index_cap, stream_status, states, dev_index, model_of);

@@ -67,6 +67,13 @@ struct mh_model {
     uint32_t *d_tprim2 = nullptr, *d_tsec2 = nullptr;
     uint32_t o2_nslots = 0, o2_p = 0, o2_h = 0, o2_nsec = 0;
     bool o2_enc_ok = false, o2_dec_ok = false;
+    // order 2: what the segment-state speculation recovers with (mh_batch_states.hip, Shared2D::warmup): rep[256] (u16; the
+    // heaviest live context that ends in byte b, 0xFFFF: none) | one bit per context, set when it has codes.  The host copy
+    // is what the asynchronous upload reads.
+    void *d_o2rep = nullptr;
+    std::vector<uint32_t> o2rep_host;
+    const uint16_t *d_rep() const { return static_cast<const uint16_t *>(d_o2rep); }
+    const uint32_t *d_live() const { return static_cast<const uint32_t *>(d_o2rep) + 128; }
 };
 
 // one model per stream on the device (include/mh.h, "BATCHES OF STREAMS, ONE MODEL EACH"; built in mh_api_each.cpp)

@@ -346,6 +346,27 @@ void place2(mh_model *m, unsigned char *b, const Build2Layout &L, uint8_t **node
     m->d_enc64 = reinterpret_cast<uint64_t *>(b + L.off[11]);
 }
 
+// rep[b]: the live context (a, b) of the largest weight, ties to the smaller a; and the live bitmap.  Weights are the
+// contexts' total counts where the build holds them, else (a table file) the number of symbols with a code.
+int o2_rep_setup(mh_model *m, const std::vector<uint64_t> &weight, const std::vector<uint8_t> &live, hipStream_t st) {
+    m->o2rep_host.assign(128 + O2_CTX / 32, 0u);
+    uint16_t *rep = reinterpret_cast<uint16_t *>(m->o2rep_host.data());
+    uint32_t *bits = m->o2rep_host.data() + 128;
+    uint64_t best[256] = {0};
+    std::fill(rep, rep + 256, uint16_t(0xFFFF));
+    for (uint32_t c = 0; c < O2_CTX; ++c) {                        // ascending a for every b: a later context needs a larger weight
+        if (!live[c]) continue;
+        bits[c >> 5] |= 1u << (c & 31u);
+        const uint32_t b = c & 255u;
+        if (rep[b] == 0xFFFF || weight[c] > best[b]) { rep[b] = uint16_t(c); best[b] = weight[c]; }
+    }
+    HIP_TRY(hipMalloc(&m->d_o2rep, m->o2rep_host.size() * 4));
+    // (a build's stream is waited for by its caller; a table file is loaded with blocking copies throughout)
+    if (st) HIP_TRY(hipMemcpyAsync(m->d_o2rep, m->o2rep_host.data(), m->o2rep_host.size() * 4, hipMemcpyHostToDevice, st));
+    else HIP_TRY(hipMemcpy(m->d_o2rep, m->o2rep_host.data(), m->o2rep_host.size() * 4, hipMemcpyHostToDevice));
+    return MH_OK;
+}
+
 // The live contexts' tables: slots for the heaviest live contexts whose two bytes are both among the 63 most frequent
 // byte values (ids 0..62; everything else is id 63 = escape).  Encoder image and tile-decoder tables are filled on the
 // device (o2_hot_pack_kernel); the host only ranks (it holds every context's weight after the build's one sync).
@@ -503,7 +524,8 @@ int build2_finish(unsigned char *b, bool owned, hipStream_t st, mh_model **out) 
             weight[c] = (uint64_t(mt[14]) << 32) | mt[13];
             live[c] = mt[1] != 0xFFFFFFFFu;
         }
-        const int rc2 = o2_hot_setup(m, weight, live, d_node_height, st);
+        int rc2 = o2_rep_setup(m, weight, live, st);
+        if (rc2 == MH_OK) rc2 = o2_hot_setup(m, weight, live, d_node_height, st);
         if (rc2 != MH_OK) return fail(rc2);
     }
     HIP_TRY_M(hipStreamSynchronize(st));                         // sec_base lives in pageable host memory
@@ -556,6 +578,7 @@ int model2_from_table(const uint8_t *bytes, size_t n, mh_model **out) {
     mh::BitReader in(bytes + 37, n - 37);
     mh::ContextCoder cc;
     std::vector<uint8_t> live2(O2_CTX, 0);
+    std::vector<uint64_t> nsym2(O2_CTX, 0);                       // symbols with a code: a table file has no other weight
     for (uint32_t c = 0; c < O2_CTX; ++c) {
         sec_base[c] = uint32_t(sec.size());
         if (in.bit()) {
@@ -567,6 +590,7 @@ int model2_from_table(const uint8_t *bytes, size_t n, mh_model **out) {
                 len8[size_t(c) * 256 + sy] = uint8_t(std::min(cd.len, 255));
                 code64[size_t(c) * 256 + sy] = cd.len <= 64 ? cd.right_aligned() : 0;
                 live += cd.len != 0;
+                nsym2[c] += cd.len != 0;
                 if (cd.len && (m->min_len == 0 || cd.len < m->min_len)) m->min_len = cd.len;
             }
             m->max_len = std::max(m->max_len, cc.max_len());
@@ -598,7 +622,8 @@ int model2_from_table(const uint8_t *bytes, size_t n, mh_model **out) {
     HIP_TRY_M(hipMemcpy(m->d_sec_base, sec_base.data(), size_t(O2_CTX) * 4, hipMemcpyHostToDevice));
     if (!sec.empty()) HIP_TRY_M(hipMemcpy(m->d_sec, sec.data(), sec.size() * 2, hipMemcpyHostToDevice));
     {   // the encoder's LDS image of the live contexts (no weights in a table file: every live context counts the same)
-        const int rc2 = o2_hot_setup(m, std::vector<uint64_t>(O2_CTX, 0), live2, nullptr, nullptr);
+        int rc2 = o2_rep_setup(m, nsym2, live2, nullptr);
+        if (rc2 == MH_OK) rc2 = o2_hot_setup(m, std::vector<uint64_t>(O2_CTX, 0), live2, nullptr, nullptr);
         if (rc2 != MH_OK) return fail(rc2);
     }
 #undef HIP_TRY_M
@@ -816,6 +841,7 @@ void mh_model_free(mh_model *m) {
     if (m->d_sec_own) (void)hipFree(m->d_sec_own);
     if (m->d_tile_own) (void)hipFree(m->d_tile_own);
     if (m->d_o2hot) (void)hipFree(m->d_o2hot);
+    if (m->d_o2rep) (void)hipFree(m->d_o2rep);
     delete m;
 }
 

@@ -347,7 +347,7 @@ int mh_recode_batch_o2(const mh_model *src, const mh_model *dst, const uint8_t *
     int rc = host_args(src, dst, payload, pay_off, nbits, n_streams, sym_off, index, chunk_symbols, out_off, out_nbits, out_index);
     if (rc != MH_OK) return rc;
     const uint64_t bound = symbol_bound(src, nbits, n_streams);
-    // index-free with a stream over the walk cap.  Order-0/1 source: index first.  Order-2 source (no batch index builder): the
+    // index-free with a stream over the walk cap.  Order-0/1 source: index first.  Order-2 source (not yet on mh_index_batch_o2): the
     // device call refuses such a stream; it is decoded alone, coded by mh_encode under dst and spliced into place in stream order.
     std::vector<uint64_t> own_idx;
     std::vector<int32_t> idx_st;

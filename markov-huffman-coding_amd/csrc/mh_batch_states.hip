@@ -1,17 +1,19 @@
-// mh_batch_states.hip — segment states of a batch of index-free order-0/1 streams (include/mh.h, "SEGMENT STATES OF
-// INDEX-FREE BATCHES").  Every stream's payload is cut into SEG_BITS-bit segments, numbered in closed form
+// mh_batch_states.hip — segment states of a batch of index-free streams of order 0, 1 or 2 (include/mh.h, "SEGMENT STATES OF
+// INDEX-FREE BATCHES" and "SEGMENT STATES OF INDEX-FREE ORDER-2 BATCHES").  Every stream's payload is cut into SEG_BITS-bit segments, numbered in closed form
 // (mh_batch_states.h); a segment owns the symbols whose code starts inside it.  One lane decodes one segment.
 //   bseg_check_kernel    offsets non-decreasing, [0] == 0, [n] == pay_total (else MH_ERR_ARG for the call); per stream
 //                        MH_ERR_ARG when nbits_i lies beyond its payload bytes
 //   bseg_spec_kernel     segment 0 from (prev0, 0); every other one from a guess: WARMUP_BITS of its predecessor's bits
-//                        decoded from context prev0 first (Huffman streams re-synchronise)
+//                        decoded from context prev0 first (Huffman streams re-synchronise); order 2: the whole predecessor
+//                        from (prev0, prev0), recovering from contexts without codes (Shared2D::warmup)
 //   bseg_repair_kernel   REPAIR_PASSES launches over ping-pong record buffers: a segment whose entry differs from its
 //                        predecessor's end (both read from the buffer the previous launch wrote) is decoded again from that
 //                        end; a pass returns at once when the one before changed nothing
 //   bseg_mark_kernel     first and last inconsistent segment of every stream
 //   bseg_walk_kernel     one lane per stream that still has one: a sequential walk from its first inconsistent segment
 //                        until its state meets a recorded entry behind which every segment is consistent; a walk longer
-//                        than walk_max_bits refuses the stream (MH_ERR_ARG) — fixed-length-code lattices never re-synchronise
+//                        than walk_max_bits refuses the stream (MH_ERR_ARG) — fixed-length-code lattices never re-synchronise;
+//                        every walked stream is counted in the header (mh_dev_batch_states_stats)
 //   bseg_proof_kernel    entry(k) == end(k - 1), entry(0) == (prev0, 0), no null table entry on the path, the last segment
 //                        ends exactly at nbits_i (src/coding.cpp:124,158): by induction the records are the true states;
 //                        a stream that fails is MH_ERR_CORRUPT
@@ -22,6 +24,8 @@
 // Every record a launch reads was written entirely by an earlier launch; within a launch a record is written by the one
 // lane that decoded it (the torn-record race of the single-stream builder cannot occur).  The number of launches does not
 // depend on the data and nothing synchronises the host.
+// The decoder is a policy (SharedD, SetD, Shared2D): it steps one symbol from a context to the next one and names the state
+// format (context << SHIFT | position, POS masks the position) and the byte a context ends in.
 #include "mh_batch_states.h"
 #include "mh_batch_dev.hpp"
 #include "mh_decode_dev.hpp"
@@ -41,10 +45,12 @@ using mhk::DecTables;
 
 namespace {
 
-constexpr unsigned long long POS_MASK = MH_INDEX_BIT_MASK;
-
 // decoder of the shared model: tables in LDS (the batch decoder's layout)
 struct SharedD {
+    static constexpr uint32_t SHIFT = 56;
+    static constexpr unsigned long long POS = MH_INDEX_BIT_MASK;
+    static constexpr bool RECOVER = false;
+    static __device__ __forceinline__ uint32_t byte(uint32_t ctx) { return ctx; }
     const uint16_t *lut;
     const uint32_t *sub_base;
     DecTables tabs;
@@ -57,6 +63,10 @@ struct SharedD {
 
 // decoder of a model set: stream i's first level and walk tree (L2)
 struct SetD {
+    static constexpr uint32_t SHIFT = 56;
+    static constexpr unsigned long long POS = MH_INDEX_BIT_MASK;
+    static constexpr bool RECOVER = false;
+    static __device__ __forceinline__ uint32_t byte(uint32_t ctx) { return ctx; }
     mhe::SetDev s;
     const uint32_t *row;
     bool o1;
@@ -67,6 +77,57 @@ struct SetD {
     }
     __device__ __forceinline__ uint32_t step(const BitSrc &src, BitCursor &bc, uint32_t prev, uint32_t &used, bool &bad) const {
         return mhe::decode_sym(s, row, o1 ? prev : 0u, src, bc, used, bad);
+    }
+};
+
+// decoder of the shared order-2 model: the general form, every level gathered from L2 (batch2_dec_idx_kernel's reads); the
+// context holds the last two symbols
+struct Shared2D {
+    static constexpr uint32_t SHIFT = 48;
+    static constexpr unsigned long long POS = MH_INDEX2_BIT_MASK;
+    static constexpr bool RECOVER = true;
+    static __device__ __forceinline__ uint32_t byte(uint32_t ctx) { return ctx & 0xFFu; }
+    const uint16_t *prim;
+    const uint32_t *sec_base;
+    DecTables tabs;
+    const uint16_t *rep;
+    const uint32_t *live;
+    __device__ __forceinline__ void setup(const StParams &p, unsigned char *) {
+        prim = p.tabs.prim; sec_base = p.tabs.sec_base; rep = p.rep; live = p.live;
+        tabs = DecTables{p.tabs.sec, p.tabs.tree, p.tabs.P, 0u, 0u};
+    }
+    __device__ __forceinline__ void select(const StParams &, uint64_t) {}
+    __device__ __forceinline__ uint32_t step(const BitSrc &src, BitCursor &bc, uint32_t ctx, uint32_t &used, bool &bad) const {
+        const uint32_t sym = mhk::decode_one(prim, sec_base, tabs, src, bc, ctx, used, bad);
+        return ((ctx << 8) | sym) & 0xFFFFu;
+    }
+    // The entry guess of the segment that starts at bit `at`: the bits [from, at) decoded from the start context.  Most of the
+    // 65536 contexts have no codes, and a guessed context runs into one almost at once; the warm-up then goes on
+    //   - in rep[b], the heaviest live context that ends in the current context's last byte b, at the same bit, or
+    //   - where there is none, in the start context one bit further;
+    //   - a live context whose codes the bits do not match (one symbol, the end of the payload) keeps the context and skips a bit.
+    // Every round consumes a bit or moves to a live context, whose round consumes one.  (A failed step leaves the cursor
+    // anywhere: it is set up again.)
+    __device__ unsigned long long warmup(const BitSrc &src, uint64_t bit0, unsigned long long state0, uint64_t from, uint64_t at) const {
+        const uint32_t ctx0 = uint32_t(state0 >> SHIFT);
+        uint32_t ctx = ctx0;
+        uint64_t pos = from;
+        BitCursor bc;
+        bc.init(src, bit0 + pos);
+        while (pos < at) {
+            uint32_t used = 0;
+            bool bad = false;
+            const uint32_t next = step(src, bc, ctx, used, bad);
+            if (!bad) { ctx = next; pos += used; continue; }
+            if ((live[ctx >> 5] >> (ctx & 31u)) & 1u) ++pos;
+            else {
+                const uint32_t r = rep[ctx & 0xFFu];
+                if (r != 0xFFFFu && r != ctx) ctx = r;
+                else { ctx = ctx0; ++pos; }
+            }
+            bc.init(src, bit0 + pos);
+        }
+        return ((unsigned long long)ctx << SHIFT) | pos;
     }
 };
 
@@ -98,8 +159,8 @@ __device__ SegRec decode_seg(const D &d, const BitSrc &src, uint64_t bit0, unsig
     SegRec r;
     r.entry = entry;
     r.count = 0;
-    const uint64_t pos = entry & POS_MASK;
-    uint32_t prev = uint32_t(entry >> 56);
+    const uint64_t pos = entry & D::POS;
+    uint32_t prev = uint32_t(entry >> D::SHIFT);
     if (pos >= lim) { r.end = entry; return r; }
     const uint32_t span = uint32_t(lim - pos);          // < 2 * SEG_BITS: an entry lies less than one code past its segment start
     BitCursor bc;
@@ -112,7 +173,7 @@ __device__ SegRec decode_seg(const D &d, const BitSrc &src, uint64_t bit0, unsig
         if (bad) { r.end = SEG_BAD; r.count = cnt; return r; }
         ++cnt;
     }
-    r.end = (uint64_t(prev) << 56) | (pos + used);
+    r.end = (uint64_t(prev) << D::SHIFT) | (pos + used);
     r.count = cnt;
     return r;
 }
@@ -149,11 +210,15 @@ __global__ void bseg_spec_kernel(StParams p, const int *hdr, const int *status, 
         d.select(p, s.i);
         uint64_t bit0;
         const BitSrc src = src_of(p, s, bit0);
-        unsigned long long entry = uint64_t(p.prev0) << 56;
+        unsigned long long entry = p.state0;
         if (s.k) {
             const uint64_t at = s.k * SEG_BITS;
-            const SegRec w = decode_seg(d, src, bit0, (uint64_t(p.prev0) << 56) | (at - WARMUP_BITS), at);
-            entry = w.end != SEG_BAD ? w.end : ((uint64_t(p.prev0) << 56) | at);
+            if constexpr (D::RECOVER) {
+                entry = d.warmup(src, bit0, p.state0, at > WARMUP2_BITS ? at - WARMUP2_BITS : 0, at);
+            } else {
+                const SegRec w = decode_seg(d, src, bit0, p.state0 | (at - WARMUP_BITS), at);
+                entry = w.end != SEG_BAD ? w.end : (p.state0 | at);
+            }
         }
         rec[u] = decode_seg(d, src, bit0, entry, seg_lim(s, s.k));
     }
@@ -216,12 +281,13 @@ __global__ void bseg_walk_kernel(StParams p, int *hdr, int *status, SegRec *rec,
         const uint64_t L = last[i];
         unsigned long long state = rec[s.base + f - 1].end;
         if (state == SEG_BAD) continue;                 // a null table entry on the true path: the proof reports it
+        atomicAdd(hdr + HDR_WALKED, 1);
         d.select(p, i);
         uint64_t bit0;
         const BitSrc src = src_of(p, s, bit0);
         const uint64_t from = f * SEG_BITS;
         for (uint64_t m = f; m < s.nseg; ) {
-            if ((state & POS_MASK) - from > p.walk_max_bits) {
+            if ((state & D::POS) - from > p.walk_max_bits) {
                 if (atomicCAS(status + i, MH_OK, MH_ERR_ARG) == MH_OK) fail(hdr + HDR_STATUS, mhb::BATCH_STATUS_ARG);
                 break;
             }
@@ -241,8 +307,8 @@ __global__ void bseg_proof_kernel(StParams p, int *hdr, int *status, const SegRe
         Seg s;
         if (!seg_of(p, status, u, s)) continue;
         const SegRec r = rec[u];
-        const unsigned long long want = s.k ? rec[u - 1].end : (uint64_t(p.prev0) << 56);
-        const bool bad = r.entry != want || r.end == SEG_BAD || (s.k + 1 == s.nseg && (r.end & POS_MASK) != s.nb);
+        const unsigned long long want = s.k ? rec[u - 1].end : p.state0;
+        const bool bad = r.entry != want || r.end == SEG_BAD || (s.k + 1 == s.nseg && (r.end & p.pos_mask) != s.nb);
         if (bad && atomicCAS(status + s.i, MH_OK, MH_ERR_CORRUPT) == MH_OK) fail(hdr + HDR_STATUS, mhk::MHK_STATUS_CORRUPT);
     }
 }
@@ -328,13 +394,13 @@ __global__ void bseg_index_kernel(StParams p, const int *hdr, const int *status,
         d.select(p, s.i);
         uint64_t bit0;
         const BitSrc src = src_of(p, s, bit0);
-        const uint64_t pos = r.entry & POS_MASK;
+        const uint64_t pos = r.entry & D::POS;
         BitCursor bc;
         bc.init(src, bit0 + pos);
-        uint32_t prev = uint32_t(r.entry >> 56), used = 0;
+        uint32_t prev = uint32_t(r.entry >> D::SHIFT), used = 0;
         bool bad = false;
         for (uint64_t t = 0;; ++t) {
-            if (((s0 + t) & cmask) == 0) slice[(s0 + t) >> cs] = (uint64_t(prev) << 56) | (pos + used);
+            if (((s0 + t) & cmask) == 0) slice[(s0 + t) >> cs] = (uint64_t(prev) << D::SHIFT) | (pos + used);
             if (t == t_last) break;
             prev = d.step(src, bc, prev, used, bad);
         }
@@ -358,14 +424,14 @@ __global__ void bseg_emit_kernel(StParams p, const int *hdr, const int *status, 
         uint64_t bit0;
         const BitSrc src = src_of(p, s, bit0);
         BitCursor bc;
-        bc.init(src, bit0 + (r.entry & POS_MASK));
-        uint32_t prev = uint32_t(r.entry >> 56), used = 0;
+        bc.init(src, bit0 + (r.entry & D::POS));
+        uint32_t prev = uint32_t(r.entry >> D::SHIFT), used = 0;
         bool bad = false;
         mhb::ByteOut bo;
         bo.init(p.out, scanned[u]);
         for (uint64_t t = 0; t < r.count; ++t) {
             prev = d.step(src, bc, prev, used, bad);
-            bo.put(prev);
+            bo.put(D::byte(prev));
         }
         bo.flush();
     }
@@ -472,12 +538,15 @@ hipError_t run_emit(const StParams &p, void *d_ws, hipStream_t st) {
 }  // namespace
 
 hipError_t launch_states(const StParams &p, void *d_ws, hipStream_t st) {
+    if (p.kind == KIND_SHARED2) return run_states<Shared2D>(p, d_ws, st);
     return p.kind == KIND_SHARED ? run_states<SharedD>(p, d_ws, st) : run_states<SetD>(p, d_ws, st);
 }
 hipError_t launch_index(const StParams &p, void *d_ws, hipStream_t st) {
+    if (p.kind == KIND_SHARED2) return run_index<Shared2D>(p, d_ws, st);
     return p.kind == KIND_SHARED ? run_index<SharedD>(p, d_ws, st) : run_index<SetD>(p, d_ws, st);
 }
 hipError_t launch_emit(const StParams &p, void *d_ws, hipStream_t st) {
+    if (p.kind == KIND_SHARED2) return run_emit<Shared2D>(p, d_ws, st);
     return p.kind == KIND_SHARED ? run_emit<SharedD>(p, d_ws, st) : run_emit<SetD>(p, d_ws, st);
 }
 
