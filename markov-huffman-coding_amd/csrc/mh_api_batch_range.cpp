@@ -1,10 +1,9 @@
-// mh_api_batch_range.cpp — lookups (stream, begin, end) into a batch of streams (include/mh.h, "RANDOM ACCESS INTO BATCHES"):
-// the device calls under one shared model or under a model set (kernels: mh_batch_range.hip), and the host-buffer forms that
-// upload only the streams the lookups touch; the shared-model host form serves mh_decode_batch_o2_ranges as well
-// (mh_api_range_o2.cpp).
+// mh_api_batch_range.cpp — lookups (stream, begin, end) into a batch of streams (include/mh.h, "RANDOM ACCESS INTO BATCHES"
+// and "RANDOM ACCESS INTO ORDER-2 STREAMS"): the device calls under one shared model of any order or under a model set
+// (kernels: mh_range.hip), and the host-buffer forms that upload only the streams the lookups touch.
 #include "mh_api_internal.hpp"
 #include "mh_batch.h"
-#include "mh_batch_range.h"
+#include "mh_range.h"
 
 #include <memory>
 #include <unordered_map>
@@ -14,8 +13,6 @@ using namespace mhapi;
 namespace {
 
 thread_local uint64_t t_batch_range_upload = 0;   // payload bytes the calling thread's last host form uploaded
-
-
 
 // ------------------------------------------------------------------------------------------------ host forms
 
@@ -70,7 +67,7 @@ int decode_direct(const Models &md, const Batch &B, size_t i, const std::vector<
             cap += rg[2 * k + 1] - rg[2 * k];
         }
         std::vector<uint8_t> tmp(static_cast<size_t>(cap) + 1);
-        const int rc = (md.o2 ? mh_decode_ranges_o2 : mh_decode_ranges)(m, pl, nb, idx, B.chunk, ni, rg.data(), js.size(), tmp.data(), size_t(cap), oo.data(), st.data());
+        const int rc = decode_ranges_host(m, md.o2, pl, nb, idx, B.chunk, ni, rg.data(), js.size(), tmp.data(), size_t(cap), oo.data(), st.data());
         t_batch_range_upload += mh_last_range_upload_bytes();
         bool any = false;
         for (size_t k = 0; k < js.size(); ++k) any |= st[k] == rc;
@@ -165,10 +162,12 @@ int decode_group(const Models &md, const Batch &B, const std::vector<size_t> &g,
     HIP_TRY(hipMemcpyAsync(d_lk.p, lk.data(), m * 24, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_lk.as<uint64_t>() + 3 * m, at.data(), m * 8, hipMemcpyHostToDevice, st));
     const uint64_t *dso = B.sym_off ? d_so : nullptr, *dix = B.index ? d_idx.as<uint64_t>() : nullptr;
-    const int rc = md.m ? (md.o2 ? mh_dev_decode_batch_o2_ranges : mh_dev_decode_batch_ranges)(md.m, d_pl.as<uint8_t>(), d_po, d_nb, n, B.prev0, dso, dix, B.chunk, d_lk.as<uint64_t>(), m,
-                                                     d_out.as<uint8_t>(), d_lk.as<uint64_t>() + 3 * m, ocap, d_st.as<int32_t>(), d_ws.p, wsb, st)
-                        : mh_dev_decode_each_ranges(s, d_pl.as<uint8_t>(), d_po, d_nb, n, B.prev0, dso, dix, B.chunk, d_lk.as<uint64_t>(), m,
-                                                    d_out.as<uint8_t>(), d_lk.as<uint64_t>() + 3 * m, ocap, d_st.as<int32_t>(), d_ws.p, wsb, st);
+    // the shared model's device call, or the set's: the same arguments behind the model
+    auto dev = [&](auto call, auto *model) {
+        return call(model, d_pl.as<uint8_t>(), d_po, d_nb, n, B.prev0, dso, dix, B.chunk, d_lk.as<uint64_t>(), m, d_out.as<uint8_t>(),
+                    d_lk.as<uint64_t>() + 3 * m, ocap, d_st.as<int32_t>(), d_ws.p, wsb, st);
+    };
+    const int rc = !md.m ? dev(mh_dev_decode_each_ranges, s) : dev(md.o2 ? mh_dev_decode_batch_o2_ranges : mh_dev_decode_batch_ranges, md.m);
     if (rc != MH_OK) return rc;
     std::vector<int32_t> h_st(m);
     std::vector<uint8_t> h_out(static_cast<size_t>(ocap));
@@ -273,47 +272,69 @@ int host_args(const Batch &B, const uint64_t *lookups, size_t n_lookups, uint8_t
 
 namespace mhq {
 
-int prepare_lookups(const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits, size_t n_streams, uint8_t prev0,
-                      const uint64_t *d_sym_off, const uint64_t *d_index, uint32_t chunk_symbols, const uint64_t *d_lookups, size_t n_lookups,
-                      uint8_t *d_out, const uint64_t *d_out_at, uint64_t out_cap, int32_t *d_lookup_status, void *d_ws, size_t ws_bytes,
-                      BatchRangeParams &p) {
+int prepare_lookups(const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits, size_t n_streams, uint32_t prev0,
+                    const uint64_t *d_sym_off, const uint64_t *d_index, uint32_t chunk_symbols, const uint64_t *d_lookups, size_t n_lookups,
+                    uint8_t *d_out, const uint64_t *d_out_at, uint64_t out_cap, int32_t *d_lookup_status, void *d_ws, size_t ws_bytes,
+                    LookupParams &p) {
     if (!d_pay_off || (n_streams && (!d_payload || !d_nbits)) || !d_ws) return MH_ERR_ARG;
     if (n_lookups && (!d_lookups || !d_out_at || !d_lookup_status)) return MH_ERR_ARG;
     if ((!d_out && out_cap) || !aligned16(d_payload) || !aligned16(d_out) || !aligned16(d_ws)) return MH_ERR_ARG;
     int shift = 0;
     if (d_index && ((shift = chunk_shift_of(chunk_symbols)) < 0 || !d_sym_off)) return MH_ERR_ARG;
-    if (ws_bytes < mh_dev_decode_batch_ranges_workspace(n_lookups)) return MH_ERR_CAPACITY;
-    p.payload = d_payload; p.pay_off = d_pay_off; p.nbits = d_nbits; p.n = n_streams; p.prev0 = prev0;
+    if (ws_bytes < range_layout(n_lookups).total) return MH_ERR_CAPACITY;
+    p.payload = d_payload; p.pay_off = d_pay_off; p.nbits = d_nbits; p.n_streams = n_streams; p.prev0 = prev0;
     p.sym_off = d_sym_off; p.index = d_index; p.chunk_shift = uint32_t(shift);
     p.walk_max_bits = MH_BATCH_WALK_MAX_BITS;
-    p.lookups = d_lookups; p.m = n_lookups;
+    p.lookups = d_lookups; p.n = n_lookups;
     p.out = d_out; p.out_at = d_out_at; p.out_cap = out_cap;
-    p.lookup_status = d_lookup_status;
+    p.status = d_lookup_status;
     return MH_OK;
 }
 
 }  // namespace mhq
 
+namespace {
+
+// mh_dev_decode_batch_ranges (o2 = false: an order-0/1 model) and mh_dev_decode_batch_o2_ranges (an order-2 model)
+int dev_decode_batch_ranges(const mh_model *m, bool o2, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits,
+                            size_t n_streams, uint8_t prev0, const uint64_t *d_sym_off, const uint64_t *d_index, uint32_t chunk_symbols,
+                            const uint64_t *d_lookups, size_t n_lookups, uint8_t *d_out, const uint64_t *d_out_at, uint64_t out_cap,
+                            int32_t *d_lookup_status, void *d_ws, size_t ws_bytes, void *stream) {
+    if (!(o2 ? order2(m) : order01(m))) return MH_ERR_ARG;
+    mhq::LookupParams p{};
+    const int rc = mhq::prepare_lookups(d_payload, d_pay_off, d_nbits, n_streams, ctx_of_prev0(m, prev0), d_sym_off, d_index, chunk_symbols,
+                                        d_lookups, n_lookups, d_out, d_out_at, out_cap, d_lookup_status, d_ws, ws_bytes, p);
+    if (rc != MH_OK) return rc;
+    if (m->max_len > mh::MAX_CODE_BITS) return MH_ERR_CODE_TOO_LONG;
+    if (!m->d_prim || !have_device()) return MH_ERR_NO_DEVICE;
+    fill_dec_tables(m, p.tab);
+    HIP_TRY(mhq::launch_lookups(p, o2 ? mhb::Model::Shared2 : mhb::Model::Shared, d_ws, static_cast<hipStream_t>(stream)));
+    return MH_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 uint64_t mh_last_batch_range_upload_bytes(void) { return t_batch_range_upload; }
 
-size_t mh_dev_decode_batch_ranges_workspace(size_t n_lookups) { return mhr::range_layout(n_lookups).total; }
+size_t mh_dev_decode_batch_ranges_workspace(size_t n_lookups) { return mhq::range_layout(n_lookups).total; }
+size_t mh_dev_decode_batch_o2_ranges_workspace(size_t n_lookups) { return mhq::range_layout(n_lookups).total; }
 
 int mh_dev_decode_batch_ranges(const mh_model *m, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits,
                                size_t n_streams, uint8_t prev0, const uint64_t *d_sym_off, const uint64_t *d_index, uint32_t chunk_symbols,
                                const uint64_t *d_lookups, size_t n_lookups, uint8_t *d_out, const uint64_t *d_out_at, uint64_t out_cap,
                                int32_t *d_lookup_status, void *d_ws, size_t ws_bytes, void *stream) {
-    if (!order01(m)) return MH_ERR_ARG;
-    mhq::BatchRangeParams p{};
-    const int rc = mhq::prepare_lookups(d_payload, d_pay_off, d_nbits, n_streams, prev0, d_sym_off, d_index, chunk_symbols, d_lookups,
-                                        n_lookups, d_out, d_out_at, out_cap, d_lookup_status, d_ws, ws_bytes, p);
-    if (rc != MH_OK) return rc;
-    if (m->max_len > mh::MAX_CODE_BITS) return MH_ERR_CODE_TOO_LONG;
-    if (!m->d_prim || !have_device()) return MH_ERR_NO_DEVICE;
-    fill_dec_tables(m, p.tab);
-    HIP_TRY(mhq::launch_batch_ranges(p, true, d_ws, static_cast<hipStream_t>(stream)));
-    return MH_OK;
+    return dev_decode_batch_ranges(m, false, d_payload, d_pay_off, d_nbits, n_streams, prev0, d_sym_off, d_index, chunk_symbols, d_lookups,
+                                   n_lookups, d_out, d_out_at, out_cap, d_lookup_status, d_ws, ws_bytes, stream);
+}
+
+int mh_dev_decode_batch_o2_ranges(const mh_model *m, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits,
+                                  size_t n_streams, uint8_t prev0, const uint64_t *d_sym_off, const uint64_t *d_index, uint32_t chunk_symbols,
+                                  const uint64_t *d_lookups, size_t n_lookups, uint8_t *d_out, const uint64_t *d_out_at, uint64_t out_cap,
+                                  int32_t *d_lookup_status, void *d_ws, size_t ws_bytes, void *stream) {
+    return dev_decode_batch_ranges(m, true, d_payload, d_pay_off, d_nbits, n_streams, prev0, d_sym_off, d_index, chunk_symbols, d_lookups,
+                                   n_lookups, d_out, d_out_at, out_cap, d_lookup_status, d_ws, ws_bytes, stream);
 }
 
 int mh_dev_decode_each_ranges(const mh_model_set *s, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits,
@@ -321,13 +342,13 @@ int mh_dev_decode_each_ranges(const mh_model_set *s, const uint8_t *d_payload, c
                               const uint64_t *d_lookups, size_t n_lookups, uint8_t *d_out, const uint64_t *d_out_at, uint64_t out_cap,
                               int32_t *d_lookup_status, void *d_ws, size_t ws_bytes, void *stream) {
     if (!s || n_streams != s->d.n) return MH_ERR_ARG;
-    mhq::BatchRangeParams p{};
+    mhq::LookupParams p{};
     const int rc = mhq::prepare_lookups(d_payload, d_pay_off, d_nbits, n_streams, prev0, d_sym_off, d_index, chunk_symbols, d_lookups,
                                         n_lookups, d_out, d_out_at, out_cap, d_lookup_status, d_ws, ws_bytes, p);
     if (rc != MH_OK) return rc;
     if (!have_device()) return MH_ERR_NO_DEVICE;
     p.set = s->d;
-    HIP_TRY(mhq::launch_batch_ranges(p, false, d_ws, static_cast<hipStream_t>(stream)));
+    HIP_TRY(mhq::launch_lookups(p, mhb::Model::Set, d_ws, static_cast<hipStream_t>(stream)));
     return MH_OK;
 }
 
@@ -335,6 +356,13 @@ int mh_decode_batch_ranges(const mh_model *m, const uint8_t *payload, uint64_t p
                            size_t n_streams, uint8_t prev0, const uint64_t *sym_off, const uint64_t *index, uint32_t chunk_symbols,
                            const uint64_t *lookups, size_t n_lookups, uint8_t *out, size_t out_cap, uint64_t *out_off, int32_t *lookup_status) {
     return decode_batch_ranges_host(m, false, payload, payload_bytes, pay_off, nbits, n_streams, prev0, sym_off, index, chunk_symbols,
+                                    lookups, n_lookups, out, out_cap, out_off, lookup_status);
+}
+
+int mh_decode_batch_o2_ranges(const mh_model *m, const uint8_t *payload, uint64_t payload_bytes, const uint64_t *pay_off, const uint64_t *nbits,
+                              size_t n_streams, uint8_t prev0, const uint64_t *sym_off, const uint64_t *index, uint32_t chunk_symbols,
+                              const uint64_t *lookups, size_t n_lookups, uint8_t *out, size_t out_cap, uint64_t *out_off, int32_t *lookup_status) {
+    return decode_batch_ranges_host(m, true, payload, payload_bytes, pay_off, nbits, n_streams, prev0, sym_off, index, chunk_symbols,
                                     lookups, n_lookups, out, out_cap, out_off, lookup_status);
 }
 

@@ -236,7 +236,7 @@ int decode_alone(const mh_model *m, const uint8_t *payload, uint64_t nbits, uint
 // mh_api_each.cpp: MH_OK when mh_model_set_from_tables accepts the table file t[nb] (host only), else its error
 int check_table(const uint8_t *t, size_t nb);
 // mh_api_range.cpp / mh_api_batch_range.cpp: the host forms of the range and lookup calls (mh_decode_ranges,
-// mh_decode_batch_ranges) over an order-0/1 model, or (o2) over an order-2 model through the _o2 device calls
+// mh_decode_batch_ranges) over an order-0/1 model, or (o2) over an order-2 model through the body of the _o2 device calls
 // (mh_decode_ranges_o2, mh_decode_batch_o2_ranges).  Each refuses a model of the other family with MH_ERR_ARG.
 int decode_ranges_host(const mh_model *m, bool o2, const uint8_t *payload, uint64_t nbits, const uint64_t *index, uint32_t chunk_symbols,
                        uint64_t n_symbols, const uint64_t *ranges, size_t n_ranges, uint8_t *out, size_t out_cap, uint64_t *out_off,

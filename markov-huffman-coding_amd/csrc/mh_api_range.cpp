@@ -1,7 +1,6 @@
-// mh_api_range.cpp — the byte-range calls of the C ABI (include/mh.h, "RANDOM ACCESS: BYTE RANGES OF AN INDEXED STREAM"):
-// ranges of one indexed order-0/1 stream decoded on the device (kernels: mh_range.hip), and the host-buffer form that
-// uploads only the payload bytes of the chunks the ranges touch; that host form serves mh_decode_ranges_o2 as well
-// (mh_api_range_o2.cpp).
+// mh_api_range.cpp — the byte-range calls of the C ABI (include/mh.h, "RANDOM ACCESS: BYTE RANGES OF AN INDEXED STREAM" and
+// "RANDOM ACCESS INTO ORDER-2 STREAMS"): ranges of one indexed stream decoded on the device under an order-0/1 or an order-2
+// model (kernels: mh_range.hip), and the host-buffer form that uploads only the payload bytes of the chunks the ranges touch.
 #include "mh_api_internal.hpp"
 #include "mh_batch.h"
 #include "mh_range.h"
@@ -16,7 +15,6 @@ thread_local uint64_t t_range_upload = 0;   // payload bytes the calling thread'
 // bytes in between (a PCIe transfer of 1 MiB takes about as long as the fixed cost of a call).
 constexpr uint64_t RANGE_MERGE_GAP = uint64_t(1) << 20;
 
-
 // a run of whole chunks [c0, c1] of one range, cut so that its payload bytes and its output fit a segment
 struct Piece {
     uint64_t j;            // range
@@ -26,28 +24,23 @@ struct Piece {
     uint64_t at;           // output offset in the caller's buffer
 };
 
-}  // namespace
-
-extern "C" {
-
-uint64_t mh_last_range_upload_bytes(void) { return t_range_upload; }
-
-size_t mh_dev_decode_ranges_workspace(size_t n_ranges) { return mhr::range_layout(n_ranges).total; }
-
-int mh_dev_decode_ranges(const mh_model *m, const uint8_t *d_payload, uint64_t payload_byte_base, uint64_t payload_bytes, uint64_t nbits,
-                         const uint64_t *d_index, uint32_t chunk_symbols, uint64_t n_symbols, const uint32_t *d_fine,
-                         const uint64_t *d_ranges, size_t n_ranges, uint8_t *d_out, const uint64_t *d_out_at, uint64_t out_cap,
-                         int32_t *d_range_status, void *d_ws, size_t ws_bytes, void *stream) {
-    if (!order01(m) || (!d_payload && payload_bytes) || (!d_index && n_symbols) || !d_ws) return MH_ERR_ARG;
+// mh_dev_decode_ranges (o2 = false: an order-0/1 model) and mh_dev_decode_ranges_o2 (an order-2 model)
+int dev_decode_ranges(const mh_model *m, bool o2, const uint8_t *d_payload, uint64_t payload_byte_base, uint64_t payload_bytes, uint64_t nbits,
+                      const uint64_t *d_index, uint32_t chunk_symbols, uint64_t n_symbols, const uint32_t *d_fine, const uint64_t *d_ranges,
+                      size_t n_ranges, uint8_t *d_out, const uint64_t *d_out_at, uint64_t out_cap, int32_t *d_range_status, void *d_ws,
+                      size_t ws_bytes, void *stream) {
+    if (!(o2 ? order2(m) : order01(m)) || (!d_payload && payload_bytes) || (!d_index && n_symbols) || !d_ws) return MH_ERR_ARG;
     if (n_ranges && (!d_ranges || !d_out_at || !d_range_status)) return MH_ERR_ARG;
     if ((!d_out && out_cap) || !aligned16(d_out) || !aligned16(d_ws)) return MH_ERR_ARG;
     const int shift = chunk_shift_of(chunk_symbols);
     if (shift < 0 || n_symbols > nbits) return MH_ERR_ARG;
+    // the order-2 fine index exists for chunks of up to 1024 symbols (its entries are 16-bit distances from the chunk's entry)
+    if (o2 && d_fine && (shift > 10 || (reinterpret_cast<uintptr_t>(d_fine) & 3u))) return MH_ERR_ARG;
     if (payload_byte_base > (nbits + 7) / 8 || payload_bytes > (nbits + 7) / 8 - payload_byte_base) return MH_ERR_ARG;
-    if (ws_bytes < mh_dev_decode_ranges_workspace(n_ranges)) return MH_ERR_CAPACITY;
+    if (ws_bytes < mhq::range_layout(n_ranges).total) return MH_ERR_CAPACITY;
     if (m->max_len > mh::MAX_CODE_BITS) return MH_ERR_CODE_TOO_LONG;
     if (!m->d_prim || !have_device()) return MH_ERR_NO_DEVICE;
-    mhr::RangeParams p{};
+    mhq::RangeParams p{};
     p.payload = d_payload; p.win_base = payload_byte_base; p.win_bytes = payload_bytes;
     p.nbits = nbits; p.n_symbols = n_symbols;
     p.index = d_index; p.chunk_shift = uint32_t(shift);
@@ -56,10 +49,35 @@ int mh_dev_decode_ranges(const mh_model *m, const uint8_t *d_payload, uint64_t p
     p.n_units = (n_symbols + (uint64_t(1) << p.unit_shift) - 1) >> p.unit_shift;
     p.ranges = d_ranges; p.n = n_ranges;
     p.out = d_out; p.out_at = d_out_at; p.out_cap = out_cap;
-    p.range_status = d_range_status;
+    p.status = d_range_status;
     fill_dec_tables(m, p.tab);
-    HIP_TRY(mhr::launch_decode_ranges(p, d_ws, static_cast<hipStream_t>(stream)));
+    HIP_TRY(mhq::launch_ranges(p, o2 ? mhb::Model::Shared2 : mhb::Model::Shared, d_ws, static_cast<hipStream_t>(stream)));
     return MH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+uint64_t mh_last_range_upload_bytes(void) { return t_range_upload; }
+
+size_t mh_dev_decode_ranges_workspace(size_t n_ranges) { return mhq::range_layout(n_ranges).total; }
+size_t mh_dev_decode_ranges_o2_workspace(size_t n_ranges) { return mhq::range_layout(n_ranges).total; }
+
+int mh_dev_decode_ranges(const mh_model *m, const uint8_t *d_payload, uint64_t payload_byte_base, uint64_t payload_bytes, uint64_t nbits,
+                         const uint64_t *d_index, uint32_t chunk_symbols, uint64_t n_symbols, const uint32_t *d_fine,
+                         const uint64_t *d_ranges, size_t n_ranges, uint8_t *d_out, const uint64_t *d_out_at, uint64_t out_cap,
+                         int32_t *d_range_status, void *d_ws, size_t ws_bytes, void *stream) {
+    return dev_decode_ranges(m, false, d_payload, payload_byte_base, payload_bytes, nbits, d_index, chunk_symbols, n_symbols, d_fine, d_ranges,
+                             n_ranges, d_out, d_out_at, out_cap, d_range_status, d_ws, ws_bytes, stream);
+}
+
+int mh_dev_decode_ranges_o2(const mh_model *m, const uint8_t *d_payload, uint64_t payload_byte_base, uint64_t payload_bytes, uint64_t nbits,
+                            const uint64_t *d_index, uint32_t chunk_symbols, uint64_t n_symbols, const uint32_t *d_fine,
+                            const uint64_t *d_ranges, size_t n_ranges, uint8_t *d_out, const uint64_t *d_out_at, uint64_t out_cap,
+                            int32_t *d_range_status, void *d_ws, size_t ws_bytes, void *stream) {
+    return dev_decode_ranges(m, true, d_payload, payload_byte_base, payload_bytes, nbits, d_index, chunk_symbols, n_symbols, d_fine, d_ranges,
+                             n_ranges, d_out, d_out_at, out_cap, d_range_status, d_ws, ws_bytes, stream);
 }
 
 /* ------------------------------------------------------- host-buffer call */
@@ -68,6 +86,13 @@ int mh_decode_ranges(const mh_model *m, const uint8_t *payload, uint64_t nbits, 
                      uint64_t n_symbols, const uint64_t *ranges, size_t n_ranges, uint8_t *out, size_t out_cap, uint64_t *out_off,
                      int32_t *range_status) {
     return decode_ranges_host(m, false, payload, nbits, index, chunk_symbols, n_symbols, ranges, n_ranges, out, out_cap, out_off,
+                              range_status);
+}
+
+int mh_decode_ranges_o2(const mh_model *m, const uint8_t *payload, uint64_t nbits, const uint64_t *index, uint32_t chunk_symbols,
+                        uint64_t n_symbols, const uint64_t *ranges, size_t n_ranges, uint8_t *out, size_t out_cap, uint64_t *out_off,
+                        int32_t *range_status) {
+    return decode_ranges_host(m, true, payload, nbits, index, chunk_symbols, n_symbols, ranges, n_ranges, out, out_cap, out_off,
                               range_status);
 }
 
@@ -163,7 +188,7 @@ int decode_ranges_host(const mh_model *m, bool o2, const uint8_t *payload, uint6
 
     const hipStream_t st = nullptr;
     if (!wins.empty()) {
-        const size_t wsb = o2 ? mh_dev_decode_ranges_o2_workspace(max_n) : mh_dev_decode_ranges_workspace(max_n);
+        const size_t wsb = mhq::range_layout(max_n).total;
         DevBuf d_pl, d_idx, d_rng, d_out, d_st, d_ws;
         HIP_TRY(d_pl.alloc(size_t(max_bytes)));
         HIP_TRY(d_idx.alloc(size_t(max_idx) * 8));
@@ -191,9 +216,9 @@ int decode_ranges_host(const mh_model *m, bool o2, const uint8_t *payload, uint6
                 o += q.e - q.b;
             }
             HIP_TRY(hipMemcpyAsync(d_rng.p, h_rng.data(), k * 24, hipMemcpyHostToDevice, st));
-            int rc = (o2 ? mh_dev_decode_ranges_o2 : mh_dev_decode_ranges)(m, d_pl.as<uint8_t>(), w.lo, bytes, nbits, d_index, chunk_symbols, n_symbols, nullptr,
-                                          d_rng.as<uint64_t>(), k, d_out.as<uint8_t>(), d_rng.as<uint64_t>() + 2 * k, w.out,
-                                          d_st.as<int32_t>(), d_ws.p, wsb, st);
+            const int rc = dev_decode_ranges(m, o2, d_pl.as<uint8_t>(), w.lo, bytes, nbits, d_index, chunk_symbols, n_symbols, nullptr,
+                                             d_rng.as<uint64_t>(), k, d_out.as<uint8_t>(), d_rng.as<uint64_t>() + 2 * k, w.out,
+                                             d_st.as<int32_t>(), d_ws.p, wsb, st);
             if (rc != MH_OK) return rc;
             HIP_TRY(hipMemcpyAsync(h_st.data(), d_st.p, k * 4, hipMemcpyDeviceToHost, st));
             if (w.out) HIP_TRY(stage_d2h(h_out.data(), d_out.p, size_t(w.out), st));

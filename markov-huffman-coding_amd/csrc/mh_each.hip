@@ -1,7 +1,7 @@
 // mh_each.hip — batches of independent order-0/1 streams, each under its own model (include/mh.h, "BATCHES OF STREAMS, ONE
 // MODEL EACH"): the reference's default per-file flow (train, write the table, encode) for N messages in a fixed number of
 // launches.  Layouts: mh_each.h; shared device code: mh_batch_dev.hpp (units, scans, bit writer), mh_each_dev.hpp (the
-// per-stream symbol decoder, shared with mh_batch_range.hip); the trees are built by
+// per-stream symbol decoder, shared with mh_range.hip); the trees are built by
 // mh_tree.hip's tree_build_kernel over the live (stream, context) pairs, so the reference's tie-breaking has one copy.
 //   each_check_kernel       offsets non-decreasing, [0] == 0, [n] == total
 //   each_live_kernel        one wave per (stream, 1 KiB sub-step): the contexts the sub-step's symbols are coded in, OR-ed

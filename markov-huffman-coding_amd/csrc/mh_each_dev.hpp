@@ -1,5 +1,5 @@
 // mh_each_dev.hpp — device code shared by the kernels that decode under a model set (include/mh.h, "BATCHES OF STREAMS, ONE
-// MODEL EACH"): the per-stream decoders (mh_each.hip) and the byte ranges of batch streams (mh_batch_range.hip).  The
+// MODEL EACH"): the per-stream decoders (mh_each.hip) and the lookups into batches (mh_range.hip).  The
 // tables stay in global memory (L2): a set's slots are far too many for LDS.  Unnamed namespace: each kernel file gets its
 // own copy.
 #pragma once

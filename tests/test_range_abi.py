@@ -41,6 +41,28 @@ def test_range_workspace_is_plain_arithmetic(mhc):
     assert lib.mh_last_range_upload_bytes() == 0
 
 
+PINNED_N = (0, 1, 2, 1000, 65536, 1 << 20)
+PINNED_WORKSPACE = [256, 256, 256, 8192, 525056, 8397056]      # as returned before the kernel families were merged
+PINNED_WORKSPACES = ["mh_dev_decode_ranges_workspace", "mh_dev_decode_ranges_o2_workspace", "mh_dev_decode_batch_ranges_workspace",
+                     "mh_dev_decode_batch_o2_ranges_workspace"]
+
+
+def test_workspace_sizes_are_pinned(mhc):
+    """The four workspace functions of the random-access family, and that the order-0/1 device calls refuse a byte less on the
+    host, before anything is launched (the calls here never get further: the pointers are host stand-ins).  An order-2 model
+    and a model set need a device: tests/test_gpu_range_family.py holds the `_o2` calls and mh_dev_decode_each_ranges, which
+    takes the batch function's size, to the same six values."""
+    lib = mhc.lib()
+    for name in PINNED_WORKSPACES:
+        assert [getattr(lib, name)(n) for n in PINNED_N] == PINNED_WORKSPACE, name
+    w = np.zeros(1 << 14, dtype=np.uint64)
+    p = (w.ctypes.data + 255) & ~255
+    m = mhc.Model.from_counts(np.ones(65536, dtype=np.uint64), 1)
+    for n, ws in zip(PINNED_N, PINNED_WORKSPACE):
+        assert lib.mh_dev_decode_batch_ranges(m.handle, p, p, p, 1, 0x20, None, None, 0, p, n, p, p, 64, p, p, ws - 1, None) == mhc.MH_ERR_CAPACITY, n
+        assert lib.mh_dev_decode_ranges(m.handle, p, 0, 64, 512, p, 256, 400, None, p, n, p, p, 16, p, p, ws - 1, None) == mhc.MH_ERR_CAPACITY, n
+
+
 def _host_call(mhc, m, payload, nbits, index, chunk, n_symbols, ranges, out_cap=64):
     lib = mhc.lib()
     rg = np.ascontiguousarray(np.asarray(ranges, dtype=np.uint64).reshape(-1, 2))
