@@ -48,19 +48,31 @@ constexpr int T_THREADS = 1024;
 constexpr int T_WAVES = T_THREADS / 64;
 constexpr int T_LDS_BYTES = 163840;
 constexpr uint64_t T_POS_MASK = 0x00FFFFFFFFFFFFFFull;
+constexpr int T_NPF = 6;                         // 16-byte payload vectors a lane fetches ahead per piece (6 KiB per wave): what fits beside the 32 output registers without a spill
 
 // bit offset of sub-chunk j's first symbol: the chunk index entry in front of it supplies the high bits
 // (order 2: the fine entry's low half is the distance from the chunk's index entry; 0xFFFF = does not fit: a position
 // past the end of the payload results, which fails the tile's sanity check and sends it to the redo pass)
 constexpr uint64_t T_POS_MASK2 = 0x0000FFFFFFFFFFFFull;
 template <int O2>
-__device__ __forceinline__ uint64_t sub_pos(const TileParams &p, uint64_t j, uint32_t f) {
+__device__ __forceinline__ uint64_t sub_pos_of(uint64_t index_word, uint32_t f) {   // index_word: the chunk index entry in front of the sub-chunk
     if (O2) {
-        const uint64_t base = p.index[(j << T_SUB_SHIFT) >> p.chunk_shift] & T_POS_MASK2;
+        const uint64_t base = index_word & T_POS_MASK2;
         return (f & 0xFFFFu) == 0xFFFFu ? ~0ull >> 1 : base + (f & 0xFFFFu);
     }
-    const uint64_t base = p.index[(j << T_SUB_SHIFT) >> p.chunk_shift] & T_POS_MASK;
+    const uint64_t base = index_word & T_POS_MASK;
     return base + ((f - uint32_t(base)) & FINE_POS_MASK);
+}
+template <int O2>
+__device__ __forceinline__ uint64_t sub_pos(const TileParams &p, uint64_t j, uint32_t f) {
+    return sub_pos_of<O2>(p.index[(j << T_SUB_SHIFT) >> p.chunk_shift], f);
+}
+
+// a wave-uniform 64-bit value, moved to scalar registers (lane 0's)
+__device__ __forceinline__ uint64_t uniform64(uint64_t v) {
+    const uint32_t lo = uint32_t(__builtin_amdgcn_readfirstlane(int(uint32_t(v))));
+    const uint32_t hi = uint32_t(__builtin_amdgcn_readfirstlane(int(uint32_t(v >> 32))));
+    return (uint64_t(hi) << 32) | lo;
 }
 
 // first payload byte a wave stages for a piece that starts at bit `start` (16-byte aligned), and the byte count
@@ -158,8 +170,8 @@ __global__ __launch_bounds__(T_THREADS) void decode_tile_kernel(TileParams p) {
         if (mx) atomicMax(&s_max[0], mx);
         if (over) atomicAdd(&s_max[1], over);
         __syncthreads();
-        maxb = s_max[0];
-        const uint32_t nover = s_max[1];
+        maxb = __builtin_amdgcn_readfirstlane(s_max[0]);          // (wave-uniform: what follows from it lives in scalar registers)
+        const uint32_t nover = __builtin_amdgcn_readfirstlane(s_max[1]);
         __syncthreads();                                              // (read by everybody before a wave stages into it)
         if (maxb > fit_all && uint64_t(nover) * 128u <= mine * T_WAVES) maxb = fit_all;
     }
@@ -187,253 +199,335 @@ __global__ __launch_bounds__(T_THREADS) void decode_tile_kernel(TileParams p) {
         __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t *>(p.sec), 0, p.nsec ? int((p.nsec + 8u) * (O2 ? 4u : 2u)) : 0, 0x00020000);
     const uint32_t chunks_per_tile = T_TILE >> p.chunk_shift;     // >= 1: chunk_shift <= 12 (launch_decode_tile)
 
-    unsigned long long seg[4] = {0, 0, 0, 0};
-    for (uint64_t tb = blockIdx.x; tb * T_WAVES < p.ntiles; tb += gridDim.x)
-    for (uint32_t tj = wave; tj < uint32_t(T_WAVES); tj += nw) {
-        const uint64_t t = tb * T_WAVES + tj;
-        if (t >= p.ntiles) break;
-        unsigned long long t0 = 0, t1 = 0, t2 = 0, t3 = 0;
-        if (STAMP) t0 = tile_stamp();
-        // ---- positions: lane l, stream k decodes sub-chunk j = (t * K + k) * 64 + l
-        uint64_t pos[K];
-        uint32_t cf[K];                                           // low byte: the context (previous symbol)
+    // ---- [r7] the piece loop, two deep.  Nothing a wave fetches depends on what it decodes: the fine entries of a piece
+    // follow from its number, its payload range from those entries.  So a wave that comes out of a piece's symbol loop first
+    // issues, in ONE batch of vector loads, the payload of its next piece (T_NPF vectors per lane, into registers) and the
+    // fine-index words of the piece after that, then turns its output around and stores it, and only then waits for the
+    // batch (the stores behind the loads are counted in that wait: the wave does not wait for its own stores), writes the
+    // payload into its region, resolves the entries and enters the next loop.  No prefetch is outstanding inside the symbol
+    // loop (its gathers' waits would wait for it).  Piece order per wave as ever: tj += nw inside a block, then tb += gridDim.x.
+    const uint32_t wv = __builtin_amdgcn_readfirstlane(wave);
+    constexpr uint64_t NONE = ~0ull;
+    uint64_t it_tb = blockIdx.x;
+    uint32_t it_tj = wv;
+    bool it_done = false;
+    auto next_piece = [&]() -> uint64_t {
+        if (it_done) return NONE;
+        uint64_t t = it_tb * T_WAVES + it_tj;
+        if (it_tj >= uint32_t(T_WAVES) || t >= p.ntiles) {        // this block of pieces is used up: the workgroup's next one
+            it_tb += gridDim.x;
+            it_tj = wv;
+            t = it_tb * T_WAVES + it_tj;
+            if (t >= p.ntiles) { it_done = true; return NONE; }
+        }
+        it_tj += nw;
+        return t;
+    };
+    // a piece's index words as loaded (lane l, stream k: sub-chunk j = (t * K + k) * 64 + l; the entry behind the piece gives its end)
+    struct Raw { uint32_t f[K], fe; uint64_t ib[K], ibe; };
+    // ... and resolved.  cls: 0 = decode it, 1 = damaged index (CORRUPT), 2 = its chunks go to the chunk decoder, 3 = no piece
+    struct Meta { uint64_t b0; uint32_t nvec, endoff, cls, qoff[K], cf[K]; };
+    auto load_raw = [&](uint64_t t, Raw &r) __attribute__((always_inline)) {
         const uint64_t j0 = t * (64u * K);
 #pragma unroll
         for (int k = 0; k < K; ++k) {
             const uint64_t j = j0 + uint64_t(k) * 64u + lane;
-            const uint32_t f = p.fine[j];
-            pos[k] = sub_pos<O2>(p, j, f);
-            cf[k] = O2 ? uint32_t(p.ctx2slot[f >> 16]) << 16 : f >> 24;     // order 2: the context's slot (0xFFFF: none)
+            r.f[k] = p.fine[j];
+            r.ib[k] = p.index[(j << T_SUB_SHIFT) >> p.chunk_shift];
         }
-        const uint64_t jn = j0 + 64u * K;
-        uint64_t end = p.nbits;
-        if (jn < nsub) end = sub_pos<O2>(p, jn, p.fine[jn]);      // same address in every lane
-        const uint64_t start = __shfl(pos[0], 0);
-        const uint64_t b0 = stage_first(start);
-        const uint64_t nbytes = ((end + 7) >> 3) - b0;
+        const uint64_t jn = j0 + 64u * K, je = jn < nsub ? jn : 0;    // (the stream's last piece ends at nbits: entry 0 is read and not used)
+        r.fe = p.fine[je];                                        // same address in every lane
+        r.ibe = p.index[(je << T_SUB_SHIFT) >> p.chunk_shift];
+    };
+    // every test an address is derived from happens here, before the piece's payload is asked for: a piece that fails one
+    // issues no payload load (nvec = 0) and is reported, or listed for the chunk decoder, when it becomes the current one
+    auto resolve = [&](uint64_t t, const Raw &r, Meta &m) __attribute__((always_inline)) {
+        uint64_t pos[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            pos[k] = sub_pos_of<O2>(r.ib[k], r.f[k]);
+            m.cf[k] = O2 ? uint32_t(p.ctx2slot[r.f[k] >> 16]) << 16 : r.f[k] >> 24;     // order 2: the context's slot (0xFFFF: none); else low byte: the context
+        }
+        const uint64_t ev = t * (64u * K) + 64u * K < nsub ? sub_pos_of<O2>(r.ibe, r.fe) : p.nbits;
+        const uint64_t end = uniform64(ev), start = uniform64(pos[0]);     // (start: lane 0's first sub-chunk)
+        m.b0 = stage_first(start);
+        const uint64_t nbytes = ((end + 7) >> 3) - m.b0;
         // every sub-chunk starts inside the piece, in order (a damaged index fails here, not in the loop)
         bool sane = end >= start && end <= p.nbits;
 #pragma unroll
         for (int k = 0; k < K; ++k) sane = sane && pos[k] >= start && pos[k] <= end;
+        // order 2: a sub-chunk whose offset did not fit its fine entry, or whose context has no slot: the chunk decoder takes the piece
+        bool fits = true;
         if (O2) {
-            // a sub-chunk whose offset did not fit its fine entry, or whose context has no slot: the chunk decoder takes the piece
-            bool fits = true;
 #pragma unroll
-            for (int k = 0; k < K; ++k) fits = fits && (cf[k] >> 16) < p.nslots;
-            if (!__all(sane && fits)) {
-                const uint64_t c0 = (t * (uint32_t(K) * T_TILE)) >> p.chunk_shift;
-                for (uint32_t c = lane; c < (T_TILE >> p.chunk_shift) * K; c += 64) p.redo[1u + atomicAdd(p.redo, 1u)] = uint32_t(c0 + c);
-                continue;
+            for (int k = 0; k < K; ++k) fits = fits && (m.cf[k] >> 16) < p.nslots;
+        }
+        m.cls = O2 && !__all(sane && fits) ? 2u : !__all(sane) ? 1u : nbytes + 16u > region ? 2u : 0u;   // (2: also larger than anything the LDS can hold)
+        m.nvec = m.cls == 0u ? uint32_t((nbytes + 15) >> 4) : 0u;
+        m.endoff = uint32_t(end - m.b0 * 8u);
+#pragma unroll
+        for (int k = 0; k < K; ++k) m.qoff[k] = uint32_t(pos[k] - m.b0 * 8u);
+    };
+    // the first T_NPF * 64 vectors of a piece, into registers: every load is issued before anything waits
+    auto fetch_payload = [&](const Meta &m, uint4 (&V)[T_NPF]) __attribute__((always_inline)) {
+        const uint4 *src = reinterpret_cast<const uint4 *>(p.payload + m.b0);
+#pragma unroll
+        for (int i = 0; i < T_NPF; ++i)
+            if (lane + 64u * uint32_t(i) < m.nvec) V[i] = src[lane + 64u * uint32_t(i)];
+    };
+    // ... and from there into the wave's region: bits reversed inside every byte, so that stream bit i of the piece sits at
+    // bit i & 31 of LDS dword i >> 5.  What a piece has beyond T_NPF * 64 vectors (fewer than sixteen waves kept) comes now,
+    // T_NPF loads per lane at a time, all of them issued before the first is waited for.
+    auto put = [&](uint4 v, uint32_t i) __attribute__((always_inline)) {
+        v.x = __builtin_bswap32(__builtin_bitreverse32(v.x));
+        v.y = __builtin_bswap32(__builtin_bitreverse32(v.y));
+        v.z = __builtin_bswap32(__builtin_bitreverse32(v.z));
+        v.w = __builtin_bswap32(__builtin_bitreverse32(v.w));
+        *reinterpret_cast<uint4 *>(reg + i * 16u) = v;
+    };
+    auto land_payload = [&](const Meta &m, uint4 (&V)[T_NPF]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < T_NPF; ++i)
+            if (lane + 64u * uint32_t(i) < m.nvec) put(V[i], lane + 64u * uint32_t(i));
+        for (uint32_t base = 64u * T_NPF; base < m.nvec; base += 64u * T_NPF) {
+            fetch_payload(Meta{m.b0 + base * 16ull, m.nvec - base}, V);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int i = 0; i < T_NPF; ++i)
+                if (base + lane + 64u * uint32_t(i) < m.nvec) put(V[i], base + lane + 64u * uint32_t(i));
+        }
+        // the dword behind the piece (a window may read it) holds zero bits (src/bitbuffer.cpp:116-127)
+        if (lane == 0 && m.cls == 0u) *reinterpret_cast<uint4 *>(reg + m.nvec * 16u) = make_uint4(0, 0, 0, 0);
+    };
+
+    unsigned long long seg[4] = {0, 0, 0, 0};
+    uint64_t tc = next_piece(), tn = NONE, tnn = NONE;            // the current piece, the next one, the one after that
+    Raw rw;
+    Meta mc, mn;
+    uint4 V[T_NPF];
+    mn.cls = 3u; mn.nvec = 0u; mn.b0 = 0;
+    // what a wave does between two symbol loops, in two halves with the output of the finished piece between them
+    auto fetch_ahead = [&]() __attribute__((always_inline)) {
+        fetch_payload(mn, V);                                     // (no piece, or one that failed a test: nvec = 0, no load)
+        tnn = tn != NONE ? next_piece() : NONE;
+        load_raw(tnn != NONE ? tnn : tn != NONE ? tn : tc, rw);   // (behind the wave's last piece: entries it has read before, not used)
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    auto land_ahead = [&](unsigned long long &s_land, unsigned long long &s_pos) __attribute__((always_inline)) {
+        __builtin_amdgcn_sched_barrier(0);
+        unsigned long long a = 0, b = 0, c = 0;
+        if (STAMP) a = tile_stamp();
+        land_payload(mn, V);
+        if (STAMP) b = tile_stamp();
+        tc = tn; mc = mn;
+        tn = tnn;
+        mn.cls = 3u; mn.nvec = 0u;
+        if (tn != NONE) resolve(tn, rw, mn);
+        if (STAMP) { c = tile_stamp(); s_land += b - a; s_pos += c - b; }
+    };
+    if (tc != NONE) {                                             // the first piece: both halves at once
+        load_raw(tc, rw);
+        tn = tc;
+        resolve(tc, rw, mn);
+        fetch_ahead();
+        land_ahead(seg[1], seg[0]);
+    }
+    while (tc != NONE) {
+        const uint64_t j0 = tc * (64u * K);
+        if (__builtin_expect(mc.cls == 0u, 1)) {
+            unsigned long long t2 = 0, t3 = 0;
+            if (STAMP) t2 = tile_stamp();
+            // LDS operations of one wave execute in order: the reads below see the writes of land_payload
+            uint32_t q[K], q0[K], cf[K];
+#pragma unroll
+            for (int k = 0; k < K; ++k) { q[k] = reg_bit0 + mc.qoff[k]; q0[k] = q[k]; cf[k] = mc.cf[k]; }
+            const uint32_t qend = reg_bit0 + mc.endoff;
+            uint32_t leafacc = DEC16_LEAF;
+            uint4 *o16[K];
+#pragma unroll
+            for (int k = 0; k < K; ++k) o16[k] = reinterpret_cast<uint4 *>(p.out + ((j0 + uint64_t(k) * 64u + lane) << T_SUB_SHIFT));
+            uint4 Q[OUT ? K : 1][T_NU];                               // OUT 1, 2: the stream's output bytes; the pieces rotate through
+            // WIN 1: the bit window lives in registers — lo/hi hold the next cnt stream bits (first in bit 0 of lo), `ahead`
+            // the LDS dword behind them, loaded one refill early; every second symbol a lane with fewer than 32 bits
+            // left takes `ahead` in (two table-resolved codes are at most 2 (P + H) <= 32 bits).  One masked ds_read_b32
+            // per ~5.5 symbols instead of a ds_read2_b32 per symbol: the LDS array was busy 60 % of the kernel's time,
+            // 60 % of that bank conflicts (profiles/r03), most of it window traffic.
+            uint32_t lo[K], hi[K], cnt[K], ahead[K], wnext[K];
+            if (WIN) {
+#pragma unroll
+                for (int k = 0; k < K; ++k) {
+                    const uint32_t wa = (q[k] >> 3) & ~3u, sh = q[k] & 31u;
+                    const lds_u32 *wp = lds_ptr<uint32_t>(wa);
+                    const uint32_t d0 = wp[0], d1 = wp[1];
+                    ahead[k] = wp[2];
+                    wnext[k] = wa + 12u;
+                    lo[k] = __builtin_amdgcn_alignbit(d1, d0, sh);
+                    hi[k] = d1 >> sh;
+                    cnt[k] = 64u - sh;
+                }
             }
-        }
-        if (!__all(sane)) {
-            if (lane == 0) atomicExch(p.status, MHK_STATUS_CORRUPT);
-            continue;
-        }
-        if (nbytes + 16u > region) {                              // larger than anything the LDS can hold: chunk decoder
-            const uint64_t c0 = (t * TSYM) >> p.chunk_shift;
-            for (uint32_t c = lane; c < chunks_per_tile * K; c += 64) p.redo[1u + atomicAdd(p.redo, 1u)] = uint32_t(c0 + c);
-            continue;
-        }
-        if (STAMP) t1 = tile_stamp();
-        // ---- stage the piece: coalesced 16-byte loads, bits reversed inside every byte, so that stream bit i of
-        // the piece sits at bit i & 31 of LDS dword i >> 5
-        {
-            const uint4 *src = reinterpret_cast<const uint4 *>(p.payload + b0);
-            const uint32_t nvec = uint32_t((nbytes + 15) >> 4);
-            for (uint32_t i = lane; i < nvec; i += 64u) {
-                uint4 v = src[i];
-                v.x = __builtin_bswap32(__builtin_bitreverse32(v.x));
-                v.y = __builtin_bswap32(__builtin_bitreverse32(v.y));
-                v.z = __builtin_bswap32(__builtin_bitreverse32(v.z));
-                v.w = __builtin_bswap32(__builtin_bitreverse32(v.w));
-                *reinterpret_cast<uint4 *>(reg + i * 16u) = v;
-            }
-            // the dword behind the piece (a window may read it) holds zero bits (src/bitbuffer.cpp:116-127)
-            if (lane == 0) *reinterpret_cast<uint4 *>(reg + nvec * 16u) = make_uint4(0, 0, 0, 0);
-        }
-        if (STAMP) t2 = tile_stamp();
-        // LDS operations of one wave execute in order: the reads below see the writes above
-        uint32_t q[K], q0[K];
-#pragma unroll
-        for (int k = 0; k < K; ++k) { q[k] = reg_bit0 + uint32_t(pos[k] - b0 * 8u); q0[k] = q[k]; }
-        uint32_t leafacc = DEC16_LEAF;
-        uint4 *o16[K];
-#pragma unroll
-        for (int k = 0; k < K; ++k) o16[k] = reinterpret_cast<uint4 *>(p.out + ((j0 + uint64_t(k) * 64u + lane) << T_SUB_SHIFT));
-        uint4 Q[OUT ? K : 1][T_NU];                               // OUT 1, 2: the stream's output bytes; the pieces rotate through
-        // WIN 1: the bit window lives in registers — lo/hi hold the next cnt stream bits (first in bit 0 of lo), `ahead`
-        // the LDS dword behind them, loaded one refill early; every second symbol a lane with fewer than 32 bits
-        // left takes `ahead` in (two table-resolved codes are at most 2 (P + H) <= 32 bits).  One masked ds_read_b32
-        // per ~5.5 symbols instead of a ds_read2_b32 per symbol: the LDS array was busy 60 % of the kernel's time,
-        // 60 % of that bank conflicts (profiles/r03), most of it window traffic.
-        uint32_t lo[K], hi[K], cnt[K], ahead[K], wnext[K];
-        if (WIN) {
-#pragma unroll
-            for (int k = 0; k < K; ++k) {
-                const uint32_t wa = (q[k] >> 3) & ~3u, sh = q[k] & 31u;
-                const lds_u32 *wp = lds_ptr<uint32_t>(wa);
-                const uint32_t d0 = wp[0], d1 = wp[1];
-                ahead[k] = wp[2];
-                wnext[k] = wa + 12u;
-                lo[k] = __builtin_amdgcn_alignbit(d1, d0, sh);
-                hi[k] = d1 >> sh;
-                cnt[k] = 64u - sh;
-            }
-        }
-        // One symbol of every stream per step, in phases that the scheduler may not mix (it otherwise finishes
-        // one stream's window before it asks for the next one's: two LDS round trips in a row instead of one):
-        //   A  (WIN 0) window dwords on their way (one ds_read2_b32 per stream)
-        //   B  window, first-level lookups on their way
-        //   C  second-level gathers on their way (every lane; a leaf indexes past the end: 0, no cache access)
-        //   D  the resolving entry, position, context, output byte
+            // One symbol of every stream per step, in phases that the scheduler may not mix (it otherwise finishes
+            // one stream's window before it asks for the next one's: two LDS round trips in a row instead of one):
+            //   A  (WIN 0) window dwords on their way (one ds_read2_b32 per stream)
+            //   B  window, first-level lookups on their way
+            //   C  second-level gathers on their way (every lane; a leaf indexes past the end: 0, no cache access)
+            //   D  the resolving entry, position, context, output byte
 #pragma unroll 1
-        for (int u = 0; u < T_NU; ++u) {                          // 16 symbols -> one 16-byte piece per stream
-            uint32_t w4[K][4];
+            for (int u = 0; u < T_NU; ++u) {                          // 16 symbols -> one 16-byte piece per stream
+                uint32_t w4[K][4];
 #pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                uint32_t w0[K], w1[K], win[K], e[K], e2[K];
-                if (WIN) {
-                    if ((j & 1) == 0) {
+                for (int j = 0; j < 16; ++j) {
+                    uint32_t w0[K], w1[K], win[K], e[K], e2[K];
+                    if (WIN) {
+                        if ((j & 1) == 0) {
 #pragma unroll
-                        for (int k = 0; k < K; ++k) {
-                            if (cnt[k] < 32u) {
-                                const uint64_t t = uint64_t(ahead[k]) << cnt[k];
-                                lo[k] |= uint32_t(t);
-                                hi[k] = uint32_t(t >> 32);            // (fewer than 32 bits left: hi was empty)
-                                cnt[k] += 32u;
-                                ahead[k] = *lds_ptr<uint32_t>(wnext[k]);
-                                wnext[k] += 4u;
+                            for (int k = 0; k < K; ++k) {
+                                if (cnt[k] < 32u) {
+                                    const uint64_t t = uint64_t(ahead[k]) << cnt[k];
+                                    lo[k] |= uint32_t(t);
+                                    hi[k] = uint32_t(t >> 32);            // (fewer than 32 bits left: hi was empty)
+                                    cnt[k] += 32u;
+                                    ahead[k] = *lds_ptr<uint32_t>(wnext[k]);
+                                    wnext[k] += 4u;
+                                }
                             }
                         }
+                    } else {
+#pragma unroll
+                        for (int k = 0; k < K; ++k) {
+                            const lds_u32 *wp = lds_ptr<uint32_t>((q[k] >> 3) & ~3u);
+                            w0[k] = wp[0];
+                            w1[k] = wp[1];
+                        }
                     }
-                } else {
+                    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                     for (int k = 0; k < K; ++k) {
-                        const lds_u32 *wp = lds_ptr<uint32_t>((q[k] >> 3) & ~3u);
-                        w0[k] = wp[0];
-                        w1[k] = wp[1];
+                        win[k] = WIN ? lo[k] : __builtin_amdgcn_alignbit(w1[k], w0[k], q[k]);   // 32 stream bits from bit q on, first in bit 0
+                        // byte address of the entry (the table starts at LDS address 0, checked at entry): context << (P + 1) | bits << 1
+                        if (O2) {                                      // slot << (P + 2) | bits << 2: 32-bit entries
+                            // (column XOR-ed with the slot: text's frequent codes otherwise put every lane on the same few banks)
+                            e[k] = *lds_ptr<uint32_t>((((win[k] ^ (cf[k] >> 16)) << 2) & ((4u << P) - 4u)) | ((cf[k] >> 16) << (P + 2)));
+                        } else {
+                            const uint32_t csh = P == 7 ? __builtin_amdgcn_perm(0u, cf[k], 0x0C0C000Cu)       // byte 0 -> byte 1
+                                                        : (cf[k] & 255u) << (P + 1);
+                            e[k] = *lds_ptr<uint16_t>(((win[k] << 1) & ((2u << P) - 2u)) | csh);
+                        }
                     }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int k = 0; k < K; ++k) {
-                    win[k] = WIN ? lo[k] : __builtin_amdgcn_alignbit(w1[k], w0[k], q[k]);   // 32 stream bits from bit q on, first in bit 0
-                    // byte address of the entry (the table starts at LDS address 0, checked at entry): context << (P + 1) | bits << 1
-                    if (O2) {                                      // slot << (P + 2) | bits << 2: 32-bit entries
-                        // (column XOR-ed with the slot: text's frequent codes otherwise put every lane on the same few banks)
-                        e[k] = *lds_ptr<uint32_t>((((win[k] ^ (cf[k] >> 16)) << 2) & ((4u << P) - 4u)) | ((cf[k] >> 16) << (P + 2)));
-                    } else {
-                        const uint32_t csh = P == 7 ? __builtin_amdgcn_perm(0u, cf[k], 0x0C0C000Cu)       // byte 0 -> byte 1
-                                                    : (cf[k] & 255u) << (P + 1);
-                        e[k] = *lds_ptr<uint16_t>(((win[k] << 1) & ((2u << P) - 2u)) | csh);
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
+                    __builtin_amdgcn_sched_barrier(0);
 #ifdef MH_EXP_PROBES
-                if (G != 0 && !O2) tile_second_probe<K, G, PC>(e, win, cf, H, sec_rsrc, lane, e2);
-                else
+                    if (G != 0 && !O2) tile_second_probe<K, G, PC>(e, win, cf, H, sec_rsrc, lane, e2);
+                    else
 #endif
 #pragma unroll
-                for (int k = 0; k < K; ++k) {
-                    if (O2) {      // (a leaf carries bit 15: shifted by H + 2 it lies past the (nslots << P) << H entries whatever its high half holds)
-                        const uint32_t idx2 = (e[k] << (H + 2)) | ((win[k] >> (P - 2)) & ((4u << H) - 4u));
-                        e2[k] = uint32_t(__builtin_amdgcn_raw_buffer_load_b32(sec_rsrc, int(idx2), 0, 0));
-                    } else {
-                        const uint32_t idx2 = (e[k] << (H + 1)) | ((win[k] >> (P - 1)) & ((2u << H) - 2u));   // byte offset of the entry
-                        e2[k] = uint32_t(uint16_t(__builtin_amdgcn_raw_buffer_load_b16(sec_rsrc, int(idx2), 0, 0)));
+                    for (int k = 0; k < K; ++k) {
+                        if (O2) {      // (a leaf carries bit 15: shifted by H + 2 it lies past the (nslots << P) << H entries whatever its high half holds)
+                            const uint32_t idx2 = (e[k] << (H + 2)) | ((win[k] >> (P - 2)) & ((4u << H) - 4u));
+                            e2[k] = uint32_t(__builtin_amdgcn_raw_buffer_load_b32(sec_rsrc, int(idx2), 0, 0));
+                        } else {
+                            const uint32_t idx2 = (e[k] << (H + 1)) | ((win[k] >> (P - 1)) & ((2u << H) - 2u));   // byte offset of the entry
+                            e2[k] = uint32_t(uint16_t(__builtin_amdgcn_raw_buffer_load_b16(sec_rsrc, int(idx2), 0, 0)));
+                        }
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int k = 0; k < K; ++k) {
+                        uint32_t ef;
+                        asm("v_max_u32 %0, %1, %2" : "=v"(ef) : "v"(e[k]), "v"(e2[k]));    // (opaque: keeps the value a plain 32-bit one)
+                        leafacc &= ef;
+                        const uint32_t len = __builtin_amdgcn_ubfe(ef, 8, 5);
+                        if (WIN) {
+                            lo[k] = __builtin_amdgcn_alignbit(hi[k], lo[k], len);
+                            hi[k] >>= len;
+                            cnt[k] -= len;
+                        } else {
+                            q[k] += len;
+                        }
+                        cf[k] = ef;
+                        w4[k][j >> 2] = (j & 3) == 0 ? (ef & 255u) : tile_put_byte(w4[k][j >> 2], ef, j & 3);
                     }
                 }
-                __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int k = 0; k < K; ++k) {
-                    uint32_t ef;
-                    asm("v_max_u32 %0, %1, %2" : "=v"(ef) : "v"(e[k]), "v"(e2[k]));    // (opaque: keeps the value a plain 32-bit one)
-                    leafacc &= ef;
-                    const uint32_t len = __builtin_amdgcn_ubfe(ef, 8, 5);
-                    if (WIN) {
-                        lo[k] = __builtin_amdgcn_alignbit(hi[k], lo[k], len);
-                        hi[k] >>= len;
-                        cnt[k] -= len;
-                    } else {
-                        q[k] += len;
+                    const uint4 v = make_uint4(w4[k][0], w4[k][1], w4[k][2], w4[k][3]);
+                    if (OUT == 0) o16[k][u] = v;
+                    else {
+#pragma unroll
+                        for (int i = 0; i + 1 < T_NU; ++i) Q[k][i] = Q[k][i + 1];
+                        Q[k][T_NU - 1] = v;
                     }
-                    cf[k] = ef;
-                    w4[k][j >> 2] = (j & 3) == 0 ? (ef & 255u) : tile_put_byte(w4[k][j >> 2], ef, j & 3);
                 }
             }
+            if (STAMP) t3 = tile_stamp();
+            // ---- every sub-chunk must end exactly where the next one starts (null entries, a wrong table or a damaged
+            // stream all miss it); a code that neither table level resolves sends the tile's chunks to the redo pass
+            if (WIN) {
+#pragma unroll
+                for (int k = 0; k < K; ++k) q[k] = (wnext[k] - 4u) * 8u - cnt[k];       // `ahead` is the dword at wnext - 4: not in the window yet
+            }
+            bool bad = false;
+            const uint32_t unresolved = (leafacc & DEC16_LEAF) ? 0u : 1u;
 #pragma unroll
             for (int k = 0; k < K; ++k) {
-                const uint4 v = make_uint4(w4[k][0], w4[k][1], w4[k][2], w4[k][3]);
-                if (OUT == 0) o16[k][u] = v;
-                else {
-#pragma unroll
-                    for (int i = 0; i + 1 < T_NU; ++i) Q[k][i] = Q[k][i + 1];
-                    Q[k][T_NU - 1] = v;
-                }
+                uint32_t nxt = __shfl_down(q0[k], 1);
+                const uint32_t first_of_next = k + 1 < K ? __shfl(q0[k + 1 < K ? k + 1 : k], 0) : qend;
+                if (lane == 63) nxt = first_of_next;
+                bad = bad || q[k] != nxt;
             }
-        }
-        if (STAMP) t3 = tile_stamp();
-        if (OUT == 1) {
-#pragma unroll
-            for (int k = 0; k < K; ++k)
-#pragma unroll
-                for (int u = 0; u < T_NU; ++u) o16[k][u] = Q[k][u];
-        }
-        if (OUT == 2) {
-            // The input piece is used up: its LDS region now turns the tile's output around, one KiB (T_LPK lanes' pieces) at a
-            // time, so that every store instruction writes 64 x 16 contiguous bytes.  A lane's piece u goes to slot
-            // u ^ swz(lane) of its T_SUB bytes: the eight lanes one ds_write_b128 group serves then hit different bank quads.
-            const uint32_t rb = reg_bit0 >> 3;
-            auto swz = [](uint32_t l) -> uint32_t { return T_SUB == 64 ? (l >> 1) & 3u : (l >> 2) & 1u; };
-#pragma unroll
-            for (int k = 0; k < K; ++k) {
-#pragma unroll
-                for (int g = 0; g < T_NG; ++g) {
-                    if (lane / uint32_t(T_LPK) == uint32_t(g)) {
-#pragma unroll
-                        for (int u = 0; u < T_NU; ++u)
-                            *lds_wptr<u32x4>(rb + (lane % uint32_t(T_LPK)) * uint32_t(T_SUB) + ((uint32_t(u) ^ swz(lane)) << 4)) =
-                                u32x4{Q[k][u].x, Q[k][u].y, Q[k][u].z, Q[k][u].w};
-                    }
-                    __builtin_amdgcn_wave_barrier();                    // (compiler fence: other lanes' writes, same wave, in order)
-                    asm volatile("" ::: "memory");
-                    const uint32_t l = lane / uint32_t(T_NU), u = lane % uint32_t(T_NU);       // reader: piece u of lane l (within the group)
-                    const u32x4 v = *lds_ptr<u32x4>(rb + l * uint32_t(T_SUB) + ((u ^ swz(l)) << 4));
-                    reinterpret_cast<uint4 *>(p.out + ((j0 + uint64_t(k) * 64u + uint32_t(g) * uint32_t(T_LPK)) << T_SUB_SHIFT))[lane] = make_uint4(v.x, v.y, v.z, v.w);
-                    __builtin_amdgcn_wave_barrier();
-                    asm volatile("" ::: "memory");
-                }
-            }
-        }
-        // ---- every sub-chunk must end exactly where the next one starts (null entries, a wrong table or a damaged
-        // stream all miss it); a code that neither table level resolves sends the tile's chunks to the redo pass
-        if (WIN) {
-#pragma unroll
-            for (int k = 0; k < K; ++k) q[k] = (wnext[k] - 4u) * 8u - cnt[k];       // `ahead` is the dword at wnext - 4: not in the window yet
-        }
-        const uint32_t qend = reg_bit0 + uint32_t(end - b0 * 8u);
-        bool bad = false;
-        uint32_t unresolved = (leafacc & DEC16_LEAF) ? 0u : 1u;
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            uint32_t nxt = __shfl_down(q0[k], 1);
-            const uint32_t first_of_next = k + 1 < K ? __shfl(q0[k + 1 < K ? k + 1 : k], 0) : qend;
-            if (lane == 63) nxt = first_of_next;
-            bad = bad || q[k] != nxt;
-        }
-        if (STAMP) {
-            const unsigned long long t4 = tile_stamp();
-            seg[0] += t1 - t0; seg[1] += t2 - t1; seg[2] += t3 - t2; seg[3] += t4 - t3;
-        }
+            bool check = true;
 #ifdef MH_EXP_PROBES
-        if (p.probe) continue;
+            check = !p.probe;
 #endif
-        if (__any(unresolved)) {                                  // rare: all chunks of this piece again, with the walk
-            const uint64_t c0 = (t * TSYM) >> p.chunk_shift;
-            for (uint32_t c = lane; c < chunks_per_tile * K; c += 64) p.redo[1u + atomicAdd(p.redo, 1u)] = uint32_t(c0 + c);
-        } else if (__any(bad)) {
-            if (lane == 0) atomicExch(p.status, MHK_STATUS_CORRUPT);
+            if (check && __any(unresolved)) {                     // rare: all chunks of this piece again, with the walk
+                const uint64_t c0 = (tc * TSYM) >> p.chunk_shift;
+                for (uint32_t c = lane; c < chunks_per_tile * K; c += 64) p.redo[1u + atomicAdd(p.redo, 1u)] = uint32_t(c0 + c);
+            } else if (check && __any(bad)) {
+                if (lane == 0) atomicExch(p.status, MHK_STATUS_CORRUPT);
+            }
+            fetch_ahead();
+            if (OUT == 1) {
+#pragma unroll
+                for (int k = 0; k < K; ++k)
+#pragma unroll
+                    for (int u = 0; u < T_NU; ++u) o16[k][u] = Q[k][u];
+            }
+            if (OUT == 2) {
+                // The input piece is used up: its LDS region now turns the tile's output around, one KiB (T_LPK lanes' pieces) at a
+                // time, so that every store instruction writes 64 x 16 contiguous bytes.  A lane's piece u goes to slot
+                // u ^ swz(lane) of its T_SUB bytes: the eight lanes one ds_write_b128 group serves then hit different bank quads.
+                const uint32_t rb = reg_bit0 >> 3;
+                auto swz = [](uint32_t l) -> uint32_t { return T_SUB == 64 ? (l >> 1) & 3u : (l >> 2) & 1u; };
+#pragma unroll
+                for (int k = 0; k < K; ++k) {
+#pragma unroll
+                    for (int g = 0; g < T_NG; ++g) {
+                        if (lane / uint32_t(T_LPK) == uint32_t(g)) {
+#pragma unroll
+                            for (int u = 0; u < T_NU; ++u)
+                                *lds_wptr<u32x4>(rb + (lane % uint32_t(T_LPK)) * uint32_t(T_SUB) + ((uint32_t(u) ^ swz(lane)) << 4)) =
+                                    u32x4{Q[k][u].x, Q[k][u].y, Q[k][u].z, Q[k][u].w};
+                        }
+                        __builtin_amdgcn_wave_barrier();                    // (compiler fence: other lanes' writes, same wave, in order)
+                        asm volatile("" ::: "memory");
+                        const uint32_t l = lane / uint32_t(T_NU), u = lane % uint32_t(T_NU);       // reader: piece u of lane l (within the group)
+                        const u32x4 v = *lds_ptr<u32x4>(rb + l * uint32_t(T_SUB) + ((u ^ swz(l)) << 4));
+                        reinterpret_cast<uint4 *>(p.out + ((j0 + uint64_t(k) * 64u + uint32_t(g) * uint32_t(T_LPK)) << T_SUB_SHIFT))[lane] = make_uint4(v.x, v.y, v.z, v.w);
+                        __builtin_amdgcn_wave_barrier();
+                        asm volatile("" ::: "memory");
+                    }
+                }
+            }
+            if (STAMP) { const unsigned long long t4 = tile_stamp(); seg[2] += t3 - t2; seg[3] += t4 - t3; }
+            land_ahead(seg[1], seg[0]);
+        } else {
+            if (mc.cls == 1u) {
+                if (lane == 0) atomicExch(p.status, MHK_STATUS_CORRUPT);
+            } else {
+                const uint64_t c0 = (tc * TSYM) >> p.chunk_shift;
+                for (uint32_t c = lane; c < chunks_per_tile * K; c += 64) p.redo[1u + atomicAdd(p.redo, 1u)] = uint32_t(c0 + c);
+            }
+            fetch_ahead();
+            land_ahead(seg[1], seg[0]);
         }
     }
     if (STAMP && lane == 0) {                                     // cycles per segment, summed over the waves (diagnostic build)
@@ -884,6 +978,20 @@ __global__ __launch_bounds__(T_THREADS) void segment_decode_kernel(IdxParams p, 
     }
 }
 
+#ifdef MH_EXP_PROBES
+// Diagnostic library only: MH_TILE_GRID=<g> caps the grid of the tile kernels, so that a stream of a megabyte gives every
+// wave many pieces (the shipped library has no such switch)
+static unsigned tile_grid_cap(unsigned grid) {
+    if (const char *g = getenv("MH_TILE_GRID")) {
+        const int v = atoi(g);
+        if (v > 0 && unsigned(v) < grid) return unsigned(v);
+    }
+    return grid;
+}
+#else
+static unsigned tile_grid_cap(unsigned grid) { return grid; }
+#endif
+
 hipError_t launch_segment_decode(const IdxParams &p, uint8_t *d_out, uint64_t out_cap, hipStream_t st) {
     if (p.tP != 7 || !p.tprim || p.order == 2 || !p.e16 || !p.c16 || !p.tile_base) return hipErrorInvalidValue;
     void (*kern)(IdxParams, uint8_t *, uint64_t) = segment_decode_kernel<7>;
@@ -904,7 +1012,7 @@ hipError_t launch_segment_decode(const IdxParams &p, uint8_t *d_out, uint64_t ou
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
     const uint64_t want = (p.ntile5 + T_WAVES - 1) / T_WAVES;
-    const unsigned grid = unsigned(want < 1 ? 1 : (want > uint64_t(cus) ? uint64_t(cus) : want));
+    const unsigned grid = tile_grid_cap(unsigned(want < 1 ? 1 : (want > uint64_t(cus) ? uint64_t(cus) : want)));
 #ifdef MH_EXP_PROBES
     if (const char *pr = getenv("MH_SEG_PROBE")) { IdxParams pp = p; pp.iter = uint32_t(atoi(pr)); hipLaunchKernelGGL(kern, dim3(grid), dim3(T_THREADS), T_LDS_BYTES, st, pp, d_out, out_cap); return hipGetLastError(); }
 #endif
@@ -933,7 +1041,7 @@ hipError_t launch_index_tile(const IdxParams &p, int mode, hipStream_t st) {
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
     const uint64_t want = (p.ntile5 + T_WAVES - 1) / T_WAVES;
-    const unsigned grid = unsigned(want < 1 ? 1 : (want > uint64_t(cus) ? uint64_t(cus) : want));
+    const unsigned grid = tile_grid_cap(unsigned(want < 1 ? 1 : (want > uint64_t(cus) ? uint64_t(cus) : want)));
     hipLaunchKernelGGL(kern, dim3(grid), dim3(T_THREADS), T_LDS_BYTES, st, p);
     return hipGetLastError();
 }
@@ -976,7 +1084,7 @@ static hipError_t launch_tile_with(void (*kern)(TileParams), TileParams p, const
     }
     // one workgroup per CU (the first-level table takes most of the LDS); with few pieces, fewer workgroups
     const uint64_t want = (p.ntiles + T_WAVES - 1) / T_WAVES;
-    const unsigned grid = unsigned(want < 1 ? 1 : (want > uint64_t(cus) ? uint64_t(cus) : want));
+    const unsigned grid = tile_grid_cap(unsigned(want < 1 ? 1 : (want > uint64_t(cus) ? uint64_t(cus) : want)));
     hipLaunchKernelGGL(kern, dim3(grid), dim3(T_THREADS), T_LDS_BYTES, st, p);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
