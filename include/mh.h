@@ -1121,6 +1121,66 @@ int mh_recode_batch_o2(const mh_model *src, const mh_model *dst, const uint8_t *
                        uint64_t *out_index, uint64_t *dropped, int32_t *stream_status);
 
 /* ---------------------------------------------------------------------------------------------------------------------
+ * DIGESTS OF BATCHES — the CRC-32 of every stream's decoded message without writing the decoded bytes.  A Huffman stream
+ * re-synchronises after damage and then ends where it should, so most single-bit flips of a payload pass every check the
+ * decoders can make and decode, with status MH_OK, to other bytes.  A digest kept beside the data catches them, and here it
+ * is taken from each decoded byte while it sits in a register: no buffer for the original data, and a workspace that holds
+ * nothing per chunk or per byte.  The checksum is CRC-32 as zlib, gzip and PNG define it (reflected polynomial 0xEDB88320,
+ * initial value and final XOR 0xFFFFFFFF): crc32 of zlib gives the same value for the same bytes.
+ * The batch is described exactly as for mh_dev_find_batch / mh_dev_find_each (payload layout, pay_off, nbits, prev0, sym_off
+ * and the index slices of mh_batch_index_base, the same alignment rules and up-front checks with the same statuses); a bank
+ * view of mh_dev_model_set_pick is a set.  mh_dev_crc_batch takes an order-0/1 model and refuses an order-2 model with
+ * MH_ERR_ARG, mh_dev_crc_batch_o2 (extension, parity unpinned; a stream starts in context (prev0, prev0), index entries in
+ * the order-2 format) takes an order-2 model and refuses any other the same way, both before any launch.
+ *   - d_crc[n] is written in full: entry i is the CRC-32 of stream i's decoded message; an empty stream gives 0.  The chunks
+ *     of a stream are digested independently and meet in d_crc[i] by XOR (crc(A || B) follows from the digests of A and B and
+ *     the length of B), which is exact in any order: two calls on the same input give identical buffers.
+ *   - d_len[n] (may be NULL): entry i is the number of decoded symbols — with an index sym_off[i+1] - sym_off[i], index-free
+ *     what the walk counted, so the call also reports the lengths of streams the reference wrote.
+ *   - d_stream_status[n] (may be NULL): for every stream the verdict mh_dev_decode_batch / mh_dev_decode_each /
+ *     mh_dev_decode_batch_o2 gives the same arguments (see SEARCH IN BATCHES).  A failed stream has crc 0 and len 0; the
+ *     other streams are unaffected.  mh_dev_status(d_ws) keeps one of the errors.
+ *   - Without d_index the call is index-free (one lane walks one stream): d_sym_off may be NULL and is neither read nor
+ *     written, sym_total and chunk_symbols are ignored; a stream over MH_BATCH_WALK_MAX_BITS is MH_ERR_ARG, as in the search.
+ *   - A CRC that differs from an expected one is not a device verdict: the caller compares two arrays.
+ * No allocation, no host synchronisation, a number of launches that does not depend on the data or on n_streams.  d_payload
+ * and d_ws 16-byte aligned; d_ws at least mh_dev_crc_batch_workspace(n, sym_total, chunk_symbols) bytes (chunk_symbols 0:
+ * index-free; the one function serves all three calls): 4 bytes per stream and 1.5 KiB.
+ * Host forms mh_crc_batch / mh_crc_batch_o2: arguments checked before a device is touched, the batch uploaded, the device
+ * call run once, results copied back; returns the first stream's error.  Index-free batches with a stream over
+ * MH_BATCH_WALK_MAX_BITS are indexed by mh_index_batch / mh_index_batch_o2 first (chunk MH_CHUNK_DEFAULT) and digested with
+ * that index, so a valid batch is never refused.
+ * mh_dev_crc_raw_batch gives the same digest for uncompressed messages, laid out as mh_dev_encode_batch takes them (d_data
+ * may start anywhere, in_off[n + 1] checked on the device: MH_ERR_ARG through mh_dev_status(d_ws)), so a store gets its
+ * digests on the device when it encodes.  Not a hot path: one lane per KiB.
+ * mh_crc32_combine is host arithmetic, no device: the CRC-32 of A || B from those of A and B and the length of B in bytes.
+ * --------------------------------------------------------------------------------------------------------------------- */
+size_t mh_dev_crc_batch_workspace(size_t n_streams, uint64_t sym_total, uint32_t chunk_symbols);
+int mh_dev_crc_batch(const mh_model *m, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits,
+                     size_t n_streams, uint64_t pay_total, uint8_t prev0, const uint64_t *d_sym_off, uint64_t sym_total,
+                     const uint64_t *d_index, uint32_t chunk_symbols, uint32_t *d_crc, uint64_t *d_len,
+                     int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream);
+/* The same with stream i under the set's model i (n_streams == mh_model_set_size(s), else MH_ERR_ARG). */
+int mh_dev_crc_each(const mh_model_set *s, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits,
+                    size_t n_streams, uint64_t pay_total, uint8_t prev0, const uint64_t *d_sym_off, uint64_t sym_total,
+                    const uint64_t *d_index, uint32_t chunk_symbols, uint32_t *d_crc, uint64_t *d_len,
+                    int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream);
+int mh_dev_crc_batch_o2(const mh_model *m, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits,
+                        size_t n_streams, uint64_t pay_total, uint8_t prev0, const uint64_t *d_sym_off, uint64_t sym_total,
+                        const uint64_t *d_index, uint32_t chunk_symbols, uint32_t *d_crc, uint64_t *d_len,
+                        int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream);
+int mh_crc_batch(const mh_model *m, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits, size_t n_streams,
+                 uint8_t prev0, const uint64_t *sym_off, const uint64_t *index, uint32_t chunk_symbols, uint32_t *crc,
+                 uint64_t *len, int32_t *stream_status);
+int mh_crc_batch_o2(const mh_model *m, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits,
+                    size_t n_streams, uint8_t prev0, const uint64_t *sym_off, const uint64_t *index, uint32_t chunk_symbols,
+                    uint32_t *crc, uint64_t *len, int32_t *stream_status);
+size_t mh_dev_crc_raw_batch_workspace(size_t n_streams, size_t total);
+int mh_dev_crc_raw_batch(const uint8_t *d_data, const uint64_t *d_in_off, size_t n_streams, size_t total, uint32_t *d_crc,
+                         void *d_ws, size_t ws_bytes, void *stream);
+uint32_t mh_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
+
+/* ---------------------------------------------------------------------------------------------------------------------
  * SEGMENT STATES OF INDEX-FREE ORDER-2 BATCHES (extension, parity unpinned) — the _o2 twins of the segment-state calls of
  * the next section, for a batch coded under one shared order-2 model (what mh_dev_encode_batch_o2 writes, stored without
  * its sidecar index).  Same arguments, layouts, workspace arithmetic, launch sequence and guarantees as the twins; what

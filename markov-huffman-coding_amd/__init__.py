@@ -67,6 +67,8 @@ EXPORTS = [
     "mh_dev_histogram_coded_batch_o2", "mh_dev_recode_batch_o2_workspace", "mh_dev_recode_batch_o2", "mh_recode_batch_o2",
     "mh_dev_batch_states_o2_workspace", "mh_dev_batch_states_o2", "mh_dev_batch_index_o2", "mh_dev_batch_emit_o2", "mh_index_batch_o2",
     "mh_dev_batch_states_stats",
+    "mh_dev_crc_batch_workspace", "mh_dev_crc_batch", "mh_dev_crc_each", "mh_dev_crc_batch_o2", "mh_crc_batch", "mh_crc_batch_o2",
+    "mh_dev_crc_raw_batch_workspace", "mh_dev_crc_raw_batch", "mh_crc32_combine",
 ]
 FIND_MAX_POSITIONS = 64                    # include/mh.h MH_FIND_MAX_POSITIONS
 FIND_FOLD_ASCII = 1                        # include/mh.h MH_FIND_FOLD_ASCII
@@ -307,6 +309,17 @@ def lib():
         l.mh_dev_batch_emit_o2.argtypes = l.mh_dev_batch_emit.argtypes
         l.mh_index_batch_o2.argtypes = l.mh_index_batch.argtypes
         l.mh_dev_batch_states_stats.argtypes = [vp, vp, C.POINTER(u32), pu64]
+        l.mh_dev_crc_batch_workspace.argtypes = [sz, u64, u32]
+        l.mh_dev_crc_batch_workspace.restype = sz
+        for fn in (l.mh_dev_crc_batch, l.mh_dev_crc_each, l.mh_dev_crc_batch_o2):
+            fn.argtypes = [vp, vp, vp, vp, sz, u64, u8, vp, u64, vp, u32, vp, vp, vp, vp, sz, vp]
+        for fn in (l.mh_crc_batch, l.mh_crc_batch_o2):
+            fn.argtypes = [vp, vp, vp, vp, sz, u8, vp, vp, u32, vp, vp, vp]
+        l.mh_dev_crc_raw_batch_workspace.argtypes = [sz, sz]
+        l.mh_dev_crc_raw_batch_workspace.restype = sz
+        l.mh_dev_crc_raw_batch.argtypes = [vp, vp, sz, sz, vp, vp, sz, vp]
+        l.mh_crc32_combine.argtypes = [u32, u32, u64]
+        l.mh_crc32_combine.restype = u32
         _lib = l
     return _lib
 
@@ -671,6 +684,81 @@ def _dev_source(payload, pay_off, nbits, sym_off, index):
         index = np.ascontiguousarray(index, dtype=np.uint64)
         d_idx = DeviceBuffer(max(index.nbytes, 8), index if index.size else None)
     return n, int(pay_off[n]), d_pl, d_po, d_nb, so, d_idx
+
+
+# ---- digests of batches (include/mh.h, "DIGESTS OF BATCHES") ---------------------------------------------------------------
+def _guarded(nbytes):
+    """A DeviceBuffer of nbytes + FIND_GUARD words of FIND_FILL behind them.  The front is created without `init`, so that the
+    device_memory modes reach it."""
+    d = DeviceBuffer(nbytes + FIND_GUARD * 8)
+    g = np.full(FIND_GUARD, FIND_FILL, dtype=np.uint64)
+    _check(lib().mh_dev_upload(C.c_void_p(d.ptr.value + nbytes), g.ctypes.data, g.nbytes), "mh_dev_upload")
+    return d
+
+
+def _guard_kept(d, nbytes):
+    return (d.download(np.uint8)[nbytes:nbytes + FIND_GUARD * 8].view(np.uint64) == FIND_FILL).all()
+
+
+def _dev_crc(fn, handle, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols, want_len=True, want_status=True):
+    """One mh_dev_crc_batch / mh_dev_crc_each / mh_dev_crc_batch_o2 call: (crc[n] uint32, len[n] uint64 or None, per-stream
+    status[n] or None, mh_dev_status); asserts that the FIND_GUARD words behind crc and len kept their fill.  The outputs, the
+    statuses and the workspace are created without contents of their own."""
+    l = lib()
+    n, pay_total, d_pl, d_po, d_nb, so, d_idx = _dev_source(payload, pay_off, nbits, sym_off, index)
+    sym_total = int(so[n]) if so is not None else 0
+    d_so = DeviceBuffer(so.nbytes, so) if so is not None else None
+    wsb = l.mh_dev_crc_batch_workspace(n, sym_total, chunk_symbols if index is not None else 0)
+    d_ws = DeviceBuffer(wsb)
+    d_crc = _guarded(n * 4)
+    d_len = _guarded(n * 8) if want_len else None
+    d_st = DeviceBuffer(max(n, 1) * 4) if want_status else None
+    _check(fn(handle, d_pl.ptr, d_po.ptr, d_nb.ptr, n, pay_total, prev0, d_so.ptr if d_so else None, sym_total, d_idx.ptr if d_idx else None,
+              chunk_symbols, d_crc.ptr, d_len.ptr if d_len else None, d_st.ptr if d_st else None, d_ws.ptr, wsb, None), "mh_dev_crc_*")
+    rc = l.mh_dev_status(d_ws.ptr, None)
+    assert _guard_kept(d_crc, n * 4) and (d_len is None or _guard_kept(d_len, n * 8)), "words written behind crc / len"
+    return (d_crc.download(np.uint32)[:n], d_len.download(np.uint64)[:n] if d_len else None,
+            d_st.download(np.int32)[:n] if d_st else None, rc)
+
+
+def crc_raw_batch(messages, shift=0):
+    """mh_dev_crc_raw_batch of a list of byte strings: (crc[n] uint32, mh_dev_status).  `shift`: d_data starts that many bytes
+    into its allocation (an odd address)."""
+    l = lib()
+    data, off = batch_offsets(messages)
+    n, total = len(off) - 1, int(data.size)
+    d_data = DeviceBuffer(shift + total + 16, np.concatenate([np.zeros(shift, dtype=np.uint8), data, np.zeros(16, dtype=np.uint8)]))
+    d_off = DeviceBuffer(off.nbytes, off)
+    wsb = l.mh_dev_crc_raw_batch_workspace(n, total)
+    d_ws = DeviceBuffer(wsb)
+    d_crc = _guarded(n * 4)
+    _check(l.mh_dev_crc_raw_batch(C.c_void_p(d_data.ptr.value + shift), d_off.ptr, n, total, d_crc.ptr, d_ws.ptr, wsb, None), "mh_dev_crc_raw_batch")
+    rc = l.mh_dev_status(d_ws.ptr, None)
+    assert _guard_kept(d_crc, n * 4), "words written behind crc"
+    return d_crc.download(np.uint32)[:n], rc
+
+
+def crc32_combine(crc_a, crc_b, len_b):
+    """mh_crc32_combine (host arithmetic): the CRC-32 of A || B from those of A and B and len(B)."""
+    return int(lib().mh_crc32_combine(crc_a, crc_b, len_b))
+
+
+def _host_crc(fn, what, handle, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols, check):
+    """mh_crc_batch / mh_crc_batch_o2 (host form): (crc[n] uint32, len[n] uint64, per-stream status[n], return code).
+    check=False returns a failed stream's status instead of raising."""
+    payload = _u8(payload)
+    pay_off = np.ascontiguousarray(pay_off, dtype=np.uint64)
+    nbits = np.ascontiguousarray(nbits, dtype=np.uint64)
+    n = len(pay_off) - 1
+    so = np.ascontiguousarray(sym_off, dtype=np.uint64) if sym_off is not None else None
+    idx = np.ascontiguousarray(index, dtype=np.uint64) if index is not None else None
+    crc, ln, st = np.zeros(max(n, 1), dtype=np.uint32), np.zeros(max(n, 1), dtype=np.uint64), np.zeros(max(n, 1), dtype=np.int32)
+    rc = fn(handle, _ptr(payload), pay_off.ctypes.data, nbits.ctypes.data if n else None, n, prev0, so.ctypes.data if so is not None else None,
+            (idx.ctypes.data if idx.size else pay_off.ctypes.data) if idx is not None else None, chunk_symbols, crc.ctypes.data, ln.ctypes.data,
+            st.ctypes.data)
+    if rc != MH_OK and (check or not st[:n].any()):
+        raise MhError(rc, what)
+    return crc[:n], ln[:n], st[:n], rc
 
 
 def _dev_histogram_coded(fn, handle, order, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols, ws_fn=None):
@@ -1050,6 +1138,14 @@ class Model:
         (hit_off[n + 1], hits[k, 3], hit_pattern[k], per-stream status[n], mh_dev_status)."""
         return _dev_find(lib().mh_dev_find_batch, self._h, ps, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols, hit_cap, count_only)
 
+    def crc_batch(self, payload, pay_off, nbits, prev0=PREV0, sym_off=None, index=None, chunk_symbols=0, check=True):
+        """mh_crc_batch (host form): (crc[n], len[n], per-stream status[n], return code)."""
+        return _host_crc(lib().mh_crc_batch, "mh_crc_batch", self._h, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols, check)
+
+    def dev_crc_batch(self, payload, pay_off, nbits, prev0=PREV0, sym_off=None, index=None, chunk_symbols=0, **kw):
+        """One mh_dev_crc_batch call with guard words behind its outputs: (crc[n], len[n], per-stream status[n], mh_dev_status)."""
+        return _dev_crc(lib().mh_dev_crc_batch, self._h, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols, **kw)
+
     def dev_histogram_coded(self, order, payload, pay_off, nbits, prev0=PREV0, sym_off=None, index=None, chunk_symbols=0):
         """One mh_dev_histogram_coded_batch call on a batch coded under this model: (counts, per-stream status[n], mh_dev_status)."""
         return _dev_histogram_coded(lib().mh_dev_histogram_coded_batch, self._h, order, payload, pay_off, nbits, prev0, sym_off, index,
@@ -1276,6 +1372,14 @@ class Model:
         return _dev_find(lib().mh_dev_find_batch_o2, self._h, ps, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols, hit_cap,
                          count_only, ws_fn=lib().mh_dev_find_batch_o2_workspace)
 
+    def crc_batch_o2(self, payload, pay_off, nbits, prev0=PREV0, sym_off=None, index=None, chunk_symbols=0, check=True):
+        """mh_crc_batch_o2 (host form; this model is order 2): crc_batch's arguments and results."""
+        return _host_crc(lib().mh_crc_batch_o2, "mh_crc_batch_o2", self._h, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols, check)
+
+    def dev_crc_batch_o2(self, payload, pay_off, nbits, prev0=PREV0, sym_off=None, index=None, chunk_symbols=0, **kw):
+        """One mh_dev_crc_batch_o2 call with guard words behind its outputs: dev_crc_batch's results."""
+        return _dev_crc(lib().mh_dev_crc_batch_o2, self._h, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols, **kw)
+
     def dev_histogram_coded_o2(self, order, payload, pay_off, nbits, prev0=PREV0, sym_off=None, index=None, chunk_symbols=0):
         """One mh_dev_histogram_coded_batch_o2 call on a batch coded under this model (any order; the model or `order` is 2):
         (counts[256, 65536 or 1 << 24], per-stream status[n], mh_dev_status)."""
@@ -1501,6 +1605,11 @@ class ModelSet:
         """One mh_dev_find_each call (two when hit_cap is None) with guard words behind its outputs, stream i under model i:
         (hit_off[n + 1], hits[k, 3], hit_pattern[k], per-stream status[n], mh_dev_status)."""
         return _dev_find(lib().mh_dev_find_each, self._h, ps, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols, hit_cap, count_only)
+
+    def crc(self, payload, pay_off, nbits, prev0=PREV0, sym_off=None, index=None, chunk_symbols=0, **kw):
+        """One mh_dev_crc_each call with guard words behind its outputs, stream i under model i: (crc[n], len[n], per-stream
+        status[n], mh_dev_status)."""
+        return _dev_crc(lib().mh_dev_crc_each, self._h, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols, **kw)
 
     def histogram_coded(self, order, payload, pay_off, nbits, prev0=PREV0, sym_off=None, index=None, chunk_symbols=0):
         """One mh_dev_histogram_coded_each call: (counts, per-stream status[n], mh_dev_status)."""

@@ -1,6 +1,6 @@
 // mh_batch_dev.hpp — device code shared by the kernels of the batch call family: the decoders (mh_batch.hip, mh_each.hip,
 // mh_batch_o2.hip), the random-access decoders (mh_range.hip), the state builder (mh_batch_states.hip), the
-// search (mh_find.hip) and the re-coders (mh_recode.hip).  What lives here, once:
+// search (mh_find.hip), the re-coders (mh_recode.hip) and the digests (mh_crc.hip).  What lives here, once:
 //   gtid, grid_threads, grid_for     thread numbering and grid sizes
 //   fail, stopped, stream_fail       the status word, the stop flag, a stream's verdict
 //   find_stream                      closed-form unit and chunk numbering

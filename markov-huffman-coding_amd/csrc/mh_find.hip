@@ -18,8 +18,7 @@
 // LDS as load_tables lays them out, the 2 KiB of masks behind them when they leave room (MLDS), else read from the workspace),
 // a model set and a shared order-2 model (tables in L2, masks in LDS at offset 0).
 #include "mh_find.h"
-#include "mh_batch_dev.hpp"
-#include "mh_each_dev.hpp"
+#include "mh_symdec_dev.hpp"
 #include "../../include/mh.h"
 
 namespace mhf {
@@ -43,52 +42,7 @@ using mhb::scan_exclusive;
 using mhb::stopped;
 using mhb::stream_fail;
 
-// The symbol decoder of a lane, one policy per model.  next() decodes one symbol in the lane's context ctx and rolls ctx on:
-// the kernels feed the symbol to the matcher and never touch the context.  A stream starts in b.prev0 (order 2: both bytes).
-//   NT, PER_CU   the workgroup shape: that of the model's batch decoder
-//   O2           the format of the batch's index entries (mhb::chunk_of)
-template <Model K> struct Dec;
-// the shared model's two-level tables in LDS; one workgroup per CU beside them (batch_dec_idx_kernel's shape)
-template <> struct Dec<Model::Shared> {
-    static constexpr int NT = mhb::B_THREADS, PER_CU = 1;
-    static constexpr bool O2 = false;
-    const uint16_t *lut;
-    const uint32_t *sub_base;
-    DecTables tabs;
-    __device__ __forceinline__ Dec(const FindParams &p, unsigned char *smem) : tabs(mhb::load_tables(p.b, smem, lut, sub_base)) {}
-    __device__ __forceinline__ void stream(const FindParams &, uint64_t) {}
-    __device__ __forceinline__ uint32_t next(const FindParams &, const BitSrc &src, BitCursor &bc, uint32_t &ctx, uint32_t &used, bool &bad) const {
-        return ctx = mhk::decode_one(lut, sub_base, tabs, src, bc, ctx, used, bad);
-    }
-};
-// stream i's slots in L2 (each_dec_idx_kernel's shape)
-template <> struct Dec<Model::Set> {
-    static constexpr int NT = 256, PER_CU = 8;
-    static constexpr bool O2 = false;
-    const uint32_t *row;
-    bool o1;
-    __device__ __forceinline__ Dec(const FindParams &, unsigned char *) : row(nullptr), o1(false) {}
-    __device__ __forceinline__ void stream(const FindParams &p, uint64_t i) { row = p.set.ctx_slot + i * 256u; o1 = p.set.type[i] != 0; }
-    __device__ __forceinline__ uint32_t next(const FindParams &p, const BitSrc &src, BitCursor &bc, uint32_t &ctx, uint32_t &used, bool &bad) const {
-        return ctx = mhe::decode_sym(p.set, row, o1 ? ctx : 0u, src, bc, used, bad);
-    }
-};
-// the shared model's order-2 tables as decode2_kernel reads them: general form, every level gathered from L2
-// (batch2_dec_idx_kernel's shape); ctx holds the last two symbols
-template <> struct Dec<Model::Shared2> {
-    static constexpr int NT = 256, PER_CU = 8;
-    static constexpr bool O2 = true;
-    const uint16_t *prim;
-    const uint32_t *sec_base;
-    DecTables tabs;
-    __device__ __forceinline__ Dec(const FindParams &p, unsigned char *) : prim(p.b.prim), sec_base(p.b.sec_base), tabs{p.b.sec, p.b.tree, p.b.P, 0u, 0u} {}
-    __device__ __forceinline__ void stream(const FindParams &, uint64_t) {}
-    __device__ __forceinline__ uint32_t next(const FindParams &, const BitSrc &src, BitCursor &bc, uint32_t &ctx, uint32_t &used, bool &bad) const {
-        const uint32_t sym = mhk::decode_one(prim, sec_base, tabs, src, bc, ctx, used, bad);
-        ctx = ((ctx << 8) | sym) & 0xFFFFu;
-        return sym;
-    }
-};
+using mhb::Dec;                                               // the symbol decoder of a lane, one policy per model (mh_symdec_dev.hpp)
 
 // mask[c]: one ds_read_b64 (MLDS) or an 8-byte load from the workspace
 template <bool MLDS> struct Masks {

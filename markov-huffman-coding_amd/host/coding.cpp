@@ -472,6 +472,29 @@ uint64_t i_coding_provider::find(FILE* input_fd, const std::vector<std::string>&
     return total;
 }
 
+// --crc: the `.cm` file as a batch of one stream, digested on the device without writing its bytes (mh_crc_batch): one line
+// `%08x %llu`, the CRC-32 and the length of the original input.  With a usable index sidecar the stream is read through it.
+void i_coding_provider::crc(FILE* input_fd) {
+    InputView in(input_fd, true);
+    if (in.size == 0) mh_or_die(MH_ERR_CORRUPT, "crc");
+    uint64_t nbits = 0;
+    mh_or_die(mh_stream_parse_header(model_, in.data[0], in.size, &nbits), "crc");
+    std::vector<uint64_t> index;
+    uint64_t n_symbols = 0;
+    uint32_t chunk = 0;
+    const bool have_index = load_index(index_path_, nbits, index, chunk, n_symbols);
+    if (have_index) index.resize((size_t)mh_batch_index_capacity(n_symbols, 1, chunk));   // (the slice of stream 0 starts at entry 0)
+    const uint64_t pay_off[2] = {0, (uint64_t)in.size - 1}, sym_off[2] = {0, n_symbols};
+    uint32_t crc = 0;
+    uint64_t len = 0;
+    StageTimer timer("crc", in.size);
+    mh_or_die(mh_crc_batch(model_, in.data + 1, pay_off, &nbits, 1, MH_PREV0, have_index ? sym_off : nullptr, have_index ? index.data() : nullptr,
+                           have_index ? chunk : 0, &crc, &len, nullptr), "crc");
+    printf("%08x %llu\n", crc, (unsigned long long)len);
+    fflush(stdout);
+    fclose(input_fd);
+}
+
 // --recode: the `.cm` file as a batch of one stream, coded again under `dst` on the device without writing its bytes
 // (mh_recode_batch).  The output is the file the reference writes for the original input with `-e` of dst's table.  With a
 // usable index sidecar the source is read through it and the output's own index is written beside the output.

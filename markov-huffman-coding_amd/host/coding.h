@@ -60,6 +60,8 @@ public:
     // extension: prints one line `pattern begin` per occurrence of the patterns in the compressed input (needs the index
     // sidecar), in ascending (end, pattern number) order, and returns their number; nothing is decompressed to a file
     uint64_t find(FILE* input_fd, const std::vector<std::string>& patterns, bool fold);
+    // --crc: prints `crc32 length` of the original input, taken on the device without writing its bytes
+    void crc(FILE* input_fd);
     // --recode: the `.cm` on input_fd (coded under this model) coded again under `dst` without writing its bytes
     // (mh_recode_batch); with a usable index sidecar the indexed path, and the output's index goes to `out_index_path`
     void recode(FILE* input_fd, FILE* output_fd, const i_coding_provider& dst, const std::string& out_index_path);

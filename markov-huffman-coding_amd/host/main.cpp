@@ -15,6 +15,8 @@
 //                    --index the indexed path, and the output's own index goes to <output>.idx
 //   --find STRING    print `pattern begin` per occurrence of STRING in the original input, searched on the device without
 //                    decompressing (repeatable, 64 bytes in all; --find-fold folds ASCII case; needs -x and --index)
+//   --crc            with -x: print `crc32 length` of the original input (CRC-32 as zlib computes it, %08x, and the byte
+//                    count), taken on the device without decompressing; with --index the indexed path
 #include <errno.h>
 #include <stdlib.h>
 #include <string.h>
@@ -44,6 +46,8 @@ static void print_help() {
     eprintf("\t--find string  with -x and --index: print `pattern begin` for every occurrence of the string in the original input\n");
     eprintf("\t               without decompressing it (repeatable, 64 bytes in all; --find-fold: ASCII letters match either case);\n");
     eprintf("\t               exit status 0 with hits, 1 with none\n");
+    eprintf("\t--crc          with -x: print the CRC-32 (as zlib computes it) and the length of the original input without\n");
+    eprintf("\t               decompressing it, as `%%08x %%llu`; with --index the indexed path; no output file is written\n");
     eprintf("\t--recode table with -x, -e and -o: write the stream coded again under `table` (the bytes are never written);\n");
     eprintf("\t               with --index the output's index goes to <output>.idx\n");
 }
@@ -63,6 +67,7 @@ struct options {
     std::vector<std::string> finds;                               // one per --find
     bool find_fold = false;
     const char* recode_table = nullptr;                           // --recode: the table the stream is coded again under
+    bool crc = false;                                             // --crc: print the digest of the original input
 };
 
 // "B:E" with decimal B <= E; anything else is an error
@@ -122,6 +127,7 @@ static options parse(int argc, char* argv[]) {
             else if (!strcmp(a, "--find")) o.finds.push_back(need(a));
             else if (!strcmp(a, "--find-fold")) o.find_fold = true;
             else if (!strcmp(a, "--recode")) o.recode_table = need(a);
+            else if (!strcmp(a, "--crc")) o.crc = true;
             else eprintf("Warning: Unknown option %s.\n", a);
             continue;
         }
@@ -225,6 +231,21 @@ int main(int argc, char* argv[]) {
         }
     }
 
+    if (o.crc) {                                                   // checked before anything is opened or a device is used
+        if (!o.extract) {
+            eprintf("Error: --crc needs -x.\n");
+            exit(1);
+        }
+        if (!o.finds.empty() || !o.ranges.empty() || o.recode_table) {
+            eprintf("Error: --crc cannot be combined with --find, --range or --recode.\n");
+            exit(1);
+        }
+        if (o.order2) {
+            eprintf("Error: --crc does not support --order2.\n");
+            exit(1);
+        }
+    }
+
     if (o.max_code_len && (o.encoding_input || o.extract || o.order2)) {
         eprintf("Error: --max-code-len limits a table that is being trained; it cannot be combined with -e, -x or --order2.\n");
         exit(1);
@@ -255,7 +276,7 @@ int main(int argc, char* argv[]) {
     if (o.encoding_output) check_access(o.encoding_output, false);
 
     FILE* input_fd = open_or_die(o.input, "rb", "input");
-    FILE* output_fd = o.output && o.finds.empty() ? open_or_die(o.output, "w+b", "output") : stdout;   // read-write: the result is written through a mapping
+    FILE* output_fd = o.output && o.finds.empty() && !o.crc ? open_or_die(o.output, "w+b", "output") : stdout;   // read-write: the result is written through a mapping
 
     i_coding_provider* coder = nullptr;
     if (o.encoding_input) {
@@ -317,6 +338,13 @@ int main(int argc, char* argv[]) {
         delete coder;
         eprintf("Done.\n");
         return hits ? 0 : 1;
+    }
+    if (o.crc) {                                                   // prints the digest; no output file
+        eprintf("Checksumming %s...\n", o.input);
+        coder->crc(input_fd);
+        delete coder;
+        eprintf("Done.\n");
+        return 0;
     }
     if (o.recode_table) {                                          // the new table: either kind, whatever the old one is
         FILE* fd = open_or_die(o.recode_table, "rb", "--recode table");
