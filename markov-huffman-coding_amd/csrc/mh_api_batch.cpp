@@ -1,9 +1,43 @@
 // mh_api_batch.cpp — the batch calls of the C ABI (include/mh.h, "BATCHES OF INDEPENDENT STREAMS"): many small order-0/1
-// streams under one shared model in a few launches (kernels: mh_batch.hip), and their host-buffer forms.
+// streams under one shared model in a few launches (kernels: mh_batch.hip), and their host-buffer forms.  The device decode
+// call of the order-2 batches (mh_api_batch_o2.cpp has the rest of that family) is the second entry of the one here.
 #include "mh_api_internal.hpp"
 #include "mh_batch.h"
+#include "mh_each.h"
 
 using namespace mhapi;
+
+namespace {
+
+// mh_dev_decode_batch (o2 = false: an order-0/1 model) and mh_dev_decode_batch_o2 (an order-2 model)
+int dev_decode_batch(const mh_model *m, bool o2, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits, size_t n_streams,
+                     uint64_t pay_total, uint8_t prev0, uint8_t *d_out, uint64_t out_cap, uint64_t *d_sym_off, uint64_t sym_total,
+                     const uint64_t *d_index, uint32_t chunk_symbols, int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
+    if (!(o2 ? order2(m) : order01(m)) || (!d_payload && pay_total) || !d_pay_off || (!d_nbits && n_streams) || !d_sym_off ||
+        (!d_out && out_cap) || !d_ws)
+        return MH_ERR_ARG;
+    if (!aligned16(d_payload) || !aligned16(d_out) || !aligned16(d_ws)) return MH_ERR_ARG;
+    const int shift = d_index ? chunk_shift_of(chunk_symbols) : 0;
+    if (shift < 0) return MH_ERR_ARG;
+    const mhb::DecLayout L = mhb::dec_layout(n_streams);
+    if (ws_bytes < L.total) return MH_ERR_CAPACITY;
+    if (d_index && sym_total > out_cap) return MH_ERR_CAPACITY;
+    if (m->max_len > mh::MAX_CODE_BITS) return MH_ERR_CODE_TOO_LONG;
+    if (!m->d_prim || !have_device()) return MH_ERR_NO_DEVICE;
+    mhb::DecodeParams p{};
+    mhb::DecBatchParams &b = p.b;
+    b.payload = d_payload; b.pay_off = d_pay_off; b.nbits = d_nbits; b.n = n_streams; b.pay_total = pay_total; b.prev0 = ctx_of_prev0(m, prev0);
+    b.out = d_out; b.out_cap = out_cap;
+    b.sym_off = reinterpret_cast<unsigned long long *>(d_sym_off); b.sym_total = sym_total;
+    b.index = d_index; b.chunk_shift = uint32_t(shift);
+    b.walk_max_bits = MH_BATCH_WALK_MAX_BITS;
+    b.stream_status = d_stream_status ? d_stream_status : reinterpret_cast<int *>(static_cast<unsigned char *>(d_ws) + L.off_status);
+    fill_dec_tables(m, b);
+    HIP_TRY(mhb::launch_decode(p, o2 ? mhb::Model::Shared2 : mhb::Model::Shared, d_ws, static_cast<hipStream_t>(stream)));
+    return MH_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -81,29 +115,20 @@ int mh_dev_encode_batch(const mh_model *m, const uint8_t *d_data, const uint64_t
 
 size_t mh_dev_decode_batch_workspace(size_t n_streams) { return mhb::dec_layout(n_streams).total; }
 
+size_t mh_dev_decode_batch_o2_workspace(size_t n_streams) { return mhb::dec_layout(n_streams).total; }
+
 int mh_dev_decode_batch(const mh_model *m, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits, size_t n_streams,
                         uint64_t pay_total, uint8_t prev0, uint8_t *d_out, uint64_t out_cap, uint64_t *d_sym_off, uint64_t sym_total,
                         const uint64_t *d_index, uint32_t chunk_symbols, int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
-    if (!order01(m) || (!d_payload && pay_total) || !d_pay_off || (!d_nbits && n_streams) || !d_sym_off || (!d_out && out_cap) || !d_ws)
-        return MH_ERR_ARG;
-    if (!aligned16(d_payload) || !aligned16(d_out) || !aligned16(d_ws)) return MH_ERR_ARG;
-    const int shift = d_index ? chunk_shift_of(chunk_symbols) : 0;
-    if (shift < 0) return MH_ERR_ARG;
-    if (ws_bytes < mh_dev_decode_batch_workspace(n_streams)) return MH_ERR_CAPACITY;
-    if (d_index && sym_total > out_cap) return MH_ERR_CAPACITY;
-    if (m->max_len > mh::MAX_CODE_BITS) return MH_ERR_CODE_TOO_LONG;
-    if (!m->d_prim || !have_device()) return MH_ERR_NO_DEVICE;
-    const mhb::DecLayout L = mhb::dec_layout(n_streams);
-    mhb::DecBatchParams p{};
-    p.payload = d_payload; p.pay_off = d_pay_off; p.nbits = d_nbits; p.n = n_streams; p.pay_total = pay_total; p.prev0 = prev0;
-    p.out = d_out; p.out_cap = out_cap;
-    p.sym_off = reinterpret_cast<unsigned long long *>(d_sym_off); p.sym_total = sym_total;
-    p.index = d_index; p.chunk_shift = uint32_t(shift);
-    p.walk_max_bits = MH_BATCH_WALK_MAX_BITS;
-    p.stream_status = d_stream_status ? d_stream_status : reinterpret_cast<int *>(static_cast<unsigned char *>(d_ws) + L.off_status);
-    fill_dec_tables(m, p);
-    HIP_TRY(mhb::launch_decode_batch(p, d_ws, static_cast<hipStream_t>(stream)));
-    return MH_OK;
+    return dev_decode_batch(m, false, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_out, out_cap, d_sym_off, sym_total, d_index,
+                            chunk_symbols, d_stream_status, d_ws, ws_bytes, stream);
+}
+
+int mh_dev_decode_batch_o2(const mh_model *m, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits, size_t n_streams,
+                           uint64_t pay_total, uint8_t prev0, uint8_t *d_out, uint64_t out_cap, uint64_t *d_sym_off, uint64_t sym_total,
+                           const uint64_t *d_index, uint32_t chunk_symbols, int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
+    return dev_decode_batch(m, true, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_out, out_cap, d_sym_off, sym_total, d_index,
+                            chunk_symbols, d_stream_status, d_ws, ws_bytes, stream);
 }
 
 }  // extern "C"

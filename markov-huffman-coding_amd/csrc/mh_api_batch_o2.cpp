@@ -1,6 +1,7 @@
 // mh_api_batch_o2.cpp — the order-2 batch calls of the C ABI (include/mh.h, "BATCHES OF ORDER-2 STREAMS"): many small
 // streams under one shared order-2 model in a few launches (kernels: mh_batch_o2.hip), and their host-buffer forms (the
-// bodies of mh_encode_batch / mh_decode_batch over the order-2 device calls).  Extension, parity unpinned.
+// bodies of mh_encode_batch / mh_decode_batch over the order-2 device calls).  mh_dev_decode_batch_o2 is the second entry of
+// mh_dev_decode_batch's body (mh_api_batch.cpp).  Extension, parity unpinned.
 #include "mh_api_internal.hpp"
 #include "mh_batch_o2.h"
 
@@ -50,33 +51,6 @@ int mh_dev_encode_batch_o2(const mh_model *m, const uint8_t *d_data, const uint6
     p.len8 = m->d_len8; p.code64 = m->d_code64; p.enc64 = m->d_enc64; p.max_len = m->max_len;
     if (m->o2_enc_ok) { p.o2img = m->d_o2img; p.o2img_bytes = m->o2img_bytes; }    // (the single-stream encoder's rule: mh_api.cpp)
     HIP_TRY(mhb::launch_encode_batch_o2(p, d_ws, static_cast<hipStream_t>(stream)));
-    return MH_OK;
-}
-
-size_t mh_dev_decode_batch_o2_workspace(size_t n_streams) { return mhb::dec_layout(n_streams).total; }
-
-int mh_dev_decode_batch_o2(const mh_model *m, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits, size_t n_streams,
-                           uint64_t pay_total, uint8_t prev0, uint8_t *d_out, uint64_t out_cap, uint64_t *d_sym_off, uint64_t sym_total,
-                           const uint64_t *d_index, uint32_t chunk_symbols, int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
-    if (!order2(m) || (!d_payload && pay_total) || !d_pay_off || (!d_nbits && n_streams) || !d_sym_off || (!d_out && out_cap) || !d_ws)
-        return MH_ERR_ARG;
-    if (!aligned16(d_payload) || !aligned16(d_out) || !aligned16(d_ws)) return MH_ERR_ARG;
-    const int shift = d_index ? chunk_shift_of(chunk_symbols) : 0;
-    if (shift < 0) return MH_ERR_ARG;
-    if (ws_bytes < mh_dev_decode_batch_o2_workspace(n_streams)) return MH_ERR_CAPACITY;
-    if (d_index && sym_total > out_cap) return MH_ERR_CAPACITY;
-    if (m->max_len > mh::MAX_CODE_BITS) return MH_ERR_CODE_TOO_LONG;
-    if (!m->d_prim || !have_device()) return MH_ERR_NO_DEVICE;
-    const mhb::DecLayout L = mhb::dec_layout(n_streams);
-    mhb::DecBatchParams p{};
-    p.payload = d_payload; p.pay_off = d_pay_off; p.nbits = d_nbits; p.n = n_streams; p.pay_total = pay_total; p.prev0 = ctx_of_prev0(m, prev0);
-    p.out = d_out; p.out_cap = out_cap;
-    p.sym_off = reinterpret_cast<unsigned long long *>(d_sym_off); p.sym_total = sym_total;
-    p.index = d_index; p.chunk_shift = uint32_t(shift);
-    p.walk_max_bits = MH_BATCH_WALK_MAX_BITS;
-    p.stream_status = d_stream_status ? d_stream_status : reinterpret_cast<int *>(static_cast<unsigned char *>(d_ws) + L.off_status);
-    fill_dec_tables(m, p);
-    HIP_TRY(mhb::launch_decode_batch_o2(p, d_ws, static_cast<hipStream_t>(stream)));
     return MH_OK;
 }
 

@@ -339,15 +339,16 @@ int mh_dev_decode_each(const mh_model_set *s, const uint8_t *d_payload, const ui
     if (d_index && sym_total > out_cap) return MH_ERR_CAPACITY;
     if (!have_device()) return MH_ERR_NO_DEVICE;
     const mhb::DecLayout L = mhb::dec_layout(n_streams);
-    mhe::DecEachParams p{};
-    p.payload = d_payload; p.pay_off = d_pay_off; p.nbits = d_nbits; p.n = n_streams; p.pay_total = pay_total; p.prev0 = prev0;
-    p.out = d_out; p.out_cap = out_cap;
-    p.sym_off = reinterpret_cast<unsigned long long *>(d_sym_off); p.sym_total = sym_total;
-    p.index = d_index; p.chunk_shift = uint32_t(shift);
-    p.walk_max_bits = MH_BATCH_WALK_MAX_BITS;
-    p.stream_status = d_stream_status ? d_stream_status : reinterpret_cast<int *>(static_cast<unsigned char *>(d_ws) + L.off_status);
+    mhb::DecodeParams p{};
+    mhb::DecBatchParams &b = p.b;
+    b.payload = d_payload; b.pay_off = d_pay_off; b.nbits = d_nbits; b.n = n_streams; b.pay_total = pay_total; b.prev0 = prev0;
+    b.out = d_out; b.out_cap = out_cap;
+    b.sym_off = reinterpret_cast<unsigned long long *>(d_sym_off); b.sym_total = sym_total;
+    b.index = d_index; b.chunk_shift = uint32_t(shift);
+    b.walk_max_bits = MH_BATCH_WALK_MAX_BITS;
+    b.stream_status = d_stream_status ? d_stream_status : reinterpret_cast<int *>(static_cast<unsigned char *>(d_ws) + L.off_status);
     p.set = s->d;
-    HIP_TRY(mhe::launch_decode_each(p, d_ws, static_cast<hipStream_t>(stream)));
+    HIP_TRY(mhb::launch_decode(p, mhb::Model::Set, d_ws, static_cast<hipStream_t>(stream)));
     return MH_OK;
 }
 

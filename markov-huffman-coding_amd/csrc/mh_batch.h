@@ -1,6 +1,7 @@
 // mh_batch.h — launch interface between the batch calls of the C ABI (mh_api_batch.cpp) and their kernels (mh_batch.hip):
 // many independent order-0/1 streams under one shared model, each starting in context prev0 (include/mh.h, "BATCHES OF
-// INDEPENDENT STREAMS").  The common kernel headers are included read-only; nothing here changes a single-stream path.
+// INDEPENDENT STREAMS"), and the batch decoders of every model kind (launch_decode).  The common kernel headers are included
+// read-only; nothing here changes a single-stream path.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -96,11 +97,11 @@ struct DecBatchParams {
     uint32_t P, nsec, sec_lds, direct, H;
 };
 
-// The model a batch to decode was coded under, for the call families that serve all three (search: mh_find.h, re-coding:
-// mh_recode.h).  Shared: one order-0/1 model (the tables go to LDS, prev0 is a byte, index entries carry one context byte).
-// Set: stream i under set model i (mh_each.h).  Shared2: one order-2 model, described as for launch_decode_batch_o2
-// (mh_batch_o2.h): the tables are the order-2 tables (general form, L2), prev0 is the 16-bit start context, index entries
-// carry the context in bits 48..63.
+// The model a batch to decode was coded under, for the call families that serve all three (decoding: launch_decode, search:
+// mh_find.h, re-coding: mh_recode.h, ...).  Shared: one order-0/1 model (the tables go to LDS, prev0 is a byte, index entries
+// carry one context byte).  Set: stream i under set model i (mh_each.h).  Shared2: one order-2 model: DecBatchParams holds the
+// model's order-2 tables (prim / sec / sec_base / tree of 65536 contexts, general form, read from L2, sec_lds = direct = 0),
+// prev0 is the 16-bit start context, index entries carry the context in bits 48..63.
 enum class Model { Shared, Set, Shared2 };
 
 // LDS bytes of a shared model's decode tables as mhb::load_tables (mh_batch_dev.hpp) lays them out: the two are a pair, and
@@ -114,6 +115,10 @@ inline size_t tables_lds(const T &t) {
 hipError_t launch_hist_fixup(const uint8_t *d_data, const uint64_t *d_in_off, uint64_t n, uint64_t total, uint32_t prev0,
                              unsigned long long *d_counts, int order, int *d_status, hipStream_t st);
 hipError_t launch_encode_batch(const EncBatchParams &p, void *d_ws, hipStream_t st);
-hipError_t launch_decode_batch(const DecBatchParams &p, void *d_ws, hipStream_t st);
+// A batch to decode under any model kind: DecodeParams { DecBatchParams b; mhe::SetDev set; } is defined in mh_each.h, which
+// knows the model set (mh_each.h includes this header, so the struct cannot be completed here); a caller includes both.
+// model: what the batch was coded under; workspace: dec_layout.
+struct DecodeParams;
+hipError_t launch_decode(const DecodeParams &p, Model model, void *d_ws, hipStream_t st);
 
 }  // namespace mhb

@@ -7,7 +7,11 @@
 //   offsets_bad, check_batch         the up-front checks of a batch to decode: every call of the family gives the same verdicts
 //   Chunk, chunk_of<O2>              chunk w of an indexed batch in either entry format
 //   load16, byte_of                  unaligned 16-byte loads
+//   Unit, unit_of<CTX>               a lane's 16 bytes of an encoder's work unit and the one or two bytes in front of them
 //   scan_exclusive                   the segmented u64 scans
+//   batch_check_kernel, batch_enc_sizes_kernel, batch_zero_kernel, batch_tail_kernel
+//                                    the stages of a batch encoder that do not look at the model (mh_batch.hip, mh_batch_o2.hip,
+//                                    mh_each.hip; the last two serve the table files of mh_each.hip as well)
 //   BitWriter, ByteOut, stream_src   bits out with shared edge words and the tail word, bytes out, a payload as a bit source
 //   load_tables                      a shared model's decode tables into LDS (their size: mhb::tables_lds, mh_batch.h)
 // Everything is in an unnamed namespace: each kernel file gets its own copy.
@@ -35,9 +39,8 @@ __device__ __forceinline__ bool stopped(const int *stop) { return *reinterpret_c
 __device__ __forceinline__ uint64_t gtid() { return uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; }
 inline dim3 grid_threads(uint64_t items, uint32_t per_block) { return dim3(uint32_t((items + per_block - 1) / per_block)); }
 
-// stream i's verdict (P: DecBatchParams or DecEachParams)
-template <typename P>
-__device__ __forceinline__ void stream_fail(const P &p, int *status, uint64_t i, int mh_code, int dev_code) {
+// stream i's verdict
+__device__ __forceinline__ void stream_fail(const DecBatchParams &p, int *status, uint64_t i, int mh_code, int dev_code) {
     p.stream_status[i] = mh_code;
     fail(status, dev_code);
 }
@@ -50,9 +53,8 @@ __device__ __forceinline__ bool offsets_bad(const T *off, uint64_t n, uint64_t t
 
 // The up-front checks of a batch to decode, thread i <= n: pay_off[0] != 0, pay_off[n] != pay_total or a decreasing pair, the
 // same of sym_off with an index -> BATCH_STATUS_ARG and the call stops (returns true); else stream_status[i] = MH_OK, or
-// MH_ERR_ARG when nbits_i does not fit the stream's payload.  P: DecBatchParams or DecEachParams.
-template <typename P>
-__device__ __forceinline__ bool check_batch(const P &p, uint64_t i, int *status, int *stop) {
+// MH_ERR_ARG when nbits_i does not fit the stream's payload.
+__device__ __forceinline__ bool check_batch(const DecBatchParams &p, uint64_t i, int *status, int *stop) {
     bool bad = offsets_bad(p.pay_off, p.n, p.pay_total, i);
     if (p.index) bad |= offsets_bad(p.sym_off, p.n, p.sym_total, i);
     if (bad) { fail(status, BATCH_STATUS_ARG); atomicExch(stop, 1); }
@@ -82,7 +84,8 @@ struct Chunk {
     __device__ __forceinline__ bool entry_ok() const { return start <= end && end <= nb; }
 };
 // O2: entries of an order-2 index (position in IDX2_POS, two context bytes from bit 48), else of an order-0/1 index
-// (MH_INDEX_BIT_MASK, one byte from bit 56).  false when w is a gap.
+// (MH_INDEX_BIT_MASK, one byte from bit 56).  false when w is a gap.  dec_idx_kernel (mh_batch.hip) carries these steps in its
+// own body, with the stream's status tested before the entry is read: change the entry format here and there.
 template <bool O2>
 __device__ __forceinline__ bool chunk_of(const DecBatchParams &b, uint64_t w, Chunk &c) {
     constexpr uint64_t pos = O2 ? mhk::IDX2_POS : MH_INDEX_BIT_MASK;
@@ -123,6 +126,38 @@ __device__ __forceinline__ void load16(const uint8_t *p, uint32_t cnt, uint32_t 
     }
 }
 __device__ __forceinline__ uint32_t byte_of(const uint32_t (&x)[4], uint32_t t) { return (x[t >> 2] >> (8u * (t & 3u))) & 255u; }
+
+// Work unit u of a batch to encode (closed-form numbering of mh_batch.h): its stream, the lane's bytes and the context in
+// front of them, CTX bytes wide (1: order 0/1, 2: order 2) and prev0 at the stream's start; false when the unit
+// (wave-uniform) has nothing to code.
+struct Unit {
+    uint64_t i, a, ni, ub, j0;
+    uint32_t cnt, ctx;
+    uint32_t x[4];
+};
+template <int CTX>
+__device__ __forceinline__ bool unit_of(const uint8_t *data, const uint64_t *in_off, uint64_t n, uint32_t prev0, uint64_t u, Unit &l) {
+    static_assert(CTX == 1 || CTX == 2, "one context byte or two");
+    l.i = find_stream(in_off, n, SUB_SHIFT, u);
+    if (l.i >= n) return false;
+    l.a = in_off[l.i];
+    l.ni = in_off[l.i + 1] - l.a;
+    l.ub = (l.a >> SUB_SHIFT) + l.i;
+    const uint64_t s0 = (u - l.ub) << SUB_SHIFT;
+    if (s0 >= l.ni) return false;
+    l.j0 = s0 + uint64_t(mhk::lane_id()) * B_VEC;
+    l.cnt = l.j0 < l.ni ? uint32_t(l.ni - l.j0 < B_VEC ? l.ni - l.j0 : B_VEC) : 0u;
+    l.x[0] = l.x[1] = l.x[2] = l.x[3] = 0;
+    l.ctx = prev0;
+    if (l.cnt) {
+        load16(data + l.a + l.j0, l.cnt, l.x);
+        if (l.j0) {                                                // (j0 is 0 or >= 16)
+            const uint8_t *f = data + l.a + l.j0;
+            l.ctx = CTX == 2 ? (uint32_t(f[-2]) << 8) | f[-1] : f[-1];
+        }
+    }
+    return true;
+}
 
 // ------------------------------------------------------------------------------------------------ scans (exclusive, u64)
 
@@ -188,6 +223,55 @@ hipError_t scan_exclusive(unsigned long long *a, uint64_t len, unsigned long lon
     hipLaunchKernelGGL(batch_scan_add_kernel, dim3(uint32_t(nb)), dim3(SCAN_T), 0, st, a, len, sums, stop);
     return hipGetLastError();
 }
+
+// ------------------------------------------------------------------------------------------------ model-free encode stages
+
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wunused-function"               // (a file that only decodes launches none of these)
+
+// offsets non-decreasing, [0] == 0, [n] == total, else BATCH_STATUS_ARG and the call stops
+__global__ void batch_check_kernel(const uint64_t *off, uint64_t n, uint64_t total, int *status, int *stop) {
+    const uint64_t i = gtid();
+    if (i > n) return;
+    if (offsets_bad(off, n, total, i)) { fail(status, BATCH_STATUS_ARG); atomicExch(stop, 1); }
+}
+
+// stream i: payload bits from the scanned unit bits, payload bytes into out_off (scanned next)
+__global__ void batch_enc_sizes_kernel(const uint64_t *in_off, uint64_t n, const unsigned long long *ubase, unsigned long long *nbits,
+                                       unsigned long long *out_off, const int *stop) {
+    if (stopped(stop)) return;
+    const uint64_t i = gtid();
+    if (i > n) return;
+    if (i == n) { out_off[i] = 0; return; }
+    const uint64_t u0 = (in_off[i] >> SUB_SHIFT) + i, u1 = (in_off[i + 1] >> SUB_SHIFT) + i + 1;
+    const unsigned long long bits = ubase[u1] - ubase[u0];
+    nbits[i] = bits;
+    out_off[i] = (bits + 7) >> 3;
+}
+
+// zeroes the output bytes [0, *off_end) (bits are OR-ed into shared edge words) or reports that they do not fit
+__global__ void batch_zero_kernel(const unsigned long long *off_end, uint8_t *out, uint64_t cap, int *status, int *stop, uint32_t *tail) {
+    if (stopped(stop)) return;
+    const uint64_t bytes = *off_end;
+    if (bytes > cap) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) { fail(status, mhk::MHK_STATUS_CAPACITY); atomicExch(stop, 1); }
+        return;
+    }
+    uint32_t *o = reinterpret_cast<uint32_t *>(out);
+    for (uint64_t k = gtid(); k < (bytes >> 2); k += uint64_t(gridDim.x) * blockDim.x) o[k] = 0u;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *tail = 0u;
+}
+
+// the bytes of the last, partial dword from the workspace's tail word (BitWriter): nothing is touched at or beyond *off_end
+__global__ void batch_tail_kernel(const unsigned long long *off_end, uint8_t *out, const uint32_t *tail, const int *stop) {
+    if (stopped(stop)) return;
+    const uint64_t bytes = *off_end;
+    if (!(bytes & 3u)) return;
+    const uint8_t *t = reinterpret_cast<const uint8_t *>(tail);
+    for (uint64_t b = bytes & ~uint64_t(3); b < bytes; ++b) out[b] = t[b & 3u];
+}
+
+#pragma clang diagnostic pop
 
 // Bits into 32-bit words, first stream bit in bit 31 of a word stored byte-swapped (MSB first inside a byte,
 // src/bitbuffer.cpp:12).  A word that lies wholly inside the lane's bits is stored; its edge words are shared with the

@@ -1,7 +1,7 @@
 // mh_batch_o2.h — launch interface between the order-2 batch calls of the C ABI (mh_api_batch_o2.cpp) and their kernels
 // (mh_batch_o2.hip): many independent streams under one shared order-2 model, each starting in context (prev0, prev0)
-// (include/mh.h, "BATCHES OF ORDER-2 STREAMS").  Layouts, work units, workspaces and the decode parameters are those of the
-// order-0/1 batch (mh_batch.h); only the encoder's tables differ.
+// (include/mh.h, "BATCHES OF ORDER-2 STREAMS").  Layouts, work units and workspaces are those of the order-0/1 batch
+// (mh_batch.h); only the encoder's tables differ.  The decoder is mhb::launch_decode under Model::Shared2.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -25,10 +25,7 @@ struct EncBatchO2Params : EncBatchParams {
 // prev0 << 8 | first byte).  Offsets are checked as in launch_hist_fixup (MH_ERR_ARG through d_status).
 hipError_t launch_hist2_fixup(const uint8_t *d_data, const uint64_t *d_in_off, uint64_t n, uint64_t total, uint32_t prev0,
                               unsigned long long *d_counts, int *d_status, hipStream_t st);
-// workspaces: enc_layout / dec_layout of mh_batch.h.  DecBatchParams: prev0 = the 16-bit start context, the model's order-2
-// tables (prim / sec / sec_base / tree of 65536 contexts, general form, sec_lds = direct = 0); index entries carry the
-// context in bits 48..63.
+// workspace: enc_layout of mh_batch.h; index entries carry the context in bits 48..63
 hipError_t launch_encode_batch_o2(const EncBatchO2Params &p, void *d_ws, hipStream_t st);
-hipError_t launch_decode_batch_o2(const DecBatchParams &p, void *d_ws, hipStream_t st);
 
 }  // namespace mhb

@@ -1,18 +1,18 @@
 // mh_batch_o2.hip — batches of independent streams under one shared ORDER-2 model (include/mh.h, "BATCHES OF ORDER-2
 // STREAMS"; extension, parity unpinned).  Every stream starts in context (prev0, prev0), as mh_encode starts an order-2 stream.
-//   batch2_check_kernel        offsets non-decreasing, [0] == 0, [n] == total (else MH_ERR_ARG through the status word)
 //   batch2_hist_fixup_kernel   the order-2 histogram of the concatenation counted each stream's first two symbols in contexts
 //                              that reach into the streams in front of it: one thread per stream moves them to its own
 //   batch2_enc_len_kernel      one wave per (stream, 1 KiB sub-step): the sub-step's payload bits
-//   batch_scan_* (shared)      exclusive scans (unit bits -> stream-relative bit offsets; payload bytes -> out_off)
+//   batch_check_kernel, batch_enc_sizes_kernel, batch_zero_kernel, batch_tail_kernel, batch_scan_*
+//                              (mh_batch_dev.hpp) the encoder's stages that do not look at the model: the offset check, unit
+//                              bits -> stream-relative bit offsets, payload bytes -> out_off, the zeroed output, its last dword
 //   batch2_enc_emit_kernel     one wave per (stream, 1 KiB sub-step): codes through the live contexts' LDS image
 //                              (o2hot_lookup16) when the model hands one over, escapes and every other model through the
 //                              packed (len << 56 | code) table in L2, codes over 56 bits through (len8, code64); the
 //                              sub-step's index entries
-//   batch2_dec_idx_kernel      one lane per (stream, chunk) with an index, the model's order-2 tables in L2 (decode2_kernel's)
-//   batch2_dec_walk_kernel     one lane per stream without an index: a count pass, then (after the scan) an emit pass
-// The work units, the scans, the bit writer and the byte output are the order-0/1 batch's (mh_batch_dev.hpp); the kernels
-// of mh_batch.hip and of the single-stream order-2 path are not changed.
+// The work units and their finder, the model-free stages, the bit writer and the byte output are the order-0/1 batch's
+// (mh_batch_dev.hpp); the decoder is mh_batch.hip's dec_*_kernel<Model::Shared2>.  The kernels of the single-stream order-2
+// path are not changed.
 #include "mh_batch_o2.h"
 #include "mh_batch_dev.hpp"
 #include "mh_decode_dev.hpp"
@@ -20,10 +20,6 @@
 #include "../../include/mh.h"
 
 namespace mhb {
-
-using mhk::BitCursor;
-using mhk::BitSrc;
-using mhk::DecTables;
 
 namespace {
 
@@ -52,13 +48,7 @@ __device__ __forceinline__ void o2hot_lookup16(const unsigned char *img, const u
 
 constexpr uint32_t HOT_ESCAPE = 0xD000u;          // image entries at or above: longer than 12 bits (ENC16_ESCAPE) — the L2 tables
 
-// ------------------------------------------------------------------------------------------------ checks, histogram fix-up
-
-__global__ void batch2_check_kernel(const uint64_t *off, uint64_t n, uint64_t total, int *status, int *stop) {
-    const uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (i > n) return;
-    if (offsets_bad(off, n, total, i)) { fail(status, BATCH_STATUS_ARG); atomicExch(stop, 1); }
-}
+// ------------------------------------------------------------------------------------------------ histogram fix-up
 
 // Position g of the concatenation was counted in context (byte g-2, byte g-1), prev0 standing in for the bytes in front of
 // position 0; stream [a, b) wants prev0 for every byte in front of a.  The two differ at a and a + 1 only (and only where the
@@ -86,31 +76,6 @@ __global__ void batch2_hist_fixup_kernel(const uint8_t *data, const uint64_t *of
 
 // ------------------------------------------------------------------------------------------------ encode
 
-// the unit's stream, the lane's bytes and the two bytes in front of them; false when the unit (wave-uniform) has nothing to code
-struct UnitLane2 {
-    uint64_t i, a, ni, ub, j0;
-    uint32_t cnt, ctx;
-    uint32_t x[4];
-};
-__device__ __forceinline__ bool unit_lane2(const EncBatchO2Params &p, uint64_t u, UnitLane2 &l) {
-    l.i = find_stream(p.in_off, p.n, SUB_SHIFT, u);
-    if (l.i >= p.n) return false;
-    l.a = p.in_off[l.i];
-    l.ni = p.in_off[l.i + 1] - l.a;
-    l.ub = (l.a >> SUB_SHIFT) + l.i;
-    const uint64_t s0 = (u - l.ub) << SUB_SHIFT;
-    if (s0 >= l.ni) return false;
-    l.j0 = s0 + uint64_t(mhk::lane_id()) * B_VEC;
-    l.cnt = l.j0 < l.ni ? uint32_t(l.ni - l.j0 < B_VEC ? l.ni - l.j0 : B_VEC) : 0u;
-    l.x[0] = l.x[1] = l.x[2] = l.x[3] = 0;
-    l.ctx = p.prev0;
-    if (l.cnt) {
-        load16(p.data + l.a + l.j0, l.cnt, l.x);
-        if (l.j0) l.ctx = (uint32_t(p.data[l.a + l.j0 - 2]) << 8) | p.data[l.a + l.j0 - 1];    // (j0 is 0 or >= 16)
-    }
-    return true;
-}
-
 template <bool HOT>
 __device__ __forceinline__ void load_image(const EncBatchO2Params &p, unsigned char *smem) {
     if (!HOT) return;
@@ -121,7 +86,7 @@ __device__ __forceinline__ void load_image(const EncBatchO2Params &p, unsigned c
 
 // the lane's sixteen image entries (HOT) — escapes and models without an image go to the L2 tables symbol by symbol
 template <bool HOT>
-__device__ __forceinline__ void image16(const unsigned char *smem, const UnitLane2 &l, uint32_t (&e)[16]) {
+__device__ __forceinline__ void image16(const unsigned char *smem, const Unit &l, uint32_t (&e)[16]) {
     if (HOT) {
         o2hot_lookup16(smem, make_uint4(l.x[0], l.x[1], l.x[2], l.x[3]), l.ctx, e);
     } else {
@@ -153,9 +118,9 @@ __global__ __launch_bounds__(B_THREADS) void batch2_enc_len_kernel(EncBatchO2Par
     load_image<HOT>(p, smem);
     const uint64_t nw = uint64_t(gridDim.x) * (B_THREADS / 64);
     for (uint64_t u = uint64_t(blockIdx.x) * (B_THREADS / 64) + threadIdx.x / 64; u < nunits; u += nw) {
-        UnitLane2 l;
+        Unit l;
         uint32_t bits = 0;
-        if (unit_lane2(p, u, l)) {
+        if (unit_of<2>(p.data, p.in_off, p.n, p.prev0, u, l)) {
             uint32_t e[16];
             image16<HOT>(smem, l, e);
             uint32_t ctx = l.ctx;
@@ -171,32 +136,6 @@ __global__ __launch_bounds__(B_THREADS) void batch2_enc_len_kernel(EncBatchO2Par
     }
 }
 
-// stream i: payload bits from the scanned unit bits, payload bytes into out_off (scanned next)
-__global__ void batch2_enc_sizes_kernel(EncBatchO2Params p, const unsigned long long *ubase, const int *stop) {
-    if (stopped(stop)) return;
-    const uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (i > p.n) return;
-    if (i == p.n) { p.out_off[i] = 0; return; }
-    const uint64_t u0 = (p.in_off[i] >> SUB_SHIFT) + i, u1 = (p.in_off[i + 1] >> SUB_SHIFT) + i + 1;
-    const unsigned long long bits = ubase[u1] - ubase[u0];
-    p.nbits[i] = bits;
-    p.out_off[i] = (bits + 7) >> 3;
-}
-
-// zeroes the payload bytes (codes are OR-ed into shared edge dwords) or reports that they do not fit
-__global__ void batch2_enc_zero_kernel(EncBatchO2Params p, int *status, int *stop, uint32_t *tail) {
-    if (stopped(stop)) return;
-    const uint64_t bytes = p.out_off[p.n];
-    if (bytes > p.cap) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) { fail(status, mhk::MHK_STATUS_CAPACITY); atomicExch(stop, 1); }
-        return;
-    }
-    const uint64_t nfull = bytes >> 2;
-    uint32_t *o = reinterpret_cast<uint32_t *>(p.out);
-    for (uint64_t k = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; k < nfull; k += uint64_t(gridDim.x) * blockDim.x) o[k] = 0u;
-    if (blockIdx.x == 0 && threadIdx.x == 0) *tail = 0u;
-}
-
 template <bool HOT>
 __global__ __launch_bounds__(B_THREADS) void batch2_enc_emit_kernel(EncBatchO2Params p, uint64_t nunits, const unsigned long long *ubase,
                                                                     uint32_t *tail, const int *stop) {
@@ -207,8 +146,8 @@ __global__ __launch_bounds__(B_THREADS) void batch2_enc_emit_kernel(EncBatchO2Pa
     const uint64_t tail_w = (bytes & 3u) ? bytes >> 2 : ~uint64_t(0);
     const uint64_t nw = uint64_t(gridDim.x) * (B_THREADS / 64);
     for (uint64_t u = uint64_t(blockIdx.x) * (B_THREADS / 64) + threadIdx.x / 64; u < nunits; u += nw) {
-        UnitLane2 l;
-        if (!unit_lane2(p, u, l)) continue;                        // wave-uniform
+        Unit l;
+        if (!unit_of<2>(p.data, p.in_off, p.n, p.prev0, u, l)) continue;   // wave-uniform
         uint32_t e[16];
         image16<HOT>(smem, l, e);
         uint32_t len[16], bits = 0, ctx = l.ctx;
@@ -234,101 +173,6 @@ __global__ __launch_bounds__(B_THREADS) void batch2_enc_emit_kernel(EncBatchO2Pa
 #pragma unroll
         for (uint32_t t = 0; t < B_VEC; ++t) bw.code(code[t], len[t]);
         bw.finish();
-    }
-}
-
-__global__ void batch2_enc_tail_kernel(EncBatchO2Params p, const uint32_t *tail, const int *stop) {
-    if (stopped(stop)) return;
-    const uint64_t bytes = p.out_off[p.n];
-    if (!(bytes & 3u)) return;
-    const uint8_t *t = reinterpret_cast<const uint8_t *>(tail);
-    for (uint64_t b = bytes & ~uint64_t(3); b < bytes; ++b) p.out[b] = t[b & 3u];
-}
-
-// ------------------------------------------------------------------------------------------------ decode
-
-constexpr int D2_THREADS = 256;                     // no tables in LDS: small workgroups, many waves per CU for the L2 gathers
-
-__global__ void batch2_dec_check_kernel(DecBatchParams p, int *status, int *stop) {
-    const uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (i > p.n) return;
-    check_batch(p, i, status, stop);
-}
-
-// the model's order-2 tables as decode2_kernel reads them: general form, every level gathered
-__device__ __forceinline__ DecTables tables2(const DecBatchParams &p) { return DecTables{p.sec, p.tree, p.P, 0u, 0u}; }
-
-__global__ __launch_bounds__(D2_THREADS) void batch2_dec_idx_kernel(DecBatchParams p, uint64_t nwork, int *status, const int *stop) {
-    if (stopped(stop)) return;
-    const DecTables tabs = tables2(p);
-    const uint32_t cs = p.chunk_shift;
-    for (uint64_t w = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; w < nwork; w += uint64_t(gridDim.x) * blockDim.x) {
-        const uint64_t i = find_stream(p.sym_off, p.n, cs, w);
-        if (i >= p.n) continue;
-        const uint64_t a = p.sym_off[i], ni = p.sym_off[i + 1] - a;
-        const uint64_t first = (w - ((a >> cs) + i)) << cs;
-        if (first >= ni || p.stream_status[i] == MH_ERR_ARG) continue;
-        const uint64_t nb = p.nbits[i];
-        const uint64_t e = p.index[w];
-        const uint64_t start = e & mhk::IDX2_POS;
-        const bool last = first + (uint64_t(1) << cs) >= ni;
-        const uint64_t end = last ? nb : (p.index[w + 1] & mhk::IDX2_POS);
-        const uint32_t nsym = uint32_t(last ? ni - first : (uint64_t(1) << cs));
-        if (start > end || end > nb) { stream_fail(p, status, i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT); continue; }
-        uint64_t bit0;
-        const BitSrc src = stream_src(p.payload, p.pay_off[i], nb, bit0);
-        BitCursor bc;
-        bc.init(src, bit0 + start);
-        uint32_t ctx = uint32_t(e >> 48), used = 0;
-        bool bad = false;
-        ByteOut bo;
-        bo.init(p.out, a + first);
-        for (uint32_t t = 0; t < nsym && !bad; ++t) {
-            const uint32_t sym = mhk::decode_one(p.prim, p.sec_base, tabs, src, bc, ctx, used, bad);
-            bo.put(sym);
-            ctx = ((ctx << 8) | sym) & 0xFFFFu;
-        }
-        bo.flush();
-        if (bad || used != end - start) stream_fail(p, status, i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT);
-    }
-}
-
-// EMIT = false: count the stream's symbols into sym_off[i] (scanned next); true: write them at out[sym_off[i] ...)
-template <bool EMIT>
-__global__ __launch_bounds__(D2_THREADS) void batch2_dec_walk_kernel(DecBatchParams p, int *status, const int *stop) {
-    if (stopped(stop)) return;
-    const DecTables tabs = tables2(p);
-    for (uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; i <= p.n; i += uint64_t(gridDim.x) * blockDim.x) {
-        if (i == p.n) { if (!EMIT) p.sym_off[i] = 0; continue; }
-        if (!EMIT) p.sym_off[i] = 0;
-        if (p.stream_status[i] != MH_OK) continue;
-        const uint64_t nb = p.nbits[i];
-        if (!EMIT && nb > p.walk_max_bits) { stream_fail(p, status, i, MH_ERR_ARG, BATCH_STATUS_ARG); continue; }
-        uint64_t count = 0;
-        if (EMIT) {
-            const uint64_t a = p.sym_off[i];
-            count = p.sym_off[i + 1] - a;
-            if (a + count > p.out_cap) { stream_fail(p, status, i, MH_ERR_CAPACITY, mhk::MHK_STATUS_CAPACITY); continue; }
-        }
-        uint64_t bit0;
-        const BitSrc src = stream_src(p.payload, p.pay_off[i], nb, bit0);
-        BitCursor bc;
-        bc.init(src, bit0);
-        uint32_t ctx = p.prev0, used = 0;
-        bool bad = false;
-        ByteOut bo;
-        bo.init(p.out, EMIT ? p.sym_off[i] : 0);
-        uint64_t k = 0;
-        // every code has at least one bit: at most nb steps (src/coding.cpp:124 — decode while bits remain)
-        while (used < nb && !bad && (!EMIT || k < count)) {
-            const uint32_t sym = mhk::decode_one(p.prim, p.sec_base, tabs, src, bc, ctx, used, bad);
-            if (EMIT && !bad) bo.put(sym);
-            ctx = ((ctx << 8) | sym) & 0xFFFFu;
-            ++k;
-        }
-        if (EMIT) bo.flush();
-        if (bad || used != nb || (EMIT && k != count)) { stream_fail(p, status, i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT); continue; }
-        if (!EMIT) p.sym_off[i] = k;                               // the stream ends exactly at nbits
     }
 }
 
@@ -359,39 +203,19 @@ hipError_t launch_encode_batch_o2(const EncBatchO2Params &p, void *d_ws, hipStre
     const uint64_t U = units_of(p.total, p.n);
     hipError_t e = hipMemsetAsync(ws, 0, 64, st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(batch2_check_kernel, dim3(uint32_t((p.n + 1 + 255) / 256)), dim3(256), 0, st, p.in_off, p.n, p.total, status, stop);
+    hipLaunchKernelGGL(batch_check_kernel, grid_threads(p.n + 1, 256), dim3(256), 0, st, p.in_off, p.n, p.total, status, stop);
     const int waves_per_block = B_THREADS / 64;
     const dim3 len_grid(grid_for(U, waves_per_block, 2)), emit_grid(grid_for(U, waves_per_block, 1));
     if (hot) hipLaunchKernelGGL(batch2_enc_len_kernel<true>, len_grid, dim3(B_THREADS), lds, st, p, U, ubits, stop);
     else hipLaunchKernelGGL(batch2_enc_len_kernel<false>, len_grid, dim3(B_THREADS), 0, st, p, U, ubits, stop);
     if ((e = scan_exclusive(ubits, U, sums, stop, st)) != hipSuccess) return e;
-    hipLaunchKernelGGL(batch2_enc_sizes_kernel, dim3(uint32_t((p.n + 1 + 255) / 256)), dim3(256), 0, st, p, ubits, stop);
+    hipLaunchKernelGGL(batch_enc_sizes_kernel, grid_threads(p.n + 1, 256), dim3(256), 0, st, p.in_off, p.n, ubits, p.nbits, p.out_off, stop);
     if ((e = scan_exclusive(p.out_off, p.n + 1, sums, stop, st)) != hipSuccess) return e;
     const uint64_t bound_words = (p.total * uint64_t(p.max_len > 0 ? p.max_len : 1) / 8 + p.n + 4) / 4;
-    hipLaunchKernelGGL(batch2_enc_zero_kernel, dim3(grid_for(bound_words, 256, 8)), dim3(256), 0, st, p, status, stop, tail);
+    hipLaunchKernelGGL(batch_zero_kernel, dim3(grid_for(bound_words, 256, 8)), dim3(256), 0, st, p.out_off + p.n, p.out, p.cap, status, stop, tail);
     if (hot) hipLaunchKernelGGL(batch2_enc_emit_kernel<true>, emit_grid, dim3(B_THREADS), lds, st, p, U, ubits, tail, stop);
     else hipLaunchKernelGGL(batch2_enc_emit_kernel<false>, emit_grid, dim3(B_THREADS), 0, st, p, U, ubits, tail, stop);
-    hipLaunchKernelGGL(batch2_enc_tail_kernel, dim3(1), dim3(1), 0, st, p, tail, stop);
-    return hipGetLastError();
-}
-
-hipError_t launch_decode_batch_o2(const DecBatchParams &p, void *d_ws, hipStream_t st) {
-    unsigned char *ws = static_cast<unsigned char *>(d_ws);
-    const DecLayout L = dec_layout(p.n);
-    int *status = reinterpret_cast<int *>(ws), *stop = status + 1;
-    auto *sums = reinterpret_cast<unsigned long long *>(ws + L.off_sums);
-    hipError_t e = hipMemsetAsync(ws, 0, 64, st);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(batch2_dec_check_kernel, dim3(uint32_t((p.n + 1 + 255) / 256)), dim3(256), 0, st, p, status, stop);
-    if (p.index) {
-        const uint64_t W = p.sym_total / (uint64_t(1) << p.chunk_shift) + p.n + 1;
-        hipLaunchKernelGGL(batch2_dec_idx_kernel, dim3(grid_for(W, D2_THREADS, 8)), dim3(D2_THREADS), 0, st, p, W, status, stop);
-        return hipGetLastError();
-    }
-    const dim3 grid(grid_for(p.n + 1, D2_THREADS, 8));
-    hipLaunchKernelGGL(batch2_dec_walk_kernel<false>, grid, dim3(D2_THREADS), 0, st, p, status, stop);
-    if ((e = scan_exclusive(p.sym_off, p.n + 1, sums, stop, st)) != hipSuccess) return e;
-    hipLaunchKernelGGL(batch2_dec_walk_kernel<true>, grid, dim3(D2_THREADS), 0, st, p, status, stop);
+    hipLaunchKernelGGL(batch_tail_kernel, dim3(1), dim3(1), 0, st, p.out_off + p.n, p.out, tail, stop);
     return hipGetLastError();
 }
 

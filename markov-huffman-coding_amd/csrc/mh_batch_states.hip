@@ -80,7 +80,7 @@ struct SetD {
     }
 };
 
-// decoder of the shared order-2 model: the general form, every level gathered from L2 (batch2_dec_idx_kernel's reads); the
+// decoder of the shared order-2 model: the general form, every level gathered from L2 (dec_idx_kernel<Shared2>'s reads); the
 // context holds the last two symbols
 struct Shared2D {
     static constexpr uint32_t SHIFT = 48;

@@ -8,7 +8,7 @@
 //                       stream reduce among themselves, then one 32-bit atomic XOR per (wave, stream) goes to d_crc[i]
 //   crc_finish_kernel   one lane per stream, every chunk judged by now: the initial value and the final XOR for a stream
 //                       that passed, 0 for one that failed
-//   crc_walk_kernel     index-free, one lane per stream under the walk cap of batch_dec_walk_kernel: the register carried
+//   crc_walk_kernel     index-free, one lane per stream under the walk cap of dec_walk_kernel: the register carried
 //                       through the whole walk, the symbols counted, finished in place
 //   crc_raw_check_kernel, crc_raw_kernel   the same digests of uncompressed messages, one lane per 1 KiB piece, the same
 //                       combine and crc_finish_kernel
@@ -242,7 +242,7 @@ hipError_t launch_crc(const CrcParams &p, Model model, void *d_ws, hipStream_t s
     // tables in L2: the byte table alone in LDS, at offset 0
     if (model == Model::Set) return launch<Model::Set, true>(p, 0, d_ws, st);
     if (model == Model::Shared2) return launch<Model::Shared2, true>(p, 0, d_ws, st);
-    // the tables as launch_decode_batch places them; the byte table behind them when 1 KiB is left of the 160 KiB
+    // the tables as launch_decode places them; the byte table behind them when 1 KiB is left of the 160 KiB
     const size_t lds = mhb::tables_lds(p.b);
     if (lds > 163840) return hipErrorInvalidValue;
     return lds + 1024 <= 163840 ? launch<Model::Shared, true>(p, lds, d_ws, st) : launch<Model::Shared, false>(p, lds, d_ws, st);

@@ -107,22 +107,16 @@ struct EncEachParams {
 };
 hipError_t launch_encode_each(const EncEachParams &p, void *d_ws, hipStream_t st);
 
-struct DecEachParams {
-    const uint8_t *payload;
-    const uint64_t *pay_off;
-    const uint64_t *nbits;
-    uint64_t n, pay_total;
-    uint32_t prev0;
-    uint8_t *out;
-    uint64_t out_cap;
-    unsigned long long *sym_off;
-    uint64_t sym_total;
-    const uint64_t *index;
-    uint32_t chunk_shift;
-    uint64_t walk_max_bits;
-    int *stream_status;
-    SetDev set;
-};
-hipError_t launch_decode_each(const DecEachParams &p, void *d_ws, hipStream_t st);
-
 }  // namespace mhe
+
+namespace mhb {
+
+// The parameters of mhb::launch_decode (mh_batch.h; kernels: mh_batch.hip).  The other call families over compressed batches
+// begin their parameters the same way (FindParams, CrcParams): it is what the symbol decoders (mhb::Dec<K>, mh_symdec_dev.hpp)
+// read.
+struct DecodeParams {
+    DecBatchParams b;               // the batch and, under a shared model, its decode tables
+    mhe::SetDev set;                // the models under a set
+};
+
+}  // namespace mhb

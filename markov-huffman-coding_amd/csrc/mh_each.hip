@@ -1,9 +1,9 @@
 // mh_each.hip — batches of independent order-0/1 streams, each under its own model (include/mh.h, "BATCHES OF STREAMS, ONE
 // MODEL EACH"): the reference's default per-file flow (train, write the table, encode) for N messages in a fixed number of
-// launches.  Layouts: mh_each.h; shared device code: mh_batch_dev.hpp (units, scans, bit writer), mh_each_dev.hpp (the
-// per-stream symbol decoder, shared with mh_range.hip); the trees are built by
-// mh_tree.hip's tree_build_kernel over the live (stream, context) pairs, so the reference's tie-breaking has one copy.
-//   each_check_kernel       offsets non-decreasing, [0] == 0, [n] == total
+// launches.  Layouts: mh_each.h; shared device code: mh_batch_dev.hpp (units and their finder, scans, the model-free encode
+// stages, bit writer); the trees are built by mh_tree.hip's tree_build_kernel over the live (stream, context) pairs, so the
+// reference's tie-breaking has one copy.
+//   batch_check_kernel      (mh_batch_dev.hpp) offsets non-decreasing, [0] == 0, [n] == total
 //   each_live_kernel        one wave per (stream, 1 KiB sub-step): the contexts the sub-step's symbols are coded in, OR-ed
 //                           into the stream's 256-bit mask (order 1: prev0 and every byte but the stream's last)
 //   each_nlive_kernel       one thread per stream: its live contexts (scanned next into slot bases)
@@ -13,76 +13,39 @@
 //   each_pack_kernel        one wave per slot: first level and walk tree from the tree's nodes
 //   each_tab_*              table files: bits per slot (scanned), bytes per stream (scanned), the pre-order traversal of
 //                           every tree by one lane (src/huffman.cpp:174-188, src/markov_huffman.cpp:80-88)
-//   each_enc_*              mh_batch.hip's encoder with the codes of stream i's slots (L2) instead of one LDS image
-//   each_dec_*              mh_batch.hip's two decoders with stream i's first level and walk tree (L2)
+//                           batch_zero_kernel and batch_tail_kernel (mh_batch_dev.hpp) around the writer, as in the encoder
+//   each_enc_*              mh_batch.hip's len and emit kernels with the codes of stream i's slots (L2) instead of one LDS
+//                           image, between the same model-free stages (mh_batch_dev.hpp)
+// The decoder is mh_batch.hip's dec_*_kernel<Model::Set> (mhb::launch_decode): stream i's first level and walk tree from L2.
 // Every loop is bounded by a symbol count, a leaf count, 64 code bits or nbits_i.  The number of launches does not depend on n,
 // except for one more tree_build_kernel launch per 4 M live contexts (TREE_SLICE).
 #include "mh_each.h"
 #include "mh_batch_dev.hpp"
-#include "mh_each_dev.hpp"
 #include "../../include/mh.h"
 
 namespace mhe {
 
-using mhb::B_SUB;
 using mhb::B_THREADS;
 using mhb::B_VEC;
-using mhb::BATCH_STATUS_ARG;
-using mhk::BitCursor;
-using mhk::BitSrc;
 constexpr uint16_t NONE = 0xFFFF;                // (mh_tree.hip: a node without children)
 
 namespace {
 
+using mhb::batch_check_kernel;
+using mhb::batch_enc_sizes_kernel;
+using mhb::batch_tail_kernel;
+using mhb::batch_zero_kernel;
 using mhb::byte_of;
-using mhb::check_batch;
-using mhb::fail;
-using mhb::find_stream;
 using mhb::grid_for;
 using mhb::grid_threads;
 using mhb::gtid;
-using mhb::load16;
 using mhb::scan_exclusive;
 using mhb::stopped;
-using mhb::stream_fail;
-using mhb::SUB_SHIFT;
+using mhb::Unit;
 
 constexpr uint32_t WAVES = B_THREADS / 64;
 constexpr uint64_t TREE_SLICE = 1u << 22;          // slots per tree_build_kernel launch: 2^22 x TB_NODE_STRIDE < 2^32
 static_assert((TREE_SLICE - 1) * mhk::TB_NODE_STRIDE + mhk::TB_NODE_STRIDE <= (1ull << 32), "tree_build_kernel's 32-bit node offsets");
-
-
-__global__ void each_check_kernel(const uint64_t *off, uint64_t n, uint64_t total, int *status, int *stop) {
-    const uint64_t i = gtid();
-    if (i > n) return;
-    const bool bad = (i == 0 && off[0] != 0) || (i == n && off[n] != total) || (i < n && off[i + 1] < off[i]);
-    if (bad) { fail(status, BATCH_STATUS_ARG); atomicExch(stop, 1); }
-}
-
-// the lane's bytes of unit u (closed-form numbering of mh_batch.h); false when the unit (wave-uniform) has nothing
-struct Unit {
-    uint64_t i, a, ni, ub, j0;
-    uint32_t cnt, prev;
-    uint32_t x[4];
-};
-__device__ __forceinline__ bool unit_of(const uint8_t *data, const uint64_t *in_off, uint64_t n, uint32_t prev0, uint64_t u, Unit &l) {
-    l.i = find_stream(in_off, n, SUB_SHIFT, u);
-    if (l.i >= n) return false;
-    l.a = in_off[l.i];
-    l.ni = in_off[l.i + 1] - l.a;
-    l.ub = (l.a >> SUB_SHIFT) + l.i;
-    const uint64_t s0 = (u - l.ub) << SUB_SHIFT;
-    if (s0 >= l.ni) return false;
-    l.j0 = s0 + uint64_t(mhk::lane_id()) * B_VEC;
-    l.cnt = l.j0 < l.ni ? uint32_t(l.ni - l.j0 < B_VEC ? l.ni - l.j0 : B_VEC) : 0u;
-    l.x[0] = l.x[1] = l.x[2] = l.x[3] = 0;
-    l.prev = prev0;
-    if (l.cnt) {
-        load16(data + l.a + l.j0, l.cnt, l.x);
-        if (l.j0) l.prev = data[l.a + l.j0 - 1];
-    }
-    return true;
-}
 
 // ------------------------------------------------------------------------------------------------ train
 
@@ -100,9 +63,9 @@ __global__ __launch_bounds__(B_THREADS) void each_live_kernel(const uint8_t *dat
     const uint64_t nw = uint64_t(gridDim.x) * WAVES;
     for (uint64_t u = uint64_t(blockIdx.x) * WAVES + threadIdx.x / 64; u < nunits; u += nw) {
         Unit l;
-        if (!unit_of(data, in_off, n, prev0, u, l)) continue;             // wave-uniform
+        if (!mhb::unit_of<1>(data, in_off, n, prev0, u, l)) continue;             // wave-uniform
         unsigned long long m[4] = {0, 0, 0, 0};
-        if (l.cnt) mark(m, l.prev);                                        // the context of the lane's first symbol
+        if (l.cnt) mark(m, l.ctx);                                        // the context of the lane's first symbol
 #pragma unroll
         for (uint32_t t = 0; t + 1 < B_VEC; ++t)                          // ... and of the following ones
             if (t + 1 < l.cnt) mark(m, byte_of(l.x, t));
@@ -165,9 +128,9 @@ __global__ __launch_bounds__(B_THREADS) void each_hist_kernel(const uint8_t *dat
     const uint64_t nw = uint64_t(gridDim.x) * WAVES;
     for (uint64_t u = uint64_t(blockIdx.x) * WAVES + threadIdx.x / 64; u < nunits; u += nw) {
         Unit l;
-        if (!unit_of(data, in_off, s.n, prev0, u, l)) continue;
+        if (!mhb::unit_of<1>(data, in_off, s.n, prev0, u, l)) continue;
         const uint32_t *row = s.ctx_slot + l.i * 256u;
-        uint32_t prev = l.prev;
+        uint32_t prev = l.ctx;
 #pragma unroll
         for (uint32_t t = 0; t < B_VEC; ++t) {
             const uint32_t sym = byte_of(l.x, t);
@@ -254,19 +217,6 @@ __global__ void each_tab_size_kernel(SetDev s, const unsigned long long *pbits, 
     tab_off[i] = (b + 7) >> 3;
 }
 
-// zeroes the output bytes [0, *off_end) (bits are OR-ed into shared edge words) or reports that they do not fit
-__global__ void each_zero_kernel(const unsigned long long *off_end, uint8_t *out, uint64_t cap, int *status, int *stop, uint32_t *tail) {
-    if (stopped(stop)) return;
-    const uint64_t bytes = *off_end;
-    if (bytes > cap) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) { fail(status, mhk::MHK_STATUS_CAPACITY); atomicExch(stop, 1); }
-        return;
-    }
-    uint32_t *o = reinterpret_cast<uint32_t *>(out);
-    for (uint64_t k = gtid(); k < (bytes >> 2); k += uint64_t(gridDim.x) * blockDim.x) o[k] = 0u;
-    if (blockIdx.x == 0 && threadIdx.x == 0) *tail = 0u;
-}
-
 // Threads 0 .. n-1: the leading 1 of an order-1 table.  Threads n .. n+nslots-1: one context each, its present bit (order 1)
 // and its tree in pre-order: 0 for an inner node, 1 + the symbol for a leaf, left before right.  The traversal keeps the
 // path from the root as bits (depth <= 64: a code's length) and walks down again from the root after each leaf to the
@@ -326,14 +276,6 @@ __global__ void each_tab_write_kernel(SetDev s, const unsigned long long *pbits,
     bw.finish();
 }
 
-__global__ void each_tail_kernel(const unsigned long long *off_end, uint8_t *out, const uint32_t *tail, const int *stop) {
-    if (stopped(stop)) return;
-    const uint64_t bytes = *off_end;
-    if (!(bytes & 3u)) return;
-    const uint8_t *t = reinterpret_cast<const uint8_t *>(tail);
-    for (uint64_t b = bytes & ~uint64_t(3); b < bytes; ++b) out[b] = t[b & 3u];
-}
-
 // ------------------------------------------------------------------------------------------------ encode
 
 // stream i's code of sym after prev: from the slot of its context (len 0: no code, the symbol is skipped as mh_encode does)
@@ -350,10 +292,10 @@ __global__ __launch_bounds__(B_THREADS) void each_enc_len_kernel(EncEachParams p
     for (uint64_t u = uint64_t(blockIdx.x) * WAVES + threadIdx.x / 64; u < nunits; u += nw) {
         Unit l;
         uint32_t bits = 0;
-        if (unit_of(p.data, p.in_off, p.n, p.prev0, u, l) && l.cnt) {
+        if (mhb::unit_of<1>(p.data, p.in_off, p.n, p.prev0, u, l) && l.cnt) {
             const uint32_t *row = p.set.ctx_slot + l.i * 256u;
             const bool o1 = p.set.type[l.i] != 0;
-            uint32_t prev = l.prev;
+            uint32_t prev = l.ctx;
 #pragma unroll
             for (uint32_t t = 0; t < B_VEC; ++t) {
                 const uint32_t sym = byte_of(l.x, t);
@@ -369,17 +311,6 @@ __global__ __launch_bounds__(B_THREADS) void each_enc_len_kernel(EncEachParams p
     }
 }
 
-__global__ void each_enc_sizes_kernel(EncEachParams p, const unsigned long long *ubase, const int *stop) {
-    if (stopped(stop)) return;
-    const uint64_t i = gtid();
-    if (i > p.n) return;
-    if (i == p.n) { p.out_off[i] = 0; return; }
-    const uint64_t u0 = (p.in_off[i] >> SUB_SHIFT) + i, u1 = (p.in_off[i + 1] >> SUB_SHIFT) + i + 1;
-    const unsigned long long bits = ubase[u1] - ubase[u0];
-    p.nbits[i] = bits;
-    p.out_off[i] = (bits + 7) >> 3;
-}
-
 __global__ __launch_bounds__(B_THREADS) void each_enc_emit_kernel(EncEachParams p, uint64_t nunits, const unsigned long long *ubase,
                                                                   uint32_t *tail, const int *stop) {
     if (stopped(stop)) return;
@@ -388,10 +319,10 @@ __global__ __launch_bounds__(B_THREADS) void each_enc_emit_kernel(EncEachParams 
     const uint64_t nw = uint64_t(gridDim.x) * WAVES;
     for (uint64_t u = uint64_t(blockIdx.x) * WAVES + threadIdx.x / 64; u < nunits; u += nw) {
         Unit l;
-        if (!unit_of(p.data, p.in_off, p.n, p.prev0, u, l)) continue;     // wave-uniform
+        if (!mhb::unit_of<1>(p.data, p.in_off, p.n, p.prev0, u, l)) continue;     // wave-uniform
         const uint32_t *row = p.set.ctx_slot + l.i * 256u;
         const bool o1 = p.set.type[l.i] != 0;
-        uint32_t bits = 0, prev = l.prev;
+        uint32_t bits = 0, prev = l.ctx;
         uint32_t lens[B_VEC];
         uint64_t codes[B_VEC];
 #pragma unroll
@@ -405,95 +336,13 @@ __global__ __launch_bounds__(B_THREADS) void each_enc_emit_kernel(EncEachParams 
         const uint32_t excl = mhk::wave_inclusive_sum(bits) - bits;
         const uint64_t sbit = (ubase[u] - ubase[l.ub]) + excl;      // stream-relative
         if (p.index && l.cnt && (l.j0 & ((uint64_t(1) << p.chunk_shift) - 1u)) == 0)
-            p.index[(l.a >> p.chunk_shift) + l.i + (l.j0 >> p.chunk_shift)] = (uint64_t(l.prev) << 56) | sbit;
+            p.index[(l.a >> p.chunk_shift) + l.i + (l.j0 >> p.chunk_shift)] = (uint64_t(l.ctx) << 56) | sbit;
         if (!bits) continue;
         mhb::BitWriter bw;
         bw.init(reinterpret_cast<uint32_t *>(p.out), tail, tail_w, uint64_t(p.out_off[l.i]) * 8u + sbit);
 #pragma unroll
         for (uint32_t t = 0; t < B_VEC; ++t) bw.code(codes[t], lens[t]);
         bw.finish();
-    }
-}
-
-// ------------------------------------------------------------------------------------------------ decode
-
-__global__ void each_dec_check_kernel(DecEachParams p, int *status, int *stop) {
-    const uint64_t i = gtid();
-    if (i > p.n) return;
-    check_batch(p, i, status, stop);
-}
-
-__global__ __launch_bounds__(256) void each_dec_idx_kernel(DecEachParams p, uint64_t nwork, int *status, const int *stop) {
-    if (stopped(stop)) return;
-    const uint32_t cs = p.chunk_shift;
-    for (uint64_t w = gtid(); w < nwork; w += uint64_t(gridDim.x) * blockDim.x) {
-        const uint64_t i = find_stream(p.sym_off, p.n, cs, w);
-        if (i >= p.n) continue;
-        const uint64_t a = p.sym_off[i], ni = p.sym_off[i + 1] - a;
-        const uint64_t first = (w - ((a >> cs) + i)) << cs;
-        if (first >= ni || p.stream_status[i] == MH_ERR_ARG) continue;
-        const uint64_t nb = p.nbits[i];
-        const uint64_t e = p.index[w];
-        const uint64_t start = e & MH_INDEX_BIT_MASK;
-        const bool last = first + (uint64_t(1) << cs) >= ni;
-        const uint64_t end = last ? nb : (p.index[w + 1] & MH_INDEX_BIT_MASK);
-        const uint32_t nsym = uint32_t(last ? ni - first : (uint64_t(1) << cs));
-        if (start > end || end > nb) { stream_fail(p, status, i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT); continue; }
-        uint64_t bit0;
-        const BitSrc src = mhb::stream_src(p.payload, p.pay_off[i], nb, bit0);
-        BitCursor bc;
-        bc.init(src, bit0 + start);
-        const uint32_t *row = p.set.ctx_slot + i * 256u;
-        const bool o1 = p.set.type[i] != 0;
-        uint32_t prev = uint32_t(e >> 56), used = 0;
-        bool bad = false;
-        mhb::ByteOut bo;
-        bo.init(p.out, a + first);
-        for (uint32_t t = 0; t < nsym && !bad; ++t) {
-            prev = decode_sym(p.set, row, o1 ? prev : 0u, src, bc, used, bad);
-            bo.put(prev);
-        }
-        bo.flush();
-        if (bad || used != end - start) stream_fail(p, status, i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT);
-    }
-}
-
-// EMIT = false: count the stream's symbols into sym_off[i] (scanned next); true: write them at out[sym_off[i] ...)
-template <bool EMIT>
-__global__ __launch_bounds__(256) void each_dec_walk_kernel(DecEachParams p, int *status, const int *stop) {
-    if (stopped(stop)) return;
-    for (uint64_t i = gtid(); i <= p.n; i += uint64_t(gridDim.x) * blockDim.x) {
-        if (i == p.n) { if (!EMIT) p.sym_off[i] = 0; continue; }
-        if (!EMIT) p.sym_off[i] = 0;
-        if (p.stream_status[i] != MH_OK) continue;
-        const uint64_t nb = p.nbits[i];
-        if (!EMIT && nb > p.walk_max_bits) { stream_fail(p, status, i, MH_ERR_ARG, BATCH_STATUS_ARG); continue; }
-        uint64_t count = 0;
-        if (EMIT) {
-            const uint64_t a = p.sym_off[i];
-            count = p.sym_off[i + 1] - a;
-            if (a + count > p.out_cap) { stream_fail(p, status, i, MH_ERR_CAPACITY, mhk::MHK_STATUS_CAPACITY); continue; }
-        }
-        uint64_t bit0;
-        const BitSrc src = mhb::stream_src(p.payload, p.pay_off[i], nb, bit0);
-        BitCursor bc;
-        bc.init(src, bit0);
-        const uint32_t *row = p.set.ctx_slot + i * 256u;
-        const bool o1 = p.set.type[i] != 0;
-        uint32_t prev = p.prev0, used = 0;
-        bool bad = false;
-        mhb::ByteOut bo;
-        bo.init(p.out, EMIT ? p.sym_off[i] : 0);
-        uint64_t k = 0;
-        // every code has at least one bit: at most nb steps (src/coding.cpp:124 — decode while bits remain)
-        while (used < nb && !bad && (!EMIT || k < count)) {
-            prev = decode_sym(p.set, row, o1 ? prev : 0u, src, bc, used, bad);
-            if (EMIT && !bad) bo.put(prev);
-            ++k;
-        }
-        if (EMIT) bo.flush();
-        if (bad || used != nb || (EMIT && k != count)) { stream_fail(p, status, i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT); continue; }
-        if (!EMIT) p.sym_off[i] = k;                               // src/coding.cpp:158: the stream ends exactly at nbits
     }
 }
 
@@ -511,7 +360,7 @@ hipError_t launch_train_count(const uint8_t *d_data, const uint64_t *d_in_off, u
     auto *sums = reinterpret_cast<unsigned long long *>(ws + L.off_sums);
     hipError_t e = hipMemsetAsync(ws, 0, L.off_counts, st);        // status block and masks
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(each_check_kernel, grid_threads(n + 1, 256), dim3(256), 0, st, d_in_off, n, total, status, stop);
+    hipLaunchKernelGGL(batch_check_kernel, grid_threads(n + 1, 256), dim3(256), 0, st, d_in_off, n, total, status, stop);
     if (order && total) {
         const uint64_t U = mhb::units_of(total, n);
         hipLaunchKernelGGL(each_live_kernel, dim3(grid_for(U, WAVES, 2)), dim3(B_THREADS), 0, st, d_data, d_in_off, n, U, prev0, masks, stop);
@@ -566,10 +415,10 @@ hipError_t launch_tables(const SetDev &s, uint8_t *d_out, uint64_t cap, unsigned
     hipLaunchKernelGGL(each_tab_size_kernel, grid_threads(s.n + 1, 256), dim3(256), 0, st, s, bits, d_tab_off, stop);
     if ((e = scan_exclusive(d_tab_off, s.n + 1, sums, stop, st)) != hipSuccess) return e;
     const uint64_t bound_words = (s.n * 33u + s.nslots * 320u + 4) / 4;
-    hipLaunchKernelGGL(each_zero_kernel, dim3(grid_for(bound_words, 256, 8)), dim3(256), 0, st, d_tab_off + s.n, d_out, cap, status, stop, tail);
+    hipLaunchKernelGGL(batch_zero_kernel, dim3(grid_for(bound_words, 256, 8)), dim3(256), 0, st, d_tab_off + s.n, d_out, cap, status, stop, tail);
     if (s.n + s.nslots)
         hipLaunchKernelGGL(each_tab_write_kernel, grid_threads(s.n + s.nslots, 256), dim3(256), 0, st, s, bits, d_tab_off, d_out, tail, stop);
-    hipLaunchKernelGGL(each_tail_kernel, dim3(1), dim3(1), 0, st, d_tab_off + s.n, d_out, tail, stop);
+    hipLaunchKernelGGL(batch_tail_kernel, dim3(1), dim3(1), 0, st, d_tab_off + s.n, d_out, tail, stop);
     return hipGetLastError();
 }
 
@@ -583,34 +432,15 @@ hipError_t launch_encode_each(const EncEachParams &p, void *d_ws, hipStream_t st
     const uint64_t U = mhb::units_of(p.total, p.n);
     hipError_t e = hipMemsetAsync(ws, 0, 64, st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(each_check_kernel, grid_threads(p.n + 1, 256), dim3(256), 0, st, p.in_off, p.n, p.total, status, stop);
+    hipLaunchKernelGGL(batch_check_kernel, grid_threads(p.n + 1, 256), dim3(256), 0, st, p.in_off, p.n, p.total, status, stop);
     hipLaunchKernelGGL(each_enc_len_kernel, dim3(grid_for(U, WAVES, 2)), dim3(B_THREADS), 0, st, p, U, ubits, stop);
     if ((e = scan_exclusive(ubits, U, sums, stop, st)) != hipSuccess) return e;
-    hipLaunchKernelGGL(each_enc_sizes_kernel, grid_threads(p.n + 1, 256), dim3(256), 0, st, p, ubits, stop);
+    hipLaunchKernelGGL(batch_enc_sizes_kernel, grid_threads(p.n + 1, 256), dim3(256), 0, st, p.in_off, p.n, ubits, p.nbits, p.out_off, stop);
     if ((e = scan_exclusive(p.out_off, p.n + 1, sums, stop, st)) != hipSuccess) return e;
     const uint64_t bound_words = (p.total * 8u + p.n + 4) / 4;
-    hipLaunchKernelGGL(each_zero_kernel, dim3(grid_for(bound_words, 256, 8)), dim3(256), 0, st, p.out_off + p.n, p.out, p.cap, status, stop, tail);
+    hipLaunchKernelGGL(batch_zero_kernel, dim3(grid_for(bound_words, 256, 8)), dim3(256), 0, st, p.out_off + p.n, p.out, p.cap, status, stop, tail);
     hipLaunchKernelGGL(each_enc_emit_kernel, dim3(grid_for(U, WAVES, 2)), dim3(B_THREADS), 0, st, p, U, ubits, tail, stop);
-    hipLaunchKernelGGL(each_tail_kernel, dim3(1), dim3(1), 0, st, p.out_off + p.n, p.out, tail, stop);
-    return hipGetLastError();
-}
-
-hipError_t launch_decode_each(const DecEachParams &p, void *d_ws, hipStream_t st) {
-    unsigned char *ws = static_cast<unsigned char *>(d_ws);
-    const mhb::DecLayout L = mhb::dec_layout(p.n);
-    int *status = reinterpret_cast<int *>(ws), *stop = status + 1;
-    auto *sums = reinterpret_cast<unsigned long long *>(ws + L.off_sums);
-    hipError_t e = hipMemsetAsync(ws, 0, 64, st);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(each_dec_check_kernel, grid_threads(p.n + 1, 256), dim3(256), 0, st, p, status, stop);
-    if (p.index) {
-        const uint64_t W = p.sym_total / (uint64_t(1) << p.chunk_shift) + p.n + 1;
-        hipLaunchKernelGGL(each_dec_idx_kernel, dim3(grid_for(W, 256, 8)), dim3(256), 0, st, p, W, status, stop);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL(each_dec_walk_kernel<false>, dim3(grid_for(p.n + 1, 256, 8)), dim3(256), 0, st, p, status, stop);
-    if ((e = scan_exclusive(p.sym_off, p.n + 1, sums, stop, st)) != hipSuccess) return e;
-    hipLaunchKernelGGL(each_dec_walk_kernel<true>, dim3(grid_for(p.n + 1, 256, 8)), dim3(256), 0, st, p, status, stop);
+    hipLaunchKernelGGL(batch_tail_kernel, dim3(1), dim3(1), 0, st, p.out_off + p.n, p.out, tail, stop);
     return hipGetLastError();
 }
 

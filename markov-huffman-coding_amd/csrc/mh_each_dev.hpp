@@ -1,7 +1,7 @@
 // mh_each_dev.hpp — device code shared by the kernels that decode under a model set (include/mh.h, "BATCHES OF STREAMS, ONE
-// MODEL EACH"): the per-stream decoders (mh_each.hip) and the lookups into batches (mh_range.hip).  The
-// tables stay in global memory (L2): a set's slots are far too many for LDS.  Unnamed namespace: each kernel file gets its
-// own copy.
+// MODEL EACH"): the batch kernel families through mhb::Dec<Model::Set> (mh_symdec_dev.hpp) and the lookups into batches
+// (mh_range.hip).  The tables stay in global memory (L2): a set's slots are far too many for LDS.  Unnamed namespace: each
+// kernel file gets its own copy.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -10,7 +10,7 @@
 //   find_off_kernel          hit_off from the scanned counts; hits beyond hit_cap -> MHK_STATUS_CAPACITY
 //   find_idx_emit_kernel     only lanes whose chunk has hits: decode again from the kept state of the chunk in front, so the
 //                            records come out in (end, pattern) order
-//   find_walk_kernel         index-free, one lane per stream: count (scan) emit, under the walk cap of batch_dec_walk_kernel
+//   find_walk_kernel         index-free, one lane per stream: count (scan) emit, under the walk cap of dec_walk_kernel
 //   find_cap_kernel          index-free: hits beyond hit_cap -> MHK_STATUS_CAPACITY
 // A chunk that is not its stream's last has chunk_symbols >= 256 > 63 symbols, so a state started at 0 is the true state at
 // its end, and a hit spans at most two chunks.  Verdicts are the batch decoders': same checks, same statuses.  Every loop is
@@ -286,7 +286,7 @@ hipError_t launch_find(const FindParams &p, const Automaton &a, Model model, voi
     // tables in L2: the masks alone in LDS, at offset 0
     if (model == Model::Set) return launch<Model::Set, true>(p, a, 0, d_ws, st);
     if (model == Model::Shared2) return launch<Model::Shared2, true>(p, a, 0, d_ws, st);
-    // the tables as launch_decode_batch places them; the masks behind them when 2 KiB are left of the 160 KiB
+    // the tables as launch_decode places them; the masks behind them when 2 KiB are left of the 160 KiB
     const size_t lds = mhb::tables_lds(p.b);
     if (lds > 163840) return hipErrorInvalidValue;
     return lds + 2048 <= 163840 ? launch<Model::Shared, true>(p, a, lds, d_ws, st) : launch<Model::Shared, false>(p, a, lds, d_ws, st);

@@ -14,7 +14,7 @@
 // Only the offsets of the streams a lookup names are read, so the cost does not depend on the batch's stream count.
 //   Tables   the symbol decoder of a lane, one policy per model (mhb::Model).  SharedTables: the order-0/1 tables in LDS as
 //            load_tables lays them out, one workgroup per CU.  SetTables: stream i's slots in L2 (mh_each.hip's decode_sym).
-//            Shared2Tables: the model's order-2 tables in L2 as batch2_dec_idx_kernel reads them (65 536 contexts: no LDS
+//            Shared2Tables: the model's order-2 tables in L2 as dec_idx_kernel<Shared2> reads them (65 536 contexts: no LDS
 //            copy; a lane is a chain of dependent gathers, so the unit size sets the latency).  Set and Shared2: workgroups of
 //            256 lanes, eight per CU.  A policy also names the format of an index entry (POS, entry_ctx) and the bound its
 //            kernels compile under.

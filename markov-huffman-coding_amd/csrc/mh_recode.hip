@@ -11,7 +11,7 @@
 //   recode_cap_kernel        index-free: more symbols than the destination index was sized for -> MHK_STATUS_CAPACITY
 //   recode_zero_kernel       clears the payload (edge words are OR-ed) or reports that it does not fit
 //   recode_idx_emit_kernel   decodes again and pushes dst's codes through BitWriter; the chunk's index entry
-//   recode_walk_kernel       index-free, one lane per stream: count (scans) emit, under the walk cap of batch_dec_walk_kernel
+//   recode_walk_kernel       index-free, one lane per stream: count (scans) emit, under the walk cap of dec_walk_kernel
 //   recode_tail_kernel       the bytes of the last, partial dword
 //   histc_idx_kernel         one lane per (stream, chunk): counts the pairs as it decodes; a chunk that fails takes its own
 //                            counts back; <FIX>: the chunks that passed inside a stream that failed take theirs back
@@ -20,7 +20,7 @@
 // Every loop is bounded by a symbol count or nbits_i.  One kernel family serves every order:
 //   Dec<K, W>    the source decoder, one policy per model (mhb::Model).  Shared: the order-0/1 tables in LDS as load_tables
 //                lays them out, one workgroup per CU.  Set: stream i's slots in L2.  Shared2: the model's order-2 tables
-//                read from L2 as batch2_dec_idx_kernel reads them, entries masked with IDX2_POS and their context taken
+//                read from L2 as dec_idx_kernel<Shared2> reads them, entries masked with IDX2_POS and their context taken
 //                from e >> 48.  Set and Shared2: workgroups of 256 lanes, eight per CU.
 //   W            some side is order 2: the lane rolls a 16-bit context ((ctx << 8) | sym) & 0xFFFF, of which an order-0/1
 //                model reads the last byte.  Else the context is the last symbol.

@@ -1,8 +1,8 @@
-// mh_symdec_dev.hpp — the symbol decoder of a lane, one policy per model kind, for the kernel families that take a decoded
-// symbol from a register instead of storing it: the search (mh_find.hip) and the digests (mh_crc.hip).  next() decodes one
-// symbol in the lane's context ctx and rolls ctx on: the kernels feed the symbol to their consumer and never touch the
-// context.  A stream starts in b.prev0 (order 2: both bytes).
-//   NT, PER_CU   the workgroup shape: that of the model's batch decoder
+// mh_symdec_dev.hpp — the symbol decoder of a lane, one policy per model kind, for the kernel families over compressed
+// batches: the decoders (mh_batch.hip), which store the symbol, and those that take it from a register instead: the search
+// (mh_find.hip) and the digests (mh_crc.hip).  next() decodes one symbol in the lane's context ctx and rolls ctx on: the
+// kernels feed the symbol to their consumer and never touch the context.  A stream starts in b.prev0 (order 2: both bytes).
+//   NT, PER_CU   the workgroup shape of every family under this model kind
 //   O2           the format of the batch's index entries (mhb::chunk_of)
 // P is the family's parameter struct: p.b (mhb::DecBatchParams: the batch and, under a shared model, its decode tables) and
 // p.set (mhe::SetDev: the models under a set).  Like mh_batch_dev.hpp, everything is in an unnamed namespace.
@@ -17,7 +17,7 @@ namespace {
 using mhk::BitCursor;
 
 template <Model K> struct Dec;
-// the shared model's two-level tables in LDS; one workgroup per CU beside them (batch_dec_idx_kernel's shape)
+// the shared model's two-level tables in LDS; one workgroup of 16 waves per CU beside them
 template <> struct Dec<Model::Shared> {
     static constexpr int NT = B_THREADS, PER_CU = 1;
     static constexpr bool O2 = false;
@@ -32,7 +32,7 @@ template <> struct Dec<Model::Shared> {
         return ctx = mhk::decode_one(lut, sub_base, tabs, src, bc, ctx, used, bad);
     }
 };
-// stream i's slots in L2 (each_dec_idx_kernel's shape)
+// stream i's slots in L2: no tables in LDS, so small workgroups and many waves per CU for the gathers
 template <> struct Dec<Model::Set> {
     static constexpr int NT = 256, PER_CU = 8;
     static constexpr bool O2 = false;
@@ -46,7 +46,7 @@ template <> struct Dec<Model::Set> {
     }
 };
 // the shared model's order-2 tables as decode2_kernel reads them: general form, every level gathered from L2
-// (batch2_dec_idx_kernel's shape); ctx holds the last two symbols
+// (the same shape as under a set); ctx holds the last two symbols
 template <> struct Dec<Model::Shared2> {
     static constexpr int NT = 256, PER_CU = 8;
     static constexpr bool O2 = true;

@@ -189,6 +189,51 @@ def pack_each(messages, order, prev0=PREV0, chunk=0):
     return merge(packs), tables
 
 
+TAIL_LENS = (0, 1, 15, 16, 1025)   # an empty stream, one lane, a lane boundary, one byte past a 1 KiB unit
+
+
+def tail_batches(packer, draw):
+    """Four batches of five streams of TAIL_LENS bytes whose packed payloads are 0, 1, 2 and 3 bytes long modulo 4 (the
+    encoders write whole dwords and finish the last, partial one apart): [(messages, Packed)].  packer(messages) is the
+    reference Packed, draw(n, seed) gives n bytes; the last stream is drawn again until the total has the wanted remainder."""
+    out = []
+    for r in range(4):
+        head = [draw(k, 100 + 10 * r + i) for i, k in enumerate(TAIL_LENS[:-1])]
+        for seed in range(200):
+            msgs = head + [draw(TAIL_LENS[-1], 1000 * (r + 1) + seed)]
+            ref = packer(msgs)
+            if int(ref.pay_off[-1]) % 4 == r:
+                break
+        assert int(ref.pay_off[-1]) % 4 == r and [len(m) for m in msgs] == list(TAIL_LENS)
+        out.append((msgs, ref))
+    return out
+
+
+def check_tail_and_capacity(mhc, encode, workspace, handle, msgs, ref, what):
+    """For the GPU tests of the three batch encoders (mhc: the binding, handed in; this module never imports it).
+    One device encode call of the batch family (encode / workspace: the mh_dev_encode_* pair, handle: its model or set) on
+    msgs, whose packed form is ref (batch_ref.Packed).  With cap exactly the payload size: MH_OK, the reference's bytes, offsets
+    and bit counts, and the 64 bytes behind cap untouched.  With cap one byte short: MH_ERR_CAPACITY and nothing written at
+    or beyond cap."""
+    lib = mhc.lib()
+    dev = lambda a: mhc.DeviceBuffer(max(a.nbytes, 16), np.ascontiguousarray(a) if a.nbytes else None)
+    data, in_off = mhc.batch_offsets(msgs)
+    n, total, pbytes = len(msgs), int(data.size), int(ref.pay_off[-1])
+    GUARD = 0xA5
+    d_data, d_in = dev(data), dev(in_off)
+    wsb = workspace(n, total)
+    for cap, want in ((pbytes, mhc.MH_OK), (pbytes - 1, mhc.MH_ERR_CAPACITY)):
+        d_out = dev(np.full(pbytes + 64, GUARD, dtype=np.uint8))
+        d_oo, d_nb, d_ws = mhc.DeviceBuffer((n + 1) * 8), mhc.DeviceBuffer(n * 8), mhc.DeviceBuffer(wsb)
+        assert encode(handle, d_data.ptr, d_in.ptr, n, total, 0x20, d_out.ptr, cap, d_oo.ptr, d_nb.ptr, None, 0, d_ws.ptr, wsb, None) == 0, what
+        assert lib.mh_dev_status(d_ws.ptr, None) == want, "%s: cap %d of %d" % (what, cap, pbytes)
+        out = d_out.download()
+        assert (out[cap:] == GUARD).all(), "%s: bytes written at or beyond cap %d of %d" % (what, cap, pbytes)
+        if want == mhc.MH_OK:
+            assert np.array_equal(out[:pbytes], ref.payload), what
+            assert np.array_equal(d_oo.download(np.uint64), ref.pay_off) and np.array_equal(d_nb.download(np.uint64)[:n], ref.nbits), what
+
+
 def select(tables, messages, prev0=PREV0):
     """Bank selection: tables = [(order, lens)] per entry.  (choice uint32[n], nbits uint64[n]): the entry that has a code for
     every pair of the stream and gives the fewest bits, ties to the lowest entry; an empty stream: entry 0; none: BANK_NONE

@@ -39,6 +39,20 @@ def test_batch_sizes_are_plain_arithmetic(mhc):
     assert lib.mh_batch_index_base(5000, 7, 1024) == 5000 // 1024 + 7
 
 
+def test_workspace_sizes_are_pinned(mhc):
+    """The encode and decode workspaces of the three batch families (one shared order-0/1 model, one shared order-2 model, a
+    model per stream) share two layouts; their sizes are pinned to what the library returned before the decoders became one
+    kernel family: (n_streams, total) -> (encode, decode)."""
+    lib = mhc.lib()
+    pinned = {(0, 0): (256, 256), (1, 1): (256, 256), (7, 1000): (256, 256), (1000, 1 << 20): (16384, 12288),
+              (65536, 4096 * 65536): (2624256, 787200), (1024, (1 << 20) - 1): (16640, 12544), (1023, 1 << 20): (16640, 12544)}
+    for (n, total), (enc, dec) in pinned.items():
+        for f in (lib.mh_dev_encode_batch_workspace, lib.mh_dev_encode_batch_o2_workspace, lib.mh_dev_encode_each_workspace):
+            assert f(n, total) == enc, (f.__name__, n, total)
+        for f in (lib.mh_dev_decode_batch_workspace, lib.mh_dev_decode_batch_o2_workspace, lib.mh_dev_decode_each_workspace):
+            assert f(n) == dec, (f.__name__, n)
+
+
 def _slices(off, chunk):
     """Python mirror of the closed-form layout: stream i's entries [in_off_i // chunk + i, ... + ceil(n_i / chunk))."""
     out = []

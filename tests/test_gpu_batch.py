@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import __graft_entry__ as entry
+import batch_ref
 from conftest import ROOT, golden
 
 pytestmark = pytest.mark.gpu
@@ -157,8 +158,23 @@ def _dev(mhc, a):
     return mhc.DeviceBuffer(max(a.nbytes, 16), a if a.nbytes else None)
 
 
-def test_capacity_one_byte_short_leaves_guard_bytes(mhc):
+@pytest.mark.parametrize("kind", ["shared", "set"])
+def test_capacity_one_byte_short_leaves_guard_bytes(mhc, kind):
+    """Both order-0/1 encoders (one shared model; a model per stream) on batch_ref.tail_batches: the payload ends 0, 1, 2 and 3
+    bytes into a dword, cap is exact and then one byte short.  Under the shared model also, as before: a batch with an empty
+    stream one byte short on the encoder, and on the index-free decoder."""
     lib = mhc.lib()
+    if kind == "set":
+        for msgs, ref in batch_ref.tail_batches(lambda m: batch_ref.pack_each(m, 1)[0], zipf):
+            models = mhc.ModelSet.from_tables(batch_ref.pack_each(msgs, 1)[1])
+            batch_ref.check_tail_and_capacity(mhc, lib.mh_dev_encode_each, lib.mh_dev_encode_each_workspace, models.handle, msgs, ref,
+                                    "mh_dev_encode_each, payload %d bytes" % int(ref.pay_off[-1]))
+        return
+    counts = batch_ref.histogram([zipf(1 << 16, 5)], 1) + np.uint64(1)      # every pair has a code
+    codes, shared = batch_ref.oracle_codes(counts, 1), mhc.Model.from_counts(counts, 1)
+    for msgs, ref in batch_ref.tail_batches(lambda m: batch_ref.pack(m, *codes, 1), zipf):
+        batch_ref.check_tail_and_capacity(mhc, lib.mh_dev_encode_batch, lib.mh_dev_encode_batch_workspace, shared.handle, msgs, ref,
+                                "mh_dev_encode_batch, payload %d bytes" % int(ref.pay_off[-1]))
     msgs = [zipf(k, 50 + k) for k in (1000, 0, 2500, 77)]
     model = mhc.Model.from_counts(mhc.histogram_o1_batch(msgs), 1)
     data, in_off = mhc.batch_offsets(msgs)

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import __graft_entry__ as entry
+import batch_ref
 import bench
 from conftest import golden
 
@@ -298,6 +299,13 @@ def test_encode_capacity_small_writes_nothing_past_cap(mhc, text_model):
                                       None, 0, d_ws.ptr, wsb, None) == 0
     assert lib.mh_dev_status(d_ws.ptr, None) == mhc.MH_ERR_CAPACITY
     assert (d_out.download()[cap:] == GUARD).all()
+    # batch_ref.tail_batches: the payload ends 0, 1, 2 and 3 bytes into a dword; cap exact, then one byte short
+    counts = batch_ref.histogram([text(1 << 16, 23)], 2)
+    codes, model = batch_ref.oracle_codes(counts, 2), mhc.Model.from_counts(counts, 2)
+    for msgs, ref in batch_ref.tail_batches(lambda m: batch_ref.pack(m, *codes, 2), text):
+        assert int(ref.nbits[-1]) > 1024                           # (the model has codes for the text's triples)
+        batch_ref.check_tail_and_capacity(mhc, lib.mh_dev_encode_batch_o2, lib.mh_dev_encode_batch_o2_workspace, model.handle, msgs, ref,
+                                "mh_dev_encode_batch_o2, payload %d bytes" % int(ref.pay_off[-1]))
 
 
 def test_stream_over_walk_cap(mhc):
