@@ -1181,6 +1181,81 @@ int mh_dev_crc_raw_batch(const uint8_t *d_data, const uint64_t *d_in_off, size_t
 uint32_t mh_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
 
 /* ---------------------------------------------------------------------------------------------------------------------
+ * DICTIONARY SEARCH IN BATCHES (extension, parity unpinned) — SEARCH IN BATCHES with thousands of patterns in one pass: the
+ * matcher is an Aho-Corasick automaton turned into a full DFA instead of Shift-And over one word, so a call is not limited
+ * to MH_FIND_MAX_POSITIONS pattern bytes.  Everything not said here is word for word SEARCH IN BATCHES (and, for the _o2
+ * calls, the search part of ORDER 2 IN SEARCH AND RE-CODING): the batch description, alignment, the up-front checks,
+ * d_hit_off, the records and their order (ascending (stream, end, pattern number)), hit_cap, count-only mode,
+ * d_stream_status with the batch decoders' verdicts, index-free mode under MH_BATCH_WALK_MAX_BITS, no allocation, no host
+ * synchronisation, a launch count that does not depend on the data, and the order each call refuses: mh_dev_find_dict_batch
+ * and mh_find_dict_batch an order-2 model, the _o2 calls an order-0/1 model (MH_ERR_ARG before any launch);
+ * mh_dev_find_dict_each takes a set or a bank view.
+ *   - A dictionary is built on the host (mh_dict_create needs no device): pattern j = bytes[pat_off[j] .. pat_off[j+1]), any
+ *     byte values; bytes, pat_off, n_patterns and flags as for mh_pattern_set_create, MH_FIND_FOLD_ASCII the only flag
+ *     (patterns are lowered at build time, 'A'..'Z' in the data take the class of their lower-case twin).  Equal patterns
+ *     may appear twice; each reports its own hits.  MH_ERR_ARG for n_patterns == 0, an empty pattern, pat_off[0] != 0,
+ *     decreasing offsets, unknown flag bits, null pointers, a pattern over MH_DICT_MAX_LEN bytes, more than
+ *     MH_DICT_MAX_PATTERNS patterns, an automaton of more than MH_DICT_MAX_STATES states (trie nodes, root included) and
+ *     more than MH_DICT_MAX_OUTPUTS flattened outputs (the sum over the states of the patterns that end there, a state's
+ *     suffix patterns included).
+ *   - The automaton: states numbered breadth-first (root 0); bytes mapped to classes (class 0: the bytes of no pattern);
+ *     a transition is 16 bits, the target state and bit 15 when the target has outputs; per state the depth and a list of
+ *     (pattern, length) sorted by pattern number.  mh_dict_states / _classes / _size / _max_len say what was built;
+ *     mh_dict_device_bytes the size of its device image (0 for NULL).
+ *   - When a usable device exists mh_dict_create also uploads the image to the current device, as building a model does:
+ *     allocating and synchronous, the only place that is.  Without a device the object is valid for the queries and for
+ *     mh_dict_find_bytes, and the device calls return MH_ERR_NO_DEVICE.  A dictionary is immutable, may be shared by
+ *     threads, and must outlive the work enqueued with it.
+ *   - mh_dict_find_bytes is the host matcher, no device: the hits of one uncompressed message in (end, pattern) order;
+ *     *n_hits is the total, hits[2r], hits[2r+1] = begin, end and hit_pattern[r] are written for r < hit_cap (either may be
+ *     NULL); MH_ERR_CAPACITY when an output is asked for and the hits do not fit, MH_ERR_ARG for null d or n_hits.
+ *   - A hit's length is its pattern's; a pattern is at most MH_DICT_MAX_LEN = 255 bytes < MH_CHUNK_MIN, so a hit spans at
+ *     most two chunks, which is all the indexed search relies on.
+ *   - The workspace is mh_dev_find_batch_workspace's for the same arguments.
+ * Host forms mh_find_dict_batch / mh_find_dict_batch_o2: as mh_find_batch / mh_find_batch_o2; a valid batch is never
+ * refused (index-free streams over the walk cap: order 0/1 indexed by mh_index_batch first, order 2 decoded alone and
+ * searched by mh_dict_find_bytes, the records spliced in stream order).
+ * --------------------------------------------------------------------------------------------------------------------- */
+typedef struct mh_dict mh_dict;
+#define MH_DICT_MAX_LEN      255u         /* one pattern; < MH_CHUNK_MIN, which the seam argument needs */
+#define MH_DICT_MAX_STATES   32768u       /* automaton states, root included */
+#define MH_DICT_MAX_PATTERNS 65536u
+#define MH_DICT_MAX_OUTPUTS  (1u << 20)   /* flattened output lists */
+int mh_dict_create(const uint8_t *bytes, const uint32_t *pat_off, size_t n_patterns, uint32_t flags, mh_dict **out);
+void mh_dict_free(mh_dict *d);
+size_t mh_dict_size(const mh_dict *d);
+int mh_dict_max_len(const mh_dict *d);
+size_t mh_dict_states(const mh_dict *d);
+int mh_dict_classes(const mh_dict *d);
+size_t mh_dict_device_bytes(const mh_dict *d);
+int mh_dict_find_bytes(const mh_dict *d, const uint8_t *data, size_t n, uint64_t *hits, uint32_t *hit_pattern, uint64_t hit_cap,
+                       uint64_t *n_hits);
+size_t mh_dev_find_dict_workspace(size_t n_streams, uint64_t sym_total, uint32_t chunk_symbols);
+int mh_dev_find_dict_batch(const mh_model *m, const mh_dict *d, const uint8_t *d_payload, const uint64_t *d_pay_off,
+                           const uint64_t *d_nbits, size_t n_streams, uint64_t pay_total, uint8_t prev0,
+                           const uint64_t *d_sym_off, uint64_t sym_total, const uint64_t *d_index, uint32_t chunk_symbols,
+                           uint64_t *d_hit_off, uint64_t *d_hits, uint32_t *d_hit_pattern, uint64_t hit_cap,
+                           int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream);
+int mh_dev_find_dict_each(const mh_model_set *s, const mh_dict *d, const uint8_t *d_payload, const uint64_t *d_pay_off,
+                          const uint64_t *d_nbits, size_t n_streams, uint64_t pay_total, uint8_t prev0,
+                          const uint64_t *d_sym_off, uint64_t sym_total, const uint64_t *d_index, uint32_t chunk_symbols,
+                          uint64_t *d_hit_off, uint64_t *d_hits, uint32_t *d_hit_pattern, uint64_t hit_cap,
+                          int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream);
+int mh_dev_find_dict_batch_o2(const mh_model *m, const mh_dict *d, const uint8_t *d_payload, const uint64_t *d_pay_off,
+                              const uint64_t *d_nbits, size_t n_streams, uint64_t pay_total, uint8_t prev0,
+                              const uint64_t *d_sym_off, uint64_t sym_total, const uint64_t *d_index, uint32_t chunk_symbols,
+                              uint64_t *d_hit_off, uint64_t *d_hits, uint32_t *d_hit_pattern, uint64_t hit_cap,
+                              int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream);
+int mh_find_dict_batch(const mh_model *m, const mh_dict *d, const uint8_t *payload, const uint64_t *pay_off,
+                       const uint64_t *nbits, size_t n_streams, uint8_t prev0, const uint64_t *sym_off, const uint64_t *index,
+                       uint32_t chunk_symbols, uint64_t *hit_off, uint64_t *hits, uint32_t *hit_pattern, uint64_t hit_cap,
+                       int32_t *stream_status);
+int mh_find_dict_batch_o2(const mh_model *m, const mh_dict *d, const uint8_t *payload, const uint64_t *pay_off,
+                          const uint64_t *nbits, size_t n_streams, uint8_t prev0, const uint64_t *sym_off, const uint64_t *index,
+                          uint32_t chunk_symbols, uint64_t *hit_off, uint64_t *hits, uint32_t *hit_pattern, uint64_t hit_cap,
+                          int32_t *stream_status);
+
+/* ---------------------------------------------------------------------------------------------------------------------
  * SEGMENT STATES OF INDEX-FREE ORDER-2 BATCHES (extension, parity unpinned) — the _o2 twins of the segment-state calls of
  * the next section, for a batch coded under one shared order-2 model (what mh_dev_encode_batch_o2 writes, stored without
  * its sidecar index).  Same arguments, layouts, workspace arithmetic, launch sequence and guarantees as the twins; what

@@ -69,9 +69,16 @@ EXPORTS = [
     "mh_dev_batch_states_stats",
     "mh_dev_crc_batch_workspace", "mh_dev_crc_batch", "mh_dev_crc_each", "mh_dev_crc_batch_o2", "mh_crc_batch", "mh_crc_batch_o2",
     "mh_dev_crc_raw_batch_workspace", "mh_dev_crc_raw_batch", "mh_crc32_combine",
+    "mh_dict_create", "mh_dict_free", "mh_dict_size", "mh_dict_max_len", "mh_dict_states", "mh_dict_classes", "mh_dict_device_bytes",
+    "mh_dict_find_bytes", "mh_dev_find_dict_workspace", "mh_dev_find_dict_batch", "mh_dev_find_dict_each", "mh_dev_find_dict_batch_o2",
+    "mh_find_dict_batch", "mh_find_dict_batch_o2",
 ]
 FIND_MAX_POSITIONS = 64                    # include/mh.h MH_FIND_MAX_POSITIONS
 FIND_FOLD_ASCII = 1                        # include/mh.h MH_FIND_FOLD_ASCII
+DICT_MAX_LEN = 255                         # include/mh.h MH_DICT_MAX_LEN
+DICT_MAX_STATES = 32768                    # include/mh.h MH_DICT_MAX_STATES
+DICT_MAX_PATTERNS = 65536                  # include/mh.h MH_DICT_MAX_PATTERNS
+DICT_MAX_OUTPUTS = 1 << 20                 # include/mh.h MH_DICT_MAX_OUTPUTS
 BANK_MAX = 64                              # include/mh.h MH_BANK_MAX
 BANK_NONE = 0xFFFFFFFF                     # include/mh.h MH_BANK_NONE
 BATCH_WALK_MAX_BITS = 1 << 23              # include/mh.h MH_BATCH_WALK_MAX_BITS
@@ -299,6 +306,21 @@ def lib():
             fn.restype = sz
         l.mh_dev_find_batch_o2.argtypes = l.mh_dev_find_batch.argtypes
         l.mh_find_batch_o2.argtypes = l.mh_find_batch.argtypes
+        l.mh_dict_create.argtypes = [vp, vp, sz, u32, C.POINTER(vp)]
+        l.mh_dict_free.argtypes = [vp]
+        l.mh_dict_free.restype = None
+        for fn in (l.mh_dict_size, l.mh_dict_states, l.mh_dict_device_bytes):
+            fn.argtypes = [vp]
+            fn.restype = sz
+        l.mh_dict_max_len.argtypes = [vp]
+        l.mh_dict_classes.argtypes = [vp]
+        l.mh_dict_find_bytes.argtypes = [vp, vp, sz, vp, vp, u64, pu64]
+        l.mh_dev_find_dict_workspace.argtypes = [sz, u64, u32]
+        l.mh_dev_find_dict_workspace.restype = sz
+        for fn in (l.mh_dev_find_dict_batch, l.mh_dev_find_dict_each, l.mh_dev_find_dict_batch_o2):
+            fn.argtypes = l.mh_dev_find_batch.argtypes
+        l.mh_find_dict_batch.argtypes = l.mh_find_batch.argtypes
+        l.mh_find_dict_batch_o2.argtypes = l.mh_find_batch.argtypes
         l.mh_dev_histogram_coded_batch_o2.argtypes = l.mh_dev_histogram_coded_batch.argtypes
         l.mh_dev_recode_batch_o2.argtypes = l.mh_dev_recode_batch.argtypes
         l.mh_recode_batch_o2.argtypes = l.mh_recode_batch.argtypes
@@ -619,6 +641,68 @@ class PatternSet:
     @property
     def max_len(self):
         return lib().mh_pattern_set_max_len(self._h)
+
+
+class Dict:
+    """Owns an mh_dict*: a dictionary of up to DICT_MAX_PATTERNS patterns of at most DICT_MAX_LEN bytes each, as an Aho-Corasick
+    DFA (include/mh.h, "DICTIONARY SEARCH IN BATCHES").  Built on the host; with a device its image is uploaded as well.  The
+    find_dict calls take it where the find calls take a PatternSet."""
+
+    def __init__(self, patterns, fold=False, flags=None):
+        pats = [bytes(p) for p in patterns]
+        buf = np.frombuffer(b"".join(pats) or b"\0", dtype=np.uint8)
+        off = np.zeros(len(pats) + 1, dtype=np.uint32)
+        if pats:
+            off[1:] = np.cumsum([len(p) for p in pats])
+        h = C.c_void_p()
+        _check(lib().mh_dict_create(buf.ctypes.data, off.ctypes.data, len(pats),
+                                    (FIND_FOLD_ASCII if fold else 0) if flags is None else flags, C.byref(h)), "mh_dict_create")
+        self._h = h
+        self.patterns = pats
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.mh_dict_free(self._h)
+            self._h = None
+
+    @property
+    def handle(self):
+        return self._h
+
+    def __len__(self):
+        return lib().mh_dict_size(self._h)
+
+    @property
+    def max_len(self):
+        return lib().mh_dict_max_len(self._h)
+
+    @property
+    def states(self):
+        return lib().mh_dict_states(self._h)
+
+    @property
+    def classes(self):
+        return lib().mh_dict_classes(self._h)
+
+    @property
+    def device_bytes(self):
+        return lib().mh_dict_device_bytes(self._h)
+
+    def find_bytes(self, data, hit_cap=None):
+        """mh_dict_find_bytes (host matcher, no device): (hits[k, 2] = (begin, end), hit_pattern[k], total, return code) of one
+        message in (end, pattern) order.  hit_cap None: a counting call first, then one with room for every hit."""
+        l = lib()
+        data = _u8(data)
+        total = C.c_uint64(0)
+        if hit_cap is None:
+            _check(l.mh_dict_find_bytes(self._h, _ptr(data), data.size, None, None, 0, C.byref(total)), "mh_dict_find_bytes")
+            hit_cap = total.value
+        hits, pat = np.zeros(max(hit_cap, 1) * 2, dtype=np.uint64), np.zeros(max(hit_cap, 1), dtype=np.uint32)
+        rc = l.mh_dict_find_bytes(self._h, _ptr(data), data.size, hits.ctypes.data, pat.ctypes.data, hit_cap, C.byref(total))
+        if rc not in (MH_OK, MH_ERR_CAPACITY):
+            raise MhError(rc, "mh_dict_find_bytes")
+        k = min(total.value, hit_cap)
+        return hits[:2 * k].reshape(-1, 2), pat[:k], total.value, rc
 
 
 def _dev_find(fn, handle, ps, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols, hit_cap, count_only, ws_fn=None):
@@ -1138,6 +1222,17 @@ class Model:
         (hit_off[n + 1], hits[k, 3], hit_pattern[k], per-stream status[n], mh_dev_status)."""
         return _dev_find(lib().mh_dev_find_batch, self._h, ps, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols, hit_cap, count_only)
 
+    def find_dict_batch(self, d, payload, pay_off, nbits, prev0=PREV0, sym_off=None, index=None, chunk_symbols=0, hit_cap=None, check=True):
+        """mh_find_dict_batch (host form): find_batch's arguments and results with a Dict for the pattern set."""
+        return self._find_batch(lib().mh_find_dict_batch, "mh_find_dict_batch", d, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols,
+                                hit_cap, check)
+
+    def dev_find_dict_batch(self, d, payload, pay_off, nbits, prev0=PREV0, sym_off=None, index=None, chunk_symbols=0, hit_cap=None,
+                            count_only=False):
+        """One mh_dev_find_dict_batch call (two when hit_cap is None) with guard words behind its outputs: dev_find_batch's results."""
+        return _dev_find(lib().mh_dev_find_dict_batch, self._h, d, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols, hit_cap,
+                         count_only, ws_fn=lib().mh_dev_find_dict_workspace)
+
     def crc_batch(self, payload, pay_off, nbits, prev0=PREV0, sym_off=None, index=None, chunk_symbols=0, check=True):
         """mh_crc_batch (host form): (crc[n], len[n], per-stream status[n], return code)."""
         return _host_crc(lib().mh_crc_batch, "mh_crc_batch", self._h, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols, check)
@@ -1365,6 +1460,17 @@ class Model:
         """mh_find_batch_o2 (host form; this model is order 2): find_batch's arguments and results."""
         return self._find_batch(lib().mh_find_batch_o2, "mh_find_batch_o2", ps, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols,
                                 hit_cap, check)
+
+    def find_dict_batch_o2(self, d, payload, pay_off, nbits, prev0=PREV0, sym_off=None, index=None, chunk_symbols=0, hit_cap=None, check=True):
+        """mh_find_dict_batch_o2 (host form; this model is order 2): find_batch's arguments and results with a Dict."""
+        return self._find_batch(lib().mh_find_dict_batch_o2, "mh_find_dict_batch_o2", d, payload, pay_off, nbits, prev0, sym_off, index,
+                                chunk_symbols, hit_cap, check)
+
+    def dev_find_dict_batch_o2(self, d, payload, pay_off, nbits, prev0=PREV0, sym_off=None, index=None, chunk_symbols=0, hit_cap=None,
+                               count_only=False):
+        """One mh_dev_find_dict_batch_o2 call (two when hit_cap is None) with guard words behind its outputs: dev_find_batch's results."""
+        return _dev_find(lib().mh_dev_find_dict_batch_o2, self._h, d, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols, hit_cap,
+                         count_only, ws_fn=lib().mh_dev_find_dict_workspace)
 
     def dev_find_batch_o2(self, ps, payload, pay_off, nbits, prev0=PREV0, sym_off=None, index=None, chunk_symbols=0, hit_cap=None,
                           count_only=False):
@@ -1605,6 +1711,12 @@ class ModelSet:
         """One mh_dev_find_each call (two when hit_cap is None) with guard words behind its outputs, stream i under model i:
         (hit_off[n + 1], hits[k, 3], hit_pattern[k], per-stream status[n], mh_dev_status)."""
         return _dev_find(lib().mh_dev_find_each, self._h, ps, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols, hit_cap, count_only)
+
+    def find_dict(self, d, payload, pay_off, nbits, prev0=PREV0, sym_off=None, index=None, chunk_symbols=0, hit_cap=None, count_only=False):
+        """One mh_dev_find_dict_each call (two when hit_cap is None) with guard words behind its outputs, stream i under model i:
+        find's results with a Dict for the pattern set."""
+        return _dev_find(lib().mh_dev_find_dict_each, self._h, d, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols, hit_cap,
+                         count_only, ws_fn=lib().mh_dev_find_dict_workspace)
 
     def crc(self, payload, pay_off, nbits, prev0=PREV0, sym_off=None, index=None, chunk_symbols=0, **kw):
         """One mh_dev_crc_each call with guard words behind its outputs, stream i under model i: (crc[n], len[n], per-stream

@@ -1,6 +1,7 @@
-// mh_api_find.cpp — the search calls of the C ABI (include/mh.h, "SEARCH IN BATCHES" and the search part of "ORDER 2 IN
-// SEARCH AND RE-CODING"): the pattern set (a host object: the Shift-And automaton of mh_find.h), the device calls under one
-// shared model of order 0/1 or 2 or under a model set (kernels: mh_find.hip) and the host-buffer forms.
+// mh_api_find.cpp — the search calls of the C ABI (include/mh.h, "SEARCH IN BATCHES", the search part of "ORDER 2 IN
+// SEARCH AND RE-CODING" and "DICTIONARY SEARCH IN BATCHES"): the pattern set (a host object: the Shift-And automaton of
+// mh_find.h), the device image of a dictionary (built in mh_dict_host.cpp), the device calls under one shared model of order
+// 0/1 or 2 or under a model set (kernels: mh_find.hip) and the host-buffer forms.  Every call is written once over a Matcher.
 #include "mh_api_internal.hpp"
 #include "mh_batch.h"
 #include "mh_find.h"
@@ -9,12 +10,21 @@ using namespace mhapi;
 
 namespace {
 
+// what a call searches for: a pattern set or a dictionary
+struct Matcher {
+    const mh_pattern_set *ps = nullptr;
+    const mh_dict *dict = nullptr;
+    explicit Matcher(const mh_pattern_set *s) : ps(s) {}
+    explicit Matcher(const mh_dict *d) : dict(d) {}
+    bool null() const { return !ps && !dict; }
+};
+
 // the checks all device calls share, in the order of mh_dev_decode_batch, and the batch part of the parameters
-int prepare(const mh_pattern_set *ps, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits, size_t n_streams,
+int prepare(const Matcher &mt, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits, size_t n_streams,
             uint64_t pay_total, uint32_t ctx0, const uint64_t *d_sym_off, uint64_t sym_total, const uint64_t *d_index, uint32_t chunk_symbols,
             uint64_t *d_hit_off, uint64_t *d_hits, uint32_t *d_hit_pattern, uint64_t hit_cap, int32_t *d_stream_status, void *d_ws,
             size_t ws_bytes, mhf::FindParams &p) {
-    if (!ps || (!d_payload && pay_total) || !d_pay_off || (!d_nbits && n_streams) || !d_hit_off || !d_ws) return MH_ERR_ARG;
+    if (mt.null() || (!d_payload && pay_total) || !d_pay_off || (!d_nbits && n_streams) || !d_hit_off || !d_ws) return MH_ERR_ARG;
     if (!aligned16(d_payload) || !aligned16(d_ws)) return MH_ERR_ARG;
     int shift = 0;
     if (d_index && ((shift = chunk_shift_of(chunk_symbols)) < 0 || !d_sym_off)) return MH_ERR_ARG;
@@ -27,7 +37,7 @@ int prepare(const mh_pattern_set *ps, const uint8_t *d_payload, const uint64_t *
     p.b.index = d_index; p.b.chunk_shift = uint32_t(shift);
     p.b.walk_max_bits = MH_BATCH_WALK_MAX_BITS;
     p.b.stream_status = d_stream_status ? d_stream_status : reinterpret_cast<int *>(static_cast<unsigned char *>(d_ws) + L.off_status);
-    p.first = ps->first; p.last = ps->last; p.max_len = ps->max_len;
+    if (mt.ps) { p.first = mt.ps->first; p.last = mt.ps->last; p.max_len = mt.ps->max_len; }
     p.hit_off = reinterpret_cast<unsigned long long *>(d_hit_off);
     p.hits = reinterpret_cast<unsigned long long *>(d_hits);
     p.hit_pattern = d_hits ? d_hit_pattern : nullptr;
@@ -35,33 +45,53 @@ int prepare(const mh_pattern_set *ps, const uint8_t *d_payload, const uint64_t *
     return MH_OK;
 }
 
-int run(const mhf::FindParams &p, const mh_pattern_set *ps, mhf::Model model, void *d_ws, void *stream) {
+int run(const mhf::FindParams &p, const Matcher &mt, mhf::Model model, void *d_ws, void *stream) {
+    if (mt.dict) {
+        if (!mt.dict->d_image) return MH_ERR_NO_DEVICE;
+        HIP_TRY(mhf::launch_find_dict(p, mt.dict->dev, model, d_ws, static_cast<hipStream_t>(stream)));
+        return MH_OK;
+    }
     mhf::Automaton a;
-    std::memcpy(a.mask, ps->mask, sizeof a.mask);
+    std::memcpy(a.mask, mt.ps->mask, sizeof a.mask);
     HIP_TRY(mhf::launch_find(p, a, model, d_ws, static_cast<hipStream_t>(stream)));
     return MH_OK;
 }
 
-// mh_dev_find_batch and mh_dev_find_batch_o2 behind their order checks: one shared model, its tables as the model's batch
-// decoder takes them
-int find_shared(const mh_model *m, mhf::Model model, const mh_pattern_set *ps, const uint8_t *d_payload, const uint64_t *d_pay_off,
+// mh_dev_find_batch, mh_dev_find_batch_o2 and their dictionary forms behind their order checks: one shared model, its tables
+// as the model's batch decoder takes them
+int find_shared(const mh_model *m, mhf::Model model, const Matcher &mt, const uint8_t *d_payload, const uint64_t *d_pay_off,
                 const uint64_t *d_nbits, size_t n_streams, uint64_t pay_total, uint8_t prev0, const uint64_t *d_sym_off, uint64_t sym_total,
                 const uint64_t *d_index, uint32_t chunk_symbols, uint64_t *d_hit_off, uint64_t *d_hits, uint32_t *d_hit_pattern, uint64_t hit_cap,
                 int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
     mhf::FindParams p{};
-    const int rc = prepare(ps, d_payload, d_pay_off, d_nbits, n_streams, pay_total, ctx_of_prev0(m, prev0), d_sym_off, sym_total, d_index,
+    const int rc = prepare(mt, d_payload, d_pay_off, d_nbits, n_streams, pay_total, ctx_of_prev0(m, prev0), d_sym_off, sym_total, d_index,
                            chunk_symbols, d_hit_off, d_hits, d_hit_pattern, hit_cap, d_stream_status, d_ws, ws_bytes, p);
     if (rc != MH_OK) return rc;
     if (m->max_len > mh::MAX_CODE_BITS) return MH_ERR_CODE_TOO_LONG;
     if (!m->d_prim || !have_device()) return MH_ERR_NO_DEVICE;
     fill_dec_tables(m, p.b);
-    return run(p, ps, model, d_ws, stream);
+    return run(p, mt, model, d_ws, stream);
+}
+
+// mh_dev_find_each and its dictionary form
+int find_each(const mh_model_set *s, const Matcher &mt, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits,
+              size_t n_streams, uint64_t pay_total, uint8_t prev0, const uint64_t *d_sym_off, uint64_t sym_total, const uint64_t *d_index,
+              uint32_t chunk_symbols, uint64_t *d_hit_off, uint64_t *d_hits, uint32_t *d_hit_pattern, uint64_t hit_cap,
+              int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
+    if (!s || n_streams != s->d.n) return MH_ERR_ARG;
+    mhf::FindParams p{};
+    const int rc = prepare(mt, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index, chunk_symbols, d_hit_off,
+                           d_hits, d_hit_pattern, hit_cap, d_stream_status, d_ws, ws_bytes, p);
+    if (rc != MH_OK) return rc;
+    if (!have_device()) return MH_ERR_NO_DEVICE;
+    p.set = s->d;
+    return run(p, mt, mhf::Model::Set, d_ws, stream);
 }
 
 // the argument checks of the two host forms, in the order of mh_decode_batch
-int host_args(const mh_model *m, const mh_pattern_set *ps, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits, size_t n_streams,
+int host_args(const mh_model *m, const Matcher &mt, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits, size_t n_streams,
               const uint64_t *sym_off, const uint64_t *index, uint32_t chunk_symbols, const uint64_t *hit_off) {
-    if (!ps || !pay_off || (!nbits && n_streams) || !hit_off) return MH_ERR_ARG;
+    if (mt.null() || !pay_off || (!nbits && n_streams) || !hit_off) return MH_ERR_ARG;
     if (index && (chunk_shift_of(chunk_symbols) < 0 || !sym_off)) return MH_ERR_ARG;
     if (!offsets_ok(pay_off, n_streams)) return MH_ERR_ARG;
     if (!payload && pay_off[n_streams]) return MH_ERR_ARG;
@@ -82,7 +112,7 @@ struct HostSearch {
     uint64_t cap = 0, nrec = 0;         // records asked for, records kept
     int dev_rc = MH_OK;
 
-    int search(const mh_model *m, const mh_pattern_set *ps, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits, size_t n_streams,
+    int search(const mh_model *m, const Matcher &mt, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits, size_t n_streams,
                uint8_t prev0, const uint64_t *sym_off, const uint64_t *index, uint32_t chunk_symbols, bool want_hits, bool want_pattern,
                uint64_t hit_cap) {
         const hipStream_t st = nullptr;
@@ -108,11 +138,10 @@ struct HostSearch {
             HIP_TRY(hipMemcpy(d_so.p, sym_off, (n_streams + 1) * 8, hipMemcpyHostToDevice));
             if (nidx) HIP_TRY(hipMemcpy(d_idx.p, index, nidx * 8, hipMemcpyHostToDevice));
         }
-        const auto dev = order2(m) ? mh_dev_find_batch_o2 : mh_dev_find_batch;
-        const int rc = dev(m, ps, d_pl.as<uint8_t>(), d_po.as<uint64_t>(), d_nb.as<uint64_t>(), n_streams, pay_total, prev0,
-                           index ? d_so.as<uint64_t>() : nullptr, sym_total, index ? d_idx.as<uint64_t>() : nullptr, chunk_symbols,
-                           d_ho.as<uint64_t>(), want_hits ? d_hits.as<uint64_t>() : nullptr, want_pattern ? d_pat.as<uint32_t>() : nullptr, cap,
-                           d_st.as<int32_t>(), d_ws.p, wsb, st);
+        const int rc = find_shared(m, order2(m) ? mhf::Model::Shared2 : mhf::Model::Shared, mt, d_pl.as<uint8_t>(), d_po.as<uint64_t>(), d_nb.as<uint64_t>(), n_streams, pay_total, prev0,
+                                   index ? d_so.as<uint64_t>() : nullptr, sym_total, index ? d_idx.as<uint64_t>() : nullptr, chunk_symbols,
+                                   d_ho.as<uint64_t>(), want_hits ? d_hits.as<uint64_t>() : nullptr, want_pattern ? d_pat.as<uint32_t>() : nullptr,
+                                   cap, d_st.as<int32_t>(), d_ws.p, wsb, st);
         if (rc != MH_OK) return rc;
         dev_rc = mh_dev_status(d_ws.p, st);
         sst.resize(n_streams);
@@ -142,7 +171,17 @@ struct HostSearch {
 
 // the hits of one decoded message under the host-side automaton, in (end, pattern) order
 struct Hit { uint64_t begin, end; uint32_t pattern; };
-void host_find(const mh_pattern_set *ps, const uint8_t *data, size_t n, std::vector<Hit> &out) {
+void host_find(const Matcher &mt, const uint8_t *data, size_t n, std::vector<Hit> &out) {
+    if (mt.dict) {
+        uint64_t total = 0;
+        mh_dict_find_bytes(mt.dict, data, n, nullptr, nullptr, 0, &total);
+        std::vector<uint64_t> at(static_cast<size_t>(total) * 2);
+        std::vector<uint32_t> pat(static_cast<size_t>(total));
+        mh_dict_find_bytes(mt.dict, data, n, at.data(), pat.data(), total, &total);
+        for (size_t r = 0; r < total; ++r) out.push_back(Hit{at[2 * r], at[2 * r + 1], pat[r]});
+        return;
+    }
+    const mh_pattern_set *ps = mt.ps;
     uint64_t D = 0;
     for (size_t k = 0; k < n; ++k) {
         D = ((D << 1) | ps->first) & ps->mask[data[k]];
@@ -154,6 +193,131 @@ void host_find(const mh_pattern_set *ps, const uint8_t *data, size_t n, std::vec
         }
     }
 }
+
+// mh_find_batch and mh_find_dict_batch
+int find_batch_host(const mh_model *m, const Matcher &mt, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits,
+                  size_t n_streams, uint8_t prev0, const uint64_t *sym_off, const uint64_t *index, uint32_t chunk_symbols, uint64_t *hit_off,
+                  uint64_t *hits, uint32_t *hit_pattern, uint64_t hit_cap, int32_t *stream_status) {
+    if (!order01(m)) return MH_ERR_ARG;
+    int rc = host_args(m, mt, payload, pay_off, nbits, n_streams, sym_off, index, chunk_symbols, hit_off);
+    if (rc != MH_OK) return rc;
+    // index-free with a stream over the walk cap: index the batch first (mh_index_batch never refuses a valid stream), then
+    // search it as an indexed batch; a stream the indexing fails keeps that error and has no symbols, so no hits
+    std::vector<uint64_t> own_so, own_idx;
+    std::vector<int32_t> idx_st;
+    bool over = false;
+    if (!index)
+        for (size_t i = 0; i < n_streams && !over; ++i) over = nbits[i] > MH_BATCH_WALK_MAX_BITS;
+    if (over) {
+        const uint64_t minl = uint64_t(m->min_len > 0 ? m->min_len : 1);
+        uint64_t bound = 0;
+        for (size_t i = 0; i < n_streams; ++i) bound += nbits[i] / minl;
+        chunk_symbols = MH_CHUNK_DEFAULT;
+        own_so.assign(n_streams + 1, 0);
+        own_idx.assign(size_t(mh_batch_index_capacity(bound, n_streams, chunk_symbols)), 0);
+        idx_st.assign(n_streams, MH_OK);
+        rc = mh_index_batch(m, payload, pay_off, nbits, n_streams, prev0, chunk_symbols, own_so.data(), own_idx.data(), own_idx.size(),
+                            idx_st.data());
+        if (rc == MH_ERR_HIP || rc == MH_ERR_NO_DEVICE || rc == MH_ERR_NOMEM || rc == MH_ERR_CAPACITY) return rc;
+        sym_off = own_so.data();
+        index = own_idx.data();
+    }
+    HostSearch hs;
+    rc = hs.search(m, mt, payload, pay_off, nbits, n_streams, prev0, sym_off, index, chunk_symbols, hits != nullptr, hit_pattern != nullptr, hit_cap);
+    if (rc != MH_OK) return rc;
+    std::copy(hs.hit_off.begin(), hs.hit_off.end(), hit_off);
+    if ((rc = hs.records(hits, hit_pattern)) != MH_OK) return rc;
+    for (size_t i = 0; i < idx_st.size(); ++i)
+        if (idx_st[i] != MH_OK) hs.sst[i] = idx_st[i];
+    return hs.finish(stream_status);
+}
+
+// mh_find_batch_o2 and mh_find_dict_batch_o2
+int find_batch_o2_host(const mh_model *m, const Matcher &mt, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits,
+                     size_t n_streams, uint8_t prev0, const uint64_t *sym_off, const uint64_t *index, uint32_t chunk_symbols, uint64_t *hit_off,
+                     uint64_t *hits, uint32_t *hit_pattern, uint64_t hit_cap, int32_t *stream_status) {
+    if (!order2(m)) return MH_ERR_ARG;
+    int rc = host_args(m, mt, payload, pay_off, nbits, n_streams, sym_off, index, chunk_symbols, hit_off);
+    if (rc != MH_OK) return rc;
+    // index-free streams over the walk cap: the device call refuses them; each is decoded alone and searched by the
+    // host-side automaton, its records spliced into place in stream order
+    std::vector<size_t> long_streams;
+    if (!index)
+        for (size_t i = 0; i < n_streams; ++i)
+            if (nbits[i] > MH_BATCH_WALK_MAX_BITS) long_streams.push_back(i);
+    HostSearch hs;
+    rc = hs.search(m, mt, payload, pay_off, nbits, n_streams, prev0, sym_off, index, chunk_symbols, hits != nullptr, hit_pattern != nullptr, hit_cap);
+    if (rc != MH_OK) return rc;
+    if (long_streams.empty()) {
+        std::copy(hs.hit_off.begin(), hs.hit_off.end(), hit_off);
+        if ((rc = hs.records(hits, hit_pattern)) != MH_OK) return rc;
+        return hs.finish(stream_status);
+    }
+    const uint64_t cap = hs.cap;
+    const std::vector<uint64_t> &dho = hs.hit_off;
+    std::vector<uint64_t> dh(static_cast<size_t>(hs.nrec) * 3);
+    std::vector<uint32_t> dp(static_cast<size_t>(hs.nrec));
+    if ((rc = hs.records(dh.data(), hit_pattern ? dp.data() : nullptr)) != MH_OK) return rc;
+    uint64_t r = 0;
+    size_t k = 0;
+    std::vector<uint8_t> bytes;
+    std::vector<Hit> found;
+    for (size_t i = 0; i < n_streams; ++i) {
+        hit_off[i] = r;
+        if (k < long_streams.size() && long_streams[k] == i) {
+            ++k;
+            found.clear();
+            hs.sst[i] = decode_alone(m, payload + pay_off[i], nbits[i], prev0, bytes);
+            if (hs.sst[i] == MH_OK) host_find(mt, bytes.data(), bytes.size(), found);
+            for (const Hit &h : found) {
+                if (r < cap) {
+                    hits[3 * r] = i; hits[3 * r + 1] = h.begin; hits[3 * r + 2] = h.end;
+                    if (hit_pattern) hit_pattern[r] = h.pattern;
+                }
+                ++r;
+            }
+            continue;
+        }
+        for (uint64_t q = dho[i]; q < dho[i + 1]; ++q, ++r) {
+            if (r >= cap) continue;                             // (q <= r: the device kept this record)
+            hits[3 * r] = dh[3 * q]; hits[3 * r + 1] = dh[3 * q + 1]; hits[3 * r + 2] = dh[3 * q + 2];
+            if (hit_pattern) hit_pattern[r] = dp[q];
+        }
+    }
+    hit_off[n_streams] = r;
+    hs.dev_rc = hits && r > cap ? MH_ERR_CAPACITY : MH_OK;
+    return hs.finish(stream_status);
+}
+
+// the device image of a dictionary on the current device: mh_dict_create calls this through mhd::g_upload
+int dict_upload(mh_dict *d) {
+    if (!have_device()) return MH_OK;
+    const mhd::DictImage L = mhd::dict_image(d->states, d->ncls, d->out_pat.size());
+    std::vector<uint8_t> img(L.total, 0);
+    std::memcpy(img.data(), d->cls, 256);
+    std::memcpy(img.data() + L.off_trans, d->trans.data(), d->trans.size() * 2);
+    std::memcpy(img.data() + L.off_out_off, d->out_off.data(), d->out_off.size() * 4);
+    if (!d->out_pat.empty()) {
+        std::memcpy(img.data() + L.off_out_pat, d->out_pat.data(), d->out_pat.size() * 4);
+        std::memcpy(img.data() + L.off_out_len, d->out_len.data(), d->out_len.size());
+    }
+    std::memcpy(img.data() + L.off_depth, d->depth.data(), d->depth.size());
+    HIP_TRY(hipGetDevice(&d->device));
+    void *p = nullptr;
+    HIP_TRY(hipMalloc(&p, L.total));
+    d->d_image = p;                                              // (mh_dict_free releases it when the copy fails)
+    HIP_TRY(hipMemcpy(p, img.data(), L.total, hipMemcpyHostToDevice));
+    const uint8_t *b = static_cast<const uint8_t *>(p);
+    d->dev = mhd::DictDev{b, reinterpret_cast<const uint16_t *>(b + L.off_trans), reinterpret_cast<const uint32_t *>(b + L.off_out_off),
+                          reinterpret_cast<const uint32_t *>(b + L.off_out_pat), b + L.off_depth, b + L.off_out_len, d->ncls, d->states,
+                          d->max_len};
+    return MH_OK;
+}
+void dict_release(mh_dict *d) {
+    (void)hipFree(d->d_image);
+    d->d_image = nullptr;
+}
+const bool g_dict_hooks = (mhd::g_upload = dict_upload, mhd::g_release = dict_release, true);
 
 }  // namespace
 
@@ -202,7 +366,7 @@ int mh_dev_find_batch(const mh_model *m, const mh_pattern_set *ps, const uint8_t
                       uint32_t chunk_symbols, uint64_t *d_hit_off, uint64_t *d_hits, uint32_t *d_hit_pattern, uint64_t hit_cap,
                       int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
     if (!order01(m)) return MH_ERR_ARG;
-    return find_shared(m, mhf::Model::Shared, ps, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index,
+    return find_shared(m, mhf::Model::Shared, Matcher(ps), d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index,
                        chunk_symbols, d_hit_off, d_hits, d_hit_pattern, hit_cap, d_stream_status, d_ws, ws_bytes, stream);
 }
 
@@ -215,7 +379,7 @@ int mh_dev_find_batch_o2(const mh_model *m, const mh_pattern_set *ps, const uint
                          const uint64_t *d_index, uint32_t chunk_symbols, uint64_t *d_hit_off, uint64_t *d_hits, uint32_t *d_hit_pattern,
                          uint64_t hit_cap, int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
     if (!order2(m)) return MH_ERR_ARG;
-    return find_shared(m, mhf::Model::Shared2, ps, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index,
+    return find_shared(m, mhf::Model::Shared2, Matcher(ps), d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index,
                        chunk_symbols, d_hit_off, d_hits, d_hit_pattern, hit_cap, d_stream_status, d_ws, ws_bytes, stream);
 }
 
@@ -223,107 +387,68 @@ int mh_dev_find_each(const mh_model_set *s, const mh_pattern_set *ps, const uint
                      size_t n_streams, uint64_t pay_total, uint8_t prev0, const uint64_t *d_sym_off, uint64_t sym_total, const uint64_t *d_index,
                      uint32_t chunk_symbols, uint64_t *d_hit_off, uint64_t *d_hits, uint32_t *d_hit_pattern, uint64_t hit_cap,
                      int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
-    if (!s || n_streams != s->d.n) return MH_ERR_ARG;
-    mhf::FindParams p{};
-    const int rc = prepare(ps, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index, chunk_symbols, d_hit_off,
-                           d_hits, d_hit_pattern, hit_cap, d_stream_status, d_ws, ws_bytes, p);
-    if (rc != MH_OK) return rc;
-    if (!have_device()) return MH_ERR_NO_DEVICE;
-    p.set = s->d;
-    return run(p, ps, mhf::Model::Set, d_ws, stream);
+    return find_each(s, Matcher(ps), d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index, chunk_symbols,
+                     d_hit_off, d_hits, d_hit_pattern, hit_cap, d_stream_status, d_ws, ws_bytes, stream);
 }
 
 int mh_find_batch(const mh_model *m, const mh_pattern_set *ps, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits,
                   size_t n_streams, uint8_t prev0, const uint64_t *sym_off, const uint64_t *index, uint32_t chunk_symbols, uint64_t *hit_off,
                   uint64_t *hits, uint32_t *hit_pattern, uint64_t hit_cap, int32_t *stream_status) {
-    if (!order01(m)) return MH_ERR_ARG;
-    int rc = host_args(m, ps, payload, pay_off, nbits, n_streams, sym_off, index, chunk_symbols, hit_off);
-    if (rc != MH_OK) return rc;
-    // index-free with a stream over the walk cap: index the batch first (mh_index_batch never refuses a valid stream), then
-    // search it as an indexed batch; a stream the indexing fails keeps that error and has no symbols, so no hits
-    std::vector<uint64_t> own_so, own_idx;
-    std::vector<int32_t> idx_st;
-    bool over = false;
-    if (!index)
-        for (size_t i = 0; i < n_streams && !over; ++i) over = nbits[i] > MH_BATCH_WALK_MAX_BITS;
-    if (over) {
-        const uint64_t minl = uint64_t(m->min_len > 0 ? m->min_len : 1);
-        uint64_t bound = 0;
-        for (size_t i = 0; i < n_streams; ++i) bound += nbits[i] / minl;
-        chunk_symbols = MH_CHUNK_DEFAULT;
-        own_so.assign(n_streams + 1, 0);
-        own_idx.assign(size_t(mh_batch_index_capacity(bound, n_streams, chunk_symbols)), 0);
-        idx_st.assign(n_streams, MH_OK);
-        rc = mh_index_batch(m, payload, pay_off, nbits, n_streams, prev0, chunk_symbols, own_so.data(), own_idx.data(), own_idx.size(),
-                            idx_st.data());
-        if (rc == MH_ERR_HIP || rc == MH_ERR_NO_DEVICE || rc == MH_ERR_NOMEM || rc == MH_ERR_CAPACITY) return rc;
-        sym_off = own_so.data();
-        index = own_idx.data();
-    }
-    HostSearch hs;
-    rc = hs.search(m, ps, payload, pay_off, nbits, n_streams, prev0, sym_off, index, chunk_symbols, hits != nullptr, hit_pattern != nullptr, hit_cap);
-    if (rc != MH_OK) return rc;
-    std::copy(hs.hit_off.begin(), hs.hit_off.end(), hit_off);
-    if ((rc = hs.records(hits, hit_pattern)) != MH_OK) return rc;
-    for (size_t i = 0; i < idx_st.size(); ++i)
-        if (idx_st[i] != MH_OK) hs.sst[i] = idx_st[i];
-    return hs.finish(stream_status);
+    return find_batch_host(m, Matcher(ps), payload, pay_off, nbits, n_streams, prev0, sym_off, index, chunk_symbols, hit_off, hits, hit_pattern,
+                           hit_cap, stream_status);
 }
 
 int mh_find_batch_o2(const mh_model *m, const mh_pattern_set *ps, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits,
                      size_t n_streams, uint8_t prev0, const uint64_t *sym_off, const uint64_t *index, uint32_t chunk_symbols, uint64_t *hit_off,
                      uint64_t *hits, uint32_t *hit_pattern, uint64_t hit_cap, int32_t *stream_status) {
+    return find_batch_o2_host(m, Matcher(ps), payload, pay_off, nbits, n_streams, prev0, sym_off, index, chunk_symbols, hit_off, hits,
+                              hit_pattern, hit_cap, stream_status);
+}
+
+// ---- dictionary search: the same calls with the DFA of an mh_dict as the matcher
+
+size_t mh_dev_find_dict_workspace(size_t n_streams, uint64_t sym_total, uint32_t chunk_symbols) {
+    return mh_dev_find_batch_workspace(n_streams, sym_total, chunk_symbols);
+}
+
+int mh_dev_find_dict_batch(const mh_model *m, const mh_dict *d, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits,
+                           size_t n_streams, uint64_t pay_total, uint8_t prev0, const uint64_t *d_sym_off, uint64_t sym_total,
+                           const uint64_t *d_index, uint32_t chunk_symbols, uint64_t *d_hit_off, uint64_t *d_hits, uint32_t *d_hit_pattern,
+                           uint64_t hit_cap, int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
+    if (!order01(m)) return MH_ERR_ARG;
+    return find_shared(m, mhf::Model::Shared, Matcher(d), d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index,
+                       chunk_symbols, d_hit_off, d_hits, d_hit_pattern, hit_cap, d_stream_status, d_ws, ws_bytes, stream);
+}
+
+int mh_dev_find_dict_batch_o2(const mh_model *m, const mh_dict *d, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits,
+                              size_t n_streams, uint64_t pay_total, uint8_t prev0, const uint64_t *d_sym_off, uint64_t sym_total,
+                              const uint64_t *d_index, uint32_t chunk_symbols, uint64_t *d_hit_off, uint64_t *d_hits, uint32_t *d_hit_pattern,
+                              uint64_t hit_cap, int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
     if (!order2(m)) return MH_ERR_ARG;
-    int rc = host_args(m, ps, payload, pay_off, nbits, n_streams, sym_off, index, chunk_symbols, hit_off);
-    if (rc != MH_OK) return rc;
-    // index-free streams over the walk cap: the device call refuses them; each is decoded alone and searched by the
-    // host-side automaton, its records spliced into place in stream order
-    std::vector<size_t> long_streams;
-    if (!index)
-        for (size_t i = 0; i < n_streams; ++i)
-            if (nbits[i] > MH_BATCH_WALK_MAX_BITS) long_streams.push_back(i);
-    HostSearch hs;
-    rc = hs.search(m, ps, payload, pay_off, nbits, n_streams, prev0, sym_off, index, chunk_symbols, hits != nullptr, hit_pattern != nullptr, hit_cap);
-    if (rc != MH_OK) return rc;
-    if (long_streams.empty()) {
-        std::copy(hs.hit_off.begin(), hs.hit_off.end(), hit_off);
-        if ((rc = hs.records(hits, hit_pattern)) != MH_OK) return rc;
-        return hs.finish(stream_status);
-    }
-    const uint64_t cap = hs.cap;
-    const std::vector<uint64_t> &dho = hs.hit_off;
-    std::vector<uint64_t> dh(static_cast<size_t>(hs.nrec) * 3);
-    std::vector<uint32_t> dp(static_cast<size_t>(hs.nrec));
-    if ((rc = hs.records(dh.data(), hit_pattern ? dp.data() : nullptr)) != MH_OK) return rc;
-    uint64_t r = 0;
-    size_t k = 0;
-    std::vector<uint8_t> bytes;
-    std::vector<Hit> found;
-    for (size_t i = 0; i < n_streams; ++i) {
-        hit_off[i] = r;
-        if (k < long_streams.size() && long_streams[k] == i) {
-            ++k;
-            found.clear();
-            hs.sst[i] = decode_alone(m, payload + pay_off[i], nbits[i], prev0, bytes);
-            if (hs.sst[i] == MH_OK) host_find(ps, bytes.data(), bytes.size(), found);
-            for (const Hit &h : found) {
-                if (r < cap) {
-                    hits[3 * r] = i; hits[3 * r + 1] = h.begin; hits[3 * r + 2] = h.end;
-                    if (hit_pattern) hit_pattern[r] = h.pattern;
-                }
-                ++r;
-            }
-            continue;
-        }
-        for (uint64_t q = dho[i]; q < dho[i + 1]; ++q, ++r) {
-            if (r >= cap) continue;                             // (q <= r: the device kept this record)
-            hits[3 * r] = dh[3 * q]; hits[3 * r + 1] = dh[3 * q + 1]; hits[3 * r + 2] = dh[3 * q + 2];
-            if (hit_pattern) hit_pattern[r] = dp[q];
-        }
-    }
-    hit_off[n_streams] = r;
-    hs.dev_rc = hits && r > cap ? MH_ERR_CAPACITY : MH_OK;
-    return hs.finish(stream_status);
+    return find_shared(m, mhf::Model::Shared2, Matcher(d), d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index,
+                       chunk_symbols, d_hit_off, d_hits, d_hit_pattern, hit_cap, d_stream_status, d_ws, ws_bytes, stream);
+}
+
+int mh_dev_find_dict_each(const mh_model_set *s, const mh_dict *d, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits,
+                          size_t n_streams, uint64_t pay_total, uint8_t prev0, const uint64_t *d_sym_off, uint64_t sym_total,
+                          const uint64_t *d_index, uint32_t chunk_symbols, uint64_t *d_hit_off, uint64_t *d_hits, uint32_t *d_hit_pattern,
+                          uint64_t hit_cap, int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
+    return find_each(s, Matcher(d), d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index, chunk_symbols,
+                     d_hit_off, d_hits, d_hit_pattern, hit_cap, d_stream_status, d_ws, ws_bytes, stream);
+}
+
+int mh_find_dict_batch(const mh_model *m, const mh_dict *d, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits,
+                       size_t n_streams, uint8_t prev0, const uint64_t *sym_off, const uint64_t *index, uint32_t chunk_symbols, uint64_t *hit_off,
+                       uint64_t *hits, uint32_t *hit_pattern, uint64_t hit_cap, int32_t *stream_status) {
+    return find_batch_host(m, Matcher(d), payload, pay_off, nbits, n_streams, prev0, sym_off, index, chunk_symbols, hit_off, hits, hit_pattern,
+                           hit_cap, stream_status);
+}
+
+int mh_find_dict_batch_o2(const mh_model *m, const mh_dict *d, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits,
+                          size_t n_streams, uint8_t prev0, const uint64_t *sym_off, const uint64_t *index, uint32_t chunk_symbols,
+                          uint64_t *hit_off, uint64_t *hits, uint32_t *hit_pattern, uint64_t hit_cap, int32_t *stream_status) {
+    return find_batch_o2_host(m, Matcher(d), payload, pay_off, nbits, n_streams, prev0, sym_off, index, chunk_symbols, hit_off, hits,
+                              hit_pattern, hit_cap, stream_status);
 }
 
 }  // extern "C"

@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "mh_batch.h"
+#include "mh_dict.h"
 #include "mh_each.h"
 
 // The Shift-And automaton of a pattern set over one 64-bit word: pattern j owns len_j consecutive bits, ascending with j;
@@ -61,5 +62,7 @@ struct FindParams {
 // model: what the batch was coded under (mhb::Model, mh_batch.h); b's tables and b.prev0 as that model's batch decoder takes them
 using mhb::Model;
 hipError_t launch_find(const FindParams &p, const Automaton &a, Model model, void *d_ws, hipStream_t st);
+// the same search with a dictionary's DFA as the matcher (mh_dict.h): p.first / last / max_len unused, same workspace
+hipError_t launch_find_dict(const FindParams &p, const mhd::DictDev &d, Model model, void *d_ws, hipStream_t st);
 
 }  // namespace mhf

@@ -431,8 +431,9 @@ void i_coding_provider::decompress(FILE* input_fd, FILE* output_fd) {
 }
 
 // --find: the `.cm` file as a batch of one indexed stream, searched on the device without writing its bytes
-// (mh_find_batch); one line `pattern begin` per hit, ascending (end, pattern number).  Returns the number of hits.
-uint64_t i_coding_provider::find(FILE* input_fd, const std::vector<std::string>& patterns, bool fold) {
+// (mh_find_batch; dict, the patterns of --find-file: mh_find_dict_batch); one line `pattern begin` per hit, ascending (end,
+// pattern number).  Returns the number of hits.
+uint64_t i_coding_provider::find(FILE* input_fd, const std::vector<std::string>& patterns, bool fold, bool dict) {
     InputView in(input_fd, true);
     if (in.size == 0) mh_or_die(MH_ERR_CORRUPT, "find");
     uint64_t nbits = 0;
@@ -452,22 +453,30 @@ uint64_t i_coding_provider::find(FILE* input_fd, const std::vector<std::string>&
         pat_off.push_back((uint32_t)bytes.size());
     }
     mh_pattern_set* ps = nullptr;
-    mh_or_die(mh_pattern_set_create((const uint8_t*)bytes.data(), pat_off.data(), patterns.size(), fold ? MH_FIND_FOLD_ASCII : 0u, &ps), "--find");
-    const uint64_t pay_off[2] = {0, (uint64_t)in.size - 1}, sym_off[2] = {0, n_symbols};
+    mh_dict* dc = nullptr;
+    const uint32_t flags = fold ? MH_FIND_FOLD_ASCII : 0u;
+    if (dict) mh_or_die(mh_dict_create((const uint8_t*)bytes.data(), pat_off.data(), patterns.size(), flags, &dc), "--find-file");
+    else mh_or_die(mh_pattern_set_create((const uint8_t*)bytes.data(), pat_off.data(), patterns.size(), flags, &ps), "--find");
+    auto search = [&](uint64_t* hit_off, uint64_t* hits, uint32_t* pat, uint64_t cap) {
+        const uint64_t pay_off[2] = {0, (uint64_t)in.size - 1}, sym_off[2] = {0, n_symbols};
+        return dict ? mh_find_dict_batch(model_, dc, in.data + 1, pay_off, &nbits, 1, MH_PREV0, sym_off, index.data(), chunk, hit_off, hits, pat,
+                                         cap, nullptr)
+                    : mh_find_batch(model_, ps, in.data + 1, pay_off, &nbits, 1, MH_PREV0, sym_off, index.data(), chunk, hit_off, hits, pat, cap,
+                                    nullptr);
+    };
     uint64_t hit_off[2] = {0, 0};
     StageTimer timer("find", in.size);
-    mh_or_die(mh_find_batch(model_, ps, in.data + 1, pay_off, &nbits, 1, MH_PREV0, sym_off, index.data(), chunk, hit_off, nullptr, nullptr, 0,
-                            nullptr), "find");
+    mh_or_die(search(hit_off, nullptr, nullptr, 0), "find");
     const uint64_t total = hit_off[1];
     if (total) {
         std::vector<uint64_t> hits((size_t)total * 3);
         std::vector<uint32_t> pat((size_t)total);
-        mh_or_die(mh_find_batch(model_, ps, in.data + 1, pay_off, &nbits, 1, MH_PREV0, sym_off, index.data(), chunk, hit_off, hits.data(),
-                                pat.data(), total, nullptr), "find");
+        mh_or_die(search(hit_off, hits.data(), pat.data(), total), "find");
         for (uint64_t r = 0; r < total; ++r) printf("%u %llu\n", pat[r], (unsigned long long)hits[3 * r + 1]);
         fflush(stdout);
     }
     mh_pattern_set_free(ps);
+    mh_dict_free(dc);
     fclose(input_fd);
     return total;
 }

@@ -59,7 +59,7 @@ public:
     void set_ranges(const std::vector<uint64_t>& begin_end) { ranges_ = begin_end; }
     // extension: prints one line `pattern begin` per occurrence of the patterns in the compressed input (needs the index
     // sidecar), in ascending (end, pattern number) order, and returns their number; nothing is decompressed to a file
-    uint64_t find(FILE* input_fd, const std::vector<std::string>& patterns, bool fold);
+    uint64_t find(FILE* input_fd, const std::vector<std::string>& patterns, bool fold, bool dict);
     // --crc: prints `crc32 length` of the original input, taken on the device without writing its bytes
     void crc(FILE* input_fd);
     // --recode: the `.cm` on input_fd (coded under this model) coded again under `dst` without writing its bytes

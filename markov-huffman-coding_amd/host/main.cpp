@@ -15,6 +15,8 @@
 //                    --index the indexed path, and the output's own index goes to <output>.idx
 //   --find STRING    print `pattern begin` per occurrence of STRING in the original input, searched on the device without
 //                    decompressing (repeatable, 64 bytes in all; --find-fold folds ASCII case; needs -x and --index)
+//   --find-file FILE the same for a dictionary: one pattern per line of FILE (split at LF, empty lines skipped, any other byte
+//                    kept; up to 65536 patterns of at most 255 bytes), searched in one pass; not together with --find
 //   --crc            with -x: print `crc32 length` of the original input (CRC-32 as zlib computes it, %08x, and the byte
 //                    count), taken on the device without decompressing; with --index the indexed path
 #include <errno.h>
@@ -46,6 +48,8 @@ static void print_help() {
     eprintf("\t--find string  with -x and --index: print `pattern begin` for every occurrence of the string in the original input\n");
     eprintf("\t               without decompressing it (repeatable, 64 bytes in all; --find-fold: ASCII letters match either case);\n");
     eprintf("\t               exit status 0 with hits, 1 with none\n");
+    eprintf("\t--find-file f  the same with one pattern per line of `f` (empty lines skipped; at most 255 bytes each), thousands in one\n");
+    eprintf("\t               pass; honours --find-fold; not together with --find\n");
     eprintf("\t--crc          with -x: print the CRC-32 (as zlib computes it) and the length of the original input without\n");
     eprintf("\t               decompressing it, as `%%08x %%llu`; with --index the indexed path; no output file is written\n");
     eprintf("\t--recode table with -x, -e and -o: write the stream coded again under `table` (the bytes are never written);\n");
@@ -66,6 +70,7 @@ struct options {
     std::vector<uint64_t> ranges;                                 // begin, end per --range
     std::vector<std::string> finds;                               // one per --find
     bool find_fold = false;
+    const char* find_file = nullptr;                              // --find-file: the patterns are its lines, searched as a dictionary
     const char* recode_table = nullptr;                           // --recode: the table the stream is coded again under
     bool crc = false;                                             // --crc: print the digest of the original input
 };
@@ -125,6 +130,7 @@ static options parse(int argc, char* argv[]) {
                 o.ranges.push_back(e);
             }
             else if (!strcmp(a, "--find")) o.finds.push_back(need(a));
+            else if (!strcmp(a, "--find-file")) o.find_file = need(a);
             else if (!strcmp(a, "--find-fold")) o.find_fold = true;
             else if (!strcmp(a, "--recode")) o.recode_table = need(a);
             else if (!strcmp(a, "--crc")) o.crc = true;
@@ -185,6 +191,29 @@ int main(int argc, char* argv[]) {
         }
     }
 
+    if (o.find_file) {                                             // its lines take the place of the --find strings
+        if (!o.finds.empty()) {
+            eprintf("Error: --find-file cannot be combined with --find.\n");
+            exit(1);
+        }
+        FILE* f = fopen(o.find_file, "rb");
+        if (!f) {
+            eprintf("Error: cannot open the --find-file %s.\n", o.find_file);
+            exit(1);
+        }
+        std::string line;
+        for (int c; (c = fgetc(f)) != EOF || !line.empty();) {
+            if (c != '\n' && c != EOF) { line.push_back((char)c); continue; }
+            if (!line.empty()) o.finds.push_back(line);
+            line.clear();
+            if (c == EOF) break;
+        }
+        fclose(f);
+        if (o.finds.empty()) {
+            eprintf("Error: the --find-file %s holds no pattern.\n", o.find_file);
+            exit(1);
+        }
+    }
     if (o.find_fold && o.finds.empty()) {
         eprintf("Error: --find-fold needs --find.\n");
         exit(1);
@@ -210,9 +239,20 @@ int main(int argc, char* argv[]) {
             }
             total += p.size();
         }
-        if (total > MH_FIND_MAX_POSITIONS) {
-            eprintf("Error: the --find strings are %zu bytes in all; at most %d.\n", total, MH_FIND_MAX_POSITIONS);
+        if (!o.find_file && total > MH_FIND_MAX_POSITIONS) {
+            eprintf("Error: the --find strings are %zu bytes in all; at most %d (--find-file takes more).\n", total, MH_FIND_MAX_POSITIONS);
             exit(1);
+        }
+        if (o.find_file) {
+            for (const std::string& p : o.finds)
+                if (p.size() > MH_DICT_MAX_LEN) {
+                    eprintf("Error: a line of the --find-file is %zu bytes; at most %u.\n", p.size(), MH_DICT_MAX_LEN);
+                    exit(1);
+                }
+            if (o.finds.size() > MH_DICT_MAX_PATTERNS) {
+                eprintf("Error: the --find-file holds %zu patterns; at most %u.\n", o.finds.size(), MH_DICT_MAX_PATTERNS);
+                exit(1);
+            }
         }
     }
 
@@ -334,7 +374,7 @@ int main(int argc, char* argv[]) {
 
     if (!o.finds.empty()) {                                        // prints the hits; no output file
         eprintf("Searching %s...\n", o.input);
-        const uint64_t hits = coder->find(input_fd, o.finds, o.find_fold);
+        const uint64_t hits = coder->find(input_fd, o.finds, o.find_fold, o.find_file != nullptr);
         delete coder;
         eprintf("Done.\n");
         return hits ? 0 : 1;
