@@ -944,6 +944,12 @@ int mh_decode_bank(const mh_model_set *bank, const uint32_t *choice, const uint8
  *     the walk ends exactly at nbits_i with no null table entry; MH_ERR_ARG for nbits_i beyond its payload bytes and,
  *     index-free, over MH_BATCH_WALK_MAX_BITS).  A failed stream has zero hits in d_hit_off and writes no record; the other
  *     streams are unaffected.  mh_dev_status(d_ws) keeps one of the errors.
+ *   - With an index, the hits are those of the bytes mh_dev_decode_batch / mh_dev_decode_each returns for the same
+ *     arguments.  An entry's context field is taken as the symbol (order 2: the two symbols) in front of its chunk, as every
+ *     index writer of this library writes it.  An entry whose context field is wrong but whose chunk still decodes to its
+ *     end bit keeps its stream's verdict MH_OK, as in mh_dev_decode_batch, and its chunk decodes to other bytes: a hit across
+ *     that seam is counted and reported as those bytes hold it (the lane in front decodes the symbols behind the seam from
+ *     the entry's context field, as the chunk's own lane does), so the count and the records always agree.
  *   - Without d_index the call is index-free (one lane walks one stream): d_sym_off may be NULL and is neither read nor
  *     written, sym_total and chunk_symbols are ignored.  Long index-free streams: mh_dev_batch_states + mh_dev_batch_index
  *     first.

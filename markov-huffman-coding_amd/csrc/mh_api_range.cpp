@@ -135,13 +135,22 @@ int decode_ranges_host(const mh_model *m, bool o2, const uint8_t *payload, uint6
         if (rst[j] != MH_OK || b == e) continue;
         const size_t keep = pieces.size();
         const uint64_t c1 = (e - 1) >> shift;
+        // a range that ends inside its last chunk does not depend on the entry behind that chunk (include/mh.h: such an item
+        // is checked for null table entries and for running past nbits only): where that entry gives no end, the chunk's
+        // span is what its symbols in front of `end` can take at most
+        const bool inside = e != n_symbols && (e & ((uint64_t(1) << shift) - 1u)) != 0;
+        auto cbound = [&](uint64_t k) {
+            const uint64_t t = cend(k), sk = ent(k);
+            if (k != c1 || !inside || (t >= sk && t <= nbits) || sk > nbits) return t;
+            return std::min(nbits, sk + (e - (k << shift)) * uint64_t(m->max_len > 0 ? m->max_len : 1));
+        };
         for (uint64_t c = b >> shift; c <= c1;) {
             const uint64_t s = ent(c);
             auto fits = [&](uint64_t k) {
-                const uint64_t t = cend(k);
+                const uint64_t t = cbound(k);
                 return t >= s && t <= nbits && ((t + 7) >> 3) - (s >> 3) <= seg && ((k - c + 1) << shift) <= seg;
             };
-            if (s > nbits || cend(c) < s || cend(c) > nbits) { rst[j] = MH_ERR_CORRUPT; break; }   // (the device checks the rest)
+            if (s > nbits || cbound(c) < s || cbound(c) > nbits) { rst[j] = MH_ERR_CORRUPT; break; }   // (the device checks the rest)
             uint64_t lo = c, hi = c1;                                                              // last chunk that fits
             while (lo < hi) {
                 const uint64_t mid = (lo + hi + 1) >> 1;
@@ -152,7 +161,7 @@ int decode_ranges_host(const mh_model *m, bool o2, const uint8_t *payload, uint6
             q.b = std::max(b, c << shift);
             q.e = std::min(e, (lo + 1) << shift);
             q.lo = s >> 3;
-            q.hi = (cend(lo) + 7) >> 3;
+            q.hi = (cbound(lo) + 7) >> 3;
             q.c0 = c; q.c1 = lo;
             q.at = out_off[j] + (q.b - b);
             pieces.push_back(q);

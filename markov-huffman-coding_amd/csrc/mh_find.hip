@@ -239,7 +239,11 @@ __global__ __launch_bounds__(Dec<K>::NT) void find_idx_count_kernel(FindParams p
         state[w] = M.keep(D);
         if (c.last || !M.alive(D)) continue;
         // the tail: what began in this chunk and still completes in the next one.  No new starts, no verdict: the next chunk's
-        // own lane judges that chunk.
+        // own lane judges that chunk.  The symbols behind the seam are decoded as that lane and the emit pass decode them: from
+        // the next entry's context field (the cursor stands on its position: used == end - start), not from this lane's
+        // running context.  The two differ only under an index whose context field is wrong, and then the count must be that
+        // of the bytes the decoders return.
+        ctx = uint32_t(p.b.index[w + 1] >> (Dec<K>::O2 ? 48 : 56));
         const uint64_t rest = c.ni - c.first - c.nsym;
         const uint32_t lim = uint32_t(rest < M.tail_max() ? rest : M.tail_max());
         uint32_t tc = 0;

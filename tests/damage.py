@@ -8,7 +8,9 @@ The contract is the reference's `assert(bi == length)` (src/coding.cpp:158) made
   - lookups / ranges into an indexed stream fail iff a chunk they read fails, where a read that ends inside a chunk is only
     checked for null entries and for running past nbits.
 The oracle's mho_decompress is the reference's NDEBUG reading (no end check) and stays as it is; the verdicts here come from
-mho_decode_span, which walks the tree bit by bit.  The damage generators are deterministic in their seed and name every case.
+mho_decode_span, which walks the tree bit by bit.  The damage generators are deterministic in their seed and name every case:
+D1-D6 damage a payload or its nbits and leave the index alone; X1-X10 damage the chunk index (a sidecar file of its own) and
+leave the payload alone.  The verdict functions take the index as an argument and judge either.
 """
 import numpy as np
 
@@ -44,13 +46,15 @@ def boundaries(lens, data, order=1, prev0=0x20):
 
 def expected_entries(lens, data, chunk, prev0=0x20, order=1):
     """(chunk index, fine index) of the stream of `data` under code lengths lens[ctx * 256 + sym]: the entries the encoder
-    writes (order 1: prev << 56 | bit; order 2: ctx << 48 | bit) and the fine index (prev << 24 | bit & 0xFFFFFF, order 1)."""
+    writes (orders 0 and 1: prev << 56 | bit, the byte in front of the chunk also where the model ignores it; order 2:
+    ctx << 48 | bit) and the fine index (prev << 24 | bit & 0xFFFFFF, order 1)."""
     d = np.asarray(data, dtype=np.uint8)
     ctx = contexts(d, order, prev0)
+    field = contexts(d, 1, prev0) if order == 0 else ctx
     pos = boundaries(lens, d, order, prev0)[:-1]
     j = np.arange(0, d.size, chunk)
     shift = np.uint64(48 if order == 2 else 56)
-    index = (ctx[j].astype(np.uint64) << shift) | pos[j].astype(np.uint64)
+    index = (field[j].astype(np.uint64) << shift) | pos[j].astype(np.uint64)
     f = np.arange(0, d.size, 64)
     fine = ((ctx[f] << 24) | (pos[f] & 0xFFFFFF)).astype(np.uint32)
     return index, fine
@@ -69,11 +73,12 @@ def _entry(e, order):
     return int(e) & ((1 << shift) - 1), int(e) >> shift
 
 
-def chunk_verdicts(om, payload, nbits, index, chunk, n_symbols, order=1):
-    """Per chunk: (ok, bytes) of the chunk decoded from its entry with the contract's checks."""
+def chunk_verdicts(om, payload, nbits, index, chunk, n_symbols, order=1, only=None):
+    """Per chunk (only: of these chunk numbers, in their order): (ok, bytes) of the chunk decoded from its entry with the
+    contract's checks."""
     res = []
     nchunks = (n_symbols + chunk - 1) // chunk
-    for j in range(nchunks):
+    for j in (range(nchunks) if only is None else only):
         bit0, ctx = _entry(index[j], order)
         end = _entry(index[j + 1], order)[0] if j + 1 < nchunks else nbits
         count = min(chunk, n_symbols - j * chunk)
@@ -94,15 +99,19 @@ def verdict_indexed(om, payload, nbits, index, chunk, n_symbols, order=1):
 
 
 def verdict_range(om, payload, nbits, index, chunk, n_symbols, begin, end, order=1):
-    """A range [begin, end) of an indexed stream: (MH_OK, bytes) iff every chunk it reads passes.  A chunk read to its end
-    takes the full chunk check; a read that ends inside a chunk decodes end - chunk start symbols from the entry and fails
-    only on a null entry or on running past nbits."""
+    """A range [begin, end) of an indexed stream: (MH_OK, bytes) iff every chunk it reads passes.  A chunk whose entry lies
+    past nbits or behind the entry before it fails every range that touches it (and, through the end check of the chunk in
+    front, every range that ends on its start boundary).  A chunk read to its end takes the full chunk check; a read that
+    ends inside a chunk decodes end - chunk start symbols from the entry and fails only on a null entry or on running past
+    nbits."""
     if begin == end:
         return MH_OK, b""
     nchunks = (n_symbols + chunk - 1) // chunk
     out = b""
     for j in range(begin // chunk, (end - 1) // chunk + 1):
         bit0, ctx = _entry(index[j], order)
+        if bit0 > nbits or (j > 0 and bit0 < _entry(index[j - 1], order)[0]):
+            return MH_ERR_CORRUPT, None
         cs, ce = j * chunk, min((j + 1) * chunk, n_symbols)
         if end >= ce:
             nxt = _entry(index[j + 1], order)[0] if j + 1 < nchunks else nbits
@@ -231,3 +240,197 @@ def all_damages(payload, nbits, bounds, code_len, chunk_offsets=(), seed=0, per_
     return (d1_end_cuts(payload, nbits, bounds) + d2_extensions(payload, nbits, kmax)
             + d3_spread_cuts(payload, nbits, chunk_offsets, per_kind=per_kind, seed=seed)
             + d4_flips(payload, nbits, bounds, code_len, seed=seed))
+
+
+# ---- index damages: lists of (name, damaged slice) ---------------------------------------------------------------------------
+# One stream's index slice `sl` (m entries: positions p[k], context fields c[k]), its code boundaries `b`, nbits and the order.
+# Where k is free, the first, a middle and the last entry.  A damage that would leave the slice as it is is not returned.
+def pos_shift(order):
+    return 48 if order == 2 else 56
+
+
+def pos_mask(order):
+    return (1 << pos_shift(order)) - 1
+
+
+def _split(sl, order):
+    sh, mk = pos_shift(order), pos_mask(order)
+    return [int(e) & mk for e in sl], [int(e) >> sh for e in sl]
+
+
+def _join(p, c, order):
+    sh, mk = pos_shift(order), pos_mask(order)
+    return np.array([((ci << sh) | (pi & mk)) & 0xFFFFFFFFFFFFFFFF for pi, ci in zip(p, c)], dtype=np.uint64)
+
+
+def _picks(m, first=0, ks=None):
+    """The entries a damage is placed on: the first, a middle and the last one, or those of `ks` that exist."""
+    return sorted({k for k in ((first, m // 2, m - 1) if ks is None else ks) if first <= k < m})
+
+
+def _moved(sl, order, name, k, new_pos, out):
+    p, c = _split(sl, order)
+    if 0 <= new_pos <= pos_mask(order) and new_pos != p[k]:
+        p[k] = new_pos
+        out.append((name, _join(p, c, order)))
+
+
+def x1_off_by_one(sl, b, nbits, order, ks=None):
+    """p[k] +- 1."""
+    out, (p, _) = [], _split(sl, order)
+    for k in _picks(len(p), 0, ks):
+        for d in (-1, 1):
+            _moved(sl, order, "X1-e%d%+d" % (k, d), k, p[k] + d, out)
+    return out
+
+
+def x2_other_boundary(sl, b, nbits, order, ks=None):
+    """p[k] moved to the code boundary one symbol earlier and one symbol later."""
+    out, (p, _) = [], _split(sl, order)
+    bl = [int(x) for x in b]
+    for k in _picks(len(p), 0, ks):
+        j = bl.index(p[k])
+        for d in (-1, 1):
+            if 0 <= j + d < len(bl):
+                _moved(sl, order, "X2-e%d%+dsym" % (k, d), k, bl[j + d], out)
+    return out
+
+
+def x3_at_and_past_the_end(sl, b, nbits, order, ks=None):
+    """p[k] = nbits, nbits + 1 and the mask itself, for inner entries and for the last one."""
+    out = []
+    for k in _picks(len(sl), 1, ks) or [0]:
+        for what, v in (("nbits", nbits), ("nbits+1", nbits + 1), ("mask", pos_mask(order))):
+            _moved(sl, order, "X3-e%d=%s" % (k, what), k, v, out)
+    return out
+
+
+def x4_behind_the_predecessor(sl, b, nbits, order, ks=None):
+    """p[k] = p[k-1] - 1, p[k] = p[k-1] (an empty chunk k - 1) and p[k] = 0, k >= 1."""
+    out, (p, _) = [], _split(sl, order)
+    for k in _picks(len(p), 1, ks):
+        for what, v in (("pred-1", p[k - 1] - 1), ("pred", p[k - 1]), ("0", 0)):
+            _moved(sl, order, "X4-e%d=%s" % (k, what), k, v, out)
+    return out
+
+
+def x5_entry_0(sl, b, nbits, order, ks=None):
+    """p[0] = 1 and p[0] = p[1]."""
+    out, (p, _) = [], _split(sl, order)
+    if p:
+        _moved(sl, order, "X5-e0=1", 0, 1, out)
+    if len(p) > 1:
+        _moved(sl, order, "X5-e0=e1", 0, p[1], out)
+    return out
+
+
+def x6_swapped_and_shifted(sl, b, nbits, order, ks=None):
+    """Neighbours swapped; the whole slice shifted by one entry, either way."""
+    out, m = [], len(sl)
+    for k in _picks(m - 1, 0, ks):
+        s = np.array(sl, dtype=np.uint64)
+        s[k], s[k + 1] = sl[k + 1], sl[k]
+        out.append(("X6-swap%d,%d" % (k, k + 1), s))
+    if m > 1:
+        out.append(("X6-shift-1", np.concatenate([sl[1:], sl[-1:]]).astype(np.uint64)))
+        out.append(("X6-shift+1", np.concatenate([sl[:1], sl[:-1]]).astype(np.uint64)))
+    return [(n, s) for n, s in out if not np.array_equal(s, sl)]
+
+
+def x7_bits_a_32_bit_compare_drops(sl, b, nbits, order, ks=None):
+    """p[k] + 2^32, and the top position bit set."""
+    out, (p, _) = [], _split(sl, order)
+    for k in _picks(len(p), 0, ks):
+        _moved(sl, order, "X7-e%d+2^32" % k, k, p[k] + (1 << 32), out)
+        _moved(sl, order, "X7-e%d|top" % k, k, p[k] | (1 << (pos_shift(order) - 1)), out)
+    return out
+
+
+def live_contexts(lens, order):
+    """Context numbers with a table (some symbol has a code) under code lengths lens[ctx * 256 + sym]."""
+    n = {0: 1, 1: 256, 2: 65536}[order]
+    return np.flatnonzero(np.asarray(lens)[:n * 256].reshape(n, 256).max(axis=1) > 0)
+
+
+def x8_context_field(sl, b, nbits, order, lens=None, seed=0, n_live=3, values=None, entries=None):
+    """The context field changed, the position kept.  Orders 0 and 1: a context with no table (when the model has one), n_live
+    live contexts, entry 0's context.  Order 2: the high byte alone, the low byte alone (each to a byte that some live context
+    carries there), and a pair with no table.  values: these field values instead; entries: these entries instead of the picks."""
+    rng = np.random.default_rng(seed)
+    out, (p, c) = [], _split(sl, order)
+    ks = _picks(len(p), 0, entries)
+    live = live_contexts(lens, order) if lens is not None else np.zeros(0, dtype=np.int64)
+    for k in ks:
+        if values is not None:
+            cand = [("=%#x" % v, int(v)) for v in values]
+        elif order == 2:
+            lv = set(int(x) for x in live)
+            dead = [v for v in (int(x) for x in rng.integers(0, 65536, 64)) if v not in lv]
+            hi = int(live[int(rng.integers(0, live.size))]) >> 8 if live.size else (c[k] >> 8) ^ 1
+            lo = int(live[int(rng.integers(0, live.size))]) & 255 if live.size else (c[k] & 255) ^ 1
+            if hi == c[k] >> 8:
+                hi ^= 1
+            if lo == c[k] & 255:
+                lo ^= 1
+            cand = [("hi=%#x" % hi, (hi << 8) | (c[k] & 255)), ("lo=%#x" % lo, (c[k] & 0xFF00) | lo)]
+            if dead:
+                cand.append(("dead=%#x" % dead[0], dead[0]))
+        else:
+            nctx = 256
+            lv = set(int(x) for x in live) if order == 1 else set(range(256))
+            dead = [v for v in range(nctx) if v not in lv]
+            cand = [("dead=%#x" % dead[len(dead) // 2], dead[len(dead) // 2])] if dead else []
+            pool = sorted(lv - {c[k]})
+            for v in (rng.choice(pool, size=min(n_live, len(pool)), replace=False) if pool else []):
+                cand.append(("live=%#x" % int(v), int(v)))
+            cand.append(("e0ctx=%#x" % c[0], c[0]))
+        for what, v in cand:
+            if v != c[k]:
+                cc = list(c)
+                cc[k] = v
+                out.append(("X8-e%d%s" % (k, what), _join(p, cc, order)))
+    return out
+
+
+def x9_whole_entry(sl, b, nbits, order, ks=None):
+    """The whole entry zero, and all ones."""
+    out = []
+    for k in _picks(len(sl), 0, ks):
+        for what, v in (("zero", 0), ("ones", 0xFFFFFFFFFFFFFFFF)):
+            if int(sl[k]) != v:
+                s = np.array(sl, dtype=np.uint64)
+                s[k] = np.uint64(v)
+                out.append(("X9-e%d=%s" % (k, what), s))
+    return out
+
+
+def x10_gaps(index, bases, sizes):
+    """A batch index with every entry between the slices (slice i: index[bases[i] : bases[i] + sizes[i]]) all ones: still a
+    valid batch.  Returns (name, index)."""
+    keep = np.zeros(len(index), dtype=bool)
+    for a, m in zip(bases, sizes):
+        keep[int(a):int(a) + int(m)] = True
+    out = np.array(index, dtype=np.uint64)
+    out[~keep] = np.uint64(0xFFFFFFFFFFFFFFFF)
+    return "X10-gaps", out
+
+
+INDEX_KINDS = {"X1": x1_off_by_one, "X2": x2_other_boundary, "X3": x3_at_and_past_the_end, "X4": x4_behind_the_predecessor,
+               "X5": x5_entry_0, "X6": x6_swapped_and_shifted, "X7": x7_bits_a_32_bit_compare_drops, "X8": x8_context_field,
+               "X9": x9_whole_entry}
+
+
+def index_damages(sl, b, nbits, order, lens=None, seed=0, kinds=None, ks=None):
+    """X1-X9 of one stream's slice, each a (name, damaged slice); the kind is the name up to the first '-'.  ks: the entries to
+    damage instead of the first, a middle and the last one."""
+    out = []
+    for kind in kinds or sorted(INDEX_KINDS, key=lambda s: int(s[1:])):
+        fn = INDEX_KINDS[kind]
+        out += fn(sl, b, nbits, order, lens, seed, entries=ks) if kind == "X8" else fn(sl, b, nbits, order, ks)
+    return out
+
+
+def flat_counts(seed=0):
+    """Order-1 counts drawn uniformly in [100, 200) for all 65 536 pairs: every context has a table and every code 8 bits, so
+    a chunk decoded from any other context byte still ends on its end bit, with other bytes."""
+    return np.random.default_rng(seed).integers(100, 200, 65536).astype(np.uint64)
