@@ -1262,6 +1262,71 @@ int mh_find_dict_batch_o2(const mh_model *m, const mh_dict *d, const uint8_t *pa
                           int32_t *stream_status);
 
 /* ---------------------------------------------------------------------------------------------------------------------
+ * EDITING BATCHES (extension, parity unpinned) — a length-preserving edit while re-coding: inside given spans of each
+ * record every byte b is replaced by map[b] (a constant map is a mask byte), and the record is coded under dst, which may be
+ * the source model itself.  The bytes are never written.  Order 0 and order 1 on both sides, independently; an order-2 model
+ * on either side is MH_ERR_ARG before any launch (order 2 and its seam bookkeeping are not built; neither are deletions and
+ * insertions, which move chunk boundaries, nor the refreshing of digests stored elsewhere).
+ *   - A span list: d_span_off[n + 1], the exclusive scan of the spans per stream, and d_spans[2r], d_spans[2r + 1] =
+ *     (begin, end), byte positions counted from the start of that stream's decoded message.  Within a stream the spans ascend
+ *     and are disjoint: begin < end <= next begin.  The part of a span at or beyond the stream's length is ignored (an
+ *     index-free caller does not know the length).  d_span_off == NULL: every byte of every stream is inside (case folding,
+ *     a charset map); d_spans is then ignored.  d_span_off[0] != 0 or decreasing offsets: MH_ERR_ARG through
+ *     mh_dev_status(d_ws) and nothing else is written, as for d_pay_off.
+ *   - d_map: 256 bytes on the device.
+ *   - Contract.  Let x be stream i's message as mh_dev_decode_batch / mh_dev_decode_each returns it for the same arguments,
+ *     and y[p] = map[x[p]] when p lies in one of the stream's spans, else x[p].  For every stream whose verdict is MH_OK the
+ *     output equals what mh_dev_encode_batch(dst) writes for y: d_out_off, d_out_nbits, the payload bytes and the index
+ *     slices, an index entry's context byte being y[start - 1] (prev0 in a stream's first chunk).  A pair (y[p-1], y[p])
+ *     without a code under dst is skipped while the destination context advances to y[p], and is counted in d_dropped[i].
+ *   - Verdicts: the batch decoders', and ONE more, the only verdict this call adds to theirs: a stream whose span list
+ *     breaks the rule above gets MH_ERR_ARG in d_stream_status and the output of a failed stream (nbits 0, no payload byte,
+ *     index slice untouched, dropped 0); mh_dev_status(d_ws) keeps the error; the other streams are unaffected.
+ *   - Everything else is word for word RE-CODING BATCHES: failed streams, the capacity rule and nothing written at or beyond
+ *     min(cap, out_off[n]), count-only mode, the index-free walk with its d_sym_off output, the workspace rule
+ *     (mh_dev_recode_edit_workspace), alignment, no allocation, no host synchronisation and a number of launches that does not
+ *     depend on the data.  With an empty span list, or the identity map, the output is mh_dev_recode_batch's byte for byte.
+ *   - mh_dev_recode_edit_each: stream i under the set's model i (n_streams == mh_model_set_size(src), else MH_ERR_ARG); a
+ *     bank view of mh_dev_model_set_pick is a set.
+ *   - Host form mh_recode_edit_batch: arguments checked before a device is touched (span_off as any offsets), spans and map
+ *     taken from host memory, the rest as mh_recode_batch (index-free streams over MH_BATCH_WALK_MAX_BITS are indexed first).
+ * Spans from search records.  mh_spans_from_hits (host, no device) and mh_dev_spans_from_hits take the records of any find
+ * call of this library — d_hit_off[n + 1], d_hits[3r ..] = (stream, begin, end) and the same hit_cap, in the documented order,
+ * ascending (stream, end, pattern) — and write the union of each stream's intervals as maximal spans, overlapping or touching
+ * records merged: d_span_off[n + 1] in full and at most hit_cap pairs in d_spans.  Begins are not monotonic in that order (a
+ * longer pattern that ends later may begin earlier); with M(r) the least begin over the stream's records r' >= r, records
+ * r - 1 and r lie in different spans exactly when end(r - 1) < M(r), and a span is (M(first), end(last)).
+ *   - d_hit_off[n] > hit_cap: the search overflowed and a redaction from it would be silently incomplete: MH_ERR_CAPACITY
+ *     (device form: through mh_dev_status(d_ws)), d_span_off all zeros, no span written.
+ *   - Device form: no allocation, no host synchronisation, a fixed number of launches whose grids are sized from hit_cap and
+ *     n_streams; d_ws 16-byte aligned, at least mh_dev_spans_from_hits_workspace(n, hit_cap) bytes (per record).  Bad offsets
+ *     or a record of a stream >= n: MH_ERR_ARG through mh_dev_status(d_ws).
+ * --------------------------------------------------------------------------------------------------------------------- */
+int mh_spans_from_hits(const uint64_t *hit_off, const uint64_t *hits, uint64_t hit_cap, size_t n_streams, uint64_t *span_off,
+                       uint64_t *spans);
+size_t mh_dev_spans_from_hits_workspace(size_t n_streams, uint64_t hit_cap);
+int mh_dev_spans_from_hits(const uint64_t *d_hit_off, const uint64_t *d_hits, uint64_t hit_cap, size_t n_streams,
+                           uint64_t *d_span_off, uint64_t *d_spans, void *d_ws, size_t ws_bytes, void *stream);
+size_t mh_dev_recode_edit_workspace(size_t n_streams, uint64_t sym_total, uint32_t chunk_symbols);
+int mh_dev_recode_edit_batch(const mh_model *src, const mh_model *dst, const uint8_t *d_payload, const uint64_t *d_pay_off,
+                             const uint64_t *d_nbits, size_t n_streams, uint64_t pay_total, uint8_t prev0, uint64_t *d_sym_off,
+                             uint64_t sym_total, const uint64_t *d_index, uint32_t chunk_symbols, const uint64_t *d_span_off,
+                             const uint64_t *d_spans, const uint8_t *d_map, uint8_t *d_out_payload, size_t cap,
+                             uint64_t *d_out_off, uint64_t *d_out_nbits, uint64_t *d_out_index, uint64_t *d_dropped,
+                             int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream);
+int mh_dev_recode_edit_each(const mh_model_set *src, const mh_model *dst, const uint8_t *d_payload, const uint64_t *d_pay_off,
+                            const uint64_t *d_nbits, size_t n_streams, uint64_t pay_total, uint8_t prev0, uint64_t *d_sym_off,
+                            uint64_t sym_total, const uint64_t *d_index, uint32_t chunk_symbols, const uint64_t *d_span_off,
+                            const uint64_t *d_spans, const uint8_t *d_map, uint8_t *d_out_payload, size_t cap,
+                            uint64_t *d_out_off, uint64_t *d_out_nbits, uint64_t *d_out_index, uint64_t *d_dropped,
+                            int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream);
+int mh_recode_edit_batch(const mh_model *src, const mh_model *dst, const uint8_t *payload, const uint64_t *pay_off,
+                         const uint64_t *nbits, size_t n_streams, uint8_t prev0, uint64_t *sym_off, const uint64_t *index,
+                         uint32_t chunk_symbols, const uint64_t *span_off, const uint64_t *spans, const uint8_t *map,
+                         uint8_t *out_payload, size_t cap, uint64_t *out_off, uint64_t *out_nbits, uint64_t *out_index,
+                         uint64_t *dropped, int32_t *stream_status);
+
+/* ---------------------------------------------------------------------------------------------------------------------
  * SEGMENT STATES OF INDEX-FREE ORDER-2 BATCHES (extension, parity unpinned) — the _o2 twins of the segment-state calls of
  * the next section, for a batch coded under one shared order-2 model (what mh_dev_encode_batch_o2 writes, stored without
  * its sidecar index).  Same arguments, layouts, workspace arithmetic, launch sequence and guarantees as the twins; what

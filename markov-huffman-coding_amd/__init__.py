@@ -72,6 +72,8 @@ EXPORTS = [
     "mh_dict_create", "mh_dict_free", "mh_dict_size", "mh_dict_max_len", "mh_dict_states", "mh_dict_classes", "mh_dict_device_bytes",
     "mh_dict_find_bytes", "mh_dev_find_dict_workspace", "mh_dev_find_dict_batch", "mh_dev_find_dict_each", "mh_dev_find_dict_batch_o2",
     "mh_find_dict_batch", "mh_find_dict_batch_o2",
+    "mh_spans_from_hits", "mh_dev_spans_from_hits_workspace", "mh_dev_spans_from_hits", "mh_dev_recode_edit_workspace",
+    "mh_dev_recode_edit_batch", "mh_dev_recode_edit_each", "mh_recode_edit_batch",
 ]
 FIND_MAX_POSITIONS = 64                    # include/mh.h MH_FIND_MAX_POSITIONS
 FIND_FOLD_ASCII = 1                        # include/mh.h MH_FIND_FOLD_ASCII
@@ -342,6 +344,15 @@ def lib():
         l.mh_dev_crc_raw_batch.argtypes = [vp, vp, sz, sz, vp, vp, sz, vp]
         l.mh_crc32_combine.argtypes = [u32, u32, u64]
         l.mh_crc32_combine.restype = u32
+        l.mh_spans_from_hits.argtypes = [vp, vp, u64, sz, vp, vp]
+        l.mh_dev_spans_from_hits_workspace.argtypes = [sz, u64]
+        l.mh_dev_spans_from_hits_workspace.restype = sz
+        l.mh_dev_spans_from_hits.argtypes = [vp, vp, u64, sz, vp, vp, vp, sz, vp]
+        l.mh_dev_recode_edit_workspace.argtypes = [sz, u64, u32]
+        l.mh_dev_recode_edit_workspace.restype = sz
+        for fn in (l.mh_dev_recode_edit_batch, l.mh_dev_recode_edit_each):
+            fn.argtypes = l.mh_dev_recode_batch.argtypes[:12] + [vp, vp, vp] + l.mh_dev_recode_batch.argtypes[12:]
+        l.mh_recode_edit_batch.argtypes = l.mh_recode_batch.argtypes[:10] + [vp, vp, vp] + l.mh_recode_batch.argtypes[10:]
         _lib = l
     return _lib
 
@@ -929,6 +940,67 @@ def _dev_recode(fn, src, dst, payload, pay_off, nbits, prev0, sym_off, index, ch
     return call(cap, True, want_index and bool(chunk_symbols), st)
 
 
+# ---- editing batches (include/mh.h, "EDITING BATCHES") ---------------------------------------------------------------------
+def _span_arrays(span_off, spans, byte_map):
+    """(span_off[n + 1] uint64 or None, spans as flat uint64 pairs, the 256-byte map) as contiguous arrays."""
+    so = None if span_off is None else np.ascontiguousarray(span_off, dtype=np.uint64)
+    sp = np.zeros(0, dtype=np.uint64) if spans is None else np.ascontiguousarray(spans, dtype=np.uint64).reshape(-1)
+    m = _u8(byte_map)
+    if m.size != 256:
+        raise ValueError("the byte map has 256 entries")
+    return so, sp, m
+
+
+def _dev_recode_edit(fn, src, dst, payload, pay_off, nbits, byte_map, span_off, spans, prev0, sym_off, index, chunk_symbols, **kw):
+    """One mh_dev_recode_edit_batch / _each call through _dev_recode: the same guards around every output, the same dict."""
+    so, sp, m = _span_arrays(span_off, spans, byte_map)
+    d_so = DeviceBuffer(so.nbytes, so) if so is not None else None
+    d_sp = DeviceBuffer(max(sp.nbytes, 16), sp if sp.size else None)
+    d_map = DeviceBuffer(256, m)
+
+    def call(*a):
+        return fn(*a[:12], d_so.ptr if d_so else None, d_sp.ptr, d_map.ptr, *a[12:])
+
+    return _dev_recode(call, src, dst, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols, ws_fn=lib().mh_dev_recode_edit_workspace, **kw)
+
+
+def spans_from_hits(hit_off, hits, hit_cap=None):
+    """mh_spans_from_hits (host, no device): the records of a find call, (hit_off[n + 1], hits[k, 3]), merged into maximal
+    spans: (span_off[n + 1], spans[m, 2], return code).  hit_cap None: the number of records given."""
+    hit_off = np.ascontiguousarray(hit_off, dtype=np.uint64)
+    hits = np.ascontiguousarray(hits, dtype=np.uint64).reshape(-1)
+    n = len(hit_off) - 1
+    cap = hits.size // 3 if hit_cap is None else hit_cap
+    so, sp = np.full(n + 1, FIND_FILL, dtype=np.uint64), np.zeros(2 * max(cap, 1), dtype=np.uint64)
+    rc = lib().mh_spans_from_hits(hit_off.ctypes.data, _ptr(hits), cap, n, so.ctypes.data, sp.ctypes.data)
+    if rc not in (MH_OK, MH_ERR_CAPACITY):
+        raise MhError(rc, "mh_spans_from_hits")
+    return so, sp[:2 * int(so[n])].reshape(-1, 2), rc
+
+
+def dev_spans_from_hits(hit_off, hits, hit_cap=None):
+    """One mh_dev_spans_from_hits call on uploaded records: (span_off[n + 1], spans[m, 2], mh_dev_status); asserts that the
+    FIND_GUARD words behind both outputs, and every pair at or beyond the spans, kept their fill."""
+    l = lib()
+    hit_off = np.ascontiguousarray(hit_off, dtype=np.uint64)
+    hits = np.ascontiguousarray(hits, dtype=np.uint64).reshape(-1)
+    n = len(hit_off) - 1
+    cap = hits.size // 3 if hit_cap is None else hit_cap
+    d_ho = DeviceBuffer(hit_off.nbytes, hit_off)
+    d_h = DeviceBuffer(max(hits.nbytes, 8), hits if hits.size else None)
+    d_so = DeviceBuffer((n + 1 + FIND_GUARD) * 8, np.full(n + 1 + FIND_GUARD, FIND_FILL, dtype=np.uint64))
+    d_sp = DeviceBuffer((2 * cap + FIND_GUARD) * 8, np.full(2 * cap + FIND_GUARD, FIND_FILL, dtype=np.uint64))
+    wsb = l.mh_dev_spans_from_hits_workspace(n, cap)
+    d_ws = DeviceBuffer(wsb, np.full(wsb, 0xA5, dtype=np.uint8))
+    _check(l.mh_dev_spans_from_hits(d_ho.ptr, d_h.ptr, cap, n, d_so.ptr, d_sp.ptr, d_ws.ptr, wsb, None), "mh_dev_spans_from_hits")
+    rc = l.mh_dev_status(d_ws.ptr, None)
+    so, sp = d_so.download(np.uint64), d_sp.download(np.uint64)
+    assert (so[n + 1:] == FIND_FILL).all(), "words written behind span_off"
+    m = int(so[n])
+    assert m <= cap and (sp[2 * m:] == FIND_FILL).all(), "pairs written at or beyond the spans"
+    return so[:n + 1], sp[:2 * m].reshape(-1, 2), rc
+
+
 def histogram_coded_batch_o2(src, order, payload, pay_off, nbits, prev0=PREV0, sym_off=None, index=None, chunk_symbols=0):
     """The training counts of an order-`order` model from a batch coded under `src`, no decoded byte written
     (mh_dev_histogram_coded_batch_o2; `src` or `order` is 2): counts[256, 65536 or 1 << 24].  Raises when a stream fails."""
@@ -1250,6 +1322,25 @@ class Model:
         """One mh_dev_recode_batch call (a batch coded under this model, coded again under `dst`) with guards around its outputs:
         the dict of _dev_recode."""
         return _dev_recode(lib().mh_dev_recode_batch, self._h, dst.handle, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols, **kw)
+
+    def dev_recode_edit_batch(self, dst, payload, pay_off, nbits, byte_map, span_off=None, spans=None, prev0=PREV0, sym_off=None, index=None,
+                              chunk_symbols=0, **kw):
+        """One mh_dev_recode_edit_batch call: dev_recode_batch with map[b] coded for every byte b inside the spans (span_off None:
+        everywhere).  The dict of _dev_recode, with its guards."""
+        return _dev_recode_edit(lib().mh_dev_recode_edit_batch, self._h, dst.handle, payload, pay_off, nbits, byte_map, span_off, spans, prev0,
+                                sym_off, index, chunk_symbols, **kw)
+
+    def recode_edit_batch(self, dst, payload, pay_off, nbits, byte_map, span_off=None, spans=None, prev0=PREV0, sym_off=None, index=None,
+                          chunk_symbols=0, cap=None, want_index=True, check=True):
+        """mh_recode_edit_batch (host form): recode_batch with the edit; the arguments and results of _recode_batch."""
+        so, sp, m = _span_arrays(span_off, spans, byte_map)
+        fn = lib().mh_recode_edit_batch
+
+        def call(*a):
+            return fn(*a[:10], so.ctypes.data if so is not None else None, _ptr(sp), m.ctypes.data, *a[10:])
+
+        return self._recode_batch(call, "mh_recode_edit_batch", dst, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols, cap, want_index,
+                                  check)
 
     def recode_batch(self, dst, payload, pay_off, nbits, prev0=PREV0, sym_off=None, index=None, chunk_symbols=0, cap=None, want_index=True,
                      check=True):
@@ -1732,6 +1823,12 @@ class ModelSet:
         """One mh_dev_recode_each call (stream i coded under this set's model i, coded again under the shared model `dst`):
         the dict of _dev_recode."""
         return _dev_recode(lib().mh_dev_recode_each, self._h, dst.handle, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols, **kw)
+
+    def recode_edit(self, dst, payload, pay_off, nbits, byte_map, span_off=None, spans=None, prev0=PREV0, sym_off=None, index=None,
+                    chunk_symbols=0, **kw):
+        """One mh_dev_recode_edit_each call: recode with map[b] coded for every byte b inside the spans: the dict of _dev_recode."""
+        return _dev_recode_edit(lib().mh_dev_recode_edit_each, self._h, dst.handle, payload, pay_off, nbits, byte_map, span_off, spans, prev0,
+                                sym_off, index, chunk_symbols, **kw)
 
     # ---- banks of shared models (include/mh.h, "BANKS OF SHARED MODELS"): this set is the bank, its streams the entries ----
     @classmethod

@@ -64,15 +64,16 @@ int histogram_coded(const mh_model *m, const mh_model_set *set, int order, const
     return MH_OK;
 }
 
-// behind the order rules of mh_dev_recode_batch, _each and _batch_o2: m or set is the source; seam: the workspace of the _o2
-// call, which has room for the seam's arrays
-int recode(const mh_model *m, const mh_model_set *set, const mh_model *dst, bool seam, const uint8_t *d_payload, const uint64_t *d_pay_off,
+// behind the order rules of mh_dev_recode_batch, _each, _batch_o2 and the _edit calls: m or set is the source; seam: the
+// workspace of the _o2 call, which has room for the seam's arrays; ed: the edit of an _edit call (order 0/1 on both sides)
+int recode(const mh_model *m, const mh_model_set *set, const mh_model *dst, bool seam, const mhr::Edit *ed, const uint8_t *d_payload, const uint64_t *d_pay_off,
            const uint64_t *d_nbits, size_t n_streams, uint64_t pay_total, uint8_t prev0, uint64_t *d_sym_off, uint64_t sym_total,
            const uint64_t *d_index, uint32_t chunk_symbols, uint8_t *d_out_payload, size_t cap, uint64_t *d_out_off, uint64_t *d_out_nbits,
            uint64_t *d_out_index, uint64_t *d_dropped, int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
     if (!d_out_off || (!d_out_nbits && n_streams)) return MH_ERR_ARG;
     if (!d_index && !d_sym_off) return MH_ERR_ARG;                    // index-free: the decoded lengths are an output
-    mhr::RecodeParams p{};
+    if (ed && !ed->map) return MH_ERR_ARG;
+    mhr::EditParams p{};
     const int rc = source(m, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index, chunk_symbols, d_ws, p.s);
     if (rc != MH_OK) return rc;
     if (!aligned16(d_out_payload)) return MH_ERR_ARG;
@@ -97,8 +98,17 @@ int recode(const mh_model *m, const mh_model_set *set, const mh_model *dst, bool
     p.dst.code64 = reinterpret_cast<const unsigned long long *>(dst->d_code64);
     p.dst.enc64 = dst->type == 2 ? reinterpret_cast<const unsigned long long *>(dst->d_enc64) : nullptr;
     p.dst.ctx_mask = dst->type == 2 ? 0xFFFFu : (dst->type ? 0xFFu : 0u);
-    HIP_TRY(mhr::launch_recode(p, model, d_ws, static_cast<hipStream_t>(stream)));
+    if (ed) {
+        p.ed = *ed;
+        HIP_TRY(mhr::launch_recode_edit(p, model, d_ws, static_cast<hipStream_t>(stream)));
+    } else {
+        HIP_TRY(mhr::launch_recode(p, model, d_ws, static_cast<hipStream_t>(stream)));
+    }
     return MH_OK;
+}
+
+mhr::Edit edit_of(const uint64_t *d_span_off, const uint64_t *d_spans, const uint8_t *d_map) {
+    return mhr::Edit{reinterpret_cast<const unsigned long long *>(d_span_off), reinterpret_cast<const unsigned long long *>(d_spans), d_map, 0u};
 }
 
 size_t recode_workspace(size_t n_streams, uint64_t sym_total, uint32_t chunk_symbols, bool seam) {
@@ -148,13 +158,14 @@ int index_first(const mh_model *src, const uint8_t *payload, const uint64_t *pay
 // verdicts, offsets, lengths and dropped counts; payload() and slices() then bring what the device wrote to wherever the
 // caller wants it.
 struct HostRecode {
-    using DevFn = decltype(&mh_dev_recode_batch);
     DevBuf d_pl, d_po, d_nb, d_so, d_idx, d_out, d_oo, d_onb, d_oidx, d_drop, d_st, d_ws;
     std::vector<int32_t> sst;           // per-stream verdicts
     std::vector<uint64_t> drop;         // per-stream dropped symbols
     size_t noidx = 0, dcap = 0;         // entries of the destination index, bytes of the payload buffer
     int dev_rc = MH_OK;
 
+    // dev: the device call, with the arguments of mh_dev_recode_batch
+    template <typename DevFn>
     int run(DevFn dev, bool seam, const mh_model *src, const mh_model *dst, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits,
             size_t n_streams, uint8_t prev0, uint64_t *sym_off, uint64_t sym_total, const uint64_t *index, uint32_t chunk_symbols,
             bool want_payload, size_t cap, uint64_t *out_off, uint64_t *out_nbits, const uint64_t *out_index) {
@@ -292,7 +303,7 @@ int mh_dev_recode_batch(const mh_model *src, const mh_model *dst, const uint8_t 
                         uint32_t chunk_symbols, uint8_t *d_out_payload, size_t cap, uint64_t *d_out_off, uint64_t *d_out_nbits,
                         uint64_t *d_out_index, uint64_t *d_dropped, int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
     if (!order01(src) || !order01(dst)) return MH_ERR_ARG;
-    return recode(src, nullptr, dst, false, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index,
+    return recode(src, nullptr, dst, false, nullptr, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index,
                   chunk_symbols, d_out_payload, cap, d_out_off, d_out_nbits, d_out_index, d_dropped, d_stream_status, d_ws, ws_bytes, stream);
 }
 
@@ -301,7 +312,7 @@ int mh_dev_recode_each(const mh_model_set *src, const mh_model *dst, const uint8
                        uint32_t chunk_symbols, uint8_t *d_out_payload, size_t cap, uint64_t *d_out_off, uint64_t *d_out_nbits,
                        uint64_t *d_out_index, uint64_t *d_dropped, int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
     if (!src || n_streams != src->d.n || !order01(dst)) return MH_ERR_ARG;
-    return recode(nullptr, src, dst, false, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index,
+    return recode(nullptr, src, dst, false, nullptr, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index,
                   chunk_symbols, d_out_payload, cap, d_out_off, d_out_nbits, d_out_index, d_dropped, d_stream_status, d_ws, ws_bytes, stream);
 }
 
@@ -310,7 +321,7 @@ int mh_dev_recode_batch_o2(const mh_model *src, const mh_model *dst, const uint8
                            uint32_t chunk_symbols, uint8_t *d_out_payload, size_t cap, uint64_t *d_out_off, uint64_t *d_out_nbits,
                            uint64_t *d_out_index, uint64_t *d_dropped, int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
     if (!order012(src) || !order012(dst) || (src->type != 2 && dst->type != 2)) return MH_ERR_ARG;
-    return recode(src, nullptr, dst, true, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index,
+    return recode(src, nullptr, dst, true, nullptr, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index,
                   chunk_symbols, d_out_payload, cap, d_out_off, d_out_nbits, d_out_index, d_dropped, d_stream_status, d_ws, ws_bytes, stream);
 }
 
@@ -335,6 +346,120 @@ int mh_recode_batch(const mh_model *src, const mh_model *dst, const uint8_t *pay
     HostRecode hr;
     rc = hr.run(mh_dev_recode_batch, false, src, dst, payload, pay_off, nbits, n_streams, prev0, sym_off, index ? sym_off[n_streams] : bound, index,
                 chunk_symbols, out_payload != nullptr, cap, out_off, out_nbits, out_index);
+    if (rc != MH_OK) return rc;
+    if ((rc = hr.payload(out_payload, out_off[n_streams])) != MH_OK || (rc = hr.slices(out_index)) != MH_OK) return rc;
+    return hr.finish(idx_st, dropped, stream_status);
+}
+
+/* ------------------------------------------------------------------------------------------------------- edit */
+
+int mh_spans_from_hits(const uint64_t *hit_off, const uint64_t *hits, uint64_t hit_cap, size_t n_streams, uint64_t *span_off, uint64_t *spans) {
+    if (!hit_off || !span_off) return MH_ERR_ARG;
+    std::fill(span_off, span_off + n_streams + 1, uint64_t(0));
+    const uint64_t total = hit_off[n_streams];
+    if (total > hit_cap) return MH_ERR_CAPACITY;
+    if (total && (!hits || !spans)) return MH_ERR_ARG;
+    if (!offsets_ok(hit_off, n_streams)) return MH_ERR_ARG;
+    uint64_t ns = 0;
+    std::vector<uint64_t> least;
+    for (size_t i = 0; i < n_streams; ++i) {
+        span_off[i] = ns;
+        const uint64_t a = hit_off[i], k = hit_off[i + 1] - a;
+        if (!k) continue;
+        const uint64_t *h = hits + 3 * a;
+        least.resize(size_t(k));                                       // least[r]: the least begin of the records r' >= r
+        uint64_t m = ~uint64_t(0);
+        for (uint64_t r = k; r-- > 0;) least[size_t(r)] = m = std::min(m, h[3 * r + 1]);
+        for (uint64_t r = 0; r < k; ++r) {
+            if (r == 0 || h[3 * (r - 1) + 2] < least[size_t(r)]) spans[2 * ns++] = least[size_t(r)];
+            spans[2 * (ns - 1) + 1] = h[3 * r + 2];
+        }
+    }
+    span_off[n_streams] = ns;
+    return MH_OK;
+}
+
+size_t mh_dev_spans_from_hits_workspace(size_t n_streams, uint64_t hit_cap) {
+    (void)n_streams;                                                  // per stream: only the offsets the caller passes
+    return mhr::span_layout(hit_cap).total;
+}
+
+int mh_dev_spans_from_hits(const uint64_t *d_hit_off, const uint64_t *d_hits, uint64_t hit_cap, size_t n_streams, uint64_t *d_span_off,
+                           uint64_t *d_spans, void *d_ws, size_t ws_bytes, void *stream) {
+    if (!d_hit_off || !d_span_off || !d_ws || (hit_cap && (!d_hits || !d_spans)) || !aligned16(d_ws)) return MH_ERR_ARG;
+    if (hit_cap >= (uint64_t(1) << 40)) return MH_ERR_ARG;
+    if (ws_bytes < mhr::span_layout(hit_cap).total) return MH_ERR_CAPACITY;
+    if (!have_device()) return MH_ERR_NO_DEVICE;
+    HIP_TRY(mhr::launch_spans_from_hits(reinterpret_cast<const unsigned long long *>(d_hit_off), reinterpret_cast<const unsigned long long *>(d_hits),
+                                        hit_cap, n_streams, reinterpret_cast<unsigned long long *>(d_span_off),
+                                        reinterpret_cast<unsigned long long *>(d_spans), d_ws, static_cast<hipStream_t>(stream)));
+    return MH_OK;
+}
+
+size_t mh_dev_recode_edit_workspace(size_t n_streams, uint64_t sym_total, uint32_t chunk_symbols) {
+    return recode_workspace(n_streams, sym_total, chunk_symbols, false);
+}
+
+int mh_dev_recode_edit_batch(const mh_model *src, const mh_model *dst, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits,
+                             size_t n_streams, uint64_t pay_total, uint8_t prev0, uint64_t *d_sym_off, uint64_t sym_total, const uint64_t *d_index,
+                             uint32_t chunk_symbols, const uint64_t *d_span_off, const uint64_t *d_spans, const uint8_t *d_map,
+                             uint8_t *d_out_payload, size_t cap, uint64_t *d_out_off, uint64_t *d_out_nbits, uint64_t *d_out_index,
+                             uint64_t *d_dropped, int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
+    if (!order01(src) || !order01(dst)) return MH_ERR_ARG;
+    const mhr::Edit ed = edit_of(d_span_off, d_spans, d_map);
+    return recode(src, nullptr, dst, false, &ed, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index,
+                  chunk_symbols, d_out_payload, cap, d_out_off, d_out_nbits, d_out_index, d_dropped, d_stream_status, d_ws, ws_bytes, stream);
+}
+
+int mh_dev_recode_edit_each(const mh_model_set *src, const mh_model *dst, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits,
+                            size_t n_streams, uint64_t pay_total, uint8_t prev0, uint64_t *d_sym_off, uint64_t sym_total, const uint64_t *d_index,
+                            uint32_t chunk_symbols, const uint64_t *d_span_off, const uint64_t *d_spans, const uint8_t *d_map,
+                            uint8_t *d_out_payload, size_t cap, uint64_t *d_out_off, uint64_t *d_out_nbits, uint64_t *d_out_index,
+                            uint64_t *d_dropped, int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
+    if (!src || n_streams != src->d.n || !order01(dst)) return MH_ERR_ARG;
+    const mhr::Edit ed = edit_of(d_span_off, d_spans, d_map);
+    return recode(nullptr, src, dst, false, &ed, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index,
+                  chunk_symbols, d_out_payload, cap, d_out_off, d_out_nbits, d_out_index, d_dropped, d_stream_status, d_ws, ws_bytes, stream);
+}
+
+int mh_recode_edit_batch(const mh_model *src, const mh_model *dst, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits,
+                         size_t n_streams, uint8_t prev0, uint64_t *sym_off, const uint64_t *index, uint32_t chunk_symbols,
+                         const uint64_t *span_off, const uint64_t *spans, const uint8_t *map, uint8_t *out_payload, size_t cap, uint64_t *out_off,
+                         uint64_t *out_nbits, uint64_t *out_index, uint64_t *dropped, int32_t *stream_status) {
+    if (!order01(src) || !order01(dst) || !map) return MH_ERR_ARG;
+    if (span_off && (!offsets_ok(span_off, n_streams) || (span_off[n_streams] && !spans))) return MH_ERR_ARG;
+    int rc = host_args(src, dst, payload, pay_off, nbits, n_streams, sym_off, index, chunk_symbols, out_off, out_nbits, out_index);
+    if (rc != MH_OK) return rc;
+    const uint64_t bound = symbol_bound(src, nbits, n_streams);
+    // index-free with a stream over the walk cap: index first (a span's positions do not depend on the index)
+    std::vector<uint64_t> own_idx;
+    std::vector<int32_t> idx_st;
+    bool over = false;
+    if (!index)
+        for (size_t i = 0; i < n_streams && !over; ++i) over = nbits[i] > MH_BATCH_WALK_MAX_BITS;
+    if (over) {
+        rc = index_first(src, payload, pay_off, nbits, n_streams, prev0, bound, out_index != nullptr, chunk_symbols, sym_off, own_idx, idx_st);
+        if (rc != MH_OK) return rc;
+        index = own_idx.data();
+    }
+    DevBuf d_soff, d_sp, d_map;
+    const size_t nsp = span_off ? size_t(span_off[n_streams]) : 0;
+    HIP_TRY(d_soff.alloc(span_off ? (n_streams + 1) * 8 : 0));
+    HIP_TRY(d_sp.alloc(nsp * 16));
+    HIP_TRY(d_map.alloc(256));
+    if (span_off) HIP_TRY(hipMemcpy(d_soff.p, span_off, (n_streams + 1) * 8, hipMemcpyHostToDevice));
+    if (nsp) HIP_TRY(hipMemcpy(d_sp.p, spans, nsp * 16, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_map.p, map, 256, hipMemcpyHostToDevice));
+    const uint64_t *so = span_off ? d_soff.as<uint64_t>() : nullptr, *sp = d_sp.as<uint64_t>();
+    const uint8_t *mp = d_map.as<uint8_t>();
+    auto dev = [=](const mh_model *s, const mh_model *d, const uint8_t *pl, const uint64_t *po, const uint64_t *nb, size_t n, uint64_t pt, uint8_t p0,
+                   uint64_t *syo, uint64_t st, const uint64_t *idx, uint32_t cs, uint8_t *o, size_t c, uint64_t *oo, uint64_t *onb, uint64_t *oi,
+                   uint64_t *dr, int32_t *sst, void *ws, size_t wsb, void *stream) {
+        return mh_dev_recode_edit_batch(s, d, pl, po, nb, n, pt, p0, syo, st, idx, cs, so, sp, mp, o, c, oo, onb, oi, dr, sst, ws, wsb, stream);
+    };
+    HostRecode hr;
+    rc = hr.run(dev, false, src, dst, payload, pay_off, nbits, n_streams, prev0, sym_off, index ? sym_off[n_streams] : bound, index, chunk_symbols,
+                out_payload != nullptr, cap, out_off, out_nbits, out_index);
     if (rc != MH_OK) return rc;
     if ((rc = hr.payload(out_payload, out_off[n_streams])) != MH_OK || (rc = hr.slices(out_index)) != MH_OK) return rc;
     return hr.finish(idx_st, dropped, stream_status);

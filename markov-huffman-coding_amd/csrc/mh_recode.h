@@ -84,9 +84,46 @@ struct RecodeParams : RecodeIO {
     Dst dst;
 };
 
+// the edit of a masked re-code (include/mh.h, "EDITING BATCHES"): inside stream i's spans [span_off[i], span_off[i + 1]) of
+// (begin, end) pairs, byte b of the decoded message is coded as map[b]
+struct Edit {
+    const unsigned long long *span_off;   // n + 1, or nullptr: every byte of every stream is inside
+    const unsigned long long *spans;
+    const uint8_t *map;                   // 256 bytes
+    uint32_t map_lds;                     // set by the launcher: the map has its 256 bytes of LDS behind the tables
+};
+
+struct EditParams : RecodeParams {
+    Edit ed;
+};
+
+// spans from search records: status block | per record: the reverse min-scan of the begins (u64), span starts and, scanned in
+// place, span numbers (u64, cap + 2) | per tile of SPAN_TILE records: first stream, last stream, the first record's scan
+// value, the carry from the tiles behind | scan block sums | per stream: nothing beyond the offsets the caller passes
+struct SpanLayout {
+    size_t off_min, off_num, off_tile, off_sums, total;
+};
+constexpr uint32_t SPAN_TILE = 256;
+inline SpanLayout span_layout(uint64_t hit_cap) {
+    SpanLayout l;
+    const uint64_t tiles = (hit_cap + SPAN_TILE - 1) / SPAN_TILE;
+    l.off_min = 64;
+    l.off_num = l.off_min + size_t(hit_cap) * 8;
+    l.off_tile = l.off_num + size_t(hit_cap + 2) * 8;
+    l.off_sums = l.off_tile + size_t(tiles) * 32;
+    l.total = (l.off_sums + size_t(mhb::scan_blocks(hit_cap + 2) + 1) * 8 + 255) & ~size_t(255);
+    return l;
+}
+
 // model: what the batch was coded under (mhb::Model, mh_batch.h); s.b's tables and s.b.prev0 as that model's batch decoder
 // takes them.  Any order of the histogram or of dst under a shared model; a model set with an order-2 side is refused.
 hipError_t launch_histogram_coded(const HistParams &p, mhb::Model model, void *d_ws, hipStream_t st);
 hipError_t launch_recode(const RecodeParams &p, mhb::Model model, void *d_ws, hipStream_t st);
+// the same with the edit applied; order 0/1 on both sides (an order-2 side is refused)
+hipError_t launch_recode_edit(const EditParams &p, mhb::Model model, void *d_ws, hipStream_t st);
+// the records of a find call (ascending (stream, end, pattern)) merged into maximal spans; a total over hit_cap: the status
+// word is MHK_STATUS_CAPACITY, span_off all zeros
+hipError_t launch_spans_from_hits(const unsigned long long *hit_off, const unsigned long long *hits, uint64_t hit_cap, uint64_t n_streams,
+                                  unsigned long long *span_off, unsigned long long *spans, void *d_ws, hipStream_t st);
 
 }  // namespace mhr

@@ -13,6 +13,9 @@
 //   recode_idx_emit_kernel   decodes again and pushes dst's codes through BitWriter; the chunk's index entry
 //   recode_walk_kernel       index-free, one lane per stream: count (scans) emit, under the walk cap of dec_walk_kernel
 //   recode_tail_kernel       the bytes of the last, partial dword
+//   recode_spans_kernel      (EDIT, include/mh.h "EDITING BATCHES") the span lists, in front of the length pass: a stream whose
+//                            list is not ascending and disjoint is MH_ERR_ARG
+//   spans_*_kernel           search records merged into spans (mh_dev_spans_from_hits): see "span lists" below
 //   histc_idx_kernel         one lane per (stream, chunk): counts the pairs as it decodes; a chunk that fails takes its own
 //                            counts back; <FIX>: the chunks that passed inside a stream that failed take theirs back
 //   histc_walk_kernel        index-free, one lane per stream: counts, and takes the stream's counts back when it fails
@@ -42,6 +45,8 @@
 //                a chunk that passed).
 // The counters: a direct-mapped cache of (key -> u64) in the LDS the tables leave, 64-bit global atomics behind it into the
 // caller's 256, 65 536 or 1 << 24 counts.
+#include <type_traits>
+
 #include "mh_recode.h"
 #include "mh_batch_dev.hpp"
 #include "mh_each_dev.hpp"
@@ -176,6 +181,76 @@ template <bool DLDS, bool W> struct Enc {
     }
 };
 
+// the edit     (EDIT: include/mh.h, "EDITING BATCHES"; order 0/1 on both sides, no W / SEAM form.)  Inside its stream's spans
+//              a lane codes map[sym] for sym.  It keeps two contexts: ctx, the true symbol, feeds dec.next and roll, so the
+//              decoder's dependent chain is what it is without the edit; dctx, the edited symbol, feeds E.at, E.put and
+//              E.entry.  A lane seeks the first span that ends behind its first position by a binary search of the stream's
+//              list and walks the list with its symbol counter: spans ascend and are disjoint (recode_spans_kernel fails
+//              the streams whose list is not so before a lane reads it), so one step is one compare with the span's end and
+//              one with its begin, the map lookup predicated on the second.  The cursor keeps the span as 32-bit offsets from
+//              the position of the seek, saturated (a chunk has at most MH_CHUNK_MAX symbols and a walk at most
+//              MH_BATCH_WALK_MAX_BITS, so a lane's own offsets stay far below 2^32 - 1, which stands for "never").  No list
+//              (span_off null): one span over everything.  The map is 256 B of LDS behind the destination's image (Edit::map_lds; read from L2 when the
+//              source's tables leave no room).
+template <bool DLDS> __device__ __forceinline__ uint32_t map_at(const Dst &d, uint32_t lds_at) {
+    return lds_at + (DLDS ? (d.ctx_mask ? 65536u : 256u) : 0u);
+}
+template <bool EDIT> using Params = std::conditional_t<EDIT, EditParams, RecodeParams>;
+template <bool EDIT> struct Spans {
+    template <typename P> __device__ __forceinline__ Spans(const P &, unsigned char *, uint32_t) {}
+    __device__ __forceinline__ void seek(uint64_t, uint64_t) {}
+    __device__ __forceinline__ uint32_t edit(uint32_t sym, uint32_t) { return sym; }
+};
+template <> struct Spans<true> {
+    const unsigned long long *off, *sp;
+    const uint8_t *g, *l;
+    uint64_t r, rend, origin;
+    uint32_t b, e;                      // the span at r, as offsets from origin
+    bool lds;
+    __device__ __forceinline__ Spans(const EditParams &p, unsigned char *smem, uint32_t at)
+        : off(p.ed.span_off), sp(p.ed.spans), g(p.ed.map), l(smem + at), r(0), rend(0), origin(0), b(0u), e(~0u), lds(p.ed.map_lds != 0u) {
+        if (lds) {
+            for (uint32_t k = threadIdx.x; k < 256u; k += blockDim.x) smem[at + k] = g[k];
+            __syncthreads();
+        }
+    }
+    __device__ __forceinline__ uint32_t rel(uint64_t x) const {
+        return x <= origin ? 0u : (x - origin >= 0xFFFFFFFFull ? ~0u : uint32_t(x - origin));
+    }
+    __device__ __forceinline__ void load() {
+        if (r < rend) { b = rel(sp[2 * r]); e = rel(sp[2 * r + 1]); } else { b = e = ~0u; }
+    }
+    // the first span of stream i that ends behind pos
+    __device__ __forceinline__ void seek(uint64_t i, uint64_t pos) {
+        origin = pos;
+        if (!off) return;
+        uint64_t lo = off[i], hi = off[i + 1];
+        rend = hi;
+        while (lo < hi) {
+            const uint64_t mid = (lo + hi) >> 1;
+            if (sp[2 * mid + 1] > pos) hi = mid; else lo = mid + 1;
+        }
+        r = lo;
+        load();
+    }
+    // the symbol at origin + pos as the destination sees it; pos goes up by one from the seek (the next span ends behind its
+    // begin, which is not in front of this one's end: one step along the list is enough)
+    __device__ __forceinline__ uint32_t edit(uint32_t sym, uint32_t pos) {
+        if (pos >= e) { ++r; load(); }
+        if (pos >= b) sym = lds ? l[sym] : g[sym];
+        return sym;
+    }
+};
+// the destination's context as a chunk's lane starts: the entry's byte, edited when the position in front of the chunk lies
+// in a span (a stream's first chunk starts from prev0, which is no byte of the message).  The cursor's origin is that
+// position: symbol t of the chunk is at offset t + at0(c).
+template <bool EDIT> __device__ __forceinline__ uint32_t start_dctx(Spans<EDIT> &sp, const Chunk &c) {
+    if (!EDIT) return c.ctx;
+    sp.seek(c.i, c.first ? c.first - 1u : 0u);
+    return c.first ? sp.edit(c.ctx, 0u) : c.ctx;
+}
+__device__ __forceinline__ uint32_t at0(const Chunk &c) { return c.first ? 1u : 0u; }
+
 // ------------------------------------------------------------------------------------------------ the kernels that never decode
 // (they read the source batch and the outputs, mhr::RecodeIO, and neither model)
 
@@ -244,6 +319,133 @@ __global__ void recode_tail_kernel(RecodeIO p, const uint32_t *tail, const int *
     if (!(bytes & 3u)) return;
     const uint8_t *t = reinterpret_cast<const uint8_t *>(tail);
     for (uint64_t b = bytes & ~uint64_t(3); b < bytes; ++b) p.out[b] = t[b & 3u];
+}
+
+// ------------------------------------------------------------------------------------------------ span lists
+
+// The span lists of an edit, in front of the length pass: span_off as any offsets (else BATCH_STATUS_ARG and the call stops);
+// span r of stream i must have begin < end and must not begin in front of the end of the stream's span before it, else the
+// stream's verdict is MH_ERR_ARG and no lane reads its list.  One grid-stride pass over the spans.
+__global__ __launch_bounds__(256) void recode_spans_kernel(EditParams p, int *status, int *stop) {
+    if (stopped(stop)) return;
+    const unsigned long long *off = p.ed.span_off, *sp = p.ed.spans;
+    const uint64_t n = p.s.b.n, total = off[n], stride = uint64_t(gridDim.x) * blockDim.x;
+    for (uint64_t i = gtid(); i <= n; i += stride)
+        if (mhb::offsets_bad(off, n, total, i)) { fail(status, BATCH_STATUS_ARG); atomicExch(stop, 1); }
+    if (!n) return;
+    for (uint64_t r = gtid(); r < total; r += stride) {
+        uint64_t lo = 0, hi = n - 1;                                  // the stream of span r: the last i < n with off[i] <= r
+        while (lo < hi) {
+            const uint64_t mid = (lo + hi + 1) >> 1;
+            if (off[mid] <= r) lo = mid; else hi = mid - 1;
+        }
+        const unsigned long long b = sp[2 * r], e = sp[2 * r + 1];
+        if (b >= e || (r > off[lo] && sp[2 * r - 1] > b)) stream_fail(p.s.b, status, lo, MH_ERR_ARG, BATCH_STATUS_ARG);
+    }
+}
+
+// Spans from search records (include/mh.h, "EDITING BATCHES").  The records of a stream ascend by end, not by begin: with
+// M(r) the least begin of the stream's records r' >= r, records r - 1 and r lie in different spans exactly when
+// end(r - 1) < M(r), and a span is (M(its first record), end(its last record)).  M is a reverse min-scan per stream:
+//   spans_tile_kernel    tiles of SPAN_TILE records: the scan inside the tile; the tile's first and last stream and the scan
+//                        value of its first record
+//   spans_carry_kernel   one lane, from the last tile to the first: the least begin behind each tile in the tile's last stream
+//   spans_mark_kernel    M complete; 1 for a record that starts a span (scanned next: the record's span number)
+//   spans_emit_kernel    a span's first record writes its begin, its last record its end; stream i's span_off
+// A total over hit_cap stops the call in spans_tile_kernel's front with MHK_STATUS_CAPACITY and span_off zeroed.  A record
+// whose stream is not below n_streams: BATCH_STATUS_ARG and the call stops.
+struct SpanParams {
+    const unsigned long long *hit_off, *hits;
+    uint64_t cap, n;
+    unsigned long long *span_off, *spans;
+    unsigned long long *mn, *num, *tile;      // mhr::SpanLayout
+};
+constexpr unsigned long long SPAN_NONE = ~0ull;
+
+__global__ __launch_bounds__(256) void spans_front_kernel(SpanParams p, int *status, int *stop) {
+    const uint64_t i = gtid();
+    if (i > p.n) return;
+    p.span_off[i] = 0;
+    if (i == p.n && p.hit_off[p.n] > p.cap) { fail(status, mhk::MHK_STATUS_CAPACITY); atomicExch(stop, 1); }
+    if (mhb::offsets_bad(p.hit_off, p.n, p.hit_off[p.n], i)) { fail(status, BATCH_STATUS_ARG); atomicExch(stop, 1); }
+}
+
+__global__ __launch_bounds__(SPAN_TILE) void spans_tile_kernel(SpanParams p, int *status, int *stop) {
+    __shared__ unsigned long long ss[SPAN_TILE], sv[SPAN_TILE];
+    if (stopped(stop)) return;
+    const uint64_t total = p.hit_off[p.n];
+    const uint64_t base = uint64_t(blockIdx.x) * SPAN_TILE, r = base + threadIdx.x;
+    if (base >= total) return;
+    // (behind the last record: a stream of its own that no record shares)
+    unsigned long long s = SPAN_NONE, v = SPAN_NONE;
+    if (r < total) {
+        s = p.hits[3 * r];
+        v = p.hits[3 * r + 1];
+        if (s >= p.n) { fail(status, BATCH_STATUS_ARG); atomicExch(stop, 1); }
+    }
+    ss[threadIdx.x] = s;
+    sv[threadIdx.x] = v;
+    __syncthreads();
+    for (uint32_t d = 1; d < SPAN_TILE; d <<= 1) {
+        const uint32_t k = threadIdx.x + d;
+        const bool take = k < SPAN_TILE && ss[k] == s;               // streams ascend: the same stream d behind, so all between
+        const unsigned long long x = take ? sv[k] : SPAN_NONE;
+        __syncthreads();
+        if (x < v) v = x;
+        sv[threadIdx.x] = v;
+        __syncthreads();
+    }
+    if (r < total) p.mn[r] = v;
+    if (threadIdx.x == 0) {
+        const uint64_t last = (total - base < SPAN_TILE ? total - base : SPAN_TILE) - 1;
+        unsigned long long *t = p.tile + 4 * uint64_t(blockIdx.x);
+        t[0] = s;
+        t[1] = ss[last];
+        t[2] = v;
+    }
+}
+
+__global__ void spans_carry_kernel(SpanParams p, const int *stop) {
+    if (stopped(stop)) return;
+    const uint64_t total = p.hit_off[p.n];
+    const uint64_t nt = (total + SPAN_TILE - 1) / SPAN_TILE;
+    unsigned long long carry = SPAN_NONE;                             // of tile k: the least begin behind it in its last stream
+    for (uint64_t k = nt; k-- > 0;) {
+        unsigned long long *t = p.tile + 4 * k;
+        t[3] = carry;
+        unsigned long long f = t[2];                                  // the first record's M
+        if (t[0] == t[1] && carry < f) f = carry;                     // one stream fills the tile: what lies behind counts
+        carry = (k && p.tile[4 * (k - 1) + 1] == t[0]) ? f : SPAN_NONE;
+    }
+}
+
+__global__ __launch_bounds__(256) void spans_mark_kernel(SpanParams p, const int *stop) {
+    if (stopped(stop)) return;
+    const uint64_t r = gtid();
+    if (r > p.cap + 1) return;
+    const uint64_t total = p.hit_off[p.n];
+    unsigned long long start = 0;
+    if (r < total) {
+        const unsigned long long *t = p.tile + 4 * (r / SPAN_TILE);
+        const unsigned long long s = p.hits[3 * r];
+        unsigned long long m = p.mn[r];
+        if (s == t[1] && t[3] < m) p.mn[r] = m = t[3];
+        start = r == p.hit_off[s] || p.hits[3 * (r - 1) + 2] < m;
+    }
+    p.num[r] = start;
+}
+
+__global__ __launch_bounds__(256) void spans_emit_kernel(SpanParams p, const int *stop) {
+    if (stopped(stop)) return;
+    const uint64_t r = gtid();
+    const uint64_t total = p.hit_off[p.n];
+    if (r <= p.n) p.span_off[r] = p.num[p.hit_off[r]];
+    if (r >= total) return;
+    const unsigned long long id = p.num[r], next = p.num[r + 1];      // (num has cap + 2 entries; num[total + 1] == num[total])
+    const bool start = next != id;
+    if (start) p.spans[2 * id] = p.mn[r];
+    const unsigned long long s = p.hits[3 * r];
+    if (r + 1 == p.hit_off[s + 1] || p.num[r + 2] != next) p.spans[2 * (start ? id : id - 1) + 1] = p.hits[3 * r + 2];
 }
 
 // ------------------------------------------------------------------------------------------------ histogram
@@ -408,14 +610,15 @@ __global__ __launch_bounds__((Dec<K, W>::NT)) void histc_walk_kernel(HistParams 
 
 // ------------------------------------------------------------------------------------------------ re-code
 
-template <Model K, bool DLDS, bool W>
-__global__ __launch_bounds__((Dec<K, W>::NT)) void recode_idx_len_kernel(RecodeParams p, uint64_t nwork, uint32_t lds_at, unsigned long long *cbits,
+template <Model K, bool DLDS, bool W, bool EDIT>
+__global__ __launch_bounds__((Dec<K, W>::NT)) void recode_idx_len_kernel(Params<EDIT> p, uint64_t nwork, uint32_t lds_at, unsigned long long *cbits,
                                                                        uint32_t *cdrop, uint32_t *chead, uint32_t *cclose, int *status,
                                                                        const int *stop) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     if (stopped(stop)) return;
     Dec<K, W> dec(p.s, smem);
     const Enc<DLDS, W> E(p.dst, smem, lds_at);
+    Spans<EDIT> sp(p, smem, map_at<DLDS>(p.dst, lds_at));
     for (uint64_t w = gtid(); w < nwork; w += uint64_t(gridDim.x) * blockDim.x) {
         Chunk c;
         if (!chunk_of<K, W>(p.s, w, c) || p.s.b.stream_status[c.i] == MH_ERR_ARG) continue;
@@ -426,14 +629,17 @@ __global__ __launch_bounds__((Dec<K, W>::NT)) void recode_idx_len_kernel(RecodeP
         bc.init(src, bit0 + c.start);
         dec.stream(p.s, c.i);
         uint32_t ctx = c.ctx, used = 0, bits = 0, drops = 0;
+        uint32_t dctx = start_dctx<EDIT>(sp, c);
         bool bad = false;
         for (uint32_t t = 0; t < c.nsym && !bad; ++t) {
             const uint32_t sym = dec.next(p.s, src, bc, ctx, used, bad);
             if (bad) break;
             if (owns<SEAM<K, W>>(c, t)) {
-                const uint32_t l = E.len(E.at(ctx, sym));
+                const uint32_t dsym = sp.edit(sym, t + at0(c));
+                const uint32_t l = E.len(E.at(EDIT ? dctx : ctx, dsym));
                 bits += l;
                 drops += l == 0u;
+                dctx = dsym;
             }
             ctx = roll<W>(ctx, sym);
         }
@@ -484,14 +690,15 @@ __global__ __launch_bounds__(256) void recode_comb_kernel(RecodeParams p, uint64
     cbits[w] = v;
 }
 
-template <Model K, bool DLDS, bool W>
-__global__ __launch_bounds__((Dec<K, W>::NT)) void recode_idx_emit_kernel(RecodeParams p, uint64_t nwork, uint32_t lds_at,
+template <Model K, bool DLDS, bool W, bool EDIT>
+__global__ __launch_bounds__((Dec<K, W>::NT)) void recode_idx_emit_kernel(Params<EDIT> p, uint64_t nwork, uint32_t lds_at,
                                                                         const unsigned long long *cbase, const uint32_t *chead,
                                                                         const uint32_t *cclose, uint32_t *tail, const int *stop) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     if (stopped(stop)) return;
     Dec<K, W> dec(p.s, smem);
     const Enc<DLDS, W> E(p.dst, smem, lds_at);
+    Spans<EDIT> sp(p, smem, map_at<DLDS>(p.dst, lds_at));
     const uint64_t bytes = p.out_off[p.s.b.n];
     const uint64_t tail_w = (bytes & 3u) ? bytes >> 2 : ~uint64_t(0);
     const uint32_t cs = p.s.b.chunk_shift;
@@ -501,7 +708,8 @@ __global__ __launch_bounds__((Dec<K, W>::NT)) void recode_idx_emit_kernel(Recode
         const unsigned long long b0 = cbase[w];
         const uint64_t rel = b0 - cbase[(p.s.b.sym_off[c.i] >> cs) + c.i];          // relative to the stream's own payload
         const bool seam = SEAM<K, W> && c.first != 0u;                              // symbol 0 is the lane's in front
-        if (p.out_index) p.out_index[w] = E.entry(seam ? cclose[w - 1] : c.ctx, rel);
+        uint32_t dctx = start_dctx<EDIT>(sp, c);
+        if (p.out_index) p.out_index[w] = E.entry(seam ? cclose[w - 1] : (EDIT ? dctx : c.ctx), rel);
         if (!p.out) continue;
         if constexpr (!SEAM<K, W>) { if (cbase[w + 1] == b0) continue; }            // (SEAM: the lane's codes are not the chunk's)
         uint64_t bit0;
@@ -515,7 +723,11 @@ __global__ __launch_bounds__((Dec<K, W>::NT)) void recode_idx_emit_kernel(Recode
         bool bad = false;
         for (uint32_t t = 0; t < c.nsym && !bad; ++t) {            // (the stream passed: bad stays false)
             const uint32_t sym = dec.next(p.s, src, bc, ctx, used, bad);
-            if (owns<SEAM<K, W>>(c, t)) E.put(bw, E.at(ctx, sym), true);
+            if (owns<SEAM<K, W>>(c, t)) {
+                const uint32_t dsym = sp.edit(sym, t + at0(c));
+                E.put(bw, E.at(EDIT ? dctx : ctx, dsym), true);
+                dctx = dsym;
+            }
             ctx = roll<W>(ctx, sym);
         }
         if constexpr (SEAM<K, W>) {
@@ -530,12 +742,13 @@ __global__ __launch_bounds__((Dec<K, W>::NT)) void recode_idx_emit_kernel(Recode
 
 // EMIT = false: the stream's verdict, its symbols into sym_off[i] (scanned next), its dst bits and dropped symbols;
 // true: its codes from out_off[i] and its index entries
-template <Model K, bool DLDS, bool W, bool EMIT>
-__global__ __launch_bounds__((Dec<K, W>::NT)) void recode_walk_kernel(RecodeParams p, uint32_t lds_at, uint32_t *tail, int *status, const int *stop) {
+template <Model K, bool DLDS, bool W, bool EMIT, bool EDIT>
+__global__ __launch_bounds__((Dec<K, W>::NT)) void recode_walk_kernel(Params<EDIT> p, uint32_t lds_at, uint32_t *tail, int *status, const int *stop) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     if (stopped(stop)) return;
     Dec<K, W> dec(p.s, smem);
     const Enc<DLDS, W> E(p.dst, smem, lds_at);
+    Spans<EDIT> sp(p, smem, map_at<DLDS>(p.dst, lds_at));
     const uint64_t n = p.s.b.n;
     const uint64_t bytes = EMIT ? p.out_off[n] : 0;
     const uint64_t tail_w = (bytes & 3u) ? bytes >> 2 : ~uint64_t(0);
@@ -560,14 +773,18 @@ __global__ __launch_bounds__((Dec<K, W>::NT)) void recode_walk_kernel(RecodePara
         BitWriter bw;
         if (EMIT && p.out) bw.init(reinterpret_cast<uint32_t *>(p.out), tail, tail_w, uint64_t(p.out_off[i]) * 8u);
         uint32_t ctx = start_ctx<K, W>(p.s), used = 0;
+        uint32_t dctx = ctx;
+        sp.seek(i, 0);
         bool bad = false;
         uint64_t k = 0, bits = 0, drops = 0;
         // every code has at least one bit: at most nb steps (src/coding.cpp:124 — decode while bits remain)
         while (used < nb && !bad && k < count) {
-            if (EMIT && p.out_index && (k & ((uint64_t(1) << ocs) - 1u)) == 0) p.out_index[(a >> ocs) + i + (k >> ocs)] = E.entry(ctx, bits);
+            if (EMIT && p.out_index && (k & ((uint64_t(1) << ocs) - 1u)) == 0) p.out_index[(a >> ocs) + i + (k >> ocs)] = E.entry(EDIT ? dctx : ctx, bits);
             const uint32_t sym = dec.next(p.s, src, bc, ctx, used, bad);
             if (bad) break;
-            const uint32_t key = E.at(ctx, sym);
+            const uint32_t dsym = sp.edit(sym, uint32_t(k));
+            const uint32_t key = E.at(EDIT ? dctx : ctx, dsym);
+            dctx = dsym;
             uint32_t l;
             if (EMIT) {
                 l = E.put(bw, key, p.out != nullptr);
@@ -627,16 +844,23 @@ hipError_t launch_hist(const HistParams &p, void *d_ws, hipStream_t st) {
     return hipGetLastError();
 }
 
-template <Model K, bool DLDS, bool W>
-hipError_t launch_rc(const RecodeParams &p, size_t lds_tables, void *d_ws, hipStream_t st) {
+// EDIT: the map's 256 bytes of LDS lie behind everything the plain call lays out, which therefore stays where it is; when
+// they do not fit (a source whose tables fill the LDS) the lanes read the map from L2
+template <Model K, bool DLDS, bool W, bool EDIT = false>
+hipError_t launch_rc(Params<EDIT> p, size_t lds_tables, void *d_ws, hipStream_t st) {
+    static_assert(!(EDIT && W), "the edit has no order-2 form");
     constexpr int NT = Dec<K, W>::NT, PER_CU = Dec<K, W>::PER_CU;
-    const size_t lds = lds_tables + (DLDS ? (p.dst.ctx_mask ? 65536 : 256) : 0);
+    size_t lds = lds_tables + (DLDS ? (p.dst.ctx_mask ? 65536 : 256) : 0);
     const uint32_t lds_at = uint32_t(lds_tables);
+    if constexpr (EDIT) {
+        p.ed.map_lds = lds + 256 <= size_t(LDS_MAX) ? 1u : 0u;
+        if (p.ed.map_lds) lds += 256;
+    }
     if (K == Model::Shared) {
-        hipError_t attr = mhk::allow_lds(reinterpret_cast<const void *>(recode_idx_len_kernel<K, DLDS, W>), LDS_MAX);
-        if (attr == hipSuccess) attr = mhk::allow_lds(reinterpret_cast<const void *>(recode_idx_emit_kernel<K, DLDS, W>), LDS_MAX);
-        if (attr == hipSuccess) attr = mhk::allow_lds(reinterpret_cast<const void *>(recode_walk_kernel<K, DLDS, W, false>), LDS_MAX);
-        if (attr == hipSuccess) attr = mhk::allow_lds(reinterpret_cast<const void *>(recode_walk_kernel<K, DLDS, W, true>), LDS_MAX);
+        hipError_t attr = mhk::allow_lds(reinterpret_cast<const void *>(recode_idx_len_kernel<K, DLDS, W, EDIT>), LDS_MAX);
+        if (attr == hipSuccess) attr = mhk::allow_lds(reinterpret_cast<const void *>(recode_idx_emit_kernel<K, DLDS, W, EDIT>), LDS_MAX);
+        if (attr == hipSuccess) attr = mhk::allow_lds(reinterpret_cast<const void *>(recode_walk_kernel<K, DLDS, W, false, EDIT>), LDS_MAX);
+        if (attr == hipSuccess) attr = mhk::allow_lds(reinterpret_cast<const void *>(recode_walk_kernel<K, DLDS, W, true, EDIT>), LDS_MAX);
         if (attr != hipSuccess) return attr;
     }
     unsigned char *ws = static_cast<unsigned char *>(d_ws);
@@ -654,13 +878,16 @@ hipError_t launch_rc(const RecodeParams &p, size_t lds_tables, void *d_ws, hipSt
     if (e == hipSuccess && nw) e = hipMemsetAsync(ws + L.off_bits, 0, L.off_sums - L.off_bits, st);   // chunk bits, dropped counts, heads
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(recode_check_kernel, grid_threads(n + 1, 256), dim3(256), 0, st, p, status, stop);
+    if constexpr (EDIT) {
+        if (p.ed.span_off) hipLaunchKernelGGL(recode_spans_kernel, dim3(grid_for(uint64_t(1) << 40, 256, 8)), dim3(256), 0, st, p, status, stop);
+    }
     if (p.s.b.index) {
-        hipLaunchKernelGGL((recode_idx_len_kernel<K, DLDS, W>), dim3(grid_for(nw, NT, PER_CU)), dim3(NT), lds, st, p, nw, lds_at, cbits, cdrop,
+        hipLaunchKernelGGL((recode_idx_len_kernel<K, DLDS, W, EDIT>), dim3(grid_for(nw, NT, PER_CU)), dim3(NT), lds, st, p, nw, lds_at, cbits, cdrop,
                            chead, cclose, status, stop);
         hipLaunchKernelGGL((recode_comb_kernel<SEAM<K, W>>), grid_threads(nw + 1, 256), dim3(256), 0, st, p, nw, cbits, cdrop, chead, stop);
         if ((e = scan_exclusive(cbits, nw + 1, sums, stop, st)) != hipSuccess) return e;
     } else {
-        hipLaunchKernelGGL((recode_walk_kernel<K, DLDS, W, false>), dim3(grid_for(n + 1, NT, PER_CU)), dim3(NT), lds, st, p, lds_at, tail,
+        hipLaunchKernelGGL((recode_walk_kernel<K, DLDS, W, false, EDIT>), dim3(grid_for(n + 1, NT, PER_CU)), dim3(NT), lds, st, p, lds_at, tail,
                            status, stop);
         if ((e = scan_exclusive(p.s.b.sym_off, n + 1, sums, stop, st)) != hipSuccess) return e;
     }
@@ -670,10 +897,10 @@ hipError_t launch_rc(const RecodeParams &p, size_t lds_tables, void *d_ws, hipSt
     if (p.out) hipLaunchKernelGGL(recode_zero_kernel, dim3(grid_for(p.cap / 4 + 1, 256, 8)), dim3(256), 0, st, p, status, stop, tail);
     if (p.s.b.index) {
         if (p.out || p.out_index)
-            hipLaunchKernelGGL((recode_idx_emit_kernel<K, DLDS, W>), dim3(grid_for(nw, NT, PER_CU)), dim3(NT), lds, st, p, nw, lds_at, cbits,
+            hipLaunchKernelGGL((recode_idx_emit_kernel<K, DLDS, W, EDIT>), dim3(grid_for(nw, NT, PER_CU)), dim3(NT), lds, st, p, nw, lds_at, cbits,
                                chead, cclose, tail, stop);
     } else if (p.out || p.out_index) {
-        hipLaunchKernelGGL((recode_walk_kernel<K, DLDS, W, true>), dim3(grid_for(n + 1, NT, PER_CU)), dim3(NT), lds, st, p, lds_at, tail,
+        hipLaunchKernelGGL((recode_walk_kernel<K, DLDS, W, true, EDIT>), dim3(grid_for(n + 1, NT, PER_CU)), dim3(NT), lds, st, p, lds_at, tail,
                            status, stop);
     }
     if (p.out) hipLaunchKernelGGL(recode_tail_kernel, dim3(1), dim3(1), 0, st, p, tail, stop);
@@ -703,6 +930,38 @@ hipError_t launch_recode(const RecodeParams &p, Model model, void *d_ws, hipStre
     const size_t img = p.dst.ctx_mask ? 65536 : 256;
     return lds + img <= size_t(LDS_MAX) ? launch_rc<Model::Shared, true, false>(p, lds, d_ws, st)
                                         : launch_rc<Model::Shared, false, false>(p, lds, d_ws, st);
+}
+
+// the branches of launch_recode for order 0/1 on both sides, each with the edit
+hipError_t launch_recode_edit(const EditParams &p, Model model, void *d_ws, hipStream_t st) {
+    if (model == Model::Shared2 || p.dst.ctx_mask == 0xFFFFu) return hipErrorInvalidValue;
+    if (model == Model::Set)
+        return p.dst.ctx_mask ? launch_rc<Model::Set, false, false, true>(p, 0, d_ws, st) : launch_rc<Model::Set, true, false, true>(p, 0, d_ws, st);
+    const size_t lds = mhb::tables_lds(p.s.b);
+    if (lds > size_t(LDS_MAX)) return hipErrorInvalidValue;
+    const size_t img = p.dst.ctx_mask ? 65536 : 256;
+    return lds + img <= size_t(LDS_MAX) ? launch_rc<Model::Shared, true, false, true>(p, lds, d_ws, st)
+                                        : launch_rc<Model::Shared, false, false, true>(p, lds, d_ws, st);
+}
+
+hipError_t launch_spans_from_hits(const unsigned long long *hit_off, const unsigned long long *hits, uint64_t hit_cap, uint64_t n_streams,
+                                  unsigned long long *span_off, unsigned long long *spans, void *d_ws, hipStream_t st) {
+    unsigned char *ws = static_cast<unsigned char *>(d_ws);
+    const SpanLayout L = span_layout(hit_cap);
+    int *status = reinterpret_cast<int *>(ws), *stop = status + 1;
+    SpanParams p{hit_off, hits, hit_cap, n_streams, span_off, spans, reinterpret_cast<unsigned long long *>(ws + L.off_min),
+                 reinterpret_cast<unsigned long long *>(ws + L.off_num), reinterpret_cast<unsigned long long *>(ws + L.off_tile)};
+    auto *sums = reinterpret_cast<unsigned long long *>(ws + L.off_sums);
+    hipError_t e = hipMemsetAsync(ws, 0, 64, st);
+    if (e != hipSuccess) return e;
+    const uint64_t tiles = (hit_cap + SPAN_TILE - 1) / SPAN_TILE;
+    hipLaunchKernelGGL(spans_front_kernel, grid_threads(n_streams + 1, 256), dim3(256), 0, st, p, status, stop);
+    if (tiles) hipLaunchKernelGGL(spans_tile_kernel, dim3(uint32_t(tiles)), dim3(SPAN_TILE), 0, st, p, status, stop);
+    if (tiles) hipLaunchKernelGGL(spans_carry_kernel, dim3(1), dim3(1), 0, st, p, stop);
+    hipLaunchKernelGGL(spans_mark_kernel, grid_threads(hit_cap + 2, 256), dim3(256), 0, st, p, stop);
+    if ((e = scan_exclusive(p.num, hit_cap + 2, sums, stop, st)) != hipSuccess) return e;
+    hipLaunchKernelGGL(spans_emit_kernel, grid_threads((hit_cap > n_streams ? hit_cap : n_streams) + 1, 256), dim3(256), 0, st, p, stop);
+    return hipGetLastError();
 }
 
 }  // namespace mhr

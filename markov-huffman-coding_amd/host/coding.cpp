@@ -507,7 +507,57 @@ void i_coding_provider::crc(FILE* input_fd) {
 // --recode: the `.cm` file as a batch of one stream, coded again under `dst` on the device without writing its bytes
 // (mh_recode_batch).  The output is the file the reference writes for the original input with `-e` of dst's table.  With a
 // usable index sidecar the source is read through it and the output's own index is written beside the output.
-void i_coding_provider::recode(FILE* input_fd, FILE* output_fd, const i_coding_provider& dst, const std::string& out_index_path) {
+// The spans of a --redact: the hits of the patterns in the one stream (mh_find_batch / mh_find_dict_batch, index-free when
+// there is no index), uploaded as they came and merged on the device; spans = (begin, end) pairs.
+static void redact_spans(const mh_model* model, const redact_options& r, const uint8_t* payload, uint64_t pay_bytes, uint64_t nbits,
+                         const uint64_t* sym_off, const uint64_t* index, uint32_t chunk, uint64_t span_off[2], std::vector<uint64_t>& spans) {
+    std::string bytes;
+    std::vector<uint32_t> pat_off(1, 0);
+    for (const std::string& p : r.patterns) {
+        bytes += p;
+        pat_off.push_back((uint32_t)bytes.size());
+    }
+    mh_pattern_set* ps = nullptr;
+    mh_dict* dc = nullptr;
+    const uint32_t flags = r.fold ? MH_FIND_FOLD_ASCII : 0u;
+    if (r.dict) mh_or_die(mh_dict_create((const uint8_t*)bytes.data(), pat_off.data(), r.patterns.size(), flags, &dc), "--redact-file");
+    else mh_or_die(mh_pattern_set_create((const uint8_t*)bytes.data(), pat_off.data(), r.patterns.size(), flags, &ps), "--redact");
+    const uint64_t pay_off[2] = {0, pay_bytes};
+    auto search = [&](uint64_t* hit_off, uint64_t* hits, uint64_t cap) {
+        return r.dict ? mh_find_dict_batch(model, dc, payload, pay_off, &nbits, 1, MH_PREV0, sym_off, index, chunk, hit_off, hits, nullptr, cap, nullptr)
+                      : mh_find_batch(model, ps, payload, pay_off, &nbits, 1, MH_PREV0, sym_off, index, chunk, hit_off, hits, nullptr, cap, nullptr);
+    };
+    uint64_t hit_off[2] = {0, 0};
+    mh_or_die(search(hit_off, nullptr, 0), "redact (search)");
+    const uint64_t total = hit_off[1];
+    span_off[0] = span_off[1] = 0;
+    spans.clear();
+    if (total) {
+        std::vector<uint64_t> hits((size_t)total * 3);
+        mh_or_die(search(hit_off, hits.data(), total), "redact (search)");
+        void *d_ho = nullptr, *d_h = nullptr, *d_so = nullptr, *d_sp = nullptr, *d_ws = nullptr;
+        const size_t wsb = mh_dev_spans_from_hits_workspace(1, total);
+        mh_or_die(mh_dev_malloc(&d_ho, 16), "redact");
+        mh_or_die(mh_dev_malloc(&d_h, hits.size() * 8), "redact");
+        mh_or_die(mh_dev_malloc(&d_so, 16), "redact");
+        mh_or_die(mh_dev_malloc(&d_sp, (size_t)total * 16), "redact");
+        mh_or_die(mh_dev_malloc(&d_ws, wsb), "redact");
+        mh_or_die(mh_dev_upload(d_ho, hit_off, 16), "redact");
+        mh_or_die(mh_dev_upload(d_h, hits.data(), hits.size() * 8), "redact");
+        mh_or_die(mh_dev_spans_from_hits((const uint64_t*)d_ho, (const uint64_t*)d_h, total, 1, (uint64_t*)d_so, (uint64_t*)d_sp, d_ws, wsb, nullptr),
+                  "redact (spans)");
+        mh_or_die(mh_dev_status(d_ws, nullptr), "redact (spans)");
+        mh_or_die(mh_dev_download(span_off, d_so, 16), "redact");
+        spans.resize((size_t)span_off[1] * 2);
+        if (!spans.empty()) mh_or_die(mh_dev_download(spans.data(), d_sp, spans.size() * 8), "redact");
+        for (void* d : {d_ho, d_h, d_so, d_sp, d_ws}) mh_dev_free(d);
+    }
+    mh_pattern_set_free(ps);
+    mh_dict_free(dc);
+}
+
+void i_coding_provider::recode(FILE* input_fd, FILE* output_fd, const i_coding_provider& dst, const std::string& out_index_path,
+                               const redact_options* redact) {
     InputView in(input_fd, true);
     if (in.size == 0) mh_or_die(MH_ERR_CORRUPT, "recode");
     uint64_t nbits = 0;
@@ -535,6 +585,19 @@ void i_coding_provider::recode(FILE* input_fd, FILE* output_fd, const i_coding_p
     const size_t bound = mh_encode_batch_bound(dst.model(), (size_t)symbols, 1);
     OutputView out;
     out.open(output_fd, bound + 1);
+    if (redact) {
+        uint64_t span_off[2];
+        std::vector<uint64_t> spans;
+        redact_spans(model_, *redact, in.data + 1, pay_off[1], nbits, indexed ? sym_off : nullptr, indexed ? index.data() : nullptr, chunk, span_off,
+                     spans);
+        uint64_t masked = 0;
+        for (size_t k = 0; k < spans.size(); k += 2) masked += spans[k + 1] - spans[k];
+        eprintf("Masking %llu bytes in %llu spans with 0x%02X.\n", (unsigned long long)masked, (unsigned long long)span_off[1], redact->mask);
+        const std::vector<uint8_t> map(256, redact->mask);
+        mh_or_die(mh_recode_edit_batch(model_, dst.model(), in.data + 1, pay_off, &nbits, 1, MH_PREV0, sym_off, indexed ? index.data() : nullptr,
+                                       chunk, span_off, spans.data(), map.data(), out.data + 1, bound, out_off, &out_nbits,
+                                       indexed ? out_index.data() : nullptr, &dropped, nullptr), "recode (--redact)");
+    } else
     mh_or_die(mh_recode_batch(model_, dst.model(), in.data + 1, pay_off, &nbits, 1, MH_PREV0, sym_off, indexed ? index.data() : nullptr, chunk,
                               out.data + 1, bound, out_off, &out_nbits, indexed ? out_index.data() : nullptr, &dropped, nullptr), "recode");
     out.data[0] = mh_stream_header(dst.model(), out_nbits);

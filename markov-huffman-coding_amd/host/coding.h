@@ -44,6 +44,13 @@ struct tree_node {
 // Reads the stream from its current position to EOF.
 void construct_table(FILE* input_fd, int order, uint64_t* counts64);
 
+// --redact: what is searched for and what takes its place while the stream is coded again
+struct redact_options {
+    std::vector<std::string> patterns;
+    bool fold = false, dict = false;             // dict: the patterns of --redact-file, searched as a dictionary
+    uint8_t mask = 0x2A;
+};
+
 class i_coding_provider {
 public:
     virtual ~i_coding_provider();
@@ -64,7 +71,10 @@ public:
     void crc(FILE* input_fd);
     // --recode: the `.cm` on input_fd (coded under this model) coded again under `dst` without writing its bytes
     // (mh_recode_batch); with a usable index sidecar the indexed path, and the output's index goes to `out_index_path`
-    void recode(FILE* input_fd, FILE* output_fd, const i_coding_provider& dst, const std::string& out_index_path);
+    // redact: the occurrences of its patterns are searched in the compressed input, merged into spans on the device
+    // (mh_dev_spans_from_hits) and coded as the mask byte (mh_recode_edit_batch); the spans and bytes masked go to stderr
+    void recode(FILE* input_fd, FILE* output_fd, const i_coding_provider& dst, const std::string& out_index_path,
+                const redact_options* redact = nullptr);
     const mh_model* model() const { return model_; }
 
 protected:

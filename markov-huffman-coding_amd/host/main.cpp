@@ -17,6 +17,10 @@
 //                    decompressing (repeatable, 64 bytes in all; --find-fold folds ASCII case; needs -x and --index)
 //   --find-file FILE the same for a dictionary: one pattern per line of FILE (split at LF, empty lines skipped, any other byte
 //                    kept; up to 65536 patterns of at most 255 bytes), searched in one pass; not together with --find
+//   --redact STRING  with --recode: the occurrences of STRING in the original input are found on the device (repeatable, the
+//                    limits of --find; --redact-fold folds ASCII case), merged into spans there, and the stream is coded again
+//                    with those bytes replaced by the --mask byte (default 0x2A); the bytes are never written.  The new
+//                    table may be the old one.  --redact-file FILE: one pattern per line, the limits of --find-file.
 //   --crc            with -x: print `crc32 length` of the original input (CRC-32 as zlib computes it, %08x, and the byte
 //                    count), taken on the device without decompressing; with --index the indexed path
 #include <errno.h>
@@ -54,6 +58,10 @@ static void print_help() {
     eprintf("\t               decompressing it, as `%%08x %%llu`; with --index the indexed path; no output file is written\n");
     eprintf("\t--recode table with -x, -e and -o: write the stream coded again under `table` (the bytes are never written);\n");
     eprintf("\t               with --index the output's index goes to <output>.idx\n");
+    eprintf("\t--redact string  with --recode: every occurrence of the string is replaced by the --mask byte while the stream is coded\n");
+    eprintf("\t               again (repeatable, 64 bytes in all; --redact-fold: ASCII letters match either case); `table` may be the -e table\n");
+    eprintf("\t--redact-file f  the same with one pattern per line of `f`, as --find-file; not together with --redact\n");
+    eprintf("\t--mask byte    the byte that takes the place of redacted bytes: decimal or 0x.., 0 to 255 (default 0x2A)\n");
 }
 
 struct options {
@@ -73,6 +81,10 @@ struct options {
     const char* find_file = nullptr;                              // --find-file: the patterns are its lines, searched as a dictionary
     const char* recode_table = nullptr;                           // --recode: the table the stream is coded again under
     bool crc = false;                                             // --crc: print the digest of the original input
+    std::vector<std::string> redacts;                             // one per --redact
+    const char* redact_file = nullptr;                            // --redact-file: the patterns are its lines
+    bool redact_fold = false, mask_given = false;
+    int mask = 0x2A;                                              // --mask: what a redacted byte becomes
 };
 
 // "B:E" with decimal B <= E; anything else is an error
@@ -134,6 +146,21 @@ static options parse(int argc, char* argv[]) {
             else if (!strcmp(a, "--find-fold")) o.find_fold = true;
             else if (!strcmp(a, "--recode")) o.recode_table = need(a);
             else if (!strcmp(a, "--crc")) o.crc = true;
+            else if (!strcmp(a, "--redact")) o.redacts.push_back(need(a));
+            else if (!strcmp(a, "--redact-file")) o.redact_file = need(a);
+            else if (!strcmp(a, "--redact-fold")) o.redact_fold = true;
+            else if (!strcmp(a, "--mask")) {
+                const char* v = need(a);
+                char* end = nullptr;
+                errno = 0;
+                const unsigned long n = strtoul(v, &end, 0);       // decimal or 0x..
+                if (!*v || *end || errno || v[0] == '-' || n > 255) {
+                    eprintf("Error: --mask takes a byte value, 0 to 255.\n");
+                    exit(1);
+                }
+                o.mask = (int)n;
+                o.mask_given = true;
+            }
             else eprintf("Warning: Unknown option %s.\n", a);
             continue;
         }
@@ -174,6 +201,48 @@ static FILE* open_or_die(const char* path, const char* mode, const char* what) {
     return f;
 }
 
+// the patterns of --find-file / --redact-file: the lines of the file, split at LF, empty lines skipped
+static void load_patterns(const char* path, const char* flag, std::vector<std::string>& out) {
+    FILE* f = fopen(path, "rb");
+    if (!f) {
+        eprintf("Error: cannot open the %s %s.\n", flag, path);
+        exit(1);
+    }
+    std::string line;
+    for (int c; (c = fgetc(f)) != EOF || !line.empty();) {
+        if (c != '\n' && c != EOF) { line.push_back((char)c); continue; }
+        if (!line.empty()) out.push_back(line);
+        line.clear();
+        if (c == EOF) break;
+    }
+    fclose(f);
+    if (out.empty()) {
+        eprintf("Error: the %s %s holds no pattern.\n", flag, path);
+        exit(1);
+    }
+}
+
+// the limits of the --find / --redact strings (Shift-And) or of a --find-file / --redact-file (the dictionary)
+static void check_patterns(const std::vector<std::string>& pats, bool from_file, const char* flag, const char* file_flag) {
+    size_t total = 0;
+    for (const std::string& p : pats) total += p.size();
+    if (!from_file && total > MH_FIND_MAX_POSITIONS) {
+        eprintf("Error: the %s strings are %zu bytes in all; at most %d (%s takes more).\n", flag, total, MH_FIND_MAX_POSITIONS, file_flag);
+        exit(1);
+    }
+    if (from_file) {
+        for (const std::string& p : pats)
+            if (p.size() > MH_DICT_MAX_LEN) {
+                eprintf("Error: a line of the %s is %zu bytes; at most %u.\n", file_flag, p.size(), MH_DICT_MAX_LEN);
+                exit(1);
+            }
+        if (pats.size() > MH_DICT_MAX_PATTERNS) {
+            eprintf("Error: the %s holds %zu patterns; at most %u.\n", file_flag, pats.size(), MH_DICT_MAX_PATTERNS);
+            exit(1);
+        }
+    }
+}
+
 int main(int argc, char* argv[]) {
     if (argc < 2) {
         print_help();
@@ -196,23 +265,7 @@ int main(int argc, char* argv[]) {
             eprintf("Error: --find-file cannot be combined with --find.\n");
             exit(1);
         }
-        FILE* f = fopen(o.find_file, "rb");
-        if (!f) {
-            eprintf("Error: cannot open the --find-file %s.\n", o.find_file);
-            exit(1);
-        }
-        std::string line;
-        for (int c; (c = fgetc(f)) != EOF || !line.empty();) {
-            if (c != '\n' && c != EOF) { line.push_back((char)c); continue; }
-            if (!line.empty()) o.finds.push_back(line);
-            line.clear();
-            if (c == EOF) break;
-        }
-        fclose(f);
-        if (o.finds.empty()) {
-            eprintf("Error: the --find-file %s holds no pattern.\n", o.find_file);
-            exit(1);
-        }
+        load_patterns(o.find_file, "--find-file", o.finds);
     }
     if (o.find_fold && o.finds.empty()) {
         eprintf("Error: --find-fold needs --find.\n");
@@ -231,29 +284,12 @@ int main(int argc, char* argv[]) {
             eprintf("Error: --find cannot be combined with --range.\n");
             exit(1);
         }
-        size_t total = 0;
-        for (const std::string& p : o.finds) {
+        for (const std::string& p : o.finds)
             if (p.empty()) {
                 eprintf("Error: --find expects a non-empty string.\n");
                 exit(1);
             }
-            total += p.size();
-        }
-        if (!o.find_file && total > MH_FIND_MAX_POSITIONS) {
-            eprintf("Error: the --find strings are %zu bytes in all; at most %d (--find-file takes more).\n", total, MH_FIND_MAX_POSITIONS);
-            exit(1);
-        }
-        if (o.find_file) {
-            for (const std::string& p : o.finds)
-                if (p.size() > MH_DICT_MAX_LEN) {
-                    eprintf("Error: a line of the --find-file is %zu bytes; at most %u.\n", p.size(), MH_DICT_MAX_LEN);
-                    exit(1);
-                }
-            if (o.finds.size() > MH_DICT_MAX_PATTERNS) {
-                eprintf("Error: the --find-file holds %zu patterns; at most %u.\n", o.finds.size(), MH_DICT_MAX_PATTERNS);
-                exit(1);
-            }
-        }
+        check_patterns(o.finds, o.find_file != nullptr, "--find", "--find-file");
     }
 
     if (o.recode_table) {                                          // checked before anything is opened or a device is used
@@ -269,6 +305,27 @@ int main(int argc, char* argv[]) {
             eprintf("Error: --recode does not support --order2.\n");
             exit(1);
         }
+    }
+    const bool redact = !o.redacts.empty() || o.redact_file;
+    if (redact) {                                                  // the rules first, then the pattern file, then everything else
+        if (!o.recode_table) {
+            eprintf("Error: --redact needs --recode.\n");
+            exit(1);
+        }
+        if (!o.redacts.empty() && o.redact_file) {
+            eprintf("Error: --redact and --redact-file cannot be combined.\n");
+            exit(1);
+        }
+        for (const std::string& p : o.redacts)
+            if (p.empty()) {
+                eprintf("Error: --redact takes a non-empty string.\n");
+                exit(1);
+            }
+        if (o.redact_file) load_patterns(o.redact_file, "--redact-file", o.redacts);
+        check_patterns(o.redacts, o.redact_file != nullptr, "--redact", "--redact-file");
+    } else if (o.mask_given || o.redact_fold) {
+        eprintf("Error: --mask and --redact-fold need --redact or --redact-file.\n");
+        exit(1);
     }
 
     if (o.crc) {                                                   // checked before anything is opened or a device is used
@@ -404,7 +461,12 @@ int main(int argc, char* argv[]) {
         }
         i_coding_provider* dst = buffer.peek_bit() == 0 ? (i_coding_provider*)new huffman_table(buffer) : new markov_huffman_table(buffer);
         eprintf("Re-coding %s ===> %s...\n", o.input, o.output);
-        coder->recode(input_fd, output_fd, *dst, std::string(o.output) + ".idx");
+        redact_options ro;
+        ro.patterns = o.redacts;
+        ro.fold = o.redact_fold;
+        ro.dict = o.redact_file != nullptr;
+        ro.mask = (uint8_t)o.mask;
+        coder->recode(input_fd, output_fd, *dst, std::string(o.output) + ".idx", redact ? &ro : nullptr);
         delete dst;
         delete coder;
         eprintf("Done.\n");
