@@ -1,7 +1,7 @@
 // mh_api_bank.cpp — the bank calls of the C ABI (include/mh.h, "BANKS OF SHARED MODELS"): selection (kernels: mh_bank.hip), the set
 // view over a bank, training (sort and gather in mh_bank.hip; histograms, trees and the set itself through the existing batch,
 // model and set builders, so the reference's tie-breaking keeps one copy) and the host-buffer forms.
-#include "mh_api_internal.hpp"
+#include "mh_api_reader.hpp"
 #include "mh_bank.h"
 
 #include <memory>
@@ -344,12 +344,6 @@ int mh_encode_bank(const mh_model_set *bank, const uint8_t *data, const uint64_t
 }
 
 namespace {
-struct GrowBank { std::vector<uint8_t> v; };
-uint8_t *grow_bank(void *ctx, size_t n) {
-    GrowBank *g = static_cast<GrowBank *>(ctx);
-    g->v.resize(n ? n : 1);
-    return g->v.data();
-}
 // entry k of a bank as a host-usable model, parsed from the bank's table file (index-free streams over the walk cap)
 int bank_entry_model(const mh_model_set *bank, uint32_t k, mh_model **m) {
     const size_t cap = mh_model_set_tables_bound(bank), wsb = mh_dev_model_set_tables_workspace(bank), K = size_t(bank->d.n);
@@ -372,24 +366,18 @@ int bank_entry_model(const mh_model_set *bank, uint32_t k, mh_model **m) {
 int mh_decode_bank(const mh_model_set *bank, const uint32_t *choice, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits,
                    size_t n_streams, uint8_t prev0, uint8_t *out, size_t out_cap, uint64_t *sym_off, const uint64_t *index, uint32_t chunk_symbols,
                    int32_t *stream_status) {
-    if (!bank_ok(bank) || (!choice && n_streams) || !pay_off || (!nbits && n_streams) || !sym_off || (!out && out_cap)) return MH_ERR_ARG;
-    if (index && chunk_shift_of(chunk_symbols) < 0) return MH_ERR_ARG;
-    if (!offsets_ok(pay_off, n_streams)) return MH_ERR_ARG;
-    const uint64_t pay_total = pay_off[n_streams];
-    if (!payload && pay_total) return MH_ERR_ARG;
+    if (!bank_ok(bank) || (!choice && n_streams) || !sym_off || (!out && out_cap)) return MH_ERR_ARG;
+    CodedBatch a{payload, pay_off, nbits, n_streams, 0, prev0, sym_off, 0, index, chunk_symbols};
+    int rc = host_batch_args(a, index != nullptr);
+    if (rc != MH_OK) return rc;
     for (size_t i = 0; i < n_streams; ++i)
-        if (nbits[i] > (pay_off[i + 1] - pay_off[i]) * 8 || choice[i] >= bank->d.n) return MH_ERR_ARG;
-    uint64_t sym_total = 0;
-    if (index) {
-        if (!offsets_ok(sym_off, n_streams)) return MH_ERR_ARG;
-        sym_total = sym_off[n_streams];
-        if (sym_total > out_cap) return MH_ERR_CAPACITY;
-    }
+        if (choice[i] >= bank->d.n) return MH_ERR_ARG;
+    if (a.sym_total > out_cap) return MH_ERR_CAPACITY;
     if (!have_device()) return MH_ERR_NO_DEVICE;
     const hipStream_t st = nullptr;
     const size_t n = n_streams;
     std::vector<size_t> long_streams;
-    uint64_t dcap = sym_total;
+    uint64_t dcap = a.sym_total;
     if (!index) {
         const uint64_t minl = uint64_t(bank->min_len > 0 ? bank->min_len : 1);
         uint64_t bound = 0;
@@ -399,76 +387,46 @@ int mh_decode_bank(const mh_model_set *bank, const uint32_t *choice, const uint8
         }
         dcap = std::min<uint64_t>(out_cap, bound);
     }
-    const size_t nidx = index ? size_t(mh_batch_index_capacity(sym_total, n, chunk_symbols)) : 0;
     const size_t wsb = mh_dev_decode_each_workspace(n);
-    DevBuf d_ch, d_pl, d_po, d_nb, d_out, d_so, d_idx, d_st, d_ws;
+    DevBatch db;
+    DevBuf d_ch, d_out, d_st, d_ws;
     HIP_TRY(d_ch.alloc(n * 4));
-    HIP_TRY(d_pl.alloc(size_t(pay_total) + 64));
-    HIP_TRY(d_po.alloc((n + 1) * 8));
-    HIP_TRY(d_nb.alloc(n * 8));
     HIP_TRY(d_out.alloc(size_t(dcap)));
-    HIP_TRY(d_so.alloc((n + 1) * 8));
-    HIP_TRY(d_idx.alloc(nidx * 8));
     HIP_TRY(d_st.alloc(n * 4));
     HIP_TRY(d_ws.alloc(wsb));
     if (n) HIP_TRY(hipMemcpy(d_ch.p, choice, n * 4, hipMemcpyHostToDevice));
-    if (pay_total) HIP_TRY(stage_h2d(d_pl.p, payload, size_t(pay_total), st));
-    HIP_TRY(hipMemcpy(d_po.p, pay_off, (n + 1) * 8, hipMemcpyHostToDevice));
-    if (n) HIP_TRY(hipMemcpy(d_nb.p, nbits, n * 8, hipMemcpyHostToDevice));
-    if (index) {
-        HIP_TRY(hipMemcpy(d_so.p, sym_off, (n + 1) * 8, hipMemcpyHostToDevice));
-        if (nidx) HIP_TRY(hipMemcpy(d_idx.p, index, nidx * 8, hipMemcpyHostToDevice));
-    }
+    if ((rc = db.upload(a, st)) != MH_OK) return rc;
     mh_model_set *v = nullptr;
-    int rc = mh_dev_model_set_pick(bank, d_ch.as<uint32_t>(), n, st, &v);
+    rc = mh_dev_model_set_pick(bank, d_ch.as<uint32_t>(), n, st, &v);
     if (rc != MH_OK) return rc;
     SetPtr own(v, mh_model_set_free);
-    rc = mh_dev_decode_each(v, d_pl.as<uint8_t>(), d_po.as<uint64_t>(), d_nb.as<uint64_t>(), n, pay_total, prev0, d_out.as<uint8_t>(), dcap,
-                            d_so.as<uint64_t>(), sym_total, index ? d_idx.as<uint64_t>() : nullptr, chunk_symbols, d_st.as<int32_t>(), d_ws.p, wsb, st);
+    rc = mh_dev_decode_each(v, db.d.payload, db.d.pay_off, db.d.nbits, n, a.pay_total, prev0, d_out.as<uint8_t>(), dcap, db.so.as<uint64_t>(),
+                            a.sym_total, db.d.index, chunk_symbols, d_st.as<int32_t>(), d_ws.p, wsb, st);
     if (rc != MH_OK) return rc;
     const int dev_rc = mh_dev_status(d_ws.p, st);
     std::vector<int32_t> sst(n);
     if (n) HIP_TRY(hipMemcpy(sst.data(), d_st.p, n * 4, hipMemcpyDeviceToHost));
     std::vector<uint64_t> dso(n + 1);
-    HIP_TRY(hipMemcpy(dso.data(), d_so.p, (n + 1) * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(dso.data(), db.so.p, (n + 1) * 8, hipMemcpyDeviceToHost));
     // the streams the device walk refused (over MH_BATCH_WALK_MAX_BITS) decode one by one under their entry's table
-    std::vector<GrowBank> extra(long_streams.size());
+    std::vector<std::vector<uint8_t>> extra(long_streams.size());
     std::vector<mh_model *> entry(bank->d.n, nullptr);
     for (size_t j = 0; j < long_streams.size(); ++j) {
         const size_t i = long_streams[j];
         int r = MH_OK;
         if (!entry[choice[i]]) r = bank_entry_model(bank, choice[i], &entry[choice[i]]);
         size_t got = 0;
-        if (r == MH_OK) r = mh_decode_to(entry[choice[i]], payload + pay_off[i], nbits[i], prev0, grow_bank, &extra[j], &got, nullptr, 0, 0);
-        extra[j].v.resize(r == MH_OK ? got : 0);
+        if (r == MH_OK) r = mh_decode_to(entry[choice[i]], payload + pay_off[i], nbits[i], prev0, grow_vec, &extra[j], &got, nullptr, 0, 0);
+        extra[j].resize(r == MH_OK ? got : 0);
         sst[i] = r;
     }
     for (mh_model *m : entry)
         if (m) mh_model_free(m);
-    int first = MH_OK;
-    for (size_t i = 0; i < n && first == MH_OK; ++i) first = sst[i];
-    if (first == MH_OK && dev_rc != MH_OK && dev_rc != MH_ERR_ARG) first = dev_rc;
+    const int first = first_failure(sst, {}, dev_rc);
     if (stream_status) std::copy(sst.begin(), sst.end(), stream_status);
-    if (long_streams.empty()) {
-        if (!index) std::copy(dso.begin(), dso.end(), sym_off);
-        if (dso[n] && dso[n] <= out_cap) HIP_TRY(stage_d2h(out, d_out.p, size_t(dso[n]), st));
-        return first;
-    }
-    std::vector<uint8_t> dev_bytes(static_cast<size_t>(dso[n]));
-    if (!dev_bytes.empty()) HIP_TRY(stage_d2h(dev_bytes.data(), d_out.p, dev_bytes.size(), st));
-    uint64_t pos = 0;
-    size_t j = 0;
-    for (size_t i = 0; i < n; ++i) {
-        const bool is_long = j < long_streams.size() && long_streams[j] == i;
-        const uint8_t *src = is_long ? extra[j].v.data() : dev_bytes.data() + dso[i];
-        const uint64_t len = is_long ? extra[j].v.size() : dso[i + 1] - dso[i];
-        if (is_long) ++j;
-        sym_off[i] = pos;
-        if (pos + len > out_cap) { if (first == MH_OK) first = MH_ERR_CAPACITY; pos += len; continue; }
-        if (len) std::memcpy(out + pos, src, size_t(len));
-        pos += len;
-    }
-    sym_off[n] = pos;
+    if (!long_streams.empty()) return splice_alone(dso, d_out.p, long_streams, extra, out, out_cap, sym_off, first, st);
+    if (!index) std::copy(dso.begin(), dso.end(), sym_off);
+    if (dso[n] && dso[n] <= out_cap) HIP_TRY(stage_d2h(out, d_out.p, size_t(dso[n]), st));
     return first;
 }
 

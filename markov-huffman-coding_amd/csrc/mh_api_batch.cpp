@@ -1,8 +1,7 @@
 // mh_api_batch.cpp — the batch calls of the C ABI (include/mh.h, "BATCHES OF INDEPENDENT STREAMS"): many small order-0/1
 // streams under one shared model in a few launches (kernels: mh_batch.hip), and their host-buffer forms.  The device decode
 // call of the order-2 batches (mh_api_batch_o2.cpp has the rest of that family) is the second entry of the one here.
-#include "mh_api_internal.hpp"
-#include "mh_batch.h"
+#include "mh_api_reader.hpp"
 #include "mh_each.h"
 
 using namespace mhapi;
@@ -10,28 +9,18 @@ using namespace mhapi;
 namespace {
 
 // mh_dev_decode_batch (o2 = false: an order-0/1 model) and mh_dev_decode_batch_o2 (an order-2 model)
-int dev_decode_batch(const mh_model *m, bool o2, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits, size_t n_streams,
-                     uint64_t pay_total, uint8_t prev0, uint8_t *d_out, uint64_t out_cap, uint64_t *d_sym_off, uint64_t sym_total,
-                     const uint64_t *d_index, uint32_t chunk_symbols, int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
-    if (!(o2 ? order2(m) : order01(m)) || (!d_payload && pay_total) || !d_pay_off || (!d_nbits && n_streams) || !d_sym_off ||
-        (!d_out && out_cap) || !d_ws)
-        return MH_ERR_ARG;
-    if (!aligned16(d_payload) || !aligned16(d_out) || !aligned16(d_ws)) return MH_ERR_ARG;
-    const int shift = d_index ? chunk_shift_of(chunk_symbols) : 0;
-    if (shift < 0) return MH_ERR_ARG;
-    const mhb::DecLayout L = mhb::dec_layout(n_streams);
-    if (ws_bytes < L.total) return MH_ERR_CAPACITY;
-    if (d_index && sym_total > out_cap) return MH_ERR_CAPACITY;
-    if (m->max_len > mh::MAX_CODE_BITS) return MH_ERR_CODE_TOO_LONG;
-    if (!m->d_prim || !have_device()) return MH_ERR_NO_DEVICE;
+int dev_decode_batch(const mh_model *m, bool o2, const CodedBatch &a, uint8_t *d_out, uint64_t out_cap, int32_t *d_stream_status, void *d_ws,
+                     size_t ws_bytes, void *stream) {
+    if (!(o2 ? order2(m) : order01(m)) || !a.sym_off || (!d_out && out_cap) || !aligned16(d_out)) return MH_ERR_ARG;
+    const mhb::DecLayout L = mhb::dec_layout(a.n);
     mhb::DecodeParams p{};
     mhb::DecBatchParams &b = p.b;
-    b.payload = d_payload; b.pay_off = d_pay_off; b.nbits = d_nbits; b.n = n_streams; b.pay_total = pay_total; b.prev0 = ctx_of_prev0(m, prev0);
+    const int rc = dev_batch_params(a, SymOff::Through, ctx_of_prev0(m, a.prev0), d_ws, ws_bytes, L.total, L.off_status, d_stream_status, b);
+    if (rc != MH_OK) return rc;
+    if (a.index && a.sym_total > out_cap) return MH_ERR_CAPACITY;
+    if (m->max_len > mh::MAX_CODE_BITS) return MH_ERR_CODE_TOO_LONG;
+    if (!m->d_prim || !have_device()) return MH_ERR_NO_DEVICE;
     b.out = d_out; b.out_cap = out_cap;
-    b.sym_off = reinterpret_cast<unsigned long long *>(d_sym_off); b.sym_total = sym_total;
-    b.index = d_index; b.chunk_shift = uint32_t(shift);
-    b.walk_max_bits = MH_BATCH_WALK_MAX_BITS;
-    b.stream_status = d_stream_status ? d_stream_status : reinterpret_cast<int *>(static_cast<unsigned char *>(d_ws) + L.off_status);
     fill_dec_tables(m, b);
     HIP_TRY(mhb::launch_decode(p, o2 ? mhb::Model::Shared2 : mhb::Model::Shared, d_ws, static_cast<hipStream_t>(stream)));
     return MH_OK;
@@ -120,15 +109,15 @@ size_t mh_dev_decode_batch_o2_workspace(size_t n_streams) { return mhb::dec_layo
 int mh_dev_decode_batch(const mh_model *m, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits, size_t n_streams,
                         uint64_t pay_total, uint8_t prev0, uint8_t *d_out, uint64_t out_cap, uint64_t *d_sym_off, uint64_t sym_total,
                         const uint64_t *d_index, uint32_t chunk_symbols, int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
-    return dev_decode_batch(m, false, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_out, out_cap, d_sym_off, sym_total, d_index,
-                            chunk_symbols, d_stream_status, d_ws, ws_bytes, stream);
+    return dev_decode_batch(m, false, {d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index, chunk_symbols}, d_out,
+                            out_cap, d_stream_status, d_ws, ws_bytes, stream);
 }
 
 int mh_dev_decode_batch_o2(const mh_model *m, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits, size_t n_streams,
                            uint64_t pay_total, uint8_t prev0, uint8_t *d_out, uint64_t out_cap, uint64_t *d_sym_off, uint64_t sym_total,
                            const uint64_t *d_index, uint32_t chunk_symbols, int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
-    return dev_decode_batch(m, true, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_out, out_cap, d_sym_off, sym_total, d_index,
-                            chunk_symbols, d_stream_status, d_ws, ws_bytes, stream);
+    return dev_decode_batch(m, true, {d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index, chunk_symbols}, d_out,
+                            out_cap, d_stream_status, d_ws, ws_bytes, stream);
 }
 
 }  // extern "C"
@@ -174,37 +163,20 @@ int mhapi::encode_batch_host(const mh_model *m, const uint8_t *data, const uint6
     return MH_OK;
 }
 
-namespace {
-struct GrowOut { std::vector<uint8_t> v; };
-uint8_t *grow_out(void *ctx, size_t n) {
-    GrowOut *g = static_cast<GrowOut *>(ctx);
-    g->v.resize(n ? n : 1);
-    return g->v.data();
-}
-}  // namespace
-
 int mhapi::decode_batch_host(const mh_model *m, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits, size_t n_streams,
                              uint8_t prev0, uint8_t *out, size_t out_cap, uint64_t *sym_off, const uint64_t *index, uint32_t chunk_symbols,
                              int32_t *stream_status, DevDecodeBatchFn dev) {
-    if (!m || !pay_off || (!nbits && n_streams) || !sym_off || (!out && out_cap)) return MH_ERR_ARG;
-    if (index && chunk_shift_of(chunk_symbols) < 0) return MH_ERR_ARG;
-    if (!offsets_ok(pay_off, n_streams)) return MH_ERR_ARG;
-    const uint64_t pay_total = pay_off[n_streams];
-    if (!payload && pay_total) return MH_ERR_ARG;
-    for (size_t i = 0; i < n_streams; ++i)
-        if (nbits[i] > (pay_off[i + 1] - pay_off[i]) * 8) return MH_ERR_ARG;
-    uint64_t sym_total = 0;
-    if (index) {
-        if (!offsets_ok(sym_off, n_streams)) return MH_ERR_ARG;
-        sym_total = sym_off[n_streams];
-        if (sym_total > out_cap) return MH_ERR_CAPACITY;
-    }
+    if (!m || !sym_off || (!out && out_cap)) return MH_ERR_ARG;
+    CodedBatch a{payload, pay_off, nbits, n_streams, 0, prev0, sym_off, 0, index, chunk_symbols};
+    int rc = host_batch_args(a, index != nullptr);
+    if (rc != MH_OK) return rc;
+    if (a.sym_total > out_cap) return MH_ERR_CAPACITY;
     if (!have_device()) return MH_ERR_NO_DEVICE;
     if (m->max_len > mh::MAX_CODE_BITS) return MH_ERR_CODE_TOO_LONG;
     const hipStream_t st = nullptr;
     // index-free: the output is at most nbits / (shortest code) bytes per stream; streams over the walk cap go through mh_decode
     std::vector<size_t> long_streams;
-    uint64_t dcap = sym_total;
+    uint64_t dcap = a.sym_total;
     if (!index) {
         const uint64_t minl = uint64_t(m->min_len > 0 ? m->min_len : 1);
         uint64_t bound = 0;
@@ -214,66 +186,35 @@ int mhapi::decode_batch_host(const mh_model *m, const uint8_t *payload, const ui
         }
         dcap = std::min<uint64_t>(out_cap, bound);
     }
-    const size_t nidx = index ? size_t(mh_batch_index_capacity(sym_total, n_streams, chunk_symbols)) : 0;
     const size_t wsb = mh_dev_decode_batch_workspace(n_streams);
-    DevBuf d_pl, d_po, d_nb, d_out, d_so, d_idx, d_st, d_ws;
-    HIP_TRY(d_pl.alloc(size_t(pay_total) + 64));
-    HIP_TRY(d_po.alloc((n_streams + 1) * 8));
-    HIP_TRY(d_nb.alloc(n_streams * 8));
+    DevBatch db;
+    DevBuf d_out, d_st, d_ws;
     HIP_TRY(d_out.alloc(size_t(dcap)));
-    HIP_TRY(d_so.alloc((n_streams + 1) * 8));
-    HIP_TRY(d_idx.alloc(nidx * 8));
     HIP_TRY(d_st.alloc(n_streams * 4));
     HIP_TRY(d_ws.alloc(wsb));
-    if (pay_total) HIP_TRY(stage_h2d(d_pl.p, payload, size_t(pay_total), st));
-    HIP_TRY(hipMemcpy(d_po.p, pay_off, (n_streams + 1) * 8, hipMemcpyHostToDevice));
-    if (n_streams) HIP_TRY(hipMemcpy(d_nb.p, nbits, n_streams * 8, hipMemcpyHostToDevice));
-    if (index) {
-        HIP_TRY(hipMemcpy(d_so.p, sym_off, (n_streams + 1) * 8, hipMemcpyHostToDevice));
-        if (nidx) HIP_TRY(hipMemcpy(d_idx.p, index, nidx * 8, hipMemcpyHostToDevice));
-    }
-    int rc = dev(m, d_pl.as<uint8_t>(), d_po.as<uint64_t>(), d_nb.as<uint64_t>(), n_streams, pay_total, prev0,
-                 d_out.as<uint8_t>(), dcap, d_so.as<uint64_t>(), sym_total, index ? d_idx.as<uint64_t>() : nullptr,
-                 chunk_symbols, d_st.as<int32_t>(), d_ws.p, wsb, st);
+    if ((rc = db.upload(a, st)) != MH_OK) return rc;
+    rc = dev(m, db.d.payload, db.d.pay_off, db.d.nbits, n_streams, a.pay_total, prev0, d_out.as<uint8_t>(), dcap, db.so.as<uint64_t>(), a.sym_total,
+             db.d.index, chunk_symbols, d_st.as<int32_t>(), d_ws.p, wsb, st);
     if (rc != MH_OK) return rc;
     const int dev_rc = mh_dev_status(d_ws.p, st);
     std::vector<int32_t> sst(n_streams);
     if (n_streams) HIP_TRY(hipMemcpy(sst.data(), d_st.p, n_streams * 4, hipMemcpyDeviceToHost));
     std::vector<uint64_t> dso(n_streams + 1);
-    HIP_TRY(hipMemcpy(dso.data(), d_so.p, (n_streams + 1) * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(dso.data(), db.so.p, (n_streams + 1) * 8, hipMemcpyDeviceToHost));
     // the streams the device walk refused (over MH_BATCH_WALK_MAX_BITS) decode one by one; their bytes go in between
-    std::vector<GrowOut> extra(long_streams.size());
+    std::vector<std::vector<uint8_t>> extra(long_streams.size());
     for (size_t k = 0; k < long_streams.size(); ++k) {
         const size_t i = long_streams[k];
         size_t nb = 0;
-        const int r = mh_decode_to(m, payload + pay_off[i], nbits[i], prev0, grow_out, &extra[k], &nb, nullptr, 0, 0);
-        extra[k].v.resize(nb);
+        const int r = mh_decode_to(m, payload + pay_off[i], nbits[i], prev0, grow_vec, &extra[k], &nb, nullptr, 0, 0);
+        extra[k].resize(nb);
         sst[i] = r;
     }
-    int first = MH_OK;
-    for (size_t i = 0; i < n_streams && first == MH_OK; ++i) first = sst[i];
-    if (first == MH_OK && dev_rc != MH_OK && dev_rc != MH_ERR_ARG) first = dev_rc;
+    const int first = first_failure(sst, {}, dev_rc);
     if (stream_status) std::copy(sst.begin(), sst.end(), stream_status);
-    if (long_streams.empty()) {
-        std::copy(dso.begin(), dso.end(), sym_off);
-        if (dso[n_streams] && dso[n_streams] <= out_cap) HIP_TRY(stage_d2h(out, d_out.p, size_t(dso[n_streams]), st));   // (a failed stream's bytes are undefined, its neighbours' are not)
-        return first;
-    }
-    std::vector<uint8_t> dev_bytes(static_cast<size_t>(dso[n_streams]));
-    if (!dev_bytes.empty()) HIP_TRY(stage_d2h(dev_bytes.data(), d_out.p, dev_bytes.size(), st));
-    uint64_t pos = 0;
-    size_t k = 0;
-    for (size_t i = 0; i < n_streams; ++i) {
-        const bool is_long = k < long_streams.size() && long_streams[k] == i;
-        const uint8_t *src = is_long ? extra[k].v.data() : dev_bytes.data() + dso[i];
-        const uint64_t len = is_long ? extra[k].v.size() : dso[i + 1] - dso[i];
-        if (is_long) ++k;
-        sym_off[i] = pos;
-        if (pos + len > out_cap) { if (first == MH_OK) first = MH_ERR_CAPACITY; pos += len; continue; }
-        if (len) std::memcpy(out + pos, src, size_t(len));
-        pos += len;
-    }
-    sym_off[n_streams] = pos;
+    if (!long_streams.empty()) return splice_alone(dso, d_out.p, long_streams, extra, out, out_cap, sym_off, first, st);
+    std::copy(dso.begin(), dso.end(), sym_off);
+    if (dso[n_streams] && dso[n_streams] <= out_cap) HIP_TRY(stage_d2h(out, d_out.p, size_t(dso[n_streams]), st));   // (a failed stream's bytes are undefined, its neighbours' are not)
     return first;
 }
 

@@ -1,8 +1,7 @@
 // mh_api_batch_range.cpp — lookups (stream, begin, end) into a batch of streams (include/mh.h, "RANDOM ACCESS INTO BATCHES"
 // and "RANDOM ACCESS INTO ORDER-2 STREAMS"): the device calls under one shared model of any order or under a model set
 // (kernels: mh_range.hip), and the host-buffer forms that upload only the streams the lookups touch.
-#include "mh_api_internal.hpp"
-#include "mh_batch.h"
+#include "mh_api_reader.hpp"
 #include "mh_range.h"
 
 #include <memory>
@@ -34,12 +33,6 @@ struct Batch {
     const uint64_t *sym_off, *index;
     uint32_t chunk;
 };
-
-uint8_t *grow_vec(void *ctx, size_t n) {
-    auto *v = static_cast<std::vector<uint8_t> *>(ctx);
-    v->resize(n ? n : 1);
-    return v->data();
-}
 
 // A stream too large to batch: through the single-stream calls (indexed: mh_decode_ranges or mh_decode_ranges_o2 on its
 // slice, which uploads only the touched chunks; index-free: mh_decode of the whole stream).  js: its decodable lookups.
@@ -279,8 +272,8 @@ int prepare_lookups(const uint8_t *d_payload, const uint64_t *d_pay_off, const u
     if (!d_pay_off || (n_streams && (!d_payload || !d_nbits)) || !d_ws) return MH_ERR_ARG;
     if (n_lookups && (!d_lookups || !d_out_at || !d_lookup_status)) return MH_ERR_ARG;
     if ((!d_out && out_cap) || !aligned16(d_payload) || !aligned16(d_out) || !aligned16(d_ws)) return MH_ERR_ARG;
-    int shift = 0;
-    if (d_index && ((shift = chunk_shift_of(chunk_symbols)) < 0 || !d_sym_off)) return MH_ERR_ARG;
+    int shift;
+    if (!index_args_ok(d_index, chunk_symbols, d_sym_off, shift)) return MH_ERR_ARG;
     if (ws_bytes < range_layout(n_lookups).total) return MH_ERR_CAPACITY;
     p.payload = d_payload; p.pay_off = d_pay_off; p.nbits = d_nbits; p.n_streams = n_streams; p.prev0 = prev0;
     p.sym_off = d_sym_off; p.index = d_index; p.chunk_shift = uint32_t(shift);

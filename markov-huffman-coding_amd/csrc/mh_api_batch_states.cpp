@@ -2,7 +2,7 @@
 // "SEGMENT STATES OF INDEX-FREE ORDER-2 BATCHES"): states, then index or emit, for a batch of index-free streams under one
 // shared model of order 0/1, a model set or one shared order-2 model (kernels: mh_batch_states.hip), and the host forms
 // that build a whole batch's index.
-#include "mh_api_internal.hpp"
+#include "mh_api_reader.hpp"
 #include "mh_batch_states.h"
 
 using namespace mhapi;
@@ -12,8 +12,7 @@ namespace {
 // the arguments every device call takes; the model's part is filled by the callers
 int common(mhs::StParams &p, int kind, const void *model, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits,
            size_t n, uint64_t pay_total, uint8_t prev0, void *d_ws, size_t ws_bytes) {
-    if ((!d_payload && pay_total) || !d_pay_off || (!d_nbits && n) || !d_ws) return MH_ERR_ARG;
-    if (!aligned16(d_payload) || !aligned16(d_ws)) return MH_ERR_ARG;
+    if (!dev_batch_ptrs_ok(d_payload, pay_total, d_pay_off, d_nbits, n, d_ws)) return MH_ERR_ARG;
     if (ws_bytes < mh_dev_batch_states_workspace(n, pay_total)) return MH_ERR_CAPACITY;
     p = mhs::StParams{};
     p.payload = d_payload; p.pay_off = d_pay_off; p.nbits = d_nbits; p.n = n; p.pay_total = pay_total;
@@ -84,23 +83,19 @@ int index_host(const uint8_t *payload, const uint64_t *pay_off, const uint64_t *
     const hipStream_t st = nullptr;
     const uint64_t pay_total = pay_off[n];
     const size_t wsb = mh_dev_batch_states_workspace(n, pay_total);
-    DevBuf d_pl, d_po, d_nb, d_so, d_st, d_ws, d_idx;
-    HIP_TRY(d_pl.alloc(size_t(pay_total) + 64));
-    HIP_TRY(d_po.alloc((n + 1) * 8));
-    HIP_TRY(d_nb.alloc(n * 8));
-    HIP_TRY(d_so.alloc((n + 1) * 8));
+    DevBatch db;                                      // (index-free: its so is where the states call writes the lengths)
+    DevBuf d_st, d_ws, d_idx;
     HIP_TRY(d_st.alloc(n * 4));
     HIP_TRY(d_ws.alloc(wsb));
-    if (pay_total) HIP_TRY(stage_h2d(d_pl.p, payload, size_t(pay_total), st));
-    HIP_TRY(hipMemcpy(d_po.p, pay_off, (n + 1) * 8, hipMemcpyHostToDevice));
-    if (n) HIP_TRY(hipMemcpy(d_nb.p, nbits, n * 8, hipMemcpyHostToDevice));
-    int rc = states(d_pl.as<uint8_t>(), d_po.as<uint64_t>(), d_nb.as<uint64_t>(), pay_total, d_so.as<uint64_t>(), d_st.as<int32_t>(), d_ws.p, wsb);
+    int rc = db.upload({payload, pay_off, nbits, n, pay_total, prev0, nullptr, 0, nullptr, chunk}, st);
+    if (rc != MH_OK) return rc;
+    rc = states(db.d.payload, db.d.pay_off, db.d.nbits, pay_total, db.so.as<uint64_t>(), d_st.as<int32_t>(), d_ws.p, wsb);
     if (rc != MH_OK) return rc;
     std::vector<uint64_t> dso(n + 1);
-    HIP_TRY(hipMemcpy(dso.data(), d_so.p, (n + 1) * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(dso.data(), db.so.p, (n + 1) * 8, hipMemcpyDeviceToHost));
     const uint64_t dcap = mh_batch_index_capacity(dso[n], n, chunk);
     HIP_TRY(d_idx.alloc(size_t(dcap) * 8));
-    rc = dev_index(d_pl.as<uint8_t>(), d_po.as<uint64_t>(), d_nb.as<uint64_t>(), pay_total, d_idx.as<uint64_t>(), dcap, d_st.as<int32_t>(), d_ws.p, wsb);
+    rc = dev_index(db.d.payload, db.d.pay_off, db.d.nbits, pay_total, d_idx.as<uint64_t>(), dcap, d_st.as<int32_t>(), d_ws.p, wsb);
     if (rc != MH_OK) return rc;
     (void)mh_dev_status(d_ws.p, st);                  // (per-stream statuses below carry every error)
     std::vector<int32_t> sst(n);
@@ -308,11 +303,9 @@ int mh_dev_batch_states_stats(const void *d_ws, void *stream, uint32_t *repair_p
 
 static int host_args(const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits, size_t n, uint32_t chunk, const uint64_t *sym_off,
                      const uint64_t *index) {
-    if (!pay_off || (!nbits && n) || !sym_off || !index || chunk_shift_of(chunk) < 0) return MH_ERR_ARG;
-    if (!offsets_ok(pay_off, n) || (!payload && pay_off[n])) return MH_ERR_ARG;
-    for (size_t i = 0; i < n; ++i)
-        if (nbits[i] > (pay_off[i + 1] - pay_off[i]) * 8) return MH_ERR_ARG;
-    return MH_OK;
+    if (!sym_off || !index) return MH_ERR_ARG;         // both are outputs: the batch itself is index-free
+    CodedBatch a{payload, pay_off, nbits, n, 0, 0, nullptr, 0, nullptr, chunk};
+    return host_batch_args(a, true);
 }
 
 int mh_index_batch(const mh_model *m, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits, size_t n_streams, uint8_t prev0,

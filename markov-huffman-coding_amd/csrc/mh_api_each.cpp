@@ -1,7 +1,7 @@
 // mh_api_each.cpp — the per-stream-model calls of the C ABI (include/mh.h, "BATCHES OF STREAMS, ONE MODEL EACH"): model
 // sets trained on the device or built from host models and table files, their table files, encode and decode (kernels:
 // mh_each.hip), and the host-buffer forms that group a batch by device footprint.
-#include "mh_api_internal.hpp"
+#include "mh_api_reader.hpp"
 #include "mh_each.h"
 
 #include <memory>
@@ -330,23 +330,16 @@ size_t mh_dev_decode_each_workspace(size_t n_streams) { return mhb::dec_layout(n
 int mh_dev_decode_each(const mh_model_set *s, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits, size_t n_streams,
                        uint64_t pay_total, uint8_t prev0, uint8_t *d_out, uint64_t out_cap, uint64_t *d_sym_off, uint64_t sym_total,
                        const uint64_t *d_index, uint32_t chunk_symbols, int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
-    if (!s || n_streams != s->d.n || (!d_payload && pay_total) || !d_pay_off || (!d_nbits && n_streams) || !d_sym_off || (!d_out && out_cap) || !d_ws)
-        return MH_ERR_ARG;
-    if (!aligned16(d_payload) || !aligned16(d_out) || !aligned16(d_ws)) return MH_ERR_ARG;
-    const int shift = d_index ? chunk_shift_of(chunk_symbols) : 0;
-    if (shift < 0) return MH_ERR_ARG;
-    if (ws_bytes < mh_dev_decode_each_workspace(n_streams)) return MH_ERR_CAPACITY;
-    if (d_index && sym_total > out_cap) return MH_ERR_CAPACITY;
-    if (!have_device()) return MH_ERR_NO_DEVICE;
+    if (!s || n_streams != s->d.n || !d_sym_off || (!d_out && out_cap) || !aligned16(d_out)) return MH_ERR_ARG;
+    const CodedBatch a{d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index, chunk_symbols};
     const mhb::DecLayout L = mhb::dec_layout(n_streams);
     mhb::DecodeParams p{};
     mhb::DecBatchParams &b = p.b;
-    b.payload = d_payload; b.pay_off = d_pay_off; b.nbits = d_nbits; b.n = n_streams; b.pay_total = pay_total; b.prev0 = prev0;
+    const int rc = dev_batch_params(a, SymOff::Through, prev0, d_ws, ws_bytes, L.total, L.off_status, d_stream_status, b);
+    if (rc != MH_OK) return rc;
+    if (d_index && sym_total > out_cap) return MH_ERR_CAPACITY;
+    if (!have_device()) return MH_ERR_NO_DEVICE;
     b.out = d_out; b.out_cap = out_cap;
-    b.sym_off = reinterpret_cast<unsigned long long *>(d_sym_off); b.sym_total = sym_total;
-    b.index = d_index; b.chunk_shift = uint32_t(shift);
-    b.walk_max_bits = MH_BATCH_WALK_MAX_BITS;
-    b.stream_status = d_stream_status ? d_stream_status : reinterpret_cast<int *>(static_cast<unsigned char *>(d_ws) + L.off_status);
     p.set = s->d;
     HIP_TRY(mhb::launch_decode(p, mhb::Model::Set, d_ws, static_cast<hipStream_t>(stream)));
     return MH_OK;
@@ -513,13 +506,6 @@ int mh_compress_each(const uint8_t *data, const uint64_t *in_off, size_t n_strea
 }
 
 namespace {
-struct GrowBuf { std::vector<uint8_t> v; };
-uint8_t *grow_buf(void *ctx, size_t n) {
-    GrowBuf *g = static_cast<GrowBuf *>(ctx);
-    g->v.resize(n ? n : 1);
-    return g->v.data();
-}
-
 // streams [g0, g1) on the device; index-free streams over the walk cap are decoded by mh_decode with a host model.
 // Output bytes go to out + pos (index: the caller's sym_off), statuses to sst.
 int decompress_group(const uint8_t *tables, const uint64_t *tab_off, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits,
@@ -545,49 +531,43 @@ int decompress_group(const uint8_t *tables, const uint64_t *tab_off, const uint8
             else dcap += nbits[g0 + k] / minl;
         }
     }
-    const size_t nidx = index ? size_t(mh_batch_index_capacity(sym_total, n, chunk)) : 0;
-    const size_t wsb = mh_dev_decode_each_workspace(n);
-    DevBuf d_pl, d_po, d_nb, d_out, d_so, d_idx, d_st, d_ws;
-    HIP_TRY(d_pl.alloc(size_t(pay_total) + 64));
-    HIP_TRY(d_po.alloc((n + 1) * 8));
-    HIP_TRY(d_nb.alloc(n * 8));
-    HIP_TRY(d_out.alloc(size_t(dcap)));
-    HIP_TRY(d_so.alloc((n + 1) * 8));
-    HIP_TRY(d_idx.alloc(nidx * 8));
-    HIP_TRY(d_st.alloc(n * 4));
-    HIP_TRY(d_ws.alloc(wsb));
-    if (pay_total) HIP_TRY(stage_h2d(d_pl.p, payload + pay_off[g0], size_t(pay_total), st));
-    HIP_TRY(hipMemcpy(d_po.p, poff.data(), (n + 1) * 8, hipMemcpyHostToDevice));
-    if (n) HIP_TRY(hipMemcpy(d_nb.p, nbits + g0, n * 8, hipMemcpyHostToDevice));
+    // the group as a batch of its own: offsets re-based to it, its index slices moved to where its sym_off puts them
+    std::vector<uint64_t> idx;
     if (index) {
-        HIP_TRY(hipMemcpy(d_so.p, so.data(), (n + 1) * 8, hipMemcpyHostToDevice));
-        std::vector<uint64_t> idx(nidx, 0);
+        idx.assign(size_t(mh_batch_index_capacity(sym_total, n, chunk)), 0);
         for (size_t k = 0; k < n; ++k) {
             const uint64_t len = so[k + 1] - so[k], cnt = (len + chunk - 1) / chunk;
             const uint64_t to = mh_batch_index_base(so[k], k, chunk), from = mh_batch_index_base(sym_off[g0 + k], g0 + k, chunk);
             if (cnt) std::memcpy(idx.data() + to, index + from, size_t(cnt) * 8);
         }
-        if (nidx) HIP_TRY(hipMemcpy(d_idx.p, idx.data(), nidx * 8, hipMemcpyHostToDevice));
     }
-    rc = mh_dev_decode_each(s, d_pl.as<uint8_t>(), d_po.as<uint64_t>(), d_nb.as<uint64_t>(), n, pay_total, prev0, d_out.as<uint8_t>(), dcap,
-                            d_so.as<uint64_t>(), sym_total, index ? d_idx.as<uint64_t>() : nullptr, chunk, d_st.as<int32_t>(), d_ws.p, wsb, st);
+    const CodedBatch a{payload + pay_off[g0], poff.data(), nbits + g0, n, pay_total, prev0, so.data(), sym_total, index ? idx.data() : nullptr, chunk};
+    const size_t wsb = mh_dev_decode_each_workspace(n);
+    DevBatch db;
+    DevBuf d_out, d_st, d_ws;
+    HIP_TRY(d_out.alloc(size_t(dcap)));
+    HIP_TRY(d_st.alloc(n * 4));
+    HIP_TRY(d_ws.alloc(wsb));
+    if ((rc = db.upload(a, st)) != MH_OK) return rc;
+    rc = mh_dev_decode_each(s, db.d.payload, db.d.pay_off, db.d.nbits, n, pay_total, prev0, d_out.as<uint8_t>(), dcap, db.so.as<uint64_t>(), sym_total,
+                            db.d.index, chunk, d_st.as<int32_t>(), d_ws.p, wsb, st);
     if (rc != MH_OK) return rc;
     const int dev_rc = mh_dev_status(d_ws.p, st);
     std::vector<int32_t> g_st(n);
     if (n) HIP_TRY(hipMemcpy(g_st.data(), d_st.p, n * 4, hipMemcpyDeviceToHost));
     std::vector<uint64_t> dso(n + 1);
-    HIP_TRY(hipMemcpy(dso.data(), d_so.p, (n + 1) * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(dso.data(), db.so.p, (n + 1) * 8, hipMemcpyDeviceToHost));
     std::vector<uint8_t> dev_bytes(static_cast<size_t>(dso[n]));
     if (!dev_bytes.empty()) HIP_TRY(stage_d2h(dev_bytes.data(), d_out.p, dev_bytes.size(), st));
-    std::vector<GrowBuf> extra(long_streams.size());
+    std::vector<std::vector<uint8_t>> extra(long_streams.size());
     for (size_t j = 0; j < long_streams.size(); ++j) {             // over the walk cap: the stream's own model through mh_decode
         const size_t k = long_streams[j], i = g0 + k;
         mh_model *m = nullptr;
         int r = toff[k + 1] > toff[k] ? mh_model_from_table_bits(tables + tab_off[i], size_t(toff[k + 1] - toff[k]), &m) : MH_ERR_CORRUPT;
         size_t nb = 0;
-        if (r == MH_OK) r = mh_decode_to(m, payload + pay_off[i], nbits[i], prev0, grow_buf, &extra[j], &nb, nullptr, 0, 0);
+        if (r == MH_OK) r = mh_decode_to(m, payload + pay_off[i], nbits[i], prev0, grow_vec, &extra[j], &nb, nullptr, 0, 0);
         if (m) mh_model_free(m);
-        extra[j].v.resize(r == MH_OK ? nb : 0);
+        extra[j].resize(r == MH_OK ? nb : 0);
         g_st[k] = r;
     }
     if (dev_rc != MH_OK && dev_rc != MH_ERR_ARG && first == MH_OK) {
@@ -598,8 +578,8 @@ int decompress_group(const uint8_t *tables, const uint64_t *tab_off, const uint8
     size_t j = 0;
     for (size_t k = 0; k < n; ++k) {
         const bool is_long = j < long_streams.size() && long_streams[j] == k;
-        const uint8_t *src = is_long ? extra[j].v.data() : dev_bytes.data() + dso[k];
-        const uint64_t len = is_long ? extra[j].v.size() : dso[k + 1] - dso[k];
+        const uint8_t *src = is_long ? extra[j].data() : dev_bytes.data() + dso[k];
+        const uint64_t len = is_long ? extra[j].size() : dso[k + 1] - dso[k];
         if (is_long) ++j;
         sst[g0 + k] = g_st[k];
         if (g_st[k] != MH_OK && first == MH_OK) first = g_st[k];
@@ -616,16 +596,12 @@ int decompress_group(const uint8_t *tables, const uint64_t *tab_off, const uint8
 int mh_decompress_each(const uint8_t *tables, const uint64_t *tab_off, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits,
                        size_t n_streams, uint8_t prev0, uint8_t *out, size_t out_cap, uint64_t *sym_off, const uint64_t *index,
                        uint32_t chunk_symbols, int32_t *stream_status) {
-    if (!tab_off || !pay_off || (!nbits && n_streams) || !sym_off || (!out && out_cap)) return MH_ERR_ARG;
-    if (index && chunk_shift_of(chunk_symbols) < 0) return MH_ERR_ARG;
-    if (!offsets_ok(tab_off, n_streams) || !offsets_ok(pay_off, n_streams)) return MH_ERR_ARG;
-    if ((!tables && tab_off[n_streams]) || (!payload && pay_off[n_streams])) return MH_ERR_ARG;
-    for (size_t i = 0; i < n_streams; ++i)
-        if (nbits[i] > (pay_off[i + 1] - pay_off[i]) * 8) return MH_ERR_ARG;
-    if (index) {
-        if (!offsets_ok(sym_off, n_streams)) return MH_ERR_ARG;
-        if (sym_off[n_streams] > out_cap) return MH_ERR_CAPACITY;
-    }
+    if (!tab_off || !sym_off || (!out && out_cap)) return MH_ERR_ARG;
+    if (!offsets_ok(tab_off, n_streams) || (!tables && tab_off[n_streams])) return MH_ERR_ARG;
+    CodedBatch a{payload, pay_off, nbits, n_streams, 0, prev0, sym_off, 0, index, chunk_symbols};
+    const int arc = host_batch_args(a, index != nullptr);
+    if (arc != MH_OK) return arc;
+    if (a.sym_total > out_cap) return MH_ERR_CAPACITY;
     if (!have_device()) return MH_ERR_NO_DEVICE;
     const uint32_t chunk = index ? chunk_symbols : 0;
     const size_t budget = group_budget();

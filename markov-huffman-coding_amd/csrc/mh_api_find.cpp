@@ -2,8 +2,7 @@
 // SEARCH AND RE-CODING" and "DICTIONARY SEARCH IN BATCHES"): the pattern set (a host object: the Shift-And automaton of
 // mh_find.h), the device image of a dictionary (built in mh_dict_host.cpp), the device calls under one shared model of order
 // 0/1 or 2 or under a model set (kernels: mh_find.hip) and the host-buffer forms.  Every call is written once over a Matcher.
-#include "mh_api_internal.hpp"
-#include "mh_batch.h"
+#include "mh_api_reader.hpp"
 #include "mh_find.h"
 
 using namespace mhapi;
@@ -19,24 +18,13 @@ struct Matcher {
     bool null() const { return !ps && !dict; }
 };
 
-// the checks all device calls share, in the order of mh_dev_decode_batch, and the batch part of the parameters
-int prepare(const Matcher &mt, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits, size_t n_streams,
-            uint64_t pay_total, uint32_t ctx0, const uint64_t *d_sym_off, uint64_t sym_total, const uint64_t *d_index, uint32_t chunk_symbols,
-            uint64_t *d_hit_off, uint64_t *d_hits, uint32_t *d_hit_pattern, uint64_t hit_cap, int32_t *d_stream_status, void *d_ws,
-            size_t ws_bytes, mhf::FindParams &p) {
-    if (mt.null() || (!d_payload && pay_total) || !d_pay_off || (!d_nbits && n_streams) || !d_hit_off || !d_ws) return MH_ERR_ARG;
-    if (!aligned16(d_payload) || !aligned16(d_ws)) return MH_ERR_ARG;
-    int shift = 0;
-    if (d_index && ((shift = chunk_shift_of(chunk_symbols)) < 0 || !d_sym_off)) return MH_ERR_ARG;
-    const uint64_t W = d_index ? mhb::work_items(n_streams, sym_total, chunk_symbols) : 0;
-    const mhf::FindLayout L = mhf::find_layout(n_streams, W);
-    if (ws_bytes < L.total) return MH_ERR_CAPACITY;
-    p.b.payload = d_payload; p.b.pay_off = d_pay_off; p.b.nbits = d_nbits; p.b.n = n_streams; p.b.pay_total = pay_total; p.b.prev0 = ctx0;
-    p.b.sym_off = d_index ? reinterpret_cast<unsigned long long *>(const_cast<uint64_t *>(d_sym_off)) : nullptr;   // (read only)
-    p.b.sym_total = d_index ? sym_total : 0;
-    p.b.index = d_index; p.b.chunk_shift = uint32_t(shift);
-    p.b.walk_max_bits = MH_BATCH_WALK_MAX_BITS;
-    p.b.stream_status = d_stream_status ? d_stream_status : reinterpret_cast<int *>(static_cast<unsigned char *>(d_ws) + L.off_status);
+// the batch part of the parameters behind the shared checks (mh_api_reader.hpp), and the search's own outputs
+int prepare(const Matcher &mt, const CodedBatch &a, uint32_t ctx0, uint64_t *d_hit_off, uint64_t *d_hits, uint32_t *d_hit_pattern, uint64_t hit_cap,
+            int32_t *d_stream_status, void *d_ws, size_t ws_bytes, mhf::FindParams &p) {
+    if (mt.null() || !d_hit_off) return MH_ERR_ARG;
+    const mhf::FindLayout L = mhf::find_layout(a.n, work_items_of(a));
+    const int rc = dev_batch_params(a, SymOff::UnderIndex, ctx0, d_ws, ws_bytes, L.total, L.off_status, d_stream_status, p.b);
+    if (rc != MH_OK) return rc;
     if (mt.ps) { p.first = mt.ps->first; p.last = mt.ps->last; p.max_len = mt.ps->max_len; }
     p.hit_off = reinterpret_cast<unsigned long long *>(d_hit_off);
     p.hits = reinterpret_cast<unsigned long long *>(d_hits);
@@ -59,13 +47,10 @@ int run(const mhf::FindParams &p, const Matcher &mt, mhf::Model model, void *d_w
 
 // mh_dev_find_batch, mh_dev_find_batch_o2 and their dictionary forms behind their order checks: one shared model, its tables
 // as the model's batch decoder takes them
-int find_shared(const mh_model *m, mhf::Model model, const Matcher &mt, const uint8_t *d_payload, const uint64_t *d_pay_off,
-                const uint64_t *d_nbits, size_t n_streams, uint64_t pay_total, uint8_t prev0, const uint64_t *d_sym_off, uint64_t sym_total,
-                const uint64_t *d_index, uint32_t chunk_symbols, uint64_t *d_hit_off, uint64_t *d_hits, uint32_t *d_hit_pattern, uint64_t hit_cap,
-                int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
+int find_shared(const mh_model *m, mhf::Model model, const Matcher &mt, const CodedBatch &a, uint64_t *d_hit_off, uint64_t *d_hits,
+                uint32_t *d_hit_pattern, uint64_t hit_cap, int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
     mhf::FindParams p{};
-    const int rc = prepare(mt, d_payload, d_pay_off, d_nbits, n_streams, pay_total, ctx_of_prev0(m, prev0), d_sym_off, sym_total, d_index,
-                           chunk_symbols, d_hit_off, d_hits, d_hit_pattern, hit_cap, d_stream_status, d_ws, ws_bytes, p);
+    const int rc = prepare(mt, a, ctx_of_prev0(m, a.prev0), d_hit_off, d_hits, d_hit_pattern, hit_cap, d_stream_status, d_ws, ws_bytes, p);
     if (rc != MH_OK) return rc;
     if (m->max_len > mh::MAX_CODE_BITS) return MH_ERR_CODE_TOO_LONG;
     if (!m->d_prim || !have_device()) return MH_ERR_NO_DEVICE;
@@ -74,14 +59,11 @@ int find_shared(const mh_model *m, mhf::Model model, const Matcher &mt, const ui
 }
 
 // mh_dev_find_each and its dictionary form
-int find_each(const mh_model_set *s, const Matcher &mt, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits,
-              size_t n_streams, uint64_t pay_total, uint8_t prev0, const uint64_t *d_sym_off, uint64_t sym_total, const uint64_t *d_index,
-              uint32_t chunk_symbols, uint64_t *d_hit_off, uint64_t *d_hits, uint32_t *d_hit_pattern, uint64_t hit_cap,
-              int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
-    if (!s || n_streams != s->d.n) return MH_ERR_ARG;
+int find_each(const mh_model_set *s, const Matcher &mt, const CodedBatch &a, uint64_t *d_hit_off, uint64_t *d_hits, uint32_t *d_hit_pattern,
+              uint64_t hit_cap, int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
+    if (!s || a.n != s->d.n) return MH_ERR_ARG;
     mhf::FindParams p{};
-    const int rc = prepare(mt, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index, chunk_symbols, d_hit_off,
-                           d_hits, d_hit_pattern, hit_cap, d_stream_status, d_ws, ws_bytes, p);
+    const int rc = prepare(mt, a, a.prev0, d_hit_off, d_hits, d_hit_pattern, hit_cap, d_stream_status, d_ws, ws_bytes, p);
     if (rc != MH_OK) return rc;
     if (!have_device()) return MH_ERR_NO_DEVICE;
     p.set = s->d;
@@ -89,15 +71,10 @@ int find_each(const mh_model_set *s, const Matcher &mt, const uint8_t *d_payload
 }
 
 // the argument checks of the two host forms, in the order of mh_decode_batch
-int host_args(const mh_model *m, const Matcher &mt, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits, size_t n_streams,
-              const uint64_t *sym_off, const uint64_t *index, uint32_t chunk_symbols, const uint64_t *hit_off) {
-    if (mt.null() || !pay_off || (!nbits && n_streams) || !hit_off) return MH_ERR_ARG;
-    if (index && (chunk_shift_of(chunk_symbols) < 0 || !sym_off)) return MH_ERR_ARG;
-    if (!offsets_ok(pay_off, n_streams)) return MH_ERR_ARG;
-    if (!payload && pay_off[n_streams]) return MH_ERR_ARG;
-    for (size_t i = 0; i < n_streams; ++i)
-        if (nbits[i] > (pay_off[i + 1] - pay_off[i]) * 8) return MH_ERR_ARG;
-    if (index && !offsets_ok(sym_off, n_streams)) return MH_ERR_ARG;
+int host_args(const mh_model *m, const Matcher &mt, CodedBatch &a, const uint64_t *hit_off) {
+    if (mt.null() || !hit_off) return MH_ERR_ARG;
+    const int rc = host_batch_args(a, a.index != nullptr);
+    if (rc != MH_OK) return rc;
     if (!have_device()) return MH_ERR_NO_DEVICE;
     if (m->max_len > mh::MAX_CODE_BITS) return MH_ERR_CODE_TOO_LONG;
     return MH_OK;
@@ -106,49 +83,33 @@ int host_args(const mh_model *m, const Matcher &mt, const uint8_t *payload, cons
 // One host-form search on the device: search() uploads the batch, runs the device call of the model's order and brings back
 // the verdicts and hit_off; records() then brings the records the device kept to wherever the caller wants them.
 struct HostSearch {
-    DevBuf d_pl, d_po, d_nb, d_so, d_idx, d_ho, d_hits, d_pat, d_st, d_ws;
+    DevBatch db;
+    DevBuf d_ho, d_hits, d_pat, d_st, d_ws;
     std::vector<int32_t> sst;           // per-stream verdicts
     std::vector<uint64_t> hit_off;      // n + 1, as the device wrote them
     uint64_t cap = 0, nrec = 0;         // records asked for, records kept
     int dev_rc = MH_OK;
 
-    int search(const mh_model *m, const Matcher &mt, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits, size_t n_streams,
-               uint8_t prev0, const uint64_t *sym_off, const uint64_t *index, uint32_t chunk_symbols, bool want_hits, bool want_pattern,
-               uint64_t hit_cap) {
+    int search(const mh_model *m, const Matcher &mt, const CodedBatch &a, bool want_hits, bool want_pattern, uint64_t hit_cap) {
         const hipStream_t st = nullptr;
-        const uint64_t pay_total = pay_off[n_streams];
-        const uint64_t sym_total = index ? sym_off[n_streams] : 0;
-        const size_t nidx = index ? size_t(mh_batch_index_capacity(sym_total, n_streams, chunk_symbols)) : 0;
-        const size_t wsb = mh_dev_find_batch_workspace(n_streams, sym_total, index ? chunk_symbols : 0);
+        const size_t n = a.n, wsb = mh_dev_find_batch_workspace(n, a.sym_total, a.index ? a.chunk_symbols : 0);
         cap = want_hits ? hit_cap : 0;
-        HIP_TRY(d_pl.alloc(size_t(pay_total) + 64));
-        HIP_TRY(d_po.alloc((n_streams + 1) * 8));
-        HIP_TRY(d_nb.alloc(n_streams * 8));
-        HIP_TRY(d_so.alloc((n_streams + 1) * 8));
-        HIP_TRY(d_idx.alloc(nidx * 8));
-        HIP_TRY(d_ho.alloc((n_streams + 1) * 8));
+        HIP_TRY(d_ho.alloc((n + 1) * 8));
         HIP_TRY(d_hits.alloc(size_t(cap) * 24));
         HIP_TRY(d_pat.alloc(size_t(cap) * 4));
-        HIP_TRY(d_st.alloc(n_streams * 4));
+        HIP_TRY(d_st.alloc(n * 4));
         HIP_TRY(d_ws.alloc(wsb));
-        if (pay_total) HIP_TRY(stage_h2d(d_pl.p, payload, size_t(pay_total), st));
-        HIP_TRY(hipMemcpy(d_po.p, pay_off, (n_streams + 1) * 8, hipMemcpyHostToDevice));
-        if (n_streams) HIP_TRY(hipMemcpy(d_nb.p, nbits, n_streams * 8, hipMemcpyHostToDevice));
-        if (index) {
-            HIP_TRY(hipMemcpy(d_so.p, sym_off, (n_streams + 1) * 8, hipMemcpyHostToDevice));
-            if (nidx) HIP_TRY(hipMemcpy(d_idx.p, index, nidx * 8, hipMemcpyHostToDevice));
-        }
-        const int rc = find_shared(m, order2(m) ? mhf::Model::Shared2 : mhf::Model::Shared, mt, d_pl.as<uint8_t>(), d_po.as<uint64_t>(), d_nb.as<uint64_t>(), n_streams, pay_total, prev0,
-                                   index ? d_so.as<uint64_t>() : nullptr, sym_total, index ? d_idx.as<uint64_t>() : nullptr, chunk_symbols,
-                                   d_ho.as<uint64_t>(), want_hits ? d_hits.as<uint64_t>() : nullptr, want_pattern ? d_pat.as<uint32_t>() : nullptr,
-                                   cap, d_st.as<int32_t>(), d_ws.p, wsb, st);
+        int rc = db.upload(a, st);
+        if (rc != MH_OK) return rc;
+        rc = find_shared(m, order2(m) ? mhf::Model::Shared2 : mhf::Model::Shared, mt, db.d, d_ho.as<uint64_t>(), want_hits ? d_hits.as<uint64_t>() : nullptr,
+                         want_pattern ? d_pat.as<uint32_t>() : nullptr, cap, d_st.as<int32_t>(), d_ws.p, wsb, st);
         if (rc != MH_OK) return rc;
         dev_rc = mh_dev_status(d_ws.p, st);
-        sst.resize(n_streams);
-        hit_off.resize(n_streams + 1);
-        if (n_streams) HIP_TRY(hipMemcpy(sst.data(), d_st.p, n_streams * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(hit_off.data(), d_ho.p, (n_streams + 1) * 8, hipMemcpyDeviceToHost));
-        nrec = std::min<uint64_t>(hit_off[n_streams], cap);
+        sst.resize(n);
+        hit_off.resize(n + 1);
+        if (n) HIP_TRY(hipMemcpy(sst.data(), d_st.p, n * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(hit_off.data(), d_ho.p, (n + 1) * 8, hipMemcpyDeviceToHost));
+        nrec = std::min<uint64_t>(hit_off[n], cap);
         return MH_OK;
     }
 
@@ -159,11 +120,9 @@ struct HostSearch {
         return MH_OK;
     }
 
-    // the call's result: the first failed stream's error, else the device's (MH_ERR_CAPACITY: the hits do not fit)
-    int finish(int32_t *stream_status) const {
-        int first = MH_OK;
-        for (size_t i = 0; i < sst.size() && first == MH_OK; ++i) first = sst[i];
-        if (first == MH_OK && dev_rc != MH_OK && dev_rc != MH_ERR_ARG) first = dev_rc;
+    // the call's result (idx_st: what indexing the batch first found); the device's MH_ERR_CAPACITY: the hits do not fit
+    int finish(const std::vector<int32_t> &idx_st, int32_t *stream_status) {
+        const int first = first_failure(sst, idx_st, dev_rc);
         if (stream_status) std::copy(sst.begin(), sst.end(), stream_status);
         return first;
     }
@@ -195,63 +154,50 @@ void host_find(const Matcher &mt, const uint8_t *data, size_t n, std::vector<Hit
 }
 
 // mh_find_batch and mh_find_dict_batch
-int find_batch_host(const mh_model *m, const Matcher &mt, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits,
-                  size_t n_streams, uint8_t prev0, const uint64_t *sym_off, const uint64_t *index, uint32_t chunk_symbols, uint64_t *hit_off,
-                  uint64_t *hits, uint32_t *hit_pattern, uint64_t hit_cap, int32_t *stream_status) {
+int find_batch_host(const mh_model *m, const Matcher &mt, CodedBatch a, uint64_t *hit_off, uint64_t *hits, uint32_t *hit_pattern, uint64_t hit_cap,
+                    int32_t *stream_status) {
     if (!order01(m)) return MH_ERR_ARG;
-    int rc = host_args(m, mt, payload, pay_off, nbits, n_streams, sym_off, index, chunk_symbols, hit_off);
+    int rc = host_args(m, mt, a, hit_off);
     if (rc != MH_OK) return rc;
-    // index-free with a stream over the walk cap: index the batch first (mh_index_batch never refuses a valid stream), then
-    // search it as an indexed batch; a stream the indexing fails keeps that error and has no symbols, so no hits
+    // index-free with a stream over the walk cap: index the batch first, then search it as an indexed batch; a stream the
+    // indexing fails has no symbols, so no hits
     std::vector<uint64_t> own_so, own_idx;
     std::vector<int32_t> idx_st;
-    bool over = false;
-    if (!index)
-        for (size_t i = 0; i < n_streams && !over; ++i) over = nbits[i] > MH_BATCH_WALK_MAX_BITS;
-    if (over) {
-        const uint64_t minl = uint64_t(m->min_len > 0 ? m->min_len : 1);
-        uint64_t bound = 0;
-        for (size_t i = 0; i < n_streams; ++i) bound += nbits[i] / minl;
-        chunk_symbols = MH_CHUNK_DEFAULT;
-        own_so.assign(n_streams + 1, 0);
-        own_idx.assign(size_t(mh_batch_index_capacity(bound, n_streams, chunk_symbols)), 0);
-        idx_st.assign(n_streams, MH_OK);
-        rc = mh_index_batch(m, payload, pay_off, nbits, n_streams, prev0, chunk_symbols, own_so.data(), own_idx.data(), own_idx.size(),
-                            idx_st.data());
-        if (rc == MH_ERR_HIP || rc == MH_ERR_NO_DEVICE || rc == MH_ERR_NOMEM || rc == MH_ERR_CAPACITY) return rc;
-        sym_off = own_so.data();
-        index = own_idx.data();
+    if (over_walk_cap(a)) {
+        own_so.assign(a.n + 1, 0);
+        if ((rc = index_first(m, a, false, own_so.data(), own_idx, idx_st)) != MH_OK) return rc;
     }
     HostSearch hs;
-    rc = hs.search(m, mt, payload, pay_off, nbits, n_streams, prev0, sym_off, index, chunk_symbols, hits != nullptr, hit_pattern != nullptr, hit_cap);
+    rc = hs.search(m, mt, a, hits != nullptr, hit_pattern != nullptr, hit_cap);
     if (rc != MH_OK) return rc;
     std::copy(hs.hit_off.begin(), hs.hit_off.end(), hit_off);
     if ((rc = hs.records(hits, hit_pattern)) != MH_OK) return rc;
-    for (size_t i = 0; i < idx_st.size(); ++i)
-        if (idx_st[i] != MH_OK) hs.sst[i] = idx_st[i];
-    return hs.finish(stream_status);
+    return hs.finish(idx_st, stream_status);
 }
 
 // mh_find_batch_o2 and mh_find_dict_batch_o2
-int find_batch_o2_host(const mh_model *m, const Matcher &mt, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits,
-                     size_t n_streams, uint8_t prev0, const uint64_t *sym_off, const uint64_t *index, uint32_t chunk_symbols, uint64_t *hit_off,
-                     uint64_t *hits, uint32_t *hit_pattern, uint64_t hit_cap, int32_t *stream_status) {
+int find_batch_o2_host(const mh_model *m, const Matcher &mt, CodedBatch a, uint64_t *hit_off, uint64_t *hits, uint32_t *hit_pattern, uint64_t hit_cap,
+                       int32_t *stream_status) {
     if (!order2(m)) return MH_ERR_ARG;
-    int rc = host_args(m, mt, payload, pay_off, nbits, n_streams, sym_off, index, chunk_symbols, hit_off);
+    int rc = host_args(m, mt, a, hit_off);
     if (rc != MH_OK) return rc;
     // index-free streams over the walk cap: the device call refuses them; each is decoded alone and searched by the
     // host-side automaton, its records spliced into place in stream order
+    const uint8_t *payload = a.payload;
+    const uint64_t *pay_off = a.pay_off, *nbits = a.nbits;
+    const size_t n_streams = a.n;
+    const uint8_t prev0 = a.prev0;
     std::vector<size_t> long_streams;
-    if (!index)
+    if (!a.index)
         for (size_t i = 0; i < n_streams; ++i)
             if (nbits[i] > MH_BATCH_WALK_MAX_BITS) long_streams.push_back(i);
     HostSearch hs;
-    rc = hs.search(m, mt, payload, pay_off, nbits, n_streams, prev0, sym_off, index, chunk_symbols, hits != nullptr, hit_pattern != nullptr, hit_cap);
+    rc = hs.search(m, mt, a, hits != nullptr, hit_pattern != nullptr, hit_cap);
     if (rc != MH_OK) return rc;
     if (long_streams.empty()) {
         std::copy(hs.hit_off.begin(), hs.hit_off.end(), hit_off);
         if ((rc = hs.records(hits, hit_pattern)) != MH_OK) return rc;
-        return hs.finish(stream_status);
+        return hs.finish({}, stream_status);
     }
     const uint64_t cap = hs.cap;
     const std::vector<uint64_t> &dho = hs.hit_off;
@@ -286,7 +232,7 @@ int find_batch_o2_host(const mh_model *m, const Matcher &mt, const uint8_t *payl
     }
     hit_off[n_streams] = r;
     hs.dev_rc = hits && r > cap ? MH_ERR_CAPACITY : MH_OK;
-    return hs.finish(stream_status);
+    return hs.finish({}, stream_status);
 }
 
 // the device image of a dictionary on the current device: mh_dict_create calls this through mhd::g_upload
@@ -366,8 +312,8 @@ int mh_dev_find_batch(const mh_model *m, const mh_pattern_set *ps, const uint8_t
                       uint32_t chunk_symbols, uint64_t *d_hit_off, uint64_t *d_hits, uint32_t *d_hit_pattern, uint64_t hit_cap,
                       int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
     if (!order01(m)) return MH_ERR_ARG;
-    return find_shared(m, mhf::Model::Shared, Matcher(ps), d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index,
-                       chunk_symbols, d_hit_off, d_hits, d_hit_pattern, hit_cap, d_stream_status, d_ws, ws_bytes, stream);
+    return find_shared(m, mhf::Model::Shared, Matcher(ps), {d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index, chunk_symbols},
+                       d_hit_off, d_hits, d_hit_pattern, hit_cap, d_stream_status, d_ws, ws_bytes, stream);
 }
 
 size_t mh_dev_find_batch_o2_workspace(size_t n_streams, uint64_t sym_total, uint32_t chunk_symbols) {
@@ -379,30 +325,30 @@ int mh_dev_find_batch_o2(const mh_model *m, const mh_pattern_set *ps, const uint
                          const uint64_t *d_index, uint32_t chunk_symbols, uint64_t *d_hit_off, uint64_t *d_hits, uint32_t *d_hit_pattern,
                          uint64_t hit_cap, int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
     if (!order2(m)) return MH_ERR_ARG;
-    return find_shared(m, mhf::Model::Shared2, Matcher(ps), d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index,
-                       chunk_symbols, d_hit_off, d_hits, d_hit_pattern, hit_cap, d_stream_status, d_ws, ws_bytes, stream);
+    return find_shared(m, mhf::Model::Shared2, Matcher(ps), {d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index, chunk_symbols},
+                       d_hit_off, d_hits, d_hit_pattern, hit_cap, d_stream_status, d_ws, ws_bytes, stream);
 }
 
 int mh_dev_find_each(const mh_model_set *s, const mh_pattern_set *ps, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits,
                      size_t n_streams, uint64_t pay_total, uint8_t prev0, const uint64_t *d_sym_off, uint64_t sym_total, const uint64_t *d_index,
                      uint32_t chunk_symbols, uint64_t *d_hit_off, uint64_t *d_hits, uint32_t *d_hit_pattern, uint64_t hit_cap,
                      int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
-    return find_each(s, Matcher(ps), d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index, chunk_symbols,
+    return find_each(s, Matcher(ps), {d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index, chunk_symbols},
                      d_hit_off, d_hits, d_hit_pattern, hit_cap, d_stream_status, d_ws, ws_bytes, stream);
 }
 
 int mh_find_batch(const mh_model *m, const mh_pattern_set *ps, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits,
                   size_t n_streams, uint8_t prev0, const uint64_t *sym_off, const uint64_t *index, uint32_t chunk_symbols, uint64_t *hit_off,
                   uint64_t *hits, uint32_t *hit_pattern, uint64_t hit_cap, int32_t *stream_status) {
-    return find_batch_host(m, Matcher(ps), payload, pay_off, nbits, n_streams, prev0, sym_off, index, chunk_symbols, hit_off, hits, hit_pattern,
-                           hit_cap, stream_status);
+    return find_batch_host(m, Matcher(ps), {payload, pay_off, nbits, n_streams, 0, prev0, sym_off, 0, index, chunk_symbols}, hit_off, hits,
+                           hit_pattern, hit_cap, stream_status);
 }
 
 int mh_find_batch_o2(const mh_model *m, const mh_pattern_set *ps, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits,
                      size_t n_streams, uint8_t prev0, const uint64_t *sym_off, const uint64_t *index, uint32_t chunk_symbols, uint64_t *hit_off,
                      uint64_t *hits, uint32_t *hit_pattern, uint64_t hit_cap, int32_t *stream_status) {
-    return find_batch_o2_host(m, Matcher(ps), payload, pay_off, nbits, n_streams, prev0, sym_off, index, chunk_symbols, hit_off, hits,
-                              hit_pattern, hit_cap, stream_status);
+    return find_batch_o2_host(m, Matcher(ps), {payload, pay_off, nbits, n_streams, 0, prev0, sym_off, 0, index, chunk_symbols}, hit_off, hits,
+                           hit_pattern, hit_cap, stream_status);
 }
 
 // ---- dictionary search: the same calls with the DFA of an mh_dict as the matcher
@@ -416,8 +362,8 @@ int mh_dev_find_dict_batch(const mh_model *m, const mh_dict *d, const uint8_t *d
                            const uint64_t *d_index, uint32_t chunk_symbols, uint64_t *d_hit_off, uint64_t *d_hits, uint32_t *d_hit_pattern,
                            uint64_t hit_cap, int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
     if (!order01(m)) return MH_ERR_ARG;
-    return find_shared(m, mhf::Model::Shared, Matcher(d), d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index,
-                       chunk_symbols, d_hit_off, d_hits, d_hit_pattern, hit_cap, d_stream_status, d_ws, ws_bytes, stream);
+    return find_shared(m, mhf::Model::Shared, Matcher(d), {d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index, chunk_symbols},
+                       d_hit_off, d_hits, d_hit_pattern, hit_cap, d_stream_status, d_ws, ws_bytes, stream);
 }
 
 int mh_dev_find_dict_batch_o2(const mh_model *m, const mh_dict *d, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits,
@@ -425,30 +371,30 @@ int mh_dev_find_dict_batch_o2(const mh_model *m, const mh_dict *d, const uint8_t
                               const uint64_t *d_index, uint32_t chunk_symbols, uint64_t *d_hit_off, uint64_t *d_hits, uint32_t *d_hit_pattern,
                               uint64_t hit_cap, int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
     if (!order2(m)) return MH_ERR_ARG;
-    return find_shared(m, mhf::Model::Shared2, Matcher(d), d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index,
-                       chunk_symbols, d_hit_off, d_hits, d_hit_pattern, hit_cap, d_stream_status, d_ws, ws_bytes, stream);
+    return find_shared(m, mhf::Model::Shared2, Matcher(d), {d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index, chunk_symbols},
+                       d_hit_off, d_hits, d_hit_pattern, hit_cap, d_stream_status, d_ws, ws_bytes, stream);
 }
 
 int mh_dev_find_dict_each(const mh_model_set *s, const mh_dict *d, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits,
                           size_t n_streams, uint64_t pay_total, uint8_t prev0, const uint64_t *d_sym_off, uint64_t sym_total,
                           const uint64_t *d_index, uint32_t chunk_symbols, uint64_t *d_hit_off, uint64_t *d_hits, uint32_t *d_hit_pattern,
                           uint64_t hit_cap, int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
-    return find_each(s, Matcher(d), d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index, chunk_symbols,
+    return find_each(s, Matcher(d), {d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index, chunk_symbols},
                      d_hit_off, d_hits, d_hit_pattern, hit_cap, d_stream_status, d_ws, ws_bytes, stream);
 }
 
 int mh_find_dict_batch(const mh_model *m, const mh_dict *d, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits,
                        size_t n_streams, uint8_t prev0, const uint64_t *sym_off, const uint64_t *index, uint32_t chunk_symbols, uint64_t *hit_off,
                        uint64_t *hits, uint32_t *hit_pattern, uint64_t hit_cap, int32_t *stream_status) {
-    return find_batch_host(m, Matcher(d), payload, pay_off, nbits, n_streams, prev0, sym_off, index, chunk_symbols, hit_off, hits, hit_pattern,
-                           hit_cap, stream_status);
+    return find_batch_host(m, Matcher(d), {payload, pay_off, nbits, n_streams, 0, prev0, sym_off, 0, index, chunk_symbols}, hit_off, hits,
+                           hit_pattern, hit_cap, stream_status);
 }
 
 int mh_find_dict_batch_o2(const mh_model *m, const mh_dict *d, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits,
                           size_t n_streams, uint8_t prev0, const uint64_t *sym_off, const uint64_t *index, uint32_t chunk_symbols,
                           uint64_t *hit_off, uint64_t *hits, uint32_t *hit_pattern, uint64_t hit_cap, int32_t *stream_status) {
-    return find_batch_o2_host(m, Matcher(d), payload, pay_off, nbits, n_streams, prev0, sym_off, index, chunk_symbols, hit_off, hits,
-                              hit_pattern, hit_cap, stream_status);
+    return find_batch_o2_host(m, Matcher(d), {payload, pay_off, nbits, n_streams, 0, prev0, sym_off, 0, index, chunk_symbols}, hit_off, hits,
+                           hit_pattern, hit_cap, stream_status);
 }
 
 }  // extern "C"

@@ -145,7 +145,6 @@ inline int status_from_device(int s) {
     }
 }
 
-// RAII device buffer for the host-buffer convenience calls
 // the shortest code of a device-built context from its meta record (mh_kernels.h, TB_META_STRIDE): mt[15] has bit l - 1 set
 // for every code length l in use, and is 0 for a one-symbol context, whose only code is one bit long (mt[2] = 1)
 inline void note_min_len(mh_model *m, const uint32_t *mt) {
@@ -155,12 +154,23 @@ inline void note_min_len(mh_model *m, const uint32_t *mt) {
     if (l && (m->min_len == 0 || l < m->min_len)) m->min_len = l;
 }
 
+// RAII device buffer for the host-buffer convenience calls
 struct DevBuf {
     void *p = nullptr;
     ~DevBuf() { if (p) (void)hipFree(p); }
     hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
     template <typename T> T *as() { return static_cast<T *>(p); }
 };
+
+// the per-stream status slot of a batch call's workspace (off: the layout's off_status)
+inline int *ws_status(void *d_ws, size_t off) { return reinterpret_cast<int *>(static_cast<unsigned char *>(d_ws) + off); }
+
+// the growing output of mh_decode_to (ctx: a std::vector<uint8_t>), for a stream whose decoded length is not known
+inline uint8_t *grow_vec(void *ctx, size_t n) {
+    auto *v = static_cast<std::vector<uint8_t> *>(ctx);
+    v->resize(n ? n : 1);
+    return v->data();
+}
 
 // what the batch calls ask of a model's order
 inline bool order01(const mh_model *m) { return m && (m->type == 0 || m->type == 1); }

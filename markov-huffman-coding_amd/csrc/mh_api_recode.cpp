@@ -2,30 +2,12 @@
 // IN SEARCH AND RE-CODING"): the training histogram of a compressed batch and the batch coded again under another model,
 // under one shared source model of any order or a model set (kernels: mh_recode.hip), and the host-buffer forms.  The order
 // rules of an entry point are in that entry point; everything behind them is here once.
-#include "mh_api_internal.hpp"
-#include "mh_batch.h"
+#include "mh_api_reader.hpp"
 #include "mh_recode.h"
 
 using namespace mhapi;
 
 namespace {
-
-// the source batch, checked in the order of mh_dev_decode_batch; sym_off is written by an index-free re-code (m: null under a set)
-int source(const mh_model *m, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits, size_t n_streams, uint64_t pay_total,
-           uint8_t prev0, const uint64_t *d_sym_off, uint64_t sym_total, const uint64_t *d_index, uint32_t chunk_symbols, const void *d_ws,
-           mhr::Src &s) {
-    if ((!d_payload && pay_total) || !d_pay_off || (!d_nbits && n_streams) || !d_ws) return MH_ERR_ARG;
-    if (!aligned16(d_payload) || !aligned16(d_ws)) return MH_ERR_ARG;
-    int shift = 0;
-    if (d_index && ((shift = chunk_shift_of(chunk_symbols)) < 0 || !d_sym_off)) return MH_ERR_ARG;
-    s.b.payload = d_payload; s.b.pay_off = d_pay_off; s.b.nbits = d_nbits; s.b.n = n_streams; s.b.pay_total = pay_total;
-    s.b.prev0 = ctx_of_prev0(m, prev0);
-    s.b.sym_off = reinterpret_cast<unsigned long long *>(const_cast<uint64_t *>(d_sym_off));
-    s.b.sym_total = sym_total;
-    s.b.index = d_index; s.b.chunk_shift = uint32_t(shift);
-    s.b.walk_max_bits = MH_BATCH_WALK_MAX_BITS;
-    return MH_OK;
-}
 
 // the source's models: a shared model's decode tables (order 0/1 as mh_dev_decode_batch hands them over, order 2 as
 // mh_dev_decode_batch_o2), or the set
@@ -43,18 +25,14 @@ int source_tables(const mh_model *m, const mh_model_set *set, mhr::Src &s, mhb::
     return MH_OK;
 }
 
-// behind the order rules of mh_dev_histogram_coded_batch, _each and _batch_o2: m or set is the source
-int histogram_coded(const mh_model *m, const mh_model_set *set, int order, const uint8_t *d_payload, const uint64_t *d_pay_off,
-                    const uint64_t *d_nbits, size_t n_streams, uint64_t pay_total, uint8_t prev0, const uint64_t *d_sym_off, uint64_t sym_total,
-                    const uint64_t *d_index, uint32_t chunk_symbols, uint64_t *d_counts, int32_t *d_stream_status, void *d_ws, size_t ws_bytes,
-                    void *stream) {
+// behind the order rules of mh_dev_histogram_coded_batch, _each and _batch_o2: m or set is the source (m: null under a set)
+int histogram_coded(const mh_model *m, const mh_model_set *set, int order, const CodedBatch &a, uint64_t *d_counts, int32_t *d_stream_status,
+                    void *d_ws, size_t ws_bytes, void *stream) {
     if (!d_counts) return MH_ERR_ARG;
     mhr::HistParams p{};
-    const int rc = source(m, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index, chunk_symbols, d_ws, p.s);
+    const mhr::HistLayout L = mhr::hist_layout(a.n);
+    const int rc = dev_batch_params(a, SymOff::Through, ctx_of_prev0(m, a.prev0), d_ws, ws_bytes, L.total, L.off_status, d_stream_status, p.s.b);
     if (rc != MH_OK) return rc;
-    const mhr::HistLayout L = mhr::hist_layout(n_streams);
-    if (ws_bytes < L.total) return MH_ERR_CAPACITY;
-    p.s.b.stream_status = d_stream_status ? d_stream_status : reinterpret_cast<int *>(static_cast<unsigned char *>(d_ws) + L.off_status);
     p.order = uint32_t(order);
     p.counts = reinterpret_cast<unsigned long long *>(d_counts);
     mhb::Model model;
@@ -64,25 +42,23 @@ int histogram_coded(const mh_model *m, const mh_model_set *set, int order, const
     return MH_OK;
 }
 
-// behind the order rules of mh_dev_recode_batch, _each, _batch_o2 and the _edit calls: m or set is the source; seam: the
-// workspace of the _o2 call, which has room for the seam's arrays; ed: the edit of an _edit call (order 0/1 on both sides)
-int recode(const mh_model *m, const mh_model_set *set, const mh_model *dst, bool seam, const mhr::Edit *ed, const uint8_t *d_payload, const uint64_t *d_pay_off,
-           const uint64_t *d_nbits, size_t n_streams, uint64_t pay_total, uint8_t prev0, uint64_t *d_sym_off, uint64_t sym_total,
-           const uint64_t *d_index, uint32_t chunk_symbols, uint8_t *d_out_payload, size_t cap, uint64_t *d_out_off, uint64_t *d_out_nbits,
-           uint64_t *d_out_index, uint64_t *d_dropped, int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
-    if (!d_out_off || (!d_out_nbits && n_streams)) return MH_ERR_ARG;
-    if (!d_index && !d_sym_off) return MH_ERR_ARG;                    // index-free: the decoded lengths are an output
+// behind the order rules of mh_dev_recode_batch, _each, _batch_o2 and the _edit calls: m or set is the source; a.sym_off is
+// written by an index-free re-code; seam: the workspace of the _o2 call, which has room for the seam's arrays; ed: the edit
+// of an _edit call (order 0/1 on both sides)
+int recode(const mh_model *m, const mh_model_set *set, const mh_model *dst, bool seam, const mhr::Edit *ed, const CodedBatch &a,
+           uint8_t *d_out_payload, size_t cap, uint64_t *d_out_off, uint64_t *d_out_nbits, uint64_t *d_out_index, uint64_t *d_dropped,
+           int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
+    if (!d_out_off || (!d_out_nbits && a.n)) return MH_ERR_ARG;
+    if (!a.index && !a.sym_off) return MH_ERR_ARG;                    // index-free: the decoded lengths are an output
     if (ed && !ed->map) return MH_ERR_ARG;
-    mhr::EditParams p{};
-    const int rc = source(m, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index, chunk_symbols, d_ws, p.s);
-    if (rc != MH_OK) return rc;
     if (!aligned16(d_out_payload)) return MH_ERR_ARG;
-    int oshift = int(p.s.b.chunk_shift);
-    if (!d_index && d_out_index && (oshift = chunk_shift_of(chunk_symbols)) < 0) return MH_ERR_ARG;
-    const uint64_t W = d_index ? mhb::work_items(n_streams, sym_total, chunk_symbols) : 0;
-    const mhr::RecodeLayout L = mhr::recode_layout(n_streams, W, seam);
-    if (ws_bytes < L.total) return MH_ERR_CAPACITY;
-    p.s.b.stream_status = d_stream_status ? d_stream_status : reinterpret_cast<int *>(static_cast<unsigned char *>(d_ws) + L.off_status);
+    int oshift = 0;                                                   // index-free: the chunk size is the destination index's
+    if (!a.index && d_out_index && (oshift = chunk_shift_of(a.chunk_symbols)) < 0) return MH_ERR_ARG;
+    mhr::EditParams p{};
+    const mhr::RecodeLayout L = mhr::recode_layout(a.n, work_items_of(a), seam);
+    const int rc = dev_batch_params(a, SymOff::Through, ctx_of_prev0(m, a.prev0), d_ws, ws_bytes, L.total, L.off_status, d_stream_status, p.s.b);
+    if (rc != MH_OK) return rc;
+    if (a.index) oshift = int(p.s.b.chunk_shift);
     p.out = d_out_payload; p.cap = d_out_payload ? cap : 0;
     p.out_off = reinterpret_cast<unsigned long long *>(d_out_off);
     p.out_nbits = reinterpret_cast<unsigned long long *>(d_out_nbits);
@@ -116,98 +92,62 @@ size_t recode_workspace(size_t n_streams, uint64_t sym_total, uint32_t chunk_sym
     return mhr::recode_layout(n_streams, W, seam).total;
 }
 
-// the argument checks of the two host forms behind their order rules, in the order of mh_decode_batch
-int host_args(const mh_model *src, const mh_model *dst, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits, size_t n_streams,
-              const uint64_t *sym_off, const uint64_t *index, uint32_t chunk_symbols, const uint64_t *out_off, const uint64_t *out_nbits,
-              const uint64_t *out_index) {
-    if (!pay_off || (!nbits && n_streams) || !out_off || (!out_nbits && n_streams) || !sym_off) return MH_ERR_ARG;
-    if ((index || out_index) && chunk_shift_of(chunk_symbols) < 0) return MH_ERR_ARG;
-    if (!offsets_ok(pay_off, n_streams)) return MH_ERR_ARG;
-    if (!payload && pay_off[n_streams]) return MH_ERR_ARG;
-    for (size_t i = 0; i < n_streams; ++i)
-        if (nbits[i] > (pay_off[i + 1] - pay_off[i]) * 8) return MH_ERR_ARG;
-    if (index && !offsets_ok(sym_off, n_streams)) return MH_ERR_ARG;
+// The host forms behind their order rules: the argument checks in the order of mh_decode_batch, then an index-free batch of
+// an order-0/1 source with a stream over the walk cap (index_first) is indexed first and re-coded as an indexed batch, with the
+// chunk size of out_index when the call writes one; a stream the indexing fails (idx_st) has no symbols, so no payload.  An
+// index-free batch is sized for symbol_bound symbols.
+int host_args(const mh_model *src, const mh_model *dst, CodedBatch &a, bool index_first_ok, const uint64_t *out_off, const uint64_t *out_nbits,
+              const uint64_t *out_index, uint64_t *sym_off, std::vector<uint64_t> &own_idx, std::vector<int32_t> &idx_st) {
+    if (!out_off || (!out_nbits && a.n) || !sym_off) return MH_ERR_ARG;
+    int rc = host_batch_args(a, a.index || out_index);
+    if (rc != MH_OK) return rc;
     if (!have_device()) return MH_ERR_NO_DEVICE;
     if (src->max_len > mh::MAX_CODE_BITS || dst->max_len > mh::MAX_CODE_BITS) return MH_ERR_CODE_TOO_LONG;
+    if (index_first_ok && over_walk_cap(a) && (rc = index_first(src, a, out_index != nullptr, sym_off, own_idx, idx_st)) != MH_OK) return rc;
+    if (!a.index) a.sym_total = symbol_bound(src->min_len, a.nbits, a.n);
     return MH_OK;
-}
-
-// at most this many symbols in the batch: what an index-free call sizes the destination index for
-uint64_t symbol_bound(const mh_model *src, const uint64_t *nbits, size_t n_streams) {
-    const uint64_t minl = uint64_t(src->min_len > 0 ? src->min_len : 1);
-    uint64_t bound = 0;
-    for (size_t i = 0; i < n_streams; ++i) bound += nbits[i] / minl;
-    return bound;
-}
-
-// An index-free batch of an order-0/1 source with a stream over the walk cap: index the batch first (mh_index_batch never
-// refuses a valid stream), then re-code it as an indexed batch; a stream the indexing fails keeps that error (idx_st) and has
-// no symbols, so no payload.
-int index_first(const mh_model *src, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits, size_t n_streams, uint8_t prev0,
-                uint64_t bound, bool keep_chunk, uint32_t &chunk_symbols, uint64_t *sym_off, std::vector<uint64_t> &own_idx,
-                std::vector<int32_t> &idx_st) {
-    if (!keep_chunk) chunk_symbols = MH_CHUNK_DEFAULT;
-    own_idx.assign(size_t(mh_batch_index_capacity(bound, n_streams, chunk_symbols)), 0);
-    idx_st.assign(n_streams, MH_OK);
-    const int rc = mh_index_batch(src, payload, pay_off, nbits, n_streams, prev0, chunk_symbols, sym_off, own_idx.data(), own_idx.size(),
-                                  idx_st.data());
-    return (rc == MH_ERR_HIP || rc == MH_ERR_NO_DEVICE || rc == MH_ERR_NOMEM || rc == MH_ERR_CAPACITY) ? rc : MH_OK;
 }
 
 // One host-form re-code on the device: run() uploads the batch, runs the device call of the family and brings back the
 // verdicts, offsets, lengths and dropped counts; payload() and slices() then bring what the device wrote to wherever the
 // caller wants it.
 struct HostRecode {
-    DevBuf d_pl, d_po, d_nb, d_so, d_idx, d_out, d_oo, d_onb, d_oidx, d_drop, d_st, d_ws;
+    DevBatch db;
+    DevBuf d_out, d_oo, d_onb, d_oidx, d_drop, d_st, d_ws;
     std::vector<int32_t> sst;           // per-stream verdicts
     std::vector<uint64_t> drop;         // per-stream dropped symbols
     size_t noidx = 0, dcap = 0;         // entries of the destination index, bytes of the payload buffer
     int dev_rc = MH_OK;
 
-    // dev: the device call, with the arguments of mh_dev_recode_batch
-    template <typename DevFn>
-    int run(DevFn dev, bool seam, const mh_model *src, const mh_model *dst, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits,
-            size_t n_streams, uint8_t prev0, uint64_t *sym_off, uint64_t sym_total, const uint64_t *index, uint32_t chunk_symbols,
-            bool want_payload, size_t cap, uint64_t *out_off, uint64_t *out_nbits, const uint64_t *out_index) {
+    // seam: the _o2 call; ed: the edit of an _edit call, on the device; sym_off: the caller's, written when index-free
+    int run(bool seam, const mhr::Edit *ed, const mh_model *src, const mh_model *dst, const CodedBatch &a, uint64_t *sym_off, bool want_payload,
+            size_t cap, uint64_t *out_off, uint64_t *out_nbits, const uint64_t *out_index) {
         const hipStream_t st = nullptr;
-        const uint64_t pay_total = pay_off[n_streams];
-        const size_t nidx = index ? size_t(mh_batch_index_capacity(sym_total, n_streams, chunk_symbols)) : 0;
-        noidx = out_index ? size_t(mh_batch_index_capacity(sym_total, n_streams, chunk_symbols)) : 0;
-        const size_t wsb = recode_workspace(n_streams, sym_total, index ? chunk_symbols : 0, seam);
+        const size_t n = a.n;
+        noidx = out_index ? size_t(mh_batch_index_capacity(a.sym_total, n, a.chunk_symbols)) : 0;
+        const size_t wsb = recode_workspace(n, a.sym_total, a.index ? a.chunk_symbols : 0, seam);
         dcap = want_payload ? cap : 0;
-        HIP_TRY(d_pl.alloc(size_t(pay_total) + 64));
-        HIP_TRY(d_po.alloc((n_streams + 1) * 8));
-        HIP_TRY(d_nb.alloc(n_streams * 8));
-        HIP_TRY(d_so.alloc((n_streams + 1) * 8));
-        HIP_TRY(d_idx.alloc(nidx * 8));
         HIP_TRY(d_out.alloc(dcap));
-        HIP_TRY(d_oo.alloc((n_streams + 1) * 8));
-        HIP_TRY(d_onb.alloc(n_streams * 8));
+        HIP_TRY(d_oo.alloc((n + 1) * 8));
+        HIP_TRY(d_onb.alloc(n * 8));
         HIP_TRY(d_oidx.alloc(noidx * 8));
-        HIP_TRY(d_drop.alloc(n_streams * 8));
-        HIP_TRY(d_st.alloc(n_streams * 4));
+        HIP_TRY(d_drop.alloc(n * 8));
+        HIP_TRY(d_st.alloc(n * 4));
         HIP_TRY(d_ws.alloc(wsb));
-        if (pay_total) HIP_TRY(stage_h2d(d_pl.p, payload, size_t(pay_total), st));
-        HIP_TRY(hipMemcpy(d_po.p, pay_off, (n_streams + 1) * 8, hipMemcpyHostToDevice));
-        if (n_streams) HIP_TRY(hipMemcpy(d_nb.p, nbits, n_streams * 8, hipMemcpyHostToDevice));
-        if (index) {
-            HIP_TRY(hipMemcpy(d_so.p, sym_off, (n_streams + 1) * 8, hipMemcpyHostToDevice));
-            if (nidx) HIP_TRY(hipMemcpy(d_idx.p, index, nidx * 8, hipMemcpyHostToDevice));
-        }
+        int rc = db.upload(a, st);
+        if (rc != MH_OK) return rc;
         if (noidx) HIP_TRY(hipMemcpy(d_oidx.p, out_index, noidx * 8, hipMemcpyHostToDevice));   // gap entries stay what the caller had
-        const int rc = dev(src, dst, d_pl.as<uint8_t>(), d_po.as<uint64_t>(), d_nb.as<uint64_t>(), n_streams, pay_total, prev0,
-                           d_so.as<uint64_t>(), sym_total, index ? d_idx.as<uint64_t>() : nullptr, chunk_symbols,
-                           want_payload ? d_out.as<uint8_t>() : nullptr, dcap, d_oo.as<uint64_t>(), d_onb.as<uint64_t>(),
-                           out_index ? d_oidx.as<uint64_t>() : nullptr, d_drop.as<uint64_t>(), d_st.as<int32_t>(), d_ws.p, wsb, st);
+        rc = recode(src, nullptr, dst, seam, ed, db.d, want_payload ? d_out.as<uint8_t>() : nullptr, dcap, d_oo.as<uint64_t>(), d_onb.as<uint64_t>(),
+                    out_index ? d_oidx.as<uint64_t>() : nullptr, d_drop.as<uint64_t>(), d_st.as<int32_t>(), d_ws.p, wsb, st);
         if (rc != MH_OK) return rc;
         dev_rc = mh_dev_status(d_ws.p, st);
-        sst.resize(n_streams);
-        drop.resize(n_streams);
-        if (n_streams) HIP_TRY(hipMemcpy(sst.data(), d_st.p, n_streams * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(out_off, d_oo.p, (n_streams + 1) * 8, hipMemcpyDeviceToHost));
-        if (n_streams) HIP_TRY(hipMemcpy(out_nbits, d_onb.p, n_streams * 8, hipMemcpyDeviceToHost));
-        if (n_streams) HIP_TRY(hipMemcpy(drop.data(), d_drop.p, n_streams * 8, hipMemcpyDeviceToHost));
-        if (!index) HIP_TRY(hipMemcpy(sym_off, d_so.p, (n_streams + 1) * 8, hipMemcpyDeviceToHost));
+        sst.resize(n);
+        drop.resize(n);
+        if (n) HIP_TRY(hipMemcpy(sst.data(), d_st.p, n * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(out_off, d_oo.p, (n + 1) * 8, hipMemcpyDeviceToHost));
+        if (n) HIP_TRY(hipMemcpy(out_nbits, d_onb.p, n * 8, hipMemcpyDeviceToHost));
+        if (n) HIP_TRY(hipMemcpy(drop.data(), d_drop.p, n * 8, hipMemcpyDeviceToHost));
+        if (!a.index) HIP_TRY(hipMemcpy(sym_off, db.so.p, (n + 1) * 8, hipMemcpyDeviceToHost));
         return MH_OK;
     }
 
@@ -222,15 +162,10 @@ struct HostRecode {
         return MH_OK;
     }
 
-    // the call's result: the first failed stream's error (idx_st: what indexing the batch first found), else the device's
-    // (MH_ERR_CAPACITY: the payload does not fit)
+    // the call's result (idx_st: what indexing the batch first found); the device's MH_ERR_CAPACITY: the payload does not fit
     int finish(const std::vector<int32_t> &idx_st, uint64_t *dropped, int32_t *stream_status) {
         if (dropped) std::copy(drop.begin(), drop.end(), dropped);
-        for (size_t i = 0; i < idx_st.size(); ++i)
-            if (idx_st[i] != MH_OK) sst[i] = idx_st[i];
-        int first = MH_OK;
-        for (size_t i = 0; i < sst.size() && first == MH_OK; ++i) first = sst[i];
-        if (first == MH_OK && dev_rc != MH_OK && dev_rc != MH_ERR_ARG) first = dev_rc;
+        const int first = first_failure(sst, idx_st, dev_rc);
         if (stream_status) std::copy(sst.begin(), sst.end(), stream_status);
         return first;
     }
@@ -266,8 +201,9 @@ int mh_dev_histogram_coded_batch(const mh_model *src, int order, const uint8_t *
                                  const uint64_t *d_index, uint32_t chunk_symbols, uint64_t *d_counts, int32_t *d_stream_status, void *d_ws,
                                  size_t ws_bytes, void *stream) {
     if (!order01(src) || (order != 0 && order != 1)) return MH_ERR_ARG;
-    return histogram_coded(src, nullptr, order, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index,
-                           chunk_symbols, d_counts, d_stream_status, d_ws, ws_bytes, stream);
+    return histogram_coded(src, nullptr, order,
+                           {d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index, chunk_symbols}, d_counts,
+                           d_stream_status, d_ws, ws_bytes, stream);
 }
 
 int mh_dev_histogram_coded_each(const mh_model_set *src, int order, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits,
@@ -275,8 +211,9 @@ int mh_dev_histogram_coded_each(const mh_model_set *src, int order, const uint8_
                                 const uint64_t *d_index, uint32_t chunk_symbols, uint64_t *d_counts, int32_t *d_stream_status, void *d_ws,
                                 size_t ws_bytes, void *stream) {
     if (!src || n_streams != src->d.n || (order != 0 && order != 1)) return MH_ERR_ARG;
-    return histogram_coded(nullptr, src, order, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index,
-                           chunk_symbols, d_counts, d_stream_status, d_ws, ws_bytes, stream);
+    return histogram_coded(nullptr, src, order,
+                           {d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index, chunk_symbols}, d_counts,
+                           d_stream_status, d_ws, ws_bytes, stream);
 }
 
 int mh_dev_histogram_coded_batch_o2(const mh_model *src, int order, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits,
@@ -284,8 +221,9 @@ int mh_dev_histogram_coded_batch_o2(const mh_model *src, int order, const uint8_
                                     const uint64_t *d_index, uint32_t chunk_symbols, uint64_t *d_counts, int32_t *d_stream_status, void *d_ws,
                                     size_t ws_bytes, void *stream) {
     if (!order012(src) || order < 0 || order > 2 || (src->type != 2 && order != 2)) return MH_ERR_ARG;
-    return histogram_coded(src, nullptr, order, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index,
-                           chunk_symbols, d_counts, d_stream_status, d_ws, ws_bytes, stream);
+    return histogram_coded(src, nullptr, order,
+                           {d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index, chunk_symbols}, d_counts,
+                           d_stream_status, d_ws, ws_bytes, stream);
 }
 
 /* ---------------------------------------------------------------------------------------------------- re-code */
@@ -303,8 +241,8 @@ int mh_dev_recode_batch(const mh_model *src, const mh_model *dst, const uint8_t 
                         uint32_t chunk_symbols, uint8_t *d_out_payload, size_t cap, uint64_t *d_out_off, uint64_t *d_out_nbits,
                         uint64_t *d_out_index, uint64_t *d_dropped, int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
     if (!order01(src) || !order01(dst)) return MH_ERR_ARG;
-    return recode(src, nullptr, dst, false, nullptr, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index,
-                  chunk_symbols, d_out_payload, cap, d_out_off, d_out_nbits, d_out_index, d_dropped, d_stream_status, d_ws, ws_bytes, stream);
+    return recode(src, nullptr, dst, false, nullptr, {d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index, chunk_symbols},
+                  d_out_payload, cap, d_out_off, d_out_nbits, d_out_index, d_dropped, d_stream_status, d_ws, ws_bytes, stream);
 }
 
 int mh_dev_recode_each(const mh_model_set *src, const mh_model *dst, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits,
@@ -312,8 +250,8 @@ int mh_dev_recode_each(const mh_model_set *src, const mh_model *dst, const uint8
                        uint32_t chunk_symbols, uint8_t *d_out_payload, size_t cap, uint64_t *d_out_off, uint64_t *d_out_nbits,
                        uint64_t *d_out_index, uint64_t *d_dropped, int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
     if (!src || n_streams != src->d.n || !order01(dst)) return MH_ERR_ARG;
-    return recode(nullptr, src, dst, false, nullptr, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index,
-                  chunk_symbols, d_out_payload, cap, d_out_off, d_out_nbits, d_out_index, d_dropped, d_stream_status, d_ws, ws_bytes, stream);
+    return recode(nullptr, src, dst, false, nullptr, {d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index, chunk_symbols},
+                  d_out_payload, cap, d_out_off, d_out_nbits, d_out_index, d_dropped, d_stream_status, d_ws, ws_bytes, stream);
 }
 
 int mh_dev_recode_batch_o2(const mh_model *src, const mh_model *dst, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits,
@@ -321,31 +259,21 @@ int mh_dev_recode_batch_o2(const mh_model *src, const mh_model *dst, const uint8
                            uint32_t chunk_symbols, uint8_t *d_out_payload, size_t cap, uint64_t *d_out_off, uint64_t *d_out_nbits,
                            uint64_t *d_out_index, uint64_t *d_dropped, int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
     if (!order012(src) || !order012(dst) || (src->type != 2 && dst->type != 2)) return MH_ERR_ARG;
-    return recode(src, nullptr, dst, true, nullptr, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index,
-                  chunk_symbols, d_out_payload, cap, d_out_off, d_out_nbits, d_out_index, d_dropped, d_stream_status, d_ws, ws_bytes, stream);
+    return recode(src, nullptr, dst, true, nullptr, {d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index, chunk_symbols},
+                  d_out_payload, cap, d_out_off, d_out_nbits, d_out_index, d_dropped, d_stream_status, d_ws, ws_bytes, stream);
 }
 
 int mh_recode_batch(const mh_model *src, const mh_model *dst, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits,
                     size_t n_streams, uint8_t prev0, uint64_t *sym_off, const uint64_t *index, uint32_t chunk_symbols, uint8_t *out_payload,
                     size_t cap, uint64_t *out_off, uint64_t *out_nbits, uint64_t *out_index, uint64_t *dropped, int32_t *stream_status) {
     if (!order01(src) || !order01(dst)) return MH_ERR_ARG;
-    int rc = host_args(src, dst, payload, pay_off, nbits, n_streams, sym_off, index, chunk_symbols, out_off, out_nbits, out_index);
-    if (rc != MH_OK) return rc;
-    const uint64_t bound = symbol_bound(src, nbits, n_streams);
-    // index-free with a stream over the walk cap: index first
+    CodedBatch a{payload, pay_off, nbits, n_streams, 0, prev0, sym_off, 0, index, chunk_symbols};
     std::vector<uint64_t> own_idx;
     std::vector<int32_t> idx_st;
-    bool over = false;
-    if (!index)
-        for (size_t i = 0; i < n_streams && !over; ++i) over = nbits[i] > MH_BATCH_WALK_MAX_BITS;
-    if (over) {
-        rc = index_first(src, payload, pay_off, nbits, n_streams, prev0, bound, out_index != nullptr, chunk_symbols, sym_off, own_idx, idx_st);
-        if (rc != MH_OK) return rc;
-        index = own_idx.data();
-    }
+    int rc = host_args(src, dst, a, true, out_off, out_nbits, out_index, sym_off, own_idx, idx_st);
+    if (rc != MH_OK) return rc;
     HostRecode hr;
-    rc = hr.run(mh_dev_recode_batch, false, src, dst, payload, pay_off, nbits, n_streams, prev0, sym_off, index ? sym_off[n_streams] : bound, index,
-                chunk_symbols, out_payload != nullptr, cap, out_off, out_nbits, out_index);
+    rc = hr.run(false, nullptr, src, dst, a, sym_off, out_payload != nullptr, cap, out_off, out_nbits, out_index);
     if (rc != MH_OK) return rc;
     if ((rc = hr.payload(out_payload, out_off[n_streams])) != MH_OK || (rc = hr.slices(out_index)) != MH_OK) return rc;
     return hr.finish(idx_st, dropped, stream_status);
@@ -407,8 +335,8 @@ int mh_dev_recode_edit_batch(const mh_model *src, const mh_model *dst, const uin
                              uint64_t *d_dropped, int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
     if (!order01(src) || !order01(dst)) return MH_ERR_ARG;
     const mhr::Edit ed = edit_of(d_span_off, d_spans, d_map);
-    return recode(src, nullptr, dst, false, &ed, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index,
-                  chunk_symbols, d_out_payload, cap, d_out_off, d_out_nbits, d_out_index, d_dropped, d_stream_status, d_ws, ws_bytes, stream);
+    return recode(src, nullptr, dst, false, &ed, {d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index, chunk_symbols},
+                  d_out_payload, cap, d_out_off, d_out_nbits, d_out_index, d_dropped, d_stream_status, d_ws, ws_bytes, stream);
 }
 
 int mh_dev_recode_edit_each(const mh_model_set *src, const mh_model *dst, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits,
@@ -418,8 +346,8 @@ int mh_dev_recode_edit_each(const mh_model_set *src, const mh_model *dst, const 
                             uint64_t *d_dropped, int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
     if (!src || n_streams != src->d.n || !order01(dst)) return MH_ERR_ARG;
     const mhr::Edit ed = edit_of(d_span_off, d_spans, d_map);
-    return recode(nullptr, src, dst, false, &ed, d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index,
-                  chunk_symbols, d_out_payload, cap, d_out_off, d_out_nbits, d_out_index, d_dropped, d_stream_status, d_ws, ws_bytes, stream);
+    return recode(nullptr, src, dst, false, &ed, {d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index, chunk_symbols},
+                  d_out_payload, cap, d_out_off, d_out_nbits, d_out_index, d_dropped, d_stream_status, d_ws, ws_bytes, stream);
 }
 
 int mh_recode_edit_batch(const mh_model *src, const mh_model *dst, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits,
@@ -428,20 +356,12 @@ int mh_recode_edit_batch(const mh_model *src, const mh_model *dst, const uint8_t
                          uint64_t *out_nbits, uint64_t *out_index, uint64_t *dropped, int32_t *stream_status) {
     if (!order01(src) || !order01(dst) || !map) return MH_ERR_ARG;
     if (span_off && (!offsets_ok(span_off, n_streams) || (span_off[n_streams] && !spans))) return MH_ERR_ARG;
-    int rc = host_args(src, dst, payload, pay_off, nbits, n_streams, sym_off, index, chunk_symbols, out_off, out_nbits, out_index);
-    if (rc != MH_OK) return rc;
-    const uint64_t bound = symbol_bound(src, nbits, n_streams);
-    // index-free with a stream over the walk cap: index first (a span's positions do not depend on the index)
+    // (a span's positions do not depend on the index that an over-cap batch gets first)
+    CodedBatch a{payload, pay_off, nbits, n_streams, 0, prev0, sym_off, 0, index, chunk_symbols};
     std::vector<uint64_t> own_idx;
     std::vector<int32_t> idx_st;
-    bool over = false;
-    if (!index)
-        for (size_t i = 0; i < n_streams && !over; ++i) over = nbits[i] > MH_BATCH_WALK_MAX_BITS;
-    if (over) {
-        rc = index_first(src, payload, pay_off, nbits, n_streams, prev0, bound, out_index != nullptr, chunk_symbols, sym_off, own_idx, idx_st);
-        if (rc != MH_OK) return rc;
-        index = own_idx.data();
-    }
+    int rc = host_args(src, dst, a, true, out_off, out_nbits, out_index, sym_off, own_idx, idx_st);
+    if (rc != MH_OK) return rc;
     DevBuf d_soff, d_sp, d_map;
     const size_t nsp = span_off ? size_t(span_off[n_streams]) : 0;
     HIP_TRY(d_soff.alloc(span_off ? (n_streams + 1) * 8 : 0));
@@ -450,16 +370,9 @@ int mh_recode_edit_batch(const mh_model *src, const mh_model *dst, const uint8_t
     if (span_off) HIP_TRY(hipMemcpy(d_soff.p, span_off, (n_streams + 1) * 8, hipMemcpyHostToDevice));
     if (nsp) HIP_TRY(hipMemcpy(d_sp.p, spans, nsp * 16, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_map.p, map, 256, hipMemcpyHostToDevice));
-    const uint64_t *so = span_off ? d_soff.as<uint64_t>() : nullptr, *sp = d_sp.as<uint64_t>();
-    const uint8_t *mp = d_map.as<uint8_t>();
-    auto dev = [=](const mh_model *s, const mh_model *d, const uint8_t *pl, const uint64_t *po, const uint64_t *nb, size_t n, uint64_t pt, uint8_t p0,
-                   uint64_t *syo, uint64_t st, const uint64_t *idx, uint32_t cs, uint8_t *o, size_t c, uint64_t *oo, uint64_t *onb, uint64_t *oi,
-                   uint64_t *dr, int32_t *sst, void *ws, size_t wsb, void *stream) {
-        return mh_dev_recode_edit_batch(s, d, pl, po, nb, n, pt, p0, syo, st, idx, cs, so, sp, mp, o, c, oo, onb, oi, dr, sst, ws, wsb, stream);
-    };
+    const mhr::Edit ed = edit_of(span_off ? d_soff.as<uint64_t>() : nullptr, d_sp.as<uint64_t>(), d_map.as<uint8_t>());
     HostRecode hr;
-    rc = hr.run(dev, false, src, dst, payload, pay_off, nbits, n_streams, prev0, sym_off, index ? sym_off[n_streams] : bound, index, chunk_symbols,
-                out_payload != nullptr, cap, out_off, out_nbits, out_index);
+    rc = hr.run(false, &ed, src, dst, a, sym_off, out_payload != nullptr, cap, out_off, out_nbits, out_index);
     if (rc != MH_OK) return rc;
     if ((rc = hr.payload(out_payload, out_off[n_streams])) != MH_OK || (rc = hr.slices(out_index)) != MH_OK) return rc;
     return hr.finish(idx_st, dropped, stream_status);
@@ -469,26 +382,19 @@ int mh_recode_batch_o2(const mh_model *src, const mh_model *dst, const uint8_t *
                        size_t n_streams, uint8_t prev0, uint64_t *sym_off, const uint64_t *index, uint32_t chunk_symbols, uint8_t *out_payload,
                        size_t cap, uint64_t *out_off, uint64_t *out_nbits, uint64_t *out_index, uint64_t *dropped, int32_t *stream_status) {
     if (!order012(src) || !order012(dst) || (src->type != 2 && dst->type != 2)) return MH_ERR_ARG;
-    int rc = host_args(src, dst, payload, pay_off, nbits, n_streams, sym_off, index, chunk_symbols, out_off, out_nbits, out_index);
-    if (rc != MH_OK) return rc;
-    const uint64_t bound = symbol_bound(src, nbits, n_streams);
     // index-free with a stream over the walk cap.  Order-0/1 source: index first.  Order-2 source (not yet on mh_index_batch_o2): the
     // device call refuses such a stream; it is decoded alone, coded by mh_encode under dst and spliced into place in stream order.
+    CodedBatch a{payload, pay_off, nbits, n_streams, 0, prev0, sym_off, 0, index, chunk_symbols};
     std::vector<uint64_t> own_idx;
     std::vector<int32_t> idx_st;
+    int rc = host_args(src, dst, a, src->type != 2, out_off, out_nbits, out_index, sym_off, own_idx, idx_st);
+    if (rc != MH_OK) return rc;
     std::vector<size_t> long_streams;
-    if (!index)
+    if (!a.index)
         for (size_t i = 0; i < n_streams; ++i)
             if (nbits[i] > MH_BATCH_WALK_MAX_BITS) long_streams.push_back(i);
-    if (!long_streams.empty() && src->type != 2) {
-        long_streams.clear();
-        rc = index_first(src, payload, pay_off, nbits, n_streams, prev0, bound, out_index != nullptr, chunk_symbols, sym_off, own_idx, idx_st);
-        if (rc != MH_OK) return rc;
-        index = own_idx.data();
-    }
     HostRecode hr;
-    rc = hr.run(mh_dev_recode_batch_o2, true, src, dst, payload, pay_off, nbits, n_streams, prev0, sym_off, index ? sym_off[n_streams] : bound,
-                index, chunk_symbols, out_payload != nullptr, cap, out_off, out_nbits, out_index);
+    rc = hr.run(true, nullptr, src, dst, a, sym_off, out_payload != nullptr, cap, out_off, out_nbits, out_index);
     if (rc != MH_OK) return rc;
     if (long_streams.empty()) {
         if ((rc = hr.payload(out_payload, out_off[n_streams])) != MH_OK || (rc = hr.slices(out_index)) != MH_OK) return rc;

@@ -494,6 +494,21 @@ def test_host_form(mhc, msgs, sources, dsts):
     assert np.array_equal(got["payload"], packed[0]) and np.array_equal(got["dropped"], packed[3])
 
 
+def test_host_form_indexes_a_batch_with_a_stream_over_the_walk_cap_first(mhc):
+    """Index-free, one stream over MH_BATCH_WALK_MAX_BITS: the host form indexes the batch first, with the chunk size of
+    out_index when it writes one and its own when it does not.  A span in the long stream, one in the first stream."""
+    long_msg = np.random.default_rng(61).integers(0, 256, 1_200_000 + 77, dtype=np.uint8).tobytes()      # ~8-bit codes under its own model
+    src = Source(mhc, [b"a few bytes", long_msg, b""], order=0)
+    assert src.model.min_code_len >= 7 and int(src.nbits[1]) > mhc.BATCH_WALK_MAX_BITS
+    dst = model_of(mhc, [long_msg, b"*" * 4000], 0)
+    span_off, spans = span_lists([[(2, 5)], [(700_001, 700_300)], []])
+    _, ref, packed = expect(src, dst, STAR, span_off, spans)
+    for want_index in (True, False):
+        got = src.model.recode_edit_batch(dst, src.payload, src.pay_off, src.nbits, STAR, span_off, spans, chunk_symbols=CHUNK,
+                                          want_index=want_index, check=False)
+        check_exact(mhc, src, got, ref, packed, "over the cap, out_index=%s" % want_index, index=want_index)
+
+
 # ---- 9. dirty workspaces and outputs; a chain on a non-default stream ------------------------------------------------------------------
 
 @pytest.mark.parametrize("byte", [0xFF, 0xA5])
