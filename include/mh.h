@@ -1265,8 +1265,8 @@ int mh_find_dict_batch_o2(const mh_model *m, const mh_dict *d, const uint8_t *pa
  * EDITING BATCHES (extension, parity unpinned) — a length-preserving edit while re-coding: inside given spans of each
  * record every byte b is replaced by map[b] (a constant map is a mask byte), and the record is coded under dst, which may be
  * the source model itself.  The bytes are never written.  Order 0 and order 1 on both sides, independently; an order-2 model
- * on either side is MH_ERR_ARG before any launch (order 2 and its seam bookkeeping are not built; neither are deletions and
- * insertions, which move chunk boundaries, nor the refreshing of digests stored elsewhere).
+ * on either side is MH_ERR_ARG before any launch (order 2 and its seam bookkeeping are not built, nor the refreshing of digests stored elsewhere;
+ * deletions and replacements of another length, which move chunk boundaries, are SPLICING BATCHES below).
  *   - A span list: d_span_off[n + 1], the exclusive scan of the spans per stream, and d_spans[2r], d_spans[2r + 1] =
  *     (begin, end), byte positions counted from the start of that stream's decoded message.  Within a stream the spans ascend
  *     and are disjoint: begin < end <= next begin.  The part of a span at or beyond the stream's length is ignored (an
@@ -1325,6 +1325,69 @@ int mh_recode_edit_batch(const mh_model *src, const mh_model *dst, const uint8_t
                          uint32_t chunk_symbols, const uint64_t *span_off, const uint64_t *spans, const uint8_t *map,
                          uint8_t *out_payload, size_t cap, uint64_t *out_off, uint64_t *out_nbits, uint64_t *out_index,
                          uint64_t *dropped, int32_t *stream_status);
+
+/* ---------------------------------------------------------------------------------------------------------------------
+ * SPLICING BATCHES (extension, parity unpinned) — an edit that changes lengths while re-coding: every span of a record is
+ * deleted or replaced by one replacement string of any length up to MH_SPLICE_MAX_REP, and the record is coded under dst,
+ * which may be the source model itself.  The bytes are never written.  Order 0 and order 1 on both sides, independently; an
+ * order-2 model on either side is MH_ERR_ARG before any launch.
+ *   - Span lists are exactly EDITING BATCHES': d_span_off[n + 1] and (begin, end) pairs, ascending and disjoint within a
+ *     stream (begin < end <= next begin; touching spans are legal).  d_span_off == NULL is MH_ERR_ARG: "everything inside"
+ *     has no meaning for a splice.  A malformed list fails its stream alone with MH_ERR_ARG, bad offsets stop the call, as there.
+ *   - Replacement: d_rep, rep_len bytes on the device, rep_len 0 .. MH_SPLICE_MAX_REP (more: MH_ERR_ARG).  0 deletes, and
+ *     d_rep may then be NULL (NULL with rep_len > 0: MH_ERR_ARG).  One replacement serves the whole call.
+ *   - Edited message.  Let x be stream i's message as the batch decoder returns it.  y is x with every span whose
+ *     begin < len(x) replaced by rep, the span's end clipped to len(x).  A span that begins at or beyond the length is
+ *     ignored (an index-free caller does not know the length).
+ *   - Output.  For every stream whose verdict is MH_OK the output equals what mh_dev_encode_batch(dst) writes for y with the
+ *     same chunk_symbols: d_out_off, d_out_nbits, the payload bytes; d_dropped (pairs of y without a code under dst are
+ *     skipped while the context advances, pairs inside or at the edges of the replacement included); d_out_sym_off[n + 1]
+ *     (required), the exclusive scan of len(y); and, when d_out_index is given, the index slices at entry
+ *     (out_sym_off[i] >> log2 chunk) + i + k, one per started chunk of y, with context byte y[start - 1] (prev0 first) and
+ *     the stream-relative bit: mh_batch_index_base(out_sym_off[i], i, chunk).  Gap entries are untouched.  A stream that
+ *     becomes empty has nbits 0 and no entry.
+ *   - Failed streams (the batch decoders' verdicts, plus MH_ERR_ARG for a bad list) have len(y) = 0, nbits 0, no payload
+ *     byte, no index entry and dropped 0.  Index-free: the source's d_sym_off is written as mh_dev_recode_batch writes it;
+ *     sym_total is ignored (index_cap bounds the destination index).
+ *   - Capacity.  out_off[n] > cap, or a d_out_index with (out_sym_off[n] >> log2 chunk) + n > index_cap entries needed:
+ *     MH_ERR_CAPACITY through mh_dev_status(d_ws); nothing is written at or beyond the caps, neither payload nor index is
+ *     written, and the offsets, bit counts, dropped counts and out_sym_off are valid, so the caller can size a second call.
+ *     d_out_payload == NULL: count only (cap ignored).
+ *   - With an empty span list the payload, offsets, bit counts, dropped counts and index are mh_dev_recode_batch's byte for
+ *     byte, and out_sym_off == sym_off.
+ *   - No allocation, no host synchronisation; the number of launches depends on rep_len == 0 and on indexed versus
+ *     index-free, never on the data.  d_ws 16-byte aligned, at least mh_dev_recode_splice_workspace(n, sym_total,
+ *     chunk_symbols, n_spans) bytes (chunk_symbols 0: index-free): per chunk number, per stream and, for the deletion's
+ *     look-back, per span.  A deletion (rep_len 0) of an indexed batch with more spans than the workspace was sized for is
+ *     MH_ERR_CAPACITY through mh_dev_status(d_ws).
+ *   - mh_dev_recode_splice_each: stream i under the set's model i (n_streams == mh_model_set_size(src), else MH_ERR_ARG).
+ *   - Host form mh_recode_splice_batch: arguments checked before a device is touched, spans and rep taken from host memory,
+ *     out_index (may be NULL) with index_cap entries, the rest as mh_recode_edit_batch (index-free streams over
+ *     MH_BATCH_WALK_MAX_BITS are indexed first).
+ * Left out: order 2; pure insertions (begin == end); a replacement per span or per pattern.
+ * --------------------------------------------------------------------------------------------------------------------- */
+#define MH_SPLICE_MAX_REP 255u
+size_t mh_dev_recode_splice_workspace(size_t n_streams, uint64_t sym_total, uint32_t chunk_symbols, uint64_t n_spans);
+int mh_dev_recode_splice_batch(const mh_model *src, const mh_model *dst, const uint8_t *d_payload, const uint64_t *d_pay_off,
+                               const uint64_t *d_nbits, size_t n_streams, uint64_t pay_total, uint8_t prev0, uint64_t *d_sym_off,
+                               uint64_t sym_total, const uint64_t *d_index, uint32_t chunk_symbols, const uint64_t *d_span_off,
+                               const uint64_t *d_spans, const uint8_t *d_rep, uint32_t rep_len, uint8_t *d_out_payload,
+                               size_t cap, uint64_t *d_out_off, uint64_t *d_out_nbits, uint64_t *d_out_sym_off,
+                               uint64_t *d_out_index, uint64_t index_cap, uint64_t *d_dropped, int32_t *d_stream_status,
+                               void *d_ws, size_t ws_bytes, void *stream);
+int mh_dev_recode_splice_each(const mh_model_set *src, const mh_model *dst, const uint8_t *d_payload, const uint64_t *d_pay_off,
+                              const uint64_t *d_nbits, size_t n_streams, uint64_t pay_total, uint8_t prev0, uint64_t *d_sym_off,
+                              uint64_t sym_total, const uint64_t *d_index, uint32_t chunk_symbols, const uint64_t *d_span_off,
+                              const uint64_t *d_spans, const uint8_t *d_rep, uint32_t rep_len, uint8_t *d_out_payload,
+                              size_t cap, uint64_t *d_out_off, uint64_t *d_out_nbits, uint64_t *d_out_sym_off,
+                              uint64_t *d_out_index, uint64_t index_cap, uint64_t *d_dropped, int32_t *d_stream_status,
+                              void *d_ws, size_t ws_bytes, void *stream);
+int mh_recode_splice_batch(const mh_model *src, const mh_model *dst, const uint8_t *payload, const uint64_t *pay_off,
+                           const uint64_t *nbits, size_t n_streams, uint8_t prev0, uint64_t *sym_off, const uint64_t *index,
+                           uint32_t chunk_symbols, const uint64_t *span_off, const uint64_t *spans, const uint8_t *rep,
+                           uint32_t rep_len, uint8_t *out_payload, size_t cap, uint64_t *out_off, uint64_t *out_nbits,
+                           uint64_t *out_sym_off, uint64_t *out_index, uint64_t index_cap, uint64_t *dropped,
+                           int32_t *stream_status);
 
 /* ---------------------------------------------------------------------------------------------------------------------
  * SEGMENT STATES OF INDEX-FREE ORDER-2 BATCHES (extension, parity unpinned) — the _o2 twins of the segment-state calls of

@@ -74,6 +74,7 @@ EXPORTS = [
     "mh_find_dict_batch", "mh_find_dict_batch_o2",
     "mh_spans_from_hits", "mh_dev_spans_from_hits_workspace", "mh_dev_spans_from_hits", "mh_dev_recode_edit_workspace",
     "mh_dev_recode_edit_batch", "mh_dev_recode_edit_each", "mh_recode_edit_batch",
+    "mh_dev_recode_splice_workspace", "mh_dev_recode_splice_batch", "mh_dev_recode_splice_each", "mh_recode_splice_batch",
 ]
 FIND_MAX_POSITIONS = 64                    # include/mh.h MH_FIND_MAX_POSITIONS
 FIND_FOLD_ASCII = 1                        # include/mh.h MH_FIND_FOLD_ASCII
@@ -353,6 +354,11 @@ def lib():
         for fn in (l.mh_dev_recode_edit_batch, l.mh_dev_recode_edit_each):
             fn.argtypes = l.mh_dev_recode_batch.argtypes[:12] + [vp, vp, vp] + l.mh_dev_recode_batch.argtypes[12:]
         l.mh_recode_edit_batch.argtypes = l.mh_recode_batch.argtypes[:10] + [vp, vp, vp] + l.mh_recode_batch.argtypes[10:]
+        l.mh_dev_recode_splice_workspace.argtypes = [sz, u64, u32, u64]
+        l.mh_dev_recode_splice_workspace.restype = sz
+        for fn in (l.mh_dev_recode_splice_batch, l.mh_dev_recode_splice_each):
+            fn.argtypes = l.mh_dev_recode_batch.argtypes[:12] + [vp, vp, vp, u32, vp, sz, vp, vp, vp, vp, u64, vp, vp, vp, sz, vp]
+        l.mh_recode_splice_batch.argtypes = l.mh_recode_batch.argtypes[:10] + [vp, vp, vp, u32, vp, sz, vp, vp, vp, vp, u64, vp, vp]
         _lib = l
     return _lib
 
@@ -964,6 +970,83 @@ def _dev_recode_edit(fn, src, dst, payload, pay_off, nbits, byte_map, span_off, 
     return _dev_recode(call, src, dst, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols, ws_fn=lib().mh_dev_recode_edit_workspace, **kw)
 
 
+# ---- splicing batches (include/mh.h, "SPLICING BATCHES") -------------------------------------------------------------------
+SPLICE_MAX_REP = 255                       # include/mh.h MH_SPLICE_MAX_REP
+
+
+def _dev_recode_splice(fn, src, dst, payload, pay_off, nbits, rep, span_off, spans, prev0, sym_off, index, chunk_symbols, cap=None,
+                       count_only=False, want_index=True, index_cap=None, n_spans=None):
+    """One mh_dev_recode_splice_batch / _each call with guards around every output, as _dev_recode puts them.  cap None or
+    index_cap None: a count-only call first, then one with exactly out_off[n] bytes and (out_sym_off[n] // chunk) + n entries of
+    room.  Returns the dict of _dev_recode and out_sym_off[n + 1].  Asserts that nothing changed outside out_off[n] payload
+    bytes, the n + 1 offsets, the n lengths and counts and the index slices, laid out by out_sym_off, of the streams that
+    passed and did not become empty."""
+    l = lib()
+    n, pay_total, d_pl, d_po, d_nb, so, d_idx = _dev_source(payload, pay_off, nbits, sym_off, index)
+    indexed = index is not None
+    G, F = FIND_GUARD, FIND_FILL
+    sof = np.ascontiguousarray(span_off, dtype=np.uint64)
+    sp = np.zeros(0, dtype=np.uint64) if spans is None else np.ascontiguousarray(spans, dtype=np.uint64).reshape(-1)
+    r = _u8(rep)
+    d_sof = DeviceBuffer(sof.nbytes, sof)
+    d_sp = DeviceBuffer(max(sp.nbytes, 16), sp if sp.size else None)
+    d_rep = DeviceBuffer(max(r.size, 16), np.concatenate([r, np.zeros(16, dtype=np.uint8)])[:max(r.size, 16)]) if r.size else None
+    d_st = DeviceBuffer(max(n, 1) * 4, np.full(max(n, 1), 99, dtype=np.int32))
+    st = int(so[n]) if indexed else 0
+    ns = sp.size // 2 if n_spans is None else n_spans
+
+    def call(room, with_payload, nidx):
+        d_so = DeviceBuffer((n + 1 + G) * 8, np.concatenate([so if indexed else np.full(n + 1, F, dtype=np.uint64), np.full(G, F, dtype=np.uint64)]))
+        wsb = l.mh_dev_recode_splice_workspace(n, st, chunk_symbols if indexed else 0, ns)
+        d_ws = DeviceBuffer(wsb)
+        d_out = DeviceBuffer(room + RANGE_GUARD + 16, np.full(room + RANGE_GUARD + 16, RANGE_FILL, dtype=np.uint8)) if with_payload else None
+        d_oo = DeviceBuffer((n + 1 + G) * 8, np.full(n + 1 + G, F, dtype=np.uint64))
+        d_oso = DeviceBuffer((n + 1 + G) * 8, np.full(n + 1 + G, F, dtype=np.uint64))
+        d_onb = DeviceBuffer((n + G) * 8, np.full(n + G, F, dtype=np.uint64))
+        d_dr = DeviceBuffer((n + G) * 8, np.full(n + G, F, dtype=np.uint64))
+        d_oi = DeviceBuffer((nidx + G) * 8, np.full(nidx + G, F, dtype=np.uint64)) if nidx is not None else None
+        _check(fn(src, dst, d_pl.ptr, d_po.ptr, d_nb.ptr, n, pay_total, prev0, d_so.ptr, st, d_idx.ptr if d_idx else None, chunk_symbols,
+                  d_sof.ptr, d_sp.ptr, d_rep.ptr if d_rep else None, r.size, d_out.ptr if d_out else None, room, d_oo.ptr, d_onb.ptr, d_oso.ptr,
+                  d_oi.ptr if d_oi else None, nidx or 0, d_dr.ptr, d_st.ptr, d_ws.ptr, wsb, None), "mh_dev_recode_splice_*")
+        rc = l.mh_dev_status(d_ws.ptr, None)
+        oo, onb, dr, dso = d_oo.download(np.uint64), d_onb.download(np.uint64), d_dr.download(np.uint64), d_so.download(np.uint64)
+        oso = d_oso.download(np.uint64)
+        status = d_st.download(np.int32)[:n]
+        assert (oo[n + 1:] == F).all() and (onb[n:] == F).all() and (dr[n:] == F).all() and (dso[n + 1:] == F).all() and (oso[n + 1:] == F).all(), \
+            "words written behind an output"
+        if indexed:
+            assert np.array_equal(dso[:n + 1], so), "sym_off written with an index"
+        res = dict(out_off=oo[:n + 1], nbits=onb[:n], dropped=dr[:n], status=status, sym_off=dso[:n + 1], out_sym_off=oso[:n + 1], rc=rc,
+                   payload=None, index=None)
+        if d_out:
+            out = d_out.download(np.uint8)
+            used = min(int(oo[n]), room) if rc != MH_ERR_CAPACITY else 0
+            assert (out[used:] == RANGE_FILL).all(), "bytes written at or beyond min(cap, out_off[n])"
+            res["payload"] = out[:used].copy()
+        if d_oi:
+            oi = d_oi.download(np.uint64)
+            mine = np.zeros(nidx + G, dtype=bool)
+            if rc != MH_ERR_CAPACITY and oso[n] != F:
+                for i in range(n):
+                    if status[i] == MH_OK:
+                        b = int(oso[i]) // chunk_symbols + i
+                        mine[b:b + (int(oso[i + 1] - oso[i]) + chunk_symbols - 1) // chunk_symbols] = True
+            assert (oi[~mine] == F).all(), "index entries written outside the slices of the streams that passed"
+            res["index"] = oi[:nidx]
+        return res
+
+    with_index = want_index and bool(chunk_symbols)
+    if count_only:
+        return call(0, False, index_cap if with_index else None)
+    if cap is None or (with_index and index_cap is None):
+        pre = call(0, False, None)
+        if cap is None:
+            cap = int(pre["out_off"][n])
+        if index_cap is None and with_index:
+            index_cap = int(pre["out_sym_off"][n]) // chunk_symbols + n
+    return call(cap, True, index_cap if with_index else None)
+
+
 def spans_from_hits(hit_off, hits, hit_cap=None):
     """mh_spans_from_hits (host, no device): the records of a find call, (hit_off[n + 1], hits[k, 3]), merged into maximal
     spans: (span_off[n + 1], spans[m, 2], return code).  hit_cap None: the number of records given."""
@@ -1329,6 +1412,54 @@ class Model:
         everywhere).  The dict of _dev_recode, with its guards."""
         return _dev_recode_edit(lib().mh_dev_recode_edit_batch, self._h, dst.handle, payload, pay_off, nbits, byte_map, span_off, spans, prev0,
                                 sym_off, index, chunk_symbols, **kw)
+
+    def dev_recode_splice_batch(self, dst, payload, pay_off, nbits, rep, span_off, spans, prev0=PREV0, sym_off=None, index=None,
+                                chunk_symbols=0, **kw):
+        """One mh_dev_recode_splice_batch call: dev_recode_batch with every span replaced by `rep` (b"": deleted).  The dict of
+        _dev_recode_splice (out_sym_off and the index laid out by it included), with its guards."""
+        return _dev_recode_splice(lib().mh_dev_recode_splice_batch, self._h, dst.handle, payload, pay_off, nbits, rep, span_off, spans, prev0,
+                                  sym_off, index, chunk_symbols, **kw)
+
+    def recode_splice_batch(self, dst, payload, pay_off, nbits, rep, span_off, spans, prev0=PREV0, sym_off=None, index=None, chunk_symbols=0,
+                            cap=None, want_index=True, index_cap=None, check=True):
+        """mh_recode_splice_batch (host form): the dict of _recode_batch and out_sym_off[n + 1].  cap / index_cap None: room for
+        the worst case, every span one byte wide and replaced."""
+        l = lib()
+        payload = _u8(payload)
+        pay_off = np.ascontiguousarray(pay_off, dtype=np.uint64)
+        nbits = np.ascontiguousarray(nbits, dtype=np.uint64)
+        n = len(pay_off) - 1
+        sof = np.ascontiguousarray(span_off, dtype=np.uint64)
+        sp = np.zeros(0, dtype=np.uint64) if spans is None else np.ascontiguousarray(spans, dtype=np.uint64).reshape(-1)
+        r = _u8(rep)
+        idx = np.ascontiguousarray(index, dtype=np.uint64) if index is not None else None
+        if idx is not None:
+            so = np.ascontiguousarray(sym_off, dtype=np.uint64).copy()
+            bound = int(so[n])
+        else:
+            so = np.zeros(n + 1, dtype=np.uint64)
+            bound = int(sum(int(b) // max(self.min_code_len, 1) for b in nbits))
+        bound += (sp.size // 2) * int(r.size)
+        if cap is None:
+            cap = l.mh_encode_batch_bound(dst.handle, bound, n)
+        out = np.zeros(max(cap, 1), dtype=np.uint8)
+        oo, onb, dr = np.zeros(n + 1, dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint64)
+        oso = np.zeros(n + 1, dtype=np.uint64)
+        st = np.zeros(max(n, 1), dtype=np.int32)
+        oi = None
+        if want_index and chunk_symbols:
+            if index_cap is None:
+                index_cap = int(l.mh_batch_index_capacity(bound, n, chunk_symbols))
+            oi = np.full(max(index_cap, 1), FIND_FILL, dtype=np.uint64)
+        rc = l.mh_recode_splice_batch(self._h, dst.handle, _ptr(payload), pay_off.ctypes.data, nbits.ctypes.data if n else None, n, prev0,
+                                      so.ctypes.data, (idx.ctypes.data if idx.size else pay_off.ctypes.data) if idx is not None else None,
+                                      chunk_symbols, sof.ctypes.data, _ptr(sp), _ptr(r), r.size, out.ctypes.data, cap, oo.ctypes.data,
+                                      onb.ctypes.data, oso.ctypes.data, oi.ctypes.data if oi is not None else None, index_cap or 0, dr.ctypes.data,
+                                      st.ctypes.data)
+        if rc != MH_OK and (check or not (st[:n].any() or rc == MH_ERR_CAPACITY)):
+            raise MhError(rc, "mh_recode_splice_batch")
+        return dict(payload=out[:min(int(oo[n]), cap)], out_off=oo, nbits=onb[:n], index=oi, dropped=dr[:n], status=st[:n], sym_off=so,
+                    out_sym_off=oso, rc=rc)
 
     def recode_edit_batch(self, dst, payload, pay_off, nbits, byte_map, span_off=None, spans=None, prev0=PREV0, sym_off=None, index=None,
                           chunk_symbols=0, cap=None, want_index=True, check=True):
@@ -1829,6 +1960,12 @@ class ModelSet:
         """One mh_dev_recode_edit_each call: recode with map[b] coded for every byte b inside the spans: the dict of _dev_recode."""
         return _dev_recode_edit(lib().mh_dev_recode_edit_each, self._h, dst.handle, payload, pay_off, nbits, byte_map, span_off, spans, prev0,
                                 sym_off, index, chunk_symbols, **kw)
+
+    def recode_splice(self, dst, payload, pay_off, nbits, rep, span_off, spans, prev0=PREV0, sym_off=None, index=None, chunk_symbols=0, **kw):
+        """One mh_dev_recode_splice_each call: recode with every span replaced by `rep` (b"": deleted): the dict of
+        _dev_recode_splice."""
+        return _dev_recode_splice(lib().mh_dev_recode_splice_each, self._h, dst.handle, payload, pay_off, nbits, rep, span_off, spans, prev0,
+                                  sym_off, index, chunk_symbols, **kw)
 
     # ---- banks of shared models (include/mh.h, "BANKS OF SHARED MODELS"): this set is the bank, its streams the entries ----
     @classmethod

@@ -1,6 +1,7 @@
 // mh_api_recode.cpp — the re-coding calls of the C ABI (include/mh.h, "RE-CODING BATCHES" and the re-coding part of "ORDER 2
 // IN SEARCH AND RE-CODING"): the training histogram of a compressed batch and the batch coded again under another model,
-// under one shared source model of any order or a model set (kernels: mh_recode.hip), and the host-buffer forms.  The order
+// under one shared source model of any order or a model set (kernels: mh_recode.hip), with the edits of "EDITING BATCHES" and
+// the splices of "SPLICING BATCHES", and the host-buffer forms.  The order
 // rules of an entry point are in that entry point; everything behind them is here once.
 #include "mh_api_reader.hpp"
 #include "mh_recode.h"
@@ -87,6 +88,63 @@ mhr::Edit edit_of(const uint64_t *d_span_off, const uint64_t *d_spans, const uin
     return mhr::Edit{reinterpret_cast<const unsigned long long *>(d_span_off), reinterpret_cast<const unsigned long long *>(d_spans), d_map, 0u};
 }
 
+// the splice of a _splice call as the caller names it
+struct SpliceArgs {
+    const uint64_t *span_off, *spans;
+    const uint8_t *rep;
+    uint32_t rep_len;
+    uint64_t *out_sym_off;
+    uint64_t index_cap;
+    uint64_t n_spans;                   // host forms: what the workspace is sized for
+};
+
+// what a _splice entry point refuses before anything else: order 2 on either side (m: null under a set), the replacement
+int splice_args(const mh_model *m, const mh_model_set *set, size_t n, const mh_model *dst, const SpliceArgs &s) {
+    if (set ? n != set->d.n : !order01(m)) return MH_ERR_ARG;
+    if (!order01(dst)) return MH_ERR_ARG;
+    if (s.rep_len > MH_SPLICE_MAX_REP || (s.rep_len && !s.rep) || !s.span_off || !s.out_sym_off) return MH_ERR_ARG;
+    return MH_OK;
+}
+
+// behind splice_args: recode() with the splice in place of the edit, its own workspace layout and out_sym_off
+int splice(const mh_model *m, const mh_model_set *set, const mh_model *dst, const SpliceArgs &s, const CodedBatch &a, uint8_t *d_out_payload,
+           size_t cap, uint64_t *d_out_off, uint64_t *d_out_nbits, uint64_t *d_out_index, uint64_t *d_dropped, int32_t *d_stream_status, void *d_ws,
+           size_t ws_bytes, void *stream) {
+    if (!d_out_off || (!d_out_nbits && a.n)) return MH_ERR_ARG;
+    if (!a.index && !a.sym_off) return MH_ERR_ARG;                    // index-free: the decoded lengths are an output
+    if (!aligned16(d_out_payload)) return MH_ERR_ARG;
+    int oshift = 0;                                                   // index-free: the chunk size is the destination index's
+    if (!a.index && d_out_index && (oshift = chunk_shift_of(a.chunk_symbols)) < 0) return MH_ERR_ARG;
+    mhr::SpliceParams p{};
+    const mhr::SpliceLayout L = mhr::splice_layout(a.n, work_items_of(a), 0);
+    const int rc = dev_batch_params(a, SymOff::Through, ctx_of_prev0(m, a.prev0), d_ws, ws_bytes, L.total, L.off_status, d_stream_status, p.s.b);
+    if (rc != MH_OK) return rc;
+    if (a.index) oshift = int(p.s.b.chunk_shift);
+    p.out = d_out_payload; p.cap = d_out_payload ? cap : 0;
+    p.out_off = reinterpret_cast<unsigned long long *>(d_out_off);
+    p.out_nbits = reinterpret_cast<unsigned long long *>(d_out_nbits);
+    p.out_index = reinterpret_cast<unsigned long long *>(d_out_index);
+    p.dropped = reinterpret_cast<unsigned long long *>(d_dropped);
+    p.out_chunk_shift = uint32_t(oshift);
+    if (dst->max_len > mh::MAX_CODE_BITS) return MH_ERR_CODE_TOO_LONG;
+    mhb::Model model;
+    const int t = source_tables(m, set, p.s, model);
+    if (t != MH_OK) return t;
+    if (!dst->d_len8 || !dst->d_code64) return MH_ERR_NO_DEVICE;
+    p.dst.len8 = dst->d_len8;
+    p.dst.code64 = reinterpret_cast<const unsigned long long *>(dst->d_code64);
+    p.dst.enc64 = nullptr;
+    p.dst.ctx_mask = dst->type ? 0xFFu : 0u;
+    p.sp.span_off = reinterpret_cast<const unsigned long long *>(s.span_off);
+    p.sp.spans = reinterpret_cast<const unsigned long long *>(s.spans);
+    p.sp.rep = s.rep;
+    p.sp.rep_len = s.rep_len;
+    p.sp.out_sym_off = reinterpret_cast<unsigned long long *>(s.out_sym_off);
+    p.sp.index_cap = s.index_cap;
+    HIP_TRY(mhr::launch_recode_splice(p, model, d_ws, ws_bytes, static_cast<hipStream_t>(stream)));
+    return MH_OK;
+}
+
 size_t recode_workspace(size_t n_streams, uint64_t sym_total, uint32_t chunk_symbols, bool seam) {
     const uint64_t W = chunk_shift_of(chunk_symbols) >= 0 ? mhb::work_items(n_streams, sym_total, chunk_symbols) : 0;
     return mhr::recode_layout(n_streams, W, seam).total;
@@ -113,7 +171,8 @@ int host_args(const mh_model *src, const mh_model *dst, CodedBatch &a, bool inde
 // caller wants it.
 struct HostRecode {
     DevBatch db;
-    DevBuf d_out, d_oo, d_onb, d_oidx, d_drop, d_st, d_ws;
+    DevBuf d_out, d_oo, d_onb, d_oidx, d_drop, d_st, d_ws, d_oso;
+    const SpliceArgs *spl = nullptr;    // a _splice call: spans and rep on the device, out_sym_off the caller's (set before run)
     std::vector<int32_t> sst;           // per-stream verdicts
     std::vector<uint64_t> drop;         // per-stream dropped symbols
     size_t noidx = 0, dcap = 0;         // entries of the destination index, bytes of the payload buffer
@@ -124,8 +183,9 @@ struct HostRecode {
             size_t cap, uint64_t *out_off, uint64_t *out_nbits, const uint64_t *out_index) {
         const hipStream_t st = nullptr;
         const size_t n = a.n;
-        noidx = out_index ? size_t(mh_batch_index_capacity(a.sym_total, n, a.chunk_symbols)) : 0;
-        const size_t wsb = recode_workspace(n, a.sym_total, a.index ? a.chunk_symbols : 0, seam);
+        noidx = !out_index ? 0 : (spl ? size_t(spl->index_cap) : size_t(mh_batch_index_capacity(a.sym_total, n, a.chunk_symbols)));
+        const size_t wsb = spl ? mhr::splice_layout(n, work_items_of(a), spl->n_spans).total
+                               : recode_workspace(n, a.sym_total, a.index ? a.chunk_symbols : 0, seam);
         dcap = want_payload ? cap : 0;
         HIP_TRY(d_out.alloc(dcap));
         HIP_TRY(d_oo.alloc((n + 1) * 8));
@@ -134,11 +194,19 @@ struct HostRecode {
         HIP_TRY(d_drop.alloc(n * 8));
         HIP_TRY(d_st.alloc(n * 4));
         HIP_TRY(d_ws.alloc(wsb));
+        if (spl) HIP_TRY(d_oso.alloc((n + 1) * 8));
         int rc = db.upload(a, st);
         if (rc != MH_OK) return rc;
         if (noidx) HIP_TRY(hipMemcpy(d_oidx.p, out_index, noidx * 8, hipMemcpyHostToDevice));   // gap entries stay what the caller had
-        rc = recode(src, nullptr, dst, seam, ed, db.d, want_payload ? d_out.as<uint8_t>() : nullptr, dcap, d_oo.as<uint64_t>(), d_onb.as<uint64_t>(),
-                    out_index ? d_oidx.as<uint64_t>() : nullptr, d_drop.as<uint64_t>(), d_st.as<int32_t>(), d_ws.p, wsb, st);
+        if (spl) {
+            SpliceArgs d = *spl;
+            d.out_sym_off = d_oso.as<uint64_t>();
+            rc = splice(src, nullptr, dst, d, db.d, want_payload ? d_out.as<uint8_t>() : nullptr, dcap, d_oo.as<uint64_t>(), d_onb.as<uint64_t>(),
+                        out_index ? d_oidx.as<uint64_t>() : nullptr, d_drop.as<uint64_t>(), d_st.as<int32_t>(), d_ws.p, wsb, st);
+        } else {
+            rc = recode(src, nullptr, dst, seam, ed, db.d, want_payload ? d_out.as<uint8_t>() : nullptr, dcap, d_oo.as<uint64_t>(), d_onb.as<uint64_t>(),
+                        out_index ? d_oidx.as<uint64_t>() : nullptr, d_drop.as<uint64_t>(), d_st.as<int32_t>(), d_ws.p, wsb, st);
+        }
         if (rc != MH_OK) return rc;
         dev_rc = mh_dev_status(d_ws.p, st);
         sst.resize(n);
@@ -148,6 +216,7 @@ struct HostRecode {
         if (n) HIP_TRY(hipMemcpy(out_nbits, d_onb.p, n * 8, hipMemcpyDeviceToHost));
         if (n) HIP_TRY(hipMemcpy(drop.data(), d_drop.p, n * 8, hipMemcpyDeviceToHost));
         if (!a.index) HIP_TRY(hipMemcpy(sym_off, db.so.p, (n + 1) * 8, hipMemcpyDeviceToHost));
+        if (spl) HIP_TRY(hipMemcpy(spl->out_sym_off, d_oso.p, (n + 1) * 8, hipMemcpyDeviceToHost));
         return MH_OK;
     }
 
@@ -373,6 +442,72 @@ int mh_recode_edit_batch(const mh_model *src, const mh_model *dst, const uint8_t
     const mhr::Edit ed = edit_of(span_off ? d_soff.as<uint64_t>() : nullptr, d_sp.as<uint64_t>(), d_map.as<uint8_t>());
     HostRecode hr;
     rc = hr.run(false, &ed, src, dst, a, sym_off, out_payload != nullptr, cap, out_off, out_nbits, out_index);
+    if (rc != MH_OK) return rc;
+    if ((rc = hr.payload(out_payload, out_off[n_streams])) != MH_OK || (rc = hr.slices(out_index)) != MH_OK) return rc;
+    return hr.finish(idx_st, dropped, stream_status);
+}
+
+/* ----------------------------------------------------------------------------------------------------- splice */
+
+size_t mh_dev_recode_splice_workspace(size_t n_streams, uint64_t sym_total, uint32_t chunk_symbols, uint64_t n_spans) {
+    const uint64_t W = chunk_shift_of(chunk_symbols) >= 0 ? mhb::work_items(n_streams, sym_total, chunk_symbols) : 0;
+    return mhr::splice_layout(n_streams, W, n_spans).total;
+}
+
+int mh_dev_recode_splice_batch(const mh_model *src, const mh_model *dst, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits,
+                               size_t n_streams, uint64_t pay_total, uint8_t prev0, uint64_t *d_sym_off, uint64_t sym_total, const uint64_t *d_index,
+                               uint32_t chunk_symbols, const uint64_t *d_span_off, const uint64_t *d_spans, const uint8_t *d_rep, uint32_t rep_len,
+                               uint8_t *d_out_payload, size_t cap, uint64_t *d_out_off, uint64_t *d_out_nbits, uint64_t *d_out_sym_off,
+                               uint64_t *d_out_index, uint64_t index_cap, uint64_t *d_dropped, int32_t *d_stream_status, void *d_ws, size_t ws_bytes,
+                               void *stream) {
+    const SpliceArgs s{d_span_off, d_spans, d_rep, rep_len, d_out_sym_off, index_cap, 0};
+    const int rc = splice_args(src, nullptr, n_streams, dst, s);
+    if (rc != MH_OK) return rc;
+    return splice(src, nullptr, dst, s, {d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index, chunk_symbols},
+                  d_out_payload, cap, d_out_off, d_out_nbits, d_out_index, d_dropped, d_stream_status, d_ws, ws_bytes, stream);
+}
+
+int mh_dev_recode_splice_each(const mh_model_set *src, const mh_model *dst, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits,
+                              size_t n_streams, uint64_t pay_total, uint8_t prev0, uint64_t *d_sym_off, uint64_t sym_total, const uint64_t *d_index,
+                              uint32_t chunk_symbols, const uint64_t *d_span_off, const uint64_t *d_spans, const uint8_t *d_rep, uint32_t rep_len,
+                              uint8_t *d_out_payload, size_t cap, uint64_t *d_out_off, uint64_t *d_out_nbits, uint64_t *d_out_sym_off,
+                              uint64_t *d_out_index, uint64_t index_cap, uint64_t *d_dropped, int32_t *d_stream_status, void *d_ws, size_t ws_bytes,
+                              void *stream) {
+    if (!src) return MH_ERR_ARG;
+    const SpliceArgs s{d_span_off, d_spans, d_rep, rep_len, d_out_sym_off, index_cap, 0};
+    const int rc = splice_args(nullptr, src, n_streams, dst, s);
+    if (rc != MH_OK) return rc;
+    return splice(nullptr, src, dst, s, {d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index, chunk_symbols},
+                  d_out_payload, cap, d_out_off, d_out_nbits, d_out_index, d_dropped, d_stream_status, d_ws, ws_bytes, stream);
+}
+
+int mh_recode_splice_batch(const mh_model *src, const mh_model *dst, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits,
+                           size_t n_streams, uint8_t prev0, uint64_t *sym_off, const uint64_t *index, uint32_t chunk_symbols,
+                           const uint64_t *span_off, const uint64_t *spans, const uint8_t *rep, uint32_t rep_len, uint8_t *out_payload, size_t cap,
+                           uint64_t *out_off, uint64_t *out_nbits, uint64_t *out_sym_off, uint64_t *out_index, uint64_t index_cap, uint64_t *dropped,
+                           int32_t *stream_status) {
+    SpliceArgs s{span_off, spans, rep, rep_len, out_sym_off, out_index ? index_cap : 0, 0};
+    int rc = splice_args(src, nullptr, n_streams, dst, s);
+    if (rc != MH_OK) return rc;
+    if (!offsets_ok(span_off, n_streams) || (span_off[n_streams] && !spans)) return MH_ERR_ARG;
+    // (a span's positions do not depend on the index that an over-cap batch gets first)
+    CodedBatch a{payload, pay_off, nbits, n_streams, 0, prev0, sym_off, 0, index, chunk_symbols};
+    std::vector<uint64_t> own_idx;
+    std::vector<int32_t> idx_st;
+    rc = host_args(src, dst, a, true, out_off, out_nbits, out_index, sym_off, own_idx, idx_st);
+    if (rc != MH_OK) return rc;
+    DevBuf d_soff, d_sp, d_rep;
+    s.n_spans = span_off[n_streams];
+    HIP_TRY(d_soff.alloc((n_streams + 1) * 8));
+    HIP_TRY(d_sp.alloc(size_t(s.n_spans) * 16));
+    HIP_TRY(d_rep.alloc(rep_len));
+    HIP_TRY(hipMemcpy(d_soff.p, span_off, (n_streams + 1) * 8, hipMemcpyHostToDevice));
+    if (s.n_spans) HIP_TRY(hipMemcpy(d_sp.p, spans, size_t(s.n_spans) * 16, hipMemcpyHostToDevice));
+    if (rep_len) HIP_TRY(hipMemcpy(d_rep.p, rep, rep_len, hipMemcpyHostToDevice));
+    s.span_off = d_soff.as<uint64_t>(); s.spans = d_sp.as<uint64_t>(); s.rep = rep_len ? d_rep.as<uint8_t>() : nullptr;
+    HostRecode hr;
+    hr.spl = &s;
+    rc = hr.run(false, nullptr, src, dst, a, sym_off, out_payload != nullptr, cap, out_off, out_nbits, out_index);
     if (rc != MH_OK) return rc;
     if ((rc = hr.payload(out_payload, out_off[n_streams])) != MH_OK || (rc = hr.slices(out_index)) != MH_OK) return rc;
     return hr.finish(idx_st, dropped, stream_status);

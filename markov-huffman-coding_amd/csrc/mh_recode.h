@@ -97,6 +97,45 @@ struct EditParams : RecodeParams {
     Edit ed;
 };
 
+// the splice of a splicing re-code (include/mh.h, "SPLICING BATCHES"): every span of stream i that begins inside the decoded
+// message is replaced by the rep_len bytes of rep (0: deleted), so the output has its own lengths, out_sym_off, and its index
+// is laid out by output positions
+struct Splice {
+    const unsigned long long *span_off;   // n + 1
+    const unsigned long long *spans;
+    const uint8_t *rep;                   // rep_len bytes (may be nullptr when 0)
+    uint32_t rep_len;                     // 0 .. MH_SPLICE_MAX_REP
+    uint32_t rep_lds;                     // set by the launcher: rep has the map's 256 bytes of LDS behind the tables
+    uint64_t span_cap;                    // set by the launcher: the spans the workspace has room for (rep_len == 0)
+    unsigned long long *out_sym_off;      // n + 1 (written): the exclusive scan of the output lengths
+    uint64_t index_cap;                   // entries of out_index
+};
+
+struct SpliceParams : RecodeParams {
+    Splice sp;
+};
+
+// splice workspace: status block | per-stream status | per chunk number: destination bits (u64, W + 1, scanned in place),
+// output symbols (u64, W + 1, scanned in place), dropped symbols (u32) | the bits and drops of rep[1..] (2 x u32) | scan
+// block sums | per span: the destination context behind a deleted span (u32; written and read only when rep_len == 0).  The
+// spans come last: the call is not told their number, it takes what ws_bytes leaves behind off_sctx as its room
+struct SpliceLayout {
+    size_t off_status, off_bits, off_syms, off_drop, off_price, off_sums, off_sctx, total;
+};
+inline SpliceLayout splice_layout(uint64_t n_streams, uint64_t nwork, uint64_t n_spans) {
+    SpliceLayout l;
+    const uint64_t len = (nwork > n_streams ? nwork : n_streams) + 1;
+    l.off_status = 64;
+    l.off_bits = (l.off_status + size_t(n_streams) * 4 + 15) & ~size_t(15);
+    l.off_syms = l.off_bits + size_t(nwork + 1) * 8;
+    l.off_drop = l.off_syms + size_t(nwork + 1) * 8;
+    l.off_price = l.off_drop + size_t(nwork) * 4;
+    l.off_sums = (l.off_price + 8 + 15) & ~size_t(15);
+    l.off_sctx = l.off_sums + size_t(mhb::scan_blocks(len) + 1) * 8;
+    l.total = (l.off_sctx + size_t(n_spans) * 4 + 255) & ~size_t(255);
+    return l;
+}
+
 // spans from search records: status block | per record: the reverse min-scan of the begins (u64), span starts and, scanned in
 // place, span numbers (u64, cap + 2) | per tile of SPAN_TILE records: first stream, last stream, the first record's scan
 // value, the carry from the tiles behind | scan block sums | per stream: nothing beyond the offsets the caller passes
@@ -121,6 +160,8 @@ hipError_t launch_histogram_coded(const HistParams &p, mhb::Model model, void *d
 hipError_t launch_recode(const RecodeParams &p, mhb::Model model, void *d_ws, hipStream_t st);
 // the same with the edit applied; order 0/1 on both sides (an order-2 side is refused)
 hipError_t launch_recode_edit(const EditParams &p, mhb::Model model, void *d_ws, hipStream_t st);
+// the splice in place of the edit; order 0/1 on both sides, p.sp.span_off not null
+hipError_t launch_recode_splice(const SpliceParams &p, mhb::Model model, void *d_ws, size_t ws_bytes, hipStream_t st);
 // the records of a find call (ascending (stream, end, pattern)) merged into maximal spans; a total over hit_cap: the status
 // word is MHK_STATUS_CAPACITY, span_off all zeros
 hipError_t launch_spans_from_hits(const unsigned long long *hit_off, const unsigned long long *hits, uint64_t hit_cap, uint64_t n_streams,

@@ -16,6 +16,9 @@
 //   recode_spans_kernel      (EDIT, include/mh.h "EDITING BATCHES") the span lists, in front of the length pass: a stream whose
 //                            list is not ascending and disjoint is MH_ERR_ARG
 //   spans_*_kernel           search records merged into spans (mh_dev_spans_from_hits): see "span lists" below
+//   splice_*_kernel          (include/mh.h "SPLICING BATCHES") spans deleted or replaced by a string of another length: the
+//                            same stages with a second scan for output positions and an index laid out by them; see
+//                            "the splice" below
 //   histc_idx_kernel         one lane per (stream, chunk): counts the pairs as it decodes; a chunk that fails takes its own
 //                            counts back; <FIX>: the chunks that passed inside a stream that failed take theirs back
 //   histc_walk_kernel        index-free, one lane per stream: counts, and takes the stream's counts back when it fails
@@ -804,6 +807,419 @@ __global__ __launch_bounds__((Dec<K, W>::NT)) void recode_walk_kernel(Params<EDI
     }
 }
 
+// ------------------------------------------------------------------------------------------------ splice
+
+// the splice   (include/mh.h, "SPLICING BATCHES"; order 0/1 on both sides.)  A span that begins inside the message is replaced
+//              by rep (rep_len bytes, 0: deleted), so output positions are not source positions.  A lane keeps ctx (the true
+//              symbol, for dec.next) and dctx (the last output byte), as the edit does, and walks its symbols with a cursor of
+//              three states: outside a span (the symbol is coded), at a span's begin (rep is coded, the symbol is not), inside
+//              (nothing is coded).  The lane whose symbols contain a span's begin owns its replacement.  Indexed source, one lane
+//              per source chunk: the length pass counts the chunk's output symbols beside its bits, a second scan turns them
+//              into output positions, and the emit pass writes a destination index entry in front of every output symbol whose
+//              position is a multiple of the chunk size: each output boundary is met by exactly one lane.
+//   start      The destination context of a lane whose chunk starts at `first` is the last output byte in front of it.  With
+//              first - 1 in no span that is the entry's byte; in a span with rep_len > 0 it is rep's last byte; in a deleted
+//              span r it is the byte in front of the run of touching spans that ends with r, which lies mid-chunk in general.
+//              splice_back_kernel, launched only when rep_len == 0, finds it per span before the length pass: one lane per
+//              span that reaches over a chunk boundary walks back through the touching spans in front of it (bounded by the
+//              stream's span count) and decodes the chunk that holds begin - 1 up to that symbol (or reads the next chunk's
+//              entry when begin is a boundary).  The two hot kernels then look the byte up and keep no cross-lane dependency;
+//              the comb kernel stays a pure sum.  A decode that fails there stores nothing of value: the lane of that chunk
+//              fails the stream in the length pass.
+//   price      The bits and drops of rep[1..] are constants of the call (splice_price_kernel): the length pass prices rep[0]
+//              in dctx and adds them.
+// rep sits in the 256 bytes of LDS where the edit keeps its map (map_at), or is read from L2 when they do not fit.
+struct Cut {
+    const unsigned long long *off, *sp;
+    const uint8_t *rep;
+    uint32_t rep_len;
+    uint64_t r, rend, origin;
+    uint32_t b, e;                      // the span at r, as offsets from origin (saturated; ~0u: never)
+    bool own;                           // the span at r begins at or behind origin: the lane codes its replacement
+    __device__ __forceinline__ Cut(const SpliceParams &p, unsigned char *smem, uint32_t at)
+        : off(p.sp.span_off), sp(p.sp.spans), rep(p.sp.rep), rep_len(p.sp.rep_len), r(0), rend(0), origin(0), b(~0u), e(~0u), own(true) {
+        if (p.sp.rep_lds) {
+            for (uint32_t k = threadIdx.x; k < rep_len; k += blockDim.x) smem[at + k] = p.sp.rep[k];
+            __syncthreads();
+            rep = smem + at;
+        }
+    }
+    __device__ __forceinline__ uint32_t rel(uint64_t x) const {
+        return x <= origin ? 0u : (x - origin >= 0xFFFFFFFFull ? ~0u : uint32_t(x - origin));
+    }
+    __device__ __forceinline__ void load() {
+        if (r < rend) { b = rel(sp[2 * r]); e = rel(sp[2 * r + 1]); own = sp[2 * r] >= origin; } else { b = e = ~0u; }
+    }
+    // the first span of stream i that ends behind pos (Spans<true>::seek)
+    __device__ __forceinline__ void seek(uint64_t i, uint64_t pos) {
+        origin = pos;
+        uint64_t lo = off[i], hi = off[i + 1];
+        rend = hi;
+        while (lo < hi) {
+            const uint64_t mid = (lo + hi) >> 1;
+            if (sp[2 * mid + 1] > pos) hi = mid; else lo = mid + 1;
+        }
+        r = lo;
+        load();
+    }
+    // from a seek at pos - 1 to origin pos: at most one span ends there
+    __device__ __forceinline__ void step_origin() {
+        ++origin;
+        if (r < rend && sp[2 * r + 1] <= origin) ++r;
+        load();
+    }
+    // the symbol at origin + pos: 0 outside a span, 1 at a span's begin, 2 inside; pos goes up by one from the seek
+    __device__ __forceinline__ uint32_t state(uint32_t pos) {
+        if (pos >= e) { ++r; load(); }
+        return pos < b ? 0u : (pos == b && own ? 1u : 2u);
+    }
+};
+
+// The destination context as chunk c's lane starts (see "start" above); the cursor is left at the chunk's first symbol.
+__device__ __forceinline__ uint32_t splice_start(Cut &cu, const Chunk &c, const uint32_t *sctx) {
+    if (!c.first) { cu.seek(c.i, 0); return c.ctx; }
+    cu.seek(c.i, c.first - 1u);
+    uint32_t d = c.ctx;
+    if (cu.r < cu.rend && cu.b == 0u) d = cu.rep_len ? cu.rep[cu.rep_len - 1u] : sctx[cu.r];   // (b == 0: it begins at first - 1 or in front)
+    cu.step_origin();
+    return d;
+}
+
+__global__ __launch_bounds__(256) void splice_check_kernel(SpliceParams p, int *status, int *stop) {
+    const uint64_t i = mhb::gtid();
+    const uint64_t n = p.s.b.n;
+    if (i > n) return;
+    p.out_off[i] = 0;
+    p.sp.out_sym_off[i] = 0;
+    if (!p.s.b.index) p.s.b.sym_off[i] = 0;
+    if (i < n) {
+        p.out_nbits[i] = 0;
+        if (p.dropped) p.dropped[i] = 0;
+    }
+    mhb::check_batch(p.s.b, i, status, stop);
+}
+
+// recode_spans_kernel reads the list through EditParams: the same pointers, no map
+inline EditParams spans_view(const SpliceParams &p) {
+    EditParams e{};
+    static_cast<RecodeParams &>(e) = p;
+    e.ed.span_off = p.sp.span_off;
+    e.ed.spans = p.sp.spans;
+    return e;
+}
+
+// the bits and the drops of rep[1 .. rep_len): pair j in the context of rep[j - 1]
+__global__ __launch_bounds__(256) void splice_price_kernel(SpliceParams p, uint32_t *price) {
+    __shared__ uint32_t acc[2];
+    if (threadIdx.x < 2u) acc[threadIdx.x] = 0u;
+    __syncthreads();
+    const uint32_t j = threadIdx.x;
+    if (j >= 1u && j < p.sp.rep_len) {
+        const uint32_t l = p.dst.len8[((uint32_t(p.sp.rep[j - 1u]) & p.dst.ctx_mask) << 8) | p.sp.rep[j]];
+        atomicAdd(&acc[0], l);
+        if (!l) atomicAdd(&acc[1], 1u);
+    }
+    __syncthreads();
+    if (threadIdx.x < 2u) price[threadIdx.x] = acc[threadIdx.x];
+}
+
+// rep_len == 0, indexed: sctx[r] for every span r over a chunk boundary, the last output byte in front of the run of touching
+// spans that ends with r.  More spans than the workspace has room for: MHK_STATUS_CAPACITY and the call stops.
+template <Model K>
+__global__ __launch_bounds__((Dec<K, false>::NT)) void splice_back_kernel(SpliceParams p, uint32_t *sctx, int *status, int *stop) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    if (stopped(stop)) return;
+    Dec<K, false> dec(p.s, smem);
+    const unsigned long long *off = p.sp.span_off, *sp = p.sp.spans;
+    const uint64_t n = p.s.b.n, total = off[n];
+    if (total > p.sp.span_cap) {
+        if (gtid() == 0) { fail(status, mhk::MHK_STATUS_CAPACITY); atomicExch(stop, 1); }
+        return;
+    }
+    if (!n) return;
+    const uint32_t cs = p.s.b.chunk_shift;
+    for (uint64_t r = gtid(); r < total; r += uint64_t(gridDim.x) * blockDim.x) {
+        sctx[r] = 0u;
+        if ((sp[2 * r + 1] >> cs) == (sp[2 * r] >> cs)) continue;     // no chunk starts in (begin, end]: no lane asks
+        uint64_t lo = 0, hi = n - 1;                                  // the stream of span r (recode_spans_kernel)
+        while (lo < hi) {
+            const uint64_t mid = (lo + hi + 1) >> 1;
+            if (off[mid] <= r) lo = mid; else hi = mid - 1;
+        }
+        const uint64_t i = lo;
+        if (p.s.b.stream_status[i] != MH_OK) continue;
+        uint64_t r0 = r;
+        while (r0 > off[i] && sp[2 * r0 - 1] == sp[2 * r0]) --r0;
+        const uint64_t begin = sp[2 * r0];
+        const uint64_t a = p.s.b.sym_off[i], ni = p.s.b.sym_off[i + 1] - a;
+        if (begin >= ni) continue;                                    // the span is ignored
+        if (!begin) { sctx[r] = p.s.b.prev0; continue; }
+        const uint64_t wb = (a >> cs) + i, pos = begin - 1u;
+        if (!(begin & ((uint64_t(1) << cs) - 1u))) { sctx[r] = uint32_t(p.s.b.index[wb + (begin >> cs)] >> 56); continue; }
+        Chunk c;
+        if (!chunk_of<K, false>(p.s, wb + (pos >> cs), c) || !c.entry_ok()) continue;
+        uint64_t bit0;
+        const BitSrc src = mhb::stream_src(p.s.b.payload, p.s.b.pay_off[i], c.nb, bit0);
+        BitCursor bc;
+        bc.init(src, bit0 + c.start);
+        dec.stream(p.s, i);
+        uint32_t ctx = c.ctx, used = 0;
+        bool bad = false;
+        const uint32_t count = uint32_t(pos - c.first) + 1u;          // <= c.nsym: pos < ni
+        for (uint32_t t = 0; t < count && !bad; ++t) {
+            const uint32_t sym = dec.next(p.s, src, bc, ctx, used, bad);
+            if (bad) break;
+            ctx = sym;
+        }
+        sctx[r] = ctx;
+    }
+}
+
+// rep's bytes behind dctx: lengths and drops (length pass: rep[0] alone, the rest is priced)
+template <bool DLDS>
+__device__ __forceinline__ void rep_len_pass(const Enc<DLDS, false> &E, const Cut &cu, const uint32_t *price, uint32_t &dctx, uint32_t &bits,
+                                             uint32_t &drops, uint32_t &osym) {
+    if (!cu.rep_len) return;
+    const uint32_t l = E.len(E.at(dctx, cu.rep[0]));
+    bits += l + price[0];
+    drops += (l == 0u) + price[1];
+    osym += cu.rep_len;
+    dctx = cu.rep[cu.rep_len - 1u];
+}
+
+template <Model K, bool DLDS>
+__global__ __launch_bounds__((Dec<K, false>::NT)) void splice_idx_len_kernel(SpliceParams p, uint64_t nwork, uint32_t lds_at, unsigned long long *cbits,
+                                                                           unsigned long long *csyms, uint32_t *cdrop, const uint32_t *sctx,
+                                                                           const uint32_t *price, int *status, const int *stop) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    if (stopped(stop)) return;
+    Dec<K, false> dec(p.s, smem);
+    const Enc<DLDS, false> E(p.dst, smem, lds_at);
+    Cut cu(p, smem, map_at<DLDS>(p.dst, lds_at));
+    for (uint64_t w = gtid(); w < nwork; w += uint64_t(gridDim.x) * blockDim.x) {
+        Chunk c;
+        if (!chunk_of<K, false>(p.s, w, c) || p.s.b.stream_status[c.i] == MH_ERR_ARG) continue;
+        if (!c.entry_ok()) { stream_fail(p.s.b, status, c.i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT); continue; }
+        uint64_t bit0;
+        const BitSrc src = mhb::stream_src(p.s.b.payload, p.s.b.pay_off[c.i], c.nb, bit0);
+        BitCursor bc;
+        bc.init(src, bit0 + c.start);
+        dec.stream(p.s, c.i);
+        uint32_t ctx = c.ctx, used = 0, bits = 0, drops = 0, osym = 0;
+        uint32_t dctx = splice_start(cu, c, sctx);
+        bool bad = false;
+        for (uint32_t t = 0; t < c.nsym && !bad; ++t) {
+            const uint32_t sym = dec.next(p.s, src, bc, ctx, used, bad);
+            if (bad) break;
+            const uint32_t st = cu.state(t);
+            if (st == 0u) {
+                const uint32_t l = E.len(E.at(dctx, sym));
+                bits += l;
+                drops += l == 0u;
+                dctx = sym;
+                ++osym;
+            } else if (st == 1u) {
+                rep_len_pass<DLDS>(E, cu, price, dctx, bits, drops, osym);
+            }
+            ctx = sym;
+        }
+        if (bad || used != c.end - c.start) { stream_fail(p.s.b, status, c.i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT); continue; }
+        cbits[w] = bits;
+        csyms[w] = osym;
+        cdrop[w] = drops;
+    }
+}
+
+// the chunks of failed streams count no bits and no output symbols; the dropped symbols of the others go to dropped[i]
+__global__ __launch_bounds__(256) void splice_comb_kernel(SpliceParams p, uint64_t nwork, unsigned long long *cbits, unsigned long long *csyms,
+                                                          const uint32_t *cdrop, const int *stop) {
+    if (stopped(stop)) return;
+    const uint64_t w = gtid();
+    if (w > nwork) return;
+    unsigned long long v = 0, y = 0;
+    if (w < nwork) {
+        const uint32_t cs = p.s.b.chunk_shift;
+        const uint64_t i = find_stream(p.s.b.sym_off, p.s.b.n, cs, w);
+        if (i < p.s.b.n) {
+            const uint64_t a = p.s.b.sym_off[i], ni = p.s.b.sym_off[i + 1] - a;
+            const uint64_t k = w - ((a >> cs) + i);
+            if ((k << cs) < ni && p.s.b.stream_status[i] == MH_OK) {
+                v = cbits[w];
+                y = csyms[w];
+                const uint32_t d = cdrop[w];
+                if (d && p.dropped) atomicAdd(&p.dropped[i], static_cast<unsigned long long>(d));
+            }
+        }
+    }
+    cbits[w] = v;
+    csyms[w] = y;
+}
+
+// stream i: payload bits and bytes as recode_sizes_kernel; indexed: out_sym_off[i] is the scanned output symbols at the
+// stream's first chunk number (gaps and failed streams count none)
+__global__ __launch_bounds__(256) void splice_sizes_kernel(SpliceParams p, const unsigned long long *cbase, const unsigned long long *obase,
+                                                           const int *stop) {
+    if (mhb::stopped(stop)) return;
+    const uint64_t i = mhb::gtid();
+    const uint64_t n = p.s.b.n;
+    if (i > n) return;
+    if (p.s.b.index) p.sp.out_sym_off[i] = obase[(p.s.b.sym_off[i] >> p.s.b.chunk_shift) + i];
+    if (i == n) { p.out_off[i] = 0; return; }
+    unsigned long long bits;
+    if (p.s.b.index) {
+        const uint32_t cs = p.s.b.chunk_shift;
+        const uint64_t w0 = (p.s.b.sym_off[i] >> cs) + i, w1 = (p.s.b.sym_off[i + 1] >> cs) + i + 1;
+        bits = cbase[w1] - cbase[w0];
+        p.out_nbits[i] = bits;
+    } else {
+        bits = p.out_nbits[i];
+    }
+    p.out_off[i] = (bits + 7) >> 3;
+}
+
+// the destination index has index_cap entries; the output needs (out_sym_off[n] >> cs) + n (after the scans: offsets and
+// lengths are complete)
+__global__ void splice_cap_kernel(SpliceParams p, int *status, int *stop) {
+    if (mhb::stopped(stop)) return;
+    if ((p.sp.out_sym_off[p.s.b.n] >> p.out_chunk_shift) + p.s.b.n > p.sp.index_cap) { mhb::fail(status, mhk::MHK_STATUS_CAPACITY); atomicExch(stop, 1); }
+}
+
+// One output symbol of a lane's emit pass: the index entry in front of it when its position o is a chunk's first, its code.
+struct SpliceOut {
+    unsigned long long *slice;          // the stream's slice of the destination index, or nullptr
+    uint32_t ocs;
+    uint64_t o, bit;                    // stream-relative output position and bit
+    bool on;
+    template <bool DLDS>
+    __device__ __forceinline__ void put(const Enc<DLDS, false> &E, BitWriter &bw, uint32_t &dctx, uint32_t sym) {
+        if (slice && (o & ((uint64_t(1) << ocs) - 1u)) == 0) slice[o >> ocs] = E.entry(dctx, bit);
+        bit += E.put(bw, E.at(dctx, sym), on);
+        dctx = sym;
+        ++o;
+    }
+};
+
+template <Model K, bool DLDS>
+__global__ __launch_bounds__((Dec<K, false>::NT)) void splice_idx_emit_kernel(SpliceParams p, uint64_t nwork, uint32_t lds_at,
+                                                                            const unsigned long long *cbase, const unsigned long long *obase,
+                                                                            const uint32_t *sctx, uint32_t *tail, const int *stop) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    if (stopped(stop)) return;
+    Dec<K, false> dec(p.s, smem);
+    const Enc<DLDS, false> E(p.dst, smem, lds_at);
+    Cut cu(p, smem, map_at<DLDS>(p.dst, lds_at));
+    const uint64_t bytes = p.out_off[p.s.b.n];
+    const uint64_t tail_w = (bytes & 3u) ? bytes >> 2 : ~uint64_t(0);
+    const uint32_t cs = p.s.b.chunk_shift;
+    for (uint64_t w = gtid(); w < nwork; w += uint64_t(gridDim.x) * blockDim.x) {
+        Chunk c;
+        if (!chunk_of<K, false>(p.s, w, c) || p.s.b.stream_status[c.i] != MH_OK) continue;
+        if (obase[w + 1] == obase[w]) continue;                                   // a lane that produces nothing writes nothing
+        const uint64_t w0 = (p.s.b.sym_off[c.i] >> cs) + c.i;
+        SpliceOut so;
+        so.o = obase[w] - obase[w0];
+        so.bit = cbase[w] - cbase[w0];
+        so.ocs = cs;
+        so.on = p.out != nullptr;
+        so.slice = p.out_index ? p.out_index + (p.sp.out_sym_off[c.i] >> cs) + c.i : nullptr;
+        uint32_t dctx = splice_start(cu, c, sctx);
+        uint64_t bit0;
+        const BitSrc src = mhb::stream_src(p.s.b.payload, p.s.b.pay_off[c.i], c.nb, bit0);
+        BitCursor bc;
+        bc.init(src, bit0 + c.start);
+        dec.stream(p.s, c.i);
+        BitWriter bw;
+        if (so.on) bw.init(reinterpret_cast<uint32_t *>(p.out), tail, tail_w, uint64_t(p.out_off[c.i]) * 8u + so.bit);
+        uint32_t ctx = c.ctx, used = 0;
+        bool bad = false;
+        for (uint32_t t = 0; t < c.nsym && !bad; ++t) {            // (the stream passed: bad stays false)
+            const uint32_t sym = dec.next(p.s, src, bc, ctx, used, bad);
+            const uint32_t st = cu.state(t);
+            if (st == 0u) {
+                so.put<DLDS>(E, bw, dctx, sym);
+            } else if (st == 1u) {
+                for (uint32_t j = 0; j < cu.rep_len; ++j) so.put<DLDS>(E, bw, dctx, cu.rep[j]);
+            }
+            ctx = sym;
+        }
+        if (so.on) bw.finish();
+    }
+}
+
+// Index-free, one lane per stream (recode_walk_kernel).  EMIT = false: the verdict, the stream's symbols into sym_off[i] and
+// its output symbols into out_sym_off[i] (both scanned next), its dst bits and dropped symbols; true: codes and index entries.
+template <Model K, bool DLDS, bool EMIT>
+__global__ __launch_bounds__((Dec<K, false>::NT)) void splice_walk_kernel(SpliceParams p, uint32_t lds_at, uint32_t *tail, int *status, const int *stop) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    if (stopped(stop)) return;
+    Dec<K, false> dec(p.s, smem);
+    const Enc<DLDS, false> E(p.dst, smem, lds_at);
+    Cut cu(p, smem, map_at<DLDS>(p.dst, lds_at));
+    const uint64_t n = p.s.b.n;
+    const uint64_t bytes = EMIT ? p.out_off[n] : 0;
+    const uint64_t tail_w = (bytes & 3u) ? bytes >> 2 : ~uint64_t(0);
+    for (uint64_t i = gtid(); i < n; i += uint64_t(gridDim.x) * blockDim.x) {
+        if (p.s.b.stream_status[i] != MH_OK) continue;
+        const uint64_t nb = p.s.b.nbits[i];
+        uint64_t count = ~uint64_t(0);
+        if (EMIT) {
+            count = p.s.b.sym_off[i + 1] - p.s.b.sym_off[i];
+            if (p.sp.out_sym_off[i + 1] == p.sp.out_sym_off[i]) continue;
+        } else if (nb > p.s.b.walk_max_bits) {
+            stream_fail(p.s.b, status, i, MH_ERR_ARG, BATCH_STATUS_ARG);
+            continue;
+        }
+        uint64_t bit0;
+        const BitSrc src = mhb::stream_src(p.s.b.payload, p.s.b.pay_off[i], nb, bit0);
+        BitCursor bc;
+        bc.init(src, bit0);
+        dec.stream(p.s, i);
+        SpliceOut so;
+        so.o = 0; so.bit = 0; so.ocs = p.out_chunk_shift;
+        so.on = EMIT && p.out != nullptr;
+        so.slice = EMIT && p.out_index ? p.out_index + (p.sp.out_sym_off[i] >> so.ocs) + i : nullptr;
+        BitWriter bw;
+        if (so.on) bw.init(reinterpret_cast<uint32_t *>(p.out), tail, tail_w, uint64_t(p.out_off[i]) * 8u);
+        uint32_t ctx = start_ctx<K, false>(p.s), used = 0, drops = 0;
+        uint32_t dctx = ctx;
+        cu.seek(i, 0);
+        bool bad = false;
+        uint64_t k = 0;
+        // every code has at least one bit: at most nb steps (src/coding.cpp:124 — decode while bits remain)
+        while (used < nb && !bad && k < count) {
+            const uint32_t sym = dec.next(p.s, src, bc, ctx, used, bad);
+            if (bad) break;
+            const uint32_t st = cu.state(uint32_t(k));
+            if (st == 0u) {
+                if (EMIT) {
+                    so.put<DLDS>(E, bw, dctx, sym);
+                } else {
+                    const uint32_t l = E.len(E.at(dctx, sym));
+                    so.bit += l; drops += l == 0u; dctx = sym; ++so.o;
+                }
+            } else if (st == 1u) {
+                for (uint32_t j = 0; j < cu.rep_len; ++j) {
+                    const uint32_t rs = cu.rep[j];
+                    if (EMIT) {
+                        so.put<DLDS>(E, bw, dctx, rs);
+                    } else {
+                        const uint32_t l = E.len(E.at(dctx, rs));
+                        so.bit += l; drops += l == 0u; dctx = rs; ++so.o;
+                    }
+                }
+            }
+            ctx = sym;
+            ++k;
+        }
+        if (EMIT) { if (so.on) bw.finish(); continue; }
+        if (bad || used != nb) { stream_fail(p.s.b, status, i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT); continue; }
+        p.s.b.sym_off[i] = k;                                       // src/coding.cpp:158: the stream ends exactly at nbits
+        p.sp.out_sym_off[i] = so.o;
+        p.out_nbits[i] = so.bit;
+        if (p.dropped) p.dropped[i] = drops;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ launches
 
 template <Model K, bool W>
@@ -907,7 +1323,82 @@ hipError_t launch_rc(Params<EDIT> p, size_t lds_tables, void *d_ws, hipStream_t 
     return hipGetLastError();
 }
 
+// the splice: rep's bytes of LDS lie where launch_rc puts the edit's map
+template <Model K, bool DLDS>
+hipError_t launch_sp(SpliceParams p, size_t lds_tables, void *d_ws, size_t ws_bytes, hipStream_t st) {
+    constexpr int NT = Dec<K, false>::NT, PER_CU = Dec<K, false>::PER_CU;
+    size_t lds = lds_tables + (DLDS ? (p.dst.ctx_mask ? 65536 : 256) : 0);
+    const uint32_t lds_at = uint32_t(lds_tables);
+    p.sp.rep_lds = p.sp.rep_len && lds + 256 <= size_t(LDS_MAX) ? 1u : 0u;
+    if (p.sp.rep_lds) lds += 256;
+    if (K == Model::Shared) {
+        hipError_t attr = mhk::allow_lds(reinterpret_cast<const void *>(splice_idx_len_kernel<K, DLDS>), LDS_MAX);
+        if (attr == hipSuccess) attr = mhk::allow_lds(reinterpret_cast<const void *>(splice_idx_emit_kernel<K, DLDS>), LDS_MAX);
+        if (attr == hipSuccess) attr = mhk::allow_lds(reinterpret_cast<const void *>(splice_walk_kernel<K, DLDS, false>), LDS_MAX);
+        if (attr == hipSuccess) attr = mhk::allow_lds(reinterpret_cast<const void *>(splice_walk_kernel<K, DLDS, true>), LDS_MAX);
+        if (attr == hipSuccess) attr = mhk::allow_lds(reinterpret_cast<const void *>(splice_back_kernel<K>), LDS_MAX);
+        if (attr != hipSuccess) return attr;
+    }
+    unsigned char *ws = static_cast<unsigned char *>(d_ws);
+    const uint64_t n = p.s.b.n;
+    const uint64_t nw = p.s.b.index ? mhb::work_items(n, p.s.b.sym_total, 1u << p.s.b.chunk_shift) : 0;
+    const SpliceLayout L = splice_layout(n, nw, 0);
+    p.sp.span_cap = (ws_bytes - L.off_sctx) / 4;
+    int *status = reinterpret_cast<int *>(ws), *stop = status + 1;
+    uint32_t *tail = reinterpret_cast<uint32_t *>(ws + TAIL_AT);
+    auto *cbits = reinterpret_cast<unsigned long long *>(ws + L.off_bits);
+    auto *csyms = reinterpret_cast<unsigned long long *>(ws + L.off_syms);
+    auto *cdrop = reinterpret_cast<uint32_t *>(ws + L.off_drop);
+    auto *price = reinterpret_cast<uint32_t *>(ws + L.off_price);
+    auto *sums = reinterpret_cast<unsigned long long *>(ws + L.off_sums);
+    auto *sctx = reinterpret_cast<uint32_t *>(ws + L.off_sctx);
+    hipError_t e = hipMemsetAsync(ws, 0, 64, st);
+    if (e == hipSuccess && nw) e = hipMemsetAsync(ws + L.off_bits, 0, L.off_price - L.off_bits, st);   // chunk bits, output symbols, dropped counts
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(splice_check_kernel, grid_threads(n + 1, 256), dim3(256), 0, st, p, status, stop);
+    hipLaunchKernelGGL(recode_spans_kernel, dim3(grid_for(uint64_t(1) << 40, 256, 8)), dim3(256), 0, st, spans_view(p), status, stop);
+    hipLaunchKernelGGL(splice_price_kernel, dim3(1), dim3(256), 0, st, p, price);
+    if (p.s.b.index) {
+        if (!p.sp.rep_len)
+            hipLaunchKernelGGL((splice_back_kernel<K>), dim3(grid_for(uint64_t(1) << 40, NT, PER_CU)), dim3(NT), lds_tables, st, p, sctx, status, stop);
+        hipLaunchKernelGGL((splice_idx_len_kernel<K, DLDS>), dim3(grid_for(nw, NT, PER_CU)), dim3(NT), lds, st, p, nw, lds_at, cbits, csyms, cdrop,
+                           sctx, price, status, stop);
+        hipLaunchKernelGGL(splice_comb_kernel, grid_threads(nw + 1, 256), dim3(256), 0, st, p, nw, cbits, csyms, cdrop, stop);
+        if ((e = scan_exclusive(cbits, nw + 1, sums, stop, st)) != hipSuccess) return e;
+        if ((e = scan_exclusive(csyms, nw + 1, sums, stop, st)) != hipSuccess) return e;
+    } else {
+        hipLaunchKernelGGL((splice_walk_kernel<K, DLDS, false>), dim3(grid_for(n + 1, NT, PER_CU)), dim3(NT), lds, st, p, lds_at, tail, status, stop);
+        if ((e = scan_exclusive(p.s.b.sym_off, n + 1, sums, stop, st)) != hipSuccess) return e;
+        if ((e = scan_exclusive(p.sp.out_sym_off, n + 1, sums, stop, st)) != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(splice_sizes_kernel, grid_threads(n + 1, 256), dim3(256), 0, st, p, cbits, csyms, stop);
+    if ((e = scan_exclusive(p.out_off, n + 1, sums, stop, st)) != hipSuccess) return e;
+    if (p.out_index) hipLaunchKernelGGL(splice_cap_kernel, dim3(1), dim3(1), 0, st, p, status, stop);
+    if (p.out) hipLaunchKernelGGL(recode_zero_kernel, dim3(grid_for(p.cap / 4 + 1, 256, 8)), dim3(256), 0, st, p, status, stop, tail);
+    if (p.s.b.index) {
+        if (p.out || p.out_index)
+            hipLaunchKernelGGL((splice_idx_emit_kernel<K, DLDS>), dim3(grid_for(nw, NT, PER_CU)), dim3(NT), lds, st, p, nw, lds_at, cbits, csyms, sctx,
+                               tail, stop);
+    } else if (p.out || p.out_index) {
+        hipLaunchKernelGGL((splice_walk_kernel<K, DLDS, true>), dim3(grid_for(n + 1, NT, PER_CU)), dim3(NT), lds, st, p, lds_at, tail, status, stop);
+    }
+    if (p.out) hipLaunchKernelGGL(recode_tail_kernel, dim3(1), dim3(1), 0, st, p, tail, stop);
+    return hipGetLastError();
+}
+
 }  // namespace
+
+// the branches of launch_recode_edit, each with the splice in place of the edit
+hipError_t launch_recode_splice(const SpliceParams &p, Model model, void *d_ws, size_t ws_bytes, hipStream_t st) {
+    if (model == Model::Shared2 || p.dst.ctx_mask == 0xFFFFu) return hipErrorInvalidValue;
+    if (model == Model::Set)
+        return p.dst.ctx_mask ? launch_sp<Model::Set, false>(p, 0, d_ws, ws_bytes, st) : launch_sp<Model::Set, true>(p, 0, d_ws, ws_bytes, st);
+    const size_t lds = mhb::tables_lds(p.s.b);
+    if (lds > size_t(LDS_MAX)) return hipErrorInvalidValue;
+    const size_t img = p.dst.ctx_mask ? 65536 : 256;
+    return lds + img <= size_t(LDS_MAX) ? launch_sp<Model::Shared, true>(p, lds, d_ws, ws_bytes, st)
+                                        : launch_sp<Model::Shared, false>(p, lds, d_ws, ws_bytes, st);
+}
 
 hipError_t launch_histogram_coded(const HistParams &p, Model model, void *d_ws, hipStream_t st) {
     if (model == Model::Shared2) return launch_hist<Model::Shared2, true>(p, d_ws, st);

@@ -575,21 +575,37 @@ void i_coding_provider::recode(FILE* input_fd, FILE* output_fd, const i_coding_p
         index.resize((size_t)mh_batch_index_capacity(n_symbols, 1, chunk));      // (the slice of stream 0 starts at entry 0)
         out_index.assign(index.size(), 0);
     }
+    uint64_t span_off[2] = {0, 0};
+    std::vector<uint64_t> spans;
     const uint64_t pay_off[2] = {0, (uint64_t)in.size - 1};
     uint64_t sym_off[2] = {0, n_symbols}, out_off[2] = {0, 0}, out_nbits = 0, dropped = 0;
     StageTimer timer("recode", in.size);
     // the output file is mapped at the destination's worst case for the stream's symbols (without an index: at most
     // nbits / shortest source code of them) and cut to the true size afterwards: one upload, one device call
     const int minl = mh_model_min_code_len(model_);
-    const uint64_t symbols = indexed ? n_symbols : nbits / (uint64_t)(minl > 0 ? minl : 1);
+    uint64_t symbols = indexed ? n_symbols : nbits / (uint64_t)(minl > 0 ? minl : 1);
+    if (redact)
+        redact_spans(model_, *redact, in.data + 1, pay_off[1], nbits, indexed ? sym_off : nullptr, indexed ? index.data() : nullptr, chunk, span_off,
+                     spans);
+    const bool splice = redact && redact->replace;
+    if (splice) {                                                 // every span grows the message by at most the replacement
+        symbols += span_off[1] * redact->rep.size();
+        if (indexed) out_index.assign((size_t)mh_batch_index_capacity(symbols, 1, chunk), 0);
+    }
     const size_t bound = mh_encode_batch_bound(dst.model(), (size_t)symbols, 1);
     OutputView out;
     out.open(output_fd, bound + 1);
-    if (redact) {
-        uint64_t span_off[2];
-        std::vector<uint64_t> spans;
-        redact_spans(model_, *redact, in.data + 1, pay_off[1], nbits, indexed ? sym_off : nullptr, indexed ? index.data() : nullptr, chunk, span_off,
-                     spans);
+    if (splice) {
+        uint64_t removed = 0, out_sym_off[2] = {0, 0};
+        for (size_t k = 0; k < spans.size(); k += 2) removed += spans[k + 1] - spans[k];
+        eprintf("Replacing %llu bytes in %llu spans with %llu bytes.\n", (unsigned long long)removed, (unsigned long long)span_off[1],
+                (unsigned long long)(span_off[1] * redact->rep.size()));
+        mh_or_die(mh_recode_splice_batch(model_, dst.model(), in.data + 1, pay_off, &nbits, 1, MH_PREV0, sym_off, indexed ? index.data() : nullptr,
+                                         chunk, span_off, spans.data(), redact->rep.empty() ? nullptr : (const uint8_t*)redact->rep.data(),
+                                         (uint32_t)redact->rep.size(), out.data + 1, bound, out_off, &out_nbits, out_sym_off,
+                                         indexed ? out_index.data() : nullptr, out_index.size(), &dropped, nullptr), "recode (--replace)");
+        n_symbols = out_sym_off[1];                               // the index sidecar below is the new length's
+    } else if (redact) {
         uint64_t masked = 0;
         for (size_t k = 0; k < spans.size(); k += 2) masked += spans[k + 1] - spans[k];
         eprintf("Masking %llu bytes in %llu spans with 0x%02X.\n", (unsigned long long)masked, (unsigned long long)span_off[1], redact->mask);

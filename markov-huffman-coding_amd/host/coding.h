@@ -49,6 +49,8 @@ struct redact_options {
     std::vector<std::string> patterns;
     bool fold = false, dict = false;             // dict: the patterns of --redact-file, searched as a dictionary
     uint8_t mask = 0x2A;
+    bool replace = false;                        // --replace: a span becomes rep (any length up to MH_SPLICE_MAX_REP, "" deletes)
+    std::string rep;
 };
 
 class i_coding_provider {
@@ -72,7 +74,8 @@ public:
     // --recode: the `.cm` on input_fd (coded under this model) coded again under `dst` without writing its bytes
     // (mh_recode_batch); with a usable index sidecar the indexed path, and the output's index goes to `out_index_path`
     // redact: the occurrences of its patterns are searched in the compressed input, merged into spans on the device
-    // (mh_dev_spans_from_hits) and coded as the mask byte (mh_recode_edit_batch); the spans and bytes masked go to stderr
+    // (mh_dev_spans_from_hits) and coded as the mask byte (mh_recode_edit_batch); the spans and bytes masked go to stderr;
+    // with redact->replace each span becomes redact->rep instead (mh_recode_splice_batch) and the index is the new length's
     void recode(FILE* input_fd, FILE* output_fd, const i_coding_provider& dst, const std::string& out_index_path,
                 const redact_options* redact = nullptr);
     const mh_model* model() const { return model_; }

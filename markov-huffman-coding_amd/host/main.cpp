@@ -21,6 +21,8 @@
 //                    limits of --find; --redact-fold folds ASCII case), merged into spans there, and the stream is coded again
 //                    with those bytes replaced by the --mask byte (default 0x2A); the bytes are never written.  The new
 //                    table may be the old one.  --redact-file FILE: one pattern per line, the limits of --find-file.
+//   --replace STRING with --redact or --redact-file: the occurrences are replaced by STRING (at most 255 bytes; "" deletes
+//                    them) instead of being masked, so the output has another length; <output>.idx is written for it
 //   --crc            with -x: print `crc32 length` of the original input (CRC-32 as zlib computes it, %08x, and the byte
 //                    count), taken on the device without decompressing; with --index the indexed path
 #include <errno.h>
@@ -62,6 +64,8 @@ static void print_help() {
     eprintf("\t               again (repeatable, 64 bytes in all; --redact-fold: ASCII letters match either case); `table` may be the -e table\n");
     eprintf("\t--redact-file f  the same with one pattern per line of `f`, as --find-file; not together with --redact\n");
     eprintf("\t--mask byte    the byte that takes the place of redacted bytes: decimal or 0x.., 0 to 255 (default 0x2A)\n");
+    eprintf("\t--replace string  with --redact or --redact-file: every occurrence becomes the string (at most 255 bytes, \"\" deletes)\n");
+    eprintf("\t               instead of mask bytes; not together with --mask\n");
 }
 
 struct options {
@@ -85,6 +89,8 @@ struct options {
     const char* redact_file = nullptr;                            // --redact-file: the patterns are its lines
     bool redact_fold = false, mask_given = false;
     int mask = 0x2A;                                              // --mask: what a redacted byte becomes
+    bool replace_given = false;
+    std::string replace;                                          // --replace: what a redacted span becomes ("" deletes it)
 };
 
 // "B:E" with decimal B <= E; anything else is an error
@@ -160,6 +166,10 @@ static options parse(int argc, char* argv[]) {
                 }
                 o.mask = (int)n;
                 o.mask_given = true;
+            }
+            else if (!strcmp(a, "--replace")) {
+                o.replace = need(a);
+                o.replace_given = true;
             }
             else eprintf("Warning: Unknown option %s.\n", a);
             continue;
@@ -307,6 +317,20 @@ int main(int argc, char* argv[]) {
         }
     }
     const bool redact = !o.redacts.empty() || o.redact_file;
+    if (o.replace_given) {
+        if (!redact) {
+            eprintf("Error: --replace needs --redact or --redact-file.\n");
+            exit(1);
+        }
+        if (o.mask_given) {
+            eprintf("Error: --replace and --mask cannot be combined.\n");
+            exit(1);
+        }
+        if (o.replace.size() > MH_SPLICE_MAX_REP) {
+            eprintf("Error: --replace takes at most %u bytes.\n", MH_SPLICE_MAX_REP);
+            exit(1);
+        }
+    }
     if (redact) {                                                  // the rules first, then the pattern file, then everything else
         if (!o.recode_table) {
             eprintf("Error: --redact needs --recode.\n");
@@ -466,6 +490,8 @@ int main(int argc, char* argv[]) {
         ro.fold = o.redact_fold;
         ro.dict = o.redact_file != nullptr;
         ro.mask = (uint8_t)o.mask;
+        ro.replace = o.replace_given;
+        ro.rep = o.replace;
         coder->recode(input_fd, output_fd, *dst, std::string(o.output) + ".idx", redact ? &ro : nullptr);
         delete dst;
         delete coder;
