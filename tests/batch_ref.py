@@ -3,12 +3,18 @@ batches, and what every batch call of include/mh.h must give for them, from the 
 the original messages (a helper module like find_ref.py and recode_ref.py; it imports numpy and the oracle, never the library).
 
 A case is drawn in two steps: draw_cases(seed) fixes every case's parameters (and its own seed) from one generator, and
-Case.world() builds the messages, patterns, lookups and model counts of one case when a test needs them."""
+Case.world() builds the messages, patterns, lookups and model counts of one case when a test needs them.  Case.edits() is a
+second such part, from a generator of its own: a dictionary, a span list, a byte map and two replacements for dictionary
+search, span merging, masked and splicing re-code (find_ref.py, edit_ref.py, splice_ref.py), and Case.expected() what the
+edit and the splices must give."""
+import bisect
 import functools
 
 import numpy as np
 
+import edit_ref
 import find_ref
+import splice_ref
 from oracle import mh_oracle as oracle
 
 PREV0 = 0x20
@@ -427,6 +433,36 @@ class Case:
         w.lookups = [lk[j] for j in rng.permutation(32)]
         w.lookup_bytes = [w.messages[i][b:e] for i, b, e in w.lookups]
 
+    # ---- the second part of a case: a dictionary, a span list, a byte map and two replacements ----
+    @functools.lru_cache(maxsize=2)
+    def edits(self):
+        """The inputs of dictionary search, span merging, masked and splicing re-code, from the messages alone.  A generator of
+        its own, seeded from the case's seed: no draw of world() moves."""
+        rng = np.random.default_rng([self.seed, 1])
+        w, e = self.world(), Edits()
+        e.fold = w.fold
+        _draw_dictionary(rng, self, w, e)
+        e.states, e.classes = trie_counts(e.dictionary, e.fold)
+        e.hits = find_ref.find_hits(w.messages, e.dictionary, fold=e.fold)
+        e.hit_off, e.records, e.hit_pattern = find_ref.hit_arrays(e.hits, len(w.messages))
+        _draw_replacements(rng, w, e)
+        _draw_spans(rng, self, w, e)
+        _draw_map(rng, self, w, e)
+        return e
+
+    @functools.lru_cache(maxsize=2)
+    def expected(self):
+        """What the masked and the splicing re-code must give under the destination model: the packer on the edited messages."""
+        w, e, x = self.world(), self.edits(), Expected()
+        do = self.orders[1]
+        put = lambda msgs: pack(msgs, *self.codes("dst"), do, w.prev0, self.chunk)
+        x.edit = put(edit_ref.apply(w.messages, e.span_off, e.spans, e.byte_map))
+        x.edit_all = put(edit_ref.apply(w.messages, None, None, e.byte_map))
+        x.spliced = [splice_ref.apply(w.messages, e.span_off, e.spans, rep) for rep in e.reps]
+        x.splice = [put(y) for y in x.spliced]
+        x.out_sym_off = [splice_ref.offsets(y) for y in x.spliced]
+        return x
+
 
 # (source order, destination order) -> cases; every pair of orders appears, the pairs with an order-2 side less often
 _PAIRS = [((0, 0), 14), ((0, 1), 16), ((1, 0), 16), ((1, 1), 18), ((0, 2), 6), ((1, 2), 9), ((2, 0), 5), ((2, 1), 6), ((2, 2), 6)]
@@ -449,3 +485,359 @@ def draw_cases(seed=SEED):
                 dk = "deep"
             cases.append(Case(len(cases), rng, orders, sk, dk))
     return cases
+
+
+# ---------------------------------------------------------------------------------------------------- dictionaries, spans, maps
+HIT_CAP = 20000                    # hits of a case's dictionary, at most
+SPLICED_BYTES = 1 << 20            # a case's spliced messages, at most
+DICT_MAX_STATES = 32768            # include/mh.h MH_DICT_MAX_STATES (trie nodes, root included)
+DICT_MAX_LEN = 255                 # include/mh.h MH_DICT_MAX_LEN, and MH_SPLICE_MAX_REP
+SPAN_CAP = 1000                    # spans of a case, at most (every one may grow by a replacement of 255 bytes)
+MAP_KINDS = ("identity", "mask", "fold", "permutation", "random", "lacking")
+PLACEMENTS = ("from 0", "to the last byte", "past the end", "at or past the end", "touching", "over a seam", "whole chunks",
+              "whole stream", "a stream without spans between two with spans")
+LDS_BYTES = 163840                 # csrc/mh_find.hip, launch_find_dict: the 160 KiB of a workgroup
+DICT_PER_CU = 8                    # csrc/mh_symdec_dev.hpp, Dec<Set>::PER_CU and Dec<Shared2>::PER_CU
+DEC_LDS_ENTRIES = (LDS_BYTES - 1024) // 2       # csrc/mh_model.hpp
+DEC_SEC_MAX_PER_CTX = 4096                      # csrc/mh_model.hpp
+
+
+class Edits:
+    """The second part of a case, built: dictionary (a list of patterns) and fold, the trie's states and classes, the
+    dictionary's hits (find_ref's list and the three arrays of a device call), special (what the named patterns are: pattern
+    numbers), span_off / spans, byte_map and map_kind, reps (the deletion and one replacement), lacking (a byte the messages
+    do not hold, or None) and rep_lacks (the replacement holds it)."""
+
+
+class Expected:
+    """The expected outputs of a case's edit and splices: edit, edit_all (no span list: everywhere), splice[k] (batch_ref.Packed
+    under the destination model), spliced[k] (the messages) and out_sym_off[k], k = 0 the deletion, 1 the replacement."""
+
+
+def _fold(b, fold):
+    return find_ref.fold_ascii(b) if fold else bytes(b)
+
+
+def trie_counts(patterns, fold):
+    """(states, classes) of a plain trie of the patterns: its nodes, the root included, and the distinct bytes on its edges plus
+    one, the class of the bytes of no pattern (a class number is a byte: 256 distinct bytes leave none for that class, and
+    nothing in it)."""
+    root, states, seen = {}, 1, set()
+    for p in patterns:
+        node = root
+        for b in _fold(p, fold):
+            seen.add(b)
+            if b not in node:
+                node[b] = {}
+                states += 1
+            node = node[b]
+    return states, min(len(seen) + 1, 256)
+
+
+class _Counter:
+    """Exact hit counts of one pattern in the messages (overlapping hits, none across two messages), up to a limit."""
+
+    def __init__(self, messages, fold):
+        self.fold, self.have = fold, _fold(b"".join(messages), fold)
+        self.off = [0]
+        for m in messages:
+            self.off.append(self.off[-1] + len(m))
+
+    def stream_of(self, at):
+        return bisect.bisect_right(self.off, at) - 1
+
+    def count(self, p, limit):
+        """The hits of p, or some number above `limit` once there are more."""
+        p = _fold(p, self.fold)
+        k, at = 0, self.have.find(p)
+        while at >= 0:
+            if at + len(p) <= self.off[self.stream_of(at) + 1]:
+                k += 1
+                if k > limit:
+                    break
+            at = self.have.find(p, at + 1)
+        return k
+
+
+def _draw_dictionary(rng, case, w, e):
+    """A hundred to about 2000 patterns of 1 to 255 bytes, within HIT_CAP hits and DICT_MAX_STATES states.  In this order: a
+    255-byte pattern across a chunk seam, one that ends on a stream's last byte, one with all its suffixes and some of its
+    prefixes (a one- or two-symbol source: the runs a, aa, ... of its bytes), patterns that occur nowhere, one duplicate,
+    substrings of the messages; then shuffled.  A pattern that would take the hits over the budget is left out, the named ones
+    included: a byte of a small alphabet alone hits more often than HIT_CAP, and so does any run in a one-symbol source, where
+    little but the seam pattern fits.  e.special says which of the named ones are in (their pattern numbers)."""
+    msgs, c, fold = w.messages, case.chunk, w.fold
+    cnt = _Counter(msgs, fold)
+    ln = [len(m) for m in msgs]
+    full = [i for i, l in enumerate(ln) if l]
+    pats, folded, special = [], set(), {}
+    room = {"hits": HIT_CAP - 1000, "states": DICT_MAX_STATES - 768}
+
+    def add(p, limit, name=None, k=None, nodes=None):
+        k = cnt.count(p, min(limit, room["hits"])) if k is None else k
+        nodes = len(p) if nodes is None else nodes                 # (an upper bound of the nodes it adds)
+        if not p or len(p) > DICT_MAX_LEN or k > min(limit, room["hits"]) or nodes > room["states"]:
+            return False
+        if name:
+            special[name] = len(pats)
+        pats.append(bytes(p))
+        folded.add(_fold(p, fold))
+        room["hits"] -= k
+        room["states"] -= nodes
+        return True
+
+    joined, total = b"".join(msgs), cnt.off[-1]
+    here = sorted(set(joined))
+    present = set(cnt.have)
+    lack = [b for b in range(256) if _fold(bytes([b]), fold)[0] not in present]
+    lack = [lack[int(rng.integers(len(lack)))]] if lack else []   # (one such byte: it is a class of its own in the automaton)
+    # 255 bytes across a chunk seam of a stream longer than the chunk
+    long = [i for i, l in enumerate(ln) if l > c]
+    for i in [long[int(j)] for j in rng.permutation(len(long))[:4]]:
+        seam = c * int(rng.integers(1, (ln[i] - 1) // c + 1))
+        a = int(rng.integers(max(0, seam - 254), min(seam - 1, ln[i] - 255) + 1))
+        if add(msgs[i][a:a + 255], HIT_CAP, "seam"):
+            assert a < seam < a + 255
+            break
+    # up to a stream's last byte
+    for i in [full[int(j)] for j in rng.permutation(len(full))[:64]]:
+        k = int(rng.integers(1, min(ln[i], 24) + 1))
+        if add(msgs[i][-k:], 2000, "end") or (ln[i] > k and add(msgs[i][-DICT_MAX_LEN:], 2000, "end")):
+            break
+    else:                                                          # (one symbol nearly everywhere: the shortest stream's whole text)
+        i = min(full, key=lambda i: (-min(ln[i], DICT_MAX_LEN), ln[i]))
+        add(msgs[i][-DICT_MAX_LEN:], HIT_CAP, "end")
+    # every suffix and some prefixes of one pattern; a one- or two-symbol source: the runs of two of its bytes and of one it lacks
+    if case.source in ("one", "two"):
+        top = int(rng.integers(100, 256))
+        whole = [0]
+        for v in [here[int(j)] for j in rng.permutation(len(here))[:2]] + lack[:1]:
+            key = np.where(np.frombuffer(cnt.have, dtype=np.uint8) == _fold(bytes([v]), fold)[0], np.repeat(np.arange(len(ln)), ln) + 1, 0)
+            edges = np.flatnonzero(np.diff(np.concatenate([[0], key, [0]])))
+            runs = np.diff(edges)[key[edges[:-1]] > 0] if edges.size else edges      # the runs of v, none across two messages
+            took = []
+            for k in range(1, top + 1):                            # (a run behind the next shorter one is one more node)
+                took.append(add(bytes([v]) * k, 3000, "family", int(np.maximum(runs - k + 1, 0).sum()), 1 if took and took[-1] else k))
+            whole.append(took.index(False) if False in took else top)
+        special["family_whole"] = max(whole[:-1]) >= 4
+    else:
+        have = np.frombuffer(cnt.have, dtype=np.uint8)
+        seen = np.bincount(have, minlength=256)
+        rare = int(np.argmin(np.where(seen > 0, seen, 1 << 62)))
+        at = int(rng.choice(np.flatnonzero(have == rare)))
+        p = joined[max(cnt.off[cnt.stream_of(at)], at + 1 - int(rng.integers(4, 9))):at + 1]
+        took = [add(p[k:], 2000) for k in range(len(p) - 1, 0, -1)]
+        for k in sorted(set(int(v) for v in rng.integers(1, max(len(p), 2), size=2))):
+            if k < len(p):
+                add(p[:k], 2000)
+        took.append(add(p, 2000, "family"))
+        special["family_whole"] = all(took)
+    # patterns that occur nowhere: substrings with one byte changed, to a byte the messages lack where there is one
+    small = case.source in ("one", "two")
+    target = int(rng.integers(300, 601 if small else 2001 if case.n_streams <= 65 else 801))
+    nowhere = 0
+    for _ in range(4 * max(target // 20, 3)):
+        if nowhere >= max(target // 20, 3):
+            break
+        m = msgs[full[int(rng.integers(len(full)))]]
+        a = int(rng.integers(len(m)))
+        p = bytearray(m[a:a + int(rng.integers(1, 20))])
+        p[int(rng.integers(len(p)))] = lack[int(rng.integers(len(lack)))] if lack and rng.random() < 0.5 else here[int(rng.integers(len(here)))]
+        if cnt.count(p, 0) == 0 and _fold(p, fold) not in folded and add(bytes(p), 0):
+            nowhere += 1
+    special["nowhere"] = nowhere
+    # a duplicate, of a pattern that hits where the budget allows
+    for j in sorted(range(len(pats)), key=lambda j: (cnt.count(pats[j], 0) == 0, j)):
+        if add(pats[j], 2000, "duplicate"):
+            break
+    # substrings of the messages; one that hits too often is drawn again at twice the length
+    for _ in range(3 * target):
+        if len(pats) >= target or room["states"] < 256:
+            break
+        at = int(rng.integers(total))
+        end = cnt.off[cnt.stream_of(at) + 1]
+        k = int(min(rng.geometric(0.15), DICT_MAX_LEN))
+        while True:
+            p = joined[at:min(at + k, end)]
+            if _fold(p, fold) not in folded and add(p, 64):
+                break
+            if at + k >= end or k >= DICT_MAX_LEN:
+                break
+            k = min(2 * k, DICT_MAX_LEN)
+    if fold:
+        pats = [p.swapcase() if j % 2 else p for j, p in enumerate(pats)]
+    order = rng.permutation(len(pats)).tolist()
+    where = {j: k for k, j in enumerate(order)}
+    e.dictionary = [pats[j] for j in order]
+    e.special = {k: (where[v] if k in ("seam", "end", "family", "duplicate") else v) for k, v in special.items()}
+
+
+def _draw_replacements(rng, w, e):
+    """The deletion, and one replacement of 1, 2, 3, 64, 255 or 4 .. 254 bytes of the source alphabet; in about a quarter of the
+    cases one of its bytes is a byte the messages lack."""
+    here = np.unique(np.frombuffer(b"".join(w.messages), dtype=np.uint8))
+    lack = np.setdiff1d(np.arange(256), here)
+    e.lacking = int(rng.choice(lack)) if lack.size else None
+    k = [1, 2, 3, 64, 255, int(rng.integers(4, 255))][int(rng.integers(6))]
+    rep = rng.choice(here, size=k).astype(np.uint8)
+    e.rep_lacks = bool(rng.random() < 0.25) and e.lacking is not None
+    if e.rep_lacks:
+        rep[int(rng.integers(k))] = e.lacking
+    e.reps = [b"", rep.tobytes()]
+
+
+def _craft(rng, L, c):
+    """A valid span list of one stream of L bytes that reaches the edges: candidates at 0, over a seam, over whole chunks, a
+    touching pair and at the end, of which those that do not overlap stay."""
+    if L == 0:
+        b = int(rng.integers(0, 3))
+        return [(b, b + int(rng.integers(1, 4)))]
+    if rng.random() < 0.2:
+        return [(0, L + int(rng.choice([0, 0, 1, 9])))]            # the whole stream
+    units = []
+    if rng.random() < 0.6:
+        units.append([(0, c + int(rng.integers(0, 6)) if L > c and rng.random() < 0.5 else int(rng.integers(1, 5)))])
+    if L > c and rng.random() < 0.7:
+        s = c * int(rng.integers(1, (L - 1) // c + 1))
+        units.append([(s - int(rng.integers(1, 6)), s + int(rng.integers(1, 6)))])
+    if L >= 3 * c and rng.random() < 0.6:
+        j = int(rng.integers(1, L // c - 1))
+        units.append([(j * c - int(rng.integers(0, 3)), (j + int(rng.integers(1, 3))) * c + int(rng.integers(0, 3)))])
+    b = int(rng.integers(0, L))
+    m = b + int(rng.integers(1, 9))
+    units.append([(b, m), (m, m + int(rng.integers(1, 9)))])
+    u, k = rng.random(), int(rng.integers(1, 6))
+    if u < 0.3:
+        units.append([(max(L - k, 0), L)])
+    elif u < 0.55:
+        units.append([(max(L - k, 0), L + int(rng.integers(1, 300)))])
+    elif u < 0.8:
+        b = L + int(rng.integers(0, 3))
+        units.append([(b, b + k)])
+    out, at = [], 0
+    for unit in sorted(units):
+        if unit[0][0] >= at:
+            out += unit
+            at = unit[-1][1]
+    return out
+
+
+def _draw_spans(rng, case, w, e):
+    """The redaction pipeline, merge_hits over the records of a drawn subset of the dictionary's hits, with crafted spans put
+    into up to ten streams (the longest among them; the merged spans that lie clear of them stay) and one stream in the middle
+    left without spans.  At most SPAN_CAP spans, and no more than keep the spliced messages within SPLICED_BYTES."""
+    msgs, c, n = w.messages, case.chunk, len(w.messages)
+    ln = [len(m) for m in msgs]
+    cap = min(SPAN_CAP, (SPLICED_BYTES - sum(ln)) // max(len(e.reps[1]), 1))
+    k = int(rng.integers(1, max(min(len(e.hits), cap - 100), 1) + 1))
+    pick = np.sort(rng.choice(len(e.hits), size=min(k, len(e.hits)), replace=False))
+    rec = e.records[pick]
+    off = np.concatenate([[0], np.cumsum(np.bincount(rec[:, 0].astype(np.int64), minlength=n))])
+    so, sp = edit_ref.merge_hits(off, rec)
+    per = [[(int(b), int(t)) for b, t in sp[int(so[i]):int(so[i + 1])]] for i in range(n)]
+    crafted = {int(np.argmax(ln))} | set(int(i) for i in rng.integers(0, n, size=int(rng.integers(2, 10))))
+    for i in sorted(crafted):                                     # (the merged spans that lie clear of the crafted ones stay)
+        made = _craft(rng, ln[i], c)
+        per[i] = sorted(made + [(b, t) for b, t in per[i] if all(t <= cb or b >= ct for cb, ct in made)])
+    if n >= 3:
+        i = int(rng.integers(1, n - 1))
+        per[i] = []
+        for j in (i - 1, i + 1):
+            per[j] = per[j] or _craft(rng, ln[j], c)
+    e.span_off = np.concatenate([[0], np.cumsum([len(p) for p in per])]).astype(np.uint64)
+    e.spans = np.array([s for p in per for s in p], dtype=np.uint64).reshape(-1, 2)
+
+
+def _draw_map(rng, case, w, e):
+    """One kind per case, going round MAP_KINDS by the case's number.  'lacking' (a random map into the source alphabet, but
+    one byte of it goes to a byte the messages lack) is 'random' where the messages hold every byte value."""
+    here = np.unique(np.frombuffer(b"".join(w.messages), dtype=np.uint8))
+    kind = MAP_KINDS[case.index % len(MAP_KINDS)]
+    m = np.arange(256, dtype=np.uint8)
+    if kind == "mask":
+        m[:] = rng.choice(here)
+    elif kind == "fold":
+        m = np.frombuffer(find_ref.fold_ascii(bytes(range(256))), dtype=np.uint8).copy()
+    elif kind == "permutation":
+        m[here] = rng.permutation(here)
+    elif kind in ("random", "lacking"):
+        m[:] = rng.choice(here, size=256)
+        if kind == "lacking" and e.lacking is not None:
+            m[rng.choice(here)] = e.lacking
+        elif kind == "lacking":
+            kind = "random"
+    e.byte_map, e.map_kind = m.tobytes(), kind
+
+
+def span_lists(span_off, spans):
+    """[[(begin, end)] per stream] of a span list."""
+    sp = np.asarray(spans, dtype=np.uint64).reshape(-1, 2).tolist()
+    return [[tuple(s) for s in sp[int(span_off[i]):int(span_off[i + 1])]] for i in range(len(span_off) - 1)]
+
+
+def placements(messages, span_off, spans, chunk):
+    """Which of PLACEMENTS a span list reaches on these messages (a set of names).  'whole chunks': a span covers a full chunk
+    of its stream, from its first byte to its last; 'over a seam': the bytes a span covers lie in two chunks."""
+    per, c, got = span_lists(span_off, spans), chunk, set()
+    for i, (m, lst) in enumerate(zip(messages, per)):
+        L = len(m)
+        for k, (b, t) in enumerate(lst):
+            if b >= L:
+                got.add("at or past the end")
+                continue
+            if b == 0:
+                got.add("from 0")
+            got.add("to the last byte" if t == L else "past the end" if t > L else "")
+            if b // c != (min(t, L) - 1) // c:
+                got.add("over a seam")
+            if (b + c - 1) // c * c + c <= min(t, L):
+                got.add("whole chunks")
+            if b == 0 and t >= L:
+                got.add("whole stream")
+            if k + 1 < len(lst) and lst[k + 1][0] == t < L:
+                got.add("touching")
+        if not lst and 0 < i < len(per) - 1 and per[i - 1] and per[i + 1]:
+            got.add("a stream without spans between two with spans")
+    return got - {""}
+
+
+def span_mask(messages, span_off, spans):
+    """One flag per byte of the concatenated messages: inside a span, or the byte in front of one or behind one."""
+    off = np.concatenate([[0], np.cumsum([len(m) for m in messages])])
+    mask = np.zeros(int(off[-1]), dtype=bool)
+    for i, lst in enumerate(span_lists(span_off, spans)):
+        L = len(messages[i])
+        for b, t in lst:
+            if b < L:
+                mask[off[i] + max(b - 1, 0):off[i] + min(t + 1, L)] = True
+    return mask
+
+
+def tables_lds(lens, codes, order):
+    """LDS bytes of the decode tables of a shared order-0 / 1 model with these code tables (csrc/mh_batch.h, mhb::tables_lds): the
+    1 KiB of bases, 256 first-level tables of 2^P entries of two bytes and the second level, P the largest of 8 .. 4 with which
+    both fit (csrc/mh_api_model.cpp).  A second-level table hangs at every P-bit prefix of a longer code and has 2^(its longest
+    code's bits behind the prefix, 8 at most) entries.  (first level alone when no P fits: the second level then stays in L2)"""
+    L = np.asarray(lens, dtype=np.int64).reshape(-1, 256)
+    cd = np.asarray(codes, dtype=np.uint64).reshape(-1, 256)
+    for P in range(8, 3, -1):
+        total = worst = 0
+        for ctx in np.flatnonzero(L.max(axis=1) > P):
+            tables = {}
+            for s in np.flatnonzero(L[ctx] > P):
+                pre = int(cd[ctx, s]) >> (int(L[ctx, s]) - P)
+                tables[pre] = max(tables.get(pre, 0), min(int(L[ctx, s]) - P, 8))
+            here = sum(1 << h for h in tables.values())
+            total, worst = total + here, max(worst, here)
+        if worst <= DEC_SEC_MAX_PER_CTX and (256 << P) + total <= DEC_LDS_ENTRIES:
+            return 1024 + (512 << P) + ((2 * total + 15) & ~15)
+    return 1024 + (512 << 8)
+
+
+def dict_rows_in_lds(case, states, classes):
+    """How many of the transition table's `states` rows the matcher keeps in LDS under the case's source (csrc/mh_find.hip,
+    launch_find_dict and launch_dict): a shared order-0 / 1 source leaves what its decode tables do not take of LDS_BYTES, an
+    order-2 source or a model set reads its tables from L2 and gets LDS_BYTES / DICT_PER_CU; 256 bytes of that hold the class
+    map, rows of 2 * classes bytes the rest (csrc/mh_dict.h: trans u16[states x ncls]); with less than 256 bytes no row."""
+    room = LDS_BYTES // DICT_PER_CU if case.orders[0] == 2 else LDS_BYTES - tables_lds(*case.codes("src"), case.orders[0])
+    return 0 if room < 256 else min(states, (room - 256) // (2 * classes))

@@ -2,6 +2,7 @@
 coverage that the fixed case list of tests/test_gpu_batch_fuzz.py must keep.  No GPU, no library call: everything here is the
 oracle, numpy and the committed files."""
 import functools
+import hashlib
 import os
 
 import numpy as np
@@ -185,9 +186,120 @@ def test_coverage_of_the_fixed_case_list():
     assert count(lambda s: any(e == 0 and not s["case"].world().messages[i] for i, b, e in s["case"].world().lookups)) >= 10
 
 
+# ---------------------------------------------------------------------------------------------------- the second part of a case
+WORLDS_DIGEST = "ba1c99016e4c9bbb9896ab9ba67396fbcba1497cce2c0f5d290131458ecdf7fc"
+
+
+def test_no_world_moved_when_the_edits_were_added():
+    """SHA-256 over every case's id, seed, prev0, chunk, fold, lookups, messages, patterns, foreign text and lookup bytes, computed
+    at the commit before Case.edits() existed: the second part of a case draws from a generator of its own."""
+    h = hashlib.sha256()
+    for case in batch_ref.draw_cases():
+        w = case.world()
+        case.edits()                                                # (building it must not move anything either)
+        h.update(repr((case.id, case.seed, w.prev0, w.chunk, w.fold, [tuple(int(v) for v in lk) for lk in w.lookups])).encode())
+        for part in (w.messages, w.patterns, w.foreign, w.lookup_bytes):
+            h.update(len(part).to_bytes(8, "little"))
+            for m in part:
+                h.update(len(m).to_bytes(8, "little") + bytes(m))
+    assert h.hexdigest() == WORLDS_DIGEST
+
+
+@functools.lru_cache(maxsize=1)
+def edit_stats():
+    out = []
+    for case in batch_ref.draw_cases():
+        w, e = case.world(), case.edits()
+        c, ln = case.chunk, [len(m) for m in w.messages]
+        folded = [find_ref.fold_ascii(p) if e.fold else p for p in e.dictionary]
+        known = set(folded)
+        s = dict(case=case, e=e, hits=len(e.hits), placements=batch_ref.placements(w.messages, e.span_off, e.spans, c),
+                 seam255=any(t - b == 255 and b // c != (t - 1) // c for _, b, t, _ in e.hits), at_end=any(t == ln[i] for i, _, t, _ in e.hits),
+                 nowhere=len(set(range(len(folded))) - {h[3] for h in e.hits}), duplicates=len(folded) - len(known),
+                 family=any(len(p) >= 4 and all(p[k:] in known for k in range(1, len(p))) and any(p[:k] in known for k in range(1, len(p)))
+                            for p in known),
+                 rarest=min(np.bincount(np.frombuffer(b"".join(w.messages), dtype=np.uint8), minlength=256)[sorted(set(b"".join(w.messages)))]),
+                 rows=batch_ref.dict_rows_in_lds(case, e.states, e.classes))
+        if 2 not in case.orders:
+            x = case.expected()
+            per = batch_ref.span_lists(e.span_off, e.spans)
+            src = batch_ref.pack(w.messages, *case.codes("src"), case.orders[0], w.prev0, c)
+            mask = batch_ref.span_mask(w.messages, e.span_off, e.spans)
+            chunks = lambda k: (k + c - 1) // c
+            s.update(spliced=sum(len(m) for m in x.spliced[1]),
+                     emptied=any(l and not len(y) for l, y in zip(ln, x.spliced[0])),
+                     first_chunk=any(b == 0 and c <= t < ln[i] for i, lst in enumerate(per) for b, t in lst),
+                     grows=any(chunks(len(y)) > chunks(l) for l, y in zip(ln, x.spliced[1])),
+                     drops=max(int(p.dropped.sum()) for p in [x.edit, x.edit_all] + x.splice),
+                     near=max(int(src.used[mask].max()), int(x.edit.used[mask].max())) if mask.any() else 0)
+        out.append(s)
+    return out
+
+
+def test_every_case_s_dictionary_spans_map_and_replacements():
+    for s in edit_stats():
+        case, e, w = s["case"], s["e"], s["case"].world()
+        ln = [len(m) for m in w.messages]
+        # the dictionary: within the automaton's and the hit budget, the named patterns in it
+        assert 100 <= len(e.dictionary) <= 2000 and all(1 <= len(p) <= batch_ref.DICT_MAX_LEN for p in e.dictionary), case.id
+        assert e.states <= batch_ref.DICT_MAX_STATES and 1 <= s["hits"] <= batch_ref.HIT_CAP, (case.id, e.states, s["hits"])
+        assert s["seam255"] and s["nowhere"] >= 1 and s["duplicates"] >= 1, case.id
+        if not s["at_end"]:      # one symbol nearly everywhere: the last 255 bytes of any stream, or all of it, hit too often
+            hit = batch_ref._Counter(w.messages, e.fold)
+            assert all(hit.count(m[-batch_ref.DICT_MAX_LEN:], batch_ref.HIT_CAP) > batch_ref.HIT_CAP for m in w.messages if m), case.id
+        if case.source not in ("one", "two") and s["rarest"] <= 2000:    # (else the pattern's last byte alone is over the budget)
+            assert s["family"] and e.special["family_whole"], case.id
+        # the span list: valid, and no more spans than keep the spliced messages small
+        for i, lst in enumerate(batch_ref.span_lists(e.span_off, e.spans)):
+            assert all(b < t for b, t in lst) and all(lst[k][1] <= lst[k + 1][0] for k in range(len(lst) - 1)), (case.id, i)
+        assert len(e.span_off) == len(ln) + 1 and int(e.span_off[-1]) == len(e.spans) <= batch_ref.SPAN_CAP, case.id
+        # the map and the replacements
+        assert e.map_kind in (batch_ref.MAP_KINDS[case.index % 6], "random") and len(e.byte_map) == 256, case.id
+        assert e.reps[0] == b"" and 1 <= len(e.reps[1]) <= 255, case.id
+        here = set(b"".join(w.messages))
+        assert e.lacking is None or e.lacking not in here, case.id
+        assert set(e.reps[1]) - here == ({e.lacking} if e.rep_lacks else set()), case.id
+        if e.map_kind == "lacking":
+            assert set(e.byte_map) - here == {e.lacking}, case.id
+        if "spliced" in s:
+            assert s["spliced"] <= batch_ref.SPLICED_BYTES, case.id
+    assert count_edits(lambda s: s["at_end"]) >= 95
+    assert count_edits(lambda s: s["family"] and s["e"].special["family_whole"]) >= 48
+    for kind in batch_ref.MAP_KINDS:
+        assert count_edits(lambda s: s["e"].map_kind == kind) >= 10, kind
+    for k in (1, 2, 3, 64, 255):
+        assert count_edits(lambda s: len(s["e"].reps[1]) == k) >= 5, k
+    assert count_edits(lambda s: s["e"].rep_lacks) >= 10
+
+
+def count_edits(pred, cases=lambda s: True):
+    return sum(1 for s in edit_stats() if cases(s) and pred(s))
+
+
+def test_coverage_of_the_edits_of_the_fixed_case_list():
+    """What the dictionary, span, edit and splice families of the fuzz must keep reaching, from the references alone."""
+    plain = lambda s: 2 not in s["case"].orders                     # the cases that edit and splice (no order-2 side)
+    assert count_edits(plain) == 64
+    for name in batch_ref.PLACEMENTS:
+        assert count_edits(lambda s: name in s["placements"], plain) >= 10, name
+    assert count_edits(lambda s: s["emptied"], plain) >= 10         # a deletion empties a stream
+    assert count_edits(lambda s: s["first_chunk"], plain) >= 10     # a deletion removes a first chunk: prev0 meets the byte behind
+    assert count_edits(lambda s: s["grows"], plain) >= 10           # a replacement raises a chunk count
+    assert count_edits(lambda s: s["drops"] > 0 and s["case"].dst_kind != "foreign", plain) >= 10
+    assert count_edits(lambda s: s["case"].deep and s["near"] > 32, plain) >= 8
+    assert count_edits(lambda s: s["case"].deep and s["near"] > 56, plain) >= 3
+    # The matcher keeps the class map and as many rows of the transition table (csrc/mh_dict.h: trans u16[states x ncls]) as fit
+    # into what the source's decode tables leave of the 160 KiB of LDS (csrc/mh_find.hip, launch_find_dict and launch_dict;
+    # batch_ref.dict_rows_in_lds): both sides of that threshold under sources with deep codes
+    deep = lambda s: s["case"].src_kind == "deep"
+    assert count_edits(lambda s: s["rows"] < s["e"].states, deep) >= 6
+    assert count_edits(lambda s: s["rows"] == s["e"].states, deep) >= 6
+    assert count_edits(lambda s: s["rows"] == 0, deep) >= 1          # (tables that fill the LDS: no row, the class map from L2)
+
+
 def test_the_new_files_leave_no_test_out():
     here = os.path.dirname(os.path.abspath(__file__))
-    for name in ("batch_ref.py", "test_batch_ref.py", "test_gpu_batch_fuzz.py"):
+    for name in ("batch_ref.py", "test_batch_ref.py", "test_gpu_batch_fuzz.py", "test_dict_abi.py", "edit_ref.py", "splice_ref.py", "find_ref.py"):
         with open(os.path.join(here, name)) as f:
             text = f.read()
         for word in ("pytest.sk", "mark.sk", "importorsk", "xfa"):

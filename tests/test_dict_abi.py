@@ -1,6 +1,7 @@
 """The dictionary object of the dictionary search (include/mh.h, "DICTIONARY SEARCH IN BATCHES") on the CPU: mh_dict_create's
 contract, the automaton's size on the golden wiki page, and the host matcher mh_dict_find_bytes against tests/find_ref.py
-(position, pattern number and order).  No device is needed for any of it.  The expected counts were computed from the golden
+(position, pattern number and order), on the golden inputs and on the dictionary of every case of the batch fuzz
+(tests/batch_ref.py).  No device is needed for any of it.  The expected counts were computed from the golden
 input with find_ref alone."""
 import os
 import re
@@ -10,10 +11,12 @@ import numpy as np
 import pytest
 
 import __graft_entry__ as entry
+import batch_ref
 import find_ref
 from conftest import ROOT, golden
 
 CSRC = os.path.join(ROOT, "markov-huffman-coding_amd", "csrc")
+FUZZ_CASES = batch_ref.draw_cases()
 
 
 @pytest.fixture(scope="module")
@@ -152,6 +155,17 @@ def test_folding(mhc, wiki):
     assert len(got) == 550 and got == find_ref.find_hits(lines, [b"c++"], fold=True)
     upper = host_hits(mhc.Dict([b"C++"], fold=True), lines)
     assert upper == got and len(host_hits(mhc.Dict([b"c++"]), lines)) < 550
+
+
+@pytest.mark.parametrize("case", FUZZ_CASES, ids=[c.id for c in FUZZ_CASES])
+def test_the_dictionary_of_every_fuzz_case(mhc, case):
+    """The dictionaries of tests/batch_ref.py (a 255-byte pattern, suffix families, duplicates, runs of one byte, folding) on
+    every message of their case: the automaton's size against a plain trie's, every hit against find_ref."""
+    w, e = case.world(), case.edits()
+    d = mhc.Dict(e.dictionary, fold=e.fold)
+    assert len(d) == len(e.dictionary) and d.max_len == max(len(p) for p in e.dictionary)
+    assert (d.states, d.classes) == (e.states, e.classes)
+    assert host_hits(d, w.messages) == e.hits
 
 
 def test_find_bytes_hit_cap(mhc):

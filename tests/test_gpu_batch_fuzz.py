@@ -1,7 +1,8 @@
 """Seeded differential fuzz of the batch call family on the GPU: every case of tests/batch_ref.py goes through every batch call
 of include/mh.h — encode, histograms, decode (indexed, index-free, segment states), lookups, search, coded histogram, re-code,
-per-stream models and banks — and every result is compared exactly with the references of tests/batch_ref.py: the CPU oracle's
-code tables and plain numpy on the original messages, never another call of the library.  tests/test_batch_ref.py pins those
+per-stream models and banks, dictionary search, spans from hits, masked and splicing re-code (the last two for the 64 cases
+without an order-2 side: they refuse one) — and every result is compared exactly with the references of tests/batch_ref.py: the
+CPU oracle's code tables and plain numpy on the original messages, never another call of the library.  tests/test_batch_ref.py pins those
 references and the edges that the case list reaches.
 
 One test per case; its id names the case.  A case runs every family and then reports all that differed, so one failure does
@@ -11,6 +12,7 @@ import pytest
 
 import __graft_entry__ as entry
 import batch_ref
+import edit_ref
 import find_ref
 from oracle import mh_oracle
 
@@ -41,7 +43,7 @@ class Rig:
         self.c, self.p0, self.msgs = case.chunk, self.w.prev0, self.w.messages
         self.n = len(self.msgs)
         self.joined = b"".join(self.msgs)
-        self.bad = []
+        self.bad, self.set = [], None
         (sc, sl), (dc, dl) = case.counts("src"), case.counts("dst")
         self.S, self.D = mhc.Model.from_counts(sc, self.so, max_len=sl), mhc.Model.from_counts(dc, self.do, max_len=dl)
         self.rs = batch_ref.pack(self.msgs, *case.codes("src"), self.so, self.p0, self.c)
@@ -119,12 +121,12 @@ class Rig:
                 self.check(not st.any() and got == w.lookup_bytes, "lookups (host form) indexed=%s" % indexed)
 
     # ---- search ----
-    def search(self, find=None, ref=None, what="search"):
+    def search(self, find=None, ref=None, what="search", ps=None, hits=None):
         w, cap_error = self.w, self.mhc.MH_ERR_CAPACITY
         find = find or (self.S.dev_find_batch_o2 if self.so == 2 else self.S.dev_find_batch)
         ref = ref or self.rs
-        ps = self.mhc.PatternSet(w.patterns, fold=w.fold)
-        hits = find_ref.find_hits(self.msgs, w.patterns, fold=w.fold)
+        ps = ps or self.mhc.PatternSet(w.patterns, fold=w.fold)
+        hits = find_ref.find_hits(self.msgs, w.patterns, fold=w.fold) if hits is None else hits
         w_off, w_rec, w_pat = find_ref.hit_arrays(hits, self.n)
         for indexed in (True, False):
             tag = "%s indexed=%s" % (what, indexed)
@@ -140,15 +142,18 @@ class Rig:
             self.check(rc == cap_error and not st.any() and same(ho, w_off) and same(rec, w_rec[:cap]) and same(pat, w_pat[:cap]), tag + ": hit_cap")
         return w_rec, w_pat
 
-    def search_and_feed_back(self):
-        w_rec, w_pat = self.search()
+    def feed_back(self, w_rec, w_pat, patterns, what):
         pick = np.unique(np.linspace(0, len(w_rec) - 1, min(len(w_rec), FEEDBACK)).astype(np.int64))
         dev = self.S.dev_decode_batch_o2_ranges if self.so == 2 else self.S.dev_decode_batch_ranges
         src, kw = self.source(self.rs, True)
         got, st, rc = dev(*src, w_rec[pick], **kw)
-        self.ok(rc, st, "hit records as lookups")
+        self.ok(rc, st, what)
         fold = find_ref.fold_ascii if self.w.fold else bytes
-        self.check([fold(g) for g in got] == [fold(self.w.patterns[int(j)]) for j in w_pat[pick]], "hit records as lookups")
+        self.check([fold(g) for g in got] == [fold(patterns[int(j)]) for j in w_pat[pick]], what)
+
+    def search_and_feed_back(self):
+        w_rec, w_pat = self.search()
+        self.feed_back(w_rec, w_pat, self.w.patterns, "hit records as lookups")
 
     # ---- coded histogram ----
     def coded_histogram(self):
@@ -180,9 +185,16 @@ class Rig:
                        tag + ": count only")
 
     # ---- per-stream models ----
+    def model_set(self):
+        """(the reference's batch with every stream under the oracle's model of its own histogram, the table files, the set)."""
+        if self.set is None:
+            re, tables = batch_ref.pack_each(self.msgs, self.so, self.p0, self.c)
+            self.set = (re, tables, self.mhc.ModelSet.from_tables(tables))
+        return self.set
+
     def each(self):
         mhc, c, p0 = self.mhc, self.c, self.p0
-        re, tables = batch_ref.pack_each(self.msgs, self.so, p0, c)
+        re, tables, ms = self.model_set()
         got = mhc.compress_each(self.msgs, order=self.so, chunk_symbols=c, prev0=p0)
         self.check([g[0] for g in got] == tables, "compress_each: tables")
         self.check([g[2] for g in got] == re.nbits.tolist(), "compress_each: nbits")
@@ -191,7 +203,6 @@ class Rig:
         if p0 == batch_ref.PREV0:                                 # the oracle's own stream of every message alone
             blobs = [mh_oracle.Model.from_data(m, self.so).compress(m)[0] for m in self.msgs]
             self.check([g[1] for g in got] == blobs, "compress_each: the oracle's files")
-        ms = mhc.ModelSet.from_tables(tables)
         for indexed in (True, False):
             src, kw = self.source(re, indexed)
             if not indexed:
@@ -228,6 +239,95 @@ class Rig:
                                       chunk_symbols=self.c, prev0=p0, check=False)
         self.check(not st.any() and out == self.joined, "decode_bank indexed")
 
+    # ---- dictionary search ----
+    def dictionary_search(self):
+        mhc, S, e = self.mhc, self.S, self.case.edits()
+        d = mhc.Dict(e.dictionary, fold=e.fold)
+        self.check((d.states, d.classes) == (e.states, e.classes), "dictionary: states, classes")
+        if self.so < 2:                                           # what test_batch_ref.py takes for the LDS that the matcher gets
+            P, nsec, in_lds = S.decode_layout()
+            lds = 1024 + (512 << P) + (((2 * nsec + 15) & ~15) if in_lds else 0)
+            self.check(lds == batch_ref.tables_lds(*self.case.codes("src"), self.so), "dictionary: the source's tables in LDS")
+        w_rec, w_pat = self.search(S.dev_find_dict_batch_o2 if self.so == 2 else S.dev_find_dict_batch, None, "dictionary search", d, e.hits)
+        if self.case.index % 4 == 0:
+            host = S.find_dict_batch_o2 if self.so == 2 else S.find_dict_batch
+            for indexed in (True, False):
+                src, kw = self.source(self.rs, indexed)
+                ho, rec, pat, st, rc = host(d, *src, **kw)
+                self.ok(rc, st, "dictionary search (host form) indexed=%s" % indexed)
+                self.check(same(ho, e.hit_off) and same(rec, w_rec) and same(pat, w_pat), "dictionary search (host form) indexed=%s" % indexed)
+        if self.eligible(self.case):
+            self.search(self.model_set()[2].find_dict, self.model_set()[0], "each dictionary search", d, e.hits)
+        self.feed_back(w_rec, w_pat, e.dictionary, "dictionary hits as lookups")
+
+    # ---- spans from hits ----
+    def spans(self):
+        e = self.case.edits()
+        want_off, want = edit_ref.merge_hits(e.hit_off, e.records)
+        for fn in (self.mhc.spans_from_hits, self.mhc.dev_spans_from_hits):
+            span_off, spans, rc = fn(e.hit_off, e.records)
+            self.check(rc == self.mhc.MH_OK and same(span_off, want_off) and same(spans, want), fn.__name__)
+
+    # ---- masked and splicing re-code ----
+    def same_recode(self, got, ref, tag, out_sym_off=None):
+        self.ok(got["rc"], got["status"], tag)
+        self.check(same(got["out_off"], ref.pay_off) and same(got["nbits"], ref.nbits) and same(got["sym_off"], self.rs.sym_off), tag + ": offsets, nbits")
+        self.check(same(got["payload"], ref.payload), tag + ": payload")
+        self.check(same(got["dropped"], ref.dropped), tag + ": dropped")
+        if out_sym_off is not None:
+            self.check(same(got["out_sym_off"], out_sym_off), tag + ": out_sym_off")
+        self.check(same(ref.slices_of(got["index"], self.c), ref.all_slices()), tag + ": index slices")
+
+    def same_counts(self, count, got, tag):
+        self.ok(count["rc"], count["status"], tag + " count only")
+        self.check(all(same(count[k], got[k]) for k in ("out_off", "nbits", "dropped", "out_sym_off") if k in got), tag + ": count only")
+
+    def edit_with(self, fn, ref, what):
+        """fn: a device form of the masked re-code, reading the reference's batch `ref`."""
+        e, x = self.case.edits(), self.case.expected()
+        for indexed in (True, False):
+            tag = "%s indexed=%s" % (what, indexed)
+            src, kw = self.source(ref, indexed)
+            got = fn(self.D, *src, e.byte_map, e.span_off, e.spans, **kw)
+            self.same_recode(got, x.edit, tag)
+            self.same_counts(fn(self.D, *src, e.byte_map, e.span_off, e.spans, count_only=True, **kw), got, tag)
+        src, kw = self.source(ref, self.case.index % 2 == 0)
+        self.same_recode(fn(self.D, *src, e.byte_map, None, None, **kw), x.edit_all, what + " everywhere")
+
+    def edit(self):
+        e, x = self.case.edits(), self.case.expected()
+        self.edit_with(self.S.dev_recode_edit_batch, self.rs, "edit (%s)" % e.map_kind)
+        if self.case.index % 4 == 0:
+            for indexed in (True, False):
+                src, kw = self.source(self.rs, indexed)
+                self.same_recode(self.S.recode_edit_batch(self.D, *src, e.byte_map, e.span_off, e.spans, **kw), x.edit,
+                                 "edit (host form) indexed=%s" % indexed)
+        if self.eligible(self.case):
+            self.edit_with(self.model_set()[2].recode_edit, self.model_set()[0], "each edit")
+
+    def splice_with(self, fn, ref, what):
+        """fn: a device form of the splicing re-code, reading the reference's batch `ref`; both replacements."""
+        e, x = self.case.edits(), self.case.expected()
+        for k, rep in enumerate(e.reps):
+            for indexed in (True, False):
+                tag = "%s of %d bytes indexed=%s" % (what, len(rep), indexed)
+                src, kw = self.source(ref, indexed)
+                got = fn(self.D, *src, rep, e.span_off, e.spans, **kw)
+                self.same_recode(got, x.splice[k], tag, x.out_sym_off[k])
+                self.same_counts(fn(self.D, *src, rep, e.span_off, e.spans, count_only=True, **kw), got, tag)
+
+    def splice(self):
+        e, x = self.case.edits(), self.case.expected()
+        self.splice_with(self.S.dev_recode_splice_batch, self.rs, "splice")
+        if self.case.index % 4 == 0:
+            for k, rep in enumerate(e.reps):
+                for indexed in (True, False):
+                    src, kw = self.source(self.rs, indexed)
+                    self.same_recode(self.S.recode_splice_batch(self.D, *src, rep, e.span_off, e.spans, **kw), x.splice[k],
+                                     "splice (host form) of %d bytes indexed=%s" % (len(rep), indexed), x.out_sym_off[k])
+        if self.eligible(self.case):
+            self.splice_with(self.model_set()[2].recode_splice, self.model_set()[0], "each splice")
+
 
     # ---- all of them ----
     @staticmethod
@@ -238,7 +338,9 @@ class Rig:
     def families(self):
         """Every family that runs for this case, in order."""
         fams = [self.encode, self.decode, self.lookups, self.search_and_feed_back, self.coded_histogram, self.recode]
-        return fams + [self.each, self.bank] if self.eligible(self.case) else fams
+        fams += [self.each, self.bank] if self.eligible(self.case) else []
+        fams += [self.dictionary_search, self.spans]
+        return fams + [self.edit, self.splice] if 2 not in self.case.orders else fams      # (edit and splice refuse an order-2 model)
 
     def run_all(self):
         for fn in self.families():
