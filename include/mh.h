@@ -547,7 +547,8 @@ size_t mh_dev_decode_batch_workspace(size_t n_streams);
  *     exactly at the next entry's offset (the last one at nbits_i), else that stream is MH_ERR_CORRUPT.
  *   - without (streams the reference wrote): d_sym_off[n + 1] is OUTPUT; a count pass decodes every stream without writing
  *     and checks that it ends exactly at nbits_i (src/coding.cpp:124,158), a scan gives the offsets, an emit pass writes the
- *     bytes — nothing at or beyond out_cap (the stream that does not fit: MH_ERR_CAPACITY).
+ *     bytes — nothing at or beyond out_cap (the stream that does not fit: MH_ERR_CAPACITY).  A stream that the count pass
+ *     refuses or finds corrupt takes 0 symbols in d_sym_off and writes no byte; the streams behind it move up.
  * d_stream_status[n] (may be NULL): MH_OK or the stream's error (MH_ERR_CORRUPT, MH_ERR_ARG: nbits_i beyond its payload
  * bytes or over MH_BATCH_WALK_MAX_BITS, MH_ERR_CAPACITY).  mh_dev_status(d_ws): the first error found. */
 int mh_dev_decode_batch(const mh_model *m, const uint8_t *d_payload, const uint64_t *d_pay_off, const uint64_t *d_nbits,
