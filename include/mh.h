@@ -1365,7 +1365,8 @@ int mh_recode_edit_batch(const mh_model *src, const mh_model *dst, const uint8_t
  *   - Host form mh_recode_splice_batch: arguments checked before a device is touched, spans and rep taken from host memory,
  *     out_index (may be NULL) with index_cap entries, the rest as mh_recode_edit_batch (index-free streams over
  *     MH_BATCH_WALK_MAX_BITS are indexed first).
- * Left out: order 2; pure insertions (begin == end); a replacement per span or per pattern.
+ * Left out of this call: order 2; pure insertions (begin == end); a replacement per span or per pattern.  The last two are
+ * SPLICING WITH A REPLACEMENT TABLE below (this call keeps refusing begin == end); order 2 is built in neither.
  * --------------------------------------------------------------------------------------------------------------------- */
 #define MH_SPLICE_MAX_REP 255u
 size_t mh_dev_recode_splice_workspace(size_t n_streams, uint64_t sym_total, uint32_t chunk_symbols, uint64_t n_spans);
@@ -1389,6 +1390,77 @@ int mh_recode_splice_batch(const mh_model *src, const mh_model *dst, const uint8
                            uint32_t rep_len, uint8_t *out_payload, size_t cap, uint64_t *out_off, uint64_t *out_nbits,
                            uint64_t *out_sym_off, uint64_t *out_index, uint64_t index_cap, uint64_t *dropped,
                            int32_t *stream_status);
+
+/* ---------------------------------------------------------------------------------------------------------------------
+ * SPLICING WITH A REPLACEMENT TABLE (extension, parity unpinned) — the splice with a replacement per span, chosen by a tag,
+ * and with insertions: `<EMAIL>` where one pattern hit, `<IP>` where another did, a third deleted, in one pass.  The
+ * arguments are mh_dev_recode_splice_batch's with d_rep, rep_len replaced by d_span_tag, d_rep_off, d_rep_bytes, n_reps.
+ *   - Table.  Replacement k is d_rep_bytes[d_rep_off[k] .. d_rep_off[k + 1]), 0 .. MH_SPLICE_MAX_REP bytes; length 0 deletes.
+ *     d_rep_off has n_reps + 1 entries (required); d_rep_bytes may be NULL when d_rep_off[n_reps] is 0.  d_rep_off[0] != 0,
+ *     decreasing offsets, an entry longer than MH_SPLICE_MAX_REP, or n_reps == 0 together with a non-empty span list:
+ *     MH_ERR_ARG through mh_dev_status(d_ws) and the call stops with nothing else written, as for bad d_pay_off.
+ *   - Tags.  d_span_tag[r] (required), parallel to d_spans, names span r's replacement.  A span whose tag is >= n_reps fails
+ *     its stream alone with MH_ERR_ARG, as a malformed list does.
+ *   - Span rule.  In this call: begin <= end <= next begin.  begin == end is an insertion in front of x[begin].  Several
+ *     insertions at one position, and an insertion touching a span on either side, are legal; they take effect in list
+ *     order.  (p, q), (p, p) with q > p is malformed.  An insertion with an empty replacement is a no-op.  A span or an
+ *     insertion with begin >= len(x) is ignored.
+ *   - Edited message.  y is x with every span that begins inside the message replaced by its tagged replacement, the end
+ *     clipped to len(x).
+ *   - Everything else is SPLICING BATCHES word for word: the output is byte for byte what mh_dev_encode_batch(dst) writes for
+ *     y; d_dropped (pairs inside and at the edges of every replacement included), d_out_sym_off and the index slices by
+ *     output position; failed streams, both capacity limits, count-only mode, index-free sources through the one-lane walk;
+ *     order 0 and 1 on both sides, a shared source or a model set (_each); order 2 is MH_ERR_ARG before any launch; no
+ *     allocation, no host synchronisation.
+ *   - Launches.  The host does not know which table entries are empty, so an indexed call always runs the deletion's
+ *     look-back: the number of launches depends on indexed versus index-free alone, never on the data or the table.  d_ws:
+ *     at least mh_dev_recode_splice_table_workspace(n, sym_total, chunk_symbols, n_spans, n_reps) bytes, 8 more per
+ *     replacement than the splice's; an indexed batch with more spans than the workspace was sized for is MH_ERR_CAPACITY
+ *     through mh_dev_status(d_ws).
+ *   - Equivalence.  With every tag 0, a one-entry table and no insertion every output equals mh_dev_recode_splice_batch's
+ *     with that replacement, byte for byte.
+ *   - Host form mh_recode_splice_table_batch: all of the table's rules (n_reps == 0 with spans included) are checked before
+ *     a device is touched and are MH_ERR_ARG; spans, tags and table taken from host memory; the rest as
+ *     mh_recode_splice_batch.
+ * Tagged spans.  mh_spans_from_hits_tagged, mh_dev_spans_from_hits_tagged (workspace: _tagged_workspace, the untagged
+ * call's) take the arguments of the untagged calls and hit_pattern (required: NULL is MH_ERR_ARG), write span_off and spans
+ * exactly as those do, and span_tag[r]: the LOWEST pattern number among the records merged into span r.  The caller sets
+ * priority by pattern order (the CLI: the earlier line of the pattern file wins).  Overflow and bad offsets as untagged; the
+ * device form keeps its guarantees (no allocation, no host synchronisation, a fixed number of launches).
+ * Left out: order 2 on either side; appending at len(x) (a span that begins there is ignored); replacements longer than
+ * MH_SPLICE_MAX_REP; back-references or any replacement computed from the matched bytes.
+ * --------------------------------------------------------------------------------------------------------------------- */
+int mh_spans_from_hits_tagged(const uint64_t *hit_off, const uint64_t *hits, const uint32_t *hit_pattern, uint64_t hit_cap,
+                              size_t n_streams, uint64_t *span_off, uint64_t *spans, uint32_t *span_tag);
+size_t mh_dev_spans_from_hits_tagged_workspace(size_t n_streams, uint64_t hit_cap);
+int mh_dev_spans_from_hits_tagged(const uint64_t *d_hit_off, const uint64_t *d_hits, const uint32_t *d_hit_pattern,
+                                  uint64_t hit_cap, size_t n_streams, uint64_t *d_span_off, uint64_t *d_spans,
+                                  uint32_t *d_span_tag, void *d_ws, size_t ws_bytes, void *stream);
+size_t mh_dev_recode_splice_table_workspace(size_t n_streams, uint64_t sym_total, uint32_t chunk_symbols, uint64_t n_spans,
+                                            size_t n_reps);
+int mh_dev_recode_splice_table_batch(const mh_model *src, const mh_model *dst, const uint8_t *d_payload,
+                                     const uint64_t *d_pay_off, const uint64_t *d_nbits, size_t n_streams, uint64_t pay_total,
+                                     uint8_t prev0, uint64_t *d_sym_off, uint64_t sym_total, const uint64_t *d_index,
+                                     uint32_t chunk_symbols, const uint64_t *d_span_off, const uint64_t *d_spans,
+                                     const uint32_t *d_span_tag, const uint64_t *d_rep_off, const uint8_t *d_rep_bytes,
+                                     size_t n_reps, uint8_t *d_out_payload, size_t cap, uint64_t *d_out_off,
+                                     uint64_t *d_out_nbits, uint64_t *d_out_sym_off, uint64_t *d_out_index, uint64_t index_cap,
+                                     uint64_t *d_dropped, int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream);
+int mh_dev_recode_splice_table_each(const mh_model_set *src, const mh_model *dst, const uint8_t *d_payload,
+                                    const uint64_t *d_pay_off, const uint64_t *d_nbits, size_t n_streams, uint64_t pay_total,
+                                    uint8_t prev0, uint64_t *d_sym_off, uint64_t sym_total, const uint64_t *d_index,
+                                    uint32_t chunk_symbols, const uint64_t *d_span_off, const uint64_t *d_spans,
+                                    const uint32_t *d_span_tag, const uint64_t *d_rep_off, const uint8_t *d_rep_bytes,
+                                    size_t n_reps, uint8_t *d_out_payload, size_t cap, uint64_t *d_out_off,
+                                    uint64_t *d_out_nbits, uint64_t *d_out_sym_off, uint64_t *d_out_index, uint64_t index_cap,
+                                    uint64_t *d_dropped, int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream);
+int mh_recode_splice_table_batch(const mh_model *src, const mh_model *dst, const uint8_t *payload, const uint64_t *pay_off,
+                                 const uint64_t *nbits, size_t n_streams, uint8_t prev0, uint64_t *sym_off,
+                                 const uint64_t *index, uint32_t chunk_symbols, const uint64_t *span_off, const uint64_t *spans,
+                                 const uint32_t *span_tag, const uint64_t *rep_off, const uint8_t *rep_bytes, size_t n_reps,
+                                 uint8_t *out_payload, size_t cap, uint64_t *out_off, uint64_t *out_nbits,
+                                 uint64_t *out_sym_off, uint64_t *out_index, uint64_t index_cap, uint64_t *dropped,
+                                 int32_t *stream_status);
 
 /* ---------------------------------------------------------------------------------------------------------------------
  * SEGMENT STATES OF INDEX-FREE ORDER-2 BATCHES (extension, parity unpinned) — the _o2 twins of the segment-state calls of

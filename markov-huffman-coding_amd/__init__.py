@@ -75,6 +75,9 @@ EXPORTS = [
     "mh_spans_from_hits", "mh_dev_spans_from_hits_workspace", "mh_dev_spans_from_hits", "mh_dev_recode_edit_workspace",
     "mh_dev_recode_edit_batch", "mh_dev_recode_edit_each", "mh_recode_edit_batch",
     "mh_dev_recode_splice_workspace", "mh_dev_recode_splice_batch", "mh_dev_recode_splice_each", "mh_recode_splice_batch",
+    "mh_spans_from_hits_tagged", "mh_dev_spans_from_hits_tagged_workspace", "mh_dev_spans_from_hits_tagged",
+    "mh_dev_recode_splice_table_workspace", "mh_dev_recode_splice_table_batch", "mh_dev_recode_splice_table_each",
+    "mh_recode_splice_table_batch",
 ]
 FIND_MAX_POSITIONS = 64                    # include/mh.h MH_FIND_MAX_POSITIONS
 FIND_FOLD_ASCII = 1                        # include/mh.h MH_FIND_FOLD_ASCII
@@ -359,6 +362,15 @@ def lib():
         for fn in (l.mh_dev_recode_splice_batch, l.mh_dev_recode_splice_each):
             fn.argtypes = l.mh_dev_recode_batch.argtypes[:12] + [vp, vp, vp, u32, vp, sz, vp, vp, vp, vp, u64, vp, vp, vp, sz, vp]
         l.mh_recode_splice_batch.argtypes = l.mh_recode_batch.argtypes[:10] + [vp, vp, vp, u32, vp, sz, vp, vp, vp, vp, u64, vp, vp]
+        l.mh_spans_from_hits_tagged.argtypes = [vp, vp, vp, u64, sz, vp, vp, vp]
+        l.mh_dev_spans_from_hits_tagged_workspace.argtypes = [sz, u64]
+        l.mh_dev_spans_from_hits_tagged_workspace.restype = sz
+        l.mh_dev_spans_from_hits_tagged.argtypes = [vp, vp, vp, u64, sz, vp, vp, vp, vp, sz, vp]
+        l.mh_dev_recode_splice_table_workspace.argtypes = [sz, u64, u32, u64, sz]
+        l.mh_dev_recode_splice_table_workspace.restype = sz
+        for fn in (l.mh_dev_recode_splice_table_batch, l.mh_dev_recode_splice_table_each):
+            fn.argtypes = l.mh_dev_recode_batch.argtypes[:12] + [vp, vp, vp, vp, vp, sz, vp, sz, vp, vp, vp, vp, u64, vp, vp, vp, sz, vp]
+        l.mh_recode_splice_table_batch.argtypes = l.mh_recode_batch.argtypes[:10] + [vp, vp, vp, vp, vp, sz, vp, sz, vp, vp, vp, vp, u64, vp, vp]
         _lib = l
     return _lib
 
@@ -974,13 +986,24 @@ def _dev_recode_edit(fn, src, dst, payload, pay_off, nbits, byte_map, span_off, 
 SPLICE_MAX_REP = 255                       # include/mh.h MH_SPLICE_MAX_REP
 
 
+def _rep_table(reps):
+    """A replacement table as the _splice_table calls take it: (rep_off[n_reps + 1], rep_bytes) from a list of byte strings, or
+    the pair itself when the caller passes one (a malformed table, for the refusals)."""
+    if isinstance(reps, tuple):
+        return np.ascontiguousarray(reps[0], dtype=np.uint64), _u8(reps[1])
+    off = np.zeros(len(reps) + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(r) for r in reps], dtype=np.uint64)
+    return off, _u8(b"".join(bytes(r) for r in reps))
+
+
 def _dev_recode_splice(fn, src, dst, payload, pay_off, nbits, rep, span_off, spans, prev0, sym_off, index, chunk_symbols, cap=None,
-                       count_only=False, want_index=True, index_cap=None, n_spans=None):
+                       count_only=False, want_index=True, index_cap=None, n_spans=None, table=None, n_reps=None):
     """One mh_dev_recode_splice_batch / _each call with guards around every output, as _dev_recode puts them.  cap None or
     index_cap None: a count-only call first, then one with exactly out_off[n] bytes and (out_sym_off[n] // chunk) + n entries of
     room.  Returns the dict of _dev_recode and out_sym_off[n + 1].  Asserts that nothing changed outside out_off[n] payload
     bytes, the n + 1 offsets, the n lengths and counts and the index slices, laid out by out_sym_off, of the streams that
-    passed and did not become empty."""
+    passed and did not become empty.  table = (span_tag, reps): fn is a _splice_table call, `rep` is unused, and the
+    workspace is mh_dev_recode_splice_table_workspace's (n_reps: what it is sized for, else the table's)."""
     l = lib()
     n, pay_total, d_pl, d_po, d_nb, so, d_idx = _dev_source(payload, pay_off, nbits, sym_off, index)
     indexed = index is not None
@@ -991,13 +1014,26 @@ def _dev_recode_splice(fn, src, dst, payload, pay_off, nbits, rep, span_off, spa
     d_sof = DeviceBuffer(sof.nbytes, sof)
     d_sp = DeviceBuffer(max(sp.nbytes, 16), sp if sp.size else None)
     d_rep = DeviceBuffer(max(r.size, 16), np.concatenate([r, np.zeros(16, dtype=np.uint8)])[:max(r.size, 16)]) if r.size else None
+    if table is not None:
+        tg = np.ascontiguousarray(table[0], dtype=np.uint32)
+        roff, rb = _rep_table(table[1])
+        nreps = len(roff) - 1
+        d_tg = DeviceBuffer(max(tg.nbytes, 16), tg if tg.size else None)
+        d_roff = DeviceBuffer(roff.nbytes, roff)
+        d_rb = DeviceBuffer(max(rb.size, 16), np.concatenate([rb, np.zeros(16, dtype=np.uint8)])[:max(rb.size, 16)]) if rb.size else None
+        how = (d_tg.ptr, d_roff.ptr, d_rb.ptr if d_rb else None, nreps)
+    else:
+        how = (d_rep.ptr if d_rep else None, r.size)
     d_st = DeviceBuffer(max(n, 1) * 4, np.full(max(n, 1), 99, dtype=np.int32))
     st = int(so[n]) if indexed else 0
     ns = sp.size // 2 if n_spans is None else n_spans
 
     def call(room, with_payload, nidx):
         d_so = DeviceBuffer((n + 1 + G) * 8, np.concatenate([so if indexed else np.full(n + 1, F, dtype=np.uint64), np.full(G, F, dtype=np.uint64)]))
-        wsb = l.mh_dev_recode_splice_workspace(n, st, chunk_symbols if indexed else 0, ns)
+        if table is not None:
+            wsb = l.mh_dev_recode_splice_table_workspace(n, st, chunk_symbols if indexed else 0, ns, nreps if n_reps is None else n_reps)
+        else:
+            wsb = l.mh_dev_recode_splice_workspace(n, st, chunk_symbols if indexed else 0, ns)
         d_ws = DeviceBuffer(wsb)
         d_out = DeviceBuffer(room + RANGE_GUARD + 16, np.full(room + RANGE_GUARD + 16, RANGE_FILL, dtype=np.uint8)) if with_payload else None
         d_oo = DeviceBuffer((n + 1 + G) * 8, np.full(n + 1 + G, F, dtype=np.uint64))
@@ -1006,7 +1042,7 @@ def _dev_recode_splice(fn, src, dst, payload, pay_off, nbits, rep, span_off, spa
         d_dr = DeviceBuffer((n + G) * 8, np.full(n + G, F, dtype=np.uint64))
         d_oi = DeviceBuffer((nidx + G) * 8, np.full(nidx + G, F, dtype=np.uint64)) if nidx is not None else None
         _check(fn(src, dst, d_pl.ptr, d_po.ptr, d_nb.ptr, n, pay_total, prev0, d_so.ptr, st, d_idx.ptr if d_idx else None, chunk_symbols,
-                  d_sof.ptr, d_sp.ptr, d_rep.ptr if d_rep else None, r.size, d_out.ptr if d_out else None, room, d_oo.ptr, d_onb.ptr, d_oso.ptr,
+                  d_sof.ptr, d_sp.ptr, *how, d_out.ptr if d_out else None, room, d_oo.ptr, d_onb.ptr, d_oso.ptr,
                   d_oi.ptr if d_oi else None, nidx or 0, d_dr.ptr, d_st.ptr, d_ws.ptr, wsb, None), "mh_dev_recode_splice_*")
         rc = l.mh_dev_status(d_ws.ptr, None)
         oo, onb, dr, dso = d_oo.download(np.uint64), d_onb.download(np.uint64), d_dr.download(np.uint64), d_so.download(np.uint64)
@@ -1082,6 +1118,53 @@ def dev_spans_from_hits(hit_off, hits, hit_cap=None):
     m = int(so[n])
     assert m <= cap and (sp[2 * m:] == FIND_FILL).all(), "pairs written at or beyond the spans"
     return so[:n + 1], sp[:2 * m].reshape(-1, 2), rc
+
+
+def spans_from_hits_tagged(hit_off, hits, hit_pattern, hit_cap=None):
+    """mh_spans_from_hits_tagged (host, no device): spans_from_hits and span_tag[m], the lowest pattern number among the
+    records merged into each span: (span_off, spans, span_tag, return code)."""
+    hit_off = np.ascontiguousarray(hit_off, dtype=np.uint64)
+    hits = np.ascontiguousarray(hits, dtype=np.uint64).reshape(-1)
+    pat = np.ascontiguousarray(hit_pattern, dtype=np.uint32)
+    n = len(hit_off) - 1
+    cap = hits.size // 3 if hit_cap is None else hit_cap
+    so, sp = np.full(n + 1, FIND_FILL, dtype=np.uint64), np.zeros(2 * max(cap, 1), dtype=np.uint64)
+    tg = np.full(max(cap, 1), 0xFFFFFFFF, dtype=np.uint32)
+    rc = lib().mh_spans_from_hits_tagged(hit_off.ctypes.data, _ptr(hits), pat.ctypes.data, cap, n, so.ctypes.data, sp.ctypes.data, tg.ctypes.data)
+    if rc not in (MH_OK, MH_ERR_CAPACITY):
+        raise MhError(rc, "mh_spans_from_hits_tagged")
+    m = int(so[n])
+    return so, sp[:2 * m].reshape(-1, 2), tg[:m], rc
+
+
+def dev_spans_from_hits_tagged(hit_off, hits, hit_pattern, hit_cap=None):
+    """One mh_dev_spans_from_hits_tagged call on uploaded records: (span_off[n + 1], spans[m, 2], span_tag[m], mh_dev_status);
+    asserts that the FIND_GUARD words behind the three outputs, and every pair and tag at or beyond the spans, kept their
+    fill."""
+    l = lib()
+    hit_off = np.ascontiguousarray(hit_off, dtype=np.uint64)
+    hits = np.ascontiguousarray(hits, dtype=np.uint64).reshape(-1)
+    pat = np.ascontiguousarray(hit_pattern, dtype=np.uint32)
+    n = len(hit_off) - 1
+    cap = hits.size // 3 if hit_cap is None else hit_cap
+    fill32 = FIND_FILL & 0xFFFFFFFF
+    d_ho = DeviceBuffer(hit_off.nbytes, hit_off)
+    d_h = DeviceBuffer(max(hits.nbytes, 8), hits if hits.size else None)
+    d_pat = DeviceBuffer(max(pat.nbytes, 8), pat if pat.size else None)
+    d_so = DeviceBuffer((n + 1 + FIND_GUARD) * 8, np.full(n + 1 + FIND_GUARD, FIND_FILL, dtype=np.uint64))
+    d_sp = DeviceBuffer((2 * cap + FIND_GUARD) * 8, np.full(2 * cap + FIND_GUARD, FIND_FILL, dtype=np.uint64))
+    d_tg = DeviceBuffer((cap + FIND_GUARD) * 4, np.full(cap + FIND_GUARD, fill32, dtype=np.uint32))
+    wsb = l.mh_dev_spans_from_hits_tagged_workspace(n, cap)
+    d_ws = DeviceBuffer(wsb, np.full(wsb, 0xA5, dtype=np.uint8))
+    _check(l.mh_dev_spans_from_hits_tagged(d_ho.ptr, d_h.ptr, d_pat.ptr, cap, n, d_so.ptr, d_sp.ptr, d_tg.ptr, d_ws.ptr, wsb, None),
+           "mh_dev_spans_from_hits_tagged")
+    rc = l.mh_dev_status(d_ws.ptr, None)
+    so, sp, tg = d_so.download(np.uint64), d_sp.download(np.uint64), d_tg.download(np.uint32)
+    assert (so[n + 1:] == FIND_FILL).all(), "words written behind span_off"
+    m = int(so[n])
+    assert m <= cap and (sp[2 * m:] == FIND_FILL).all(), "pairs written at or beyond the spans"
+    assert (tg[m:] == fill32).all(), "tags written at or beyond the spans"
+    return so[:n + 1], sp[:2 * m].reshape(-1, 2), tg[:m], rc
 
 
 def histogram_coded_batch_o2(src, order, payload, pay_off, nbits, prev0=PREV0, sym_off=None, index=None, chunk_symbols=0):
@@ -1420,10 +1503,21 @@ class Model:
         return _dev_recode_splice(lib().mh_dev_recode_splice_batch, self._h, dst.handle, payload, pay_off, nbits, rep, span_off, spans, prev0,
                                   sym_off, index, chunk_symbols, **kw)
 
+    def dev_recode_splice_table_batch(self, dst, payload, pay_off, nbits, span_tag, reps, span_off, spans, prev0=PREV0, sym_off=None,
+                                      index=None, chunk_symbols=0, **kw):
+        """One mh_dev_recode_splice_table_batch call: span r replaced by reps[span_tag[r]] (b"": deleted; begin == end: an
+        insertion).  reps: a list of byte strings, or (rep_off, rep_bytes).  The dict of _dev_recode_splice, with its guards."""
+        return _dev_recode_splice(lib().mh_dev_recode_splice_table_batch, self._h, dst.handle, payload, pay_off, nbits, b"", span_off, spans, prev0,
+                                  sym_off, index, chunk_symbols, table=(span_tag, reps), **kw)
+
+    def recode_splice_table_batch(self, dst, payload, pay_off, nbits, span_tag, reps, span_off, spans, **kw):
+        """mh_recode_splice_table_batch (host form): recode_splice_batch with a replacement per span; the same dict."""
+        return self.recode_splice_batch(dst, payload, pay_off, nbits, b"", span_off, spans, table=(span_tag, reps), **kw)
+
     def recode_splice_batch(self, dst, payload, pay_off, nbits, rep, span_off, spans, prev0=PREV0, sym_off=None, index=None, chunk_symbols=0,
-                            cap=None, want_index=True, index_cap=None, check=True):
+                            cap=None, want_index=True, index_cap=None, check=True, table=None):
         """mh_recode_splice_batch (host form): the dict of _recode_batch and out_sym_off[n + 1].  cap / index_cap None: room for
-        the worst case, every span one byte wide and replaced."""
+        the worst case, every span one byte wide and replaced.  table = (span_tag, reps): mh_recode_splice_table_batch."""
         l = lib()
         payload = _u8(payload)
         pay_off = np.ascontiguousarray(pay_off, dtype=np.uint64)
@@ -1440,6 +1534,15 @@ class Model:
             so = np.zeros(n + 1, dtype=np.uint64)
             bound = int(sum(int(b) // max(self.min_code_len, 1) for b in nbits))
         bound += (sp.size // 2) * int(r.size)
+        if table is not None:
+            tg = np.ascontiguousarray(table[0], dtype=np.uint32)
+            roff, rb = _rep_table(table[1])
+            bound += (sp.size // 2) * SPLICE_MAX_REP
+            how = (tg.ctypes.data if tg.size else pay_off.ctypes.data, roff.ctypes.data, _ptr(rb), len(roff) - 1)
+            fn, name = l.mh_recode_splice_table_batch, "mh_recode_splice_table_batch"
+        else:
+            how = (_ptr(r), r.size)
+            fn, name = l.mh_recode_splice_batch, "mh_recode_splice_batch"
         if cap is None:
             cap = l.mh_encode_batch_bound(dst.handle, bound, n)
         out = np.zeros(max(cap, 1), dtype=np.uint8)
@@ -1451,13 +1554,13 @@ class Model:
             if index_cap is None:
                 index_cap = int(l.mh_batch_index_capacity(bound, n, chunk_symbols))
             oi = np.full(max(index_cap, 1), FIND_FILL, dtype=np.uint64)
-        rc = l.mh_recode_splice_batch(self._h, dst.handle, _ptr(payload), pay_off.ctypes.data, nbits.ctypes.data if n else None, n, prev0,
-                                      so.ctypes.data, (idx.ctypes.data if idx.size else pay_off.ctypes.data) if idx is not None else None,
-                                      chunk_symbols, sof.ctypes.data, _ptr(sp), _ptr(r), r.size, out.ctypes.data, cap, oo.ctypes.data,
-                                      onb.ctypes.data, oso.ctypes.data, oi.ctypes.data if oi is not None else None, index_cap or 0, dr.ctypes.data,
-                                      st.ctypes.data)
+        rc = fn(self._h, dst.handle, _ptr(payload), pay_off.ctypes.data, nbits.ctypes.data if n else None, n, prev0,
+                so.ctypes.data, (idx.ctypes.data if idx.size else pay_off.ctypes.data) if idx is not None else None,
+                chunk_symbols, sof.ctypes.data, _ptr(sp), *how, out.ctypes.data, cap, oo.ctypes.data,
+                onb.ctypes.data, oso.ctypes.data, oi.ctypes.data if oi is not None else None, index_cap or 0, dr.ctypes.data,
+                st.ctypes.data)
         if rc != MH_OK and (check or not (st[:n].any() or rc == MH_ERR_CAPACITY)):
-            raise MhError(rc, "mh_recode_splice_batch")
+            raise MhError(rc, name)
         return dict(payload=out[:min(int(oo[n]), cap)], out_off=oo, nbits=onb[:n], index=oi, dropped=dr[:n], status=st[:n], sym_off=so,
                     out_sym_off=oso, rc=rc)
 
@@ -1960,6 +2063,12 @@ class ModelSet:
         """One mh_dev_recode_edit_each call: recode with map[b] coded for every byte b inside the spans: the dict of _dev_recode."""
         return _dev_recode_edit(lib().mh_dev_recode_edit_each, self._h, dst.handle, payload, pay_off, nbits, byte_map, span_off, spans, prev0,
                                 sym_off, index, chunk_symbols, **kw)
+
+    def recode_splice_table(self, dst, payload, pay_off, nbits, span_tag, reps, span_off, spans, prev0=PREV0, sym_off=None, index=None,
+                            chunk_symbols=0, **kw):
+        """One mh_dev_recode_splice_table_each call: Model.dev_recode_splice_table_batch under this set."""
+        return _dev_recode_splice(lib().mh_dev_recode_splice_table_each, self._h, dst.handle, payload, pay_off, nbits, b"", span_off, spans, prev0,
+                                  sym_off, index, chunk_symbols, table=(span_tag, reps), **kw)
 
     def recode_splice(self, dst, payload, pay_off, nbits, rep, span_off, spans, prev0=PREV0, sym_off=None, index=None, chunk_symbols=0, **kw):
         """One mh_dev_recode_splice_each call: recode with every span replaced by `rep` (b"": deleted): the dict of

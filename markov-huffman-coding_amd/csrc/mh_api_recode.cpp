@@ -96,6 +96,12 @@ struct SpliceArgs {
     uint64_t *out_sym_off;
     uint64_t index_cap;
     uint64_t n_spans;                   // host forms: what the workspace is sized for
+    // a _splice_table call: rep / rep_len unused, span r replaced by table entry span_tag[r]
+    bool table = false;
+    const uint32_t *span_tag = nullptr;
+    const uint64_t *rep_off = nullptr;
+    const uint8_t *rep_bytes = nullptr;
+    size_t n_reps = 0;
 };
 
 // what a _splice entry point refuses before anything else: order 2 on either side (m: null under a set), the replacement
@@ -103,7 +109,13 @@ int splice_args(const mh_model *m, const mh_model_set *set, size_t n, const mh_m
     if (set ? n != set->d.n : !order01(m)) return MH_ERR_ARG;
     if (!order01(dst)) return MH_ERR_ARG;
     if (s.rep_len > MH_SPLICE_MAX_REP || (s.rep_len && !s.rep) || !s.span_off || !s.out_sym_off) return MH_ERR_ARG;
+    if (s.table && (!s.span_tag || !s.rep_off)) return MH_ERR_ARG;
     return MH_OK;
+}
+
+// the workspace of a _splice or _splice_table call
+mhr::SpliceLayout splice_layout_of(const SpliceArgs &s, uint64_t n, uint64_t nwork, uint64_t n_spans) {
+    return s.table ? mhr::splice_table_layout(n, nwork, n_spans, s.n_reps) : mhr::splice_layout(n, nwork, n_spans);
 }
 
 // behind splice_args: recode() with the splice in place of the edit, its own workspace layout and out_sym_off
@@ -115,8 +127,8 @@ int splice(const mh_model *m, const mh_model_set *set, const mh_model *dst, cons
     if (!aligned16(d_out_payload)) return MH_ERR_ARG;
     int oshift = 0;                                                   // index-free: the chunk size is the destination index's
     if (!a.index && d_out_index && (oshift = chunk_shift_of(a.chunk_symbols)) < 0) return MH_ERR_ARG;
-    mhr::SpliceParams p{};
-    const mhr::SpliceLayout L = mhr::splice_layout(a.n, work_items_of(a), 0);
+    mhr::SpliceTableParams p{};
+    const mhr::SpliceLayout L = splice_layout_of(s, a.n, work_items_of(a), 0);
     const int rc = dev_batch_params(a, SymOff::Through, ctx_of_prev0(m, a.prev0), d_ws, ws_bytes, L.total, L.off_status, d_stream_status, p.s.b);
     if (rc != MH_OK) return rc;
     if (a.index) oshift = int(p.s.b.chunk_shift);
@@ -141,6 +153,14 @@ int splice(const mh_model *m, const mh_model_set *set, const mh_model *dst, cons
     p.sp.rep_len = s.rep_len;
     p.sp.out_sym_off = reinterpret_cast<unsigned long long *>(s.out_sym_off);
     p.sp.index_cap = s.index_cap;
+    if (s.table) {
+        p.tb.span_tag = s.span_tag;
+        p.tb.rep_off = reinterpret_cast<const unsigned long long *>(s.rep_off);
+        p.tb.rep_bytes = s.rep_bytes;
+        p.tb.n_reps = s.n_reps;
+        HIP_TRY(mhr::launch_recode_splice_table(p, model, d_ws, ws_bytes, static_cast<hipStream_t>(stream)));
+        return MH_OK;
+    }
     HIP_TRY(mhr::launch_recode_splice(p, model, d_ws, ws_bytes, static_cast<hipStream_t>(stream)));
     return MH_OK;
 }
@@ -184,7 +204,7 @@ struct HostRecode {
         const hipStream_t st = nullptr;
         const size_t n = a.n;
         noidx = !out_index ? 0 : (spl ? size_t(spl->index_cap) : size_t(mh_batch_index_capacity(a.sym_total, n, a.chunk_symbols)));
-        const size_t wsb = spl ? mhr::splice_layout(n, work_items_of(a), spl->n_spans).total
+        const size_t wsb = spl ? splice_layout_of(*spl, n, work_items_of(a), spl->n_spans).total
                                : recode_workspace(n, a.sym_total, a.index ? a.chunk_symbols : 0, seam);
         dcap = want_payload ? cap : 0;
         HIP_TRY(d_out.alloc(dcap));
@@ -393,6 +413,41 @@ int mh_dev_spans_from_hits(const uint64_t *d_hit_off, const uint64_t *d_hits, ui
     return MH_OK;
 }
 
+int mh_spans_from_hits_tagged(const uint64_t *hit_off, const uint64_t *hits, const uint32_t *hit_pattern, uint64_t hit_cap, size_t n_streams,
+                              uint64_t *span_off, uint64_t *spans, uint32_t *span_tag) {
+    if (!hit_pattern) return MH_ERR_ARG;
+    const int rc = mh_spans_from_hits(hit_off, hits, hit_cap, n_streams, span_off, spans);
+    if (rc != MH_OK) return rc;
+    if (span_off[n_streams] && !span_tag) return MH_ERR_ARG;
+    // span q of stream i holds the records whose end lies in (end(q - 1), end(q)]: records ascend by end
+    for (size_t i = 0; i < n_streams; ++i) {
+        uint64_t r = hit_off[i];
+        for (uint64_t q = span_off[i]; q < span_off[i + 1]; ++q) {
+            uint32_t t = ~uint32_t(0);
+            for (; r < hit_off[i + 1] && hits[3 * r + 2] <= spans[2 * q + 1]; ++r) t = std::min(t, hit_pattern[r]);
+            span_tag[q] = t;
+        }
+    }
+    return MH_OK;
+}
+
+size_t mh_dev_spans_from_hits_tagged_workspace(size_t n_streams, uint64_t hit_cap) { return mh_dev_spans_from_hits_workspace(n_streams, hit_cap); }
+
+int mh_dev_spans_from_hits_tagged(const uint64_t *d_hit_off, const uint64_t *d_hits, const uint32_t *d_hit_pattern, uint64_t hit_cap,
+                                  size_t n_streams, uint64_t *d_span_off, uint64_t *d_spans, uint32_t *d_span_tag, void *d_ws, size_t ws_bytes,
+                                  void *stream) {
+    if (!d_hit_pattern || (hit_cap && !d_span_tag)) return MH_ERR_ARG;
+    if (!d_hit_off || !d_span_off || !d_ws || (hit_cap && (!d_hits || !d_spans)) || !aligned16(d_ws)) return MH_ERR_ARG;
+    if (hit_cap >= (uint64_t(1) << 40)) return MH_ERR_ARG;
+    if (ws_bytes < mhr::span_layout(hit_cap).total) return MH_ERR_CAPACITY;
+    if (!have_device()) return MH_ERR_NO_DEVICE;
+    HIP_TRY(mhr::launch_spans_from_hits_tagged(reinterpret_cast<const unsigned long long *>(d_hit_off),
+                                               reinterpret_cast<const unsigned long long *>(d_hits), d_hit_pattern, hit_cap, n_streams,
+                                               reinterpret_cast<unsigned long long *>(d_span_off), reinterpret_cast<unsigned long long *>(d_spans),
+                                               d_span_tag, d_ws, static_cast<hipStream_t>(stream)));
+    return MH_OK;
+}
+
 size_t mh_dev_recode_edit_workspace(size_t n_streams, uint64_t sym_total, uint32_t chunk_symbols) {
     return recode_workspace(n_streams, sym_total, chunk_symbols, false);
 }
@@ -505,6 +560,85 @@ int mh_recode_splice_batch(const mh_model *src, const mh_model *dst, const uint8
     if (s.n_spans) HIP_TRY(hipMemcpy(d_sp.p, spans, size_t(s.n_spans) * 16, hipMemcpyHostToDevice));
     if (rep_len) HIP_TRY(hipMemcpy(d_rep.p, rep, rep_len, hipMemcpyHostToDevice));
     s.span_off = d_soff.as<uint64_t>(); s.spans = d_sp.as<uint64_t>(); s.rep = rep_len ? d_rep.as<uint8_t>() : nullptr;
+    HostRecode hr;
+    hr.spl = &s;
+    rc = hr.run(false, nullptr, src, dst, a, sym_off, out_payload != nullptr, cap, out_off, out_nbits, out_index);
+    if (rc != MH_OK) return rc;
+    if ((rc = hr.payload(out_payload, out_off[n_streams])) != MH_OK || (rc = hr.slices(out_index)) != MH_OK) return rc;
+    return hr.finish(idx_st, dropped, stream_status);
+}
+
+/* ----------------------------------------------------------------------------------------------- table splice */
+
+size_t mh_dev_recode_splice_table_workspace(size_t n_streams, uint64_t sym_total, uint32_t chunk_symbols, uint64_t n_spans, size_t n_reps) {
+    const uint64_t W = chunk_shift_of(chunk_symbols) >= 0 ? mhb::work_items(n_streams, sym_total, chunk_symbols) : 0;
+    return mhr::splice_table_layout(n_streams, W, n_spans, n_reps).total;
+}
+
+int mh_dev_recode_splice_table_batch(const mh_model *src, const mh_model *dst, const uint8_t *d_payload, const uint64_t *d_pay_off,
+                                     const uint64_t *d_nbits, size_t n_streams, uint64_t pay_total, uint8_t prev0, uint64_t *d_sym_off,
+                                     uint64_t sym_total, const uint64_t *d_index, uint32_t chunk_symbols, const uint64_t *d_span_off,
+                                     const uint64_t *d_spans, const uint32_t *d_span_tag, const uint64_t *d_rep_off, const uint8_t *d_rep_bytes,
+                                     size_t n_reps, uint8_t *d_out_payload, size_t cap, uint64_t *d_out_off, uint64_t *d_out_nbits,
+                                     uint64_t *d_out_sym_off, uint64_t *d_out_index, uint64_t index_cap, uint64_t *d_dropped,
+                                     int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
+    const SpliceArgs s{d_span_off, d_spans, nullptr, 0, d_out_sym_off, index_cap, 0, true, d_span_tag, d_rep_off, d_rep_bytes, n_reps};
+    const int rc = splice_args(src, nullptr, n_streams, dst, s);
+    if (rc != MH_OK) return rc;
+    return splice(src, nullptr, dst, s, {d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index, chunk_symbols},
+                  d_out_payload, cap, d_out_off, d_out_nbits, d_out_index, d_dropped, d_stream_status, d_ws, ws_bytes, stream);
+}
+
+int mh_dev_recode_splice_table_each(const mh_model_set *src, const mh_model *dst, const uint8_t *d_payload, const uint64_t *d_pay_off,
+                                    const uint64_t *d_nbits, size_t n_streams, uint64_t pay_total, uint8_t prev0, uint64_t *d_sym_off,
+                                    uint64_t sym_total, const uint64_t *d_index, uint32_t chunk_symbols, const uint64_t *d_span_off,
+                                    const uint64_t *d_spans, const uint32_t *d_span_tag, const uint64_t *d_rep_off, const uint8_t *d_rep_bytes,
+                                    size_t n_reps, uint8_t *d_out_payload, size_t cap, uint64_t *d_out_off, uint64_t *d_out_nbits,
+                                    uint64_t *d_out_sym_off, uint64_t *d_out_index, uint64_t index_cap, uint64_t *d_dropped,
+                                    int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
+    if (!src) return MH_ERR_ARG;
+    const SpliceArgs s{d_span_off, d_spans, nullptr, 0, d_out_sym_off, index_cap, 0, true, d_span_tag, d_rep_off, d_rep_bytes, n_reps};
+    const int rc = splice_args(nullptr, src, n_streams, dst, s);
+    if (rc != MH_OK) return rc;
+    return splice(nullptr, src, dst, s, {d_payload, d_pay_off, d_nbits, n_streams, pay_total, prev0, d_sym_off, sym_total, d_index, chunk_symbols},
+                  d_out_payload, cap, d_out_off, d_out_nbits, d_out_index, d_dropped, d_stream_status, d_ws, ws_bytes, stream);
+}
+
+int mh_recode_splice_table_batch(const mh_model *src, const mh_model *dst, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits,
+                                 size_t n_streams, uint8_t prev0, uint64_t *sym_off, const uint64_t *index, uint32_t chunk_symbols,
+                                 const uint64_t *span_off, const uint64_t *spans, const uint32_t *span_tag, const uint64_t *rep_off,
+                                 const uint8_t *rep_bytes, size_t n_reps, uint8_t *out_payload, size_t cap, uint64_t *out_off,
+                                 uint64_t *out_nbits, uint64_t *out_sym_off, uint64_t *out_index, uint64_t index_cap, uint64_t *dropped,
+                                 int32_t *stream_status) {
+    SpliceArgs s{span_off, spans, nullptr, 0, out_sym_off, out_index ? index_cap : 0, 0, true, span_tag, rep_off, rep_bytes, n_reps};
+    int rc = splice_args(src, nullptr, n_streams, dst, s);
+    if (rc != MH_OK) return rc;
+    if (!offsets_ok(span_off, n_streams) || (span_off[n_streams] && !spans)) return MH_ERR_ARG;
+    // the table, as the device checks it, before a device is touched
+    if (rep_off[0] != 0 || (span_off[n_streams] && !n_reps)) return MH_ERR_ARG;
+    for (size_t k = 0; k < n_reps; ++k)
+        if (rep_off[k + 1] < rep_off[k] || rep_off[k + 1] - rep_off[k] > MH_SPLICE_MAX_REP) return MH_ERR_ARG;
+    const size_t rep_total = size_t(rep_off[n_reps]);
+    if (rep_total && !rep_bytes) return MH_ERR_ARG;
+    CodedBatch a{payload, pay_off, nbits, n_streams, 0, prev0, sym_off, 0, index, chunk_symbols};
+    std::vector<uint64_t> own_idx;
+    std::vector<int32_t> idx_st;
+    rc = host_args(src, dst, a, true, out_off, out_nbits, out_index, sym_off, own_idx, idx_st);
+    if (rc != MH_OK) return rc;
+    DevBuf d_soff, d_sp, d_tag, d_roff, d_rep;
+    s.n_spans = span_off[n_streams];
+    HIP_TRY(d_soff.alloc((n_streams + 1) * 8));
+    HIP_TRY(d_sp.alloc(size_t(s.n_spans) * 16));
+    HIP_TRY(d_tag.alloc(size_t(s.n_spans) * 4 + 4));
+    HIP_TRY(d_roff.alloc((n_reps + 1) * 8));
+    HIP_TRY(d_rep.alloc(rep_total));
+    HIP_TRY(hipMemcpy(d_soff.p, span_off, (n_streams + 1) * 8, hipMemcpyHostToDevice));
+    if (s.n_spans) HIP_TRY(hipMemcpy(d_sp.p, spans, size_t(s.n_spans) * 16, hipMemcpyHostToDevice));
+    if (s.n_spans) HIP_TRY(hipMemcpy(d_tag.p, span_tag, size_t(s.n_spans) * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_roff.p, rep_off, (n_reps + 1) * 8, hipMemcpyHostToDevice));
+    if (rep_total) HIP_TRY(hipMemcpy(d_rep.p, rep_bytes, rep_total, hipMemcpyHostToDevice));
+    s.span_off = d_soff.as<uint64_t>(); s.spans = d_sp.as<uint64_t>(); s.span_tag = d_tag.as<uint32_t>();
+    s.rep_off = d_roff.as<uint64_t>(); s.rep_bytes = rep_total ? d_rep.as<uint8_t>() : nullptr;
     HostRecode hr;
     hr.spl = &s;
     rc = hr.run(false, nullptr, src, dst, a, sym_off, out_payload != nullptr, cap, out_off, out_nbits, out_index);

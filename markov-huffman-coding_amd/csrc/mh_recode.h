@@ -136,6 +136,30 @@ inline SpliceLayout splice_layout(uint64_t n_streams, uint64_t nwork, uint64_t n
     return l;
 }
 
+// the table of a table splice (include/mh.h, "SPLICING WITH A REPLACEMENT TABLE"): span r is replaced by entry span_tag[r],
+// the bytes rep_bytes[rep_off[k] .. rep_off[k + 1]); sp.rep / sp.rep_len / sp.rep_lds are unused
+struct SpliceTable {
+    const uint32_t *span_tag;             // one per span
+    const unsigned long long *rep_off;    // n_reps + 1
+    const uint8_t *rep_bytes;
+    uint64_t n_reps;
+};
+
+struct SpliceTableParams : SpliceParams {
+    SpliceTable tb;
+};
+
+// table splice workspace: the splice's, with the bits and drops of rep_k[1..] per table entry (2 x u32 each; one entry's
+// room at least, so a one-entry table lays out as the single replacement does)
+inline SpliceLayout splice_table_layout(uint64_t n_streams, uint64_t nwork, uint64_t n_spans, uint64_t n_reps) {
+    SpliceLayout l = splice_layout(n_streams, nwork, 0);
+    const uint64_t len = (nwork > n_streams ? nwork : n_streams) + 1;
+    l.off_sums = (l.off_price + size_t(n_reps ? n_reps : 1) * 8 + 15) & ~size_t(15);
+    l.off_sctx = l.off_sums + size_t(mhb::scan_blocks(len) + 1) * 8;
+    l.total = (l.off_sctx + size_t(n_spans) * 4 + 255) & ~size_t(255);
+    return l;
+}
+
 // spans from search records: status block | per record: the reverse min-scan of the begins (u64), span starts and, scanned in
 // place, span numbers (u64, cap + 2) | per tile of SPAN_TILE records: first stream, last stream, the first record's scan
 // value, the carry from the tiles behind | scan block sums | per stream: nothing beyond the offsets the caller passes
@@ -162,9 +186,15 @@ hipError_t launch_recode(const RecodeParams &p, mhb::Model model, void *d_ws, hi
 hipError_t launch_recode_edit(const EditParams &p, mhb::Model model, void *d_ws, hipStream_t st);
 // the splice in place of the edit; order 0/1 on both sides, p.sp.span_off not null
 hipError_t launch_recode_splice(const SpliceParams &p, mhb::Model model, void *d_ws, size_t ws_bytes, hipStream_t st);
+// the table splice: a replacement per span, insertions (begin == end) legal; order 0/1 on both sides
+hipError_t launch_recode_splice_table(const SpliceTableParams &p, mhb::Model model, void *d_ws, size_t ws_bytes, hipStream_t st);
 // the records of a find call (ascending (stream, end, pattern)) merged into maximal spans; a total over hit_cap: the status
 // word is MHK_STATUS_CAPACITY, span_off all zeros
 hipError_t launch_spans_from_hits(const unsigned long long *hit_off, const unsigned long long *hits, uint64_t hit_cap, uint64_t n_streams,
                                   unsigned long long *span_off, unsigned long long *spans, void *d_ws, hipStream_t st);
+// the same, and span_tag[r]: the lowest hit_pattern among the records merged into span r
+hipError_t launch_spans_from_hits_tagged(const unsigned long long *hit_off, const unsigned long long *hits, const uint32_t *hit_pattern,
+                                         uint64_t hit_cap, uint64_t n_streams, unsigned long long *span_off, unsigned long long *spans,
+                                         uint32_t *span_tag, void *d_ws, hipStream_t st);
 
 }  // namespace mhr

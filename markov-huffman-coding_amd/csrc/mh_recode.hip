@@ -19,7 +19,10 @@
 //   splice_*_kernel          (include/mh.h "SPLICING BATCHES") spans deleted or replaced by a string of another length: the
 //                            same stages with a second scan for output positions and an index laid out by them; see
 //                            "the splice" below
-//   histc_idx_kernel         one lane per (stream, chunk): counts the pairs as it decodes; a chunk that fails takes its own
+//   splice_t*_kernel         (include/mh.h "SPLICING WITH A REPLACEMENT TABLE") the splice with a replacement per span, chosen by the
+//                            span's tag from a table, and insertions: siblings of splice_*_kernel; see "the table splice" below
+//   spans_tag_kernel         (mh_dev_spans_from_hits_tagged) the lowest pattern number of each merged span
+//   histc_idx_kernel        one lane per (stream, chunk): counts the pairs as it decodes; a chunk that fails takes its own
 //                            counts back; <FIX>: the chunks that passed inside a stream that failed take theirs back
 //   histc_walk_kernel        index-free, one lane per stream: counts, and takes the stream's counts back when it fails
 // Verdicts are the batch decoders' (mh_dev_decode_batch, _each, _batch_o2 by the source model): same checks, same statuses.
@@ -1220,6 +1223,377 @@ __global__ __launch_bounds__((Dec<K, false>::NT)) void splice_walk_kernel(Splice
     }
 }
 
+// ------------------------------------------------------------------------------------------------ table splice
+
+// the table splice   (include/mh.h, "SPLICING WITH A REPLACEMENT TABLE".)  The splice with a replacement per span: span r is
+//              replaced by table entry tag[r], and begin == end inserts in front of x[begin].  The stages, the ownership rule
+//              (the lane whose symbols contain begin codes the replacement: an insertion at a chunk boundary belongs to the
+//              lane of the chunk that starts there), the two scans and the index by output positions are the splice's; these
+//              kernels are its siblings with the cursor below.  The table is read from L2, once per owned span.
+//   cursor     Spans obey begin <= end <= next begin, so several may begin at one position: step() codes the replacements of
+//              all spans that begin at the current position, in list order, before it says whether the symbol is coded.
+//   start      first - 1 in a span with a non-empty replacement: that replacement's last byte; in a deleted span r: sctx[r].
+//              splice_tback_kernel always runs (the host does not know which entries are empty): a lane works only for a
+//              deleted span over a chunk boundary and walks back through the touching spans in front of it while they are
+//              empty; a touching span with a non-empty replacement gives its last byte, else the splice's rule holds.
+//   price      price[2k], price[2k + 1]: the bits and drops of rep_k[1..] (splice_tprice_kernel, which also checks the table).
+//   tags       splice_tspans_kernel, in front of everything that reads the table: the span rule and tag < n_reps, else the
+//              stream fails alone and no lane reads its list.
+struct TCut {
+    const unsigned long long *off, *sp, *rep_off;
+    const uint32_t *tag;
+    const uint8_t *bytes;
+    const uint8_t *rep;                 // the replacement of the last fetch, its entry and length
+    uint32_t k, rep_len;
+    uint64_t r, rend, origin;
+    uint32_t b, e;                      // the span at r, as offsets from origin (saturated; ~0u: never)
+    bool own;                           // the span at r begins at or behind origin and its replacement is not coded yet
+    __device__ __forceinline__ explicit TCut(const SpliceTableParams &p)
+        : off(p.sp.span_off), sp(p.sp.spans), rep_off(p.tb.rep_off), tag(p.tb.span_tag), bytes(p.tb.rep_bytes), rep(nullptr), k(0u), rep_len(0u),
+          r(0), rend(0), origin(0), b(~0u), e(~0u), own(false) {}
+    __device__ __forceinline__ uint32_t rel(uint64_t x) const {
+        return x <= origin ? 0u : (x - origin >= 0xFFFFFFFFull ? ~0u : uint32_t(x - origin));
+    }
+    __device__ __forceinline__ void load() {
+        if (r < rend) { b = rel(sp[2 * r]); e = rel(sp[2 * r + 1]); own = sp[2 * r] >= origin; } else { b = e = ~0u; own = false; }
+    }
+    __device__ __forceinline__ void fetch(uint64_t q) {
+        k = tag[q];
+        const unsigned long long o = rep_off[k];
+        rep = bytes + o;
+        rep_len = uint32_t(rep_off[k + 1] - o);
+    }
+    // stream i from its first symbol: every span of the list, an insertion at 0 included
+    __device__ __forceinline__ void start(uint64_t i) {
+        origin = 0;
+        r = off[i];
+        rend = off[i + 1];
+        load();
+    }
+    // stream i from position first > 0: the first span that ends at or behind first (a span or an insertion in front of
+    // first - 1 is another lane's); true when that span holds first - 1
+    __device__ __forceinline__ bool seek(uint64_t i, uint64_t first) {
+        origin = first;
+        uint64_t lo = off[i], hi = off[i + 1];
+        rend = hi;
+        while (lo < hi) {
+            const uint64_t mid = (lo + hi) >> 1;
+            if (sp[2 * mid + 1] >= first) hi = mid; else lo = mid + 1;
+        }
+        r = lo;
+        load();
+        return r < rend && sp[2 * r] < first;
+    }
+    // the symbol at origin + pos, pos going up by one from the start: emit() runs once for every span that begins here (the
+    // replacement fetched); true when the symbol lies in no span and is coded
+    template <typename F> __device__ __forceinline__ bool step(uint32_t pos, F &&emit) {
+        for (;;) {
+            if (pos < b) return true;
+            if (own && pos == b) { fetch(r); emit(); own = false; }
+            if (pos < e) return false;
+            ++r;
+            load();
+        }
+    }
+};
+
+// The destination context as chunk c's lane starts; the cursor is left at the chunk's first symbol.
+__device__ __forceinline__ uint32_t splice_tstart(TCut &cu, const Chunk &c, const uint32_t *sctx) {
+    if (!c.first) { cu.start(c.i); return c.ctx; }
+    if (!cu.seek(c.i, c.first)) return c.ctx;
+    cu.fetch(cu.r);
+    return cu.rep_len ? cu.rep[cu.rep_len - 1u] : sctx[cu.r];
+}
+
+// the table: rep_off[0] == 0, no decreasing offsets, no entry over MH_SPLICE_MAX_REP bytes, else BATCH_STATUS_ARG and the call
+// stops; entry k's bits and drops behind its first byte into price[2k], price[2k + 1].  One workgroup per entry; an entry
+// is read only when it lies inside the table's rep_off[n_reps] bytes.
+__global__ __launch_bounds__(256) void splice_tprice_kernel(SpliceTableParams p, uint32_t *price, int *status, int *stop) {
+    __shared__ uint32_t acc[2];
+    const unsigned long long *ro = p.tb.rep_off;
+    const uint64_t nr = p.tb.n_reps;
+    if (blockIdx.x == 0 && threadIdx.x == 0 && ro[0] != 0) { fail(status, BATCH_STATUS_ARG); atomicExch(stop, 1); }
+    for (uint64_t k = blockIdx.x; k < nr; k += gridDim.x) {
+        const unsigned long long o0 = ro[k], o1 = ro[k + 1];
+        if (o1 < o0 || o1 - o0 > MH_SPLICE_MAX_REP || o1 > ro[nr]) {
+            if (threadIdx.x == 0) { fail(status, BATCH_STATUS_ARG); atomicExch(stop, 1); }
+            continue;
+        }
+        if (threadIdx.x < 2u) acc[threadIdx.x] = 0u;
+        __syncthreads();
+        const uint32_t j = threadIdx.x;
+        if (j >= 1u && j < uint32_t(o1 - o0)) {
+            const uint8_t *rep = p.tb.rep_bytes + o0;
+            const uint32_t l = p.dst.len8[((uint32_t(rep[j - 1u]) & p.dst.ctx_mask) << 8) | rep[j]];
+            atomicAdd(&acc[0], l);
+            if (!l) atomicAdd(&acc[1], 1u);
+        }
+        __syncthreads();
+        if (threadIdx.x < 2u) price[2 * k + threadIdx.x] = acc[threadIdx.x];
+        __syncthreads();
+    }
+}
+
+// recode_spans_kernel for this call's rule: span r of stream i with begin > end, beginning in front of the end of the span
+// before it, or with a tag that is no table entry: the stream's verdict is MH_ERR_ARG.  Spans and no table: the call stops.
+__global__ __launch_bounds__(256) void splice_tspans_kernel(SpliceTableParams p, int *status, int *stop) {
+    if (stopped(stop)) return;
+    const unsigned long long *off = p.sp.span_off, *sp = p.sp.spans;
+    const uint64_t n = p.s.b.n, total = off[n], stride = uint64_t(gridDim.x) * blockDim.x;
+    for (uint64_t i = gtid(); i <= n; i += stride)
+        if (mhb::offsets_bad(off, n, total, i)) { fail(status, BATCH_STATUS_ARG); atomicExch(stop, 1); }
+    if (!n) return;
+    if (total && !p.tb.n_reps) {
+        if (gtid() == 0) { fail(status, BATCH_STATUS_ARG); atomicExch(stop, 1); }
+        return;
+    }
+    for (uint64_t r = gtid(); r < total; r += stride) {
+        uint64_t lo = 0, hi = n - 1;                                  // the stream of span r: the last i < n with off[i] <= r
+        while (lo < hi) {
+            const uint64_t mid = (lo + hi + 1) >> 1;
+            if (off[mid] <= r) lo = mid; else hi = mid - 1;
+        }
+        const unsigned long long b = sp[2 * r], e = sp[2 * r + 1];
+        if (b > e || (r > off[lo] && sp[2 * r - 1] > b) || p.tb.span_tag[r] >= p.tb.n_reps)
+            stream_fail(p.s.b, status, lo, MH_ERR_ARG, BATCH_STATUS_ARG);
+    }
+}
+
+// splice_back_kernel for the table, always launched on an indexed batch: sctx[r] for every deleted span r over a chunk
+// boundary.  More spans than the workspace has room for: MHK_STATUS_CAPACITY and the call stops.
+template <Model K>
+__global__ __launch_bounds__((Dec<K, false>::NT)) void splice_tback_kernel(SpliceTableParams p, uint32_t *sctx, int *status, int *stop) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    if (stopped(stop)) return;
+    Dec<K, false> dec(p.s, smem);
+    const unsigned long long *off = p.sp.span_off, *sp = p.sp.spans, *ro = p.tb.rep_off;
+    const uint64_t n = p.s.b.n, total = off[n];
+    if (total > p.sp.span_cap) {
+        if (gtid() == 0) { fail(status, mhk::MHK_STATUS_CAPACITY); atomicExch(stop, 1); }
+        return;
+    }
+    if (!n) return;
+    const uint32_t cs = p.s.b.chunk_shift;
+    for (uint64_t r = gtid(); r < total; r += uint64_t(gridDim.x) * blockDim.x) {
+        sctx[r] = 0u;
+        if ((sp[2 * r + 1] >> cs) == (sp[2 * r] >> cs)) continue;     // no chunk starts in (begin, end]: no lane asks
+        uint64_t lo = 0, hi = n - 1;                                  // the stream of span r (recode_spans_kernel)
+        while (lo < hi) {
+            const uint64_t mid = (lo + hi + 1) >> 1;
+            if (off[mid] <= r) lo = mid; else hi = mid - 1;
+        }
+        const uint64_t i = lo;
+        if (p.s.b.stream_status[i] != MH_OK) continue;                // (a passed stream's tags are table entries)
+        const uint32_t k = p.tb.span_tag[r];
+        if (ro[k + 1] != ro[k]) continue;                             // replaced: its own last byte serves
+        const uint64_t a = p.s.b.sym_off[i], ni = p.s.b.sym_off[i + 1] - a;
+        if (sp[2 * r] >= ni) continue;                                // the span is ignored
+        uint64_t r0 = r;
+        uint32_t got = ~0u;
+        while (r0 > off[i] && sp[2 * r0 - 1] == sp[2 * r0]) {         // the touching span in front: through it while it is empty
+            const uint32_t kp = p.tb.span_tag[r0 - 1];
+            const unsigned long long o0 = ro[kp], o1 = ro[kp + 1];
+            if (o1 != o0) { got = p.tb.rep_bytes[o1 - 1u]; break; }
+            --r0;
+        }
+        if (got != ~0u) { sctx[r] = got; continue; }
+        const uint64_t begin = sp[2 * r0];
+        if (!begin) { sctx[r] = p.s.b.prev0; continue; }
+        const uint64_t wb = (a >> cs) + i, pos = begin - 1u;
+        if (!(begin & ((uint64_t(1) << cs) - 1u))) { sctx[r] = uint32_t(p.s.b.index[wb + (begin >> cs)] >> 56); continue; }
+        Chunk c;
+        if (!chunk_of<K, false>(p.s, wb + (pos >> cs), c) || !c.entry_ok()) continue;
+        uint64_t bit0;
+        const BitSrc src = mhb::stream_src(p.s.b.payload, p.s.b.pay_off[i], c.nb, bit0);
+        BitCursor bc;
+        bc.init(src, bit0 + c.start);
+        dec.stream(p.s, i);
+        uint32_t ctx = c.ctx, used = 0;
+        bool bad = false;
+        const uint32_t count = uint32_t(pos - c.first) + 1u;          // <= c.nsym: pos < ni
+        for (uint32_t t = 0; t < count && !bad; ++t) {
+            const uint32_t sym = dec.next(p.s, src, bc, ctx, used, bad);
+            if (bad) break;
+            ctx = sym;
+        }
+        sctx[r] = ctx;
+    }
+}
+
+template <Model K, bool DLDS>
+__global__ __launch_bounds__((Dec<K, false>::NT)) void splice_tidx_len_kernel(SpliceTableParams p, uint64_t nwork, uint32_t lds_at,
+                                                                            unsigned long long *cbits, unsigned long long *csyms, uint32_t *cdrop,
+                                                                            const uint32_t *sctx, const uint32_t *price, int *status,
+                                                                            const int *stop) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    if (stopped(stop)) return;
+    Dec<K, false> dec(p.s, smem);
+    const Enc<DLDS, false> E(p.dst, smem, lds_at);
+    TCut cu(p);
+    for (uint64_t w = gtid(); w < nwork; w += uint64_t(gridDim.x) * blockDim.x) {
+        Chunk c;
+        if (!chunk_of<K, false>(p.s, w, c) || p.s.b.stream_status[c.i] == MH_ERR_ARG) continue;
+        if (!c.entry_ok()) { stream_fail(p.s.b, status, c.i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT); continue; }
+        uint64_t bit0;
+        const BitSrc src = mhb::stream_src(p.s.b.payload, p.s.b.pay_off[c.i], c.nb, bit0);
+        BitCursor bc;
+        bc.init(src, bit0 + c.start);
+        dec.stream(p.s, c.i);
+        uint32_t ctx = c.ctx, used = 0, bits = 0, drops = 0, osym = 0;
+        uint32_t dctx = splice_tstart(cu, c, sctx);
+        bool bad = false;
+        for (uint32_t t = 0; t < c.nsym && !bad; ++t) {
+            const uint32_t sym = dec.next(p.s, src, bc, ctx, used, bad);
+            if (bad) break;
+            const bool coded = cu.step(t, [&] {
+                if (!cu.rep_len) return;
+                const uint32_t l = E.len(E.at(dctx, cu.rep[0]));     // rep[0] in dctx; the rest is priced
+                bits += l + price[2 * cu.k];
+                drops += (l == 0u) + price[2 * cu.k + 1u];
+                osym += cu.rep_len;
+                dctx = cu.rep[cu.rep_len - 1u];
+            });
+            if (coded) {
+                const uint32_t l = E.len(E.at(dctx, sym));
+                bits += l;
+                drops += l == 0u;
+                dctx = sym;
+                ++osym;
+            }
+            ctx = sym;
+        }
+        if (bad || used != c.end - c.start) { stream_fail(p.s.b, status, c.i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT); continue; }
+        cbits[w] = bits;
+        csyms[w] = osym;
+        cdrop[w] = drops;
+    }
+}
+
+template <Model K, bool DLDS>
+__global__ __launch_bounds__((Dec<K, false>::NT)) void splice_tidx_emit_kernel(SpliceTableParams p, uint64_t nwork, uint32_t lds_at,
+                                                                             const unsigned long long *cbase, const unsigned long long *obase,
+                                                                             const uint32_t *sctx, uint32_t *tail, const int *stop) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    if (stopped(stop)) return;
+    Dec<K, false> dec(p.s, smem);
+    const Enc<DLDS, false> E(p.dst, smem, lds_at);
+    TCut cu(p);
+    const uint64_t bytes = p.out_off[p.s.b.n];
+    const uint64_t tail_w = (bytes & 3u) ? bytes >> 2 : ~uint64_t(0);
+    const uint32_t cs = p.s.b.chunk_shift;
+    for (uint64_t w = gtid(); w < nwork; w += uint64_t(gridDim.x) * blockDim.x) {
+        Chunk c;
+        if (!chunk_of<K, false>(p.s, w, c) || p.s.b.stream_status[c.i] != MH_OK) continue;
+        if (obase[w + 1] == obase[w]) continue;                                   // a lane that produces nothing writes nothing
+        const uint64_t w0 = (p.s.b.sym_off[c.i] >> cs) + c.i;
+        SpliceOut so;
+        so.o = obase[w] - obase[w0];
+        so.bit = cbase[w] - cbase[w0];
+        so.ocs = cs;
+        so.on = p.out != nullptr;
+        so.slice = p.out_index ? p.out_index + (p.sp.out_sym_off[c.i] >> cs) + c.i : nullptr;
+        uint32_t dctx = splice_tstart(cu, c, sctx);
+        uint64_t bit0;
+        const BitSrc src = mhb::stream_src(p.s.b.payload, p.s.b.pay_off[c.i], c.nb, bit0);
+        BitCursor bc;
+        bc.init(src, bit0 + c.start);
+        dec.stream(p.s, c.i);
+        BitWriter bw;
+        if (so.on) bw.init(reinterpret_cast<uint32_t *>(p.out), tail, tail_w, uint64_t(p.out_off[c.i]) * 8u + so.bit);
+        uint32_t ctx = c.ctx, used = 0;
+        bool bad = false;
+        for (uint32_t t = 0; t < c.nsym && !bad; ++t) {            // (the stream passed: bad stays false)
+            const uint32_t sym = dec.next(p.s, src, bc, ctx, used, bad);
+            const bool coded = cu.step(t, [&] {
+                for (uint32_t j = 0; j < cu.rep_len; ++j) so.put<DLDS>(E, bw, dctx, cu.rep[j]);
+            });
+            if (coded) so.put<DLDS>(E, bw, dctx, sym);
+            ctx = sym;
+        }
+        if (so.on) bw.finish();
+    }
+}
+
+// Index-free, one lane per stream (splice_walk_kernel)
+template <Model K, bool DLDS, bool EMIT>
+__global__ __launch_bounds__((Dec<K, false>::NT)) void splice_twalk_kernel(SpliceTableParams p, uint32_t lds_at, uint32_t *tail, int *status,
+                                                                         const int *stop) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    if (stopped(stop)) return;
+    Dec<K, false> dec(p.s, smem);
+    const Enc<DLDS, false> E(p.dst, smem, lds_at);
+    TCut cu(p);
+    const uint64_t n = p.s.b.n;
+    const uint64_t bytes = EMIT ? p.out_off[n] : 0;
+    const uint64_t tail_w = (bytes & 3u) ? bytes >> 2 : ~uint64_t(0);
+    for (uint64_t i = gtid(); i < n; i += uint64_t(gridDim.x) * blockDim.x) {
+        if (p.s.b.stream_status[i] != MH_OK) continue;
+        const uint64_t nb = p.s.b.nbits[i];
+        uint64_t count = ~uint64_t(0);
+        if (EMIT) {
+            count = p.s.b.sym_off[i + 1] - p.s.b.sym_off[i];
+            if (p.sp.out_sym_off[i + 1] == p.sp.out_sym_off[i]) continue;
+        } else if (nb > p.s.b.walk_max_bits) {
+            stream_fail(p.s.b, status, i, MH_ERR_ARG, BATCH_STATUS_ARG);
+            continue;
+        }
+        uint64_t bit0;
+        const BitSrc src = mhb::stream_src(p.s.b.payload, p.s.b.pay_off[i], nb, bit0);
+        BitCursor bc;
+        bc.init(src, bit0);
+        dec.stream(p.s, i);
+        SpliceOut so;
+        so.o = 0; so.bit = 0; so.ocs = p.out_chunk_shift;
+        so.on = EMIT && p.out != nullptr;
+        so.slice = EMIT && p.out_index ? p.out_index + (p.sp.out_sym_off[i] >> so.ocs) + i : nullptr;
+        BitWriter bw;
+        if (so.on) bw.init(reinterpret_cast<uint32_t *>(p.out), tail, tail_w, uint64_t(p.out_off[i]) * 8u);
+        uint32_t ctx = start_ctx<K, false>(p.s), used = 0, drops = 0;
+        uint32_t dctx = ctx;
+        cu.start(i);
+        bool bad = false;
+        uint64_t k = 0;
+        auto one = [&](uint32_t s) {
+            if (EMIT) {
+                so.put<DLDS>(E, bw, dctx, s);
+            } else {
+                const uint32_t l = E.len(E.at(dctx, s));
+                so.bit += l; drops += l == 0u; dctx = s; ++so.o;
+            }
+        };
+        // every code has at least one bit: at most nb steps (src/coding.cpp:124 — decode while bits remain)
+        while (used < nb && !bad && k < count) {
+            const uint32_t sym = dec.next(p.s, src, bc, ctx, used, bad);
+            if (bad) break;
+            const bool coded = cu.step(uint32_t(k), [&] {
+                for (uint32_t j = 0; j < cu.rep_len; ++j) one(cu.rep[j]);
+            });
+            if (coded) one(sym);
+            ctx = sym;
+            ++k;
+        }
+        if (EMIT) { if (so.on) bw.finish(); continue; }
+        if (bad || used != nb) { stream_fail(p.s.b, status, i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT); continue; }
+        p.s.b.sym_off[i] = k;                                       // src/coding.cpp:158: the stream ends exactly at nbits
+        p.sp.out_sym_off[i] = so.o;
+        p.out_nbits[i] = so.bit;
+        if (p.dropped) p.dropped[i] = drops;
+    }
+}
+
+// span tags (mh_dev_spans_from_hits_tagged), behind spans_emit_kernel: num[r] is record r's span number when it starts a
+// span, one more than it otherwise.  First the starting record's pattern by a plain store, then the minimum with the others'.
+template <bool MIN>
+__global__ __launch_bounds__(256) void spans_tag_kernel(SpanParams p, const uint32_t *pattern, uint32_t *span_tag, const int *stop) {
+    if (stopped(stop)) return;
+    const uint64_t r = gtid();
+    if (r >= p.hit_off[p.n]) return;
+    const unsigned long long id = p.num[r];
+    const bool start = p.num[r + 1] != id;
+    if (!MIN) { if (start) span_tag[id] = pattern[r]; }
+    else if (!start) atomicMin(&span_tag[id - 1], pattern[r]);
+}
+
 // ------------------------------------------------------------------------------------------------ launches
 
 template <Model K, bool W>
@@ -1386,7 +1760,83 @@ hipError_t launch_sp(SpliceParams p, size_t lds_tables, void *d_ws, size_t ws_by
     return hipGetLastError();
 }
 
+// the table splice: launch_sp with the table's kernels; no LDS beyond the tables and the destination's image.  The look-back
+// pre-pass runs on every indexed call, so the launches depend on indexed versus index-free alone.
+template <Model K, bool DLDS>
+hipError_t launch_spt(const SpliceTableParams &p0, size_t lds_tables, void *d_ws, size_t ws_bytes, hipStream_t st) {
+    constexpr int NT = Dec<K, false>::NT, PER_CU = Dec<K, false>::PER_CU;
+    SpliceTableParams p = p0;
+    const SpliceParams &ps = p;
+    const size_t lds = lds_tables + (DLDS ? (p.dst.ctx_mask ? 65536 : 256) : 0);
+    const uint32_t lds_at = uint32_t(lds_tables);
+    if (K == Model::Shared) {
+        hipError_t attr = mhk::allow_lds(reinterpret_cast<const void *>(splice_tidx_len_kernel<K, DLDS>), LDS_MAX);
+        if (attr == hipSuccess) attr = mhk::allow_lds(reinterpret_cast<const void *>(splice_tidx_emit_kernel<K, DLDS>), LDS_MAX);
+        if (attr == hipSuccess) attr = mhk::allow_lds(reinterpret_cast<const void *>(splice_twalk_kernel<K, DLDS, false>), LDS_MAX);
+        if (attr == hipSuccess) attr = mhk::allow_lds(reinterpret_cast<const void *>(splice_twalk_kernel<K, DLDS, true>), LDS_MAX);
+        if (attr == hipSuccess) attr = mhk::allow_lds(reinterpret_cast<const void *>(splice_tback_kernel<K>), LDS_MAX);
+        if (attr != hipSuccess) return attr;
+    }
+    unsigned char *ws = static_cast<unsigned char *>(d_ws);
+    const uint64_t n = p.s.b.n;
+    const uint64_t nw = p.s.b.index ? mhb::work_items(n, p.s.b.sym_total, 1u << p.s.b.chunk_shift) : 0;
+    const SpliceLayout L = splice_table_layout(n, nw, 0, p.tb.n_reps);
+    p.sp.span_cap = (ws_bytes - L.off_sctx) / 4;
+    int *status = reinterpret_cast<int *>(ws), *stop = status + 1;
+    uint32_t *tail = reinterpret_cast<uint32_t *>(ws + TAIL_AT);
+    auto *cbits = reinterpret_cast<unsigned long long *>(ws + L.off_bits);
+    auto *csyms = reinterpret_cast<unsigned long long *>(ws + L.off_syms);
+    auto *cdrop = reinterpret_cast<uint32_t *>(ws + L.off_drop);
+    auto *price = reinterpret_cast<uint32_t *>(ws + L.off_price);
+    auto *sums = reinterpret_cast<unsigned long long *>(ws + L.off_sums);
+    auto *sctx = reinterpret_cast<uint32_t *>(ws + L.off_sctx);
+    hipError_t e = hipMemsetAsync(ws, 0, 64, st);
+    if (e == hipSuccess && nw) e = hipMemsetAsync(ws + L.off_bits, 0, L.off_price - L.off_bits, st);   // chunk bits, output symbols, dropped counts
+    if (e != hipSuccess) return e;
+    const uint64_t nr = p.tb.n_reps;
+    hipLaunchKernelGGL(splice_check_kernel, grid_threads(n + 1, 256), dim3(256), 0, st, ps, status, stop);
+    hipLaunchKernelGGL(splice_tprice_kernel, dim3(uint32_t(nr < 1 ? 1 : (nr > 65536 ? 65536 : nr))), dim3(256), 0, st, p, price, status, stop);
+    hipLaunchKernelGGL(splice_tspans_kernel, dim3(grid_for(uint64_t(1) << 40, 256, 8)), dim3(256), 0, st, p, status, stop);
+    if (p.s.b.index) {
+        hipLaunchKernelGGL((splice_tback_kernel<K>), dim3(grid_for(uint64_t(1) << 40, NT, PER_CU)), dim3(NT), lds_tables, st, p, sctx, status, stop);
+        hipLaunchKernelGGL((splice_tidx_len_kernel<K, DLDS>), dim3(grid_for(nw, NT, PER_CU)), dim3(NT), lds, st, p, nw, lds_at, cbits, csyms, cdrop,
+                           sctx, price, status, stop);
+        hipLaunchKernelGGL(splice_comb_kernel, grid_threads(nw + 1, 256), dim3(256), 0, st, ps, nw, cbits, csyms, cdrop, stop);
+        if ((e = scan_exclusive(cbits, nw + 1, sums, stop, st)) != hipSuccess) return e;
+        if ((e = scan_exclusive(csyms, nw + 1, sums, stop, st)) != hipSuccess) return e;
+    } else {
+        hipLaunchKernelGGL((splice_twalk_kernel<K, DLDS, false>), dim3(grid_for(n + 1, NT, PER_CU)), dim3(NT), lds, st, p, lds_at, tail, status, stop);
+        if ((e = scan_exclusive(p.s.b.sym_off, n + 1, sums, stop, st)) != hipSuccess) return e;
+        if ((e = scan_exclusive(p.sp.out_sym_off, n + 1, sums, stop, st)) != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(splice_sizes_kernel, grid_threads(n + 1, 256), dim3(256), 0, st, ps, cbits, csyms, stop);
+    if ((e = scan_exclusive(p.out_off, n + 1, sums, stop, st)) != hipSuccess) return e;
+    if (p.out_index) hipLaunchKernelGGL(splice_cap_kernel, dim3(1), dim3(1), 0, st, ps, status, stop);
+    if (p.out) hipLaunchKernelGGL(recode_zero_kernel, dim3(grid_for(p.cap / 4 + 1, 256, 8)), dim3(256), 0, st, ps, status, stop, tail);
+    if (p.s.b.index) {
+        if (p.out || p.out_index)
+            hipLaunchKernelGGL((splice_tidx_emit_kernel<K, DLDS>), dim3(grid_for(nw, NT, PER_CU)), dim3(NT), lds, st, p, nw, lds_at, cbits, csyms,
+                               sctx, tail, stop);
+    } else if (p.out || p.out_index) {
+        hipLaunchKernelGGL((splice_twalk_kernel<K, DLDS, true>), dim3(grid_for(n + 1, NT, PER_CU)), dim3(NT), lds, st, p, lds_at, tail, status, stop);
+    }
+    if (p.out) hipLaunchKernelGGL(recode_tail_kernel, dim3(1), dim3(1), 0, st, ps, tail, stop);
+    return hipGetLastError();
+}
+
 }  // namespace
+
+// the branches of launch_recode_splice, each with the table
+hipError_t launch_recode_splice_table(const SpliceTableParams &p, Model model, void *d_ws, size_t ws_bytes, hipStream_t st) {
+    if (model == Model::Shared2 || p.dst.ctx_mask == 0xFFFFu) return hipErrorInvalidValue;
+    if (model == Model::Set)
+        return p.dst.ctx_mask ? launch_spt<Model::Set, false>(p, 0, d_ws, ws_bytes, st) : launch_spt<Model::Set, true>(p, 0, d_ws, ws_bytes, st);
+    const size_t lds = mhb::tables_lds(p.s.b);
+    if (lds > size_t(LDS_MAX)) return hipErrorInvalidValue;
+    const size_t img = p.dst.ctx_mask ? 65536 : 256;
+    return lds + img <= size_t(LDS_MAX) ? launch_spt<Model::Shared, true>(p, lds, d_ws, ws_bytes, st)
+                                        : launch_spt<Model::Shared, false>(p, lds, d_ws, ws_bytes, st);
+}
 
 // the branches of launch_recode_edit, each with the splice in place of the edit
 hipError_t launch_recode_splice(const SpliceParams &p, Model model, void *d_ws, size_t ws_bytes, hipStream_t st) {
@@ -1452,6 +1902,22 @@ hipError_t launch_spans_from_hits(const unsigned long long *hit_off, const unsig
     hipLaunchKernelGGL(spans_mark_kernel, grid_threads(hit_cap + 2, 256), dim3(256), 0, st, p, stop);
     if ((e = scan_exclusive(p.num, hit_cap + 2, sums, stop, st)) != hipSuccess) return e;
     hipLaunchKernelGGL(spans_emit_kernel, grid_threads((hit_cap > n_streams ? hit_cap : n_streams) + 1, 256), dim3(256), 0, st, p, stop);
+    return hipGetLastError();
+}
+
+// the untagged launches, then two more over the records (the numbers stay in the workspace)
+hipError_t launch_spans_from_hits_tagged(const unsigned long long *hit_off, const unsigned long long *hits, const uint32_t *hit_pattern,
+                                         uint64_t hit_cap, uint64_t n_streams, unsigned long long *span_off, unsigned long long *spans,
+                                         uint32_t *span_tag, void *d_ws, hipStream_t st) {
+    const hipError_t e = launch_spans_from_hits(hit_off, hits, hit_cap, n_streams, span_off, spans, d_ws, st);
+    if (e != hipSuccess || !hit_cap) return e;
+    unsigned char *ws = static_cast<unsigned char *>(d_ws);
+    const SpanLayout L = span_layout(hit_cap);
+    int *stop = reinterpret_cast<int *>(ws) + 1;
+    SpanParams p{hit_off, hits, hit_cap, n_streams, span_off, spans, reinterpret_cast<unsigned long long *>(ws + L.off_min),
+                 reinterpret_cast<unsigned long long *>(ws + L.off_num), reinterpret_cast<unsigned long long *>(ws + L.off_tile)};
+    hipLaunchKernelGGL(spans_tag_kernel<false>, grid_threads(hit_cap, 256), dim3(256), 0, st, p, hit_pattern, span_tag, stop);
+    hipLaunchKernelGGL(spans_tag_kernel<true>, grid_threads(hit_cap, 256), dim3(256), 0, st, p, hit_pattern, span_tag, stop);
     return hipGetLastError();
 }
 

@@ -510,7 +510,8 @@ void i_coding_provider::crc(FILE* input_fd) {
 // The spans of a --redact: the hits of the patterns in the one stream (mh_find_batch / mh_find_dict_batch, index-free when
 // there is no index), uploaded as they came and merged on the device; spans = (begin, end) pairs.
 static void redact_spans(const mh_model* model, const redact_options& r, const uint8_t* payload, uint64_t pay_bytes, uint64_t nbits,
-                         const uint64_t* sym_off, const uint64_t* index, uint32_t chunk, uint64_t span_off[2], std::vector<uint64_t>& spans) {
+                         const uint64_t* sym_off, const uint64_t* index, uint32_t chunk, uint64_t span_off[2], std::vector<uint64_t>& spans,
+                         std::vector<uint32_t>* tags = nullptr) {
     std::string bytes;
     std::vector<uint32_t> pat_off(1, 0);
     for (const std::string& p : r.patterns) {
@@ -523,18 +524,44 @@ static void redact_spans(const mh_model* model, const redact_options& r, const u
     if (r.dict) mh_or_die(mh_dict_create((const uint8_t*)bytes.data(), pat_off.data(), r.patterns.size(), flags, &dc), "--redact-file");
     else mh_or_die(mh_pattern_set_create((const uint8_t*)bytes.data(), pat_off.data(), r.patterns.size(), flags, &ps), "--redact");
     const uint64_t pay_off[2] = {0, pay_bytes};
-    auto search = [&](uint64_t* hit_off, uint64_t* hits, uint64_t cap) {
-        return r.dict ? mh_find_dict_batch(model, dc, payload, pay_off, &nbits, 1, MH_PREV0, sym_off, index, chunk, hit_off, hits, nullptr, cap, nullptr)
-                      : mh_find_batch(model, ps, payload, pay_off, &nbits, 1, MH_PREV0, sym_off, index, chunk, hit_off, hits, nullptr, cap, nullptr);
+    auto search = [&](uint64_t* hit_off, uint64_t* hits, uint32_t* pat, uint64_t cap) {
+        return r.dict ? mh_find_dict_batch(model, dc, payload, pay_off, &nbits, 1, MH_PREV0, sym_off, index, chunk, hit_off, hits, pat, cap, nullptr)
+                      : mh_find_batch(model, ps, payload, pay_off, &nbits, 1, MH_PREV0, sym_off, index, chunk, hit_off, hits, pat, cap, nullptr);
     };
     uint64_t hit_off[2] = {0, 0};
-    mh_or_die(search(hit_off, nullptr, 0), "redact (search)");
+    mh_or_die(search(hit_off, nullptr, nullptr, 0), "redact (search)");
     const uint64_t total = hit_off[1];
     span_off[0] = span_off[1] = 0;
     spans.clear();
-    if (total) {
+    if (tags) tags->clear();
+    if (total && tags) {                                          // --replace-file: the tagged merge, which keeps the pattern numbers
         std::vector<uint64_t> hits((size_t)total * 3);
-        mh_or_die(search(hit_off, hits.data(), total), "redact (search)");
+        std::vector<uint32_t> pat((size_t)total);
+        mh_or_die(search(hit_off, hits.data(), pat.data(), total), "redact (search)");
+        void *d_ho = nullptr, *d_h = nullptr, *d_p = nullptr, *d_so = nullptr, *d_sp = nullptr, *d_tg = nullptr, *d_ws = nullptr;
+        const size_t wsb = mh_dev_spans_from_hits_tagged_workspace(1, total);
+        mh_or_die(mh_dev_malloc(&d_ho, 16), "redact");
+        mh_or_die(mh_dev_malloc(&d_h, hits.size() * 8), "redact");
+        mh_or_die(mh_dev_malloc(&d_p, pat.size() * 4), "redact");
+        mh_or_die(mh_dev_malloc(&d_so, 16), "redact");
+        mh_or_die(mh_dev_malloc(&d_sp, (size_t)total * 16), "redact");
+        mh_or_die(mh_dev_malloc(&d_tg, (size_t)total * 4), "redact");
+        mh_or_die(mh_dev_malloc(&d_ws, wsb), "redact");
+        mh_or_die(mh_dev_upload(d_ho, hit_off, 16), "redact");
+        mh_or_die(mh_dev_upload(d_h, hits.data(), hits.size() * 8), "redact");
+        mh_or_die(mh_dev_upload(d_p, pat.data(), pat.size() * 4), "redact");
+        mh_or_die(mh_dev_spans_from_hits_tagged((const uint64_t*)d_ho, (const uint64_t*)d_h, (const uint32_t*)d_p, total, 1, (uint64_t*)d_so,
+                                                (uint64_t*)d_sp, (uint32_t*)d_tg, d_ws, wsb, nullptr), "redact (spans)");
+        mh_or_die(mh_dev_status(d_ws, nullptr), "redact (spans)");
+        mh_or_die(mh_dev_download(span_off, d_so, 16), "redact");
+        spans.resize((size_t)span_off[1] * 2);
+        tags->resize((size_t)span_off[1]);
+        if (!spans.empty()) mh_or_die(mh_dev_download(spans.data(), d_sp, spans.size() * 8), "redact");
+        if (!tags->empty()) mh_or_die(mh_dev_download(tags->data(), d_tg, tags->size() * 4), "redact");
+        for (void* d : {d_ho, d_h, d_p, d_so, d_sp, d_tg, d_ws}) mh_dev_free(d);
+    } else if (total) {
+        std::vector<uint64_t> hits((size_t)total * 3);
+        mh_or_die(search(hit_off, hits.data(), nullptr, total), "redact (search)");
         void *d_ho = nullptr, *d_h = nullptr, *d_so = nullptr, *d_sp = nullptr, *d_ws = nullptr;
         const size_t wsb = mh_dev_spans_from_hits_workspace(1, total);
         mh_or_die(mh_dev_malloc(&d_ho, 16), "redact");
@@ -584,18 +611,43 @@ void i_coding_provider::recode(FILE* input_fd, FILE* output_fd, const i_coding_p
     // nbits / shortest source code of them) and cut to the true size afterwards: one upload, one device call
     const int minl = mh_model_min_code_len(model_);
     uint64_t symbols = indexed ? n_symbols : nbits / (uint64_t)(minl > 0 ? minl : 1);
+    const bool table = redact && redact->table;
+    std::vector<uint32_t> tags;
     if (redact)
         redact_spans(model_, *redact, in.data + 1, pay_off[1], nbits, indexed ? sym_off : nullptr, indexed ? index.data() : nullptr, chunk, span_off,
-                     spans);
+                     spans, table ? &tags : nullptr);
     const bool splice = redact && redact->replace;
-    if (splice) {                                                 // every span grows the message by at most the replacement
+    uint64_t inserted = 0;
+    if (table) {
+        for (uint32_t t : tags) inserted += redact->reps[t].size();
+        symbols += inserted;
+        if (indexed) out_index.assign((size_t)mh_batch_index_capacity(symbols, 1, chunk), 0);
+    } else if (splice) {                                          // every span grows the message by at most the replacement
         symbols += span_off[1] * redact->rep.size();
         if (indexed) out_index.assign((size_t)mh_batch_index_capacity(symbols, 1, chunk), 0);
     }
     const size_t bound = mh_encode_batch_bound(dst.model(), (size_t)symbols, 1);
     OutputView out;
     out.open(output_fd, bound + 1);
-    if (splice) {
+    if (table) {
+        uint64_t removed = 0, out_sym_off[2] = {0, 0};
+        for (size_t k = 0; k < spans.size(); k += 2) removed += spans[k + 1] - spans[k];
+        eprintf("Replacing %llu bytes in %llu spans with %llu bytes.\n", (unsigned long long)removed, (unsigned long long)span_off[1],
+                (unsigned long long)inserted);
+        std::vector<uint64_t> rep_off(1, 0);
+        std::string rep_bytes;
+        for (const std::string& s : redact->reps) {
+            rep_bytes += s;
+            rep_off.push_back(rep_bytes.size());
+        }
+        tags.push_back(0);                                        // (never read: a pointer for an empty list)
+        mh_or_die(mh_recode_splice_table_batch(model_, dst.model(), in.data + 1, pay_off, &nbits, 1, MH_PREV0, sym_off,
+                                               indexed ? index.data() : nullptr, chunk, span_off, spans.data(), tags.data(), rep_off.data(),
+                                               (const uint8_t*)rep_bytes.data(), redact->reps.size(), out.data + 1, bound, out_off, &out_nbits,
+                                               out_sym_off, indexed ? out_index.data() : nullptr, out_index.size(), &dropped, nullptr),
+                  "recode (--replace-file)");
+        n_symbols = out_sym_off[1];                               // the index sidecar below is the new length's
+    } else if (splice) {
         uint64_t removed = 0, out_sym_off[2] = {0, 0};
         for (size_t k = 0; k < spans.size(); k += 2) removed += spans[k + 1] - spans[k];
         eprintf("Replacing %llu bytes in %llu spans with %llu bytes.\n", (unsigned long long)removed, (unsigned long long)span_off[1],

@@ -51,6 +51,8 @@ struct redact_options {
     uint8_t mask = 0x2A;
     bool replace = false;                        // --replace: a span becomes rep (any length up to MH_SPLICE_MAX_REP, "" deletes)
     std::string rep;
+    bool table = false;                          // --replace-file: a span becomes reps[its tag], the lowest pattern number merged into it
+    std::vector<std::string> reps;               // one per pattern ("" deletes)
 };
 
 class i_coding_provider {

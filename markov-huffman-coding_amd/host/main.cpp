@@ -23,6 +23,9 @@
 //                    table may be the old one.  --redact-file FILE: one pattern per line, the limits of --find-file.
 //   --replace STRING with --redact or --redact-file: the occurrences are replaced by STRING (at most 255 bytes; "" deletes
 //                    them) instead of being masked, so the output has another length; <output>.idx is written for it
+//   --replace-file FILE with --redact-file, not with --replace or --mask: line j of FILE replaces pattern j (split at LF, empty
+//                    lines kept: an empty line deletes; a final LF adds no line; as many lines as patterns, at most 255 bytes
+//                    each).  Overlapping or touching hits become one span, replaced by the line of its lowest pattern number
 //   --crc            with -x: print `crc32 length` of the original input (CRC-32 as zlib computes it, %08x, and the byte
 //                    count), taken on the device without decompressing; with --index the indexed path
 #include <errno.h>
@@ -65,6 +68,8 @@ static void print_help() {
     eprintf("\t--redact-file f  the same with one pattern per line of `f`, as --find-file; not together with --redact\n");
     eprintf("\t--mask byte    the byte that takes the place of redacted bytes: decimal or 0x.., 0 to 255 (default 0x2A)\n");
     eprintf("\t--replace string  with --redact or --redact-file: every occurrence becomes the string (at most 255 bytes, \"\" deletes)\n");
+    eprintf("\t--replace-file f  with --redact-file: line j of `f` replaces pattern j (an empty line deletes; where patterns overlap the\n");
+    eprintf("\t               earlier line of the pattern file wins); not together with --replace or --mask\n");
     eprintf("\t               instead of mask bytes; not together with --mask\n");
 }
 
@@ -91,6 +96,8 @@ struct options {
     int mask = 0x2A;                                              // --mask: what a redacted byte becomes
     bool replace_given = false;
     std::string replace;                                          // --replace: what a redacted span becomes ("" deletes it)
+    const char* replace_file = nullptr;                           // --replace-file: line j replaces pattern j of --redact-file
+    std::vector<std::string> replacements;                        // its lines, empty ones kept
 };
 
 // "B:E" with decimal B <= E; anything else is an error
@@ -171,6 +178,7 @@ static options parse(int argc, char* argv[]) {
                 o.replace = need(a);
                 o.replace_given = true;
             }
+            else if (!strcmp(a, "--replace-file")) o.replace_file = need(a);
             else eprintf("Warning: Unknown option %s.\n", a);
             continue;
         }
@@ -230,6 +238,24 @@ static void load_patterns(const char* path, const char* flag, std::vector<std::s
         eprintf("Error: the %s %s holds no pattern.\n", flag, path);
         exit(1);
     }
+}
+
+// the replacements of --replace-file: the lines of the file, split at LF, empty lines kept (an empty line deletes); a final
+// LF adds no line
+static void load_replacements(const char* path, std::vector<std::string>& out) {
+    FILE* f = fopen(path, "rb");
+    if (!f) {
+        eprintf("Error: cannot open the --replace-file %s.\n", path);
+        exit(1);
+    }
+    std::string line;
+    bool open_line = false;                                       // bytes, or nothing yet, behind the last LF
+    for (int c; (c = fgetc(f)) != EOF;) {
+        if (c == '\n') { out.push_back(line); line.clear(); open_line = false; }
+        else { line.push_back((char)c); open_line = true; }
+    }
+    if (open_line) out.push_back(line);
+    fclose(f);
 }
 
 // the limits of the --find / --redact strings (Shift-And) or of a --find-file / --redact-file (the dictionary)
@@ -331,6 +357,16 @@ int main(int argc, char* argv[]) {
             exit(1);
         }
     }
+    if (o.replace_file) {
+        if (!o.redact_file) {
+            eprintf("Error: --replace-file needs --redact-file.\n");
+            exit(1);
+        }
+        if (o.replace_given || o.mask_given) {
+            eprintf("Error: --replace-file cannot be combined with --replace or --mask.\n");
+            exit(1);
+        }
+    }
     if (redact) {                                                  // the rules first, then the pattern file, then everything else
         if (!o.recode_table) {
             eprintf("Error: --redact needs --recode.\n");
@@ -347,6 +383,18 @@ int main(int argc, char* argv[]) {
             }
         if (o.redact_file) load_patterns(o.redact_file, "--redact-file", o.redacts);
         check_patterns(o.redacts, o.redact_file != nullptr, "--redact", "--redact-file");
+        if (o.replace_file) {
+            load_replacements(o.replace_file, o.replacements);
+            if (o.replacements.size() != o.redacts.size()) {
+                eprintf("Error: the --replace-file %s holds %zu lines for %zu patterns.\n", o.replace_file, o.replacements.size(), o.redacts.size());
+                exit(1);
+            }
+            for (const std::string& r : o.replacements)
+                if (r.size() > MH_SPLICE_MAX_REP) {
+                    eprintf("Error: a line of the --replace-file takes at most %u bytes.\n", MH_SPLICE_MAX_REP);
+                    exit(1);
+                }
+        }
     } else if (o.mask_given || o.redact_fold) {
         eprintf("Error: --mask and --redact-fold need --redact or --redact-file.\n");
         exit(1);
@@ -492,6 +540,8 @@ int main(int argc, char* argv[]) {
         ro.mask = (uint8_t)o.mask;
         ro.replace = o.replace_given;
         ro.rep = o.replace;
+        ro.table = o.replace_file != nullptr;
+        ro.reps = o.replacements;
         coder->recode(input_fd, output_fd, *dst, std::string(o.output) + ".idx", redact ? &ro : nullptr);
         delete dst;
         delete coder;
