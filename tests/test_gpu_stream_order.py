@@ -59,6 +59,7 @@ EXEMPT = {
     "mh_dev_model_set_train": "synchronises `stream` twice: once to size the set (its live-context count), once at the end for the status.",
     "mh_dev_model_set_pick": "Allocates the view and synchronises `stream` once",
     "mh_dev_bank_train": "Allocates the bank and synchronises `stream` a number of times that depends on K and the iterations, not on n.",
+    "mh_dev_batch_states_stats": "mh_dev_batch_states_stats (read-only, any order; synchronises the stream) says how the last states call in d_ws settled",
 }
 
 
@@ -66,13 +67,47 @@ def test_the_exempt_list_quotes_the_header_and_is_run():
     import inspect
     import os
     import re
+    import test_gpu_stream_order_edit as more                     # (the second module of these tests; it imports this one)
     with open(os.path.join(entry.ROOT, "include", "mh.h")) as f:
         header = re.sub(r"\s+", " ", re.sub(r"\n\s*\*", " ", f.read()))
-    run = inspect.getsource(test_exempt_calls_on_the_stream) + inspect.getsource(test_chain_d_one_stream)
+    run = inspect.getsource(test_exempt_calls_on_the_stream) + inspect.getsource(test_chain_d_one_stream) + \
+        inspect.getsource(more.test_exempt_states_stats_on_the_stream)
     for call, sentence in EXEMPT.items():
         assert re.sub(r"\s+", " ", sentence) in header, "%s: not a sentence of include/mh.h: %s" % (call, sentence)
         assert header.count(call + "("), call
         assert "lib.%s(" % call in run, "%s is listed and never run on the stream" % call
+
+
+STREAM_CALLS = 82                  # the declarations of include/mh.h that take `void *stream`, as stream_taking_calls() finds them
+UNDRIVEN = {}                      # call -> why it cannot be driven on the stream; three entries at the most, each named in the pull request
+
+
+def stream_taking_calls(header):
+    """The names of the mh_dev_* declarations of a header whose argument list holds `void *stream`, comments stripped."""
+    import re
+    text = re.sub(r"//[^\n]*", " ", re.sub(r"/\*.*?\*/", " ", header, flags=re.S))
+    return [m.group(1) for m in re.finditer(r"\b(mh_dev_\w+)\s*\(([^()]*)\)\s*;", text) if re.search(r"\bvoid\s*\*\s*stream\b", m.group(2))]
+
+
+def test_every_stream_taking_call_is_driven_on_the_stream():
+    """Every mh_dev_* call of include/mh.h that takes a stream appears as `lib.NAME` in the source of the stream-order modules
+    (tests/test_gpu_stream_order*.py), in a chain or in an exempt test: a new call in the header fails this until a chain drives
+    it.  `lib.NAME` followed by `(` or, where a chain hands the function to Chain.call or to an add_* helper, by `,` or `)`:
+    never a longer name (`lib.NAME_workspace`).  The count is pinned so that a parser that finds nothing cannot pass."""
+    import glob
+    import os
+    import re
+    with open(os.path.join(entry.ROOT, "include", "mh.h")) as f:
+        calls = stream_taking_calls(f.read())
+    assert len(calls) == len(set(calls)) == STREAM_CALLS, "include/mh.h declares %d stream-taking device calls, this test pins %d" % (len(calls), STREAM_CALLS)
+    source = ""
+    for path in sorted(glob.glob(os.path.join(os.path.dirname(os.path.abspath(__file__)), "test_gpu_stream_order*.py"))):
+        with open(path) as f:
+            source += f.read()
+    assert len(UNDRIVEN) <= 3 and set(UNDRIVEN) <= set(calls)
+    missing = [c for c in calls if c not in UNDRIVEN and not re.search(r"\blib\.%s\b(?!\w)" % c, source)]
+    assert not missing, "stream-taking calls of include/mh.h that no stream-order chain drives: %s" % ", ".join(missing)
+    assert set(EXEMPT) <= set(calls), "an exempt call takes a stream"
 
 
 class Env:
