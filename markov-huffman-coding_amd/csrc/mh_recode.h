@@ -99,14 +99,14 @@ struct EditParams : RecodeParams {
 
 // the splice of a splicing re-code (include/mh.h, "SPLICING BATCHES"): every span of stream i that begins inside the decoded
 // message is replaced by the rep_len bytes of rep (0: deleted), so the output has its own lengths, out_sym_off, and its index
-// is laid out by output positions
+// is laid out by output positions.  One kernel family serves this call and the table's (mh_recode.hip, TABLE): rep and rep_len
+// are read by the single-replacement call alone (!TABLE), every other field by both
 struct Splice {
     const unsigned long long *span_off;   // n + 1
     const unsigned long long *spans;
-    const uint8_t *rep;                   // rep_len bytes (may be nullptr when 0)
-    uint32_t rep_len;                     // 0 .. MH_SPLICE_MAX_REP
-    uint32_t rep_lds;                     // set by the launcher: rep has the map's 256 bytes of LDS behind the tables
-    uint64_t span_cap;                    // set by the launcher: the spans the workspace has room for (rep_len == 0)
+    const uint8_t *rep;                   // !TABLE: rep_len bytes (may be nullptr when 0)
+    uint32_t rep_len;                     // !TABLE: 0 .. MH_SPLICE_MAX_REP
+    uint64_t span_cap;                    // set by the launcher: the spans the workspace has room for (!TABLE: used when rep_len == 0)
     unsigned long long *out_sym_off;      // n + 1 (written): the exclusive scan of the output lengths
     uint64_t index_cap;                   // entries of out_index
 };
@@ -137,7 +137,8 @@ inline SpliceLayout splice_layout(uint64_t n_streams, uint64_t nwork, uint64_t n
 }
 
 // the table of a table splice (include/mh.h, "SPLICING WITH A REPLACEMENT TABLE"): span r is replaced by entry span_tag[r],
-// the bytes rep_bytes[rep_off[k] .. rep_off[k + 1]); sp.rep / sp.rep_len / sp.rep_lds are unused
+// the bytes rep_bytes[rep_off[k] .. rep_off[k + 1]).  Read under TABLE alone, where sp.rep / sp.rep_len are unused; the
+// single-replacement kernels take SpliceParams and carry none of this in their argument block
 struct SpliceTable {
     const uint32_t *span_tag;             // one per span
     const unsigned long long *rep_off;    // n_reps + 1

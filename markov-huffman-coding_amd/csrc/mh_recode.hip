@@ -16,12 +16,12 @@
 //   recode_spans_kernel      (EDIT, include/mh.h "EDITING BATCHES") the span lists, in front of the length pass: a stream whose
 //                            list is not ascending and disjoint is MH_ERR_ARG
 //   spans_*_kernel           search records merged into spans (mh_dev_spans_from_hits): see "span lists" below
-//   splice_*_kernel          (include/mh.h "SPLICING BATCHES") spans deleted or replaced by a string of another length: the
-//                            same stages with a second scan for output positions and an index laid out by them; see
-//                            "the splice" below
-//   splice_t*_kernel         (include/mh.h "SPLICING WITH A REPLACEMENT TABLE") the splice with a replacement per span, chosen by the
-//                            span's tag from a table, and insertions: siblings of splice_*_kernel; see "the table splice" below
-//   spans_tag_kernel         (mh_dev_spans_from_hits_tagged) the lowest pattern number of each merged span
+//   splice_*_kernel          (include/mh.h "SPLICING BATCHES" and "SPLICING WITH A REPLACEMENT TABLE") spans deleted or replaced
+//                            by a string of another length: the same stages with a second scan for output positions and an
+//                            index laid out by them.  One family, <TABLE>: one replacement for the call, or one per span, chosen
+//                            by the span's tag from a table, and insertions; see "the splice" below
+//   splice_spans_kernel      recode_spans_kernel for the table's rule: begin <= end, tag < n_reps
+//   spans_tag_kernel        (mh_dev_spans_from_hits_tagged) the lowest pattern number of each merged span
 //   histc_idx_kernel        one lane per (stream, chunk): counts the pairs as it decodes; a chunk that fails takes its own
 //                            counts back; <FIX>: the chunks that passed inside a stream that failed take theirs back
 //   histc_walk_kernel        index-free, one lane per stream: counts, and takes the stream's counts back when it fails
@@ -329,6 +329,16 @@ __global__ void recode_tail_kernel(RecodeIO p, const uint32_t *tail, const int *
 
 // ------------------------------------------------------------------------------------------------ span lists
 
+// the stream of span r: the last i < n with off[i] <= r (n > 0)
+__device__ __forceinline__ uint64_t span_stream(const unsigned long long *off, uint64_t n, uint64_t r) {
+    uint64_t lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const uint64_t mid = (lo + hi + 1) >> 1;
+        if (off[mid] <= r) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
 // The span lists of an edit, in front of the length pass: span_off as any offsets (else BATCH_STATUS_ARG and the call stops);
 // span r of stream i must have begin < end and must not begin in front of the end of the stream's span before it, else the
 // stream's verdict is MH_ERR_ARG and no lane reads its list.  One grid-stride pass over the spans.
@@ -340,13 +350,9 @@ __global__ __launch_bounds__(256) void recode_spans_kernel(EditParams p, int *st
         if (mhb::offsets_bad(off, n, total, i)) { fail(status, BATCH_STATUS_ARG); atomicExch(stop, 1); }
     if (!n) return;
     for (uint64_t r = gtid(); r < total; r += stride) {
-        uint64_t lo = 0, hi = n - 1;                                  // the stream of span r: the last i < n with off[i] <= r
-        while (lo < hi) {
-            const uint64_t mid = (lo + hi + 1) >> 1;
-            if (off[mid] <= r) lo = mid; else hi = mid - 1;
-        }
+        const uint64_t i = span_stream(off, n, r);
         const unsigned long long b = sp[2 * r], e = sp[2 * r + 1];
-        if (b >= e || (r > off[lo] && sp[2 * r - 1] > b)) stream_fail(p.s.b, status, lo, MH_ERR_ARG, BATCH_STATUS_ARG);
+        if (b >= e || (r > off[i] && sp[2 * r - 1] > b)) stream_fail(p.s.b, status, i, MH_ERR_ARG, BATCH_STATUS_ARG);
     }
 }
 
@@ -812,80 +818,125 @@ __global__ __launch_bounds__((Dec<K, W>::NT)) void recode_walk_kernel(Params<EDI
 
 // ------------------------------------------------------------------------------------------------ splice
 
-// the splice   (include/mh.h, "SPLICING BATCHES"; order 0/1 on both sides.)  A span that begins inside the message is replaced
-//              by rep (rep_len bytes, 0: deleted), so output positions are not source positions.  A lane keeps ctx (the true
-//              symbol, for dec.next) and dctx (the last output byte), as the edit does, and walks its symbols with a cursor of
-//              three states: outside a span (the symbol is coded), at a span's begin (rep is coded, the symbol is not), inside
-//              (nothing is coded).  The lane whose symbols contain a span's begin owns its replacement.  Indexed source, one lane
-//              per source chunk: the length pass counts the chunk's output symbols beside its bits, a second scan turns them
-//              into output positions, and the emit pass writes a destination index entry in front of every output symbol whose
-//              position is a multiple of the chunk size: each output boundary is met by exactly one lane.
+// the splice   (include/mh.h, "SPLICING BATCHES" and "SPLICING WITH A REPLACEMENT TABLE"; order 0/1 on both sides.)  A span that
+//              begins inside the message is replaced by a string of another length (0 bytes: deleted), so output positions
+//              are not source positions.  A lane keeps ctx (the true symbol, for dec.next) and dctx (the last output byte),
+//              as the edit does, and walks its symbols with the cursor below.  The lane whose symbols contain a span's begin
+//              owns its replacement (an insertion at a chunk boundary belongs to the lane of the chunk that starts there).
+//              Indexed source, one lane per source chunk: the length pass counts the chunk's output symbols beside its bits,
+//              a second scan turns them into output positions, and the emit pass writes a destination index entry in front
+//              of every output symbol whose position is a multiple of the chunk size: each output boundary is met by
+//              exactly one lane.
+//   TABLE      One kernel family for both calls; TABLE selects how a span's replacement is found and nothing else.  false:
+//              the call's one string, sp.rep / sp.rep_len, and spans obey begin < end (recode_spans_kernel).  true: span r
+//              is replaced by table entry tag[r], and begin == end inserts in front of x[begin] (splice_spans_kernel: begin
+//              <= end, tag < n_reps, else the stream fails alone and no lane reads its list).  With every tag 0, a one-entry
+//              table and no insertion the two calls run the same steps on the same workspace layout.  The replacement is
+//              read from L2, once per owned span.
+//   cursor     Spans obey begin <= end <= next begin, so several may begin at one position: step() codes the replacements of
+//              all spans that begin at the current position, in list order, before it says whether the symbol is coded.
 //   start      The destination context of a lane whose chunk starts at `first` is the last output byte in front of it.  With
-//              first - 1 in no span that is the entry's byte; in a span with rep_len > 0 it is rep's last byte; in a deleted
-//              span r it is the byte in front of the run of touching spans that ends with r, which lies mid-chunk in general.
-//              splice_back_kernel, launched only when rep_len == 0, finds it per span before the length pass: one lane per
-//              span that reaches over a chunk boundary walks back through the touching spans in front of it (bounded by the
-//              stream's span count) and decodes the chunk that holds begin - 1 up to that symbol (or reads the next chunk's
-//              entry when begin is a boundary).  The two hot kernels then look the byte up and keep no cross-lane dependency;
-//              the comb kernel stays a pure sum.  A decode that fails there stores nothing of value: the lane of that chunk
-//              fails the stream in the length pass.
-//   price      The bits and drops of rep[1..] are constants of the call (splice_price_kernel): the length pass prices rep[0]
-//              in dctx and adds them.
-// rep sits in the 256 bytes of LDS where the edit keeps its map (map_at), or is read from L2 when they do not fit.
-struct Cut {
-    const unsigned long long *off, *sp;
-    const uint8_t *rep;
-    uint32_t rep_len;
+//              first - 1 in no span that is the entry's byte; in a span with a non-empty replacement it is that
+//              replacement's last byte; in a deleted span r it is sctx[r], which lies mid-chunk in general.
+//              splice_back_kernel finds it per span before the length pass (!TABLE: launched only when rep_len == 0; TABLE:
+//              always, the host does not know which entries are empty): one lane per deleted span that reaches over a chunk
+//              boundary walks back through the touching spans in front of it while they are empty (bounded by the stream's
+//              span count); a touching span with a non-empty replacement gives its last byte, else the lane decodes the
+//              chunk that holds begin - 1 up to that symbol (or reads the next chunk's entry when begin is a boundary).  The
+//              two hot kernels then look the byte up and keep no cross-lane dependency; the comb kernel stays a pure sum.
+//              A decode that fails there stores nothing of value: the lane of that chunk fails the stream in the length
+//              pass.
+//   price      price[2k], price[2k + 1]: the bits and drops of entry k's bytes behind its first (splice_price_kernel, which
+//              also checks the table); the length pass prices the first byte in dctx and adds them.  !TABLE: entry 0 is rep.
+template <bool TABLE> using SpParams = std::conditional_t<TABLE, SpliceTableParams, SpliceParams>;
+template <bool TABLE> struct Cut {
+    const unsigned long long *off, *sp, *rep_off;
+    const uint32_t *tag;
+    const uint8_t *bytes;
+    const uint8_t *rep;                 // the replacement of the last fetch, its entry and length
+    uint32_t k, rep_len;
     uint64_t r, rend, origin;
     uint32_t b, e;                      // the span at r, as offsets from origin (saturated; ~0u: never)
-    bool own;                           // the span at r begins at or behind origin: the lane codes its replacement
-    __device__ __forceinline__ Cut(const SpliceParams &p, unsigned char *smem, uint32_t at)
-        : off(p.sp.span_off), sp(p.sp.spans), rep(p.sp.rep), rep_len(p.sp.rep_len), r(0), rend(0), origin(0), b(~0u), e(~0u), own(true) {
-        if (p.sp.rep_lds) {
-            for (uint32_t k = threadIdx.x; k < rep_len; k += blockDim.x) smem[at + k] = p.sp.rep[k];
-            __syncthreads();
-            rep = smem + at;
-        }
+    bool own;                           // the span at r begins at or behind origin and its replacement is not coded yet
+    __device__ __forceinline__ explicit Cut(const SpParams<TABLE> &p)
+        : off(p.sp.span_off), sp(p.sp.spans), rep_off(nullptr), tag(nullptr), bytes(nullptr), rep(nullptr), k(0u), rep_len(0u),
+          r(0), rend(0), origin(0), b(~0u), e(~0u), own(false) {
+        if constexpr (TABLE) { rep_off = p.tb.rep_off; tag = p.tb.span_tag; bytes = p.tb.rep_bytes; }
+        else { rep = p.sp.rep; rep_len = p.sp.rep_len; }
     }
     __device__ __forceinline__ uint32_t rel(uint64_t x) const {
         return x <= origin ? 0u : (x - origin >= 0xFFFFFFFFull ? ~0u : uint32_t(x - origin));
     }
     __device__ __forceinline__ void load() {
-        if (r < rend) { b = rel(sp[2 * r]); e = rel(sp[2 * r + 1]); own = sp[2 * r] >= origin; } else { b = e = ~0u; }
+        if (r < rend) { b = rel(sp[2 * r]); e = rel(sp[2 * r + 1]); own = sp[2 * r] >= origin; } else { b = e = ~0u; own = false; }
     }
-    // the first span of stream i that ends behind pos (Spans<true>::seek)
-    __device__ __forceinline__ void seek(uint64_t i, uint64_t pos) {
-        origin = pos;
+    // the replacement of span q.  !TABLE: the call's, entry 0, which the constructor set: no loads
+    __device__ __forceinline__ void fetch(uint64_t q) {
+        if constexpr (TABLE) {
+            k = tag[q];
+            const unsigned long long o = rep_off[k];
+            rep = bytes + o;
+            rep_len = uint32_t(rep_off[k + 1] - o);
+        }
+    }
+    // stream i from its first symbol: every span of the list, an insertion at 0 included
+    __device__ __forceinline__ void start(uint64_t i) {
+        origin = 0;
+        r = off[i];
+        rend = off[i + 1];
+        load();
+    }
+    // stream i from position first > 0: the first span that ends at or behind first (a span or an insertion in front of
+    // first - 1 is another lane's); true when that span holds first - 1
+    __device__ __forceinline__ bool seek(uint64_t i, uint64_t first) {
+        origin = first;
         uint64_t lo = off[i], hi = off[i + 1];
         rend = hi;
         while (lo < hi) {
             const uint64_t mid = (lo + hi) >> 1;
-            if (sp[2 * mid + 1] > pos) hi = mid; else lo = mid + 1;
+            if (sp[2 * mid + 1] >= first) hi = mid; else lo = mid + 1;
         }
         r = lo;
         load();
+        return r < rend && sp[2 * r] < first;
     }
-    // from a seek at pos - 1 to origin pos: at most one span ends there
-    __device__ __forceinline__ void step_origin() {
-        ++origin;
-        if (r < rend && sp[2 * r + 1] <= origin) ++r;
-        load();
-    }
-    // the symbol at origin + pos: 0 outside a span, 1 at a span's begin, 2 inside; pos goes up by one from the seek
-    __device__ __forceinline__ uint32_t state(uint32_t pos) {
-        if (pos >= e) { ++r; load(); }
-        return pos < b ? 0u : (pos == b && own ? 1u : 2u);
+    // the symbol at origin + pos, pos going up by one from the start: emit() runs once for every span that begins here (the
+    // replacement fetched); true when the symbol lies in no span and is coded
+    template <typename F> __device__ __forceinline__ bool step(uint32_t pos, F &&emit) {
+        for (;;) {
+            if (pos < b) return true;
+            if (own && pos == b) { fetch(r); emit(); own = false; }
+            if (pos < e) return false;
+            ++r;
+            load();
+        }
     }
 };
 
 // The destination context as chunk c's lane starts (see "start" above); the cursor is left at the chunk's first symbol.
-__device__ __forceinline__ uint32_t splice_start(Cut &cu, const Chunk &c, const uint32_t *sctx) {
-    if (!c.first) { cu.seek(c.i, 0); return c.ctx; }
-    cu.seek(c.i, c.first - 1u);
-    uint32_t d = c.ctx;
-    if (cu.r < cu.rend && cu.b == 0u) d = cu.rep_len ? cu.rep[cu.rep_len - 1u] : sctx[cu.r];   // (b == 0: it begins at first - 1 or in front)
-    cu.step_origin();
-    return d;
+template <bool TABLE> __device__ __forceinline__ uint32_t splice_start(Cut<TABLE> &cu, const Chunk &c, const uint32_t *sctx) {
+    if (!c.first) { cu.start(c.i); return c.ctx; }
+    if (!cu.seek(c.i, c.first)) return c.ctx;
+    cu.fetch(cu.r);
+    return cu.rep_len ? cu.rep[cu.rep_len - 1u] : sctx[cu.r];
+}
+
+// the end of span q's replacement: empty, or its last byte at base[end - 1] (splice_back_kernel asks for the byte only
+// where it needs it)
+struct RepEnd {
+    const uint8_t *base;
+    uint64_t end;
+    bool empty;
+    __device__ __forceinline__ uint32_t last() const { return base[end - 1u]; }
+};
+template <bool TABLE> __device__ __forceinline__ RepEnd rep_end(const SpParams<TABLE> &p, uint64_t q) {
+    if constexpr (TABLE) {
+        const uint32_t k = p.tb.span_tag[q];
+        const unsigned long long o0 = p.tb.rep_off[k], o1 = p.tb.rep_off[k + 1];
+        return {p.tb.rep_bytes, o1, o1 == o0};
+    } else {
+        return {p.sp.rep, p.sp.rep_len, p.sp.rep_len == 0u};
+    }
 }
 
 __global__ __launch_bounds__(256) void splice_check_kernel(SpliceParams p, int *status, int *stop) {
@@ -911,25 +962,69 @@ inline EditParams spans_view(const SpliceParams &p) {
     return e;
 }
 
-// the bits and the drops of rep[1 .. rep_len): pair j in the context of rep[j - 1]
-__global__ __launch_bounds__(256) void splice_price_kernel(SpliceParams p, uint32_t *price) {
+// entry k's bits and drops behind its first byte into price[2k], price[2k + 1]: pair j in the context of byte j - 1.  One
+// workgroup per entry.  TABLE: rep_off[0] == 0, no decreasing offsets, no entry over MH_SPLICE_MAX_REP bytes, else
+// BATCH_STATUS_ARG and the call stops; an entry is read only when it lies inside the table's rep_off[n_reps] bytes.  !TABLE:
+// the one entry (rep, rep_len), which the call checked.
+template <bool TABLE>
+__global__ __launch_bounds__(256) void splice_price_kernel(SpParams<TABLE> p, uint32_t *price, int *status, int *stop) {
     __shared__ uint32_t acc[2];
-    if (threadIdx.x < 2u) acc[threadIdx.x] = 0u;
-    __syncthreads();
-    const uint32_t j = threadIdx.x;
-    if (j >= 1u && j < p.sp.rep_len) {
-        const uint32_t l = p.dst.len8[((uint32_t(p.sp.rep[j - 1u]) & p.dst.ctx_mask) << 8) | p.sp.rep[j]];
-        atomicAdd(&acc[0], l);
-        if (!l) atomicAdd(&acc[1], 1u);
+    uint64_t nr = 1;
+    if constexpr (TABLE) {
+        nr = p.tb.n_reps;
+        if (blockIdx.x == 0 && threadIdx.x == 0 && p.tb.rep_off[0] != 0) { fail(status, BATCH_STATUS_ARG); atomicExch(stop, 1); }
     }
-    __syncthreads();
-    if (threadIdx.x < 2u) price[threadIdx.x] = acc[threadIdx.x];
+    for (uint64_t k = blockIdx.x; k < nr; k += gridDim.x) {
+        const uint8_t *rep = p.sp.rep;
+        uint32_t len = p.sp.rep_len;
+        if constexpr (TABLE) {
+            const unsigned long long o0 = p.tb.rep_off[k], o1 = p.tb.rep_off[k + 1];
+            if (o1 < o0 || o1 - o0 > MH_SPLICE_MAX_REP || o1 > p.tb.rep_off[nr]) {
+                if (threadIdx.x == 0) { fail(status, BATCH_STATUS_ARG); atomicExch(stop, 1); }
+                continue;
+            }
+            rep = p.tb.rep_bytes + o0;
+            len = uint32_t(o1 - o0);
+        }
+        if (threadIdx.x < 2u) acc[threadIdx.x] = 0u;
+        __syncthreads();
+        const uint32_t j = threadIdx.x;
+        if (j >= 1u && j < len) {
+            const uint32_t l = p.dst.len8[((uint32_t(rep[j - 1u]) & p.dst.ctx_mask) << 8) | rep[j]];
+            atomicAdd(&acc[0], l);
+            if (!l) atomicAdd(&acc[1], 1u);
+        }
+        __syncthreads();
+        if (threadIdx.x < 2u) price[2 * k + threadIdx.x] = acc[threadIdx.x];
+        __syncthreads();
+    }
 }
 
-// rep_len == 0, indexed: sctx[r] for every span r over a chunk boundary, the last output byte in front of the run of touching
-// spans that ends with r.  More spans than the workspace has room for: MHK_STATUS_CAPACITY and the call stops.
-template <Model K>
-__global__ __launch_bounds__((Dec<K, false>::NT)) void splice_back_kernel(SpliceParams p, uint32_t *sctx, int *status, int *stop) {
+// recode_spans_kernel for the table's rule: span r of stream i with begin > end, beginning in front of the end of the span
+// before it, or with a tag that is no table entry: the stream's verdict is MH_ERR_ARG.  Spans and no table: the call stops.
+__global__ __launch_bounds__(256) void splice_spans_kernel(SpliceTableParams p, int *status, int *stop) {
+    if (stopped(stop)) return;
+    const unsigned long long *off = p.sp.span_off, *sp = p.sp.spans;
+    const uint64_t n = p.s.b.n, total = off[n], stride = uint64_t(gridDim.x) * blockDim.x;
+    for (uint64_t i = gtid(); i <= n; i += stride)
+        if (mhb::offsets_bad(off, n, total, i)) { fail(status, BATCH_STATUS_ARG); atomicExch(stop, 1); }
+    if (!n) return;
+    if (total && !p.tb.n_reps) {
+        if (gtid() == 0) { fail(status, BATCH_STATUS_ARG); atomicExch(stop, 1); }
+        return;
+    }
+    for (uint64_t r = gtid(); r < total; r += stride) {
+        const uint64_t i = span_stream(off, n, r);
+        const unsigned long long b = sp[2 * r], e = sp[2 * r + 1];
+        if (b > e || (r > off[i] && sp[2 * r - 1] > b) || p.tb.span_tag[r] >= p.tb.n_reps)
+            stream_fail(p.s.b, status, i, MH_ERR_ARG, BATCH_STATUS_ARG);
+    }
+}
+
+// indexed: sctx[r] for every deleted span r over a chunk boundary, the last output byte in front of it (see "start" above).
+// More spans than the workspace has room for: MHK_STATUS_CAPACITY and the call stops.
+template <Model K, bool TABLE>
+__global__ __launch_bounds__((Dec<K, false>::NT)) void splice_back_kernel(SpParams<TABLE> p, uint32_t *sctx, int *status, int *stop) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     if (stopped(stop)) return;
     Dec<K, false> dec(p.s, smem);
@@ -944,18 +1039,20 @@ __global__ __launch_bounds__((Dec<K, false>::NT)) void splice_back_kernel(Splice
     for (uint64_t r = gtid(); r < total; r += uint64_t(gridDim.x) * blockDim.x) {
         sctx[r] = 0u;
         if ((sp[2 * r + 1] >> cs) == (sp[2 * r] >> cs)) continue;     // no chunk starts in (begin, end]: no lane asks
-        uint64_t lo = 0, hi = n - 1;                                  // the stream of span r (recode_spans_kernel)
-        while (lo < hi) {
-            const uint64_t mid = (lo + hi + 1) >> 1;
-            if (off[mid] <= r) lo = mid; else hi = mid - 1;
-        }
-        const uint64_t i = lo;
-        if (p.s.b.stream_status[i] != MH_OK) continue;
-        uint64_t r0 = r;
-        while (r0 > off[i] && sp[2 * r0 - 1] == sp[2 * r0]) --r0;
-        const uint64_t begin = sp[2 * r0];
+        const uint64_t i = span_stream(off, n, r);
+        if (p.s.b.stream_status[i] != MH_OK) continue;                // (a passed stream's tags are table entries)
+        if (!rep_end<TABLE>(p, r).empty) continue;                    // replaced: its own last byte serves
         const uint64_t a = p.s.b.sym_off[i], ni = p.s.b.sym_off[i + 1] - a;
-        if (begin >= ni) continue;                                    // the span is ignored
+        if (sp[2 * r] >= ni) continue;                                // the span is ignored
+        uint64_t r0 = r;
+        uint32_t got = ~0u;
+        while (r0 > off[i] && sp[2 * r0 - 1] == sp[2 * r0]) {         // the touching span in front: through it while it is empty
+            const RepEnd front = rep_end<TABLE>(p, r0 - 1);
+            if (!front.empty) { got = front.last(); break; }
+            --r0;
+        }
+        if (got != ~0u) { sctx[r] = got; continue; }
+        const uint64_t begin = sp[2 * r0];
         if (!begin) { sctx[r] = p.s.b.prev0; continue; }
         const uint64_t wb = (a >> cs) + i, pos = begin - 1u;
         if (!(begin & ((uint64_t(1) << cs) - 1u))) { sctx[r] = uint32_t(p.s.b.index[wb + (begin >> cs)] >> 56); continue; }
@@ -978,27 +1075,16 @@ __global__ __launch_bounds__((Dec<K, false>::NT)) void splice_back_kernel(Splice
     }
 }
 
-// rep's bytes behind dctx: lengths and drops (length pass: rep[0] alone, the rest is priced)
-template <bool DLDS>
-__device__ __forceinline__ void rep_len_pass(const Enc<DLDS, false> &E, const Cut &cu, const uint32_t *price, uint32_t &dctx, uint32_t &bits,
-                                             uint32_t &drops, uint32_t &osym) {
-    if (!cu.rep_len) return;
-    const uint32_t l = E.len(E.at(dctx, cu.rep[0]));
-    bits += l + price[0];
-    drops += (l == 0u) + price[1];
-    osym += cu.rep_len;
-    dctx = cu.rep[cu.rep_len - 1u];
-}
-
-template <Model K, bool DLDS>
-__global__ __launch_bounds__((Dec<K, false>::NT)) void splice_idx_len_kernel(SpliceParams p, uint64_t nwork, uint32_t lds_at, unsigned long long *cbits,
-                                                                           unsigned long long *csyms, uint32_t *cdrop, const uint32_t *sctx,
-                                                                           const uint32_t *price, int *status, const int *stop) {
+template <Model K, bool DLDS, bool TABLE>
+__global__ __launch_bounds__((Dec<K, false>::NT)) void splice_idx_len_kernel(SpParams<TABLE> p, uint64_t nwork, uint32_t lds_at,
+                                                                           unsigned long long *cbits, unsigned long long *csyms, uint32_t *cdrop,
+                                                                           const uint32_t *sctx, const uint32_t *price, int *status,
+                                                                           const int *stop) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     if (stopped(stop)) return;
     Dec<K, false> dec(p.s, smem);
     const Enc<DLDS, false> E(p.dst, smem, lds_at);
-    Cut cu(p, smem, map_at<DLDS>(p.dst, lds_at));
+    Cut<TABLE> cu(p);
     for (uint64_t w = gtid(); w < nwork; w += uint64_t(gridDim.x) * blockDim.x) {
         Chunk c;
         if (!chunk_of<K, false>(p.s, w, c) || p.s.b.stream_status[c.i] == MH_ERR_ARG) continue;
@@ -1014,15 +1100,20 @@ __global__ __launch_bounds__((Dec<K, false>::NT)) void splice_idx_len_kernel(Spl
         for (uint32_t t = 0; t < c.nsym && !bad; ++t) {
             const uint32_t sym = dec.next(p.s, src, bc, ctx, used, bad);
             if (bad) break;
-            const uint32_t st = cu.state(t);
-            if (st == 0u) {
+            const bool coded = cu.step(t, [&] {
+                if (!cu.rep_len) return;
+                const uint32_t l = E.len(E.at(dctx, cu.rep[0]));     // rep[0] in dctx; the rest is priced
+                bits += l + price[2 * cu.k];
+                drops += (l == 0u) + price[2 * cu.k + 1u];
+                osym += cu.rep_len;
+                dctx = cu.rep[cu.rep_len - 1u];
+            });
+            if (coded) {
                 const uint32_t l = E.len(E.at(dctx, sym));
                 bits += l;
                 drops += l == 0u;
                 dctx = sym;
                 ++osym;
-            } else if (st == 1u) {
-                rep_len_pass<DLDS>(E, cu, price, dctx, bits, drops, osym);
             }
             ctx = sym;
         }
@@ -1102,15 +1193,15 @@ struct SpliceOut {
     }
 };
 
-template <Model K, bool DLDS>
-__global__ __launch_bounds__((Dec<K, false>::NT)) void splice_idx_emit_kernel(SpliceParams p, uint64_t nwork, uint32_t lds_at,
+template <Model K, bool DLDS, bool TABLE>
+__global__ __launch_bounds__((Dec<K, false>::NT)) void splice_idx_emit_kernel(SpParams<TABLE> p, uint64_t nwork, uint32_t lds_at,
                                                                             const unsigned long long *cbase, const unsigned long long *obase,
                                                                             const uint32_t *sctx, uint32_t *tail, const int *stop) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     if (stopped(stop)) return;
     Dec<K, false> dec(p.s, smem);
     const Enc<DLDS, false> E(p.dst, smem, lds_at);
-    Cut cu(p, smem, map_at<DLDS>(p.dst, lds_at));
+    Cut<TABLE> cu(p);
     const uint64_t bytes = p.out_off[p.s.b.n];
     const uint64_t tail_w = (bytes & 3u) ? bytes >> 2 : ~uint64_t(0);
     const uint32_t cs = p.s.b.chunk_shift;
@@ -1137,373 +1228,6 @@ __global__ __launch_bounds__((Dec<K, false>::NT)) void splice_idx_emit_kernel(Sp
         bool bad = false;
         for (uint32_t t = 0; t < c.nsym && !bad; ++t) {            // (the stream passed: bad stays false)
             const uint32_t sym = dec.next(p.s, src, bc, ctx, used, bad);
-            const uint32_t st = cu.state(t);
-            if (st == 0u) {
-                so.put<DLDS>(E, bw, dctx, sym);
-            } else if (st == 1u) {
-                for (uint32_t j = 0; j < cu.rep_len; ++j) so.put<DLDS>(E, bw, dctx, cu.rep[j]);
-            }
-            ctx = sym;
-        }
-        if (so.on) bw.finish();
-    }
-}
-
-// Index-free, one lane per stream (recode_walk_kernel).  EMIT = false: the verdict, the stream's symbols into sym_off[i] and
-// its output symbols into out_sym_off[i] (both scanned next), its dst bits and dropped symbols; true: codes and index entries.
-template <Model K, bool DLDS, bool EMIT>
-__global__ __launch_bounds__((Dec<K, false>::NT)) void splice_walk_kernel(SpliceParams p, uint32_t lds_at, uint32_t *tail, int *status, const int *stop) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    if (stopped(stop)) return;
-    Dec<K, false> dec(p.s, smem);
-    const Enc<DLDS, false> E(p.dst, smem, lds_at);
-    Cut cu(p, smem, map_at<DLDS>(p.dst, lds_at));
-    const uint64_t n = p.s.b.n;
-    const uint64_t bytes = EMIT ? p.out_off[n] : 0;
-    const uint64_t tail_w = (bytes & 3u) ? bytes >> 2 : ~uint64_t(0);
-    for (uint64_t i = gtid(); i < n; i += uint64_t(gridDim.x) * blockDim.x) {
-        if (p.s.b.stream_status[i] != MH_OK) continue;
-        const uint64_t nb = p.s.b.nbits[i];
-        uint64_t count = ~uint64_t(0);
-        if (EMIT) {
-            count = p.s.b.sym_off[i + 1] - p.s.b.sym_off[i];
-            if (p.sp.out_sym_off[i + 1] == p.sp.out_sym_off[i]) continue;
-        } else if (nb > p.s.b.walk_max_bits) {
-            stream_fail(p.s.b, status, i, MH_ERR_ARG, BATCH_STATUS_ARG);
-            continue;
-        }
-        uint64_t bit0;
-        const BitSrc src = mhb::stream_src(p.s.b.payload, p.s.b.pay_off[i], nb, bit0);
-        BitCursor bc;
-        bc.init(src, bit0);
-        dec.stream(p.s, i);
-        SpliceOut so;
-        so.o = 0; so.bit = 0; so.ocs = p.out_chunk_shift;
-        so.on = EMIT && p.out != nullptr;
-        so.slice = EMIT && p.out_index ? p.out_index + (p.sp.out_sym_off[i] >> so.ocs) + i : nullptr;
-        BitWriter bw;
-        if (so.on) bw.init(reinterpret_cast<uint32_t *>(p.out), tail, tail_w, uint64_t(p.out_off[i]) * 8u);
-        uint32_t ctx = start_ctx<K, false>(p.s), used = 0, drops = 0;
-        uint32_t dctx = ctx;
-        cu.seek(i, 0);
-        bool bad = false;
-        uint64_t k = 0;
-        // every code has at least one bit: at most nb steps (src/coding.cpp:124 — decode while bits remain)
-        while (used < nb && !bad && k < count) {
-            const uint32_t sym = dec.next(p.s, src, bc, ctx, used, bad);
-            if (bad) break;
-            const uint32_t st = cu.state(uint32_t(k));
-            if (st == 0u) {
-                if (EMIT) {
-                    so.put<DLDS>(E, bw, dctx, sym);
-                } else {
-                    const uint32_t l = E.len(E.at(dctx, sym));
-                    so.bit += l; drops += l == 0u; dctx = sym; ++so.o;
-                }
-            } else if (st == 1u) {
-                for (uint32_t j = 0; j < cu.rep_len; ++j) {
-                    const uint32_t rs = cu.rep[j];
-                    if (EMIT) {
-                        so.put<DLDS>(E, bw, dctx, rs);
-                    } else {
-                        const uint32_t l = E.len(E.at(dctx, rs));
-                        so.bit += l; drops += l == 0u; dctx = rs; ++so.o;
-                    }
-                }
-            }
-            ctx = sym;
-            ++k;
-        }
-        if (EMIT) { if (so.on) bw.finish(); continue; }
-        if (bad || used != nb) { stream_fail(p.s.b, status, i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT); continue; }
-        p.s.b.sym_off[i] = k;                                       // src/coding.cpp:158: the stream ends exactly at nbits
-        p.sp.out_sym_off[i] = so.o;
-        p.out_nbits[i] = so.bit;
-        if (p.dropped) p.dropped[i] = drops;
-    }
-}
-
-// ------------------------------------------------------------------------------------------------ table splice
-
-// the table splice   (include/mh.h, "SPLICING WITH A REPLACEMENT TABLE".)  The splice with a replacement per span: span r is
-//              replaced by table entry tag[r], and begin == end inserts in front of x[begin].  The stages, the ownership rule
-//              (the lane whose symbols contain begin codes the replacement: an insertion at a chunk boundary belongs to the
-//              lane of the chunk that starts there), the two scans and the index by output positions are the splice's; these
-//              kernels are its siblings with the cursor below.  The table is read from L2, once per owned span.
-//   cursor     Spans obey begin <= end <= next begin, so several may begin at one position: step() codes the replacements of
-//              all spans that begin at the current position, in list order, before it says whether the symbol is coded.
-//   start      first - 1 in a span with a non-empty replacement: that replacement's last byte; in a deleted span r: sctx[r].
-//              splice_tback_kernel always runs (the host does not know which entries are empty): a lane works only for a
-//              deleted span over a chunk boundary and walks back through the touching spans in front of it while they are
-//              empty; a touching span with a non-empty replacement gives its last byte, else the splice's rule holds.
-//   price      price[2k], price[2k + 1]: the bits and drops of rep_k[1..] (splice_tprice_kernel, which also checks the table).
-//   tags       splice_tspans_kernel, in front of everything that reads the table: the span rule and tag < n_reps, else the
-//              stream fails alone and no lane reads its list.
-struct TCut {
-    const unsigned long long *off, *sp, *rep_off;
-    const uint32_t *tag;
-    const uint8_t *bytes;
-    const uint8_t *rep;                 // the replacement of the last fetch, its entry and length
-    uint32_t k, rep_len;
-    uint64_t r, rend, origin;
-    uint32_t b, e;                      // the span at r, as offsets from origin (saturated; ~0u: never)
-    bool own;                           // the span at r begins at or behind origin and its replacement is not coded yet
-    __device__ __forceinline__ explicit TCut(const SpliceTableParams &p)
-        : off(p.sp.span_off), sp(p.sp.spans), rep_off(p.tb.rep_off), tag(p.tb.span_tag), bytes(p.tb.rep_bytes), rep(nullptr), k(0u), rep_len(0u),
-          r(0), rend(0), origin(0), b(~0u), e(~0u), own(false) {}
-    __device__ __forceinline__ uint32_t rel(uint64_t x) const {
-        return x <= origin ? 0u : (x - origin >= 0xFFFFFFFFull ? ~0u : uint32_t(x - origin));
-    }
-    __device__ __forceinline__ void load() {
-        if (r < rend) { b = rel(sp[2 * r]); e = rel(sp[2 * r + 1]); own = sp[2 * r] >= origin; } else { b = e = ~0u; own = false; }
-    }
-    __device__ __forceinline__ void fetch(uint64_t q) {
-        k = tag[q];
-        const unsigned long long o = rep_off[k];
-        rep = bytes + o;
-        rep_len = uint32_t(rep_off[k + 1] - o);
-    }
-    // stream i from its first symbol: every span of the list, an insertion at 0 included
-    __device__ __forceinline__ void start(uint64_t i) {
-        origin = 0;
-        r = off[i];
-        rend = off[i + 1];
-        load();
-    }
-    // stream i from position first > 0: the first span that ends at or behind first (a span or an insertion in front of
-    // first - 1 is another lane's); true when that span holds first - 1
-    __device__ __forceinline__ bool seek(uint64_t i, uint64_t first) {
-        origin = first;
-        uint64_t lo = off[i], hi = off[i + 1];
-        rend = hi;
-        while (lo < hi) {
-            const uint64_t mid = (lo + hi) >> 1;
-            if (sp[2 * mid + 1] >= first) hi = mid; else lo = mid + 1;
-        }
-        r = lo;
-        load();
-        return r < rend && sp[2 * r] < first;
-    }
-    // the symbol at origin + pos, pos going up by one from the start: emit() runs once for every span that begins here (the
-    // replacement fetched); true when the symbol lies in no span and is coded
-    template <typename F> __device__ __forceinline__ bool step(uint32_t pos, F &&emit) {
-        for (;;) {
-            if (pos < b) return true;
-            if (own && pos == b) { fetch(r); emit(); own = false; }
-            if (pos < e) return false;
-            ++r;
-            load();
-        }
-    }
-};
-
-// The destination context as chunk c's lane starts; the cursor is left at the chunk's first symbol.
-__device__ __forceinline__ uint32_t splice_tstart(TCut &cu, const Chunk &c, const uint32_t *sctx) {
-    if (!c.first) { cu.start(c.i); return c.ctx; }
-    if (!cu.seek(c.i, c.first)) return c.ctx;
-    cu.fetch(cu.r);
-    return cu.rep_len ? cu.rep[cu.rep_len - 1u] : sctx[cu.r];
-}
-
-// the table: rep_off[0] == 0, no decreasing offsets, no entry over MH_SPLICE_MAX_REP bytes, else BATCH_STATUS_ARG and the call
-// stops; entry k's bits and drops behind its first byte into price[2k], price[2k + 1].  One workgroup per entry; an entry
-// is read only when it lies inside the table's rep_off[n_reps] bytes.
-__global__ __launch_bounds__(256) void splice_tprice_kernel(SpliceTableParams p, uint32_t *price, int *status, int *stop) {
-    __shared__ uint32_t acc[2];
-    const unsigned long long *ro = p.tb.rep_off;
-    const uint64_t nr = p.tb.n_reps;
-    if (blockIdx.x == 0 && threadIdx.x == 0 && ro[0] != 0) { fail(status, BATCH_STATUS_ARG); atomicExch(stop, 1); }
-    for (uint64_t k = blockIdx.x; k < nr; k += gridDim.x) {
-        const unsigned long long o0 = ro[k], o1 = ro[k + 1];
-        if (o1 < o0 || o1 - o0 > MH_SPLICE_MAX_REP || o1 > ro[nr]) {
-            if (threadIdx.x == 0) { fail(status, BATCH_STATUS_ARG); atomicExch(stop, 1); }
-            continue;
-        }
-        if (threadIdx.x < 2u) acc[threadIdx.x] = 0u;
-        __syncthreads();
-        const uint32_t j = threadIdx.x;
-        if (j >= 1u && j < uint32_t(o1 - o0)) {
-            const uint8_t *rep = p.tb.rep_bytes + o0;
-            const uint32_t l = p.dst.len8[((uint32_t(rep[j - 1u]) & p.dst.ctx_mask) << 8) | rep[j]];
-            atomicAdd(&acc[0], l);
-            if (!l) atomicAdd(&acc[1], 1u);
-        }
-        __syncthreads();
-        if (threadIdx.x < 2u) price[2 * k + threadIdx.x] = acc[threadIdx.x];
-        __syncthreads();
-    }
-}
-
-// recode_spans_kernel for this call's rule: span r of stream i with begin > end, beginning in front of the end of the span
-// before it, or with a tag that is no table entry: the stream's verdict is MH_ERR_ARG.  Spans and no table: the call stops.
-__global__ __launch_bounds__(256) void splice_tspans_kernel(SpliceTableParams p, int *status, int *stop) {
-    if (stopped(stop)) return;
-    const unsigned long long *off = p.sp.span_off, *sp = p.sp.spans;
-    const uint64_t n = p.s.b.n, total = off[n], stride = uint64_t(gridDim.x) * blockDim.x;
-    for (uint64_t i = gtid(); i <= n; i += stride)
-        if (mhb::offsets_bad(off, n, total, i)) { fail(status, BATCH_STATUS_ARG); atomicExch(stop, 1); }
-    if (!n) return;
-    if (total && !p.tb.n_reps) {
-        if (gtid() == 0) { fail(status, BATCH_STATUS_ARG); atomicExch(stop, 1); }
-        return;
-    }
-    for (uint64_t r = gtid(); r < total; r += stride) {
-        uint64_t lo = 0, hi = n - 1;                                  // the stream of span r: the last i < n with off[i] <= r
-        while (lo < hi) {
-            const uint64_t mid = (lo + hi + 1) >> 1;
-            if (off[mid] <= r) lo = mid; else hi = mid - 1;
-        }
-        const unsigned long long b = sp[2 * r], e = sp[2 * r + 1];
-        if (b > e || (r > off[lo] && sp[2 * r - 1] > b) || p.tb.span_tag[r] >= p.tb.n_reps)
-            stream_fail(p.s.b, status, lo, MH_ERR_ARG, BATCH_STATUS_ARG);
-    }
-}
-
-// splice_back_kernel for the table, always launched on an indexed batch: sctx[r] for every deleted span r over a chunk
-// boundary.  More spans than the workspace has room for: MHK_STATUS_CAPACITY and the call stops.
-template <Model K>
-__global__ __launch_bounds__((Dec<K, false>::NT)) void splice_tback_kernel(SpliceTableParams p, uint32_t *sctx, int *status, int *stop) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    if (stopped(stop)) return;
-    Dec<K, false> dec(p.s, smem);
-    const unsigned long long *off = p.sp.span_off, *sp = p.sp.spans, *ro = p.tb.rep_off;
-    const uint64_t n = p.s.b.n, total = off[n];
-    if (total > p.sp.span_cap) {
-        if (gtid() == 0) { fail(status, mhk::MHK_STATUS_CAPACITY); atomicExch(stop, 1); }
-        return;
-    }
-    if (!n) return;
-    const uint32_t cs = p.s.b.chunk_shift;
-    for (uint64_t r = gtid(); r < total; r += uint64_t(gridDim.x) * blockDim.x) {
-        sctx[r] = 0u;
-        if ((sp[2 * r + 1] >> cs) == (sp[2 * r] >> cs)) continue;     // no chunk starts in (begin, end]: no lane asks
-        uint64_t lo = 0, hi = n - 1;                                  // the stream of span r (recode_spans_kernel)
-        while (lo < hi) {
-            const uint64_t mid = (lo + hi + 1) >> 1;
-            if (off[mid] <= r) lo = mid; else hi = mid - 1;
-        }
-        const uint64_t i = lo;
-        if (p.s.b.stream_status[i] != MH_OK) continue;                // (a passed stream's tags are table entries)
-        const uint32_t k = p.tb.span_tag[r];
-        if (ro[k + 1] != ro[k]) continue;                             // replaced: its own last byte serves
-        const uint64_t a = p.s.b.sym_off[i], ni = p.s.b.sym_off[i + 1] - a;
-        if (sp[2 * r] >= ni) continue;                                // the span is ignored
-        uint64_t r0 = r;
-        uint32_t got = ~0u;
-        while (r0 > off[i] && sp[2 * r0 - 1] == sp[2 * r0]) {         // the touching span in front: through it while it is empty
-            const uint32_t kp = p.tb.span_tag[r0 - 1];
-            const unsigned long long o0 = ro[kp], o1 = ro[kp + 1];
-            if (o1 != o0) { got = p.tb.rep_bytes[o1 - 1u]; break; }
-            --r0;
-        }
-        if (got != ~0u) { sctx[r] = got; continue; }
-        const uint64_t begin = sp[2 * r0];
-        if (!begin) { sctx[r] = p.s.b.prev0; continue; }
-        const uint64_t wb = (a >> cs) + i, pos = begin - 1u;
-        if (!(begin & ((uint64_t(1) << cs) - 1u))) { sctx[r] = uint32_t(p.s.b.index[wb + (begin >> cs)] >> 56); continue; }
-        Chunk c;
-        if (!chunk_of<K, false>(p.s, wb + (pos >> cs), c) || !c.entry_ok()) continue;
-        uint64_t bit0;
-        const BitSrc src = mhb::stream_src(p.s.b.payload, p.s.b.pay_off[i], c.nb, bit0);
-        BitCursor bc;
-        bc.init(src, bit0 + c.start);
-        dec.stream(p.s, i);
-        uint32_t ctx = c.ctx, used = 0;
-        bool bad = false;
-        const uint32_t count = uint32_t(pos - c.first) + 1u;          // <= c.nsym: pos < ni
-        for (uint32_t t = 0; t < count && !bad; ++t) {
-            const uint32_t sym = dec.next(p.s, src, bc, ctx, used, bad);
-            if (bad) break;
-            ctx = sym;
-        }
-        sctx[r] = ctx;
-    }
-}
-
-template <Model K, bool DLDS>
-__global__ __launch_bounds__((Dec<K, false>::NT)) void splice_tidx_len_kernel(SpliceTableParams p, uint64_t nwork, uint32_t lds_at,
-                                                                            unsigned long long *cbits, unsigned long long *csyms, uint32_t *cdrop,
-                                                                            const uint32_t *sctx, const uint32_t *price, int *status,
-                                                                            const int *stop) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    if (stopped(stop)) return;
-    Dec<K, false> dec(p.s, smem);
-    const Enc<DLDS, false> E(p.dst, smem, lds_at);
-    TCut cu(p);
-    for (uint64_t w = gtid(); w < nwork; w += uint64_t(gridDim.x) * blockDim.x) {
-        Chunk c;
-        if (!chunk_of<K, false>(p.s, w, c) || p.s.b.stream_status[c.i] == MH_ERR_ARG) continue;
-        if (!c.entry_ok()) { stream_fail(p.s.b, status, c.i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT); continue; }
-        uint64_t bit0;
-        const BitSrc src = mhb::stream_src(p.s.b.payload, p.s.b.pay_off[c.i], c.nb, bit0);
-        BitCursor bc;
-        bc.init(src, bit0 + c.start);
-        dec.stream(p.s, c.i);
-        uint32_t ctx = c.ctx, used = 0, bits = 0, drops = 0, osym = 0;
-        uint32_t dctx = splice_tstart(cu, c, sctx);
-        bool bad = false;
-        for (uint32_t t = 0; t < c.nsym && !bad; ++t) {
-            const uint32_t sym = dec.next(p.s, src, bc, ctx, used, bad);
-            if (bad) break;
-            const bool coded = cu.step(t, [&] {
-                if (!cu.rep_len) return;
-                const uint32_t l = E.len(E.at(dctx, cu.rep[0]));     // rep[0] in dctx; the rest is priced
-                bits += l + price[2 * cu.k];
-                drops += (l == 0u) + price[2 * cu.k + 1u];
-                osym += cu.rep_len;
-                dctx = cu.rep[cu.rep_len - 1u];
-            });
-            if (coded) {
-                const uint32_t l = E.len(E.at(dctx, sym));
-                bits += l;
-                drops += l == 0u;
-                dctx = sym;
-                ++osym;
-            }
-            ctx = sym;
-        }
-        if (bad || used != c.end - c.start) { stream_fail(p.s.b, status, c.i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT); continue; }
-        cbits[w] = bits;
-        csyms[w] = osym;
-        cdrop[w] = drops;
-    }
-}
-
-template <Model K, bool DLDS>
-__global__ __launch_bounds__((Dec<K, false>::NT)) void splice_tidx_emit_kernel(SpliceTableParams p, uint64_t nwork, uint32_t lds_at,
-                                                                             const unsigned long long *cbase, const unsigned long long *obase,
-                                                                             const uint32_t *sctx, uint32_t *tail, const int *stop) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    if (stopped(stop)) return;
-    Dec<K, false> dec(p.s, smem);
-    const Enc<DLDS, false> E(p.dst, smem, lds_at);
-    TCut cu(p);
-    const uint64_t bytes = p.out_off[p.s.b.n];
-    const uint64_t tail_w = (bytes & 3u) ? bytes >> 2 : ~uint64_t(0);
-    const uint32_t cs = p.s.b.chunk_shift;
-    for (uint64_t w = gtid(); w < nwork; w += uint64_t(gridDim.x) * blockDim.x) {
-        Chunk c;
-        if (!chunk_of<K, false>(p.s, w, c) || p.s.b.stream_status[c.i] != MH_OK) continue;
-        if (obase[w + 1] == obase[w]) continue;                                   // a lane that produces nothing writes nothing
-        const uint64_t w0 = (p.s.b.sym_off[c.i] >> cs) + c.i;
-        SpliceOut so;
-        so.o = obase[w] - obase[w0];
-        so.bit = cbase[w] - cbase[w0];
-        so.ocs = cs;
-        so.on = p.out != nullptr;
-        so.slice = p.out_index ? p.out_index + (p.sp.out_sym_off[c.i] >> cs) + c.i : nullptr;
-        uint32_t dctx = splice_tstart(cu, c, sctx);
-        uint64_t bit0;
-        const BitSrc src = mhb::stream_src(p.s.b.payload, p.s.b.pay_off[c.i], c.nb, bit0);
-        BitCursor bc;
-        bc.init(src, bit0 + c.start);
-        dec.stream(p.s, c.i);
-        BitWriter bw;
-        if (so.on) bw.init(reinterpret_cast<uint32_t *>(p.out), tail, tail_w, uint64_t(p.out_off[c.i]) * 8u + so.bit);
-        uint32_t ctx = c.ctx, used = 0;
-        bool bad = false;
-        for (uint32_t t = 0; t < c.nsym && !bad; ++t) {            // (the stream passed: bad stays false)
-            const uint32_t sym = dec.next(p.s, src, bc, ctx, used, bad);
             const bool coded = cu.step(t, [&] {
                 for (uint32_t j = 0; j < cu.rep_len; ++j) so.put<DLDS>(E, bw, dctx, cu.rep[j]);
             });
@@ -1514,15 +1238,16 @@ __global__ __launch_bounds__((Dec<K, false>::NT)) void splice_tidx_emit_kernel(S
     }
 }
 
-// Index-free, one lane per stream (splice_walk_kernel)
-template <Model K, bool DLDS, bool EMIT>
-__global__ __launch_bounds__((Dec<K, false>::NT)) void splice_twalk_kernel(SpliceTableParams p, uint32_t lds_at, uint32_t *tail, int *status,
-                                                                         const int *stop) {
+// Index-free, one lane per stream (recode_walk_kernel).  EMIT = false: the verdict, the stream's symbols into sym_off[i] and
+// its output symbols into out_sym_off[i] (both scanned next), its dst bits and dropped symbols; true: codes and index entries.
+template <Model K, bool DLDS, bool EMIT, bool TABLE>
+__global__ __launch_bounds__((Dec<K, false>::NT)) void splice_walk_kernel(SpParams<TABLE> p, uint32_t lds_at, uint32_t *tail, int *status,
+                                                                        const int *stop) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     if (stopped(stop)) return;
     Dec<K, false> dec(p.s, smem);
     const Enc<DLDS, false> E(p.dst, smem, lds_at);
-    TCut cu(p);
+    Cut<TABLE> cu(p);
     const uint64_t n = p.s.b.n;
     const uint64_t bytes = EMIT ? p.out_off[n] : 0;
     const uint64_t tail_w = (bytes & 3u) ? bytes >> 2 : ~uint64_t(0);
@@ -1697,26 +1422,27 @@ hipError_t launch_rc(Params<EDIT> p, size_t lds_tables, void *d_ws, hipStream_t 
     return hipGetLastError();
 }
 
-// the splice: rep's bytes of LDS lie where launch_rc puts the edit's map
-template <Model K, bool DLDS>
-hipError_t launch_sp(SpliceParams p, size_t lds_tables, void *d_ws, size_t ws_bytes, hipStream_t st) {
+// the splice: no LDS beyond the tables and the destination's image.  TABLE: the look-back pre-pass runs on every indexed
+// call, so the launches depend on indexed versus index-free alone; !TABLE: it runs when rep_len == 0.
+template <Model K, bool DLDS, bool TABLE>
+hipError_t launch_sp(SpParams<TABLE> p, size_t lds_tables, void *d_ws, size_t ws_bytes, hipStream_t st) {
     constexpr int NT = Dec<K, false>::NT, PER_CU = Dec<K, false>::PER_CU;
-    size_t lds = lds_tables + (DLDS ? (p.dst.ctx_mask ? 65536 : 256) : 0);
+    const size_t lds = lds_tables + (DLDS ? (p.dst.ctx_mask ? 65536 : 256) : 0);
     const uint32_t lds_at = uint32_t(lds_tables);
-    p.sp.rep_lds = p.sp.rep_len && lds + 256 <= size_t(LDS_MAX) ? 1u : 0u;
-    if (p.sp.rep_lds) lds += 256;
     if (K == Model::Shared) {
-        hipError_t attr = mhk::allow_lds(reinterpret_cast<const void *>(splice_idx_len_kernel<K, DLDS>), LDS_MAX);
-        if (attr == hipSuccess) attr = mhk::allow_lds(reinterpret_cast<const void *>(splice_idx_emit_kernel<K, DLDS>), LDS_MAX);
-        if (attr == hipSuccess) attr = mhk::allow_lds(reinterpret_cast<const void *>(splice_walk_kernel<K, DLDS, false>), LDS_MAX);
-        if (attr == hipSuccess) attr = mhk::allow_lds(reinterpret_cast<const void *>(splice_walk_kernel<K, DLDS, true>), LDS_MAX);
-        if (attr == hipSuccess) attr = mhk::allow_lds(reinterpret_cast<const void *>(splice_back_kernel<K>), LDS_MAX);
+        hipError_t attr = mhk::allow_lds(reinterpret_cast<const void *>(splice_idx_len_kernel<K, DLDS, TABLE>), LDS_MAX);
+        if (attr == hipSuccess) attr = mhk::allow_lds(reinterpret_cast<const void *>(splice_idx_emit_kernel<K, DLDS, TABLE>), LDS_MAX);
+        if (attr == hipSuccess) attr = mhk::allow_lds(reinterpret_cast<const void *>(splice_walk_kernel<K, DLDS, false, TABLE>), LDS_MAX);
+        if (attr == hipSuccess) attr = mhk::allow_lds(reinterpret_cast<const void *>(splice_walk_kernel<K, DLDS, true, TABLE>), LDS_MAX);
+        if (attr == hipSuccess) attr = mhk::allow_lds(reinterpret_cast<const void *>(splice_back_kernel<K, TABLE>), LDS_MAX);
         if (attr != hipSuccess) return attr;
     }
     unsigned char *ws = static_cast<unsigned char *>(d_ws);
     const uint64_t n = p.s.b.n;
     const uint64_t nw = p.s.b.index ? mhb::work_items(n, p.s.b.sym_total, 1u << p.s.b.chunk_shift) : 0;
-    const SpliceLayout L = splice_layout(n, nw, 0);
+    uint64_t nr = 1;                                                  // table entries: price[2k], price[2k + 1]
+    if constexpr (TABLE) nr = p.tb.n_reps;
+    const SpliceLayout L = splice_table_layout(n, nw, 0, nr);         // (one entry lays out as splice_layout)
     p.sp.span_cap = (ws_bytes - L.off_sctx) / 4;
     int *status = reinterpret_cast<int *>(ws), *stop = status + 1;
     uint32_t *tail = reinterpret_cast<uint32_t *>(ws + TAIL_AT);
@@ -1729,19 +1455,23 @@ hipError_t launch_sp(SpliceParams p, size_t lds_tables, void *d_ws, size_t ws_by
     hipError_t e = hipMemsetAsync(ws, 0, 64, st);
     if (e == hipSuccess && nw) e = hipMemsetAsync(ws + L.off_bits, 0, L.off_price - L.off_bits, st);   // chunk bits, output symbols, dropped counts
     if (e != hipSuccess) return e;
+    const dim3 span_grid(grid_for(uint64_t(1) << 40, 256, 8));
     hipLaunchKernelGGL(splice_check_kernel, grid_threads(n + 1, 256), dim3(256), 0, st, p, status, stop);
-    hipLaunchKernelGGL(recode_spans_kernel, dim3(grid_for(uint64_t(1) << 40, 256, 8)), dim3(256), 0, st, spans_view(p), status, stop);
-    hipLaunchKernelGGL(splice_price_kernel, dim3(1), dim3(256), 0, st, p, price);
+    if constexpr (!TABLE) hipLaunchKernelGGL(recode_spans_kernel, span_grid, dim3(256), 0, st, spans_view(p), status, stop);
+    hipLaunchKernelGGL(splice_price_kernel<TABLE>, dim3(uint32_t(nr < 1 ? 1 : (nr > 65536 ? 65536 : nr))), dim3(256), 0, st, p, price, status, stop);
+    if constexpr (TABLE) hipLaunchKernelGGL(splice_spans_kernel, span_grid, dim3(256), 0, st, p, status, stop);   // (behind the table's checks)
     if (p.s.b.index) {
-        if (!p.sp.rep_len)
-            hipLaunchKernelGGL((splice_back_kernel<K>), dim3(grid_for(uint64_t(1) << 40, NT, PER_CU)), dim3(NT), lds_tables, st, p, sctx, status, stop);
-        hipLaunchKernelGGL((splice_idx_len_kernel<K, DLDS>), dim3(grid_for(nw, NT, PER_CU)), dim3(NT), lds, st, p, nw, lds_at, cbits, csyms, cdrop,
-                           sctx, price, status, stop);
+        if (TABLE || !p.sp.rep_len)
+            hipLaunchKernelGGL((splice_back_kernel<K, TABLE>), dim3(grid_for(uint64_t(1) << 40, NT, PER_CU)), dim3(NT), lds_tables, st, p, sctx, status,
+                               stop);
+        hipLaunchKernelGGL((splice_idx_len_kernel<K, DLDS, TABLE>), dim3(grid_for(nw, NT, PER_CU)), dim3(NT), lds, st, p, nw, lds_at, cbits, csyms,
+                           cdrop, sctx, price, status, stop);
         hipLaunchKernelGGL(splice_comb_kernel, grid_threads(nw + 1, 256), dim3(256), 0, st, p, nw, cbits, csyms, cdrop, stop);
         if ((e = scan_exclusive(cbits, nw + 1, sums, stop, st)) != hipSuccess) return e;
         if ((e = scan_exclusive(csyms, nw + 1, sums, stop, st)) != hipSuccess) return e;
     } else {
-        hipLaunchKernelGGL((splice_walk_kernel<K, DLDS, false>), dim3(grid_for(n + 1, NT, PER_CU)), dim3(NT), lds, st, p, lds_at, tail, status, stop);
+        hipLaunchKernelGGL((splice_walk_kernel<K, DLDS, false, TABLE>), dim3(grid_for(n + 1, NT, PER_CU)), dim3(NT), lds, st, p, lds_at, tail, status,
+                           stop);
         if ((e = scan_exclusive(p.s.b.sym_off, n + 1, sums, stop, st)) != hipSuccess) return e;
         if ((e = scan_exclusive(p.sp.out_sym_off, n + 1, sums, stop, st)) != hipSuccess) return e;
     }
@@ -1751,103 +1481,38 @@ hipError_t launch_sp(SpliceParams p, size_t lds_tables, void *d_ws, size_t ws_by
     if (p.out) hipLaunchKernelGGL(recode_zero_kernel, dim3(grid_for(p.cap / 4 + 1, 256, 8)), dim3(256), 0, st, p, status, stop, tail);
     if (p.s.b.index) {
         if (p.out || p.out_index)
-            hipLaunchKernelGGL((splice_idx_emit_kernel<K, DLDS>), dim3(grid_for(nw, NT, PER_CU)), dim3(NT), lds, st, p, nw, lds_at, cbits, csyms, sctx,
-                               tail, stop);
+            hipLaunchKernelGGL((splice_idx_emit_kernel<K, DLDS, TABLE>), dim3(grid_for(nw, NT, PER_CU)), dim3(NT), lds, st, p, nw, lds_at, cbits, csyms,
+                               sctx, tail, stop);
     } else if (p.out || p.out_index) {
-        hipLaunchKernelGGL((splice_walk_kernel<K, DLDS, true>), dim3(grid_for(n + 1, NT, PER_CU)), dim3(NT), lds, st, p, lds_at, tail, status, stop);
+        hipLaunchKernelGGL((splice_walk_kernel<K, DLDS, true, TABLE>), dim3(grid_for(n + 1, NT, PER_CU)), dim3(NT), lds, st, p, lds_at, tail, status,
+                           stop);
     }
     if (p.out) hipLaunchKernelGGL(recode_tail_kernel, dim3(1), dim3(1), 0, st, p, tail, stop);
     return hipGetLastError();
 }
 
-// the table splice: launch_sp with the table's kernels; no LDS beyond the tables and the destination's image.  The look-back
-// pre-pass runs on every indexed call, so the launches depend on indexed versus index-free alone.
-template <Model K, bool DLDS>
-hipError_t launch_spt(const SpliceTableParams &p0, size_t lds_tables, void *d_ws, size_t ws_bytes, hipStream_t st) {
-    constexpr int NT = Dec<K, false>::NT, PER_CU = Dec<K, false>::PER_CU;
-    SpliceTableParams p = p0;
-    const SpliceParams &ps = p;
-    const size_t lds = lds_tables + (DLDS ? (p.dst.ctx_mask ? 65536 : 256) : 0);
-    const uint32_t lds_at = uint32_t(lds_tables);
-    if (K == Model::Shared) {
-        hipError_t attr = mhk::allow_lds(reinterpret_cast<const void *>(splice_tidx_len_kernel<K, DLDS>), LDS_MAX);
-        if (attr == hipSuccess) attr = mhk::allow_lds(reinterpret_cast<const void *>(splice_tidx_emit_kernel<K, DLDS>), LDS_MAX);
-        if (attr == hipSuccess) attr = mhk::allow_lds(reinterpret_cast<const void *>(splice_twalk_kernel<K, DLDS, false>), LDS_MAX);
-        if (attr == hipSuccess) attr = mhk::allow_lds(reinterpret_cast<const void *>(splice_twalk_kernel<K, DLDS, true>), LDS_MAX);
-        if (attr == hipSuccess) attr = mhk::allow_lds(reinterpret_cast<const void *>(splice_tback_kernel<K>), LDS_MAX);
-        if (attr != hipSuccess) return attr;
-    }
-    unsigned char *ws = static_cast<unsigned char *>(d_ws);
-    const uint64_t n = p.s.b.n;
-    const uint64_t nw = p.s.b.index ? mhb::work_items(n, p.s.b.sym_total, 1u << p.s.b.chunk_shift) : 0;
-    const SpliceLayout L = splice_table_layout(n, nw, 0, p.tb.n_reps);
-    p.sp.span_cap = (ws_bytes - L.off_sctx) / 4;
-    int *status = reinterpret_cast<int *>(ws), *stop = status + 1;
-    uint32_t *tail = reinterpret_cast<uint32_t *>(ws + TAIL_AT);
-    auto *cbits = reinterpret_cast<unsigned long long *>(ws + L.off_bits);
-    auto *csyms = reinterpret_cast<unsigned long long *>(ws + L.off_syms);
-    auto *cdrop = reinterpret_cast<uint32_t *>(ws + L.off_drop);
-    auto *price = reinterpret_cast<uint32_t *>(ws + L.off_price);
-    auto *sums = reinterpret_cast<unsigned long long *>(ws + L.off_sums);
-    auto *sctx = reinterpret_cast<uint32_t *>(ws + L.off_sctx);
-    hipError_t e = hipMemsetAsync(ws, 0, 64, st);
-    if (e == hipSuccess && nw) e = hipMemsetAsync(ws + L.off_bits, 0, L.off_price - L.off_bits, st);   // chunk bits, output symbols, dropped counts
-    if (e != hipSuccess) return e;
-    const uint64_t nr = p.tb.n_reps;
-    hipLaunchKernelGGL(splice_check_kernel, grid_threads(n + 1, 256), dim3(256), 0, st, ps, status, stop);
-    hipLaunchKernelGGL(splice_tprice_kernel, dim3(uint32_t(nr < 1 ? 1 : (nr > 65536 ? 65536 : nr))), dim3(256), 0, st, p, price, status, stop);
-    hipLaunchKernelGGL(splice_tspans_kernel, dim3(grid_for(uint64_t(1) << 40, 256, 8)), dim3(256), 0, st, p, status, stop);
-    if (p.s.b.index) {
-        hipLaunchKernelGGL((splice_tback_kernel<K>), dim3(grid_for(uint64_t(1) << 40, NT, PER_CU)), dim3(NT), lds_tables, st, p, sctx, status, stop);
-        hipLaunchKernelGGL((splice_tidx_len_kernel<K, DLDS>), dim3(grid_for(nw, NT, PER_CU)), dim3(NT), lds, st, p, nw, lds_at, cbits, csyms, cdrop,
-                           sctx, price, status, stop);
-        hipLaunchKernelGGL(splice_comb_kernel, grid_threads(nw + 1, 256), dim3(256), 0, st, ps, nw, cbits, csyms, cdrop, stop);
-        if ((e = scan_exclusive(cbits, nw + 1, sums, stop, st)) != hipSuccess) return e;
-        if ((e = scan_exclusive(csyms, nw + 1, sums, stop, st)) != hipSuccess) return e;
-    } else {
-        hipLaunchKernelGGL((splice_twalk_kernel<K, DLDS, false>), dim3(grid_for(n + 1, NT, PER_CU)), dim3(NT), lds, st, p, lds_at, tail, status, stop);
-        if ((e = scan_exclusive(p.s.b.sym_off, n + 1, sums, stop, st)) != hipSuccess) return e;
-        if ((e = scan_exclusive(p.sp.out_sym_off, n + 1, sums, stop, st)) != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(splice_sizes_kernel, grid_threads(n + 1, 256), dim3(256), 0, st, ps, cbits, csyms, stop);
-    if ((e = scan_exclusive(p.out_off, n + 1, sums, stop, st)) != hipSuccess) return e;
-    if (p.out_index) hipLaunchKernelGGL(splice_cap_kernel, dim3(1), dim3(1), 0, st, ps, status, stop);
-    if (p.out) hipLaunchKernelGGL(recode_zero_kernel, dim3(grid_for(p.cap / 4 + 1, 256, 8)), dim3(256), 0, st, ps, status, stop, tail);
-    if (p.s.b.index) {
-        if (p.out || p.out_index)
-            hipLaunchKernelGGL((splice_tidx_emit_kernel<K, DLDS>), dim3(grid_for(nw, NT, PER_CU)), dim3(NT), lds, st, p, nw, lds_at, cbits, csyms,
-                               sctx, tail, stop);
-    } else if (p.out || p.out_index) {
-        hipLaunchKernelGGL((splice_twalk_kernel<K, DLDS, true>), dim3(grid_for(n + 1, NT, PER_CU)), dim3(NT), lds, st, p, lds_at, tail, status, stop);
-    }
-    if (p.out) hipLaunchKernelGGL(recode_tail_kernel, dim3(1), dim3(1), 0, st, ps, tail, stop);
-    return hipGetLastError();
+// the branches of launch_recode_edit, each with the splice in place of the edit
+template <bool TABLE>
+hipError_t launch_splice(const SpParams<TABLE> &p, Model model, void *d_ws, size_t ws_bytes, hipStream_t st) {
+    if (model == Model::Shared2 || p.dst.ctx_mask == 0xFFFFu) return hipErrorInvalidValue;
+    if (model == Model::Set)
+        return p.dst.ctx_mask ? launch_sp<Model::Set, false, TABLE>(p, 0, d_ws, ws_bytes, st)
+                              : launch_sp<Model::Set, true, TABLE>(p, 0, d_ws, ws_bytes, st);
+    const size_t lds = mhb::tables_lds(p.s.b);
+    if (lds > size_t(LDS_MAX)) return hipErrorInvalidValue;
+    const size_t img = p.dst.ctx_mask ? 65536 : 256;
+    return lds + img <= size_t(LDS_MAX) ? launch_sp<Model::Shared, true, TABLE>(p, lds, d_ws, ws_bytes, st)
+                                        : launch_sp<Model::Shared, false, TABLE>(p, lds, d_ws, ws_bytes, st);
 }
 
 }  // namespace
 
-// the branches of launch_recode_splice, each with the table
 hipError_t launch_recode_splice_table(const SpliceTableParams &p, Model model, void *d_ws, size_t ws_bytes, hipStream_t st) {
-    if (model == Model::Shared2 || p.dst.ctx_mask == 0xFFFFu) return hipErrorInvalidValue;
-    if (model == Model::Set)
-        return p.dst.ctx_mask ? launch_spt<Model::Set, false>(p, 0, d_ws, ws_bytes, st) : launch_spt<Model::Set, true>(p, 0, d_ws, ws_bytes, st);
-    const size_t lds = mhb::tables_lds(p.s.b);
-    if (lds > size_t(LDS_MAX)) return hipErrorInvalidValue;
-    const size_t img = p.dst.ctx_mask ? 65536 : 256;
-    return lds + img <= size_t(LDS_MAX) ? launch_spt<Model::Shared, true>(p, lds, d_ws, ws_bytes, st)
-                                        : launch_spt<Model::Shared, false>(p, lds, d_ws, ws_bytes, st);
+    return launch_splice<true>(p, model, d_ws, ws_bytes, st);
 }
 
-// the branches of launch_recode_edit, each with the splice in place of the edit
 hipError_t launch_recode_splice(const SpliceParams &p, Model model, void *d_ws, size_t ws_bytes, hipStream_t st) {
-    if (model == Model::Shared2 || p.dst.ctx_mask == 0xFFFFu) return hipErrorInvalidValue;
-    if (model == Model::Set)
-        return p.dst.ctx_mask ? launch_sp<Model::Set, false>(p, 0, d_ws, ws_bytes, st) : launch_sp<Model::Set, true>(p, 0, d_ws, ws_bytes, st);
-    const size_t lds = mhb::tables_lds(p.s.b);
-    if (lds > size_t(LDS_MAX)) return hipErrorInvalidValue;
-    const size_t img = p.dst.ctx_mask ? 65536 : 256;
-    return lds + img <= size_t(LDS_MAX) ? launch_sp<Model::Shared, true>(p, lds, d_ws, ws_bytes, st)
-                                        : launch_sp<Model::Shared, false>(p, lds, d_ws, ws_bytes, st);
+    return launch_splice<false>(p, model, d_ws, ws_bytes, st);
 }
 
 hipError_t launch_histogram_coded(const HistParams &p, Model model, void *d_ws, hipStream_t st) {

@@ -306,6 +306,31 @@ def test_a_malformed_list_and_a_damaged_stream_fail_alone(mhc, msgs, sources, ds
         assert np.array_equal(slices_of(got["index"], got["out_sym_off"], CHUNK, ok), slices_of(clean["index"], clean["out_sym_off"], CHUNK, ok)), what
 
 
+@pytest.mark.parametrize("rep_len", [0, 10])
+@pytest.mark.parametrize("indexed", [True, False])
+def test_an_empty_span_fails_its_stream_alone(mhc, msgs, sources, dsts, indexed, rep_len):
+    """begin == end is the one rule by which this call differs from the table's, where it inserts: here it is malformed.  An
+    undamaged batch, the empty span between two good ones in the middle stream: that stream alone is MH_ERR_ARG and gives
+    what an empty message gives, nothing; every other stream is the reference's, exactly."""
+    src, dst, rep = sources["o1"], dsts["other"], REPS[rep_len]
+    n, mid = len(msgs), 4
+    lists = [[], [(0, 1)], [(1, 2)], [(10, 13)], [(0, 2), (100, 100), (254, 256)], [(0, 2), (254, 257)], [(200, 600)], [(5, 6), (250, 300), (300, 520)]]
+    assert len(msgs[mid]) == 256 and mid == n // 2
+    got = splice(src, dst, rep, *span_lists(lists), indexed)
+    what = (indexed, rep_len)
+    assert got["status"].tolist() == [mhc.MH_ERR_ARG if i == mid else mhc.MH_OK for i in range(n)] and got["rc"] != mhc.MH_OK, (what, got["status"])
+    lists[mid] = []
+    y = splice_ref.apply(src.msgs, *span_lists(lists), rep)
+    y[mid] = b""
+    ref = recode_ref.recode(y, oracle_of(dst), src.chunk)
+    r_pay, r_off, r_nb, r_drop = recode_ref.packed(ref)
+    oso = splice_ref.offsets(y)
+    assert np.array_equal(got["out_sym_off"], oso), (what, got["out_sym_off"], oso)
+    assert np.array_equal(got["out_off"], r_off) and np.array_equal(got["nbits"], r_nb) and np.array_equal(got["dropped"], r_drop), what
+    assert np.array_equal(got["payload"], r_pay), what
+    assert np.array_equal(slices_of(got["index"], oso, CHUNK), np.concatenate([r[3] for r in ref])), what
+
+
 def test_bad_span_offsets_stop_the_call(mhc, msgs, sources, dsts):
     src = sources["o1"]
     span_off, spans = span_lists([[(0, 1)] for _ in msgs])
@@ -342,6 +367,41 @@ def test_prefilled_workspace_and_outputs(mhc, msgs, sources, dsts, byte):
             y, ref, packed = expect(src, dst, REPS[rep_len], span_off, spans)
             for indexed in (True, False):
                 check_exact(mhc, src, splice(src, dst, REPS[rep_len], span_off, spans, indexed), y, ref, packed, (byte, rep_len, indexed))
+
+
+@pytest.mark.parametrize("indexed", [True, False])
+def test_a_deletion_fits_a_prefilled_workspace_of_exactly_the_stated_size(mhc, msgs, sources, dsts, indexed):
+    """rep_len = 0 on the runs of touching spans, the call with the look-back pre-pass and its per-span contexts at the end of
+    the workspace: mh_dev_recode_splice_workspace bytes, every one 0xFF, and not a byte more.  The results are the reference's
+    and the guard behind the workspace is intact."""
+    lib, D = mhc.lib(), mhc.DeviceBuffer
+    src, dst = sources["o1"], dsts["other"]
+    per, _ = placements(msgs)["runs of touching spans"]
+    span_off, spans = span_lists(per)
+    y, ref, packed = expect(src, dst, b"", span_off, spans)
+    oso = splice_ref.offsets(y)
+    n, total, G = len(msgs), int(src.sym_off[-1]) if indexed else 0, 256
+    pl = np.concatenate([src.payload, np.zeros(64, dtype=np.uint8)])
+    d_pl, d_po, d_nb = D(pl.nbytes, pl), D(src.pay_off.nbytes, src.pay_off), D(src.nbits.nbytes, src.nbits)
+    d_so = D(src.sym_off.nbytes, src.sym_off if indexed else np.full(n + 1, 0xA5A5A5A5A5A5A5A5, dtype=np.uint64))
+    idx = np.asarray(src.index, dtype=np.uint64)
+    d_idx, d_sof, d_sp = D(idx.nbytes, idx), D(span_off.nbytes, span_off), D(spans.nbytes, spans)
+    wsb = lib.mh_dev_recode_splice_workspace(n, total, CHUNK if indexed else 0, len(spans))
+    d_ws = D(wsb + G, np.concatenate([np.full(wsb, 0xFF, dtype=np.uint8), np.full(G, 0x5A, dtype=np.uint8)]))
+    cap, nidx = int(packed[1][n]), int(oso[n]) // CHUNK + n
+    d_out = D(cap + 64, np.full(cap + 64, 0xA5, dtype=np.uint8))
+    d_oo, d_onb, d_oso, d_oi, d_dr = [D(k * 8, np.full(k, 0xA5A5A5A5A5A5A5A5, dtype=np.uint64)) for k in (n + 1, n, n + 1, nidx, n)]
+    d_st = D(n * 4, np.full(n, 99, dtype=np.int32))
+    rc = lib.mh_dev_recode_splice_batch(src.model.handle, dst.handle, d_pl.ptr, d_po.ptr, d_nb.ptr, n, int(src.pay_off[-1]), 0x20, d_so.ptr, total,
+                                        d_idx.ptr if indexed else None, CHUNK, d_sof.ptr, d_sp.ptr, None, 0, d_out.ptr, cap, d_oo.ptr, d_onb.ptr,
+                                        d_oso.ptr, d_oi.ptr, nidx, d_dr.ptr, d_st.ptr, d_ws.ptr, wsb, None)
+    assert rc == mhc.MH_OK and lib.mh_dev_status(d_ws.ptr, None) == mhc.MH_OK and not d_st.download(np.int32)[:n].any()
+    assert (d_ws.download(np.uint8)[wsb:wsb + G] == 0x5A).all(), "bytes written behind the workspace"
+    assert np.array_equal(d_oo.download(np.uint64)[:n + 1], packed[1]) and np.array_equal(d_onb.download(np.uint64)[:n], packed[2])
+    assert np.array_equal(d_dr.download(np.uint64)[:n], packed[3]) and np.array_equal(d_oso.download(np.uint64)[:n + 1], oso)
+    assert np.array_equal(d_so.download(np.uint64)[:n + 1], src.sym_off)
+    assert np.array_equal(d_out.download(np.uint8)[:cap], packed[0]) and (d_out.download(np.uint8)[cap:] == 0xA5).all()
+    assert np.array_equal(slices_of(d_oi.download(np.uint64)[:nidx], oso, CHUNK), np.concatenate([r[3] for r in ref]))
 
 
 def test_host_form(mhc, msgs, sources, dsts):
@@ -466,6 +526,7 @@ def test_the_same_workspace_twice_gives_identical_results(mhc, msgs, sources, ds
         assert np.array_equal(slices_of(d_oi.download(np.uint64), oso, CHUNK), np.concatenate([r[3] for r in ref])), rep_len
 
 
+# (every source reads the replacement from L2 since the splice is one kernel family; here the destination's image does too)
 def test_a_source_whose_tables_fill_the_lds_reads_the_replacement_from_l2(mhc):
     """The source model of tests/test_gpu_edit.py whose tables leave 144 bytes of LDS: neither the order-0 image nor the
     replacement's 256 bytes fit, and both come from L2."""
