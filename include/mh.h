@@ -1463,6 +1463,120 @@ int mh_recode_splice_table_batch(const mh_model *src, const mh_model *dst, const
                                  int32_t *stream_status);
 
 /* ---------------------------------------------------------------------------------------------------------------------
+ * ORDER 2 IN EDITING AND SPLICING (extension, parity unpinned) — the masked re-code and the table splice with an order-2
+ * model on a side, so that a store kept under order 2 is scrubbed as it is searched: compressed.  The contract is that of
+ * mh_dev_recode_edit_batch and mh_dev_recode_splice_table_batch word for word, except for what follows.  x is stream i's
+ * message as the source's batch decoder returns it (mh_dev_decode_batch_o2 for an order-2 source).
+ *   - Orders.  Edit: source -> destination 2 -> 2, 2 -> 1, 2 -> 0, 1 -> 2, 0 -> 2.  Table splice: an order-2 source under any
+ *     destination (2 -> 2, 2 -> 1, 2 -> 0).  Order 0/1 on both sides stays with the calls above and is MH_ERR_ARG here, as is
+ *     a table splice of an order-0/1 source under an order-2 destination (left out: mh_dev_recode_batch_o2 to order 2 first
+ *     is one call).  Shared models only: src and dst are `const mh_model *` members and the calls have no model-set
+ *     parameter, so a set cannot be passed and there is no _each form.
+ *   - Output.  For every stream whose verdict is MH_OK, byte for byte what mh_dev_encode_batch_o2(dst) writes for y under an
+ *     order-2 dst and what mh_dev_encode_batch(dst) writes under an order-0/1 dst: offsets, bit counts, payload and index
+ *     slices in dst's entry format, for the splice also d_out_sym_off and an index laid out by output positions.  An order-2
+ *     entry carries (y[s - 2], y[s - 1]) of the OUTPUT; prev0 stands for every position in front of 0.
+ *   - Drops.  A symbol whose (context, symbol) has no code under dst is skipped and counted in d_dropped[i] while the
+ *     destination context advances; the bytes of a replacement and both of its edges are included.
+ *   - Equivalence.  With an empty span list or the identity map every output equals mh_dev_recode_batch_o2's byte for byte.
+ *   - A single replacement is a one-entry table with every tag 0: there is no separate single-replacement call.
+ *   - Everything else is the calls' above: the batch decoders' verdicts and failed streams left empty; MH_ERR_ARG for a
+ *     stream whose span list is malformed or whose tag is out of range, for that stream alone; both capacity rules and
+ *     count-only mode; index-free sources through the one-lane walk, which writes d_sym_off; no allocation, no host
+ *     synchronisation, and a number of launches that depends on indexed versus index-free alone.
+ *   - Workspaces.  mh_dev_recode_edit_batch_o2_workspace is mh_dev_recode_batch_o2_workspace: the edit call's and 8 bytes
+ *     per chunk number for the seam of an order-0/1 source.  mh_dev_recode_splice_table_batch_o2_workspace is
+ *     mh_dev_recode_splice_table_workspace: nothing new per chunk or per span.
+ * The argument block.  The two device calls take one struct instead of thirty positional parameters: a call with more than
+ * thirty positional pointers of a few types is the least safe thing in this header, and the declarations with a positional
+ * `void *stream` are a closed, counted set whose stream order one test module drives; the calls that take a block are
+ * counted and driven on a non-default stream by a module of their own.  The members are the positional calls' parameters
+ * under the same names and in the same order, the batch's as one nested mh_coded_batch_args.  struct_size must equal
+ * sizeof of the struct, else MH_ERR_ARG (the block can grow later); a NULL block is MH_ERR_ARG; without a device
+ * MH_ERR_NO_DEVICE.  Order rules, struct_size, a NULL d_map and the required pointers are refused before any launch.
+ * Host forms mh_recode_edit_batch_o2 and mh_recode_splice_table_batch_o2: positional, host pointers, the rules checked
+ * before a device is touched, the rest as mh_recode_edit_batch and mh_recode_splice_table_batch, except that EVERY index-free
+ * batch is indexed first (mh_index_batch_o2 for an order-2 source, mh_index_batch for an order-0/1 source; with the chunk
+ * size of out_index when the call writes one) and edited as an indexed batch: sym_off is written as before, and a valid batch
+ * is never refused for a stream over MH_BATCH_WALK_MAX_BITS.
+ * Left out: the CLI (--order2 with --recode or --redact stays refused); model sets; the table splice of an order-0/1 source
+ * under an order-2 destination; and everything the table splice leaves out: appending at len(x), replacements longer than
+ * MH_SPLICE_MAX_REP, back-references or any replacement computed from the matched bytes.
+ * --------------------------------------------------------------------------------------------------------------------- */
+typedef struct mh_coded_batch_args {
+    const uint8_t *d_payload;
+    const uint64_t *d_pay_off;
+    const uint64_t *d_nbits;
+    size_t n_streams;
+    uint64_t pay_total;
+    uint8_t prev0;
+    uint64_t *d_sym_off;
+    uint64_t sym_total;
+    const uint64_t *d_index;
+    uint32_t chunk_symbols;
+} mh_coded_batch_args;
+typedef struct mh_recode_edit_o2_args {
+    uint32_t struct_size;
+    const mh_model *src;
+    const mh_model *dst;
+    mh_coded_batch_args batch;
+    const uint64_t *d_span_off;
+    const uint64_t *d_spans;
+    const uint8_t *d_map;
+    uint8_t *d_out_payload;
+    size_t cap;
+    uint64_t *d_out_off;
+    uint64_t *d_out_nbits;
+    uint64_t *d_out_index;
+    uint64_t *d_dropped;
+    int32_t *d_stream_status;
+    void *d_ws;
+    size_t ws_bytes;
+    void *stream;
+} mh_recode_edit_o2_args;
+typedef struct mh_recode_splice_o2_args {
+    uint32_t struct_size;
+    const mh_model *src;
+    const mh_model *dst;
+    mh_coded_batch_args batch;
+    const uint64_t *d_span_off;
+    const uint64_t *d_spans;
+    const uint32_t *d_span_tag;
+    const uint64_t *d_rep_off;
+    const uint8_t *d_rep_bytes;
+    size_t n_reps;
+    uint8_t *d_out_payload;
+    size_t cap;
+    uint64_t *d_out_off;
+    uint64_t *d_out_nbits;
+    uint64_t *d_out_sym_off;
+    uint64_t *d_out_index;
+    uint64_t index_cap;
+    uint64_t *d_dropped;
+    int32_t *d_stream_status;
+    void *d_ws;
+    size_t ws_bytes;
+    void *stream;
+} mh_recode_splice_o2_args;
+size_t mh_dev_recode_edit_batch_o2_workspace(size_t n_streams, uint64_t sym_total, uint32_t chunk_symbols);
+size_t mh_dev_recode_splice_table_batch_o2_workspace(size_t n_streams, uint64_t sym_total, uint32_t chunk_symbols,
+                                                     uint64_t n_spans, size_t n_reps);
+int mh_dev_recode_edit_batch_o2(const mh_recode_edit_o2_args *a);
+int mh_dev_recode_splice_table_batch_o2(const mh_recode_splice_o2_args *a);
+int mh_recode_edit_batch_o2(const mh_model *src, const mh_model *dst, const uint8_t *payload, const uint64_t *pay_off,
+                            const uint64_t *nbits, size_t n_streams, uint8_t prev0, uint64_t *sym_off, const uint64_t *index,
+                            uint32_t chunk_symbols, const uint64_t *span_off, const uint64_t *spans, const uint8_t *map,
+                            uint8_t *out_payload, size_t cap, uint64_t *out_off, uint64_t *out_nbits, uint64_t *out_index,
+                            uint64_t *dropped, int32_t *stream_status);
+int mh_recode_splice_table_batch_o2(const mh_model *src, const mh_model *dst, const uint8_t *payload, const uint64_t *pay_off,
+                                    const uint64_t *nbits, size_t n_streams, uint8_t prev0, uint64_t *sym_off,
+                                    const uint64_t *index, uint32_t chunk_symbols, const uint64_t *span_off,
+                                    const uint64_t *spans, const uint32_t *span_tag, const uint64_t *rep_off,
+                                    const uint8_t *rep_bytes, size_t n_reps, uint8_t *out_payload, size_t cap,
+                                    uint64_t *out_off, uint64_t *out_nbits, uint64_t *out_sym_off, uint64_t *out_index,
+                                    uint64_t index_cap, uint64_t *dropped, int32_t *stream_status);
+
+/* ---------------------------------------------------------------------------------------------------------------------
  * SEGMENT STATES OF INDEX-FREE ORDER-2 BATCHES (extension, parity unpinned) — the _o2 twins of the segment-state calls of
  * the next section, for a batch coded under one shared order-2 model (what mh_dev_encode_batch_o2 writes, stored without
  * its sidecar index).  Same arguments, layouts, workspace arithmetic, launch sequence and guarantees as the twins; what

@@ -78,6 +78,8 @@ EXPORTS = [
     "mh_spans_from_hits_tagged", "mh_dev_spans_from_hits_tagged_workspace", "mh_dev_spans_from_hits_tagged",
     "mh_dev_recode_splice_table_workspace", "mh_dev_recode_splice_table_batch", "mh_dev_recode_splice_table_each",
     "mh_recode_splice_table_batch",
+    "mh_dev_recode_edit_batch_o2_workspace", "mh_dev_recode_splice_table_batch_o2_workspace", "mh_dev_recode_edit_batch_o2",
+    "mh_dev_recode_splice_table_batch_o2", "mh_recode_edit_batch_o2", "mh_recode_splice_table_batch_o2",
 ]
 FIND_MAX_POSITIONS = 64                    # include/mh.h MH_FIND_MAX_POSITIONS
 FIND_FOLD_ASCII = 1                        # include/mh.h MH_FIND_FOLD_ASCII
@@ -95,6 +97,49 @@ class MhError(RuntimeError):
         self.status = status
         msg = lib().mh_strerror(status).decode() if _lib is not None else str(status)
         super().__init__("%s: %s (%d)" % (what, msg, status))
+
+
+class CodedBatchArgs(C.Structure):
+    """include/mh.h mh_coded_batch_args: the batch description inside the argument blocks below."""
+    _fields_ = [("d_payload", C.c_void_p), ("d_pay_off", C.c_void_p), ("d_nbits", C.c_void_p), ("n_streams", C.c_size_t),
+                ("pay_total", C.c_uint64), ("prev0", C.c_uint8), ("d_sym_off", C.c_void_p), ("sym_total", C.c_uint64),
+                ("d_index", C.c_void_p), ("chunk_symbols", C.c_uint32)]
+
+
+class RecodeEditO2Args(C.Structure):
+    """include/mh.h mh_recode_edit_o2_args: the parameters of mh_dev_recode_edit_batch under the same names, in the same order."""
+    _fields_ = [("struct_size", C.c_uint32), ("src", C.c_void_p), ("dst", C.c_void_p), ("batch", CodedBatchArgs),
+                ("d_span_off", C.c_void_p), ("d_spans", C.c_void_p), ("d_map", C.c_void_p), ("d_out_payload", C.c_void_p),
+                ("cap", C.c_size_t), ("d_out_off", C.c_void_p), ("d_out_nbits", C.c_void_p), ("d_out_index", C.c_void_p),
+                ("d_dropped", C.c_void_p), ("d_stream_status", C.c_void_p), ("d_ws", C.c_void_p), ("ws_bytes", C.c_size_t),
+                ("stream", C.c_void_p)]
+
+
+class RecodeSpliceO2Args(C.Structure):
+    """include/mh.h mh_recode_splice_o2_args: the parameters of mh_dev_recode_splice_table_batch, same names, same order."""
+    _fields_ = [("struct_size", C.c_uint32), ("src", C.c_void_p), ("dst", C.c_void_p), ("batch", CodedBatchArgs),
+                ("d_span_off", C.c_void_p), ("d_spans", C.c_void_p), ("d_span_tag", C.c_void_p), ("d_rep_off", C.c_void_p),
+                ("d_rep_bytes", C.c_void_p), ("n_reps", C.c_size_t), ("d_out_payload", C.c_void_p), ("cap", C.c_size_t),
+                ("d_out_off", C.c_void_p), ("d_out_nbits", C.c_void_p), ("d_out_sym_off", C.c_void_p), ("d_out_index", C.c_void_p),
+                ("index_cap", C.c_uint64), ("d_dropped", C.c_void_p), ("d_stream_status", C.c_void_p), ("d_ws", C.c_void_p),
+                ("ws_bytes", C.c_size_t), ("stream", C.c_void_p)]
+
+
+def args_block(cls, *a):
+    """An argument block of class `cls` from the positional parameters of the order-0/1 twin call: struct_size set, the members
+    filled in order, the batch's ten into the nested block."""
+    want = sum(len(CodedBatchArgs._fields_) if typ is CodedBatchArgs else 1 for _, typ in cls._fields_[1:])
+    if len(a) != want:
+        raise TypeError("%s takes %d members behind struct_size, %d given" % (cls.__name__, want, len(a)))
+    blk = cls()
+    blk.struct_size = C.sizeof(cls)
+    it = iter(a)
+    for name, typ in cls._fields_[1:]:
+        into, names = (blk.batch, [f[0] for f in CodedBatchArgs._fields_]) if typ is CodedBatchArgs else (blk, [name])
+        for k in names:
+            v = next(it)
+            setattr(into, k, v.value if isinstance(v, C.c_void_p) else v)
+    return blk
 
 
 _lib = None
@@ -371,6 +416,14 @@ def lib():
         for fn in (l.mh_dev_recode_splice_table_batch, l.mh_dev_recode_splice_table_each):
             fn.argtypes = l.mh_dev_recode_batch.argtypes[:12] + [vp, vp, vp, vp, vp, sz, vp, sz, vp, vp, vp, vp, u64, vp, vp, vp, sz, vp]
         l.mh_recode_splice_table_batch.argtypes = l.mh_recode_batch.argtypes[:10] + [vp, vp, vp, vp, vp, sz, vp, sz, vp, vp, vp, vp, u64, vp, vp]
+        l.mh_dev_recode_edit_batch_o2_workspace.argtypes = [sz, u64, u32]
+        l.mh_dev_recode_edit_batch_o2_workspace.restype = sz
+        l.mh_dev_recode_splice_table_batch_o2_workspace.argtypes = [sz, u64, u32, u64, sz]
+        l.mh_dev_recode_splice_table_batch_o2_workspace.restype = sz
+        l.mh_dev_recode_edit_batch_o2.argtypes = [C.POINTER(RecodeEditO2Args)]
+        l.mh_dev_recode_splice_table_batch_o2.argtypes = [C.POINTER(RecodeSpliceO2Args)]
+        l.mh_recode_edit_batch_o2.argtypes = l.mh_recode_edit_batch.argtypes
+        l.mh_recode_splice_table_batch_o2.argtypes = l.mh_recode_splice_table_batch.argtypes
         _lib = l
     return _lib
 
@@ -969,8 +1022,9 @@ def _span_arrays(span_off, spans, byte_map):
     return so, sp, m
 
 
-def _dev_recode_edit(fn, src, dst, payload, pay_off, nbits, byte_map, span_off, spans, prev0, sym_off, index, chunk_symbols, **kw):
-    """One mh_dev_recode_edit_batch / _each call through _dev_recode: the same guards around every output, the same dict."""
+def _dev_recode_edit(fn, src, dst, payload, pay_off, nbits, byte_map, span_off, spans, prev0, sym_off, index, chunk_symbols, ws_fn=None, **kw):
+    """One mh_dev_recode_edit_batch / _each call through _dev_recode: the same guards around every output, the same dict.
+    ws_fn: the sizing call (default mh_dev_recode_edit_workspace)."""
     so, sp, m = _span_arrays(span_off, spans, byte_map)
     d_so = DeviceBuffer(so.nbytes, so) if so is not None else None
     d_sp = DeviceBuffer(max(sp.nbytes, 16), sp if sp.size else None)
@@ -979,7 +1033,7 @@ def _dev_recode_edit(fn, src, dst, payload, pay_off, nbits, byte_map, span_off, 
     def call(*a):
         return fn(*a[:12], d_so.ptr if d_so else None, d_sp.ptr, d_map.ptr, *a[12:])
 
-    return _dev_recode(call, src, dst, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols, ws_fn=lib().mh_dev_recode_edit_workspace, **kw)
+    return _dev_recode(call, src, dst, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols, ws_fn=ws_fn or lib().mh_dev_recode_edit_workspace, **kw)
 
 
 # ---- splicing batches (include/mh.h, "SPLICING BATCHES") -------------------------------------------------------------------
@@ -997,13 +1051,14 @@ def _rep_table(reps):
 
 
 def _dev_recode_splice(fn, src, dst, payload, pay_off, nbits, rep, span_off, spans, prev0, sym_off, index, chunk_symbols, cap=None,
-                       count_only=False, want_index=True, index_cap=None, n_spans=None, table=None, n_reps=None):
+                       count_only=False, want_index=True, index_cap=None, n_spans=None, table=None, n_reps=None, ws_fn=None):
     """One mh_dev_recode_splice_batch / _each call with guards around every output, as _dev_recode puts them.  cap None or
     index_cap None: a count-only call first, then one with exactly out_off[n] bytes and (out_sym_off[n] // chunk) + n entries of
     room.  Returns the dict of _dev_recode and out_sym_off[n + 1].  Asserts that nothing changed outside out_off[n] payload
     bytes, the n + 1 offsets, the n lengths and counts and the index slices, laid out by out_sym_off, of the streams that
     passed and did not become empty.  table = (span_tag, reps): fn is a _splice_table call, `rep` is unused, and the
-    workspace is mh_dev_recode_splice_table_workspace's (n_reps: what it is sized for, else the table's)."""
+    workspace is mh_dev_recode_splice_table_workspace's (n_reps: what it is sized for, else the table's; ws_fn: another sizing
+    call with the same parameters)."""
     l = lib()
     n, pay_total, d_pl, d_po, d_nb, so, d_idx = _dev_source(payload, pay_off, nbits, sym_off, index)
     indexed = index is not None
@@ -1031,7 +1086,7 @@ def _dev_recode_splice(fn, src, dst, payload, pay_off, nbits, rep, span_off, spa
     def call(room, with_payload, nidx):
         d_so = DeviceBuffer((n + 1 + G) * 8, np.concatenate([so if indexed else np.full(n + 1, F, dtype=np.uint64), np.full(G, F, dtype=np.uint64)]))
         if table is not None:
-            wsb = l.mh_dev_recode_splice_table_workspace(n, st, chunk_symbols if indexed else 0, ns, nreps if n_reps is None else n_reps)
+            wsb = (ws_fn or l.mh_dev_recode_splice_table_workspace)(n, st, chunk_symbols if indexed else 0, ns, nreps if n_reps is None else n_reps)
         else:
             wsb = l.mh_dev_recode_splice_workspace(n, st, chunk_symbols if indexed else 0, ns)
         d_ws = DeviceBuffer(wsb)
@@ -1514,8 +1569,40 @@ class Model:
         """mh_recode_splice_table_batch (host form): recode_splice_batch with a replacement per span; the same dict."""
         return self.recode_splice_batch(dst, payload, pay_off, nbits, b"", span_off, spans, table=(span_tag, reps), **kw)
 
+    # ---- order 2 in editing and splicing (include/mh.h, "ORDER 2 IN EDITING AND SPLICING") -----------------------------------
+    def dev_recode_edit_batch_o2(self, dst, payload, pay_off, nbits, byte_map, span_off=None, spans=None, prev0=PREV0, sym_off=None, index=None,
+                                 chunk_symbols=0, **kw):
+        """One mh_dev_recode_edit_batch_o2 call (this model or `dst` is order 2): dev_recode_edit_batch's arguments, dict and guards."""
+        l = lib()
+
+        def call(*a):
+            return l.mh_dev_recode_edit_batch_o2(C.byref(args_block(RecodeEditO2Args, *a)))
+
+        return _dev_recode_edit(call, self._h, dst.handle, payload, pay_off, nbits, byte_map, span_off, spans, prev0, sym_off, index, chunk_symbols,
+                                ws_fn=l.mh_dev_recode_edit_batch_o2_workspace, **kw)
+
+    def dev_recode_splice_table_batch_o2(self, dst, payload, pay_off, nbits, span_tag, reps, span_off, spans, prev0=PREV0, sym_off=None,
+                                         index=None, chunk_symbols=0, **kw):
+        """One mh_dev_recode_splice_table_batch_o2 call (this model is order 2): dev_recode_splice_table_batch's arguments, dict
+        and guards."""
+        l = lib()
+
+        def call(*a):
+            return l.mh_dev_recode_splice_table_batch_o2(C.byref(args_block(RecodeSpliceO2Args, *a)))
+
+        return _dev_recode_splice(call, self._h, dst.handle, payload, pay_off, nbits, b"", span_off, spans, prev0, sym_off, index, chunk_symbols,
+                                  table=(span_tag, reps), ws_fn=l.mh_dev_recode_splice_table_batch_o2_workspace, **kw)
+
+    def recode_edit_batch_o2(self, dst, payload, pay_off, nbits, byte_map, **kw):
+        """mh_recode_edit_batch_o2 (host form; this model or `dst` is order 2): recode_edit_batch's arguments and results."""
+        return self.recode_edit_batch(dst, payload, pay_off, nbits, byte_map, o2=True, **kw)
+
+    def recode_splice_table_batch_o2(self, dst, payload, pay_off, nbits, span_tag, reps, span_off, spans, **kw):
+        """mh_recode_splice_table_batch_o2 (host form; this model is order 2): recode_splice_table_batch's arguments and results."""
+        return self.recode_splice_batch(dst, payload, pay_off, nbits, b"", span_off, spans, table=(span_tag, reps), o2=True, **kw)
+
     def recode_splice_batch(self, dst, payload, pay_off, nbits, rep, span_off, spans, prev0=PREV0, sym_off=None, index=None, chunk_symbols=0,
-                            cap=None, want_index=True, index_cap=None, check=True, table=None):
+                            cap=None, want_index=True, index_cap=None, check=True, table=None, o2=False):
         """mh_recode_splice_batch (host form): the dict of _recode_batch and out_sym_off[n + 1].  cap / index_cap None: room for
         the worst case, every span one byte wide and replaced.  table = (span_tag, reps): mh_recode_splice_table_batch."""
         l = lib()
@@ -1540,6 +1627,8 @@ class Model:
             bound += (sp.size // 2) * SPLICE_MAX_REP
             how = (tg.ctypes.data if tg.size else pay_off.ctypes.data, roff.ctypes.data, _ptr(rb), len(roff) - 1)
             fn, name = l.mh_recode_splice_table_batch, "mh_recode_splice_table_batch"
+            if o2:
+                fn, name = l.mh_recode_splice_table_batch_o2, "mh_recode_splice_table_batch_o2"
         else:
             how = (_ptr(r), r.size)
             fn, name = l.mh_recode_splice_batch, "mh_recode_splice_batch"
@@ -1565,15 +1654,16 @@ class Model:
                     out_sym_off=oso, rc=rc)
 
     def recode_edit_batch(self, dst, payload, pay_off, nbits, byte_map, span_off=None, spans=None, prev0=PREV0, sym_off=None, index=None,
-                          chunk_symbols=0, cap=None, want_index=True, check=True):
-        """mh_recode_edit_batch (host form): recode_batch with the edit; the arguments and results of _recode_batch."""
+                          chunk_symbols=0, cap=None, want_index=True, check=True, o2=False):
+        """mh_recode_edit_batch (host form): recode_batch with the edit; the arguments and results of _recode_batch.  o2:
+        mh_recode_edit_batch_o2."""
         so, sp, m = _span_arrays(span_off, spans, byte_map)
-        fn = lib().mh_recode_edit_batch
+        fn = lib().mh_recode_edit_batch_o2 if o2 else lib().mh_recode_edit_batch
 
         def call(*a):
             return fn(*a[:10], so.ctypes.data if so is not None else None, _ptr(sp), m.ctypes.data, *a[10:])
 
-        return self._recode_batch(call, "mh_recode_edit_batch", dst, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols, cap, want_index,
+        return self._recode_batch(call, "mh_recode_edit_batch_o2" if o2 else "mh_recode_edit_batch", dst, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols, cap, want_index,
                                   check)
 
     def recode_batch(self, dst, payload, pay_off, nbits, prev0=PREV0, sym_off=None, index=None, chunk_symbols=0, cap=None, want_index=True,

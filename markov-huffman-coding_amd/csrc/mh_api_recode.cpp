@@ -1,7 +1,7 @@
 // mh_api_recode.cpp — the re-coding calls of the C ABI (include/mh.h, "RE-CODING BATCHES" and the re-coding part of "ORDER 2
 // IN SEARCH AND RE-CODING"): the training histogram of a compressed batch and the batch coded again under another model,
 // under one shared source model of any order or a model set (kernels: mh_recode.hip), with the edits of "EDITING BATCHES" and
-// the splices of "SPLICING BATCHES", and the host-buffer forms.  The order
+// the splices of "SPLICING BATCHES", their order-2 forms of "ORDER 2 IN EDITING AND SPLICING", and the host-buffer forms.  The order
 // rules of an entry point are in that entry point; everything behind them is here once.
 #include "mh_api_reader.hpp"
 #include "mh_recode.h"
@@ -45,7 +45,7 @@ int histogram_coded(const mh_model *m, const mh_model_set *set, int order, const
 
 // behind the order rules of mh_dev_recode_batch, _each, _batch_o2 and the _edit calls: m or set is the source; a.sym_off is
 // written by an index-free re-code; seam: the workspace of the _o2 call, which has room for the seam's arrays; ed: the edit
-// of an _edit call (order 0/1 on both sides)
+// of an _edit call (the _o2 edit passes seam as well)
 int recode(const mh_model *m, const mh_model_set *set, const mh_model *dst, bool seam, const mhr::Edit *ed, const CodedBatch &a,
            uint8_t *d_out_payload, size_t cap, uint64_t *d_out_off, uint64_t *d_out_nbits, uint64_t *d_out_index, uint64_t *d_dropped,
            int32_t *d_stream_status, void *d_ws, size_t ws_bytes, void *stream) {
@@ -104,10 +104,15 @@ struct SpliceArgs {
     size_t n_reps = 0;
 };
 
-// what a _splice entry point refuses before anything else: order 2 on either side (m: null under a set), the replacement
-int splice_args(const mh_model *m, const mh_model_set *set, size_t n, const mh_model *dst, const SpliceArgs &s) {
-    if (set ? n != set->d.n : !order01(m)) return MH_ERR_ARG;
-    if (!order01(dst)) return MH_ERR_ARG;
+// what a _splice entry point refuses before anything else: order 2 on either side (m: null under a set), the replacement;
+// o2 (the _o2 call): an order-2 source under any destination instead
+int splice_args(const mh_model *m, const mh_model_set *set, size_t n, const mh_model *dst, const SpliceArgs &s, bool o2 = false) {
+    if (o2) {
+        if (!order2(m) || !order012(dst)) return MH_ERR_ARG;
+    } else {
+        if (set ? n != set->d.n : !order01(m)) return MH_ERR_ARG;
+        if (!order01(dst)) return MH_ERR_ARG;
+    }
     if (s.rep_len > MH_SPLICE_MAX_REP || (s.rep_len && !s.rep) || !s.span_off || !s.out_sym_off) return MH_ERR_ARG;
     if (s.table && (!s.span_tag || !s.rep_off)) return MH_ERR_ARG;
     return MH_OK;
@@ -145,8 +150,8 @@ int splice(const mh_model *m, const mh_model_set *set, const mh_model *dst, cons
     if (!dst->d_len8 || !dst->d_code64) return MH_ERR_NO_DEVICE;
     p.dst.len8 = dst->d_len8;
     p.dst.code64 = reinterpret_cast<const unsigned long long *>(dst->d_code64);
-    p.dst.enc64 = nullptr;
-    p.dst.ctx_mask = dst->type ? 0xFFu : 0u;
+    p.dst.enc64 = dst->type == 2 ? reinterpret_cast<const unsigned long long *>(dst->d_enc64) : nullptr;
+    p.dst.ctx_mask = dst->type == 2 ? 0xFFFFu : (dst->type ? 0xFFu : 0u);
     p.sp.span_off = reinterpret_cast<const unsigned long long *>(s.span_off);
     p.sp.spans = reinterpret_cast<const unsigned long long *>(s.spans);
     p.sp.rep = s.rep;
@@ -173,15 +178,18 @@ size_t recode_workspace(size_t n_streams, uint64_t sym_total, uint32_t chunk_sym
 // The host forms behind their order rules: the argument checks in the order of mh_decode_batch, then an index-free batch of
 // an order-0/1 source with a stream over the walk cap (index_first) is indexed first and re-coded as an indexed batch, with the
 // chunk size of out_index when the call writes one; a stream the indexing fails (idx_st) has no symbols, so no payload.  An
-// index-free batch is sized for symbol_bound symbols.
+// index-free batch is sized for symbol_bound symbols.  always_index (the _o2 editing forms): every index-free batch is indexed
+// first, whatever its streams' lengths.
 int host_args(const mh_model *src, const mh_model *dst, CodedBatch &a, bool index_first_ok, const uint64_t *out_off, const uint64_t *out_nbits,
-              const uint64_t *out_index, uint64_t *sym_off, std::vector<uint64_t> &own_idx, std::vector<int32_t> &idx_st) {
+              const uint64_t *out_index, uint64_t *sym_off, std::vector<uint64_t> &own_idx, std::vector<int32_t> &idx_st,
+              bool always_index = false) {
     if (!out_off || (!out_nbits && a.n) || !sym_off) return MH_ERR_ARG;
     int rc = host_batch_args(a, a.index || out_index);
     if (rc != MH_OK) return rc;
     if (!have_device()) return MH_ERR_NO_DEVICE;
     if (src->max_len > mh::MAX_CODE_BITS || dst->max_len > mh::MAX_CODE_BITS) return MH_ERR_CODE_TOO_LONG;
-    if (index_first_ok && over_walk_cap(a) && (rc = index_first(src, a, out_index != nullptr, sym_off, own_idx, idx_st)) != MH_OK) return rc;
+    const bool first = always_index ? !a.index && a.n > 0 : over_walk_cap(a);
+    if (index_first_ok && first && (rc = index_first(src, a, out_index != nullptr, sym_off, own_idx, idx_st)) != MH_OK) return rc;
     if (!a.index) a.sym_total = symbol_bound(src->min_len, a.nbits, a.n);
     return MH_OK;
 }
@@ -259,6 +267,79 @@ struct HostRecode {
         return first;
     }
 };
+
+// mh_recode_edit_batch and mh_recode_edit_batch_o2 behind their order rules (seam: the _o2 call)
+int host_edit(bool seam, const mh_model *src, const mh_model *dst, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits,
+              size_t n_streams, uint8_t prev0, uint64_t *sym_off, const uint64_t *index, uint32_t chunk_symbols, const uint64_t *span_off,
+              const uint64_t *spans, const uint8_t *map, uint8_t *out_payload, size_t cap, uint64_t *out_off, uint64_t *out_nbits,
+              uint64_t *out_index, uint64_t *dropped, int32_t *stream_status) {
+    if (!map) return MH_ERR_ARG;
+    if (span_off && (!offsets_ok(span_off, n_streams) || (span_off[n_streams] && !spans))) return MH_ERR_ARG;
+    // (a span's positions do not depend on the index that an over-cap batch gets first)
+    CodedBatch a{payload, pay_off, nbits, n_streams, 0, prev0, sym_off, 0, index, chunk_symbols};
+    std::vector<uint64_t> own_idx;
+    std::vector<int32_t> idx_st;
+    int rc = host_args(src, dst, a, true, out_off, out_nbits, out_index, sym_off, own_idx, idx_st, seam);
+    if (rc != MH_OK) return rc;
+    DevBuf d_soff, d_sp, d_map;
+    const size_t nsp = span_off ? size_t(span_off[n_streams]) : 0;
+    HIP_TRY(d_soff.alloc(span_off ? (n_streams + 1) * 8 : 0));
+    HIP_TRY(d_sp.alloc(nsp * 16));
+    HIP_TRY(d_map.alloc(256));
+    if (span_off) HIP_TRY(hipMemcpy(d_soff.p, span_off, (n_streams + 1) * 8, hipMemcpyHostToDevice));
+    if (nsp) HIP_TRY(hipMemcpy(d_sp.p, spans, nsp * 16, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_map.p, map, 256, hipMemcpyHostToDevice));
+    const mhr::Edit ed = edit_of(span_off ? d_soff.as<uint64_t>() : nullptr, d_sp.as<uint64_t>(), d_map.as<uint8_t>());
+    HostRecode hr;
+    rc = hr.run(seam, &ed, src, dst, a, sym_off, out_payload != nullptr, cap, out_off, out_nbits, out_index);
+    if (rc != MH_OK) return rc;
+    if ((rc = hr.payload(out_payload, out_off[n_streams])) != MH_OK || (rc = hr.slices(out_index)) != MH_OK) return rc;
+    return hr.finish(idx_st, dropped, stream_status);
+}
+
+
+// mh_recode_splice_table_batch and mh_recode_splice_table_batch_o2 (o2: that call's order rule)
+int host_splice_table(bool o2, const mh_model *src, const mh_model *dst, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits,
+                      size_t n_streams, uint8_t prev0, uint64_t *sym_off, const uint64_t *index, uint32_t chunk_symbols, const uint64_t *span_off,
+                      const uint64_t *spans, const uint32_t *span_tag, const uint64_t *rep_off, const uint8_t *rep_bytes, size_t n_reps,
+                      uint8_t *out_payload, size_t cap, uint64_t *out_off, uint64_t *out_nbits, uint64_t *out_sym_off, uint64_t *out_index,
+                      uint64_t index_cap, uint64_t *dropped, int32_t *stream_status) {
+    SpliceArgs s{span_off, spans, nullptr, 0, out_sym_off, out_index ? index_cap : 0, 0, true, span_tag, rep_off, rep_bytes, n_reps};
+    int rc = splice_args(src, nullptr, n_streams, dst, s, o2);
+    if (rc != MH_OK) return rc;
+    if (!offsets_ok(span_off, n_streams) || (span_off[n_streams] && !spans)) return MH_ERR_ARG;
+    // the table, as the device checks it, before a device is touched
+    if (rep_off[0] != 0 || (span_off[n_streams] && !n_reps)) return MH_ERR_ARG;
+    for (size_t k = 0; k < n_reps; ++k)
+        if (rep_off[k + 1] < rep_off[k] || rep_off[k + 1] - rep_off[k] > MH_SPLICE_MAX_REP) return MH_ERR_ARG;
+    const size_t rep_total = size_t(rep_off[n_reps]);
+    if (rep_total && !rep_bytes) return MH_ERR_ARG;
+    CodedBatch a{payload, pay_off, nbits, n_streams, 0, prev0, sym_off, 0, index, chunk_symbols};
+    std::vector<uint64_t> own_idx;
+    std::vector<int32_t> idx_st;
+    rc = host_args(src, dst, a, true, out_off, out_nbits, out_index, sym_off, own_idx, idx_st, o2);
+    if (rc != MH_OK) return rc;
+    DevBuf d_soff, d_sp, d_tag, d_roff, d_rep;
+    s.n_spans = span_off[n_streams];
+    HIP_TRY(d_soff.alloc((n_streams + 1) * 8));
+    HIP_TRY(d_sp.alloc(size_t(s.n_spans) * 16));
+    HIP_TRY(d_tag.alloc(size_t(s.n_spans) * 4 + 4));
+    HIP_TRY(d_roff.alloc((n_reps + 1) * 8));
+    HIP_TRY(d_rep.alloc(rep_total));
+    HIP_TRY(hipMemcpy(d_soff.p, span_off, (n_streams + 1) * 8, hipMemcpyHostToDevice));
+    if (s.n_spans) HIP_TRY(hipMemcpy(d_sp.p, spans, size_t(s.n_spans) * 16, hipMemcpyHostToDevice));
+    if (s.n_spans) HIP_TRY(hipMemcpy(d_tag.p, span_tag, size_t(s.n_spans) * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_roff.p, rep_off, (n_reps + 1) * 8, hipMemcpyHostToDevice));
+    if (rep_total) HIP_TRY(hipMemcpy(d_rep.p, rep_bytes, rep_total, hipMemcpyHostToDevice));
+    s.span_off = d_soff.as<uint64_t>(); s.spans = d_sp.as<uint64_t>(); s.span_tag = d_tag.as<uint32_t>();
+    s.rep_off = d_roff.as<uint64_t>(); s.rep_bytes = rep_total ? d_rep.as<uint8_t>() : nullptr;
+    HostRecode hr;
+    hr.spl = &s;
+    rc = hr.run(false, nullptr, src, dst, a, sym_off, out_payload != nullptr, cap, out_off, out_nbits, out_index);
+    if (rc != MH_OK) return rc;
+    if ((rc = hr.payload(out_payload, out_off[n_streams])) != MH_OK || (rc = hr.slices(out_index)) != MH_OK) return rc;
+    return hr.finish(idx_st, dropped, stream_status);
+}
 
 }  // namespace
 
@@ -478,28 +559,9 @@ int mh_recode_edit_batch(const mh_model *src, const mh_model *dst, const uint8_t
                          size_t n_streams, uint8_t prev0, uint64_t *sym_off, const uint64_t *index, uint32_t chunk_symbols,
                          const uint64_t *span_off, const uint64_t *spans, const uint8_t *map, uint8_t *out_payload, size_t cap, uint64_t *out_off,
                          uint64_t *out_nbits, uint64_t *out_index, uint64_t *dropped, int32_t *stream_status) {
-    if (!order01(src) || !order01(dst) || !map) return MH_ERR_ARG;
-    if (span_off && (!offsets_ok(span_off, n_streams) || (span_off[n_streams] && !spans))) return MH_ERR_ARG;
-    // (a span's positions do not depend on the index that an over-cap batch gets first)
-    CodedBatch a{payload, pay_off, nbits, n_streams, 0, prev0, sym_off, 0, index, chunk_symbols};
-    std::vector<uint64_t> own_idx;
-    std::vector<int32_t> idx_st;
-    int rc = host_args(src, dst, a, true, out_off, out_nbits, out_index, sym_off, own_idx, idx_st);
-    if (rc != MH_OK) return rc;
-    DevBuf d_soff, d_sp, d_map;
-    const size_t nsp = span_off ? size_t(span_off[n_streams]) : 0;
-    HIP_TRY(d_soff.alloc(span_off ? (n_streams + 1) * 8 : 0));
-    HIP_TRY(d_sp.alloc(nsp * 16));
-    HIP_TRY(d_map.alloc(256));
-    if (span_off) HIP_TRY(hipMemcpy(d_soff.p, span_off, (n_streams + 1) * 8, hipMemcpyHostToDevice));
-    if (nsp) HIP_TRY(hipMemcpy(d_sp.p, spans, nsp * 16, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_map.p, map, 256, hipMemcpyHostToDevice));
-    const mhr::Edit ed = edit_of(span_off ? d_soff.as<uint64_t>() : nullptr, d_sp.as<uint64_t>(), d_map.as<uint8_t>());
-    HostRecode hr;
-    rc = hr.run(false, &ed, src, dst, a, sym_off, out_payload != nullptr, cap, out_off, out_nbits, out_index);
-    if (rc != MH_OK) return rc;
-    if ((rc = hr.payload(out_payload, out_off[n_streams])) != MH_OK || (rc = hr.slices(out_index)) != MH_OK) return rc;
-    return hr.finish(idx_st, dropped, stream_status);
+    if (!order01(src) || !order01(dst)) return MH_ERR_ARG;
+    return host_edit(false, src, dst, payload, pay_off, nbits, n_streams, prev0, sym_off, index, chunk_symbols, span_off, spans, map, out_payload, cap,
+                     out_off, out_nbits, out_index, dropped, stream_status);
 }
 
 /* ----------------------------------------------------------------------------------------------------- splice */
@@ -610,41 +672,9 @@ int mh_recode_splice_table_batch(const mh_model *src, const mh_model *dst, const
                                  const uint8_t *rep_bytes, size_t n_reps, uint8_t *out_payload, size_t cap, uint64_t *out_off,
                                  uint64_t *out_nbits, uint64_t *out_sym_off, uint64_t *out_index, uint64_t index_cap, uint64_t *dropped,
                                  int32_t *stream_status) {
-    SpliceArgs s{span_off, spans, nullptr, 0, out_sym_off, out_index ? index_cap : 0, 0, true, span_tag, rep_off, rep_bytes, n_reps};
-    int rc = splice_args(src, nullptr, n_streams, dst, s);
-    if (rc != MH_OK) return rc;
-    if (!offsets_ok(span_off, n_streams) || (span_off[n_streams] && !spans)) return MH_ERR_ARG;
-    // the table, as the device checks it, before a device is touched
-    if (rep_off[0] != 0 || (span_off[n_streams] && !n_reps)) return MH_ERR_ARG;
-    for (size_t k = 0; k < n_reps; ++k)
-        if (rep_off[k + 1] < rep_off[k] || rep_off[k + 1] - rep_off[k] > MH_SPLICE_MAX_REP) return MH_ERR_ARG;
-    const size_t rep_total = size_t(rep_off[n_reps]);
-    if (rep_total && !rep_bytes) return MH_ERR_ARG;
-    CodedBatch a{payload, pay_off, nbits, n_streams, 0, prev0, sym_off, 0, index, chunk_symbols};
-    std::vector<uint64_t> own_idx;
-    std::vector<int32_t> idx_st;
-    rc = host_args(src, dst, a, true, out_off, out_nbits, out_index, sym_off, own_idx, idx_st);
-    if (rc != MH_OK) return rc;
-    DevBuf d_soff, d_sp, d_tag, d_roff, d_rep;
-    s.n_spans = span_off[n_streams];
-    HIP_TRY(d_soff.alloc((n_streams + 1) * 8));
-    HIP_TRY(d_sp.alloc(size_t(s.n_spans) * 16));
-    HIP_TRY(d_tag.alloc(size_t(s.n_spans) * 4 + 4));
-    HIP_TRY(d_roff.alloc((n_reps + 1) * 8));
-    HIP_TRY(d_rep.alloc(rep_total));
-    HIP_TRY(hipMemcpy(d_soff.p, span_off, (n_streams + 1) * 8, hipMemcpyHostToDevice));
-    if (s.n_spans) HIP_TRY(hipMemcpy(d_sp.p, spans, size_t(s.n_spans) * 16, hipMemcpyHostToDevice));
-    if (s.n_spans) HIP_TRY(hipMemcpy(d_tag.p, span_tag, size_t(s.n_spans) * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_roff.p, rep_off, (n_reps + 1) * 8, hipMemcpyHostToDevice));
-    if (rep_total) HIP_TRY(hipMemcpy(d_rep.p, rep_bytes, rep_total, hipMemcpyHostToDevice));
-    s.span_off = d_soff.as<uint64_t>(); s.spans = d_sp.as<uint64_t>(); s.span_tag = d_tag.as<uint32_t>();
-    s.rep_off = d_roff.as<uint64_t>(); s.rep_bytes = rep_total ? d_rep.as<uint8_t>() : nullptr;
-    HostRecode hr;
-    hr.spl = &s;
-    rc = hr.run(false, nullptr, src, dst, a, sym_off, out_payload != nullptr, cap, out_off, out_nbits, out_index);
-    if (rc != MH_OK) return rc;
-    if ((rc = hr.payload(out_payload, out_off[n_streams])) != MH_OK || (rc = hr.slices(out_index)) != MH_OK) return rc;
-    return hr.finish(idx_st, dropped, stream_status);
+    return host_splice_table(false, src, dst, payload, pay_off, nbits, n_streams, prev0, sym_off, index, chunk_symbols, span_off, spans, span_tag,
+                             rep_off, rep_bytes, n_reps, out_payload, cap, out_off, out_nbits, out_sym_off, out_index, index_cap, dropped,
+                             stream_status);
 }
 
 int mh_recode_batch_o2(const mh_model *src, const mh_model *dst, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits,
@@ -732,6 +762,62 @@ int mh_recode_batch_o2(const mh_model *src, const mh_model *dst, const uint8_t *
         hr.dev_rc = (out_payload && !fits) ? MH_ERR_CAPACITY : MH_OK;
     }
     return hr.finish(idx_st, dropped, stream_status);
+}
+
+/* ------------------------------------------------------------------------ order 2 in editing and splicing */
+
+// the seam's arrays, as recode_layout(…, seam) lays them out: 8 bytes per chunk number more than the order-0/1 call
+size_t mh_dev_recode_edit_batch_o2_workspace(size_t n_streams, uint64_t sym_total, uint32_t chunk_symbols) {
+    return recode_workspace(n_streams, sym_total, chunk_symbols, true);
+}
+
+// nothing new per span or per chunk: the table splice's
+size_t mh_dev_recode_splice_table_batch_o2_workspace(size_t n_streams, uint64_t sym_total, uint32_t chunk_symbols, uint64_t n_spans, size_t n_reps) {
+    return mh_dev_recode_splice_table_workspace(n_streams, sym_total, chunk_symbols, n_spans, n_reps);
+}
+
+static CodedBatch batch_of(const mh_coded_batch_args &b) {
+    return {b.d_payload, b.d_pay_off, b.d_nbits, b.n_streams, b.pay_total, b.prev0, b.d_sym_off, b.sym_total, b.d_index, b.chunk_symbols};
+}
+
+int mh_dev_recode_edit_batch_o2(const mh_recode_edit_o2_args *a) {
+    if (!a || a->struct_size != sizeof(*a)) return MH_ERR_ARG;
+    if (!have_device()) return MH_ERR_NO_DEVICE;                      // (an order-2 model exists on a device alone)
+    if (!order012(a->src) || !order012(a->dst) || (a->src->type != 2 && a->dst->type != 2)) return MH_ERR_ARG;
+    const mhr::Edit ed = edit_of(a->d_span_off, a->d_spans, a->d_map);
+    return recode(a->src, nullptr, a->dst, true, &ed, batch_of(a->batch), a->d_out_payload, a->cap, a->d_out_off, a->d_out_nbits, a->d_out_index,
+                  a->d_dropped, a->d_stream_status, a->d_ws, a->ws_bytes, a->stream);
+}
+
+int mh_dev_recode_splice_table_batch_o2(const mh_recode_splice_o2_args *a) {
+    if (!a || a->struct_size != sizeof(*a)) return MH_ERR_ARG;
+    if (!have_device()) return MH_ERR_NO_DEVICE;                      // (an order-2 model exists on a device alone)
+    const SpliceArgs s{a->d_span_off, a->d_spans, nullptr, 0, a->d_out_sym_off, a->index_cap, 0, true, a->d_span_tag, a->d_rep_off, a->d_rep_bytes,
+                       a->n_reps};
+    const int rc = splice_args(a->src, nullptr, a->batch.n_streams, a->dst, s, true);
+    if (rc != MH_OK) return rc;
+    return splice(a->src, nullptr, a->dst, s, batch_of(a->batch), a->d_out_payload, a->cap, a->d_out_off, a->d_out_nbits, a->d_out_index, a->d_dropped,
+                  a->d_stream_status, a->d_ws, a->ws_bytes, a->stream);
+}
+
+int mh_recode_edit_batch_o2(const mh_model *src, const mh_model *dst, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits,
+                            size_t n_streams, uint8_t prev0, uint64_t *sym_off, const uint64_t *index, uint32_t chunk_symbols,
+                            const uint64_t *span_off, const uint64_t *spans, const uint8_t *map, uint8_t *out_payload, size_t cap,
+                            uint64_t *out_off, uint64_t *out_nbits, uint64_t *out_index, uint64_t *dropped, int32_t *stream_status) {
+    if (!order012(src) || !order012(dst) || (src->type != 2 && dst->type != 2)) return MH_ERR_ARG;
+    return host_edit(true, src, dst, payload, pay_off, nbits, n_streams, prev0, sym_off, index, chunk_symbols, span_off, spans, map, out_payload, cap,
+                     out_off, out_nbits, out_index, dropped, stream_status);
+}
+
+int mh_recode_splice_table_batch_o2(const mh_model *src, const mh_model *dst, const uint8_t *payload, const uint64_t *pay_off,
+                                    const uint64_t *nbits, size_t n_streams, uint8_t prev0, uint64_t *sym_off, const uint64_t *index,
+                                    uint32_t chunk_symbols, const uint64_t *span_off, const uint64_t *spans, const uint32_t *span_tag,
+                                    const uint64_t *rep_off, const uint8_t *rep_bytes, size_t n_reps, uint8_t *out_payload, size_t cap,
+                                    uint64_t *out_off, uint64_t *out_nbits, uint64_t *out_sym_off, uint64_t *out_index, uint64_t index_cap,
+                                    uint64_t *dropped, int32_t *stream_status) {
+    return host_splice_table(true, src, dst, payload, pay_off, nbits, n_streams, prev0, sym_off, index, chunk_symbols, span_off, spans, span_tag,
+                             rep_off, rep_bytes, n_reps, out_payload, cap, out_off, out_nbits, out_sym_off, out_index, index_cap, dropped,
+                             stream_status);
 }
 
 }  // extern "C"

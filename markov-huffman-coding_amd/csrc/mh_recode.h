@@ -117,7 +117,8 @@ struct SpliceParams : RecodeParams {
 
 // splice workspace: status block | per-stream status | per chunk number: destination bits (u64, W + 1, scanned in place),
 // output symbols (u64, W + 1, scanned in place), dropped symbols (u32) | the bits and drops of rep[1..] (2 x u32) | scan
-// block sums | per span: the destination context behind a deleted span (u32; written and read only when rep_len == 0).  The
+// block sums | per span: the destination context behind a deleted span (u32; written and read only when rep_len == 0; an
+// order-2 source: the last two output bytes behind a replacement shorter than two bytes).  The
 // spans come last: the call is not told their number, it takes what ws_bytes leaves behind off_sctx as its room
 struct SpliceLayout {
     size_t off_status, off_bits, off_syms, off_drop, off_price, off_sums, off_sctx, total;
@@ -183,11 +184,14 @@ inline SpanLayout span_layout(uint64_t hit_cap) {
 // takes them.  Any order of the histogram or of dst under a shared model; a model set with an order-2 side is refused.
 hipError_t launch_histogram_coded(const HistParams &p, mhb::Model model, void *d_ws, hipStream_t st);
 hipError_t launch_recode(const RecodeParams &p, mhb::Model model, void *d_ws, hipStream_t st);
-// the same with the edit applied; order 0/1 on both sides (an order-2 side is refused)
+// the same with the edit applied, any orders under a shared model (include/mh.h, "ORDER 2 IN EDITING AND SPLICING": an order-2
+// side takes the workspace of recode_layout(…, seam = true)); a model set with an order-2 destination is refused
 hipError_t launch_recode_edit(const EditParams &p, mhb::Model model, void *d_ws, hipStream_t st);
 // the splice in place of the edit; order 0/1 on both sides, p.sp.span_off not null
 hipError_t launch_recode_splice(const SpliceParams &p, mhb::Model model, void *d_ws, size_t ws_bytes, hipStream_t st);
-// the table splice: a replacement per span, insertions (begin == end) legal; order 0/1 on both sides
+// the table splice: a replacement per span, insertions (begin == end) legal; order 0/1 on both sides, or an order-2 source
+// (Shared2) under any destination, on the same workspace layout: sctx[r] then holds two bytes.  An order-0/1 source under an
+// order-2 destination is refused
 hipError_t launch_recode_splice_table(const SpliceTableParams &p, mhb::Model model, void *d_ws, size_t ws_bytes, hipStream_t st);
 // the records of a find call (ascending (stream, end, pattern)) merged into maximal spans; a total over hit_cap: the status
 // word is MHK_STATUS_CAPACITY, span_off all zeros

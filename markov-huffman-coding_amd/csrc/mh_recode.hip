@@ -187,7 +187,7 @@ template <bool DLDS, bool W> struct Enc {
     }
 };
 
-// the edit     (EDIT: include/mh.h, "EDITING BATCHES"; order 0/1 on both sides, no W / SEAM form.)  Inside its stream's spans
+// the edit     (EDIT: include/mh.h, "EDITING BATCHES" and, under W, "ORDER 2 IN EDITING AND SPLICING".)  Inside its stream's spans
 //              a lane codes map[sym] for sym.  It keeps two contexts: ctx, the true symbol, feeds dec.next and roll, so the
 //              decoder's dependent chain is what it is without the edit; dctx, the edited symbol, feeds E.at, E.put and
 //              E.entry.  A lane seeks the first span that ends behind its first position by a binary search of the stream's
@@ -198,6 +198,11 @@ template <bool DLDS, bool W> struct Enc {
 //              MH_BATCH_WALK_MAX_BITS, so a lane's own offsets stay far below 2^32 - 1, which stands for "never").  No list
 //              (span_off null): one span over everything.  The map is 256 B of LDS behind the destination's image (Edit::map_lds; read from L2 when the
 //              source's tables leave no room).
+//              Under W dctx is the last two edited bytes, rolled as ctx is.  Under the seam the lane of chunk k does not own
+//              symbol 0 of its chunk but edits it at its position and rolls it into dctx, so its first own code lies under
+//              (y[first - 1], y[first]); close is dctx behind the chunk's last symbol, head the next chunk's first symbol,
+//              edited at its own position, under close.  The map is pointwise: every lane computes the edited byte two in
+//              front itself, no lane needs a word from another.
 template <bool DLDS> __device__ __forceinline__ uint32_t map_at(const Dst &d, uint32_t lds_at) {
     return lds_at + (DLDS ? (d.ctx_mask ? 65536u : 256u) : 0u);
 }
@@ -249,13 +254,21 @@ template <> struct Spans<true> {
 };
 // the destination's context as a chunk's lane starts: the entry's byte, edited when the position in front of the chunk lies
 // in a span (a stream's first chunk starts from prev0, which is no byte of the message).  The cursor's origin is that
-// position: symbol t of the chunk is at offset t + at0(c).
-template <bool EDIT> __device__ __forceinline__ uint32_t start_dctx(Spans<EDIT> &sp, const Chunk &c) {
+// position: symbol t of the chunk is at offset t + at0(c).  An order-2 entry carries x[first - 2] and x[first - 1]: the
+// origin lies BACK = 2 positions in front of the chunk and each of the two is mapped at its own position.
+template <Model K, bool W> constexpr uint32_t BACK = Dec<K, W>::O2 ? 2u : 1u;
+template <Model K, bool W, bool EDIT> __device__ __forceinline__ uint32_t start_dctx(Spans<EDIT> &sp, const Chunk &c) {
     if (!EDIT) return c.ctx;
-    sp.seek(c.i, c.first ? c.first - 1u : 0u);
-    return c.first ? sp.edit(c.ctx, 0u) : c.ctx;
+    sp.seek(c.i, c.first ? c.first - BACK<K, W> : 0u);              // (a chunk behind the first starts at 256 or more)
+    if (!c.first) return c.ctx;
+    if constexpr (BACK<K, W> == 2u) {
+        const uint32_t hi = sp.edit(c.ctx >> 8, 0u);
+        return (hi << 8) | sp.edit(c.ctx & 0xFFu, 1u);
+    } else {
+        return sp.edit(c.ctx, 0u);
+    }
 }
-__device__ __forceinline__ uint32_t at0(const Chunk &c) { return c.first ? 1u : 0u; }
+template <Model K, bool W> __device__ __forceinline__ uint32_t at0(const Chunk &c) { return c.first ? BACK<K, W> : 0u; }
 
 // ------------------------------------------------------------------------------------------------ the kernels that never decode
 // (they read the source batch and the outputs, mhr::RecodeIO, and neither model)
@@ -641,18 +654,18 @@ __global__ __launch_bounds__((Dec<K, W>::NT)) void recode_idx_len_kernel(Params<
         bc.init(src, bit0 + c.start);
         dec.stream(p.s, c.i);
         uint32_t ctx = c.ctx, used = 0, bits = 0, drops = 0;
-        uint32_t dctx = start_dctx<EDIT>(sp, c);
+        uint32_t dctx = start_dctx<K, W, EDIT>(sp, c);
         bool bad = false;
         for (uint32_t t = 0; t < c.nsym && !bad; ++t) {
             const uint32_t sym = dec.next(p.s, src, bc, ctx, used, bad);
             if (bad) break;
+            const uint32_t dsym = sp.edit(sym, t + at0<K, W>(c));
             if (owns<SEAM<K, W>>(c, t)) {
-                const uint32_t dsym = sp.edit(sym, t + at0(c));
                 const uint32_t l = E.len(E.at(EDIT ? dctx : ctx, dsym));
                 bits += l;
                 drops += l == 0u;
-                dctx = dsym;
             }
+            if (EDIT) dctx = roll<W>(dctx, dsym);
             ctx = roll<W>(ctx, sym);
         }
         if (bad || used != c.end - c.start) { stream_fail(p.s.b, status, c.i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT); continue; }
@@ -660,12 +673,12 @@ __global__ __launch_bounds__((Dec<K, W>::NT)) void recode_idx_len_kernel(Params<
             if (!c.last) {
                 // the next chunk's first symbol, whose two context bytes only this lane knows.  No verdict: when the stream
                 // passes, the next chunk's lane decoded the same bits in the same context.
-                cclose[w] = ctx;
+                cclose[w] = EDIT ? dctx : ctx;
                 uint32_t u2 = used;
                 bool b2 = false;
                 const uint32_t sym = dec.next(p.s, src, bc, ctx, u2, b2);
                 if (!b2) {
-                    const uint32_t l = E.len(E.at(ctx, sym));
+                    const uint32_t l = E.len(E.at(EDIT ? dctx : ctx, sp.edit(sym, c.nsym + at0<K, W>(c))));
                     chead[w] = l;
                     drops += l == 0u;
                 }
@@ -720,7 +733,7 @@ __global__ __launch_bounds__((Dec<K, W>::NT)) void recode_idx_emit_kernel(Params
         const unsigned long long b0 = cbase[w];
         const uint64_t rel = b0 - cbase[(p.s.b.sym_off[c.i] >> cs) + c.i];          // relative to the stream's own payload
         const bool seam = SEAM<K, W> && c.first != 0u;                              // symbol 0 is the lane's in front
-        uint32_t dctx = start_dctx<EDIT>(sp, c);
+        uint32_t dctx = start_dctx<K, W, EDIT>(sp, c);
         if (p.out_index) p.out_index[w] = E.entry(seam ? cclose[w - 1] : (EDIT ? dctx : c.ctx), rel);
         if (!p.out) continue;
         if constexpr (!SEAM<K, W>) { if (cbase[w + 1] == b0) continue; }            // (SEAM: the lane's codes are not the chunk's)
@@ -735,17 +748,15 @@ __global__ __launch_bounds__((Dec<K, W>::NT)) void recode_idx_emit_kernel(Params
         bool bad = false;
         for (uint32_t t = 0; t < c.nsym && !bad; ++t) {            // (the stream passed: bad stays false)
             const uint32_t sym = dec.next(p.s, src, bc, ctx, used, bad);
-            if (owns<SEAM<K, W>>(c, t)) {
-                const uint32_t dsym = sp.edit(sym, t + at0(c));
-                E.put(bw, E.at(EDIT ? dctx : ctx, dsym), true);
-                dctx = dsym;
-            }
+            const uint32_t dsym = sp.edit(sym, t + at0<K, W>(c));
+            if (owns<SEAM<K, W>>(c, t)) E.put(bw, E.at(EDIT ? dctx : ctx, dsym), true);
+            if (EDIT) dctx = roll<W>(dctx, dsym);
             ctx = roll<W>(ctx, sym);
         }
         if constexpr (SEAM<K, W>) {
             if (!c.last && !bad) {
                 const uint32_t sym = dec.next(p.s, src, bc, ctx, used, bad);
-                E.put(bw, E.at(ctx, sym), !bad);
+                E.put(bw, E.at(EDIT ? dctx : ctx, sp.edit(sym, c.nsym + at0<K, W>(c))), !bad);
             }
         }
         bw.finish();
@@ -796,7 +807,7 @@ __global__ __launch_bounds__((Dec<K, W>::NT)) void recode_walk_kernel(Params<EDI
             if (bad) break;
             const uint32_t dsym = sp.edit(sym, uint32_t(k));
             const uint32_t key = E.at(EDIT ? dctx : ctx, dsym);
-            dctx = dsym;
+            if (EDIT) dctx = roll<W>(dctx, dsym);
             uint32_t l;
             if (EMIT) {
                 l = E.put(bw, key, p.out != nullptr);
@@ -818,10 +829,11 @@ __global__ __launch_bounds__((Dec<K, W>::NT)) void recode_walk_kernel(Params<EDI
 
 // ------------------------------------------------------------------------------------------------ splice
 
-// the splice   (include/mh.h, "SPLICING BATCHES" and "SPLICING WITH A REPLACEMENT TABLE"; order 0/1 on both sides.)  A span that
+// the splice   (include/mh.h, "SPLICING BATCHES" and "SPLICING WITH A REPLACEMENT TABLE": order 0/1 on both sides; "ORDER 2 IN
+//              EDITING AND SPLICING": an order-2 source under any destination, see "order 2" below.)  A span that
 //              begins inside the message is replaced by a string of another length (0 bytes: deleted), so output positions
-//              are not source positions.  A lane keeps ctx (the true symbol, for dec.next) and dctx (the last output byte),
-//              as the edit does, and walks its symbols with the cursor below.  The lane whose symbols contain a span's begin
+//              are not source positions.  A lane keeps ctx (the true symbol, for dec.next) and dctx (the last output byte;
+//              under an order-2 source the last two), as the edit does, and walks its symbols with the cursor below.  The lane whose symbols contain a span's begin
 //              owns its replacement (an insertion at a chunk boundary belongs to the lane of the chunk that starts there).
 //              Indexed source, one lane per source chunk: the length pass counts the chunk's output symbols beside its bits,
 //              a second scan turns them into output positions, and the emit pass writes a destination index entry in front
@@ -835,7 +847,8 @@ __global__ __launch_bounds__((Dec<K, W>::NT)) void recode_walk_kernel(Params<EDI
 //              read from L2, once per owned span.
 //   cursor     Spans obey begin <= end <= next begin, so several may begin at one position: step() codes the replacements of
 //              all spans that begin at the current position, in list order, before it says whether the symbol is coded.
-//   start      The destination context of a lane whose chunk starts at `first` is the last output byte in front of it.  With
+//   start      (An order-0/1 source; "order 2" below says what changes for two bytes.)  The destination context of a lane
+//              whose chunk starts at `first` is the last output byte in front of it.  With
 //              first - 1 in no span that is the entry's byte; in a span with a non-empty replacement it is that
 //              replacement's last byte; in a deleted span r it is sctx[r], which lies mid-chunk in general.
 //              splice_back_kernel finds it per span before the length pass (!TABLE: launched only when rep_len == 0; TABLE:
@@ -848,6 +861,17 @@ __global__ __launch_bounds__((Dec<K, W>::NT)) void recode_walk_kernel(Params<EDI
 //              pass.
 //   price      price[2k], price[2k + 1]: the bits and drops of entry k's bytes behind its first (splice_price_kernel, which
 //              also checks the table); the length pass prices the first byte in dctx and adds them.  !TABLE: entry 0 is rep.
+//   order 2    (SW<K>: an order-2 source, K = Shared2, under any destination; include/mh.h "ORDER 2 IN EDITING AND SPLICING";
+//              TABLE only.)  ctx and dctx are 16-bit contexts, rolled; dctx is the last TWO output bytes, of which an order-0/1
+//              destination reads the later one.  start: a replacement of two or more bytes supplies both; a shorter one has
+//              sctx[r], both bytes behind it, and splice_back_kernel serves every span shorter than two bytes with a chunk
+//              boundary F in (begin, end + 1]: at F = end + 1 x[F - 1] is the first byte behind the span and the byte in
+//              front of it the last output byte behind the replacement.  It collects the two bytes from the back: the
+//              replacement's, then those of the touching spans and insertions in front, then source bytes (the entry of the
+//              chunk at that position decoded up to it, at most twice: behind one source byte a span may touch again), prev0
+//              in front of position 0.  price: entry k's bytes from its THIRD on, triple (j - 2, j - 1, j) under the
+//              destination's mask; the lanes code the first two in dctx.
+template <Model K> constexpr bool SW = K == Model::Shared2;
 template <bool TABLE> using SpParams = std::conditional_t<TABLE, SpliceTableParams, SpliceParams>;
 template <bool TABLE> struct Cut {
     const unsigned long long *off, *sp, *rep_off;
@@ -914,11 +938,28 @@ template <bool TABLE> struct Cut {
 };
 
 // The destination context as chunk c's lane starts (see "start" above); the cursor is left at the chunk's first symbol.
-template <bool TABLE> __device__ __forceinline__ uint32_t splice_start(Cut<TABLE> &cu, const Chunk &c, const uint32_t *sctx) {
+// W: the last two output bytes.  q is the last span that begins in front of `first`.  It holds first - 1: the two bytes behind
+// its replacement, tail2(q).  It ends at first - 1 (an insertion there included): the later of those two, then the entry's
+// x[first - 1].  Else both bytes of the entry.
+template <bool W, bool TABLE> __device__ __forceinline__ uint32_t splice_start(Cut<TABLE> &cu, const Chunk &c, const uint32_t *sctx) {
     if (!c.first) { cu.start(c.i); return c.ctx; }
-    if (!cu.seek(c.i, c.first)) return c.ctx;
-    cu.fetch(cu.r);
-    return cu.rep_len ? cu.rep[cu.rep_len - 1u] : sctx[cu.r];
+    const bool in = cu.seek(c.i, c.first);
+    if constexpr (W) {
+        if (!in && !(cu.r > cu.off[c.i] && cu.sp[2 * cu.r - 1] + 1u == c.first)) return c.ctx;
+        const uint64_t q = in ? cu.r : cu.r - 1u;
+        cu.fetch(q);
+        const uint32_t t2 = cu.rep_len >= 2u ? (uint32_t(cu.rep[cu.rep_len - 2u]) << 8) | cu.rep[cu.rep_len - 1u] : sctx[q];
+        return in ? t2 : ((t2 & 0xFFu) << 8) | (c.ctx & 0xFFu);
+    } else {
+        if (!in) return c.ctx;
+        cu.fetch(cu.r);
+        return cu.rep_len ? cu.rep[cu.rep_len - 1u] : sctx[cu.r];
+    }
+}
+// the destination context behind a replacement of rep_len > 0 bytes that was entered in dctx
+template <bool W> __device__ __forceinline__ uint32_t rep_ctx(uint32_t dctx, const uint8_t *rep, uint32_t rep_len) {
+    if (!W) return rep[rep_len - 1u];
+    return ((rep_len >= 2u ? uint32_t(rep[rep_len - 2u]) : dctx & 0xFFu) << 8) | rep[rep_len - 1u];
 }
 
 // the end of span q's replacement: empty, or its last byte at base[end - 1] (splice_back_kernel asks for the byte only
@@ -966,7 +1007,8 @@ inline EditParams spans_view(const SpliceParams &p) {
 // workgroup per entry.  TABLE: rep_off[0] == 0, no decreasing offsets, no entry over MH_SPLICE_MAX_REP bytes, else
 // BATCH_STATUS_ARG and the call stops; an entry is read only when it lies inside the table's rep_off[n_reps] bytes.  !TABLE:
 // the one entry (rep, rep_len), which the call checked.
-template <bool TABLE>
+// W: from the third byte on, byte j in the context of bytes j - 2 and j - 1.
+template <bool TABLE, bool W>
 __global__ __launch_bounds__(256) void splice_price_kernel(SpParams<TABLE> p, uint32_t *price, int *status, int *stop) {
     __shared__ uint32_t acc[2];
     uint64_t nr = 1;
@@ -989,8 +1031,14 @@ __global__ __launch_bounds__(256) void splice_price_kernel(SpParams<TABLE> p, ui
         if (threadIdx.x < 2u) acc[threadIdx.x] = 0u;
         __syncthreads();
         const uint32_t j = threadIdx.x;
-        if (j >= 1u && j < len) {
-            const uint32_t l = p.dst.len8[((uint32_t(rep[j - 1u]) & p.dst.ctx_mask) << 8) | rep[j]];
+        if (j >= (W ? 2u : 1u) && j < len) {
+            uint32_t l;
+            if constexpr (W) {
+                l = p.dst.len8[((((uint32_t(rep[j - 2u]) << 8) | rep[j - 1u]) & p.dst.ctx_mask) << 8) | rep[j]];
+                if (l > 64u) l = 0u;
+            } else {
+                l = p.dst.len8[((uint32_t(rep[j - 1u]) & p.dst.ctx_mask) << 8) | rep[j]];
+            }
             atomicAdd(&acc[0], l);
             if (!l) atomicAdd(&acc[1], 1u);
         }
@@ -1021,13 +1069,45 @@ __global__ __launch_bounds__(256) void splice_spans_kernel(SpliceTableParams p, 
     }
 }
 
+// the order-2 look-back's decode: the context behind the first `count` symbols of chunk c of stream i (count <= c.nsym; a
+// decode that fails returns what it has)
+template <Model K>
+__device__ __forceinline__ uint32_t splice_ctx_at(const Src &s, Dec<K, SW<K>> &dec, uint64_t i, const Chunk &c, uint32_t count) {
+    uint64_t bit0;
+    const BitSrc src = mhb::stream_src(s.b.payload, s.b.pay_off[i], c.nb, bit0);
+    BitCursor bc;
+    bc.init(src, bit0 + c.start);
+    dec.stream(s, i);
+    uint32_t ctx = c.ctx, used = 0;
+    bool bad = false;
+    for (uint32_t t = 0; t < count && !bad; ++t) {
+        const uint32_t sym = dec.next(s, src, bc, ctx, used, bad);
+        if (bad) break;
+        ctx = roll<SW<K>>(ctx, sym);
+    }
+    return ctx;
+}
+
+// span q's replacement (TABLE)
+struct RepBytes {
+    const uint8_t *b;
+    uint32_t len;
+};
+__device__ __forceinline__ RepBytes rep_bytes(const SpliceTableParams &p, uint64_t q) {
+    const uint32_t k = p.tb.span_tag[q];
+    const unsigned long long o = p.tb.rep_off[k];
+    return {p.tb.rep_bytes + o, uint32_t(p.tb.rep_off[k + 1] - o)};
+}
+
 // indexed: sctx[r] for every deleted span r over a chunk boundary, the last output byte in front of it (see "start" above).
-// More spans than the workspace has room for: MHK_STATUS_CAPACITY and the call stops.
+// More spans than the workspace has room for: MHK_STATUS_CAPACITY and the call stops.  SW<K>: sctx[r] for every span r
+// replaced by fewer than two bytes with a chunk boundary in (begin, end + 1], the last two output bytes behind its
+// replacement (see "order 2" above).
 template <Model K, bool TABLE>
-__global__ __launch_bounds__((Dec<K, false>::NT)) void splice_back_kernel(SpParams<TABLE> p, uint32_t *sctx, int *status, int *stop) {
+__global__ __launch_bounds__((Dec<K, SW<K>>::NT)) void splice_back_kernel(SpParams<TABLE> p, uint32_t *sctx, int *status, int *stop) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     if (stopped(stop)) return;
-    Dec<K, false> dec(p.s, smem);
+    Dec<K, SW<K>> dec(p.s, smem);
     const unsigned long long *off = p.sp.span_off, *sp = p.sp.spans;
     const uint64_t n = p.s.b.n, total = off[n];
     if (total > p.sp.span_cap) {
@@ -1038,56 +1118,92 @@ __global__ __launch_bounds__((Dec<K, false>::NT)) void splice_back_kernel(SpPara
     const uint32_t cs = p.s.b.chunk_shift;
     for (uint64_t r = gtid(); r < total; r += uint64_t(gridDim.x) * blockDim.x) {
         sctx[r] = 0u;
-        if ((sp[2 * r + 1] >> cs) == (sp[2 * r] >> cs)) continue;     // no chunk starts in (begin, end]: no lane asks
-        const uint64_t i = span_stream(off, n, r);
-        if (p.s.b.stream_status[i] != MH_OK) continue;                // (a passed stream's tags are table entries)
-        if (!rep_end<TABLE>(p, r).empty) continue;                    // replaced: its own last byte serves
-        const uint64_t a = p.s.b.sym_off[i], ni = p.s.b.sym_off[i + 1] - a;
-        if (sp[2 * r] >= ni) continue;                                // the span is ignored
-        uint64_t r0 = r;
-        uint32_t got = ~0u;
-        while (r0 > off[i] && sp[2 * r0 - 1] == sp[2 * r0]) {         // the touching span in front: through it while it is empty
-            const RepEnd front = rep_end<TABLE>(p, r0 - 1);
-            if (!front.empty) { got = front.last(); break; }
-            --r0;
+        // Two bodies on purpose.  The order-2 walk (two bytes, through touching spans and source bytes in turn) run with one
+        // byte would serve order 0/1 too, but the order-0/1 kernels must compile to what they were: even sharing the decode
+        // loop alone moved their four resource lines (+2 ... +8 instructions, 2 SGPR spills), so that body stays as it was.
+        if constexpr (SW<K>) {
+            if (((sp[2 * r + 1] + 1u) >> cs) == (sp[2 * r] >> cs)) continue;   // no chunk starts in (begin, end + 1]: no lane asks
+            const uint64_t i = span_stream(off, n, r);
+            if (p.s.b.stream_status[i] != MH_OK) continue;            // (a passed stream's tags are table entries)
+            const RepBytes me = rep_bytes(p, r);
+            if (me.len >= 2u) continue;                               // its own last two bytes serve
+            const uint64_t a = p.s.b.sym_off[i], ni = p.s.b.sym_off[i + 1] - a;
+            if (sp[2 * r] >= ni) continue;                            // the span is ignored
+            // from the back: acc holds `got` bytes, the last output byte lowest
+            uint32_t acc = me.len ? me.b[0] : 0u, got = me.len;
+            uint64_t q = r, pos = sp[2 * r];                          // the output in front of x[pos], spans q and later passed
+            uint64_t have = ~uint64_t(0);                             // two: (x[have - 2], x[have - 1])
+            uint32_t two = 0;
+            while (got < 2u) {                                        // (at most the stream's spans and two bytes more)
+                if (q > off[i] && sp[2 * q - 1] == pos) {             // a span or an insertion in front touches
+                    const RepBytes f = rep_bytes(p, --q);
+                    for (uint32_t j = f.len; j > 0u && got < 2u; --j) acc |= uint32_t(f.b[j - 1u]) << (8u * got++);
+                    pos = sp[2 * q];
+                    continue;
+                }
+                if (!pos) { acc |= (p.s.b.prev0 & 0xFFu) << (8u * got++); continue; }
+                if (have != pos && have != pos + 1u) {                // x[pos - 1] from the source, x[pos - 2] with it
+                    Chunk c;
+                    if (!chunk_of<K, true>(p.s, (a >> cs) + i + (pos >> cs), c) || !c.entry_ok()) break;
+                    two = splice_ctx_at<K>(p.s, dec, i, c, uint32_t(pos - c.first));
+                    have = pos;
+                }
+                acc |= (have == pos ? two & 0xFFu : (two >> 8) & 0xFFu) << (8u * got++);
+                --pos;
+            }
+            sctx[r] = acc;
+        } else {
+            if ((sp[2 * r + 1] >> cs) == (sp[2 * r] >> cs)) continue;     // no chunk starts in (begin, end]: no lane asks
+            const uint64_t i = span_stream(off, n, r);
+            if (p.s.b.stream_status[i] != MH_OK) continue;                // (a passed stream's tags are table entries)
+            if (!rep_end<TABLE>(p, r).empty) continue;                    // replaced: its own last byte serves
+            const uint64_t a = p.s.b.sym_off[i], ni = p.s.b.sym_off[i + 1] - a;
+            if (sp[2 * r] >= ni) continue;                                // the span is ignored
+            uint64_t r0 = r;
+            uint32_t got = ~0u;
+            while (r0 > off[i] && sp[2 * r0 - 1] == sp[2 * r0]) {         // the touching span in front: through it while it is empty
+                const RepEnd front = rep_end<TABLE>(p, r0 - 1);
+                if (!front.empty) { got = front.last(); break; }
+                --r0;
+            }
+            if (got != ~0u) { sctx[r] = got; continue; }
+            const uint64_t begin = sp[2 * r0];
+            if (!begin) { sctx[r] = p.s.b.prev0; continue; }
+            const uint64_t wb = (a >> cs) + i, pos = begin - 1u;
+            if (!(begin & ((uint64_t(1) << cs) - 1u))) { sctx[r] = uint32_t(p.s.b.index[wb + (begin >> cs)] >> 56); continue; }
+            Chunk c;
+            if (!chunk_of<K, false>(p.s, wb + (pos >> cs), c) || !c.entry_ok()) continue;
+            uint64_t bit0;
+            const BitSrc src = mhb::stream_src(p.s.b.payload, p.s.b.pay_off[i], c.nb, bit0);
+            BitCursor bc;
+            bc.init(src, bit0 + c.start);
+            dec.stream(p.s, i);
+            uint32_t ctx = c.ctx, used = 0;
+            bool bad = false;
+            const uint32_t count = uint32_t(pos - c.first) + 1u;          // <= c.nsym: pos < ni
+            for (uint32_t t = 0; t < count && !bad; ++t) {
+                const uint32_t sym = dec.next(p.s, src, bc, ctx, used, bad);
+                if (bad) break;
+                ctx = sym;
+            }
+            sctx[r] = ctx;
         }
-        if (got != ~0u) { sctx[r] = got; continue; }
-        const uint64_t begin = sp[2 * r0];
-        if (!begin) { sctx[r] = p.s.b.prev0; continue; }
-        const uint64_t wb = (a >> cs) + i, pos = begin - 1u;
-        if (!(begin & ((uint64_t(1) << cs) - 1u))) { sctx[r] = uint32_t(p.s.b.index[wb + (begin >> cs)] >> 56); continue; }
-        Chunk c;
-        if (!chunk_of<K, false>(p.s, wb + (pos >> cs), c) || !c.entry_ok()) continue;
-        uint64_t bit0;
-        const BitSrc src = mhb::stream_src(p.s.b.payload, p.s.b.pay_off[i], c.nb, bit0);
-        BitCursor bc;
-        bc.init(src, bit0 + c.start);
-        dec.stream(p.s, i);
-        uint32_t ctx = c.ctx, used = 0;
-        bool bad = false;
-        const uint32_t count = uint32_t(pos - c.first) + 1u;          // <= c.nsym: pos < ni
-        for (uint32_t t = 0; t < count && !bad; ++t) {
-            const uint32_t sym = dec.next(p.s, src, bc, ctx, used, bad);
-            if (bad) break;
-            ctx = sym;
-        }
-        sctx[r] = ctx;
     }
 }
 
 template <Model K, bool DLDS, bool TABLE>
-__global__ __launch_bounds__((Dec<K, false>::NT)) void splice_idx_len_kernel(SpParams<TABLE> p, uint64_t nwork, uint32_t lds_at,
+__global__ __launch_bounds__((Dec<K, SW<K>>::NT)) void splice_idx_len_kernel(SpParams<TABLE> p, uint64_t nwork, uint32_t lds_at,
                                                                            unsigned long long *cbits, unsigned long long *csyms, uint32_t *cdrop,
                                                                            const uint32_t *sctx, const uint32_t *price, int *status,
                                                                            const int *stop) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     if (stopped(stop)) return;
-    Dec<K, false> dec(p.s, smem);
-    const Enc<DLDS, false> E(p.dst, smem, lds_at);
+    Dec<K, SW<K>> dec(p.s, smem);
+    const Enc<DLDS, SW<K>> E(p.dst, smem, lds_at);
     Cut<TABLE> cu(p);
     for (uint64_t w = gtid(); w < nwork; w += uint64_t(gridDim.x) * blockDim.x) {
         Chunk c;
-        if (!chunk_of<K, false>(p.s, w, c) || p.s.b.stream_status[c.i] == MH_ERR_ARG) continue;
+        if (!chunk_of<K, SW<K>>(p.s, w, c) || p.s.b.stream_status[c.i] == MH_ERR_ARG) continue;
         if (!c.entry_ok()) { stream_fail(p.s.b, status, c.i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT); continue; }
         uint64_t bit0;
         const BitSrc src = mhb::stream_src(p.s.b.payload, p.s.b.pay_off[c.i], c.nb, bit0);
@@ -1095,7 +1211,7 @@ __global__ __launch_bounds__((Dec<K, false>::NT)) void splice_idx_len_kernel(SpP
         bc.init(src, bit0 + c.start);
         dec.stream(p.s, c.i);
         uint32_t ctx = c.ctx, used = 0, bits = 0, drops = 0, osym = 0;
-        uint32_t dctx = splice_start(cu, c, sctx);
+        uint32_t dctx = splice_start<SW<K>>(cu, c, sctx);
         bool bad = false;
         for (uint32_t t = 0; t < c.nsym && !bad; ++t) {
             const uint32_t sym = dec.next(p.s, src, bc, ctx, used, bad);
@@ -1105,17 +1221,24 @@ __global__ __launch_bounds__((Dec<K, false>::NT)) void splice_idx_len_kernel(SpP
                 const uint32_t l = E.len(E.at(dctx, cu.rep[0]));     // rep[0] in dctx; the rest is priced
                 bits += l + price[2 * cu.k];
                 drops += (l == 0u) + price[2 * cu.k + 1u];
+                if constexpr (SW<K>) {                                // rep[1] too: behind rep[0], one byte of dctx still counts
+                    if (cu.rep_len >= 2u) {
+                        const uint32_t l1 = E.len(E.at(roll<true>(dctx, cu.rep[0]), cu.rep[1]));
+                        bits += l1;
+                        drops += l1 == 0u;
+                    }
+                }
                 osym += cu.rep_len;
-                dctx = cu.rep[cu.rep_len - 1u];
+                dctx = rep_ctx<SW<K>>(dctx, cu.rep, cu.rep_len);
             });
             if (coded) {
                 const uint32_t l = E.len(E.at(dctx, sym));
                 bits += l;
                 drops += l == 0u;
-                dctx = sym;
+                dctx = roll<SW<K>>(dctx, sym);
                 ++osym;
             }
-            ctx = sym;
+            ctx = roll<SW<K>>(ctx, sym);
         }
         if (bad || used != c.end - c.start) { stream_fail(p.s.b, status, c.i, MH_ERR_CORRUPT, mhk::MHK_STATUS_CORRUPT); continue; }
         cbits[w] = bits;
@@ -1184,30 +1307,30 @@ struct SpliceOut {
     uint32_t ocs;
     uint64_t o, bit;                    // stream-relative output position and bit
     bool on;
-    template <bool DLDS>
-    __device__ __forceinline__ void put(const Enc<DLDS, false> &E, BitWriter &bw, uint32_t &dctx, uint32_t sym) {
+    template <bool DLDS, bool W>
+    __device__ __forceinline__ void put(const Enc<DLDS, W> &E, BitWriter &bw, uint32_t &dctx, uint32_t sym) {
         if (slice && (o & ((uint64_t(1) << ocs) - 1u)) == 0) slice[o >> ocs] = E.entry(dctx, bit);
         bit += E.put(bw, E.at(dctx, sym), on);
-        dctx = sym;
+        dctx = roll<W>(dctx, sym);
         ++o;
     }
 };
 
 template <Model K, bool DLDS, bool TABLE>
-__global__ __launch_bounds__((Dec<K, false>::NT)) void splice_idx_emit_kernel(SpParams<TABLE> p, uint64_t nwork, uint32_t lds_at,
+__global__ __launch_bounds__((Dec<K, SW<K>>::NT)) void splice_idx_emit_kernel(SpParams<TABLE> p, uint64_t nwork, uint32_t lds_at,
                                                                             const unsigned long long *cbase, const unsigned long long *obase,
                                                                             const uint32_t *sctx, uint32_t *tail, const int *stop) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     if (stopped(stop)) return;
-    Dec<K, false> dec(p.s, smem);
-    const Enc<DLDS, false> E(p.dst, smem, lds_at);
+    Dec<K, SW<K>> dec(p.s, smem);
+    const Enc<DLDS, SW<K>> E(p.dst, smem, lds_at);
     Cut<TABLE> cu(p);
     const uint64_t bytes = p.out_off[p.s.b.n];
     const uint64_t tail_w = (bytes & 3u) ? bytes >> 2 : ~uint64_t(0);
     const uint32_t cs = p.s.b.chunk_shift;
     for (uint64_t w = gtid(); w < nwork; w += uint64_t(gridDim.x) * blockDim.x) {
         Chunk c;
-        if (!chunk_of<K, false>(p.s, w, c) || p.s.b.stream_status[c.i] != MH_OK) continue;
+        if (!chunk_of<K, SW<K>>(p.s, w, c) || p.s.b.stream_status[c.i] != MH_OK) continue;
         if (obase[w + 1] == obase[w]) continue;                                   // a lane that produces nothing writes nothing
         const uint64_t w0 = (p.s.b.sym_off[c.i] >> cs) + c.i;
         SpliceOut so;
@@ -1216,7 +1339,7 @@ __global__ __launch_bounds__((Dec<K, false>::NT)) void splice_idx_emit_kernel(Sp
         so.ocs = cs;
         so.on = p.out != nullptr;
         so.slice = p.out_index ? p.out_index + (p.sp.out_sym_off[c.i] >> cs) + c.i : nullptr;
-        uint32_t dctx = splice_start(cu, c, sctx);
+        uint32_t dctx = splice_start<SW<K>>(cu, c, sctx);
         uint64_t bit0;
         const BitSrc src = mhb::stream_src(p.s.b.payload, p.s.b.pay_off[c.i], c.nb, bit0);
         BitCursor bc;
@@ -1232,7 +1355,7 @@ __global__ __launch_bounds__((Dec<K, false>::NT)) void splice_idx_emit_kernel(Sp
                 for (uint32_t j = 0; j < cu.rep_len; ++j) so.put<DLDS>(E, bw, dctx, cu.rep[j]);
             });
             if (coded) so.put<DLDS>(E, bw, dctx, sym);
-            ctx = sym;
+            ctx = roll<SW<K>>(ctx, sym);
         }
         if (so.on) bw.finish();
     }
@@ -1241,12 +1364,12 @@ __global__ __launch_bounds__((Dec<K, false>::NT)) void splice_idx_emit_kernel(Sp
 // Index-free, one lane per stream (recode_walk_kernel).  EMIT = false: the verdict, the stream's symbols into sym_off[i] and
 // its output symbols into out_sym_off[i] (both scanned next), its dst bits and dropped symbols; true: codes and index entries.
 template <Model K, bool DLDS, bool EMIT, bool TABLE>
-__global__ __launch_bounds__((Dec<K, false>::NT)) void splice_walk_kernel(SpParams<TABLE> p, uint32_t lds_at, uint32_t *tail, int *status,
+__global__ __launch_bounds__((Dec<K, SW<K>>::NT)) void splice_walk_kernel(SpParams<TABLE> p, uint32_t lds_at, uint32_t *tail, int *status,
                                                                         const int *stop) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     if (stopped(stop)) return;
-    Dec<K, false> dec(p.s, smem);
-    const Enc<DLDS, false> E(p.dst, smem, lds_at);
+    Dec<K, SW<K>> dec(p.s, smem);
+    const Enc<DLDS, SW<K>> E(p.dst, smem, lds_at);
     Cut<TABLE> cu(p);
     const uint64_t n = p.s.b.n;
     const uint64_t bytes = EMIT ? p.out_off[n] : 0;
@@ -1273,7 +1396,7 @@ __global__ __launch_bounds__((Dec<K, false>::NT)) void splice_walk_kernel(SpPara
         so.slice = EMIT && p.out_index ? p.out_index + (p.sp.out_sym_off[i] >> so.ocs) + i : nullptr;
         BitWriter bw;
         if (so.on) bw.init(reinterpret_cast<uint32_t *>(p.out), tail, tail_w, uint64_t(p.out_off[i]) * 8u);
-        uint32_t ctx = start_ctx<K, false>(p.s), used = 0, drops = 0;
+        uint32_t ctx = start_ctx<K, SW<K>>(p.s), used = 0, drops = 0;
         uint32_t dctx = ctx;
         cu.start(i);
         bool bad = false;
@@ -1283,7 +1406,7 @@ __global__ __launch_bounds__((Dec<K, false>::NT)) void splice_walk_kernel(SpPara
                 so.put<DLDS>(E, bw, dctx, s);
             } else {
                 const uint32_t l = E.len(E.at(dctx, s));
-                so.bit += l; drops += l == 0u; dctx = s; ++so.o;
+                so.bit += l; drops += l == 0u; dctx = roll<SW<K>>(dctx, s); ++so.o;
             }
         };
         // every code has at least one bit: at most nb steps (src/coding.cpp:124 — decode while bits remain)
@@ -1294,7 +1417,7 @@ __global__ __launch_bounds__((Dec<K, false>::NT)) void splice_walk_kernel(SpPara
                 for (uint32_t j = 0; j < cu.rep_len; ++j) one(cu.rep[j]);
             });
             if (coded) one(sym);
-            ctx = sym;
+            ctx = roll<SW<K>>(ctx, sym);
             ++k;
         }
         if (EMIT) { if (so.on) bw.finish(); continue; }
@@ -1363,7 +1486,6 @@ hipError_t launch_hist(const HistParams &p, void *d_ws, hipStream_t st) {
 // they do not fit (a source whose tables fill the LDS) the lanes read the map from L2
 template <Model K, bool DLDS, bool W, bool EDIT = false>
 hipError_t launch_rc(Params<EDIT> p, size_t lds_tables, void *d_ws, hipStream_t st) {
-    static_assert(!(EDIT && W), "the edit has no order-2 form");
     constexpr int NT = Dec<K, W>::NT, PER_CU = Dec<K, W>::PER_CU;
     size_t lds = lds_tables + (DLDS ? (p.dst.ctx_mask ? 65536 : 256) : 0);
     const uint32_t lds_at = uint32_t(lds_tables);
@@ -1426,7 +1548,7 @@ hipError_t launch_rc(Params<EDIT> p, size_t lds_tables, void *d_ws, hipStream_t 
 // call, so the launches depend on indexed versus index-free alone; !TABLE: it runs when rep_len == 0.
 template <Model K, bool DLDS, bool TABLE>
 hipError_t launch_sp(SpParams<TABLE> p, size_t lds_tables, void *d_ws, size_t ws_bytes, hipStream_t st) {
-    constexpr int NT = Dec<K, false>::NT, PER_CU = Dec<K, false>::PER_CU;
+    constexpr int NT = Dec<K, SW<K>>::NT, PER_CU = Dec<K, SW<K>>::PER_CU;
     const size_t lds = lds_tables + (DLDS ? (p.dst.ctx_mask ? 65536 : 256) : 0);
     const uint32_t lds_at = uint32_t(lds_tables);
     if (K == Model::Shared) {
@@ -1458,7 +1580,7 @@ hipError_t launch_sp(SpParams<TABLE> p, size_t lds_tables, void *d_ws, size_t ws
     const dim3 span_grid(grid_for(uint64_t(1) << 40, 256, 8));
     hipLaunchKernelGGL(splice_check_kernel, grid_threads(n + 1, 256), dim3(256), 0, st, p, status, stop);
     if constexpr (!TABLE) hipLaunchKernelGGL(recode_spans_kernel, span_grid, dim3(256), 0, st, spans_view(p), status, stop);
-    hipLaunchKernelGGL(splice_price_kernel<TABLE>, dim3(uint32_t(nr < 1 ? 1 : (nr > 65536 ? 65536 : nr))), dim3(256), 0, st, p, price, status, stop);
+    hipLaunchKernelGGL((splice_price_kernel<TABLE, SW<K>>), dim3(uint32_t(nr < 1 ? 1 : (nr > 65536 ? 65536 : nr))), dim3(256), 0, st, p, price, status, stop);
     if constexpr (TABLE) hipLaunchKernelGGL(splice_spans_kernel, span_grid, dim3(256), 0, st, p, status, stop);   // (behind the table's checks)
     if (p.s.b.index) {
         if (TABLE || !p.sp.rep_len)
@@ -1494,7 +1616,11 @@ hipError_t launch_sp(SpParams<TABLE> p, size_t lds_tables, void *d_ws, size_t ws
 // the branches of launch_recode_edit, each with the splice in place of the edit
 template <bool TABLE>
 hipError_t launch_splice(const SpParams<TABLE> &p, Model model, void *d_ws, size_t ws_bytes, hipStream_t st) {
-    if (model == Model::Shared2 || p.dst.ctx_mask == 0xFFFFu) return hipErrorInvalidValue;
+    if (model == Model::Shared2) {                                    // any destination; tables in L2, no image in LDS
+        if constexpr (TABLE) return launch_sp<Model::Shared2, false, true>(p, 0, d_ws, ws_bytes, st);
+        else return hipErrorInvalidValue;
+    }
+    if (p.dst.ctx_mask == 0xFFFFu) return hipErrorInvalidValue;
     if (model == Model::Set)
         return p.dst.ctx_mask ? launch_sp<Model::Set, false, TABLE>(p, 0, d_ws, ws_bytes, st)
                               : launch_sp<Model::Set, true, TABLE>(p, 0, d_ws, ws_bytes, st);
@@ -1538,13 +1664,16 @@ hipError_t launch_recode(const RecodeParams &p, Model model, void *d_ws, hipStre
                                         : launch_rc<Model::Shared, false, false>(p, lds, d_ws, st);
 }
 
-// the branches of launch_recode for order 0/1 on both sides, each with the edit
+// the branches of launch_recode, each with the edit
 hipError_t launch_recode_edit(const EditParams &p, Model model, void *d_ws, hipStream_t st) {
-    if (model == Model::Shared2 || p.dst.ctx_mask == 0xFFFFu) return hipErrorInvalidValue;
+    const bool dst2 = p.dst.ctx_mask == 0xFFFFu;
+    if (model == Model::Shared2) return launch_rc<Model::Shared2, false, true, true>(p, 0, d_ws, st);
+    if (model == Model::Set && dst2) return hipErrorInvalidValue;
     if (model == Model::Set)
         return p.dst.ctx_mask ? launch_rc<Model::Set, false, false, true>(p, 0, d_ws, st) : launch_rc<Model::Set, true, false, true>(p, 0, d_ws, st);
     const size_t lds = mhb::tables_lds(p.s.b);
     if (lds > size_t(LDS_MAX)) return hipErrorInvalidValue;
+    if (dst2) return launch_rc<Model::Shared, false, true, true>(p, lds, d_ws, st);
     const size_t img = p.dst.ctx_mask ? 65536 : 256;
     return lds + img <= size_t(LDS_MAX) ? launch_rc<Model::Shared, true, false, true>(p, lds, d_ws, st)
                                         : launch_rc<Model::Shared, false, false, true>(p, lds, d_ws, st);
