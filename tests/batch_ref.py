@@ -6,7 +6,10 @@ A case is drawn in two steps: draw_cases(seed) fixes every case's parameters (an
 Case.world() builds the messages, patterns, lookups and model counts of one case when a test needs them.  Case.edits() is a
 second such part, from a generator of its own: a dictionary, a span list, a byte map and two replacements for dictionary
 search, span merging, masked and splicing re-code (find_ref.py, edit_ref.py, splice_ref.py), and Case.expected() what the
-edit and the splices must give."""
+edit and the splices must give.  Case.table() is a third, again from a generator of its own: a replacement table, the span
+list with a tag per span and insertions put in by craft, and the tagged merge of the dictionary's hits (splice_table_ref.py);
+Case.expected_table() is what the table splice must give.  Both expectations come under the case's destination and under a
+covering one, trained on the originals and on every edited form, under which nothing is dropped."""
 import bisect
 import functools
 
@@ -15,6 +18,7 @@ import numpy as np
 import edit_ref
 import find_ref
 import splice_ref
+import splice_table_ref
 from oracle import mh_oracle as oracle
 
 PREV0 = 0x20
@@ -372,6 +376,7 @@ class Case:
             return histogram(w.foreign, order, w.prev0), 0
         return histogram(w.messages, order, w.prev0), self.limit[which] if kind == "limited" else 0
 
+    @functools.lru_cache(maxsize=4)
     def codes(self, which):
         counts, limit = self.counts(which)
         order = self.orders[0 if which == "src" else 1]
@@ -452,15 +457,66 @@ class Case:
 
     @functools.lru_cache(maxsize=2)
     def expected(self):
-        """What the masked and the splicing re-code must give under the destination model: the packer on the edited messages."""
+        """What the masked and the splicing re-code must give under the destination model: the packer on the edited messages.
+        A case with an order-2 side: the edit under the covering destination as well."""
         w, e, x = self.world(), self.edits(), Expected()
         do = self.orders[1]
         put = lambda msgs: pack(msgs, *self.codes("dst"), do, w.prev0, self.chunk)
-        x.edit = put(edit_ref.apply(w.messages, e.span_off, e.spans, e.byte_map))
-        x.edit_all = put(edit_ref.apply(w.messages, None, None, e.byte_map))
-        x.spliced = [splice_ref.apply(w.messages, e.span_off, e.spans, rep) for rep in e.reps]
+        x.edited, x.edited_all, x.spliced = self._edited()
+        x.edit, x.edit_all = put(x.edited), put(x.edited_all)
         x.splice = [put(y) for y in x.spliced]
         x.out_sym_off = [splice_ref.offsets(y) for y in x.spliced]
+        if 2 in self.orders:
+            x.edit_cover, x.edit_all_cover = self.put_cover(x.edited), self.put_cover(x.edited_all)
+        return x
+
+    def _edited(self):
+        """(the masked messages, the messages masked everywhere, [the messages with every span deleted, ... replaced])."""
+        w, e = self.world(), self.edits()
+        return (edit_ref.apply(w.messages, e.span_off, e.spans, e.byte_map), edit_ref.apply(w.messages, None, None, e.byte_map),
+                [splice_ref.apply(w.messages, e.span_off, e.spans, rep) for rep in e.reps])
+
+    # ---- the third part of a case: a replacement table, a tagged span list with insertions, the tagged merge ----
+    @functools.lru_cache(maxsize=2)
+    def table(self):
+        """The inputs of the tagged span merge and the table splice.  A generator of its own, seeded from the case's seed: no draw
+        of world() or edits() moves."""
+        rng = np.random.default_rng([self.seed, 2])
+        w, e, t = self.world(), self.edits(), Table()
+        _draw_table(rng, w, e, t)
+        _draw_tagged(rng, self, w, e, t)
+        t.merged = splice_table_ref.merge_tagged(e.hit_off, e.records, e.hit_pattern)
+        return t
+
+    def _table_spliced(self):
+        t = self.table()
+        return splice_table_ref.apply(self.world().messages, t.span_off, t.spans, t.tags, t.reps)
+
+    @functools.lru_cache(maxsize=2)
+    def cover_counts(self):
+        """The counts of the covering destination: the originals and every edited form of the case (masked, masked everywhere,
+        both splices, the table splice) under the destination's order."""
+        w = self.world()
+        edited, edited_all, spliced = self._edited()
+        return histogram(w.messages + edited + edited_all + spliced[0] + spliced[1] + self._table_spliced(), self.orders[1], w.prev0)
+
+    @functools.lru_cache(maxsize=2)
+    def cover_codes(self):
+        return oracle_codes(self.cover_counts(), self.orders[1])
+
+    def put_cover(self, msgs):
+        return pack(msgs, *self.cover_codes(), self.orders[1], self.world().prev0, self.chunk)
+
+    @functools.lru_cache(maxsize=2)
+    def expected_table(self):
+        """What the table splice must give: splice_table_ref.apply on the original messages, packed under the case's destination
+        and under the covering one, where no symbol is dropped."""
+        w, x = self.world(), ExpectedTable()
+        x.spliced = self._table_spliced()
+        x.out_sym_off = splice_table_ref.offsets(x.spliced)
+        x.packed = pack(x.spliced, *self.codes("dst"), self.orders[1], w.prev0, self.chunk)
+        x.cover = self.put_cover(x.spliced)
+        assert not x.cover.dropped.any(), "the covering destination drops a symbol"
         return x
 
 
@@ -511,7 +567,19 @@ class Edits:
 
 class Expected:
     """The expected outputs of a case's edit and splices: edit, edit_all (no span list: everywhere), splice[k] (batch_ref.Packed
-    under the destination model), spliced[k] (the messages) and out_sym_off[k], k = 0 the deletion, 1 the replacement."""
+    under the destination model), spliced[k] (the messages) and out_sym_off[k], k = 0 the deletion, 1 the replacement; edited and
+    edited_all (the messages); with an order-2 side edit_cover and edit_all_cover, the edit under the covering destination."""
+
+
+class Table:
+    """The third part of a case, built: reps (the replacement table) and empty (the number of its empty entry), span_off /
+    spans / tags (the tagged list, insertions included) and merged (span_off, spans, tags of the tagged merge of the
+    dictionary's hits)."""
+
+
+class ExpectedTable:
+    """The expected output of a case's table splice: spliced (the messages), out_sym_off, packed (batch_ref.Packed under the
+    destination model) and cover (under the covering destination)."""
 
 
 def _fold(b, fold):
@@ -767,6 +835,268 @@ def _draw_map(rng, case, w, e):
         elif kind == "lacking":
             kind = "random"
     e.byte_map, e.map_kind = m.tobytes(), kind
+
+
+# ---------------------------------------------------------------------------------------------------- tables and tagged lists
+TABLE_ROOM = 250                   # entries of SPAN_CAP that the crafted insertions of a case may take
+INSERTIONS = ("at 0", "at a seam", "one byte in front of a seam", "one byte behind a seam", "at the end of a span", "at the begin of a span",
+              "several at one position", "the empty entry", "at len - 1", "at len or beyond", "in an empty stream", "a chain to a seam")
+OUTPUT_SEAMS = ("inside a replacement", "one byte behind a replacement", "two bytes behind a replacement", "behind three touching spans")
+
+
+def _draw_table(rng, w, e, t):
+    """2 to 8 entries: the empty one, the case's replacement, and entries of 1, 2, 3, 64, 255 or 4 .. 254 bytes of the source
+    alphabet; in about a quarter of the cases an entry gets a byte the messages lack, in about a third two entries are equal;
+    then shuffled."""
+    here = np.unique(np.frombuffer(b"".join(w.messages), dtype=np.uint8))
+    k = int(rng.integers(2, 9))
+    reps = [b"", e.reps[1]]
+    while len(reps) < k:
+        ln = [1, 2, 3, 64, 255, int(rng.integers(4, 255))][int(rng.integers(6))]
+        reps.append(rng.choice(here, size=ln).astype(np.uint8).tobytes())
+    lacks = int(rng.integers(2, k)) if k >= 3 and e.lacking is not None and rng.random() < 0.25 else None
+    if lacks is not None:
+        r = bytearray(reps[lacks])
+        r[int(rng.integers(len(r)))] = e.lacking
+        reps[lacks] = bytes(r)
+    if k >= 4 and rng.random() < 0.35:                             # (the twin of an entry, not over the one that got the lacking byte)
+        b = int(rng.choice([j for j in range(2, k) if j != lacks]))
+        reps[b] = reps[int(rng.choice([j for j in range(1, k) if j != b]))]
+    t.reps = [reps[int(j)] for j in rng.permutation(k)]
+    t.empty = t.reps.index(b"")
+
+
+def _insert(lst, p, tag):
+    """Puts the insertion (p, p, tag) into one stream's well-formed list of (begin, end, tag): behind everything that ends at or
+    in front of p, the insertions at p included; a span that holds p strictly inside is split in two at p."""
+    for k, (b, end, g) in enumerate(lst):
+        if b < p < end:
+            lst[k:k + 1] = [(b, p, g), (p, end, g)]
+            break
+    lst.insert(sum(1 for _, end, _ in lst if end <= p), (p, p, tag))
+
+
+def _put_unit(lst, unit, keep=0):
+    """Puts touching spans into one stream's list; what they overlap gives way: a span is clipped, an insertion strictly
+    between the unit's ends is dropped.  keep: as many source bytes behind the unit are cleared of spans as well."""
+    lo, hi = unit[0][0], unit[-1][1] + keep
+    out = []
+    for b, end, g in lst:
+        if end <= lo or b >= hi:
+            out.append((b, end, g))
+            continue
+        if b < lo:
+            out.append((b, lo, g))
+        if end > hi:
+            out.append((hi, end, g))
+    at = sum(1 for _, end, _ in out if end <= lo)
+    lst[:] = out[:at] + list(unit) + out[at:]
+
+
+def splice_pieces(L, lst, reps):
+    """One spliced stream of L source bytes as pieces in output order: ('src', output begin, length, source begin, None) and
+    ('rep', output begin, length, source position, number of the span in lst)."""
+    out, at, o = [], 0, 0
+    for r, (b, end, g) in enumerate(lst):
+        if b >= L:
+            break
+        if b > at:
+            out.append(("src", o, b - at, at, None))
+            o += b - at
+        out.append(("rep", o, len(reps[g]), b, r))
+        o += len(reps[g])
+        at = min(end, L)
+    if L > at:
+        out.append(("src", o, L - at, at, None))
+    return out
+
+
+def _craft_insertions(rng, lst, L, c, k, empty, every, head=False):
+    """Insertions of every kind of INSERTIONS that one stream of L bytes admits (every: all of them, else each with
+    probability 1 / 2), and spans that end one byte in front of a seam (head: one of them from 0 up to the first seam)."""
+    tag = lambda: int(rng.integers(k))
+    other = lambda g: (g + 1 + int(rng.integers(k - 1))) % k
+    go = lambda: every or rng.random() < 0.5
+    if L == 0:
+        for p in (0, int(rng.integers(0, 3))):
+            _insert(lst, p, tag())
+        return
+    seams = list(range(c, L, c))
+    seam = lambda: seams[int(rng.integers(len(seams)))]
+    if head and seams:                                             # all but one byte in front of the first seam deleted: prev0 meets it
+        _put_unit(lst, [(0, c - 1, empty)], keep=1)
+    free = [s for s in seams if not (head and s == c)]            # (a single seam: the chain or a span that ends in front of it)
+    chain = free[int(rng.integers(len(free)))] if free and go() and (len(free) > 1 or rng.random() < 0.5) else None
+    if chain:                                                      # deletion, insertion, deletion up to a seam
+        d1, d2 = int(rng.integers(1, 6)), int(rng.integers(1, 6))
+        a = chain - d1 - d2
+        _put_unit(lst, [(a, a + d1, empty), (a + d1, a + d1, other(empty)), (a + d1, chain, empty)])
+    for s in seams[:8]:                                            # a span that ends one byte in front of a seam, and x[seam - 1]
+        if s != chain and not (head and s == c) and go():          # in no span: it follows what the span left, not x[seam - 2]
+            _put_unit(lst, [(s - 1 - int(rng.integers(1, 4)), s - 1, tag())], keep=1)
+    if go():
+        _insert(lst, 0, tag())
+    if seams:
+        for d in (0, -1, 1):
+            s = seam()
+            if go() and s + d < L:
+                _insert(lst, s + d, tag() if d >= 0 else other(empty))
+    real = [(b, end) for b, end, _ in lst if b < end < L]
+    if real and go():
+        _insert(lst, real[int(rng.integers(len(real)))][1], tag())
+    if real and go():
+        _insert(lst, real[int(rng.integers(len(real)))][0], tag())
+    if go():
+        p, g = int(rng.integers(L)), tag()
+        _insert(lst, p, g)
+        _insert(lst, p, other(g))
+    if go():
+        _insert(lst, int(rng.integers(L)), empty)
+    if go():
+        _insert(lst, L - 1, tag())
+    if go():
+        _insert(lst, L, tag())
+    if go():
+        _insert(lst, L + int(rng.integers(1, 300)), tag())
+
+
+def _craft_output_seams(rng, lst, L, c, reps, first):
+    """At every seam of the OUTPUT of one stream, in ascending order (what is put in at one seam moves no earlier one), one of
+    OUTPUT_SEAMS, going round them from `first`: the unit goes into a run of source bytes that no span touches, where there is
+    one at the right distance in front of the seam."""
+    k, Q, turn = len(reps), c, first
+    while Q <= 6 * c:                                              # (the first six seams: a short chunk has many)
+        pieces = splice_pieces(L, lst, reps)
+        if not pieces or Q >= pieces[-1][1] + pieces[-1][2]:
+            return
+        kind = OUTPUT_SEAMS[turn % len(OUTPUT_SEAMS)]
+        for _ in range(8):                                         # (other tags, other lengths: another distance)
+            g = [int(v) for v in rng.integers(k, size=3)]
+            r = [len(reps[v]) for v in g]
+            if kind == "inside a replacement":
+                if r[0] < 2:
+                    continue
+                T, width, make = Q - int(rng.integers(1, r[0])), 1, lambda p: [(p, p + int(rng.integers(0, 2)), g[0])]
+            elif kind == "behind three touching spans":
+                T, width, make = Q - sum(r), 4, lambda p: [(p, p + 1, g[0]), (p + 1, p + 2, g[1]), (p + 2, p + 3, g[2])]
+            else:
+                if r[0] < 1:
+                    continue
+                behind = 1 if kind == "one byte behind a replacement" else 2
+                T, width, make = Q - r[0] - behind, 1 + behind + 1, lambda p: [(p, p + 1, g[0])]
+            run = [(o, n, sb) for what, o, n, sb, _ in pieces if what == "src" and o < T and T + width < o + n]
+            if run:
+                o, n, sb = run[0]
+                _put_unit(lst, make(sb + T - o))
+                break
+        Q, turn = Q + c, turn + 1
+
+
+def _draw_tagged(rng, case, w, e, t):
+    """The span list of edits() with a tag per span, drawn over the table, and insertions put in by craft: into the longest
+    stream every kind it admits, into up to four more streams, one longer than a chunk and one empty among them where there
+    are such, about half of them, and spans that end one byte in front of a seam (in the second long stream one that deletes
+    everything up to there from 0); then units at the seams of the OUTPUT of the streams longer than a chunk.  A span that holds a
+    crafted insertion is split there; where a crafted unit of touching spans overlaps spans of the list, they are clipped.
+    The insertions get TABLE_ROOM entries of SPAN_CAP: a list with less room first loses spans, drawn evenly."""
+    c, ln = case.chunk, [len(m) for m in w.messages]
+    n, k = len(ln), len(t.reps)
+    tags = rng.integers(k, size=len(e.spans))
+    keep = np.ones(len(e.spans), dtype=bool)
+    if len(e.spans) > SPAN_CAP - TABLE_ROOM:
+        keep[rng.choice(len(e.spans), size=len(e.spans) - (SPAN_CAP - TABLE_ROOM), replace=False)] = False
+    per, r = [], 0
+    for lst in span_lists(e.span_off, e.spans):
+        per.append([(int(b), int(end), int(tags[r + j])) for j, (b, end) in enumerate(lst) if keep[r + j]])
+        r += len(lst)
+    longest = int(np.argmax(ln))
+    long = [i for i in range(n) if ln[i] > c and i != longest]
+    empty = [i for i in range(n) if ln[i] == 0]
+    more = [int(i) for i in rng.integers(0, n, size=int(rng.integers(1, 3)))]
+    more += [long[int(rng.integers(len(long)))]] if long else []
+    more += [empty[int(rng.integers(len(empty)))]] if empty else []
+    room = lambda: SPAN_CAP - sum(len(p) for p in per)
+    for j, i in enumerate([longest] + sorted(set(more) - {longest})):
+        if room() >= 48:
+            _craft_insertions(rng, per[i], ln[i], c, k, t.empty, j == 0, bool(long) and i == more[-1 - bool(empty)])
+    for j, i in enumerate([longest] + sorted(set(long) & set(more))):
+        if room() >= 16:
+            _craft_output_seams(rng, per[i], ln[i], c, t.reps, case.index + j)
+    t.span_off, t.spans, t.tags = splice_table_ref.tagged_lists(per)
+
+
+def tagged_span_lists(span_off, spans, tags):
+    """[[(begin, end, tag)] per stream] of a tagged span list."""
+    tags = [int(g) for g in tags]
+    out, r = [], 0
+    for lst in span_lists(span_off, spans):
+        out.append([(b, end, tags[r + j]) for j, (b, end) in enumerate(lst)])
+        r += len(lst)
+    return out
+
+
+def insertions(messages, span_off, spans, tags, reps, chunk):
+    """Which of INSERTIONS a tagged list reaches on these messages (a set of names), from the list alone.  A span next to an
+    insertion is the nearest entry of the list that is no insertion; a chain is a deletion, one or more insertions where it
+    ends, one of them not empty, and a deletion from there up to a seam inside the stream."""
+    c, got = chunk, set()
+    for m, lst in zip(messages, tagged_span_lists(span_off, spans, tags)):
+        L = len(m)
+        for j, (b, end, g) in enumerate(lst):
+            if b != end:
+                continue
+            if L == 0 or b >= L:
+                got.add("in an empty stream" if L == 0 else "at len or beyond")
+                continue
+            got.add("at 0" if b == 0 else "at a seam" if b % c == 0 else "")
+            got.add("one byte in front of a seam" if (b + 1) % c == 0 and b + 1 < L else "one byte behind a seam" if b % c == 1 and b > c else "")
+            got.add("at len - 1" if b == L - 1 else "")
+            got.add("the empty entry" if not reps[g] else "")
+            front = [x for x in lst[:j] if x[0] < x[1]][-1:]
+            behind = [x for x in lst[j + 1:] if x[0] < x[1]][:1]
+            got.add("at the end of a span" if front and front[0][1] == b else "")
+            got.add("at the begin of a span" if behind and behind[0][0] == b else "")
+            if any(x[0] == x[1] == b and x[2] != g for x in lst[j + 1:j + 4]):
+                got.add("several at one position")
+        for j, (b, end, g) in enumerate(lst):                      # a chain
+            if b < end and not reps[g]:
+                k = j + 1
+                while k < len(lst) and lst[k][0] == lst[k][1] == end:
+                    k += 1
+                if k > j + 1 and k < len(lst) and any(reps[x[2]] for x in lst[j + 1:k]):
+                    b2, e2, g2 = lst[k]
+                    if b2 == end < e2 < L and e2 % c == 0 and not reps[g2]:
+                        got.add("a chain to a seam")
+    return got - {""}
+
+
+def output_seams(messages, span_off, spans, tags, reps, chunk):
+    """Which of OUTPUT_SEAMS a tagged list reaches: where the chunks of the spliced messages start, from splice_pieces.  A
+    replacement here has at least one byte; touching spans are entries of the list, insertions included, each of which begins
+    where the one in front ends."""
+    got = set()
+    for m, lst in zip(messages, tagged_span_lists(span_off, spans, tags)):
+        L = len(m)
+        pieces = splice_pieces(L, lst, reps)
+        if not pieces:
+            continue
+        total = pieces[-1][1] + pieces[-1][2]
+        run = {}                                                   # number of a span in lst -> the touching spans up to it
+        for r, (b, end, g) in enumerate(lst):
+            run[r] = run[r - 1] + 1 if r and b < L and lst[r - 1][1] == b else 1
+        for what, o, n, sb, r in pieces:
+            if what != "rep":
+                continue
+            stop, at = o + n, min(lst[r][1], L)                    # where it ends in the output and in the source
+            nxt = lst[r + 1][0] if r + 1 < len(lst) and lst[r + 1][0] < L else L + 1
+            if n and any(o < q < stop for q in range((o // chunk + 1) * chunk, stop, chunk)):
+                got.add("inside a replacement")
+            for d, name in ((1, "one byte behind a replacement"), (2, "two bytes behind a replacement")):
+                if n and (stop + d) % chunk == 0 and stop + d < total and at + d <= min(nxt, L):
+                    got.add(name)
+            if run[r] >= 3 and stop and stop % chunk == 0 and stop < total and nxt > at:
+                got.add("behind three touching spans")
+    return got
 
 
 def span_lists(span_off, spans):

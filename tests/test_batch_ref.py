@@ -9,8 +9,10 @@ import numpy as np
 import pytest
 
 import batch_ref
+import edit_o2_ref
 import find_ref
 import recode_ref
+import splice_table_ref
 from conftest import GOLDEN_DIR, expected_file, golden, golden_names
 from oracle import mh_oracle
 
@@ -66,6 +68,24 @@ def test_pack_equals_recode_ref_under_a_destination_with_drops(x, y, order):
     assert np.array_equal(p.payload, payload) and np.array_equal(p.pay_off, off)
     assert np.array_equal(p.nbits, nbits) and np.array_equal(p.dropped, dropped)
     assert all(np.array_equal(a, w[3]) for a, w in zip(p.slices, want))
+
+
+@pytest.mark.parametrize("order", [0, 1, 2])
+def test_pack_under_the_covering_destination_equals_the_oracle_s_compress_of_every_spliced_message(order):
+    """The first case with an order-2 source, a destination of this order and the oracle's own prev0: its table-spliced messages
+    under the covering destination, message by message."""
+    case = next(c for c in batch_ref.draw_cases() if c.orders == (2, order) and c.world().prev0 == recode_ref.PREV0)
+    x = case.expected_table()
+    o = mh_oracle.Model.from_counts(case.cover_counts(), order)
+    lens, _ = o.codes_o2() if order == 2 else o.codes()
+    p = x.cover
+    assert len(x.spliced) == case.n_streams and x.spliced != case.world().messages and not p.dropped.any()
+    for i, m in enumerate(x.spliced):
+        blob, nbits = o.compress(m)
+        assert int(p.nbits[i]) == nbits, (case.id, i)
+        assert p.payload[int(p.pay_off[i]):int(p.pay_off[i + 1])].tobytes() == blob[1:], (case.id, i)
+        if order < 2:
+            assert np.array_equal(p.slices[i], recode_ref.index_slice(lens, m, order, case.chunk)), (case.id, i)
 
 
 @pytest.mark.parametrize("x,y", [("input_a.txt", "input_b.txt"), ("input_ipsum.txt", "union_ipsum_wiki"), ("input_wiki_cpp.txt", "union_ipsum_wiki"),
@@ -220,20 +240,67 @@ def edit_stats():
                             for p in known),
                  rarest=min(np.bincount(np.frombuffer(b"".join(w.messages), dtype=np.uint8), minlength=256)[sorted(set(b"".join(w.messages)))]),
                  rows=batch_ref.dict_rows_in_lds(case, e.states, e.classes))
-        if 2 not in case.orders:
-            x = case.expected()
-            per = batch_ref.span_lists(e.span_off, e.spans)
-            src = batch_ref.pack(w.messages, *case.codes("src"), case.orders[0], w.prev0, c)
-            mask = batch_ref.span_mask(w.messages, e.span_off, e.spans)
-            chunks = lambda k: (k + c - 1) // c
-            s.update(spliced=sum(len(m) for m in x.spliced[1]),
-                     emptied=any(l and not len(y) for l, y in zip(ln, x.spliced[0])),
-                     first_chunk=any(b == 0 and c <= t < ln[i] for i, lst in enumerate(per) for b, t in lst),
-                     grows=any(chunks(len(y)) > chunks(l) for l, y in zip(ln, x.spliced[1])),
-                     drops=max(int(p.dropped.sum()) for p in [x.edit, x.edit_all] + x.splice),
-                     near=max(int(src.used[mask].max()), int(x.edit.used[mask].max())) if mask.any() else 0)
+        x = case.expected()
+        per = batch_ref.span_lists(e.span_off, e.spans)
+        src = batch_ref.pack(w.messages, *case.codes("src"), case.orders[0], w.prev0, c)
+        mask = batch_ref.span_mask(w.messages, e.span_off, e.spans)
+        chunks = lambda k: (k + c - 1) // c
+        s.update(spliced=sum(len(m) for m in x.spliced[1]),
+                 emptied=any(l and not len(y) for l, y in zip(ln, x.spliced[0])),
+                 first_chunk=any(b == 0 and c <= t < ln[i] for i, lst in enumerate(per) for b, t in lst),
+                 grows=any(chunks(len(y)) > chunks(l) for l, y in zip(ln, x.spliced[1])),
+                 drops=max(int(p.dropped.sum()) for p in [x.edit, x.edit_all] + x.splice),
+                 near=max(int(src.used[mask].max()), int(x.edit.used[mask].max())) if mask.any() else 0,
+                 cover_drops=sum(int(p.dropped.sum()) for p in (x.edit_cover, x.edit_all_cover)) if 2 in case.orders else 0)
+        s.update(table_stats(case, src))
         out.append(s)
     return out
+
+
+def splices(case):
+    """Whether the case runs a table splice: no order-2 side, or an order-2 source."""
+    return case.orders[0] == 2 or 2 not in case.orders
+
+
+def table_stats(case, src):
+    """The third part of a case (src: the packer's form of the messages under the source model)."""
+    w, t = case.world(), case.table()
+    c, ln = case.chunk, [len(m) for m in w.messages]
+    per = batch_ref.tagged_span_lists(t.span_off, t.spans, t.tags)
+    s = dict(t=t, well_formed=all(splice_table_ref.well_formed([p[:2] for p in lst]) for lst in per),
+             insertions=batch_ref.insertions(w.messages, t.span_off, t.spans, t.tags, t.reps, c),
+             output_seams=batch_ref.output_seams(w.messages, t.span_off, t.spans, t.tags, t.reps, c))
+    if not splices(case):
+        return s
+    x = case.expected_table()
+    # a lane that starts at source position c or 2 c: the two OUTPUT bytes in front of it are not the two source bytes there
+    moved = 0
+    for F in (c, 2 * c):
+        ctx = edit_o2_ref.start_context(w.messages, t.span_off, t.spans, t.tags, t.reps, F, w.prev0)
+        moved += sum(1 for m, v in zip(w.messages, ctx) if v is not None and v != (m[F - 2] << 8) | m[F - 1])
+    # a span that ends one byte in front of a seam F and x[F - 1] in no span (the look-back's F = end + 1): the earlier of the two
+    # output bytes in front of F is not x[F - 2]
+    stops = [{min(end, ln[i]) for b, end, _ in lst if b < ln[i]} for i, lst in enumerate(per)]
+    ends = 0
+    for F in sorted({p + 1 for i, st in enumerate(stops) for p in st if (p + 1) % c == 0 and p + 1 < ln[i]}):
+        ctx = edit_o2_ref.start_context(w.messages, t.span_off, t.spans, t.tags, t.reps, F, w.prev0)
+        ends += sum(1 for i, (m, v) in enumerate(zip(w.messages, ctx)) if v is not None and F - 1 in stops[i] and v >> 8 != m[F - 2]
+                    and not any(b < F <= end for b, end, _ in per[i]))
+    # the codes within two symbols of a span: of the source symbols around it, and of the output symbols in and around what it put in
+    in_off, out_off = np.concatenate([[0], np.cumsum(ln)]), x.out_sym_off.astype(np.int64)
+    near_in, near_out = np.zeros(int(in_off[-1]), dtype=bool), np.zeros(int(out_off[-1]), dtype=bool)
+    for i, lst in enumerate(per):
+        for b, end, _ in lst:
+            if b < ln[i]:
+                near_in[in_off[i] + max(b - 2, 0):in_off[i] + b] = True
+                near_in[in_off[i] + min(end, ln[i]):in_off[i] + min(end + 2, ln[i])] = True
+        for what, o, n, _, _ in batch_ref.splice_pieces(ln[i], lst, t.reps):
+            if what == "rep":
+                near_out[max(out_off[i] + o - 2, out_off[i]):min(out_off[i] + o + n + 2, out_off[i + 1])] = True
+    used = [src.used[near_in], x.packed.used[near_out], x.cover.used[near_out]]
+    s.update(table_spliced=sum(len(m) for m in x.spliced), table_cover_drops=int(x.cover.dropped.sum()), moved=moved, ends=ends,
+             table_near=max(int(u.max()) for u in used if u.size))
+    return s
 
 
 def test_every_case_s_dictionary_spans_map_and_replacements():
@@ -276,6 +343,69 @@ def count_edits(pred, cases=lambda s: True):
     return sum(1 for s in edit_stats() if cases(s) and pred(s))
 
 
+EDITS_DIGEST = "7688c5f6e1108deb796419bbe4d0073da90388920da09e93200d51b0e73f2acd"
+
+
+def test_no_edits_moved_when_the_tables_were_added():
+    """SHA-256 over every case's dictionary, replacements, byte map and span list, computed at the commit before Case.table()
+    existed: the third part of a case draws from a generator of its own."""
+    h = hashlib.sha256()
+    for case in batch_ref.draw_cases():
+        e = case.edits()
+        case.table()                                                # (building it must not move anything either)
+        h.update(repr((case.id, e.fold, e.map_kind, e.lacking, e.rep_lacks)).encode())
+        for part in (e.dictionary, e.reps, [e.byte_map]):
+            h.update(len(part).to_bytes(8, "little"))
+            for m in part:
+                h.update(len(m).to_bytes(8, "little") + bytes(m))
+        for a in (e.span_off, e.spans):
+            a = np.ascontiguousarray(a, dtype=np.uint64)
+            h.update(a.size.to_bytes(8, "little") + a.tobytes())
+    assert h.hexdigest() == EDITS_DIGEST
+
+
+def test_every_case_s_table_and_tagged_list():
+    for s in edit_stats():
+        case, t, e = s["case"], s["t"], s["e"]
+        here = set(b"".join(case.world().messages))
+        assert 2 <= len(t.reps) <= 8 and t.reps[t.empty] == b"" and e.reps[1] in t.reps, case.id
+        assert all(len(r) <= batch_ref.DICT_MAX_LEN for r in t.reps), case.id
+        assert set(b"".join(t.reps)) - here <= ({e.lacking} if e.lacking is not None else set()), case.id
+        assert s["well_formed"], case.id
+        assert len(t.span_off) == case.n_streams + 1 and int(t.span_off[-1]) == len(t.spans) == len(t.tags) <= batch_ref.SPAN_CAP, case.id
+        assert int(t.tags.max()) < len(t.reps), case.id
+        want = splice_table_ref.merge_tagged(e.hit_off, e.records, e.hit_pattern)
+        assert all(np.array_equal(a, b) for a, b in zip(t.merged, want)), case.id
+        assert s["cover_drops"] == 0, case.id                       # the masked messages under the covering destination
+        if splices(case):
+            assert s["table_spliced"] <= batch_ref.SPLICED_BYTES and s["table_cover_drops"] == 0, case.id
+    for k in (2, 8):
+        assert count_edits(lambda s: len(s["t"].reps) == k) >= 5, k
+    assert count_edits(lambda s: len(set(s["t"].reps)) < len(s["t"].reps)) >= 10                 # two equal entries
+    assert count_edits(lambda s: s["e"].lacking is not None and any(s["e"].lacking in r for r in s["t"].reps)) >= 10
+    assert count_edits(lambda s: s["t"].tags.size and len(set(s["t"].tags.tolist())) == len(s["t"].reps)) >= 48   # every entry in use
+
+
+def test_coverage_of_the_tables_of_the_fixed_case_list():
+    """What the table-splice families of the fuzz must keep reaching, from the references alone: every kind of insertion under
+    both kernel families, and, under an order-2 source, the starts of output chunks and of lanes that the look-back has to get
+    right."""
+    plain = lambda s: 2 not in s["case"].orders
+    o2 = lambda s: s["case"].orders[0] == 2
+    assert count_edits(plain) == 64 and count_edits(o2) == 17
+    assert count_edits(lambda s: s["case"].orders[1] == 2 and not o2(s)) == 15                  # the refusals
+    for name in batch_ref.INSERTIONS:
+        assert count_edits(lambda s: name in s["insertions"], plain) >= 10, name
+        assert count_edits(lambda s: name in s["insertions"], o2) >= 4, name
+    for name in batch_ref.OUTPUT_SEAMS:
+        assert count_edits(lambda s: name in s["output_seams"], o2) >= 3, name
+    assert count_edits(lambda s: s["case"].deep and s["table_near"] > 32, o2) >= 3
+    assert count_edits(lambda s: s["moved"] > 0, o2) >= 12
+    # the earlier of the two bytes reaches the output only through an order-2 destination (an order-0 / 1 one reads the later)
+    assert count_edits(lambda s: s["ends"] > 0, o2) >= 8
+    assert count_edits(lambda s: s["ends"] > 0, lambda s: s["case"].orders == (2, 2)) >= 4
+
+
 def test_coverage_of_the_edits_of_the_fixed_case_list():
     """What the dictionary, span, edit and splice families of the fuzz must keep reaching, from the references alone."""
     plain = lambda s: 2 not in s["case"].orders                     # the cases that edit and splice (no order-2 side)
@@ -299,7 +429,8 @@ def test_coverage_of_the_edits_of_the_fixed_case_list():
 
 def test_the_new_files_leave_no_test_out():
     here = os.path.dirname(os.path.abspath(__file__))
-    for name in ("batch_ref.py", "test_batch_ref.py", "test_gpu_batch_fuzz.py", "test_dict_abi.py", "edit_ref.py", "splice_ref.py", "find_ref.py"):
+    for name in ("batch_ref.py", "test_batch_ref.py", "test_gpu_batch_fuzz.py", "test_dict_abi.py", "edit_ref.py", "splice_ref.py", "find_ref.py",
+                 "splice_table_ref.py", "edit_o2_ref.py", "test_edit_o2_ref.py", "test_gpu_workspace_reuse.py"):
         with open(os.path.join(here, name)) as f:
             text = f.read()
         for word in ("pytest.sk", "mark.sk", "importorsk", "xfa"):

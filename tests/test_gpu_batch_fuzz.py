@@ -1,9 +1,15 @@
 """Seeded differential fuzz of the batch call family on the GPU: every case of tests/batch_ref.py goes through every batch call
 of include/mh.h — encode, histograms, decode (indexed, index-free, segment states), lookups, search, coded histogram, re-code,
-per-stream models and banks, dictionary search, spans from hits, masked and splicing re-code (the last two for the 64 cases
-without an order-2 side: they refuse one) — and every result is compared exactly with the references of tests/batch_ref.py: the
-CPU oracle's code tables and plain numpy on the original messages, never another call of the library.  tests/test_batch_ref.py pins those
-references and the edges that the case list reaches.
+per-stream models and banks, dictionary search, spans from hits (plain and tagged), masked and splicing re-code, the table
+splice (a replacement per span, insertions) and their order-2 forms — and every result is compared exactly with the references
+of tests/batch_ref.py: the CPU oracle's code tables and plain numpy on the original messages, never another call of the library.
+tests/test_batch_ref.py pins those references and the edges that the case list reaches.
+
+The 64 cases without an order-2 side run edit, splice and splice_table; the 32 with one run edit_o2 (all five pairs of orders) and
+splice_table_o2: the 17 with an order-2 source splice, the 15 with an order-0 / 1 source under an order-2 destination must be
+refused with MH_ERR_ARG.  The order-2 forms are compared under the case's destination and under a covering one, trained on the
+originals and every edited form: nothing is dropped there, so every byte at the edge of a span has a code that depends on its
+exact context, and a wrong look-back cannot hide behind a drop.
 
 One test per case; its id names the case.  A case runs every family and then reports all that differed, so one failure does
 not hide the next.  The decoders read the reference's payloads and index, not the encoder's output."""
@@ -43,7 +49,7 @@ class Rig:
         self.c, self.p0, self.msgs = case.chunk, self.w.prev0, self.w.messages
         self.n = len(self.msgs)
         self.joined = b"".join(self.msgs)
-        self.bad, self.set = [], None
+        self.bad, self.set, self.cover = [], None, None
         (sc, sl), (dc, dl) = case.counts("src"), case.counts("dst")
         self.S, self.D = mhc.Model.from_counts(sc, self.so, max_len=sl), mhc.Model.from_counts(dc, self.do, max_len=dl)
         self.rs = batch_ref.pack(self.msgs, *case.codes("src"), self.so, self.p0, self.c)
@@ -282,17 +288,19 @@ class Rig:
         self.ok(count["rc"], count["status"], tag + " count only")
         self.check(all(same(count[k], got[k]) for k in ("out_off", "nbits", "dropped", "out_sym_off") if k in got), tag + ": count only")
 
-    def edit_with(self, fn, ref, what):
-        """fn: a device form of the masked re-code, reading the reference's batch `ref`."""
+    def edit_with(self, fn, ref, what, dst=None, want=None):
+        """fn: a device form of the masked re-code, reading the reference's batch `ref`; want: (with the span list, everywhere)
+        under dst, by default the case's destination."""
         e, x = self.case.edits(), self.case.expected()
+        dst, (edit, edit_all) = dst or self.D, want or (x.edit, x.edit_all)
         for indexed in (True, False):
             tag = "%s indexed=%s" % (what, indexed)
             src, kw = self.source(ref, indexed)
-            got = fn(self.D, *src, e.byte_map, e.span_off, e.spans, **kw)
-            self.same_recode(got, x.edit, tag)
-            self.same_counts(fn(self.D, *src, e.byte_map, e.span_off, e.spans, count_only=True, **kw), got, tag)
+            got = fn(dst, *src, e.byte_map, e.span_off, e.spans, **kw)
+            self.same_recode(got, edit, tag)
+            self.same_counts(fn(dst, *src, e.byte_map, e.span_off, e.spans, count_only=True, **kw), got, tag)
         src, kw = self.source(ref, self.case.index % 2 == 0)
-        self.same_recode(fn(self.D, *src, e.byte_map, None, None, **kw), x.edit_all, what + " everywhere")
+        self.same_recode(fn(dst, *src, e.byte_map, None, None, **kw), edit_all, what + " everywhere")
 
     def edit(self):
         e, x = self.case.edits(), self.case.expected()
@@ -328,6 +336,90 @@ class Rig:
         if self.eligible(self.case):
             self.splice_with(self.model_set()[2].recode_splice, self.model_set()[0], "each splice")
 
+    # ---- tagged spans from hits ----
+    def spans_tagged(self):
+        e, t = self.case.edits(), self.case.table()
+        want_off, want, want_tag = t.merged
+        plain_off, plain = edit_ref.merge_hits(e.hit_off, e.records)
+        self.check(same(want_off, plain_off) and same(want, plain), "spans_tagged: the two references' spans")
+        for fn in (self.mhc.spans_from_hits_tagged, self.mhc.dev_spans_from_hits_tagged):
+            span_off, spans, tags, rc = fn(e.hit_off, e.records, e.hit_pattern)
+            self.check(rc == self.mhc.MH_OK and same(span_off, want_off) and same(spans, want), fn.__name__ + ": spans")
+            self.check(same(tags, want_tag), fn.__name__ + ": tags")
+
+    # ---- the table splice ----
+    def covering(self):
+        """The covering destination's model."""
+        if self.cover is None:
+            self.cover = self.mhc.Model.from_counts(self.case.cover_counts(), self.do)
+        return self.cover
+
+    def table_with(self, fn, ref, what, dst, want, out_sym_off, tags, reps, span_off, spans, counts=True):
+        """fn: a device form of the table splice, reading the reference's batch `ref`; want: batch_ref.Packed under dst."""
+        for indexed in (True, False):
+            tag = "%s indexed=%s" % (what, indexed)
+            src, kw = self.source(ref, indexed)
+            got = fn(dst, *src, tags, reps, span_off, spans, **kw)
+            self.same_recode(got, want, tag, out_sym_off)
+            if counts:
+                self.same_counts(fn(dst, *src, tags, reps, span_off, spans, count_only=True, **kw), got, tag)
+
+    def one_entry_tables(self, fn, what):
+        """A table of one entry, every span of the untagged list under tag 0: the single replacement's expectation."""
+        e, x = self.case.edits(), self.case.expected()
+        for k, rep in enumerate(e.reps):
+            self.table_with(fn, self.rs, "%s, one entry of %d bytes" % (what, len(rep)), self.D, x.splice[k], x.out_sym_off[k],
+                            np.zeros(len(e.spans), dtype=np.uint32), [rep], e.span_off, e.spans, counts=False)
+
+    def table_host(self, fn, what, dst, want, out_sym_off):
+        t = self.case.table()
+        for indexed in (True, False):
+            src, kw = self.source(self.rs, indexed)
+            self.same_recode(fn(dst, *src, t.tags, t.reps, t.span_off, t.spans, **kw), want, "%s (host form) indexed=%s" % (what, indexed), out_sym_off)
+
+    def splice_table(self):
+        t, x = self.case.table(), self.case.expected_table()
+        mine = (t.tags, t.reps, t.span_off, t.spans)
+        self.table_with(self.S.dev_recode_splice_table_batch, self.rs, "splice_table", self.D, x.packed, x.out_sym_off, *mine)
+        self.one_entry_tables(self.S.dev_recode_splice_table_batch, "splice_table")
+        if self.case.index % 4 == 0:
+            self.table_host(self.S.recode_splice_table_batch, "splice_table", self.D, x.packed, x.out_sym_off)
+        if self.eligible(self.case):
+            self.table_with(self.model_set()[2].recode_splice_table, self.model_set()[0], "each splice_table", self.D, x.packed, x.out_sym_off, *mine)
+
+    # ---- order 2 in editing and splicing ----
+    def edit_o2(self):
+        e, x = self.case.edits(), self.case.expected()
+        fn = self.S.dev_recode_edit_batch_o2
+        self.edit_with(fn, self.rs, "edit_o2 (%s)" % e.map_kind)
+        self.edit_with(fn, self.rs, "edit_o2 (%s), covering" % e.map_kind, self.covering(), (x.edit_cover, x.edit_all_cover))
+        if self.case.index % 4 == 0:
+            for indexed in (True, False):
+                src, kw = self.source(self.rs, indexed)
+                self.same_recode(self.S.recode_edit_batch_o2(self.D, *src, e.byte_map, span_off=e.span_off, spans=e.spans, **kw), x.edit,
+                                 "edit_o2 (host form) indexed=%s" % indexed)
+
+    def splice_table_o2(self):
+        t = self.case.table()
+        mine = (t.tags, t.reps, t.span_off, t.spans)
+        fn = self.S.dev_recode_splice_table_batch_o2
+        if self.so < 2:                                           # an order-0 / 1 source under an order-2 destination: refused
+            for call, what in ((fn, "device"), (self.S.recode_splice_table_batch_o2, "host")):
+                src, kw = self.source(self.rs, True)
+                try:
+                    call(self.D, *src, *mine, **kw)
+                    self.check(False, "splice_table_o2 (%s form): no refusal of an order-%d source" % (what, self.so))
+                except self.mhc.MhError as err:
+                    self.check(err.status == self.mhc.MH_ERR_ARG, "splice_table_o2 (%s form): refused with %d" % (what, err.status))
+            return
+        x = self.case.expected_table()
+        self.table_with(fn, self.rs, "splice_table_o2", self.D, x.packed, x.out_sym_off, *mine)
+        self.table_with(fn, self.rs, "splice_table_o2, covering", self.covering(), x.cover, x.out_sym_off, *mine)
+        self.one_entry_tables(fn, "splice_table_o2")
+        if self.case.index % 4 == 0:
+            self.table_host(self.S.recode_splice_table_batch_o2, "splice_table_o2", self.D, x.packed, x.out_sym_off)
+            self.table_host(self.S.recode_splice_table_batch_o2, "splice_table_o2, covering", self.covering(), x.cover, x.out_sym_off)
+
 
     # ---- all of them ----
     @staticmethod
@@ -339,8 +431,8 @@ class Rig:
         """Every family that runs for this case, in order."""
         fams = [self.encode, self.decode, self.lookups, self.search_and_feed_back, self.coded_histogram, self.recode]
         fams += [self.each, self.bank] if self.eligible(self.case) else []
-        fams += [self.dictionary_search, self.spans]
-        return fams + [self.edit, self.splice] if 2 not in self.case.orders else fams      # (edit and splice refuse an order-2 model)
+        fams += [self.dictionary_search, self.spans, self.spans_tagged]
+        return fams + ([self.edit, self.splice, self.splice_table] if 2 not in self.case.orders else [self.edit_o2, self.splice_table_o2])
 
     def run_all(self):
         for fn in self.families():
