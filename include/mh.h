@@ -1577,6 +1577,111 @@ int mh_recode_splice_table_batch_o2(const mh_model *src, const mh_model *dst, co
                                     uint64_t index_cap, uint64_t *dropped, int32_t *stream_status);
 
 /* ---------------------------------------------------------------------------------------------------------------------
+ * SELECTING RECORDS OF BATCHES (extension, parity unpinned) — a compressed batch is a record store, and these calls change
+ * which records it holds without decoding one: keep the records a search hit (grep with compressed output), drop them, drop
+ * the records whose verdict is not MH_OK, put the records in another order, append one batch to another.  Every stream of a
+ * batch is byte-aligned and self-contained, so its payload bytes move as they are.  Its index slice cannot be moved by
+ * hand: slice i sits at mh_batch_index_base(sym_off[i], i, chunk) = sym_off[i] / chunk + i, so moving, dropping or appending
+ * one record shifts every slice behind it by an amount that depends on all symbol counts in front, and two batches' index
+ * arrays laid end to end are silently wrong.  This section does that relocation.
+ * Model-free: no model is passed and nothing is decoded, so the calls serve batches under a shared order-0/1 model, an
+ * order-2 model, a model set or a bank view alike; index entries are copied as 64-bit words whatever their format.
+ *   - Sources.  `sources` is a HOST array of n_sources = 1 .. MH_SELECT_MAX_SOURCES batch descriptions (their pointers are
+ *     device pointers in the device call, host pointers in the host form); it is copied into the kernel arguments and may
+ *     be freed when the call returns.  prev0 is ignored.  d_sym_off and d_index may be NULL per source; d_payload may be
+ *     NULL when pay_total is 0 or nothing is gathered (count only).  0 sources or more than 8: MH_ERR_ARG.
+ *   - Picks.  d_picks[n_picks]: pick j is (source << 56) | stream.  MH_SELECT_NONE (all ones) yields an empty output stream
+ *     with status MH_OK.  Repeats and any order are allowed; n_picks may be 0.
+ *   - Output.  The output batch is byte for byte what the batch encoder of the sources' model (mh_dev_encode_batch,
+ *     mh_dev_encode_batch_o2, mh_dev_encode_each) writes for the picked messages in pick order: d_out_nbits[j] is copied,
+ *     d_out_off[n_picks + 1] is the exclusive scan of ceil(nbits / 8), the payload is the first ceil(nbits / 8) bytes of
+ *     the source stream, d_out_sym_off[n_picks + 1] is the scan of the symbol counts (written when every source has
+ *     d_sym_off, else it must be NULL: MH_ERR_ARG), and slice j (ceil(m_j / chunk) entries) is copied to
+ *     mh_batch_index_base(out_sym_off[j], j, chunk).  Index entries in the gaps between slices are left untouched.  No
+ *     payload byte is written at or behind out_off[n_picks] rounded up to 16, or at or behind cap, whichever is smaller.
+ *   - Index.  An index is written only when every source has d_sym_off and a d_index with this same chunk_symbols (the
+ *     block's; a power of two in [MH_CHUNK_MIN, MH_CHUNK_MAX]); otherwise a non-NULL d_out_index is MH_ERR_ARG before any
+ *     launch.  d_out_index == NULL: no index is written and chunk_symbols is ignored.
+ *   - Checks on the device.  Every source's offsets are checked as the batch decoders check them (d_pay_off[0] == 0,
+ *     [n] == pay_total, non-decreasing; the same of d_sym_off with sym_total when given): a failure is MH_ERR_ARG through
+ *     mh_dev_status(d_ws) and the call stops.  A pick whose source or stream number is out of range gets MH_ERR_ARG in
+ *     d_pick_status[j] (may be NULL) for that pick alone and an empty output stream; so does a pick whose nbits exceeds 8 x
+ *     its payload bytes.  The other picks are unaffected; mh_dev_status(d_ws) keeps the first error.
+ *   - Capacity.  out_off[n_picks] > cap, or mh_batch_index_capacity(out_sym_off[n_picks], n_picks, chunk) > index_cap with
+ *     an index: MH_ERR_CAPACITY through mh_dev_status(d_ws); offsets, lengths and statuses are still written, neither payload
+ *     nor index is.  d_out_payload == NULL: count only (cap ignored).
+ *   - Pointer, size and n_sources rules are refused before any launch: a NULL block, struct_size other than sizeof of the
+ *     struct (the block can grow later), NULL sources, d_picks (with n_picks > 0), d_out_off, d_out_nbits or d_ws, a source
+ *     without d_pay_off, d_nbits or (when payload is gathered and pay_total > 0) d_payload, d_out_payload or d_ws not 16-byte
+ *     aligned: MH_ERR_ARG; a workspace below mh_dev_select_batch_workspace: MH_ERR_CAPACITY.  Without a device:
+ *     MH_ERR_NO_DEVICE.
+ *   - The call allocates nothing and makes no host synchronisation; the number of launches depends only on count-only versus
+ *     full and on whether an index is written.  All arithmetic is 64-bit.  The outputs must not overlap the sources.
+ *   - Side information.  What the caller keeps per stream beside the batch — bank entry numbers for mh_dev_model_set_pick,
+ *     CRCs, keys — is gathered by the caller with the same pick list.
+ * mh_dev_picks_from_hits turns a per-stream predicate into a pick list without a host wait.  Stream i of n_streams is kept
+ * iff d_hit_off (n + 1, from any find call; may be NULL) is NULL or the stream has at least one hit — with
+ * MH_PICKS_WITHOUT_HITS in flags: has none — and d_stream_status (n, may be NULL) is NULL or d_stream_status[i] == MH_OK.
+ * d_picks[n_streams] gets the kept streams in ascending order as picks of `source` (< MH_SELECT_MAX_SOURCES), then
+ * MH_SELECT_NONE up to n; d_n_kept (one uint64) their number.  The trailing empty streams leave every prefix of the selected
+ * batch a valid batch of n_kept streams, so the caller passes n_picks = n_streams at once and trims when it later reads
+ * n_kept.  Unknown flag bits, NULL d_picks (n > 0), d_n_kept or d_ws: MH_ERR_ARG.
+ * The launch context.  The declarations with a positional `void *stream` and the argument blocks with a `void *stream`
+ * member are two closed, counted sets, each driven on a non-default stream by a test module of its own.  The calls of this
+ * section take a block whose workspace and stream are one nested mh_launch, as the batch is a nested mh_coded_batch_args; a
+ * third module counts and drives them.  The promise is the same: stream-ordered, no allocation, no synchronisation.
+ * Host forms mh_select_batch and mh_picks_from_hits: positional, host pointers, plain C++ — no device is needed, as for
+ * mh_spans_from_hits.  Results and verdicts are the device calls'; they return the first pick's error, else MH_ERR_CAPACITY.
+ * Left out: the CLI; re-ordering the tables of a per-stream model set (the caller re-indexes its set); selecting in place;
+ * sources whose index chunk sizes differ.
+ * --------------------------------------------------------------------------------------------------------------------- */
+#define MH_SELECT_MAX_SOURCES 8u
+#define MH_SELECT_NONE        0xFFFFFFFFFFFFFFFFull
+#define MH_PICKS_WITHOUT_HITS 1u
+typedef struct mh_launch {
+    void *d_ws;
+    size_t ws_bytes;
+    void *stream;
+} mh_launch;
+typedef struct mh_select_args {
+    uint32_t struct_size;
+    const mh_coded_batch_args *sources;
+    uint32_t n_sources;
+    const uint64_t *d_picks;
+    size_t n_picks;
+    uint8_t *d_out_payload;
+    size_t cap;
+    uint64_t *d_out_off;
+    uint64_t *d_out_nbits;
+    uint64_t *d_out_sym_off;
+    uint64_t *d_out_index;
+    uint64_t index_cap;
+    uint32_t chunk_symbols;
+    int32_t *d_pick_status;
+    mh_launch launch;
+} mh_select_args;
+typedef struct mh_picks_args {
+    uint32_t struct_size;
+    const uint64_t *d_hit_off;
+    const int32_t *d_stream_status;
+    size_t n_streams;
+    uint32_t source;
+    uint32_t flags;
+    uint64_t *d_picks;
+    uint64_t *d_n_kept;
+    mh_launch launch;
+} mh_picks_args;
+size_t mh_dev_select_batch_workspace(size_t total_source_streams, size_t n_picks);
+int mh_dev_select_batch(const mh_select_args *a);
+size_t mh_dev_picks_from_hits_workspace(size_t n_streams);
+int mh_dev_picks_from_hits(const mh_picks_args *a);
+int mh_select_batch(const mh_coded_batch_args *sources, uint32_t n_sources, const uint64_t *picks, size_t n_picks,
+                    uint8_t *out_payload, size_t cap, uint64_t *out_off, uint64_t *out_nbits, uint64_t *out_sym_off,
+                    uint64_t *out_index, uint64_t index_cap, uint32_t chunk_symbols, int32_t *pick_status);
+int mh_picks_from_hits(const uint64_t *hit_off, const int32_t *stream_status, size_t n_streams, uint32_t source, uint32_t flags,
+                       uint64_t *picks, uint64_t *n_kept);
+
+/* ---------------------------------------------------------------------------------------------------------------------
  * SEGMENT STATES OF INDEX-FREE ORDER-2 BATCHES (extension, parity unpinned) — the _o2 twins of the segment-state calls of
  * the next section, for a batch coded under one shared order-2 model (what mh_dev_encode_batch_o2 writes, stored without
  * its sidecar index).  Same arguments, layouts, workspace arithmetic, launch sequence and guarantees as the twins; what

@@ -80,6 +80,8 @@ EXPORTS = [
     "mh_recode_splice_table_batch",
     "mh_dev_recode_edit_batch_o2_workspace", "mh_dev_recode_splice_table_batch_o2_workspace", "mh_dev_recode_edit_batch_o2",
     "mh_dev_recode_splice_table_batch_o2", "mh_recode_edit_batch_o2", "mh_recode_splice_table_batch_o2",
+    "mh_dev_select_batch_workspace", "mh_dev_select_batch", "mh_dev_picks_from_hits_workspace", "mh_dev_picks_from_hits",
+    "mh_select_batch", "mh_picks_from_hits",
 ]
 FIND_MAX_POSITIONS = 64                    # include/mh.h MH_FIND_MAX_POSITIONS
 FIND_FOLD_ASCII = 1                        # include/mh.h MH_FIND_FOLD_ASCII
@@ -90,6 +92,9 @@ DICT_MAX_OUTPUTS = 1 << 20                 # include/mh.h MH_DICT_MAX_OUTPUTS
 BANK_MAX = 64                              # include/mh.h MH_BANK_MAX
 BANK_NONE = 0xFFFFFFFF                     # include/mh.h MH_BANK_NONE
 BATCH_WALK_MAX_BITS = 1 << 23              # include/mh.h MH_BATCH_WALK_MAX_BITS
+SELECT_MAX_SOURCES = 8                     # include/mh.h MH_SELECT_MAX_SOURCES
+SELECT_NONE = 0xFFFFFFFFFFFFFFFF           # include/mh.h MH_SELECT_NONE
+PICKS_WITHOUT_HITS = 1                     # include/mh.h MH_PICKS_WITHOUT_HITS
 
 
 class MhError(RuntimeError):
@@ -123,6 +128,54 @@ class RecodeSpliceO2Args(C.Structure):
                 ("d_out_off", C.c_void_p), ("d_out_nbits", C.c_void_p), ("d_out_sym_off", C.c_void_p), ("d_out_index", C.c_void_p),
                 ("index_cap", C.c_uint64), ("d_dropped", C.c_void_p), ("d_stream_status", C.c_void_p), ("d_ws", C.c_void_p),
                 ("ws_bytes", C.c_size_t), ("stream", C.c_void_p)]
+
+
+class Launch(C.Structure):
+    """include/mh.h mh_launch: the workspace and the stream of a call that takes a block."""
+    _fields_ = [("d_ws", C.c_void_p), ("ws_bytes", C.c_size_t), ("stream", C.c_void_p)]
+
+
+class SelectArgs(C.Structure):
+    """include/mh.h mh_select_args."""
+    _fields_ = [("struct_size", C.c_uint32), ("sources", C.POINTER(CodedBatchArgs)), ("n_sources", C.c_uint32), ("d_picks", C.c_void_p),
+                ("n_picks", C.c_size_t), ("d_out_payload", C.c_void_p), ("cap", C.c_size_t), ("d_out_off", C.c_void_p),
+                ("d_out_nbits", C.c_void_p), ("d_out_sym_off", C.c_void_p), ("d_out_index", C.c_void_p), ("index_cap", C.c_uint64),
+                ("chunk_symbols", C.c_uint32), ("d_pick_status", C.c_void_p), ("launch", Launch)]
+
+
+class PicksArgs(C.Structure):
+    """include/mh.h mh_picks_args."""
+    _fields_ = [("struct_size", C.c_uint32), ("d_hit_off", C.c_void_p), ("d_stream_status", C.c_void_p), ("n_streams", C.c_size_t),
+                ("source", C.c_uint32), ("flags", C.c_uint32), ("d_picks", C.c_void_p), ("d_n_kept", C.c_void_p), ("launch", Launch)]
+
+
+def _addr(v):
+    return v.value if isinstance(v, C.c_void_p) else v
+
+
+def coded_batches(sources):
+    """A ctypes array of mh_coded_batch_args from (payload, pay_off, nbits, n_streams, pay_total, sym_off, sym_total, index,
+    chunk_symbols) tuples of addresses and numbers."""
+    arr = (CodedBatchArgs * max(len(sources), 1))()
+    for b, (payload, pay_off, nbits, n, pay_total, sym_off, sym_total, index, chunk) in zip(arr, sources):
+        b.d_payload, b.d_pay_off, b.d_nbits, b.n_streams, b.pay_total = _addr(payload), _addr(pay_off), _addr(nbits), n, pay_total
+        b.d_sym_off, b.sym_total, b.d_index, b.chunk_symbols = _addr(sym_off), sym_total, _addr(index), chunk
+    return arr
+
+
+def select_args(sources, n_sources, picks, n_picks, out_payload, cap, out_off, out_nbits, out_sym_off, out_index, index_cap, chunk_symbols,
+                pick_status, ws, ws_bytes, stream):
+    """An mh_select_args block (sources: a coded_batches array, which the block keeps alive)."""
+    blk = SelectArgs(C.sizeof(SelectArgs), sources, n_sources, _addr(picks), n_picks, _addr(out_payload), cap, _addr(out_off), _addr(out_nbits),
+                     _addr(out_sym_off), _addr(out_index), index_cap, chunk_symbols, _addr(pick_status), Launch(_addr(ws), ws_bytes, _addr(stream)))
+    blk.keep = sources
+    return blk
+
+
+def picks_args(hit_off, stream_status, n_streams, source, flags, picks, n_kept, ws, ws_bytes, stream):
+    """An mh_picks_args block."""
+    return PicksArgs(C.sizeof(PicksArgs), _addr(hit_off), _addr(stream_status), n_streams, source, flags, _addr(picks), _addr(n_kept),
+                     Launch(_addr(ws), ws_bytes, _addr(stream)))
 
 
 def args_block(cls, *a):
@@ -424,6 +477,14 @@ def lib():
         l.mh_dev_recode_splice_table_batch_o2.argtypes = [C.POINTER(RecodeSpliceO2Args)]
         l.mh_recode_edit_batch_o2.argtypes = l.mh_recode_edit_batch.argtypes
         l.mh_recode_splice_table_batch_o2.argtypes = l.mh_recode_splice_table_batch.argtypes
+        l.mh_dev_select_batch_workspace.argtypes = [sz, sz]
+        l.mh_dev_select_batch_workspace.restype = sz
+        l.mh_dev_select_batch.argtypes = [C.POINTER(SelectArgs)]
+        l.mh_dev_picks_from_hits_workspace.argtypes = [sz]
+        l.mh_dev_picks_from_hits_workspace.restype = sz
+        l.mh_dev_picks_from_hits.argtypes = [C.POINTER(PicksArgs)]
+        l.mh_select_batch.argtypes = [C.POINTER(CodedBatchArgs), u32, vp, sz, vp, sz, vp, vp, vp, vp, u64, u32, vp]
+        l.mh_picks_from_hits.argtypes = [vp, vp, sz, u32, u32, vp, vp]
         _lib = l
     return _lib
 
@@ -1173,6 +1234,114 @@ def dev_spans_from_hits(hit_off, hits, hit_cap=None):
     m = int(so[n])
     assert m <= cap and (sp[2 * m:] == FIND_FILL).all(), "pairs written at or beyond the spans"
     return so[:n + 1], sp[:2 * m].reshape(-1, 2), rc
+
+
+class Selected:
+    """What a select call wrote: payload and index are the whole buffers (guard bytes and gap entries included), status the
+    return code (host form) or mh_dev_status (device form)."""
+
+
+def _select_sources(batches, upload):
+    """(coded_batches array, the arrays or device buffers it points into) of (payload, pay_off, nbits, sym_off, index, chunk)
+    tuples of numpy arrays; payload (a batch that is only counted), sym_off and index may be None."""
+    rows, keep = [], []
+    for payload, pay_off, nbits, sym_off, index, chunk in batches:
+        pay_off = np.ascontiguousarray(pay_off, dtype=np.uint64)
+        n = len(pay_off) - 1
+        parts = [None if payload is None else _u8(payload), pay_off, np.ascontiguousarray(nbits, dtype=np.uint64),
+                 None if sym_off is None else np.ascontiguousarray(sym_off, dtype=np.uint64),
+                 None if index is None else np.ascontiguousarray(index, dtype=np.uint64)]
+        held = [None if a is None else upload(a) for a in parts]
+        keep.append(held)
+        at = [None if h is None else (h.ptr if isinstance(h, DeviceBuffer) else (h.ctypes.data if h.size else None)) for h in held]
+        rows.append((at[0], at[1], at[2], n, int(pay_off[n]), at[3], int(parts[3][n]) if parts[3] is not None else 0, at[4], chunk))
+    return coded_batches(rows), keep
+
+
+def _select_sizes(batches, picks, chunk_symbols, cap, index_cap):
+    """Output sizes large enough for any pick list: every pick at most the longest source stream."""
+    n = len(picks)
+    most = max([int(np.diff(np.asarray(b[1], dtype=np.uint64).astype(np.int64)).max(initial=0)) for b in batches] + [0])
+    syms = max([int(np.diff(np.asarray(b[3], dtype=np.uint64).astype(np.int64)).max(initial=0)) for b in batches if b[3] is not None] + [0])
+    cap = n * most if cap is None else cap
+    if index_cap is None:
+        index_cap = n * syms // chunk_symbols + n + 1 if chunk_symbols else 0
+    return cap, index_cap
+
+
+def select_batch(batches, picks, chunk_symbols=0, cap=None, index_cap=None, want_sym=True, want_index=True, fill=0xA5):
+    """mh_select_batch (host, no device) on (payload, pay_off, nbits, sym_off, index, chunk) tuples of numpy arrays: a Selected.
+    Buffers are prefilled with `fill`; cap / index_cap None: room for any pick list."""
+    picks = np.ascontiguousarray(picks, dtype=np.uint64)
+    n = picks.size
+    src, keep = _select_sources(batches, lambda a: a)
+    cap, index_cap = _select_sizes(batches, picks, chunk_symbols, cap, index_cap)
+    r = Selected()
+    word = int.from_bytes(bytes([fill]) * 8, "little")
+    r.payload = np.full(cap + 64, fill, dtype=np.uint8)
+    r.out_off, r.nbits = np.full(n + 1, word, dtype=np.uint64), np.full(n, word, dtype=np.uint64)
+    r.sym_off = np.full(n + 1, word, dtype=np.uint64) if want_sym else None
+    r.index = np.full(index_cap + 8, word, dtype=np.uint64) if want_index and chunk_symbols else None
+    r.pick_status = np.full(n, -99, dtype=np.int32)
+    at = lambda a: None if a is None else a.ctypes.data
+    r.status = lib().mh_select_batch(src, len(batches), _ptr(picks), n, at(r.payload), cap, at(r.out_off), _ptr(r.nbits), at(r.sym_off),
+                                     at(r.index), index_cap, chunk_symbols, _ptr(r.pick_status))
+    r.cap, r.index_cap = cap, index_cap
+    return r
+
+
+def dev_select_batch(batches, picks, chunk_symbols=0, cap=None, index_cap=None, want_sym=True, want_index=True, count_only=False, fill=0xA5):
+    """One mh_dev_select_batch call on uploaded batches, every output and the workspace prefilled with `fill`: a Selected."""
+    l = lib()
+    picks = np.ascontiguousarray(picks, dtype=np.uint64)
+    n = picks.size
+    src, keep = _select_sources(batches, lambda a: DeviceBuffer(max(a.nbytes, 16), a if a.size else None))
+    cap, index_cap = _select_sizes(batches, picks, chunk_symbols, cap, index_cap)
+    filled = lambda nbytes: DeviceBuffer(max(nbytes, 16), np.full(max(nbytes, 16), fill, dtype=np.uint8))
+    d_picks = DeviceBuffer(max(picks.nbytes, 16), picks if n else None)
+    d_out = None if count_only else filled(cap + 64)
+    d_oo, d_nb, d_st = filled((n + 1) * 8), filled(n * 8), filled(n * 4)
+    d_so = filled((n + 1) * 8) if want_sym else None
+    d_idx = filled((index_cap + 8) * 8) if want_index and chunk_symbols else None
+    wsb = l.mh_dev_select_batch_workspace(sum(len(b[1]) - 1 for b in batches), n)
+    d_ws = filled(wsb)
+    p = lambda d: None if d is None else d.ptr
+    blk = select_args(src, len(batches), d_picks.ptr, n, p(d_out), cap, d_oo.ptr, d_nb.ptr, p(d_so), p(d_idx), index_cap, chunk_symbols, d_st.ptr,
+                      d_ws.ptr, wsb, None)
+    _check(l.mh_dev_select_batch(C.byref(blk)), "mh_dev_select_batch")
+    r = Selected()
+    r.status = l.mh_dev_status(d_ws.ptr, None)
+    r.payload = None if d_out is None else d_out.download()[:cap + 64]
+    r.out_off, r.nbits, r.pick_status = d_oo.download(np.uint64)[:n + 1], d_nb.download(np.uint64)[:n], d_st.download(np.int32)[:n]
+    r.sym_off = None if d_so is None else d_so.download(np.uint64)[:n + 1]
+    r.index = None if d_idx is None else d_idx.download(np.uint64)[:index_cap + 8]
+    r.cap, r.index_cap = cap, index_cap
+    return r
+
+
+def picks_from_hits(hit_off, stream_status, n_streams, source=0, flags=0):
+    """mh_picks_from_hits (host, no device): (picks[n_streams], n_kept)."""
+    ho = None if hit_off is None else np.ascontiguousarray(hit_off, dtype=np.uint64)
+    st = None if stream_status is None else np.ascontiguousarray(stream_status, dtype=np.int32)
+    picks, kept = np.full(n_streams, 0xA5A5A5A5A5A5A5A5, dtype=np.uint64), np.zeros(1, dtype=np.uint64)
+    _check(lib().mh_picks_from_hits(None if ho is None else ho.ctypes.data, None if st is None or not st.size else st.ctypes.data, n_streams, source,
+                                    flags, _ptr(picks), kept.ctypes.data), "mh_picks_from_hits")
+    return picks, int(kept[0])
+
+
+def dev_picks_from_hits(hit_off, stream_status, n_streams, source=0, flags=0):
+    """One mh_dev_picks_from_hits call on uploaded arrays, outputs and workspace prefilled with 0xA5: (picks[n_streams], n_kept)."""
+    l = lib()
+    up = lambda a, t: None if a is None else DeviceBuffer(max(np.asarray(a).size * np.dtype(t).itemsize, 16), np.ascontiguousarray(a, dtype=t))
+    d_ho, d_st = up(hit_off, np.uint64), up(stream_status, np.int32)
+    filled = lambda nbytes: DeviceBuffer(max(nbytes, 16), np.full(max(nbytes, 16), 0xA5, dtype=np.uint8))
+    wsb = l.mh_dev_picks_from_hits_workspace(n_streams)
+    d_picks, d_kept, d_ws = filled(n_streams * 8), filled(8), filled(wsb)
+    p = lambda d: None if d is None else d.ptr
+    blk = picks_args(p(d_ho), p(d_st), n_streams, source, flags, d_picks.ptr, d_kept.ptr, d_ws.ptr, wsb, None)
+    _check(l.mh_dev_picks_from_hits(C.byref(blk)), "mh_dev_picks_from_hits")
+    _check(l.mh_dev_status(d_ws.ptr, None), "mh_dev_picks_from_hits status")
+    return d_picks.download(np.uint64)[:n_streams], int(d_kept.download(np.uint64)[0])
 
 
 def spans_from_hits_tagged(hit_off, hits, hit_pattern, hit_cap=None):
