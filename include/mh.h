@@ -1428,7 +1428,7 @@ int mh_recode_splice_batch(const mh_model *src, const mh_model *dst, const uint8
  * priority by pattern order (the CLI: the earlier line of the pattern file wins).  Overflow and bad offsets as untagged; the
  * device form keeps its guarantees (no allocation, no host synchronisation, a fixed number of launches).
  * Left out: order 2 on either side; appending at len(x) (a span that begins there is ignored); replacements longer than
- * MH_SPLICE_MAX_REP; back-references or any replacement computed from the matched bytes.
+ * MH_SPLICE_MAX_REP; back-references (a table computed from the matched bytes is TOKENS FROM MATCHED BYTES below).
  * --------------------------------------------------------------------------------------------------------------------- */
 int mh_spans_from_hits_tagged(const uint64_t *hit_off, const uint64_t *hits, const uint32_t *hit_pattern, uint64_t hit_cap,
                               size_t n_streams, uint64_t *span_off, uint64_t *spans, uint32_t *span_tag);
@@ -1501,7 +1501,7 @@ int mh_recode_splice_table_batch(const mh_model *src, const mh_model *dst, const
  * is never refused for a stream over MH_BATCH_WALK_MAX_BITS.
  * Left out: the CLI (--order2 with --recode or --redact stays refused); model sets; the table splice of an order-0/1 source
  * under an order-2 destination; and everything the table splice leaves out: appending at len(x), replacements longer than
- * MH_SPLICE_MAX_REP, back-references or any replacement computed from the matched bytes.
+ * MH_SPLICE_MAX_REP, back-references (a table computed from the matched bytes is TOKENS FROM MATCHED BYTES below).
  * --------------------------------------------------------------------------------------------------------------------- */
 typedef struct mh_coded_batch_args {
     const uint8_t *d_payload;
@@ -1680,6 +1680,91 @@ int mh_select_batch(const mh_coded_batch_args *sources, uint32_t n_sources, cons
                     uint64_t *out_index, uint64_t index_cap, uint32_t chunk_symbols, int32_t *pick_status);
 int mh_picks_from_hits(const uint64_t *hit_off, const int32_t *stream_status, size_t n_streams, uint32_t source, uint32_t flags,
                        uint64_t *picks, uint64_t *n_kept);
+
+/* ---------------------------------------------------------------------------------------------------------------------
+ * TOKENS FROM MATCHED BYTES (extension, parity unpinned) — pseudonymisation: a replacement table whose entry for span r is
+ * computed from the bytes the span matched, so that a store scrubbed with `<EMAIL:9f3a61c2d07b4e15>` can still be joined,
+ * counted and de-duplicated by the redacted value: equal bytes give equal tokens under a secret key, and the key cannot be
+ * recovered from the tokens.  The matched bytes never reach memory: a lane decodes a symbol into a register, absorbs it
+ * and drops it.  The table is what mh_dev_recode_splice_table_batch, _each and _batch_o2 take.
+ *   - Digest.  SipHash-2-4 (64-bit result, 128-bit key: k0, k1 are the key's two little-endian words) of
+ *     x[begin, min(end, len(x))), x being stream i's message as the source's batch decoder returns it.  With MH_TOKEN_FOLD in
+ *     flags, ASCII A-Z are absorbed as a-z.  Other flag bits: MH_ERR_ARG.  mh_span_token_digest is the same function of a
+ *     byte string in host memory (plain C++, no device): the token of a known value, to query a scrubbed store.
+ *   - Formats.  Format f is (prefix, hex digits, suffix): d_fmt_off has 2 * n_formats + 1 entries, the prefix is
+ *     d_fmt_bytes[d_fmt_off[2f] .. d_fmt_off[2f + 1]), the suffix d_fmt_bytes[d_fmt_off[2f + 1] .. d_fmt_off[2f + 2]), and
+ *     d_hex_digits[f] is 0 .. 16.  A format longer than MH_SPLICE_MAX_REP in all, decreasing offsets, d_fmt_off[0] != 0,
+ *     more than 16 digits, or n_formats == 0 with a non-empty span list: MH_ERR_ARG through mh_dev_status(d_ws) and the call
+ *     stops, as for bad d_pay_off.
+ *   - Token.  Span r's entry is prefix, the first hex_digits characters of "%016x" of the digest, suffix, under format
+ *     d_span_tag[r] (a NULL tag array: format 0).  hex_digits 0 gives a constant entry, an empty format a deletion, so one
+ *     call serves a mixed policy.
+ *   - Output.  A table of n_reps entries, n_reps being the caller's bound on the spans (the hit_cap of the search):
+ *     d_rep_off[n_reps + 1], the exclusive scan of the entry lengths, entries behind the last span empty; d_rep_bytes, at
+ *     most rep_cap bytes (d_rep_off[n_reps] > rep_cap: MH_ERR_CAPACITY through mh_dev_status(d_ws), no byte written, the
+ *     offsets valid; NULL: count only); d_rep_tag[r] = r for r < n_reps, the tag array of the splice; d_stream_status[n]
+ *     (required).  The splice is then called with d_rep_tag as d_span_tag and this n_reps.
+ *   - Span lists are the table splice's: begin <= end <= next begin.  A list that breaks the rule, or a tag >= n_formats,
+ *     fails its stream alone with MH_ERR_ARG.  Every entry of a failed stream is empty.  A span with begin >= len(x) gets
+ *     its format with the digest of the empty string (the splice ignores it).  More spans than n_reps
+ *     (d_span_off[n] > n_reps): MH_ERR_CAPACITY through mh_dev_status(d_ws) and the call stops.
+ *   - Indexed source.  One lane per span.  The lane starts at the index entry of chunk begin / chunk_symbols, decodes and
+ *     drops the symbols in front, absorbs the span's symbols, and decodes on over chunk boundaries.  At every boundary it
+ *     reaches, and at len(x), its bit position must equal the next entry's (nbits at the end): else MH_ERR_CORRUPT.
+ *   - Index-free source.  One lane per stream walks from bit 0 in prev0, digests the stream's spans in list order and walks
+ *     on to nbits.  Streams over MH_BATCH_WALK_MAX_BITS: MH_ERR_ARG.  d_sym_off is neither read nor written.
+ *   - Verdicts.  ONLY THE STREAMS WITH SPANS ARE DECODED: a stream without spans gets MH_OK, whatever its payload holds.
+ *     An index-free stream with spans gets the verdict of the batch decoder's walk.  An indexed stream with spans is judged
+ *     on the chunks its spans touch, by the batch decoder's rules (entries against each other and nbits, a code that does
+ *     not end, the bit position at a boundary): damage in a chunk no span touches is not seen.  nbits beyond the payload of
+ *     a stream with spans: MH_ERR_ARG.  Bad d_pay_off, d_sym_off (under an index) or d_span_off stop the call.
+ *   - Models.  Exactly one of src (a shared model of order 0, 1 or 2) and src_set (stream i under the set's model i,
+ *     n_streams == mh_model_set_size, a bank view included) is given, else MH_ERR_ARG.
+ *   - The call makes no allocation and no host synchronisation; the number of launches is the same for every call.  d_ws:
+ *     16-byte aligned, at least mh_dev_span_tokens_workspace(n_streams, n_reps) bytes (8 per entry), else MH_ERR_CAPACITY.
+ *   - The declaration.  The block says what is done, the mh_launch where: a shape of its own, counted and driven on a
+ *     non-default stream by a test module of its own.  struct_size must equal sizeof of the struct; a NULL block or launch,
+ *     NULL d_span_off, d_rep_off, d_rep_tag (n_reps > 0), d_stream_status (n_streams > 0), d_fmt_off or d_hex_digits
+ *     (n_formats > 0): MH_ERR_ARG before any launch.  Without a device: MH_ERR_NO_DEVICE.
+ *   - Host form mh_span_tokens_batch: positional, host pointers, a shared model; every rule of the formats and the offsets
+ *     is checked before a device is touched (MH_ERR_ARG); n_reps is span_off[n_streams]; rep_off is required, rep_bytes NULL
+ *     counts; an index-free batch with a stream over MH_BATCH_WALK_MAX_BITS is indexed first, and a stream that this
+ *     indexing fails keeps that verdict and has empty entries, as every failed stream.  Returns the first failed stream's
+ *     error, else MH_ERR_CAPACITY when the table does not fit.
+ * Known limit: one lane per span is correct for any length but serial: a span of 64 KiB takes one lane's time for 64 KiB.
+ * Left out: back-references and capture groups; tokens over MH_SPLICE_MAX_REP (255) bytes; de-duplicating equal table entries.
+ * --------------------------------------------------------------------------------------------------------------------- */
+#define MH_TOKEN_FOLD 1u
+typedef struct mh_span_tokens_args {
+    uint32_t struct_size;
+    const mh_model *src;
+    const mh_model_set *src_set;
+    mh_coded_batch_args batch;
+    const uint64_t *d_span_off;
+    const uint64_t *d_spans;
+    const uint32_t *d_span_tag;
+    uint8_t key[16];
+    uint32_t flags;
+    const uint64_t *d_fmt_off;
+    const uint8_t *d_fmt_bytes;
+    const uint8_t *d_hex_digits;
+    size_t n_formats;
+    size_t n_reps;
+    uint64_t *d_rep_off;
+    uint8_t *d_rep_bytes;
+    size_t rep_cap;
+    uint32_t *d_rep_tag;
+    int32_t *d_stream_status;
+} mh_span_tokens_args;
+uint64_t mh_span_token_digest(const uint8_t *key, const uint8_t *bytes, size_t n, uint32_t flags);
+size_t mh_dev_span_tokens_workspace(size_t n_streams, size_t n_reps);
+int mh_dev_span_tokens_batch(const mh_span_tokens_args *a, const mh_launch *launch);
+int mh_span_tokens_batch(const mh_model *src, const uint8_t *payload, const uint64_t *pay_off, const uint64_t *nbits,
+                         size_t n_streams, uint8_t prev0, const uint64_t *sym_off, const uint64_t *index,
+                         uint32_t chunk_symbols, const uint64_t *span_off, const uint64_t *spans, const uint32_t *span_tag,
+                         const uint8_t *key, uint32_t flags, const uint64_t *fmt_off, const uint8_t *fmt_bytes,
+                         const uint8_t *hex_digits, size_t n_formats, uint64_t *rep_off, uint8_t *rep_bytes, size_t rep_cap,
+                         uint32_t *rep_tag, int32_t *stream_status);
 
 /* ---------------------------------------------------------------------------------------------------------------------
  * SEGMENT STATES OF INDEX-FREE ORDER-2 BATCHES (extension, parity unpinned) — the _o2 twins of the segment-state calls of

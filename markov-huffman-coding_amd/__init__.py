@@ -82,6 +82,7 @@ EXPORTS = [
     "mh_dev_recode_splice_table_batch_o2", "mh_recode_edit_batch_o2", "mh_recode_splice_table_batch_o2",
     "mh_dev_select_batch_workspace", "mh_dev_select_batch", "mh_dev_picks_from_hits_workspace", "mh_dev_picks_from_hits",
     "mh_select_batch", "mh_picks_from_hits",
+    "mh_span_token_digest", "mh_dev_span_tokens_workspace", "mh_dev_span_tokens_batch", "mh_span_tokens_batch",
 ]
 FIND_MAX_POSITIONS = 64                    # include/mh.h MH_FIND_MAX_POSITIONS
 FIND_FOLD_ASCII = 1                        # include/mh.h MH_FIND_FOLD_ASCII
@@ -95,6 +96,8 @@ BATCH_WALK_MAX_BITS = 1 << 23              # include/mh.h MH_BATCH_WALK_MAX_BITS
 SELECT_MAX_SOURCES = 8                     # include/mh.h MH_SELECT_MAX_SOURCES
 SELECT_NONE = 0xFFFFFFFFFFFFFFFF           # include/mh.h MH_SELECT_NONE
 PICKS_WITHOUT_HITS = 1                     # include/mh.h MH_PICKS_WITHOUT_HITS
+TOKEN_FOLD = 1                             # include/mh.h MH_TOKEN_FOLD
+SPLICE_MAX_REP = 255                       # include/mh.h MH_SPLICE_MAX_REP
 
 
 class MhError(RuntimeError):
@@ -149,6 +152,15 @@ class PicksArgs(C.Structure):
                 ("source", C.c_uint32), ("flags", C.c_uint32), ("d_picks", C.c_void_p), ("d_n_kept", C.c_void_p), ("launch", Launch)]
 
 
+class SpanTokensArgs(C.Structure):
+    """include/mh.h mh_span_tokens_args."""
+    _fields_ = [("struct_size", C.c_uint32), ("src", C.c_void_p), ("src_set", C.c_void_p), ("batch", CodedBatchArgs),
+                ("d_span_off", C.c_void_p), ("d_spans", C.c_void_p), ("d_span_tag", C.c_void_p), ("key", C.c_uint8 * 16),
+                ("flags", C.c_uint32), ("d_fmt_off", C.c_void_p), ("d_fmt_bytes", C.c_void_p), ("d_hex_digits", C.c_void_p),
+                ("n_formats", C.c_size_t), ("n_reps", C.c_size_t), ("d_rep_off", C.c_void_p), ("d_rep_bytes", C.c_void_p),
+                ("rep_cap", C.c_size_t), ("d_rep_tag", C.c_void_p), ("d_stream_status", C.c_void_p)]
+
+
 def _addr(v):
     return v.value if isinstance(v, C.c_void_p) else v
 
@@ -176,6 +188,33 @@ def picks_args(hit_off, stream_status, n_streams, source, flags, picks, n_kept, 
     """An mh_picks_args block."""
     return PicksArgs(C.sizeof(PicksArgs), _addr(hit_off), _addr(stream_status), n_streams, source, flags, _addr(picks), _addr(n_kept),
                      Launch(_addr(ws), ws_bytes, _addr(stream)))
+
+
+def span_tokens_args(src, src_set, batch, span_off, spans, span_tag, key, flags, fmt_off, fmt_bytes, hex_digits, n_formats, n_reps,
+                     rep_off, rep_bytes, rep_cap, rep_tag, stream_status):
+    """An mh_span_tokens_args block.  batch: one coded_batches tuple (with prev0 appended: ten values); key: 16 bytes."""
+    payload, pay_off, nbits, n, pay_total, sym_off, sym_total, index, chunk, prev0 = batch
+    blk = SpanTokensArgs()
+    blk.struct_size = C.sizeof(SpanTokensArgs)
+    blk.src, blk.src_set = _addr(src), _addr(src_set)
+    b = blk.batch
+    b.d_payload, b.d_pay_off, b.d_nbits, b.n_streams, b.pay_total, b.prev0 = _addr(payload), _addr(pay_off), _addr(nbits), n, pay_total, prev0
+    b.d_sym_off, b.sym_total, b.d_index, b.chunk_symbols = _addr(sym_off), sym_total, _addr(index), chunk
+    blk.d_span_off, blk.d_spans, blk.d_span_tag = _addr(span_off), _addr(spans), _addr(span_tag)
+    key = bytes(key)
+    if len(key) != 16:
+        raise ValueError("a token key has 16 bytes")
+    blk.key = (C.c_uint8 * 16)(*key)
+    blk.flags = flags
+    blk.d_fmt_off, blk.d_fmt_bytes, blk.d_hex_digits, blk.n_formats = _addr(fmt_off), _addr(fmt_bytes), _addr(hex_digits), n_formats
+    blk.n_reps, blk.d_rep_off, blk.d_rep_bytes, blk.rep_cap = n_reps, _addr(rep_off), _addr(rep_bytes), rep_cap
+    blk.d_rep_tag, blk.d_stream_status = _addr(rep_tag), _addr(stream_status)
+    return blk
+
+
+def launch_args(ws, ws_bytes, stream):
+    """An mh_launch: where a call that takes one runs."""
+    return Launch(_addr(ws), ws_bytes, _addr(stream))
 
 
 def args_block(cls, *a):
@@ -485,6 +524,12 @@ def lib():
         l.mh_dev_picks_from_hits.argtypes = [C.POINTER(PicksArgs)]
         l.mh_select_batch.argtypes = [C.POINTER(CodedBatchArgs), u32, vp, sz, vp, sz, vp, vp, vp, vp, u64, u32, vp]
         l.mh_picks_from_hits.argtypes = [vp, vp, sz, u32, u32, vp, vp]
+        l.mh_span_token_digest.argtypes = [vp, vp, sz, u32]
+        l.mh_span_token_digest.restype = u64
+        l.mh_dev_span_tokens_workspace.argtypes = [sz, sz]
+        l.mh_dev_span_tokens_workspace.restype = sz
+        l.mh_dev_span_tokens_batch.argtypes = [C.POINTER(SpanTokensArgs), C.POINTER(Launch)]
+        l.mh_span_tokens_batch.argtypes = [vp, vp, vp, vp, sz, u8, vp, vp, u32, vp, vp, vp, vp, u32, vp, vp, vp, sz, vp, vp, sz, vp, vp]
         _lib = l
     return _lib
 
@@ -1397,6 +1442,113 @@ def histogram_coded_batch_o2(src, order, payload, pay_off, nbits, prev0=PREV0, s
     counts, status, rc = src.dev_histogram_coded_o2(order, payload, pay_off, nbits, prev0, sym_off, index, chunk_symbols)
     _check(rc, "mh_dev_histogram_coded_batch_o2")
     return counts
+
+
+# ---- tokens from matched bytes (include/mh.h, "TOKENS FROM MATCHED BYTES") -------------------------------------------------
+def span_token_digest(key, data, flags=0):
+    """mh_span_token_digest (host, no device): the keyed 64-bit digest of a byte string."""
+    k, d = _u8(bytes(key)), _u8(data)
+    if k.size != 16:
+        raise ValueError("a token key has 16 bytes")
+    return int(lib().mh_span_token_digest(k.ctypes.data, _ptr(d), d.size, flags))
+
+
+def token_formats(formats):
+    """(fmt_off[2 n + 1], fmt_bytes, hex_digits[n]) of a list of (prefix, hex_digits, suffix)."""
+    off, blob = [0], b""
+    for prefix, _, suffix in formats:
+        blob += bytes(prefix)
+        off.append(len(blob))
+        blob += bytes(suffix)
+        off.append(len(blob))
+    return np.asarray(off, dtype=np.uint64), _u8(blob), np.asarray([h for _, h, _ in formats], dtype=np.uint8)
+
+
+def dev_span_tokens(src, payload, pay_off, nbits, span_off, spans, span_tag, formats, key, flags=0, prev0=PREV0, sym_off=None, index=None,
+                    chunk_symbols=0, n_reps=None, rep_cap=None, count_only=False, ws_n_reps=None, fmt_arrays=None):
+    """One mh_dev_span_tokens_batch call on an uploaded batch under src (a Model or a ModelSet), with FIND_GUARD words of
+    FIND_FILL behind rep_off, rep_tag and the statuses, RANGE_GUARD bytes behind rep_bytes and the workspace filled with 0xFF
+    beforehand.  n_reps None: the number of spans; rep_cap None: a count-only call first, then one with exactly rep_off[n_reps]
+    bytes.  ws_n_reps: what the workspace is sized for.  fmt_arrays: (fmt_off, fmt_bytes, hex_digits) as they are, instead of
+    `formats`.  Returns dict(rep_off, rep_bytes or None, rep_tag, status, rc = mh_dev_status); a call the library refuses
+    before any launch raises MhError.  Asserts that nothing changed behind the outputs or at or beyond rep_off[n_reps] bytes."""
+    l = lib()
+    n, pay_total, d_pl, d_po, d_nb, so, d_idx = _dev_source(payload, pay_off, nbits, sym_off, index)
+    indexed = index is not None
+    G, F = FIND_GUARD, FIND_FILL
+    sof = np.ascontiguousarray(span_off, dtype=np.uint64)
+    sp = np.zeros(0, dtype=np.uint64) if spans is None else np.ascontiguousarray(spans, dtype=np.uint64).reshape(-1)
+    nr = sp.size // 2 if n_reps is None else n_reps
+    foff, fb, hexd = fmt_arrays if fmt_arrays is not None else token_formats(formats)
+    foff, fb, hexd = np.ascontiguousarray(foff, dtype=np.uint64), _u8(fb), np.ascontiguousarray(hexd, dtype=np.uint8)
+    d_sof = DeviceBuffer(sof.nbytes, sof)
+    d_sp = DeviceBuffer(max(sp.nbytes, 16), sp if sp.size else None)
+    d_tg = None
+    if span_tag is not None:
+        tg = np.ascontiguousarray(span_tag, dtype=np.uint32)
+        d_tg = DeviceBuffer(max(tg.nbytes, 16), tg if tg.size else None)
+    d_foff = DeviceBuffer(foff.nbytes, foff)
+    d_fb = DeviceBuffer(max(fb.size, 16), np.concatenate([fb, np.zeros(16, dtype=np.uint8)])[:max(fb.size, 16)])
+    d_hex = DeviceBuffer(max(hexd.size, 16), np.concatenate([hexd, np.zeros(16, dtype=np.uint8)])[:max(hexd.size, 16)])
+    d_so = DeviceBuffer(so.nbytes, so) if indexed else None
+    is_set = isinstance(src, ModelSet)
+
+    def call(room, with_bytes):
+        wsb = l.mh_dev_span_tokens_workspace(n, nr if ws_n_reps is None else ws_n_reps)
+        d_ws = DeviceBuffer(wsb, np.full(wsb, 0xFF, dtype=np.uint8))
+        d_roff = DeviceBuffer((nr + 1 + G) * 8, np.full(nr + 1 + G, F, dtype=np.uint64))
+        d_rtag = DeviceBuffer((nr + 2 * G) * 4, np.full(nr + 2 * G, F & 0xFFFFFFFF, dtype=np.uint32))
+        d_st = DeviceBuffer((n + 2 * G) * 4, np.full(n + 2 * G, 99, dtype=np.int32))
+        d_rb = DeviceBuffer(room + RANGE_GUARD + 16, np.full(room + RANGE_GUARD + 16, RANGE_FILL, dtype=np.uint8)) if with_bytes else None
+        blk = span_tokens_args(None if is_set else src.handle, src.handle if is_set else None,
+                               (d_pl.ptr, d_po.ptr, d_nb.ptr, n, pay_total, d_so.ptr if d_so else None, int(so[n]) if indexed else 0,
+                                d_idx.ptr if d_idx else None, chunk_symbols if indexed else 0, prev0),
+                               d_sof.ptr, d_sp.ptr, d_tg.ptr if d_tg else None, key, flags, d_foff.ptr, d_fb.ptr, d_hex.ptr, len(hexd), nr,
+                               d_roff.ptr, d_rb.ptr if d_rb else None, room, d_rtag.ptr, d_st.ptr)
+        launch = launch_args(d_ws.ptr, wsb, None)
+        _check(l.mh_dev_span_tokens_batch(C.byref(blk), C.byref(launch)), "mh_dev_span_tokens_batch")
+        rc = l.mh_dev_status(d_ws.ptr, None)
+        roff, rtag, st = d_roff.download(np.uint64), d_rtag.download(np.uint32), d_st.download(np.int32)
+        assert (roff[nr + 1:] == F).all() and (rtag[nr:] == F & 0xFFFFFFFF).all() and (st[n:] == 99).all(), "words written behind an output"
+        res = dict(rep_off=roff[:nr + 1], rep_tag=rtag[:nr], status=st[:n], rc=rc, rep_bytes=None)
+        if d_rb:
+            out = d_rb.download(np.uint8)
+            used = min(int(roff[nr]), room) if rc == MH_OK or roff[nr] <= room else 0
+            if roff[nr] == F:
+                used = 0                                                # (the call stopped before the offsets were written)
+            assert (out[used:] == RANGE_FILL).all(), "bytes written at or beyond rep_off[n_reps]"
+            res["rep_bytes"] = out[:used].copy()
+        if indexed:
+            assert np.array_equal(d_so.download(np.uint64), so), "sym_off written"
+        return res
+
+    if count_only:
+        return call(0, False)
+    if rep_cap is None:
+        rep_cap = int(call(0, False)["rep_off"][nr])
+    return call(rep_cap, True)
+
+
+def span_tokens_batch(model, payload, pay_off, nbits, span_off, spans, span_tag, formats, key, flags=0, prev0=PREV0, sym_off=None, index=None,
+                      chunk_symbols=0, rep_cap=None):
+    """mh_span_tokens_batch, the host form: (rep_off, rep_bytes, rep_tag, status, return code)."""
+    payload, pay_off, nbits = _u8(payload), np.ascontiguousarray(pay_off, dtype=np.uint64), np.ascontiguousarray(nbits, dtype=np.uint64)
+    n = len(pay_off) - 1
+    sof = np.ascontiguousarray(span_off, dtype=np.uint64)
+    sp = np.ascontiguousarray(spans, dtype=np.uint64).reshape(-1)
+    nr = sp.size // 2
+    tg = None if span_tag is None else np.ascontiguousarray(span_tag, dtype=np.uint32)
+    foff, fb, hexd = token_formats(formats)
+    k = _u8(bytes(key))
+    so = None if sym_off is None else np.ascontiguousarray(sym_off, dtype=np.uint64)
+    idx = None if index is None else np.ascontiguousarray(index, dtype=np.uint64)
+    cap = SPLICE_MAX_REP * nr if rep_cap is None else rep_cap
+    roff, rb, rtag, st = np.zeros(nr + 1, dtype=np.uint64), np.zeros(max(cap, 1), dtype=np.uint8), np.zeros(max(nr, 1), dtype=np.uint32), np.zeros(max(n, 1), dtype=np.int32)
+    rc = lib().mh_span_tokens_batch(model.handle, _ptr(payload), pay_off.ctypes.data, nbits.ctypes.data, n, prev0, so.ctypes.data if so is not None else None,
+                                    idx.ctypes.data if idx is not None else None, chunk_symbols, sof.ctypes.data, _ptr(sp), _ptr(tg) if tg is not None else None,
+                                    k.ctypes.data, flags, foff.ctypes.data, _ptr(fb), _ptr(hexd), len(hexd), roff.ctypes.data, rb.ctypes.data, cap,
+                                    rtag.ctypes.data, st.ctypes.data)
+    return roff, rb[:min(int(roff[nr]), cap)], rtag[:nr], st[:n], rc
 
 
 class Model:

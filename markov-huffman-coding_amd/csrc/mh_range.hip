@@ -12,101 +12,26 @@
 //   lookup_kernel<Tables, INDEXED>  the same over pay_off / nbits / sym_off / index slices, or one lane per lookup walking an
 //                                   index-free stream from bit 0 in context prev0
 // Only the offsets of the streams a lookup names are read, so the cost does not depend on the batch's stream count.
-//   Tables   the symbol decoder of a lane, one policy per model (mhb::Model).  SharedTables: the order-0/1 tables in LDS as
-//            load_tables lays them out, one workgroup per CU.  SetTables: stream i's slots in L2 (mh_each.hip's decode_sym).
-//            Shared2Tables: the model's order-2 tables in L2 as dec_idx_kernel<Shared2> reads them (65 536 contexts: no LDS
-//            copy; a lane is a chain of dependent gathers, so the unit size sets the latency).  Set and Shared2: workgroups of
-//            256 lanes, eight per CU.  A policy also names the format of an index entry (POS, entry_ctx) and the bound its
-//            kernels compile under.
+//   Tables   the symbol decoder of a lane, one policy per model (mhb::Model): SharedTables, SetTables, Shared2Tables, with
+//            item_of and tables_room in mh_range_dev.hpp, which the span tokens (mh_token.hip) share.
 //   Format   where a unit of a single stream starts and what bounds it: the part of include/mh.h in which the two orders
 //            differ (Format01, Format2).  Everything else of range_kernel is written once.
 // The scan, the bit source of a window and ByteOut are mh_batch_dev.hpp's, used as they are.
-#include "mh_range.h"
-#include "mh_batch_dev.hpp"
-#include "mh_decode_dev.hpp"
-#include "mh_dev.hpp"
-#include "mh_each_dev.hpp"
-#include "../../include/mh.h"
+#include "mh_range_dev.hpp"
 
 namespace mhq {
 
 using mhb::BATCH_STATUS_ARG;
 using mhb::Model;
-using mhk::BitCursor;
-using mhk::BitSrc;
-using mhk::DecTables;
 
 namespace {
 
-constexpr int LDS_MAX = 163840;
-// The LDS tables take up to 160 KiB: one workgroup per CU.  Below SPREAD lookups per CU the shared-model lookups run 256-lane
-// workgroups instead, so that their lanes spread over four times as many CUs (measured on an MI355X: 3-23 % faster at 1 K-16 K
-// lookups, the same above).
-constexpr uint64_t SPREAD = 256;
 constexpr uint32_t FINE2_NONE = 0xFFFFu;            // an order-2 fine entry whose distance does not fit 16 bits
 
 __device__ __forceinline__ void item_fail(int *item_status, int *status, uint64_t j, int mh_code, int dev_code) {
     atomicCAS(&item_status[j], MH_OK, mh_code);
     mhb::fail(status, dev_code);
 }
-
-// ------------------------------------------------------------------------------------------------ the symbol decoders
-// next() decodes one symbol in the lane's context ctx and advances ctx.  P: RangeParams or LookupParams (both carry tab).
-//   BOUND, PER_CU   the launch bound the kernels compile under and the workgroups a CU holds
-//   POS, entry_ctx  the bit offset and the context of an index entry
-
-// an order-0/1 index entry, and a model that is the same for every stream
-struct Entry01 {
-    static constexpr uint64_t POS = MH_INDEX_BIT_MASK;
-    static __device__ __forceinline__ uint32_t entry_ctx(uint64_t e) { return uint32_t(e >> 56); }
-    __device__ __forceinline__ void stream(const LookupParams &, uint64_t) {}
-};
-
-// the shared model: LDS tables, one context table per byte (order 0: the same table 256 times)
-struct SharedTables : Entry01 {
-    static constexpr int BOUND = mhb::B_THREADS, PER_CU = 1;
-    static constexpr bool LDS = true;
-    const uint16_t *lut;
-    const uint32_t *sub_base;
-    DecTables tabs;
-    template <typename P> __device__ __forceinline__ void init(const P &p, unsigned char *smem) { tabs = mhb::load_tables(p.tab, smem, lut, sub_base); }
-    template <typename P>
-    __device__ __forceinline__ uint32_t next(const P &, const BitSrc &src, BitCursor &bc, uint32_t &ctx, uint32_t &used, bool &bad) const {
-        return ctx = mhk::decode_one(lut, sub_base, tabs, src, bc, ctx, used, bad);
-    }
-};
-
-// the set's model of stream i: its context -> slot row and its order, tables in L2.  (Compiled under the shared model's bound
-// and launched with 256 lanes.)
-struct SetTables : Entry01 {
-    static constexpr int BOUND = 1024, PER_CU = 8;
-    static constexpr bool LDS = false;
-    const uint32_t *row;
-    bool o1;
-    __device__ __forceinline__ void init(const LookupParams &, unsigned char *) {}
-    __device__ __forceinline__ void stream(const LookupParams &p, uint64_t i) { row = p.set.ctx_slot + i * 256u; o1 = p.set.type[i] != 0; }
-    __device__ __forceinline__ uint32_t next(const LookupParams &p, const BitSrc &src, BitCursor &bc, uint32_t &ctx, uint32_t &used, bool &bad) const {
-        return ctx = mhe::decode_sym(p.set, row, o1 ? ctx : 0u, src, bc, used, bad);
-    }
-};
-
-// the shared order-2 model: general form, every level gathered from L2; ctx holds the last two symbols (a pair without a
-// code is a null entry: bad)
-struct Shared2Tables {
-    static constexpr int BOUND = 256, PER_CU = 8;
-    static constexpr bool LDS = false;
-    static constexpr uint64_t POS = mhk::IDX2_POS;
-    static __device__ __forceinline__ uint32_t entry_ctx(uint64_t e) { return uint32_t(e >> 48); }
-    DecTables tabs;
-    template <typename P> __device__ __forceinline__ void init(const P &p, unsigned char *) { tabs = DecTables{p.tab.sec, p.tab.tree, p.tab.P, 0u, 0u}; }
-    __device__ __forceinline__ void stream(const LookupParams &, uint64_t) {}
-    template <typename P>
-    __device__ __forceinline__ uint32_t next(const P &p, const BitSrc &src, BitCursor &bc, uint32_t &ctx, uint32_t &used, bool &bad) const {
-        const uint32_t sym = mhk::decode_one(p.tab.prim, p.tab.sec_base, tabs, src, bc, ctx, used, bad);
-        ctx = ((ctx << 8) | sym) & 0xFFFFu;
-        return sym;
-    }
-};
 
 // item j's share of a unit: `skip` symbols decoded and dropped, then `store` symbols to the item's output from byte `ahead`
 template <typename Tables, typename P>
@@ -165,16 +90,6 @@ __global__ void count_kernel(Params p, unsigned long long *bases, int *status) {
     p.status[j] = st;
     bases[j] = cnt;
     if (st != MH_OK) mhb::fail(status, st == MH_ERR_ARG ? BATCH_STATUS_ARG : mhk::MHK_STATUS_CAPACITY);
-}
-
-// the item of w: the largest j with bases[j] <= w (items without units share their successor's base)
-__device__ __forceinline__ uint64_t item_of(const unsigned long long *bases, uint64_t n, uint64_t w) {
-    uint64_t lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi + 1) >> 1;
-        if (bases[mid] <= w) lo = mid; else hi = mid - 1;
-    }
-    return lo;
 }
 
 // ------------------------------------------------------------------------------------------------ one stream
@@ -378,19 +293,6 @@ hipError_t count_and_scan(const Params &p, void *d_ws, hipStream_t st, unsigned 
     if (e != hipSuccess || p.n == 0) return e;
     hipLaunchKernelGGL(count_kernel<Params>, dim3(uint32_t((p.n + 1 + 255) / 256)), dim3(256), 0, st, p, bases, status);
     return mhb::scan_exclusive(bases, p.n + 1, sums, stop, st);
-}
-
-// the dynamic LDS of a policy's kernels: the shared model's tables, which every kernel in fns must be allowed to take
-template <typename Tables, typename P, size_t N>
-hipError_t tables_room(const P &p, const void *const (&fns)[N], size_t &lds) {
-    lds = 0;
-    if (!Tables::LDS) return hipSuccess;
-    for (const void *fn : fns) {
-        const hipError_t attr = mhk::allow_lds(fn, LDS_MAX);
-        if (attr != hipSuccess) return attr;
-    }
-    lds = mhb::tables_lds(p.tab);
-    return lds > size_t(LDS_MAX) ? hipErrorInvalidValue : hipSuccess;
 }
 
 template <typename Format>

@@ -583,6 +583,24 @@ static void redact_spans(const mh_model* model, const redact_options& r, const u
     mh_dict_free(dc);
 }
 
+bool parse_token_format(const std::string& s, token_format& f) {
+    f = token_format();
+    f.prefix = s;
+    for (size_t at = s.find('%'); at != std::string::npos; at = s.find('%', at + 1)) {
+        size_t q = at + 1;
+        unsigned digits = 0;
+        while (q < s.size() && s[q] >= '0' && s[q] <= '9' && q - at <= 2) digits = digits * 10 + unsigned(s[q++] - '0');
+        if (q >= s.size() || s[q] != 'H') continue;
+        if (q == at + 1) digits = 16;
+        if (digits < 1 || digits > 16) continue;
+        f.prefix = s.substr(0, at);
+        f.suffix = s.substr(q + 1);
+        f.hex_digits = (uint8_t)digits;
+        break;
+    }
+    return f.prefix.size() + f.suffix.size() + f.hex_digits <= MH_SPLICE_MAX_REP;
+}
+
 void i_coding_provider::recode(FILE* input_fd, FILE* output_fd, const i_coding_provider& dst, const std::string& out_index_path,
                                const redact_options* redact) {
     InputView in(input_fd, true);
@@ -611,14 +629,47 @@ void i_coding_provider::recode(FILE* input_fd, FILE* output_fd, const i_coding_p
     // nbits / shortest source code of them) and cut to the true size afterwards: one upload, one device call
     const int minl = mh_model_min_code_len(model_);
     uint64_t symbols = indexed ? n_symbols : nbits / (uint64_t)(minl > 0 ? minl : 1);
-    const bool table = redact && redact->table;
+    const bool token = redact && redact->token;
+    const bool table = redact && (redact->table || token);         // tokens: a table with an entry per span
     std::vector<uint32_t> tags;
     if (redact)
         redact_spans(model_, *redact, in.data + 1, pay_off[1], nbits, indexed ? sym_off : nullptr, indexed ? index.data() : nullptr, chunk, span_off,
-                     spans, table ? &tags : nullptr);
+                     spans, redact->table ? &tags : nullptr);
     const bool splice = redact && redact->replace;
     uint64_t inserted = 0;
-    if (table) {
+    // --token-key: the spans' tokens (mh_span_tokens_batch) as a table with one entry per span, tagged 0, 1, 2, ...
+    std::vector<uint64_t> tok_off(1, 0);
+    std::vector<uint8_t> tok_bytes;
+    if (token) {
+        std::vector<uint64_t> fmt_off(1, 0);
+        std::string fmt_bytes;
+        std::vector<uint8_t> hex;
+        const std::vector<std::string> one(1, redact->rep);
+        for (const std::string& s : redact->table ? redact->reps : one) {
+            token_format f;
+            parse_token_format(s, f);                              // (main checked the length)
+            fmt_bytes += f.prefix;
+            fmt_off.push_back(fmt_bytes.size());
+            fmt_bytes += f.suffix;
+            fmt_off.push_back(fmt_bytes.size());
+            hex.push_back(f.hex_digits);
+        }
+        const size_t ns = (size_t)span_off[1];
+        tok_off.assign(ns + 1, 0);
+        tok_bytes.resize(ns * MH_SPLICE_MAX_REP + 1);
+        std::vector<uint32_t> tok_tag(ns + 1, 0);
+        spans.resize(spans.size() + 2);                            // (never read: pointers for an empty list)
+        tags.resize(ns + 1);
+        mh_or_die(mh_span_tokens_batch(model_, in.data + 1, pay_off, &nbits, 1, MH_PREV0, indexed ? sym_off : nullptr, indexed ? index.data() : nullptr,
+                                       chunk, span_off, spans.data(), redact->table ? tags.data() : nullptr, redact->key,
+                                       redact->fold ? MH_TOKEN_FOLD : 0u, fmt_off.data(), (const uint8_t*)fmt_bytes.data(), hex.data(), hex.size(),
+                                       tok_off.data(), tok_bytes.data(), tok_bytes.size(), tok_tag.data(), nullptr), "recode (--token-key)");
+        spans.resize(ns * 2);
+        tags.assign(tok_tag.begin(), tok_tag.begin() + ns);
+        inserted = tok_off[ns];
+        symbols += inserted;
+        if (indexed) out_index.assign((size_t)mh_batch_index_capacity(symbols, 1, chunk), 0);
+    } else if (table) {
         for (uint32_t t : tags) inserted += redact->reps[t].size();
         symbols += inserted;
         if (indexed) out_index.assign((size_t)mh_batch_index_capacity(symbols, 1, chunk), 0);
@@ -636,6 +687,10 @@ void i_coding_provider::recode(FILE* input_fd, FILE* output_fd, const i_coding_p
                 (unsigned long long)inserted);
         std::vector<uint64_t> rep_off(1, 0);
         std::string rep_bytes;
+        if (token) {
+            rep_off = tok_off;
+            rep_bytes.assign((const char*)tok_bytes.data(), (size_t)inserted);
+        } else
         for (const std::string& s : redact->reps) {
             rep_bytes += s;
             rep_off.push_back(rep_bytes.size());
@@ -643,7 +698,7 @@ void i_coding_provider::recode(FILE* input_fd, FILE* output_fd, const i_coding_p
         tags.push_back(0);                                        // (never read: a pointer for an empty list)
         mh_or_die(mh_recode_splice_table_batch(model_, dst.model(), in.data + 1, pay_off, &nbits, 1, MH_PREV0, sym_off,
                                                indexed ? index.data() : nullptr, chunk, span_off, spans.data(), tags.data(), rep_off.data(),
-                                               (const uint8_t*)rep_bytes.data(), redact->reps.size(), out.data + 1, bound, out_off, &out_nbits,
+                                               (const uint8_t*)rep_bytes.data(), rep_off.size() - 1, out.data + 1, bound, out_off, &out_nbits,
                                                out_sym_off, indexed ? out_index.data() : nullptr, out_index.size(), &dropped, nullptr),
                   "recode (--replace-file)");
         n_symbols = out_sym_off[1];                               // the index sidecar below is the new length's

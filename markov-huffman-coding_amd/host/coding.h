@@ -53,7 +53,17 @@ struct redact_options {
     std::string rep;
     bool table = false;                          // --replace-file: a span becomes reps[its tag], the lowest pattern number merged into it
     std::vector<std::string> reps;               // one per pattern ("" deletes)
+    bool token = false;                          // --token-key: rep / reps are formats, %H or %NH standing for the token's hex digits
+    uint8_t key[16] = {0};
 };
+
+// A replacement string under --token-key: the text in front of the first %H or %NH (N 1..16), the digits, the text behind.
+// No such mark: the whole string is the prefix and hex_digits is 0.  False when the token would exceed MH_SPLICE_MAX_REP bytes.
+struct token_format {
+    std::string prefix, suffix;
+    uint8_t hex_digits = 0;
+};
+bool parse_token_format(const std::string& s, token_format& f);
 
 class i_coding_provider {
 public:

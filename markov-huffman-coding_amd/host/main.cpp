@@ -23,11 +23,16 @@
 //                    table may be the old one.  --redact-file FILE: one pattern per line, the limits of --find-file.
 //   --replace STRING with --redact or --redact-file: the occurrences are replaced by STRING (at most 255 bytes; "" deletes
 //                    them) instead of being masked, so the output has another length; <output>.idx is written for it
+//   --token-key HEX32 with --replace or --replace-file: the 16-byte key (32 hex digits) of keyed tokens.  The first %H of a
+//                    replacement string then stands for 16 hex digits of the SipHash-2-4 of the bytes the span matched (under
+//                    --redact-fold: of their lower-case form), %NH with N 1..16 for the first N of them; equal matches get equal
+//                    tokens (include/mh.h, "TOKENS FROM MATCHED BYTES").  Without the key every string stays literal.
 //   --replace-file FILE with --redact-file, not with --replace or --mask: line j of FILE replaces pattern j (split at LF, empty
 //                    lines kept: an empty line deletes; a final LF adds no line; as many lines as patterns, at most 255 bytes
 //                    each).  Overlapping or touching hits become one span, replaced by the line of its lowest pattern number
 //   --crc            with -x: print `crc32 length` of the original input (CRC-32 as zlib computes it, %08x, and the byte
 //                    count), taken on the device without decompressing; with --index the indexed path
+#include <ctype.h>
 #include <errno.h>
 #include <stdlib.h>
 #include <string.h>
@@ -68,6 +73,8 @@ static void print_help() {
     eprintf("\t--redact-file f  the same with one pattern per line of `f`, as --find-file; not together with --redact\n");
     eprintf("\t--mask byte    the byte that takes the place of redacted bytes: decimal or 0x.., 0 to 255 (default 0x2A)\n");
     eprintf("\t--replace string  with --redact or --redact-file: every occurrence becomes the string (at most 255 bytes, \"\" deletes)\n");
+    eprintf("\t--token-key hex32  with --replace or --replace-file: the first %%H (or %%NH, N 1..16) of a replacement stands for 16 (N) hex\n");
+    eprintf("\t               digits of the keyed digest of the matched bytes; the key is 32 hex digits\n");
     eprintf("\t--replace-file f  with --redact-file: line j of `f` replaces pattern j (an empty line deletes; where patterns overlap the\n");
     eprintf("\t               earlier line of the pattern file wins); not together with --replace or --mask\n");
     eprintf("\t               instead of mask bytes; not together with --mask\n");
@@ -98,6 +105,8 @@ struct options {
     std::string replace;                                          // --replace: what a redacted span becomes ("" deletes it)
     const char* replace_file = nullptr;                           // --replace-file: line j replaces pattern j of --redact-file
     std::vector<std::string> replacements;                        // its lines, empty ones kept
+    const char* token_key = nullptr;                              // --token-key: %H in a replacement stands for a keyed token
+    uint8_t key[16] = {0};
 };
 
 // "B:E" with decimal B <= E; anything else is an error
@@ -179,6 +188,7 @@ static options parse(int argc, char* argv[]) {
                 o.replace_given = true;
             }
             else if (!strcmp(a, "--replace-file")) o.replace_file = need(a);
+            else if (!strcmp(a, "--token-key")) o.token_key = need(a);
             else eprintf("Warning: Unknown option %s.\n", a);
             continue;
         }
@@ -367,6 +377,27 @@ int main(int argc, char* argv[]) {
             exit(1);
         }
     }
+    if (o.token_key) {
+        if (!o.replace_given && !o.replace_file) {
+            eprintf("Error: --token-key needs --replace or --replace-file.\n");
+            exit(1);
+        }
+        bool ok = strlen(o.token_key) == 32;
+        for (int k = 0; ok && k < 32; ++k) ok = isxdigit((unsigned char)o.token_key[k]) != 0;
+        if (!ok) {
+            eprintf("Error: --token-key takes 32 hex digits.\n");
+            exit(1);
+        }
+        for (int k = 0; k < 16; ++k) {
+            const char two[3] = {o.token_key[2 * k], o.token_key[2 * k + 1], 0};
+            o.key[k] = (uint8_t)strtoul(two, nullptr, 16);
+        }
+        token_format f;
+        if (o.replace_given && !parse_token_format(o.replace, f)) {
+            eprintf("Error: --replace takes at most %u bytes, the token's digits included.\n", MH_SPLICE_MAX_REP);
+            exit(1);
+        }
+    }
     if (redact) {                                                  // the rules first, then the pattern file, then everything else
         if (!o.recode_table) {
             eprintf("Error: --redact needs --recode.\n");
@@ -392,6 +423,12 @@ int main(int argc, char* argv[]) {
             for (const std::string& r : o.replacements)
                 if (r.size() > MH_SPLICE_MAX_REP) {
                     eprintf("Error: a line of the --replace-file takes at most %u bytes.\n", MH_SPLICE_MAX_REP);
+                    exit(1);
+                }
+            token_format f;
+            for (const std::string& r : o.replacements)
+                if (o.token_key && !parse_token_format(r, f)) {
+                    eprintf("Error: a line of the --replace-file takes at most %u bytes, the token's digits included.\n", MH_SPLICE_MAX_REP);
                     exit(1);
                 }
         }
@@ -542,6 +579,8 @@ int main(int argc, char* argv[]) {
         ro.rep = o.replace;
         ro.table = o.replace_file != nullptr;
         ro.reps = o.replacements;
+        ro.token = o.token_key != nullptr;
+        memcpy(ro.key, o.key, 16);
         coder->recode(input_fd, output_fd, *dst, std::string(o.output) + ".idx", redact ? &ro : nullptr);
         delete dst;
         delete coder;
